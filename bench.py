@@ -18,11 +18,14 @@ WORLD_SIZE come from the launcher) or the bare `python bench.py --gpus N ...`: w
 starts its N ranks itself (launch_ranks: before anything loads the library or touches HIP), relays rank 0's JSON line and the worst
 exit code; fewer than N visible GPUs, or a rank count that differs from --gpus, is an error, never a silently different n_gpus.
 
-Adds to the JSON line:
+A plain run sets up, warms up, times the --steps steps and prints the result line.  --dump-outputs DIR also writes what the
+last timed step handed its caller (x, y; see dump_outputs).  --full adds to the JSON line:
   roofline     -- HBM roofline of the dominant kernel: algorithmic bytes (12 nnz + 4(rows+1) + 8 rows + 8 cols) over the
                   HIP-event duration sampled live in the timed solves on the solver's stream.
+  kkt_prim, kkt_dual -- the last step's KKT residuals recomputed on the host.
   cpu_baseline -- the CPU oracle (a port: the reference needs CHOLMOD, absent here) MEASURED on this host, all cores of
                   the process's CPU share, on a bounded sample of the same workload (no constants from profiles/).
+  extra_fp32_inner_preconditioner, other_configs, setup_s_second_workspace, host_threads -- further measurements in the same process.
 """
 import argparse
 import json
@@ -74,18 +77,44 @@ def parse():
     ap.add_argument("--batch-count", type=int, default=C3_COUNT, help="C3: number of QPs in the whole batch")
     ap.add_argument("--stream-depth", type=int, default=int(os.environ.get("QPDO_BENCH_STREAM_DEPTH", "12")),
                     help="C3: batches in flight on the batch stream (1 = one launch at a time, each step waited for before the next)")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="bound of the cpu_baseline sample of the main workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the informational C2 / C3-batch measurements")
-    ap.add_argument("--no-mixed-extra", action="store_true", help="skip the informational fp32-inner-preconditioner solve")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="--full: bound of the cpu_baseline sample of the main workload")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the informational C2 / C3-batch measurements")
+    ap.add_argument("--no-mixed-extra", action="store_true", help="--full without the informational fp32-inner-preconditioner solve")
     ap.add_argument("--launch-check", action="store_true",
                     help="rank plumbing only: rendezvous, barrier and the two reductions of the timed region, no GPU work (CPU tests of --gpus N)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline, host KKT check, CPU baselines, the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64, at most 64 MB in all; rank 0's share)")
     ap.add_argument("--rows-extra-child", action="store_true", help=argparse.SUPPRESS)    # internal: see row_partition_extra
     a = ap.parse_args()
     a.gpus_explicit = a.gpus is not None
     if a.gpus is None:                                      # left at its default: adopt the launcher's world size
         a.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     return a
+
+
+DUMP_LIMIT = 64 << 20      # --dump-outputs: bytes in all
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array the timed path handed its caller in the last step.  Should they
+    exceed DUMP_LIMIT in all, every array is cut to a fixed, seeded sample of its rows (axis 0), written with the row numbers
+    beside it as <name>_rows.npy, so that two builds given the same arguments write the same sample."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        frac = DUMP_LIMIT / (2.0 * total)              # the row numbers take at most as much room as the rows
+        rng = np.random.default_rng(0)
+        for k in sorted(arrays):
+            v = arrays[k]
+            rows = np.sort(rng.choice(len(v), size=max(1, int(len(v) * frac)), replace=False))
+            arrays[k], arrays[k + "_rows"] = v[rows], rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
 
 
 def dist_setup(n_gpus):
@@ -294,6 +323,9 @@ def run_batch(a, rank, world, dist):
     tot_newton, tot_solved, tot_failed, tot_items = allreduce(dist, [newton, solved, failed, len(B.indices) * a.steps], "sum")
     if rank != 0:
         return None
+    if a.dump_outputs and a.steps > 0:
+        last = images[(a.steps - 1) % depth]            # the image the last step wrote into: x, y of every item of this rank's shard
+        dump_outputs(a.dump_outputs, dict(x=np.stack([x for x, _ in last.outs]), y=np.stack([y for _, y in last.outs])))
     cfg = problems.CONFIGS["C3"]
     out = {
         "metric": "primal-dual Newton iters/sec (+ time-to-eps) on random sparse QP", "value": tot_newton / dt_max, "unit": "newton_iters/s",
@@ -309,8 +341,10 @@ def run_batch(a, rank, world, dist):
         "qps_per_s": tot_items / dt_max, "solved": tot_solved, "failed": tot_failed, "items": tot_items, "generate_s": t_gen,
         "kernel_s_per_step_rank0": kernel_s / max(1, a.steps),
         "host_submit_s_per_step_rank0": t_submit / max(1, a.steps), "host_wait_s_per_step_rank0": t_wait / max(1, a.steps),
-        "roofline": small_kernel_roofline(newton / max(1, a.steps), kernel_s / max(1, a.steps), 1),       # rank 0's launch
     }
+    if not a.full:
+        return out
+    out["roofline"] = small_kernel_roofline(newton / max(1, a.steps), kernel_s / max(1, a.steps), 1)       # rank 0's launch
     if world == 1 and not a.no_cpu_baseline:
         sl = [problems.config_qp("C3", i) for i in range(min(count, 256))]
         out["cpu_baseline"] = cpu_baseline_batch(sl, min(a.cpu_seconds, 10.0), {k: v for k, v in st.items() if k != "verbose"})
@@ -631,9 +665,19 @@ def main():
     if rows_mode:      # one QP: every rank counted the same passes
         tot_newton, tot_cg = tot_newton / world, tot_cg / world
 
-    last = r
-    rp, rd = problems.kkt_residuals(prob_last, last["x"], last["y"]) if last["info"]["status_val"] not in (-3, -4) else (None, None)
-    # roofline of the dominant kernel, live HIP-event samples from the timed solves.  With the Schur-complement mode
+    if rank == 0 and a.dump_outputs and a.steps > 0:
+        # what qpdo_solve handed its caller in the last step: x and y, or the certificate of the infeasibility it reports
+        outs = dict(x=r["x"], y=r["y"])
+        cert = {-3: "prim_inf_cert", -4: "dual_inf_cert"}.get(r["info"]["status_val"])
+        if cert:
+            outs[cert] = r[cert]
+        dump_outputs(a.dump_outputs, outs)
+
+    roof = rp = rd = None
+    if a.full:
+        last = r
+        rp, rd = problems.kkt_residuals(prob_last, last["x"], last["y"]) if last["info"]["status_val"] not in (-3, -4) else (None, None)
+    # (--full) roofline of the dominant kernel, live HIP-event samples from the timed solves.  With the Schur-complement mode
     # of the PCG the bulk of the time is the inner solves' A_c product (k_spmv_slab<EpiSchurW>: the k active rows of A,
     # compact index space, k changes per pass, so bytes and time are summed over the samples); otherwise it is the Q
     # product of the PCG operator (k_spmv_slab<EpiPcgQ>).  A back-to-back micro-benchmark of the full-size kernel beside it.
@@ -643,7 +687,9 @@ def main():
                 return json.load(fh)
         except Exception:
             return None
-    if rows_mode:
+    if not a.full:
+        pass                                                # a plain run: the headline figure alone
+    elif rows_mode:
         # row-partitioned solve: the HIP-event samples of the inner products are not taken across collectives; the figure is the
         # back-to-back micro-benchmark of this rank's slice of A (the same slab kernel the inner products use)
         bench_t, full_bytes = s.bench_spmv(0, reps=20)
@@ -654,9 +700,14 @@ def main():
         # dense LDL' (C2): the dominant kernel is the fp64-MFMA trailing update; MFMA utilisation comes from the committed
         # PMC profile, the live figure here is the factor's flop rate from the solve's own statistics
         fc = s.stats()["factor_count"]
-        t_f, chk = s.bench_dense_factor(reps=5)           # HIP events on the solver's stream, the factor of the final pass's weights
-        tf = cfg["n"] ** 3 / 3.0 / t_f / 1e12
-        roof = dense_roofline(cfg["n"], t_f, chk, fc, s.stats().get("onelaunch_factors", 0), load_profile)
+        try:
+            t_f, chk = s.bench_dense_factor(reps=5)       # HIP events on the solver's stream, the factor of the final pass's weights
+            roof = dense_roofline(cfg["n"], t_f, chk, fc, s.stats().get("onelaunch_factors", 0), load_profile)
+        except RuntimeError as e:
+            # The factorization's kernels poll hand-off flags with a bounded spin.  On a device shared with other processes (ranks
+            # on one GPU) a consumer can run out of spins: qpdo_solve redoes such a step with the separate kernels, this
+            # micro-benchmark returns an error.  The roofline is an extra of the line, never a reason to lose the rank.
+            roof = dict(bound="mfma", kernel="dense LDL' factorization", error=repr(e))
     elif ac_n > at_n and ac_time > 0:
         bench_t, full_bytes = s.bench_spmv(0, reps=20)
         achieved = ac_bytes / ac_time / 1e9
@@ -703,7 +754,7 @@ def main():
         if pmc is not None and a.workload == "C4":
             roof["traffic"] = pmc["Q  (CSR n x n)"]["traffic_bytes"]
             roof["traffic_source"] = "profiles/r01_pmc_spmv_c4.json (2*FETCH_SIZE + WRITE_SIZE, separate --pmc passes)"
-    if roof["bound"] == "hbm":
+    if roof is not None and roof["bound"] == "hbm":
         for which, key in ((0, "spmv_A_GBs"), (1, "spmv_At_GBs")):
             t_, b_ = s.bench_spmv(which, reps=20)
             roof[key] = b_ / t_ / 1e9
@@ -736,12 +787,15 @@ def main():
             "setup_s": t_setup, "generate_s": t_gen,
             "roofline": roof,
         }
+        if not a.full:
+            for k in ("kkt_prim", "kkt_dual", "roofline"):
+                del out[k]
     s.delete()
-    if world > 1 and not rows_mode and not a.no_other_configs:
+    if a.full and world > 1 and not rows_mode and not a.no_other_configs:
         rp_extra = row_partition_extra(a, rank, world, dist)            # every rank takes part; rank 0 reports
         if rank == 0:
             out.setdefault("other_configs", {})["row_partition"] = rp_extra
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline_single(prob, a.cpu_seconds, "direct" if cfg["n"] <= 20000 else "pcg")
         except Exception as e:  # the baseline is a reported extra, never a reason to lose the GPU line
@@ -768,7 +822,7 @@ def main():
                          "which is why the whole solve is ~75x slower per pass than the sampled early passes" % (meta.get("threads"), npass, sec))
             except Exception as e:
                 out["cpu_baseline"]["full_solve"] = dict(error=repr(e))
-    if rank == 0 and world == 1 and schur_passes and not a.no_mixed_extra:
+    if a.full and rank == 0 and world == 1 and schur_passes and not a.no_mixed_extra:
         # Informational extra, NOT part of `value`: the same solve with the opt-in fp32 copy of the inner preconditioner's
         # matrix values (QPDO_PCG_INNER_F32=1; every vector, accumulation and the outer CG on the exact K stay fp64).
         try:
@@ -786,7 +840,7 @@ def main():
             out["extra_fp32_inner_preconditioner"] = dict(error=repr(e))
         finally:
             os.environ.pop("QPDO_PCG_INNER_F32", None)
-    if rank == 0 and world == 1 and a.workload == "C4" and not a.no_other_configs:
+    if a.full and rank == 0 and world == 1 and a.workload == "C4" and not a.no_other_configs:
         # Informational extras, NOT part of `value`: the other single-GPU configurations of BASELINE.json, measured in the
         # same process (configs[1]: one QP n=1e4, m=2e4; configs[2]: 4096 MPC-sized QPs through the fused batch kernel), each
         # with its own measured CPU baseline

@@ -160,7 +160,7 @@ def test_bench_under_torch_distributed_run_with_two_ranks_on_one_gpu(gpu_require
         with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:
             so.bind(("127.0.0.1", 0)); port = so.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-               os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "C2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+               os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "C2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                              env=dict(env, QPDO_BENCH_ROWS_BACKEND="host", QPDO_BENCH_ROWS_PASSES="8", QPDO_BENCH_SHARE_GPU="1", QPDO_DEVICE="0"))
         if out.returncode == 0 or attempt == 1 or not any(t in out.stderr for t in rendezvous_trouble):
@@ -182,7 +182,7 @@ def test_bench_under_torch_distributed_run_with_two_ranks_on_one_gpu(gpu_require
     assert rp["iterations"] == 8 and rp["collectives"] > 0
 
 
-@pytest.mark.parametrize("workload,extra", [("C2", ["--steps", "3", "--warmup", "1", "--no-cpu-baseline"]),
+@pytest.mark.parametrize("workload,extra", [("C2", ["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]),
                                             ("C3", ["--steps", "2", "--warmup", "1", "--max-iter", "300", "--batch-count", "512", "--no-cpu-baseline"])])
 def test_bench_contract_with_two_ranks_on_one_gpu(workload, extra, gpu_required):
     """bench.py for N > 1, as the BARE command `python bench.py --gpus 2 ...` with no launcher environment: the script starts its own two
