@@ -134,6 +134,19 @@ int  qpdo_amd_get_stats(const QPDOWorkspace *work, QPDOAmdStats *out);
 int  qpdo_amd_get_trace(const QPDOWorkspace *work, const QPDOAmdTraceRec **recs, long *count);
 int  qpdo_amd_sync(QPDOWorkspace *work);
 
+/* New values of Q and / or A in the sparsity pattern given to qpdo_setup.  Q, A: the same dimensions, stype (Q), itype-independent
+ * pattern (p, i) and number of entries as at setup; only x differs.  NULL: that matrix is unchanged.  Returns 0, or nonzero with
+ * qpdo_amd_last_error() set -- and then the workspace is exactly as before the call (checks precede every write).
+ * After a successful call the workspace is bit for bit the one qpdo_setup returns for the new matrices, the latest UNSCALED q, l, u
+ * (from setup, qpdo_update_q, qpdo_update_bounds), the constant c and the workspace's current settings: scaling computed again from
+ * scratch, x = y = 0, status QPDO_UNSOLVED; info->setup_time = the call's duration.  A warm start is the caller's (qpdo_warm_start).
+ * The pattern: the first call that passes a matrix compares its (p, i) with the setup's on the device; later calls compare the
+ * dimensions, stype, entry counts and column pointers only -- changing row indices without changing their count is UNDEFINED.
+ * Costs: the first call allocates 4 B per entry of A and of the full storage of Q (the maps; + 8 B per stored entry of Q when stype is
+ * +-1); a scaled workspace keeps the unscaled values on the device from setup on (8 B per entry of A and of the full Q).
+ * Not for row-partitioned workspaces (qpdo_amd_dist_config): refused. */
+int  qpdo_amd_update_matrices(QPDOWorkspace *work, const cholmod_sparse *Q, const cholmod_sparse *A);
+
 /* HIP-event timing of the SpMV kernel on the workspace's own (scaled) matrices.
  * which: 0 = A (CSR m x n), 1 = A' (CSR n x m), 2 = Q (full symmetric CSR). */
 int  qpdo_amd_bench_spmv(QPDOWorkspace *work, int which, int reps, double *avg_seconds, double *alg_bytes);

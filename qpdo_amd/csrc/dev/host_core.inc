@@ -275,7 +275,8 @@ static int dev_exclusive_scan(QpdoDev *d, TempAllocs &tmp, int *a, long long tot
     return 0;
 }
 // dst = transpose of src as CSR, rows sorted by (source) major index: stable LSD radix sort of the entry positions by minor index
-static int dev_transpose(QpdoDev *d, TempAllocs &tmp, const DevCsr &src, DevCsr *dst, bool temp_dst) {
+// perm_out != nullptr (N entries): also the final payload of the sort, perm_out[k] = the source position of entry k of dst
+static int dev_transpose(QpdoDev *d, TempAllocs &tmp, const DevCsr &src, DevCsr *dst, bool temp_dst, u32 *perm_out = nullptr) {
     const long long N = src.nnz; const int T = src.ncols;
     dst->nrows = src.ncols; dst->ncols = src.nrows; dst->nnz = N;
     int rc;
@@ -311,14 +312,16 @@ static int dev_transpose(QpdoDev *d, TempAllocs &tmp, const DevCsr &src, DevCsr 
         kin = kout; vin = pb[cur]; cur ^= 1;
     }
     hipLaunchKernelGGL(k_tr_gather, dim3(2048), dim3(BLK), 0, d->stream, N, vin, (const u32 *)major, (const double *)src.val, dst->ci, dst->val);
+    if (perm_out) HIPCHK(hipMemcpyAsync(perm_out, vin, (size_t)N * sizeof(u32), hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipGetLastError());
     return 0;
 }
 // uploads the caller's CSC arrays of an r x c matrix as the CSR arrays of its c x r transpose (index narrowing on the device)
-static int upload_csc_as_csr_of_transpose(QpdoDev *d, TempAllocs &tmp, DevCsr *M, const QdevCsc *h, bool temp_arrays) {
+// (with_values = false: the pattern only -- M->val stays unallocated; the pattern check of qpdo_amd_update_matrices)
+static int upload_csc_as_csr_of_transpose(QpdoDev *d, TempAllocs &tmp, DevCsr *M, const QdevCsc *h, bool temp_arrays, bool with_values = true) {
     M->nrows = h->ncols; M->ncols = h->nrows; M->nnz = h->nnz;
     int rc = 0;
-    if (temp_arrays) { if (tmp.get(&M->rp, (size_t)M->nrows + 1) || tmp.get(&M->ci, (size_t)M->nnz) || tmp.get(&M->val, (size_t)M->nnz)) return set_err(hipErrorOutOfMemory, "setup scratch", __LINE__); }
+    if (temp_arrays) { if (tmp.get(&M->rp, (size_t)M->nrows + 1) || tmp.get(&M->ci, (size_t)M->nnz) || (with_values && tmp.get(&M->val, (size_t)M->nnz))) return set_err(hipErrorOutOfMemory, "setup scratch", __LINE__); }
     else { if ((rc = dev_alloc(d, &M->rp, (size_t)M->nrows + 1)) || (rc = dev_alloc(d, &M->ci, (size_t)M->nnz)) || (rc = dev_alloc(d, &M->val, (size_t)M->nnz))) return rc; }
     if (h->itype == 0) {
         HIPCHK(hipMemcpyAsync(M->rp, h->p, ((size_t)M->nrows + 1) * sizeof(int), hipMemcpyHostToDevice, d->stream));
@@ -334,7 +337,7 @@ static int upload_csc_as_csr_of_transpose(QpdoDev *d, TempAllocs &tmp, DevCsr *M
             hipLaunchKernelGGL(k_narrow_i64, dim3(2048), dim3(BLK), 0, d->stream, (long long)M->nnz, (const long long *)w, M->ci);
         }
     }
-    if (M->nnz && (rc = h2d_staged(d, M->val, h->x, (size_t)M->nnz * sizeof(double)))) return rc;
+    if (with_values && M->nnz && (rc = h2d_staged(d, M->val, h->x, (size_t)M->nnz * sizeof(double)))) return rc;
     M->tpr = pick_tpr(*M);
     return 0;
 }

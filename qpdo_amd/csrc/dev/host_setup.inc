@@ -55,7 +55,7 @@ int qdev_create_csc(QpdoDev **out, int device, int32_t n, int32_t m, const QdevC
             if (!rc) rc = dev_alloc(d, &d->Qf.ci, (size_t)d->Qf.nnz);
             if (!rc) rc = dev_alloc(d, &d->Qf.val, (size_t)d->Qf.nnz);
             if (!rc) {
-                hipLaunchKernelGGL(k_sym_fill, dim3(2048), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const double *)R.val,
+                hipLaunchKernelGGL(k_sym_fill<double>, dim3(2048), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const double *)R.val,
                                    (const int *)S.rp, (const int *)S.ci, (const double *)S.val, (const int *)d->Qf.rp, d->Qf.ci, d->Qf.val);
                 d->Qf.tpr = pick_tpr(d->Qf);
             }
@@ -309,6 +309,8 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
         if (want > 1) d->hybrid_budget = want;
     }
     d->st.linsolve = d->linsolve;
+    d->cfg.linsolve = d->linsolve; d->cfg.dense_chain = d->dense_chain; d->cfg.dense_fpanel = d->dense_fpanel; d->cfg.dense_mid = d->dense_mid;
+    d->cfg.wb_enable = d->wb_enable; d->cfg.deflate = d->deflate; d->cfg.pcg_maxit = d->pcg_maxit; d->cfg.band_b = d->band_b;
     return 0;
 }
 // absolute stopping rule of the linear solves follows the caller's eps_abs (QPDO_PCG_ABS: the factor, default 1e-5; 0 disables)

@@ -146,5 +146,13 @@ struct QpdoDev {
     // pinned staging for large host -> device uploads (h2d_staged): owned by the workspace, released when setup ends
     char *pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; bool pin_failed = false;
     std::vector<void *> allocs;
+    // qpdo_amd_update_matrices (dev/host_update.inc).  raw*: the caller's unscaled values (a scaled workspace: kept by qdev_keep_raw_values at
+    // setup, so that a matrix passed as NULL is scaled again from its own values); map*: built by the first call that needs them
+    double *rawA = nullptr, *rawQ = nullptr;      // CSC order of A (= At), the full storage of Q (= Qf)
+    u32 *mapA = nullptr, *mapQ = nullptr;         // mapA[k]: CSC position of entry k of CSR(A); mapQ[k]: the caller's position of entry k of Qf
+    double *qstage = nullptr;                     // the caller's stored Q values (stype +-1), gathered through mapQ
+    std::vector<long long> upd_Ap, upd_Qp;        // column pointers whose pattern passed the device check (later calls compare these)
+    // what qdev_configure decided; a solve may change these (fallbacks, hybrid), qpdo_amd_update_matrices puts them back
+    struct { int linsolve, dense_chain, dense_fpanel, dense_mid, wb_enable, deflate, pcg_maxit, band_b; } cfg{};
 };
 

@@ -113,7 +113,7 @@ __global__ void k_tr_gather(long long N, const u32 *__restrict__ perm, const u32
                             int *__restrict__ ci, double *__restrict__ val) {
     for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < N; k += (long long)gridDim.x * blockDim.x) {
         const u32 p = perm[k];
-        ci[k] = (int)major[p]; val[k] = vsrc[p];
+        ci[k] = (int)major[p]; if (vsrc) val[k] = vsrc[p];      // (vsrc == nullptr: a pattern-only transposition)
     }
 }
 __global__ void k_max_row_len(int nrows, const int *__restrict__ rp, int *__restrict__ out) {
@@ -135,9 +135,11 @@ __global__ void k_sym_count(int n, int st, const int *__restrict__ Rrp, const in
         cnt[i] = c;
     }
 }
-__global__ __launch_bounds__(256) void k_sym_fill(int n, int st, const int *__restrict__ Rrp, const int *__restrict__ Rci, const double *__restrict__ Rval,
-                                                  const int *__restrict__ Srp, const int *__restrict__ Sci, const double *__restrict__ Sval,
-                                                  const int *__restrict__ orp, int *__restrict__ oci, double *__restrict__ oval) {
+// (V = double: the values; V = u32: index payloads -- qpdo_amd_update_matrices's map from the full storage back to the caller's entries)
+template <class V>
+__global__ __launch_bounds__(256) void k_sym_fill(int n, int st, const int *__restrict__ Rrp, const int *__restrict__ Rci, const V *__restrict__ Rval,
+                                                  const int *__restrict__ Srp, const int *__restrict__ Sci, const V *__restrict__ Sval,
+                                                  const int *__restrict__ orp, int *__restrict__ oci, V *__restrict__ oval) {
     // one wave per row: the two kept parts are contiguous runs of their (index-sorted or not) source rows, compacted in order by ballot
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * BLK + threadIdx.x) >> 6, nwaves = gridDim.x * (BLK / 64);
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(256) void k_sym_fill(int n, int st, const int *__re
             const int b = fromR ? Rrp[i] : Srp[i], e = fromR ? Rrp[i + 1] : Srp[i + 1];
             for (int k0 = b; k0 < e; k0 += 64) {
                 const int k = k0 + lane;
-                int idx = 0; double v = 0.0; bool keep = false;
+                int idx = 0; V v = V(0); bool keep = false;
                 if (k < e) {
                     idx = fromR ? Rci[k] : Sci[k]; v = fromR ? Rval[k] : Sval[k];
                     keep = fromR ? ((st < 0) ? (idx <= i) : (idx >= i)) : ((st < 0) ? (idx > i) : (idx < i));

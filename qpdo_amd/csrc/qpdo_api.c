@@ -38,6 +38,10 @@ struct QPDOBackend {
                                    * cold start of a fused-path workspace, which is part of the solve's launch) */
     int auto_ws;                  /* qpdo_warm_start is being called by qpdo_solve itself (qpdo.c:312-314) */
     long fused_solves, fused_factor_count; double fused_kernel_s; int last_fused;
+    /* qpdo_amd_update_matrices: the caller's latest UNSCALED q, l, u (the scaled mirrors in work->data cannot give them back bit for
+     * bit) and the shape of the matrices given to qpdo_setup */
+    c_float *q_raw, *l_raw, *u_raw;
+    int q_stype; int64_t q_nnz, a_nnz;
 };
 
 #define c_max(a, b) (((a) > (b)) ? (a) : (b))
@@ -382,6 +386,21 @@ static int install_scaling(QPDOWorkspace *work) {
     return qdev_set_scaling(work->chol->dev, 1, sc->D, sc->Dinv, sc->E, sc->Einv, sc->c, sc->cinv);
 }
 
+/* small problems: the fused one-launch solve (QPDO_SMALL_FUSED=0 keeps the generic path; an explicit QPDO_LINSOLVE asks for one of the
+ * generic path's solvers; a row-partitioned workspace is never small) */
+static void small_resident_setup(QPDOWorkspace *work, const QPDOSettings *settings) {
+    const size_t n = work->data->n, m = work->data->m;
+    const char *ls = getenv("QPDO_LINSOLVE");
+    const int want = env_int("QPDO_SMALL_FUSED", 1) && !(ls && *ls && strcmp(ls, "auto"));
+    if (want && (long)n <= env_int("QPDO_SMALL_FUSED_MAX_N", 160) && qdev_small_resident_fits((int32_t)n, (int32_t)m)) {
+        QdevSmallView v;
+        if (qdev_small_view(work->chol->dev, &v) == 0) {
+            long cap = (long)settings->max_iter < 16384 ? (long)settings->max_iter : 16384;
+            work->chol->small = qdev_small_resident_create(&v, cap);      /* NULL: not fatal, the generic path serves the workspace */
+        }
+    }
+}
+
 /* ---- qpdo_setup (reference src/qpdo.c:49-212) ----------------------------------------- */
 QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
     if (!validate_data(data)) { QPDO_EPRINT("Data validation returned failure"); return QPDO_NULL; }
@@ -421,6 +440,10 @@ QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
     work->n_mu_changed = 0;
     work->chol->reset_newton = 1;
     work->chol->fix_status_reset = env_int("QPDO_FIX_STATUS_RESET", 0);
+    work->chol->q_raw = vec_dup(data->q, n); work->chol->l_raw = vec_dup(data->l, m); work->chol->u_raw = vec_dup(data->u, m);
+    if (!work->chol->q_raw || !work->chol->l_raw || !work->chol->u_raw) goto fail;
+    work->chol->q_stype = data->Q->stype;
+    work->chol->q_nnz = idx_at(data->Q->p, data->Q->itype, (int64_t)data->Q->ncol); work->chol->a_nnz = idx_at(data->A->p, data->A->itype, (int64_t)data->A->ncol);
 
     int on_device = 0;
     {   /* matrices to the device.  One GPU (the default): the caller's CSC arrays are uploaded as they are -- they ARE CSR(A') -- and
@@ -527,6 +550,8 @@ QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
         work->scaling->E = calloc(m ? m : 1, sizeof(c_float));
         work->scaling->Einv = calloc(m ? m : 1, sizeof(c_float));
         if (!work->scaling->D || !work->scaling->Dinv || !work->scaling->E || !work->scaling->Einv) goto fail;
+        /* the unscaled values stay on the device for qpdo_amd_update_matrices (a matrix it is not given is scaled again from them) */
+        if (qdev_keep_raw_values(work->chol->dev)) goto fail_dev;
         /* scale_data (scaling.c:24-91): A, Q, q on the device; l, u through the host mirrors */
         const double ts0 = wall_now();
         if (qdev_scale_data(work->chol->dev, (int)settings->scaling, 0, work->scaling->D, work->scaling->E, &work->scaling->c)) goto fail_dev;
@@ -545,18 +570,7 @@ QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
         if (qdev_set_scaling(work->chol->dev, 0, NULL, NULL, NULL, NULL, 1.0, 1.0)) goto fail_dev;
         work->norm_q = vec_norm_inf(work->data->q, n);
     }
-    {   /* small problems: the fused one-launch solve (QPDO_SMALL_FUSED=0 keeps the generic path; an explicit QPDO_LINSOLVE asks for one
-         * of the generic path's solvers; a row-partitioned workspace is never small) */
-        const char *ls = getenv("QPDO_LINSOLVE");
-        const int want = env_int("QPDO_SMALL_FUSED", 1) && !(ls && *ls && strcmp(ls, "auto"));
-        if (want && (long)n <= env_int("QPDO_SMALL_FUSED_MAX_N", 160) && qdev_small_resident_fits((int32_t)n, (int32_t)m)) {
-            QdevSmallView v;
-            if (qdev_small_view(work->chol->dev, &v) == 0) {
-                long cap = (long)settings->max_iter < 16384 ? (long)settings->max_iter : 16384;
-                work->chol->small = qdev_small_resident_create(&v, cap);      /* NULL: not fatal, the generic path serves the workspace */
-            }
-        }
-    }
+    small_resident_setup(work, settings);
     update_status(work->info, QPDO_UNSOLVED);
     work->info->solve_time = 0.0;
     work->info->run_time = 0.0;
@@ -913,8 +927,8 @@ void qpdo_update_bounds(QPDOWorkspace *work, const c_float *l, const c_float *u)
             }
         }
     }
-    if (l != NULL) memcpy(work->data->l, l, m * sizeof(c_float));
-    if (u != NULL) memcpy(work->data->u, u, m * sizeof(c_float));
+    if (l != NULL) { memcpy(work->data->l, l, m * sizeof(c_float)); memcpy(work->chol->l_raw, l, m * sizeof(c_float)); }
+    if (u != NULL) { memcpy(work->data->u, u, m * sizeof(c_float)); memcpy(work->chol->u_raw, u, m * sizeof(c_float)); }
     if (work->settings->scaling) {
         if (l != NULL) for (size_t i = 0; i < m; i++) work->data->l[i] = work->scaling->E[i] * work->data->l[i];
         if (u != NULL) for (size_t i = 0; i < m; i++) work->data->u[i] = work->scaling->E[i] * work->data->u[i];
@@ -927,6 +941,7 @@ void qpdo_update_q(QPDOWorkspace *work, const c_float *q) {
     size_t n = work->data->n;
     QpdoDev *dev = work->chol->dev;
     memcpy(work->data->q, q, n * sizeof(c_float));
+    memcpy(work->chol->q_raw, q, n * sizeof(c_float));
     if (work->settings->scaling) {
         /* device side (round 3): Qx and x stay in HBM; the host receives the new cost scaling c and norm_q only and keeps its copy
          * of the scaled q (work->data->q) in step by reading it back -- n doubles, instead of 2n down + 5n up before */
@@ -943,6 +958,66 @@ void qpdo_update_q(QPDOWorkspace *work, const c_float *q) {
     }
 }
 
+/* ---- qpdo_amd_update_matrices (include/qpdo_amd_ext.h) ----------------------------------------------------------
+ * New values of Q and / or A in the setup's pattern.  Afterwards the workspace is the one qpdo_setup would return for the new matrices,
+ * the latest unscaled q, l, u, the constant c and the current settings: the scaling is computed again from scratch (the raw values of a
+ * matrix passed as NULL are kept on the device), every iterate and factor state goes back to its post-setup value. */
+static int update_refuse(const char *msg) { qdev_set_error(msg); return -1; }
+int qpdo_amd_update_matrices(QPDOWorkspace *work, const cholmod_sparse *Q, const cholmod_sparse *A) {
+    if (!work || !work->chol || !work->chol->dev || !work->data) return update_refuse("qpdo_amd_update_matrices: NULL workspace");
+    struct QPDOBackend *be = work->chol;
+    const size_t n = work->data->n, m = work->data->m;
+    if (Q && !sparse_ok(Q)) return update_refuse("qpdo_amd_update_matrices: unsupported sparse storage of Q");
+    if (A && !sparse_ok(A)) return update_refuse("qpdo_amd_update_matrices: unsupported sparse storage of A");
+    if (Q && (Q->nrow != n || Q->ncol != n)) return update_refuse("qpdo_amd_update_matrices: Q is not n x n");
+    if (A && (A->nrow != m || A->ncol != n)) return update_refuse("qpdo_amd_update_matrices: A is not m x n");
+    if (Q && Q->stype != be->q_stype) return update_refuse("qpdo_amd_update_matrices: Q has another stype than at setup");
+    if (Q && idx_at(Q->p, Q->itype, (int64_t)n) != be->q_nnz) return update_refuse("qpdo_amd_update_matrices: Q has another number of entries than at setup");
+    if (A && idx_at(A->p, A->itype, (int64_t)n) != be->a_nnz) return update_refuse("qpdo_amd_update_matrices: A has another number of entries than at setup");
+    QPDOTimer t; tic(&t);
+    QdevCsc a, qq;
+    if (A) { QdevCsc v = {(int32_t)A->nrow, (int32_t)A->ncol, be->a_nnz, A->itype, A->p, A->i, (const double *)A->x, 0}; a = v; }
+    if (Q) { QdevCsc v = {(int32_t)Q->nrow, (int32_t)Q->ncol, be->q_nnz, Q->itype, Q->p, Q->i, (const double *)Q->x, Q->stype}; qq = v; }
+    /* the device checks the pattern (and refuses a row-partitioned workspace) before it writes anything */
+    const int rc = qdev_update_matrices(be->dev, A ? &a : NULL, Q ? &qq : NULL, be->q_raw, be->l_raw, be->u_raw);
+    if (rc) return rc;
+    /* from here on, as qpdo_setup: the host mirrors, the scaling, the fused resident, the post-setup scalars */
+    memcpy(work->data->q, be->q_raw, n * sizeof(c_float));
+    if (m) { memcpy(work->data->l, be->l_raw, m * sizeof(c_float)); memcpy(work->data->u, be->u_raw, m * sizeof(c_float)); }
+    int fail = 0;
+    if (work->scaling) {
+        QPDOScaling *sc = work->scaling;
+        fail = qdev_scale_data(be->dev, (int)work->settings->scaling, 0, sc->D, sc->E, &sc->c) || install_scaling(work) ||
+               qdev_download_q(be->dev, work->data->q);
+        if (!fail) {
+            for (size_t i = 0; i < m; i++) { work->data->l[i] = sc->E[i] * work->data->l[i]; work->data->u[i] = sc->E[i] * work->data->u[i]; }
+            fail = qdev_upload_bounds(be->dev, work->data->l, work->data->u);
+        }
+        if (!fail) {
+            c_float mx = 0.0;
+            for (size_t i = 0; i < n; i++) { c_float s = c_absval(sc->Dinv[i] * work->data->q[i]); mx = s > mx ? s : mx; }
+            work->norm_q = mx;
+        }
+    } else {
+        fail = qdev_set_scaling(be->dev, 0, NULL, NULL, NULL, NULL, 1.0, 1.0);
+        work->norm_q = vec_norm_inf(work->data->q, n);
+    }
+    if (n) { memset(work->x, 0, n * sizeof(c_float)); memset(work->dx, 0, n * sizeof(c_float)); memset(work->solution->x, 0, n * sizeof(c_float)); }
+    if (m) { memset(work->y, 0, m * sizeof(c_float)); memset(work->dy, 0, m * sizeof(c_float)); memset(work->solution->y, 0, m * sizeof(c_float)); }
+    work->initialized = 0; work->n_mu_changed = 0; work->sigma = work->settings->sigma_init; work->tau = 0.0;
+    work->eps_in = 0.0; work->sqrt_mu_min = 0.0;
+    be->reset_newton = 1; be->ws_state = 0; be->auto_ws = 0; be->ntrace = 0; be->newton_passes = 0;
+    be->fused_solves = 0; be->fused_factor_count = 0; be->fused_kernel_s = 0.0; be->last_fused = 0;
+    /* the fused resident is rebuilt rather than proven clean (its arena holds the last solve's factor and iterates) */
+    qdev_small_resident_destroy(be->small); be->small = NULL;
+    if (!fail) small_resident_setup(work, work->settings);
+    memset(work->info, 0, sizeof(*work->info));
+    update_status(work->info, fail ? QPDO_ERROR : QPDO_UNSOLVED);
+    work->info->setup_time = toc(&t);
+    if (fail) { QPDO_EPRINT("device backend: %s", qdev_last_error()); return -1; }
+    return 0;
+}
+
 /* ---- qpdo_cleanup (reference src/qpdo.c:591-689) ---------------------------------------------------- */
 void qpdo_cleanup(QPDOWorkspace *work) {
     if (!work) return;
@@ -950,7 +1025,10 @@ void qpdo_cleanup(QPDOWorkspace *work) {
     if (work->scaling) { free(work->scaling->D); free(work->scaling->Dinv); free(work->scaling->E); free(work->scaling->Einv); free(work->scaling); }
     free(work->x); free(work->y); free(work->dx); free(work->dy);
     free(work->settings);
-    if (work->chol) { qdev_small_resident_destroy(work->chol->small); qdev_destroy(work->chol->dev); free(work->chol->trace); free(work->chol); }
+    if (work->chol) {
+        qdev_small_resident_destroy(work->chol->small); qdev_destroy(work->chol->dev); free(work->chol->trace);
+        free(work->chol->q_raw); free(work->chol->l_raw); free(work->chol->u_raw); free(work->chol);
+    }
     if (work->solution) { free(work->solution->x); free(work->solution->y); free(work->solution); }
     free(work->timer);
     free(work->info);

@@ -106,6 +106,13 @@ typedef struct {
 int qdev_create_dist(QpdoDev **out, int device, int32_t n, int32_t m, const QdevCsr *Ar, const QdevCsr *At, const QdevCsr *Qf,
                      const QdevCsr *Qs, const double *q, const double *l, const double *u, const QdevDist *dist);
 int qdev_rccl_unique_id(void *out128);
+/* qpdo_amd_update_matrices (dev/host_update.inc).  keep_raw_values: at setup of a scaled workspace, before qdev_scale_data -- device copies
+ * of the unscaled values of A (CSC order) and of the full Q.  update_matrices: checks the pattern of A / Q (NULL: unchanged) against the
+ * workspace before it writes anything, then writes the new unscaled values into the three stored matrices, puts every state that outlives
+ * a solve back to its post-setup value and uploads the unscaled q, l, u; the caller scales as qpdo_setup does.  One GPU only. */
+int qdev_keep_raw_values(QpdoDev *d);
+int qdev_update_matrices(QpdoDev *d, const QdevCsc *A, const QdevCsc *Q, const double *q, const double *l, const double *u);
+void qdev_set_error(const char *msg);
 void qdev_destroy(QpdoDev *d);
 int qdev_sync(QpdoDev *d);
 

@@ -55,6 +55,7 @@ static int set_err(hipError_t e, const char *what, int line) {
 #include "dev/mid_kernels.inc"
 #include "dev/transpose.inc"
 #include "dev/band.inc"
+#include "dev/update.inc"
 #include "dev/host_core.inc"
 
 extern "C" {
@@ -63,4 +64,5 @@ extern "C" {
 #include "dev/host_dense.inc"
 #include "dev/host_band.inc"
 #include "dev/host_step.inc"
+#include "dev/host_update.inc"
 }  // extern "C"

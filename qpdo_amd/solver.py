@@ -107,7 +107,8 @@ class BatchItem(C.Structure):
 
 EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solve_batch", "qpdo_amd_batch_kernel_seconds", "qpdo_amd_batch_stream_create",
                "qpdo_amd_batch_stream_submit", "qpdo_amd_batch_stream_wait", "qpdo_amd_batch_stream_destroy", "qpdo_amd_device_count", "qpdo_amd_last_error", "qpdo_amd_get_stats", "qpdo_amd_get_trace",
-               "qpdo_amd_sync", "qpdo_amd_pass_decision", "qpdo_amd_bench_spmv", "qpdo_amd_bench_dense_factor", "qpdo_amd_spmv", "qpdo_amd_linesearch", "qpdo_amd_download"]
+               "qpdo_amd_sync", "qpdo_amd_pass_decision", "qpdo_amd_bench_spmv", "qpdo_amd_bench_dense_factor", "qpdo_amd_spmv", "qpdo_amd_linesearch", "qpdo_amd_download",
+               "qpdo_amd_update_matrices"]
 
 _lib = None
 
@@ -142,6 +143,8 @@ def lib():
         L.qpdo_amd_bench_dense_factor.argtypes = [W, C.c_int, dp, dp]
         L.qpdo_amd_linesearch.argtypes = [W, C.c_double, C.c_double, dp, dp, dp]
         L.qpdo_amd_download.argtypes = [W, C.c_int, dp]
+        L.qpdo_amd_update_matrices.argtypes = [W, C.POINTER(CholmodSparse), C.POINTER(CholmodSparse)]
+        L.qpdo_amd_update_matrices.restype = C.c_int
         L.qpdo_amd_dist_config.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qpdo_amd_dist_unique_id.argtypes = [C.c_void_p]
         L.qpdo_amd_solve_batch.restype = C.c_long
@@ -197,6 +200,35 @@ def _sparse_view(M, stype, keep, index_dtype=None):
     return s
 
 
+def project_to_pattern(M, indptr, indices):
+    """The values of the sparse matrix M laid out in the CSC pattern (indptr, indices) -- sorted row indices, as setup hands them over.
+    M's own pattern must be a subset of it: an entry of the pattern that M lacks becomes an explicit 0.0; an entry of M outside the
+    pattern raises ValueError.  Duplicates of M are summed first.  Pure host arithmetic (qpdo_amd_update_matrices takes the setup's
+    pattern only)."""
+    if sp.isspmatrix_csc(M) and M.has_canonical_format and len(M.indices) == len(indices) and np.array_equal(M.indptr, indptr) \
+            and np.array_equal(M.indices, indices):
+        return np.array(M.data, np.float64)            # the pattern itself (the common case): no search
+    M = sp.csc_matrix(M, copy=True)
+    M.sum_duplicates()
+    ncol = len(indptr) - 1
+    if M.shape[1] != ncol:
+        raise ValueError("matrix has %d columns, the pattern %d" % (M.shape[1], ncol))
+    nrow = M.shape[0]
+    pcol = np.repeat(np.arange(ncol, dtype=np.int64), np.diff(np.asarray(indptr, np.int64)))
+    pkey = pcol * nrow + np.asarray(indices, np.int64)
+    mcol = np.repeat(np.arange(ncol, dtype=np.int64), np.diff(M.indptr.astype(np.int64)))
+    mkey = mcol * nrow + M.indices.astype(np.int64)
+    pos = np.searchsorted(pkey, mkey)
+    ok = pos < len(pkey)
+    ok[ok] = pkey[pos[ok]] == mkey[ok]
+    if not ok.all():
+        k = int(np.flatnonzero(~ok)[0])
+        raise ValueError("entry (%d, %d) is outside the sparsity pattern given to setup" % (int(M.indices[k]), int(mcol[k])))
+    x = np.zeros(len(pkey))
+    x[pos] = M.data
+    return x
+
+
 class QPDO:
     """solver = QPDO(); solver.setup(Q, q, A, l, u, **settings); res = solver.solve()"""
 
@@ -220,6 +252,7 @@ class QPDO:
             raise ValueError("incompatible vector dimensions")
         l = np.clip(l, -QPDO_INFTY, QPDO_INFTY)      # qpdo.m:138-139
         u = np.clip(u, -QPDO_INFTY, QPDO_INFTY)
+        self._Qtril = Qstype is None
         if Qstype is None:
             Q = sp.tril(Q).tocsc()                     # the mex reads the lower triangle (qpdo_mex.c:150)
             Qstype = -1
@@ -239,6 +272,36 @@ class QPDO:
         if not w:
             raise RuntimeError("Invalid problem setup: %s" % (lib().qpdo_amd_last_error() or b"").decode())
         self._w, self.n, self.m = w, n, m
+        # the pattern as handed over (sorted CSC; keep[] holds Q's p, i, x then A's): update_matrices projects onto it
+        self._Qstype, self._Qpat, self._Apat = Qstype, (keep[3], keep[4]), (keep[6], keep[7])
+        return self
+
+    def update_matrices(self, Q=None, A=None):
+        """New values of Q and / or A (None: unchanged) in the pattern given to setup; a matrix whose pattern is a subset of the setup's is
+        projected onto it (dropped entries become explicit zeros).  Afterwards the workspace is the one setup would return for the new
+        matrices and the latest q, l, u (qpdo_amd_update_matrices); warm-start explicitly if wanted."""
+        keep, views = [], []
+        for is_Q, M, pat, stype, shape in ((True, Q, self._Qpat, self._Qstype, (self.n, self.n)), (False, A, self._Apat, 0, (self.m, self.n))):
+            if M is None:
+                views.append(None)
+                continue
+            M = sp.csc_matrix(M)
+            if M.shape != shape:
+                raise ValueError("matrix is %d x %d, expected %d x %d" % (M.shape + shape))
+            if is_Q and self._Qtril and not (M.has_canonical_format and np.array_equal(M.indptr, pat[0]) and np.array_equal(M.indices, pat[1])):
+                M = sp.tril(M).tocsc()                 # as setup normalised it (a matrix in the stored pattern already is lower)
+            x = project_to_pattern(M, pat[0], pat[1])
+            keep.append(x)
+            s = CholmodSparse()
+            s.nrow, s.ncol, s.nzmax = shape[0], shape[1], max(1, len(x))
+            s.p, s.i, s.x = pat[0].ctypes.data, pat[1].ctypes.data, x.ctypes.data
+            s.nz, s.z = None, None
+            s.stype, s.itype, s.xtype, s.dtype, s.sorted, s.packed = stype, (2 if pat[0].dtype == np.int64 else 0), 1, 0, 1, 1
+            views.append(s)
+        rc = lib().qpdo_amd_update_matrices(self._w, C.byref(views[0]) if views[0] is not None else None,
+                                            C.byref(views[1]) if views[1] is not None else None)
+        if rc:
+            raise RuntimeError("update_matrices: %s" % (lib().qpdo_amd_last_error() or b"").decode())
         return self
 
     @property
