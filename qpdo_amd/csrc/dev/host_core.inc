@@ -100,6 +100,7 @@ static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, 
 static int setup_slabs(QpdoDev *d, DevCsr *M) {
     const char *tp = getenv("QPDO_SLAB_TPR");
     if (tp && (atoi(tp) == 8 || atoi(tp) == 16 || atoi(tp) == 32)) g_slab_tpr = atoi(tp);
+    { const char *ov = getenv("QPDO_SLAB_OVERLAP"); M->slab_ovl = !(ov && *ov && atoi(ov) == 0); }
     const char *force = getenv("QPDO_SPMV");            // "slab" | "plain" | unset (auto)
     const double bytes = 12.0 * (double)M->nnz;
     bool want = bytes >= 192.0 * 1024 * 1024 && M->nrows >= 4096;   // beyond what L2 + Infinity Cache keep resident

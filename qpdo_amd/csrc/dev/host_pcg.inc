@@ -16,7 +16,7 @@ static int build_compact(QpdoDev *d) {
     LAUNCH(k_gather_rowinfo, vgrid(k), k, (const int *)d->rowlist, d->Ar.rp, dl, d->row_cnt, d->dc);
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, k, d->Arc.rp);
     DevCsr &R = d->Arc;
-    R.nrows = k; R.ncols = n; R.tpr = d->Ar.tpr; R.use_slab = d->Ar.use_slab && k >= 4096;
+    R.nrows = k; R.ncols = n; R.tpr = d->Ar.tpr; R.use_slab = d->Ar.use_slab && k >= 4096; R.slab_ovl = d->Ar.slab_ovl;
     int RW16 = 0;
     if (R.use_slab) {
         R.rows_per_wg = (k + 255) / 256; R.slab_grid = (k + R.rows_per_wg - 1) / R.rows_per_wg;
@@ -36,7 +36,7 @@ static int build_compact(QpdoDev *d) {
     // A_c': columns, renumbered
     DevCsr &T = d->Atc;
     const DevCsr &M = d->At;
-    T.nrows = n; T.ncols = k; T.tpr = M.tpr; T.use_slab = M.use_slab && k >= 1024;
+    T.nrows = n; T.ncols = k; T.tpr = M.tpr; T.use_slab = M.use_slab && k >= 1024; T.slab_ovl = M.slab_ovl;
     int W16 = 0;
     if (T.use_slab) {
         T.rows_per_wg = M.rows_per_wg; T.slab_grid = M.slab_grid;

@@ -50,7 +50,16 @@ __global__ __launch_bounds__(256) void k_spmv(int nrows, const int *__restrict__
 static const int SLAB_THREADS = 1024;
 #define SLAB_UNR 8               // 16-byte loads in flight per lane
 static int g_slab_tpr = 16;     // lanes per row segment (QPDO_SLAB_TPR: 8 | 16 | 32; 16 x 16-byte loads measured best at C4)
-template <class Epi, bool I16, int TPR>
+// OVL (the default; QPDO_SLAB_OVERLAP=0 keeps the old schedule): the slab boundaries are hidden behind matrix loads already in flight.
+// Without it, every CU's HBM queue drains at each boundary -- the last segments, two barriers, the x-slice copy from L2 and one
+// HBM miss before the new slab's first data.  With it, each lane group issues the value and index loads of ITS first row of the
+// next slab (fixed assignment: group g takes row g; the LDS counter then starts at the number of groups) before it goes into the
+// barrier, and the same before the staging of slab 0.  The loads do not depend on x.  They land in the registers of the streaming
+// loop, and the trip is computed from them after the copy exactly as the loop would have: the arithmetic of a row does not change.
+// The x slice is copied with 16-byte global_load_lds (dst = wave base + 16 * lane), so the copy costs one L2 round trip, not one
+// per 16 KB.  (Lab, tools/lab/slab_lab.hip LAB_OVL=1, round 6: the early loads alone do not pay at the compact shapes -- the
+// register copy waits for them in order; with the async copy: -4 % at k = 66 000, -3.5 % at 73 000, -1 % on the full matrix.)
+template <class Epi, bool I16, int TPR, bool OVL>
 __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                     int rows_per_wg, const int2 *__restrict__ seg, const int *__restrict__ cism,
                                                     const unsigned short *__restrict__ i16sm,
@@ -66,6 +75,78 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
     const int R = min(rows_per_wg, nrows - row0);
     for (int r = tid; r < R; r += SLAB_THREADS) acc[r] = 0.0;
     const int lane = tid & (TPR - 1);
+    constexpr int NG = SLAB_THREADS / TPR;              // lane groups per workgroup
+    constexpr int STEP = 2 * SLAB_UNR * TPR;            // entries per trip of a lane group
+    // 16-byte value loads and paired index loads from an even start (the element before an odd `beg` and the one after an
+    // odd end are masked): one instruction covers 2*TPR consecutive entries and SLAB_UNR of them are in flight per lane -- a
+    // C4 segment (~170 entries) is a single trip.  No scalar tail loop: slots past the end re-read the first pair and
+    // contribute exact zeros.  (Lab, tools/lab/slab_lab.hip, C4 shape: 8-byte loads x4: 5.8 TB/s; 16-byte x4: 6.2; x8: 6.9
+    // with the slab-major image, 6.2 without.)
+    // index words: a pair of 16-bit slab-local indices, or a pair of 32-bit ones; unpacked at the use, so that nothing waits for a
+    // load in flight before the row's first trip is computed
+    using IdxW = typename std::conditional<I16, unsigned, int2>::type;
+    auto load_trip = [&](double2 *v, IdxW *w, int k, int kb, int end) {
+#pragma unroll
+        for (int u = 0; u < SLAB_UNR; u++) {
+            const int kk = k + u * 2 * TPR;
+            const int kc = kk < end ? kk : kb;
+            v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
+            if constexpr (I16) w[u] = *reinterpret_cast<const unsigned *>(i16sm + kc);
+            else               w[u] = *reinterpret_cast<const int2 *>(cism + kc);
+        }
+    };
+    // OVL: the first trip of the group's prefetched row (pv, pw: written on every pass of the prefetch, so that they are live
+    // only from there to the row's first trip -- the register allocator then gives them the registers of the streaming loop)
+    double2 pv[SLAB_UNR]; IdxW pw[SLAB_UNR];
+    int pr = -1, pbeg = 0, pend = 0;
+    // row r's segment [beg, end) of the staged slab, added to acc[r]; PRE: the loads of the first trip are in pv / pw
+    auto row_seg = [&](int r, int beg, int end, auto pre) {
+        constexpr bool PRE = decltype(pre)::value;
+        const int kb = beg & ~1;
+        double sa[2 * SLAB_UNR];
+#pragma unroll
+        for (int u = 0; u < 2 * SLAB_UNR; u++) sa[u] = 0.0;
+        auto fma_trip = [&](const double2 *v, const IdxW *w, int k) {
+#pragma unroll
+            for (int u = 0; u < SLAB_UNR; u++) {
+                const int kk = k + u * 2 * TPR;
+                int ax, ay;
+                if constexpr (I16) { ax = (int)(w[u] & 0xffffu); ay = (int)(w[u] >> 16); }
+                else               { ax = w[u].x; ay = w[u].y; }
+                const double px = v[u].x * xs[ax], py = v[u].y * xs[ay];
+                sa[2 * u] += (kk >= beg && kk < end) ? px : 0.0;
+                sa[2 * u + 1] += (kk + 1 < end) ? py : 0.0;
+            }
+        };
+        int k = kb + 2 * lane;
+        if (PRE && k < end) { fma_trip(pv, pw, k); k += STEP; }
+        for (; k < end; k += STEP) {
+            double2 v[SLAB_UNR]; IdxW w[SLAB_UNR];
+            load_trip(v, w, k, kb, end);
+            fma_trip(v, w, k);
+        }
+        double t = 0.0;
+#pragma unroll
+        for (int u = 0; u < SLAB_UNR; u++) t += sa[2 * u] + sa[2 * u + 1];
+#pragma unroll
+        for (int o = TPR / 2; o > 0; o >>= 1) t += __shfl_down(t, o, TPR);
+        if (lane == 0) acc[r] += t;
+    };
+    // OVL: the first row batch of slab s is group g -> row g; its first trip's loads are issued here, before the barrier.  Called
+    // with s == nslabs too (no loads then): pv / pw are defined on every path around the slab loop.
+    auto prefetch = [&](int s) {
+#pragma unroll
+        for (int u = 0; u < SLAB_UNR; u++) { pv[u] = make_double2(0.0, 0.0); pw[u] = IdxW{}; }
+        pr = -1;
+        const int g = tid / TPR;
+        if (s < nslabs && g < R && !epi.skip(row0 + g)) {
+            const int2 sg = seg[(size_t)(row0 + g) * nslabs + s];
+            pr = g; pbeg = sg.x; pend = sg.x + sg.y;
+            const int kb = pbeg & ~1;
+            if (kb + 2 * lane < pend) load_trip(pv, pw, kb + 2 * lane, kb, pend);
+        }
+    };
+    if (OVL) prefetch(0);
     for (int s = 0; s < nslabs; s++) {
         const int c0 = s * W;
         const int cw = min(W, ncols - c0);
@@ -74,11 +155,19 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
             const int pairs = cw >> 1;
             const double2 *src = reinterpret_cast<const double2 *>(x + c0);
             double2 *dst = reinterpret_cast<double2 *>(xs);
-            for (int i = tid; i < pairs; i += SLAB_THREADS) dst[i] = src[i];
+            if (OVL) {      // global -> LDS without VGPRs: every copy of a lane in flight at once, not one L2 round trip each
+                for (int i = tid; i < pairs; i += SLAB_THREADS)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + i),
+                                                     (__attribute__((address_space(3))) void *)(dst + (i & ~63)), 16, 0, 0);
+            } else {
+                for (int i = tid; i < pairs; i += SLAB_THREADS) dst[i] = src[i];
+            }
             if ((cw & 1) && tid == 0) xs[cw - 1] = x[c0 + cw - 1];
-            if (tid == 0) next_row = 0;
+            if (tid == 0) next_row = OVL ? NG : 0;
+            if (OVL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the copies have landed in LDS
         }
         __syncthreads();
+        if (OVL && pr >= 0) row_seg(pr, pbeg, pend, std::true_type());
         // Rows are handed out dynamically (LDS counter): with only a few row segments per lane group and slab a
         // static split leaves groups idle at the end-of-slab barrier.  One lane per WAVE grabs a batch of 64/TPR
         // rows and broadcasts it wave-wide, so the loop exit is wave-uniform (no divergent break around the
@@ -94,41 +183,9 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
             const int row = row0 + r;
             if (epi.skip(row)) continue;
             const int2 sg = seg[(size_t)row * nslabs + s];
-            const int beg = sg.x, end = sg.x + sg.y;
-            // 16-byte value loads and paired index loads from an even start (the element before an odd `beg` and the
-            // one after an odd end are masked): one instruction covers 2*TPR consecutive entries and SLAB_UNR of them
-            // are in flight per lane -- a C4 segment (~170 entries) is a single trip.  No scalar tail loop: slots past
-            // the end re-read the first pair and contribute exact zeros.  (Lab, tools/lab/slab_lab.hip, C4 shape:
-            // 8-byte loads x4: 5.8 TB/s; 16-byte x4: 6.2; x8: 6.9 with the slab-major image, 6.2 without.)
-            const int kb = beg & ~1;
-            double sa[2 * SLAB_UNR];
-#pragma unroll
-            for (int u = 0; u < 2 * SLAB_UNR; u++) sa[u] = 0.0;
-            for (int k = kb + 2 * lane; k < end; k += 2 * SLAB_UNR * TPR) {
-                double2 v[SLAB_UNR]; int ax[SLAB_UNR], ay[SLAB_UNR];
-#pragma unroll
-                for (int u = 0; u < SLAB_UNR; u++) {
-                    const int kk = k + u * 2 * TPR;
-                    const int kc = kk < end ? kk : kb;
-                    v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
-                    if (I16) { const ushort2 a = *reinterpret_cast<const ushort2 *>(i16sm + kc); ax[u] = a.x; ay[u] = a.y; }
-                    else     { const int2 a = *reinterpret_cast<const int2 *>(cism + kc); ax[u] = a.x; ay[u] = a.y; }
-                }
-#pragma unroll
-                for (int u = 0; u < SLAB_UNR; u++) {
-                    const int kk = k + u * 2 * TPR;
-                    const double px = v[u].x * xs[ax[u]], py = v[u].y * xs[ay[u]];
-                    sa[2 * u] += (kk >= beg && kk < end) ? px : 0.0;
-                    sa[2 * u + 1] += (kk + 1 < end) ? py : 0.0;
-                }
-            }
-            double t = 0.0;
-#pragma unroll
-            for (int u = 0; u < SLAB_UNR; u++) t += sa[2 * u] + sa[2 * u + 1];
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) t += __shfl_down(t, o, TPR);
-            if (lane == 0) acc[r] += t;
+            row_seg(r, sg.x, sg.x + sg.y, std::false_type());
         }
+        if (OVL) prefetch(s + 1);
     }
     __syncthreads();
     for (int r = tid; r < R; r += SLAB_THREADS) epi.row(row0 + r, acc[r]);
@@ -444,15 +501,18 @@ static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi e
     const size_t lds = ((size_t)M.W + (size_t)M.rows_per_wg) * sizeof(double);
     static thread_local bool attr_set = false;   // per instantiation
     if (!attr_set) {
-#define SLAB_ATTR(I16, T) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spmv_slab<Epi, I16, T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512)
-        SLAB_ATTR(false, 8); SLAB_ATTR(false, 16); SLAB_ATTR(false, 32); SLAB_ATTR(true, 8); SLAB_ATTR(true, 16); SLAB_ATTR(true, 32);
+#define SLAB_ATTR(I16, T, O) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spmv_slab<Epi, I16, T, O>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512)
+        SLAB_ATTR(false, 8, false); SLAB_ATTR(false, 16, false); SLAB_ATTR(false, 32, false); SLAB_ATTR(true, 8, false); SLAB_ATTR(true, 16, false); SLAB_ATTR(true, 32, false);
+        SLAB_ATTR(false, 8, true); SLAB_ATTR(false, 16, true); SLAB_ATTR(false, 32, true); SLAB_ATTR(true, 8, true); SLAB_ATTR(true, 16, true); SLAB_ATTR(true, 32, true);
 #undef SLAB_ATTR
         attr_set = true;
     }
     if (M.sm_dirty) slab_major_build(d, M);
-#define SLAB_GO(I16, T) hipLaunchKernelGGL((k_spmv_slab<Epi, I16, T>), dim3(M.slab_grid), dim3(SLAB_THREADS), lds, d->stream, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, M.vsm, x, epi)
-    if (M.i16sm) { if (g_slab_tpr == 8) SLAB_GO(true, 8); else if (g_slab_tpr == 32) SLAB_GO(true, 32); else SLAB_GO(true, 16); }
-    else        { if (g_slab_tpr == 8) SLAB_GO(false, 8); else if (g_slab_tpr == 32) SLAB_GO(false, 32); else SLAB_GO(false, 16); }
+#define SLAB_GO(I16, T, O) hipLaunchKernelGGL((k_spmv_slab<Epi, I16, T, O>), dim3(M.slab_grid), dim3(SLAB_THREADS), lds, d->stream, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, M.vsm, x, epi)
+#define SLAB_TPR(I16, O) { if (g_slab_tpr == 8) SLAB_GO(I16, 8, O); else if (g_slab_tpr == 32) SLAB_GO(I16, 32, O); else SLAB_GO(I16, 16, O); }
+    if (M.slab_ovl) { if (M.i16sm) SLAB_TPR(true, true) else SLAB_TPR(false, true) }
+    else            { if (M.i16sm) SLAB_TPR(true, false) else SLAB_TPR(false, false) }
+#undef SLAB_TPR
 #undef SLAB_GO
     d->st.spmv_calls++;
     d->st.spmv_bytes += (int64_t)M.alg_bytes();

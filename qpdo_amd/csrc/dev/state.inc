@@ -25,6 +25,7 @@ struct DevCsr {
     // LDS-staged variant: columns are cut into `nslabs` slabs of W columns; sp[r*(nslabs+1)+s] is the
     // position inside row r where slab s starts (rows are column-sorted, so a slab is a sub-range)
     int use_slab = 0, nslabs = 0, W = 0, rows_per_wg = 0, slab_grid = 0;
+    int slab_ovl = 1;        // k_spmv_slab issues the next slab's first loads before its barriers (QPDO_SLAB_OVERLAP=0: the old schedule)
     int *sp = nullptr;
     unsigned short *ci16 = nullptr;   // column index inside its slab (W < 65536): 10 instead of 12 bytes per nonzero
     // Slab-major image, the arrays the slab kernel actually streams: per workgroup the row segments of slab 0 back to

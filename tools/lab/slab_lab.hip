@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+#include <type_traits>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s line %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
 typedef unsigned long long u64;
 __device__ __host__ inline u64 mix(u64 z) { z += 0x9e3779b97f4a7c15ULL; z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL; z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL; return z ^ (z >> 31); }
@@ -190,8 +191,11 @@ __global__ __launch_bounds__(256) void k_slab_permute(int nrows, int nslabs, int
             for (int e = lane; e < sg.y; e += 16) { vsm[sg.x + e] = val[src + e]; i16sm[sg.x + e] = ci16[src + e]; }
         }
 }
-// production-form kernel: int2 segment table, ternary masking of the products; UNR 16-byte loads in flight per lane
-template <int TPR, int UNR, int NT = 1024>
+// production-form kernel: int2 segment table, ternary masking of the products; UNR 16-byte loads in flight per lane.
+// OVL (round 6): each lane group issues the loads of its first row segment of the next slab (group g -> row g, the LDS
+// counter then starts at NT/TPR) before the end-of-slab barrier, and of slab 0 before the first staging barrier.
+// OVL 2: the same, and the x slice is copied with 16-byte global_load_lds (no VGPRs, all of a lane's copies in flight at once)
+template <int TPR, int UNR, int NT = 1024, int OVL = 0>
 __global__ __launch_bounds__(NT) void k_slab_prod(int nrows, int ncols, int nslabs, int W, int rows_per_wg, const int2 *__restrict__ seg,
                                                     const unsigned short *__restrict__ i16sm, const double *__restrict__ vsm,
                                                     const double *__restrict__ x, double *__restrict__ y) {
@@ -203,14 +207,75 @@ __global__ __launch_bounds__(NT) void k_slab_prod(int nrows, int ncols, int nsla
     const int R = min(rows_per_wg, nrows - row0);
     for (int r = tid; r < R; r += NT) acc[r] = 0.0;
     const int lane = tid & (TPR - 1);
+    // a trip: UNR 16-byte value loads and UNR paired 16-bit index words (unpacked at the use, so that a load in flight is not waited for)
+    auto load_trip = [&](double2 *v, unsigned *w, int k, int kb, int end) {
+#pragma unroll
+        for (int u = 0; u < UNR; u++) {
+            const int kk = k + u * 2 * TPR; const int kc = kk < end ? kk : kb;
+            v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
+            w[u] = *reinterpret_cast<const unsigned *>(i16sm + kc);
+        }
+    };
+    double2 pv[UNR]; unsigned pw[UNR];                // written on every path of the prefetch: live only up to the first trip
+    int pr = -1, pbeg = 0, pend = 0;
+    auto row_seg = [&](int r, int beg, int end, auto pre) {
+        constexpr bool PRE = decltype(pre)::value;
+        const int kb = beg & ~1;
+        double sa[2 * UNR];
+#pragma unroll
+        for (int u = 0; u < 2 * UNR; u++) sa[u] = 0.0;
+        auto fma_trip = [&](const double2 *v, const unsigned *w, int k) {
+#pragma unroll
+            for (int u = 0; u < UNR; u++) {
+                const int kk = k + u * 2 * TPR;
+                const double px = v[u].x * xs[w[u] & 0xffffu], py = v[u].y * xs[w[u] >> 16];
+                sa[2 * u] += (kk >= beg && kk < end) ? px : 0.0;
+                sa[2 * u + 1] += (kk + 1 < end) ? py : 0.0;
+            }
+        };
+        int k = kb + 2 * lane;
+        if (PRE && k < end) { fma_trip(pv, pw, k); k += 2 * UNR * TPR; }
+        for (; k < end; k += 2 * UNR * TPR) {
+            double2 v[UNR]; unsigned w[UNR];
+            load_trip(v, w, k, kb, end);
+            fma_trip(v, w, k);
+        }
+        double t = 0.0;
+#pragma unroll
+        for (int u = 0; u < 2 * UNR; u++) t += sa[u];
+#pragma unroll
+        for (int o = TPR / 2; o > 0; o >>= 1) t += __shfl_down(t, o, TPR);
+        if (lane == 0) acc[r] += t;
+    };
+    auto prefetch = [&](int s) {
+#pragma unroll
+        for (int u = 0; u < UNR; u++) { pv[u] = make_double2(0.0, 0.0); pw[u] = 0; }
+        pr = -1;
+        const int g = tid / TPR;
+        if (s < nslabs && g < R) {
+            const int2 sg = seg[(size_t)(row0 + g) * nslabs + s];
+            pr = g; pbeg = sg.x; pend = sg.x + sg.y;
+            const int kb = pbeg & ~1;
+            if (kb + 2 * lane < pend) load_trip(pv, pw, kb + 2 * lane, kb, pend);
+        }
+    };
+    if (OVL) prefetch(0);
     for (int s = 0; s < nslabs; s++) {
         const int c0 = s * W, cw = min(W, ncols - c0);
         __syncthreads();
         { const int pairs = cw >> 1; const double2 *src = reinterpret_cast<const double2 *>(x + c0); double2 *dst = reinterpret_cast<double2 *>(xs);
-          for (int i = tid; i < pairs; i += NT) dst[i] = src[i];
+          if (OVL == 2) {
+              for (int i = tid; i < pairs; i += NT)
+                  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + i),
+                                                   (__attribute__((address_space(3))) void *)(dst + (i & ~63)), 16, 0, 0);
+          } else {
+              for (int i = tid; i < pairs; i += NT) dst[i] = src[i];
+          }
           if ((cw & 1) && tid == 0) xs[cw - 1] = x[c0 + cw - 1];
-          if (tid == 0) next_row = 0; }
+          if (tid == 0) next_row = OVL ? NT / TPR : 0;
+          if (OVL == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
         __syncthreads();
+        if (OVL && pr >= 0) row_seg(pr, pbeg, pend, std::true_type());
         const int gw = (tid & 63) / TPR;
         for (;;) {
             int base = 0;
@@ -221,34 +286,9 @@ __global__ __launch_bounds__(NT) void k_slab_prod(int nrows, int ncols, int nsla
             if (r >= R) continue;
             const int row = row0 + r;
             const int2 sg = seg[(size_t)row * nslabs + s];
-            const int beg = sg.x, end = sg.x + sg.y;
-            const int kb = beg & ~1;
-            double sa[2 * UNR];
-#pragma unroll
-            for (int u = 0; u < 2 * UNR; u++) sa[u] = 0.0;
-            for (int k = kb + 2 * lane; k < end; k += 2 * UNR * TPR) {
-                double2 v[UNR]; int ax[UNR], ay[UNR];
-#pragma unroll
-                for (int u = 0; u < UNR; u++) {
-                    const int kk = k + u * 2 * TPR; const int kc = kk < end ? kk : kb;
-                    v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
-                    const ushort2 a = *reinterpret_cast<const ushort2 *>(i16sm + kc); ax[u] = a.x; ay[u] = a.y;
-                }
-#pragma unroll
-                for (int u = 0; u < UNR; u++) {
-                    const int kk = k + u * 2 * TPR;
-                    const double px = v[u].x * xs[ax[u]], py = v[u].y * xs[ay[u]];
-                    sa[2 * u] += (kk >= beg && kk < end) ? px : 0.0;
-                    sa[2 * u + 1] += (kk + 1 < end) ? py : 0.0;
-                }
-            }
-            double t = 0.0;
-#pragma unroll
-            for (int u = 0; u < 2 * UNR; u++) t += sa[u];
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) t += __shfl_down(t, o, TPR);
-            if (lane == 0) acc[r] += t;
+            row_seg(r, sg.x, sg.x + sg.y, std::false_type());
         }
+        if (OVL) prefetch(s + 1);
     }
     __syncthreads();
     for (int r = tid; r < R; r += NT) y[row0 + r] = acc[r];
@@ -468,7 +508,7 @@ static void run_prod_db(const char *name, int m, int n, int nwg, const unsigned 
     printf("%-44s wg %4d x 1024 thr, W %5d, %2d slabs: %.3f ms  algorithmic %.2f TB/s  checksum %.10e\n", name, grid, W, nslabs, ms, nnz * 12 / ms / 1e9, cs); fflush(stdout);
     CK(hipFree(sp)); CK(hipFree(seg)); CK(hipFree(i16)); CK(hipFree(i16sm)); CK(hipFree(vsm));
 }
-template <int TPR, int UNR, int NT>
+template <int TPR, int UNR, int NT, int OVL = 0>
 static void run_prod_wg(const char *name, int m, int n, int nwg, int budget_div, const int *sp0, int nslabs0, const unsigned short *ci16_rm, const int *ci_rm, const double *val_rm, const double *x, double *y, double nnz) {
     // rebuild slab tables for this (W, rows-per-wg): W from the LDS budget of one workgroup
     const int rpw = (m + nwg - 1) / nwg;
@@ -482,11 +522,11 @@ static void run_prod_wg(const char *name, int m, int n, int nwg, int budget_div,
     hipLaunchKernelGGL(k_slab_permute, dim3(2048), dim3(256), 0, 0, m, nslabs, W, (const int *)sp, (const int2 *)seg, (const unsigned short *)i16, val_rm, vsm, i16sm);
     CK(hipDeviceSynchronize());
     const int grid = (m + rpw - 1) / rpw; const size_t lds = (size_t)(W + rpw) * 8;
-    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slab_prod<TPR, UNR, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slab_prod<TPR, UNR, NT, OVL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    for (int w = 0; w < 2; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
+    for (int w = 0; w < 2; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT, OVL>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
     CK(hipEventRecord(e0, 0));
-    for (int w = 0; w < 10; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
+    for (int w = 0; w < 10; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT, OVL>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= 10;
     { std::vector<double> h(m); CK(hipMemcpy(h.data(), y, (size_t)m * 8, hipMemcpyDeviceToHost)); double cs = 0.0; for (int i = 0; i < m; i++) cs += h[i] * ((i % 7) + 1);
@@ -709,6 +749,20 @@ int main() {
             run_prod_wg<16, 8, 1024>("full m tpr16 unr8 (production)", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
             run_prod_wg<16, 7, 1024>("full m tpr16 unr7", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
             run_prod_wg<16, 6, 1024>("full m tpr16 unr6", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
+            }
+            return 0;
+        }
+        if (getenv("LAB_OVL")) {     // round 6: next slab's first loads issued before the barriers, against production, alternating
+            for (int rep = 0; rep < 3; rep++) {
+            run_prod_wg<16, 8, 1024>("k=66000 production", 66000, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, 66000.0 * per_row);
+            run_prod_wg<16, 8, 1024, 1>("k=66000 overlap", 66000, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, 66000.0 * per_row);
+            run_prod_wg<16, 8, 1024, 2>("k=66000 overlap + glds copy", 66000, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, 66000.0 * per_row);
+            run_prod_wg<16, 8, 1024>("k=73000 production", kk, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnzk);
+            run_prod_wg<16, 8, 1024, 1>("k=73000 overlap", kk, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnzk);
+            run_prod_wg<16, 8, 1024, 2>("k=73000 overlap + glds copy", kk, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnzk);
+            run_prod_wg<16, 8, 1024>("full m production", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
+            run_prod_wg<16, 8, 1024, 1>("full m overlap", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
+            run_prod_wg<16, 8, 1024, 2>("full m overlap + glds copy", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
             }
             return 0;
         }
