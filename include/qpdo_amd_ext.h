@@ -40,7 +40,6 @@
  *   the XCD-aware order), QPDO_DENSE_FPANEL ("1": a whole outer panel in one
  *   launch; slower at present)
  *   QPDO_SETUP_THREADS  host threads of the CSC -> CSR conversions in qpdo_setup (default min(16, cores)); QPDO_SETUP_PROF=1 prints phase times
- *   QPDO_SLAB_TPR    lanes per row segment of the slab SpMV (8 | 16 | 32, default 16)
  *   QPDO_SPMV        "slab" | "plain" (default: LDS-staged slab kernel for matrices >= 192 MB)
  *   QPDO_DEFLATE     "0" disables the heavy-row deflation of the PCG preconditioner
  *   QPDO_IDX16       "0" disables the 16-bit slab-local column indices

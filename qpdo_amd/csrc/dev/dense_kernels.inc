@@ -21,8 +21,8 @@ typedef double dvec4 __attribute__((ext_vector_type(4)));
 // assembled in row tiles [lo, lo + tile), each walking the column's weighted rows again and keeping only the entries that fall into
 // the tile -- every element still receives its contributions in ascending row order, so the tiled and the untiled assembly give the
 // same bits, and the order of the direct solver is bounded by HBM (an n x n matrix), not by LDS.
-// (launch-ahead route: the product A't of the step's right-hand side rides on this launch -- blocks [g0, gridDim.x) --, the same lane
-// groups, partial sums and shuffles as k_spmv, so the same bits; it writes the padded right-hand side itself)
+// (launch-ahead route: the product A't of the step's right-hand side rides on this launch -- blocks [g0, gridDim.x) --, through
+// spmv_rows, the row loop of k_spmv, so the same bits; it writes the padded right-hand side itself)
 struct AsmRhs { int on, g0, tpr, nrows; const int *rp, *ci; const double *val, *x, *rdi; double *atdy, *rhs; };
 __global__ __launch_bounds__(64) void k_dense_assemble(int n, int ld, int tile, const int *__restrict__ qrp, const int *__restrict__ qci,
                                                        const double *__restrict__ qval, const int *__restrict__ trp,
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(64) void k_dense_assemble(int n, int ld, int tile, 
     if (spec) { if (spec->cnt[C_SPEC_SKIP]) return; if (spec->cnt[C_SPEC_BRANCH] == 1) sigma_f = sigma_f1; }
     if (ar.on && (int)blockIdx.x >= ar.g0) {
         EpiRhsX e{ar.rdi, ar.atdy, ar.rhs, rx};
-        spmv_rows_rt((int)blockIdx.x - ar.g0, (int)gridDim.x - ar.g0, ar.tpr, ar.nrows, ar.rp, ar.ci, ar.val, ar.x, e, 64);
+        spmv_rows((int)blockIdx.x - ar.g0, (int)gridDim.x - ar.g0, ar.tpr, ar.nrows, ar.rp, ar.ci, ar.val, ar.x, e, 64);
         return;
     }
     const int nblk = ar.on ? ar.g0 : (int)gridDim.x;                 // blocks of the assembly proper

@@ -98,8 +98,6 @@ static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, 
     return rc;
 }
 static int setup_slabs(QpdoDev *d, DevCsr *M) {
-    const char *tp = getenv("QPDO_SLAB_TPR");
-    if (tp && (atoi(tp) == 8 || atoi(tp) == 16 || atoi(tp) == 32)) g_slab_tpr = atoi(tp);
     { const char *ov = getenv("QPDO_SLAB_OVERLAP"); M->slab_ovl = !(ov && *ov && atoi(ov) == 0); }
     const char *force = getenv("QPDO_SPMV");            // "slab" | "plain" | unset (auto)
     const double bytes = 12.0 * (double)M->nnz;

@@ -47,7 +47,7 @@ static int build_compact(QpdoDev *d) {
         T.nslabs = nslabs; T.W = W;
         if (T.ci16 && W < 65536) W16 = W;
     }
-    const int g = M.use_slab ? 2048 : spmv_grid(M, M.tpr, false);
+    const int g = M.use_slab ? 2048 : spmv_grid(M, false);
     const int words = (m + 63) / 64;
     const size_t lds_tab = (size_t)words * (sizeof(u64) + sizeof(int));
     if (lds_tab <= 60 * 1024) {          // flags and renumbering as LDS tables: the kernels stream the matrix only
@@ -107,7 +107,7 @@ static int defl_build(QpdoDev *d) {
     if (r <= 0 || r > DEFL_MAX) return 0;
     const DevCsr &T = d->Atc;
     // P: Jacobi diagonal of the remainder (floored), A_h': the heavy columns of A_c'
-    const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, d->At.tpr, false);
+    const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, false);
     DISPATCH_TPR(d->At, k_jacobi_diag2, gAt, n, T.rp, T.ci, T.val, (const double *)d->tmp_m, (const double *)d->dc, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
     DISPATCH_TPR(d->At, k_count_flagged, gAt, n, T.rp, T.ci, (const double *)d->defl_flag, d->row_cnt);
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, n, d->Ath.rp);
@@ -158,8 +158,7 @@ static int defl_apply(QpdoDev *d, const int *done, double *p_rz) {
     hipLaunchKernelGGL(k_defl_w, dim3(1), dim3(DEFL_MAX), 0, d->stream, done, r, (const double *)d->defl_Sinv, (const double *)d->defl_v,
                        (const int *)d->defl_list, d->defl_t);
     EpiDeflZ e{d->pc_diag, d->pc_r, d->pc_z, p_rz};
-    if (done) launch_spmv_pcg(d, d->Ath, d->defl_t, e, true);
-    else launch_spmv(d, d->Ath, d->defl_t, e, true);
+    launch_spmv(d, d->Ath, d->defl_t, e, true, done);
     d->st.spmv_calls--; d->st.spmv_bytes -= (int64_t)d->Ath.alg_bytes();     // not one of the big products
     return spmv_pgrid(d->Ath);
 }
@@ -198,11 +197,11 @@ static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const 
     if (!dist) {
         const bool f32 = d->inner_f32 && d->Atc.use_slab && d->Arc.use_slab && d->Atc.vsm32 && d->Arc.vsm32 && d->Atc.i16sm && d->Arc.i16sm;
         if (f32) launch_spmv_slab32(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, done2);
-        else launch_spmv_pcg(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, true, done2);
+        else launch_spmv(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, true, done2);
         // HIP-event sample of the dominant kernel (the A_c product), taken mid-batch by the caller's choice of `sample`
         if (sample) (void)hipEventRecord(d->ev0, d->stream);
         if (f32) launch_spmv_slab32(d, d->Arc, d->tmp_n, EpiSchurW{d->dc, u, w}, done2);
-        else launch_spmv_pcg(d, d->Arc, d->tmp_n, EpiSchurW{d->dc, u, w}, false, done2);
+        else launch_spmv(d, d->Arc, d->tmp_n, EpiSchurW{d->dc, u, w}, false, done2);
         if (sample) (void)hipEventRecord(d->ev1, d->stream);
         *fcnt = spmv_pgrid(d->Atc);
         return 0;
@@ -286,7 +285,7 @@ static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
     LAUNCH(k_axpy_const, g, n, (const double *)d->qdiag, d->sigma_f, d->pc_diag);                  // Dq
     // inner diagonal Sd_i = 1/d_i + sum_j A_ij^2 / Dq_j over this rank's compact rows (partitioned: no exchange)
     if (kl > 0) {
-        DISPATCH_TPR(d->Ar, k_schur_diag, (d->Ar.use_slab ? 2048 : spmv_grid(d->Ar, d->Ar.tpr, false)), kl, d->Arc.rp, d->Arc.ci, d->Arc.val,
+        DISPATCH_TPR(d->Ar, k_schur_diag, (d->Ar.use_slab ? 2048 : spmv_grid(d->Ar, false)), kl, d->Arc.rp, d->Arc.ci, d->Arc.val,
                      (const double *)d->pc_diag, (const double *)d->dc, d->s_diag);
     }
     // Inner tolerance.  An inner residual rho leaves M z - r = A_c' D rho: the error that matters is weighted by D, so
@@ -327,16 +326,16 @@ static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
         if (outer >= SCHUR_OUTER_MAXIT) { if (d->defl_debug) fprintf(stderr, "[schur] k=%d outer cap reached (inner=%d)\n", k, inner); *fallback = 1; return 0; }
         if (dist) {     // K p = sigma_f p + sum over ranks of ( Q_rows p + A_c,loc' (d_c .* A_c,loc p) ), as in the Jacobi path
             HIPCHK(hipMemsetAsync(d->Kp_part, 0, (size_t)n * 8, d->stream));
-            if (kl > 0) launch_spmv_pcg(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false);
-            if (d->nloc > 0) launch_spmv_pcg(d, d->Qs, d->pc_p, EpiAddTo{d->Kp_part, d->n0}, false);
-            if (kl > 0) launch_spmv_pcg(d, d->Atc, d->tc, EpiAddTo{d->Kp_part, 0}, false);
+            if (kl > 0) launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
+            if (d->nloc > 0) launch_spmv(d, d->Qs, d->pc_p, EpiAddTo{d->Kp_part, d->n0}, false, done);
+            if (kl > 0) launch_spmv(d, d->Atc, d->tc, EpiAddTo{d->Kp_part, 0}, false, done);
             int rcx = comm_allreduce(d, d->Kp_part, (size_t)n, 0); if (rcx) return rcx;
             hipLaunchKernelGGL(k_pcg_dist_finish, dim3(g), dim3(BLK), 0, d->stream, n, done, (const double *)d->Kp_part, (const double *)d->pc_p,
                                d->sigma_f, d->pc_Kp, P + P_PKP * PGRID);
         } else {
-        launch_spmv_pcg(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false);
-        launch_spmv_pcg(d, d->Qf, d->pc_p, EpiPcgQ{d->pc_p, d->sigma_f, d->pc_Kp}, false);
-        launch_spmv_pcg(d, d->Atc, d->tc, EpiPcgAt{d->pc_p, d->pc_Kp, P + P_PKP * PGRID}, true);
+        launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
+        launch_spmv(d, d->Qf, d->pc_p, EpiPcgQ{d->pc_p, d->sigma_f, d->pc_Kp}, false, done);
+        launch_spmv(d, d->Atc, d->tc, EpiPcgAt{d->pc_p, d->pc_Kp, P + P_PKP * PGRID}, true, done);
         }
         LAUNCH(k_pcg_update, g, n, (const Ctrl *)d->ctrl, (const double *)(P + P_PKP * PGRID), pKp_cnt, (const double *)d->pc_p, (const double *)d->pc_Kp,
                (const double *)d->pc_diag, d->dx, d->pc_r, d->pc_z, P + P_RZ * PGRID, P + P_RR * PGRID,
@@ -421,14 +420,14 @@ static int pcg_solve(QpdoDev *d, int *iters_out) {
     const bool dist = d->comm.active;
     if (!defl && dist) {   // sum_i A_ij^2 d_i over the local rows, summed over ranks, plus Q_jj + sigma_f
         if (k > 0) {
-            const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, d->At.tpr, false);
+            const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, false);
             DISPATCH_TPR(d->At, k_jacobi_diag, gAt, n, d->Atc.rp, d->Atc.ci, d->Atc.val, (const double *)d->dc, (const double *)d->zeros_n, 0.0, d->dist_tmp);
         } else HIPCHK(hipMemsetAsync(d->dist_tmp, 0, (size_t)n * 8, d->stream));
         rc = comm_allreduce(d, d->dist_tmp, (size_t)n, 0); if (rc) return rc;
         LAUNCH(k_add3, vgrid(n), n, (const double *)d->dist_tmp, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
     } else if (!defl) {   // Jacobi diagonal: Q_jj + sigma_f + sum_i A_ij^2 d_i
         if (k > 0) {
-            const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, d->At.tpr, false);
+            const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, false);
             DISPATCH_TPR(d->At, k_jacobi_diag, gAt, n, d->Atc.rp, d->Atc.ci, d->Atc.val, (const double *)d->dc, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
         } else {
             LAUNCH(k_axpy_const, vgrid(n), n, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
@@ -450,23 +449,23 @@ static int pcg_solve(QpdoDev *d, int *iters_out) {
         if (dist) {
             // K p = sigma_f p + sum over ranks of ( Q_rows p  [rows n0..]  +  A_c,loc' (d_c .* A_c,loc p) )
             HIPCHK(hipMemsetAsync(d->Kp_part, 0, (size_t)n * 8, d->stream));
-            if (k > 0) launch_spmv_pcg(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false);
+            if (k > 0) launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
             if (sample) (void)hipEventRecord(d->ev0, d->stream);
-            if (d->nloc > 0) launch_spmv_pcg(d, d->Qs, d->pc_p, EpiAddTo{d->Kp_part, d->n0}, false);
+            if (d->nloc > 0) launch_spmv(d, d->Qs, d->pc_p, EpiAddTo{d->Kp_part, d->n0}, false, done);
             if (sample) (void)hipEventRecord(d->ev1, d->stream);
-            if (k > 0) launch_spmv_pcg(d, d->Atc, d->tc, EpiAddTo{d->Kp_part, 0}, false);
+            if (k > 0) launch_spmv(d, d->Atc, d->tc, EpiAddTo{d->Kp_part, 0}, false, done);
             int rcx = comm_allreduce(d, d->Kp_part, (size_t)n, 0); if (rcx) return rcx;
             hipLaunchKernelGGL(k_pcg_dist_finish, dim3(g), dim3(BLK), 0, d->stream, n, done, (const double *)d->Kp_part, (const double *)d->pc_p,
                                d->sigma_f, d->pc_Kp, P + P_PKP * PGRID);
         } else if (k > 0) {
-            launch_spmv_pcg(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false);
+            launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
             if (sample) (void)hipEventRecord(d->ev0, d->stream);
-            launch_spmv_pcg(d, d->Qf, d->pc_p, EpiPcgQ{d->pc_p, d->sigma_f, d->pc_Kp}, false);
+            launch_spmv(d, d->Qf, d->pc_p, EpiPcgQ{d->pc_p, d->sigma_f, d->pc_Kp}, false, done);
             if (sample) (void)hipEventRecord(d->ev1, d->stream);
-            launch_spmv_pcg(d, d->Atc, d->tc, EpiPcgAt{d->pc_p, d->pc_Kp, P + P_PKP * PGRID}, true);
+            launch_spmv(d, d->Atc, d->tc, EpiPcgAt{d->pc_p, d->pc_Kp, P + P_PKP * PGRID}, true, done);
         } else {
             if (sample) (void)hipEventRecord(d->ev0, d->stream);
-            launch_spmv_pcg(d, d->Qf, d->pc_p, EpiPcgQdot{d->pc_p, d->sigma_f, d->pc_Kp, P + P_PKP * PGRID}, true);
+            launch_spmv(d, d->Qf, d->pc_p, EpiPcgQdot{d->pc_p, d->sigma_f, d->pc_Kp, P + P_PKP * PGRID}, true, done);
             if (sample) (void)hipEventRecord(d->ev1, d->stream);
         }
         LAUNCH(k_pcg_update, g, n, d->ctrl, P + P_PKP * PGRID, pKp_cnt, d->pc_p, d->pc_Kp, d->pc_diag, d->dx, d->pc_r, d->pc_z,

@@ -338,7 +338,7 @@ int qdev_scale_data(QpdoDev *d, int iters, int use_Qx, double *D_host, double *E
     const int n = d->n, m = d->m;
     LAUNCH(k_fill, vgrid(n), n, 1.0, d->D);
     LAUNCH(k_fill, vgrid(m), m, 1.0, d->E);
-    const int gAt = spmv_grid(d->At, d->At.tpr, false), gAr = spmv_grid(d->Ar, d->Ar.tpr, false);
+    const int gAt = spmv_grid(d->At, false), gAr = spmv_grid(d->Ar, false);
     for (int it = 0; it < iters; it++) {
         // column norms of A = row norms of CSR(A'); row norms of A = row norms of CSR(A)
         DISPATCH_TPR(d->At, k_row_absmax, gAt, n, d->At.rp, d->At.val, d->tmp_n);
@@ -356,7 +356,7 @@ int qdev_scale_data(QpdoDev *d, int iters, int use_Qx, double *D_host, double *E
         DISPATCH_TPR(d->At, k_scale_rows_cols, gAt, n, d->At.rp, d->At.ci, d->At.val, (const double *)nullptr, (const double *)(d->tmp_m + d->m0),
                      (const double *)d->tmp_n, (const double *)nullptr);
     }
-    const int gQ = spmv_grid(d->Qf, d->Qf.tpr, false);
+    const int gQ = spmv_grid(d->Qf, false);
     DISPATCH_TPR(d->Qf, k_scale_sym, gQ, n, d->Qf.rp, d->Qf.ci, d->Qf.val, (const double *)d->D);
     if (d->comm.active && d->Qs.nnz) hipLaunchKernelGGL(k_scale_sym_rows, dim3(vgrid(d->nloc)), dim3(BLK), 0, d->stream, d->nloc, d->n0, d->Qs.rp, d->Qs.ci, d->Qs.val, (const double *)d->D);
     d->qdiag_valid = 0; d->dense_valid = 0; d->dense_factored = 0;

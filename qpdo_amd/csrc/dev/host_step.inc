@@ -41,7 +41,7 @@ static int newton_finish_step(QpdoDev *d, int proximal, double sigma, bool redo,
         // Q dx and A dx in one launch (spmv.inc k_spmv_pair): A's blocks first; Q's block partials are indexed by blockIdx.x, so their
         // pointers are shifted back by A's grid -- the same grids, the same partials as the two launches
         if (redo) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_NL, 0);      // (the first time it is still zero from k_ctrl_clear_pass)
-        const int gA = spmv_grid(d->Ar, d->Ar.tpr, true), gQ = spmv_grid(d->Qf, d->Qf.tpr, true);
+        const int gA = spmv_grid(d->Ar, true), gQ = spmv_grid(d->Qf, true);
         EpiQdx eq{d->dx, d->df, sigma, proximal, d->Qdx, d->part + P_DXQDX * PGRID - gA, d->part + P_DXDF * PGRID - gA};
         hipLaunchKernelGGL((k_spmv_pair<EpiAdxLs, EpiQdx>), dim3(gA + gQ), dim3(BLK), 0, d->stream, gA, d->Ar.tpr, d->Ar.nrows, (const int *)d->Ar.rp,
                            (const int *)d->Ar.ci, (const double *)d->Ar.val, (const double *)d->dx, e, d->Qf.tpr, d->Qf.nrows, (const int *)d->Qf.rp,
@@ -178,7 +178,7 @@ static int ahead_enqueue_step(QpdoDev *d, int proximal, double sigma) {
     e.Adx = d->Adx; e.dy = d->dy; e.delta = d->ls_delta; e.alpha = d->ls_alpha; e.key = d->ls_key[0]; e.idx = d->ls_idx[0];
     e.p_eta = d->part + P_ETA_M * PGRID; e.p_beta = d->part + P_BETA_M * PGRID; e.p_a0 = d->part + P_A0 * PGRID; e.p_b0 = d->part + P_B0 * PGRID;
     e.ctrl = d->ctrl;
-    const int gA = spmv_grid(d->Ar, d->Ar.tpr, true), gQ = spmv_grid(d->Qf, d->Qf.tpr, true);
+    const int gA = spmv_grid(d->Ar, true), gQ = spmv_grid(d->Qf, true);
     EpiQdx eq{d->dx, d->df, sigma, proximal, d->Qdx, d->part + P_DXQDX * PGRID - gA, d->part + P_DXDF * PGRID - gA};
     hipLaunchKernelGGL((k_spmv_pair<EpiAdxLs, EpiQdx>), dim3(gA + gQ), dim3(BLK), 0, d->stream, gA, d->Ar.tpr, d->Ar.nrows, (const int *)d->Ar.rp,
                        (const int *)d->Ar.ci, (const double *)d->Ar.val, (const double *)d->dx, e, d->Qf.tpr, d->Qf.nrows, (const int *)d->Qf.rp,
@@ -394,7 +394,7 @@ int qdev_dual_infeasibility_and_mu(QpdoDev *d, int do_dinf, int proximal, double
         LAUNCH(k_sub_clear, gn, n, (const double *)d->x, (const double *)d->xbar, d->dx, d->ctrl);            // qpdo.c:383
         if (!d->Qf.use_slab && !d->Ar.use_slab && m > 0) {
             // Q dx (qpdo.c:385, no sigma) and A dx (qpdo.c:387) in one launch (k_spmv_pair: each product on its own grid, the same lane groups)
-            const int gA = spmv_grid(d->Ar, d->Ar.tpr, false), gQ = spmv_grid(d->Qf, d->Qf.tpr, false);
+            const int gA = spmv_grid(d->Ar, false), gQ = spmv_grid(d->Qf, false);
             hipLaunchKernelGGL((k_spmv_pair<EpiStore, EpiStore>), dim3(gA + gQ), dim3(BLK), 0, d->stream, gA, d->Ar.tpr, d->Ar.nrows, (const int *)d->Ar.rp,
                                (const int *)d->Ar.ci, (const double *)d->Ar.val, (const double *)d->dx, EpiStore{d->Adx}, d->Qf.tpr, d->Qf.nrows, (const int *)d->Qf.rp,
                                (const int *)d->Qf.ci, (const double *)d->Qf.val, (const double *)d->dx, EpiStore{d->Qdx});

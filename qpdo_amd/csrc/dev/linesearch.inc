@@ -278,9 +278,9 @@ __global__ __launch_bounds__(1024) void k_ls_small(Ctrl *ctrl, const double *__r
     if (spec && ctrl->cnt[C_SPEC_SKIP]) return;                        // launch-ahead (vector.inc SpecArgs): this pass is not a Newton step
     if (blockIdx.x > 0) {
         // launch-ahead route: A'dy of this step (needed by the iterate update only, not by the search) as extra workgroups of this launch;
-        // the lane groups, partial sums and shuffles of k_spmv: the same bits
+        // spmv_rows, the row loop of k_spmv: the same bits
         EpiStore e{lp.y};
-        spmv_rows_rt((int)blockIdx.x - 1, (int)gridDim.x - 1, lp.tpr, lp.nrows, lp.rp, lp.ci, lp.val, lp.x, e, 1024);
+        spmv_rows((int)blockIdx.x - 1, (int)gridDim.x - 1, lp.tpr, lp.nrows, lp.rp, lp.ci, lp.val, lp.x, e, 1024);
         return;
     }
     constexpr int NSUB = LS_SMALL_MAX / LS_TILE;                       // 8 sub-blocks of 1024 items = two "virtual threads" per thread

@@ -11,30 +11,42 @@ __device__ __forceinline__ double group_sum(double v) {
     return v;
 }
 
-template <int TPR, class Epi>
-__global__ __launch_bounds__(256) void k_spmv(int nrows, const int *__restrict__ rp, const int *__restrict__ ci,
-                                              const double *__restrict__ val, const double *__restrict__ x, Epi epi) {
-    __shared__ double sm[32];
-    const int lane = threadIdx.x % TPR;
-    const int group = (blockIdx.x * BLK + threadIdx.x) / TPR;
-    const int ngroups = gridDim.x * (BLK / TPR);
+// The CSR row loop of every plain product (k_spmv, and the products folded into k_spmv_pair, k_ls_small and k_dense_assemble):
+// block `bid` of `nblk` blocks of `bs` threads, lane groups of `tpr` lanes, two partial sums, the tail added to s0, the shuffle
+// tree, epi.row in lane 0.  tpr is a std::integral_constant (k_spmv<TPR>) or a run-time int (the folded products: one
+// instantiation serves every matrix); the operations and their order are the same either way, so every caller gets the same bits.
+template <class Tpr, class Epi>
+__device__ __forceinline__ void spmv_rows(int bid, int nblk, Tpr tpr, int nrows, const int *__restrict__ rp, const int *__restrict__ ci,
+                                          const double *__restrict__ val, const double *__restrict__ x, Epi &epi, int bs = BLK) {
+    const int lane = threadIdx.x & (tpr - 1);
+    const int group = (bid * bs + threadIdx.x) / tpr;
+    const int ngroups = nblk * (bs / tpr);
     for (int row = group; row < nrows; row += ngroups) {
         double s = 0.0;
         if (!epi.skip(row)) {
             const int beg = rp[row], end = rp[row + 1];
             double s0 = 0.0, s1 = 0.0;
             int k = beg + lane;
-            for (; k + TPR < end; k += 2 * TPR) {
-                const double v0 = val[k], v1 = val[k + TPR];
-                const int c0 = ci[k], c1 = ci[k + TPR];
+            for (; k + tpr < end; k += 2 * tpr) {
+                const double v0 = val[k], v1 = val[k + tpr];
+                const int c0 = ci[k], c1 = ci[k + tpr];
                 s0 += v0 * x[c0];
                 s1 += v1 * x[c1];
             }
             if (k < end) s0 += val[k] * x[ci[k]];
-            s = group_sum<TPR>(s0 + s1);
+            s = s0 + s1;
+            for (int o = tpr / 2; o > 0; o >>= 1) s += __shfl_down(s, o, tpr);
         }
         if (lane == 0) epi.row(row, s);
     }
+}
+// done: the PCG's latch (every thread leaves at once when the solver has converged), or nullptr
+template <int TPR, class Epi>
+__global__ __launch_bounds__(256) void k_spmv(const int *__restrict__ done, int nrows, const int *__restrict__ rp, const int *__restrict__ ci,
+                                              const double *__restrict__ val, const double *__restrict__ x, Epi epi) {
+    __shared__ double sm[32];
+    if (done && *done) return;
+    spmv_rows(blockIdx.x, gridDim.x, std::integral_constant<int, TPR>(), nrows, rp, ci, val, x, epi);
     epi.finish(sm);
 }
 
@@ -49,7 +61,7 @@ __global__ __launch_bounds__(256) void k_spmv(int nrows, const int *__restrict__
 // ------------------------------------------------------------------------------------------------
 static const int SLAB_THREADS = 1024;
 #define SLAB_UNR 8               // 16-byte loads in flight per lane
-static int g_slab_tpr = 16;     // lanes per row segment (QPDO_SLAB_TPR: 8 | 16 | 32; 16 x 16-byte loads measured best at C4)
+static constexpr int SLAB_TPR = 16;     // lanes per row segment (16 x 16-byte loads measured best at C4; 8 and 32: tools/lab/slab_lab.hip)
 // OVL (the default; QPDO_SLAB_OVERLAP=0 keeps the old schedule): the slab boundaries are hidden behind matrix loads already in flight.
 // Without it, every CU's HBM queue drains at each boundary -- the last segments, two barriers, the x-slice copy from L2 and one
 // HBM miss before the new slab's first data.  With it, each lane group issues the value and index loads of ITS first row of the
@@ -59,11 +71,12 @@ static int g_slab_tpr = 16;     // lanes per row segment (QPDO_SLAB_TPR: 8 | 16 
 // The x slice is copied with 16-byte global_load_lds (dst = wave base + 16 * lane), so the copy costs one L2 round trip, not one
 // per 16 KB.  (Lab, tools/lab/slab_lab.hip LAB_OVL=1, round 6: the early loads alone do not pay at the compact shapes -- the
 // register copy waits for them in order; with the async copy: -4 % at k = 66 000, -3.5 % at 73 000, -1 % on the full matrix.)
-template <class Epi, bool I16, int TPR, bool OVL>
+template <class Epi, bool I16, bool OVL>
 __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                     int rows_per_wg, const int2 *__restrict__ seg, const int *__restrict__ cism,
                                                     const unsigned short *__restrict__ i16sm,
                                                     const double *__restrict__ vsm, const double *__restrict__ x, Epi epi) {
+    constexpr int TPR = SLAB_TPR;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double sm[32];
     __shared__ int next_row;
@@ -199,7 +212,7 @@ template <class Epi>
 __global__ __launch_bounds__(1024) void k_spmv_slab32(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                       int rows_per_wg, const int2 *__restrict__ seg, const unsigned short *__restrict__ i16sm,
                                                       const float *__restrict__ vsm32, const double *__restrict__ x, Epi epi) {
-    constexpr int TPR = 16;
+    constexpr int TPR = SLAB_TPR;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double sm[32];
     __shared__ int next_row;
@@ -485,95 +498,65 @@ struct EpiResid {                          // r = rhs - (Kp + A' t), ||r||inf ->
     __device__ void finish(double *sm) { block_max_to(mx, &ctrl->nrm[slot], sm); }
 };
 
-static inline int spmv_grid(const DevCsr &M, int tpr, bool partials) {
+static inline int spmv_grid(const DevCsr &M, bool partials) {
     if (M.use_slab) return M.slab_grid;
-    long long groups_per_block = BLK / tpr;
+    long long groups_per_block = BLK / M.tpr;
     long long g = (M.nrows + groups_per_block - 1) / groups_per_block;
     long long cap = partials ? PGRID : 4096;
     if (g > cap) g = cap;
     if (g < 1) g = 1;
     return (int)g;
 }
+// number of blocks a partial-emitting spmv launch uses (consumers need it)
+static inline int spmv_pgrid(const DevCsr &M) { return spmv_grid(M, true); }
+// KERNEL<M.tpr> on GRID blocks of BLK threads (further template arguments, such as k_spmv's Epi, are deduced from the arguments)
+#define DISPATCH_TPR(M, KERNEL, GRID, ...)                                                                  \
+    switch ((M).tpr) {                                                                                      \
+        case 4:  hipLaunchKernelGGL((KERNEL<4>),  dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
+        case 8:  hipLaunchKernelGGL((KERNEL<8>),  dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
+        case 16: hipLaunchKernelGGL((KERNEL<16>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
+        case 32: hipLaunchKernelGGL((KERNEL<32>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL((KERNEL<64>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
+    }
 // (re)build the slab-major image of M from its row-major arrays and slab pointers
 static void slab_major_build(QpdoDev *d, const DevCsr &M);
-template <class Epi>
-static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done) {
-    const size_t lds = ((size_t)M.W + (size_t)M.rows_per_wg) * sizeof(double);
-    static thread_local bool attr_set = false;   // per instantiation
-    if (!attr_set) {
-#define SLAB_ATTR(I16, T, O) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spmv_slab<Epi, I16, T, O>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512)
-        SLAB_ATTR(false, 8, false); SLAB_ATTR(false, 16, false); SLAB_ATTR(false, 32, false); SLAB_ATTR(true, 8, false); SLAB_ATTR(true, 16, false); SLAB_ATTR(true, 32, false);
-        SLAB_ATTR(false, 8, true); SLAB_ATTR(false, 16, true); SLAB_ATTR(false, 32, true); SLAB_ATTR(true, 8, true); SLAB_ATTR(true, 16, true); SLAB_ATTR(true, 32, true);
-#undef SLAB_ATTR
-        attr_set = true;
-    }
+// One launch of the slab kernel K with what every such launch needs: the kernel's LDS limit (set once per kernel and host thread),
+// the slab-major image rebuilt when the row-major arrays have changed, LDS for the x slice and the row sums, the statistics.
+template <auto K, class... Args>
+static void launch_slab(QpdoDev *d, const DevCsr &M, Args... args) {
+    static thread_local bool attr_set = false;   // per kernel
+    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr_set = true; }
     if (M.sm_dirty) slab_major_build(d, M);
-#define SLAB_GO(I16, T, O) hipLaunchKernelGGL((k_spmv_slab<Epi, I16, T, O>), dim3(M.slab_grid), dim3(SLAB_THREADS), lds, d->stream, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, M.vsm, x, epi)
-#define SLAB_TPR(I16, O) { if (g_slab_tpr == 8) SLAB_GO(I16, 8, O); else if (g_slab_tpr == 32) SLAB_GO(I16, 32, O); else SLAB_GO(I16, 16, O); }
-    if (M.slab_ovl) { if (M.i16sm) SLAB_TPR(true, true) else SLAB_TPR(false, true) }
-    else            { if (M.i16sm) SLAB_TPR(true, false) else SLAB_TPR(false, false) }
-#undef SLAB_TPR
-#undef SLAB_GO
+    const size_t lds = ((size_t)M.W + (size_t)M.rows_per_wg) * sizeof(double);
+    hipLaunchKernelGGL(K, dim3(M.slab_grid), dim3(SLAB_THREADS), lds, d->stream, args...);
     d->st.spmv_calls++;
     d->st.spmv_bytes += (int64_t)M.alg_bytes();
+}
+template <class Epi>
+static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done) {
+#define SLAB_GO(I16, OVL) launch_slab<k_spmv_slab<Epi, I16, OVL>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, M.vsm, x, epi)
+    if (M.slab_ovl) { if (M.i16sm) SLAB_GO(true, true); else SLAB_GO(false, true); }
+    else            { if (M.i16sm) SLAB_GO(true, false); else SLAB_GO(false, false); }
+#undef SLAB_GO
 }
 template <class Epi>
 static void launch_spmv_slab32(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done) {
-    const size_t lds = ((size_t)M.W + (size_t)M.rows_per_wg) * sizeof(double);
-    static thread_local bool attr_set = false;   // per instantiation
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spmv_slab32<Epi>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr_set = true; }
-    if (M.sm_dirty) slab_major_build(d, M);
-    hipLaunchKernelGGL((k_spmv_slab32<Epi>), dim3(M.slab_grid), dim3(SLAB_THREADS), lds, d->stream, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg,
-                       (const int2 *)M.seg, (const unsigned short *)M.i16sm, (const float *)M.vsm32, x, epi);
-    d->st.spmv_calls++;
-    d->st.spmv_bytes += (int64_t)M.alg_bytes();
+    launch_slab<k_spmv_slab32<Epi>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.i16sm, M.vsm32, x, epi);
 }
+// y = M x with the kernel M was set up for; done: the PCG's latch (the product is skipped once it is set), or nullptr
 template <class Epi>
-static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, bool partials) {
-    const int g = spmv_grid(M, M.tpr, partials);
-    if (M.use_slab) { launch_spmv_slab(d, M, x, epi, (const int *)nullptr); return; }
-    switch (M.tpr) {
-        case 4:  hipLaunchKernelGGL((k_spmv<4, Epi>),  dim3(g), dim3(BLK), 0, d->stream, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        case 8:  hipLaunchKernelGGL((k_spmv<8, Epi>),  dim3(g), dim3(BLK), 0, d->stream, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        case 16: hipLaunchKernelGGL((k_spmv<16, Epi>), dim3(g), dim3(BLK), 0, d->stream, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        case 32: hipLaunchKernelGGL((k_spmv<32, Epi>), dim3(g), dim3(BLK), 0, d->stream, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        default: hipLaunchKernelGGL((k_spmv<64, Epi>), dim3(g), dim3(BLK), 0, d->stream, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-    }
+static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, bool partials, const int *done = nullptr) {
+    if (M.use_slab) { launch_spmv_slab(d, M, x, epi, done); return; }
+    const int g = spmv_grid(M, partials);
+    DISPATCH_TPR(M, k_spmv, g, done, M.nrows, M.rp, M.ci, M.val, x, epi);
     d->st.spmv_calls++;
     d->st.spmv_bytes += (int64_t)M.alg_bytes();
 }
-// number of blocks a partial-emitting spmv launch uses (consumers need it)
-static inline int spmv_pgrid(const DevCsr &M) { return spmv_grid(M, M.tpr, true); }
 
 // Two independent products in ONE launch (small problems: a launch is ~4-5 us whatever it computes, and Q dx and A dx of a Newton step
 // depend on nothing of each other): blocks [0, gA) take the first with its own grid, the rest the second.  Lanes per row are run-time
-// values here (the same shuffles in the same order as group_sum<TPR>), so one instantiation serves every pair of matrices.  The second
-// epilogue indexes its block partials by blockIdx.x: the host passes those pointers shifted back by gA.
-template <class Epi>
-__device__ __forceinline__ void spmv_rows_rt(int bid, int nblk, int tpr, int nrows, const int *__restrict__ rp, const int *__restrict__ ci,
-                                             const double *__restrict__ val, const double *__restrict__ x, Epi &epi, int bs = BLK) {
-    const int lane = threadIdx.x & (tpr - 1);
-    const int group = (bid * bs + threadIdx.x) / tpr;            // bs: threads per block of the launch this runs in
-    const int ngroups = nblk * (bs / tpr);
-    for (int row = group; row < nrows; row += ngroups) {
-        double s = 0.0;
-        if (!epi.skip(row)) {
-            const int beg = rp[row], end = rp[row + 1];
-            double s0 = 0.0, s1 = 0.0;
-            int k = beg + lane;
-            for (; k + tpr < end; k += 2 * tpr) {
-                const double v0 = val[k], v1 = val[k + tpr];
-                const int c0 = ci[k], c1 = ci[k + tpr];
-                s0 += v0 * x[c0];
-                s1 += v1 * x[c1];
-            }
-            if (k < end) s0 += val[k] * x[ci[k]];
-            s = s0 + s1;
-            for (int o = tpr / 2; o > 0; o >>= 1) s += __shfl_down(s, o, tpr);
-        }
-        if (lane == 0) epi.row(row, s);
-    }
-}
+// values here (spmv_rows with an int width), so one instantiation serves every pair of matrices.  The second epilogue indexes its block
+// partials by blockIdx.x: the host passes those pointers shifted back by gA.
 template <class EpiA, class EpiB>
 __global__ __launch_bounds__(256) void k_spmv_pair(int gA, int tprA, int nrowsA, const int *__restrict__ rpA, const int *__restrict__ ciA,
                                                    const double *__restrict__ valA, const double *__restrict__ xA, EpiA epiA, int tprB, int nrowsB,
@@ -581,53 +564,8 @@ __global__ __launch_bounds__(256) void k_spmv_pair(int gA, int tprA, int nrowsA,
                                                    const double *__restrict__ xB, EpiB epiB, const int *__restrict__ skip = nullptr) {
     __shared__ double sm[32];
     if (skip && *skip) return;                                      // launch-ahead (vector.inc SpecArgs): this pass is not a Newton step
-    if ((int)blockIdx.x < gA) { spmv_rows_rt(blockIdx.x, gA, tprA, nrowsA, rpA, ciA, valA, xA, epiA); epiA.finish(sm); }
-    else { spmv_rows_rt(blockIdx.x - gA, gridDim.x - gA, tprB, nrowsB, rpB, ciB, valB, xB, epiB); epiB.finish(sm); }
-}
-
-// PCG variant: identical body, but every thread leaves at once when the solver has converged.
-template <int TPR, class Epi>
-__global__ __launch_bounds__(256) void k_spmv_pcg(const int *__restrict__ done, int nrows, const int *__restrict__ rp,
-                                                  const int *__restrict__ ci, const double *__restrict__ val,
-                                                  const double *__restrict__ x, Epi epi) {
-    __shared__ double sm[32];
-    if (*done) return;
-    const int lane = threadIdx.x % TPR;
-    const int group = (blockIdx.x * BLK + threadIdx.x) / TPR;
-    const int ngroups = gridDim.x * (BLK / TPR);
-    for (int row = group; row < nrows; row += ngroups) {
-        double s = 0.0;
-        if (!epi.skip(row)) {
-            const int beg = rp[row], end = rp[row + 1];
-            double s0 = 0.0, s1 = 0.0;
-            int k = beg + lane;
-            for (; k + TPR < end; k += 2 * TPR) {
-                const double v0 = val[k], v1 = val[k + TPR];
-                const int c0 = ci[k], c1 = ci[k + TPR];
-                s0 += v0 * x[c0];
-                s1 += v1 * x[c1];
-            }
-            if (k < end) s0 += val[k] * x[ci[k]];
-            s = group_sum<TPR>(s0 + s1);
-        }
-        if (lane == 0) epi.row(row, s);
-    }
-    epi.finish(sm);
-}
-template <class Epi>
-static void launch_spmv_pcg(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, bool partials, const int *latch = nullptr) {
-    const int g = spmv_grid(M, M.tpr, partials);
-    const int *done = latch ? latch : &d->ctrl->cnt[C_PCG_DONE];
-    if (M.use_slab) { launch_spmv_slab(d, M, x, epi, done); return; }
-    switch (M.tpr) {
-        case 4:  hipLaunchKernelGGL((k_spmv_pcg<4, Epi>),  dim3(g), dim3(BLK), 0, d->stream, done, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        case 8:  hipLaunchKernelGGL((k_spmv_pcg<8, Epi>),  dim3(g), dim3(BLK), 0, d->stream, done, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        case 16: hipLaunchKernelGGL((k_spmv_pcg<16, Epi>), dim3(g), dim3(BLK), 0, d->stream, done, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        case 32: hipLaunchKernelGGL((k_spmv_pcg<32, Epi>), dim3(g), dim3(BLK), 0, d->stream, done, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-        default: hipLaunchKernelGGL((k_spmv_pcg<64, Epi>), dim3(g), dim3(BLK), 0, d->stream, done, M.nrows, M.rp, M.ci, M.val, x, epi); break;
-    }
-    d->st.spmv_calls++;
-    d->st.spmv_bytes += (int64_t)M.alg_bytes();
+    if ((int)blockIdx.x < gA) { spmv_rows(blockIdx.x, gA, tprA, nrowsA, rpA, ciA, valA, xA, epiA); epiA.finish(sm); }
+    else { spmv_rows(blockIdx.x - gA, gridDim.x - gA, tprB, nrowsB, rpB, ciB, valB, xB, epiB); epiB.finish(sm); }
 }
 
 // row-wise max |a_ij| (Ruiz norms, cholmod_interface.c:162-199) -- one lane group per row
@@ -921,13 +859,3 @@ __global__ __launch_bounds__(256) void k_compact_rows_bits(int nrows, const int 
         }
     }
 }
-
-#define DISPATCH_TPR(M, KERNEL, GRID, ...)                                                                  \
-    switch ((M).tpr) {                                                                                      \
-        case 4:  hipLaunchKernelGGL((KERNEL<4>),  dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        case 8:  hipLaunchKernelGGL((KERNEL<8>),  dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        case 16: hipLaunchKernelGGL((KERNEL<16>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        case 32: hipLaunchKernelGGL((KERNEL<32>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((KERNEL<64>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-    }
-
