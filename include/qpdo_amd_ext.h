@@ -17,7 +17,7 @@
  *                    QPDOAmdStats.hybrid_pcg_passes counts the PCG passes; every numerical PCG failure hands the pass to the dense factor).  "0": off; "1": on from n = 4096; "<budget>" > 1: on from n = 4096 with that budget
  *   QPDO_DENSE_MID   "0": the dense factorization as the multi-launch blocked pipeline of rounds 1-4 instead of ONE launch of tile-owning
  *                    workgroups (k_mid_factor, the default at every order since round 5: n = 1e4 8.4 ms against 13.3 ms).  The
- *                    look-ahead / outer-panel / syrk knobs below act on the multi-launch path only
+ *                    look-ahead below acts on the multi-launch path only
  *   QPDO_CTRL_PUBLISH "0": the per-pass read-back of the control block as hipMemcpyAsync + hipStreamSynchronize instead of a kernel that
  *                    writes the block and a sequence word into coherent pinned memory while the host spins (bounded; default since round 5:
  *                    15.7 -> 9.9 us per read-back).  Only the transport differs: the same bits
@@ -32,13 +32,9 @@
  *                    section 5; read at qpdo_setup; QPDOAmdStats.ahead_steps / ahead_skips).  The same kernels in the same order: the same bits,
  *                    except on a pass whose factor the host-first path would keep (it is refactored: the same matrix)
  *   QPDO_DENSE_LOWRANK  "0": refactor on every weight change, "1": low-rank update of the kept dense factor (default: from n = 9000 up)
- *   QPDO_DENSE_LOOKAHEAD "0": factor on one stream, "1": overlap the next panel with the trailing update (default: from n = 7000 up)
- *   QPDO_DENSE_RESERVE_CUS  CUs left out of the trailing-update stream's mask (default 32; 0 = no mask)
+ *   QPDO_DENSE_LOOKAHEAD "0": factor on one stream, "1": overlap the next panel with the trailing update (default: from n = 7000 up;
+ *                    read at qpdo_setup)
  *   QPDO_DENSE_SOLVE "steps": per-block-step triangular solve kernels instead of the one-launch chained solves
- *   Experiment knobs of the dense factor (every setting leaves the same factor bits):
- *   QPDO_DENSE_OUTER (block columns per outer panel, default 4), QPDO_SYRK_KC (16 | 32), QPDO_SYRK_SWZ ("0": 2-D tile grid instead of
- *   the XCD-aware order), QPDO_DENSE_FPANEL ("1": a whole outer panel in one
- *   launch; slower at present)
  *   QPDO_SETUP_THREADS  host threads of the CSC -> CSR conversions in qpdo_setup (default min(16, cores)); QPDO_SETUP_PROF=1 prints phase times
  *   QPDO_SPMV        "slab" | "plain" (default: LDS-staged slab kernel for matrices >= 192 MB)
  *   QPDO_DEFLATE     "0" disables the heavy-row deflation of the PCG preconditioner

@@ -121,47 +121,27 @@ __global__ __launch_bounds__(64) void k_dense_assemble(int n, int ld, int tile, 
         for (int i = n + lane; i < ld; i += 64) col[i] = 0.0;
     }
 }
-// 64x64x64 product on the matrix cores for one workgroup of 4 waves: wave w owns the 32x32 quadrant
-// (w>>1, w&1) as 2x2 tiles of v_mfma_f64_16x16x4_f64; As/Bs are [k][row] / [k][col] LDS images with a row
-// stride of 80 doubles (the two k-rows a half-wave reads land on disjoint banks).
-// A/B lane map: lane l holds A[l&15][k = l>>4], B[k = l>>4][l&15]; C/D: row = (l>>4) + 4*reg, col = l&15.
-__device__ __forceinline__ void mfma_64x64x64(const double (*As)[80], const double (*Bs)[80], dvec4 acc[2][2], int wr, int wc, int li, int lk) {
-#pragma unroll 4
-    for (int k0 = 0; k0 < DNB; k0 += 4) {
-        const double a0 = As[k0 + lk][wr + li], a1 = As[k0 + lk][wr + 16 + li];
-        const double b0 = Bs[k0 + lk][wc + li], b1 = Bs[k0 + lk][wc + 16 + li];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-}
 __device__ __forceinline__ double lane_bcast(double v, int lane) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_readlane(lo, lane); hi = __builtin_amdgcn_readlane(hi, lane);
     return __hiloint2double(hi, lo);
 }
-// ---- hand-off between workgroups inside one launch (k_ldl_fpanel): 8-byte agent-scope accesses on both sides --------------------
+// ---- hand-off between workgroups inside one launch (k_mid_factor): 8-byte agent-scope accesses on both sides --------------------
 __device__ __forceinline__ double ld_agent(const double *p) {
     return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 __device__ __forceinline__ void st_agent(double *p, double v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-template <bool AG> __device__ __forceinline__ double ld_sel(const double *p) { if (AG) return ld_agent(p); else return *p; }
-template <bool AG> __device__ __forceinline__ void st_sel(double *p, double v) { if (AG) st_agent(p, v); else *p = v; }
 
-// LDL' of a 64x64 diagonal block, eliminated in four 16-column sub-blocks.  Wave 0 factors the 16x16 diagonal sub-block in registers
-// (lanes 0-15 hold the rows of the sub-block, lanes 16-31 the columns of its running inverse -- Gauss-Jordan on the identity, the two
-// roles differing only by selects; one LDS publication per step, no barrier: a single wave), then the rows below and the rest of the block are updated on the
-// matrix cores (X = A L_ss^-T, L = X / D, C -= X L'), and the inverse of the whole block is assembled from the four small inverses by block
-// forward substitution, also on the matrix cores.  (Round 1 eliminated all 64 columns with two waves holding 64 registers per lane: 63
-// dependent-issue FMAs per lane plus a two-wave barrier per step, 0.37 us; here 15 FMAs and no barrier.)  The block sits in LDS throughout:
+// LDL' of a 64x64 diagonal block, eliminated in four 16-column sub-panels (diag64_lds_v2 below); the rest of the block is updated on
+// the matrix cores (C -= X L'), and the inverse of the whole block is assembled from the four 16x16 inverses by block forward
+// substitution, also on the matrix cores.  The block sits in LDS throughout:
 //   T  [64][65]   the block; on exit strictly lower = L, diagonal = D
 //   Ic [10][16][16]  lower 16x16 blocks of L^-1, block (bi, bj) at bi (bi + 1) / 2 + bj, element (r, c) at r*16 + (c ^ r) (bank swizzle)
-//   cb [2][32]    column publication of the 16-wide factorization
-//   Xs [64][17]   X = L D of the current 16-column sub-panel (the exact accumulators, not L times D)
-// 62 720 bytes.
+//   cb [64]       with the first 64 doubles of Xs: the two column buffers of the sub-panel elimination
+//   Xs [64][17]   X = L D of the current 16-column sub-panel (rows >= 16 only)
+// 62 976 bytes.
 static const int DG_TS = DNB + 1;
 static const int DG_LDS = DNB * DG_TS + 10 * 256 + 64 + DNB * 17;          // doubles
 __device__ __forceinline__ int ic_at(int bi, int bj, int r, int c) { return (bi * (bi + 1) / 2 + bj) * 256 + r * 16 + (c ^ r); }
@@ -184,125 +164,17 @@ __device__ long long g_dg_t[32];
 #define DG_T(i) do { } while (0)
 #define DG_T2(i, cond) do { } while (0)
 #endif
-__device__ __forceinline__ void diag64_lds(double *T, double *Ic, double *cbuf, double *Xs, int tid) {
-    const int wave = tid >> 6, l = tid & 63;
-    const int li = l & 15, lk = l >> 4;
-    constexpr int TS = DG_TS;
-#pragma unroll 1
-    for (int s = 0; s < 4; s++) {
-        const int o = 16 * s;
-        if (wave == 0 && l < 32) {
-            const bool is_a = l < 16;
-            const int i = l & 15;
-            double r[16];
-#pragma unroll
-            for (int c = 0; c < 16; c++) {
-                const double t = T[(o + i) * TS + o + c];
-                r[c] = is_a ? ((c <= i) ? t : 0.0) : ((c == i) ? 1.0 : 0.0);
-            }
-            // Step j: s_j = r[j] / d_j, r[c] -= s_j v_c for c > j with v = column j, published through LDS by lanes 0-15.  One step costs
-            // ~165 ns (tools/lab/diag_lab.hip): the chain FMA -> LDS write -> LDS read -> reciprocal -> FMA; taking the pivot from lane j's
-            // register (v_readlane) to invert it during the LDS round trip, publishing column j+1 before the other 14 updates of step j, or
-            // two pivots per LDS round trip (every lane applying step j to column j+1 itself: same bits) measured the same or slower: a
-            // step is ~180 cycles of round trip plus ~9 cycles per dependent-issue fp64 operation of the one wave.
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                double *cb = cbuf + (j & 1) * 32;
-                cb[l] = r[j];                                        // lanes 0-15: column j of the sub-block, rows >= j current
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");       // one wave: its LDS operations complete in order
-                // 1/d_j: hardware reciprocal + two Newton steps (full double accuracy for the well-scaled pivots of an SPD block)
-                const double dj = cb[j];
-                double inv = __builtin_amdgcn_rcp(dj);
-                inv = fma(fma(-dj, inv, 1.0), inv, inv);
-                inv = fma(fma(-dj, inv, 1.0), inv, inv);
-                const double sj = r[j] * inv;
-#pragma unroll
-                for (int c = j + 1; c < 16; c++) r[c] = fma(-sj, cb[c], r[c]);
-                r[j] = (is_a && i > j) ? sj : r[j];
-                // pin the updated row here: left alone the compiler computes only r[j+1] now and defers the other updates, keeping the
-                // published columns of all 16 steps alive (256 registers and spills)
-#pragma unroll
-                for (int c = j + 1; c < 16; c++) asm volatile("" : "+v"(r[c]));
-            }
-#pragma unroll
-            for (int c = 0; c < 16; c++) {
-                // lanes 0-15: L below the diagonal, D on it; lanes 16-31: column i of L_ss^-1 (one predicated store, no branches)
-                double *dst = is_a ? &T[(o + i) * TS + o + c] : &Ic[ic_at(s, s, c, i)];
-                const double val = is_a ? r[c] : ((c >= i) ? r[c] : 0.0);
-                if (!is_a || c <= i) *dst = val;
-            }
-        }
-        __syncthreads();
-        DG_T(2 + 3 * s);
-        if (s == 3) break;
-        // rows below: L = (A L_ss^-T) / D, row block rb on wave rb
-        if (wave > s) {
-            const int rb = wave;
-            dvec4 acc = (dvec4){0.0, 0.0, 0.0, 0.0};
-            acc = mfma16([&](int r, int k) { return T[(rb * 16 + r) * TS + o + k]; },
-                         [&](int k, int c) { return Ic[ic_at(s, s, c, k)]; }, acc, li, lk);
-            const double dcol = T[(o + li) * TS + o + li];
-#pragma unroll
-            for (int v = 0; v < 4; v++) { const int row = rb * 16 + lk + 4 * v; Xs[row * 17 + li] = acc[v]; T[row * TS + o + li] = acc[v] / dcol; }
-        }
-        __syncthreads();
-        DG_T(3 + 3 * s);
-        // the rest of the block: C(bi, bj) -= X(bi) L(bj)', s < bj <= bi <= 3, dealt over the waves
-        {
-            int q = 0;
-#pragma unroll 1
-            for (int bi = s + 1; bi < 4; bi++)
-#pragma unroll 1
-                for (int bj = s + 1; bj <= bi; bj++, q++) {
-                    if ((q & 3) != wave) continue;
-                    dvec4 acc = (dvec4){0.0, 0.0, 0.0, 0.0};
-                    acc = mfma16([&](int r, int k) { return Xs[(bi * 16 + r) * 17 + k]; },
-                                 [&](int k, int c) { return T[(bj * 16 + c) * TS + o + k]; }, acc, li, lk);
-#pragma unroll
-                    for (int v = 0; v < 4; v++) { double *t = &T[(bi * 16 + lk + 4 * v) * TS + bj * 16 + li]; *t = *t - acc[v]; }
-                }
-        }
-        __syncthreads();
-        DG_T(4 + 3 * s);
-    }
-    // inverse of the block from the four small ones: X(bi, bj) = - L_bibi^-1 sum_{k=bj}^{bi-1} L(bi, k) X(k, bj), by block diagonals;
-    // the sum is staged in the destination block itself (a wave's reads of it precede its writes)
-#pragma unroll 1
-    for (int dgl = 1; dgl < 4; dgl++) {
-        const int bi = dgl + wave, bj = wave;
-        if (bi < 4) {
-            dvec4 acc = (dvec4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-            for (int k = bj; k < bi; k++)
-                acc = mfma16([&](int r, int kk) { return T[(bi * 16 + r) * TS + k * 16 + kk]; },
-                             [&](int kk, int c) { return Ic[ic_at(k, bj, kk, c)]; }, acc, li, lk);
-#pragma unroll
-            for (int v = 0; v < 4; v++) Ic[ic_at(bi, bj, lk + 4 * v, li)] = acc[v];
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            dvec4 a2 = (dvec4){0.0, 0.0, 0.0, 0.0};
-            a2 = mfma16([&](int r, int kk) { return Ic[ic_at(bi, bi, r, kk)]; },
-                        [&](int kk, int c) { return Ic[ic_at(bi, bj, kk, c)]; }, a2, li, lk);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-            for (int v = 0; v < 4; v++) Ic[ic_at(bi, bj, lk + 4 * v, li)] = -a2[v];
-        }
-        __syncthreads();
-    }
-}
 #ifndef DIAG_READLANE_ONLY
 #define DIAG_LDS_BCAST 1      // (lab switch: -DDIAG_READLANE_ONLY keeps every broadcast on v_readlane, 2.3 instead of 2.0 us per sub-panel)
 #endif
-// ---- round 5: the same block with the 16-column sub-panels eliminated IN REGISTERS --------------------------------------------------
-// diag64_lds above pays ~165 ns per pivot (column published through LDS, read back, reciprocal, 15 FMAs) for the 16 rows of the
-// sub-block only, and then an MFMA phase for the rows below.  Here wave 0 holds the whole 64-row x 16-column sub-panel, one row per
-// lane and 16 registers: the pivot and the 15-j entries of column j that the step needs are the register r[j] of lanes o+j .. o+15,
-// taken with v_readlane into SGPRs -- no LDS round trip, and as scalar operands they serve all 64 lanes, so the rows BELOW the
-// sub-block are eliminated by the very same instructions (no X = A L_ss^-T phase).  A step is a reciprocal (v_rcp + two Newton steps),
-// 2 (16 - j) readlanes and 15 - j FMAs.  Meanwhile the idle waves invert the 16 x 16 unit-lower factors the same way (row k of the
+// ---- the 16-column sub-panels eliminated IN REGISTERS ---------------------------------------------------------------------------------
+// Wave 0 holds the whole 64-row x 16-column sub-panel, one row per lane and 16 registers: the pivot and the 15-j entries of column j
+// that the step needs are the register r[j] of lanes o+j .. o+15, taken with v_readlane into SGPRs -- no LDS round trip, and as scalar
+// operands they serve all 64 lanes, so the rows BELOW the sub-block are eliminated by the very same instructions.  A step is a
+// reciprocal (v_rcp + two Newton steps), 2 (16 - j) readlanes and 15 - j FMAs.  Meanwhile the idle waves invert the 16 x 16 unit-lower factors the same way (row k of the
 // running inverse broadcast by readlane) and form the off-diagonal blocks of L^-1 on the matrix cores as soon as their operands are
-// final, so only the last block row of the inverse is left when the factorization ends.
-// Same interface and the same LDS images as diag64_lds (T, Ic, Xs; cbuf unused).  Not bit-identical to it (l = a / d is formed as
-// a * (1/d), X = l d is recomputed): the dense path's parity bar is a tolerance.
+// final, so only the last block row of the inverse is left when the factorization ends.  (Rounds 2-4 published each column through
+// LDS instead, ~165 ns per pivot for the 16 rows of the sub-block alone, and then ran an MFMA phase for the rows below: LAB_NOTES.)
 // NW waves may share the work: the columns of the inverse are independent of each other, wave w of the team takes columns w, w + NW, ...
 template <int NW, int w>
 __device__ __forceinline__ void tri16_inv_wave(const double *T, double *Ic, int s, int l) {
@@ -353,7 +225,7 @@ __device__ __forceinline__ void diag64_lds_v2(double *T, double *Ic, double *Xs,
         if (wave == 0) {
             double r[16], dd[16];
 #ifdef DIAG_LDS_BCAST
-            double *cbq = Ic + 10 * 256;                                     // the 128 doubles behind the inverse blocks (cbuf of diag64_lds + the head of Xs: rows < 16 of Xs are never used)
+            double *cbq = Ic + 10 * 256;                                     // the 128 doubles behind the inverse blocks (cb + the head of Xs: rows < 16 of Xs are never used)
 #endif
 #pragma unroll
             for (int c = 0; c < 16; c++) r[c] = T[l * TS + o + c];           // (lanes above the sub-panel carry entries of the upper triangle: never stored)
@@ -458,7 +330,7 @@ __device__ __forceinline__ void diag64_lds_v2(double *T, double *Ic, double *Xs,
         return;
     }
     // a padded block: identity blocks of L^-1 for the padding, the last factored 16 x 16 inverse, then the blocks below the diagonal by
-    // block diagonals (as diag64_lds)
+    // block diagonals
     for (int e = tid; e < 10 * 256; e += 256) {
         const int blk = e >> 8, r = (e >> 4) & 15, c = e & 15;
         int bi = 0; while ((bi + 1) * (bi + 2) / 2 <= blk) bi++;
@@ -475,12 +347,10 @@ __device__ __forceinline__ void diag64_lds_v2(double *T, double *Ic, double *Xs,
     }
 }
 // load block kb into LDS, factor, write L (strictly lower part of K), D, L^-1 (column-major: Li[c*64 + r] = (L^-1)[r][c], for the
-// panel solve and the forward solves) and its transpose (LiT[r*64 + c], backward solves).  AG: the outputs other workgroups of the same
-// launch consume (D, L^-1) leave through agent-scope stores.
-template <bool AG, int VER = 2>
+// panel solve and the forward solves) and its transpose (LiT[r*64 + c], backward solves)
 __device__ __forceinline__ void diag64_block(double *S, double *__restrict__ K, int ld, int kb, double *__restrict__ Dg, double *__restrict__ Linv,
                              double *__restrict__ LinvT, int tid) {
-    double *T = S, *Ic = S + DNB * DG_TS, *cbuf = Ic + 10 * 256, *Xs = cbuf + 64;
+    double *T = S, *Ic = S + DNB * DG_TS, *Xs = Ic + 10 * 256 + 64;
     const size_t base = (size_t)kb * DNB + (size_t)kb * DNB * ld;
     const int r = tid & 63, c0 = tid >> 6;
 #pragma unroll 4
@@ -488,32 +358,27 @@ __device__ __forceinline__ void diag64_block(double *S, double *__restrict__ K, 
     DG_T(0);
     __syncthreads();
     DG_T(1);
-    if constexpr (VER == 2) diag64_lds_v2(T, Ic, Xs, tid); else diag64_lds(T, Ic, cbuf, Xs, tid);
+    diag64_lds_v2(T, Ic, Xs, tid);
     DG_T(14);
     double *o1 = Linv + (size_t)kb * DNB * DNB, *o2 = LinvT + (size_t)kb * DNB * DNB;
 #pragma unroll 4
     for (int e = 0; e < DNB / 4; e++) {
         const int c = c0 + 4 * e;
         if (r > c) K[base + r + (size_t)c * ld] = T[r * DG_TS + c];
-        st_sel<AG>(&o1[(size_t)c * DNB + r], diag64_inv(Ic, r, c));
+        o1[(size_t)c * DNB + r] = diag64_inv(Ic, r, c);
         o2[(size_t)c * DNB + r] = diag64_inv(Ic, c, r);
     }
-    if (tid < DNB) st_sel<AG>(&Dg[kb * DNB + tid], T[tid * DG_TS + tid]);
+    if (tid < DNB) Dg[kb * DNB + tid] = T[tid * DG_TS + tid];
     DG_T(15);
 }
-template <int VER>
-__global__ __launch_bounds__(256) void k_ldl_diag_blocked_v(double *__restrict__ K, int ld, int kb, double *__restrict__ Dg, double *__restrict__ Linv,
-                                                            double *__restrict__ LinvT) {
+__global__ __launch_bounds__(256) void k_ldl_diag_blocked(double *__restrict__ K, int ld, int kb, double *__restrict__ Dg, double *__restrict__ Linv,
+                                                          double *__restrict__ LinvT) {
     __shared__ double S[DG_LDS];
-    diag64_block<false, VER>(S, K, ld, kb, Dg, Linv, LinvT, threadIdx.x);
+    diag64_block(S, K, ld, kb, Dg, Linv, LinvT, threadIdx.x);
 }
-#define k_ldl_diag_blocked k_ldl_diag_blocked_v<2>
 // panel below the diagonal block on the matrix cores: X = A L_kk^-T  =>  W = X (= L D), L = X / D.  L is also written
 // transposed into the upper triangle of K so that the backward solve reads contiguous columns.
-// One workgroup per 64-row tile.
-// AG_IN: D and L_kk^-1 come from another workgroup of the same launch (agent-scope loads); AG_OUT: L is consumed by other
-// workgroups of the same launch (agent-scope stores).  S: 2*32*80 doubles of LDS.
-template <bool AG_IN, bool AG_OUT>
+// One workgroup per 64-row tile.  S: 2*32*80 doubles of LDS.
 __device__ __forceinline__ void ldl_panel_tile(double *S, double *__restrict__ K, int ld, int kb, int ti, int wcol, const double *__restrict__ Dg,
                                                const double *__restrict__ Linv, double *__restrict__ W) {
     // 40 KB of LDS (two 32-deep k chunks through the same buffers) so that the tiles of a panel find room beside the trailing
@@ -537,7 +402,7 @@ __device__ __forceinline__ void ldl_panel_tile(double *S, double *__restrict__ K
         for (int idx = tid; idx < KC * DNB; idx += 256) {
             const int r = idx % DNB, k = idx / DNB, kg = h * KC + k;
             As[k][r] = K[(size_t)ti * DNB + r + ((size_t)kb * DNB + kg) * ld];      // A[row r][k]
-            Bs[k][r] = ld_sel<AG_IN>(&Li[(size_t)kg * DNB + r]);                     // B[k][col r] = (L^-1)[r][k]
+            Bs[k][r] = Li[(size_t)kg * DNB + r];                                      // B[k][col r] = (L^-1)[r][k]
         }
         __syncthreads();
 #pragma unroll 4
@@ -565,9 +430,9 @@ __device__ __forceinline__ void ldl_panel_tile(double *S, double *__restrict__ K
         const int col = c0 + 4 * e;
         const double x = S[col * (DNB + 1) + lr];
         W[(size_t)ti * DNB + lr + ((size_t)wcol * DNB + col) * ld] = x;                   // W = L D
-        st_sel<AG_OUT>(&K[(size_t)ti * DNB + lr + ((size_t)kb * DNB + col) * ld], x / ld_sel<AG_IN>(&Dg[kb * DNB + col]));      // L
+        K[(size_t)ti * DNB + lr + ((size_t)kb * DNB + col) * ld] = x / Dg[kb * DNB + col];                                // L
     }
-    const double dl = ld_sel<AG_IN>(&Dg[kb * DNB + lr]);
+    const double dl = Dg[kb * DNB + lr];
 #pragma unroll 4
     for (int e = 0; e < DNB / 4; e++) {                                                  // L' in the (otherwise unused) upper triangle
         const int row = c0 + 4 * e;                                                      // tile row -> column of the transposed copy
@@ -577,13 +442,14 @@ __device__ __forceinline__ void ldl_panel_tile(double *S, double *__restrict__ K
 __global__ __launch_bounds__(256) void k_ldl_panel(double *__restrict__ K, int ld, int kb, int wcol, const double *__restrict__ Dg,
                                                    const double *__restrict__ Linv, double *__restrict__ W) {
     __shared__ double S[2 * 32 * 80];
-    ldl_panel_tile<false, false>(S, K, ld, kb, kb + 1 + blockIdx.x, wcol, Dg, Linv, W);
+    ldl_panel_tile(S, K, ld, kb, kb + 1 + blockIdx.x, wcol, Dg, Linv, W);
 }
 // update on the matrix cores: C(ti,tj) -= sum_{q<nkb} W(ti, wcol0+q) * L(tj, kb0+q)'  for tj in [tj_lo, tj_hi), ti >= tj.
 // nkb = 1 updates the rest of the current 256-wide outer panel, nkb = 4 the trailing matrix (one read-modify-write
-// of C per 256 eliminated columns instead of per 64).  Software pipelined: the k dimension is cut into 32-deep
+// of C per 256 eliminated columns instead of per 64).  Software pipelined: the k dimension is cut into 16-deep
 // chunks held in double-buffered LDS tiles; the global loads of chunk c+1 are in flight while the MFMAs of chunk c
-// run (one barrier per chunk; 16-deep chunks: 40 KB LDS => four workgroups per CU, 32-deep: 80 KB => two).
+// run (one barrier per chunk; 40 KB LDS => four workgroups per CU).
+static const int SY_KC = 16;
 static const int SY_STRIP = 8;
 // number of tiles of the trapezoid {C columns, R rows, column <= row} (host side of the 1-D order below)
 static inline int syrk_tiles(int R, int C) {
@@ -594,9 +460,7 @@ static inline int syrk_tiles(int R, int C) {
     }
     return tot;
 }
-// AG_IN: the L operand comes from another workgroup of the same launch (agent-scope loads).
 // S: max(4 * SY_KC * 80, 64 * 65) doubles of LDS.
-template <int SY_KC, bool AG_IN>
 __device__ __forceinline__ void ldl_syrk_tile(double *S, double *__restrict__ K, int ld, const double *__restrict__ W, int kb0, int nkb, int wcol0,
                                               int ti, int tj) {
     // one LDS array: A tiles [buf][k][row] at S + buf*T, B tiles at S + (2+buf)*T, T = SY_KC*80 (row stride 80 doubles: the
@@ -614,7 +478,7 @@ __device__ __forceinline__ void ldl_syrk_tile(double *S, double *__restrict__ K,
         const int q = ch / (DNB / SY_KC), h = ch % (DNB / SY_KC);
         const size_t wc0 = ((size_t)(wcol0 + q) * DNB + (size_t)h * SY_KC) * ld, kc0 = ((size_t)(kb0 + q) * DNB + (size_t)h * SY_KC) * ld;
 #pragma unroll
-        for (int e = 0; e < SY_KC / 4; e++) { const size_t ko = (size_t)(lk0 + 4 * e) * ld; ra[e] = Wp[wc0 + ko]; rb[e] = ld_sel<AG_IN>(&Kp[kc0 + ko]); }
+        for (int e = 0; e < SY_KC / 4; e++) { const size_t ko = (size_t)(lk0 + 4 * e) * ld; ra[e] = Wp[wc0 + ko]; rb[e] = Kp[kc0 + ko]; }
     };
     auto lstore = [&](int buf, const double (&ra)[SY_KC / 4], const double (&rb)[SY_KC / 4]) {
         double *A = S + buf * T, *B = S + (2 + buf) * T;
@@ -677,9 +541,8 @@ __device__ __forceinline__ void ldl_syrk_tile(double *S, double *__restrict__ K,
         *cp = *cp - S[col * (DNB + 1) + lr];
     }
 }
-template <int SY_KC>
-__global__ __launch_bounds__(256, SY_KC == 16 ? 4 : 2) void k_ldl_syrk(double *__restrict__ K, int ld, const double *__restrict__ W, int kb0, int nkb, int wcol0,
-                                                  int tj_lo, int tj_hi, int nb_swz) {
+__global__ __launch_bounds__(256, 4) void k_ldl_syrk(double *__restrict__ K, int ld, const double *__restrict__ W, int kb0, int nkb, int wcol0,
+                                                     int tj_lo, int tj_hi, int nb_swz) {
     int ti, tj;
     if (nb_swz > 0) {
         // 1-D grid over the tiles of the trapezoid {tj_lo <= tj < tj_hi, tj <= ti < nb}, in an order made for the eight L2s: workgroups
@@ -710,83 +573,7 @@ __global__ __launch_bounds__(256, SY_KC == 16 ? 4 : 2) void k_ldl_syrk(double *_
     }
     constexpr int SZ = (4 * SY_KC * 80 > DNB * (DNB + 1)) ? 4 * SY_KC * 80 : DNB * (DNB + 1);
     __shared__ double S[SZ];
-    ldl_syrk_tile<SY_KC, false>(S, K, ld, W, kb0, nkb, wcol0, ti, tj);
-}
-// ---- one outer panel in ONE launch ---------------------------------------------------------------------------------------------
-// The factorization of an outer panel (DOUTER block columns) used to be a chain of 3 launches per block column -- diagonal block,
-// panel solve, update of the rest of the outer panel -- each waiting for the previous one and each competing for workgroup slots with
-// the trailing update of the previous outer panel on the other stream (r02 timeline at n = 1e4: 200 us per outer panel alone, 470 us
-// beside a wide trailing update; 33 of 38 outer panels were bound by this chain).  Here workgroup 0 factors the diagonal blocks and
-// owns the DOUTER x DOUTER tiles of the diagonal block of the outer panel; every other workgroup owns FP_ROWS tile rows below it and
-// follows: it waits for flag D(kb) (D and L_kk^-1 published), solves its tiles of block column kb, waits for flag L(kb) (the L tiles
-// of the diagonal block published) and updates its tiles of the remaining columns.  The arithmetic per tile is that of the separate
-// kernels (same device functions), so the factor has the same bits.
-// Hand-off: the producer's data leave through 8-byte agent-scope stores, every storing wave drains them (s_waitcnt vmcnt(0)), the
-// workgroup meets at a barrier and one lane stores the flag; consumers poll the flag with one lane, meet at a barrier and read the
-// data with 8-byte agent-scope loads.  A workgroup waits only for workgroup 0, which is dispatched first; a bounded spin turns a lost
-// producer into C_CHAIN_ERR (the host then refactors with the separate kernels).  Flags carry the launch's epoch: nothing to reset.
-// out-of-line instances for k_ldl_fpanel: inlined into one function the tile bodies' address arithmetic stays live across each other
-// and spills (700 bytes of scratch per lane at the 168 registers that three workgroups per CU allow)
-template <bool AG_IN, bool AG_OUT>
-__device__ __forceinline__ void fp_panel_tile(double *S, double *K, int ld, int kb, int ti, int wcol, const double *Dg, const double *Linv, double *W) {
-    ldl_panel_tile<AG_IN, AG_OUT>(S, K, ld, kb, ti, wcol, Dg, Linv, W);
-}
-__device__ __forceinline__ void fp_syrk_tile(double *S, double *K, int ld, const double *W, int kb, int wcol, int ti, int tj) {
-    ldl_syrk_tile<16, true>(S, K, ld, W, kb, 1, wcol, ti, tj);
-}
-__device__ __forceinline__ void fp_diag_block(double *S, double *K, int ld, int kb, double *Dg, double *Linv, double *LinvT, int tid) {
-    diag64_block<true>(S, K, ld, kb, Dg, Linv, LinvT, tid);
-}
-static const int FP_ROWS = 3;
-static const int FP_SPIN_MAX = 1 << 22;
-static const int FP_MAX_OUTER = 16;
-__global__ __launch_bounds__(256, 2) void k_ldl_fpanel(double *__restrict__ K, int ld, int nb, int J0, int Jend, double *__restrict__ W, double *__restrict__ Dg,
-                                                       double *__restrict__ Linv, double *__restrict__ LinvT, unsigned int *flags, unsigned int epoch, Ctrl *ctrl) {
-    __shared__ double S[DG_LDS];
-    __shared__ int s_lost;
-    const int tid = threadIdx.x;
-    if (blockIdx.x == 0) {
-        for (int kb = J0; kb < Jend; kb++) {
-            __syncthreads();                                       // the tiles of the previous column are done with S
-            fp_diag_block(S, K, ld, kb, Dg, Linv, LinvT, tid);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) __hip_atomic_store(&flags[kb - J0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (kb + 1 == Jend) break;
-            for (int tj = kb + 1; tj < Jend; tj++) fp_panel_tile<true, true>(S, K, ld, kb, tj, kb - J0, Dg, Linv, W);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) __hip_atomic_store(&flags[FP_MAX_OUTER + kb - J0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int ti = kb + 1; ti < Jend; ti++)
-                for (int tj = kb + 1; tj <= ti; tj++) fp_syrk_tile(S, K, ld, W, kb, kb - J0, ti, tj);
-        }
-        return;
-    }
-    if (tid == 0) s_lost = 0;
-    __syncthreads();
-    const int t0 = Jend + FP_ROWS * ((int)blockIdx.x - 1);
-    auto wait_flag = [&](int idx) {
-        if (tid == 0) {
-            int spins = 0;
-            while (__hip_atomic_load(&flags[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-                if (++spins > FP_SPIN_MAX) { s_lost = 1; break; }
-                __builtin_amdgcn_s_sleep(4);
-            }
-        }
-        __syncthreads();
-        return s_lost != 0;
-    };
-    for (int kb = J0; kb < Jend; kb++) {
-        if (wait_flag(kb - J0)) break;
-        for (int r = 0; r < FP_ROWS; r++)
-            if (t0 + r < nb) fp_panel_tile<true, false>(S, K, ld, kb, t0 + r, kb - J0, Dg, Linv, W);
-        if (kb + 1 == Jend) break;
-        if (wait_flag(FP_MAX_OUTER + kb - J0)) break;
-        for (int r = 0; r < FP_ROWS; r++)
-            if (t0 + r < nb)
-                for (int tj = kb + 1; tj < Jend; tj++) fp_syrk_tile(S, K, ld, W, kb, kb - J0, t0 + r, tj);
-    }
-    if (s_lost && tid == 0) atomicOr(&ctrl->cnt[C_CHAIN_ERR], 1);
+    ldl_syrk_tile(S, K, ld, W, kb0, nkb, wcol0, ti, tj);
 }
 // forward step kb: z_k = L_kk^-1 x_k (matrix-vector with the stored inverse: no serial chain), wave 0 publishes
 // it, then wave b updates the 64 rows of block kb+1+b:  x_i -= L(i, kb) z_k.

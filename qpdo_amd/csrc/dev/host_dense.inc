@@ -1,7 +1,7 @@
 // host_dense.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): dense factorization, solves, low-rank update
 // ---- dense direct solve ------------------------------------------------------------------------------
-// inner 64-blocks per outer panel (default 4 = 256 columns; QPDO_DENSE_OUTER for experiments: measured at n = 1e4 in DESIGN.md)
-static const int DOUTER = [] { const char *e = getenv("QPDO_DENSE_OUTER"); const int v = e ? atoi(e) : 4; return (v >= 1 && v <= 16) ? v : 4; }();
+static const int DOUTER = 4;                 // inner 64-blocks per outer panel (256 columns)
+static const int DENSE_RESERVE_CUS = 32;     // CUs left out of the look-ahead stream's mask
 static int dense_alloc(QpdoDev *d) {
     if (d->Kd) return 0;
     const int ld = (d->n + DNB - 1) / DNB * DNB;
@@ -11,15 +11,13 @@ static int dense_alloc(QpdoDev *d) {
     if (!rc && !d->stream2) {
         // The trailing updates would fill every CU and starve the one-workgroup diagonal kernel of the next panel
         // (it needs 66 KB of LDS on one CU), so their stream leaves a few CUs out of its mask.
-        int reserve = 32;
-        if (const char *rs = getenv("QPDO_DENSE_RESERVE_CUS")) reserve = atoi(rs);
         hipDeviceProp_t prop; int ncu = 256;
         if (hipGetDeviceProperties(&prop, d->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
         hipError_t e = hipErrorInvalidValue;
-        if (reserve > 0 && reserve < ncu) {
+        if (DENSE_RESERVE_CUS < ncu) {
             const int words = (ncu + 31) / 32;
             std::vector<uint32_t> mask((size_t)words, 0u);
-            for (int c = 0; c < ncu - reserve; c++) mask[c >> 5] |= 1u << (c & 31);
+            for (int c = 0; c < ncu - DENSE_RESERVE_CUS; c++) mask[c >> 5] |= 1u << (c & 31);
             e = hipExtStreamCreateWithCUMask(&d->stream2, (uint32_t)words, mask.data());
             if (e != hipSuccess) { (void)hipGetLastError(); d->stream2 = nullptr; }
         }
@@ -28,7 +26,6 @@ static int dense_alloc(QpdoDev *d) {
         if (e != hipSuccess) rc = set_err(e, "dense look-ahead stream", __LINE__);
     }
     if (!rc) rc = dev_alloc(d, &d->Dg, (size_t)ld);
-    if (!rc) rc = dev_alloc(d, &d->fp_flags, (size_t)2 * FP_MAX_OUTER);
     if (!rc) rc = dev_alloc(d, &d->Linv, (size_t)d->dense_nblk * DNB * DNB);
     if (!rc && d->dense_nblk <= MID_MAX_NB) {
         rc = dev_alloc(d, &d->mid_flags, (size_t)(d->dense_nblk + 1) * d->dense_nblk);
@@ -75,12 +72,9 @@ static int dense_factor(QpdoDev *d, bool with_rhs = false) {
     d->mid_fwd_valid = 0;
     const int n = d->n, ld = d->dense_ld, nb = d->dense_nblk;
     const int g = ld < 1024 ? ld : 1024;
-    // (experiment knobs are read per factorization, so one process can compare variants)
-    const bool kc16 = [] { const char *e = getenv("QPDO_SYRK_KC"); return !(e && atoi(e) == 32); }();
     // look-ahead pays from n ~ 7000 up (tools/dense_lookahead_crossover.sh, factor ms with | without: n = 2000: 1.60 | 1.46, 4000: 3.39 | 3.18,
     // 6000: 5.82 | 5.72, 7000: 7.24 | 7.35, 8000: 8.85 | 9.14, 1e4: 13.4 | 14.0, 12288: 22.2 | 23.9): below, the two streams only slow each other
-    const int la_env = [] { const char *e = getenv("QPDO_DENSE_LOOKAHEAD"); return (e && *e) ? (atoi(e) != 0) : -1; }();
-    const bool lookahead = la_env >= 0 ? la_env != 0 : n >= 7000;
+    const bool lookahead = d->dense_lookahead >= 0 ? d->dense_lookahead != 0 : n >= 7000;
     // the assembly's accumulator is an LDS tile of up to DENSE_ASM_TILE_MAX rows (QPDO_DENSE_ASM_TILE: a smaller tile, for the tests
     // of the tiled path at small n); larger orders are assembled in several row tiles per column -- the same bits
     const int asm_tile = n < d->dense_asm_tile ? (n > 0 ? n : 1) : d->dense_asm_tile;
@@ -111,16 +105,14 @@ static int dense_factor(QpdoDev *d, bool with_rhs = false) {
     // beyond.  One-deep look-ahead: F_p, a_p on the main stream, b_p on stream2, so that F_{p+1} overlaps b_p.
     //   F_p <- a_{p-1};  a_p, b_p <- F_p, b_{p-1};  W_p lives in buffer p&1 (F_{p+1} <- a_p <- b_{p-1}: its reader is done).
     // Every element of K receives the same updates in the same order as without look-ahead: results are bit-identical.
-    const bool swz = [] { const char *e = getenv("QPDO_SYRK_SWZ"); return !(e && atoi(e) == 0); }();
     auto syrk = [&](hipStream_t st, const double *W, int kb0, int nkb, int wcol0, int tj_lo, int tj_hi) {
         dim3 grid(nb - tj_lo, tj_hi - tj_lo);
         int nb_swz = 0;
-        if (swz && nkb > 1) {                               // wide updates: 1-D grid in the L2-friendly tile order
+        if (nkb > 1) {                                      // wide updates: 1-D grid in the L2-friendly tile order
             const int nt = syrk_tiles(nb - tj_lo, tj_hi - tj_lo);
             grid = dim3((nt + 7) / 8 * 8, 1); nb_swz = nb;
         }
-        if (kc16) hipLaunchKernelGGL(k_ldl_syrk<16>, grid, dim3(256), 0, st, d->Kd, ld, W, kb0, nkb, wcol0, tj_lo, tj_hi, nb_swz);
-        else      hipLaunchKernelGGL(k_ldl_syrk<32>, grid, dim3(256), 0, st, d->Kd, ld, W, kb0, nkb, wcol0, tj_lo, tj_hi, nb_swz);
+        hipLaunchKernelGGL(k_ldl_syrk, grid, dim3(256), 0, st, d->Kd, ld, W, kb0, nkb, wcol0, tj_lo, tj_hi, nb_swz);
     };
     hipStream_t sc = d->stream;
     bool b_pending = false;
@@ -128,11 +120,6 @@ static int dense_factor(QpdoDev *d, bool with_rhs = false) {
     for (int J0 = 0; J0 < nb; J0 += DOUTER, p++) {
         const int Jend = J0 + DOUTER < nb ? J0 + DOUTER : nb;
         double *W = d->Wd + (size_t)(p & 1) * ld * DNB * DOUTER;
-        if (d->dense_fpanel && DOUTER <= FP_MAX_OUTER) {    // the whole outer panel in one launch (workgroups chained through flags)
-            const int rows = nb - Jend;
-            hipLaunchKernelGGL(k_ldl_fpanel, dim3(1 + (rows + FP_ROWS - 1) / FP_ROWS), dim3(256), 0, sc, d->Kd, ld, nb, J0, Jend, W, d->Dg, d->Linv,
-                               d->LinvT, d->fp_flags, ++d->fp_epoch, d->ctrl);
-        } else
         for (int kb = J0; kb < Jend; kb++) {
             hipLaunchKernelGGL(k_ldl_diag_blocked, dim3(1), dim3(256), 0, sc, d->Kd, ld, kb, d->Dg, d->Linv, d->LinvT);
             const int below = nb - kb - 1;

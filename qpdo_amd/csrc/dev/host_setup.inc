@@ -19,13 +19,7 @@ int qdev_create_csc(QpdoDev **out, int device, int32_t n, int32_t m, const QdevC
     QpdoDev *d = new QpdoDev();
     d->device = device; d->n = n; d->m = m; d->mloc = m; d->nloc = n;
     QdevDist none; memset(&none, 0, sizeof(none)); none.world = 1; none.mloc = m; none.nloc = n;
-    hipError_t e;
-    {
-        const char *pr = getenv("QPDO_STREAM_PRIO");
-        int lo = 0, hi = 0;
-        if (pr && atoi(pr) != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) e = hipStreamCreateWithPriority(&d->stream, hipStreamNonBlocking, hi);
-        else e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    }
+    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete d; return set_err(e, "hipStreamCreate", __LINE__); }
     TempAllocs tmp;
     int rc = upload_csc_as_csr_of_transpose(d, tmp, &d->At, A, false);            // CSR(A') = the CSC arrays of A
@@ -88,13 +82,7 @@ int qdev_create_dist(QpdoDev **out, int device, int32_t n, int32_t m, const Qdev
     d->comm.active = dist->world > 1 || dist->force;
     d->comm.mode = d->comm.active ? (dist->fn ? 1 : 2) : 0;
     int rc = 0;
-    hipError_t e = hipSuccess;
-    {   // QPDO_STREAM_PRIO=1: the solver's stream gets the highest queue priority (experiments with the dense look-ahead)
-        const char *pr = getenv("QPDO_STREAM_PRIO");
-        int lo = 0, hi = 0;
-        if (pr && atoi(pr) != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) e = hipStreamCreateWithPriority(&d->stream, hipStreamNonBlocking, hi);
-        else e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-    }
+    hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete d; return set_err(e, "hipStreamCreate", __LINE__); }
     if (!rc) rc = upload_csr(d, &d->Ar, Ar);
     if (!rc) rc = upload_csr(d, &d->At, At);
@@ -261,9 +249,8 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     if (sc && *sc) d->schur_mode = atoi(sc) != 0;
     const char *ch = getenv("QPDO_DENSE_SOLVE");
     if (ch && !strcmp(ch, "steps")) d->dense_chain = 0;
-    const char *fp = getenv("QPDO_DENSE_FPANEL");
-    if (fp && *fp) d->dense_fpanel = atoi(fp) != 0;
     { const char *md = getenv("QPDO_DENSE_MID"); if (md && *md) d->dense_mid = atoi(md) != 0; }      // 0: mid-size orders through the multi-launch factorization too
+    { const char *la = getenv("QPDO_DENSE_LOOKAHEAD"); if (la && *la) d->dense_lookahead = atoi(la) != 0; }
     // Low-rank update of the kept factor: pays from n ~ 2500 up (tools/lowrank_crossover.py, m = 2n: n = 256: 39 ms with, 11 ms without;
     // 1024: 51 | 43; 2048: 102 | 91; 3072: 106 | 117; 1e4: 0.49 s | 0.63 s) -- below that a fresh MFMA factorization costs less than
     // the update's dozen small launches and its host read-back.  QPDO_DENSE_LOWRANK=0/1 overrides.
@@ -309,7 +296,7 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
         if (want > 1) d->hybrid_budget = want;
     }
     d->st.linsolve = d->linsolve;
-    d->cfg.linsolve = d->linsolve; d->cfg.dense_chain = d->dense_chain; d->cfg.dense_fpanel = d->dense_fpanel; d->cfg.dense_mid = d->dense_mid;
+    d->cfg.linsolve = d->linsolve; d->cfg.dense_chain = d->dense_chain; d->cfg.dense_mid = d->dense_mid; d->cfg.dense_lookahead = d->dense_lookahead;
     d->cfg.wb_enable = d->wb_enable; d->cfg.deflate = d->deflate; d->cfg.pcg_maxit = d->pcg_maxit; d->cfg.band_b = d->band_b;
     return 0;
 }

@@ -82,7 +82,7 @@ static int step_redo_if_lost(QpdoDev *d, int proximal, double sigma) {
         else { int lin = 0; d->pcg_abs_now = proximal ? d->pcg_abs : -1.0; d->cur_proximal = proximal; rc = pcg_solve(d, &lin); if (rc) return rc; d->st.lin_iters += lin; }
         return newton_finish_step(d, proximal, sigma, true, true);
     }
-    if (!(d->linsolve == 1 && (d->dense_chain || d->dense_fpanel))) {
+    if (!(d->linsolve == 1 && d->dense_chain)) {
         // the latch is set although no polling kernel can have run in this step (stale): the device skipped this step's iterate update
         // on its account, so it cannot be ignored -- clear it and report, instead of looping to max_iter on a frozen iterate
         LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
@@ -90,7 +90,7 @@ static int step_redo_if_lost(QpdoDev *d, int proximal, double sigma) {
     }
     const int m = d->m;
     LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-    d->dense_chain = 0; d->dense_fpanel = 0; d->dense_mid = 0; d->wb_enable = 0; d->st.chain_fallbacks++;
+    d->dense_chain = 0; d->dense_mid = 0; d->wb_enable = 0; d->st.chain_fallbacks++;
     LAUNCH(k_newton_prep, vgrid(m), m, 3, d->active, d->active_old, d->isq, d->mu, d->res_prim_in, d->d, d->dy);      // dy = t again
     int rc = spmv_At(d, d->dy, EpiRhs{d->res_dual_in, d->Atdy, d->rhs}, false); if (rc) return rc;
     rc = dense_factor(d); if (rc) return rc;

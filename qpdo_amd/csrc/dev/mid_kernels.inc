@@ -62,7 +62,9 @@ __device__ __forceinline__ void mid_publish(unsigned int *flag, unsigned int epo
     __syncthreads();
     if (tid == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// 64 x 64 x 32 product on the matrix cores: the 32-deep half of mfma_64x64x64 (As / Bs: [32][80] images)
+// 64 x 64 x 32 product on the matrix cores for one workgroup of 4 waves: wave w owns the 32x32 quadrant (w>>1, w&1) as 2x2 tiles of
+// v_mfma_f64_16x16x4_f64; As / Bs are [k][row] / [k][col] images, [32][80] (the two k-rows a half-wave reads land on disjoint banks).
+// A/B lane map: lane l holds A[l&15][k = l>>4], B[k = l>>4][l&15]; C/D: row = (l>>4) + 4*reg, col = l&15.
 __device__ __forceinline__ void mfma_64x64x32(const double (*As)[80], const double (*Bs)[80], dvec4 acc[2][2], int wr, int wc, int li, int lk) {
     // operands of k-step s + 1 are read from LDS before the four products of k-step s are issued (explicit register double buffer:
     // the matrix pipe does not wait for an LDS round trip at the head of every k-step)

@@ -90,7 +90,7 @@ struct QpdoDev {
     double *Kd = nullptr, *Wd = nullptr, *Dg = nullptr, *Linv = nullptr, *LinvT = nullptr, *dz = nullptr, *dxw = nullptr;
     double *ch_y = nullptr, *ch_x = nullptr, *dsol = nullptr; int dense_chain = 1;
     hipStream_t stream2 = nullptr;            // dense factor look-ahead: trailing updates run here
-    int dense_fpanel = 0; unsigned int *fp_flags = nullptr, fp_epoch = 0;      // one-launch outer panels (k_ldl_fpanel)
+    int dense_lookahead = -1;                 // multi-launch factor: -1 automatic (from n = 7000 up), 0 off, 1 on (QPDO_DENSE_LOOKAHEAD)
     // mid-size orders (dense_nblk <= MID_MAX_NB): the whole factorization and the forward solve in one launch (k_mid_factor, dev/mid_kernels.inc)
     int dense_mid = 1, mid_fwd_valid = 0; unsigned int *mid_flags = nullptr, mid_epoch = 0; double *mid_C = nullptr, *mid_dinv = nullptr;   // k_mid_factor: flags, the published C tiles (one per block row), 1 / D
     // low-rank factor update (Woodbury on the kept factor): see the k_wb_* kernels
@@ -154,6 +154,6 @@ struct QpdoDev {
     double *qstage = nullptr;                     // the caller's stored Q values (stype +-1), gathered through mapQ
     std::vector<long long> upd_Ap, upd_Qp;        // column pointers whose pattern passed the device check (later calls compare these)
     // what qdev_configure decided; a solve may change these (fallbacks, hybrid), qpdo_amd_update_matrices puts them back
-    struct { int linsolve, dense_chain, dense_fpanel, dense_mid, wb_enable, deflate, pcg_maxit, band_b; } cfg{};
+    struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, deflate, pcg_maxit, band_b; } cfg{};
 };
 

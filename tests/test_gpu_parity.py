@@ -288,28 +288,22 @@ def test_dense_factor_is_reused_when_weights_do_not_change(gpu_required, monkeyp
 
 
 def test_dense_factor_schedules_leave_the_same_bits(gpu_required, monkeypatch):
-    """look-ahead on a second stream, the XCD-aware tile order, the k-chunk depth and the one-launch outer panel only reschedule
-    the factorization: every element of K receives the same updates in the same order, so the solve is bit-identical"""
+    """the multi-launch factorization on one stream and with the look-ahead on a second stream: the look-ahead only reschedules the
+    factorization, every element of K receives the same updates in the same order, so the solve is bit-identical"""
     monkeypatch.setenv("QPDO_LINSOLVE", "dense")
     monkeypatch.setenv("QPDO_DENSE_LOWRANK", "0")
     monkeypatch.setenv("QPDO_DENSE_MID", "0")          # the multi-launch factorization (since round 5 the fallback of the one-launch kernel)
     p = problems.random_qp(77, 1500, 2600, 0.01, 100)
     base = None
-    for var in ({"QPDO_DENSE_LOOKAHEAD": "0"}, {"QPDO_DENSE_LOOKAHEAD": "1"}, {"QPDO_DENSE_LOOKAHEAD": "1", "QPDO_SYRK_SWZ": "0"},
-                {"QPDO_DENSE_LOOKAHEAD": "1", "QPDO_SYRK_KC": "32"}, {"QPDO_DENSE_LOOKAHEAD": "1", "QPDO_DENSE_FPANEL": "1"},
-                {"QPDO_DENSE_LOOKAHEAD": "0", "QPDO_DENSE_FPANEL": "1"}):
-        for k in ("QPDO_DENSE_LOOKAHEAD", "QPDO_SYRK_SWZ", "QPDO_SYRK_KC", "QPDO_DENSE_FPANEL"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in var.items():
-            monkeypatch.setenv(k, v)
+    for lookahead in ("0", "1"):
+        monkeypatch.setenv("QPDO_DENSE_LOOKAHEAD", lookahead)
         r = solver.solve_problem(p, verbose=0)
-        # (a polling kernel that loses its producer on a disturbed GPU makes the step fall back to the separate kernels: same bits)
-        assert r["info"]["status_val"] == 1 and (r["stats"]["chain_fallbacks"] == 0 or "QPDO_DENSE_FPANEL" in var), var
+        assert r["info"]["status_val"] == 1 and r["stats"]["chain_fallbacks"] == 0, lookahead
         if base is None:
             base = r
         else:
-            assert r["info"]["iterations"] == base["info"]["iterations"], var
-            assert np.array_equal(r["x"], base["x"]) and np.array_equal(r["y"], base["y"]), var
+            assert r["info"]["iterations"] == base["info"]["iterations"], lookahead
+            assert np.array_equal(r["x"], base["x"]) and np.array_equal(r["y"], base["y"]), lookahead
 
 
 def test_one_launch_factorization_matches_the_multi_launch_one_and_the_oracle(gpu_required, monkeypatch):
