@@ -154,6 +154,34 @@ int  qpdo_amd_spmv(QPDOWorkspace *work, int which, const double *v, double *y);
  * src/linesearch.c:74-158) on the device, host in/out (parity tests) */
 int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const double *delta,
                          const double *alpha, double *tau);
+/* ---- the direct solvers as single linear solves (tests of the factorizations; tests/test_gpu_direct_solvers.py) ----------------------
+ * qpdo_amd_direct_solve: x (n) = K^-1 rhs (n) with K = Q + sigma I + A' diag(dw) A (dw: m weights), Q and A the workspace's stored, i.e.
+ * scaled, matrices (the caller's own with settings->scaling = 0), through the workspace's direct solver exactly as a Newton pass drives
+ * it: the dense LDL' (QPDO_LINSOLVE=dense, with its QPDO_DENSE_* routes) or the band LDL' (QPDO_LINSOLVE=band).
+ *   flags bit 0  refactor.  Clear: the factor kept from the previous call is reused -- with QPDO_DENSE_LOWRANK on, every row whose weight
+ *                differs from the factored one gets a low-rank slot (more than 256 such rows refactor); otherwise it is reused as it is,
+ *                i.e. the caller passes the factored weights.  No factor yet, or (dense) another sigma: refactor.
+ *   flags bit 1  the factorization launch carries the forward solve along (one-launch route of the dense factor).
+ * Returns 0; QPDO_AMD_DIRECT_LOST when a polling kernel lost its producer or the band factorization met a pivot that is not a positive
+ * finite number (the latch is cleared, the result is not redone, qpdo_amd_last_error says which); -1 on any other failure, including a
+ * PCG workspace and a row-partitioned one (refused).  The workspace's weights, sigma and direction are untouched; the next qpdo_solve
+ * drops the kept factor and runs as on a workspace that never saw this call.
+ * qpdo_amd_download_factor: copies a factor array of the last factorization to the host; count must be the array's length.
+ *   which 6: the geometry, 4 entries: ld = n rounded up to 64, nb = ld / 64 (dense), np = n rounded up to 4, b = the half-bandwidth
+ *            (band); 0 where that solver never factored.
+ *   dense, column-major, element (i, j) at [i + j ld]:
+ *     0  Kd     ld x ld.  Below the diagonal: L (unit diagonal implied).  The upper triangle of every off-diagonal 64 x 64 tile holds the
+ *               transposed copy that the backward solve reads: Kd(j, i) = L(i, j) for i, j in different tiles.  The diagonal and the upper
+ *               triangle of a diagonal tile keep assembled values; rows / columns n .. ld-1 are identity padding.
+ *     1  Dg     ld: D.
+ *     2  Linv   nb x 64 x 64: the inverse of the unit-lower diagonal block k of L, column-major: Linv[k 4096 + c 64 + r] = (L_kk^-1)(r, c).
+ *     3  LinvT  the same blocks transposed: LinvT[k 4096 + c 64 + r] = (L_kk^-1)(c, r).
+ *   band, lower band storage, np x (b + 1):
+ *     4  Kb     Kb[j (b+1) + t] = L(j + t, j) for t >= 1, D_j at t = 0 (zero beyond the matrix; columns n .. np-1 identity padding).
+ *     5  Lt     Lt[i (b+1) + t] = L(i, i - t), the row-band copy the backward solve reads (t >= 1).  */
+#define QPDO_AMD_DIRECT_LOST (-2)
+int  qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags);
+int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count);
 /* copy a device-resident vector to the host: 0 x, 1 Qx, 2 y, 3 mu, 4 d (factor weights),
  * 5 dx, 6 dy, 7 Ax, 8 Aty, 9 l, 10 u, 11 ybar, 12 xbar, 13 w (of the last loop pass that ran) */
 int  qpdo_amd_download(QPDOWorkspace *work, int which, double *dst);

@@ -521,6 +521,10 @@ int qdev_begin_solve(QpdoDev *d) {
     HIPCHK(hipSetDevice(d->device));
     d->last_jacobi_iters = 0; d->schur_off = 0; d->schur_strikes = 0; d->ctrl_clean = 0; d->step_pending = 0; d->axpy_pending = 0;
     if (d->hybrid) { d->linsolve = 0; d->hybrid_active = 1; }
+    if (d->direct_hook_used) {       // a factor kept by the test entry qdev_direct_solve is not this solve's: start as an untouched workspace
+        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0; d->dense_fact_sigma = 0.0;
+        d->dense_last_branch = -1; d->dense_last_sigma = -1.0; d->direct_hook_used = 0;
+    }
     // the lost-producer latch of the polling kernels is cleared by the redo (step_redo_if_lost) -- and here, so that a solve that was
     // left between the latch and its redo (a HIP error on the way) cannot make k_axpy5 skip every iterate update of the next solve
     LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);

@@ -628,6 +628,89 @@ int qdev_bench_dense_factor(QpdoDev *d, int reps, double *avg_seconds, double *c
     }
     return 0;
 }
+// ---- the direct solvers as single linear solves (tests: tests/test_gpu_direct_solvers.py) ---------------------------------------
+// K x = rhs with K = Q + sigma I + A' diag(dw) A, through the workspace's direct solver as a Newton pass drives it: dense_factor /
+// wb_extend / dense_solve (linsolve 1) or band_factor / band_solve (3), no other kernels.  flags bit 0: refactor; clear: a kept factor of
+// this sigma is reused -- with the low-rank update for the rows whose weight moved since it when wb_enable is set (more than WB_MAX of
+// them refactor), as it is (the caller passes the factored weights) otherwise.  Bit 1: the factorization launch carries the forward
+// solve (dense_factor(d, true)).  The workspace's weights, sigma_f and dx are put back afterwards; the kept factor stays for the next
+// call and is dropped by the next qdev_begin_solve.  A lost producer of a polling kernel, or a bad band pivot, returns
+// QDEV_DIRECT_LOST with the latch cleared -- never a silent redo.
+int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *rhs, double *x, int flags) {
+    HIPCHK(hipSetDevice(d->device));
+    if (d->comm.active) return set_err(hipErrorInvalidValue, "direct solve: not for row-partitioned workspaces", __LINE__);
+    if (d->linsolve != 1 && d->linsolve != 3) return set_err(hipErrorInvalidValue, "direct solve: the workspace's solver is not a direct one (dense or band)", __LINE__);
+    const int n = d->n, m = d->m;
+    std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1));
+    if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(dx_keep.data(), d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (m) HIPCHK(hipMemcpyAsync(d->d, dw, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d->rhs, rhs, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    const double sigma_keep = d->sigma_f;
+    d->sigma_f = sigma;
+    d->direct_hook_used = 1;
+    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+    const bool refactor = (flags & 1) != 0, carry = (flags & 2) != 0;
+    int rc = 0;
+    if (d->linsolve == 3) {
+        if (refactor || !d->dense_valid) rc = band_factor(d);
+        if (!rc) rc = band_solve(d);
+    } else {
+        bool full = refactor || !d->dense_factored || d->sigma_f != d->dense_fact_sigma;
+        if (!full && d->wb_enable) {
+            int overflow = 0;
+            rc = wb_extend(d, &overflow);
+            if (!rc && overflow) full = true;
+        }
+        if (!rc && full) rc = dense_factor(d, carry);
+        if (!rc) rc = dense_solve(d);
+    }
+    if (!rc && n) HIPCHK(hipMemcpyAsync(x, d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (!rc) rc = read_ctrl(d);
+    bool lost = false;
+    if (!rc && d->hctrl->cnt[C_CHAIN_ERR]) {
+        lost = true;
+        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0;
+    }
+    d->sigma_f = sigma_keep;
+    if (m) HIPCHK(hipMemcpyAsync(d->d, d_keep.data(), (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d->dx, dx_keep.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (rc) return rc;
+    if (lost) {
+        snprintf(g_err, sizeof(g_err), "direct solve: %s", d->linsolve == 3 ? "the band factorization met a pivot that is not a positive finite number"
+                                                                            : "a polling kernel lost its producer");
+        return QDEV_DIRECT_LOST;
+    }
+    return 0;
+}
+// the factor arrays of the last factorization (layouts: include/qpdo_amd_ext.h, qpdo_amd_download_factor)
+int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
+    HIPCHK(hipSetDevice(d->device));
+    const size_t ld = (size_t)d->dense_ld, nb = (size_t)d->dense_nblk, band = (size_t)d->band_np * (size_t)(d->band_b + 1);
+    if (which == 6) {
+        if (count < 4) return set_err(hipErrorInvalidValue, "download factor: the geometry needs 4 entries", __LINE__);
+        dst[0] = d->Kd ? (double)ld : 0.0; dst[1] = d->Kd ? (double)nb : 0.0; dst[2] = d->Kb ? (double)d->band_np : 0.0; dst[3] = d->Kb ? (double)d->band_b : 0.0;
+        return 0;
+    }
+    const double *src = nullptr; size_t len = 0;
+    switch (which) {
+        case 0: src = d->Kd; len = ld * ld; break;
+        case 1: src = d->Dg; len = ld; break;
+        case 2: src = d->Linv; len = nb * DNB * DNB; break;
+        case 3: src = d->LinvT; len = nb * DNB * DNB; break;
+        case 4: src = d->Kb; len = band; break;
+        case 5: src = d->Lt; len = band; break;
+        default: return set_err(hipErrorInvalidValue, "download factor: unknown array", __LINE__);
+    }
+    if (!src) return set_err(hipErrorInvalidValue, "download factor: this workspace has not factored with that solver", __LINE__);
+    if (count < 0 || (size_t)count != len) return set_err(hipErrorInvalidValue, "download factor: count is not the array's length", __LINE__);
+    HIPCHK(hipMemcpyAsync(dst, src, len * 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
 int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host) {
     HIPCHK(hipSetDevice(d->device));
     DevCsr *M = mat_by_id(d, which);

@@ -99,6 +99,7 @@ struct QpdoDev {
     int *wb_slot = nullptr, *wb_rows = nullptr, *wb_cnt = nullptr;
     hipEvent_t evF[2] = {nullptr, nullptr}, evB[2] = {nullptr, nullptr};
     int dense_last_branch = -1; double dense_last_sigma = -1.0;
+    int direct_hook_used = 0;      // qdev_direct_solve ran since the last solve: the next qdev_begin_solve drops its kept factor
     // n-vectors
     double *x, *xbar, *Qx, *Aty, *q, *df, *res_dual, *res_dual_in, *rhs, *dx, *Qdx, *Atdy, *D, *Dinv;
     double *pc_r, *pc_z, *pc_p, *pc_Kp, *pc_diag, *tmp_n;

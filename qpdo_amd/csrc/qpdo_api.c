@@ -1059,6 +1059,13 @@ int qpdo_amd_spmv(QPDOWorkspace *work, int which, const double *v, double *y) { 
 int qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const double *delta, const double *alpha, double *tau) {
     return qdev_linesearch(work->chol->dev, eta, beta, delta, alpha, tau);
 }
+int qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags) {
+    const int rc = qdev_direct_solve(work->chol->dev, dw, sigma, rhs, x, flags);
+    return rc == QDEV_DIRECT_LOST ? QPDO_AMD_DIRECT_LOST : rc ? -1 : 0;
+}
+int qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count) {
+    return qdev_download_factor(work->chol->dev, which, dst, count) ? -1 : 0;
+}
 int qpdo_amd_download(QPDOWorkspace *work, int which, double *dst) { return qdev_download_vec(work->chol->dev, which, dst); }
 int qpdo_amd_get_stats(const QPDOWorkspace *work, QPDOAmdStats *out) {
     QdevStats st;

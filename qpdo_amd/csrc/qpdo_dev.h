@@ -201,6 +201,11 @@ int qdev_bench_spmv(QpdoDev *d, int which, int reps, double *avg_seconds, double
 int qdev_bench_dense_factor(QpdoDev *d, int reps, double *avg_seconds, double *check);
 /* standalone SpMV for parity tests: y = M v */
 int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host);
+/* one solve of K x = rhs, K = Q + sigma I + A' diag(dw) A, through the workspace's direct solver (tests; qpdo_amd_direct_solve) and the
+ * factor arrays it left (qpdo_amd_download_factor).  QDEV_DIRECT_LOST: a polling kernel lost its producer / a bad band pivot. */
+#define QDEV_DIRECT_LOST (-9)
+int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *rhs, double *x, int flags);
+int qdev_download_factor(QpdoDev *d, int which, double *dst, long count);
 /* standalone piecewise-affine linesearch for parity tests (2m entries) */
 int qdev_linesearch(QpdoDev *d, double eta, double beta, const double *delta, const double *alpha,
                     double *tau);

@@ -108,7 +108,7 @@ class BatchItem(C.Structure):
 EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solve_batch", "qpdo_amd_batch_kernel_seconds", "qpdo_amd_batch_stream_create",
                "qpdo_amd_batch_stream_submit", "qpdo_amd_batch_stream_wait", "qpdo_amd_batch_stream_destroy", "qpdo_amd_device_count", "qpdo_amd_last_error", "qpdo_amd_get_stats", "qpdo_amd_get_trace",
                "qpdo_amd_sync", "qpdo_amd_pass_decision", "qpdo_amd_bench_spmv", "qpdo_amd_bench_dense_factor", "qpdo_amd_spmv", "qpdo_amd_linesearch", "qpdo_amd_download",
-               "qpdo_amd_update_matrices"]
+               "qpdo_amd_update_matrices", "qpdo_amd_direct_solve", "qpdo_amd_download_factor"]
 
 _lib = None
 
@@ -143,6 +143,10 @@ def lib():
         L.qpdo_amd_bench_dense_factor.argtypes = [W, C.c_int, dp, dp]
         L.qpdo_amd_linesearch.argtypes = [W, C.c_double, C.c_double, dp, dp, dp]
         L.qpdo_amd_download.argtypes = [W, C.c_int, dp]
+        L.qpdo_amd_direct_solve.argtypes = [W, dp, C.c_double, dp, dp, C.c_int]
+        L.qpdo_amd_direct_solve.restype = C.c_int
+        L.qpdo_amd_download_factor.argtypes = [W, C.c_int, dp, C.c_long]
+        L.qpdo_amd_download_factor.restype = C.c_int
         L.qpdo_amd_update_matrices.argtypes = [W, C.POINTER(CholmodSparse), C.POINTER(CholmodSparse)]
         L.qpdo_amd_update_matrices.restype = C.c_int
         L.qpdo_amd_dist_config.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -159,6 +163,13 @@ def lib():
         L.qpdo_amd_batch_stream_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
+
+
+DIRECT_LOST = -2       # QPDO_AMD_DIRECT_LOST (include/qpdo_amd_ext.h)
+
+
+class LostProducer(RuntimeError):
+    """qpdo_amd_direct_solve: a polling kernel lost its producer, or the band factorization met a bad pivot"""
 
 
 def device_count():
@@ -404,6 +415,45 @@ class QPDO:
         if rc:
             raise RuntimeError(lib().qpdo_amd_last_error().decode())
         return t.value
+
+    def direct_solve(self, dw, sigma, rhs, refactor=True, carry_forward=False):
+        """x = K^-1 rhs, K = Q + sigma I + A' diag(dw) A, through the workspace's direct solver (qpdo_amd_direct_solve).  A lost producer
+        (or a bad band pivot) raises LostProducer, any other failure RuntimeError."""
+        dw = np.ascontiguousarray(dw, np.float64)
+        rhs = np.ascontiguousarray(rhs, np.float64)
+        if len(dw) != self.m or len(rhs) != self.n:
+            raise ValueError("dw needs m entries and rhs n")
+        x = np.zeros(self.n)
+        rc = lib().qpdo_amd_direct_solve(self._w, _as_dp(dw), float(sigma), _as_dp(rhs), _as_dp(x), (1 if refactor else 0) | (2 if carry_forward else 0))
+        if rc:
+            msg = (lib().qpdo_amd_last_error() or b"").decode()
+            raise (LostProducer if rc == DIRECT_LOST else RuntimeError)("direct_solve: %s" % msg)
+        return x
+
+    def factor_geometry(self):
+        g = np.zeros(4)
+        if lib().qpdo_amd_download_factor(self._w, 6, _as_dp(g), 4):
+            raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+        return dict(ld=int(g[0]), nb=int(g[1]), np=int(g[2]), b=int(g[3]))
+
+    def download_factor(self, name):
+        """a factor array of the last factorization (layouts: include/qpdo_amd_ext.h).  Kd comes back as the ld x ld matrix (element
+        (i, j) = Kd[i, j]), Kb / Lt as np x (b + 1) arrays (row j = column / row j of the band), Dg flat, Linv / LinvT as their raw nb x 4096
+        arrays."""
+        g = self.factor_geometry()
+        ld, nb, npad, b = g["ld"], g["nb"], g["np"], g["b"]
+        which, count = {"Kd": (0, ld * ld), "Dg": (1, ld), "Linv": (2, nb * 4096), "LinvT": (3, nb * 4096),
+                        "Kb": (4, npad * (b + 1)), "Lt": (5, npad * (b + 1))}[name]
+        out = np.zeros(count)
+        if lib().qpdo_amd_download_factor(self._w, which, _as_dp(out), count):
+            raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+        if name == "Kd":
+            return out.reshape(ld, ld).T
+        if name in ("Kb", "Lt"):
+            return out.reshape(npad, b + 1)
+        if name in ("Linv", "LinvT"):
+            return out.reshape(nb, 4096)
+        return out
 
     def download(self, name):
         which, n = {"x": (0, self.n), "Qx": (1, self.n), "y": (2, self.m), "mu": (3, self.m), "d": (4, self.m),

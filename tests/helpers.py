@@ -137,3 +137,174 @@ def device_active_count_consistent(prob, settings, k):
     w, l, u = s.download("w"), s.download("l"), s.download("u")
     s.delete()
     return len(tr) == k + 1 and int(tr[k]["kind"]) == 0 and int(tr[k]["n_active"]) == int(((w <= l) | (w >= u)).sum())
+
+
+# ---- the direct solvers as linear solvers (tests/test_direct_solver_checks_cpu.py, tests/test_gpu_direct_solvers.py) ----------------------
+# The reference is K = Q + sigma I + A' diag(dw) A in extended precision (np.longdouble) from the problem's sparse data; the checks are the
+# textbook ones for an LDL' of an SPD matrix without pivoting and for a backward-stable solve, with u the unit roundoff of float64.
+U64 = np.finfo(np.float64).eps / 2
+
+
+def _coo(M):
+    import scipy.sparse as sp
+    M = sp.coo_matrix(M)
+    return M.row.astype(np.int64), M.col.astype(np.int64), M.data.astype(np.longdouble)
+
+
+def newton_matrix(Qfull, A, sigma, dw):
+    """dense K = Q + sigma I + A' diag(dw) A in np.longdouble (Qfull: the full symmetric Q; one outer product per row of A)"""
+    import scipy.sparse as sp
+    n = Qfull.shape[0]
+    K = np.zeros((n, n), np.longdouble)
+    qr, qc, qv = _coo(Qfull)
+    np.add.at(K, (qr, qc), qv)
+    K[np.arange(n), np.arange(n)] += np.longdouble(sigma)
+    A = sp.csr_matrix(A)
+    dw = np.asarray(dw, np.longdouble)
+    for r in range(A.shape[0]):
+        if dw[r] == 0:
+            continue
+        c = A.indices[A.indptr[r]:A.indptr[r + 1]]
+        v = A.data[A.indptr[r]:A.indptr[r + 1]].astype(np.longdouble)
+        K[np.ix_(c, c)] += dw[r] * np.outer(v, v)
+    return K
+
+
+def newton_residual(Qfull, A, sigma, dw, x, b):
+    """b - K x in np.longdouble in O(nnz), K never formed; also |K|inf (exact when no entry of K is a sum of terms of both signs, an upper
+    bound otherwise -- which only makes eta smaller than the true backward error by that cancellation)"""
+    n = Qfull.shape[0]
+    xl = np.asarray(x, np.longdouble)
+    qr, qc, qv = _coo(Qfull)
+    Kx = np.zeros(n, np.longdouble)
+    np.add.at(Kx, qr, qv * xl[qc])
+    Kx += np.longdouble(sigma) * xl
+    rowabs = np.zeros(n, np.longdouble)
+    np.add.at(rowabs, qr, np.abs(qv))
+    rowabs += abs(np.longdouble(sigma))
+    m = A.shape[0]
+    if m:
+        ar, ac, av = _coo(A)
+        dwl = np.asarray(dw, np.longdouble)
+        Ax = np.zeros(m, np.longdouble)
+        np.add.at(Ax, ar, av * xl[ac])
+        np.add.at(Kx, ac, av * (dwl * Ax)[ar])
+        Aabs1 = np.zeros(m, np.longdouble)
+        np.add.at(Aabs1, ar, np.abs(av))
+        np.add.at(rowabs, ac, np.abs(av) * (np.abs(dwl) * Aabs1)[ar])
+    return np.asarray(b, np.longdouble) - Kx, float(rowabs.max()) if n else 0.0
+
+
+def backward_error(Qfull, A, sigma, dw, x, b, K=None):
+    """normwise backward error of a solve: |b - K x|inf / (|K|inf |x|inf + |b|inf); K (dense, optional) gives the exact |K|inf"""
+    r, kinf = newton_residual(Qfull, A, sigma, dw, x, b)
+    if K is not None:
+        kinf = float(np.abs(K).sum(axis=1).max())
+    den = kinf * float(np.abs(x).max()) + float(np.abs(b).max())
+    return float(np.abs(r).max()) / den if den > 0 else float(np.abs(r).max())
+
+
+def ldl_elementwise_ratio(K, L, D, c=4.0):
+    """max over the lower triangle of |K - L D L'| / (c n u |L| |D| |L'|): <= 1 is the textbook componentwise bound of an LDL' without
+    pivoting of an SPD matrix (Higham, Accuracy and Stability of Numerical Algorithms, 10.1); c = 4 covers the check's own rounding (the
+    product is evaluated in float64 BLAS).  An entry whose bound is 0 must be reproduced exactly (else the ratio is inf)."""
+    n = K.shape[0]
+    L = np.asarray(L, np.float64)
+    D = np.asarray(D, np.float64)
+    LD = L * D[None, :]
+    E = np.abs(np.asarray(K, np.longdouble) - (LD @ L.T).astype(np.longdouble)).astype(np.float64)
+    bound = c * n * U64 * ((np.abs(LD)) @ np.abs(L).T)
+    low = np.tril(np.ones((n, n), bool))
+    zero = low & (bound == 0)
+    if np.any(E[zero] != 0):
+        return float("inf")
+    nz = low & (bound > 0)
+    return float((E[nz] / bound[nz]).max()) if nz.any() else 0.0
+
+
+def ldl_normwise_ratio(K, L, D, c=4.0):
+    """max |K - L D L'| / (c n u max |L| |D| |L'|) over the lower triangle: the normwise form of the bound above"""
+    n = K.shape[0]
+    L = np.asarray(L, np.float64)
+    LD = L * np.asarray(D, np.float64)[None, :]
+    E = np.abs(np.asarray(K, np.longdouble) - (LD @ L.T).astype(np.longdouble)).astype(np.float64)
+    bound = c * n * U64 * float(np.tril(np.abs(LD) @ np.abs(L).T).max())
+    return float(np.tril(E).max()) / bound if bound > 0 else float(np.tril(E).max())
+
+
+def blocked_ldl_with_inverse(K, nb=64):
+    """a right-looking blocked LDL' whose panels are C L_jj^-T / D_j with the explicit inverse of the unit-lower diagonal block -- the
+    scheme of the device's factorizations (k_ldl_panel, k_mid_factor), for the CPU comparison of its componentwise accuracy"""
+    A = np.array(K, np.float64)
+    n = A.shape[0]
+    L, D = np.eye(n), np.zeros(n)
+    for j0 in range(0, n, nb):
+        j1 = min(n, j0 + nb)
+        Lb, Db = ldl_numpy(A[j0:j1, j0:j1])
+        L[j0:j1, j0:j1], D[j0:j1] = Lb, Db
+        X = A[j1:, j0:j1] @ np.linalg.inv(Lb).T
+        L[j1:, j0:j1] = X / Db[None, :]
+        A[j1:, j1:] -= X @ L[j1:, j0:j1].T
+    return L, D
+
+
+def ldl_numpy(K):
+    """a plain right-looking LDL' without pivoting (float64): unit-lower L and D with K = L D L'"""
+    A = np.array(K, np.float64)
+    n = A.shape[0]
+    L = np.eye(n)
+    D = np.zeros(n)
+    for j in range(n):
+        D[j] = A[j, j]
+        L[j + 1:, j] = A[j + 1:, j] / D[j]
+        A[j + 1:, j + 1:] -= np.outer(L[j + 1:, j], A[j + 1:, j])
+    return L, D
+
+
+def tiled_factor_image(L, D, tile=64):
+    """the dense solver's storage of a factor (include/qpdo_amd_ext.h, qpdo_amd_download_factor): ld x ld, L strictly below the diagonal,
+    its transposed copy in the upper triangle of every off-diagonal tile, identity padding; and D padded with ones"""
+    n = L.shape[0]
+    ld = (n + tile - 1) // tile * tile
+    Kd = np.eye(ld)
+    Kd[:n, :n] = np.tril(L, -1)
+    blk = np.arange(ld) // tile
+    off = blk[:, None] != blk[None, :]
+    up = np.triu(off, 1)
+    Kd[up] = Kd.T[up]
+    Dg = np.ones(ld)
+    Dg[:n] = D
+    return Kd, Dg
+
+
+def factor_from_image(Kd, Dg, n):
+    """L (unit lower, n x n) and D from the dense solver's storage"""
+    return np.tril(Kd[:n, :n], -1) + np.eye(n), np.asarray(Dg[:n], np.float64)
+
+
+def transposed_copy_mismatch(Kd, tile=64):
+    """number of entries of the off-diagonal tiles whose upper-triangle copy is not bit for bit the lower-triangle L"""
+    ld = Kd.shape[0]
+    blk = np.arange(ld) // tile
+    low = blk[:, None] > blk[None, :]
+    lo = Kd[low]
+    cp = Kd.T[low]
+    return int(np.count_nonzero(lo.view(np.uint64) != cp.view(np.uint64)))
+
+
+def solve_with_image(Kd, Dg, b, tile=64):
+    """x = K^-1 b the way the device's triangular solves read the storage: forward with L below the diagonal, backward with the
+    transposed copies of the off-diagonal tiles (and the diagonal tiles' own L, as the stored inverses are)"""
+    ld = Kd.shape[0]
+    n = len(b)
+    z = np.zeros(ld)
+    z[:n] = b
+    Lfwd = np.tril(Kd, -1) + np.eye(ld)
+    blk = np.arange(ld) // tile
+    same = blk[:, None] == blk[None, :]
+    Ubwd = np.where(same, np.tril(Kd, -1).T, np.triu(Kd, 1)) + np.eye(ld)       # upper: L' from the copies, the diagonal tiles' own L'
+    import scipy.linalg as sla
+    y = sla.solve_triangular(Lfwd, z, lower=True, unit_diagonal=True)
+    y /= Dg
+    x = sla.solve_triangular(Ubwd, y, lower=False, unit_diagonal=True)
+    return x[:n]
