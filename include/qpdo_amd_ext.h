@@ -32,6 +32,14 @@
  *                    section 5; read at qpdo_setup; QPDOAmdStats.ahead_steps / ahead_skips).  The same kernels in the same order: the same bits,
  *                    except on a pass whose factor the host-first path would keep (it is refactored: the same matrix)
  *   QPDO_DENSE_LOWRANK  "0": refactor on every weight change, "1": low-rank update of the kept dense factor (default: from n = 9000 up)
+ *   QPDO_DENSE_UPDOWN   unset or "0": off (default).  "1" or "<k>" (k > 1): a Newton pass that keeps sigma and changes the weight of at most k rows of
+ *                    A (k = 1 for "1"; at most 64) changes the kept dense factor IN PLACE, one row at a time (K' = K + delta a a': a chained
+ *                    forward solve, a prefix scan for D' and the multipliers, one streaming pass over the tiles of L that also rewrites the
+ *                    transposed copies and the diagonal blocks' inverses) instead of factoring again; more rows take the
+ *                    path they took without it (QPDO_DENSE_LOWRANK if on, else a factorization).  While the factor carries such a change every
+ *                    solve is checked against the true K (three SpMV; refinement sweeps as on the low-rank path) and a failed check, or a
+ *                    downdate whose scan meets a non-positive pivot, refactors (QPDOAmdStats.updown_*).  Dense solver with the chained
+ *                    solves on one GPU only; switches the launch-ahead route off (it refactors every pass by construction).  Read at qpdo_setup
  *   QPDO_DENSE_LOOKAHEAD "0": factor on one stream, "1": overlap the next panel with the trailing update (default: from n = 7000 up;
  *                    read at qpdo_setup)
  *   QPDO_DENSE_SOLVE "steps": per-block-step triangular solve kernels instead of the one-launch chained solves
@@ -113,6 +121,12 @@ typedef struct {
     long   onelaunch_factors;/* dense factorizations that ran as ONE launch of the tile-dataflow kernel (k_mid_factor, the default)          */
     long   ahead_steps;     /* Newton steps launched ahead of the host's decision (mid-size dense route, QPDO_LAUNCH_AHEAD) that ran ...   */
     long   ahead_skips;     /* ... and passes whose launched-ahead step left at once because the pass was an outer update or the last one  */
+    /* in-place up/downdate of the kept dense factor (QPDO_DENSE_UPDOWN; appended: the members above keep their offsets) */
+    long   updown_solves;   /* dense solves with a kept factor that carries up/downdates, accepted by their residual check (no factorization) */
+    long   updown_rows;     /* changed rows of A SENT through the up/downdate (three launches each; a row its scan refuses, and the rows behind it in that
+                             * pass, are counted but never touch the factor: updown_rejects); factor_count does not move on such a pass */
+    long   updown_rejects;  /* up/downdated factors given up for a refactorization: a scan met a pivot that is not a positive finite number
+                             * (the factor was not touched by that row), or a solve missed its residual check after the refinement sweeps */
 } QPDOAmdStats;
 
 int  qpdo_amd_device_count(void);
@@ -160,7 +174,9 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
  * it: the dense LDL' (QPDO_LINSOLVE=dense, with its QPDO_DENSE_* routes) or the band LDL' (QPDO_LINSOLVE=band).
  *   flags bit 0  refactor.  Clear: the factor kept from the previous call is reused -- with QPDO_DENSE_LOWRANK on, every row whose weight
  *                differs from the factored one gets a low-rank slot (more than 256 such rows refactor); otherwise it is reused as it is,
- *                i.e. the caller passes the factored weights.  No factor yet, or (dense) another sigma: refactor.
+ *                i.e. the caller passes the factored weights.  No factor yet, or (dense) another sigma: refactor.  With QPDO_DENSE_UPDOWN on,
+ *                rows whose weight differs go through the in-place up/downdate of the kept factor if they are at most its cap (and no
+ *                low-rank slot is held); more rows take the low-rank path if that is on and refactor otherwise.
  *   flags bit 1  the factorization launch carries the forward solve along (one-launch route of the dense factor).
  * Returns 0; QPDO_AMD_DIRECT_LOST when a polling kernel lost its producer or the band factorization met a pivot that is not a positive
  * finite number (the latch is cleared, the result is not redone, qpdo_amd_last_error says which); -1 on any other failure, including a

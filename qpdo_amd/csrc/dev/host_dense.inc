@@ -36,9 +36,19 @@ static int dense_alloc(QpdoDev *d) {
             if (e != hipSuccess) rc = set_err(e, "hipFuncSetAttribute", __LINE__);
         }
     }
+    if (!rc && (d->wb_enable || d->ud_cap)) rc = dev_alloc(d, &d->d_fact, d->m > 0 ? (size_t)d->m : 1);
+    if (!rc && d->ud_cap) {
+        rc = dev_alloc(d, &d->ud_a, (size_t)ld * UD_CAP_MAX);
+        if (!rc) rc = dev_alloc(d, &d->ud_p, (size_t)ld * UD_CAP_MAX);
+        if (!rc) rc = dev_alloc(d, &d->ud_q, (size_t)ld * UD_CAP_MAX);
+        if (!rc) rc = dev_alloc(d, &d->ud_G, (size_t)ld * d->dense_nblk);
+        if (!rc) rc = dev_alloc(d, &d->ud_Dn, (size_t)ld);
+        if (!rc) rc = dev_alloc(d, &d->ud_beta, (size_t)ld);
+        if (!rc) rc = dev_alloc(d, &d->ud_rows, (size_t)UD_CAP_MAX);
+        if (!rc) rc = dev_alloc(d, &d->ud_cnt, (size_t)2);
+    }
     if (!rc && d->wb_enable) {
         const size_t mm = d->m > 0 ? (size_t)d->m : 1;
-        rc = dev_alloc(d, &d->d_fact, mm);
         if (!rc) rc = dev_alloc(d, &d->wb_Z, (size_t)ld * (WB_MAX + 16));      // + one padding group of right-hand sides
         if (!rc) rc = dev_alloc(d, &d->wb_T, (size_t)ld * (WB_MAX + 16));
         if (!rc) rc = dev_alloc(d, &d->wb_T2, (size_t)ld * (WB_MAX + 16));
@@ -92,11 +102,9 @@ static int dense_factor(QpdoDev *d, bool with_rhs = false) {
         d->mid_fwd_valid = with_rhs ? 1 : 0;
         d->st.onelaunch_factors++;
         d->dense_valid = 1;
-        d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0;
-        if (d->wb_enable && d->m > 0) {
-            HIPCHK(hipMemcpyAsync(d->d_fact, d->d, (size_t)d->m * 8, hipMemcpyDeviceToDevice, d->stream));
-            HIPCHK(hipMemsetAsync(d->wb_slot, 0xFF, (size_t)d->m * sizeof(int), d->stream));
-        }
+        d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0; d->ud_dirty = 0;
+        if (d->d_fact && d->m > 0) HIPCHK(hipMemcpyAsync(d->d_fact, d->d, (size_t)d->m * 8, hipMemcpyDeviceToDevice, d->stream));
+        if (d->wb_enable && d->m > 0) HIPCHK(hipMemsetAsync(d->wb_slot, 0xFF, (size_t)d->m * sizeof(int), d->stream));
         d->st.factor_count++;
         return 0;
     }
@@ -148,11 +156,10 @@ static int dense_factor(QpdoDev *d, bool with_rhs = false) {
     if (b_pending) HIPCHK(hipStreamWaitEvent(sc, d->evB[(p - 1) & 1], 0));
     HIPCHK(hipGetLastError());
     d->dense_valid = 1;
-    d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0;
-    if (d->wb_enable && d->m > 0) {        // the factor belongs to this weight vector; no row holds a low-rank slot
-        HIPCHK(hipMemcpyAsync(d->d_fact, d->d, (size_t)d->m * 8, hipMemcpyDeviceToDevice, d->stream));
-        HIPCHK(hipMemsetAsync(d->wb_slot, 0xFF, (size_t)d->m * sizeof(int), d->stream));
-    }
+    d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0; d->ud_dirty = 0;
+    // the factor belongs to this weight vector; no row holds a low-rank slot
+    if (d->d_fact && d->m > 0) HIPCHK(hipMemcpyAsync(d->d_fact, d->d, (size_t)d->m * 8, hipMemcpyDeviceToDevice, d->stream));
+    if (d->wb_enable && d->m > 0) HIPCHK(hipMemsetAsync(d->wb_slot, 0xFF, (size_t)d->m * sizeof(int), d->stream));
     d->st.factor_count++;
     return 0;
 }
@@ -187,8 +194,62 @@ __global__ void k_add_to(int n, const double *__restrict__ a, double *__restrict
 }
 static const double WB_RES_TOL = 1e-13;    // relative inf-norm residual accepted for a low-rank solve
 static const int WB_MAX_REFINE = 5;
+// Residual check and refinement of a solve whose inner solver is not a fresh factorization (the low-rank path, an up/downdated factor):
+// r = rhs - K dx on the true K = Q + sigma I + A' diag(d) A by three SpMV, accepted at WB_RES_TOL relative to |rhs|inf; up to WB_MAX_REFINE
+// sweeps, a sweep that does not reduce the residual fourfold ends them and is accepted only near the floor.  inner(it) enqueues sweep
+// it: dx (it = 0) or its correction from r (in d->pc_r); guard() is asked after each read-back and ends the sweeps without acceptance.
+// The one copy of the acceptance rule; *ok = 0: the caller refactors.
+extern "C++" template <class Inner, class Guard>
+static int dense_refine_checked(QpdoDev *d, Inner inner, Guard guard, bool *ok) {
+    const int n = d->n;
+    *ok = false;
+    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
+    LAUNCH(k_absmax_mul, vgrid(n), n, (const double *)d->rhs, (const double *)nullptr, d->ctrl, N_A);
+    double prev = 0.0;
+    for (int it = 0; it <= WB_MAX_REFINE; it++) {
+        int rc = inner(it); if (rc) return rc;
+        // r = rhs - K dx
+        LAUNCH(k_ctrl_set_nrm0, 1, d->ctrl, N_B);
+        launch_spmv(d, d->Ar, d->dx, EpiPcgA{d->d, d->tmp_m, nullptr}, false);
+        launch_spmv(d, d->Qf, d->dx, EpiPcgQ{d->dx, d->sigma_f, d->pc_Kp}, false);
+        launch_spmv(d, d->At, d->tmp_m, EpiResid{d->rhs, d->pc_Kp, d->pc_r, d->ctrl, N_B}, true);
+        bool go = true;
+        rc = guard(&go); if (rc) return rc;                  // (reads the control block back)
+        const double nb_ = nrm_of(d->hctrl, N_A), nr_ = nrm_of(d->hctrl, N_B);
+        if (!go) break;
+        if (nr_ <= WB_RES_TOL * nb_) { *ok = true; break; }
+        if (it > 0 && !(nr_ < 0.25 * prev)) { *ok = nr_ <= 1e3 * WB_RES_TOL * nb_; break; }      // stalled: accept only near the floor
+        prev = nr_;
+    }
+    return 0;
+}
+// A solve with a kept factor that carries in-place up/downdates (d->ud_dirty; dev/updown.inc).  A downdate of a heavy row cancels
+// digits of D and L (the recurrence itself does: tests/test_dense_updown_cpu.py), so the result is checked exactly as the low-rank path
+// checks its own (dense_refine_checked), with the updated factor as the inner solver.  A failed check -- or the latch of a scan that
+// refused a row, which arrives with the same read-back -- refactors and solves again.
+static int dense_solve_updown(QpdoDev *d) {
+    const int n = d->n;
+    bool ok = false;
+    int rc = dense_refine_checked(d, [&](int it) -> int {
+        if (it == 0) return dense_solve_core(d, d->rhs, d->dx);
+        int rci = dense_solve_core(d, d->pc_r); if (rci) return rci;
+        LAUNCH(k_add_to, vgrid(n), n, (const double *)d->dsol, d->dx);
+        return 0;
+    }, [&](bool *go) -> int {
+        int rcg = read_ctrl(d); if (rcg) return rcg;
+        *go = d->hctrl->cnt[C_UD_REJECT] == 0;
+        return 0;
+    }, &ok);
+    if (rc) return rc;
+    if (ok) { d->st.updown_solves++; return 0; }
+    d->st.updown_rejects++;
+    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_UD_REJECT, 0);
+    rc = dense_factor(d); if (rc) return rc;
+    return dense_solve_core(d, d->rhs, d->dx);
+}
 static int dense_solve(QpdoDev *d) {
     const int n = d->n, ld = d->dense_ld, k = d->wb_k;
+    if (k == 0 && d->ud_dirty) return dense_solve_updown(d);
     int rc = dense_solve_core(d, d->rhs, k == 0 ? d->dx : (double *)nullptr); if (rc) return rc;
     if (k == 0) return 0;
     // Low-rank path.  One application  e = z0 - Z (I + W G)^-1 W U z0,  z0 = K0^-1 r,  is the solve with the updated
@@ -197,12 +258,9 @@ static int dense_solve(QpdoDev *d) {
     // So it is used as the inner solver of an iterative refinement on the true K = Q + sigma I + A' diag(d) A
     // (three SpMV per sweep) until the residual is at the level of a fresh factorization; a sweep that stalls, a
     // NaN or a tiny pivot of I + W G (a downdate removing most of a direction of K0) falls back to refactoring.
-    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
-    LAUNCH(k_absmax_mul, vgrid(n), n, (const double *)d->rhs, (const double *)nullptr, d->ctrl, N_A);
     bool ok = false;
-    double prev = 0.0;
-    for (int it = 0; it <= WB_MAX_REFINE; it++) {
-        if (it > 0) { rc = dense_solve_core(d, d->pc_r); if (rc) return rc; }
+    rc = dense_refine_checked(d, [&](int it) -> int {
+        if (it > 0) { int rci = dense_solve_core(d, d->pc_r); if (rci) return rci; }
         hipLaunchKernelGGL(k_wb_v, dim3(k), dim3(64), 0, d->stream, (const int *)d->wb_rows, d->Ar.rp, d->Ar.ci, d->Ar.val, (const double *)d->dsol,
                            (const double *)d->d, (const double *)d->d_fact, d->wb_v, d->wb_w);
         hipLaunchKernelGGL(k_wb_lu, dim3(1), dim3(1024), k <= WB_LDS_MAX ? (size_t)k * (k + 2) * 8 : 0, d->stream, k, (const double *)d->wb_G, (const double *)d->wb_w,
@@ -213,21 +271,16 @@ static int dense_solve(QpdoDev *d) {
             LAUNCH(k_wb_apply, vgrid(n), n, ld, k, (const double *)d->wb_Z, (const double *)d->wb_t, (const double *)d->dsol, d->pc_z);
             LAUNCH(k_add_to, vgrid(n), n, (const double *)d->pc_z, d->dx);
         }
-        // r = rhs - K dx
-        LAUNCH(k_ctrl_set_nrm0, 1, d->ctrl, N_B);
-        launch_spmv(d, d->Ar, d->dx, EpiPcgA{d->d, d->tmp_m, nullptr}, false);
-        launch_spmv(d, d->Qf, d->dx, EpiPcgQ{d->dx, d->sigma_f, d->pc_Kp}, false);
-        launch_spmv(d, d->At, d->tmp_m, EpiResid{d->rhs, d->pc_Kp, d->pc_r, d->ctrl, N_B}, true);
+        return 0;
+    }, [&](bool *go) -> int {
         double minpiv = 0.0;
         HIPCHK(hipMemcpyAsync(&minpiv, d->wb_t + WB_MAX, sizeof(double), hipMemcpyDeviceToHost, d->stream));
-        rc = read_ctrl(d); if (rc) return rc;
-        const double nb_ = nrm_of(d->hctrl, N_A), nr_ = nrm_of(d->hctrl, N_B);
+        int rcg = read_ctrl(d); if (rcg) return rcg;
         d->st.lowrank_sweeps++;
-        if (!(minpiv >= WB_MIN_PIVOT)) break;
-        if (nr_ <= WB_RES_TOL * nb_) { ok = true; break; }
-        if (it > 0 && !(nr_ < 0.25 * prev)) { ok = nr_ <= 1e3 * WB_RES_TOL * nb_; break; }      // stalled: accept only near the floor
-        prev = nr_;
-    }
+        *go = minpiv >= WB_MIN_PIVOT;
+        return 0;
+    }, &ok);
+    if (rc) return rc;
     if (ok) { d->st.lowrank_solves++; return 0; }
     d->st.lowrank_rejects++;
     rc = dense_factor(d); if (rc) return rc;
@@ -268,4 +321,35 @@ static int wb_extend(QpdoDev *d, int *overflow) {
     d->st.lowrank_cols += k_new;
     return 0;
 }
-
+// In-place up/downdate of the kept factor (dev/updown.inc) for the rows whose weight differs from the factored one.  *applied = 0: more
+// than d->ud_cap rows differ and nothing was touched (the caller takes the path it took without this route); 1: the rows -- possibly
+// none -- are in the stream one after another (chained forward solve, scan + tile products, streaming pass), d_fact follows on the
+// device, no factorization.  A row whose scan refuses it stops there and behind it: the solve that follows reads the latch.
+static int ud_apply(QpdoDev *d, int *applied) {
+    const int ld = d->dense_ld, nb = d->dense_nblk;
+    *applied = 0;
+    int cnt = 0;
+    if (d->m > 0) {
+        hipLaunchKernelGGL(k_ud_select, dim3(1), dim3(1024), 0, d->stream, d->m, (const double *)d->d, (const double *)d->d_fact, d->ud_cap, d->ud_rows, d->ud_cnt);
+        HIPCHK(hipMemcpyAsync(&cnt, d->ud_cnt, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+    }
+    if (cnt > d->ud_cap) return 0;
+    *applied = 1;
+    if (cnt == 0) return 0;
+    d->mid_fwd_valid = 0;
+    hipLaunchKernelGGL(k_ud_load, dim3(cnt), dim3(256), 0, d->stream, ld, (const int *)d->ud_rows, d->Ar.rp, d->Ar.ci, d->Ar.val, d->ud_a, d->ud_p, d->ud_q);
+    for (int k = 0; k < cnt; k++) {
+        const double *a = d->ud_a + (size_t)k * ld, *p = d->ud_p + (size_t)k * ld, *q = d->ud_q + (size_t)k * ld;
+        hipLaunchKernelGGL(k_ldl_chain<true>, dim3(1, nb), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->Linv,
+                           (const double *)d->Dg, a, (double *)p, (double *)q, ld, d->ctrl);
+        hipLaunchKernelGGL(k_ud_prep, dim3(nb, nb + 1), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->Dg, p, q,
+                           (const int *)d->ud_rows, k, (const double *)d->d, (const double *)d->d_fact, d->ud_G, d->ud_Dn, d->ud_beta, d->ctrl);
+        hipLaunchKernelGGL(k_ud_apply, dim3(nb, nb), dim3(256), 0, d->stream, d->Kd, ld, nb, d->Dg, d->Linv, d->LinvT, a, p, (const double *)d->ud_G,
+                           (const double *)d->ud_Dn, (const double *)d->ud_beta, (const int *)d->ud_rows, k, (const double *)d->d, d->d_fact, (const Ctrl *)d->ctrl);
+    }
+    HIPCHK(hipGetLastError());
+    d->ud_dirty = 1;
+    d->st.updown_rows += cnt;              // rows SENT: one that its scan refuses, and the rows behind it, never touch the factor (updown_rejects then counts the pass)
+    return 0;
+}

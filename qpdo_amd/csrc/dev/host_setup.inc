@@ -261,6 +261,11 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     // 10000: 297 | 356, 12000: 578 | 691; profiles/r05_lowrank_crossover.txt)
     else d->wb_enable = d->n >= 9000;
     if (!d->dense_chain) d->wb_enable = 0;                       // the refinement sweeps assume the one-launch solves
+    // In-place up/downdate of the kept factor for passes that change few weights (dev/updown.inc): opt-in.  "1": at most UD_DEFAULT_CAP
+    // changed rows per pass, "<k>" (k > 1): at most k (<= UD_CAP_MAX); more rows take the path they took without it.  Needs the chained
+    // solves (p = L^-1 a is one of them); dense solver on one GPU only (checked below, once the solver is chosen).
+    { const char *ud = getenv("QPDO_DENSE_UPDOWN"); const int k = (ud && *ud) ? atoi(ud) : 0; d->ud_cap = k <= 0 ? 0 : k == 1 ? UD_DEFAULT_CAP : k > UD_CAP_MAX ? UD_CAP_MAX : k; }
+    if (!d->dense_chain) d->ud_cap = 0;
     // The direct solver is bounded by HBM, not by LDS (the assembly tiles its accumulator): DENSE_LIMIT_N = 40000 keeps the dense
     // matrix (12.8 GB at that order; look-ahead buffers beside it) and every 32-bit tile index in range.
     if (d->dense_max_n > DENSE_LIMIT_N) d->dense_max_n = DENSE_LIMIT_N;
@@ -295,9 +300,10 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
         d->hybrid = (want != 0 && linsolve < 0 && d->linsolve == 1 && d->n >= nmin && !d->comm.active) ? 1 : 0;
         if (want > 1) d->hybrid_budget = want;
     }
+    if (d->linsolve != 1 || d->comm.active) d->ud_cap = 0;
     d->st.linsolve = d->linsolve;
     d->cfg.linsolve = d->linsolve; d->cfg.dense_chain = d->dense_chain; d->cfg.dense_mid = d->dense_mid; d->cfg.dense_lookahead = d->dense_lookahead;
-    d->cfg.wb_enable = d->wb_enable; d->cfg.deflate = d->deflate; d->cfg.pcg_maxit = d->pcg_maxit; d->cfg.band_b = d->band_b;
+    d->cfg.wb_enable = d->wb_enable; d->cfg.ud_cap = d->ud_cap; d->cfg.deflate = d->deflate; d->cfg.pcg_maxit = d->pcg_maxit; d->cfg.band_b = d->band_b;
     return 0;
 }
 // absolute stopping rule of the linear solves follows the caller's eps_abs (QPDO_PCG_ABS: the factor, default 1e-5; 0 disables)
@@ -528,6 +534,7 @@ int qdev_begin_solve(QpdoDev *d) {
     // the lost-producer latch of the polling kernels is cleared by the redo (step_redo_if_lost) -- and here, so that a solve that was
     // left between the latch and its redo (a HIP error on the way) cannot make k_axpy5 skip every iterate update of the next solve
     LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+    if (d->ud_cap) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_UD_REJECT, 0);      // (likewise the up/downdate's latch)
     if (d->m) HIPCHK(hipMemsetAsync(d->active_old, 0, (size_t)d->m * sizeof(int), d->stream));
     return 0;
 }

@@ -90,7 +90,7 @@ static int step_redo_if_lost(QpdoDev *d, int proximal, double sigma) {
     }
     const int m = d->m;
     LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-    d->dense_chain = 0; d->dense_mid = 0; d->wb_enable = 0; d->st.chain_fallbacks++;
+    d->dense_chain = 0; d->dense_mid = 0; d->wb_enable = 0; d->ud_cap = 0; d->st.chain_fallbacks++;
     LAUNCH(k_newton_prep, vgrid(m), m, 3, d->active, d->active_old, d->isq, d->mu, d->res_prim_in, d->d, d->dy);      // dy = t again
     int rc = spmv_At(d, d->dy, EpiRhs{d->res_dual_in, d->Atdy, d->rhs}, false); if (rc) return rc;
     rc = dense_factor(d); if (rc) return rc;
@@ -141,12 +141,13 @@ static int pcg_rescue(QpdoDev *d, int *lin) {
 // paid on the outer-update passes and the last one).  The host reads the control block while the step runs, makes its own decision as
 // before, and qdev_newton_step only books what is already in flight -- after checking that both decisions agree.
 // Route: dense one-launch factorization (k_mid_factor) + chained backward solve, every pass refactors (no low-rank path: n < 9000),
-// one GPU, the one-launch linesearch, deferred step with the axpys folded into the next residual launch.  The kernels, their grids
+// one GPU, the one-launch linesearch, deferred step with the axpys folded into the next residual launch.  Not with QPDO_DENSE_UPDOWN:
+// this route refactors every pass by construction, that one exists to keep the factor.  The kernels, their grids
 // and their order are those of qdev_newton_step -> dense_factor / dense_solve / newton_finish_step: the same bits.
 static bool ahead_route_ok(const QpdoDev *d) {
     return d->launch_ahead && d->linsolve == 1 && !d->hybrid_active && !d->comm.active && d->defer_step && d->fuse_resid && d->ctrl_publish &&
            d->fuse_outer && d->m > 0 && !d->Qf.use_slab && !d->Ar.use_slab && !d->At.use_slab && d->ls_small && 2 * d->m <= LS_SMALL_MAX &&
-           d->Kd && d->dense_mid && d->dense_chain && d->mid_flags && d->dense_nblk <= MID_MAX_NB && !d->wb_enable;
+           d->Kd && d->dense_mid && d->dense_chain && d->mid_flags && d->dense_nblk <= MID_MAX_NB && !d->wb_enable && !d->ud_cap;
 }
 static int ahead_enqueue_step(QpdoDev *d, int proximal, double sigma) {
     const int n = d->n, m = d->m, ld = d->dense_ld, nb = d->dense_nblk;
@@ -245,13 +246,20 @@ int qdev_newton_step(QpdoDev *d, int branch, int n_changed, int proximal, double
         // and is read back with the step)
         if (!d->dense_valid) {
             // reference: full factorization in branch 0, rank update of the kept factor otherwise (newton.c:21-33)
-            bool full = !d->dense_factored || branch == 0 || !d->wb_enable || d->sigma_f != d->dense_fact_sigma;
-            if (!full) {
-                int overflow = 0;
-                rc = wb_extend(d, &overflow); if (rc) return rc;
-                if (overflow) full = true; else d->dense_valid = 1;
+            bool full = !d->dense_factored || branch == 0 || d->sigma_f != d->dense_fact_sigma;
+            // QPDO_DENSE_UPDOWN: few changed rows change the kept factor in place (no low-rank slot held: its columns belong to the factor as it was)
+            int updated = 0;
+            if (!full && d->ud_cap > 0 && d->wb_k == 0) { rc = ud_apply(d, &updated); if (rc) return rc; }
+            if (updated) d->dense_valid = 1;
+            else {
+                if (!d->wb_enable) full = true;
+                if (!full) {
+                    int overflow = 0;
+                    rc = wb_extend(d, &overflow); if (rc) return rc;
+                    if (overflow) full = true; else d->dense_valid = 1;
+                }
+                if (full) { rc = dense_factor(d, true); if (rc) return rc; }
             }
-            if (full) { rc = dense_factor(d, true); if (rc) return rc; }
         }
         rc = dense_solve(d); if (rc) return rc;
 #ifdef QPDO_TEST_HOOKS
@@ -632,7 +640,8 @@ int qdev_bench_dense_factor(QpdoDev *d, int reps, double *avg_seconds, double *c
 // K x = rhs with K = Q + sigma I + A' diag(dw) A, through the workspace's direct solver as a Newton pass drives it: dense_factor /
 // wb_extend / dense_solve (linsolve 1) or band_factor / band_solve (3), no other kernels.  flags bit 0: refactor; clear: a kept factor of
 // this sigma is reused -- with the low-rank update for the rows whose weight moved since it when wb_enable is set (more than WB_MAX of
-// them refactor), as it is (the caller passes the factored weights) otherwise.  Bit 1: the factorization launch carries the forward
+// them refactor), as it is (the caller passes the factored weights) otherwise; with ud_cap set, up to that many changed rows change the
+// kept factor in place (ud_apply) and more of them take the low-rank path or, without it, refactor.  Bit 1: the factorization launch carries the forward
 // solve (dense_factor(d, true)).  The workspace's weights, sigma_f and dx are put back afterwards; the kept factor stays for the next
 // call and is dropped by the next qdev_begin_solve.  A lost producer of a polling kernel, or a bad band pivot, returns
 // QDEV_DIRECT_LOST with the latch cleared -- never a silent redo.
@@ -651,6 +660,7 @@ int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *
     d->sigma_f = sigma;
     d->direct_hook_used = 1;
     LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+    if (d->ud_cap) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_UD_REJECT, 0);      // (a latch left by a call that ended early is not this call's)
     const bool refactor = (flags & 1) != 0, carry = (flags & 2) != 0;
     int rc = 0;
     if (d->linsolve == 3) {
@@ -658,7 +668,10 @@ int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *
         if (!rc) rc = band_solve(d);
     } else {
         bool full = refactor || !d->dense_factored || d->sigma_f != d->dense_fact_sigma;
-        if (!full && d->wb_enable) {
+        int updated = 0;
+        if (!full && d->ud_cap > 0 && d->wb_k == 0) rc = ud_apply(d, &updated);
+        if (!rc && !full && !updated && d->ud_cap > 0 && !d->wb_enable) full = true;      // more changed rows than the cap: refactor
+        if (!rc && !full && !updated && d->wb_enable) {
             int overflow = 0;
             rc = wb_extend(d, &overflow);
             if (!rc && overflow) full = true;

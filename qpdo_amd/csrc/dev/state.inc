@@ -5,6 +5,7 @@
 enum { N_PRIM = 0, N_DUAL, N_PRIM_IN, N_DUAL_IN, N_A, N_B, N_C, N_D, N_COUNT };
 enum { C_ACTIVE = 0, C_ENTER, C_LEAVE, C_NL, C_KSTAR, C_MUCH, C_VIOL, C_PCG_DONE, C_PCG_IT, C_CHAIN_ERR, C_DINF,
        C_SPEC_SKIP, C_SPEC_BRANCH,            // launch-ahead of the Newton step (k_resid_mn decides, host_step.inc spec_enqueue_step): nonzero = the guarded kernels leave at once; the factor branch
+       C_UD_REJECT,                           // up/downdate of the kept dense factor (dev/updown.inc): a scan met a pivot that is not a positive finite number
        C_COUNT = 16 };
 enum { V_TAU = 0, V_A0, V_B0, V_RZ, V_BNORM, V_OOB, V_QDX, V_OBJ, V_F, V_RR, V_RNORM, V_RINF = 15, V_COUNT = 16 };
 struct Ctrl {
@@ -97,6 +98,10 @@ struct QpdoDev {
     int dense_factored = 0, wb_enable = 1, wb_k = 0; double dense_fact_sigma = 0.0;
     double *d_fact = nullptr, *wb_Z = nullptr, *wb_T = nullptr, *wb_T2 = nullptr, *wb_G = nullptr, *wb_M = nullptr, *wb_v = nullptr, *wb_w = nullptr, *wb_t = nullptr;
     int *wb_slot = nullptr, *wb_rows = nullptr, *wb_cnt = nullptr;
+    // in-place up/downdate of the kept factor (QPDO_DENSE_UPDOWN; dev/updown.inc): ud_cap = changed rows a pass may apply (0: off),
+    // ud_dirty = the factor carries at least one up/downdate since its last full factorization (its solves are residual-checked)
+    int ud_cap = 0, ud_dirty = 0; int *ud_rows = nullptr, *ud_cnt = nullptr;
+    double *ud_a = nullptr, *ud_p = nullptr, *ud_q = nullptr, *ud_G = nullptr, *ud_Dn = nullptr, *ud_beta = nullptr;
     hipEvent_t evF[2] = {nullptr, nullptr}, evB[2] = {nullptr, nullptr};
     int dense_last_branch = -1; double dense_last_sigma = -1.0;
     int direct_hook_used = 0;      // qdev_direct_solve ran since the last solve: the next qdev_begin_solve drops its kept factor
@@ -155,6 +160,6 @@ struct QpdoDev {
     double *qstage = nullptr;                     // the caller's stored Q values (stype +-1), gathered through mapQ
     std::vector<long long> upd_Ap, upd_Qp;        // column pointers whose pattern passed the device check (later calls compare these)
     // what qdev_configure decided; a solve may change these (fallbacks, hybrid), qpdo_amd_update_matrices puts them back
-    struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, deflate, pcg_maxit, band_b; } cfg{};
+    struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, ud_cap, deflate, pcg_maxit, band_b; } cfg{};
 };
 

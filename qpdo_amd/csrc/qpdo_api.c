@@ -1096,6 +1096,7 @@ int qpdo_amd_get_stats(const QPDOWorkspace *work, QPDOAmdStats *out) {
     out->hybrid_pcg_passes = (long)st.hybrid_pcg_passes; out->band_fallbacks = (long)st.band_fallbacks;
     out->onelaunch_factors = (long)st.onelaunch_factors;
     out->ahead_steps = (long)st.ahead_steps; out->ahead_skips = (long)st.ahead_skips;
+    out->updown_solves = (long)st.updown_solves; out->updown_rows = (long)st.updown_rows; out->updown_rejects = (long)st.updown_rejects;
     out->fused_solves = work->chol->fused_solves;
     out->fused_kernel_s = work->chol->last_fused ? work->chol->fused_kernel_s : 0.0;
     if (work->chol->last_fused) { out->factor_count = work->chol->fused_factor_count; out->linsolve = 2; }

@@ -72,6 +72,9 @@ typedef struct {
     int64_t onelaunch_factors;  /* dense factorizations through the one-launch tile-dataflow kernel (k_mid_factor) */
     int64_t ahead_steps;        /* Newton steps that were enqueued behind their pass's residual launch and went ahead on the device's own decision */
     int64_t ahead_skips;        /* passes whose launched-ahead step left at once (outer update, termination, lost producer) */
+    int64_t updown_solves;      /* dense solves with a kept factor that carries in-place up/downdates, accepted by their residual check */
+    int64_t updown_rows;        /* changed rows SENT through the in-place up/downdate of the kept factor (QPDO_DENSE_UPDOWN); refused rows included */
+    int64_t updown_rejects;     /* up/downdated factors given up for a refactorization: a scan met a bad pivot, or a solve missed its residual check */
 } QdevStats;
 
 int qdev_device_count(void);
