@@ -9,7 +9,11 @@
  *   QPDO_DEVICE      HIP device ordinal (default: LOCAL_RANK if set, else 0)
  *   QPDO_LINSOLVE    "pcg" | "dense" | "band" | "auto" (default auto: the BAND direct solver when the Newton matrix is banded -- half-bandwidth
  *                    of Q + A'A <= 127, chain-structured QPs -- and n >= 2048; otherwise dense LDL' for n <= QPDO_DENSE_MAX_N = 12288, PCG
- *                    above; "band" on a matrix that is not banded makes qpdo_setup fail with a message; the dense solver accepts
+ *                    above; "band" takes the band solver for every half-bandwidth <= 1023 with n >= 4 (b + 1) -- 128 .. 1023 through the
+ *                    tiled fp64-MFMA factorization of dev/band_wide.inc, which is never chosen automatically (its crossover against
+ *                    dense and PCG is not measured yet) except as the rescue of a PCG solve that cannot converge above n = 40000 --
+ *                    and on a matrix that is not banded (half-bandwidth > 1023 or order too small) makes qpdo_setup fail with a
+ *                    message; the dense solver accepts
  *                    n <= 40000 -- its assembly tiles the LDS accumulator, QPDO_DENSE_ASM_TILE rows at a time -- and is also the rescue of
  *                    a PCG solve that cannot converge up to that order)
  *   QPDO_HYBRID      where the dense solver is selected automatically and n >= 8192, every solve starts with PCG and switches to the dense
@@ -183,8 +187,8 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
  * PCG workspace and a row-partitioned one (refused).  The workspace's weights, sigma and direction are untouched; the next qpdo_solve
  * drops the kept factor and runs as on a workspace that never saw this call.
  * qpdo_amd_download_factor: copies a factor array of the last factorization to the host; count must be the array's length.
- *   which 6: the geometry, 4 entries: ld = n rounded up to 64, nb = ld / 64 (dense), np = n rounded up to 4, b = the half-bandwidth
- *            (band); 0 where that solver never factored.
+ *   which 6: the geometry, 4 entries: ld = n rounded up to 64, nb = ld / 64 (dense), np = n rounded up to 4 (to 64 for b > 127), b = the
+ *            half-bandwidth (band); 0 where that solver never factored.
  *   dense, column-major, element (i, j) at [i + j ld]:
  *     0  Kd     ld x ld.  Below the diagonal: L (unit diagonal implied).  The upper triangle of every off-diagonal 64 x 64 tile holds the
  *               transposed copy that the backward solve reads: Kd(j, i) = L(i, j) for i, j in different tiles.  The diagonal and the upper
@@ -194,7 +198,12 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
  *     3  LinvT  the same blocks transposed: LinvT[k 4096 + c 64 + r] = (L_kk^-1)(c, r).
  *   band, lower band storage, np x (b + 1):
  *     4  Kb     Kb[j (b+1) + t] = L(j + t, j) for t >= 1, D_j at t = 0 (zero beyond the matrix; columns n .. np-1 identity padding).
- *     5  Lt     Lt[i (b+1) + t] = L(i, i - t), the row-band copy the backward solve reads (t >= 1).  */
+ *     5  Lt     Lt[i (b+1) + t] = L(i, i - t), the row-band copy the backward solve reads (t >= 1).
+ *   band with b > 127, 64 x 64 tiles, w = (b + 63) / 64 (arrays 4 and 5 return -1 with a message on such a workspace):
+ *     7  Wb     (np / 64) x (w + 1) x 64 x 64: Wb[(J (w+1) + s) 4096 + c 64 + r] = element (r, c) of tile (J + s, J) of the unit-lower L
+ *               (diagonal tiles: 1 on the diagonal, 0 above it; rows / columns n .. np-1 identity padding; tiles whose block row is
+ *               >= np / 64 are zero).  An element outside the band, i - j > b, is an exact zero.
+ *     8  Wd     np: D (ones behind n).  */
 #define QPDO_AMD_DIRECT_LOST (-2)
 int  qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags);
 int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count);

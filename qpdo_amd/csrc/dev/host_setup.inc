@@ -282,12 +282,13 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     if (d->comm.active) { d->linsolve = 0; d->deflate = 0; }   // the dense factor and the Woodbury rows are not partitioned
     // A banded Newton matrix (chain-structured QPs: half-bandwidth of Q + A'A <= 127) gets the band direct solver -- what CHOLMOD's
     // natural-order factorization gives the reference on such problems -- by default from n = 2048 up (below, the dense MFMA factor of a
-    // small matrix is as fast), or when asked for (QPDO_LINSOLVE=band; an explicit pcg / dense keeps those).
+    // small matrix is as fast), or when asked for (QPDO_LINSOLVE=band; an explicit pcg / dense keeps those).  Half-bandwidths 128 .. 1023
+    // (the tiled solver of dev/band_wide.inc) are taken only when asked for: its crossover against dense and PCG decides the default later.
     if (linsolve < 0 || linsolve == 3) {
         int rcb = band_detect(d); if (rcb) return rcb;
         const int wide_enough = d->n >= 4 * (d->band_b + 1);
-        if (d->band_b > 0 && wide_enough && (linsolve == 3 || d->n >= 2048)) d->linsolve = 3;
-        else if (linsolve == 3) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: the Newton matrix is not banded (half-bandwidth > %d or order too small)", BAND_MAX_B); return -1; }
+        if (d->band_b > 0 && wide_enough && (linsolve == 3 || (d->band_b <= BAND_MAX_B && d->n >= 2048))) d->linsolve = 3;
+        else if (linsolve == 3) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: the Newton matrix is not banded (half-bandwidth > %d or order too small)", BAND_WIDE_MAX_B); return -1; }
     }
     if (pcg_tol > 0) d->pcg_tol = pcg_tol;
     if (pcg_maxit > 0) d->pcg_maxit = pcg_maxit;

@@ -101,7 +101,8 @@ static int step_redo_if_lost(QpdoDev *d, int proximal, double sigma) {
 // The reference factors whatever K it is given (cholmod_interface.c:8-30) and never fails for lack of iterations.  Where the dense factor is
 // not available -- n > DENSE_LIMIT_N, or a row-partitioned workspace -- a PCG solve that cannot converge is not yet an error:
 //   (a) a BANDED Newton matrix (chain-structured QPs; detected now if the workspace was configured with an explicit solver) has an exact
-//       direct solver at any order: the band solver takes over for the rest of this workspace's solves (dev/band.inc);
+//       direct solver at any order: the band solver takes over for the rest of this workspace's solves (dev/band.inc up to half-bandwidth
+//       127, the tiled one of dev/band_wide.inc up to 1023);
 //   (b) otherwise the pass is solved again by PLAIN Jacobi-PCG -- Schur-complement mode and heavy-row deflation off, four times the
 //       iteration cap: the two accelerations change the preconditioned spectrum and either can be what stalled.
 // QPDOAmdStats.pcg_rescues / pcg_rescue_kinds say which fired; if neither helps the first failure's message stands and qpdo_solve ends
@@ -705,10 +706,11 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
     const size_t ld = (size_t)d->dense_ld, nb = (size_t)d->dense_nblk, band = (size_t)d->band_np * (size_t)(d->band_b + 1);
     if (which == 6) {
         if (count < 4) return set_err(hipErrorInvalidValue, "download factor: the geometry needs 4 entries", __LINE__);
-        dst[0] = d->Kd ? (double)ld : 0.0; dst[1] = d->Kd ? (double)nb : 0.0; dst[2] = d->Kb ? (double)d->band_np : 0.0; dst[3] = d->Kb ? (double)d->band_b : 0.0;
+        dst[0] = d->Kd ? (double)ld : 0.0; dst[1] = d->Kd ? (double)nb : 0.0; dst[2] = (d->Kb || d->bw_Wb) ? (double)d->band_np : 0.0; dst[3] = (d->Kb || d->bw_Wb) ? (double)d->band_b : 0.0;
         return 0;
     }
     const double *src = nullptr; size_t len = 0;
+    if ((which == 4 || which == 5) && d->bw_Wb) return set_err(hipErrorInvalidValue, "download factor: a band wider than 127 is held as tiles (arrays 7 and 8)", __LINE__);
     switch (which) {
         case 0: src = d->Kd; len = ld * ld; break;
         case 1: src = d->Dg; len = ld; break;
@@ -716,6 +718,8 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
         case 3: src = d->LinvT; len = nb * DNB * DNB; break;
         case 4: src = d->Kb; len = band; break;
         case 5: src = d->Lt; len = band; break;
+        case 7: src = d->bw_Wb; len = (size_t)(d->band_np / DNB) * (size_t)(d->bw_w + 1) * BW_T; break;
+        case 8: src = d->bw_Wd; len = (size_t)d->band_np; break;
         default: return set_err(hipErrorInvalidValue, "download factor: unknown array", __LINE__);
     }
     if (!src) return set_err(hipErrorInvalidValue, "download factor: this workspace has not factored with that solver", __LINE__);

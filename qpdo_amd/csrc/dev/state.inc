@@ -86,8 +86,11 @@ struct QpdoDev {
     // the solve at the first pass whose iteration count exceeds the budget
     int hybrid = 0, hybrid_active = 0, hybrid_budget = 450;
     int dense_asm_tile = 19000;   // rows of a column the assembly accumulates in LDS at a time (152 KB of the 160 KB)
-    // band direct solver (dev/band.inc): half-bandwidth of Q + A'A (-1: not banded within BAND_MAX_B), order padded to 4, band storage
+    // band direct solver (dev/band.inc): half-bandwidth of Q + A'A (-1: not banded within BAND_WIDE_MAX_B), order padded to 4, band storage
     int band_b = -1, band_np = 0; double *Kb = nullptr, *Lt = nullptr, *band_z = nullptr;
+    // half-bandwidths BAND_MAX_B + 1 .. BAND_WIDE_MAX_B (dev/band_wide.inc): order padded to 64, w = (b + 63) / 64; the band as 64 x 64 tiles
+    // (w + 1 per block column), the diagonal tiles while they are being updated, D, the diagonal blocks' inverses and their transposes
+    int bw_w = 0; double *bw_Wb = nullptr, *bw_Wdiag = nullptr, *bw_Wd = nullptr, *bw_Li = nullptr, *bw_LiT = nullptr;
     double *Kd = nullptr, *Wd = nullptr, *Dg = nullptr, *Linv = nullptr, *LinvT = nullptr, *dz = nullptr, *dxw = nullptr;
     double *ch_y = nullptr, *ch_x = nullptr, *dsol = nullptr; int dense_chain = 1;
     hipStream_t stream2 = nullptr;            // dense factor look-ahead: trailing updates run here

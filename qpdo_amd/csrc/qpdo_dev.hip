@@ -56,6 +56,7 @@ static int set_err(hipError_t e, const char *what, int line) {
 #include "dev/updown.inc"
 #include "dev/transpose.inc"
 #include "dev/band.inc"
+#include "dev/band_wide.inc"
 #include "dev/update.inc"
 #include "dev/host_core.inc"
 

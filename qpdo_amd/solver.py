@@ -440,11 +440,13 @@ class QPDO:
     def download_factor(self, name):
         """a factor array of the last factorization (layouts: include/qpdo_amd_ext.h).  Kd comes back as the ld x ld matrix (element
         (i, j) = Kd[i, j]), Kb / Lt as np x (b + 1) arrays (row j = column / row j of the band), Dg flat, Linv / LinvT as their raw nb x 4096
-        arrays."""
+        arrays.  A band wider than 127 has Wb and Wd instead of Kb and Lt: Wb as (np / 64) x (w + 1) x 64 x 64, w = (b + 63) // 64, where
+        Wb[J, s, c, r] is element (r, c) of tile (J + s, J) of the unit-lower L; Wd = D flat."""
         g = self.factor_geometry()
         ld, nb, npad, b = g["ld"], g["nb"], g["np"], g["b"]
         which, count = {"Kd": (0, ld * ld), "Dg": (1, ld), "Linv": (2, nb * 4096), "LinvT": (3, nb * 4096),
-                        "Kb": (4, npad * (b + 1)), "Lt": (5, npad * (b + 1))}[name]
+                        "Kb": (4, npad * (b + 1)), "Lt": (5, npad * (b + 1)),
+                        "Wb": (7, npad // 64 * ((b + 63) // 64 + 1) * 4096), "Wd": (8, npad)}[name]
         out = np.zeros(count)
         if lib().qpdo_amd_download_factor(self._w, which, _as_dp(out), count):
             raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
@@ -452,6 +454,8 @@ class QPDO:
             return out.reshape(ld, ld).T
         if name in ("Kb", "Lt"):
             return out.reshape(npad, b + 1)
+        if name == "Wb":
+            return out.reshape(npad // 64, (b + 63) // 64 + 1, 64, 64)
         if name in ("Linv", "LinvT"):
             return out.reshape(nb, 4096)
         return out
