@@ -79,7 +79,6 @@ static int upload_csr(QpdoDev *d, DevCsr *M, const QdevCsr *h) {
     return 0;
 }
 static int read_ctrl(QpdoDev *d);
-static int step_complete_pending(QpdoDev *d, double *tau, int *redone);      // host_step.inc
 // decide whether M streams from HBM (then use the LDS-staged kernel) and build its slab pointers
 // arrays of the slab-major image (two padding entries: the 16-byte loads may touch one element past a segment)
 static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, bool with_f32 = false) {

@@ -1,4 +1,4 @@
-// host_dense.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): dense factorization, solves, low-rank update
+// host_dense.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): dense factorization, solves, low-rank update, in-place up/downdate; the one launch site of the assembly, of the one-launch factorization and of the chained solves
 // ---- dense direct solve ------------------------------------------------------------------------------
 static const int DOUTER = 4;                 // inner 64-blocks per outer panel (256 columns)
 static const int DENSE_RESERVE_CUS = 32;     // CUs left out of the look-ahead stream's mask
@@ -76,37 +76,79 @@ static int dense_alloc(QpdoDev *d) {
     }
     return rc;
 }
+// ---- the launches that the host-first Newton step and the launched-ahead one (host_step.inc ahead_enqueue_step) both issue: one site each ----
+// Assembly of K = Q + sigma_f I + A' diag(d) A, and what becomes of the right-hand side in the same launch:
+enum { ASM_RHS_NONE,        // nothing: the solve loads its own (k_dense_load_rhs)
+       ASM_RHS_COPY,        // d->rhs is copied, padded, for the one-launch factorization that follows
+       ASM_RHS_FORM };      // launch-ahead: extra workgroups form rhs = -res_dual_in - A't themselves (EpiRhs' work); the launch looks at the
+                            // device's decision first (spec) and takes the kept factor's sigma_f in branch 1
+static void launch_dense_assemble(QpdoDev *d, int rhs_mode, double sigma_f) {
+    const int n = d->n, ld = d->dense_ld;
+    const int g = ld < 1024 ? ld : 1024;
+    // the assembly's accumulator is an LDS tile of up to DENSE_ASM_TILE_MAX rows (QPDO_DENSE_ASM_TILE: a smaller tile, for the tests
+    // of the tiled path at small n); larger orders are assembled in several row tiles per column -- the same bits
+    const int asm_tile = n < d->dense_asm_tile ? (n > 0 ? n : 1) : d->dense_asm_tile;
+    const bool form = rhs_mode == ASM_RHS_FORM;
+    AsmRhs ar{};
+    int gR = 0;
+    if (form) {
+        ar.on = 1; ar.g0 = g; ar.tpr = d->At.tpr; ar.nrows = d->At.nrows; ar.rp = d->At.rp; ar.ci = d->At.ci; ar.val = d->At.val; ar.x = d->dy;
+        ar.rdi = d->res_dual_in; ar.atdy = d->Atdy; ar.rhs = d->rhs;
+        gR = (d->At.nrows + 64 / ar.tpr - 1) / (64 / ar.tpr); if (gR > 1024) gR = 1024; if (gR < 1) gR = 1;
+        d->st.spmv_calls++; d->st.spmv_bytes += (int64_t)d->At.alg_bytes();
+    }
+    hipLaunchKernelGGL(k_dense_assemble, dim3(g + gR), dim3(64), (size_t)asm_tile * sizeof(double), d->stream, n, ld, asm_tile, d->Qf.rp, d->Qf.ci, d->Qf.val,
+                       d->At.rp, d->At.ci, d->At.val, d->Ar.rp, d->Ar.ci, d->Ar.val, (const double *)d->d, sigma_f, d->Kd,
+                       rhs_mode == ASM_RHS_COPY ? (const double *)d->rhs : (const double *)nullptr, d->dxw, (unsigned long long *)d->dz, (unsigned long long *)d->ch_x,
+                       form ? (const Ctrl *)d->ctrl : (const Ctrl *)nullptr, form ? d->sigma_f : 0.0, ar);
+}
+// mid-size order: every tile of the lower triangle has a workgroup of its own, the factorization is ONE launch (dev/mid_kernels.inc); with_rhs:
+// nb more workgroups carry the forward solve of the right-hand side that the assembly launch left in dxw (padded, with the sentinels of the
+// polled vectors); spec = 1: launch-ahead, the kernel leaves if the device decided against a Newton step
+static void launch_mid_factor(QpdoDev *d, bool with_rhs, int spec) {
+    const int nb = d->dense_nblk;
+    hipLaunchKernelGGL(k_mid_factor, dim3(nb * (nb + 1) / 2 + (with_rhs ? nb : 0)), dim3(256), MID_LDS_DOUBLES * 8, d->stream, d->Kd, d->n, d->dense_ld, nb, d->Dg,
+                       d->Linv, d->LinvT, with_rhs ? (const double *)d->dxw : (const double *)nullptr, d->dz, d->ch_y, d->mid_flags, ++d->mid_epoch, d->ctrl,
+                       d->mid_C, d->mid_dinv, spec);
+}
+// one chained triangular solve per right-hand side (grid: right-hand side x block row), block rows chained through polled device-scope
+// loads: FWD: out = D^-1 L^-1 src (ld entries each), else out = L^-T src (the first nout entries; out may be null); pub: the polled vector
+extern "C++" template <bool FWD>
+static void launch_ldl_chain(QpdoDev *d, int nrhs, const double *src, double *pub, double *out, int nout, int spec = 0) {
+    hipLaunchKernelGGL(k_ldl_chain<FWD>, dim3(nrhs, d->dense_nblk), dim3(256), 0, d->stream, (const double *)d->Kd, d->dense_ld, d->dense_nblk,
+                       (const double *)(FWD ? d->Linv : d->LinvT), (const double *)d->Dg, src, pub, out, nout, d->ctrl, spec);
+}
+// A factorization of the current (sigma_f, d) has just been enqueued: the one place that books it.  fwd_carried: its launch left the
+// forward solve of d->rhs in ch_y and no solve has used it yet.  The factor belongs to this weight vector and no row holds a low-rank
+// slot: d_fact and wb_slot follow where they exist.  (Neither can fire for a launched-ahead step, which must enqueue nothing the
+// host-first step does not: ahead_route_ok requires !wb_enable && !ud_cap.  d_fact exists only if one of the two was set when
+// dense_alloc ran, dense_alloc allocates once per workspace, and both are fixed at setup (d->cfg) -- only a lost producer clears them,
+// together with dense_chain, which takes the workspace off the launch-ahead route until the configuration is put back as a whole.  A change that lets the configuration be
+// read again after the allocation must guard the copy.)
+static int dense_factor_enqueued(QpdoDev *d, bool onelaunch, bool fwd_carried) {
+    d->mid_fwd_valid = fwd_carried ? 1 : 0;
+    if (onelaunch) d->st.onelaunch_factors++;
+    d->st.factor_count++;
+    d->dense_valid = 1;
+    d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0; d->ud_dirty = 0;
+    if (d->d_fact && d->m > 0) HIPCHK(hipMemcpyAsync(d->d_fact, d->d, (size_t)d->m * 8, hipMemcpyDeviceToDevice, d->stream));
+    if (d->wb_enable && d->m > 0) HIPCHK(hipMemsetAsync(d->wb_slot, 0xFF, (size_t)d->m * sizeof(int), d->stream));
+    return 0;
+}
 // with_rhs: the caller's next solve is K x = d->rhs -- a mid-size factorization then carries the forward solve along (k_mid_factor)
 static int dense_factor(QpdoDev *d, bool with_rhs = false) {
     int rc = dense_alloc(d); if (rc) return rc;
     d->mid_fwd_valid = 0;
     const int n = d->n, ld = d->dense_ld, nb = d->dense_nblk;
-    const int g = ld < 1024 ? ld : 1024;
     // look-ahead pays from n ~ 7000 up (tools/dense_lookahead_crossover.sh, factor ms with | without: n = 2000: 1.60 | 1.46, 4000: 3.39 | 3.18,
     // 6000: 5.82 | 5.72, 7000: 7.24 | 7.35, 8000: 8.85 | 9.14, 1e4: 13.4 | 14.0, 12288: 22.2 | 23.9): below, the two streams only slow each other
     const bool lookahead = d->dense_lookahead >= 0 ? d->dense_lookahead != 0 : n >= 7000;
-    // the assembly's accumulator is an LDS tile of up to DENSE_ASM_TILE_MAX rows (QPDO_DENSE_ASM_TILE: a smaller tile, for the tests
-    // of the tiled path at small n); larger orders are assembled in several row tiles per column -- the same bits
-    const int asm_tile = n < d->dense_asm_tile ? (n > 0 ? n : 1) : d->dense_asm_tile;
     const bool mid = d->dense_mid && d->dense_chain && d->mid_flags && nb <= MID_MAX_NB;
-    hipLaunchKernelGGL(k_dense_assemble, dim3(g), dim3(64), (size_t)asm_tile * sizeof(double), d->stream, n, ld, asm_tile, d->Qf.rp, d->Qf.ci, d->Qf.val,
-                       d->At.rp, d->At.ci, d->At.val, d->Ar.rp, d->Ar.ci, d->Ar.val, (const double *)d->d, d->sigma_f, d->Kd,
-                       (mid && with_rhs) ? (const double *)d->rhs : (const double *)nullptr, d->dxw, (unsigned long long *)d->dz, (unsigned long long *)d->ch_x);
+    launch_dense_assemble(d, (mid && with_rhs) ? ASM_RHS_COPY : ASM_RHS_NONE, d->sigma_f);
     if (mid) {
-        // mid-size order: every tile of the lower triangle has a workgroup of its own, the factorization is ONE launch (dev/mid_kernels.inc);
-        // its right-hand side (padded, with the sentinels of the polled vectors) was loaded by the assembly launch
-        const int grid = nb * (nb + 1) / 2 + (with_rhs ? nb : 0);
-        hipLaunchKernelGGL(k_mid_factor, dim3(grid), dim3(256), MID_LDS_DOUBLES * 8, d->stream, d->Kd, n, ld, nb, d->Dg, d->Linv, d->LinvT,
-                           with_rhs ? (const double *)d->dxw : (const double *)nullptr, d->dz, d->ch_y, d->mid_flags, ++d->mid_epoch, d->ctrl, d->mid_C, d->mid_dinv);
+        launch_mid_factor(d, with_rhs, 0);
         HIPCHK(hipGetLastError());
-        d->mid_fwd_valid = with_rhs ? 1 : 0;
-        d->st.onelaunch_factors++;
-        d->dense_valid = 1;
-        d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0; d->ud_dirty = 0;
-        if (d->d_fact && d->m > 0) HIPCHK(hipMemcpyAsync(d->d_fact, d->d, (size_t)d->m * 8, hipMemcpyDeviceToDevice, d->stream));
-        if (d->wb_enable && d->m > 0) HIPCHK(hipMemsetAsync(d->wb_slot, 0xFF, (size_t)d->m * sizeof(int), d->stream));
-        d->st.factor_count++;
-        return 0;
+        return dense_factor_enqueued(d, true, with_rhs);
     }
     // Outer panel p (DOUTER block columns): F_p = its factorization (a serial diag -> panel -> narrow update chain that
     // fills few CUs), a_p = trailing update of the NEXT outer panel's columns, b_p = trailing update of everything
@@ -155,13 +197,7 @@ static int dense_factor(QpdoDev *d, bool with_rhs = false) {
     }
     if (b_pending) HIPCHK(hipStreamWaitEvent(sc, d->evB[(p - 1) & 1], 0));
     HIPCHK(hipGetLastError());
-    d->dense_valid = 1;
-    d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0; d->ud_dirty = 0;
-    // the factor belongs to this weight vector; no row holds a low-rank slot
-    if (d->d_fact && d->m > 0) HIPCHK(hipMemcpyAsync(d->d_fact, d->d, (size_t)d->m * 8, hipMemcpyDeviceToDevice, d->stream));
-    if (d->wb_enable && d->m > 0) HIPCHK(hipMemsetAsync(d->wb_slot, 0xFF, (size_t)d->m * sizeof(int), d->stream));
-    d->st.factor_count++;
-    return 0;
+    return dense_factor_enqueued(d, false, false);
 }
 // z0 = K0^-1 src; the result (ld entries) is at d->dsol; dst (optional, n entries) receives a copy
 static int dense_solve_core(QpdoDev *d, const double *src, double *dst = nullptr) {
@@ -170,11 +206,8 @@ static int dense_solve_core(QpdoDev *d, const double *src, double *dst = nullptr
     d->mid_fwd_valid = 0;
     if (!fwd_done) LAUNCH(k_dense_load_rhs, vgrid(ld), n, ld, src, d->dxw, d->dense_chain ? d->dz : (double *)nullptr, d->ch_x);
     if (d->dense_chain) {          // one launch per direction, block rows chained through polled device-scope loads
-        if (!fwd_done)
-        hipLaunchKernelGGL(k_ldl_chain<true>, dim3(1, nb), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->Linv,
-                           (const double *)d->Dg, (const double *)d->dxw, d->dz, d->ch_y, ld, d->ctrl);
-        hipLaunchKernelGGL(k_ldl_chain<false>, dim3(1, nb), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->LinvT,
-                           (const double *)d->Dg, (const double *)d->ch_y, d->ch_x, dst, n, d->ctrl);
+        if (!fwd_done) launch_ldl_chain<true>(d, 1, d->dxw, d->dz, d->ch_y, ld);
+        launch_ldl_chain<false>(d, 1, d->ch_y, d->ch_x, dst, n);
         d->dsol = d->ch_x;
         return 0;
     }
@@ -192,10 +225,14 @@ static int dense_solve_core(QpdoDev *d, const double *src, double *dst = nullptr
 __global__ void k_add_to(int n, const double *__restrict__ a, double *__restrict__ y) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) y[i] = y[i] + a[i];
 }
+// r = rhs - K dx on the true K = Q + sigma_f I + A' diag(d) A by three SpMV, into pc_r; its inf-norm into N_B of the control block.
+// (Defined in host_probe.inc, beside its other caller: the EpiResid products are instantiated where they first appear outside a
+// template, and that place decides where their kernels sit in the code object -- it stays where it has been.)
+static void true_residual(QpdoDev *d);
 static const double WB_RES_TOL = 1e-13;    // relative inf-norm residual accepted for a low-rank solve
 static const int WB_MAX_REFINE = 5;
 // Residual check and refinement of a solve whose inner solver is not a fresh factorization (the low-rank path, an up/downdated factor):
-// r = rhs - K dx on the true K = Q + sigma I + A' diag(d) A by three SpMV, accepted at WB_RES_TOL relative to |rhs|inf; up to WB_MAX_REFINE
+// the true residual (true_residual), accepted at WB_RES_TOL relative to |rhs|inf; up to WB_MAX_REFINE
 // sweeps, a sweep that does not reduce the residual fourfold ends them and is accepted only near the floor.  inner(it) enqueues sweep
 // it: dx (it = 0) or its correction from r (in d->pc_r); guard() is asked after each read-back and ends the sweeps without acceptance.
 // The one copy of the acceptance rule; *ok = 0: the caller refactors.
@@ -208,11 +245,7 @@ static int dense_refine_checked(QpdoDev *d, Inner inner, Guard guard, bool *ok) 
     double prev = 0.0;
     for (int it = 0; it <= WB_MAX_REFINE; it++) {
         int rc = inner(it); if (rc) return rc;
-        // r = rhs - K dx
-        LAUNCH(k_ctrl_set_nrm0, 1, d->ctrl, N_B);
-        launch_spmv(d, d->Ar, d->dx, EpiPcgA{d->d, d->tmp_m, nullptr}, false);
-        launch_spmv(d, d->Qf, d->dx, EpiPcgQ{d->dx, d->sigma_f, d->pc_Kp}, false);
-        launch_spmv(d, d->At, d->tmp_m, EpiResid{d->rhs, d->pc_Kp, d->pc_r, d->ctrl, N_B}, true);
+        true_residual(d);
         bool go = true;
         rc = guard(&go); if (rc) return rc;                  // (reads the control block back)
         const double nb_ = nrm_of(d->hctrl, N_A), nr_ = nrm_of(d->hctrl, N_B);
@@ -290,7 +323,7 @@ static int dense_solve(QpdoDev *d) {
 // Z = K0^-1 U' (one chained solve per column, all columns advancing together) and their row and column of G.  *overflow = 1: more
 // than WB_MAX rows differ, the caller refactors.
 static int wb_extend(QpdoDev *d, int *overflow) {
-    const int ld = d->dense_ld, nb = d->dense_nblk, k_old = d->wb_k;
+    const int ld = d->dense_ld, k_old = d->wb_k;
     *overflow = 0;
     hipLaunchKernelGGL(k_wb_select, dim3(1), dim3(1024), 0, d->stream, d->m, (const double *)d->d, (const double *)d->d_fact, d->wb_slot, d->wb_rows,
                        k_old, d->wb_cnt);
@@ -308,11 +341,9 @@ static int wb_extend(QpdoDev *d, int *overflow) {
         double *T2 = d->wb_T2 + (size_t)k_old * ld;
         const int tot = ld * k_new;
         LAUNCH(k_fill_sentinel, vgrid(tot), tot, T, T);
-        hipLaunchKernelGGL(k_ldl_chain<true>, dim3(k_new, nb), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->Linv,
-                           (const double *)d->Dg, (const double *)X, T, T2, ld, d->ctrl);
+        launch_ldl_chain<true>(d, k_new, X, T, T2, ld);
         LAUNCH(k_fill_sentinel, vgrid(tot), tot, X, X);
-        hipLaunchKernelGGL(k_ldl_chain<false>, dim3(k_new, nb), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->LinvT,
-                           (const double *)d->Dg, (const double *)T2, X, (double *)nullptr, 0, d->ctrl);
+        launch_ldl_chain<false>(d, k_new, T2, X, nullptr, 0);
     }
     hipLaunchKernelGGL(k_wb_G, dim3(cnt, k_new), dim3(64), 0, d->stream, k_old, (const int *)d->wb_rows, d->Ar.rp, d->Ar.ci, d->Ar.val,
                        (const double *)d->wb_Z, ld, d->wb_G);
@@ -341,8 +372,7 @@ static int ud_apply(QpdoDev *d, int *applied) {
     hipLaunchKernelGGL(k_ud_load, dim3(cnt), dim3(256), 0, d->stream, ld, (const int *)d->ud_rows, d->Ar.rp, d->Ar.ci, d->Ar.val, d->ud_a, d->ud_p, d->ud_q);
     for (int k = 0; k < cnt; k++) {
         const double *a = d->ud_a + (size_t)k * ld, *p = d->ud_p + (size_t)k * ld, *q = d->ud_q + (size_t)k * ld;
-        hipLaunchKernelGGL(k_ldl_chain<true>, dim3(1, nb), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->Linv,
-                           (const double *)d->Dg, a, (double *)p, (double *)q, ld, d->ctrl);
+        launch_ldl_chain<true>(d, 1, a, (double *)p, (double *)q, ld);
         hipLaunchKernelGGL(k_ud_prep, dim3(nb, nb + 1), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->Dg, p, q,
                            (const int *)d->ud_rows, k, (const double *)d->d, (const double *)d->d_fact, d->ud_G, d->ud_Dn, d->ud_beta, d->ctrl);
         hipLaunchKernelGGL(k_ud_apply, dim3(nb, nb), dim3(256), 0, d->stream, d->Kd, ld, nb, d->Dg, d->Linv, d->LinvT, a, p, (const double *)d->ud_G,
@@ -352,4 +382,28 @@ static int ud_apply(QpdoDev *d, int *applied) {
     d->ud_dirty = 1;
     d->st.updown_rows += cnt;              // rows SENT: one that its scan refuses, and the rows behind it, never touch the factor (updown_rejects then counts the pass)
     return 0;
+}
+// Bring the kept factor up to date with the current (sigma_f, d) when it is not known to be (d->dense_valid = 0) -- the one copy of the
+// rule, for the Newton pass and for the test hook that drives the solver as a pass does (host_probe.inc qdev_direct_solve).  As the
+// reference: a full factorization where it is forced (branch 0, newton.c:21-33), where there is no factor or sigma_f moved; otherwise
+// the rows whose weight moved change the kept factor -- in place for up to ud_cap of them (QPDO_DENSE_UPDOWN; no low-rank slot held: its
+// columns belong to the factor as it was), through low-rank slots where wb_enable is set -- and whatever neither route takes (more rows
+// than WB_MAX, or no low-rank path) refactors.  carry_fwd: a factorization launch takes the forward solve of d->rhs along.
+static int dense_refresh_factor(QpdoDev *d, bool force_full, bool carry_fwd) {
+    bool full = force_full || !d->dense_factored || d->sigma_f != d->dense_fact_sigma;
+    int rc = 0, updated = 0;
+    if (!full && d->ud_cap > 0 && d->wb_k == 0) { rc = ud_apply(d, &updated); if (rc) return rc; }
+    if (updated) { d->dense_valid = 1; return 0; }
+    if (!d->wb_enable) full = true;
+    if (!full) {
+        int overflow = 0;
+        rc = wb_extend(d, &overflow); if (rc) return rc;
+        if (!overflow) { d->dense_valid = 1; return 0; }
+    }
+    return dense_factor(d, carry_fwd);
+}
+// a fresh factorization of this pass's matrix, then the solve of K dx = d->rhs with it
+static int dense_factor_and_solve(QpdoDev *d, bool carry_fwd) {
+    int rc = dense_factor(d, carry_fwd); if (rc) return rc;
+    return dense_solve(d);
 }

@@ -1,0 +1,199 @@
+// host_probe.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): measurement and parity entry points -- kernels and solvers driven on their own, for the benchmarks and the tests
+static DevCsr *mat_by_id(QpdoDev *d, int which) { return which == 0 ? &d->Ar : which == 1 ? &d->At : &d->Qf; }
+
+int qdev_bench_spmv(QpdoDev *d, int which, int reps, double *avg_seconds, double *alg_bytes) {
+    HIPCHK(hipSetDevice(d->device));
+    DevCsr *M = mat_by_id(d, which);
+    double *xin = (M->ncols == d->n) ? d->pc_p : d->pc_t;
+    double *yout = (M->nrows == d->n) ? d->pc_Kp : d->tmp_m;
+    LAUNCH(k_fill, vgrid(M->ncols), M->ncols, 1.0, xin);
+    launch_spmv(d, *M, xin, EpiStore{yout}, false);     // warm-up
+    HIPCHK(hipEventRecord(d->ev0, d->stream));
+    for (int r = 0; r < reps; r++) launch_spmv(d, *M, xin, EpiStore{yout}, false);
+    HIPCHK(hipEventRecord(d->ev1, d->stream));
+    HIPCHK(hipEventSynchronize(d->ev1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+    *avg_seconds = (double)ms * 1e-3 / (double)reps;
+    *alg_bytes = M->alg_bytes();
+    return 0;
+}
+// r = rhs - K dx into pc_r, its inf-norm into N_B (declared in host_dense.inc, where dense_refine_checked calls it)
+static void true_residual(QpdoDev *d) {
+    LAUNCH(k_ctrl_set_nrm0, 1, d->ctrl, N_B);
+    launch_spmv(d, d->Ar, d->dx, EpiPcgA{d->d, d->tmp_m, nullptr}, false);
+    launch_spmv(d, d->Qf, d->dx, EpiPcgQ{d->dx, d->sigma_f, d->pc_Kp}, false);
+    launch_spmv(d, d->At, d->tmp_m, EpiResid{d->rhs, d->pc_Kp, d->pc_r, d->ctrl, N_B}, true);
+}
+// dense factorization of K = Q + sigma_f I + A' diag(d) A with the workspace's CURRENT weights, `reps` times back to back, timed
+// with HIP events on the solver's stream (the look-ahead stream joins it before the factor ends).  flops = n^3 / 3 per factor.
+// check != NULL: relative residual ||rhs - K x||inf / ||rhs||inf of one solve with the fresh factor (rhs = the diagonal of Q + 1).
+int qdev_bench_dense_factor(QpdoDev *d, int reps, double *avg_seconds, double *check) {
+    HIPCHK(hipSetDevice(d->device));
+    if (d->comm.active) return set_err(hipErrorInvalidValue, "dense factor bench: not for partitioned workspaces", __LINE__);
+    int rc = dense_alloc(d); if (rc) return rc;
+    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+    rc = dense_factor(d); if (rc) return rc;               // warm-up (allocations, code objects)
+    HIPCHK(hipEventRecord(d->ev0, d->stream));
+    for (int r = 0; r < reps; r++) { rc = dense_factor(d); if (rc) return rc; }
+    HIPCHK(hipEventRecord(d->ev1, d->stream));
+    HIPCHK(hipEventSynchronize(d->ev1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+    *avg_seconds = (double)ms * 1e-3 / (double)(reps > 0 ? reps : 1);
+    d->st.factor_count -= reps + 1;
+    if (d->st.onelaunch_factors >= reps + 1) d->st.onelaunch_factors -= reps + 1;
+    if (check) {
+        const int n = d->n;
+        if (!d->qdiag_valid) { LAUNCH(k_extract_diag, vgrid(n), n, d->Qf.rp, d->Qf.ci, d->Qf.val, d->qdiag); d->qdiag_valid = 1; }
+        LAUNCH(k_axpy_const, vgrid(n), n, (const double *)d->qdiag, 1.0, d->rhs);
+        const int wbk = d->wb_k; d->wb_k = 0;
+        rc = dense_solve(d); d->wb_k = wbk; if (rc) return rc;
+        LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
+        LAUNCH(k_absmax_mul, vgrid(n), n, (const double *)d->rhs, (const double *)nullptr, d->ctrl, N_A);
+        true_residual(d);
+        rc = read_ctrl(d); if (rc) return rc;
+        if (d->hctrl->cnt[C_CHAIN_ERR]) return set_err(hipErrorUnknown, "dense factor bench: a polling kernel lost its producer", __LINE__);
+        *check = nrm_of(d->hctrl, N_B) / nrm_of(d->hctrl, N_A);
+        d->dense_valid = 0;
+    }
+    return 0;
+}
+// ---- the direct solvers as single linear solves (tests: tests/test_gpu_direct_solvers.py) ---------------------------------------
+// K x = rhs with K = Q + sigma I + A' diag(dw) A, through the workspace's direct solver as a Newton pass drives it: dense_refresh_factor /
+// dense_solve (linsolve 1; the pass's own functions) or band_factor / band_solve (3), no other kernels.  flags bit 0: refactor; clear: a kept factor of
+// this sigma is reused -- with the low-rank update for the rows whose weight moved since it when wb_enable is set (more than WB_MAX of
+// them refactor), as it is (the caller passes the factored weights) otherwise, unless the workspace itself has marked that factor stale (dense_valid = 0, e.g. an outer
+// update of a solve since it was made): then it is refactored, as a Newton pass would; with ud_cap set, up to that many changed rows change the
+// kept factor in place (ud_apply) and more of them take the low-rank path or, without it, refactor.  Bit 1: the factorization launch carries the forward
+// solve (dense_factor(d, true)).  The workspace's weights, sigma_f and dx are put back afterwards; the kept factor stays for the next
+// call and is dropped by the next qdev_begin_solve.  A lost producer of a polling kernel, or a bad band pivot, returns
+// QDEV_DIRECT_LOST with the latch cleared -- never a silent redo.
+int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *rhs, double *x, int flags) {
+    HIPCHK(hipSetDevice(d->device));
+    if (d->comm.active) return set_err(hipErrorInvalidValue, "direct solve: not for row-partitioned workspaces", __LINE__);
+    if (d->linsolve != 1 && d->linsolve != 3) return set_err(hipErrorInvalidValue, "direct solve: the workspace's solver is not a direct one (dense or band)", __LINE__);
+    const int n = d->n, m = d->m;
+    std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1));
+    if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(dx_keep.data(), d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (m) HIPCHK(hipMemcpyAsync(d->d, dw, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d->rhs, rhs, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    const double sigma_keep = d->sigma_f;
+    d->sigma_f = sigma;
+    d->direct_hook_used = 1;
+    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+    if (d->ud_cap) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_UD_REJECT, 0);      // (a latch left by a call that ended early is not this call's)
+    const bool refactor = (flags & 1) != 0, carry = (flags & 2) != 0;
+    int rc = 0;
+    if (d->linsolve == 3) {
+        if (refactor || !d->dense_valid) rc = band_factor(d);
+        if (!rc) rc = band_solve(d);
+    } else {
+        // a Newton pass knows whether (sigma_f, d) moved since the factorization; this caller only says "refactor" or not, and where the
+        // workspace can follow moved weights (ud_cap, wb_enable) the kept factor is brought up to date with whatever rows did move
+        if (refactor || !d->dense_factored || d->sigma_f != d->dense_fact_sigma || d->ud_cap > 0 || d->wb_enable) d->dense_valid = 0;
+        if (!d->dense_valid) rc = dense_refresh_factor(d, refactor, carry);
+        if (!rc) rc = dense_solve(d);
+    }
+    if (!rc && n) HIPCHK(hipMemcpyAsync(x, d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (!rc) rc = read_ctrl(d);
+    bool lost = false;
+    if (!rc && d->hctrl->cnt[C_CHAIN_ERR]) {
+        lost = true;
+        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0;
+    }
+    d->sigma_f = sigma_keep;
+    if (m) HIPCHK(hipMemcpyAsync(d->d, d_keep.data(), (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d->dx, dx_keep.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (rc) return rc;
+    if (lost) {
+        snprintf(g_err, sizeof(g_err), "direct solve: %s", d->linsolve == 3 ? "the band factorization met a pivot that is not a positive finite number"
+                                                                            : "a polling kernel lost its producer");
+        return QDEV_DIRECT_LOST;
+    }
+    return 0;
+}
+// the factor arrays of the last factorization (layouts: include/qpdo_amd_ext.h, qpdo_amd_download_factor)
+int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
+    HIPCHK(hipSetDevice(d->device));
+    const size_t ld = (size_t)d->dense_ld, nb = (size_t)d->dense_nblk, band = (size_t)d->band_np * (size_t)(d->band_b + 1);
+    if (which == 6) {
+        if (count < 4) return set_err(hipErrorInvalidValue, "download factor: the geometry needs 4 entries", __LINE__);
+        dst[0] = d->Kd ? (double)ld : 0.0; dst[1] = d->Kd ? (double)nb : 0.0; dst[2] = (d->Kb || d->bw_Wb) ? (double)d->band_np : 0.0; dst[3] = (d->Kb || d->bw_Wb) ? (double)d->band_b : 0.0;
+        return 0;
+    }
+    const double *src = nullptr; size_t len = 0;
+    if ((which == 4 || which == 5) && d->bw_Wb) return set_err(hipErrorInvalidValue, "download factor: a band wider than 127 is held as tiles (arrays 7 and 8)", __LINE__);
+    switch (which) {
+        case 0: src = d->Kd; len = ld * ld; break;
+        case 1: src = d->Dg; len = ld; break;
+        case 2: src = d->Linv; len = nb * DNB * DNB; break;
+        case 3: src = d->LinvT; len = nb * DNB * DNB; break;
+        case 4: src = d->Kb; len = band; break;
+        case 5: src = d->Lt; len = band; break;
+        case 7: src = d->bw_Wb; len = (size_t)(d->band_np / DNB) * (size_t)(d->bw_w + 1) * BW_T; break;
+        case 8: src = d->bw_Wd; len = (size_t)d->band_np; break;
+        default: return set_err(hipErrorInvalidValue, "download factor: unknown array", __LINE__);
+    }
+    if (!src) return set_err(hipErrorInvalidValue, "download factor: this workspace has not factored with that solver", __LINE__);
+    if (count < 0 || (size_t)count != len) return set_err(hipErrorInvalidValue, "download factor: count is not the array's length", __LINE__);
+    HIPCHK(hipMemcpyAsync(dst, src, len * 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host) {
+    HIPCHK(hipSetDevice(d->device));
+    DevCsr *M = mat_by_id(d, which);
+    double *xin = (M->ncols == d->n) ? d->pc_p : d->pc_t;
+    double *yout = (M->nrows == d->n) ? d->pc_Kp : d->tmp_m;
+    if (M->ncols) HIPCHK(hipMemcpyAsync(xin, v_host, (size_t)M->ncols * 8, hipMemcpyHostToDevice, d->stream));
+    launch_spmv(d, *M, xin, EpiStore{yout}, false);
+    if (M->nrows) HIPCHK(hipMemcpyAsync(y_host, yout, (size_t)M->nrows * 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+int qdev_linesearch(QpdoDev *d, double eta, double beta, const double *delta, const double *alpha, double *tau) {
+    HIPCHK(hipSetDevice(d->device));
+    const int M2 = 2 * d->m;
+    if (M2 == 0) { *tau = -beta / eta; return 0; }
+    HIPCHK(hipMemcpyAsync(d->ls_delta, delta, (size_t)M2 * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->ls_alpha, alpha, (size_t)M2 * 8, hipMemcpyHostToDevice, d->stream));
+    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_NL, 0);
+    const int g = vgrid(M2);
+    LAUNCH(k_ls_prep_raw, g, M2, d->ls_delta, d->ls_alpha, d->ls_key[0], d->ls_idx[0], d->part + P_A0 * PGRID, d->part + P_B0 * PGRID, d->ctrl);
+    // eta, beta enter through the partial slots so that k_ls_scan2 forms a0, b0 exactly as in a Newton step:
+    // eta = 0.5*(eta_m + dxQdx) with eta_m = 2*eta, dxQdx = 0
+    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_ETA_M * PGRID, 2.0 * eta);
+    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_BETA_M * PGRID, 2.0 * beta);
+    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_DXQDX * PGRID, 0.0);
+    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_DXDF * PGRID, 0.0);
+    // pm applies to ETA/BETA (1 value) and A0/B0 (g values): run scan2 with pm = g after zero-padding ETA/BETA slots
+    if (g > 1) {
+        HIPCHK(hipMemsetAsync(d->part + P_ETA_M * PGRID + 1, 0, (size_t)(g - 1) * 8, d->stream));
+        HIPCHK(hipMemsetAsync(d->part + P_BETA_M * PGRID + 1, 0, (size_t)(g - 1) * 8, d->stream));
+    }
+    int rc = linesearch_device(d, g, 1); if (rc) return rc;
+    rc = read_ctrl(d); if (rc) return rc;
+    *tau = d->hctrl->val[V_TAU];
+    return 0;
+}
+
+
+// ---- the workspace's device arrays, for the fused one-workgroup kernel (qpdo_small.hip: qdev_small_resident_*) ------------------------
+int qdev_small_view(QpdoDev *d, QdevSmallView *v) {
+    if (d->comm.active) return set_err(hipErrorInvalidValue, "qdev_small_view: row-partitioned workspace", __LINE__);
+    memset(v, 0, sizeof(*v));
+    v->device = d->device; v->stream = (void *)d->stream; v->n = d->n; v->m = d->m;
+    v->Arp = d->Ar.rp; v->Aci = d->Ar.ci; v->Aval = d->Ar.val;
+    v->Trp = d->At.rp; v->Tci = d->At.ci; v->Tval = d->At.val;
+    v->Qrp = d->Qf.rp; v->Qci = d->Qf.ci; v->Qval = d->Qf.val;
+    v->q = d->q; v->l = d->l; v->u = d->u;
+    v->scaled = d->scaled; v->D = d->D; v->Dinv = d->Dinv; v->E = d->E; v->Einv = d->Einv; v->c = d->sc_c; v->cinv = d->sc_cinv;
+    v->st_x = d->x; v->st_xbar = d->xbar; v->st_Qx = d->Qx; v->st_Aty = d->Aty;
+    v->st_y = d->y; v->st_ybar = d->ybar; v->st_Ax = d->Ax; v->st_mu = d->mu; v->st_isq = d->isq;
+    return 0;
+}

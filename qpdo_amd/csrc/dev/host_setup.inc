@@ -1,4 +1,4 @@
-// host_setup.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): create/destroy, configuration, scaling, warm start, residual pass
+// host_setup.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): create/destroy, configuration, scaling, warm start
 
 int qdev_rccl_unique_id(void *out128) {
     ncclUniqueId id;
@@ -539,74 +539,3 @@ int qdev_begin_solve(QpdoDev *d) {
     if (d->m) HIPCHK(hipMemsetAsync(d->active_old, 0, (size_t)d->m * sizeof(int), d->stream));
     return 0;
 }
-
-// ---- residual pass ---------------------------------------------------------------------------------
-static bool ahead_route_ok(const QpdoDev *d);                               // host_step.inc
-static int outer_tail_flush(QpdoDev *d);                                    // host_step.inc
-static int ahead_enqueue_step(QpdoDev *d, int proximal, double sigma);      // host_step.inc
-int qdev_residuals(QpdoDev *d, int proximal, double sigma, QdevResid *out) { return qdev_residuals_ahead(d, proximal, sigma, nullptr, out); }
-int qdev_residuals_ahead(QpdoDev *d, int proximal, double sigma, const QdevAhead *ahead, QdevResid *out) {
-    HIPCHK(hipSetDevice(d->device));
-    const int n = d->n, m = d->m;
-    bool go_ahead = ahead && ahead_route_ok(d);
-    d->ahead_inflight = 0;
-    { int rcf = outer_tail_flush(d); if (rcf) return rcf; }       // (nothing is pending after a complete outer update)
-    auto launch_resid = [&]() -> int {
-        if (!d->ctrl_clean) LAUNCH(k_ctrl_clear_pass, 1, d->ctrl);          // (a Newton step leaves the slots zeroed: k_newton_prep)
-        d->ctrl_clean = 0;
-        const int gm = vgrid(m), gn = vgrid(n);
-        ResidM a{m, d->scaled, d->sc_cinv, d->Ax, d->y, d->ybar, d->mu, d->l, d->u, d->E, d->Einv, d->res_prim, d->w, d->res_prim_in, d->active, d->active_old};
-        ResidN b{n, d->scaled, proximal, sigma, d->Qx, d->q, d->x, d->xbar, d->Aty, d->Dinv, d->df, d->res_dual, d->res_dual_in};
-        StepAx st{d->axpy_pending, d->x, d->Qx, d->Aty, d->y, d->Ax, d->dx, d->Qdx, d->Atdy, d->dy, d->Adx};
-        d->axpy_pending = 0;
-        PubArgs pb{nullptr, nullptr, 0, d->pub_ticket};
-        const bool fused_pub = d->ctrl_publish && d->fuse_resid;
-        if (fused_pub) { pb.host = d->hctrl; pb.hseq = d->hseq; pb.seq = ++d->pub_seq; }
-        SpecArgs sp{};
-        if (go_ahead && fused_pub) {
-            sp.on = 1; sp.allow_outer = ahead->allow_outer; sp.force_outer = ahead->force_outer; sp.reset_newton = ahead->reset_newton;
-            sp.max_rank = ahead->max_rank; sp.eps_abs = ahead->eps_abs; sp.eps_in = ahead->eps_in; sp.infty = ahead->infty; sp.cinv = d->sc_cinv;
-            sp.isq = d->isq; sp.d = d->d; sp.dy = d->dy;
-        }
-        LAUNCH(k_resid_mn, gm + gn, gm, a, b, d->ctrl, st, pb, sp);
-        if (sp.on) {
-            // the step goes into the stream before the host looks at the norms; the device decides whether it runs
-            int rca = ahead_enqueue_step(d, proximal, sigma); if (rca) return rca;
-            d->ahead_inflight = 1;
-        }
-        if (!fused_pub) return read_ctrl(d);
-        int rcw = ctrl_wait(d, d->hseq, pb.seq); if (rcw) return rcw;
-        HIPCHK(hipGetLastError());
-        return 0;
-    };
-    int rc = launch_resid(); if (rc) return rc;
-    out->prev_step_done = 0; out->prev_tau = 0.0;
-    if (d->step_pending) {
-        // the Newton step of the previous pass completes here (deferred read-back): its tau, and the lost-producer latch of its
-        // chained solves -- if that was set the device skipped the iterate update, so the residuals above are those of the OLD
-        // iterate; the step is redone stepwise and the residual kernels run again
-        int redone = 0;
-        rc = step_complete_pending(d, &out->prev_tau, &redone); if (rc) return rc;
-        out->prev_step_done = 1;
-        if (redone) {
-            // (a launched-ahead step of THIS pass left at once: the residual launch saw the latch of the lost producer)
-            if (d->ahead_inflight) { d->ahead_inflight = 0; d->st.ahead_skips++; d->st.spmv_calls -= d->ahead_spmv_calls0; d->st.spmv_bytes -= d->ahead_spmv_bytes0; }
-            d->ctrl_clean = 0; go_ahead = false;
-            rc = launch_resid(); if (rc) return rc;
-        }
-    }
-    out->ahead_enqueued = d->ahead_inflight; out->ahead_went = 0; out->ahead_branch = -1;
-    if (d->ahead_inflight) {
-        out->ahead_went = d->hctrl->cnt[C_SPEC_SKIP] == 0; out->ahead_branch = d->ahead_branch = d->hctrl->cnt[C_SPEC_BRANCH];
-        if (!out->ahead_went) { d->ahead_inflight = 0; d->st.ahead_skips++; d->st.spmv_calls -= d->ahead_spmv_calls0; d->st.spmv_bytes -= d->ahead_spmv_bytes0; }
-    }
-    const Ctrl *c = d->hctrl;
-    out->res_prim = nrm_of(c, N_PRIM);
-    out->res_prim_in = nrm_of(c, N_PRIM_IN);
-    out->res_dual = nrm_of(c, N_DUAL);
-    out->res_dual_in = nrm_of(c, N_DUAL_IN);
-    if (d->scaled) { out->res_dual *= d->sc_cinv; out->res_dual_in *= d->sc_cinv; }   // termination.c:45,72
-    out->n_active = c->cnt[C_ACTIVE]; out->n_enter = c->cnt[C_ENTER]; out->n_leave = c->cnt[C_LEAVE];
-    return 0;
-}
-

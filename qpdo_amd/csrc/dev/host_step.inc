@@ -1,10 +1,49 @@
-// host_step.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): linesearch driver, Newton step, outer-update helpers, measurement entry points
+// host_step.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): the Newton pass -- linesearch driver, the step's launches (one site each, shared by the host-first and the launched-ahead step), Newton step, residual pass -- and the outer-update helpers
+// ---- the launches of a step after its linear solve: the host-first step and the launched-ahead one issue them through these ----------
+// sort + scan + search of the linesearch in one launch (small problems; the bits of the radix path).  ahead: the launched-ahead step --
+// the kernel leaves if the device decided against a Newton step, and A'dy (iteration.c:23 needs it, the search does not) rides on the
+// launch as extra workgroups instead of being a launch of its own
+static void launch_ls_small(QpdoDev *d, int pm, int pn, bool ahead) {
+    LsProd lp{};
+    int gS = 0;
+    if (ahead) {
+        lp = LsProd{d->At.tpr, d->At.nrows, d->At.rp, d->At.ci, d->At.val, d->dy, d->Atdy};
+        gS = (d->At.nrows + 1024 / lp.tpr - 1) / (1024 / lp.tpr); if (gS > 128) gS = 128; if (gS < 1) gS = 1;
+        d->st.spmv_calls++; d->st.spmv_bytes += (int64_t)d->At.alg_bytes();
+    }
+    hipLaunchKernelGGL(k_ls_small, dim3(1 + gS), dim3(1024), 0, d->stream, d->ctrl, (const double *)d->part, pm, pn, (const u64 *)d->ls_key[0],
+                       (const double *)d->ls_delta, (const double *)d->ls_alpha, 2 * d->m, ahead ? 1 : 0, lp);
+}
+// the m-side of the linesearch as the epilogue of A dx
+static EpiAdxLs epi_adx_ls(QpdoDev *d) {
+    EpiAdxLs e{};
+    e.m = d->m; e.mu = d->mu; e.isq = d->isq; e.w = d->w; e.l = d->l; e.u = d->u; e.y = d->y; e.active = d->active; e.active_old = d->active_old;
+    e.Adx = d->Adx; e.dy = d->dy; e.delta = d->ls_delta; e.alpha = d->ls_alpha; e.key = d->ls_key[0]; e.idx = d->ls_idx[0];
+    e.p_eta = d->part + P_ETA_M * PGRID; e.p_beta = d->part + P_BETA_M * PGRID; e.p_a0 = d->part + P_A0 * PGRID; e.p_b0 = d->part + P_B0 * PGRID;
+    e.ctrl = d->ctrl;
+    return e;
+}
+// Q dx and A dx in one launch (spmv.inc k_spmv_pair): A's blocks first; Q's block partials are indexed by blockIdx.x, so their
+// pointers are shifted back by A's grid -- the same grids, the same partials as the two launches.  skip (launch-ahead, else null): the
+// kernel leaves if that word is set
+static void launch_adx_qdx_pair(QpdoDev *d, int proximal, double sigma, const int *skip) {
+    const int gA = spmv_grid(d->Ar, true), gQ = spmv_grid(d->Qf, true);
+    EpiQdx eq{d->dx, d->df, sigma, proximal, d->Qdx, d->part + P_DXQDX * PGRID - gA, d->part + P_DXDF * PGRID - gA};
+    hipLaunchKernelGGL((k_spmv_pair<EpiAdxLs, EpiQdx>), dim3(gA + gQ), dim3(BLK), 0, d->stream, gA, d->Ar.tpr, d->Ar.nrows, (const int *)d->Ar.rp,
+                       (const int *)d->Ar.ci, (const double *)d->Ar.val, (const double *)d->dx, epi_adx_ls(d), d->Qf.tpr, d->Qf.nrows, (const int *)d->Qf.rp,
+                       (const int *)d->Qf.ci, (const double *)d->Qf.val, (const double *)d->dx, eq, skip);
+    d->st.spmv_calls += 2; d->st.spmv_bytes += (int64_t)d->Ar.alg_bytes() + (int64_t)d->Qf.alg_bytes();
+}
+// the five axpys of the iterate update (skipped on the device if a chained solve reported a lost producer)
+static void launch_axpy5(QpdoDev *d) {
+    const int n = d->n, m = d->m;
+    LAUNCH(k_axpy5, vgrid(n > m ? n : m), n, m, d->ctrl, d->x, d->dx, d->Qx, d->Qdx, d->Aty, d->Atdy, d->y, d->dy, d->Ax, d->Adx);
+}
 // ---- linesearch sort + scan + search (shared by the Newton step and the parity entry point) -----------
 static int linesearch_device(QpdoDev *d, int pm, int pn) {
     const int M2 = 2 * d->m;
     if (d->ls_small && M2 <= LS_SMALL_MAX) {       // small problems: sort + scan + search in one launch, same bits as the path below
-        hipLaunchKernelGGL(k_ls_small, dim3(1), dim3(1024), 0, d->stream, d->ctrl, (const double *)d->part, pm, pn, (const u64 *)d->ls_key[0],
-                           (const double *)d->ls_delta, (const double *)d->ls_alpha, M2);
+        launch_ls_small(d, pm, pn, false);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -27,74 +66,61 @@ static int linesearch_device(QpdoDev *d, int pm, int pn) {
 }
 
 // the rest of a Newton step after the linear solve: Qdx (+ sigma dx) and the n-side dots, A dx with the m-side of the linesearch fused
-// behind it, A'dy, the breakpoint search, the five axpys (skipped on the device if a chained solve reported a lost producer); with
-// `sync` the control block is read back (tau, the lost-producer latch)
+// behind it, A'dy, the breakpoint search, the five axpys; with `sync` the control block is read back (tau, the lost-producer latch)
 static int newton_finish_step(QpdoDev *d, int proximal, double sigma, bool redo, bool sync) {
-    const int n = d->n, m = d->m;
-    EpiAdxLs e{};
-    e.m = m; e.mu = d->mu; e.isq = d->isq; e.w = d->w; e.l = d->l; e.u = d->u; e.y = d->y; e.active = d->active; e.active_old = d->active_old;
-    e.Adx = d->Adx; e.dy = d->dy; e.delta = d->ls_delta; e.alpha = d->ls_alpha; e.key = d->ls_key[0]; e.idx = d->ls_idx[0];
-    e.p_eta = d->part + P_ETA_M * PGRID; e.p_beta = d->part + P_BETA_M * PGRID; e.p_a0 = d->part + P_A0 * PGRID; e.p_b0 = d->part + P_B0 * PGRID;
-    e.ctrl = d->ctrl;
     int rc2 = 0;
-    if (d->fuse_outer && !d->comm.active && !d->Qf.use_slab && !d->Ar.use_slab && m > 0) {
-        // Q dx and A dx in one launch (spmv.inc k_spmv_pair): A's blocks first; Q's block partials are indexed by blockIdx.x, so their
-        // pointers are shifted back by A's grid -- the same grids, the same partials as the two launches
+    if (d->fuse_outer && !d->comm.active && !d->Qf.use_slab && !d->Ar.use_slab && d->m > 0) {
         if (redo) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_NL, 0);      // (the first time it is still zero from k_ctrl_clear_pass)
-        const int gA = spmv_grid(d->Ar, true), gQ = spmv_grid(d->Qf, true);
-        EpiQdx eq{d->dx, d->df, sigma, proximal, d->Qdx, d->part + P_DXQDX * PGRID - gA, d->part + P_DXDF * PGRID - gA};
-        hipLaunchKernelGGL((k_spmv_pair<EpiAdxLs, EpiQdx>), dim3(gA + gQ), dim3(BLK), 0, d->stream, gA, d->Ar.tpr, d->Ar.nrows, (const int *)d->Ar.rp,
-                           (const int *)d->Ar.ci, (const double *)d->Ar.val, (const double *)d->dx, e, d->Qf.tpr, d->Qf.nrows, (const int *)d->Qf.rp,
-                           (const int *)d->Qf.ci, (const double *)d->Qf.val, (const double *)d->dx, eq);
-        d->st.spmv_calls += 2; d->st.spmv_bytes += (int64_t)d->Ar.alg_bytes() + (int64_t)d->Qf.alg_bytes();
+        launch_adx_qdx_pair(d, proximal, sigma, nullptr);
     } else {
     launch_spmv(d, d->Qf, d->dx, EpiQdx{d->dx, d->df, sigma, proximal, d->Qdx, d->part + P_DXQDX * PGRID, d->part + P_DXDF * PGRID}, true);
     if (redo) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_NL, 0);      // (the first time it is still zero from k_ctrl_clear_pass)
-    rc2 = spmv_A(d, d->dx, e, true); if (rc2) return rc2;
+    rc2 = spmv_A(d, d->dx, epi_adx_ls(d), true); if (rc2) return rc2;
     }
     rc2 = spmv_At(d, d->dy, EpiStore{d->Atdy}, false); if (rc2) return rc2;
     rc2 = linesearch_device(d, pgrid_A(d), spmv_pgrid(d->Qf)); if (rc2) return rc2;
     // (a deferred step leaves its five axpys to the residual launch that follows it: k_resid_mn applies them in front of its own work;
     // qdev_finish_step flushes them if the solve ends first)
     if (!sync && d->fuse_resid) { d->axpy_pending = 1; return 0; }
-    LAUNCH(k_axpy5, vgrid(n > m ? n : m), n, m, d->ctrl, d->x, d->dx, d->Qx, d->Qdx, d->Aty, d->Atdy, d->y, d->dy, d->Ax, d->Adx);
+    launch_axpy5(d);
     return sync ? read_ctrl(d) : 0;
 }
-// The one-launch triangular solves poll their producers inside a launch; that relies on workgroups being dispatched in linear-id
-// order, which the HIP model does not promise (and a GPU shared with other processes can stretch).  A lost producer is latched in
-// C_CHAIN_ERR, the iterate update of that step was skipped on the device, and the step is redone -- for the rest of this workspace's
-// life with the stepwise solves (one launch per block step, no polling) on a fresh factor.  Never an error for the caller.  Called
-// with a freshly read control block; leaves the redone step's control block in d->hctrl.
+// The PCG solve of this pass.  The absolute stopping rule needs the proximal term: sigma > 0 pulls an error along a flat direction of
+// Q + A'DA back in the next pass; without it (settings->proximal = 0) such an error persists and the trajectory leaves the reference's
+// (seen on one of 120 sweep instances), so those solves keep the relative rule alone.
+static int pcg_solve_pass(QpdoDev *d, int proximal, int *lin) {
+    d->pcg_abs_now = proximal ? d->pcg_abs : -1.0;
+    d->cur_proximal = proximal;
+    return pcg_solve(d, lin);
+}
+// A latch in C_CHAIN_ERR means that the device skipped this pass's iterate update; the pass is redone by another solver, which this
+// workspace keeps from then on.  Never an error for the caller, never inf / NaN in dx, never silently.  Two producers set the latch:
+//  - The one-launch triangular solves poll their producers inside a launch; that relies on workgroups being dispatched in linear-id
+//    order, which the HIP model does not promise (and a GPU shared with other processes can stretch).  A lost producer is redone with
+//    the stepwise solves (one launch per block step, no polling) on a fresh multi-launch factor.
+//  - The band factorization met a pivot that is not a positive finite number (k_band_factor latches bit 1): with settings->proximal = 0
+//    the banded Q + A'DA may be singular along a direction.  The dense solver takes over (n <= DENSE_LIMIT_N; it reports such a matrix
+//    through its own residual checks), or PCG.
+// Called with a freshly read control block; leaves the redone step's control block in d->hctrl.
 static int step_redo_if_lost(QpdoDev *d, int proximal, double sigma) {
     if (!d->hctrl->cnt[C_CHAIN_ERR]) return 0;
-    if (d->linsolve == 3) {
-        // The band factorization met a pivot that is not a positive finite number (k_band_factor latches bit 1): with settings->proximal = 0
-        // the banded Q + A'DA may be singular along a direction.  The device skipped this pass's iterate update; the pass is redone -- and the
-        // rest of this workspace's solves are made -- by the dense solver (n <= DENSE_LIMIT_N, which reports such a matrix through its own
-        // residual checks) or by PCG.  Never inf / NaN in dx, never silently.
-        const int m = d->m;
-        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-        d->st.band_fallbacks++;
-        d->linsolve = (d->n <= DENSE_LIMIT_N && !d->comm.active) ? 1 : 0; d->st.linsolve = d->linsolve; d->dense_valid = 0; d->dense_factored = 0;
-        LAUNCH(k_newton_prep, vgrid(m), m, 3, d->active, d->active_old, d->isq, d->mu, d->res_prim_in, d->d, d->dy);      // dy = t again
-        int rc = spmv_At(d, d->dy, EpiRhs{d->res_dual_in, d->Atdy, d->rhs}, false); if (rc) return rc;
-        if (d->linsolve == 1) { rc = dense_factor(d, true); if (rc) return rc; rc = dense_solve(d); if (rc) return rc; }
-        else { int lin = 0; d->pcg_abs_now = proximal ? d->pcg_abs : -1.0; d->cur_proximal = proximal; rc = pcg_solve(d, &lin); if (rc) return rc; d->st.lin_iters += lin; }
-        return newton_finish_step(d, proximal, sigma, true, true);
-    }
-    if (!(d->linsolve == 1 && d->dense_chain)) {
-        // the latch is set although no polling kernel can have run in this step (stale): the device skipped this step's iterate update
-        // on its account, so it cannot be ignored -- clear it and report, instead of looping to max_iter on a frozen iterate
-        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-        return set_err(hipErrorUnknown, "lost-producer latch set without a chained solve in flight (stale latch; step skipped)", __LINE__);
-    }
+    const bool band = d->linsolve == 3;
     const int m = d->m;
     LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-    d->dense_chain = 0; d->dense_mid = 0; d->wb_enable = 0; d->ud_cap = 0; d->st.chain_fallbacks++;
+    if (band) {
+        d->st.band_fallbacks++;
+        d->linsolve = (d->n <= DENSE_LIMIT_N && !d->comm.active) ? 1 : 0; d->st.linsolve = d->linsolve; d->dense_valid = 0; d->dense_factored = 0;
+    } else if (d->linsolve == 1 && d->dense_chain) {
+        d->dense_chain = 0; d->dense_mid = 0; d->wb_enable = 0; d->ud_cap = 0; d->st.chain_fallbacks++;
+    } else {
+        // the latch is set although no polling kernel can have run in this step (stale): the device skipped this step's iterate update
+        // on its account, so it cannot be ignored -- it is cleared and reported, instead of looping to max_iter on a frozen iterate
+        return set_err(hipErrorUnknown, "lost-producer latch set without a chained solve in flight (stale latch; step skipped)", __LINE__);
+    }
     LAUNCH(k_newton_prep, vgrid(m), m, 3, d->active, d->active_old, d->isq, d->mu, d->res_prim_in, d->d, d->dy);      // dy = t again
     int rc = spmv_At(d, d->dy, EpiRhs{d->res_dual_in, d->Atdy, d->rhs}, false); if (rc) return rc;
-    rc = dense_factor(d); if (rc) return rc;
-    rc = dense_solve(d); if (rc) return rc;
+    if (d->linsolve == 1) { rc = dense_factor_and_solve(d, band); if (rc) return rc; }      // (after a band: the factorization may carry the right-hand side)
+    else { int lin = 0; rc = pcg_solve_pass(d, proximal, &lin); if (rc) return rc; d->st.lin_iters += lin; }
     return newton_finish_step(d, proximal, sigma, true, true);
 }
 
@@ -143,60 +169,35 @@ static int pcg_rescue(QpdoDev *d, int *lin) {
 // before, and qdev_newton_step only books what is already in flight -- after checking that both decisions agree.
 // Route: dense one-launch factorization (k_mid_factor) + chained backward solve, every pass refactors (no low-rank path: n < 9000),
 // one GPU, the one-launch linesearch, deferred step with the axpys folded into the next residual launch.  Not with QPDO_DENSE_UPDOWN:
-// this route refactors every pass by construction, that one exists to keep the factor.  The kernels, their grids
-// and their order are those of qdev_newton_step -> dense_factor / dense_solve / newton_finish_step: the same bits.
+// this route refactors every pass by construction, that one exists to keep the factor.  Each launch below is the
+// launch site that qdev_newton_step -> dense_factor / dense_solve / newton_finish_step go through, with the guard switched on: the same bits.
 static bool ahead_route_ok(const QpdoDev *d) {
     return d->launch_ahead && d->linsolve == 1 && !d->hybrid_active && !d->comm.active && d->defer_step && d->fuse_resid && d->ctrl_publish &&
            d->fuse_outer && d->m > 0 && !d->Qf.use_slab && !d->Ar.use_slab && !d->At.use_slab && d->ls_small && 2 * d->m <= LS_SMALL_MAX &&
            d->Kd && d->dense_mid && d->dense_chain && d->mid_flags && d->dense_nblk <= MID_MAX_NB && !d->wb_enable && !d->ud_cap;
 }
 static int ahead_enqueue_step(QpdoDev *d, int proximal, double sigma) {
-    const int n = d->n, m = d->m, ld = d->dense_ld, nb = d->dense_nblk;
-    const Ctrl *spec = d->ctrl;
-    const int *skip = &d->ctrl->cnt[C_SPEC_SKIP];
-    d->ahead_spmv_calls0 = d->st.spmv_calls; d->ahead_spmv_bytes0 = d->st.spmv_bytes;
-    // qdev_newton_step: the weights and t were made by the residual launch's publishing block (k_newton_prep's work; vector.inc SpecArgs);
-    // dense_factor(d, true): assembly, with the right-hand side rhs = -res_dual_in - A't (EpiRhs) computed by extra blocks of the same
-    // launch straight into the factorization's padded copy; the one-launch factorization with the forward solve
-    d->ahead_sigma_f02 = proximal ? sigma : 0.0;
-    const int g = ld < 1024 ? ld : 1024;
-    const int asm_tile = n < d->dense_asm_tile ? (n > 0 ? n : 1) : d->dense_asm_tile;
-    AsmRhs ar{};
-    ar.on = 1; ar.g0 = g; ar.tpr = d->At.tpr; ar.nrows = d->At.nrows; ar.rp = d->At.rp; ar.ci = d->At.ci; ar.val = d->At.val; ar.x = d->dy;
-    ar.rdi = d->res_dual_in; ar.atdy = d->Atdy; ar.rhs = d->rhs;
-    int gR = (d->At.nrows + 64 / ar.tpr - 1) / (64 / ar.tpr); if (gR > 1024) gR = 1024; if (gR < 1) gR = 1;
-    hipLaunchKernelGGL(k_dense_assemble, dim3(g + gR), dim3(64), (size_t)asm_tile * sizeof(double), d->stream, n, ld, asm_tile, d->Qf.rp, d->Qf.ci, d->Qf.val,
-                       d->At.rp, d->At.ci, d->At.val, d->Ar.rp, d->Ar.ci, d->Ar.val, (const double *)d->d, d->ahead_sigma_f02, d->Kd,
-                       (const double *)nullptr, d->dxw, (unsigned long long *)d->dz, (unsigned long long *)d->ch_x, spec, d->sigma_f, ar);
-    d->st.spmv_calls++; d->st.spmv_bytes += (int64_t)d->At.alg_bytes();
-    hipLaunchKernelGGL(k_mid_factor, dim3(nb * (nb + 1) / 2 + nb), dim3(256), MID_LDS_DOUBLES * 8, d->stream, d->Kd, n, ld, nb, d->Dg, d->Linv, d->LinvT,
-                       (const double *)d->dxw, d->dz, d->ch_y, d->mid_flags, ++d->mid_epoch, d->ctrl, d->mid_C, d->mid_dinv, 1);
+    const auto calls0 = d->st.spmv_calls; const auto bytes0 = d->st.spmv_bytes;
+    // qdev_newton_step: the weights and t were made by the residual launch's publishing block (k_newton_prep's work; vector.inc SpecArgs)
+    d->ahead_sigma_f02 = proximal ? sigma : 0.0;      // sigma_f of branches 0 and 2; branch 1 keeps the factor's (the assembly picks on the device)
+    // dense_factor(d, true): assembly, forming the right-hand side on the way; the one-launch factorization with the forward solve
+    launch_dense_assemble(d, ASM_RHS_FORM, d->ahead_sigma_f02);
+    launch_mid_factor(d, true, 1);
     // dense_solve: the forward solve came with the factorization; backward chain into dx
-    hipLaunchKernelGGL(k_ldl_chain<false>, dim3(1, nb), dim3(256), 0, d->stream, (const double *)d->Kd, ld, nb, (const double *)d->LinvT,
-                       (const double *)d->Dg, (const double *)d->ch_y, d->ch_x, d->dx, n, d->ctrl, 1);
-    // newton_finish_step: Q dx | A dx (+ the m-side of the linesearch), A'dy, the breakpoint search; the axpys ride on the next residual launch
-    EpiAdxLs e{};
-    e.m = m; e.mu = d->mu; e.isq = d->isq; e.w = d->w; e.l = d->l; e.u = d->u; e.y = d->y; e.active = d->active; e.active_old = d->active_old;
-    e.Adx = d->Adx; e.dy = d->dy; e.delta = d->ls_delta; e.alpha = d->ls_alpha; e.key = d->ls_key[0]; e.idx = d->ls_idx[0];
-    e.p_eta = d->part + P_ETA_M * PGRID; e.p_beta = d->part + P_BETA_M * PGRID; e.p_a0 = d->part + P_A0 * PGRID; e.p_b0 = d->part + P_B0 * PGRID;
-    e.ctrl = d->ctrl;
-    const int gA = spmv_grid(d->Ar, true), gQ = spmv_grid(d->Qf, true);
-    EpiQdx eq{d->dx, d->df, sigma, proximal, d->Qdx, d->part + P_DXQDX * PGRID - gA, d->part + P_DXDF * PGRID - gA};
-    hipLaunchKernelGGL((k_spmv_pair<EpiAdxLs, EpiQdx>), dim3(gA + gQ), dim3(BLK), 0, d->stream, gA, d->Ar.tpr, d->Ar.nrows, (const int *)d->Ar.rp,
-                       (const int *)d->Ar.ci, (const double *)d->Ar.val, (const double *)d->dx, e, d->Qf.tpr, d->Qf.nrows, (const int *)d->Qf.rp,
-                       (const int *)d->Qf.ci, (const double *)d->Qf.val, (const double *)d->dx, eq, skip);
-    d->st.spmv_calls += 2; d->st.spmv_bytes += (int64_t)d->Ar.alg_bytes() + (int64_t)d->Qf.alg_bytes();
-    // A'dy (iteration.c:23 needs it, the search does not) rides on the linesearch launch as extra workgroups
-    LsProd lp{d->At.tpr, d->At.nrows, d->At.rp, d->At.ci, d->At.val, d->dy, d->Atdy};
-    int gS = (d->At.nrows + 1024 / lp.tpr - 1) / (1024 / lp.tpr); if (gS > 128) gS = 128; if (gS < 1) gS = 1;
-    hipLaunchKernelGGL(k_ls_small, dim3(1 + gS), dim3(1024), 0, d->stream, d->ctrl, (const double *)d->part, pgrid_A(d), spmv_pgrid(d->Qf), (const u64 *)d->ls_key[0],
-                       (const double *)d->ls_delta, (const double *)d->ls_alpha, 2 * m, 1, lp);
-    d->st.spmv_calls++; d->st.spmv_bytes += (int64_t)d->At.alg_bytes();
+    launch_ldl_chain<false>(d, 1, d->ch_y, d->ch_x, d->dx, d->n, 1);
+    // newton_finish_step: A dx (+ the m-side of the linesearch) | Q dx, the breakpoint search with A'dy; the axpys ride on the next residual launch
+    launch_adx_qdx_pair(d, proximal, sigma, &d->ctrl->cnt[C_SPEC_SKIP]);
+    launch_ls_small(d, pgrid_A(d), spmv_pgrid(d->Qf), true);
     HIPCHK(hipGetLastError());
-    d->ahead_spmv_calls0 = d->st.spmv_calls - d->ahead_spmv_calls0; d->ahead_spmv_bytes0 = d->st.spmv_bytes - d->ahead_spmv_bytes0;     // (taken back if the step leaves)
+    d->ahead_spmv_calls0 = d->st.spmv_calls - calls0; d->ahead_spmv_bytes0 = d->st.spmv_bytes - bytes0;     // (taken back if the step leaves)
     return 0;
 }
-// the launched-ahead step ran: book what qdev_newton_step / dense_factor / dense_solve / newton_finish_step would have booked
+// a launched-ahead step left at once (the device decided against it, or saw the latch of a lost producer): un-book it
+static void ahead_drop_step(QpdoDev *d) {
+    d->ahead_inflight = 0; d->st.ahead_skips++;
+    d->st.spmv_calls -= d->ahead_spmv_calls0; d->st.spmv_bytes -= d->ahead_spmv_bytes0;
+}
+// the launched-ahead step ran: book what qdev_newton_step / dense_solve / newton_finish_step would have booked
 static int ahead_adopt_step(QpdoDev *d, int branch, int proximal, double sigma, double *tau_out, int *lin_iters_out) {
     d->ahead_inflight = 0;
     const int dev_branch = d->ahead_branch;            // (as read with this pass's residual norms: qdev_residuals_ahead)
@@ -206,8 +207,7 @@ static int ahead_adopt_step(QpdoDev *d, int branch, int proximal, double sigma, 
     }
     if (branch == 0 || branch == 2) d->sigma_f = d->ahead_sigma_f02;
     d->ctrl_clean = 1;
-    d->mid_fwd_valid = 0; d->st.onelaunch_factors++; d->st.factor_count++;
-    d->dense_valid = 1; d->dense_factored = 1; d->dense_fact_sigma = d->sigma_f; d->wb_k = 0;
+    int rc = dense_factor_enqueued(d, true, false); if (rc) return rc;      // (the backward chain has used the carried forward solve)
     d->dsol = d->ch_x;
 #ifdef QPDO_TEST_HOOKS
     if (d->chain_inject >= 0 && (long long)d->st.newton_passes == d->chain_inject) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 1);
@@ -245,23 +245,7 @@ int qdev_newton_step(QpdoDev *d, int branch, int n_changed, int proximal, double
     } else if (d->linsolve == 1) {
         // (the latch of the polling kernels -- one-launch outer panels, chained solves -- was cleared by this pass's k_ctrl_clear_pass
         // and is read back with the step)
-        if (!d->dense_valid) {
-            // reference: full factorization in branch 0, rank update of the kept factor otherwise (newton.c:21-33)
-            bool full = !d->dense_factored || branch == 0 || d->sigma_f != d->dense_fact_sigma;
-            // QPDO_DENSE_UPDOWN: few changed rows change the kept factor in place (no low-rank slot held: its columns belong to the factor as it was)
-            int updated = 0;
-            if (!full && d->ud_cap > 0 && d->wb_k == 0) { rc = ud_apply(d, &updated); if (rc) return rc; }
-            if (updated) d->dense_valid = 1;
-            else {
-                if (!d->wb_enable) full = true;
-                if (!full) {
-                    int overflow = 0;
-                    rc = wb_extend(d, &overflow); if (rc) return rc;
-                    if (overflow) full = true; else d->dense_valid = 1;
-                }
-                if (full) { rc = dense_factor(d, true); if (rc) return rc; }
-            }
-        }
+        if (!d->dense_valid) { rc = dense_refresh_factor(d, branch == 0, true); if (rc) return rc; }
         rc = dense_solve(d); if (rc) return rc;
 #ifdef QPDO_TEST_HOOKS
         {   // test hook (QPDO_DENSE_CHAIN_INJECT=<pass>): pretend the chained solve of that Newton pass lost a producer
@@ -270,32 +254,25 @@ int qdev_newton_step(QpdoDev *d, int branch, int n_changed, int proximal, double
         }
 #endif
     } else {
-        // The absolute stopping rule needs the proximal term: sigma > 0 pulls an error along a flat direction of Q + A'DA back in the
-        // next pass; without it (settings->proximal = 0) such an error persists and the trajectory leaves the reference's
-        // (seen on one of 120 sweep instances), so those solves keep the relative rule alone.
-        d->pcg_abs_now = proximal ? d->pcg_abs : -1.0;
-        d->cur_proximal = proximal;
         const bool was_hybrid = d->hybrid_active;
-        rc = pcg_solve(d, &lin);
+        rc = pcg_solve_pass(d, proximal, &lin);
         if (rc == 0 && was_hybrid) d->st.hybrid_pcg_passes++;
-        if ((rc == PCG_NOT_CONVERGED || rc == PCG_NAN) && d->hybrid_active) {
-            // (every numerical failure of the PCG solve -- budget, cap, stagnation, NaN -- hands the pass to the dense factor: a workspace
-            // whose solver was chosen as "dense" must not end in QPDO_ERROR where the dense solver alone would have succeeded)
+        const bool failed = rc == PCG_NOT_CONVERGED || rc == PCG_NAN;      // every numerical failure: budget, cap, stagnation, NaN
+        if (failed && d->hybrid_active) {
+            // (a workspace whose solver was chosen as "dense" must not end in QPDO_ERROR where the dense solver alone would have succeeded)
             // hybrid: this pass's system is past the point where PCG is the cheaper solver -- the dense factor from here on (same system)
             d->hybrid_active = 0; d->linsolve = 1; d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0;
-            rc = dense_factor(d, true); if (rc) return rc;
-            rc = dense_solve(d); if (rc) return rc;
+            rc = dense_factor_and_solve(d, true); if (rc) return rc;
             lin = 0;
-        } else if ((rc == PCG_NOT_CONVERGED || rc == PCG_NAN) && d->pcg_dense_fallback && !d->comm.active && n <= DENSE_LIMIT_N) {
+        } else if (failed && d->pcg_dense_fallback && !d->comm.active && n <= DENSE_LIMIT_N) {
             // The reference solves this system with a direct factorization (cholmod_interface.c:35-52,98-102) and does not care how
             // ill-conditioned it is.  A PCG solve that stagnates above 1e-8 -- seen with settings->proximal = 0, where Q + A'DA may be
             // singular to working precision -- is therefore redone by the dense LDL' solver, which this workspace keeps from then on
             // (the same (sigma_f, d) system, so the trajectory is the reference's).  Above the dense limit the error stands.
             d->linsolve = 1; d->dense_valid = 0; d->st.pcg_dense_fallbacks++;
-            rc = dense_factor(d, true); if (rc) return rc;
-            rc = dense_solve(d); if (rc) return rc;
+            rc = dense_factor_and_solve(d, true); if (rc) return rc;
             lin = 0;
-        } else if ((rc == PCG_NOT_CONVERGED || rc == PCG_NAN) && d->pcg_dense_fallback) {
+        } else if (failed && d->pcg_dense_fallback) {
             // no dense factor at this order / on a row partition: the other rescues (band direct solver, plain-Jacobi retry)
             rc = pcg_rescue(d, &lin); if (rc) return rc;
         } else if (rc) return rc;
@@ -303,16 +280,15 @@ int qdev_newton_step(QpdoDev *d, int branch, int n_changed, int proximal, double
     d->dense_last_branch = branch; d->dense_last_sigma = d->sigma_f;
     d->st.lin_iters += lin;
     *lin_iters_out = lin;
-    auto finish_step = [&](bool redo, bool sync) -> int { return newton_finish_step(d, proximal, sigma, redo, sync); };
     if (d->defer_step && (d->linsolve == 1 || d->linsolve == 3) && !d->comm.active) {
         // deferred read-back: everything above is in flight; tau and the lost-producer latch arrive with the next residual pass
-        rc = finish_step(false, false); if (rc) return rc;
+        rc = newton_finish_step(d, proximal, sigma, false, false); if (rc) return rc;
         d->step_pending = 1; d->pend_proximal = proximal; d->pend_sigma = sigma;
         *tau_out = NAN;
         d->st.newton_passes++;
         return 0;
     }
-    rc = finish_step(false, true); if (rc) return rc;
+    rc = newton_finish_step(d, proximal, sigma, false, true); if (rc) return rc;
     rc = step_redo_if_lost(d, proximal, sigma); if (rc) return rc;
     *tau_out = d->hctrl->val[V_TAU];
     d->st.newton_passes++;
@@ -334,14 +310,94 @@ int qdev_finish_step(QpdoDev *d, int *had_pending, double *tau) {
     HIPCHK(hipSetDevice(d->device));
     *had_pending = d->step_pending;
     if (!d->step_pending) return 0;
-    if (d->axpy_pending) {
-        const int n = d->n, m = d->m;
-        LAUNCH(k_axpy5, vgrid(n > m ? n : m), n, m, d->ctrl, d->x, d->dx, d->Qx, d->Qdx, d->Aty, d->Atdy, d->y, d->dy, d->Ax, d->Adx);
-        d->axpy_pending = 0;
-    }
+    if (d->axpy_pending) { launch_axpy5(d); d->axpy_pending = 0; }
     int rc = read_ctrl(d); if (rc) return rc;
     int redone = 0;
     return step_complete_pending(d, tau, &redone);
+}
+
+// The tail of an outer update -- shifting the estimates, the mu-changed weights, the sigma term of Qx, saving res_prim -- is four
+// elementwise kernels that depend on nothing of each other; with QPDO_FUSE_OUTER they are collected and launched as ONE (k_outer_tail) by
+// the call that ends every outer update (qdev_save_res_prim), or by outer_tail_flush if something else wants the vectors first.
+static int outer_tail_launch(QpdoDev *d, int save) {
+    if (!d->tail_shift && !d->tail_muchg && !d->tail_sigma && !save) return 0;
+    OuterTail t{};
+    t.n = d->n; t.m = d->m; t.shift = d->tail_shift; t.muchg = d->tail_muchg; t.sigma = d->tail_sigma; t.save = save && d->m > 0; t.dsig = d->tail_dsig;
+    t.x = d->x; t.y = d->y; t.at_scale = d->at_scale; t.isq = d->isq; t.res_prim = d->res_prim; t.changed = d->mu_changed;
+    t.xbar = d->xbar; t.ybar = d->ybar; t.d = d->d; t.Qx = d->Qx; t.res_prim_old = d->res_prim_old; t.ctrl = d->ctrl;
+    d->tail_shift = d->tail_muchg = d->tail_sigma = 0; d->tail_dsig = 0.0;
+    LAUNCH(k_outer_tail, vgrid(d->n > d->m ? d->n : d->m), t);
+    HIPCHK(hipGetLastError());
+    if (t.save) d->ctrl_clean = 1;
+    return 0;
+}
+static int outer_tail_flush(QpdoDev *d) { return outer_tail_launch(d, 0); }
+
+// ---- residual pass ---------------------------------------------------------------------------------
+int qdev_residuals(QpdoDev *d, int proximal, double sigma, QdevResid *out) { return qdev_residuals_ahead(d, proximal, sigma, nullptr, out); }
+int qdev_residuals_ahead(QpdoDev *d, int proximal, double sigma, const QdevAhead *ahead, QdevResid *out) {
+    HIPCHK(hipSetDevice(d->device));
+    const int n = d->n, m = d->m;
+    bool go_ahead = ahead && ahead_route_ok(d);
+    d->ahead_inflight = 0;
+    { int rcf = outer_tail_flush(d); if (rcf) return rcf; }       // (nothing is pending after a complete outer update)
+    auto launch_resid = [&]() -> int {
+        if (!d->ctrl_clean) LAUNCH(k_ctrl_clear_pass, 1, d->ctrl);          // (a Newton step leaves the slots zeroed: k_newton_prep)
+        d->ctrl_clean = 0;
+        const int gm = vgrid(m), gn = vgrid(n);
+        ResidM a{m, d->scaled, d->sc_cinv, d->Ax, d->y, d->ybar, d->mu, d->l, d->u, d->E, d->Einv, d->res_prim, d->w, d->res_prim_in, d->active, d->active_old};
+        ResidN b{n, d->scaled, proximal, sigma, d->Qx, d->q, d->x, d->xbar, d->Aty, d->Dinv, d->df, d->res_dual, d->res_dual_in};
+        StepAx st{d->axpy_pending, d->x, d->Qx, d->Aty, d->y, d->Ax, d->dx, d->Qdx, d->Atdy, d->dy, d->Adx};
+        d->axpy_pending = 0;
+        PubArgs pb{nullptr, nullptr, 0, d->pub_ticket};
+        const bool fused_pub = d->ctrl_publish && d->fuse_resid;
+        if (fused_pub) { pb.host = d->hctrl; pb.hseq = d->hseq; pb.seq = ++d->pub_seq; }
+        SpecArgs sp{};
+        if (go_ahead && fused_pub) {
+            sp.on = 1; sp.allow_outer = ahead->allow_outer; sp.force_outer = ahead->force_outer; sp.reset_newton = ahead->reset_newton;
+            sp.max_rank = ahead->max_rank; sp.eps_abs = ahead->eps_abs; sp.eps_in = ahead->eps_in; sp.infty = ahead->infty; sp.cinv = d->sc_cinv;
+            sp.isq = d->isq; sp.d = d->d; sp.dy = d->dy;
+        }
+        LAUNCH(k_resid_mn, gm + gn, gm, a, b, d->ctrl, st, pb, sp);
+        if (sp.on) {
+            // the step goes into the stream before the host looks at the norms; the device decides whether it runs
+            int rca = ahead_enqueue_step(d, proximal, sigma); if (rca) return rca;
+            d->ahead_inflight = 1;
+        }
+        if (!fused_pub) return read_ctrl(d);
+        int rcw = ctrl_wait(d, d->hseq, pb.seq); if (rcw) return rcw;
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    int rc = launch_resid(); if (rc) return rc;
+    out->prev_step_done = 0; out->prev_tau = 0.0;
+    if (d->step_pending) {
+        // the Newton step of the previous pass completes here (deferred read-back): its tau, and the lost-producer latch of its
+        // chained solves -- if that was set the device skipped the iterate update, so the residuals above are those of the OLD
+        // iterate; the step is redone stepwise and the residual kernels run again
+        int redone = 0;
+        rc = step_complete_pending(d, &out->prev_tau, &redone); if (rc) return rc;
+        out->prev_step_done = 1;
+        if (redone) {
+            // (a launched-ahead step of THIS pass left at once: the residual launch saw the latch of the lost producer)
+            if (d->ahead_inflight) ahead_drop_step(d);
+            d->ctrl_clean = 0; go_ahead = false;
+            rc = launch_resid(); if (rc) return rc;
+        }
+    }
+    out->ahead_enqueued = d->ahead_inflight; out->ahead_went = 0; out->ahead_branch = -1;
+    if (d->ahead_inflight) {
+        out->ahead_went = d->hctrl->cnt[C_SPEC_SKIP] == 0; out->ahead_branch = d->ahead_branch = d->hctrl->cnt[C_SPEC_BRANCH];
+        if (!out->ahead_went) ahead_drop_step(d);
+    }
+    const Ctrl *c = d->hctrl;
+    out->res_prim = nrm_of(c, N_PRIM);
+    out->res_prim_in = nrm_of(c, N_PRIM_IN);
+    out->res_dual = nrm_of(c, N_DUAL);
+    out->res_dual_in = nrm_of(c, N_DUAL_IN);
+    if (d->scaled) { out->res_dual *= d->sc_cinv; out->res_dual_in *= d->sc_cinv; }   // termination.c:45,72
+    out->n_active = c->cnt[C_ACTIVE]; out->n_enter = c->cnt[C_ENTER]; out->n_leave = c->cnt[C_LEAVE];
+    return 0;
 }
 
 // ---- outer-update helpers ---------------------------------------------------------------------------------
@@ -472,22 +528,6 @@ int qdev_dual_infeasibility(QpdoDev *d, int proximal, double sigma, double tau, 
     int nch = 0;
     return qdev_dual_infeasibility_and_mu(d, 1, proximal, sigma, tau, eps_dual_inf, 0, 0, 0, 0, 0, 0, is_infeasible, &nch);
 }
-// The tail of an outer update -- shifting the estimates, the mu-changed weights, the sigma term of Qx, saving res_prim -- is four
-// elementwise kernels that depend on nothing of each other; with QPDO_FUSE_OUTER they are collected and launched as ONE (k_outer_tail) by
-// the call that ends every outer update (qdev_save_res_prim), or by outer_tail_flush if something else wants the vectors first.
-static int outer_tail_launch(QpdoDev *d, int save) {
-    if (!d->tail_shift && !d->tail_muchg && !d->tail_sigma && !save) return 0;
-    OuterTail t{};
-    t.n = d->n; t.m = d->m; t.shift = d->tail_shift; t.muchg = d->tail_muchg; t.sigma = d->tail_sigma; t.save = save && d->m > 0; t.dsig = d->tail_dsig;
-    t.x = d->x; t.y = d->y; t.at_scale = d->at_scale; t.isq = d->isq; t.res_prim = d->res_prim; t.changed = d->mu_changed;
-    t.xbar = d->xbar; t.ybar = d->ybar; t.d = d->d; t.Qx = d->Qx; t.res_prim_old = d->res_prim_old; t.ctrl = d->ctrl;
-    d->tail_shift = d->tail_muchg = d->tail_sigma = 0; d->tail_dsig = 0.0;
-    LAUNCH(k_outer_tail, vgrid(d->n > d->m ? d->n : d->m), t);
-    HIPCHK(hipGetLastError());
-    if (t.save) d->ctrl_clean = 1;
-    return 0;
-}
-static int outer_tail_flush(QpdoDev *d) { return outer_tail_launch(d, 0); }
 int qdev_shift_estimates(QpdoDev *d) {
     HIPCHK(hipSetDevice(d->device));
     if (d->fuse_outer) { d->tail_shift = 1; return 0; }
@@ -577,206 +617,5 @@ int qdev_store_solution(QpdoDev *d, double *sol_x, double *sol_y, double *x, dou
         HIPCHK(hipMemcpyAsync(dy, d->dy, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
     }
     HIPCHK(hipStreamSynchronize(d->stream));
-    return 0;
-}
-
-// ---- measurement + parity entry points ---------------------------------------------------------------------
-static DevCsr *mat_by_id(QpdoDev *d, int which) { return which == 0 ? &d->Ar : which == 1 ? &d->At : &d->Qf; }
-
-int qdev_bench_spmv(QpdoDev *d, int which, int reps, double *avg_seconds, double *alg_bytes) {
-    HIPCHK(hipSetDevice(d->device));
-    DevCsr *M = mat_by_id(d, which);
-    double *xin = (M->ncols == d->n) ? d->pc_p : d->pc_t;
-    double *yout = (M->nrows == d->n) ? d->pc_Kp : d->tmp_m;
-    LAUNCH(k_fill, vgrid(M->ncols), M->ncols, 1.0, xin);
-    launch_spmv(d, *M, xin, EpiStore{yout}, false);     // warm-up
-    HIPCHK(hipEventRecord(d->ev0, d->stream));
-    for (int r = 0; r < reps; r++) launch_spmv(d, *M, xin, EpiStore{yout}, false);
-    HIPCHK(hipEventRecord(d->ev1, d->stream));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-    *avg_seconds = (double)ms * 1e-3 / (double)reps;
-    *alg_bytes = M->alg_bytes();
-    return 0;
-}
-// dense factorization of K = Q + sigma_f I + A' diag(d) A with the workspace's CURRENT weights, `reps` times back to back, timed
-// with HIP events on the solver's stream (the look-ahead stream joins it before the factor ends).  flops = n^3 / 3 per factor.
-// check != NULL: relative residual ||rhs - K x||inf / ||rhs||inf of one solve with the fresh factor (rhs = the diagonal of Q + 1).
-int qdev_bench_dense_factor(QpdoDev *d, int reps, double *avg_seconds, double *check) {
-    HIPCHK(hipSetDevice(d->device));
-    if (d->comm.active) return set_err(hipErrorInvalidValue, "dense factor bench: not for partitioned workspaces", __LINE__);
-    int rc = dense_alloc(d); if (rc) return rc;
-    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-    rc = dense_factor(d); if (rc) return rc;               // warm-up (allocations, code objects)
-    HIPCHK(hipEventRecord(d->ev0, d->stream));
-    for (int r = 0; r < reps; r++) { rc = dense_factor(d); if (rc) return rc; }
-    HIPCHK(hipEventRecord(d->ev1, d->stream));
-    HIPCHK(hipEventSynchronize(d->ev1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-    *avg_seconds = (double)ms * 1e-3 / (double)(reps > 0 ? reps : 1);
-    d->st.factor_count -= reps + 1;
-    if (d->st.onelaunch_factors >= reps + 1) d->st.onelaunch_factors -= reps + 1;
-    if (check) {
-        const int n = d->n;
-        if (!d->qdiag_valid) { LAUNCH(k_extract_diag, vgrid(n), n, d->Qf.rp, d->Qf.ci, d->Qf.val, d->qdiag); d->qdiag_valid = 1; }
-        LAUNCH(k_axpy_const, vgrid(n), n, (const double *)d->qdiag, 1.0, d->rhs);
-        const int wbk = d->wb_k; d->wb_k = 0;
-        rc = dense_solve(d); d->wb_k = wbk; if (rc) return rc;
-        LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
-        LAUNCH(k_absmax_mul, vgrid(n), n, (const double *)d->rhs, (const double *)nullptr, d->ctrl, N_A);
-        LAUNCH(k_ctrl_set_nrm0, 1, d->ctrl, N_B);
-        launch_spmv(d, d->Ar, d->dx, EpiPcgA{d->d, d->tmp_m, nullptr}, false);
-        launch_spmv(d, d->Qf, d->dx, EpiPcgQ{d->dx, d->sigma_f, d->pc_Kp}, false);
-        launch_spmv(d, d->At, d->tmp_m, EpiResid{d->rhs, d->pc_Kp, d->pc_r, d->ctrl, N_B}, true);
-        rc = read_ctrl(d); if (rc) return rc;
-        if (d->hctrl->cnt[C_CHAIN_ERR]) return set_err(hipErrorUnknown, "dense factor bench: a polling kernel lost its producer", __LINE__);
-        *check = nrm_of(d->hctrl, N_B) / nrm_of(d->hctrl, N_A);
-        d->dense_valid = 0;
-    }
-    return 0;
-}
-// ---- the direct solvers as single linear solves (tests: tests/test_gpu_direct_solvers.py) ---------------------------------------
-// K x = rhs with K = Q + sigma I + A' diag(dw) A, through the workspace's direct solver as a Newton pass drives it: dense_factor /
-// wb_extend / dense_solve (linsolve 1) or band_factor / band_solve (3), no other kernels.  flags bit 0: refactor; clear: a kept factor of
-// this sigma is reused -- with the low-rank update for the rows whose weight moved since it when wb_enable is set (more than WB_MAX of
-// them refactor), as it is (the caller passes the factored weights) otherwise; with ud_cap set, up to that many changed rows change the
-// kept factor in place (ud_apply) and more of them take the low-rank path or, without it, refactor.  Bit 1: the factorization launch carries the forward
-// solve (dense_factor(d, true)).  The workspace's weights, sigma_f and dx are put back afterwards; the kept factor stays for the next
-// call and is dropped by the next qdev_begin_solve.  A lost producer of a polling kernel, or a bad band pivot, returns
-// QDEV_DIRECT_LOST with the latch cleared -- never a silent redo.
-int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *rhs, double *x, int flags) {
-    HIPCHK(hipSetDevice(d->device));
-    if (d->comm.active) return set_err(hipErrorInvalidValue, "direct solve: not for row-partitioned workspaces", __LINE__);
-    if (d->linsolve != 1 && d->linsolve != 3) return set_err(hipErrorInvalidValue, "direct solve: the workspace's solver is not a direct one (dense or band)", __LINE__);
-    const int n = d->n, m = d->m;
-    std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1));
-    if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
-    if (n) HIPCHK(hipMemcpyAsync(dx_keep.data(), d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
-    if (m) HIPCHK(hipMemcpyAsync(d->d, dw, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
-    if (n) HIPCHK(hipMemcpyAsync(d->rhs, rhs, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    const double sigma_keep = d->sigma_f;
-    d->sigma_f = sigma;
-    d->direct_hook_used = 1;
-    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-    if (d->ud_cap) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_UD_REJECT, 0);      // (a latch left by a call that ended early is not this call's)
-    const bool refactor = (flags & 1) != 0, carry = (flags & 2) != 0;
-    int rc = 0;
-    if (d->linsolve == 3) {
-        if (refactor || !d->dense_valid) rc = band_factor(d);
-        if (!rc) rc = band_solve(d);
-    } else {
-        bool full = refactor || !d->dense_factored || d->sigma_f != d->dense_fact_sigma;
-        int updated = 0;
-        if (!full && d->ud_cap > 0 && d->wb_k == 0) rc = ud_apply(d, &updated);
-        if (!rc && !full && !updated && d->ud_cap > 0 && !d->wb_enable) full = true;      // more changed rows than the cap: refactor
-        if (!rc && !full && !updated && d->wb_enable) {
-            int overflow = 0;
-            rc = wb_extend(d, &overflow);
-            if (!rc && overflow) full = true;
-        }
-        if (!rc && full) rc = dense_factor(d, carry);
-        if (!rc) rc = dense_solve(d);
-    }
-    if (!rc && n) HIPCHK(hipMemcpyAsync(x, d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
-    if (!rc) rc = read_ctrl(d);
-    bool lost = false;
-    if (!rc && d->hctrl->cnt[C_CHAIN_ERR]) {
-        lost = true;
-        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0;
-    }
-    d->sigma_f = sigma_keep;
-    if (m) HIPCHK(hipMemcpyAsync(d->d, d_keep.data(), (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
-    if (n) HIPCHK(hipMemcpyAsync(d->dx, dx_keep.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    if (rc) return rc;
-    if (lost) {
-        snprintf(g_err, sizeof(g_err), "direct solve: %s", d->linsolve == 3 ? "the band factorization met a pivot that is not a positive finite number"
-                                                                            : "a polling kernel lost its producer");
-        return QDEV_DIRECT_LOST;
-    }
-    return 0;
-}
-// the factor arrays of the last factorization (layouts: include/qpdo_amd_ext.h, qpdo_amd_download_factor)
-int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
-    HIPCHK(hipSetDevice(d->device));
-    const size_t ld = (size_t)d->dense_ld, nb = (size_t)d->dense_nblk, band = (size_t)d->band_np * (size_t)(d->band_b + 1);
-    if (which == 6) {
-        if (count < 4) return set_err(hipErrorInvalidValue, "download factor: the geometry needs 4 entries", __LINE__);
-        dst[0] = d->Kd ? (double)ld : 0.0; dst[1] = d->Kd ? (double)nb : 0.0; dst[2] = (d->Kb || d->bw_Wb) ? (double)d->band_np : 0.0; dst[3] = (d->Kb || d->bw_Wb) ? (double)d->band_b : 0.0;
-        return 0;
-    }
-    const double *src = nullptr; size_t len = 0;
-    if ((which == 4 || which == 5) && d->bw_Wb) return set_err(hipErrorInvalidValue, "download factor: a band wider than 127 is held as tiles (arrays 7 and 8)", __LINE__);
-    switch (which) {
-        case 0: src = d->Kd; len = ld * ld; break;
-        case 1: src = d->Dg; len = ld; break;
-        case 2: src = d->Linv; len = nb * DNB * DNB; break;
-        case 3: src = d->LinvT; len = nb * DNB * DNB; break;
-        case 4: src = d->Kb; len = band; break;
-        case 5: src = d->Lt; len = band; break;
-        case 7: src = d->bw_Wb; len = (size_t)(d->band_np / DNB) * (size_t)(d->bw_w + 1) * BW_T; break;
-        case 8: src = d->bw_Wd; len = (size_t)d->band_np; break;
-        default: return set_err(hipErrorInvalidValue, "download factor: unknown array", __LINE__);
-    }
-    if (!src) return set_err(hipErrorInvalidValue, "download factor: this workspace has not factored with that solver", __LINE__);
-    if (count < 0 || (size_t)count != len) return set_err(hipErrorInvalidValue, "download factor: count is not the array's length", __LINE__);
-    HIPCHK(hipMemcpyAsync(dst, src, len * 8, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return 0;
-}
-int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host) {
-    HIPCHK(hipSetDevice(d->device));
-    DevCsr *M = mat_by_id(d, which);
-    double *xin = (M->ncols == d->n) ? d->pc_p : d->pc_t;
-    double *yout = (M->nrows == d->n) ? d->pc_Kp : d->tmp_m;
-    if (M->ncols) HIPCHK(hipMemcpyAsync(xin, v_host, (size_t)M->ncols * 8, hipMemcpyHostToDevice, d->stream));
-    launch_spmv(d, *M, xin, EpiStore{yout}, false);
-    if (M->nrows) HIPCHK(hipMemcpyAsync(y_host, yout, (size_t)M->nrows * 8, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return 0;
-}
-int qdev_linesearch(QpdoDev *d, double eta, double beta, const double *delta, const double *alpha, double *tau) {
-    HIPCHK(hipSetDevice(d->device));
-    const int M2 = 2 * d->m;
-    if (M2 == 0) { *tau = -beta / eta; return 0; }
-    HIPCHK(hipMemcpyAsync(d->ls_delta, delta, (size_t)M2 * 8, hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->ls_alpha, alpha, (size_t)M2 * 8, hipMemcpyHostToDevice, d->stream));
-    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_NL, 0);
-    const int g = vgrid(M2);
-    LAUNCH(k_ls_prep_raw, g, M2, d->ls_delta, d->ls_alpha, d->ls_key[0], d->ls_idx[0], d->part + P_A0 * PGRID, d->part + P_B0 * PGRID, d->ctrl);
-    // eta, beta enter through the partial slots so that k_ls_scan2 forms a0, b0 exactly as in a Newton step:
-    // eta = 0.5*(eta_m + dxQdx) with eta_m = 2*eta, dxQdx = 0
-    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_ETA_M * PGRID, 2.0 * eta);
-    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_BETA_M * PGRID, 2.0 * beta);
-    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_DXQDX * PGRID, 0.0);
-    hipLaunchKernelGGL(k_set_partial, dim3(1), dim3(1), 0, d->stream, d->part + P_DXDF * PGRID, 0.0);
-    // pm applies to ETA/BETA (1 value) and A0/B0 (g values): run scan2 with pm = g after zero-padding ETA/BETA slots
-    if (g > 1) {
-        HIPCHK(hipMemsetAsync(d->part + P_ETA_M * PGRID + 1, 0, (size_t)(g - 1) * 8, d->stream));
-        HIPCHK(hipMemsetAsync(d->part + P_BETA_M * PGRID + 1, 0, (size_t)(g - 1) * 8, d->stream));
-    }
-    int rc = linesearch_device(d, g, 1); if (rc) return rc;
-    rc = read_ctrl(d); if (rc) return rc;
-    *tau = d->hctrl->val[V_TAU];
-    return 0;
-}
-
-
-// ---- the workspace's device arrays, for the fused one-workgroup kernel (qpdo_small.hip: qdev_small_resident_*) ------------------------
-int qdev_small_view(QpdoDev *d, QdevSmallView *v) {
-    if (d->comm.active) return set_err(hipErrorInvalidValue, "qdev_small_view: row-partitioned workspace", __LINE__);
-    memset(v, 0, sizeof(*v));
-    v->device = d->device; v->stream = (void *)d->stream; v->n = d->n; v->m = d->m;
-    v->Arp = d->Ar.rp; v->Aci = d->Ar.ci; v->Aval = d->Ar.val;
-    v->Trp = d->At.rp; v->Tci = d->At.ci; v->Tval = d->At.val;
-    v->Qrp = d->Qf.rp; v->Qci = d->Qf.ci; v->Qval = d->Qf.val;
-    v->q = d->q; v->l = d->l; v->u = d->u;
-    v->scaled = d->scaled; v->D = d->D; v->Dinv = d->Dinv; v->E = d->E; v->Einv = d->Einv; v->c = d->sc_c; v->cinv = d->sc_cinv;
-    v->st_x = d->x; v->st_xbar = d->xbar; v->st_Qx = d->Qx; v->st_Aty = d->Aty;
-    v->st_y = d->y; v->st_ybar = d->ybar; v->st_Ax = d->Ax; v->st_mu = d->mu; v->st_isq = d->isq;
     return 0;
 }

@@ -4,7 +4,7 @@
 // ------------------------------------------------------------------------------------------------
 enum { N_PRIM = 0, N_DUAL, N_PRIM_IN, N_DUAL_IN, N_A, N_B, N_C, N_D, N_COUNT };
 enum { C_ACTIVE = 0, C_ENTER, C_LEAVE, C_NL, C_KSTAR, C_MUCH, C_VIOL, C_PCG_DONE, C_PCG_IT, C_CHAIN_ERR, C_DINF,
-       C_SPEC_SKIP, C_SPEC_BRANCH,            // launch-ahead of the Newton step (k_resid_mn decides, host_step.inc spec_enqueue_step): nonzero = the guarded kernels leave at once; the factor branch
+       C_SPEC_SKIP, C_SPEC_BRANCH,            // launch-ahead of the Newton step (k_resid_mn decides, host_step.inc ahead_enqueue_step): nonzero = the guarded kernels leave at once; the factor branch
        C_UD_REJECT,                           // up/downdate of the kept dense factor (dev/updown.inc): a scan met a pivot that is not a positive finite number
        C_COUNT = 16 };
 enum { V_TAU = 0, V_A0, V_B0, V_RZ, V_BNORM, V_OOB, V_QDX, V_OBJ, V_F, V_RR, V_RNORM, V_RINF = 15, V_COUNT = 16 };

@@ -66,5 +66,6 @@ extern "C" {
 #include "dev/host_dense.inc"
 #include "dev/host_band.inc"
 #include "dev/host_step.inc"
+#include "dev/host_probe.inc"
 #include "dev/host_update.inc"
 }  // extern "C"

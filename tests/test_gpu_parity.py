@@ -363,8 +363,9 @@ def test_control_block_read_back_by_publication_is_the_copy_path_bit_for_bit(gpu
 def test_newton_step_launched_ahead_of_the_host_decision_changes_no_bit(gpu_required, monkeypatch):
     """Mid-size dense route: the Newton step of a pass is enqueued behind the residual launch, which forms the host's decision (end of the
     solve / outer update / factorization branch: qpdo.c:343-449, newton.c:21-33) on the device; the step's kernels leave at once when the
-    answer is no (dev/host_step.inc ahead_enqueue_step, QPDO_LAUNCH_AHEAD=0: the host decides first).  The kernels and their order are the
-    same, so every count, every per-pass record and every bit of the iterates must be: cold solves with and without Ruiz scaling, without
+    answer is no (dev/host_step.inc ahead_enqueue_step, QPDO_LAUNCH_AHEAD=0: the host decides first).  Both routes go through the same
+    launch sites (dev/host_dense.inc launch_dense_assemble / launch_mid_factor / launch_ldl_chain, dev/host_step.inc launch_adx_qdx_pair /
+    launch_ls_small); the kernels and their order are the same, so every count, every per-pass record and every bit of the iterates must be: cold solves with and without Ruiz scaling, without
     the proximal term, with inner_max_iter forcing outer updates, a primal-infeasible instance (the solve ends in an outer update), and a
     warm start / update sequence on one workspace.  The statistics must show that the steps did go ahead."""
     def rec(t):
