@@ -62,6 +62,18 @@ __device__ __forceinline__ void block_sum4(double &a, double &b, double &c, doub
     for (int i = 1; i < nw; i++) { ta += sm[i]; tb += sm[nw + i]; tc += sm[2 * nw + i]; te += sm[3 * nw + i]; }
     a = ta; b = tb; c = tc; e = te;
 }
+// block_sum4 of a 256-thread block, computed by the first 256 threads of a block of 256 or more (the others pass zeros and get the
+// sums too): the same wave sums, the same four LDS slots per value, the same order of additions.  sm: >= 16 doubles.
+__device__ __forceinline__ void block_sum4_256(double &a, double &b, double &c, double &e, double *sm) {
+    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); e = wave_sum(e);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    __syncthreads();
+    if (l == 0 && w < 4) { sm[w] = a; sm[4 + w] = b; sm[8 + w] = c; sm[12 + w] = e; }
+    __syncthreads();
+    double ta = sm[0], tb = sm[4], tc = sm[8], te = sm[12];
+    for (int i = 1; i < 4; i++) { ta += sm[i]; tb += sm[4 + i]; tc += sm[8 + i]; te += sm[12 + i]; }
+    a = ta; b = tb; c = tc; e = te;
+}
 __device__ __forceinline__ int block_sum_int(int v, int *sm) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -98,6 +98,7 @@ static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, 
 }
 static int setup_slabs(QpdoDev *d, DevCsr *M) {
     { const char *ov = getenv("QPDO_SLAB_OVERLAP"); M->slab_ovl = !(ov && *ov && atoi(ov) == 0); }
+    { const char *nt = getenv("QPDO_SLAB_NT"); M->slab_nt = (nt && atoi(nt) != 0) ? 1 : 0; }
     const char *force = getenv("QPDO_SPMV");            // "slab" | "plain" | unset (auto)
     const double bytes = 12.0 * (double)M->nnz;
     bool want = bytes >= 192.0 * 1024 * 1024 && M->nrows >= 4096;   // beyond what L2 + Infinity Cache keep resident

@@ -16,7 +16,7 @@ static int build_compact(QpdoDev *d) {
     LAUNCH(k_gather_rowinfo, vgrid(k), k, (const int *)d->rowlist, d->Ar.rp, dl, d->row_cnt, d->dc);
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, k, d->Arc.rp);
     DevCsr &R = d->Arc;
-    R.nrows = k; R.ncols = n; R.tpr = d->Ar.tpr; R.use_slab = d->Ar.use_slab && k >= 4096; R.slab_ovl = d->Ar.slab_ovl;
+    R.nrows = k; R.ncols = n; R.tpr = d->Ar.tpr; R.use_slab = d->Ar.use_slab && k >= 4096; R.slab_ovl = d->Ar.slab_ovl; R.slab_nt = d->Ar.slab_nt;
     int RW16 = 0;
     if (R.use_slab) {
         R.rows_per_wg = (k + 255) / 256; R.slab_grid = (k + R.rows_per_wg - 1) / R.rows_per_wg;
@@ -36,7 +36,7 @@ static int build_compact(QpdoDev *d) {
     // A_c': columns, renumbered
     DevCsr &T = d->Atc;
     const DevCsr &M = d->At;
-    T.nrows = n; T.ncols = k; T.tpr = M.tpr; T.use_slab = M.use_slab && k >= 1024; T.slab_ovl = M.slab_ovl;
+    T.nrows = n; T.ncols = k; T.tpr = M.tpr; T.use_slab = M.use_slab && k >= 1024; T.slab_ovl = M.slab_ovl; T.slab_nt = M.slab_nt;
     int W16 = 0;
     if (T.use_slab) {
         T.rows_per_wg = M.rows_per_wg; T.slab_grid = M.slab_grid;
@@ -190,12 +190,15 @@ static const int PCG_NAN = -8;                  // a NaN residual: a numerical f
 //
 // One application  w = S' u = u ./ d + A_c ((A_c' u) ./ Dq):  t in d->tmp_n, the partial sums of (A_c' u).t in Pf (fcnt of them).
 // par: parity of the local partial sums (in P3) that accompany this application.
+static bool schur_inner_f32(const QpdoDev *d) {
+    return d->inner_f32 && d->Atc.use_slab && d->Arc.use_slab && d->Atc.vsm32 && d->Arc.vsm32 && d->Atc.i16sm && d->Arc.i16sm;
+}
 static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const int *done2, bool sample, int *fcnt) {
     const bool dist = d->comm.active;
     const int n = d->n, kl = d->kact;
     double *Pf = d->part2 + 6 * PGRID;
     if (!dist) {
-        const bool f32 = d->inner_f32 && d->Atc.use_slab && d->Arc.use_slab && d->Atc.vsm32 && d->Arc.vsm32 && d->Atc.i16sm && d->Arc.i16sm;
+        const bool f32 = schur_inner_f32(d);
         if (f32) launch_spmv_slab32(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, done2);
         else launch_spmv(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, true, done2);
         // HIP-event sample of the dominant kernel (the A_c product), taken mid-batch by the caller's choice of `sample`
@@ -226,8 +229,16 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
     const int *done2 = &d->ctrl2->cnt[C_PCG_DONE];
     const double *glob3 = dist ? d->dist_tmp + d->n : (const double *)nullptr;
     int fcnt = 0;
+    // Folded schedule (single GPU, fp64 inner matrices, one element per thread of k_cgcg_step's grid): two launches per iteration.
+    // Product 2 of application j - 1 performs step j (EpiSchurStep), product 1 of application j forms that step's three partial
+    // sums first (EpiDivDotSums).  The bits are those of the three-launch schedule below, which QPDO_INNER_FOLD=0 selects.
+    const bool fold = d->inner_fold && !dist && !schur_inner_f32(d) && (long long)g * BLK >= kl;
     LAUNCH(k_cgcg_init, g, kl, (const double *)d->s_v, (const double *)d->s_diag, (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, P3, d->ctrl2);
-    int rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt); if (rc) return -1;
+    int rc = 0;
+    if (fold) {
+        launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, 0, d->s_r, d->s_z, d->dc, (double *)nullptr}, true, done2);
+        fcnt = spmv_pgrid(d->Atc);
+    } else { rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt); if (rc) return -1; }
     d->st.inner_solves++;
     int j = 0;
     // Batches between host syncs.  The iteration count of an inner solve is almost the same as that of the previous one
@@ -237,7 +248,15 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
     int batch = d->schur_last_inner > 12 ? d->schur_last_inner - 6 : d->pcg_batch;
     while (j < SCHUR_INNER_MAXIT) {
         const int it_before = j, sample_b = batch / 2;
-        for (int b = 0; b < batch; b++, j++) {
+        if (fold) for (int b = 0; b < batch; b++, j++) {
+            // (the HIP-event sample of the A_c product now includes the step it performs; its byte count is that of the product)
+            if (b == sample_b) (void)hipEventRecord(d->ev0, d->stream);
+            launch_spmv(d, d->Arc, d->tmp_n, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol}, false);
+            if (b == sample_b) (void)hipEventRecord(d->ev1, d->stream);
+            launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3}, true, done2);
+            d->st.inner_steps++;
+        }
+        else for (int b = 0; b < batch; b++, j++) {
             LAUNCH(k_cgcg_step, g, kl, j, d->ctrl2, glob3, P3, g, (const double *)Pf, fcnt, (const double *)d->s_Sp, (const double *)d->s_diag,
                    (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol);
             rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, !dist && b == sample_b, &fcnt); if (rc) return -1;

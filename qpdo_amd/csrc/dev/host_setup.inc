@@ -169,6 +169,7 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         d->Arc.vsm = nullptr; d->Arc.i16sm = nullptr; d->Arc.cism = nullptr; d->Arc.seg = nullptr; d->Arc.vsm32 = nullptr;
         d->Atc.vsm = nullptr; d->Atc.i16sm = nullptr; d->Atc.cism = nullptr; d->Atc.seg = nullptr; d->Atc.vsm32 = nullptr;
         { const char *f32 = getenv("QPDO_PCG_INNER_F32"); d->inner_f32 = (f32 && atoi(f32) != 0) ? 1 : 0; }
+        { const char *fo = getenv("QPDO_INNER_FOLD"); d->inner_fold = !(fo && *fo && atoi(fo) == 0); }
         rc = dev_alloc(d, &d->Arc.rp, (size_t)m + 1);
         if (!rc) rc = dev_alloc(d, &d->Arc.ci, (size_t)d->Ar.nnz);
         if (!rc) rc = dev_alloc(d, &d->Arc.val, (size_t)d->Ar.nnz);

@@ -212,6 +212,89 @@ __global__ __launch_bounds__(256) void k_cgcg_step(int k, int j, Ctrl *ctrl, con
     }
 }
 
+// The inner CG's vector step folded into its two products (QPDO_INNER_FOLD=0: k_cgcg_step between them, as before; same bits).
+// Product 1 of application j: before its own rows, workgroup b forms the partial sums of the step that the previous launch performed --
+// sum r.u, sum r.r, sum u^2/d over the 256-element blocks b, b + gridDim, ... of the k-vectors, with the per-element expressions and the
+// block_sum4 tree of k_cgcg_step -- into P3[.][np][block] (P3 == nullptr: the application after k_cgcg_init, whose slot 0 is filled).
+struct EpiDivDotSums {
+    const double *w; double *out, *p_f;
+    int k, np; const double *r, *u, *dc; double *P3;
+    double acc = 0.0;
+    __device__ bool skip(int) const { return false; }
+    __device__ bool prologue(double *sm) {
+        if (!P3) return true;
+        const int nblk = (k + 255) >> 8;
+        for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+            const int i = blk * 256 + (int)threadIdx.x;
+            double a = 0.0, c = 0.0, e2 = 0.0, zero = 0.0;
+            if (threadIdx.x < 256 && i < k) { const double ri = r[i], un = u[i]; a = ri * un; c = ri * ri; e2 = un * un / dc[i]; }
+            block_sum4_256(a, c, e2, zero, sm);
+            if (threadIdx.x == 0) { P3[(0 * 2 + np) * PGRID + blk] = a; P3[(1 * 2 + np) * PGRID + blk] = c; P3[(2 * 2 + np) * PGRID + blk] = e2; }
+        }
+        return true;
+    }
+    __device__ void row(int r_, double s) { const double t = s / w[r_]; out[r_] = t; acc += s * t; }
+    __device__ void finish(double *sm) {
+        double t = block_sum(acc, sm);
+        if (threadIdx.x == 0) p_f[blockIdx.x] = t;
+    }
+};
+// Product 2 of application j - 1 performs step j: at its top every workgroup re-reduces the partial sums P3[.][par][0..pcnt) and
+// Pf[0..fcnt) in the order of k_cgcg_step (its first 256 threads are one block of that kernel), derives rn, the convergence test,
+// beta and alpha with that kernel's expressions, and leaves alpha and beta in LDS; then, per owned row, w_i = u_i / d_i + (A_c t)_i
+// as EpiSchurW and the five updates and u_i = r_i / diag_i in k_cgcg_step's order.  w never goes to memory; u is read by this launch
+// for the workgroup's own rows only (its x is t), so it is written in place.  Converged or NaN: every workgroup leaves (the decision
+// is the same in all of them), workgroup 0 sets the latch to j + 1.  Only a latch set by an EARLIER launch ends this one at its top,
+// so the kernel's own `done` argument is nullptr for this functor.
+struct EpiSchurStep {
+    int j; Ctrl *ctrl; const double *P3; int pcnt; const double *Pf; int fcnt;
+    const double *dg, *dc; double *x, *r, *u, *p, *s; double tol;
+    const double *ab = nullptr;                 // alpha, beta in LDS
+    __device__ bool skip(int) const { return false; }
+    __device__ bool prologue(double *sm) {
+        { const int dn = ctrl->cnt[C_PCG_DONE]; if (dn && dn <= j) return false; }
+        const int par = j & 1;
+        double gam = 0.0, rr = 0.0, e = 0.0, f = 0.0;
+        if (threadIdx.x < 256) {
+            for (int q = threadIdx.x; q < pcnt; q += 256) { gam += P3[(0 * 2 + par) * PGRID + q]; rr += P3[(1 * 2 + par) * PGRID + q]; e += P3[(2 * 2 + par) * PGRID + q]; }
+            for (int q = threadIdx.x; q < fcnt; q += 256) f += Pf[q];
+        }
+        block_sum4_256(gam, rr, e, f, sm);
+        const double delta = e + f;
+        const double rn = sqrt(rr);
+        const double bnorm = (j == 0) ? rn : ctrl->val[V_BNORM];
+        const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+        if (rn <= tol * bnorm || !(rr == rr)) {
+            if (first) { ctrl->cnt[C_PCG_DONE] = j + 1; ctrl->val[V_RNORM] = rn; if (j == 0) ctrl->val[V_BNORM] = bnorm; }
+            return false;
+        }
+        const double beta = (j == 0) ? 0.0 : gam / ctrl->val[VS_GAM + par];
+        const double alpha = (j == 0) ? gam / delta : gam / (delta - beta * gam / ctrl->val[VS_ALP + par]);
+        if (threadIdx.x == 0) { sm[16] = alpha; sm[17] = beta; }
+        if (first) {
+            const int np = par ^ 1;
+            ctrl->val[VS_GAM + np] = gam; ctrl->val[VS_ALP + np] = alpha;
+            ctrl->cnt[C_PCG_IT] += 1; ctrl->val[V_RNORM] = rn;
+            if (j == 0) ctrl->val[V_BNORM] = bnorm;
+        }
+        ab = sm + 16;
+        __syncthreads();
+        return true;
+    }
+    __device__ void row(int i, double acc) {
+        const double alpha = ab[0], beta = ab[1];
+        const double ui = u[i];
+        const double wi = ui / dc[i] + acc;
+        const double pi = ui + beta * p[i], si = wi + beta * s[i];
+        p[i] = pi; s[i] = si;
+        x[i] = x[i] + alpha * pi;
+        const double ri = r[i] - alpha * si;
+        r[i] = ri;
+        u[i] = ri / dg[i];
+    }
+    __device__ void finish(double *) {}
+};
+
 // ------------------------------------------------------------------------------------------------
 // Heavy-row deflation of the Jacobi preconditioner.  After a penalty update a handful of rows carry
 // weights d_i 1e4..1e6 times the median; they add isolated huge eigenvalues that cost Jacobi-PCG

@@ -40,12 +40,19 @@ __device__ __forceinline__ void spmv_rows(int bid, int nblk, Tpr tpr, int nrows,
         if (lane == 0) epi.row(row, s);
     }
 }
+// Optional hook of an epilogue functor: bool prologue(double *sm), called by every thread at the top of the product kernels (k_spmv,
+// k_spmv_slab) with the kernel's 32 doubles of LDS; false (uniform over the launch's running workgroups) ends the workgroup.
+template <class Epi>
+__device__ __forceinline__ auto epi_prologue(Epi &epi, double *sm, int) -> decltype(epi.prologue(sm)) { return epi.prologue(sm); }
+template <class Epi>
+__device__ __forceinline__ bool epi_prologue(Epi &, double *, long) { return true; }
 // done: the PCG's latch (every thread leaves at once when the solver has converged), or nullptr
 template <int TPR, class Epi>
 __global__ __launch_bounds__(256) void k_spmv(const int *__restrict__ done, int nrows, const int *__restrict__ rp, const int *__restrict__ ci,
                                               const double *__restrict__ val, const double *__restrict__ x, Epi epi) {
     __shared__ double sm[32];
     if (done && *done) return;
+    if (!epi_prologue(epi, sm, 0)) return;
     spmv_rows(blockIdx.x, gridDim.x, std::integral_constant<int, TPR>(), nrows, rp, ci, val, x, epi);
     epi.finish(sm);
 }
@@ -71,7 +78,14 @@ static constexpr int SLAB_TPR = 16;     // lanes per row segment (16 x 16-byte l
 // The x slice is copied with 16-byte global_load_lds (dst = wave base + 16 * lane), so the copy costs one L2 round trip, not one
 // per 16 KB.  (Lab, tools/lab/slab_lab.hip LAB_OVL=1, round 6: the early loads alone do not pay at the compact shapes -- the
 // register copy waits for them in order; with the async copy: -4 % at k = 66 000, -3.5 % at 73 000, -1 % on the full matrix.)
-template <class Epi, bool I16, bool OVL>
+// NT (opt-in, QPDO_SLAB_NT=1): the values are read once per launch, so their 16-byte loads are non-temporal -- 8 of the 10 streamed
+// bytes per nonzero no longer push the x vector and the seg table, which every workgroup re-reads, out of L2.  The index words, x
+// staging, seg, acc and the epilogue's vectors keep the default policy.  (Lab, tools/lab/slab_lab.hip LAB_NT=1, round 7: values
+// alone -6 % per launch at the compact shapes, non-temporal index words +10 %, alone or together with the values.  The C4 solve does
+// not show the lab's gain -- back-to-back launches re-read nothing of the matrix from L2 either way -- and is 0.5 % slower with it:
+// off by default, docs/LAB_NOTES.md R7.)
+typedef double slab_d2 __attribute__((ext_vector_type(2)));
+template <class Epi, bool I16, bool OVL, bool NT>
 __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                     int rows_per_wg, const int2 *__restrict__ seg, const int *__restrict__ cism,
                                                     const unsigned short *__restrict__ i16sm,
@@ -103,7 +117,10 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
         for (int u = 0; u < SLAB_UNR; u++) {
             const int kk = k + u * 2 * TPR;
             const int kc = kk < end ? kk : kb;
-            v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
+            if constexpr (NT) {
+                const slab_d2 t = __builtin_nontemporal_load(reinterpret_cast<const slab_d2 *>(vsm + kc));
+                v[u] = make_double2(t.x, t.y);
+            } else v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
             if constexpr (I16) w[u] = *reinterpret_cast<const unsigned *>(i16sm + kc);
             else               w[u] = *reinterpret_cast<const int2 *>(cism + kc);
         }
@@ -160,6 +177,8 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
         }
     };
     if (OVL) prefetch(0);
+    // (behind the first matrix loads: the hook's few KB from L2 and its barriers run while those are in flight)
+    if (!epi_prologue(epi, sm, 0)) return;
     for (int s = 0; s < nslabs; s++) {
         const int c0 = s * W;
         const int cw = min(W, ncols - c0);
@@ -534,9 +553,11 @@ static void launch_slab(QpdoDev *d, const DevCsr &M, Args... args) {
 }
 template <class Epi>
 static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done) {
-#define SLAB_GO(I16, OVL) launch_slab<k_spmv_slab<Epi, I16, OVL>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, M.vsm, x, epi)
-    if (M.slab_ovl) { if (M.i16sm) SLAB_GO(true, true); else SLAB_GO(false, true); }
-    else            { if (M.i16sm) SLAB_GO(true, false); else SLAB_GO(false, false); }
+#define SLAB_GO(I16, OVL, NT) launch_slab<k_spmv_slab<Epi, I16, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, M.vsm, x, epi)
+#define SLAB_GO_NT(I16, OVL) do { if (M.slab_nt) SLAB_GO(I16, OVL, true); else SLAB_GO(I16, OVL, false); } while (0)
+    if (M.slab_ovl) { if (M.i16sm) SLAB_GO_NT(true, true); else SLAB_GO_NT(false, true); }
+    else            { if (M.i16sm) SLAB_GO_NT(true, false); else SLAB_GO_NT(false, false); }
+#undef SLAB_GO_NT
 #undef SLAB_GO
 }
 template <class Epi>

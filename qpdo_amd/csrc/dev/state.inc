@@ -27,6 +27,7 @@ struct DevCsr {
     // position inside row r where slab s starts (rows are column-sorted, so a slab is a sub-range)
     int use_slab = 0, nslabs = 0, W = 0, rows_per_wg = 0, slab_grid = 0;
     int slab_ovl = 1;        // k_spmv_slab issues the next slab's first loads before its barriers (QPDO_SLAB_OVERLAP=0: the old schedule)
+    int slab_nt = 0;         // QPDO_SLAB_NT=1: k_spmv_slab reads the values with non-temporal loads (off: faster per launch in the lab, not in the C4 solve)
     int *sp = nullptr;
     unsigned short *ci16 = nullptr;   // column index inside its slab (W < 65536): 10 instead of 12 bytes per nonzero
     // Slab-major image, the arrays the slab kernel actually streams: per workgroup the row segments of slab 0 back to
@@ -139,7 +140,7 @@ struct QpdoDev {
     Ctrl *ctrl2 = nullptr, *hctrl2 = nullptr; double *part2 = nullptr;
     double *s_x = nullptr, *s_r = nullptr, *s_z = nullptr, *s_p = nullptr, *s_Sp = nullptr, *s_diag = nullptr, *s_v = nullptr, *s_s = nullptr;
     int kg = 0;                                                           // row-partitioned Schur mode: global number of weighted rows (k-vectors stay partitioned)
-    int inner_f32 = 0; int schur_mode = -1 /* -1 auto, 0 off, 1 on */, schur_off = 0, schur_strikes = 0, last_jacobi_iters = 0, schur_last_inner = 0; long long schur_passes = 0;
+    int inner_f32 = 0; int inner_fold = 1 /* the inner CG's vector step inside its two products (QPDO_INNER_FOLD=0: k_cgcg_step) */; int schur_mode = -1 /* -1 auto, 0 off, 1 on */, schur_off = 0, schur_strikes = 0, last_jacobi_iters = 0, schur_last_inner = 0; long long schur_passes = 0;
     double *part = nullptr;  // P_COUNT * PGRID
     // scaling
     int scaled = 0; double sc_c = 1.0, sc_cinv = 1.0;

@@ -1,5 +1,6 @@
-"""A/B timing of two builds of libqpdo_amd.so on one box: the C4 cold-start solve, alternating processes.
-usage: ab_c4.py libA.so libB.so [reps]"""
+"""A/B timing of builds of libqpdo_amd.so on one box: the C4 cold-start solve, alternating processes.
+usage: ab_c4.py libA.so libB.so [more sides ...] [reps]
+A side is a library, or VAR=VALUE,VAR=VALUE@library: that build with those environment switches (e.g. QPDO_INNER_FOLD=0@libqpdo_amd.so)."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r"""
@@ -14,11 +15,13 @@ for _ in range(2):
     out.append(dict(t=dt, it=r["info"]["iterations"], st=r["info"]["status_val"], cg=s.stats()["lin_iters"]))
 print(json.dumps(out))
 """ % ROOT
-libs = sys.argv[1:3]
-reps = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+args = sys.argv[1:]
+reps = int(args.pop()) if args and args[-1].isdigit() else 2
 for rep in range(reps):
-    for lib in libs:
+    for side in args:
+        switches, _, lib = side.rpartition("@")
         env = dict(os.environ, QPDO_AMD_LIB=os.path.abspath(lib))
+        env.update(kv.split("=", 1) for kv in switches.split(",") if kv)
         o = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True)
         line = [l for l in o.stdout.splitlines() if l.startswith("[")]
-        print(os.path.basename(lib), line[-1] if line else o.stderr[-500:], flush=True)
+        print((switches + " " if switches else "") + os.path.basename(lib), line[-1] if line else o.stderr[-500:], flush=True)

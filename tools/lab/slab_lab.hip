@@ -195,7 +195,9 @@ __global__ __launch_bounds__(256) void k_slab_permute(int nrows, int nslabs, int
 // OVL (round 6): each lane group issues the loads of its first row segment of the next slab (group g -> row g, the LDS
 // counter then starts at NT/TPR) before the end-of-slab barrier, and of slab 0 before the first staging barrier.
 // OVL 2: the same, and the x slice is copied with 16-byte global_load_lds (no VGPRs, all of a lane's copies in flight at once)
-template <int TPR, int UNR, int NT = 1024, int OVL = 0>
+// NTL (round 7): non-temporal loads of the matrix stream -- 1: values and index words, 2: values only, 3: index words only
+typedef double lab_d2 __attribute__((ext_vector_type(2)));
+template <int TPR, int UNR, int NT = 1024, int OVL = 0, int NTL = 0>
 __global__ __launch_bounds__(NT) void k_slab_prod(int nrows, int ncols, int nslabs, int W, int rows_per_wg, const int2 *__restrict__ seg,
                                                     const unsigned short *__restrict__ i16sm, const double *__restrict__ vsm,
                                                     const double *__restrict__ x, double *__restrict__ y) {
@@ -212,8 +214,10 @@ __global__ __launch_bounds__(NT) void k_slab_prod(int nrows, int ncols, int nsla
 #pragma unroll
         for (int u = 0; u < UNR; u++) {
             const int kk = k + u * 2 * TPR; const int kc = kk < end ? kk : kb;
-            v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
-            w[u] = *reinterpret_cast<const unsigned *>(i16sm + kc);
+            if (NTL == 1 || NTL == 2) { const lab_d2 t = __builtin_nontemporal_load(reinterpret_cast<const lab_d2 *>(vsm + kc)); v[u] = make_double2(t.x, t.y); }
+            else v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
+            if (NTL == 1 || NTL == 3) w[u] = __builtin_nontemporal_load(reinterpret_cast<const unsigned *>(i16sm + kc));
+            else w[u] = *reinterpret_cast<const unsigned *>(i16sm + kc);
         }
     };
     double2 pv[UNR]; unsigned pw[UNR];                // written on every path of the prefetch: live only up to the first trip
@@ -508,7 +512,7 @@ static void run_prod_db(const char *name, int m, int n, int nwg, const unsigned 
     printf("%-44s wg %4d x 1024 thr, W %5d, %2d slabs: %.3f ms  algorithmic %.2f TB/s  checksum %.10e\n", name, grid, W, nslabs, ms, nnz * 12 / ms / 1e9, cs); fflush(stdout);
     CK(hipFree(sp)); CK(hipFree(seg)); CK(hipFree(i16)); CK(hipFree(i16sm)); CK(hipFree(vsm));
 }
-template <int TPR, int UNR, int NT, int OVL = 0>
+template <int TPR, int UNR, int NT, int OVL = 0, int NTL = 0>
 static void run_prod_wg(const char *name, int m, int n, int nwg, int budget_div, const int *sp0, int nslabs0, const unsigned short *ci16_rm, const int *ci_rm, const double *val_rm, const double *x, double *y, double nnz) {
     // rebuild slab tables for this (W, rows-per-wg): W from the LDS budget of one workgroup
     const int rpw = (m + nwg - 1) / nwg;
@@ -522,11 +526,11 @@ static void run_prod_wg(const char *name, int m, int n, int nwg, int budget_div,
     hipLaunchKernelGGL(k_slab_permute, dim3(2048), dim3(256), 0, 0, m, nslabs, W, (const int *)sp, (const int2 *)seg, (const unsigned short *)i16, val_rm, vsm, i16sm);
     CK(hipDeviceSynchronize());
     const int grid = (m + rpw - 1) / rpw; const size_t lds = (size_t)(W + rpw) * 8;
-    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slab_prod<TPR, UNR, NT, OVL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_slab_prod<TPR, UNR, NT, OVL, NTL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    for (int w = 0; w < 2; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT, OVL>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
+    for (int w = 0; w < 2; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT, OVL, NTL>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
     CK(hipEventRecord(e0, 0));
-    for (int w = 0; w < 10; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT, OVL>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
+    for (int w = 0; w < 10; w++) hipLaunchKernelGGL((k_slab_prod<TPR, UNR, NT, OVL, NTL>), dim3(grid), dim3(NT), lds, 0, m, n, nslabs, W, rpw, (const int2 *)seg, (const unsigned short *)i16sm, (const double *)vsm, x, y);
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= 10;
     { std::vector<double> h(m); CK(hipMemcpy(h.data(), y, (size_t)m * 8, hipMemcpyDeviceToHost)); double cs = 0.0; for (int i = 0; i < m; i++) cs += h[i] * ((i % 7) + 1);
@@ -763,6 +767,23 @@ int main() {
             run_prod_wg<16, 8, 1024>("full m production", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
             run_prod_wg<16, 8, 1024, 1>("full m overlap", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
             run_prod_wg<16, 8, 1024, 2>("full m overlap + glds copy", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
+            }
+            return 0;
+        }
+        if (getenv("LAB_NT")) {      // round 7: non-temporal loads of the matrix stream against production (overlap + glds copy), alternating
+            for (int rep = 0; rep < 3; rep++) {
+            run_prod_wg<16, 8, 1024, 2>("k=66000 production", 66000, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, 66000.0 * per_row);
+            run_prod_wg<16, 8, 1024, 2, 1>("k=66000 nt values + indices", 66000, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, 66000.0 * per_row);
+            run_prod_wg<16, 8, 1024, 2, 2>("k=66000 nt values", 66000, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, 66000.0 * per_row);
+            run_prod_wg<16, 8, 1024, 2, 3>("k=66000 nt indices", 66000, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, 66000.0 * per_row);
+            run_prod_wg<16, 8, 1024, 2>("k=73000 production", kk, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnzk);
+            run_prod_wg<16, 8, 1024, 2, 1>("k=73000 nt values + indices", kk, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnzk);
+            run_prod_wg<16, 8, 1024, 2, 2>("k=73000 nt values", kk, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnzk);
+            run_prod_wg<16, 8, 1024, 2, 3>("k=73000 nt indices", kk, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnzk);
+            run_prod_wg<16, 8, 1024, 2>("full m production", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
+            run_prod_wg<16, 8, 1024, 2, 1>("full m nt values + indices", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
+            run_prod_wg<16, 8, 1024, 2, 2>("full m nt values", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
+            run_prod_wg<16, 8, 1024, 2, 3>("full m nt indices", m, n, 256, 1, sp, nslabs, ci16, ci, val, x, y, nnz);
             }
             return 0;
         }
