@@ -36,6 +36,15 @@ __device__ __forceinline__ void block_max_to(double v, u64 *dst, double *sm) {
         if (t > 0.0) atomicMax(dst, (u64)__double_as_longlong(t));
     }
 }
+// max over the block of non-negative values; result valid in every thread.  sm: >= blockDim.x / 64 doubles that no thread still reads.
+__device__ __forceinline__ double block_max(double v, double *sm) {
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = sm[0];
+    for (int i = 1; i < (int)(blockDim.x >> 6); i++) t = sm[i] > t ? sm[i] : t;
+    return t;
+}
 // reference c_absval / '>' semantics: a NaN never replaces the running maximum (lin_alg.c:107-140)
 __device__ __forceinline__ double absmax_acc(double mx, double a) {
     double s = a < 0 ? -a : a;
@@ -51,19 +60,9 @@ __device__ __forceinline__ double reduce_partials(const double *p, int cnt, doub
     for (int i = threadIdx.x; i < cnt; i += blockDim.x) s += p[i];
     return block_sum(s, sm);
 }
-// four sums at once: one pair of barriers instead of four.  sm: >= 4 * (blockDim.x / 64) doubles.
-__device__ __forceinline__ void block_sum4(double &a, double &b, double &c, double &e, double *sm) {
-    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); e = wave_sum(e);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, nw = (int)(blockDim.x >> 6);
-    __syncthreads();
-    if (l == 0) { sm[w] = a; sm[nw + w] = b; sm[2 * nw + w] = c; sm[3 * nw + w] = e; }
-    __syncthreads();
-    double ta = sm[0], tb = sm[nw], tc = sm[2 * nw], te = sm[3 * nw];
-    for (int i = 1; i < nw; i++) { ta += sm[i]; tb += sm[nw + i]; tc += sm[2 * nw + i]; te += sm[3 * nw + i]; }
-    a = ta; b = tb; c = tc; e = te;
-}
-// block_sum4 of a 256-thread block, computed by the first 256 threads of a block of 256 or more (the others pass zeros and get the
-// sums too): the same wave sums, the same four LDS slots per value, the same order of additions.  sm: >= 16 doubles.
+// Four sums at once over the first 256 threads of a block of 256 or more (the others pass zeros and get the sums too): one pair of
+// barriers instead of four; per value the wave sums, four LDS slots and the order of additions of block_sum in a 256-thread block.
+// sm: >= 16 doubles.
 __device__ __forceinline__ void block_sum4_256(double &a, double &b, double &c, double &e, double *sm) {
     a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); e = wave_sum(e);
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;

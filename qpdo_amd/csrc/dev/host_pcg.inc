@@ -47,17 +47,11 @@ static int build_compact(QpdoDev *d) {
         T.nslabs = nslabs; T.W = W;
         if (T.ci16 && W < 65536) W16 = W;
     }
-    const int g = M.use_slab ? 2048 : spmv_grid(M, false);
+    const int g = rowloop_grid(M);
     const int words = (m + 63) / 64;
     const size_t lds_tab = (size_t)words * (sizeof(u64) + sizeof(int));
     if (lds_tab <= 60 * 1024) {          // flags and renumbering as LDS tables: the kernels stream the matrix only
-        switch (M.tpr) {
-            case 4:  hipLaunchKernelGGL((k_count_flagged_bits<4>),  dim3(g), dim3(BLK), (size_t)words * 8, d->stream, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt); break;
-            case 8:  hipLaunchKernelGGL((k_count_flagged_bits<8>),  dim3(g), dim3(BLK), (size_t)words * 8, d->stream, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt); break;
-            case 16: hipLaunchKernelGGL((k_count_flagged_bits<16>), dim3(g), dim3(BLK), (size_t)words * 8, d->stream, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt); break;
-            case 32: hipLaunchKernelGGL((k_count_flagged_bits<32>), dim3(g), dim3(BLK), (size_t)words * 8, d->stream, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt); break;
-            default: hipLaunchKernelGGL((k_count_flagged_bits<64>), dim3(g), dim3(BLK), (size_t)words * 8, d->stream, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt); break;
-        }
+        DISPATCH_TPR_LDS(M, k_count_flagged_bits, g, (size_t)words * 8, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt);
         hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, n, T.rp);
         hipLaunchKernelGGL(k_compact_rows_bits, dim3(2048), dim3(BLK), lds_tab, d->stream, n, M.rp, M.ci, M.val, (const u64 *)d->flag_bits,
                            (const int *)d->flag_wprefix, words, (const int *)T.rp, T.ci, T.val, W16, M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr);
@@ -67,7 +61,6 @@ static int build_compact(QpdoDev *d) {
         LAUNCH(k_compact_rows, 2048, n, M.rp, M.ci, M.val, dl, (const int *)T.rp, T.ci, T.val, (const int *)d->cidx, W16,
                M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr);
     }
-    DevCsr Tsave = T;     // (keep pointer to allocated ci16 even when this pass cannot use it)
     if (T.use_slab) LAUNCH(k_build_slab_ptr, vgrid(n), n, T.rp, T.ci, T.nslabs, T.W, T.sp, (int *)nullptr);
     int nn[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(&nn[0], d->Arc.rp + k, sizeof(int), hipMemcpyDeviceToHost, d->stream));
@@ -75,9 +68,33 @@ static int build_compact(QpdoDev *d) {
     HIPCHK(hipStreamSynchronize(d->stream));
     R.nnz = nn[0]; T.nnz = nn[1];
     R.sm_dirty = 1; T.sm_dirty = 1;
-    (void)Tsave;
     d->kact = k;
     return 0;
+}
+// Si = S^-1 of the symmetric positive definite leading r x r block of S (row stride N) by Cholesky on the host; L, Li: zeroed
+// workspace of the same shape.  false: S is not positive definite.
+static bool spd_inverse(int r, int N, const double *S, double *L, double *Li, double *Si) {
+    for (int i = 0; i < r; i++)                     // Cholesky S = L L'
+        for (int j = 0; j <= i; j++) {
+            double t = S[i * N + j];
+            for (int q = 0; q < j; q++) t -= L[i * N + q] * L[j * N + q];
+            if (i == j) { if (!(t > 0.0)) return false; L[i * N + i] = sqrt(t); }
+            else L[i * N + j] = t / L[j * N + j];
+        }
+    for (int c = 0; c < r; c++)                     // Li = L^-1 (lower)
+        for (int i = 0; i < r; i++) {
+            if (i < c) { Li[i * N + c] = 0.0; continue; }
+            double t = (i == c) ? 1.0 : 0.0;
+            for (int q = c; q < i; q++) t -= L[i * N + q] * Li[q * N + c];
+            Li[i * N + c] = t / L[i * N + i];
+        }
+    for (int i = 0; i < r; i++)                     // S^-1 = Li' Li
+        for (int j = 0; j <= i; j++) {
+            double t = 0.0;
+            for (int q = i; q < r; q++) t += Li[q * N + i] * Li[q * N + j];
+            Si[i * N + j] = t; Si[j * N + i] = t;
+        }
+    return true;
 }
 // choose the heavy rows of this pass (in the compact space) and build P, A_h', S^-1.  Sets d->defl_r.
 static int defl_build(QpdoDev *d) {
@@ -107,7 +124,7 @@ static int defl_build(QpdoDev *d) {
     if (r <= 0 || r > DEFL_MAX) return 0;
     const DevCsr &T = d->Atc;
     // P: Jacobi diagonal of the remainder (floored), A_h': the heavy columns of A_c'
-    const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, false);
+    const int gAt = rowloop_grid(d->At);
     DISPATCH_TPR(d->At, k_jacobi_diag2, gAt, n, T.rp, T.ci, T.val, (const double *)d->tmp_m, (const double *)d->dc, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
     DISPATCH_TPR(d->At, k_count_flagged, gAt, n, T.rp, T.ci, (const double *)d->defl_flag, d->row_cnt);
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, n, d->Ath.rp);
@@ -123,27 +140,7 @@ static int defl_build(QpdoDev *d) {
     double *S = Sv.data(), *L = Lv.data(), *Li = Liv.data(), *Si = Siv.data();
     HIPCHK(hipMemcpyAsync(S, d->defl_S, (size_t)DEFL_MAX * DEFL_MAX * 8, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
-    const int N = DEFL_MAX;
-    for (int i = 0; i < r; i++)                     // Cholesky S = L L'
-        for (int j = 0; j <= i; j++) {
-            double t = S[i * N + j];
-            for (int q = 0; q < j; q++) t -= L[i * N + q] * L[j * N + q];
-            if (i == j) { if (!(t > 0.0)) return 0; L[i * N + i] = sqrt(t); }
-            else L[i * N + j] = t / L[j * N + j];
-        }
-    for (int c = 0; c < r; c++)                     // Li = L^-1 (lower)
-        for (int i = 0; i < r; i++) {
-            if (i < c) { Li[i * N + c] = 0.0; continue; }
-            double t = (i == c) ? 1.0 : 0.0;
-            for (int q = c; q < i; q++) t -= L[i * N + q] * Li[q * N + c];
-            Li[i * N + c] = t / L[i * N + i];
-        }
-    for (int i = 0; i < r; i++)                     // S^-1 = Li' Li
-        for (int j = 0; j <= i; j++) {
-            double t = 0.0;
-            for (int q = i; q < r; q++) t += Li[q * N + i] * Li[q * N + j];
-            Si[i * N + j] = t; Si[j * N + i] = t;
-        }
+    if (!spd_inverse(r, DEFL_MAX, S, L, Li, Si)) return 0;
     HIPCHK(hipMemcpyAsync(d->defl_Sinv, Si, (size_t)DEFL_MAX * DEFL_MAX * 8, hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     d->defl_r = r;
@@ -229,9 +226,9 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
     const int *done2 = &d->ctrl2->cnt[C_PCG_DONE];
     const double *glob3 = dist ? d->dist_tmp + d->n : (const double *)nullptr;
     int fcnt = 0;
-    // Folded schedule (single GPU, fp64 inner matrices, one element per thread of k_cgcg_step's grid): two launches per iteration.
-    // Product 2 of application j - 1 performs step j (EpiSchurStep), product 1 of application j forms that step's three partial
-    // sums first (EpiDivDotSums).  The bits are those of the three-launch schedule below, which QPDO_INNER_FOLD=0 selects.
+    // Two-launch schedule (single GPU, fp64 inner matrices, one element per thread of k_cgcg_step's grid): product 2 of application
+    // j - 1 performs step j (EpiSchurStep), product 1 of application j forms that step's three partial sums first (EpiDivDotSums).
+    // QPDO_INNER_FOLD=0 selects the three-launch schedule; both run the same device functions (pcg_kernels.inc) and give the same bits.
     const bool fold = d->inner_fold && !dist && !schur_inner_f32(d) && (long long)g * BLK >= kl;
     LAUNCH(k_cgcg_init, g, kl, (const double *)d->s_v, (const double *)d->s_diag, (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, P3, d->ctrl2);
     int rc = 0;
@@ -248,18 +245,19 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
     int batch = d->schur_last_inner > 12 ? d->schur_last_inner - 6 : d->pcg_batch;
     while (j < SCHUR_INNER_MAXIT) {
         const int it_before = j, sample_b = batch / 2;
-        if (fold) for (int b = 0; b < batch; b++, j++) {
-            // (the HIP-event sample of the A_c product now includes the step it performs; its byte count is that of the product)
-            if (b == sample_b) (void)hipEventRecord(d->ev0, d->stream);
-            launch_spmv(d, d->Arc, d->tmp_n, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol}, false);
-            if (b == sample_b) (void)hipEventRecord(d->ev1, d->stream);
-            launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3}, true, done2);
-            d->st.inner_steps++;
-        }
-        else for (int b = 0; b < batch; b++, j++) {
-            LAUNCH(k_cgcg_step, g, kl, j, d->ctrl2, glob3, P3, g, (const double *)Pf, fcnt, (const double *)d->s_Sp, (const double *)d->s_diag,
-                   (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol);
-            rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, !dist && b == sample_b, &fcnt); if (rc) return -1;
+        for (int b = 0; b < batch; b++, j++) {           // issue iteration j: step j, then S' applied to the new u
+            const bool sample = !dist && b == sample_b;
+            if (fold) {
+                // (the HIP-event sample of the A_c product includes the step it performs; its byte count is that of the product)
+                if (sample) (void)hipEventRecord(d->ev0, d->stream);
+                launch_spmv(d, d->Arc, d->tmp_n, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol}, false);
+                if (sample) (void)hipEventRecord(d->ev1, d->stream);
+                launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3}, true, done2);
+            } else {
+                LAUNCH(k_cgcg_step, g, kl, j, d->ctrl2, glob3, P3, g, (const double *)Pf, fcnt, (const double *)d->s_Sp, (const double *)d->s_diag,
+                       (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol);
+                rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, sample, &fcnt); if (rc) return -1;
+            }
             d->st.inner_steps++;
         }
         rc = read_ctrl2(d); if (rc) return rc;
@@ -295,16 +293,55 @@ static int schur_apply(QpdoDev *d, double tol, double *p_rz, int *inner_iters, i
     launch_spmv(d, d->Atc, d->s_x, EpiDeflZ{d->pc_diag, d->pc_r, d->pc_z, p_rz}, true);
     return spmv_pgrid(d->Atc);
 }
+// The per-block partial arrays of the outer PCG in d->part, named once per solve.
+struct PcgPart { double *rz, *rr, *pKp, *rinf; };
+static PcgPart pcg_part(const QpdoDev *d) { double *P = d->part; return {P + P_RZ * PGRID, P + P_RR * PGRID, P + P_PKP * PGRID, P + P_RINF * PGRID}; }
+// The device latch is set on convergence and on a NaN residual alike; this is the host's copy of the convergence test, on the
+// residual norms the device published with the latch.
+static bool pcg_within_tol(const QpdoDev *d) {
+    return d->hctrl->val[V_RNORM] <= d->pcg_tol * d->hctrl->val[V_BNORM] || d->hctrl->val[V_RINF] <= d->pcg_abs_now;
+}
+// Kp = K p for p = pc_p, K = Q + sigma_f I + A_c' D A_c, with the per-block partial sums of p.Kp in p_pKp (*cnt of them); every
+// launch leaves at once when the latch `done` is set.  Only launches, events and the collective: capturable into a hipGraph.
+// sample: HIP events around the Q product.
+static int pcg_K_apply(QpdoDev *d, const int *done, double *p_pKp, bool sample, int *cnt) {
+    const int n = d->n, k = d->kact;
+    if (d->comm.active) {   // K p = sigma_f p + sum over ranks of ( Q_rows p  [rows n0..]  +  A_c,loc' (d_c .* A_c,loc p) )
+        HIPCHK(hipMemsetAsync(d->Kp_part, 0, (size_t)n * 8, d->stream));
+        if (k > 0) launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
+        if (sample) (void)hipEventRecord(d->ev0, d->stream);
+        if (d->nloc > 0) launch_spmv(d, d->Qs, d->pc_p, EpiAddTo{d->Kp_part, d->n0}, false, done);
+        if (sample) (void)hipEventRecord(d->ev1, d->stream);
+        if (k > 0) launch_spmv(d, d->Atc, d->tc, EpiAddTo{d->Kp_part, 0}, false, done);
+        int rc = comm_allreduce(d, d->Kp_part, (size_t)n, 0); if (rc) return rc;
+        *cnt = vgrid(n);
+        hipLaunchKernelGGL(k_pcg_dist_finish, dim3(*cnt), dim3(BLK), 0, d->stream, n, done, (const double *)d->Kp_part, (const double *)d->pc_p,
+                           d->sigma_f, d->pc_Kp, p_pKp);
+    } else if (k > 0) {
+        launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
+        if (sample) (void)hipEventRecord(d->ev0, d->stream);
+        launch_spmv(d, d->Qf, d->pc_p, EpiPcgQ{d->pc_p, d->sigma_f, d->pc_Kp}, false, done);
+        if (sample) (void)hipEventRecord(d->ev1, d->stream);
+        launch_spmv(d, d->Atc, d->tc, EpiPcgAt{d->pc_p, d->pc_Kp, p_pKp}, true, done);
+        *cnt = spmv_pgrid(d->Atc);
+    } else {                // no weighted rows
+        if (sample) (void)hipEventRecord(d->ev0, d->stream);
+        launch_spmv(d, d->Qf, d->pc_p, EpiPcgQdot{d->pc_p, d->sigma_f, d->pc_Kp, p_pKp}, true, done);
+        if (sample) (void)hipEventRecord(d->ev1, d->stream);
+        *cnt = spmv_pgrid(d->Qf);
+    }
+    return 0;
+}
 // K dx = rhs with the Schur-preconditioned outer CG.  *fallback = 1: did not converge, the caller reruns Jacobi-PCG.
 static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
     const bool dist = d->comm.active;
     const int n = d->n, kl = d->kact, k = dist ? d->kg : d->kact, g = vgrid(n);
-    double *P = d->part;
+    const PcgPart P = pcg_part(d);
     *fallback = 0;
     LAUNCH(k_axpy_const, g, n, (const double *)d->qdiag, d->sigma_f, d->pc_diag);                  // Dq
     // inner diagonal Sd_i = 1/d_i + sum_j A_ij^2 / Dq_j over this rank's compact rows (partitioned: no exchange)
     if (kl > 0) {
-        DISPATCH_TPR(d->Ar, k_schur_diag, (d->Ar.use_slab ? 2048 : spmv_grid(d->Ar, false)), kl, d->Arc.rp, d->Arc.ci, d->Arc.val,
+        DISPATCH_TPR(d->Ar, k_schur_diag, rowloop_grid(d->Ar), kl, d->Arc.rp, d->Arc.ci, d->Arc.val,
                      (const double *)d->pc_diag, (const double *)d->dc, d->s_diag);
     }
     // Inner tolerance.  An inner residual rho leaves M z - r = A_c' D rho: the error that matters is weighted by D, so
@@ -313,7 +350,7 @@ static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
     LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
     if (kl > 0) LAUNCH(k_absmax_mul, vgrid(kl), kl, (const double *)d->dc, (const double *)nullptr, d->ctrl, N_A);
     if (dist) { int rcx = comm_allreduce(d, reinterpret_cast<double *>(&d->ctrl->nrm[N_A]), 1, 1); if (rcx) return rcx; }   // bit pattern of a non-negative double
-    LAUNCH(k_pcg_init, g, n, d->rhs, d->pc_diag, d->dx, d->pc_r, d->pc_z, d->pc_p, P + P_RZ * PGRID, P + P_RR * PGRID);
+    LAUNCH(k_pcg_init, g, n, d->rhs, d->pc_diag, d->dx, d->pc_r, d->pc_z, d->pc_p, P.rz, P.rr);
     { int rc0 = read_ctrl(d); if (rc0) return rc0; }
     const double dmax = nrm_of(d->hctrl, N_A);
     d->schur_last_inner = 0;
@@ -324,12 +361,11 @@ static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
     double tau = tau0 * (dmax > 1e4 ? 1e4 / dmax : 1.0);
     if (tau < 1e-13) tau = 1e-13;
     int inner = 0, st = 0;
-    int cnt_rz = schur_apply(d, tau, P + P_RZ * PGRID, &inner, &st);
+    int cnt_rz = schur_apply(d, tau, P.rz, &inner, &st);
     if (cnt_rz < 0) return -1;
     if (st) { *fallback = 1; return 0; }
     LAUNCH(k_copy, g, n, (const double *)d->pc_z, d->pc_p);
-    LAUNCH(k_pcg_init2, 1, P + P_RZ * PGRID, cnt_rz, P + P_RR * PGRID, g, d->ctrl);
-    const int pKp_cnt = dist ? g : spmv_pgrid(d->Atc);
+    LAUNCH(k_pcg_init2, 1, P.rz, cnt_rz, P.rr, g, d->ctrl);
     const int *done = &d->ctrl->cnt[C_PCG_DONE];
     int outer = 0;
     double prev_rn = -1.0;
@@ -343,41 +379,28 @@ static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
         }
         if (d->hybrid_active && outer + inner > d->hybrid_budget) { snprintf(g_err, sizeof(g_err), "hybrid: PCG budget exceeded"); return PCG_NOT_CONVERGED; }
         if (outer >= SCHUR_OUTER_MAXIT) { if (d->defl_debug) fprintf(stderr, "[schur] k=%d outer cap reached (inner=%d)\n", k, inner); *fallback = 1; return 0; }
-        if (dist) {     // K p = sigma_f p + sum over ranks of ( Q_rows p + A_c,loc' (d_c .* A_c,loc p) ), as in the Jacobi path
-            HIPCHK(hipMemsetAsync(d->Kp_part, 0, (size_t)n * 8, d->stream));
-            if (kl > 0) launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
-            if (d->nloc > 0) launch_spmv(d, d->Qs, d->pc_p, EpiAddTo{d->Kp_part, d->n0}, false, done);
-            if (kl > 0) launch_spmv(d, d->Atc, d->tc, EpiAddTo{d->Kp_part, 0}, false, done);
-            int rcx = comm_allreduce(d, d->Kp_part, (size_t)n, 0); if (rcx) return rcx;
-            hipLaunchKernelGGL(k_pcg_dist_finish, dim3(g), dim3(BLK), 0, d->stream, n, done, (const double *)d->Kp_part, (const double *)d->pc_p,
-                               d->sigma_f, d->pc_Kp, P + P_PKP * PGRID);
-        } else {
-        launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
-        launch_spmv(d, d->Qf, d->pc_p, EpiPcgQ{d->pc_p, d->sigma_f, d->pc_Kp}, false, done);
-        launch_spmv(d, d->Atc, d->tc, EpiPcgAt{d->pc_p, d->pc_Kp, P + P_PKP * PGRID}, true, done);
-        }
-        LAUNCH(k_pcg_update, g, n, (const Ctrl *)d->ctrl, (const double *)(P + P_PKP * PGRID), pKp_cnt, (const double *)d->pc_p, (const double *)d->pc_Kp,
-               (const double *)d->pc_diag, d->dx, d->pc_r, d->pc_z, P + P_RZ * PGRID, P + P_RR * PGRID,
-               d->scaled ? (const double *)d->Dinv : (const double *)nullptr, P + P_RINF * PGRID);
+        int pKp_cnt = 0;
+        { int rc = pcg_K_apply(d, done, P.pKp, false, &pKp_cnt); if (rc) return rc; }
+        LAUNCH(k_pcg_update, g, n, (const Ctrl *)d->ctrl, P.pKp, pKp_cnt, (const double *)d->pc_p, (const double *)d->pc_Kp,
+               (const double *)d->pc_diag, d->dx, d->pc_r, d->pc_z, P.rz, P.rr,
+               d->scaled ? (const double *)d->Dinv : (const double *)nullptr, P.rinf);
         // Convergence is decided HERE, from the residual the update just formed (round 3; it used to be decided after the
         // preconditioner had been applied to that residual): a converged iteration no longer pays for an inner solve -- ~60 inner
         // iterations, one in eight of a pass -- whose result nobody uses.  Same test on the same numbers: same iteration counts, same dx.
-        LAUNCH(k_pcg_scalar, 1, d->ctrl, (const double *)(P + P_RZ * PGRID), cnt_rz, (const double *)(P + P_RR * PGRID), g, d->pcg_tol,
-               (const double *)(P + P_RINF * PGRID), d->scaled ? d->sc_cinv : 1.0, d->pcg_abs_now, 1);
+        LAUNCH(k_pcg_scalar, 1, d->ctrl, P.rz, cnt_rz, P.rr, g, d->pcg_tol, P.rinf, d->scaled ? d->sc_cinv : 1.0, d->pcg_abs_now, 1);
         { int rc = read_ctrl(d); if (rc) return rc; }
         outer++;
         if (d->hctrl->cnt[C_PCG_DONE]) break;
-        cnt_rz = schur_apply(d, tau, P + P_RZ * PGRID, &inner, &st);
+        cnt_rz = schur_apply(d, tau, P.rz, &inner, &st);
         if (cnt_rz < 0) return -1;
         if (st) { if (d->defl_debug) fprintf(stderr, "[schur] k=%d inner solve did not converge (outer=%d inner=%d)\n", k, outer, inner); *fallback = 1; return 0; }
-        LAUNCH(k_pcg_scalar, 1, d->ctrl, (const double *)(P + P_RZ * PGRID), cnt_rz, (const double *)(P + P_RR * PGRID), g, d->pcg_tol,
-               (const double *)(P + P_RINF * PGRID), d->scaled ? d->sc_cinv : 1.0, d->pcg_abs_now, 2);
+        LAUNCH(k_pcg_scalar, 1, d->ctrl, P.rz, cnt_rz, P.rr, g, d->pcg_tol, P.rinf, d->scaled ? d->sc_cinv : 1.0, d->pcg_abs_now, 2);
         LAUNCH(k_pcg_p, g, n, (const Ctrl *)d->ctrl, (const double *)d->pc_z, d->pc_p);
     }
     if (d->defl_debug) fprintf(stderr, "[schur] dmax=%.2e tau_end=%.1e ", dmax, tau);
     {   // the latch is also set by a NaN residual: that is not convergence -- let the Jacobi path redo the pass
         const double rnv = d->hctrl->val[V_RNORM], bnv = d->hctrl->val[V_BNORM];
-        if (outer > 0 && !(rnv <= d->pcg_tol * bnv || d->hctrl->val[V_RINF] <= d->pcg_abs_now)) { *fallback = 1; return 0; }
+        if (outer > 0 && !pcg_within_tol(d)) { *fallback = 1; return 0; }
         if (outer > 0 && bnv > 0.0 && rnv / bnv > d->st.pcg_max_relres) d->st.pcg_max_relres = rnv / bnv;
     }
     *iters_out = outer + inner;
@@ -437,61 +460,37 @@ static int pcg_solve(QpdoDev *d, int *iters_out) {
     rc = defl_build(d); if (rc) return rc;
     const bool defl = d->defl_r > 0;
     const bool dist = d->comm.active;
-    if (!defl && dist) {   // sum_i A_ij^2 d_i over the local rows, summed over ranks, plus Q_jj + sigma_f
-        if (k > 0) {
-            const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, false);
-            DISPATCH_TPR(d->At, k_jacobi_diag, gAt, n, d->Atc.rp, d->Atc.ci, d->Atc.val, (const double *)d->dc, (const double *)d->zeros_n, 0.0, d->dist_tmp);
-        } else HIPCHK(hipMemsetAsync(d->dist_tmp, 0, (size_t)n * 8, d->stream));
+    // Jacobi diagonal Q_jj + sigma_f + sum_i A_ij^2 d_i; row-partitioned: the sum over the local rows, summed over the ranks, then the rest
+    auto jacobi_diag = [&](const double *base, double shift, double *out) {
+        DISPATCH_TPR(d->At, k_jacobi_diag, rowloop_grid(d->At), n, d->Atc.rp, d->Atc.ci, d->Atc.val, (const double *)d->dc, base, shift, out);
+    };
+    if (!defl && dist) {
+        if (k > 0) jacobi_diag(d->zeros_n, 0.0, d->dist_tmp);
+        else HIPCHK(hipMemsetAsync(d->dist_tmp, 0, (size_t)n * 8, d->stream));
         rc = comm_allreduce(d, d->dist_tmp, (size_t)n, 0); if (rc) return rc;
         LAUNCH(k_add3, vgrid(n), n, (const double *)d->dist_tmp, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
-    } else if (!defl) {   // Jacobi diagonal: Q_jj + sigma_f + sum_i A_ij^2 d_i
-        if (k > 0) {
-            const int gAt = d->At.use_slab ? 2048 : spmv_grid(d->At, false);
-            DISPATCH_TPR(d->At, k_jacobi_diag, gAt, n, d->Atc.rp, d->Atc.ci, d->Atc.val, (const double *)d->dc, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
-        } else {
-            LAUNCH(k_axpy_const, vgrid(n), n, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
-        }
+    } else if (!defl) {
+        if (k > 0) jacobi_diag(d->qdiag, d->sigma_f, d->pc_diag);
+        else LAUNCH(k_axpy_const, vgrid(n), n, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
     }
     const int g = vgrid(n);
-    double *P = d->part;
+    const PcgPart P = pcg_part(d);
     const int *done = &d->ctrl->cnt[C_PCG_DONE];
-    LAUNCH(k_pcg_init, g, n, d->rhs, d->pc_diag, d->dx, d->pc_r, d->pc_z, d->pc_p, P + P_RZ * PGRID, P + P_RR * PGRID);
+    LAUNCH(k_pcg_init, g, n, d->rhs, d->pc_diag, d->dx, d->pc_r, d->pc_z, d->pc_p, P.rz, P.rr);
     int cnt_rz = g;
     if (defl) {
-        cnt_rz = defl_apply(d, nullptr, P + P_RZ * PGRID);
+        cnt_rz = defl_apply(d, nullptr, P.rz);
         LAUNCH(k_copy, g, n, (const double *)d->pc_z, d->pc_p);
     }
-    LAUNCH(k_pcg_init2, 1, P + P_RZ * PGRID, cnt_rz, P + P_RR * PGRID, g, d->ctrl);
-    const int pKp_cnt = dist ? vgrid(n) : (k > 0 ? spmv_pgrid(d->Atc) : spmv_pgrid(d->Qf));
+    LAUNCH(k_pcg_init2, 1, P.rz, cnt_rz, P.rr, g, d->ctrl);
     // one PCG iteration as a sequence of launches on the backend stream
     auto issue_iteration = [&](bool sample) -> int {
-        if (dist) {
-            // K p = sigma_f p + sum over ranks of ( Q_rows p  [rows n0..]  +  A_c,loc' (d_c .* A_c,loc p) )
-            HIPCHK(hipMemsetAsync(d->Kp_part, 0, (size_t)n * 8, d->stream));
-            if (k > 0) launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
-            if (sample) (void)hipEventRecord(d->ev0, d->stream);
-            if (d->nloc > 0) launch_spmv(d, d->Qs, d->pc_p, EpiAddTo{d->Kp_part, d->n0}, false, done);
-            if (sample) (void)hipEventRecord(d->ev1, d->stream);
-            if (k > 0) launch_spmv(d, d->Atc, d->tc, EpiAddTo{d->Kp_part, 0}, false, done);
-            int rcx = comm_allreduce(d, d->Kp_part, (size_t)n, 0); if (rcx) return rcx;
-            hipLaunchKernelGGL(k_pcg_dist_finish, dim3(g), dim3(BLK), 0, d->stream, n, done, (const double *)d->Kp_part, (const double *)d->pc_p,
-                               d->sigma_f, d->pc_Kp, P + P_PKP * PGRID);
-        } else if (k > 0) {
-            launch_spmv(d, d->Arc, d->pc_p, EpiPcgA{d->dc, d->tc, nullptr}, false, done);
-            if (sample) (void)hipEventRecord(d->ev0, d->stream);
-            launch_spmv(d, d->Qf, d->pc_p, EpiPcgQ{d->pc_p, d->sigma_f, d->pc_Kp}, false, done);
-            if (sample) (void)hipEventRecord(d->ev1, d->stream);
-            launch_spmv(d, d->Atc, d->tc, EpiPcgAt{d->pc_p, d->pc_Kp, P + P_PKP * PGRID}, true, done);
-        } else {
-            if (sample) (void)hipEventRecord(d->ev0, d->stream);
-            launch_spmv(d, d->Qf, d->pc_p, EpiPcgQdot{d->pc_p, d->sigma_f, d->pc_Kp, P + P_PKP * PGRID}, true, done);
-            if (sample) (void)hipEventRecord(d->ev1, d->stream);
-        }
-        LAUNCH(k_pcg_update, g, n, d->ctrl, P + P_PKP * PGRID, pKp_cnt, d->pc_p, d->pc_Kp, d->pc_diag, d->dx, d->pc_r, d->pc_z,
-               P + P_RZ * PGRID, P + P_RR * PGRID, d->scaled ? (const double *)d->Dinv : (const double *)nullptr, P + P_RINF * PGRID);
-        if (defl) defl_apply(d, done, P + P_RZ * PGRID);
-        LAUNCH(k_pcg_scalar, 1, d->ctrl, P + P_RZ * PGRID, cnt_rz, P + P_RR * PGRID, g, d->pcg_tol,
-               (const double *)(P + P_RINF * PGRID), d->scaled ? d->sc_cinv : 1.0, d->pcg_abs_now);
+        int pKp_cnt = 0;
+        { int rcx = pcg_K_apply(d, done, P.pKp, sample, &pKp_cnt); if (rcx) return rcx; }
+        LAUNCH(k_pcg_update, g, n, d->ctrl, P.pKp, pKp_cnt, d->pc_p, d->pc_Kp, d->pc_diag, d->dx, d->pc_r, d->pc_z,
+               P.rz, P.rr, d->scaled ? (const double *)d->Dinv : (const double *)nullptr, P.rinf);
+        if (defl) defl_apply(d, done, P.rz);
+        LAUNCH(k_pcg_scalar, 1, d->ctrl, P.rz, cnt_rz, P.rr, g, d->pcg_tol, P.rinf, d->scaled ? d->sc_cinv : 1.0, d->pcg_abs_now);
         LAUNCH(k_pcg_p, g, n, d->ctrl, d->pc_z, d->pc_p);
         return 0;
     };
@@ -544,7 +543,7 @@ static int pcg_solve(QpdoDev *d, int *iters_out) {
     d->last_jacobi_iters = *iters_out;
     {   // DONE is also latched on a NaN residual (k_pcg_scalar): "converged" means DONE with a finite residual within tolerance
         const double rnv = d->hctrl->val[V_RNORM], bnv = d->hctrl->val[V_BNORM];
-        const bool conv = d->hctrl->cnt[C_PCG_DONE] && (bnv == 0.0 || *iters_out == 0 || rnv <= d->pcg_tol * bnv || d->hctrl->val[V_RINF] <= d->pcg_abs_now);
+        const bool conv = d->hctrl->cnt[C_PCG_DONE] && (bnv == 0.0 || *iters_out == 0 || pcg_within_tol(d));
         if (!conv && d->hybrid_active) { snprintf(g_err, sizeof(g_err), "hybrid: PCG budget exceeded"); return PCG_NOT_CONVERGED; }      // (no soft accept: the dense factor takes over)
         rc = pcg_verdict(d, conv, (bnv == 0.0 || *iters_out == 0) ? 0.0 : rnv, bnv, "Jacobi-PCG", stalled); if (rc) return rc;
     }

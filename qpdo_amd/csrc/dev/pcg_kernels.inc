@@ -49,15 +49,8 @@ __global__ __launch_bounds__(256) void k_pcg_update(int n, const Ctrl *__restric
         const double s = fabs(Dinv ? Dinv[i] * ri : ri);
         mx = s > mx ? s : mx;
     }
-    double ta = block_sum(a, sm), tc = block_sum(c, sm + 16);
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) sm[32 + (threadIdx.x >> 6)] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = sm[32];
-        for (int w = 1; w < (int)(blockDim.x >> 6); w++) t = sm[32 + w] > t ? sm[32 + w] : t;
-        p_rz[blockIdx.x] = ta; p_rr[blockIdx.x] = tc; p_rinf[blockIdx.x] = t;
-    }
+    const double ta = block_sum(a, sm), tc = block_sum(c, sm + 16), t = block_max(mx, sm + 32);
+    if (threadIdx.x == 0) { p_rz[blockIdx.x] = ta; p_rr[blockIdx.x] = tc; p_rinf[blockIdx.x] = t; }
 }
 // scalar step: convergence latch, beta, rz roll-over (single block)
 // Stopping rule: relative, ||r||_2 <= tol ||rhs||_2, OR absolute, cinv * max_i |Dinv_i r_i| <= abs_floor -- the latter is the
@@ -80,13 +73,8 @@ __global__ __launch_bounds__(256) void k_pcg_scalar(Ctrl *ctrl, const double *__
     const double rz2 = phase == 1 ? 0.0 : reduce_partials(p_rz, cnt_rz, sm), rr = reduce_partials(p_rr, cnt, sm + 16);
     double mx = 0.0;
     for (int i = threadIdx.x; i < cnt; i += blockDim.x) { const double v = p_rinf[i]; mx = v > mx ? v : mx; }
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) sm[32 + (threadIdx.x >> 6)] = mx;
-    __syncthreads();
+    const double rinf = block_max(mx, sm + 32) * cinv;
     if (threadIdx.x == 0) {
-        double rinf = sm[32];
-        for (int w = 1; w < (int)(blockDim.x >> 6); w++) rinf = sm[32 + w] > rinf ? sm[32 + w] : rinf;
-        rinf *= cinv;
         ctrl->cnt[C_PCG_IT] += 1;
         ctrl->val[V_RNORM] = sqrt(rr);
         ctrl->val[V_RINF] = rinf;
@@ -107,35 +95,95 @@ __global__ void k_pcg_p(int n, const Ctrl *__restrict__ ctrl, const double *__re
 // ------------------------------------------------------------------------------------------------
 // Single-reduction (Chronopoulos-Gear) Jacobi-PCG for the inner system of the Schur-complement mode,
 //     S' s = v,   S' = D^-1 + A_c Dq^-1 A_c'   (k x k, never formed; rank r owns k_loc of its rows).
-// One iteration = ONE vector kernel (k_cgcg_step) + the two products of S' u:
-//     p = u + beta p;  s = w + beta s;  x += alpha p;  r -= alpha s;  u = r ./ diag        (k_cgcg_step)
+// Iteration j is step j followed by one application of S' to the new u:
+//     p = u + beta p;  s = w + beta s;  x += alpha p;  r -= alpha s;  u = r ./ diag        (step)
 //     tn = A_c' u (all-reduced over the ranks);  t = tn ./ Dq                              (product 1)
 //     w = u ./ d + A_c t                                                                    (product 2)
-//     gamma = (r,u);  delta = (w,u) = sum u^2/d + sum tn t;  beta' = gamma/gamma_old;  alpha' = gamma / (delta - beta' gamma / alpha)
-// Every scalar is known right after product 1: (r,u), (r,r) and sum u^2/d are local partial sums formed by k_cgcg_step
-// BEFORE the product (single GPU: re-reduced in fixed order by the next k_cgcg_step; multi GPU: three doubles appended
-// to the n-vector payload of the one all-reduce), and sum tn t is a dot of the replicated n-vector that every rank
-// computes identically.  Hence 3 launches per iteration on one GPU (was 5) and exactly one collective per iteration
-// on several, with the k-vectors partitioned.  Partial-sum arrays and the (gamma, alpha) state are double-buffered
-// by the parity of the host-supplied iteration index j, because blocks of one launch read what another block of the
-// same launch must not overwrite.  All reductions run in a fixed order: bitwise reproducible.
+//     gamma = (r,u);  delta = (w,u) = sum u^2/d + sum tn t;  beta = gamma/gamma_old;  alpha = gamma / (delta - beta gamma / alpha_old)
+// Every scalar of step j is known right after product 1 of the application before it: (r,u), (r,r) and sum u^2/d are per-block
+// partial sums over the 256-element blocks of the k-vectors (single GPU: P3, re-reduced in fixed order by every workgroup of the
+// step; several GPUs: their three totals ride at the end of the n-vector payload of the one all-reduce, glob3), and sum tn t (Pf)
+// is a dot of the replicated n-vector that every rank computes identically: one collective per iteration, the k-vectors partitioned.
+// Partial-sum arrays and the (gamma, alpha) state are double-buffered by the parity of the host-supplied index j, because
+// workgroups of one launch read what another workgroup of the same launch must not overwrite.  All reductions run in a fixed
+// order: bitwise reproducible, and the same bits from both schedules --
+//     three launches: k_cgcg_step, product 1 (EpiDivDot), product 2 (EpiSchurW);
+//     two launches (single GPU, fp64 matrices, k <= PGRID * 256): product 2 performs the step behind its rows (EpiSchurStep) and
+//     product 1 forms the step's partial sums in front of its own (EpiDivDotSums) --
+// because both are built from the same three functions: cgcg_scalars, cgcg_elem, cgcg_sums (+ cgcg_put3).
 // ------------------------------------------------------------------------------------------------
 enum { VS_GAM = 11, VS_ALP = 13 };      // ctrl->val slots (two each, by parity) of the inner solver's control block
+// the three per-element terms of (r,u), (r,r), sum u^2/d
+__device__ __forceinline__ void cgcg_sums(double ri, double ui, double dci, double &a, double &c, double &e) { a = ri * ui; c = ri * ri; e = ui * ui / dci; }
+// block sums of the three terms (first 256 threads of the workgroup) -> P3[.][par][blk]     (P3: [3 sums][2 parities][PGRID])
+__device__ __forceinline__ void cgcg_put3(double a, double c, double e, double *__restrict__ P3, int par, int blk, double *sm) {
+    double zero = 0.0;
+    block_sum4_256(a, c, e, zero, sm);
+    if (threadIdx.x == 0) { P3[(0 * 2 + par) * PGRID + blk] = a; P3[(1 * 2 + par) * PGRID + blk] = c; P3[(2 * 2 + par) * PGRID + blk] = e; }
+}
+// Element i of the step, operands in registers (the caller decides when they are loaded); leaves the new r_i, u_i in ri, un.
+__device__ __forceinline__ void cgcg_elem(int i, double alpha, double beta, double ui, double wi, double pi0, double si0, double xi, double ri0, double dgi,
+                                          double *x, double *r, double *u, double *p, double *s, double &ri, double &un) {
+    const double pi = ui + beta * pi0, si = wi + beta * si0;
+    p[i] = pi; s[i] = si;
+    x[i] = xi + alpha * pi;
+    ri = ri0 - alpha * si;
+    r[i] = ri;
+    un = ri / dgi;
+    u[i] = un;
+}
+// The scalar part of step j, run by every workgroup of the launch that performs it (its first 256 threads reduce; all threads get
+// the result).  false: no step -- an EARLIER launch has latched (the latch holds the index of the launch that set it, + 1), or the
+// residual has converged or is NaN (the host tells them apart from V_RNORM), which workgroup 0 latches here.  Only an earlier
+// launch's latch may end a workgroup at the top: workgroup 0 of this very launch may set it while other waves are still there, and
+// a workgroup whose waves split on it would reduce over missing partials; the in-launch exit is uniform, because every workgroup
+// derives rn from the same read-only sums.  true: alpha and beta of the step, and workgroup 0 has published gamma, alpha (next
+// parity), the iteration count and the norms.  It does so before the element updates of the launch: the slots other workgroups
+// still read are those of this parity, and V_BNORM is only written at j == 0, where nobody reads it.
+// glob3 (row-partitioned): the three k-sums arrive reduced over the ranks, only f is summed here.  sm: >= 16 doubles.
+__device__ __forceinline__ bool cgcg_scalars(int j, Ctrl *ctrl, const double *__restrict__ glob3, const double *P3, int pcnt, const double *__restrict__ Pf, int fcnt,
+                                             double tol, double *sm, double &alpha, double &beta) {
+    { const int dn = ctrl->cnt[C_PCG_DONE]; if (dn && dn <= j) return false; }
+    const int par = j & 1;
+    double gam = 0.0, rr = 0.0, e = 0.0, f = 0.0;
+    if (threadIdx.x < 256) {
+        if (!glob3) for (int q = threadIdx.x; q < pcnt; q += 256) { gam += P3[(0 * 2 + par) * PGRID + q]; rr += P3[(1 * 2 + par) * PGRID + q]; e += P3[(2 * 2 + par) * PGRID + q]; }
+        for (int q = threadIdx.x; q < fcnt; q += 256) f += Pf[q];
+    }
+    if (glob3) { double z0 = 0.0, z1 = 0.0, z2 = 0.0; block_sum4_256(z0, z1, z2, f, sm); gam = glob3[0]; rr = glob3[1]; e = glob3[2]; }
+    else block_sum4_256(gam, rr, e, f, sm);
+    const double delta = e + f;                                  // (w,u) = u' D^-1 u + tn' Dq^-1 tn
+    const double rn = sqrt(rr);
+    const double bnorm = (j == 0) ? rn : ctrl->val[V_BNORM];
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (rn <= tol * bnorm || !(rr == rr)) {
+        if (first) { ctrl->cnt[C_PCG_DONE] = j + 1; ctrl->val[V_RNORM] = rn; if (j == 0) ctrl->val[V_BNORM] = bnorm; }
+        return false;
+    }
+    beta = (j == 0) ? 0.0 : gam / ctrl->val[VS_GAM + par];
+    alpha = (j == 0) ? gam / delta : gam / (delta - beta * gam / ctrl->val[VS_ALP + par]);
+    if (first) {
+        const int np = par ^ 1;
+        ctrl->val[VS_GAM + np] = gam; ctrl->val[VS_ALP + np] = alpha;
+        ctrl->cnt[C_PCG_IT] += 1; ctrl->val[V_RNORM] = rn;
+        if (j == 0) ctrl->val[V_BNORM] = bnorm;
+    }
+    return true;
+}
 __global__ __launch_bounds__(256) void k_cgcg_init(int k, const double *__restrict__ b, const double *__restrict__ dg, const double *__restrict__ dc,
                                                    double *__restrict__ x, double *__restrict__ r, double *__restrict__ u, double *__restrict__ p,
-                                                   double *__restrict__ s, double *__restrict__ P3 /* [3][2][PGRID], slot 0 written */, Ctrl *ctrl) {
-    __shared__ double sm[48];
+                                                   double *__restrict__ s, double *__restrict__ P3 /* slot 0 written */, Ctrl *ctrl) {
+    __shared__ double sm[16];
     double a = 0.0, c = 0.0, e = 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
         const double bi = b[i], ui = bi / dg[i];
         x[i] = 0.0; r[i] = bi; u[i] = ui; p[i] = 0.0; s[i] = 0.0;
-        a += bi * ui; c += bi * bi; e += ui * ui / dc[i];
+        double ta, tc, te;
+        cgcg_sums(bi, ui, dc[i], ta, tc, te);
+        a += ta; c += tc; e += te;
     }
-    const double ta = block_sum(a, sm), tc = block_sum(c, sm + 16), te = block_sum(e, sm + 32);
-    if (threadIdx.x == 0) {
-        P3[0 * 2 * PGRID + blockIdx.x] = ta; P3[1 * 2 * PGRID + blockIdx.x] = tc; P3[2 * 2 * PGRID + blockIdx.x] = te;
-        if (blockIdx.x == 0) { ctrl->cnt[C_PCG_DONE] = 0; ctrl->cnt[C_PCG_IT] = 0; ctrl->val[V_RNORM] = 0.0; }
-    }
+    cgcg_put3(a, c, e, P3, 0, blockIdx.x, sm);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl->cnt[C_PCG_DONE] = 0; ctrl->cnt[C_PCG_IT] = 0; ctrl->val[V_RNORM] = 0.0; }
 }
 // sums of the three local partial arrays of parity `par` -> out[0..3) (multi GPU: appended to the all-reduce payload)
 __global__ __launch_bounds__(256) void k_cgcg_pack3(const int *__restrict__ done, const double *__restrict__ P3, int par, int cnt, double *__restrict__ out) {
@@ -145,77 +193,38 @@ __global__ __launch_bounds__(256) void k_cgcg_pack3(const int *__restrict__ done
                  e = reduce_partials(P3 + (2 * 2 + par) * PGRID, cnt, sm + 32);
     if (threadIdx.x == 0) { out[0] = a; out[1] = c; out[2] = e; }
 }
+// Step j as a launch of its own; w = S' u from the application before it.
 __global__ __launch_bounds__(256) void k_cgcg_step(int k, int j, Ctrl *ctrl, const double *__restrict__ glob3, double *__restrict__ P3, int pcnt,
                                                    const double *__restrict__ Pf, int fcnt, const double *__restrict__ w, const double *__restrict__ dg,
                                                    const double *__restrict__ dc, double *__restrict__ x, double *__restrict__ r, double *__restrict__ u,
                                                    double *__restrict__ p, double *__restrict__ s, double tol) {
-    __shared__ double sm[32];
-    // The latch holds (index of the launch that set it) + 1.  Only a latch set by an EARLIER launch ends this one at the top:
-    // block 0 of this very launch may set it below while other waves are still here, and a workgroup whose waves split on it
-    // would reduce over missing partials.  The in-launch exit further down is uniform -- every block derives rn from the same
-    // read-only partial sums.
-    { const int dn = ctrl->cnt[C_PCG_DONE]; if (dn && dn <= j) return; }
-    const int par = j & 1;
-    // The vector operands do not depend on the scalars: the grid covers k with one element per thread (k <= PGRID * 256), so
+    __shared__ double sm[16];
+    // The vector operands do not depend on the scalars: when the grid covers k with one element per thread (k <= PGRID * 256)
     // their loads are issued first and are in flight while the partial sums are re-reduced.
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool own = i < k && (int)(gridDim.x * blockDim.x) >= k;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    const bool own = i < k && stride >= k;
     double ui = 0.0, pi0 = 0.0, wi = 0.0, si0 = 0.0, xi = 0.0, ri0 = 0.0, dgi = 1.0, dci = 1.0;
     if (own) { ui = u[i]; pi0 = p[i]; wi = w[i]; si0 = s[i]; xi = x[i]; ri0 = r[i]; dgi = dg[i]; dci = dc[i]; }
-    double gam = 0.0, rr = 0.0, e = 0.0, f = 0.0;
-    if (glob3) { gam = glob3[0]; rr = glob3[1]; e = glob3[2]; }
-    else for (int q = threadIdx.x; q < pcnt; q += blockDim.x) { gam += P3[(0 * 2 + par) * PGRID + q]; rr += P3[(1 * 2 + par) * PGRID + q]; e += P3[(2 * 2 + par) * PGRID + q]; }
-    for (int q = threadIdx.x; q < fcnt; q += blockDim.x) f += Pf[q];
-    if (glob3) { double z0 = 0.0, z1 = 0.0, z2 = 0.0; block_sum4(z0, z1, z2, f, sm); }
-    else block_sum4(gam, rr, e, f, sm);
-    const double delta = e + f;                                  // (w,u) = u' D^-1 u + tn' Dq^-1 tn
-    const double rn = sqrt(rr);
-    const double bnorm = (j == 0) ? rn : ctrl->val[V_BNORM];
-    if (rn <= tol * bnorm || !(rr == rr)) {                      // converged (or NaN: the host tells them apart from V_RNORM)
-        if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl->cnt[C_PCG_DONE] = j + 1; ctrl->val[V_RNORM] = rn; if (j == 0) ctrl->val[V_BNORM] = bnorm; }
-        return;
-    }
-    const double beta = (j == 0) ? 0.0 : gam / ctrl->val[VS_GAM + par];
-    const double alpha = (j == 0) ? gam / delta : gam / (delta - beta * gam / ctrl->val[VS_ALP + par]);
-    double a = 0.0, c = 0.0, e2 = 0.0, zero = 0.0;
+    double alpha, beta;
+    if (!cgcg_scalars(j, ctrl, glob3, P3, pcnt, Pf, fcnt, tol, sm, alpha, beta)) return;
+    double a = 0.0, c = 0.0, e = 0.0, ri, un;
     if (own) {
-        const double pi = ui + beta * pi0, si = wi + beta * si0;
-        p[i] = pi; s[i] = si;
-        x[i] = xi + alpha * pi;
-        const double ri = ri0 - alpha * si;
-        r[i] = ri;
-        const double un = ri / dgi;
-        u[i] = un;
-        a = ri * un; c = ri * ri; e2 = un * un / dci;
-    } else if ((int)(gridDim.x * blockDim.x) < k) {              // (not reached with vgrid(k) for k <= 262144; kept for generality)
-        for (int q = i; q < k; q += gridDim.x * blockDim.x) {
-            const double uq = u[q];
-            const double pq = uq + beta * p[q], sq = w[q] + beta * s[q];
-            p[q] = pq; s[q] = sq;
-            x[q] += alpha * pq;
-            const double rq = r[q] - alpha * sq;
-            r[q] = rq;
-            const double un = rq / dg[q];
-            u[q] = un;
-            a += rq * un; c += rq * rq; e2 += un * un / dc[q];
+        cgcg_elem(i, alpha, beta, ui, wi, pi0, si0, xi, ri0, dgi, x, r, u, p, s, ri, un);
+        cgcg_sums(ri, un, dci, a, c, e);
+    } else if (stride < k) {                                     // (not reached with vgrid(k) for k <= 262144; the fold is off beyond)
+        for (int q = i; q < k; q += stride) {
+            double ta, tc, te;
+            cgcg_elem(q, alpha, beta, u[q], w[q], p[q], s[q], x[q], r[q], dg[q], x, r, u, p, s, ri, un);
+            cgcg_sums(ri, un, dc[q], ta, tc, te);
+            a += ta; c += tc; e += te;
         }
     }
-    block_sum4(a, c, e2, zero, sm);
-    if (threadIdx.x == 0) {
-        const int np = par ^ 1;
-        P3[(0 * 2 + np) * PGRID + blockIdx.x] = a; P3[(1 * 2 + np) * PGRID + blockIdx.x] = c; P3[(2 * 2 + np) * PGRID + blockIdx.x] = e2;
-        if (blockIdx.x == 0) {
-            ctrl->val[VS_GAM + np] = gam; ctrl->val[VS_ALP + np] = alpha;
-            ctrl->cnt[C_PCG_IT] += 1; ctrl->val[V_RNORM] = rn;
-            if (j == 0) ctrl->val[V_BNORM] = bnorm;
-        }
-    }
+    cgcg_put3(a, c, e, P3, (j & 1) ^ 1, blockIdx.x, sm);
 }
 
-// The inner CG's vector step folded into its two products (QPDO_INNER_FOLD=0: k_cgcg_step between them, as before; same bits).
-// Product 1 of application j: before its own rows, workgroup b forms the partial sums of the step that the previous launch performed --
-// sum r.u, sum r.r, sum u^2/d over the 256-element blocks b, b + gridDim, ... of the k-vectors, with the per-element expressions and the
-// block_sum4 tree of k_cgcg_step -- into P3[.][np][block] (P3 == nullptr: the application after k_cgcg_init, whose slot 0 is filled).
+// Product 1 of the two-launch schedule.  Before its own rows, workgroup b forms the partial sums of the step that the launch
+// before it performed, over the 256-element blocks b, b + gridDim, ... of the k-vectors (its first 256 threads are one block of
+// k_cgcg_step), into P3[.][np][block].  P3 == nullptr: the application after k_cgcg_init, whose slot 0 is filled.
 struct EpiDivDotSums {
     const double *w; double *out, *p_f;
     int k, np; const double *r, *u, *dc; double *P3;
@@ -226,10 +235,9 @@ struct EpiDivDotSums {
         const int nblk = (k + 255) >> 8;
         for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
             const int i = blk * 256 + (int)threadIdx.x;
-            double a = 0.0, c = 0.0, e2 = 0.0, zero = 0.0;
-            if (threadIdx.x < 256 && i < k) { const double ri = r[i], un = u[i]; a = ri * un; c = ri * ri; e2 = un * un / dc[i]; }
-            block_sum4_256(a, c, e2, zero, sm);
-            if (threadIdx.x == 0) { P3[(0 * 2 + np) * PGRID + blk] = a; P3[(1 * 2 + np) * PGRID + blk] = c; P3[(2 * 2 + np) * PGRID + blk] = e2; }
+            double a = 0.0, c = 0.0, e = 0.0;
+            if (threadIdx.x < 256 && i < k) cgcg_sums(r[i], u[i], dc[i], a, c, e);
+            cgcg_put3(a, c, e, P3, np, blk, sm);
         }
         return true;
     }
@@ -239,58 +247,27 @@ struct EpiDivDotSums {
         if (threadIdx.x == 0) p_f[blockIdx.x] = t;
     }
 };
-// Product 2 of application j - 1 performs step j: at its top every workgroup re-reduces the partial sums P3[.][par][0..pcnt) and
-// Pf[0..fcnt) in the order of k_cgcg_step (its first 256 threads are one block of that kernel), derives rn, the convergence test,
-// beta and alpha with that kernel's expressions, and leaves alpha and beta in LDS; then, per owned row, w_i = u_i / d_i + (A_c t)_i
-// as EpiSchurW and the five updates and u_i = r_i / diag_i in k_cgcg_step's order.  w never goes to memory; u is read by this launch
-// for the workgroup's own rows only (its x is t), so it is written in place.  Converged or NaN: every workgroup leaves (the decision
-// is the same in all of them), workgroup 0 sets the latch to j + 1.  Only a latch set by an EARLIER launch ends this one at its top,
-// so the kernel's own `done` argument is nullptr for this functor.
+// Product 2 of the two-launch schedule: application j - 1 performs step j.  At its top every workgroup runs cgcg_scalars and
+// leaves alpha and beta in LDS; then, per owned row, w_i = u_i / d_i + (A_c t)_i as EpiSchurW and the element step.  w never goes
+// to memory; u is read by this launch for the workgroup's own rows only (its x is t), so it is written in place.  The kernel's own
+// `done` argument is nullptr for this functor: cgcg_scalars decides which latch may end the launch.
 struct EpiSchurStep {
     int j; Ctrl *ctrl; const double *P3; int pcnt; const double *Pf; int fcnt;
     const double *dg, *dc; double *x, *r, *u, *p, *s; double tol;
     const double *ab = nullptr;                 // alpha, beta in LDS
     __device__ bool skip(int) const { return false; }
     __device__ bool prologue(double *sm) {
-        { const int dn = ctrl->cnt[C_PCG_DONE]; if (dn && dn <= j) return false; }
-        const int par = j & 1;
-        double gam = 0.0, rr = 0.0, e = 0.0, f = 0.0;
-        if (threadIdx.x < 256) {
-            for (int q = threadIdx.x; q < pcnt; q += 256) { gam += P3[(0 * 2 + par) * PGRID + q]; rr += P3[(1 * 2 + par) * PGRID + q]; e += P3[(2 * 2 + par) * PGRID + q]; }
-            for (int q = threadIdx.x; q < fcnt; q += 256) f += Pf[q];
-        }
-        block_sum4_256(gam, rr, e, f, sm);
-        const double delta = e + f;
-        const double rn = sqrt(rr);
-        const double bnorm = (j == 0) ? rn : ctrl->val[V_BNORM];
-        const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-        if (rn <= tol * bnorm || !(rr == rr)) {
-            if (first) { ctrl->cnt[C_PCG_DONE] = j + 1; ctrl->val[V_RNORM] = rn; if (j == 0) ctrl->val[V_BNORM] = bnorm; }
-            return false;
-        }
-        const double beta = (j == 0) ? 0.0 : gam / ctrl->val[VS_GAM + par];
-        const double alpha = (j == 0) ? gam / delta : gam / (delta - beta * gam / ctrl->val[VS_ALP + par]);
+        double alpha, beta;
+        if (!cgcg_scalars(j, ctrl, nullptr, P3, pcnt, Pf, fcnt, tol, sm, alpha, beta)) return false;
         if (threadIdx.x == 0) { sm[16] = alpha; sm[17] = beta; }
-        if (first) {
-            const int np = par ^ 1;
-            ctrl->val[VS_GAM + np] = gam; ctrl->val[VS_ALP + np] = alpha;
-            ctrl->cnt[C_PCG_IT] += 1; ctrl->val[V_RNORM] = rn;
-            if (j == 0) ctrl->val[V_BNORM] = bnorm;
-        }
         ab = sm + 16;
         __syncthreads();
         return true;
     }
     __device__ void row(int i, double acc) {
-        const double alpha = ab[0], beta = ab[1];
-        const double ui = u[i];
-        const double wi = ui / dc[i] + acc;
-        const double pi = ui + beta * p[i], si = wi + beta * s[i];
-        p[i] = pi; s[i] = si;
-        x[i] = x[i] + alpha * pi;
-        const double ri = r[i] - alpha * si;
-        r[i] = ri;
-        u[i] = ri / dg[i];
+        const double ui = u[i], wi = ui / dc[i] + acc;
+        double ri, un;
+        cgcg_elem(i, ab[0], ab[1], ui, wi, p[i], s[i], x[i], r[i], dg[i], x, r, u, p, s, ri, un);
     }
     __device__ void finish(double *) {}
 };

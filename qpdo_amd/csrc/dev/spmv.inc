@@ -475,21 +475,6 @@ struct EpiPcgAt {                          // Kp += A' t ; partial p.Kp
         if (threadIdx.x == 0) p_pKp[blockIdx.x] = t;
     }
 };
-struct EpiDivStore {                       // out = (M x) ./ w
-    const double *w; double *out;
-    __device__ bool skip(int) const { return false; }
-    __device__ void row(int r, double s) { out[r] = s / w[r]; }
-    __device__ void finish(double *) {}
-};
-struct EpiSchurA {                         // Sp = p ./ d + A_c t ; partial p.Sp   (S' = D^-1 + A_c Dq^-1 A_c')
-    const double *dc, *p; double *Sp, *p_pSp; double acc = 0.0;
-    __device__ bool skip(int) const { return false; }
-    __device__ void row(int r, double s) { const double v = p[r] / dc[r] + s; Sp[r] = v; acc += p[r] * v; }
-    __device__ void finish(double *sm) {
-        double t = block_sum(acc, sm);
-        if (threadIdx.x == 0) p_pSp[blockIdx.x] = t;
-    }
-};
 struct EpiDivDot {                         // t = (M x) ./ w ; partial sum of (M x) .* t   (product 1 of the single-reduction inner CG)
     const double *w; double *out, *p_f; double acc = 0.0;
     __device__ bool skip(int) const { return false; }
@@ -528,15 +513,19 @@ static inline int spmv_grid(const DevCsr &M, bool partials) {
 }
 // number of blocks a partial-emitting spmv launch uses (consumers need it)
 static inline int spmv_pgrid(const DevCsr &M) { return spmv_grid(M, true); }
-// KERNEL<M.tpr> on GRID blocks of BLK threads (further template arguments, such as k_spmv's Epi, are deduced from the arguments)
-#define DISPATCH_TPR(M, KERNEL, GRID, ...)                                                                  \
-    switch ((M).tpr) {                                                                                      \
-        case 4:  hipLaunchKernelGGL((KERNEL<4>),  dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        case 8:  hipLaunchKernelGGL((KERNEL<8>),  dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        case 16: hipLaunchKernelGGL((KERNEL<16>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        case 32: hipLaunchKernelGGL((KERNEL<32>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
-        default: hipLaunchKernelGGL((KERNEL<64>), dim3(GRID), dim3(BLK), 0, d->stream, __VA_ARGS__); break; \
+// grid of the row-loop kernels (TPR lanes per row, no partial sums: the diagonals and the per-pass counts) over a matrix laid out like M
+static inline int rowloop_grid(const DevCsr &M) { return M.use_slab ? 2048 : spmv_grid(M, false); }
+// KERNEL<M.tpr> on GRID blocks of BLK threads with LDS bytes of dynamic LDS (further template arguments, such as k_spmv's Epi, are
+// deduced from the arguments)
+#define DISPATCH_TPR_LDS(M, KERNEL, GRID, LDS, ...)                                                             \
+    switch ((M).tpr) {                                                                                          \
+        case 4:  hipLaunchKernelGGL((KERNEL<4>),  dim3(GRID), dim3(BLK), (LDS), d->stream, __VA_ARGS__); break; \
+        case 8:  hipLaunchKernelGGL((KERNEL<8>),  dim3(GRID), dim3(BLK), (LDS), d->stream, __VA_ARGS__); break; \
+        case 16: hipLaunchKernelGGL((KERNEL<16>), dim3(GRID), dim3(BLK), (LDS), d->stream, __VA_ARGS__); break; \
+        case 32: hipLaunchKernelGGL((KERNEL<32>), dim3(GRID), dim3(BLK), (LDS), d->stream, __VA_ARGS__); break; \
+        default: hipLaunchKernelGGL((KERNEL<64>), dim3(GRID), dim3(BLK), (LDS), d->stream, __VA_ARGS__); break; \
     }
+#define DISPATCH_TPR(M, KERNEL, GRID, ...) DISPATCH_TPR_LDS(M, KERNEL, GRID, 0, __VA_ARGS__)
 // (re)build the slab-major image of M from its row-major arrays and slab pointers
 static void slab_major_build(QpdoDev *d, const DevCsr &M);
 // One launch of the slab kernel K with what every such launch needs: the kernel's LDS limit (set once per kernel and host thread),
