@@ -259,6 +259,53 @@ long qpdo_amd_batch_stream_submit(QPDOAmdBatchStream *stream, long count, QPDOAm
 int  qpdo_amd_batch_stream_wait(QPDOAmdBatchStream *stream, long ticket, double *kernel_seconds);
 void qpdo_amd_batch_stream_destroy(QPDOAmdBatchStream *stream);
 
+/* ---- a resident FLEET of small QPs (closed-loop MPC: the matrices never change, every control step changes q and the bounds) -------
+ * A fleet is `count` small QPs set up ONCE and kept on the device.  Item i behaves bit for bit as a workspace of its own that
+ * received qpdo_setup(data[i], settings), then -- in the order the fleet calls were made -- qpdo_update_bounds for every fleet
+ * update that passed an l or u entry for it, qpdo_update_q for every fleet update that passed a q entry, qpdo_warm_start for every
+ * fleet warm start and qpdo_solve for every fleet solve, the reference's quirks included: a solve clears `initialized`, so a solve
+ * that no warm start precedes starts from zero (src/qpdo.c:312-314); qpdo_update_q recomputes the cost scaling c from the current x
+ * and Qx -- whatever the last solve or warm start left -- and rescales Q and Qx by c / c_old (src/qpdo.c:552-580); a solve that
+ * runs out of passes overwrites an UNSOLVED status only (src/qpdo.c:451-453).
+ * create   copies everything it needs (the caller's data may be freed afterwards), makes the only matrix upload the fleet ever
+ *          makes and scales every item on the device in one launch.  Every item must fit the fused kernel (n, m <= 1024 and the
+ *          matrix checks of qpdo_setup) and have l <= u; otherwise NULL with qpdo_amd_last_error() set and nothing left allocated.
+ *          The settings are FIXED at create: there is no qpdo_update_settings for a fleet, and no way to change matrix values.
+ * update   q, l, u: arrays of `count` pointers (q[i]: n_i values, l[i] / u[i]: m_i).  A NULL array leaves that kind of data unchanged
+ *          for all items, a NULL entry for that item.  Within one call the bounds are applied first, then q (the two commute in the
+ *          reference: bounds touch l, u and the row scaling E only).  An item whose l[i] and u[i] are both passed with l > u somewhere
+ *          makes the call fail before anything is written (the reference sets QPDO_ERROR on that workspace instead).
+ * warm_start       x0, y0 as for update; an item with a NULL entry (or array) starts that vector from zero, as qpdo_warm_start(work, NULL, ..).
+ * warm_start_last  in bits warm_start with the unscaled x and y the last solve returned for each item, taken from the device copy (no
+ *          host traffic); an item whose status after the last solve is -3, -4, -10 (never solved) or -99 is warm-started from zero.
+ * solve    ONE kernel launch for the whole fleet; uploads nothing.  Fills info[i] and, where x / y and their entries are non-NULL, the
+ *          solution (NaN for infeasible statuses, as the batch call does); returns when the results are on the host.
+ * Every call returns 0, or nonzero with qpdo_amd_last_error() set and the fleet as it was (checks precede every write).
+ * One thread at a time per fleet; different fleets are independent.  Not for row-partitioned setups; one fleet lives on one GPU
+ * (QPDO_DEVICE) -- the caller shards items over processes as for batches.
+ * Stats: vector_bytes_uploaded_last_call of an update or warm start = 8 bytes per vector element passed + a fixed table of
+ * QPDO_AMD_FLEET_TABLE_BYTES per item (the offsets of the item's vectors in the upload); 0 after warm_start_last. */
+#define QPDO_AMD_FLEET_TABLE_BYTES 16
+typedef struct QPDOAmdFleet_ QPDOAmdFleet;
+typedef struct {
+    long count;
+    long matrix_bytes_uploaded;             /* by create; never grows afterwards */
+    long vector_bytes_uploaded_last_call;   /* by the last update / warm_start / warm_start_last */
+    long solve_launches;                    /* kernel launches made by solve calls ... */
+    long solves;                            /* ... and the solve calls themselves */
+    double last_kernel_seconds;             /* HIP-event duration of the last solve's launch */
+} QPDOAmdFleetStats;
+QPDOAmdFleet *qpdo_amd_fleet_create(long count, const QPDOData *const *data, const QPDOSettings *settings);
+int  qpdo_amd_fleet_update(QPDOAmdFleet *f, const c_float *const *q, const c_float *const *l, const c_float *const *u);
+int  qpdo_amd_fleet_warm_start(QPDOAmdFleet *f, const c_float *const *x0, const c_float *const *y0);
+int  qpdo_amd_fleet_warm_start_last(QPDOAmdFleet *f);
+int  qpdo_amd_fleet_solve(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info);
+int  qpdo_amd_fleet_get_stats(const QPDOAmdFleet *f, QPDOAmdFleetStats *out);
+/* the infeasibility certificates of `item` from the last solve: prim_inf_cert (m values, meaningful at status -3), dual_inf_cert (n, at -4);
+ * either may be NULL */
+int  qpdo_amd_fleet_get_certificates(const QPDOAmdFleet *f, long item, c_float *prim_inf_cert, c_float *dual_inf_cert);
+void qpdo_amd_fleet_destroy(QPDOAmdFleet *f);
+
 #ifdef __cplusplus
 }
 #endif

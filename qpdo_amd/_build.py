@@ -134,15 +134,16 @@ def build_all(force=False, verbose=False):
     return build_gen(force), build_lib(force, verbose)
 
 
-def build_abi_driver(out_dir, sanitize=False):
-    """Compiles tests/abi_driver.c -- a plain-C caller that includes only include/qpdo.h -- and links it against the
+def build_abi_driver(out_dir, sanitize=False, driver="abi_driver.c"):
+    """Compiles tests/abi_driver.c -- a plain-C caller that includes only include/qpdo.h -- (or another stand-alone C caller under
+    tests/, `driver`) and links it against the
     product library.  sanitize=True: the host driver (qpdo_api.c, gcc) is rebuilt with -fsanitize=address,undefined and
     linked with the already compiled device objects into libqpdo_amd_asan.so inside out_dir (the product library in
     the tree is not touched); the driver is instrumented too.  Returns the path of the executable."""
     root = os.path.dirname(_HERE)
-    src = os.path.join(root, "tests", "abi_driver.c")
+    src = os.path.join(root, "tests", driver)
     os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "abi_driver_asan" if sanitize else "abi_driver")
+    exe = os.path.join(out_dir, os.path.splitext(driver)[0] + ("_asan" if sanitize else ""))
     if not sanitize:
         lib = ensure_lib()
         subprocess.check_call(["gcc", "-std=gnu11", "-O1", "-Wall", "-Werror", "-I", INCLUDE, src, "-o", exe,

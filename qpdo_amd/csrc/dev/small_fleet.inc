@@ -1,0 +1,308 @@
+// small_fleet.inc -- a resident FLEET of small QPs (qpdo_amd_fleet_*, include/qpdo_amd_ext.h; part of qpdo_small.hip's translation unit).
+// The many-item form of one small workspace: the matrices of all items are converted, uploaded and scaled ONCE (k_small_fleet_setup:
+// small_scale of the fused kernel, one workgroup per item); every item keeps a SmallRes record in device memory -- its scaling vectors,
+// its cost scaling c, the state vectors qpdo_warm_start leaves behind, x / Qx of the last solve -- and a control step is
+//   update      k_small_fleet_update   qpdo_update_bounds then qpdo_update_q of every item that has an entry (qpdo.c:522-586)
+//   warm start  k_small_fleet, op 1/2  the shared solve body in mode 1 (qpdo.c:217-299)
+//   solve       k_small_fleet, op 0    the shared solve body from the item's state (mode 2), or from zero (mode 0)
+// each ONE launch for the whole fleet, in the oracle's operation order: item i carries the bits of a workspace of its own.
+
+// Ruiz + cost scaling of every item, tpos, the state zeroed: what k_small_solve has after its own scaling phase, left in the item's arrays
+__global__ __launch_bounds__(SM_THREADS) void k_small_fleet_setup(SmallQP *probs, int count, QPDOSettings st) {
+    __shared__ double sm[32];
+    if ((int)blockIdx.x >= count) return;
+    SmallQP &Pg = probs[blockIdx.x];
+    SmallQP P = Pg;
+    SmallRes *R = Pg.res;
+    const int n = P.n, m = P.m;
+    small_build_tpos(P);
+    FOR_T(j, n) { R->state_x[j] = 0.0; R->state_Qx[j] = 0.0; R->st_xbar[j] = 0.0; R->st_Aty[j] = 0.0; }
+    FOR_T(i, m) { R->st_y[i] = 0.0; R->st_ybar[i] = 0.0; R->st_Ax[i] = 0.0; R->st_mu[i] = 0.0; R->st_isq[i] = 0.0; }
+    SYNC;
+    double c = 1.0, cinv = 1.0;
+    if (st.scaling > 0)
+        small_scale(P, (int)st.scaling, const_cast<double *>(R->rD), const_cast<double *>(R->rDinv), const_cast<double *>(R->rE), const_cast<double *>(R->rEinv),
+                    P.nv + (size_t)NV_T * n, P.mv + (size_t)MV_T * m, c, cinv, sm);
+    if (threadIdx.x == 0) {
+        R->r_c = c; R->r_cinv = cinv; R->mode = 0; R->sigma_end = st.sigma_init; R->tau_end = 0.0; R->ws_objective = 0.0;
+        R->fleet_status = QPDO_UNSOLVED;
+        small_status(Pg.info, QPDO_UNSOLVED);
+    }
+}
+// qpdo_update_bounds (qpdo.c:522-544), then qpdo_update_q (qpdo.c:549-586) of item i when tab[4 i + 1] / [4 i + 2] (l, u) or tab[4 i] (q) name
+// an offset into `stage` (-1: no entry).  The two commute: bounds touch l, u and read E only.  The c / c_old rescale of Q's values and of Qx, the
+// exact inf-norm and every product in the oracle's order (oracle_update_q).
+__global__ __launch_bounds__(SM_THREADS) void k_small_fleet_update(SmallQP *probs, int count, QPDOSettings st, const int *tab, const double *stage) {
+    __shared__ double sm[32];
+    if ((int)blockIdx.x >= count) return;
+    const int oq = __builtin_amdgcn_readfirstlane(tab[4 * blockIdx.x]), ol = __builtin_amdgcn_readfirstlane(tab[4 * blockIdx.x + 1]),
+              ou = __builtin_amdgcn_readfirstlane(tab[4 * blockIdx.x + 2]);
+    if (oq < 0 && ol < 0 && ou < 0) return;
+    SmallQP &Pg = probs[blockIdx.x];
+    SmallRes *R = Pg.res;
+    const int n = Pg.n, m = Pg.m;
+    const int scaled = st.scaling > 0, prox = (int)st.proximal;
+    const double *E = R->rE, *D = R->rD;
+    if (ol >= 0) { const double *ln = stage + ol; double *l = Pg.l; FOR_T(i, m) l[i] = scaled ? E[i] * ln[i] : ln[i]; }
+    if (ou >= 0) { const double *un = stage + ou; double *u = Pg.u; FOR_T(i, m) u[i] = scaled ? E[i] * un[i] : un[i]; }
+    if (oq < 0) return;
+    const double *qn = stage + oq;
+    double *q = Pg.q, *x = R->state_x, *Qx = R->state_Qx;
+    if (!scaled) { FOR_T(j, n) q[j] = qn[j]; return; }
+    const double c_old = R->r_c, cinv_old = R->r_cinv, sigma = R->sigma_end;
+    double mx = 0.0;
+    FOR_T(j, n) {                                    // (entry j of every vector belongs to this thread throughout)
+        const double qj = D[j] * qn[j];
+        q[j] = qj;
+        double qx = Qx[j];
+        if (prox) { qx = qx + (-sigma) * x[j]; Qx[j] = qx; }
+        const double t = s_abs(qj + cinv_old * qx);
+        mx = t > mx ? t : mx;
+    }
+    const double nrm = blk_max(mx, sm);              // (its barriers: every thread has read c_old before lane 0 writes the new one)
+    const double c = 1 / s_max(1.0, nrm), cinv = 1 / c;
+    const double f = c / c_old;
+    FOR_T(j, n) {
+        q[j] *= c;
+        double qx = Qx[j] * f;
+        if (prox) qx = qx + st.sigma_init * x[j];
+        Qx[j] = qx;
+    }
+    const int nnzQ = Pg.Qrp[n];
+    double *Qval = Pg.Qval;
+    FOR_T(k, nnzQ) Qval[k] *= f;
+    if (threadIdx.x == 0) { R->r_c = c; R->r_cinv = cinv; if (prox) R->sigma_end = st.sigma_init; }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+struct FleetItem { int n, m; size_t o_q, o_l, o_u, o_solx, o_soly, o_dx, o_dy, out_off; };
+struct SmallFleet {
+    int device = 0; long count = 0; QPDOSettings st;
+    hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    char *arena = nullptr;                          // [matrices + q, l, u of all items][outputs of all items][records' vectors][scratch]
+    SmallQP *dprobs = nullptr; SmallRes *dres = nullptr;
+    double *dstage = nullptr; int *dtab = nullptr;  // a call's vectors and its per-item table (QPDO_AMD_FLEET_TABLE_BYTES each)
+    char *hstage = nullptr; size_t stage_doubles = 0;       // pinned: [vectors][table]
+    char *hout = nullptr; size_t out_off = 0, out_bytes = 0;  // pinned image of the outputs
+    SmallQP *hp = nullptr;                          // pinned image of the descriptors (info comes back in them)
+    std::vector<FleetItem> it;
+    size_t lds = 0; int kflags = 0;
+    long matrix_bytes = 0, vector_bytes_last = 0, solve_launches = 0, solves = 0; double kernel_s = 0.0;
+    bool solved = false;
+};
+static void fleet_free(SmallFleet *F) {
+    if (!F) return;
+    (void)hipSetDevice(F->device);
+    if (F->stream) (void)hipStreamSynchronize(F->stream);
+    if (F->arena) (void)hipFree(F->arena);
+    if (F->dprobs) (void)hipFree(F->dprobs);
+    if (F->dres) (void)hipFree(F->dres);
+    if (F->dstage) (void)hipFree(F->dstage);
+    if (F->hstage) (void)hipHostFree(F->hstage);
+    if (F->hout) (void)hipHostFree(F->hout);
+    if (F->hp) (void)hipHostFree(F->hp);
+    if (F->ev0) (void)hipEventDestroy(F->ev0);
+    if (F->ev1) (void)hipEventDestroy(F->ev1);
+    if (F->stream) (void)hipStreamDestroy(F->stream);
+    delete F;
+}
+
+extern "C" {
+
+void qdev_small_fleet_destroy(void *h) { fleet_free((SmallFleet *)h); }
+
+// data: `count` QPDOData pointers, every item already checked (qdev_small_eligible, validate_data).  Converts, uploads and scales; NULL on
+// failure with qdev_small_last_error() set and nothing left allocated.
+void *qdev_small_fleet_create(int device, long count, const void *const *data_, const void *settings_) {
+    int rc = 0;
+    const QPDOData *const *data = (const QPDOData *const *)data_;
+    SmallFleet *F = new SmallFleet();
+    F->device = device; F->count = count; F->st = *(const QPDOSettings *)settings_;
+    F->it.resize((size_t)count);
+    std::vector<Lay> lay((size_t)count);
+    std::vector<SmallQP> hp((size_t)count);
+    std::vector<SmallRes> hr((size_t)count);
+    std::vector<size_t> o_rec((size_t)count);
+    char *h = nullptr;
+    size_t total = 0, nmax = 1, mmax = 0, stage = 0;
+    auto reserve = [&](size_t bytes) { size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; };
+    parallel_items(count, [&](long i) { const QPDOData *d = data[i]; Lay &L = lay[(size_t)i]; L.nnzA = (size_t)idx_at(d->A->p, d->A->itype, (long long)d->A->ncol); L.nnzQ = (size_t)sym_full_nnz(d->Q); });
+    for (long i = 0; i < count; i++) {
+        const QPDOData *d = data[i]; Lay &L = lay[(size_t)i];
+        const size_t n = d->n, m = d->m;
+        lay_inputs(L, n, m, reserve);
+        if (n > nmax) nmax = n;
+        if (m > mmax) mmax = m;
+        stage += n + 2 * m;                          // the largest call: q, l and u of every item
+    }
+    // (a call's table holds 32-bit offsets, in doubles, into the staging of the whole fleet)
+    if (stage >= 2147483647ULL) { snprintf(s_err, sizeof(s_err), "fleet: %zu vector elements per call exceed the 2^31 the call table can address; split the fleet", stage); delete F; return nullptr; }
+    const size_t upload_bytes = total;
+    for (long i = 0; i < count; i++) {
+        const QPDOData *d = data[i]; Lay &L = lay[(size_t)i];
+        lay_outputs(L, d->n, d->m, reserve);
+    }
+    const size_t out_bytes = total - upload_bytes;
+    for (long i = 0; i < count; i++) {
+        const QPDOData *d = data[i]; Lay &L = lay[(size_t)i];
+        const size_t n = d->n, m = d->m;
+        o_rec[(size_t)i] = reserve((6 * n + 7 * m) * 8 + 8);          // D, Dinv, x, Qx, xbar, A'y | E, Einv, y, ybar, Ax, mu, 1/sqrt(mu)
+        lay_scratch(L, n, m, reserve);
+    }
+    SHIP(hipSetDevice(device));
+    SHIP(hipStreamCreateWithFlags(&F->stream, hipStreamNonBlocking));
+    SHIP(hipEventCreate(&F->ev0)); SHIP(hipEventCreate(&F->ev1));
+    SHIP(hipMalloc((void **)&F->arena, total));
+    SHIP(hipMalloc((void **)&F->dprobs, (size_t)count * sizeof(SmallQP)));
+    SHIP(hipMalloc((void **)&F->dres, (size_t)count * sizeof(SmallRes)));
+    F->stage_doubles = stage;
+    SHIP(hipMalloc((void **)&F->dstage, stage * 8 + (size_t)count * QPDO_AMD_FLEET_TABLE_BYTES + 16));
+    F->dtab = (int *)(F->dstage + stage);
+    SHIP(hipHostMalloc((void **)&F->hstage, stage * 8 + (size_t)count * QPDO_AMD_FLEET_TABLE_BYTES + 16, hipHostMallocDefault));
+    SHIP(hipHostMalloc((void **)&F->hout, out_bytes ? out_bytes : 1, hipHostMallocDefault));
+    SHIP(hipHostMalloc((void **)&F->hp, (size_t)count * sizeof(SmallQP), hipHostMallocDefault));
+    F->out_off = upload_bytes; F->out_bytes = out_bytes;
+    h = (char *)calloc(upload_bytes ? upload_bytes : 1, 1);
+    if (!h) { snprintf(s_err, sizeof(s_err), "fleet: host staging allocation failed"); rc = -1; goto done; }
+    parallel_items(count, [&](long i) {              // the conversions of slot_submit, straight into the staging image
+        static thread_local ConvScratch W;
+        lay_convert(data[i], lay[(size_t)i], h, W);
+    });
+    SHIP(hipMemcpyAsync(F->arena, h, upload_bytes, hipMemcpyHostToDevice, F->stream));     // the only matrix upload the fleet ever makes
+    F->matrix_bytes = (long)upload_bytes;
+    {
+        int klds = 0; size_t ub = 0;
+        F->lds = small_lds_bytes(nmax, mmax, &klds, &ub, true);
+        if (!klds) F->lds = small_lds_bytes(nmax, mmax, nullptr, &ub, false);      // the factor in global memory: no look-ahead, one set of column buffers (fits up to n = m = 1024)
+        F->kflags = klds | ((int)(ub / 8) << 1);
+        // the work vectors beside the factor in LDS when both fit (as a batch through the latency kernel has them)
+        size_t voff, vbytes;
+        small_vec_lds(F->lds, nmax, mmax, &voff, &vbytes);
+        const unsigned vec_off = (klds && voff + vbytes <= SMALL_LDS_BUDGET) ? (unsigned)voff : 0u;
+        if (vec_off) F->lds = voff + vbytes;
+        char *dbase = F->arena;
+        for (long i = 0; i < count; i++) {
+            const QPDOData *d = data[i]; Lay &L = lay[(size_t)i]; SmallQP &p = hp[(size_t)i]; SmallRes &r = hr[(size_t)i]; FleetItem &I = F->it[(size_t)i];
+            const size_t n = d->n, m = d->m;
+            lay_describe(p, d, L, dbase); memset(&r, 0, sizeof(r));
+            p.res = F->dres + i;
+            double *v = (double *)(dbase + o_rec[(size_t)i]);
+            double *D = v, *Dinv = D + n, *sx = Dinv + n, *sQx = sx + n, *sxb = sQx + n, *sAty = sxb + n;
+            double *E = sAty + n, *Einv = E + m, *sy = Einv + m, *syb = sy + m, *sAx = syb + m, *smu = sAx + m, *sisq = smu + m;
+            r.rD = D; r.rDinv = Dinv; r.rE = E; r.rEinv = Einv; r.r_c = 1.0; r.r_cinv = 1.0;
+            r.state_x = sx; r.state_Qx = sQx; r.st_xbar = sxb; r.st_Aty = sAty; r.st_y = sy; r.st_ybar = syb; r.st_Ax = sAx; r.st_mu = smu; r.st_isq = sisq;
+            r.lds_vec_off = vec_off; r.fleet_status = QPDO_UNSOLVED;
+            I.n = (int)n; I.m = (int)m; I.o_solx = L.solx - upload_bytes; I.o_soly = L.soly - upload_bytes; I.o_dx = L.dx - upload_bytes; I.o_dy = L.dy - upload_bytes;
+        }
+    }
+    SHIP(hipMemcpyAsync(F->dprobs, hp.data(), (size_t)count * sizeof(SmallQP), hipMemcpyHostToDevice, F->stream));
+    SHIP(hipMemcpyAsync(F->dres, hr.data(), (size_t)count * sizeof(SmallRes), hipMemcpyHostToDevice, F->stream));
+    SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
+    hipLaunchKernelGGL(k_small_fleet_setup, dim3((unsigned)count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)count, F->st);
+    SHIP(hipGetLastError());
+    SHIP(hipStreamSynchronize(F->stream));           // (the pageable staging images above are read until here)
+done:
+    free(h);
+    if (rc) { fleet_free(F); return nullptr; }
+    return F;
+}
+
+// q, l, u: arrays of `count` pointers or NULL; entries may be NULL.  Checked by the caller (qpdo_api.c): l <= u where both are passed.
+int qdev_small_fleet_update(void *h_, const double *const *q, const double *const *l, const double *const *u) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    double *hs = (double *)F->hstage; int *ht = (int *)(hs + F->stage_doubles);
+    size_t off = 0;
+    for (long i = 0; i < F->count; i++) {
+        const size_t n = (size_t)F->it[(size_t)i].n, m = (size_t)F->it[(size_t)i].m;
+        int *t = ht + 4 * i;
+        t[0] = t[1] = t[2] = -1; t[3] = 0;
+        if (q && q[i]) { t[0] = (int)off; memcpy(hs + off, q[i], n * 8); off += n; }
+        if (l && l[i]) { t[1] = (int)off; if (m) memcpy(hs + off, l[i], m * 8); off += m; }
+        if (u && u[i]) { t[2] = (int)off; if (m) memcpy(hs + off, u[i], m * 8); off += m; }
+    }
+    SHIP(hipSetDevice(F->device));
+    if (off) SHIP(hipMemcpyAsync(F->dstage, hs, off * 8, hipMemcpyHostToDevice, F->stream));
+    SHIP(hipMemcpyAsync(F->dtab, ht, (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES, hipMemcpyHostToDevice, F->stream));
+    hipLaunchKernelGGL(k_small_fleet_update, dim3((unsigned)F->count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)F->count, F->st, (const int *)F->dtab, (const double *)F->dstage);
+    SHIP(hipGetLastError());
+    SHIP(hipStreamSynchronize(F->stream));           // (the pinned staging is free for the next call)
+    F->vector_bytes_last = (long)(off * 8 + (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES);
+done:
+    return rc;
+}
+// last = 1: every item from the x, y its last solve returned (device copies; zero where that solve left no finite solution)
+int qdev_small_fleet_warm_start(void *h_, const double *const *x0, const double *const *y0, int last) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    double *hs = (double *)F->hstage; int *ht = (int *)(hs + F->stage_doubles);
+    size_t off = 0;
+    SHIP(hipSetDevice(F->device));
+    if (!last) {
+        for (long i = 0; i < F->count; i++) {
+            const size_t n = (size_t)F->it[(size_t)i].n, m = (size_t)F->it[(size_t)i].m;
+            int *t = ht + 4 * i;
+            t[0] = t[1] = t[2] = -1; t[3] = 0;
+            if (x0 && x0[i]) { t[0] = (int)off; memcpy(hs + off, x0[i], n * 8); off += n; }
+            if (y0 && y0[i]) { t[1] = (int)off; if (m) memcpy(hs + off, y0[i], m * 8); off += m; }
+        }
+        if (off) SHIP(hipMemcpyAsync(F->dstage, hs, off * 8, hipMemcpyHostToDevice, F->stream));
+        SHIP(hipMemcpyAsync(F->dtab, ht, (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES, hipMemcpyHostToDevice, F->stream));
+    }
+    hipLaunchKernelGGL(k_small_fleet, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, F->stream, F->dprobs, (int)F->count, F->st, F->kflags, last ? 2 : 1,
+                       (const int *)F->dtab, (const double *)F->dstage);
+    SHIP(hipGetLastError());
+    SHIP(hipStreamSynchronize(F->stream));
+    F->vector_bytes_last = last ? 0 : (long)(off * 8 + (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES);
+done:
+    return rc;
+}
+// ONE launch for the whole fleet; x, y: arrays of `count` pointers or NULL (entries may be NULL), info: `count` QPDOInfo
+int qdev_small_fleet_solve(void *h_, double *const *x, double *const *y, void *info_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    QPDOInfo *info = (QPDOInfo *)info_;
+    SHIP(hipSetDevice(F->device));
+    SHIP(hipEventRecord(F->ev0, F->stream));
+    hipLaunchKernelGGL(k_small_fleet, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, F->stream, F->dprobs, (int)F->count, F->st, F->kflags, 0,
+                       (const int *)F->dtab, (const double *)F->dstage);
+    SHIP(hipGetLastError());
+    SHIP(hipEventRecord(F->ev1, F->stream));
+    F->solve_launches++;
+    SHIP(hipMemcpyAsync(F->hp, F->dprobs, (size_t)F->count * sizeof(SmallQP), hipMemcpyDeviceToHost, F->stream));
+    if (F->out_bytes) SHIP(hipMemcpyAsync(F->hout, F->arena + F->out_off, F->out_bytes, hipMemcpyDeviceToHost, F->stream));
+    SHIP(hipStreamSynchronize(F->stream));
+    { float ms = 0.f; if (hipEventElapsedTime(&ms, F->ev0, F->ev1) == hipSuccess) F->kernel_s = (double)ms * 1e-3; }
+    F->solves++; F->solved = true;
+    parallel_items(F->count, [&](long i) {
+        const FleetItem &I = F->it[(size_t)i];
+        if (info) info[i] = F->hp[(size_t)i].info;
+        const long stv = F->hp[(size_t)i].info.status_val;
+        const bool infeasible = (stv == QPDO_PRIMAL_INFEASIBLE) || (stv == QPDO_DUAL_INFEASIBLE);
+        const double *sx = (const double *)(F->hout + I.o_solx), *sy = (const double *)(F->hout + I.o_soly);
+        if (x && x[i]) for (int k = 0; k < I.n; k++) x[i][k] = infeasible ? NAN : sx[k];
+        if (y && y[i]) for (int k = 0; k < I.m; k++) y[i][k] = infeasible ? NAN : sy[k];
+    });
+done:
+    return rc;
+}
+// the certificates of the last solve as the kernel left them (host image): dy (m) of a primal infeasible item, dx (n) of a dual infeasible one
+int qdev_small_fleet_certificates(const void *h_, long item, double *prim_inf_cert, double *dual_inf_cert) {
+    const SmallFleet *F = (const SmallFleet *)h_;
+    if (!F->solved) { snprintf(s_err, sizeof(s_err), "fleet: no solve yet"); return -1; }
+    const FleetItem &I = F->it[(size_t)item];
+    if (prim_inf_cert && I.m) memcpy(prim_inf_cert, F->hout + I.o_dy, (size_t)I.m * 8);
+    if (dual_inf_cert) memcpy(dual_inf_cert, F->hout + I.o_dx, (size_t)I.n * 8);
+    return 0;
+}
+void qdev_small_fleet_stats(const void *h_, long *out5, double *kernel_s) {
+    const SmallFleet *F = (const SmallFleet *)h_;
+    out5[0] = F->count; out5[1] = F->matrix_bytes; out5[2] = F->vector_bytes_last; out5[3] = F->solve_launches; out5[4] = F->solves;
+    *kernel_s = F->kernel_s;
+}
+void qdev_small_fleet_dims(const void *h_, long item, int *n, int *m) {
+    const SmallFleet *F = (const SmallFleet *)h_;
+    *n = F->it[(size_t)item].n; *m = F->it[(size_t)item].m;
+}
+
+}  // extern "C"

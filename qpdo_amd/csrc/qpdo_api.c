@@ -1188,3 +1188,87 @@ int qpdo_amd_batch_stream_wait(QPDOAmdBatchStream *stream, long ticket, double *
     return rc;
 }
 void qpdo_amd_batch_stream_destroy(QPDOAmdBatchStream *stream) { qdev_small_stream_destroy(stream); }
+
+/* ---- a resident fleet of small QPs: see include/qpdo_amd_ext.h.  Argument checks here (they precede every write and need no device),
+ * the work in qdev_small_fleet_* (qpdo_small.hip) ------------------------------------------------------------------------------- */
+static int fleet_refuse(const char *msg) { qdev_set_error(msg); return -1; }
+QPDOAmdFleet *qpdo_amd_fleet_create(long count, const QPDOData *const *data, const QPDOSettings *settings) {
+    if (count <= 0) { fleet_refuse("qpdo_amd_fleet_create: count must be positive"); return NULL; }
+    if (!data) { fleet_refuse("qpdo_amd_fleet_create: NULL data array"); return NULL; }
+    if (!settings) { fleet_refuse("qpdo_amd_fleet_create: NULL settings"); return NULL; }
+    if (!validate_settings(settings)) { fleet_refuse("qpdo_amd_fleet_create: invalid settings"); return NULL; }
+    for (long i = 0; i < count; i++) {
+        char msg[160];
+        QPDOAmdBatchItem it;
+        memset(&it, 0, sizeof(it));
+        it.data = data[i];
+        if (!data[i] || !qdev_small_eligible(1, &it)) {
+            snprintf(msg, sizeof(msg), "qpdo_amd_fleet_create: item %ld does not fit the fused kernel (n, m <= 1024, the matrix checks of qpdo_setup)", i);
+            fleet_refuse(msg); return NULL;
+        }
+        for (size_t j = 0; j < data[i]->m; j++)          /* (validate.c:20-28; the pointers were checked by qdev_small_eligible) */
+            if (data[i]->l[j] > data[i]->u[j]) {
+                snprintf(msg, sizeof(msg), "qpdo_amd_fleet_create: item %ld has a lower bound above its upper bound (index %ld)", i, (long)j);
+                fleet_refuse(msg); return NULL;
+            }
+    }
+    const int ndev = qdev_device_count();
+    if (ndev <= 0) { fleet_refuse("qpdo_amd_fleet_create: no HIP device available (this library has no CPU path)"); return NULL; }
+    const int device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
+    void *f = qdev_small_fleet_create(device, count, (const void *const *)data, settings);
+    if (!f) { char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_create: %s", qdev_small_last_error()); fleet_refuse(msg); }
+    return (QPDOAmdFleet *)f;
+}
+int qpdo_amd_fleet_update(QPDOAmdFleet *f, const c_float *const *q, const c_float *const *l, const c_float *const *u) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_update: NULL fleet");
+    long st[5]; double ks;
+    qdev_small_fleet_stats(f, st, &ks);
+    if (l && u)
+        for (long i = 0; i < st[0]; i++) {
+            if (!l[i] || !u[i]) continue;
+            int n, m;
+            qdev_small_fleet_dims(f, i, &n, &m);
+            for (int j = 0; j < m; j++)
+                if (l[i][j] > u[i][j]) {
+                    char msg[160];
+                    snprintf(msg, sizeof(msg), "qpdo_amd_fleet_update: item %ld: lower bound at index %d is greater than upper bound", i, j);
+                    return fleet_refuse(msg);
+                }
+        }
+    if (qdev_small_fleet_update(f, q, l, u)) { char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_update: %s", qdev_small_last_error()); return fleet_refuse(msg); }
+    return 0;
+}
+int qpdo_amd_fleet_warm_start(QPDOAmdFleet *f, const c_float *const *x0, const c_float *const *y0) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_warm_start: NULL fleet");
+    if (qdev_small_fleet_warm_start(f, x0, y0, 0)) { char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_warm_start: %s", qdev_small_last_error()); return fleet_refuse(msg); }
+    return 0;
+}
+int qpdo_amd_fleet_warm_start_last(QPDOAmdFleet *f) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_warm_start_last: NULL fleet");
+    if (qdev_small_fleet_warm_start(f, NULL, NULL, 1)) { char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_warm_start_last: %s", qdev_small_last_error()); return fleet_refuse(msg); }
+    return 0;
+}
+int qpdo_amd_fleet_solve(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_solve: NULL fleet");
+    if (!info) return fleet_refuse("qpdo_amd_fleet_solve: NULL info array");
+    if (qdev_small_fleet_solve(f, x, y, info)) { char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_solve: %s", qdev_small_last_error()); return fleet_refuse(msg); }
+    return 0;
+}
+int qpdo_amd_fleet_get_stats(const QPDOAmdFleet *f, QPDOAmdFleetStats *out) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_get_stats: NULL fleet");
+    if (!out) return fleet_refuse("qpdo_amd_fleet_get_stats: NULL output");
+    long st[5]; double ks;
+    qdev_small_fleet_stats(f, st, &ks);
+    out->count = st[0]; out->matrix_bytes_uploaded = st[1]; out->vector_bytes_uploaded_last_call = st[2];
+    out->solve_launches = st[3]; out->solves = st[4]; out->last_kernel_seconds = ks;
+    return 0;
+}
+int qpdo_amd_fleet_get_certificates(const QPDOAmdFleet *f, long item, c_float *prim_inf_cert, c_float *dual_inf_cert) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_get_certificates: NULL fleet");
+    long st[5]; double ks;
+    qdev_small_fleet_stats(f, st, &ks);
+    if (item < 0 || item >= st[0]) return fleet_refuse("qpdo_amd_fleet_get_certificates: item out of range");
+    if (qdev_small_fleet_certificates(f, item, prim_inf_cert, dual_inf_cert)) return fleet_refuse("qpdo_amd_fleet_get_certificates: no solve yet");
+    return 0;
+}
+void qpdo_amd_fleet_destroy(QPDOAmdFleet *f) { if (f) qdev_small_fleet_destroy(f); }

@@ -80,6 +80,9 @@ struct SmallRes {
     double *out_x, *out_y;                   // out: the internal (scaled) iterates, the host mirrors work->x / work->y (y after termination.c:85)
     QPDOAmdTraceRec *trace; long trace_cap, ntrace;      // optional per-pass trace (pinned host memory), records written / capacity
     double sigma_end, tau_end;
+    // a FLEET item's record only (k_small_fleet*, dev/small_fleet.inc; appended: the members above keep their offsets): the status a workspace's
+    // info would carry after the last solve (qpdo.c:451-453: a solve that runs out of passes overwrites an UNSOLVED status only)
+    long fleet_status;
 };
 enum { NV_X = 0, NV_XBAR, NV_QX, NV_ATY, NV_DF, NV_RD, NV_RDI, NV_RHS, NV_DX, NV_QDX, NV_ATDY, NV_D, NV_DINV, NV_T, NV_COUNT };
 enum { MV_Y = 0, MV_YBAR, MV_AX, MV_MU, MV_ISQ, MV_W, MV_RP, MV_RPOLD, MV_RPI, MV_DY, MV_ADX, MV_DW, MV_E, MV_EINV, MV_ATS, MV_T, MV_DWF, MV_COUNT };
@@ -1106,8 +1109,13 @@ __device__ __forceinline__ T *uni_ptr(T *p) {
 // LAT = 0: the batch kernel (held to 128 VGPRs so that two workgroups share a CU); LAT = 1: the latency variant for ONE workspace
 // (qdev_small_resident_solve): the same code with the whole register file of a CU's SIMDs to itself (no spills) -- same operations
 // in the same order, so the same bits.
-template <int LAT>
-__device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, const QPDOSettings &st, int kflags) {
+// FLEET = 1 (with LAT = 1): the items are a resident fleet (dev/small_fleet.inc) -- every item has a SmallRes record in device memory, tpos
+// was built and the data scaled by the fleet's setup launch, and the launch is either a warm start of all items (fleet_op 1: x0 / y0 at the
+// offsets fleet_tab[4 i], [4 i + 1] of fleet_stage, -1: none; fleet_op 2: the item's last solution) or the solve (fleet_op 0) from the
+// item's state (mode 2) or, when no warm start came since the last solve, from zero (mode 0, qpdo.c:312-314).
+template <int LAT, int FLEET = 0>
+__device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, const QPDOSettings &st, int kflags, int fleet_op = 0,
+                                                 const int *fleet_tab = nullptr, const double *fleet_stage = nullptr) {
     const int klds_ok = kflags & 1, ucap = kflags >> 1;          // bit 0: the packed factor lives in LDS; the rest: doubles in the union region U
     __shared__ double sm[32];
     __shared__ double red_scr[64];                    // two banks of reduction partials (RedBank)
@@ -1140,6 +1148,17 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
             state_x = uni_ptr(Rg->state_x); state_Qx = uni_ptr(Rg->state_Qx); trace = uni_ptr(Rg->trace); trace_cap = Rg->trace_cap;
             out_x = uni_ptr(Rg->out_x); out_y = uni_ptr(Rg->out_y);
             mode = __builtin_amdgcn_readfirstlane(Rg->mode);
+            if constexpr (FLEET) {
+                P.x0 = nullptr; P.y0 = nullptr;
+                if (fleet_op == 1) {
+                    const int ox = __builtin_amdgcn_readfirstlane(fleet_tab[4 * blockIdx.x]), oy = __builtin_amdgcn_readfirstlane(fleet_tab[4 * blockIdx.x + 1]);
+                    mode = 1; if (ox >= 0) P.x0 = fleet_stage + ox; if (oy >= 0) P.y0 = fleet_stage + oy;
+                } else if (fleet_op == 2) {       // the unscaled x, y the last solve returned, if it returned finite ones
+                    const long fs = Rg->fleet_status;
+                    const int fin = __builtin_amdgcn_readfirstlane((int)!(fs == QPDO_PRIMAL_INFEASIBLE || fs == QPDO_DUAL_INFEASIBLE || fs == QPDO_UNSOLVED || fs == QPDO_ERROR));
+                    mode = 1; if (fin) { P.x0 = P.sol_x; P.y0 = P.sol_y; }
+                }
+            }
             // One workspace has the CU to itself: its ~30 work vectors move from global memory (L2-resident, but every barrier that follows a
             // vector update waits for the stores' round trip) into LDS when they fit beside the factor.  Same operations on the same values.
         }
@@ -1168,7 +1187,7 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
            *res_prim_old = V[MV_RPOLD], *res_prim_in = V[MV_RPI], *dy = V[MV_DY], *Adx = V[MV_ADX], *dw = V[MV_DW], *E = V[MV_E],
            *Einv = V[MV_EINV], *ats = V[MV_ATS], *tm = V[MV_T], *dwf = V[MV_DWF];
     int *active = P.iv, *active_old = P.iv + m, *changed = P.iv + 2 * m;
-    double *xs = dyn, *colbuf = dyn + n, *tk = dyn + 2 * (size_t)n, *gbuf = dyn + (LAT ? 16 : 8) * (size_t)n;   // dyn .. dyn + 8n: l and l*d of four columns during a factorization; the latency kernel: two such buffers (look-ahead)
+    double *xs = dyn, *colbuf = dyn + n, *tk = dyn + 2 * (size_t)n, *gbuf = dyn + ((LAT && !(FLEET && !klds_ok)) ? 16 : 8) * (size_t)n;   // dyn .. dyn + 8n: l and l*d of four columns during a factorization; the latency kernel: two such buffers (look-ahead; a fleet whose factor is not in LDS has no look-ahead: one)
     double *d_s = gbuf + (((size_t)(n > m ? n : m) / 4 + 4 + 1) & ~(size_t)1);
     int *rp_s = (int *)(d_s + m);
     double *Klds = (double *)(rp_s + (((size_t)m + 1 + 3) & ~(size_t)3));          // start of U
@@ -1182,7 +1201,7 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
     double sc_c = 1.0, sc_cinv = 1.0;
 
     FOR_T(r, m + 1) rp_s[r] = P.Arp[r];
-    small_build_tpos(P);
+    if constexpr (!FLEET) small_build_tpos(P);
     // ---- setup: workspace zero + scaling (qpdo.c:49-212) ----
     FOR_T(i, NV_COUNT * n) P.nv[i] = 0.0;
     FOR_T(i, MV_COUNT * m) P.mv[i] = 0.0;
@@ -1242,6 +1261,7 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
             double obj = small_objective(n, prox, sigma, Qx, x, P.q);     // qpdo.c:257 (compute_objective on the warm-started x)
             if (scaled) obj *= sc_cinv;
             Rg->ws_objective = obj + P.c_const;
+            if constexpr (FLEET) { Rg->mode = 2; Rg->sigma_end = sigma; }      // initialized: the next solve starts from this state
         }
         return;
     }
@@ -1530,7 +1550,10 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
     FOR_T(i, m) { if (scaled) { const double v = y[i] * sc_cinv; y[i] = v; P.sol_y[i] = v * E[i]; } else P.sol_y[i] = y[i]; }
     FOR_T(j, n) P.cert_dx[j] = dx[j];
     FOR_T(i, m) P.cert_dy[i] = dy[i];
-    if (LAT && state_x) { FOR_T(j, n) { state_x[j] = x[j]; state_Qx[j] = Qx[j]; out_x[j] = x[j]; } FOR_T(i, m) out_y[i] = y[i]; }
+    if (LAT && state_x) {
+        FOR_T(j, n) { state_x[j] = x[j]; state_Qx[j] = Qx[j]; if constexpr (!FLEET) out_x[j] = x[j]; }
+        if constexpr (!FLEET) { FOR_T(i, m) out_y[i] = y[i]; }
+    }
     SYNC;
     if (threadIdx.x == 0) {
         double obj = small_objective(n, prox, sigma, Qx, x, P.q);
@@ -1543,7 +1566,12 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
         Pg.info.setup_time = (double)(t_solve - t_begin) * 1e-8;          // scaling + warm start + initialize_mu of this item
         Pg.info.solve_time = (double)(t_end - t_solve) * 1e-8;
         Pg.info.run_time = Pg.info.setup_time + Pg.info.solve_time;
-        small_status(Pg.info, status);
+        if constexpr (FLEET) {
+            long fs = Rg->fleet_status;
+            if (status != QPDO_MAX_ITER_REACHED || fs == QPDO_UNSOLVED) fs = status;
+            Rg->fleet_status = fs; Rg->mode = 0;                                // (qpdo.c:455: the solve clears `initialized`)
+            small_status(Pg.info, fs);
+        } else small_status(Pg.info, status);
         Pg.newton_passes = newton; Pg.factor_count = nfactor; (void)nrestore;
         if constexpr (LAT) {
             if (Rg) {
@@ -1558,6 +1586,10 @@ __global__ __launch_bounds__(SM_THREADS, 4) void k_small_solve(SmallQP *probs, i
 }
 __global__ __launch_bounds__(SM_THREADS, 2) void k_small_solve_lat(SmallQP *probs, int count, QPDOSettings st, int klds_ok) {
     small_solve_body<1>(probs, count, st, klds_ok);
+}
+// the fleet's instantiation of the same body (latency shape): warm start (op 1, 2) or solve (op 0) of every item
+__global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet(SmallQP *probs, int count, QPDOSettings st, int kflags, int op, const int *tab, const double *stage) {
+    small_solve_body<1, 1>(probs, count, st, kflags, op, tab, stage);
 }
 
 // ================================================================================================
@@ -1634,6 +1666,46 @@ static void sym_full32_raw(const cholmod_sparse *Q, int *rp, int *ci, double *va
 // batch i still run: a launch is as slow as its slowest item (an instance that never reaches eps runs max_iter passes on one
 // workgroup), and with one batch at a time the other CUs idle behind it.
 struct Lay { size_t Arp, Aci, Aval, Trp, Tci, Tval, Qrp, Qci, Qval, q, l, u, x0, y0, nv, mv, lsv, iv, tpos, K, solx, soly, dx, dy; size_t nnzA, nnzQ; };
+// One copy of an item's image inside an arena, for a batch slot (slot_submit) and a resident fleet (qdev_small_fleet_create): the regions
+// (`reserve(bytes)` hands out 256-byte aligned offsets), the conversions into a host staging image, the device descriptor.
+template <class R> static void lay_inputs(Lay &L, size_t n, size_t m, R &reserve) {
+    L.Arp = reserve((m + 1) * 4); L.Aci = reserve(L.nnzA * 4 + 4); L.Aval = reserve(L.nnzA * 8 + 8);
+    L.Trp = reserve((n + 1) * 4); L.Tci = reserve(L.nnzA * 4 + 4); L.Tval = reserve(L.nnzA * 8 + 8);
+    L.Qrp = reserve((n + 1) * 4); L.Qci = reserve(L.nnzQ * 4 + 4); L.Qval = reserve(L.nnzQ * 8 + 8);
+    L.q = reserve(n * 8); L.l = reserve(m * 8 + 8); L.u = reserve(m * 8 + 8);
+}
+template <class R> static void lay_outputs(Lay &L, size_t n, size_t m, R &reserve) {
+    L.solx = reserve(n * 8); L.soly = reserve(m * 8 + 8); L.dx = reserve(n * 8); L.dy = reserve(m * 8 + 8);
+}
+template <class R> static void lay_scratch(Lay &L, size_t n, size_t m, R &reserve) {
+    L.nv = reserve((size_t)NV_COUNT * n * 8); L.mv = reserve((size_t)MV_COUNT * m * 8 + 8); L.lsv = reserve(4 * m * 8 + 8);
+    L.iv = reserve(3 * m * 4 + 4); L.tpos = reserve(L.nnzA * 4 + 4); L.K = reserve(n * n * 8);
+}
+// CSC -> the three CSR images, and q, l, u, into the host image h of the arena
+static void lay_convert(const QPDOData *d, const Lay &L, char *h, ConvScratch &W) {
+    const size_t n = d->n, m = d->m;
+    csc_to_csr32_raw(d->A, (int *)(h + L.Arp), (int *)(h + L.Aci), (double *)(h + L.Aval), W.next);
+    csc_as_csrT32_raw(d->A, (int *)(h + L.Trp), (int *)(h + L.Tci), (double *)(h + L.Tval));
+    sym_full32_raw(d->Q, (int *)(h + L.Qrp), (int *)(h + L.Qci), (double *)(h + L.Qval), W);
+    memcpy(h + L.q, d->q, n * 8); if (m) { memcpy(h + L.l, d->l, m * 8); memcpy(h + L.u, d->u, m * 8); }
+}
+// the item's descriptor over the device arena (x0 / y0, prof, res and batch_vec_off are the caller's)
+static void lay_describe(SmallQP &p, const QPDOData *d, const Lay &L, char *dbase) {
+    memset(&p, 0, sizeof(p));
+    p.n = (int)d->n; p.m = (int)d->m; p.c_const = d->c;
+    p.Arp = (const int *)(dbase + L.Arp); p.Aci = (const int *)(dbase + L.Aci); p.Aval = (double *)(dbase + L.Aval);
+    p.Trp = (const int *)(dbase + L.Trp); p.Tci = (const int *)(dbase + L.Tci); p.Tval = (double *)(dbase + L.Tval);
+    p.Qrp = (const int *)(dbase + L.Qrp); p.Qci = (const int *)(dbase + L.Qci); p.Qval = (double *)(dbase + L.Qval);
+    p.q = (double *)(dbase + L.q); p.l = (double *)(dbase + L.l); p.u = (double *)(dbase + L.u);
+    p.nv = (double *)(dbase + L.nv); p.mv = (double *)(dbase + L.mv); p.lsv = (double *)(dbase + L.lsv); p.iv = (int *)(dbase + L.iv); p.tpos = (int *)(dbase + L.tpos);
+    p.K = (double *)(dbase + L.K);
+    p.sol_x = (double *)(dbase + L.solx); p.sol_y = (double *)(dbase + L.soly); p.cert_dx = (double *)(dbase + L.dx); p.cert_dy = (double *)(dbase + L.dy);
+}
+// the work vectors of an item of (nmax, mmax) behind `lds` bytes of the latency layout: their offset and size in the dynamic LDS
+static void small_vec_lds(size_t lds, size_t nmax, size_t mmax, size_t *voff, size_t *vbytes) {
+    *voff = (lds + 15) & ~(size_t)15;
+    *vbytes = ((size_t)NV_COUNT * nmax + (size_t)MV_COUNT * mmax) * 8 + 3 * mmax * 4 + 16;
+}
 struct SmallSlot {
     int device = -1;
     hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1720,25 +1792,19 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
     for (long i = 0; i < count; i++) {
         const QPDOData *d = items[i].data; Lay &L = lay[(size_t)i];
         const size_t n = d->n, m = d->m;
-        L.Arp = reserve((m + 1) * 4); L.Aci = reserve(L.nnzA * 4 + 4); L.Aval = reserve(L.nnzA * 8 + 8);
-        L.Trp = reserve((n + 1) * 4); L.Tci = reserve(L.nnzA * 4 + 4); L.Tval = reserve(L.nnzA * 8 + 8);
-        L.Qrp = reserve((n + 1) * 4); L.Qci = reserve(L.nnzQ * 4 + 4); L.Qval = reserve(L.nnzQ * 8 + 8);
-        L.q = reserve(n * 8); L.l = reserve(m * 8 + 8); L.u = reserve(m * 8 + 8);
+        lay_inputs(L, n, m, reserve);
         L.x0 = items[i].x0 ? reserve(n * 8) : (size_t)-1; L.y0 = items[i].y0 ? reserve(m * 8 + 8) : (size_t)-1;
     }
     lap("conversions");
     const size_t upload_bytes = total;       // inputs
     for (long i = 0; i < count; i++) {
         const QPDOData *d = items[i].data; Lay &L = lay[(size_t)i];
-        const size_t n = d->n, m = d->m;
-        L.solx = reserve(n * 8); L.soly = reserve(m * 8 + 8); L.dx = reserve(n * 8); L.dy = reserve(m * 8 + 8);
+        lay_outputs(L, d->n, d->m, reserve);
     }
     const size_t out_bytes = total - upload_bytes;
     for (long i = 0; i < count; i++) {
         const QPDOData *d = items[i].data; Lay &L = lay[(size_t)i];
-        const size_t n = d->n, m = d->m;
-        L.nv = reserve((size_t)NV_COUNT * n * 8); L.mv = reserve((size_t)MV_COUNT * m * 8 + 8); L.lsv = reserve(4 * m * 8 + 8);
-        L.iv = reserve(3 * m * 4 + 4); L.tpos = reserve(L.nnzA * 4 + 4); L.K = reserve(n * n * 8);
+        lay_scratch(L, d->n, d->m, reserve);
     }
     char *harena = nullptr, *dbase = nullptr; SmallQP *hp = nullptr;
     SHIP(hipSetDevice(device));
@@ -1769,11 +1835,9 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
                 // memset of the whole region used to do it
                 static thread_local ConvScratch W;
                 auto tail0 = [&](size_t off, size_t bytes, size_t next_off) { if (next_off > off + bytes) memset(h + off + bytes, 0, next_off - off - bytes); };
-                csc_to_csr32_raw(d->A, (int *)(h + L.Arp), (int *)(h + L.Aci), (double *)(h + L.Aval), W.next);
+                lay_convert(d, L, h, W);
                 tail0(L.Arp, (m + 1) * 4, L.Aci); tail0(L.Aci, L.nnzA * 4, L.Aval); tail0(L.Aval, L.nnzA * 8, L.Trp);
-                csc_as_csrT32_raw(d->A, (int *)(h + L.Trp), (int *)(h + L.Tci), (double *)(h + L.Tval));
                 tail0(L.Trp, (n + 1) * 4, L.Tci); tail0(L.Tci, L.nnzA * 4, L.Tval); tail0(L.Tval, L.nnzA * 8, L.Qrp);
-                sym_full32_raw(d->Q, (int *)(h + L.Qrp), (int *)(h + L.Qci), (double *)(h + L.Qval), W);
                 tail0(L.Qrp, (n + 1) * 4, L.Qci); tail0(L.Qci, L.nnzQ * 4, L.Qval); tail0(L.Qval, L.nnzQ * 8, L.q);
                 tail0(L.q, n * 8, L.l); tail0(L.l, m * 8, L.u);
                 {   // u, then the optional x0 / y0, up to the end of this item's region
@@ -1782,7 +1846,6 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
                     if (L.y0 != (size_t)-1) { tail0(off, bytes, L.y0); off = L.y0; bytes = m * 8; }
                     tail0(off, bytes, reg_end);
                 }
-                memcpy(h + L.q, d->q, n * 8); if (m) { memcpy(h + L.l, d->l, m * 8); memcpy(h + L.u, d->u, m * 8); }
                 if (items[i].x0) memcpy(h + L.x0, items[i].x0, n * 8);
                 if (items[i].y0 && m) memcpy(h + L.y0, items[i].y0, m * 8);
             });
@@ -1794,16 +1857,8 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
     if (tprof) { SHIP(hipStreamSynchronize(S.stream)); lap("upload"); }
     for (long i = 0; i < count; i++) {
         const QPDOData *d = items[i].data; Lay &L = lay[(size_t)i]; SmallQP &p = hp[(size_t)i];
-        memset(&p, 0, sizeof(p));
-        p.n = (int)d->n; p.m = (int)d->m; p.c_const = d->c;
-        p.Arp = (const int *)(dbase + L.Arp); p.Aci = (const int *)(dbase + L.Aci); p.Aval = (double *)(dbase + L.Aval);
-        p.Trp = (const int *)(dbase + L.Trp); p.Tci = (const int *)(dbase + L.Tci); p.Tval = (double *)(dbase + L.Tval);
-        p.Qrp = (const int *)(dbase + L.Qrp); p.Qci = (const int *)(dbase + L.Qci); p.Qval = (double *)(dbase + L.Qval);
-        p.q = (double *)(dbase + L.q); p.l = (double *)(dbase + L.l); p.u = (double *)(dbase + L.u);
+        lay_describe(p, d, L, dbase);
         p.x0 = items[i].x0 ? (const double *)(dbase + L.x0) : nullptr; p.y0 = items[i].y0 ? (const double *)(dbase + L.y0) : nullptr;
-        p.nv = (double *)(dbase + L.nv); p.mv = (double *)(dbase + L.mv); p.lsv = (double *)(dbase + L.lsv); p.iv = (int *)(dbase + L.iv); p.tpos = (int *)(dbase + L.tpos);
-        p.K = (double *)(dbase + L.K);
-        p.sol_x = (double *)(dbase + L.solx); p.sol_y = (double *)(dbase + L.soly); p.cert_dx = (double *)(dbase + L.dx); p.cert_dy = (double *)(dbase + L.dy);
     }
     {
         const char *pf = getenv("QPDO_SMALL_PROF");
@@ -1832,8 +1887,8 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
         // 0.087 s), the latency kernel the faster single item (an item that runs all 10000 passes: 0.27 against 0.33 s).  A batch that is
         // solved one at a time under a large pass limit is as slow as its slowest item: it takes the latency kernel; batches of a STREAM
         // overlap their stragglers with the next batches' ordinary items: they take the wide kernel.
-        const size_t voff = (lds_lat + 15) & ~(size_t)15;
-        const size_t vbytes = ((size_t)NV_COUNT * nmax + (size_t)MV_COUNT * mmax) * 8 + 3 * mmax * 4 + 16;
+        size_t voff, vbytes;
+        small_vec_lds(lds_lat, nmax, mmax, &voff, &vbytes);
         const char *bk = getenv("QPDO_SMALL_BATCH_KERNEL");
         const bool lat_fits = klds_ok && klds_lat && ub_lat == ubytes && voff + vbytes <= budget;
         const bool use_lat = lat_fits && !(bk && !strcmp(bk, "wide")) && (bk ? !strcmp(bk, "lat") : (one_at_a_time && (count <= 256 || settings->max_iter >= 1000)));
@@ -2137,3 +2192,5 @@ void qdev_small_stream_destroy(void *h) {
 }
 
 }  // extern "C"
+
+#include "dev/small_fleet.inc"

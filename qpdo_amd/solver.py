@@ -109,7 +109,18 @@ class BatchItem(C.Structure):
 EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solve_batch", "qpdo_amd_batch_kernel_seconds", "qpdo_amd_batch_stream_create",
                "qpdo_amd_batch_stream_submit", "qpdo_amd_batch_stream_wait", "qpdo_amd_batch_stream_destroy", "qpdo_amd_device_count", "qpdo_amd_last_error", "qpdo_amd_get_stats", "qpdo_amd_get_trace",
                "qpdo_amd_sync", "qpdo_amd_pass_decision", "qpdo_amd_bench_spmv", "qpdo_amd_bench_dense_factor", "qpdo_amd_spmv", "qpdo_amd_linesearch", "qpdo_amd_download",
-               "qpdo_amd_update_matrices", "qpdo_amd_direct_solve", "qpdo_amd_download_factor"]
+               "qpdo_amd_update_matrices", "qpdo_amd_direct_solve", "qpdo_amd_download_factor",
+               "qpdo_amd_fleet_create", "qpdo_amd_fleet_update", "qpdo_amd_fleet_warm_start", "qpdo_amd_fleet_warm_start_last",
+               "qpdo_amd_fleet_solve", "qpdo_amd_fleet_get_stats", "qpdo_amd_fleet_get_certificates", "qpdo_amd_fleet_destroy"]
+
+
+class FleetStats(C.Structure):
+    """QPDOAmdFleetStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("count", C.c_long), ("matrix_bytes_uploaded", C.c_long), ("vector_bytes_uploaded_last_call", C.c_long),
+                ("solve_launches", C.c_long), ("solves", C.c_long), ("last_kernel_seconds", C.c_double)]
+
+
+FLEET_TABLE_BYTES = 16     # QPDO_AMD_FLEET_TABLE_BYTES
 
 _lib = None
 
@@ -162,6 +173,16 @@ def lib():
         L.qpdo_amd_batch_stream_wait.restype = C.c_int
         L.qpdo_amd_batch_stream_wait.argtypes = [C.c_void_p, C.c_long, C.POINTER(C.c_double)]
         L.qpdo_amd_batch_stream_destroy.argtypes = [C.c_void_p]
+        pp = C.POINTER(dp)
+        L.qpdo_amd_fleet_create.restype = C.c_void_p
+        L.qpdo_amd_fleet_create.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), C.POINTER(QPDOSettings)]
+        L.qpdo_amd_fleet_update.argtypes = [C.c_void_p, pp, pp, pp]
+        L.qpdo_amd_fleet_warm_start.argtypes = [C.c_void_p, pp, pp]
+        L.qpdo_amd_fleet_warm_start_last.argtypes = [C.c_void_p]
+        L.qpdo_amd_fleet_solve.argtypes = [C.c_void_p, pp, pp, C.POINTER(QPDOInfo)]
+        L.qpdo_amd_fleet_get_stats.argtypes = [C.c_void_p, C.POINTER(FleetStats)]
+        L.qpdo_amd_fleet_get_certificates.argtypes = [C.c_void_p, C.c_long, dp, dp]
+        L.qpdo_amd_fleet_destroy.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -607,6 +628,127 @@ class BatchStream:
             lib().qpdo_amd_batch_stream_destroy(self._h)
             self._h = None
             self._inflight.clear()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Fleet:
+    """A resident fleet of small QPs (qpdo_amd_fleet_*): set up once, then per control step update() / warm_start_last() / solve(), one
+    launch each for all items.  Item i carries the bits of a QPDO workspace of its own driven through the same calls.  The settings are
+    fixed at construction."""
+
+    def __init__(self, probs, settings=None, **kw):
+        self._h = None
+        if settings is None:
+            settings = default_settings(**kw)
+        elif kw:
+            for k, v in kw.items():
+                if not hasattr(settings, k):
+                    raise KeyError("unrecognized solver setting '%s'" % k)
+                setattr(settings, k, v)
+        img = Batch(probs)                                   # the host image of the data; the library copies what it needs
+        self.count = len(probs)
+        self.dims = [(len(x), len(y)) for x, y in img.outs]
+        arr = (C.POINTER(QPDOData) * max(1, self.count))(*[img.items[i].data for i in range(self.count)])
+        h = lib().qpdo_amd_fleet_create(self.count, arr, C.byref(settings))
+        if not h:
+            raise RuntimeError("Fleet: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+        self._h = h
+        self._outs = [(np.zeros(n), np.zeros(m)) for n, m in self.dims]
+        self._xp = (dp * self.count)(*[_as_dp(x) for x, _ in self._outs])
+        self._yp = (dp * self.count)(*[_as_dp(y) for _, y in self._outs])
+        self._info = (QPDOInfo * self.count)()
+        self.kernel_seconds = 0.0
+
+    def _ptrs(self, vecs, which, clip=False):
+        """list of `count` vectors (None entries allowed) -> (array of pointers or None, the arrays kept alive)"""
+        if vecs is None:
+            return None, []
+        if len(vecs) != self.count:
+            raise ValueError("%s: expected a list of %d vectors, got %d" % (which[0], self.count, len(vecs)))
+        keep, arr = [], (dp * self.count)()
+        for i, v in enumerate(vecs):
+            if v is None:
+                continue
+            v = np.ascontiguousarray(v, np.float64)
+            if v.shape != (self.dims[i][which[1]],):
+                raise ValueError("%s[%d]: expected shape (%d,), got %r" % (which[0], i, self.dims[i][which[1]], v.shape))
+            if clip:
+                v = np.clip(v, -QPDO_INFTY, QPDO_INFTY)     # qpdo.m:215-216
+            keep.append(v)
+            arr[i] = _as_dp(v)
+        return arr, keep
+
+    def _call(self, rc, what):
+        if rc:
+            raise RuntimeError("Fleet.%s: %s" % (what, (lib().qpdo_amd_last_error() or b"").decode()))
+
+    def update(self, q=None, l=None, u=None):
+        """new q / l / u per item (lists of length count; None entries and None lists: unchanged).  Bounds first, then q."""
+        qa, k1 = self._ptrs(q, ("q", 0))
+        la, k2 = self._ptrs(l, ("l", 1), clip=True)
+        ua, k3 = self._ptrs(u, ("u", 1), clip=True)
+        self._call(lib().qpdo_amd_fleet_update(self._h, qa, la, ua), "update")
+
+    def warm_start(self, x=None, y=None):
+        xa, k1 = self._ptrs(x, ("x", 0))
+        ya, k2 = self._ptrs(y, ("y", 1))
+        self._call(lib().qpdo_amd_fleet_warm_start(self._h, xa, ya), "warm_start")
+
+    def warm_start_last(self):
+        self._call(lib().qpdo_amd_fleet_warm_start_last(self._h), "warm_start_last")
+
+    def solve(self, results=True):
+        """results=False: skip building the per-item dicts; the outputs are in info_view() and outs"""
+        self._call(lib().qpdo_amd_fleet_solve(self._h, self._xp, self._yp, self._info), "solve")
+        self.kernel_seconds = self.stats()["last_kernel_seconds"]
+        return self.results() if results else None
+
+    @property
+    def outs(self):
+        return self._outs
+
+    def info_view(self):
+        names, formats, offsets = [], [], []
+        for f, t in QPDOInfo._fields_:
+            if f == "status":
+                continue
+            names.append(f); formats.append(np.dtype(t)); offsets.append(getattr(QPDOInfo, f).offset)
+        dt = np.dtype(dict(names=names, formats=formats, offsets=offsets, itemsize=C.sizeof(QPDOInfo)))
+        return np.frombuffer(self._info, dtype=dt, count=self.count)
+
+    def results(self):
+        """the per-item dicts of Batch.results() (info, x, y) plus the certificates QPDO.solve() returns (NaN unless the status is -3 / -4)"""
+        names = [f for f, _ in QPDOInfo._fields_]
+        res = []
+        for i, (x, y) in enumerate(self._outs):
+            info = {f: getattr(self._info[i], f) for f in names}
+            info["status"] = info["status"].decode()
+            n, m = self.dims[i]
+            r = dict(info=info, x=x.copy(), y=y.copy(), prim_inf_cert=np.full(m, np.nan), dual_inf_cert=np.full(n, np.nan))
+            if info["status_val"] in (-3, -4):
+                pc, dc = np.zeros(m), np.zeros(n)
+                self._call(lib().qpdo_amd_fleet_get_certificates(self._h, i, _as_dp(pc), _as_dp(dc)), "results")
+                if info["status_val"] == -3:
+                    r["prim_inf_cert"] = pc
+                else:
+                    r["dual_inf_cert"] = dc
+            res.append(r)
+        return res
+
+    def stats(self):
+        s = FleetStats()
+        self._call(lib().qpdo_amd_fleet_get_stats(self._h, C.byref(s)), "stats")
+        return {f: getattr(s, f) for f, _ in FleetStats._fields_}
+
+    def close(self):
+        if self._h:
+            lib().qpdo_amd_fleet_destroy(self._h)
+            self._h = None
 
     def __del__(self):
         try:
