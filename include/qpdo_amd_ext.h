@@ -207,6 +207,41 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
 #define QPDO_AMD_DIRECT_LOST (-2)
 int  qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags);
 int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count);
+/* ---- the PCG linear-solve path as single steps (tests of its pieces; tests/test_gpu_pcg_pieces.py) ------------------------------------
+ * K = Q + sigma I + A' diag(dw) A with the workspace's stored matrices (the caller's own with settings->scaling = 0), dw: m weights; a row
+ * is "weighted" when dw_i != 0.0 (so -0.0 is not, a subnormal is).  Only for PCG workspaces (QPDO_LINSOLVE=pcg) on one GPU: a dense, band
+ * or row-partitioned workspace is refused (-1).  dw, v, out and info must not be NULL, also where m = 0.
+ * qpdo_amd_pcg_probe, info: QPDO_AMD_PCG_INFO_LEN doubles.
+ *   mode 0  the per-pass compact matrices are built from dw and ONE K product runs on p = v (n): out (n) = K v.  info[0] = k, the number of
+ *           weighted rows; info[1] = cnt; info[16 .. 16 + cnt) = the per-workgroup partial sums of p.Kp as the device left them.
+ *   mode 1  ONE solve of K x = v exactly as a Newton pass runs it (Schur-complement mode, heavy-row deflation, graph replay as the workspace
+ *           is configured), with the relative stopping rule ||r||_2 <= pcg_tol ||v||_2 alone: out (n) = x.  info[0] = k, [1] = iterations
+ *           (Schur mode: outer + inner steps), [2] = deflated rows, [3] = 1 when the Schur mode delivered x, [4], [5] = the recursive residual
+ *           and right-hand side 2-norms of the last iteration, [6], [7] = inner solves and inner steps launched, [8] = class: 0 ok,
+ *           1 not converged, 2 NaN residual, [9] = iterations of the outer CG alone (= [1] outside the Schur mode).
+ * Returns 0; QPDO_AMD_PCG_NOT_CONVERGED / QPDO_AMD_PCG_NAN for a solve of class 1 / 2 (out is not written, qpdo_amd_last_error carries the
+ * solver's message); -1 on any other failure.  The workspace's weights, sigma, direction, right-hand side, stopping rule, Schur-mode
+ * state and counters are put back: the next qpdo_solve runs as on a workspace that never saw the call.
+ * qpdo_amd_download_compact: what the last probe (or Newton pass) left; count = the number of ELEMENTS and must be the array's length.
+ *   which = 16 mat + part, mat 0 A_c (k x n: the weighted rows of A), 1 A_c' (n x k: CSR(A') restricted to them, columns renumbered),
+ *   2 A_h' (n x k: the deflated columns of A_c', after a deflated solve only); refused while the last pass built no such matrix (k = 0):
+ *     part 0  geometry, 7 x int64: nrows, ncols, nnz, use_slab, nslabs, W, ci16 present
+ *          1  rp   int32  nrows + 1         2  ci  int32  nnz         3  val  double  nnz
+ *          4  ci16 uint16 nnz: ci mod W (slab kernel with 16-bit indices; count 0 where absent)
+ *          5  sp   int32  nrows x (nslabs + 1): sp[r (nslabs + 1) + s] = first position of row r whose column is >= s W, sp[.. + nslabs] =
+ *                  the row's end (slab kernel; count 0 where absent)
+ *   48 index space, 5 x int64: n, m, k, words = (m + 63) / 64, deflated rows
+ *   49 rowlist int32 k: the weighted rows, ascending      50 cidx int32 m: weighted rows before row i      51 dc double k: their weights
+ *   52 flag_bits uint64 words: bit b of word w = row 64 w + b is weighted      53 flag_wprefix int32 words: cidx[64 w]
+ *   54 pc_diag double n: the diagonal preconditioner of the last solve (Jacobi route: Q_jj + sigma + sum_i A_ij^2 dw_i; Schur mode: Q_jj +
+ *      sigma; deflated: the remainder without the heavy rows, floored)      55 s_diag double k: Schur mode, 1 / dw_i + sum_j A_ij^2 / pc_diag_j
+ *   56 defl_list int32 (deflated rows): their compact row numbers      57 defl_Sinv double 256 x 256, row stride 256: the inverse of
+ *      S = D_h^-1 + A_h P^-1 A_h' in its leading block */
+#define QPDO_AMD_PCG_NOT_CONVERGED (-3)
+#define QPDO_AMD_PCG_NAN (-4)
+#define QPDO_AMD_PCG_INFO_LEN 1040
+int  qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, const double *v, double *out, int mode, double *info);
+int  qpdo_amd_download_compact(QPDOWorkspace *work, int which, void *dst, long count);
 /* copy a device-resident vector to the host: 0 x, 1 Qx, 2 y, 3 mu, 4 d (factor weights),
  * 5 dx, 6 dy, 7 Ax, 8 Aty, 9 l, 10 u, 11 ybar, 12 xbar, 13 w (of the last loop pass that ran) */
 int  qpdo_amd_download(QPDOWorkspace *work, int which, double *dst);

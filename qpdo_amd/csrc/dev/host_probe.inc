@@ -145,6 +145,132 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
     HIPCHK(hipStreamSynchronize(d->stream));
     return 0;
 }
+// ---- the PCG path as single linear-algebra steps (tests: tests/test_gpu_pcg_pieces.py) -------------------------------------------------
+// K = Q + sigma I + A' diag(dw) A through the functions a Newton pass of a PCG workspace calls.  mode 0: build_compact, then ONE
+// pcg_K_apply on p = v with the latch cleared (every launch of the product leaves at once while C_PCG_DONE is set): out = K v, info =
+// [kact, cnt] and the cnt per-block partial sums of p.Kp from info[QDEV_PCG_INFO_HEAD] on.  mode 1: ONE pcg_solve of K x = v with the
+// relative stopping rule alone: out = x, info = [kact, iters, defl_r, Schur mode delivered, V_RNORM, V_BNORM, inner solves, inner steps,
+// class (0 ok, 1 not converged, 2 NaN), outer iterations].  info holds QDEV_PCG_INFO_LEN doubles.  A solve of class 1 or 2 returns QDEV_PCG_NOT_CONVERGED /
+// QDEV_PCG_NAN with pcg_verdict's message, never a HIP code.  Whatever the call overwrites -- the weights, sigma_f, dx, rhs, the stopping
+// rule, the Schur mode's strikes and batch memory, the counters -- is put back: the next solve runs as on a workspace that never saw it.
+static_assert(QDEV_PCG_NOT_CONVERGED == PCG_NOT_CONVERGED && QDEV_PCG_NAN == PCG_NAN, "qpdo_dev.h carries the PCG failure classes");
+static_assert(QDEV_PCG_INFO_LEN == QDEV_PCG_INFO_HEAD + PGRID, "info: the head and one slot per partial sum");
+int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, double *out, int mode, double *info) {
+    HIPCHK(hipSetDevice(d->device));
+    if (d->comm.active) return set_err(hipErrorInvalidValue, "pcg probe: not for row-partitioned workspaces", __LINE__);
+    if (d->linsolve != 0) return set_err(hipErrorInvalidValue, "pcg probe: the workspace's solver is not PCG", __LINE__);
+    if (mode != 0 && mode != 1) return set_err(hipErrorInvalidValue, "pcg probe: mode is 0 (one K product) or 1 (one solve)", __LINE__);
+    const int n = d->n, m = d->m;
+    std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1)), rhs_keep((size_t)(n > 0 ? n : 1));
+    if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(dx_keep.data(), d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(rhs_keep.data(), d->rhs, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (m) HIPCHK(hipMemcpyAsync(d->d, dw, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(mode == 0 ? d->pc_p : d->rhs, v, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    const double sigma_keep = d->sigma_f, abs_keep = d->pcg_abs_now;
+    const int off_keep = d->schur_off, strikes_keep = d->schur_strikes, inner_keep = d->schur_last_inner, jac_keep = d->last_jacobi_iters;
+    const long long sp_keep = d->schur_passes, dp_keep = d->defl_passes;
+    const QdevStats st_keep = d->st;
+    const double ev_keep[3] = {d->ev_spmv_ms, d->ev_ac_ms, d->ev_ac_bytes}; const long long evn_keep[2] = {d->ev_spmv_n, d->ev_ac_n};
+    d->sigma_f = sigma; d->pcg_abs_now = -1.0;
+    for (int i = 0; i < QDEV_PCG_INFO_HEAD; i++) info[i] = 0.0;
+    int rc = 0;
+    if (mode == 0) {
+        if (!d->qdiag_valid) { LAUNCH(k_extract_diag, vgrid(n), n, d->Qf.rp, d->Qf.ci, d->Qf.val, d->qdiag); d->qdiag_valid = 1; }
+        rc = build_compact(d);
+        int cnt = 0;
+        if (!rc) {
+            LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_PCG_DONE, 0);
+            rc = pcg_K_apply(d, &d->ctrl->cnt[C_PCG_DONE], pcg_part(d).pKp, false, &cnt);
+        }
+        if (!rc && n) HIPCHK(hipMemcpyAsync(out, d->pc_Kp, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+        if (!rc) HIPCHK(hipMemcpyAsync(info + QDEV_PCG_INFO_HEAD, pcg_part(d).pKp, (size_t)cnt * 8, hipMemcpyDeviceToHost, d->stream));
+        if (!rc) HIPCHK(hipStreamSynchronize(d->stream));
+        if (!rc) HIPCHK(hipGetLastError());
+        info[0] = (double)d->kact; info[1] = (double)cnt;
+    } else {
+        int iters = 0;
+        rc = pcg_solve(d, &iters);
+        if (!rc && n) HIPCHK(hipMemcpyAsync(out, d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+        const bool schur = d->schur_passes != sp_keep;
+        info[0] = (double)d->kact; info[1] = (double)iters; info[2] = schur ? 0.0 : (double)d->defl_r; info[3] = schur ? 1.0 : 0.0;
+        info[4] = d->hctrl->val[V_RNORM]; info[5] = d->hctrl->val[V_BNORM];
+        info[6] = (double)(d->st.inner_solves - st_keep.inner_solves); info[7] = (double)(d->st.inner_steps - st_keep.inner_steps);
+        info[8] = rc == 0 ? 0.0 : rc == PCG_NOT_CONVERGED ? 1.0 : rc == PCG_NAN ? 2.0 : -1.0;
+        info[9] = (double)d->hctrl->cnt[C_PCG_IT];          // the outer iteration's own count (Schur mode: iters = this + the inner iterations)
+    }
+    d->sigma_f = sigma_keep; d->pcg_abs_now = abs_keep;
+    d->schur_off = off_keep; d->schur_strikes = strikes_keep; d->schur_last_inner = inner_keep; d->last_jacobi_iters = jac_keep;
+    d->schur_passes = sp_keep; d->defl_passes = dp_keep; d->st = st_keep;
+    d->ev_spmv_ms = ev_keep[0]; d->ev_ac_ms = ev_keep[1]; d->ev_ac_bytes = ev_keep[2]; d->ev_spmv_n = evn_keep[0]; d->ev_ac_n = evn_keep[1];
+    d->ctrl_clean = 0;                     // (the solve used the control block's per-pass slots: the next residual pass clears them itself)
+    if (m) HIPCHK(hipMemcpyAsync(d->d, d_keep.data(), (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d->dx, dx_keep.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d->rhs, rhs_keep.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return rc;
+}
+// the compact structures that the last build_compact / pcg_solve left (layouts: include/qpdo_amd_ext.h, qpdo_amd_download_compact);
+// count is the number of elements of the array and must match
+int qdev_download_compact(QpdoDev *d, int which, void *dst, long count) {
+    HIPCHK(hipSetDevice(d->device));
+    if (d->comm.active) return set_err(hipErrorInvalidValue, "download compact: not for row-partitioned workspaces", __LINE__);
+    if (d->linsolve != 0) return set_err(hipErrorInvalidValue, "download compact: the workspace's solver is not PCG", __LINE__);
+    const int k = d->kact, words = (d->m + 63) / 64;
+    const void *src = nullptr; size_t len = 0, esz = 8;
+    if (which == 48) {
+        if (count != 5) return set_err(hipErrorInvalidValue, "download compact: the index space's geometry has 5 entries", __LINE__);
+        long long *g = (long long *)dst;
+        g[0] = d->n; g[1] = d->m; g[2] = k; g[3] = words; g[4] = d->defl_r;
+        return 0;
+    }
+    if (which >= 0 && which < 48) {
+        const int mat = which / 16, part = which % 16;
+        if (mat == 2 ? d->defl_r <= 0 : k <= 0) return set_err(hipErrorInvalidValue, "download compact: the last pass did not build that matrix", __LINE__);
+        const DevCsr &M = mat == 0 ? d->Arc : mat == 1 ? d->Atc : d->Ath;
+        long long nnz = M.nnz;
+        if (mat == 2) {                      // (Ath.nnz is the bound the launches are sized by; the count is the last row pointer)
+            int e = 0;
+            HIPCHK(hipMemcpyAsync(&e, M.rp + M.nrows, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+            HIPCHK(hipStreamSynchronize(d->stream));
+            nnz = e;
+        }
+        const bool slab = mat != 2 && M.use_slab;
+        switch (part) {
+            case 0: {
+                if (count != 7) return set_err(hipErrorInvalidValue, "download compact: a matrix's geometry has 7 entries", __LINE__);
+                long long *g = (long long *)dst;
+                g[0] = M.nrows; g[1] = M.ncols; g[2] = nnz; g[3] = slab; g[4] = slab ? M.nslabs : 0; g[5] = slab ? M.W : 0;
+                g[6] = (slab && M.ci16 != nullptr) ? 1 : 0;      // (the array is only meaningful, and only read, under the slab kernel)
+                return 0;
+            }
+            case 1: src = M.rp; len = (size_t)M.nrows + 1; esz = 4; break;
+            case 2: src = M.ci; len = (size_t)nnz; esz = 4; break;
+            case 3: src = M.val; len = (size_t)nnz; break;
+            case 4: if (slab && M.ci16) { src = M.ci16; len = (size_t)nnz; esz = 2; } break;
+            case 5: if (slab) { src = M.sp; len = (size_t)M.nrows * (size_t)(M.nslabs + 1); esz = 4; } break;
+            default: return set_err(hipErrorInvalidValue, "download compact: unknown array", __LINE__);
+        }
+    } else switch (which) {
+        case 49: src = d->rowlist; len = (size_t)k; esz = 4; break;
+        case 50: src = d->cidx; len = (size_t)d->m; esz = 4; break;
+        case 51: src = d->dc; len = (size_t)k; break;
+        case 52: src = d->flag_bits; len = (size_t)words; break;
+        case 53: src = d->flag_wprefix; len = (size_t)words; esz = 4; break;
+        case 54: src = d->pc_diag; len = (size_t)d->n; break;
+        case 55: src = d->s_diag; len = (size_t)k; break;
+        case 56: src = d->defl_list; len = (size_t)d->defl_r; esz = 4; break;
+        case 57: src = d->defl_Sinv; len = d->defl_Sinv ? (size_t)DEFL_MAX * DEFL_MAX : 0; break;
+        default: return set_err(hipErrorInvalidValue, "download compact: unknown array", __LINE__);
+    }
+    if (count < 0 || (size_t)count != len) return set_err(hipErrorInvalidValue, "download compact: count is not the array's length", __LINE__);
+    if (!len) return 0;
+    if (!src) return set_err(hipErrorInvalidValue, "download compact: this workspace does not hold that array", __LINE__);
+    HIPCHK(hipMemcpyAsync(dst, src, len * esz, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
 int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host) {
     HIPCHK(hipSetDevice(d->device));
     DevCsr *M = mat_by_id(d, which);

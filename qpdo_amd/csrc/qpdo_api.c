@@ -1066,6 +1066,22 @@ int qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, c
 int qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count) {
     return qdev_download_factor(work->chol->dev, which, dst, count) ? -1 : 0;
 }
+/* the pointer checks of the two PCG test entries are made here, before the backend is touched (tests/pcg_probe_args_driver.c) */
+int qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, const double *v, double *out, int mode, double *info) {
+    if (mode != 0 && mode != 1) { qdev_set_error("pcg probe: mode is 0 (one K product) or 1 (one solve)"); return -1; }
+    if (!dw || !v || !out || !info) { qdev_set_error("pcg probe: NULL vector (dw, v, out and info are required, also at m = 0)"); return -1; }
+    if (!(sigma == sigma)) { qdev_set_error("pcg probe: sigma is NaN"); return -1; }
+    if (!work || !work->chol || !work->chol->dev) { qdev_set_error("pcg probe: NULL workspace"); return -1; }
+    const int rc = qdev_pcg_probe(work->chol->dev, dw, sigma, v, out, mode, info);
+    return rc == QDEV_PCG_NOT_CONVERGED ? QPDO_AMD_PCG_NOT_CONVERGED : rc == QDEV_PCG_NAN ? QPDO_AMD_PCG_NAN : rc ? -1 : 0;
+}
+int qpdo_amd_download_compact(QPDOWorkspace *work, int which, void *dst, long count) {
+    if (which < 0 || which > 57 || (which < 48 && which % 16 > 5)) { qdev_set_error("download compact: unknown array"); return -1; }
+    if (count < 0) { qdev_set_error("download compact: negative count"); return -1; }
+    if (count > 0 && !dst) { qdev_set_error("download compact: NULL destination"); return -1; }
+    if (!work || !work->chol || !work->chol->dev) { qdev_set_error("download compact: NULL workspace"); return -1; }
+    return qdev_download_compact(work->chol->dev, which, dst, count) ? -1 : 0;
+}
 int qpdo_amd_download(QPDOWorkspace *work, int which, double *dst) { return qdev_download_vec(work->chol->dev, which, dst); }
 int qpdo_amd_get_stats(const QPDOWorkspace *work, QPDOAmdStats *out) {
     QdevStats st;

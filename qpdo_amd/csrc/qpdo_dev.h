@@ -209,6 +209,14 @@ int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host);
 #define QDEV_DIRECT_LOST (-9)
 int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *rhs, double *x, int flags);
 int qdev_download_factor(QpdoDev *d, int which, double *dst, long count);
+/* the PCG path as single steps (tests; qpdo_amd_pcg_probe, dev/host_probe.inc): mode 0 one K product after build_compact, mode 1 one
+ * pcg_solve; and the compact structures the last of either left (qpdo_amd_download_compact).  info: QDEV_PCG_INFO_LEN doubles. */
+#define QDEV_PCG_NOT_CONVERGED (-7)
+#define QDEV_PCG_NAN (-8)
+#define QDEV_PCG_INFO_HEAD 16
+#define QDEV_PCG_INFO_LEN (16 + 1024)
+int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, double *out, int mode, double *info);
+int qdev_download_compact(QpdoDev *d, int which, void *dst, long count);
 /* standalone piecewise-affine linesearch for parity tests (2m entries) */
 int qdev_linesearch(QpdoDev *d, double eta, double beta, const double *delta, const double *alpha,
                     double *tau);

@@ -109,7 +109,7 @@ class BatchItem(C.Structure):
 EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solve_batch", "qpdo_amd_batch_kernel_seconds", "qpdo_amd_batch_stream_create",
                "qpdo_amd_batch_stream_submit", "qpdo_amd_batch_stream_wait", "qpdo_amd_batch_stream_destroy", "qpdo_amd_device_count", "qpdo_amd_last_error", "qpdo_amd_get_stats", "qpdo_amd_get_trace",
                "qpdo_amd_sync", "qpdo_amd_pass_decision", "qpdo_amd_bench_spmv", "qpdo_amd_bench_dense_factor", "qpdo_amd_spmv", "qpdo_amd_linesearch", "qpdo_amd_download",
-               "qpdo_amd_update_matrices", "qpdo_amd_direct_solve", "qpdo_amd_download_factor",
+               "qpdo_amd_update_matrices", "qpdo_amd_direct_solve", "qpdo_amd_download_factor", "qpdo_amd_pcg_probe", "qpdo_amd_download_compact",
                "qpdo_amd_fleet_create", "qpdo_amd_fleet_update", "qpdo_amd_fleet_warm_start", "qpdo_amd_fleet_warm_start_last",
                "qpdo_amd_fleet_solve", "qpdo_amd_fleet_get_stats", "qpdo_amd_fleet_get_certificates", "qpdo_amd_fleet_destroy"]
 
@@ -159,6 +159,10 @@ def lib():
         L.qpdo_amd_direct_solve.restype = C.c_int
         L.qpdo_amd_download_factor.argtypes = [W, C.c_int, dp, C.c_long]
         L.qpdo_amd_download_factor.restype = C.c_int
+        L.qpdo_amd_pcg_probe.argtypes = [W, dp, C.c_double, dp, dp, C.c_int, dp]
+        L.qpdo_amd_pcg_probe.restype = C.c_int
+        L.qpdo_amd_download_compact.argtypes = [W, C.c_int, C.c_void_p, C.c_long]
+        L.qpdo_amd_download_compact.restype = C.c_int
         L.qpdo_amd_update_matrices.argtypes = [W, C.POINTER(CholmodSparse), C.POINTER(CholmodSparse)]
         L.qpdo_amd_update_matrices.restype = C.c_int
         L.qpdo_amd_dist_config.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -188,6 +192,17 @@ def lib():
 
 
 DIRECT_LOST = -2       # QPDO_AMD_DIRECT_LOST (include/qpdo_amd_ext.h)
+
+
+PCG_NOT_CONVERGED, PCG_NAN, PCG_INFO_LEN, PCG_INFO_HEAD = -3, -4, 1040, 16      # QPDO_AMD_PCG_* (include/qpdo_amd_ext.h)
+
+
+class PcgNotConverged(RuntimeError):
+    """qpdo_amd_pcg_probe: the solve ended without meeting its tolerance (iteration cap, stagnation)"""
+
+
+class PcgNaN(RuntimeError):
+    """qpdo_amd_pcg_probe: the solve met a NaN residual"""
 
 
 class LostProducer(RuntimeError):
@@ -451,6 +466,68 @@ class QPDO:
             msg = (lib().qpdo_amd_last_error() or b"").decode()
             raise (LostProducer if rc == DIRECT_LOST else RuntimeError)("direct_solve: %s" % msg)
         return x
+
+    def _pcg_probe(self, dw, sigma, v, mode):
+        dw = np.ascontiguousarray(dw, np.float64)
+        v = np.ascontiguousarray(v, np.float64)
+        if len(dw) != self.m or len(v) != self.n:
+            raise ValueError("dw needs m entries and v n")
+        dwb = np.zeros(max(self.m, 1)); dwb[:self.m] = dw            # (the C side refuses NULL, which an empty array may be)
+        vb = np.zeros(max(self.n, 1)); vb[:self.n] = v
+        out, info = np.zeros(max(self.n, 1)), np.zeros(PCG_INFO_LEN)
+        rc = lib().qpdo_amd_pcg_probe(self._w, _as_dp(dwb), float(sigma), _as_dp(vb), _as_dp(out), mode, _as_dp(info))
+        if rc:
+            msg = (lib().qpdo_amd_last_error() or b"").decode()
+            raise {PCG_NOT_CONVERGED: PcgNotConverged, PCG_NAN: PcgNaN}.get(rc, RuntimeError)("pcg_probe: %s" % msg)
+        return out[:self.n].copy(), info
+
+    def pcg_K_product(self, dw, sigma, p):
+        """one K product of the PCG path after a fresh build of the compact matrices (qpdo_amd_pcg_probe, mode 0): K p, and a dict with
+        kact and the per-workgroup partial sums of p.Kp as the device left them"""
+        out, info = self._pcg_probe(dw, sigma, p, 0)
+        cnt = int(info[1])
+        return out, dict(kact=int(info[0]), cnt=cnt, partials=info[PCG_INFO_HEAD:PCG_INFO_HEAD + cnt].copy())
+
+    def pcg_solve(self, dw, sigma, rhs):
+        """one linear solve K x = rhs as a Newton pass of a PCG workspace runs it (qpdo_amd_pcg_probe, mode 1): x and a dict of what ran.
+        A capped or stagnated solve raises PcgNotConverged, a NaN residual PcgNaN."""
+        out, info = self._pcg_probe(dw, sigma, rhs, 1)
+        return out, dict(kact=int(info[0]), iters=int(info[1]), defl_r=int(info[2]), schur=bool(info[3]), rnorm=float(info[4]),
+                         bnorm=float(info[5]), inner_solves=int(info[6]), inner_steps=int(info[7]), outer=int(info[9]))
+
+    _COMPACT_VECS = {"rowlist": (49, np.int32, "k"), "cidx": (50, np.int32, "m"), "dc": (51, np.float64, "k"),
+                     "flag_bits": (52, np.uint64, "words"), "flag_wprefix": (53, np.int32, "words"), "pc_diag": (54, np.float64, "n"),
+                     "s_diag": (55, np.float64, "k"), "defl_list": (56, np.int32, "defl_r"), "defl_Sinv": (57, np.float64, None)}
+
+    def _compact_get(self, which, dtype, count):
+        out = np.zeros(max(count, 1), dtype)
+        if lib().qpdo_amd_download_compact(self._w, which, out.ctypes.data_as(C.c_void_p), count):
+            raise RuntimeError("download_compact: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+        return out[:count]
+
+    def compact_geometry(self):
+        g = self._compact_get(48, np.int64, 5)
+        return dict(n=int(g[0]), m=int(g[1]), k=int(g[2]), words=int(g[3]), defl_r=int(g[4]))
+
+    def download_compact_vector(self, name):
+        """a vector of the compact index space of the last PCG probe or Newton pass (qpdo_amd_download_compact; defl_Sinv: 256 x 256)"""
+        which, dtype, key = self._COMPACT_VECS[name]
+        if key is None:
+            return self._compact_get(which, dtype, 256 * 256).reshape(256, 256)
+        return self._compact_get(which, dtype, self.compact_geometry()[key])
+
+    def download_compact_matrix(self, name):
+        """a compact matrix of the last PCG probe or Newton pass -- "Arc" (k x n), "Atc" (n x k), "Ath" (n x k, deflated solves) -- as a
+        dict: the geometry, rp, ci, val, and ci16 / sp (None where the matrix has none)"""
+        base = 16 * {"Arc": 0, "Atc": 1, "Ath": 2}[name]
+        g = self._compact_get(base, np.int64, 7)
+        r = dict(nrows=int(g[0]), ncols=int(g[1]), nnz=int(g[2]), use_slab=int(g[3]), nslabs=int(g[4]), W=int(g[5]), has_ci16=int(g[6]))
+        r["rp"] = self._compact_get(base + 1, np.int32, r["nrows"] + 1)
+        r["ci"] = self._compact_get(base + 2, np.int32, r["nnz"])
+        r["val"] = self._compact_get(base + 3, np.float64, r["nnz"])
+        r["ci16"] = self._compact_get(base + 4, np.uint16, r["nnz"]) if r["has_ci16"] else None
+        r["sp"] = self._compact_get(base + 5, np.int32, r["nrows"] * (r["nslabs"] + 1)).reshape(r["nrows"], r["nslabs"] + 1) if r["use_slab"] else None
+        return r
 
     def factor_geometry(self):
         g = np.zeros(4)
