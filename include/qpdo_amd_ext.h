@@ -294,7 +294,7 @@ long qpdo_amd_batch_stream_submit(QPDOAmdBatchStream *stream, long count, QPDOAm
 int  qpdo_amd_batch_stream_wait(QPDOAmdBatchStream *stream, long ticket, double *kernel_seconds);
 void qpdo_amd_batch_stream_destroy(QPDOAmdBatchStream *stream);
 
-/* ---- a resident FLEET of small QPs (closed-loop MPC: the matrices never change, every control step changes q and the bounds) -------
+/* ---- a resident FLEET of small QPs (closed-loop MPC: every control step changes q and the bounds; with the flag below also Q / A values) ----
  * A fleet is `count` small QPs set up ONCE and kept on the device.  Item i behaves bit for bit as a workspace of its own that
  * received qpdo_setup(data[i], settings), then -- in the order the fleet calls were made -- qpdo_update_bounds for every fleet
  * update that passed an l or u entry for it, qpdo_update_q for every fleet update that passed a q entry, qpdo_warm_start for every
@@ -305,7 +305,8 @@ void qpdo_amd_batch_stream_destroy(QPDOAmdBatchStream *stream);
  * create   copies everything it needs (the caller's data may be freed afterwards), makes the only matrix upload the fleet ever
  *          makes and scales every item on the device in one launch.  Every item must fit the fused kernel (n, m <= 1024 and the
  *          matrix checks of qpdo_setup) and have l <= u; otherwise NULL with qpdo_amd_last_error() set and nothing left allocated.
- *          The settings are FIXED at create: there is no qpdo_update_settings for a fleet, and no way to change matrix values.
+ *          The settings are FIXED at create: there is no qpdo_update_settings for a fleet.  Matrix VALUES can change in a fleet
+ *          created with QPDO_AMD_FLEET_MATRIX_UPDATES only (below).
  * update   q, l, u: arrays of `count` pointers (q[i]: n_i values, l[i] / u[i]: m_i).  A NULL array leaves that kind of data unchanged
  *          for all items, a NULL entry for that item.  Within one call the bounds are applied first, then q (the two commute in the
  *          reference: bounds touch l, u and the row scaling E only).  An item whose l[i] and u[i] are both passed with l > u somewhere
@@ -321,6 +322,30 @@ void qpdo_amd_batch_stream_destroy(QPDOAmdBatchStream *stream);
  * Stats: vector_bytes_uploaded_last_call of an update or warm start = 8 bytes per vector element passed + a fixed table of
  * QPDO_AMD_FLEET_TABLE_BYTES per item (the offsets of the item's vectors in the upload); 0 after warm_start_last. */
 #define QPDO_AMD_FLEET_TABLE_BYTES 16
+/* ---- new Q / A VALUES for fleet items (real-time-iteration NMPC, LTV models: the pattern stays, the values move) ---------------------
+ * qpdo_amd_fleet_create equals qpdo_amd_fleet_create_ex(.., 0): the arena, uploads, launches and bits of a fleet that cannot change its
+ * matrices.  flags = QPDO_AMD_FLEET_MATRIX_UPDATES additionally keeps, per item: two int32 maps (one per entry of A, one per entry of the
+ * full Q unless stype is 0) that ride in create's upload (matrix_bytes_uploaded includes them); device copies of the unscaled q, l, u
+ * (fleet updates keep them current); with scaling > 0 device copies of the unscaled values of A and of the full Q (scaling rounds, and
+ * qpdo_update_q rescales Q: neither can be undone bit for bit); host copies of the two CSC patterns; pinned and device staging for every
+ * stored entry of every Q and A.  resident_extra_bytes is the device total.  Unknown flag bits are refused before any device call.
+ * update_matrices  Q, A: arrays of `count` pointers to matrices in the item's create-time pattern (Q in its create-time stype storage).  A
+ *          NULL array leaves that matrix unchanged for all items, a NULL entry for that item; both arrays NULL: returns 0, nothing is
+ *          launched.  An item with neither entry is not touched: its state, status and a pending warm start are kept.  An item with an
+ *          entry is afterwards, bit for bit, what qpdo_setup leaves for the new matrix or matrices, the latest values of the one not
+ *          passed, the latest UNSCALED q, l, u (create and every fleet update since), c and the fleet's settings: scaling from scratch,
+ *          state zero, sigma = sigma_init, status QPDO_UNSOLVED (so "out of passes overwrites UNSOLVED only" starts afresh), no pending
+ *          warm start.  The outputs of its last solve stay readable, and warm_start_last is then qpdo_warm_start with the x, y that
+ *          solve returned if it returned finite ones (the status it left none of -3, -4, -10, -99), from zero otherwise: the
+ *          real-time-iteration step  update_matrices -> update(q, l, u) -> warm_start_last -> solve  without host traffic for x, y.
+ *          Checks (all on the host, before any write or upload; the call is all-or-nothing): the fleet has the flag; per passed matrix
+ *          nrow, ncol, stype (Q), the entry count, EVERY column pointer and row index equal the create-time pattern (either itype), x is
+ *          not NULL.  The message names the item and the reason.
+ *          Cost: 8 bytes per passed entry + QPDO_AMD_FLEET_MATRIX_TABLE_BYTES per item in ONE upload, ONE launch (one workgroup per
+ *          item: a gather per CSR image, then the item's setup -- the Ruiz iterations dominate), one stream sync.
+ * solve_launches and solves of QPDOAmdFleetStats are not moved by matrix calls; matrix_bytes_uploaded stays what create uploaded. */
+#define QPDO_AMD_FLEET_MATRIX_UPDATES 1L
+#define QPDO_AMD_FLEET_MATRIX_TABLE_BYTES 8
 typedef struct QPDOAmdFleet_ QPDOAmdFleet;
 typedef struct {
     long count;
@@ -330,7 +355,17 @@ typedef struct {
     long solves;                            /* ... and the solve calls themselves */
     double last_kernel_seconds;             /* HIP-event duration of the last solve's launch */
 } QPDOAmdFleetStats;
+typedef struct {
+    long calls;                             /* update_matrices calls that launched */
+    long items_last_call;                   /* items that had a Q or an A entry in the last such call */
+    long value_bytes_uploaded_last_call;    /* 8 per entry passed + QPDO_AMD_FLEET_MATRIX_TABLE_BYTES per item of the fleet */
+    long resident_extra_bytes;              /* device memory the flag costs (maps, unscaled copies, staging); 0 without it */
+    double last_kernel_seconds;             /* HIP-event duration of the last update_matrices launch */
+} QPDOAmdFleetMatrixStats;
 QPDOAmdFleet *qpdo_amd_fleet_create(long count, const QPDOData *const *data, const QPDOSettings *settings);
+QPDOAmdFleet *qpdo_amd_fleet_create_ex(long count, const QPDOData *const *data, const QPDOSettings *settings, long flags);
+int  qpdo_amd_fleet_update_matrices(QPDOAmdFleet *f, const cholmod_sparse *const *Q, const cholmod_sparse *const *A);
+int  qpdo_amd_fleet_get_matrix_stats(const QPDOAmdFleet *f, QPDOAmdFleetMatrixStats *out);
 int  qpdo_amd_fleet_update(QPDOAmdFleet *f, const c_float *const *q, const c_float *const *l, const c_float *const *u);
 int  qpdo_amd_fleet_warm_start(QPDOAmdFleet *f, const c_float *const *x0, const c_float *const *y0);
 int  qpdo_amd_fleet_warm_start_last(QPDOAmdFleet *f);

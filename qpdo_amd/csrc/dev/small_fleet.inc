@@ -5,17 +5,14 @@
 //   update      k_small_fleet_update   qpdo_update_bounds then qpdo_update_q of every item that has an entry (qpdo.c:522-586)
 //   warm start  k_small_fleet, op 1/2  the shared solve body in mode 1 (qpdo.c:217-299)
 //   solve       k_small_fleet, op 0    the shared solve body from the item's state (mode 2), or from zero (mode 0)
+//   new Q / A   k_small_fleet_matrices the new values into the item's three CSR images, then the item's setup again (flag MATRIX_UPDATES)
 // each ONE launch for the whole fleet, in the oracle's operation order: item i carries the bits of a workspace of its own.
 
-// Ruiz + cost scaling of every item, tpos, the state zeroed: what k_small_solve has after its own scaling phase, left in the item's arrays
-__global__ __launch_bounds__(SM_THREADS) void k_small_fleet_setup(SmallQP *probs, int count, QPDOSettings st) {
-    __shared__ double sm[32];
-    if ((int)blockIdx.x >= count) return;
-    SmallQP &Pg = probs[blockIdx.x];
-    SmallQP P = Pg;
-    SmallRes *R = Pg.res;
+// What qpdo_setup leaves behind for the item's unscaled matrices, q, l, u, everything but tpos (a function of the pattern): the state zeroed,
+// Ruiz + cost scaling, the record of a fresh workspace.  ONE copy, for create (k_small_fleet_setup) and for new matrix values
+// (k_small_fleet_matrices).  The last solve's outputs and whether they are finite (last_finite) are not part of a workspace and stay.
+__device__ void small_fleet_item_setup(SmallQP &Pg, SmallQP &P, SmallRes *R, const QPDOSettings &st, double *sm) {
     const int n = P.n, m = P.m;
-    small_build_tpos(P);
     FOR_T(j, n) { R->state_x[j] = 0.0; R->state_Qx[j] = 0.0; R->st_xbar[j] = 0.0; R->st_Aty[j] = 0.0; }
     FOR_T(i, m) { R->st_y[i] = 0.0; R->st_ybar[i] = 0.0; R->st_Ax[i] = 0.0; R->st_mu[i] = 0.0; R->st_isq[i] = 0.0; }
     SYNC;
@@ -28,6 +25,52 @@ __global__ __launch_bounds__(SM_THREADS) void k_small_fleet_setup(SmallQP *probs
         R->fleet_status = QPDO_UNSOLVED;
         small_status(Pg.info, QPDO_UNSOLVED);
     }
+}
+// Ruiz + cost scaling of every item, tpos, the state zeroed: what k_small_solve has after its own scaling phase, left in the item's arrays
+__global__ __launch_bounds__(SM_THREADS) void k_small_fleet_setup(SmallQP *probs, int count, QPDOSettings st) {
+    __shared__ double sm[32];
+    if ((int)blockIdx.x >= count) return;
+    SmallQP &Pg = probs[blockIdx.x];
+    SmallQP P = Pg;
+    SmallRes *R = Pg.res;
+    small_build_tpos(P);
+    if (R->raw_q) {                                 // MATRIX_UPDATES: the unscaled q, l, u and (scaling rounds: it cannot be undone bit for bit) matrix values
+        const int n = P.n, m = P.m;
+        FOR_T(j, n) R->raw_q[j] = P.q[j];
+        FOR_T(i, m) { R->raw_l[i] = P.l[i]; R->raw_u[i] = P.u[i]; }
+        if (st.scaling > 0) {
+            const int nnzA = P.Trp[n], nnzQ = P.Qrp[n];
+            FOR_T(k, nnzA) R->rawA[k] = P.Tval[k];
+            FOR_T(k, nnzQ) R->rawQ[k] = P.Qval[k];
+        }
+    }
+    small_fleet_item_setup(Pg, P, R, st, sm);
+}
+// New values of Q and / or A in the create-time pattern for item i when tab[2 i] / tab[2 i + 1] name an offset into `stage` (-1: no entry;
+// neither: the workgroup leaves).  Q arrives as the caller's stored values, A as its CSC values = the value array of CSR(A').  A matrix that
+// is not passed is restored from its unscaled copy (scaling 0: the values in place are the unscaled ones), q, l, u from theirs, and the
+// item is set up as at create: afterwards it holds what qpdo_setup leaves for these inputs.
+__global__ __launch_bounds__(SM_THREADS) void k_small_fleet_matrices(SmallQP *probs, int count, QPDOSettings st, const int *tab, const double *stage) {
+    __shared__ double sm[32];
+    if ((int)blockIdx.x >= count) return;
+    const int oQ = __builtin_amdgcn_readfirstlane(tab[2 * blockIdx.x]), oA = __builtin_amdgcn_readfirstlane(tab[2 * blockIdx.x + 1]);
+    if (oQ < 0 && oA < 0) return;
+    SmallQP &Pg = probs[blockIdx.x];
+    SmallQP P = Pg;
+    SmallRes *R = Pg.res;
+    const int n = P.n, m = P.m, nnzA = P.Trp[n], nnzQ = P.Qrp[n];
+    const int scaled = st.scaling > 0;
+    if (oA >= 0) { const double *an = stage + oA; double *rawA = R->rawA; FOR_T(k, nnzA) { const double v = an[k]; P.Tval[k] = v; if (scaled) rawA[k] = v; } }
+    else if (scaled) { const double *rawA = R->rawA; FOR_T(k, nnzA) P.Tval[k] = rawA[k]; }
+    if (oQ >= 0) {
+        const double *qn = stage + oQ; const int *mapQ = R->mapQ; double *rawQ = R->rawQ;
+        FOR_T(k, nnzQ) { const double v = qn[mapQ ? mapQ[k] : k]; P.Qval[k] = v; if (scaled) rawQ[k] = v; }
+    } else if (scaled) { const double *rawQ = R->rawQ; FOR_T(k, nnzQ) P.Qval[k] = rawQ[k]; }
+    FOR_T(j, n) P.q[j] = R->raw_q[j];
+    FOR_T(i, m) { P.l[i] = R->raw_l[i]; P.u[i] = R->raw_u[i]; }
+    SYNC;
+    if (oA >= 0 || scaled) { const int *mapA = R->mapA; FOR_T(k, nnzA) P.Aval[k] = P.Tval[mapA[k]]; }
+    small_fleet_item_setup(Pg, P, R, st, sm);       // (its first barrier orders the stores above before the scaling reads them)
 }
 // qpdo_update_bounds (qpdo.c:522-544), then qpdo_update_q (qpdo.c:549-586) of item i when tab[4 i + 1] / [4 i + 2] (l, u) or tab[4 i] (q) name
 // an offset into `stage` (-1: no entry).  The two commute: bounds touch l, u and read E only.  The c / c_old rescale of Q's values and of Qx, the
@@ -43,6 +86,11 @@ __global__ __launch_bounds__(SM_THREADS) void k_small_fleet_update(SmallQP *prob
     const int n = Pg.n, m = Pg.m;
     const int scaled = st.scaling > 0, prox = (int)st.proximal;
     const double *E = R->rE, *D = R->rD;
+    if (R->raw_q) {                                 // MATRIX_UPDATES: the unscaled vectors a later k_small_fleet_matrices sets the item up from
+        if (oq >= 0) { const double *qn = stage + oq; double *rq = R->raw_q; FOR_T(j, n) rq[j] = qn[j]; }
+        if (ol >= 0) { const double *ln = stage + ol; double *rl = R->raw_l; FOR_T(i, m) rl[i] = ln[i]; }
+        if (ou >= 0) { const double *un = stage + ou; double *ru = R->raw_u; FOR_T(i, m) ru[i] = un[i]; }
+    }
     if (ol >= 0) { const double *ln = stage + ol; double *l = Pg.l; FOR_T(i, m) l[i] = scaled ? E[i] * ln[i] : ln[i]; }
     if (ou >= 0) { const double *un = stage + ou; double *u = Pg.u; FOR_T(i, m) u[i] = scaled ? E[i] * un[i] : un[i]; }
     if (oq < 0) return;
@@ -76,6 +124,8 @@ __global__ __launch_bounds__(SM_THREADS) void k_small_fleet_update(SmallQP *prob
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 struct FleetItem { int n, m; size_t o_q, o_l, o_u, o_solx, o_soly, o_dx, o_dy, out_off; };
+// MATRIX_UPDATES: the create-time CSC pattern of an item's A and stored Q (host copies: every update_matrices call is compared against them in full)
+struct FleetPattern { size_t Anrow = 0, Ancol = 0, Qnrow = 0, Qncol = 0; int Qstype = 0; std::vector<int> Ap, Ai, Qp, Qi; };
 struct SmallFleet {
     int device = 0; long count = 0; QPDOSettings st;
     hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -89,6 +139,12 @@ struct SmallFleet {
     size_t lds = 0; int kflags = 0;
     long matrix_bytes = 0, vector_bytes_last = 0, solve_launches = 0, solves = 0; double kernel_s = 0.0;
     bool solved = false;
+    // QPDO_AMD_FLEET_MATRIX_UPDATES (all empty / zero without the flag)
+    long flags = 0;
+    std::vector<FleetPattern> pat;
+    char *dmstage = nullptr, *hmstage = nullptr;    // a matrix call's [table: 2 ints per item][values], device and pinned
+    size_t mstage_doubles = 0;
+    long m_calls = 0, m_items_last = 0, m_bytes_last = 0, m_extra_bytes = 0; double m_kernel_s = 0.0;
 };
 static void fleet_free(SmallFleet *F) {
     if (!F) return;
@@ -98,6 +154,8 @@ static void fleet_free(SmallFleet *F) {
     if (F->dprobs) (void)hipFree(F->dprobs);
     if (F->dres) (void)hipFree(F->dres);
     if (F->dstage) (void)hipFree(F->dstage);
+    if (F->dmstage) (void)hipFree(F->dmstage);
+    if (F->hmstage) (void)hipHostFree(F->hmstage);
     if (F->hstage) (void)hipHostFree(F->hstage);
     if (F->hout) (void)hipHostFree(F->hout);
     if (F->hp) (void)hipHostFree(F->hp);
@@ -113,11 +171,15 @@ void qdev_small_fleet_destroy(void *h) { fleet_free((SmallFleet *)h); }
 
 // data: `count` QPDOData pointers, every item already checked (qdev_small_eligible, validate_data).  Converts, uploads and scales; NULL on
 // failure with qdev_small_last_error() set and nothing left allocated.
-void *qdev_small_fleet_create(int device, long count, const void *const *data_, const void *settings_) {
+void *qdev_small_fleet_create(int device, long count, const void *const *data_, const void *settings_, long flags) {
     int rc = 0;
+    const bool mu = (flags & QPDO_AMD_FLEET_MATRIX_UPDATES) != 0;
+    struct MatLay { size_t mapA = 0, mapQ = 0, rq = 0, rl = 0, ru = 0, rawA = 0, rawQ = 0; bool has_mapQ = false; };
+    std::vector<MatLay> ml(mu ? (size_t)count : 0);
+    size_t extra = 0, mstage = 0;
     const QPDOData *const *data = (const QPDOData *const *)data_;
     SmallFleet *F = new SmallFleet();
-    F->device = device; F->count = count; F->st = *(const QPDOSettings *)settings_;
+    F->device = device; F->count = count; F->st = *(const QPDOSettings *)settings_; F->flags = flags;
     F->it.resize((size_t)count);
     std::vector<Lay> lay((size_t)count);
     std::vector<SmallQP> hp((size_t)count);
@@ -126,6 +188,7 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     char *h = nullptr;
     size_t total = 0, nmax = 1, mmax = 0, stage = 0;
     auto reserve = [&](size_t bytes) { size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; };
+    auto reserve_extra = [&](size_t bytes) { const size_t o = reserve(bytes); extra += total - o; return o; };
     parallel_items(count, [&](long i) { const QPDOData *d = data[i]; Lay &L = lay[(size_t)i]; L.nnzA = (size_t)idx_at(d->A->p, d->A->itype, (long long)d->A->ncol); L.nnzQ = (size_t)sym_full_nnz(d->Q); });
     for (long i = 0; i < count; i++) {
         const QPDOData *d = data[i]; Lay &L = lay[(size_t)i];
@@ -134,7 +197,15 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
         if (n > nmax) nmax = n;
         if (m > mmax) mmax = m;
         stage += n + 2 * m;                          // the largest call: q, l and u of every item
+        if (mu) {                                    // the maps ride in create's upload
+            MatLay &X = ml[(size_t)i];
+            X.mapA = reserve_extra(L.nnzA * 4 + 4);
+            X.has_mapQ = d->Q->stype != 0;
+            if (X.has_mapQ) X.mapQ = reserve_extra(L.nnzQ * 4 + 4);
+            mstage += L.nnzA + (size_t)idx_at(d->Q->p, d->Q->itype, (long long)d->Q->ncol);      // the largest call: every stored entry of every Q and A
+        }
     }
+    if (mstage >= 2147483647ULL) { snprintf(s_err, sizeof(s_err), "fleet: %zu matrix entries per call exceed the 2^31 the call table can address; split the fleet", mstage); delete F; return nullptr; }
     // (a call's table holds 32-bit offsets, in doubles, into the staging of the whole fleet)
     if (stage >= 2147483647ULL) { snprintf(s_err, sizeof(s_err), "fleet: %zu vector elements per call exceed the 2^31 the call table can address; split the fleet", stage); delete F; return nullptr; }
     const size_t upload_bytes = total;
@@ -148,6 +219,11 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
         const size_t n = d->n, m = d->m;
         o_rec[(size_t)i] = reserve((6 * n + 7 * m) * 8 + 8);          // D, Dinv, x, Qx, xbar, A'y | E, Einv, y, ybar, Ax, mu, 1/sqrt(mu)
         lay_scratch(L, n, m, reserve);
+        if (mu) {
+            MatLay &X = ml[(size_t)i];
+            X.rq = reserve_extra(n * 8); X.rl = reserve_extra(m * 8 + 8); X.ru = reserve_extra(m * 8 + 8);
+            if (F->st.scaling > 0) { X.rawA = reserve_extra(L.nnzA * 8 + 8); X.rawQ = reserve_extra(L.nnzQ * 8 + 8); }
+        }
     }
     SHIP(hipSetDevice(device));
     SHIP(hipStreamCreateWithFlags(&F->stream, hipStreamNonBlocking));
@@ -159,6 +235,14 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     SHIP(hipMalloc((void **)&F->dstage, stage * 8 + (size_t)count * QPDO_AMD_FLEET_TABLE_BYTES + 16));
     F->dtab = (int *)(F->dstage + stage);
     SHIP(hipHostMalloc((void **)&F->hstage, stage * 8 + (size_t)count * QPDO_AMD_FLEET_TABLE_BYTES + 16, hipHostMallocDefault));
+    if (mu) {
+        const size_t mbytes = (size_t)count * QPDO_AMD_FLEET_MATRIX_TABLE_BYTES + mstage * 8 + 16;
+        F->mstage_doubles = mstage;
+        SHIP(hipMalloc((void **)&F->dmstage, mbytes));
+        SHIP(hipHostMalloc((void **)&F->hmstage, mbytes, hipHostMallocDefault));
+        F->m_extra_bytes = (long)(extra + mbytes);
+        F->pat.resize((size_t)count);
+    }
     SHIP(hipHostMalloc((void **)&F->hout, out_bytes ? out_bytes : 1, hipHostMallocDefault));
     SHIP(hipHostMalloc((void **)&F->hp, (size_t)count * sizeof(SmallQP), hipHostMallocDefault));
     F->out_off = upload_bytes; F->out_bytes = out_bytes;
@@ -166,7 +250,17 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     if (!h) { snprintf(s_err, sizeof(s_err), "fleet: host staging allocation failed"); rc = -1; goto done; }
     parallel_items(count, [&](long i) {              // the conversions of slot_submit, straight into the staging image
         static thread_local ConvScratch W;
-        lay_convert(data[i], lay[(size_t)i], h, W);
+        if (!mu) { lay_convert(data[i], lay[(size_t)i], h, W); return; }
+        const QPDOData *d = data[i]; const MatLay &X = ml[(size_t)i]; FleetPattern &Pt = F->pat[(size_t)i];
+        lay_convert(d, lay[(size_t)i], h, W, (int *)(h + X.mapA), X.has_mapQ ? (int *)(h + X.mapQ) : nullptr);
+        auto keep = [](const cholmod_sparse *M, std::vector<int> &p, std::vector<int> &ix) {
+            const long long nc = (long long)M->ncol, nnz = idx_at(M->p, M->itype, nc);
+            p.resize((size_t)nc + 1); ix.resize((size_t)nnz);
+            for (long long j = 0; j <= nc; j++) p[(size_t)j] = (int)idx_at(M->p, M->itype, j);
+            for (long long k = 0; k < nnz; k++) ix[(size_t)k] = (int)idx_at(M->i, M->itype, k);
+        };
+        Pt.Anrow = d->A->nrow; Pt.Ancol = d->A->ncol; Pt.Qnrow = d->Q->nrow; Pt.Qncol = d->Q->ncol; Pt.Qstype = d->Q->stype;
+        keep(d->A, Pt.Ap, Pt.Ai); keep(d->Q, Pt.Qp, Pt.Qi);
     });
     SHIP(hipMemcpyAsync(F->arena, h, upload_bytes, hipMemcpyHostToDevice, F->stream));     // the only matrix upload the fleet ever makes
     F->matrix_bytes = (long)upload_bytes;
@@ -192,6 +286,12 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
             r.rD = D; r.rDinv = Dinv; r.rE = E; r.rEinv = Einv; r.r_c = 1.0; r.r_cinv = 1.0;
             r.state_x = sx; r.state_Qx = sQx; r.st_xbar = sxb; r.st_Aty = sAty; r.st_y = sy; r.st_ybar = syb; r.st_Ax = sAx; r.st_mu = smu; r.st_isq = sisq;
             r.lds_vec_off = vec_off; r.fleet_status = QPDO_UNSOLVED;
+            if (mu) {
+                const MatLay &X = ml[(size_t)i];
+                r.mapA = (const int *)(dbase + X.mapA); r.mapQ = X.has_mapQ ? (const int *)(dbase + X.mapQ) : nullptr;
+                r.raw_q = (double *)(dbase + X.rq); r.raw_l = (double *)(dbase + X.rl); r.raw_u = (double *)(dbase + X.ru);
+                if (F->st.scaling > 0) { r.rawA = (double *)(dbase + X.rawA); r.rawQ = (double *)(dbase + X.rawQ); }
+            }
             I.n = (int)n; I.m = (int)m; I.o_solx = L.solx - upload_bytes; I.o_soly = L.soly - upload_bytes; I.o_dx = L.dx - upload_bytes; I.o_dy = L.dy - upload_bytes;
         }
     }
@@ -230,6 +330,65 @@ int qdev_small_fleet_update(void *h_, const double *const *q, const double *cons
     F->vector_bytes_last = (long)(off * 8 + (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES);
 done:
     return rc;
+}
+// Q, A: arrays of `count` cholmod_sparse pointers or NULL; entries may be NULL.  Every passed matrix is compared with the create-time pattern
+// in full before anything is written; then one upload [table][values], one launch (k_small_fleet_matrices), one stream sync.
+static int fleet_pattern_differs(const cholmod_sparse *M, size_t nrow, size_t ncol, int stype, bool check_stype, const std::vector<int> &p, const std::vector<int> &ix,
+                                 const char *name, long item) {
+    auto refuse = [&](const char *why) { snprintf(s_err, sizeof(s_err), "item %ld: %s %s", item, name, why); return 1; };
+    if (M->nrow != nrow) return refuse("has a different number of rows than at create");
+    if (M->ncol != ncol) return refuse("has a different number of columns than at create");
+    if (check_stype && M->stype != stype) return refuse("has a different stype than at create");
+    if (M->itype != 0 && M->itype != 2) return refuse("has an unknown itype");
+    if (!M->p || (!M->i && !ix.empty())) return refuse("has a NULL pattern array");
+    if (idx_at(M->p, M->itype, (long long)ncol) != (long long)ix.size()) return refuse("has a different number of entries than at create");
+    for (size_t j = 0; j <= ncol; j++) if (idx_at(M->p, M->itype, (long long)j) != (long long)p[j]) return refuse("has a column pointer that differs from the pattern at create");
+    for (size_t k = 0; k < ix.size(); k++) if (idx_at(M->i, M->itype, (long long)k) != (long long)ix[k]) return refuse("has a row index that differs from the pattern at create");
+    if (!M->x && !ix.empty()) return refuse("has a NULL value array x");
+    return 0;
+}
+int qdev_small_fleet_update_matrices(void *h_, const void *const *Q_, const void *const *A_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    const cholmod_sparse *const *Q = (const cholmod_sparse *const *)Q_, *const *A = (const cholmod_sparse *const *)A_;
+    if (!(F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES)) {
+        snprintf(s_err, sizeof(s_err), "the fleet was created without QPDO_AMD_FLEET_MATRIX_UPDATES (qpdo_amd_fleet_create_ex)");
+        return -1;
+    }
+    for (long i = 0; i < F->count; i++) {
+        const FleetPattern &Pt = F->pat[(size_t)i];
+        if (Q && Q[i] && fleet_pattern_differs(Q[i], Pt.Qnrow, Pt.Qncol, Pt.Qstype, true, Pt.Qp, Pt.Qi, "Q", i)) return -1;
+        if (A && A[i] && fleet_pattern_differs(A[i], Pt.Anrow, Pt.Ancol, 0, false, Pt.Ap, Pt.Ai, "A", i)) return -1;
+    }
+    if (!Q && !A) return 0;
+    const size_t tab_bytes = (size_t)F->count * QPDO_AMD_FLEET_MATRIX_TABLE_BYTES;
+    int *ht = (int *)F->hmstage; double *hs = (double *)(F->hmstage + tab_bytes);
+    size_t off = 0; long items = 0;
+    for (long i = 0; i < F->count; i++) {
+        const FleetPattern &Pt = F->pat[(size_t)i];
+        int *t = ht + 2 * i;
+        t[0] = t[1] = -1;
+        if (Q && Q[i]) { t[0] = (int)off; if (!Pt.Qi.empty()) memcpy(hs + off, Q[i]->x, Pt.Qi.size() * 8); off += Pt.Qi.size(); }
+        if (A && A[i]) { t[1] = (int)off; if (!Pt.Ai.empty()) memcpy(hs + off, A[i]->x, Pt.Ai.size() * 8); off += Pt.Ai.size(); }
+        items += (t[0] >= 0 || t[1] >= 0);
+    }
+    SHIP(hipSetDevice(F->device));
+    SHIP(hipMemcpyAsync(F->dmstage, F->hmstage, tab_bytes + off * 8, hipMemcpyHostToDevice, F->stream));
+    SHIP(hipEventRecord(F->ev0, F->stream));
+    hipLaunchKernelGGL(k_small_fleet_matrices, dim3((unsigned)F->count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)F->count, F->st,
+                       (const int *)F->dmstage, (const double *)(F->dmstage + tab_bytes));
+    SHIP(hipGetLastError());
+    SHIP(hipEventRecord(F->ev1, F->stream));
+    SHIP(hipStreamSynchronize(F->stream));           // (the pinned staging is free for the next call)
+    { float ms = 0.f; if (hipEventElapsedTime(&ms, F->ev0, F->ev1) == hipSuccess) F->m_kernel_s = (double)ms * 1e-3; }
+    F->m_calls++; F->m_items_last = items; F->m_bytes_last = (long)(tab_bytes + off * 8);
+done:
+    return rc;
+}
+void qdev_small_fleet_matrix_stats(const void *h_, long *out4, double *kernel_s) {
+    const SmallFleet *F = (const SmallFleet *)h_;
+    out4[0] = F->m_calls; out4[1] = F->m_items_last; out4[2] = F->m_bytes_last; out4[3] = F->m_extra_bytes;
+    *kernel_s = F->m_kernel_s;
 }
 // last = 1: every item from the x, y its last solve returned (device copies; zero where that solve left no finite solution)
 int qdev_small_fleet_warm_start(void *h_, const double *const *x0, const double *const *y0, int last) {

@@ -1209,6 +1209,10 @@ void qpdo_amd_batch_stream_destroy(QPDOAmdBatchStream *stream) { qdev_small_stre
  * the work in qdev_small_fleet_* (qpdo_small.hip) ------------------------------------------------------------------------------- */
 static int fleet_refuse(const char *msg) { qdev_set_error(msg); return -1; }
 QPDOAmdFleet *qpdo_amd_fleet_create(long count, const QPDOData *const *data, const QPDOSettings *settings) {
+    return qpdo_amd_fleet_create_ex(count, data, settings, 0L);
+}
+QPDOAmdFleet *qpdo_amd_fleet_create_ex(long count, const QPDOData *const *data, const QPDOSettings *settings, long flags) {
+    if (flags & ~QPDO_AMD_FLEET_MATRIX_UPDATES) { fleet_refuse("qpdo_amd_fleet_create_ex: unknown flag bits (known: QPDO_AMD_FLEET_MATRIX_UPDATES)"); return NULL; }
     if (count <= 0) { fleet_refuse("qpdo_amd_fleet_create: count must be positive"); return NULL; }
     if (!data) { fleet_refuse("qpdo_amd_fleet_create: NULL data array"); return NULL; }
     if (!settings) { fleet_refuse("qpdo_amd_fleet_create: NULL settings"); return NULL; }
@@ -1231,7 +1235,7 @@ QPDOAmdFleet *qpdo_amd_fleet_create(long count, const QPDOData *const *data, con
     const int ndev = qdev_device_count();
     if (ndev <= 0) { fleet_refuse("qpdo_amd_fleet_create: no HIP device available (this library has no CPU path)"); return NULL; }
     const int device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
-    void *f = qdev_small_fleet_create(device, count, (const void *const *)data, settings);
+    void *f = qdev_small_fleet_create(device, count, (const void *const *)data, settings, flags);
     if (!f) { char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_create: %s", qdev_small_last_error()); fleet_refuse(msg); }
     return (QPDOAmdFleet *)f;
 }
@@ -1277,6 +1281,22 @@ int qpdo_amd_fleet_get_stats(const QPDOAmdFleet *f, QPDOAmdFleetStats *out) {
     qdev_small_fleet_stats(f, st, &ks);
     out->count = st[0]; out->matrix_bytes_uploaded = st[1]; out->vector_bytes_uploaded_last_call = st[2];
     out->solve_launches = st[3]; out->solves = st[4]; out->last_kernel_seconds = ks;
+    return 0;
+}
+int qpdo_amd_fleet_update_matrices(QPDOAmdFleet *f, const cholmod_sparse *const *Q, const cholmod_sparse *const *A) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_update_matrices: NULL fleet");
+    if (qdev_small_fleet_update_matrices(f, (const void *const *)Q, (const void *const *)A)) {
+        char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_update_matrices: %s", qdev_small_last_error()); return fleet_refuse(msg);
+    }
+    return 0;
+}
+int qpdo_amd_fleet_get_matrix_stats(const QPDOAmdFleet *f, QPDOAmdFleetMatrixStats *out) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_get_matrix_stats: NULL fleet");
+    if (!out) return fleet_refuse("qpdo_amd_fleet_get_matrix_stats: NULL output");
+    long st[4]; double ks;
+    qdev_small_fleet_matrix_stats(f, st, &ks);
+    out->calls = st[0]; out->items_last_call = st[1]; out->value_bytes_uploaded_last_call = st[2]; out->resident_extra_bytes = st[3];
+    out->last_kernel_seconds = ks;
     return 0;
 }
 int qpdo_amd_fleet_get_certificates(const QPDOAmdFleet *f, long item, c_float *prim_inf_cert, c_float *dual_inf_cert) {

@@ -233,12 +233,15 @@ long  qdev_small_stream_submit(void *stream, long count, void *items, const void
 int   qdev_small_stream_wait(void *stream, long ticket, double *kernel_seconds);
 void  qdev_small_stream_destroy(void *stream);
 /* a resident fleet of small QPs (qpdo_small.hip, dev/small_fleet.inc); arguments are checked by the callers in qpdo_api.c */
-void *qdev_small_fleet_create(int device, long count, const void *const *data /* QPDOData */, const void *settings /* QPDOSettings */);
+void *qdev_small_fleet_create(int device, long count, const void *const *data /* QPDOData */, const void *settings /* QPDOSettings */, long flags);
 int   qdev_small_fleet_update(void *fleet, const double *const *q, const double *const *l, const double *const *u);
 int   qdev_small_fleet_warm_start(void *fleet, const double *const *x0, const double *const *y0, int last);
 int   qdev_small_fleet_solve(void *fleet, double *const *x, double *const *y, void *info /* QPDOInfo[count] */);
 int   qdev_small_fleet_certificates(const void *fleet, long item, double *prim_inf_cert, double *dual_inf_cert);
 void  qdev_small_fleet_stats(const void *fleet, long *out5, double *kernel_seconds);
+/* the pattern checks are inside (complete, before any write): nonzero with qdev_small_last_error() naming the item and the reason */
+int   qdev_small_fleet_update_matrices(void *fleet, const void *const *Q /* cholmod_sparse */, const void *const *A);
+void  qdev_small_fleet_matrix_stats(const void *fleet, long *out4, double *kernel_seconds);
 void  qdev_small_fleet_dims(const void *fleet, long item, int *n, int *m);
 void  qdev_small_fleet_destroy(void *fleet);
 

@@ -83,6 +83,14 @@ struct SmallRes {
     // a FLEET item's record only (k_small_fleet*, dev/small_fleet.inc; appended: the members above keep their offsets): the status a workspace's
     // info would carry after the last solve (qpdo.c:451-453: a solve that runs out of passes overwrites an UNSOLVED status only)
     long fleet_status;
+    // whether the x, y the last solve returned are finite (its status none of -3, -4, -10, -99): written at the end of every solve, read by
+    // warm_start_last -- new matrix values reset fleet_status to UNSOLVED, the last solution stays a valid starting point
+    int last_finite;
+    // a fleet created with QPDO_AMD_FLEET_MATRIX_UPDATES (NULL otherwise): for entry k of CSR(A) its position in the caller's CSC values, for
+    // entry k of the full Q its position in the caller's stored values (NULL: stype 0, the same order); the unscaled q, l, u as of create and every
+    // update since; with scaling, the unscaled values of A (CSC order) and of the full Q
+    const int *mapA, *mapQ;
+    double *raw_q, *raw_l, *raw_u, *rawA, *rawQ;
 };
 enum { NV_X = 0, NV_XBAR, NV_QX, NV_ATY, NV_DF, NV_RD, NV_RDI, NV_RHS, NV_DX, NV_QDX, NV_ATDY, NV_D, NV_DINV, NV_T, NV_COUNT };
 enum { MV_Y = 0, MV_YBAR, MV_AX, MV_MU, MV_ISQ, MV_W, MV_RP, MV_RPOLD, MV_RPI, MV_DY, MV_ADX, MV_DW, MV_E, MV_EINV, MV_ATS, MV_T, MV_DWF, MV_COUNT };
@@ -1154,8 +1162,7 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
                     const int ox = __builtin_amdgcn_readfirstlane(fleet_tab[4 * blockIdx.x]), oy = __builtin_amdgcn_readfirstlane(fleet_tab[4 * blockIdx.x + 1]);
                     mode = 1; if (ox >= 0) P.x0 = fleet_stage + ox; if (oy >= 0) P.y0 = fleet_stage + oy;
                 } else if (fleet_op == 2) {       // the unscaled x, y the last solve returned, if it returned finite ones
-                    const long fs = Rg->fleet_status;
-                    const int fin = __builtin_amdgcn_readfirstlane((int)!(fs == QPDO_PRIMAL_INFEASIBLE || fs == QPDO_DUAL_INFEASIBLE || fs == QPDO_UNSOLVED || fs == QPDO_ERROR));
+                    const int fin = __builtin_amdgcn_readfirstlane(Rg->last_finite);
                     mode = 1; if (fin) { P.x0 = P.sol_x; P.y0 = P.sol_y; }
                 }
             }
@@ -1570,6 +1577,7 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
             long fs = Rg->fleet_status;
             if (status != QPDO_MAX_ITER_REACHED || fs == QPDO_UNSOLVED) fs = status;
             Rg->fleet_status = fs; Rg->mode = 0;                                // (qpdo.c:455: the solve clears `initialized`)
+            Rg->last_finite = (int)!(fs == QPDO_PRIMAL_INFEASIBLE || fs == QPDO_DUAL_INFEASIBLE || fs == QPDO_UNSOLVED || fs == QPDO_ERROR);
             small_status(Pg.info, fs);
         } else small_status(Pg.info, status);
         Pg.newton_passes = newton; Pg.factor_count = nfactor; (void)nrestore;
@@ -1604,7 +1612,8 @@ static inline long long idx_at(const void *a, int itype, long long k) { return i
 // Row i of the full Q = (lower stored) CSR row i of the stored triangle [columns <= i] followed by the stored column i below the
 // diagonal, (upper stored) the stored column i above the diagonal followed by CSR row i [columns >= i]; same rule as the host driver's
 // sym_to_full_csr (qpdo_api.c).
-static void csc_to_csr32_raw(const cholmod_sparse *M, int *rp, int *ci, double *val, std::vector<int> &next) {
+// `map` (optional): for entry s of the CSR image its position k in the caller's CSC arrays.
+static void csc_to_csr32_raw(const cholmod_sparse *M, int *rp, int *ci, double *val, std::vector<int> &next, int *map = nullptr) {
     const long long nr = (long long)M->nrow, nc = (long long)M->ncol, nnz = idx_at(M->p, M->itype, nc);
     for (long long i = 0; i <= nr; i++) rp[i] = 0;
     for (long long k = 0; k < nnz; k++) rp[idx_at(M->i, M->itype, k) + 1]++;
@@ -1613,7 +1622,7 @@ static void csc_to_csr32_raw(const cholmod_sparse *M, int *rp, int *ci, double *
     for (long long i = 0; i < nr; i++) next[(size_t)i] = rp[i];
     const double *x = (const double *)M->x;
     for (long long j = 0; j < nc; j++)
-        for (long long k = idx_at(M->p, M->itype, j); k < idx_at(M->p, M->itype, j + 1); k++) { const int s2 = next[(size_t)idx_at(M->i, M->itype, k)]++; ci[s2] = (int)j; val[s2] = x[k]; }
+        for (long long k = idx_at(M->p, M->itype, j); k < idx_at(M->p, M->itype, j + 1); k++) { const int s2 = next[(size_t)idx_at(M->i, M->itype, k)]++; ci[s2] = (int)j; val[s2] = x[k]; if (map) map[s2] = (int)k; }
 }
 static void csc_as_csrT32_raw(const cholmod_sparse *M, int *rp, int *ci, double *val) {
     const long long nc = (long long)M->ncol, nnz = idx_at(M->p, M->itype, nc);
@@ -1633,15 +1642,17 @@ static long long sym_full_nnz(const cholmod_sparse *Q) {              // entries
         }
     return c;
 }
-struct ConvScratch { std::vector<int> next, Rrp, Rci; std::vector<double> Rval; };
-static void sym_full32_raw(const cholmod_sparse *Q, int *rp, int *ci, double *val, ConvScratch &W) {
+struct ConvScratch { std::vector<int> next, Rrp, Rci, Rmap; std::vector<double> Rval; };
+// `map` (optional, stype != 0): for entry s of the full matrix the position in the caller's stored values it was taken from
+static void sym_full32_raw(const cholmod_sparse *Q, int *rp, int *ci, double *val, ConvScratch &W, int *map = nullptr) {
     const int st = Q->stype;
     if (st == 0) { csc_as_csrT32_raw(Q, rp, ci, val); return; }
     const long long n = (long long)Q->ncol, nnzs = idx_at(Q->p, Q->itype, n);
     if ((long long)W.Rrp.size() < n + 1) W.Rrp.resize((size_t)n + 1);
     if ((long long)W.Rci.size() < nnzs + 1) { W.Rci.resize((size_t)nnzs + 1); W.Rval.resize((size_t)nnzs + 1); }
-    csc_to_csr32_raw(Q, W.Rrp.data(), W.Rci.data(), W.Rval.data(), W.next);
-    const int *Rrp = W.Rrp.data(), *Rci = W.Rci.data(); const double *Rval = W.Rval.data();
+    if (map && (long long)W.Rmap.size() < nnzs + 1) W.Rmap.resize((size_t)nnzs + 1);
+    csc_to_csr32_raw(Q, W.Rrp.data(), W.Rci.data(), W.Rval.data(), W.next, map ? W.Rmap.data() : nullptr);
+    const int *Rrp = W.Rrp.data(), *Rci = W.Rci.data(), *Rmap = W.Rmap.data(); const double *Rval = W.Rval.data();
     const double *x = (const double *)Q->x;
     auto keep_csr = [&](long long i, long long j) { return st < 0 ? j <= i : j >= i; };
     auto keep_mir = [&](long long i, long long j) { return st < 0 ? i > j : i < j; };
@@ -1650,11 +1661,11 @@ static void sym_full32_raw(const cholmod_sparse *Q, int *rp, int *ci, double *va
         rp[i] = s2;
         const long long b0 = idx_at(Q->p, Q->itype, i), e0 = idx_at(Q->p, Q->itype, i + 1);
         if (st < 0) {
-            for (int k = Rrp[i]; k < Rrp[i + 1]; k++) if (keep_csr(i, Rci[k])) { ci[s2] = Rci[k]; val[s2] = Rval[k]; s2++; }
-            for (long long k = b0; k < e0; k++) { const long long r = idx_at(Q->i, Q->itype, k); if (keep_mir(r, i)) { ci[s2] = (int)r; val[s2] = x[k]; s2++; } }
+            for (int k = Rrp[i]; k < Rrp[i + 1]; k++) if (keep_csr(i, Rci[k])) { ci[s2] = Rci[k]; val[s2] = Rval[k]; if (map) map[s2] = Rmap[k]; s2++; }
+            for (long long k = b0; k < e0; k++) { const long long r = idx_at(Q->i, Q->itype, k); if (keep_mir(r, i)) { ci[s2] = (int)r; val[s2] = x[k]; if (map) map[s2] = (int)k; s2++; } }
         } else {
-            for (long long k = b0; k < e0; k++) { const long long r = idx_at(Q->i, Q->itype, k); if (keep_mir(r, i)) { ci[s2] = (int)r; val[s2] = x[k]; s2++; } }
-            for (int k = Rrp[i]; k < Rrp[i + 1]; k++) if (keep_csr(i, Rci[k])) { ci[s2] = Rci[k]; val[s2] = Rval[k]; s2++; }
+            for (long long k = b0; k < e0; k++) { const long long r = idx_at(Q->i, Q->itype, k); if (keep_mir(r, i)) { ci[s2] = (int)r; val[s2] = x[k]; if (map) map[s2] = (int)k; s2++; } }
+            for (int k = Rrp[i]; k < Rrp[i + 1]; k++) if (keep_csr(i, Rci[k])) { ci[s2] = Rci[k]; val[s2] = Rval[k]; if (map) map[s2] = Rmap[k]; s2++; }
         }
     }
     rp[n] = s2;
@@ -1682,11 +1693,11 @@ template <class R> static void lay_scratch(Lay &L, size_t n, size_t m, R &reserv
     L.iv = reserve(3 * m * 4 + 4); L.tpos = reserve(L.nnzA * 4 + 4); L.K = reserve(n * n * 8);
 }
 // CSC -> the three CSR images, and q, l, u, into the host image h of the arena
-static void lay_convert(const QPDOData *d, const Lay &L, char *h, ConvScratch &W) {
+static void lay_convert(const QPDOData *d, const Lay &L, char *h, ConvScratch &W, int *mapA = nullptr, int *mapQ = nullptr) {
     const size_t n = d->n, m = d->m;
-    csc_to_csr32_raw(d->A, (int *)(h + L.Arp), (int *)(h + L.Aci), (double *)(h + L.Aval), W.next);
+    csc_to_csr32_raw(d->A, (int *)(h + L.Arp), (int *)(h + L.Aci), (double *)(h + L.Aval), W.next, mapA);
     csc_as_csrT32_raw(d->A, (int *)(h + L.Trp), (int *)(h + L.Tci), (double *)(h + L.Tval));
-    sym_full32_raw(d->Q, (int *)(h + L.Qrp), (int *)(h + L.Qci), (double *)(h + L.Qval), W);
+    sym_full32_raw(d->Q, (int *)(h + L.Qrp), (int *)(h + L.Qci), (double *)(h + L.Qval), W, mapQ);
     memcpy(h + L.q, d->q, n * 8); if (m) { memcpy(h + L.l, d->l, m * 8); memcpy(h + L.u, d->u, m * 8); }
 }
 // the item's descriptor over the device arena (x0 / y0, prof, res and batch_vec_off are the caller's)

@@ -111,7 +111,8 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_sync", "qpdo_amd_pass_decision", "qpdo_amd_bench_spmv", "qpdo_amd_bench_dense_factor", "qpdo_amd_spmv", "qpdo_amd_linesearch", "qpdo_amd_download",
                "qpdo_amd_update_matrices", "qpdo_amd_direct_solve", "qpdo_amd_download_factor", "qpdo_amd_pcg_probe", "qpdo_amd_download_compact",
                "qpdo_amd_fleet_create", "qpdo_amd_fleet_update", "qpdo_amd_fleet_warm_start", "qpdo_amd_fleet_warm_start_last",
-               "qpdo_amd_fleet_solve", "qpdo_amd_fleet_get_stats", "qpdo_amd_fleet_get_certificates", "qpdo_amd_fleet_destroy"]
+               "qpdo_amd_fleet_solve", "qpdo_amd_fleet_get_stats", "qpdo_amd_fleet_get_certificates", "qpdo_amd_fleet_destroy",
+               "qpdo_amd_fleet_create_ex", "qpdo_amd_fleet_update_matrices", "qpdo_amd_fleet_get_matrix_stats"]
 
 
 class FleetStats(C.Structure):
@@ -120,7 +121,15 @@ class FleetStats(C.Structure):
                 ("solve_launches", C.c_long), ("solves", C.c_long), ("last_kernel_seconds", C.c_double)]
 
 
+class FleetMatrixStats(C.Structure):
+    """QPDOAmdFleetMatrixStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("calls", C.c_long), ("items_last_call", C.c_long), ("value_bytes_uploaded_last_call", C.c_long),
+                ("resident_extra_bytes", C.c_long), ("last_kernel_seconds", C.c_double)]
+
+
 FLEET_TABLE_BYTES = 16     # QPDO_AMD_FLEET_TABLE_BYTES
+FLEET_MATRIX_UPDATES = 1   # QPDO_AMD_FLEET_MATRIX_UPDATES
+FLEET_MATRIX_TABLE_BYTES = 8     # QPDO_AMD_FLEET_MATRIX_TABLE_BYTES
 
 _lib = None
 
@@ -180,6 +189,11 @@ def lib():
         pp = C.POINTER(dp)
         L.qpdo_amd_fleet_create.restype = C.c_void_p
         L.qpdo_amd_fleet_create.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), C.POINTER(QPDOSettings)]
+        L.qpdo_amd_fleet_create_ex.restype = C.c_void_p
+        L.qpdo_amd_fleet_create_ex.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), C.POINTER(QPDOSettings), C.c_long]
+        sparse_pp = C.POINTER(C.POINTER(CholmodSparse))
+        L.qpdo_amd_fleet_update_matrices.argtypes = [C.c_void_p, sparse_pp, sparse_pp]
+        L.qpdo_amd_fleet_get_matrix_stats.argtypes = [C.c_void_p, C.POINTER(FleetMatrixStats)]
         L.qpdo_amd_fleet_update.argtypes = [C.c_void_p, pp, pp, pp]
         L.qpdo_amd_fleet_warm_start.argtypes = [C.c_void_p, pp, pp]
         L.qpdo_amd_fleet_warm_start_last.argtypes = [C.c_void_p]
@@ -716,9 +730,9 @@ class BatchStream:
 class Fleet:
     """A resident fleet of small QPs (qpdo_amd_fleet_*): set up once, then per control step update() / warm_start_last() / solve(), one
     launch each for all items.  Item i carries the bits of a QPDO workspace of its own driven through the same calls.  The settings are
-    fixed at construction."""
+    fixed at construction.  matrix_updates=True (QPDO_AMD_FLEET_MATRIX_UPDATES) also allows update_matrices(): new Q / A values per item."""
 
-    def __init__(self, probs, settings=None, **kw):
+    def __init__(self, probs, settings=None, matrix_updates=False, **kw):
         self._h = None
         if settings is None:
             settings = default_settings(**kw)
@@ -731,7 +745,11 @@ class Fleet:
         self.count = len(probs)
         self.dims = [(len(x), len(y)) for x, y in img.outs]
         arr = (C.POINTER(QPDOData) * max(1, self.count))(*[img.items[i].data for i in range(self.count)])
-        h = lib().qpdo_amd_fleet_create(self.count, arr, C.byref(settings))
+        self._qstype = [int(p.get("Qstype", -1)) for p in probs]
+        if matrix_updates:
+            h = lib().qpdo_amd_fleet_create_ex(self.count, arr, C.byref(settings), FLEET_MATRIX_UPDATES)
+        else:
+            h = lib().qpdo_amd_fleet_create(self.count, arr, C.byref(settings))
         if not h:
             raise RuntimeError("Fleet: %s" % (lib().qpdo_amd_last_error() or b"").decode())
         self._h = h
@@ -770,6 +788,40 @@ class Fleet:
         la, k2 = self._ptrs(l, ("l", 1), clip=True)
         ua, k3 = self._ptrs(u, ("u", 1), clip=True)
         self._call(lib().qpdo_amd_fleet_update(self._h, qa, la, ua), "update")
+
+    def _mat_ptrs(self, mats, which):
+        """list of `count` scipy matrices (None entries allowed) -> (array of cholmod_sparse pointers or None, what they point into); converted
+        as Batch converts at create.  which: "Q" (n x n, in the item's create-time Qstype storage) or "A" (m x n)"""
+        if mats is None:
+            return None, []
+        if len(mats) != self.count:
+            raise ValueError("%s: expected a list of %d matrices, got %d" % (which, self.count, len(mats)))
+        keep, arr = [], (C.POINTER(CholmodSparse) * self.count)()
+        for i, M in enumerate(mats):
+            if M is None:
+                continue
+            n, m = self.dims[i]
+            shape = (n, n) if which == "Q" else (m, n)
+            M = sp.csc_matrix(M)
+            if M.shape != shape:
+                raise ValueError("%s[%d]: expected shape %r, got %r" % (which, i, shape, M.shape))
+            view = _sparse_view(M, self._qstype[i] if which == "Q" else 0, keep)
+            keep.append(view)
+            arr[i] = C.pointer(view)
+        return arr, keep
+
+    def update_matrices(self, Q=None, A=None):
+        """new VALUES of Q / A per item in the create-time pattern (lists of length count of scipy matrices; None entries and None lists:
+        unchanged).  An item with an entry becomes the workspace qpdo_setup leaves for its new matrices and its latest q, l, u; the others
+        are not touched.  Needs matrix_updates=True at construction."""
+        Qa, k1 = self._mat_ptrs(Q, "Q")
+        Aa, k2 = self._mat_ptrs(A, "A")
+        self._call(lib().qpdo_amd_fleet_update_matrices(self._h, Qa, Aa), "update_matrices")
+
+    def matrix_stats(self):
+        s = FleetMatrixStats()
+        self._call(lib().qpdo_amd_fleet_get_matrix_stats(self._h, C.byref(s)), "matrix_stats")
+        return {f: getattr(s, f) for f, _ in FleetMatrixStats._fields_}
 
     def warm_start(self, x=None, y=None):
         xa, k1 = self._ptrs(x, ("x", 0))
