@@ -218,7 +218,8 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *           is configured), with the relative stopping rule ||r||_2 <= pcg_tol ||v||_2 alone: out (n) = x.  info[0] = k, [1] = iterations
  *           (Schur mode: outer + inner steps), [2] = deflated rows, [3] = 1 when the Schur mode delivered x, [4], [5] = the recursive residual
  *           and right-hand side 2-norms of the last iteration, [6], [7] = inner solves and inner steps launched, [8] = class: 0 ok,
- *           1 not converged, 2 NaN residual, [9] = iterations of the outer CG alone (= [1] outside the Schur mode).
+ *           1 not converged, 2 NaN residual, [9] = iterations of the outer CG alone (= [1] outside the Schur mode), [10] = 1 when the Schur
+ *           mode took its inner diagonal from the pass's one read of the weighted rows (QPDO_COMPACT_ONE_READ), 0 when k_schur_diag ran.
  * Returns 0; QPDO_AMD_PCG_NOT_CONVERGED / QPDO_AMD_PCG_NAN for a solve of class 1 / 2 (out is not written, qpdo_amd_last_error carries the
  * solver's message); -1 on any other failure.  The workspace's weights, sigma, direction, right-hand side, stopping rule, Schur-mode
  * state and counters are put back: the next qpdo_solve runs as on a workspace that never saw the call.
@@ -236,7 +237,16 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *   54 pc_diag double n: the diagonal preconditioner of the last solve (Jacobi route: Q_jj + sigma + sum_i A_ij^2 dw_i; Schur mode: Q_jj +
  *      sigma; deflated: the remainder without the heavy rows, floored)      55 s_diag double k: Schur mode, 1 / dw_i + sum_j A_ij^2 / pc_diag_j
  *   56 defl_list int32 (deflated rows): their compact row numbers      57 defl_Sinv double 256 x 256, row stride 256: the inverse of
- *      S = D_h^-1 + A_h P^-1 A_h' in its leading block */
+ *      S = D_h^-1 + A_h P^-1 A_h' in its leading block
+ *   60 ls_idx uint32 2 m: the breakpoint indices in the order the last linesearch's radix sort left them (2 m > 8192, or QPDO_LS_SMALL=0;
+ *      candidates first, by ratio, ties by index)
+ *   which = 64 + 16 mat + part, mat 0 A_c, 1 A_c': the slab-major image that the slab kernel streams (count 0 where the matrix does not
+ *   take the slab kernel):
+ *     part 0  seg  int32 pairs, 2 nrows nslabs: seg[r nslabs + s] = {first position in the image, length} of row r's entries in slab s
+ *          1  vsm  double nnz: the values, per workgroup the segments of slab 0 back to back, then those of slab 1, ...
+ *          2  the slab-local column indices in the same order: uint16 where ci16 is present, else int32 (ci - s W)
+ *   96 (count 0, dst unused): marks both images stale and runs one product with each compact matrix that takes the slab kernel, so
+ *      that the image is rebuilt from the CSR, sp and seg as after any change of the row-major arrays */
 #define QPDO_AMD_PCG_NOT_CONVERGED (-3)
 #define QPDO_AMD_PCG_NAN (-4)
 #define QPDO_AMD_PCG_INFO_LEN 1040

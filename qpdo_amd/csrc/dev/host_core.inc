@@ -183,6 +183,18 @@ static inline double nrm_of(const Ctrl *c, int slot) {
     double v; u64 b = c->nrm[slot]; memcpy(&v, &b, 8); return v;
 }
 #define LAUNCH(kernel, grid, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLK), 0, d->stream, __VA_ARGS__)
+// exclusive scan of cnt[0 .. n) into out[0 .. n), the total into *total (or nowhere): tile sums, then every tile's own scan behind the sums
+// in front of it (spmv.inc k_scn_sums / k_scn_apply; scratch of the workspace, no allocation)
+static void dev_scan(QpdoDev *d, const int *cnt, int n, int *out, int *total) {
+    const int nt = n > 0 ? (n + SCN_TILE - 1) / SCN_TILE : 1;
+    if (nt > 1) LAUNCH(k_scn_sums, nt, cnt, n, d->scan_tsum);
+    LAUNCH(k_scn_apply, nt, cnt, n, (const int *)d->scan_tsum, out, total);
+}
+// row counts to row pointers: out[0 .. n] (QPDO_GRID_SCANS=0: the one-workgroup kernel)
+static void scan_counts(QpdoDev *d, const int *cnt, int n, int *out) {
+    if (d->grid_scans) dev_scan(d, cnt, n, out, out + n);
+    else hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, cnt, n, out);
+}
 
 // ---- collectives ----------------------------------------------------------------------------------------
 static int comm_allreduce(QpdoDev *d, double *dev, size_t cnt, int op /*0 sum, 1 max*/) {

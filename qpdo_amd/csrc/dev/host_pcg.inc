@@ -1,20 +1,31 @@
 // host_pcg.inc -- part of qpdo_dev.hip (one translation unit; included in order): host side (extern C): compact index space, deflation, Schur-complement mode, PCG driver
 // ---- linear solve -----------------------------------------------------------------------------------
 // Build the compact index space of this Newton pass: k weighted rows, A_c (k x n) copied out of CSR(A),
-// A_c' (n x k) compacted out of CSR(A') with renumbered columns, d_c.  ~4 passes over A, once per Newton pass.
+// A_c' (n x k) compacted out of CSR(A') with renumbered columns, d_c; both with their slab tables and slab-major images where they take the
+// slab kernel.  Once per Newton pass: one read of the weighted rows of A, two of CSR(A') (count, then compaction).
+// Schur-complement mode whenever its inner system is well conditioned (k/n <= 0.8) and worth the set-up (k >= 256); kglob: the number of
+// weighted rows over all ranks
+static bool schur_allowed(const QpdoDev *d, long long kglob) {
+    return !d->schur_off && d->schur_mode != 0 && kglob >= 256 && (double)kglob <= 0.8 * (double)d->n && kglob <= (long long)d->m;
+}
 static int build_compact(QpdoDev *d) {
     const int n = d->n, m = d->mloc;                 // local rows; dl = their weights
     const double *dl = d->d + d->m0;
-    d->kact = 0;
+    d->kact = 0; d->sdiag_valid = 0;
     if (m == 0) return 0;
-    hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(1024), 0, d->stream, m, dl, d->cidx, d->rowlist, d->kcount, d->flag_bits, d->flag_wprefix);
+    if (d->grid_scans) {                 // (the words' counts pass through row_cnt, which the row counts below overwrite)
+        const int fwords = (m + 63) / 64;
+        LAUNCH(k_flag_words, (fwords + 3) / 4, m, dl, d->flag_bits, d->row_cnt);
+        dev_scan(d, d->row_cnt, fwords, d->flag_wprefix, d->kcount);
+        LAUNCH(k_flag_apply, (fwords + 3) / 4, m, (const u64 *)d->flag_bits, (const int *)d->flag_wprefix, d->cidx, d->rowlist);
+    } else hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(1024), 0, d->stream, m, dl, d->cidx, d->rowlist, d->kcount, d->flag_bits, d->flag_wprefix);
     int k = 0;
     HIPCHK(hipMemcpyAsync(&k, d->kcount, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     if (k <= 0) return 0;
     // A_c: rows
     LAUNCH(k_gather_rowinfo, vgrid(k), k, (const int *)d->rowlist, d->Ar.rp, dl, d->row_cnt, d->dc);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, k, d->Arc.rp);
+    scan_counts(d, d->row_cnt, k, d->Arc.rp);
     DevCsr &R = d->Arc;
     R.nrows = k; R.ncols = n; R.tpr = d->Ar.tpr; R.use_slab = d->Ar.use_slab && k >= 4096; R.slab_ovl = d->Ar.slab_ovl; R.slab_nt = d->Ar.slab_nt;
     int RW16 = 0;
@@ -30,9 +41,23 @@ static int build_compact(QpdoDev *d) {
         R.nslabs = nslabs; R.W = W;
         if (R.ci16) RW16 = W;
     }
-    LAUNCH(k_copy_rows, 2048, k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const unsigned short *)d->Ar.ci16, d->Ar.val,
-           (const int *)d->Arc.rp, d->Arc.ci, d->Arc.ci16, d->Arc.val, RW16);
-    if (R.use_slab) LAUNCH(k_build_slab_ptr, vgrid(k), k, R.rp, R.ci, R.nslabs, R.W, R.sp, (int *)nullptr);
+    const bool one_read = d->compact_one_read && R.use_slab && R.nslabs <= PASS_SLABS_MAX;
+    if (one_read) {
+        // sp and seg of the copy first, from the source rows; then one read of those rows writes the CSR copy, the slab image and -- where
+        // this pass can take the Schur mode on one GPU and k_schur_diag would run 64 lanes per row -- that mode's inner diagonal
+        const bool diag = d->Ar.tpr == 64 && !d->comm.active && schur_allowed(d, k);
+        LAUNCH(k_build_slab_ptr_rows, vgrid(k), k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const int *)R.rp, R.nslabs, R.W, R.sp);
+        hipLaunchKernelGGL(k_slab_seg, dim3(R.slab_grid), dim3(1024), 0, d->stream, R.nrows, R.nslabs, R.rows_per_wg, (const int *)R.sp, R.seg);
+#define COPY_ROWS_SLAB(DIAG) LAUNCH((k_copy_rows_slab<DIAG>), PASS_GRID, k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const unsigned short *)d->Ar.ci16, \
+            d->Ar.val, (const int *)R.rp, R.ci, R.ci16, R.val, RW16, R.nslabs, R.W, (const int *)R.sp, (const int2 *)R.seg, R.vsm, R.i16sm, R.cism, \
+            R.vsm32, (const double *)d->qdiag, d->sigma_f, (const double *)d->dc, d->s_diag)
+        if (diag) { COPY_ROWS_SLAB(true); d->sdiag_valid = 1; d->sdiag_sigma = d->sigma_f; } else COPY_ROWS_SLAB(false);
+#undef COPY_ROWS_SLAB
+    } else {
+        LAUNCH(k_copy_rows, 2048, k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const unsigned short *)d->Ar.ci16, d->Ar.val,
+               (const int *)d->Arc.rp, d->Arc.ci, d->Arc.ci16, d->Arc.val, RW16);
+        if (R.use_slab) LAUNCH(k_build_slab_ptr, vgrid(k), k, R.rp, R.ci, R.nslabs, R.W, R.sp, (int *)nullptr);
+    }
     // A_c': columns, renumbered
     DevCsr &T = d->Atc;
     const DevCsr &M = d->At;
@@ -50,24 +75,40 @@ static int build_compact(QpdoDev *d) {
     const int g = rowloop_grid(M);
     const int words = (m + 63) / 64;
     const size_t lds_tab = (size_t)words * (sizeof(u64) + sizeof(int));
-    if (lds_tab <= 60 * 1024) {          // flags and renumbering as LDS tables: the kernels stream the matrix only
+    // one read of CSR(A') for the CSR and the image: with the LDS tables, and where the slab-local 16-bit index is the image's own
+    const bool t_one_read = d->compact_t_one_read && lds_tab <= 60 * 1024 && (!T.use_slab || (T.nslabs <= PASS_SLABS_MAX && (!T.ci16 || W16 > 0)));
+    if (t_one_read) {
+        // counts per (row, slab) from the counting pass: the slab pointers follow from the scanned row pointers without a search; then
+        // seg, then the compaction writes every kept pair to the CSR and to its slab-major place
+        int *spT = T.use_slab ? T.sp : (int *)nullptr;
+        hipLaunchKernelGGL(k_count_flagged_slabs, dim3(2048), dim3(BLK), (size_t)words * 8, d->stream, n, M.rp, M.ci, (const u64 *)d->flag_bits, words,
+                           (const int *)d->rowlist, k, T.nslabs, T.W, d->row_cnt, spT);
+        scan_counts(d, d->row_cnt, n, T.rp);
+        if (spT) {
+            LAUNCH(k_sp_add_rp, vgrid(n), n, T.nslabs, (const int *)T.rp, T.sp);
+            hipLaunchKernelGGL(k_slab_seg, dim3(T.slab_grid), dim3(1024), 0, d->stream, T.nrows, T.nslabs, T.rows_per_wg, (const int *)T.sp, T.seg);
+        }
+        hipLaunchKernelGGL(k_compact_rows_bits_slab, dim3(PASS_GRID), dim3(BLK), lds_tab, d->stream, n, M.rp, M.ci, M.val, (const u64 *)d->flag_bits,
+                           (const int *)d->flag_wprefix, words, (const int *)T.rp, T.ci, T.val, W16, M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr,
+                           T.nslabs, T.W, (const int *)spT, (const int2 *)T.seg, T.vsm, T.i16sm, T.cism, T.vsm32);
+    } else if (lds_tab <= 60 * 1024) {          // flags and renumbering as LDS tables: the kernels stream the matrix only
         DISPATCH_TPR_LDS(M, k_count_flagged_bits, g, (size_t)words * 8, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt);
-        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, n, T.rp);
+        scan_counts(d, d->row_cnt, n, T.rp);
         hipLaunchKernelGGL(k_compact_rows_bits, dim3(2048), dim3(BLK), lds_tab, d->stream, n, M.rp, M.ci, M.val, (const u64 *)d->flag_bits,
                            (const int *)d->flag_wprefix, words, (const int *)T.rp, T.ci, T.val, W16, M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr);
     } else {
         DISPATCH_TPR(M, k_count_flagged, g, n, M.rp, M.ci, dl, d->row_cnt);
-        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, n, T.rp);
+        scan_counts(d, d->row_cnt, n, T.rp);
         LAUNCH(k_compact_rows, 2048, n, M.rp, M.ci, M.val, dl, (const int *)T.rp, T.ci, T.val, (const int *)d->cidx, W16,
                M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr);
     }
-    if (T.use_slab) LAUNCH(k_build_slab_ptr, vgrid(n), n, T.rp, T.ci, T.nslabs, T.W, T.sp, (int *)nullptr);
+    if (T.use_slab && !t_one_read) LAUNCH(k_build_slab_ptr, vgrid(n), n, T.rp, T.ci, T.nslabs, T.W, T.sp, (int *)nullptr);
     int nn[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(&nn[0], d->Arc.rp + k, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipMemcpyAsync(&nn[1], T.rp + n, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     R.nnz = nn[0]; T.nnz = nn[1];
-    R.sm_dirty = 1; T.sm_dirty = 1;
+    R.sm_dirty = one_read ? 0 : 1; T.sm_dirty = (t_one_read && T.use_slab) ? 0 : 1;      // stale images are rebuilt by the first product (slab_major_build)
     d->kact = k;
     return 0;
 }
@@ -127,7 +168,7 @@ static int defl_build(QpdoDev *d) {
     const int gAt = rowloop_grid(d->At);
     DISPATCH_TPR(d->At, k_jacobi_diag2, gAt, n, T.rp, T.ci, T.val, (const double *)d->tmp_m, (const double *)d->dc, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
     DISPATCH_TPR(d->At, k_count_flagged, gAt, n, T.rp, T.ci, (const double *)d->defl_flag, d->row_cnt);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, d->row_cnt, n, d->Ath.rp);
+    scan_counts(d, d->row_cnt, n, d->Ath.rp);
     LAUNCH(k_compact_rows, 2048, n, T.rp, T.ci, T.val, (const double *)d->defl_flag, (const int *)d->Ath.rp, d->Ath.ci, d->Ath.val,
            (const int *)nullptr, 0, (unsigned short *)nullptr);
     d->Ath.nrows = n; d->Ath.ncols = k; d->Ath.tpr = 4; d->Ath.use_slab = 0; d->Ath.nnz = (long long)r * d->max_row_nnz_A;
@@ -340,7 +381,9 @@ static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
     *fallback = 0;
     LAUNCH(k_axpy_const, g, n, (const double *)d->qdiag, d->sigma_f, d->pc_diag);                  // Dq
     // inner diagonal Sd_i = 1/d_i + sum_j A_ij^2 / Dq_j over this rank's compact rows (partitioned: no exchange)
-    if (kl > 0) {
+    // (build_compact has left it when it read the weighted rows once, with this sigma_f)
+    d->sdiag_from_build = kl > 0 && d->sdiag_valid && d->sdiag_sigma == d->sigma_f;
+    if (kl > 0 && !d->sdiag_from_build) {
         DISPATCH_TPR(d->Ar, k_schur_diag, rowloop_grid(d->Ar), kl, d->Arc.rp, d->Arc.ci, d->Arc.val,
                      (const double *)d->pc_diag, (const double *)d->dc, d->s_diag);
     }
@@ -449,8 +492,7 @@ static int pcg_solve(QpdoDev *d, int *iters_out) {
             kglob = (long long)ks;
             d->kg = (int)kglob;
         }
-        const bool allowed = !d->schur_off && d->schur_mode != 0 && kglob >= 256 && (double)kglob <= 0.8 * (double)n && kglob <= (long long)d->m;
-        if (allowed) {
+        if (schur_allowed(d, kglob)) {
             int fb = 0;
             rc = pcg_schur_solve(d, iters_out, &fb); if (rc) return rc;
             if (!fb) return 0;

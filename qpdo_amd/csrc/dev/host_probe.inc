@@ -191,6 +191,7 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
         info[0] = (double)d->kact; info[1] = (double)cnt;
     } else {
         int iters = 0;
+        d->sdiag_from_build = 0;
         rc = pcg_solve(d, &iters);
         if (!rc && n) HIPCHK(hipMemcpyAsync(out, d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
         const bool schur = d->schur_passes != sp_keep;
@@ -199,6 +200,7 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
         info[6] = (double)(d->st.inner_solves - st_keep.inner_solves); info[7] = (double)(d->st.inner_steps - st_keep.inner_steps);
         info[8] = rc == 0 ? 0.0 : rc == PCG_NOT_CONVERGED ? 1.0 : rc == PCG_NAN ? 2.0 : -1.0;
         info[9] = (double)d->hctrl->cnt[C_PCG_IT];          // the outer iteration's own count (Schur mode: iters = this + the inner iterations)
+        info[10] = (schur && d->sdiag_from_build) ? 1.0 : 0.0;      // the Schur diagonal came from build_compact's one read, not from k_schur_diag
     }
     d->sigma_f = sigma_keep; d->pcg_abs_now = abs_keep;
     d->schur_off = off_keep; d->schur_strikes = strikes_keep; d->schur_last_inner = inner_keep; d->last_jacobi_iters = jac_keep;
@@ -252,6 +254,29 @@ int qdev_download_compact(QpdoDev *d, int which, void *dst, long count) {
             case 5: if (slab) { src = M.sp; len = (size_t)M.nrows * (size_t)(M.nslabs + 1); esz = 4; } break;
             default: return set_err(hipErrorInvalidValue, "download compact: unknown array", __LINE__);
         }
+    } else if (which == 96) {
+        // the lazy path: both images marked stale, then one product with each compact matrix that takes the slab kernel (launch_slab
+        // rebuilds the image from the CSR, sp and seg by slab_major_build); nothing is copied
+        if (count != 0) return set_err(hipErrorInvalidValue, "download compact: the rebuild request carries no array (count 0)", __LINE__);
+        if (k <= 0) return set_err(hipErrorInvalidValue, "download compact: the last pass did not build that matrix", __LINE__);
+        d->Arc.sm_dirty = d->Atc.sm_dirty = 1;
+        const int64_t calls = d->st.spmv_calls, bytes = d->st.spmv_bytes;
+        if (d->Arc.use_slab) launch_spmv(d, d->Arc, d->pc_p, EpiStore{d->tc}, false);
+        if (d->Atc.use_slab) launch_spmv(d, d->Atc, d->tc, EpiStore{d->tmp_n}, false);
+        d->st.spmv_calls = calls; d->st.spmv_bytes = bytes;
+        HIPCHK(hipStreamSynchronize(d->stream));
+        HIPCHK(hipGetLastError());
+        return 0;
+    } else if (which >= 64 && which < 96) {
+        const int mat = (which - 64) / 16, part = which % 16;
+        if (k <= 0) return set_err(hipErrorInvalidValue, "download compact: the last pass did not build that matrix", __LINE__);
+        const DevCsr &M = mat == 0 ? d->Arc : d->Atc;
+        if (M.use_slab) switch (part) {       // (count 0 where the matrix does not take the slab kernel)
+            case 0: src = M.seg; len = (size_t)2 * M.nrows * (size_t)M.nslabs; esz = 4; break;
+            case 1: src = M.vsm; len = (size_t)M.nnz; break;
+            case 2: if (M.i16sm) { src = M.i16sm; esz = 2; } else { src = M.cism; esz = 4; } len = (size_t)M.nnz; break;
+            default: return set_err(hipErrorInvalidValue, "download compact: unknown array", __LINE__);
+        }
     } else switch (which) {
         case 49: src = d->rowlist; len = (size_t)k; esz = 4; break;
         case 50: src = d->cidx; len = (size_t)d->m; esz = 4; break;
@@ -262,6 +287,7 @@ int qdev_download_compact(QpdoDev *d, int which, void *dst, long count) {
         case 55: src = d->s_diag; len = (size_t)k; break;
         case 56: src = d->defl_list; len = (size_t)d->defl_r; esz = 4; break;
         case 57: src = d->defl_Sinv; len = d->defl_Sinv ? (size_t)DEFL_MAX * DEFL_MAX : 0; break;
+        case 60: src = d->ls_idx[0]; len = (size_t)2 * d->m; esz = 4; break;      // (the radix path's eight passes end in buffer 0)
         default: return set_err(hipErrorInvalidValue, "download compact: unknown array", __LINE__);
     }
     if (count < 0 || (size_t)count != len) return set_err(hipErrorInvalidValue, "download compact: count is not the array's length", __LINE__);

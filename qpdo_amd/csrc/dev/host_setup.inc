@@ -115,6 +115,7 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
     A_(ls_key[0], M2); A_(ls_key[1], M2); A_(ls_idx[0], M2); A_(ls_idx[1], M2);
     d->rs_nblocks = (int)((M2 + RS_TILE - 1) / RS_TILE); if (d->rs_nblocks < 1) d->rs_nblocks = 1;
     A_(rs_hist, (size_t)256 * d->rs_nblocks);
+    A_(scan_tsum, (size_t)(n > m ? n : m) / SCN_TILE + 2 + (size_t)256 * d->rs_nblocks / SCN_TILE);      // tiles of the longest scan: n, m or the histograms
     d->ls_nblk = (int)((M2 + LS_TILE - 1) / LS_TILE); if (d->ls_nblk < 1) d->ls_nblk = 1;
     A_(ls_bt, (size_t)2 * d->ls_nblk + 2);
     A_(ctrl, 1); A_(part, (size_t)P_COUNT * PGRID);
@@ -170,6 +171,9 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         d->Atc.vsm = nullptr; d->Atc.i16sm = nullptr; d->Atc.cism = nullptr; d->Atc.seg = nullptr; d->Atc.vsm32 = nullptr;
         { const char *f32 = getenv("QPDO_PCG_INNER_F32"); d->inner_f32 = (f32 && atoi(f32) != 0) ? 1 : 0; }
         { const char *fo = getenv("QPDO_INNER_FOLD"); d->inner_fold = !(fo && *fo && atoi(fo) == 0); }
+        { const char *gs = getenv("QPDO_GRID_SCANS"); d->grid_scans = !(gs && *gs && atoi(gs) == 0); }
+        { const char *co = getenv("QPDO_COMPACT_ONE_READ"); d->compact_one_read = !(co && *co && atoi(co) == 0); }
+        { const char *ct = getenv("QPDO_COMPACT_T_ONE_READ"); d->compact_t_one_read = !(ct && *ct && atoi(ct) == 0); }
         rc = dev_alloc(d, &d->Arc.rp, (size_t)m + 1);
         if (!rc) rc = dev_alloc(d, &d->Arc.ci, (size_t)d->Ar.nnz);
         if (!rc) rc = dev_alloc(d, &d->Arc.val, (size_t)d->Ar.nnz);

@@ -51,7 +51,8 @@ static int linesearch_device(QpdoDev *d, int pm, int pn) {
     for (int pass = 0; pass < 8; pass++) {
         const int shift = 8 * pass;
         LAUNCH(k_rs_hist, d->rs_nblocks, d->ls_key[cur], M2, shift, d->rs_nblocks, d->rs_hist);
-        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, d->stream, d->rs_hist, 256 * d->rs_nblocks);
+        if (d->grid_scans) dev_scan(d, d->rs_hist, 256 * d->rs_nblocks, d->rs_hist, (int *)nullptr);      // in place; consecutive items per thread
+        else hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, d->stream, d->rs_hist, 256 * d->rs_nblocks);
         LAUNCH(k_rs_scatter, d->rs_nblocks, d->ls_key[cur], d->ls_idx[cur], d->ls_key[1 - cur], d->ls_idx[1 - cur], M2, shift,
                d->rs_nblocks, d->rs_hist);
         cur = 1 - cur;

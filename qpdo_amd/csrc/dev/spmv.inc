@@ -324,6 +324,24 @@ __global__ void k_build_slab_ptr(int nrows, const int *__restrict__ rp, const in
     }
 }
 
+// the same pointers for the per-pass copy of the listed rows, searched in the SOURCE rows (the copy has the same columns in the same order):
+// sp[j] = rp2[j] + the offset inside row rowlist[j]; the copy itself has not been written yet
+__global__ void k_build_slab_ptr_rows(int k, const int *__restrict__ rowlist, const int *__restrict__ rp, const int *__restrict__ ci,
+                                      const int *__restrict__ rp2, int nslabs, int W, int *__restrict__ sp) {
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < k; j += gridDim.x * blockDim.x) {
+        const int r = rowlist[j];
+        const int b = rp[r], e = rp[r + 1], d0 = rp2[j] - b;
+        int *o = sp + (size_t)j * (nslabs + 1);
+        for (int s = 0; s < nslabs; s++) {
+            const int target = s * W;
+            int lo = b, hi = e;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (ci[mid] < target) lo = mid + 1; else hi = mid; }
+            o[s] = lo + d0;
+        }
+        o[nslabs] = e + d0;
+    }
+}
+
 // slab-major order of the segments of one workgroup's rows: t = s*R + r; exclusive scan of the lengths
 __global__ __launch_bounds__(1024) void k_slab_seg(int nrows, int nslabs, int rows_per_wg, const int *__restrict__ sp, int2 *__restrict__ seg) {
     __shared__ int sums[1024];
@@ -754,6 +772,88 @@ __global__ __launch_bounds__(256) void k_copy_rows(int k, const int *__restrict_
         }
     }
 }
+// ---- per-pass compact matrices with their slab image from ONE read ----------------------------------------------------------------
+// An entry's place in the image is its CSR position plus a per-(row, slab) shift, seg.x - sp; a row's slab starts and shifts are loaded once
+// per row (wave-uniform) and an entry finds its slab by counting the starts at or below its position (empty segments included: the
+// starts are monotone).  Up to PASS_SLABS_MAX slabs; the host keeps the former kernels beyond that.  The loops issue the loads of PASS_U
+// 64-entry steps before the first dependent instruction (the walk's base depends on the ballots, its loads do not).
+static const int PASS_SLABS_MAX = 8, PASS_U = 8;
+// Their grid.  The row loops split the rows statically over the grid, so workgroups beyond those resident at once run after the rest.  The
+// per-row tables cost scalar registers, which leave 7 waves per SIMD: 7 x 256 workgroups of 4 waves are resident for the copy on 256 CUs,
+// 2048 were not.  The compaction's LDS tables (37.5 KB at m = 2e5) allow it only 4 workgroups per CU; it runs in two rounds with either
+// grid and was measured faster with this one as well (C4, with the deeper prefetch: 0.88 -> 0.76 ms); its own optimum was not searched.
+static const int PASS_GRID = 7 * 256;
+struct RowSlabs {
+    int ob[PASS_SLABS_MAX], dl[PASS_SLABS_MAX];
+    __device__ __forceinline__ void load(const int *__restrict__ o, const int2 *__restrict__ sg, int nslabs) {
+#pragma unroll
+        for (int t = 0; t < PASS_SLABS_MAX; t++) {
+            ob[t] = t < nslabs ? o[t] : 0x7fffffff;
+            dl[t] = t < nslabs ? sg[t].x - o[t] : 0;
+        }
+    }
+    // slab of CSR position p and the shift to its place in the image
+    __device__ __forceinline__ int slab(int p, int &shift) const {
+        int sl = 0; shift = dl[0];
+#pragma unroll
+        for (int t = 1; t < PASS_SLABS_MAX; t++) { const bool in = p >= ob[t]; sl += in ? 1 : 0; shift = in ? dl[t] : shift; }
+        return sl;
+    }
+};
+// k_copy_rows for a copy that takes the slab kernel: the CSR copy as k_copy_rows writes it, every entry at its slab-major place as well (where
+// k_slab_permute would put it: sp and seg of the copy are built first, from the source rows), and with DIAG the row's diagonal of the
+// Schur mode's inner system in k_schur_diag<64>'s order (lane L adds entries L, L + 64, ... ascending, group_sum<64>, 1 / dc + s;
+// Dq_j = qdiag_j + sigma_f, the one addition of k_axpy_const): the same bits as the three kernels.  (W16 > 0 is the copy's own W: the
+// slab-local index c mod W is c - slab W.)
+template <bool DIAG>
+__global__ __launch_bounds__(256) void k_copy_rows_slab(int k, const int *__restrict__ rowlist, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                        const unsigned short *__restrict__ ci16, const double *__restrict__ val,
+                                                        const int *__restrict__ rp2, int *__restrict__ ci2, unsigned short *__restrict__ ci16_2,
+                                                        double *__restrict__ val2, int W16, int nslabs, int W, const int *__restrict__ sp,
+                                                        const int2 *__restrict__ seg, double *__restrict__ vsm, unsigned short *__restrict__ i16sm,
+                                                        int *__restrict__ cism, float *__restrict__ vsm32, const double *__restrict__ qdiag,
+                                                        double sigma_f, const double *__restrict__ dc, double *__restrict__ sdiag) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * BLK + threadIdx.x) >> 6;
+    const int nwaves = gridDim.x * (BLK >> 6);
+    for (int jw = wave; jw < k; jw += nwaves) {
+        const int j = __builtin_amdgcn_readfirstlane(jw);
+        const int r = rowlist[j];
+        const int src = rp[r], len = rp[r + 1] - src, dst = rp2[j];
+        RowSlabs rs; rs.load(sp + (size_t)j * (nslabs + 1), seg + (size_t)j * nslabs, nslabs);
+        double s = 0.0;
+        for (int e0 = 0; e0 < len; e0 += 64 * PASS_U) {
+            int c[PASS_U]; double v[PASS_U]; unsigned short h[PASS_U];
+#pragma unroll
+            for (int u = 0; u < PASS_U; u++) {
+                const int e = e0 + 64 * u + lane;
+                c[u] = 0; v[u] = 0.0; h[u] = 0;
+                if (e < len) { c[u] = ci[src + e]; v[u] = val[src + e]; if (ci16_2 && W16 <= 0) h[u] = ci16[src + e]; }
+            }
+#pragma unroll
+            for (int u = 0; u < PASS_U; u++) {
+                const int e = e0 + 64 * u + lane;
+                if (e < len) {
+                    const int p = dst + e;
+                    int shift; const int sl = rs.slab(p, shift);
+                    const int cl = c[u] - sl * W;
+                    const unsigned short c16 = W16 > 0 ? (unsigned short)cl : h[u];
+                    ci2[p] = c[u]; val2[p] = v[u];
+                    if (ci16_2) ci16_2[p] = c16;
+                    const int q = p + shift;
+                    vsm[q] = v[u];
+                    if (vsm32) vsm32[q] = (float)v[u];
+                    if (i16sm) i16sm[q] = c16; else cism[q] = cl;
+                    if (DIAG) s += v[u] * v[u] / (qdiag[c[u]] + sigma_f);
+                }
+            }
+        }
+        if (DIAG) {
+            s = group_sum<64>(s);
+            if (lane == 0) sdiag[j] = 1.0 / dc[j] + s;
+        }
+    }
+}
 __global__ void k_fill_ci16(long long nnz, const int *__restrict__ ci, int W, unsigned short *__restrict__ ci16) {
     for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += (long long)gridDim.x * blockDim.x)
         ci16[k] = (unsigned short)(ci[k] % W);
@@ -808,6 +908,70 @@ __global__ __launch_bounds__(1024) void k_scan_counts(const int *__restrict__ cn
     __syncthreads();
     int run = sums[threadIdx.x];
     for (int i = beg; i < end; i++) { out[i] = run; run += cnt[i]; }
+}
+// The same scan on many workgroups, none of which waits for another: tile sums in one launch; in the next every workgroup adds up the sums
+// of the tiles in front of its own and scans its tile (one tile: that launch alone).  Integers: any association gives the same result.
+// cnt and out may be the same array (every thread holds its items in registers before it stores); total (or null) receives the grand total.
+// (Every tile re-adds the sums in front of it: quadratic in the number of tiles, which is about 100 at the largest per-pass scan; a
+// scan over many thousands of tiles wants a scan of the sums in between, as dev_exclusive_scan of the setup has.)
+static const int SCN_ITEMS = 8;
+static const int SCN_TILE = BLK * SCN_ITEMS;         // 2048
+__global__ __launch_bounds__(256) void k_scn_sums(const int *__restrict__ cnt, int n, int *__restrict__ tsum) {
+    __shared__ int ws[BLK / 64];
+    const int base = blockIdx.x * SCN_TILE + threadIdx.x * SCN_ITEMS;
+    int s = 0;
+#pragma unroll
+    for (int u = 0; u < SCN_ITEMS; u++) if (base + u < n) s += cnt[base + u];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < BLK / 64; w++) t += ws[w]; tsum[blockIdx.x] = t; }
+}
+__global__ __launch_bounds__(256) void k_scn_apply(const int *cnt, int n, const int *__restrict__ tsum, int *out, int *__restrict__ total) {
+    __shared__ int woff[BLK / 64], wtot[BLK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int off = 0;                                              // the tiles in front of this one
+    for (int i = threadIdx.x; i < (int)blockIdx.x; i += BLK) off += tsum[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) off += __shfl_down(off, o, 64);
+    const int base = blockIdx.x * SCN_TILE + threadIdx.x * SCN_ITEMS;
+    int v[SCN_ITEMS], s = 0;
+#pragma unroll
+    for (int u = 0; u < SCN_ITEMS; u++) { v[u] = base + u < n ? cnt[base + u] : 0; s += v[u]; }
+    int inc = s;                                              // inclusive scan of the thread sums over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+    if (lane == 0) woff[wave] = off;
+    if (lane == 63) wtot[wave] = inc;
+    __syncthreads();
+    int run = inc - s;
+    for (int w = 0; w < BLK / 64; w++) { run += woff[w]; if (w < wave) run += wtot[w]; }
+#pragma unroll
+    for (int u = 0; u < SCN_ITEMS; u++) { if (base + u < n) out[base + u] = run; run += v[u]; }
+    if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == BLK - 1) *total = run;      // (items behind n count zero)
+}
+// k_flag_scan in three steps over the 64-row words: the flags of a word as its bit mask and their number; a scan of the numbers (wprefix);
+// cidx and rowlist from the masks and the prefix.  The same arrays as k_flag_scan leaves.
+__global__ __launch_bounds__(256) void k_flag_words(int m, const double *__restrict__ dw, u64 *__restrict__ bits, int *__restrict__ wcnt) {
+    const int lane = threadIdx.x & 63;
+    const int words = (m + 63) >> 6, nwaves = gridDim.x * (BLK >> 6);
+    for (int w = (blockIdx.x * BLK + threadIdx.x) >> 6; w < words; w += nwaves) {
+        const int i = w * 64 + lane;
+        const u64 b = __ballot(i < m && dw[i] != 0.0);
+        if (lane == 0) { bits[w] = b; wcnt[w] = __popcll(b); }
+    }
+}
+__global__ __launch_bounds__(256) void k_flag_apply(int m, const u64 *__restrict__ bits, const int *__restrict__ wprefix, int *__restrict__ cidx,
+                                                    int *__restrict__ rowlist) {
+    const int lane = threadIdx.x & 63;
+    const int words = (m + 63) >> 6, nwaves = gridDim.x * (BLK >> 6);
+    for (int w = (blockIdx.x * BLK + threadIdx.x) >> 6; w < words; w += nwaves) {
+        const int i = w * 64 + lane;
+        const u64 b = bits[w];
+        const int pos = wprefix[w] + __popcll(b & ((1ull << lane) - 1ull));
+        if (i < m) { cidx[i] = pos; if ((b >> lane) & 1ull) rowlist[pos] = i; }
+    }
 }
 // one wave per row: stable compaction of (ci, val) pairs whose column weight is nonzero; kept columns are
 // renumbered through `remap` (monotone, so rows stay column-sorted) and, if W16 > 0, their slab-local
@@ -866,6 +1030,111 @@ __global__ __launch_bounds__(256) void k_compact_rows_bits(int nrows, const int 
                 if (W16 > 0) ci16[pos] = (unsigned short)(cn % W16);
             }
             base += __popcll(bal);
+        }
+    }
+}
+
+// k_count_flagged_bits, one wave per row, that also delivers the row's slab pointers: the renumbering is monotone, so a kept entry of
+// original column c lies in slab t or beyond exactly when c >= rowlist[t W] (thr; no entry when t W >= k).  sp (or null: no slab kernel
+// for this matrix) receives the pointers RELATIVE to the row's start: [0, kept below slab 1, ..., all kept]; k_sp_add_rp adds the
+// row pointers once they are scanned.  The same counts as k_count_flagged_bits.
+__global__ __launch_bounds__(256) void k_count_flagged_slabs(int nrows, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                             const u64 *__restrict__ bits, int words, const int *__restrict__ rowlist, int k,
+                                                             int nslabs, int W, int *__restrict__ cnt, int *__restrict__ sp) {
+    extern __shared__ u64 sbits_cs[];
+    for (int i = threadIdx.x; i < words; i += BLK) sbits_cs[i] = bits[i];
+    int thr[PASS_SLABS_MAX];
+#pragma unroll
+    for (int t = 0; t < PASS_SLABS_MAX; t++) thr[t] = (sp && t >= 1 && t < nslabs && (long long)t * W < k) ? rowlist[t * W] : 0x7fffffff;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * BLK + threadIdx.x) >> 6;
+    const int nwaves = gridDim.x * (BLK >> 6);
+    for (int row = wave; row < nrows; row += nwaves) {
+        const int beg = rp[row], end = rp[row + 1];
+        int tot = 0, ge[PASS_SLABS_MAX];
+#pragma unroll
+        for (int t = 0; t < PASS_SLABS_MAX; t++) ge[t] = 0;
+        for (int k0 = beg; k0 < end; k0 += 64 * PASS_U) {
+            int col[PASS_U];
+#pragma unroll
+            for (int u = 0; u < PASS_U; u++) { const int e = k0 + 64 * u + lane; col[u] = e < end ? ci[e] : -1; }
+#pragma unroll
+            for (int u = 0; u < PASS_U; u++) {
+                const bool keep = col[u] >= 0 && ((sbits_cs[col[u] >> 6] >> (col[u] & 63)) & 1ull);
+                tot += __popcll(__ballot(keep));
+                if (sp) {
+#pragma unroll
+                    for (int t = 1; t < PASS_SLABS_MAX; t++) if (t < nslabs) ge[t] += __popcll(__ballot(keep && col[u] >= thr[t]));
+                }
+            }
+        }
+        if (lane == 0) {
+            cnt[row] = tot;
+            if (sp) {
+                int *o = sp + (size_t)row * (nslabs + 1);
+                o[0] = 0; o[nslabs] = tot;
+#pragma unroll
+                for (int t = 1; t < PASS_SLABS_MAX; t++) if (t < nslabs) o[t] = tot - ge[t];
+            }
+        }
+    }
+}
+__global__ void k_sp_add_rp(int nrows, int nslabs, const int *__restrict__ rp, int *__restrict__ sp) {
+    const long long total = (long long)nrows * (nslabs + 1);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) sp[i] += rp[i / (nslabs + 1)];
+}
+// k_compact_rows_bits that also writes every kept (index, value) pair at its slab-major place (sp, seg of the compact matrix are built
+// first; sp == null: no image).  The same pairs in the same places of the CSR; with an image W16 is its W and cn mod W is cn - slab W.
+__global__ __launch_bounds__(256) void k_compact_rows_bits_slab(int nrows, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                                const double *__restrict__ val, const u64 *__restrict__ bits,
+                                                                const int *__restrict__ wprefix, int words, const int *__restrict__ rp2,
+                                                                int *__restrict__ ci2, double *__restrict__ val2, int W16,
+                                                                unsigned short *__restrict__ ci16, int nslabs, int W, const int *__restrict__ sp,
+                                                                const int2 *__restrict__ seg, double *__restrict__ vsm,
+                                                                unsigned short *__restrict__ i16sm, int *__restrict__ cism, float *__restrict__ vsm32) {
+    extern __shared__ u64 sbits_cmps[];
+    int *spre = reinterpret_cast<int *>(sbits_cmps + words);
+    for (int i = threadIdx.x; i < words; i += BLK) { sbits_cmps[i] = bits[i]; spre[i] = wprefix[i]; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const u64 lt = (1ull << lane) - 1ull;
+    const int wave = (blockIdx.x * BLK + threadIdx.x) >> 6;
+    const int nwaves = gridDim.x * (BLK >> 6);
+    for (int roww = wave; roww < nrows; roww += nwaves) {
+        const int row = __builtin_amdgcn_readfirstlane(roww);
+        const int beg = rp[row], end = rp[row + 1];
+        int base = rp2[row];
+        RowSlabs rs;
+        if (sp) rs.load(sp + (size_t)row * (nslabs + 1), seg + (size_t)row * nslabs, nslabs);
+        for (int k0 = beg; k0 < end; k0 += 64 * PASS_U) {
+            int c[PASS_U]; double v[PASS_U];
+#pragma unroll
+            for (int u = 0; u < PASS_U; u++) {
+                const int e = k0 + 64 * u + lane;
+                c[u] = -1; v[u] = 0.0;
+                if (e < end) { c[u] = ci[e]; v[u] = val[e]; }
+            }
+#pragma unroll
+            for (int u = 0; u < PASS_U; u++) {
+                u64 wbits = 0; bool keep = false;
+                if (c[u] >= 0) { wbits = sbits_cmps[c[u] >> 6]; keep = (wbits >> (c[u] & 63)) & 1ull; }
+                const u64 bal = __ballot(keep);
+                if (keep) {
+                    const int pos = base + __popcll(bal & lt);
+                    const int cn = spre[c[u] >> 6] + __popcll(wbits & ((1ull << (c[u] & 63)) - 1ull));
+                    ci2[pos] = cn; val2[pos] = v[u];
+                    if (sp) {
+                        int shift; const int sl = rs.slab(pos, shift);
+                        const int cl = cn - sl * W, q = pos + shift;
+                        if (W16 > 0) ci16[pos] = (unsigned short)cl;
+                        vsm[q] = v[u];
+                        if (vsm32) vsm32[q] = (float)v[u];
+                        if (i16sm) i16sm[q] = (unsigned short)cl; else cism[q] = cl;
+                    } else if (W16 > 0) ci16[pos] = (unsigned short)(cn % W16);
+                }
+                base += __popcll(bal);
+            }
         }
     }
 }

@@ -507,7 +507,8 @@ class QPDO:
         A capped or stagnated solve raises PcgNotConverged, a NaN residual PcgNaN."""
         out, info = self._pcg_probe(dw, sigma, rhs, 1)
         return out, dict(kact=int(info[0]), iters=int(info[1]), defl_r=int(info[2]), schur=bool(info[3]), rnorm=float(info[4]),
-                         bnorm=float(info[5]), inner_solves=int(info[6]), inner_steps=int(info[7]), outer=int(info[9]))
+                         bnorm=float(info[5]), inner_solves=int(info[6]), inner_steps=int(info[7]), outer=int(info[9]),
+                         diag_from_build=bool(info[10]))
 
     _COMPACT_VECS = {"rowlist": (49, np.int32, "k"), "cidx": (50, np.int32, "m"), "dc": (51, np.float64, "k"),
                      "flag_bits": (52, np.uint64, "words"), "flag_wprefix": (53, np.int32, "words"), "pc_diag": (54, np.float64, "n"),
@@ -542,6 +543,27 @@ class QPDO:
         r["ci16"] = self._compact_get(base + 4, np.uint16, r["nnz"]) if r["has_ci16"] else None
         r["sp"] = self._compact_get(base + 5, np.int32, r["nrows"] * (r["nslabs"] + 1)).reshape(r["nrows"], r["nslabs"] + 1) if r["use_slab"] else None
         return r
+
+    def download_compact_image(self, name):
+        """the slab-major image of "Arc" or "Atc" as the slab kernel streams it (qpdo_amd_download_compact, which >= 64): seg as an
+        nrows x nslabs x 2 array of (start, length), vsm, and the slab-local indices; None where the matrix takes the plain kernel"""
+        mat = {"Arc": 0, "Atc": 1}[name]
+        g = self._compact_get(16 * mat, np.int64, 7)
+        nrows, nnz, use_slab, nslabs, has_ci16 = int(g[0]), int(g[2]), int(g[3]), int(g[4]), int(g[6])
+        if not use_slab:
+            return None
+        base = 64 + 16 * mat
+        return dict(seg=self._compact_get(base, np.int32, 2 * nrows * nslabs).reshape(nrows, nslabs, 2),
+                    vsm=self._compact_get(base + 1, np.float64, nnz),
+                    idx=self._compact_get(base + 2, np.uint16 if has_ci16 else np.int32, nnz))
+
+    def download_linesearch_order(self):
+        """the breakpoint indices as the last linesearch's radix sort left them (qpdo_amd_download_compact, which 60)"""
+        return self._compact_get(60, np.uint32, 2 * self.m)
+
+    def rebuild_compact_images(self):
+        """marks the images of the compact matrices stale and runs one product with each, which rebuilds them from the CSR arrays"""
+        self._compact_get(96, np.int32, 0)
 
     def factor_geometry(self):
         g = np.zeros(4)
