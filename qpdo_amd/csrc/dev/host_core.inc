@@ -183,17 +183,22 @@ static inline double nrm_of(const Ctrl *c, int slot) {
     double v; u64 b = c->nrm[slot]; memcpy(&v, &b, 8); return v;
 }
 #define LAUNCH(kernel, grid, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLK), 0, d->stream, __VA_ARGS__)
-// exclusive scan of cnt[0 .. n) into out[0 .. n), the total into *total (or nowhere): tile sums, then every tile's own scan behind the sums
-// in front of it (spmv.inc k_scn_sums / k_scn_apply; scratch of the workspace, no allocation)
-static void dev_scan(QpdoDev *d, const int *cnt, int n, int *out, int *total) {
-    const int nt = n > 0 ? (n + SCN_TILE - 1) / SCN_TILE : 1;
-    if (nt > 1) LAUNCH(k_scn_sums, nt, cnt, n, d->scan_tsum);
-    LAUNCH(k_scn_apply, nt, cnt, n, (const int *)d->scan_tsum, out, total);
+// ---- the integer scan and the sorting pass (dev/scan_sort.inc) ----------------------------------------------------------------------
+// exclusive scan of cnt[0 .. n) into out[0 .. n) (cnt == out: in place), the total into *total (or nowhere): tile sums, then every tile's
+// own scan behind the sums in front of it.  tsum: scratch of scan_tiles(n) ints (a pass: d->scan_tsum; the set-up: its TempAllocs)
+static inline int scan_tiles(int n) { return n > 0 ? (int)(((long long)n + SCN_TILE - 1) / SCN_TILE) : 1; }
+static void dev_scan(QpdoDev *d, const int *cnt, int n, int *out, int *total, int *tsum) {
+    const int nt = scan_tiles(n);
+    if (nt > 1) LAUNCH(k_scn_sums, nt, cnt, n, tsum);
+    LAUNCH(k_scn_apply, nt, cnt, n, (const int *)tsum, out, total);
 }
-// row counts to row pointers: out[0 .. n] (QPDO_GRID_SCANS=0: the one-workgroup kernel)
-static void scan_counts(QpdoDev *d, const int *cnt, int n, int *out) {
-    if (d->grid_scans) dev_scan(d, cnt, n, out, out + n);
-    else hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, cnt, n, out);
+// one pass of the stable sort of N (key, payload) pairs by the keys' 8-bit digit at `shift`: histogram of the nblocks = ceil(N / (BLK ITEMS))
+// tiles, its scan in place, scatter.  hist: 256 nblocks ints; vin == NULL: the payload is the position
+template <class K, int ITEMS, class I>
+static void radix_pass(QpdoDev *d, const K *kin, const u32 *vin, K *kout, u32 *vout, I N, int shift, int nblocks, int *hist, int *tsum) {
+    LAUNCH((k_radix_hist<K, ITEMS, I>), nblocks, kin, N, shift, nblocks, hist);
+    dev_scan(d, hist, 256 * nblocks, hist, (int *)nullptr, tsum);
+    LAUNCH((k_radix_scatter<K, ITEMS, I>), nblocks, kin, vin, kout, vout, N, shift, nblocks, (const int *)hist);
 }
 
 // ---- collectives ----------------------------------------------------------------------------------------
@@ -274,17 +279,6 @@ struct TempAllocs {                       // device scratch of the setup convers
     template <class T> int get(T **p, size_t count) { void *q = nullptr; if (hipMalloc(&q, (count ? count : 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return -1; } v.push_back(q); *p = (T *)q; return 0; }
     void release(hipStream_t st) { if (!v.empty()) (void)hipStreamSynchronize(st); for (void *q : v) (void)hipFree(q); v.clear(); }
 };
-// exclusive scan of a[0 .. total) in place
-static int dev_exclusive_scan(QpdoDev *d, TempAllocs &tmp, int *a, long long total) {
-    if (total <= 0) return 0;
-    const int ntiles = (int)((total + SC_TILE - 1) / SC_TILE);
-    int *tsum = nullptr, *toff = nullptr;
-    if (tmp.get(&tsum, (size_t)ntiles) || tmp.get(&toff, (size_t)ntiles + 1)) return set_err(hipErrorOutOfMemory, "setup scratch", __LINE__);
-    hipLaunchKernelGGL(k_sc_tile_sums, dim3(ntiles), dim3(1024), 0, d->stream, (const int *)a, total, tsum);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, (const int *)tsum, ntiles, toff);
-    hipLaunchKernelGGL(k_sc_tile_scan, dim3(ntiles), dim3(1024), 0, d->stream, a, total, (const int *)toff);
-    return 0;
-}
 // dst = transpose of src as CSR, rows sorted by (source) major index: stable LSD radix sort of the entry positions by minor index
 // perm_out != nullptr (N entries): also the final payload of the sort, perm_out[k] = the source position of entry k of dst
 static int dev_transpose(QpdoDev *d, TempAllocs &tmp, const DevCsr &src, DevCsr *dst, bool temp_dst, u32 *perm_out = nullptr) {
@@ -301,25 +295,22 @@ static int dev_transpose(QpdoDev *d, TempAllocs &tmp, const DevCsr &src, DevCsr 
     }
     dst->tpr = pick_tpr(*dst);
     if (N == 0 || T == 0) return 0;
-    hipLaunchKernelGGL(k_tr_count, dim3(2048), dim3(BLK), 0, d->stream, N, (const int *)src.ci, dst->rp);
-    rc = dev_exclusive_scan(d, tmp, dst->rp, (long long)T); if (rc) return rc;
-    { const int Ni = (int)N; HIPCHK(hipMemcpyAsync(dst->rp + T, &Ni, sizeof(int), hipMemcpyHostToDevice, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); }
     int bits = 1; while (bits < 31 && (1ll << bits) < (long long)T) bits++;
     const int passes = (bits + 7) / 8;
     const int nblocks = (int)((N + RT_TILE - 1) / RT_TILE);
-    u32 *kb[2] = {nullptr, nullptr}, *pb[2] = {nullptr, nullptr}, *major = nullptr; int *hist = nullptr;
+    const int tiles = scan_tiles(T) > scan_tiles(256 * nblocks) ? scan_tiles(T) : scan_tiles(256 * nblocks);
+    u32 *kb[2] = {nullptr, nullptr}, *pb[2] = {nullptr, nullptr}, *major = nullptr; int *hist = nullptr, *tsum = nullptr;
     if (tmp.get(&pb[0], (size_t)N) || tmp.get(&pb[1], (size_t)N) || tmp.get(&major, (size_t)N) || tmp.get(&hist, (size_t)256 * nblocks) ||
-        (passes > 1 && (tmp.get(&kb[0], (size_t)N) || tmp.get(&kb[1], (size_t)N))))
+        tmp.get(&tsum, (size_t)tiles) || (passes > 1 && (tmp.get(&kb[0], (size_t)N) || tmp.get(&kb[1], (size_t)N))))
         return set_err(hipErrorOutOfMemory, "setup scratch (transposition)", __LINE__);
+    hipLaunchKernelGGL(k_tr_count, dim3(2048), dim3(BLK), 0, d->stream, N, (const int *)src.ci, dst->rp);
+    dev_scan(d, dst->rp, T, dst->rp, dst->rp + T, tsum);            // (the total is N: every entry was counted)
     hipLaunchKernelGGL(k_expand_rows, dim3(2048), dim3(BLK), 0, d->stream, src.nrows, (const int *)src.rp, major);
     const u32 *kin = (const u32 *)src.ci, *vin = nullptr;
     int cur = 0;
     for (int p = 0; p < passes; p++) {
-        const int shift = 8 * p;
-        hipLaunchKernelGGL(k_rt_hist, dim3(nblocks), dim3(BLK), 0, d->stream, kin, N, shift, nblocks, hist);
-        rc = dev_exclusive_scan(d, tmp, hist, (long long)256 * nblocks); if (rc) return rc;
         u32 *kout = passes > 1 ? kb[cur] : pb[cur ^ 1];                // (a single pass: the keys go nowhere useful; reuse the spare payload buffer)
-        hipLaunchKernelGGL(k_rt_scatter, dim3(nblocks), dim3(BLK), 0, d->stream, kin, vin, kout, pb[cur], N, shift, nblocks, (const int *)hist);
+        radix_pass<u32, RT_ITEMS, long long>(d, kin, vin, kout, pb[cur], N, 8 * p, nblocks, hist, tsum);
         kin = kout; vin = pb[cur]; cur ^= 1;
     }
     hipLaunchKernelGGL(k_tr_gather, dim3(2048), dim3(BLK), 0, d->stream, N, vin, (const u32 *)major, (const double *)src.val, dst->ci, dst->val);

@@ -13,19 +13,17 @@ static int build_compact(QpdoDev *d) {
     const double *dl = d->d + d->m0;
     d->kact = 0; d->sdiag_valid = 0;
     if (m == 0) return 0;
-    if (d->grid_scans) {                 // (the words' counts pass through row_cnt, which the row counts below overwrite)
-        const int fwords = (m + 63) / 64;
-        LAUNCH(k_flag_words, (fwords + 3) / 4, m, dl, d->flag_bits, d->row_cnt);
-        dev_scan(d, d->row_cnt, fwords, d->flag_wprefix, d->kcount);
-        LAUNCH(k_flag_apply, (fwords + 3) / 4, m, (const u64 *)d->flag_bits, (const int *)d->flag_wprefix, d->cidx, d->rowlist);
-    } else hipLaunchKernelGGL(k_flag_scan, dim3(1), dim3(1024), 0, d->stream, m, dl, d->cidx, d->rowlist, d->kcount, d->flag_bits, d->flag_wprefix);
+    const int fwords = (m + 63) / 64;     // (the words' counts pass through row_cnt, which the row counts below overwrite)
+    LAUNCH(k_flag_words, (fwords + 3) / 4, m, dl, d->flag_bits, d->row_cnt);
+    dev_scan(d, d->row_cnt, fwords, d->flag_wprefix, d->kcount, d->scan_tsum);
+    LAUNCH(k_flag_apply, (fwords + 3) / 4, m, (const u64 *)d->flag_bits, (const int *)d->flag_wprefix, d->cidx, d->rowlist);
     int k = 0;
     HIPCHK(hipMemcpyAsync(&k, d->kcount, sizeof(int), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     if (k <= 0) return 0;
     // A_c: rows
     LAUNCH(k_gather_rowinfo, vgrid(k), k, (const int *)d->rowlist, d->Ar.rp, dl, d->row_cnt, d->dc);
-    scan_counts(d, d->row_cnt, k, d->Arc.rp);
+    dev_scan(d, d->row_cnt, k, d->Arc.rp, d->Arc.rp + k, d->scan_tsum);
     DevCsr &R = d->Arc;
     R.nrows = k; R.ncols = n; R.tpr = d->Ar.tpr; R.use_slab = d->Ar.use_slab && k >= 4096; R.slab_ovl = d->Ar.slab_ovl; R.slab_nt = d->Ar.slab_nt;
     int RW16 = 0;
@@ -83,7 +81,7 @@ static int build_compact(QpdoDev *d) {
         int *spT = T.use_slab ? T.sp : (int *)nullptr;
         hipLaunchKernelGGL(k_count_flagged_slabs, dim3(2048), dim3(BLK), (size_t)words * 8, d->stream, n, M.rp, M.ci, (const u64 *)d->flag_bits, words,
                            (const int *)d->rowlist, k, T.nslabs, T.W, d->row_cnt, spT);
-        scan_counts(d, d->row_cnt, n, T.rp);
+        dev_scan(d, d->row_cnt, n, T.rp, T.rp + n, d->scan_tsum);
         if (spT) {
             LAUNCH(k_sp_add_rp, vgrid(n), n, T.nslabs, (const int *)T.rp, T.sp);
             hipLaunchKernelGGL(k_slab_seg, dim3(T.slab_grid), dim3(1024), 0, d->stream, T.nrows, T.nslabs, T.rows_per_wg, (const int *)T.sp, T.seg);
@@ -93,12 +91,12 @@ static int build_compact(QpdoDev *d) {
                            T.nslabs, T.W, (const int *)spT, (const int2 *)T.seg, T.vsm, T.i16sm, T.cism, T.vsm32);
     } else if (lds_tab <= 60 * 1024) {          // flags and renumbering as LDS tables: the kernels stream the matrix only
         DISPATCH_TPR_LDS(M, k_count_flagged_bits, g, (size_t)words * 8, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt);
-        scan_counts(d, d->row_cnt, n, T.rp);
+        dev_scan(d, d->row_cnt, n, T.rp, T.rp + n, d->scan_tsum);
         hipLaunchKernelGGL(k_compact_rows_bits, dim3(2048), dim3(BLK), lds_tab, d->stream, n, M.rp, M.ci, M.val, (const u64 *)d->flag_bits,
                            (const int *)d->flag_wprefix, words, (const int *)T.rp, T.ci, T.val, W16, M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr);
     } else {
         DISPATCH_TPR(M, k_count_flagged, g, n, M.rp, M.ci, dl, d->row_cnt);
-        scan_counts(d, d->row_cnt, n, T.rp);
+        dev_scan(d, d->row_cnt, n, T.rp, T.rp + n, d->scan_tsum);
         LAUNCH(k_compact_rows, 2048, n, M.rp, M.ci, M.val, dl, (const int *)T.rp, T.ci, T.val, (const int *)d->cidx, W16,
                M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr);
     }
@@ -168,7 +166,7 @@ static int defl_build(QpdoDev *d) {
     const int gAt = rowloop_grid(d->At);
     DISPATCH_TPR(d->At, k_jacobi_diag2, gAt, n, T.rp, T.ci, T.val, (const double *)d->tmp_m, (const double *)d->dc, (const double *)d->qdiag, d->sigma_f, d->pc_diag);
     DISPATCH_TPR(d->At, k_count_flagged, gAt, n, T.rp, T.ci, (const double *)d->defl_flag, d->row_cnt);
-    scan_counts(d, d->row_cnt, n, d->Ath.rp);
+    dev_scan(d, d->row_cnt, n, d->Ath.rp, d->Ath.rp + n, d->scan_tsum);
     LAUNCH(k_compact_rows, 2048, n, T.rp, T.ci, T.val, (const double *)d->defl_flag, (const int *)d->Ath.rp, d->Ath.ci, d->Ath.val,
            (const int *)nullptr, 0, (unsigned short *)nullptr);
     d->Ath.nrows = n; d->Ath.ncols = k; d->Ath.tpr = 4; d->Ath.use_slab = 0; d->Ath.nnz = (long long)r * d->max_row_nnz_A;

@@ -31,15 +31,15 @@ int qdev_create_csc(QpdoDev **out, int device, int32_t n, int32_t m, const QdevC
             DevCsr S, R;
             rc = upload_csc_as_csr_of_transpose(d, tmp, &S, Q, true);
             if (!rc) rc = dev_transpose(d, tmp, S, &R, true);
-            int *cnt = nullptr;
-            if (!rc && tmp.get(&cnt, (size_t)n + 1)) rc = set_err(hipErrorOutOfMemory, "setup scratch", __LINE__);
+            int *cnt = nullptr, *tsum = nullptr;
+            if (!rc && (tmp.get(&cnt, (size_t)n + 1) || tmp.get(&tsum, (size_t)scan_tiles(n)))) rc = set_err(hipErrorOutOfMemory, "setup scratch", __LINE__);
             if (!rc) {
                 d->Qf.nrows = d->Qf.ncols = n;
                 rc = dev_alloc(d, &d->Qf.rp, (size_t)n + 1);
             }
             if (!rc) {
                 hipLaunchKernelGGL(k_sym_count, dim3(vgrid(n)), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const int *)S.rp, (const int *)S.ci, cnt);
-                hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, (const int *)cnt, n, d->Qf.rp);
+                dev_scan(d, cnt, n, d->Qf.rp, d->Qf.rp + n, tsum);
                 int total = 0;
                 e = hipMemcpyAsync(&total, d->Qf.rp + n, sizeof(int), hipMemcpyDeviceToHost, d->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
@@ -171,7 +171,6 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         d->Atc.vsm = nullptr; d->Atc.i16sm = nullptr; d->Atc.cism = nullptr; d->Atc.seg = nullptr; d->Atc.vsm32 = nullptr;
         { const char *f32 = getenv("QPDO_PCG_INNER_F32"); d->inner_f32 = (f32 && atoi(f32) != 0) ? 1 : 0; }
         { const char *fo = getenv("QPDO_INNER_FOLD"); d->inner_fold = !(fo && *fo && atoi(fo) == 0); }
-        { const char *gs = getenv("QPDO_GRID_SCANS"); d->grid_scans = !(gs && *gs && atoi(gs) == 0); }
         { const char *co = getenv("QPDO_COMPACT_ONE_READ"); d->compact_one_read = !(co && *co && atoi(co) == 0); }
         { const char *ct = getenv("QPDO_COMPACT_T_ONE_READ"); d->compact_t_one_read = !(ct && *ct && atoi(ct) == 0); }
         rc = dev_alloc(d, &d->Arc.rp, (size_t)m + 1);

@@ -49,12 +49,8 @@ static int linesearch_device(QpdoDev *d, int pm, int pn) {
     }
     int cur = 0;
     for (int pass = 0; pass < 8; pass++) {
-        const int shift = 8 * pass;
-        LAUNCH(k_rs_hist, d->rs_nblocks, d->ls_key[cur], M2, shift, d->rs_nblocks, d->rs_hist);
-        if (d->grid_scans) dev_scan(d, d->rs_hist, 256 * d->rs_nblocks, d->rs_hist, (int *)nullptr);      // in place; consecutive items per thread
-        else hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, d->stream, d->rs_hist, 256 * d->rs_nblocks);
-        LAUNCH(k_rs_scatter, d->rs_nblocks, d->ls_key[cur], d->ls_idx[cur], d->ls_key[1 - cur], d->ls_idx[1 - cur], M2, shift,
-               d->rs_nblocks, d->rs_hist);
+        radix_pass<u64, RS_ITEMS, int>(d, d->ls_key[cur], d->ls_idx[cur], d->ls_key[1 - cur], d->ls_idx[1 - cur], M2, 8 * pass, d->rs_nblocks,
+                                       d->rs_hist, d->scan_tsum);
         cur = 1 - cur;
     }
     // 8 passes: result back in buffer 0

@@ -134,15 +134,15 @@ int qdev_update_matrices(QpdoDev *d, const QdevCsc *A, const QdevCsc *Q, const d
             if (!rc && differs) rc = pattern_error("Q");
         }
         if (!rc && firstQ && Q->stype != 0) {                  // one stored triangle: setup's symmetric expansion with index payloads
-            DevCsr S, R; int *cnt = nullptr, *orp = nullptr, *oci = nullptr; u32 *permR = nullptr, *iota = nullptr;
+            DevCsr S, R; int *cnt = nullptr, *tsum = nullptr, *orp = nullptr, *oci = nullptr; u32 *permR = nullptr, *iota = nullptr;
             rc = upload_csc_as_csr_of_transpose(d, tmp, &S, Q, true, false);
-            if (!rc && (tmp.get(&permR, (size_t)S.nnz) || tmp.get(&iota, (size_t)S.nnz) || tmp.get(&cnt, (size_t)n + 1) || tmp.get(&orp, (size_t)n + 1)))
+            if (!rc && (tmp.get(&permR, (size_t)S.nnz) || tmp.get(&iota, (size_t)S.nnz) || tmp.get(&cnt, (size_t)n + 1) || tmp.get(&tsum, (size_t)scan_tiles(n)) || tmp.get(&orp, (size_t)n + 1)))
                 rc = set_err(hipErrorOutOfMemory, "update scratch", __LINE__);
             if (!rc) rc = dev_transpose(d, tmp, S, &R, true, permR);
             int total = 0;
             if (!rc) {
                 hipLaunchKernelGGL(k_sym_count, dim3(vgrid(n)), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const int *)S.rp, (const int *)S.ci, cnt);
-                hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, d->stream, (const int *)cnt, n, orp);
+                dev_scan(d, cnt, n, orp, orp + n, tsum);
                 hipError_t e = hipMemcpyAsync(&total, orp + n, sizeof(int), hipMemcpyDeviceToHost, d->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
                 if (e != hipSuccess) rc = set_err(e, "symmetric expansion", __LINE__);

@@ -2,78 +2,12 @@
 // ------------------------------------------------------------------------------------------------
 // Exact linesearch (linesearch.c:74-158): stable LSD radix sort of the 2m breakpoints on the
 // 64-bit pattern of t (positive doubles order as unsigned integers; non-candidates carry a
-// sentinel key and sort last; ties keep index order like glibc's merge-sort qsort), then an
-// exclusive scan of the slope/intercept increments and a first-crossing search.
+// sentinel key and sort last; ties keep index order like glibc's merge-sort qsort; the sorting
+// pass is scan_sort.inc's), then an exclusive scan of the slope/intercept increments and a
+// first-crossing search.
 // ------------------------------------------------------------------------------------------------
-static const int RS_ITEMS = 8;                       // keys per thread per tile
+static const int RS_ITEMS = 8;                       // keys per thread per tile of the sort
 static const int RS_TILE = BLK * RS_ITEMS;           // 2048
-
-__global__ __launch_bounds__(256) void k_rs_hist(const u64 *__restrict__ keys, int N, int shift, int nblocks, int *__restrict__ hist) {
-    __shared__ int lh[256];
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-    const int base = blockIdx.x * RS_TILE;
-    for (int r = 0; r < RS_ITEMS; r++) {
-        const int i = base + r * BLK + threadIdx.x;
-        if (i < N) atomicAdd(&lh[(int)((keys[i] >> shift) & 255ull)], 1);
-    }
-    __syncthreads();
-    hist[threadIdx.x * nblocks + blockIdx.x] = lh[threadIdx.x];
-}
-// exclusive scan of hist (digit-major, length 256*nblocks) by one block
-// exclusive scan of the digit histograms (integers: any association gives the same result).  1024 threads, contiguous chunk per thread,
-// thread totals scanned with wave shuffles + 16 wave totals (the 256-thread version with a serial scan of the totals took 85 us at 2m = 4e5)
-__global__ __launch_bounds__(1024) void k_rs_scan(int *__restrict__ hist, int total) {
-    __shared__ int wtot[16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int chunk = (total + 1023) / 1024;
-    const int beg = min(tid * chunk, total), end = min(beg + chunk, total);
-    int s = 0;
-#pragma unroll 4
-    for (int i = beg; i < end; i++) s += hist[i];
-    int inc = s;                                              // inclusive scan over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int run = inc - s;
-    for (int q = 0; q < wave; q++) run += wtot[q];
-    for (int i = beg; i < end; i++) { const int t = hist[i]; hist[i] = run; run += t; }
-}
-__global__ __launch_bounds__(256) void k_rs_scatter(const u64 *__restrict__ kin, const u32 *__restrict__ vin, u64 *__restrict__ kout,
-                                                    u32 *__restrict__ vout, int N, int shift, int nblocks,
-                                                    const int *__restrict__ hist) {
-    __shared__ int base[256];
-    __shared__ int cnt[4][256];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    base[tid] = hist[tid * nblocks + blockIdx.x];
-    const int tile = blockIdx.x * RS_TILE;
-    for (int r = 0; r < RS_ITEMS; r++) {
-        for (int w = 0; w < 4; w++) cnt[w][tid] = 0;
-        __syncthreads();
-        const int i = tile + r * BLK + tid;
-        const bool valid = i < N;
-        u64 key = 0; u32 val = 0; int dig = 0;
-        if (valid) { key = kin[i]; val = vin[i]; dig = (int)((key >> shift) & 255ull); }
-        u64 peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const u64 bal = __ballot(valid && ((dig >> b) & 1));
-            peers &= ((dig >> b) & 1) ? bal : ~bal;
-        }
-        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0) cnt[wave][dig] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            int off = base[dig] + rank;
-            for (int w = 0; w < wave; w++) off += cnt[w][dig];
-            kout[off] = key; vout[off] = val;
-        }
-        __syncthreads();
-        base[tid] += cnt[0][tid] + cnt[1][tid] + cnt[2][tid] + cnt[3][tid];
-        __syncthreads();
-    }
-}
 
 static const int LS_ITEMS = 4;
 static const int LS_TILE = BLK * LS_ITEMS;           // 1024 breakpoints per block

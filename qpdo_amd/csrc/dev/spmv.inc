@@ -714,37 +714,6 @@ __global__ void k_extract_diag(int n, const int *__restrict__ rp, const int *__r
     }
 }
 
-// compact index space of a Newton pass: cidx[i] = number of weighted rows before i, rowlist = their ids; also the flags as a bit mask
-// (bits[w] bit b = row 64 w + b carries weight) and wprefix[w] = cidx[64 w].  One block; wave q owns a contiguous range of 64-row words:
-// coalesced loads and ballots, no barrier inside the two sweeps (the former version walked per-thread chunks: 0.45 ms at m = 2e5).
-__global__ __launch_bounds__(1024) void k_flag_scan(int m, const double *__restrict__ dw, int *__restrict__ cidx, int *__restrict__ rowlist,
-                                                    int *__restrict__ count, u64 *__restrict__ bits, int *__restrict__ wprefix) {
-    __shared__ int wtot[16];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int words = (m + 63) >> 6, wseg = (words + 15) / 16;
-    const int w0 = wave * wseg, w1 = min(w0 + wseg, words);
-    int c = 0;
-    for (int w = w0; w < w1; w++) {
-        const int i = w * 64 + lane;
-        const u64 b = __ballot(i < m && dw[i] != 0.0);
-        c += __popcll(b);
-        if (lane == 0) bits[w] = b;
-    }
-    if (lane == 0) wtot[wave] = c;
-    __syncthreads();
-    int run = 0;
-    for (int q = 0; q < wave; q++) run += wtot[q];
-    if (threadIdx.x == 0) { int t = 0; for (int q = 0; q < 16; q++) t += wtot[q]; *count = t; }
-    for (int w = w0; w < w1; w++) {
-        const int i = w * 64 + lane;
-        const bool f = i < m && dw[i] != 0.0;
-        const u64 b = __ballot(f);
-        const int pos = run + __popcll(b & ((1ull << lane) - 1ull));
-        if (i < m) { cidx[i] = pos; if (f) rowlist[pos] = i; }
-        if (lane == 0) wprefix[w] = run;
-        run += __popcll(b);
-    }
-}
 __global__ void k_gather_rowinfo(int k, const int *__restrict__ rowlist, const int *__restrict__ rp, const double *__restrict__ dw,
                                  int *__restrict__ cnt, double *__restrict__ dc) {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < k; j += gridDim.x * blockDim.x) {
@@ -895,64 +864,9 @@ __global__ __launch_bounds__(256) void k_count_flagged_bits(int nrows, const int
         if (lane == 0) cnt[row] = c;
     }
 }
-// exclusive scan of cnt[0..n) into out[0..n] by one block (n up to a few 1e5)
-__global__ __launch_bounds__(1024) void k_scan_counts(const int *__restrict__ cnt, int n, int *__restrict__ out) {
-    __shared__ int sums[1024];
-    const int chunk = (n + 1023) / 1024;
-    const int beg = threadIdx.x * chunk, end = min(beg + chunk, n);
-    int s = 0;
-    for (int i = beg; i < end; i++) s += cnt[i];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { int run = 0; for (int i = 0; i < 1024; i++) { int t = sums[i]; sums[i] = run; run += t; } out[n] = run; }
-    __syncthreads();
-    int run = sums[threadIdx.x];
-    for (int i = beg; i < end; i++) { out[i] = run; run += cnt[i]; }
-}
-// The same scan on many workgroups, none of which waits for another: tile sums in one launch; in the next every workgroup adds up the sums
-// of the tiles in front of its own and scans its tile (one tile: that launch alone).  Integers: any association gives the same result.
-// cnt and out may be the same array (every thread holds its items in registers before it stores); total (or null) receives the grand total.
-// (Every tile re-adds the sums in front of it: quadratic in the number of tiles, which is about 100 at the largest per-pass scan; a
-// scan over many thousands of tiles wants a scan of the sums in between, as dev_exclusive_scan of the setup has.)
-static const int SCN_ITEMS = 8;
-static const int SCN_TILE = BLK * SCN_ITEMS;         // 2048
-__global__ __launch_bounds__(256) void k_scn_sums(const int *__restrict__ cnt, int n, int *__restrict__ tsum) {
-    __shared__ int ws[BLK / 64];
-    const int base = blockIdx.x * SCN_TILE + threadIdx.x * SCN_ITEMS;
-    int s = 0;
-#pragma unroll
-    for (int u = 0; u < SCN_ITEMS; u++) if (base + u < n) s += cnt[base + u];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < BLK / 64; w++) t += ws[w]; tsum[blockIdx.x] = t; }
-}
-__global__ __launch_bounds__(256) void k_scn_apply(const int *cnt, int n, const int *__restrict__ tsum, int *out, int *__restrict__ total) {
-    __shared__ int woff[BLK / 64], wtot[BLK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int off = 0;                                              // the tiles in front of this one
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += BLK) off += tsum[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) off += __shfl_down(off, o, 64);
-    const int base = blockIdx.x * SCN_TILE + threadIdx.x * SCN_ITEMS;
-    int v[SCN_ITEMS], s = 0;
-#pragma unroll
-    for (int u = 0; u < SCN_ITEMS; u++) { v[u] = base + u < n ? cnt[base + u] : 0; s += v[u]; }
-    int inc = s;                                              // inclusive scan of the thread sums over the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 0) woff[wave] = off;
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int run = inc - s;
-    for (int w = 0; w < BLK / 64; w++) { run += woff[w]; if (w < wave) run += wtot[w]; }
-#pragma unroll
-    for (int u = 0; u < SCN_ITEMS; u++) { if (base + u < n) out[base + u] = run; run += v[u]; }
-    if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == BLK - 1) *total = run;      // (items behind n count zero)
-}
-// k_flag_scan in three steps over the 64-row words: the flags of a word as its bit mask and their number; a scan of the numbers (wprefix);
-// cidx and rowlist from the masks and the prefix.  The same arrays as k_flag_scan leaves.
+// compact index space of a Newton pass: cidx[i] = number of weighted rows before i, rowlist = their ids; also the flags as a bit mask
+// (bits[w] bit b = row 64 w + b carries weight) and wprefix[w] = cidx[64 w].  Three steps over the 64-row words: the flags of a word as
+// its bit mask and their number; a scan of the numbers (dev_scan: wprefix); cidx and rowlist from the masks and the prefix.
 __global__ __launch_bounds__(256) void k_flag_words(int m, const double *__restrict__ dw, u64 *__restrict__ bits, int *__restrict__ wcnt) {
     const int lane = threadIdx.x & 63;
     const int words = (m + 63) >> 6, nwaves = gridDim.x * (BLK >> 6);

@@ -64,11 +64,10 @@ struct QpdoDev {
     int *row_cnt = nullptr, *cidx = nullptr, *rowlist = nullptr, *kcount = nullptr; int kact = 0;
     u64 *flag_bits = nullptr; int *flag_wprefix = nullptr;      // the pass's weighted rows as a bit mask + per-word prefix (LDS tables of the compaction)
     double *dc = nullptr, *tc = nullptr; int lds_doubles_At = 0;
-    // per-pass set-up (build_compact, the linesearch sort), each switch read at setup; 0 selects the former sequence, the same bits:
-    int grid_scans = 1;       // QPDO_GRID_SCANS: the integer scans (row pointers, flags, radix histograms) on many workgroups instead of one
+    // per-pass set-up (build_compact), each switch read at setup; 0 selects the former sequence, the same bits:
     int compact_one_read = 1; // QPDO_COMPACT_ONE_READ: A_c's CSR copy, slab image and Schur diagonal from one read of the weighted rows
     int compact_t_one_read = 1; // QPDO_COMPACT_T_ONE_READ: A_c' the same way: slab pointers from the counting pass, CSR and image from one compaction
-    int *scan_tsum = nullptr; // tile sums of the scans
+    int *scan_tsum = nullptr; // tile sums of a pass's scans (dev_scan)
     int sdiag_valid = 0; double sdiag_sigma = 0.0;      // s_diag holds this pass's Schur diagonal, formed with that sigma_f
     int sdiag_from_build = 0;                           // the last pcg_schur_solve took that diagonal instead of running k_schur_diag (probe: info[10])
     double *qdiag = nullptr; int qdiag_valid = 0;

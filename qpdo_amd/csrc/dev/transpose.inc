@@ -10,7 +10,7 @@
 //     qpdo_api.c sym_to_full_csr).
 // Integer work only; the arrays are bit-for-bit those of the host path (tests: test_device_setup_matches_host_setup).
 // ------------------------------------------------------------------------------------------------
-static const int RT_ITEMS = 32;                      // keys per thread per block
+static const int RT_ITEMS = 32;                      // keys per thread per block of the sort (scan_sort.inc)
 static const int RT_TILE = BLK * RT_ITEMS;           // 8192 keys per block
 
 __global__ void k_narrow_i64(long long n, const long long *__restrict__ in, int *__restrict__ out) {
@@ -25,89 +25,6 @@ __global__ __launch_bounds__(256) void k_expand_rows(int nrows, const int *__res
     const int wave = (blockIdx.x * BLK + threadIdx.x) >> 6, nwaves = gridDim.x * (BLK / 64);
     for (int r = wave; r < nrows; r += nwaves)
         for (int k = rp[r] + lane; k < rp[r + 1]; k += 64) out[k] = (u32)r;
-}
-__global__ __launch_bounds__(256) void k_rt_hist(const u32 *__restrict__ keys, long long N, int shift, int nblocks, int *__restrict__ hist) {
-    __shared__ int lh[256];
-    lh[threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * RT_TILE;
-    for (int r = 0; r < RT_ITEMS; r++) {
-        const long long i = base + (long long)r * BLK + threadIdx.x;
-        if (i < N) atomicAdd(&lh[(int)((keys[i] >> shift) & 255u)], 1);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * nblocks + blockIdx.x] = lh[threadIdx.x];
-}
-// exclusive scan of a long integer array in three launches (tile sums, scan of the tile sums by one block, rescan with offsets);
-// integers: any association gives the same result
-static const int SC_TILE = 1024 * 64;
-__global__ __launch_bounds__(1024) void k_sc_tile_sums(const int *__restrict__ a, long long total, int *__restrict__ tsum) {
-    __shared__ int ws[16];
-    const long long beg = (long long)blockIdx.x * SC_TILE;
-    int s = 0;
-    for (int q = 0; q < 64; q++) { const long long i = beg + (long long)q * 1024 + threadIdx.x; if (i < total) s += a[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < 16; w++) t += ws[w]; tsum[blockIdx.x] = t; }
-}
-__global__ __launch_bounds__(1024) void k_sc_tile_scan(int *__restrict__ a, long long total, const int *__restrict__ toff) {
-    // tile = 64 rows of 1024 consecutive elements; row q is scanned across the block with wave shuffles, rows one after the other
-    __shared__ int wtot[16]; __shared__ int carry;
-    const long long beg = (long long)blockIdx.x * SC_TILE;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = toff[blockIdx.x];
-    __syncthreads();
-    for (int q = 0; q < 64; q++) {
-        const long long i = beg + (long long)q * 1024 + threadIdx.x;
-        const int v = i < total ? a[i] : 0;
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        int run = carry + inc - v;
-        for (int w = 0; w < wave; w++) run += wtot[w];
-        if (i < total) a[i] = run;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = run + v;
-        __syncthreads();
-    }
-}
-// one pass of the stable sort: (key, pos) pairs of block b go to the slots their digit owns; pos_in == NULL: the position is the index
-__global__ __launch_bounds__(256) void k_rt_scatter(const u32 *__restrict__ kin, const u32 *__restrict__ vin, u32 *__restrict__ kout,
-                                                    u32 *__restrict__ vout, long long N, int shift, int nblocks, const int *__restrict__ hist) {
-    __shared__ int base[256];
-    __shared__ int cnt[4][256];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    base[tid] = hist[(size_t)tid * nblocks + blockIdx.x];
-    const long long tile = (long long)blockIdx.x * RT_TILE;
-    for (int r = 0; r < RT_ITEMS; r++) {
-        for (int w = 0; w < 4; w++) cnt[w][tid] = 0;
-        __syncthreads();
-        const long long i = tile + (long long)r * BLK + tid;
-        const bool valid = i < N;
-        u32 key = 0, val = 0; int dig = 0;
-        if (valid) { key = kin[i]; val = vin ? vin[i] : (u32)i; dig = (int)((key >> shift) & 255u); }
-        u64 peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const u64 bal = __ballot(valid && ((dig >> b) & 1));
-            peers &= ((dig >> b) & 1) ? bal : ~bal;
-        }
-        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0) cnt[wave][dig] = __popcll(peers);
-        __syncthreads();
-        if (valid) {
-            int off = base[dig] + rank;
-            for (int w = 0; w < wave; w++) off += cnt[w][dig];
-            kout[off] = key; vout[off] = val;
-        }
-        __syncthreads();
-        base[tid] += cnt[0][tid] + cnt[1][tid] + cnt[2][tid] + cnt[3][tid];
-        __syncthreads();
-    }
 }
 __global__ void k_tr_gather(long long N, const u32 *__restrict__ perm, const u32 *__restrict__ major, const double *__restrict__ vsrc,
                             int *__restrict__ ci, double *__restrict__ val) {

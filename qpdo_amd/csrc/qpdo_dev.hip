@@ -47,6 +47,7 @@ static int set_err(hipError_t e, const char *what, int line) {
 
 #include "dev/state.inc"
 #include "dev/helpers.inc"
+#include "dev/scan_sort.inc"
 #include "dev/spmv.inc"
 #include "dev/vector.inc"
 #include "dev/pcg_kernels.inc"

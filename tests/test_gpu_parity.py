@@ -726,13 +726,15 @@ def test_matrix_storage_variants_give_identical_results(gpu_required):
             assert np.array_equal(r["x"], base["x"]) and np.array_equal(r["y"], base["y"])
 
 
-@pytest.mark.parametrize("shape", [(120, 200, 0.06, 0), (700, 300, 0.2, 40), (3000, 70000, 0.002, 100), (1, 5, 1.0, 0), (40, 0, 0.1, 0)])
+@pytest.mark.parametrize("shape", [(120, 200, 0.06, 0), (700, 300, 0.2, 40), (3000, 70000, 0.002, 100), (2048, 4096, 0.01, 0), (1, 5, 1.0, 0),
+                                   (40, 0, 0.1, 0)])
 def test_device_setup_matches_host_setup(shape, gpu_required, monkeypatch):
     """qpdo_setup's matrix conversions (CSC -> CSR(A), stored triangle -> full symmetric CSR(Q)) run on the device by default (a stable
     radix transposition, dev/transpose.inc); QPDO_SETUP_HOST=1 keeps the OpenMP loops of the host.  Integer work: the arrays must be
     the same, so the three products and the whole solve carry the same bits -- for lower / upper / full storage of Q, 32- and 64-bit
-    indices, wide (more than one radix pass over the row index), empty (m = 0) and one-column shapes.  (Also forced onto the generic
-    path: small shapes would otherwise run through the fused kernel, which reads the same arrays.)"""
+    indices, wide (more than one radix pass over the row index), empty (m = 0) and one-column shapes.  The conversions' row pointers come
+    from the device-wide scan in 2048-entry tiles: 35, 7 and 2 tiles with ragged ends at (3000, 70000), exactly one and exactly two at
+    (2048, 4096).  (Also forced onto the generic path: small shapes would otherwise run through the fused kernel, which reads the same arrays.)"""
     import scipy.sparse as sp
     n, m, dens, neq = shape
     monkeypatch.setenv("QPDO_SMALL_FUSED", "0")

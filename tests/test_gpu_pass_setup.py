@@ -1,22 +1,24 @@
-"""The per-pass set-up of the PCG path with its three switches on (the default) against the former sequences, bit for bit:
+"""The per-pass set-up of the PCG path with its two switches on (the default) against the former sequences, bit for bit:
 QPDO_COMPACT_ONE_READ (A_c's CSR copy, slab image and Schur diagonal from one read of the weighted rows, instead of k_copy_rows,
 k_build_slab_ptr, k_slab_permute and k_schur_diag), QPDO_COMPACT_T_ONE_READ (A_c': slab pointers from the counting pass, CSR and image
-from one compaction, instead of k_count_flagged_bits, k_compact_rows_bits, k_build_slab_ptr and k_slab_permute) and QPDO_GRID_SCANS
-(row pointers, the flag scan and the radix sort's histogram scan on many workgroups instead of one).  Nothing moves an operation of a
-floating-point sum and integer scans are exact, so every array that qpdo_amd_download_compact hands out -- the slab-major images
+from one compaction, instead of k_count_flagged_bits, k_compact_rows_bits, k_build_slab_ptr and k_slab_permute).  Nothing moves an
+operation of a floating-point sum, so every array that qpdo_amd_download_compact hands out -- the slab-major images
 included (which >= 64) --, K v, whole linear solves and whole QP solves must come out the same to the bit.  A further check rebuilds
 each image by the lazy path (slab_major_build) and finds it unchanged: CSR, sp, seg and image are consistent after a build.
+Every integer scan of a pass (flag words, row pointers, the linesearch sort's histograms) is the one device-wide scan, dev_scan; its
+results are compared with NumPy: the index space and the compact matrices with tests/pcg_ref.py, the sorted order with a stable argsort.
 The whole file runs in about 12 s on the MI355X."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
 import pcg_ref as R
+from oracle import binding as ob
 from qpdo_amd import problems, solver
 
 pytestmark = pytest.mark.gpu
 
-SWITCHES = ("QPDO_COMPACT_ONE_READ", "QPDO_COMPACT_T_ONE_READ", "QPDO_GRID_SCANS")
+SWITCHES = ("QPDO_COMPACT_ONE_READ", "QPDO_COMPACT_T_ONE_READ")
 VECS = ("rowlist", "cidx", "dc", "flag_bits", "flag_wprefix")
 INFO_KEYS = ("status_val", "iterations", "oterations", "objective", "res_prim_norm", "res_dual_norm")
 
@@ -51,7 +53,7 @@ def _system(n, m, k, seed):
 
 
 def _workspace(monkeypatch, Qf, A, on, idx16):
-    """on: "0" / "1" for all three switches, or the name of the one switch that is on"""
+    """on: "0" / "1" for both switches, or the name of the one switch that is on"""
     monkeypatch.setenv("QPDO_LINSOLVE", "pcg")
     monkeypatch.setenv("QPDO_SPMV", "slab")
     monkeypatch.setenv("QPDO_IDX16", idx16)
@@ -150,6 +152,10 @@ def test_set_up_matches_former_sequence_bitwise(shape, idx16, gpu_required, monk
     off, on = res["0"], res["1"]
     assert on["kact"] == k
     assert _first_difference(off, on) is None, _first_difference(off, on)
+    # the index space (flag words, their scan) and both compact matrices (row-pointer scans of up to 15 tiles) against NumPy
+    ix, ref_arc, ref_atc = R.compact_matrices(A, dw)
+    bad = R.compaction_mismatch(dict(on, k=on["kact"]), ix, ref_arc, ref_atc)
+    assert bad is None, bad
     # the cases are what the table says, and the inputs hold what they should
     arc, atc = on["Arc"], on["Atc"]
     assert (arc["use_slab"], atc["use_slab"], arc["nslabs"], atc["nslabs"]) == (slab_r, slab_t, ns_r, ns_t)
@@ -182,7 +188,7 @@ def two_slab_system():
 
 
 def test_each_switch_alone_bitwise(two_slab_system, gpu_required, monkeypatch):
-    """the mixed states: each switch on by itself (the other two off) against all off, at the shape where both matrices take the slab
+    """the mixed states: each switch on by itself (the other off) against both off, at the shape where both matrices take the slab
     kernel with two slabs and the linear solve runs in the Schur mode"""
     Qf, A, dw, _ = two_slab_system
     v = np.random.default_rng(5).standard_normal(Qf.shape[0])
@@ -192,11 +198,9 @@ def test_each_switch_alone_bitwise(two_slab_system, gpu_required, monkeypatch):
         assert _first_difference(off, one) is None, (switch, _first_difference(off, one))
 
 
-def _solve(p, monkeypatch, switch, on):
+def _solve(p, monkeypatch, on):
     for s in SWITCHES:
-        monkeypatch.setenv(s, "1")
-    if switch:
-        monkeypatch.setenv(switch, on)
+        monkeypatch.setenv(s, on)
     return solver.solve_problem(p, verbose=0)
 
 
@@ -207,45 +211,42 @@ def _assert_same_solve(r0, r1):
     assert np.array_equal(r0["x"].view(np.uint64), r1["x"].view(np.uint64)) and np.array_equal(r0["y"].view(np.uint64), r1["y"].view(np.uint64))
 
 
-@pytest.mark.parametrize("args,single", [((8200, 3000, 16000, 0.004, 0), ("QPDO_GRID_SCANS",)), ((0, 6400, 20000, 0.003, 0), ())], ids=["n3000", "n6400"])
-def test_schur_mode_solve_bitwise(args, single, gpu_required, monkeypatch):
+@pytest.mark.parametrize("args", [(8200, 3000, 16000, 0.004, 0), (0, 6400, 20000, 0.003, 0)], ids=["n3000", "n6400"])
+def test_schur_mode_solve_bitwise(args, gpu_required, monkeypatch):
     """whole solves in the Schur mode with the slab kernels, every switch off against every switch on.  n = 3000: A_c' on the slab
-    kernel, A_c on the plain one; 2 m = 32000 breakpoints take the radix sort in every Newton step, whose histogram scan is one of the
-    scans: that switch is also taken off on its own.  n = 6400: passes with 4096 <= k <= 0.8 n have A_c on the slab kernel too (16 lanes
-    per row: k_schur_diag stays)."""
+    kernel, A_c on the plain one; 2 m = 32000 breakpoints take the radix sort in every Newton step.  n = 6400: passes with
+    4096 <= k <= 0.8 n have A_c on the slab kernel too (16 lanes per row: k_schur_diag stays)."""
     monkeypatch.setenv("QPDO_LINSOLVE", "pcg")
     monkeypatch.setenv("QPDO_PCG_SCHUR", "1")
     monkeypatch.setenv("QPDO_SPMV", "slab")
     p = problems.random_qp(*args)
     assert 2 * p["m"] > 8192
-    on = _solve(p, monkeypatch, None, "1")
+    on = _solve(p, monkeypatch, "1")
     assert on["stats"]["schur_passes"] > 0 and on["info"]["iterations"] > 3
-    for switch in single:
-        _assert_same_solve(_solve(p, monkeypatch, switch, "0"), on)
-    for s in SWITCHES:
-        monkeypatch.setenv(s, "0")
-    _assert_same_solve(solver.solve_problem(p, verbose=0), on)
+    _assert_same_solve(_solve(p, monkeypatch, "0"), on)
 
 
-def test_linesearch_sort_bitwise(gpu_required, monkeypatch):
-    """the radix path of the linesearch on its own (2 m = 20002 > 8192 breakpoints, 10 histogram tiles, a ragged last one): tau with the
-    histogram scan on many workgroups and on one, and the sorted order itself, which is also the stable order of numpy; ties and
-    non-candidates in the input"""
+@pytest.mark.parametrize("m", [8000, 10001, 16000])
+def test_linesearch_sort_bitwise(m, gpu_required, monkeypatch):
+    """the radix path of the linesearch on its own (2 m > 8192 breakpoints; ties and non-candidates in the input): the sorted order is
+    the stable order of numpy, exactly, and tau is the oracle's.  The digit histograms have 256 entries per 2048 breakpoints and are
+    scanned in 2048-entry tiles: m = 8000 gives exactly one tile (the single launch), 10001 a ragged second one, 16000 exactly two."""
     monkeypatch.setenv("QPDO_LINSOLVE", "pcg")                # (the order is read through qpdo_amd_download_compact)
-    m = 10001
+    assert 2 * m > 8192 and 256 * -(-2 * m // 2048) == {8000: 2048, 10001: 2560, 16000: 4096}[m]
     rng = np.random.default_rng(9)
     p = problems.random_qp(1, 4, m, 0.5)
     delta = rng.standard_normal(2 * m); alpha = rng.standard_normal(2 * m) * np.abs(delta)
     alpha[::7] = delta[::7]                                   # ties at t = 1
     delta[5::11] = np.abs(delta[5::11]); alpha[5::11] = -np.abs(alpha[5::11])      # t < 0: not candidates
     t = alpha / delta
-    ref = np.argsort(np.where(t > 0, t, np.inf), kind="stable")
-    taus, orders = [], []
-    for on in ("0", "1"):
-        monkeypatch.setenv("QPDO_GRID_SCANS", on)
-        s = solver.QPDO().setup(p["Q"], p["q"], p["A"], p["l"], p["u"], Qstype=-1, verbose=0, scaling=0)
-        taus.append(np.float64(s.linesearch(3.0, -2.0, delta, alpha)))
-        orders.append(s.download_linesearch_order())
+    ref_order = np.argsort(np.where(t > 0, t, np.inf), kind="stable")
+    ref_tau = ob.pwa_linesearch(3.0, -2.0, delta, alpha)
+    s = solver.QPDO().setup(p["Q"], p["q"], p["A"], p["l"], p["u"], Qstype=-1, verbose=0, scaling=0)
+    try:
+        tau = s.linesearch(3.0, -2.0, delta, alpha)
+        order = s.download_linesearch_order()
+    finally:
         s.delete()
-    assert np.array_equal(orders[0], orders[1]) and np.array_equal(orders[1], ref) and np.sum(t > 0) > 8192
-    assert taus[0].view(np.uint64) == taus[1].view(np.uint64) and np.isfinite(taus[0])
+    print("m = %d: tau %.17g, oracle %.17g" % (m, tau, ref_tau))
+    assert np.array_equal(order, ref_order) and np.sum(t > 0) > 8192
+    assert np.isfinite(tau) and abs(tau - ref_tau) <= 1e-10 * max(1.0, abs(ref_tau))

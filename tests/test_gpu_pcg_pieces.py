@@ -92,7 +92,8 @@ def check_probe(ws, Qf, A, sigma, dw, p, group, tag):
 # ---- (a) + (b): compaction, exact, and the K product on the same workspaces --------------------------------------------------------------
 @pytest.mark.parametrize("m", [1, 63, 64, 65, 1023, 1024, 1025, 1089])
 def test_compaction_and_K_product_every_pattern(m, gpu_required, monkeypatch):
-    """row counts around the word and wave-segment edges of k_flag_scan (1025 rows: 17 words, two per wave, the last waves own none)"""
+    """row counts around the edges of the 64-row flag words (k_flag_words, their scan, k_flag_apply: a ragged last word, a full one, one
+    row into the next, 1025 rows: 17 words)"""
     n = 200 + 37 * (m % 9)
     Qf, A = R.system(n, m, 1, empty_row=m // 2)
     ws = _workspace(monkeypatch, Qf, A)
@@ -107,6 +108,21 @@ def test_compaction_and_K_product_every_pattern(m, gpu_required, monkeypatch):
                 assert got["rowlist"][j] == m // 2 and got["Arc"]["rp"][j] == got["Arc"]["rp"][j + 1]       # counted in k, an empty row of A_c
             if name == "none":
                 assert got["k"] == 0
+    finally:
+        ws.delete()
+
+
+def test_compaction_flag_words_cross_a_scan_tile(gpu_required, monkeypatch):
+    """m = 131141: 2050 flag words, so their scan (2048-entry tiles) has a second tile, which holds two words; about half the rows
+    weighted, some of them in those two words"""
+    n, m = 300, 131141
+    assert (m + 63) // 64 == 2050
+    Qf, A = R.system(n, m, 5, per_row=3)
+    dw = R.k_weights(m, m // 2, 17)
+    assert np.count_nonzero(dw[2048 * 64:]) > 0 and np.count_nonzero(dw[2049 * 64:]) > 0
+    ws = _workspace(monkeypatch, Qf, A)
+    try:
+        check_probe(ws, Qf, A, 1.0, dw, R.probe_vectors(n)["random"], "flag words in two scan tiles", "m=%d k=%d" % (m, m // 2))
     finally:
         ws.delete()
 

@@ -1,6 +1,7 @@
 """A/B timing of builds of libqpdo_amd.so on one box: the C4 cold-start solve, alternating processes.
 usage: ab_c4.py libA.so libB.so [more sides ...] [reps]
-A side is a library, or VAR=VALUE,VAR=VALUE@library: that build with those environment switches (e.g. QPDO_INNER_FOLD=0@libqpdo_amd.so)."""
+A side is a library, or VAR=VALUE,VAR=VALUE@library: that build with those environment switches (e.g. QPDO_INNER_FOLD=0@libqpdo_amd.so).
+With QPDO_SETUP_PROF=1 among them (or in the environment) the set-up's "[setup] ..." timing lines are printed under the side's line."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 code = r"""
@@ -25,3 +26,6 @@ for rep in range(reps):
         o = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True)
         line = [l for l in o.stdout.splitlines() if l.startswith("[")]
         print((switches + " " if switches else "") + os.path.basename(lib), line[-1] if line else o.stderr[-500:], flush=True)
+        for l in o.stderr.splitlines():
+            if l.startswith("[setup]"):
+                print("    " + l, flush=True)
