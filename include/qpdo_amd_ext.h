@@ -288,6 +288,36 @@ long qpdo_amd_solve_batch(long count, QPDOAmdBatchItem *items, const QPDOSetting
 /* HIP-event duration of the fused kernel launch of the last qpdo_amd_solve_batch on this process (0 if it took the threaded path) */
 double qpdo_amd_batch_kernel_seconds(void);
 
+/* ---- where the fused kernel keeps the Newton matrix K = Q + sigma I + A'DA (batches, batch streams, fleets) ------------------------------
+ * One layout per LAUNCH, decided from all its items:
+ *   PACKED  the packed lower triangle of the largest item, n (n+1) / 2 doubles, fits the workgroup's LDS beside the rest (n up to about
+ *           170-200, depending on m): K lives there.  This decision comes first and is what it was before the band layout existed.
+ *   BAND    otherwise, when for EVERY item the lower band of K, n_i (b_i + 1) doubles (element (i, j), j <= i <= j + b, at
+ *           j (b+1) + (i - j)), fits the same region beside the fixed part sized for the largest n and m of the launch: every item's K
+ *           lives in LDS in band storage, and the factorization and both triangular solves touch the band alone.  b_i, the item's
+ *           half-bandwidth, is the largest |i - j| over the stored entries of Q and the largest column span (last - first column) over
+ *           the rows of A: a function of the pattern, so scaling, qpdo_update_q and qpdo_amd_fleet_update_matrices never change it.  A
+ *           dense item in such a launch is b = n - 1; an item with m = 0 takes Q's bandwidth.  b_i <= 128: an item with a wider band sends the
+ *           launch to GLOBAL (the widest band measured, b = 70, wins; nothing wider was measured).  The work vectors of a fleet,
+ *           and of a batch that takes the latency kernel, go to LDS as well where they fit behind the band image; the band
+ *           factorization has no look-ahead, so such a launch keeps one set of column buffers.
+ *   GLOBAL  otherwise: K is a full n x n square in global memory (everything up to n = m = 1024).
+ * QPDO_SMALL_BAND=0 in the environment keeps K out of the band layout (PACKED or GLOBAL as before); it is read at every launch and query.
+ * CONTRACT: an item solved in the band layout returns what it returns through the global-memory layout, and what the CPU oracle returns --
+ * status, iteration counts, x, y, objective, residual norms, certificates, the per-pass trace -- bit for bit, with one exception: natural-
+ * order LDL' of a band matrix creates no fill outside the band, and the operations the band code leaves out are subtractions of an exact
+ * zero product; such a subtraction can turn a -0.0 into +0.0 (a right-hand-side component that is exactly -0.0: -0.0 - (-0.0) = +0.0), so a
+ * zero may come back with the other sign.  No nonzero value can differ.
+ * qpdo_amd_small_factor_layout: the layout a launch over these items takes -- the launches go through the same function -- as pure host
+ * arithmetic, no device needed.  kind 0: qpdo_amd_solve_batch, 1: a batch of a stream, 2: a fleet.  half_bandwidth: optional out, `count`
+ * entries.  settings may be NULL (no setting enters the rule).  -1: an item does not fit the fused kernel (or count < 1, an unknown kind). */
+#define QPDO_AMD_SMALL_K_GLOBAL 0
+#define QPDO_AMD_SMALL_K_PACKED 1
+#define QPDO_AMD_SMALL_K_BAND   2
+int qpdo_amd_small_factor_layout(long count, const QPDOData *const *data, const QPDOSettings *settings, int kind, long *half_bandwidth);
+/* the last qpdo_amd_solve_batch of this process, as qpdo_amd_batch_kernel_seconds (-1: none yet through the fused kernel) */
+int qpdo_amd_batch_factor_layout(void);
+
 /* ---- STREAMED batches (BASELINE.json configs[2]: "batch of 4096 MPC-sized QPs ... streamed") ----------------------------
  * A fused-kernel launch is as slow as its slowest item: an instance that never reaches eps_abs (in the reference either)
  * holds one workgroup for max_iter passes while the other CUs idle.  A batch stream keeps up to `depth` batches in flight,
@@ -381,6 +411,9 @@ int  qpdo_amd_fleet_warm_start(QPDOAmdFleet *f, const c_float *const *x0, const 
 int  qpdo_amd_fleet_warm_start_last(QPDOAmdFleet *f);
 int  qpdo_amd_fleet_solve(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info);
 int  qpdo_amd_fleet_get_stats(const QPDOAmdFleet *f, QPDOAmdFleetStats *out);
+/* what this fleet's launches use (QPDO_AMD_SMALL_K_*; fixed at create: new matrix values keep the pattern, hence the band); -1: NULL fleet.
+ * update, update_matrices, warm_start and warm_start_last behave on a band fleet as on any other */
+int  qpdo_amd_fleet_factor_layout(const QPDOAmdFleet *f);
 /* the infeasibility certificates of `item` from the last solve: prim_inf_cert (m values, meaningful at status -3), dual_inf_cert (n, at -4);
  * either may be NULL */
 int  qpdo_amd_fleet_get_certificates(const QPDOAmdFleet *f, long item, c_float *prim_inf_cert, c_float *dual_inf_cert);

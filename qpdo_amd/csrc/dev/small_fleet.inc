@@ -136,7 +136,7 @@ struct SmallFleet {
     char *hout = nullptr; size_t out_off = 0, out_bytes = 0;  // pinned image of the outputs
     SmallQP *hp = nullptr;                          // pinned image of the descriptors (info comes back in them)
     std::vector<FleetItem> it;
-    size_t lds = 0; int kflags = 0;
+    size_t lds = 0; int kflags = 0, layout = 0;
     long matrix_bytes = 0, vector_bytes_last = 0, solve_launches = 0, solves = 0; double kernel_s = 0.0;
     bool solved = false;
     // QPDO_AMD_FLEET_MATRIX_UPDATES (all empty / zero without the flag)
@@ -265,14 +265,15 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     SHIP(hipMemcpyAsync(F->arena, h, upload_bytes, hipMemcpyHostToDevice, F->stream));     // the only matrix upload the fleet ever makes
     F->matrix_bytes = (long)upload_bytes;
     {
-        int klds = 0; size_t ub = 0;
-        F->lds = small_lds_bytes(nmax, mmax, &klds, &ub, true);
-        if (!klds) F->lds = small_lds_bytes(nmax, mmax, nullptr, &ub, false);      // the factor in global memory: no look-ahead, one set of column buffers (fits up to n = m = 1024)
-        F->kflags = klds | ((int)(ub / 8) << 1);
+        // where K lives: the rule of every launch (small_plan); the pattern, hence every item's half-bandwidth, is fixed for the fleet's life
+        std::vector<int> bws;
+        const SmallPlan plan = small_plan(2, nmax, mmax, [&]() { return small_band_bytes(count, [&](long i) { return data[i]; }, bws); });
+        F->lds = plan.lds; F->layout = plan.layout;
+        F->kflags = small_kflags(plan);
         // the work vectors beside the factor in LDS when both fit (as a batch through the latency kernel has them)
         size_t voff, vbytes;
         small_vec_lds(F->lds, nmax, mmax, &voff, &vbytes);
-        const unsigned vec_off = (klds && voff + vbytes <= SMALL_LDS_BUDGET) ? (unsigned)voff : 0u;
+        const unsigned vec_off = (plan.layout != K_GLOBAL && voff + vbytes <= SMALL_LDS_BUDGET) ? (unsigned)voff : 0u;
         if (vec_off) F->lds = voff + vbytes;
         char *dbase = F->arena;
         for (long i = 0; i < count; i++) {
@@ -280,6 +281,7 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
             const size_t n = d->n, m = d->m;
             lay_describe(p, d, L, dbase); memset(&r, 0, sizeof(r));
             p.res = F->dres + i;
+            if (plan.layout == K_BAND) p.bw = bws[(size_t)i];
             double *v = (double *)(dbase + o_rec[(size_t)i]);
             double *D = v, *Dinv = D + n, *sx = Dinv + n, *sQx = sx + n, *sxb = sQx + n, *sAty = sxb + n;
             double *E = sAty + n, *Einv = E + m, *sy = Einv + m, *syb = sy + m, *sAx = syb + m, *smu = sAx + m, *sisq = smu + m;
@@ -459,6 +461,7 @@ void qdev_small_fleet_stats(const void *h_, long *out5, double *kernel_s) {
     out5[0] = F->count; out5[1] = F->matrix_bytes; out5[2] = F->vector_bytes_last; out5[3] = F->solve_launches; out5[4] = F->solves;
     *kernel_s = F->kernel_s;
 }
+int qdev_small_fleet_layout(const void *h_) { return ((const SmallFleet *)h_)->layout; }
 void qdev_small_fleet_dims(const void *h_, long item, int *n, int *m) {
     const SmallFleet *F = (const SmallFleet *)h_;
     *n = F->it[(size_t)item].n; *m = F->it[(size_t)item].m;

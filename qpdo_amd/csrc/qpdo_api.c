@@ -1150,6 +1150,18 @@ static void *batch_worker(void *arg) {
     return NULL;
 }
 double qpdo_amd_batch_kernel_seconds(void) { return qdev_small_last_kernel_seconds(); }
+/* where the fused kernel keeps the Newton matrix: see include/qpdo_amd_ext.h.  The query and the launches share one rule (small_plan, qpdo_small.hip) */
+int qpdo_amd_batch_factor_layout(void) { return qdev_small_last_batch_layout(); }
+int qpdo_amd_small_factor_layout(long count, const QPDOData *const *data, const QPDOSettings *settings, int kind, long *half_bandwidth) {
+    (void)settings;                                  /* (no setting enters the rule) */
+    const int lay = qdev_small_factor_layout(count, (const void *const *)data, kind, half_bandwidth);
+    if (lay < 0) qdev_set_error(qdev_small_last_error());
+    return lay;
+}
+int qpdo_amd_fleet_factor_layout(const QPDOAmdFleet *f) {
+    if (!f) { qdev_set_error("qpdo_amd_fleet_factor_layout: NULL fleet"); return -1; }
+    return qdev_small_fleet_layout(f);
+}
 long qpdo_amd_solve_batch(long count, QPDOAmdBatchItem *items, const QPDOSettings *settings, int nthreads) {
     if (count <= 0) return 0;
     /* small problems: the fused one-workgroup-per-QP kernel solves the whole batch in one launch

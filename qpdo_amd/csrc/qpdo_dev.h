@@ -227,6 +227,8 @@ int qdev_small_eligible(long count, const void *items);
 int qdev_small_batch(int device, long count, void *items, const void *settings);
 const char *qdev_small_last_error(void);
 double qdev_small_last_kernel_seconds(void);
+int qdev_small_last_batch_layout(void);
+int qdev_small_factor_layout(long count, const void *const *data /* QPDOData */, int kind, long *half_bandwidth);
 /* batch stream: up to `depth` fused-kernel batches in flight, each on its own HIP stream */
 void *qdev_small_stream_create(int device, int depth);
 long  qdev_small_stream_submit(void *stream, long count, void *items, const void *settings);
@@ -243,6 +245,7 @@ void  qdev_small_fleet_stats(const void *fleet, long *out5, double *kernel_secon
 int   qdev_small_fleet_update_matrices(void *fleet, const void *const *Q /* cholmod_sparse */, const void *const *A);
 void  qdev_small_fleet_matrix_stats(const void *fleet, long *out4, double *kernel_seconds);
 void  qdev_small_fleet_dims(const void *fleet, long item, int *n, int *m);
+int   qdev_small_fleet_layout(const void *fleet);
 void  qdev_small_fleet_destroy(void *fleet);
 
 /* ---- ONE small workspace through the fused kernel (the default path of qpdo_solve for problems whose whole state fits one

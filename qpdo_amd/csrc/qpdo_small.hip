@@ -60,6 +60,7 @@ struct SmallQP {
     long long *prof;                         // optional: per-phase wall-clock ticks (diagnostic runs only)
     struct SmallRes *res;                    // resident mode (latency kernel only): see SmallRes; NULL in a batch
     unsigned batch_vec_off;                  // a batch through the latency kernel: byte offset of the vector workspace inside the dynamic LDS (0: global memory)
+    int bw;                                  // half-bandwidth of Q + A'DA for every D (small_item_bw); read in the band layout of K only
 };
 // ---- resident mode (qpdo_solve of ONE small workspace through the latency kernel, qdev_small_resident_*): the matrices, q, l, u are the
 // workspace's own device arrays, already scaled by qpdo_setup (bit-identical to the oracle's scaling), so the kernel skips its Ruiz
@@ -369,10 +370,12 @@ __device__ void small_scale(SmallQP &P, int iters, double *D, double *Dinv, doub
 
 // ---- dense system -----------------------------------------------------------------------------------------
 // K is addressed as K[koff(j) + i] (i >= j).  When the packed lower triangle fits in LDS it lives there
-// (koff = j*n - j(j+1)/2), otherwise in global memory as a full column-major square (koff = j*n).
+// (koff = j*n - j(j+1)/2); otherwise, when the lower BAND of every item fits, there as band storage -- element (i, j), j <= i <= j + b, at
+// j (b+1) + (i - j), i.e. koff = j*b --; otherwise in global memory as a full column-major square (koff = j*n).  ld: b or n.
+enum { K_GLOBAL = 0, K_PACKED = 1, K_BAND = 2 };      // = QPDO_AMD_SMALL_K_* (qpdo_amd_ext.h)
 struct KView {
-    double *K; int n; int packed;
-    __device__ __forceinline__ size_t off(int j) const { return packed ? (size_t)j * n - (size_t)j * (j + 1) / 2 : (size_t)j * n; }
+    double *K; int n; int packed; int ld;
+    __device__ __forceinline__ size_t off(int j) const { return packed ? (size_t)j * n - (size_t)j * (j + 1) / 2 : (size_t)j * ld; }
     __device__ __forceinline__ double &at(int i, int j) const { return K[off(j) + i]; }
 };
 // Assembly in the oracle's order -- Q first, then the rows r of A ascending, sigma_f last -- WITHOUT a barrier per row: the
@@ -392,7 +395,8 @@ __device__ void small_build_tpos(SmallQP &P) {
 }
 __device__ void small_assemble(SmallQP &P, const KView &kv, const double *dw, double sigma_f, const int *rp_s, double *d_s) {
     const int n = P.n, m = P.m;
-    const size_t tot = kv.packed ? (size_t)n * (n + 1) / 2 : (size_t)n * n;
+    // (band storage, ld = b < n: n (b+1) entries; every entry touched below lies inside the band by construction of b)
+    const size_t tot = kv.packed ? (size_t)n * (n + 1) / 2 : (size_t)n * (kv.ld < n ? kv.ld + 1 : n);
     for (size_t i = threadIdx.x; i < tot; i += blockDim.x) kv.K[i] = 0.0;
     FOR_T(r, m) d_s[r] = dw[r];                    // weights of this pass into LDS
     SYNC;
@@ -1113,6 +1117,170 @@ __device__ __forceinline__ T *uni_ptr(T *p) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
     return (T *)(((unsigned long long)hi << 32) | lo);
 }
+// ---- K as a lower BAND in LDS (K_BAND): element (i, j), j <= i <= min(j + b, n - 1), at K[j b + i] -----------------------------------
+// Natural-order LDL' of a band matrix creates no fill outside the band, so every element receives the subtractions
+// K(i,j) -= l_ik (l_jk d_k), ascending k, that small_factor4_t gives it, EXCEPT those with an operand outside the band (i - k > b): there
+// l_ik is an exact zero in the dense order and the product a zero, whose subtraction changes at most the sign of a zero.  A term whose
+// operand is a zero INSIDE the band is computed.  These are functions of their own, called, not inlined: one copy of the code for the
+// three kernels, and the register allocation of the kernels' other paths stays what it was.
+//
+// Right-looking, FOUR columns per barrier pair as small_factor4_t while b >= 3 and four columns remain: every thread factors the leading
+// 4 x 4 block itself (inside the band when b >= 3), the rows k+4 .. min(k+3+b, n-1) are carried through the four columns by one thread
+// each, and the trailing update is confined to the window of those rows and columns (wave w: columns k+4+w, k+4+w+8, ..; lanes: rows).
+// b < 3, where the block would reach outside the band, and the last n mod 4 columns: one column per barrier pair -- which columns share a
+// barrier pair never changes what an element receives.  F: 8n doubles (l and l*d of the four columns, by row).
+// (a value every lane computed alike, moved to scalar registers: the block's values would otherwise hold ~30 VGPRs through the step)
+__device__ __forceinline__ double uni_f64(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+__device__ __attribute__((noinline)) void small_factor_band(int n_, int b_, double *Kg, double *Fg) {
+    const int n = __builtin_amdgcn_readfirstlane(n_), b = __builtin_amdgcn_readfirstlane(b_);
+    lds_f64 *K = (lds_f64 *)uni_ptr(Kg), *F = (lds_f64 *)uni_ptr(Fg);
+    lds_f64 *L0 = F, *L1 = F + n, *L2 = F + 2 * n, *L3 = F + 3 * n, *T0 = F + 4 * n, *T1 = F + 5 * n, *T2 = F + 6 * n, *T3 = F + 7 * n;
+    const int li = threadIdx.x & 63, wj = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int k = 0;
+    if (b >= 3)
+    for (; k + 3 < n; k += 4) {
+        const int o0 = k * b, o1 = o0 + b, o2 = o1 + b, o3 = o2 + b;
+        const double d0 = uni_f64(K[o0 + k]), inv0 = uni_f64(1.0 / d0);
+        const double l10 = K[o0 + k + 1] * inv0, l20 = K[o0 + k + 2] * inv0, l30 = K[o0 + k + 3] * inv0;
+        const double t10 = l10 * d0, t20 = l20 * d0, t30 = l30 * d0;
+        const double d1 = uni_f64(K[o1 + k + 1] - l10 * t10), inv1 = uni_f64(1.0 / d1);
+        const double l21 = (K[o1 + k + 2] - l20 * t10) * inv1, l31 = (K[o1 + k + 3] - l30 * t10) * inv1;
+        const double t21 = l21 * d1, t31 = l31 * d1;
+        const double d2 = uni_f64((K[o2 + k + 2] - l20 * t20) - l21 * t21), inv2 = uni_f64(1.0 / d2);
+        const double l32 = ((K[o2 + k + 3] - l30 * t20) - l31 * t21) * inv2, t32 = l32 * d2;
+        const double d3 = uni_f64(((K[o3 + k + 3] - l30 * t30) - l31 * t31) - l32 * t32), inv3 = uni_f64(1.0 / d3);
+        const int hi = k + 3 + b < n - 1 ? k + 3 + b : n - 1;      // last row of the window
+        for (int i = k + 4 + (int)threadIdx.x; i <= hi; i += blockDim.x) {
+            const int dk = i - k;                       // l_i,k+c lies inside the band when dk - c <= b  (dk - 3 <= b: every row of the window)
+            const bool x0 = dk <= b, x1 = dk - 1 <= b, x2 = dk - 2 <= b;
+            double l0 = 0.0, l1 = 0.0, l2 = 0.0;
+            if (x0) { l0 = K[o0 + i] * inv0; K[o0 + i] = l0; }
+            if (x1) { double v = K[o1 + i]; if (x0) v = v - l0 * t10; l1 = v * inv1; K[o1 + i] = l1; }
+            if (x2) { double v = K[o2 + i]; if (x0) v = v - l0 * t20; if (x1) v = v - l1 * t21; l2 = v * inv2; K[o2 + i] = l2; }
+            double v3 = K[o3 + i];
+            if (x0) v3 = v3 - l0 * t30;
+            if (x1) v3 = v3 - l1 * t31;
+            if (x2) v3 = v3 - l2 * t32;
+            const double l3 = v3 * inv3;
+            K[o3 + i] = l3;
+            L0[i] = l0; L1[i] = l1; L2[i] = l2; L3[i] = l3;
+            T0[i] = l0 * d0; T1[i] = l1 * d1; T2[i] = l2 * d2; T3[i] = l3 * d3;
+        }
+        SYNC;
+        if (threadIdx.x == 0) {                       // (inputs of every thread above: overwritten after the barrier)
+            K[o0 + k + 1] = l10; K[o0 + k + 2] = l20; K[o0 + k + 3] = l30;
+            K[o1 + k + 1] = d1;  K[o1 + k + 2] = l21; K[o1 + k + 3] = l31;
+            K[o2 + k + 2] = d2;  K[o2 + k + 3] = l32; K[o3 + k + 3] = d3;
+        }
+        // the window's lower triangle: column j, rows j .. hi (i - j <= b - 1: inside the band)
+        for (int j = k + 4 + wj; j <= hi; j += nw) {
+            const int oj = j * b;
+            const double s0 = T0[j], s1 = T1[j], s2 = T2[j], s3 = T3[j];
+            for (int i = j + li; i <= hi; i += 64) {
+                const int dk = i - k;
+                const double a0 = L0[i], a1 = L1[i], a2 = L2[i], a3 = L3[i];
+                double w = K[oj + i];
+                if (dk <= b) w = w - a0 * s0;
+                if (dk - 1 <= b) w = w - a1 * s1;
+                if (dk - 2 <= b) w = w - a2 * s2;
+                K[oj + i] = w - a3 * s3;
+            }
+        }
+        SYNC;
+    }
+    for (; k < n; k++) {
+        const int o0 = k * b;
+        const double d0 = K[o0 + k], inv0 = 1.0 / d0;
+        const int hi = k + b < n - 1 ? k + b : n - 1;
+        for (int i = k + 1 + (int)threadIdx.x; i <= hi; i += blockDim.x) { const double l0 = K[o0 + i] * inv0; K[o0 + i] = l0; L0[i] = l0; T0[i] = l0 * d0; }
+        SYNC;
+        for (int j = k + 1 + wj; j <= hi; j += nw) {
+            const int oj = j * b;
+            const double s0 = T0[j];
+            for (int i = j + li; i <= hi; i += 64) K[oj + i] = K[oj + i] - L0[i] * s0;
+        }
+        SYNC;
+    }
+}
+// Both triangular solves by ONE wave without a barrier, as small_ldl_solve_wave, for n up to 1024: x lives in LDS (xs: b on entry, the
+// solution on exit) and only the rows of the current window are in registers.  Lane l owns the rows i = l mod 64; of those, slot r holds the
+// rows with (i >> 6) mod R = r, R = 1, 2 with 64 R >= b, so a window of b consecutive rows never has two rows in one slot.  Step j
+// (forward, ascending): x_j is final, the lane that holds it broadcasts it (v_readlane), stores it and takes its slot's next row j + 64 R
+// from xs; the rows j+1 .. min(j+b, n-1) receive  x_i -= L(i,j) x_j.  Then x_j /= d_j, then the same descending with L(j,i) for the rows
+// max(j-b, 0) .. j-1: per element the subtractions of the column-oriented loops of small_ldl_solve (the oracle's ldl_solve) in their
+// order, without those whose L entry lies outside the band.  The L entries and the next rows of G steps are loaded while the G steps
+// before them are applied (their addresses do not depend on x).
+template <int R, int G>
+__device__ __forceinline__ void band_solve_wave(int n, int b, const lds_f64 *K, lds_f64 *xs) {
+    constexpr int M = 64 * R - 1;
+    const int lane = threadIdx.x & 63;
+    double x[R], LA[G][R], LB[G][R], EA, EB;
+#define BSEL(dst, s_) do { dst = x[0]; _Pragma("unroll") for (int r = 1; r < R; r++) if ((s_) == r) dst = x[r]; } while (0)
+    // ---- L z = b
+#pragma unroll
+    for (int r = 0; r < R; r++) { const int i = lane + 64 * r; x[r] = i < n ? xs[i] : 0.0; }
+#define FWD_LOAD(L, E, j0_) do { const int pl = (lane - (j0_)) & 63, ir = (j0_) + pl + 64 * R; E = (pl < G && ir < n) ? xs[ir] : 0.0; \
+        _Pragma("unroll") for (int u = 0; u < G; u++) { const int j = (j0_) + u; const int hi = j + b < n - 1 ? j + b : n - 1; \
+        _Pragma("unroll") for (int r = 0; r < R; r++) { const int i = j + 1 + ((lane + 64 * r - j - 1) & M); L[u][r] = K[(j < n && i <= hi) ? j * b + i : 0]; } } } while (0)
+#define FWD_STEPS(L, E, j0_) do { const int sj = ((j0_) >> 6) & (R - 1), pl = (lane - (j0_)) & 63; \
+        _Pragma("unroll") for (int u = 0; u < G; u++) { const int j = (j0_) + u; if (j < n) { const int hi = j + b < n - 1 ? j + b : n - 1; \
+            double xp; BSEL(xp, sj); const double xj = rl64(xp, j & 63); \
+            if (pl == u) { xs[j] = xj; _Pragma("unroll") for (int r = 0; r < R; r++) if (sj == r) x[r] = E; } \
+            _Pragma("unroll") for (int r = 0; r < R; r++) { const int i = j + 1 + ((lane + 64 * r - j - 1) & M); if (i <= hi) x[r] = x[r] - L[u][r] * xj; } } } } while (0)
+    FWD_LOAD(LA, EA, 0);
+#pragma nounroll
+    for (int j0 = 0; j0 < n; j0 += 2 * G) {
+        FWD_LOAD(LB, EB, j0 + G);
+        FWD_STEPS(LA, EA, j0);
+        FWD_LOAD(LA, EA, j0 + 2 * G);
+        FWD_STEPS(LB, EB, j0 + G);
+    }
+#undef FWD_LOAD
+#undef FWD_STEPS
+    // ---- z / d  (this wave's own LDS operations execute in program order: the stores above are seen)
+    for (int i = lane; i < n; i += 64) xs[i] = xs[i] / K[i * b + i];
+    // ---- L' x = z: step j (descending) eliminates x_j from the rows above;  L(j,i) sits at i b + j
+#pragma unroll
+    for (int r = 0; r < R; r++) { const int i = (n - 1) - ((n - 1 - lane - 64 * r) & M); x[r] = i >= 0 ? xs[i] : 0.0; }
+    // group j0_ (a multiple of G): steps j0_ + G - 1 down to j0_
+#define BWD_LOAD(L, E, j0_) do { const int pl = (lane - (j0_)) & 63, ir = (j0_) + pl - 64 * R; E = ((j0_) >= 0 && pl < G && ir >= 0) ? xs[ir] : 0.0; \
+        _Pragma("unroll") for (int u = 0; u < G; u++) { const int j = (j0_) + u; const int lo = j - b > 0 ? j - b : 0; \
+        _Pragma("unroll") for (int r = 0; r < R; r++) { const int i = j - 1 - ((j - 1 - lane - 64 * r) & M); L[u][r] = K[((j0_) >= 0 && j < n && i >= lo) ? i * b + j : 0]; } } } while (0)
+#define BWD_STEPS(L, E, j0_) do { const int sj = ((j0_) >> 6) & (R - 1), pl = (lane - (j0_)) & 63; \
+        _Pragma("unroll") for (int u = G - 1; u >= 0; u--) { const int j = (j0_) + u; if (j < n) { const int lo = j - b > 0 ? j - b : 0; \
+            double xp; BSEL(xp, sj); const double xj = rl64(xp, j & 63); \
+            if (pl == u) { xs[j] = xj; _Pragma("unroll") for (int r = 0; r < R; r++) if (sj == r) x[r] = E; } \
+            _Pragma("unroll") for (int r = 0; r < R; r++) { const int i = j - 1 - ((j - 1 - lane - 64 * r) & M); if (i >= lo) x[r] = x[r] - L[u][r] * xj; } } } } while (0)
+    const int jtop = (n - 1) & ~(G - 1);
+    BWD_LOAD(LA, EA, jtop);
+#pragma nounroll
+    for (int j0 = jtop; j0 >= 0; j0 -= 2 * G) {
+        BWD_LOAD(LB, EB, j0 - G);
+        BWD_STEPS(LA, EA, j0);
+        BWD_LOAD(LA, EA, j0 - 2 * G);
+        if (j0 - G >= 0) BWD_STEPS(LB, EB, j0 - G);
+    }
+#undef BWD_LOAD
+#undef BWD_STEPS
+#undef BSEL
+}
+__device__ __attribute__((noinline)) void small_ldl_solve_band(int n_, int b_, double *Kg, const double *rhs, double *xout, double *xsg) {
+    const int n = __builtin_amdgcn_readfirstlane(n_), b = __builtin_amdgcn_readfirstlane(b_);
+    const lds_f64 *K = (const lds_f64 *)uni_ptr(Kg); lds_f64 *xs = (lds_f64 *)uni_ptr(xsg);
+    rhs = uni_ptr(rhs); xout = uni_ptr(xout);
+    FOR_T(i, n) xs[i] = rhs[i];
+    SYNC;
+    if (threadIdx.x < 64) {
+        if (b <= 64) band_solve_wave<1, 4>(n, b, K, xs);
+        else band_solve_wave<2, 2>(n, b, K, xs);          // (b <= 128: the launch rule, small_plan)
+    }
+    SYNC;
+    FOR_T(i, n) xout[i] = xs[i];
+    SYNC;
+}
+
 // ---- the whole solve of one QP by one workgroup ----------------------------------------------------------
 // LAT = 0: the batch kernel (held to 128 VGPRs so that two workgroups share a CU); LAT = 1: the latency variant for ONE workspace
 // (qdev_small_resident_solve): the same code with the whole register file of a CU's SIMDs to itself (no spills) -- same operations
@@ -1124,12 +1292,12 @@ __device__ __forceinline__ T *uni_ptr(T *p) {
 template <int LAT, int FLEET = 0>
 __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, const QPDOSettings &st, int kflags, int fleet_op = 0,
                                                  const int *fleet_tab = nullptr, const double *fleet_stage = nullptr) {
-    const int klds_ok = kflags & 1, ucap = kflags >> 1;          // bit 0: the packed factor lives in LDS; the rest: doubles in the union region U
+    const int klay = kflags & 3, klds_ok = klay == K_PACKED, kband = klay == K_BAND, ucap = kflags >> 2;      // bits 0-1: where K lives (K_GLOBAL / K_PACKED / K_BAND, small_plan); the rest: doubles in the union region U
     __shared__ double sm[32];
     __shared__ double red_scr[64];                    // two banks of reduction partials (RedBank)
     extern __shared__ __attribute__((aligned(16))) double dyn[];
     // dynamic LDS: [xs: n][colbuf: n][tk: 2n][12n more for the four-column factorization with look-ahead][gbuf][d_s: m][rp_s: m+1][U], U = one region shared by the packed factor K
-    // (if it fits) and the linesearch scratch (delta, alpha, sort keys, sort indices, flags).  The linesearch of a
+    // (if it fits; else the item's band image n (b+1), K_BAND, if those of all items fit) and the linesearch scratch (delta, alpha, sort keys, sort indices, flags).  The linesearch of a
     // pass runs after the pass's solve, so it may overwrite K: the factor is then rebuilt in the next pass instead
     // of being reused when the weights did not change -- the same bits, a little more work -- and the workgroup needs
     // ~67 KB instead of ~104 KB at n = 120, m = 360: two workgroups per CU instead of one.
@@ -1139,7 +1307,7 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
     // each field through v_readfirstlane tells the compiler it is uniform: the descriptor and the address arithmetic move to SGPRs.
     SmallQP &Pg = probs[blockIdx.x];                  // (outputs are written through this one)
     SmallQP P;
-    P.n = __builtin_amdgcn_readfirstlane(Pg.n); P.m = __builtin_amdgcn_readfirstlane(Pg.m);
+    P.n = __builtin_amdgcn_readfirstlane(Pg.n); P.m = __builtin_amdgcn_readfirstlane(Pg.m); P.bw = __builtin_amdgcn_readfirstlane(Pg.bw);
 #define UNI_PTR(f) P.f = uni_ptr(Pg.f)
     UNI_PTR(Arp); UNI_PTR(Aci); UNI_PTR(Aval); UNI_PTR(Trp); UNI_PTR(Tci); UNI_PTR(Tval); UNI_PTR(Qrp); UNI_PTR(Qci); UNI_PTR(Qval);
     UNI_PTR(q); UNI_PTR(l); UNI_PTR(u); UNI_PTR(x0); UNI_PTR(y0); UNI_PTR(nv); UNI_PTR(mv); UNI_PTR(lsv); UNI_PTR(iv); UNI_PTR(tpos); UNI_PTR(K);
@@ -1194,7 +1362,7 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
            *res_prim_old = V[MV_RPOLD], *res_prim_in = V[MV_RPI], *dy = V[MV_DY], *Adx = V[MV_ADX], *dw = V[MV_DW], *E = V[MV_E],
            *Einv = V[MV_EINV], *ats = V[MV_ATS], *tm = V[MV_T], *dwf = V[MV_DWF];
     int *active = P.iv, *active_old = P.iv + m, *changed = P.iv + 2 * m;
-    double *xs = dyn, *colbuf = dyn + n, *tk = dyn + 2 * (size_t)n, *gbuf = dyn + ((LAT && !(FLEET && !klds_ok)) ? 16 : 8) * (size_t)n;   // dyn .. dyn + 8n: l and l*d of four columns during a factorization; the latency kernel: two such buffers (look-ahead; a fleet whose factor is not in LDS has no look-ahead: one)
+    double *xs = dyn, *colbuf = dyn + n, *tk = dyn + 2 * (size_t)n, *gbuf = dyn + ((LAT && (FLEET ? klds_ok : !kband)) ? 16 : 8) * (size_t)n;   // dyn .. dyn + 8n: l and l*d of four columns during a factorization; the latency kernel: two such buffers (look-ahead; a fleet whose factor is not packed in LDS and a band launch have no look-ahead: one)
     double *d_s = gbuf + (((size_t)(n > m ? n : m) / 4 + 4 + 1) & ~(size_t)1);
     int *rp_s = (int *)(d_s + m);
     double *Klds = (double *)(rp_s + (((size_t)m + 1 + 3) & ~(size_t)3));          // start of U
@@ -1203,7 +1371,8 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
     u64 *skey = (u64 *)(ls_alpha + 2 * (size_t)m);
     u32 *sidx = (u32 *)(skey + np2s);
     unsigned char *jflag = (unsigned char *)(sidx + np2s);
-    KView kv; kv.n = n; kv.packed = klds_ok; kv.K = klds_ok ? Klds : P.K;
+    const int bw = P.bw, k_in_lds = klds_ok | kband;
+    KView kv; kv.n = n; kv.packed = klds_ok; kv.ld = kband ? bw : n; kv.K = k_in_lds ? Klds : P.K;
     const int scaled = st.scaling > 0, prox = (int)st.proximal;
     double sc_c = 1.0, sc_cinv = 1.0;
 
@@ -1510,20 +1679,22 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
                     // look-ahead in the latency kernel only (80 -> 71 us at n = 120); in the wide kernel, two workgroups per CU at 128 VGPRs, it gains
                     // nothing at max_iter 300 and its registers cost the stalled passes 5 % (measured both ways)
                     if constexpr (LAT) small_factor4_la<1>(n, Klds, dyn); else small_factor4_t<true>(n, Klds, dyn);
-                } else small_factor4_t<false>(n, P.K, dyn);
+                } else if (kband) small_factor_band(n, bw, Klds, dyn);
+                else small_factor4_t<false>(n, P.K, dyn);
                 PH(PH_FACTOR); factor_valid = 1; nfactor++;
                 // The factor shares its LDS region with the linesearch scratch, so it does not survive the pass.  A copy in the
                 // item's global K buffer (58 KB at n = 120, L2-resident) lets the next passes RESTORE it while (sigma_f, d) stay
                 // what they are -- the reference's factor reuse (newton.c:21-33: nothing to do when no row enters or leaves) --
                 // instead of re-assembling and re-factoring to the same bits.  An instance that crawls towards eps for thousands
                 // of passes with a fixed active set spends most of its time there.
-                if (klds_ok) { const int tot = n * (n + 1) / 2; FOR_T(i, tot) P.K[i] = Klds[i]; lds_has_factor = 1; SYNC; }
-            } else if (klds_ok && !lds_has_factor) {
-                const int tot = n * (n + 1) / 2; FOR_T(i, tot) Klds[i] = P.K[i]; lds_has_factor = 1; nrestore++; SYNC;
+                // (the band image: n (b+1) entries)
+                if (k_in_lds) { const int tot = klds_ok ? n * (n + 1) / 2 : n * (bw + 1); FOR_T(i, tot) P.K[i] = Klds[i]; lds_has_factor = 1; SYNC; }
+            } else if (k_in_lds && !lds_has_factor) {
+                const int tot = klds_ok ? n * (n + 1) / 2 : n * (bw + 1); FOR_T(i, tot) Klds[i] = P.K[i]; lds_has_factor = 1; nrestore++; SYNC;
                 PH(PH_FACTOR);
             }
             last_branch = branch; last_sigma_f = sigma_f;
-            small_ldl_solve(P, kv, rhs, dx, xs);
+            if (kband) small_ldl_solve_band(n, bw, Klds, rhs, dx, xs); else small_ldl_solve(P, kv, rhs, dx, xs);
             PH(PH_SOLVE);
             spmv2_rows_staged(n, P.Qrp, P.Qci, P.Qval, Qdx, m, rp_s, P.Aci, P.Aval, Adx, dx, Klds, ucap);
             if (prox) { FOR_T(j, n) Qdx[j] = Qdx[j] + sigma * dx[j]; }      // (own entries of both products: no barrier between)
@@ -1728,7 +1899,7 @@ struct SmallSlot {
     std::vector<Lay> lay;
     // the batch in flight
     long count = 0; QPDOAmdBatchItem *items = nullptr; size_t upload_bytes = 0, out_bytes = 0; bool busy = false; long ticket = -1;
-    double kernel_s = 0.0;
+    double kernel_s = 0.0; int layout = -1;
 };
 // run f(i) for i in [0, count) on up to 16 host threads
 template <class F>
@@ -1781,6 +1952,64 @@ static size_t small_lds_bytes(size_t nmax, size_t mmax, int *klds_ok, size_t *un
     if (union_bytes) *union_bytes = ub;
     return lds + ub;
 }
+// ---- where K lives: THE rule, in one place (slot_submit, the fleet's create and qpdo_amd_small_factor_layout all come here) --------------
+// Half-bandwidth of Q + sigma I + A'DA for every D: the largest |i - j| over the stored entries of Q and the largest column span (last
+// column - first column) over the rows of A -- band_detect's rule (dev/host_band.inc) over ALL rows, so it depends on the pattern alone:
+// not on the weights, the scaling, qpdo_update_q's rescaling or new matrix values in the same pattern.
+static int small_item_bw(const QPDOData *d) {
+    long long b = 0;
+    const cholmod_sparse *Q = d->Q, *A = d->A;
+    for (long long j = 0; j < (long long)Q->ncol; j++)
+        for (long long k = idx_at(Q->p, Q->itype, j); k < idx_at(Q->p, Q->itype, j + 1); k++) {
+            const long long i = idx_at(Q->i, Q->itype, k), w = i > j ? i - j : j - i;
+            if (w > b) b = w;
+        }
+    static thread_local std::vector<int> first;       // the first column of every row (the columns of a CSC ascend)
+    first.assign((size_t)A->nrow, -1);
+    for (long long j = 0; j < (long long)A->ncol; j++)
+        for (long long k = idx_at(A->p, A->itype, j); k < idx_at(A->p, A->itype, j + 1); k++) {
+            int &f = first[(size_t)idx_at(A->i, A->itype, k)];
+            if (f < 0) f = (int)j; else if (j - f > b) b = j - f;
+        }
+    return (int)b;
+}
+// bw[i] of every item and the largest band image  n_i (b_i + 1) * 8  among them (data(i): the item's QPDOData)
+static const int SMALL_BAND_MAX_B = 128;             // the one-wave band solve keeps up to 128 window rows in registers (band_solve_wave<2, 2>); a wider item sends the launch to global memory
+template <class D> static size_t small_band_bytes(long count, D data, std::vector<int> &bw) {
+    bw.resize((size_t)count);
+    parallel_items(count, [&](long i) { bw[(size_t)i] = small_item_bw(data(i)); });
+    size_t mx = 0;
+    for (long i = 0; i < count; i++) {
+        if (bw[(size_t)i] > SMALL_BAND_MAX_B) return (size_t)-1;
+        const size_t by = (size_t)data(i)->n * ((size_t)bw[(size_t)i] + 1) * 8;
+        if (by > mx) mx = by;
+    }
+    return mx;
+}
+// kind 0: qpdo_amd_solve_batch, 1: a batch of a stream (both: the wide kernel's fixed part), 2: a fleet (the latency kernel's, two sets
+// of column buffers, while the factor is packed).  Today's decision first: PACKED when the packed factor of (nmax, mmax) fits.  Only where
+// K would go to global memory: BAND when the band image of EVERY item (band_bytes(): computed only then) fits the union region beside the
+// fixed part of (nmax, mmax) -- one set of column buffers: the band factorization has no look-ahead.  Otherwise GLOBAL.  QPDO_SMALL_BAND=0
+// (and the occupancy experiment QPDO_SMALL_K_GLOBAL=1) keep K out of the band layout.
+struct SmallPlan { int layout; size_t lds, ubytes; };
+static int small_kflags(const SmallPlan &p) { return p.layout | ((int)(p.ubytes / 8) << 2); }
+template <class BB> static SmallPlan small_plan(int kind, size_t nmax, size_t mmax, BB band_bytes) {
+    SmallPlan p; int ok = 0;
+    p.lds = small_lds_bytes(nmax, mmax, &ok, &p.ubytes, kind == 2);
+    bool forced_global = false;
+    if (kind != 2) { if (const char *kg = getenv("QPDO_SMALL_K_GLOBAL")) { if (atoi(kg) && ok) { ok = 0; forced_global = true; } } }      // occupancy experiments
+    if (ok) { p.layout = K_PACKED; return p; }
+    p.layout = K_GLOBAL;
+    p.lds = small_lds_bytes(nmax, mmax, nullptr, &p.ubytes, false);      // the factor in global memory: no look-ahead, one set of column buffers (fits up to n = m = 1024)
+    const char *be = getenv("QPDO_SMALL_BAND");
+    if (forced_global || (be && atoi(be) == 0)) return p;
+    const size_t bb = band_bytes(), fixed = p.lds - p.ubytes;
+    if (bb == (size_t)-1) return p;
+    const size_t ub = bb > p.ubytes ? bb : p.ubytes;
+    if (fixed + ub <= SMALL_LDS_BUDGET) { p.layout = K_BAND; p.ubytes = ub; p.lds = fixed + ub; }
+    return p;
+}
+static volatile int s_last_batch_layout = -1;    // where K lived in the last qdev_small_batch of this process
 static volatile double s_last_kernel_s = 0.0;   // (a statistic: written by whichever batch finished last; an aligned 8-byte store)
 //          // HIP-event duration of the last finished k_small_solve launch (bench.py's latency statement)
 
@@ -1884,24 +2113,29 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
         size_t nmax = 1, mmax = 0;
         for (long i = 0; i < count; i++) { if (items[i].data->n > nmax) nmax = items[i].data->n; if (items[i].data->m > mmax) mmax = items[i].data->m; }
         const size_t budget = SMALL_LDS_BUDGET;
-        int klds_ok = 0; size_t ubytes = 0;
-        size_t lds = small_lds_bytes(nmax, mmax, &klds_ok, &ubytes);
-        if (const char *kg = getenv("QPDO_SMALL_K_GLOBAL")) { if (atoi(kg) && klds_ok) { klds_ok = 0; lds = small_lds_bytes(nmax, mmax, nullptr, &ubytes); } }      // occupancy experiments
+        std::vector<int> bws;
+        const SmallPlan plan = small_plan(one_at_a_time ? 0 : 1, nmax, mmax, [&]() { return small_band_bytes(count, [&](long i) { return items[i].data; }, bws); });
+        const int klds_ok = plan.layout == K_PACKED; const size_t ubytes = plan.ubytes;
+        size_t lds = plan.lds;
+        if (plan.layout == K_BAND) for (long i = 0; i < count; i++) hp[(size_t)i].bw = bws[(size_t)i];
+        S.layout = plan.layout;
         int klds_lat = 0; size_t ub_lat = 0;
         const size_t lds_lat = small_lds_bytes(nmax, mmax, &klds_lat, &ub_lat, true);           // the latency kernel's layout (two factor buffers)
         SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(budget)));
         if (const char *pad = getenv("QPDO_SMALL_LDS_MIN")) { const size_t v = (size_t)atol(pad); if (v > lds && v <= budget) lds = v; }   // occupancy experiments
-        const int kflags = klds_ok | ((int)(ubytes / 8) << 1);       // (the LDS_MIN padding experiment below the launch only grows the tail)
+        const int kflags = small_kflags(plan);       // (the LDS_MIN padding experiment below the launch only grows the tail)
         // Which kernel (QPDO_SMALL_BATCH_KERNEL=wide|lat overrides).  "lat": the latency variant -- one workgroup per CU with 256 VGPRs and
         // the item's ~30 work vectors in LDS beside the factor; "wide": two workgroups per CU at 128 VGPRs, vectors in global memory.  Same
         // operations on the same values either way.  The wide kernel has the throughput (4096 C3 items at max_iter 300: 0.064 against
         // 0.087 s), the latency kernel the faster single item (an item that runs all 10000 passes: 0.27 against 0.33 s).  A batch that is
         // solved one at a time under a large pass limit is as slow as its slowest item: it takes the latency kernel; batches of a STREAM
         // overlap their stragglers with the next batches' ordinary items: they take the wide kernel.
+        // A band launch takes the latency kernel on the same conditions: its work vectors go behind the band image where they fit (its
+        // fixed part is the wide kernel's: no look-ahead buffers).
         size_t voff, vbytes;
-        small_vec_lds(lds_lat, nmax, mmax, &voff, &vbytes);
+        small_vec_lds(plan.layout == K_BAND ? plan.lds : lds_lat, nmax, mmax, &voff, &vbytes);
         const char *bk = getenv("QPDO_SMALL_BATCH_KERNEL");
-        const bool lat_fits = klds_ok && klds_lat && ub_lat == ubytes && voff + vbytes <= budget;
+        const bool lat_fits = (plan.layout == K_BAND || (klds_ok && klds_lat && ub_lat == ubytes)) && voff + vbytes <= budget;
         const bool use_lat = lat_fits && !(bk && !strcmp(bk, "wide")) && (bk ? !strcmp(bk, "lat") : (one_at_a_time && (count <= 256 || settings->max_iter >= 1000)));
         if (use_lat) {
             for (long i = 0; i < count; i++) hp[(size_t)i].batch_vec_off = (unsigned)voff;
@@ -1970,6 +2204,7 @@ extern "C" {
 
 const char *qdev_small_last_error(void) { return s_err; }
 double qdev_small_last_kernel_seconds(void) { return s_last_kernel_s; }
+int qdev_small_last_batch_layout(void) { return s_last_batch_layout; }
 
 // 1 if every item fits the fused kernel
 int qdev_small_eligible(long count, const void *items_) {
@@ -1994,11 +2229,36 @@ int qdev_small_eligible(long count, const void *items_) {
     return 1;
 }
 
+// The layout a launch of `kind` over these items takes (small_plan: the function the launches go through), half_bandwidth[i] of every
+// item when asked for; -1: an item does not fit the fused kernel, or an unknown kind.  Host arithmetic only.
+int qdev_small_factor_layout(long count, const void *const *data_, int kind, long *half_bandwidth) {
+    const QPDOData *const *data = (const QPDOData *const *)data_;
+    if (count < 1 || !data || kind < 0 || kind > 2) { snprintf(s_err, sizeof(s_err), "factor layout: count must be positive, data not NULL, kind 0, 1 or 2"); return -1; }
+    size_t nmax = 1, mmax = 0;
+    for (long i = 0; i < count; i++) {
+        QPDOAmdBatchItem it;
+        memset(&it, 0, sizeof(it));
+        it.data = data[i];
+        if (!data[i] || !qdev_small_eligible(1, &it)) { snprintf(s_err, sizeof(s_err), "factor layout: item %ld does not fit the fused kernel", i); return -1; }
+        if (data[i]->n > nmax) nmax = data[i]->n;
+        if (data[i]->m > mmax) mmax = data[i]->m;
+    }
+    std::vector<int> bws;
+    auto band_bytes = [&]() { return small_band_bytes(count, [&](long i) { return data[i]; }, bws); };
+    const SmallPlan plan = small_plan(kind, nmax, mmax, band_bytes);
+    if (half_bandwidth) {
+        if (bws.empty()) (void)band_bytes();
+        for (long i = 0; i < count; i++) half_bandwidth[i] = bws[(size_t)i];
+    }
+    return plan.layout;
+}
+
 // Solve all items with the fused kernel on `device`, one batch at a time.  Returns 0 on success.
 int qdev_small_batch(int device, long count, void *items_, const void *settings_) {
     std::lock_guard<std::mutex> lock(s_slot0_mu);
     int rc = slot_submit(s_slot0, device, count, (QPDOAmdBatchItem *)items_, (const QPDOSettings *)settings_, true);
     if (rc == 0) rc = slot_finish(s_slot0);
+    if (rc == 0) s_last_batch_layout = s_slot0.layout;
     s_slot0.busy = false;
     return rc;
 }
@@ -2093,7 +2353,7 @@ void *qdev_small_resident_create(const QdevSmallView *v, long trace_cap) {
     SHIP(hipHostMalloc((void **)&R->htrace, (size_t)trace_cap * sizeof(QPDOAmdTraceRec), hipHostMallocDefault));
     R->trace_cap = trace_cap;
     SHIP(hipEventCreate(&R->ev0)); SHIP(hipEventCreate(&R->ev1));
-    { size_t ub = 0; R->lds = small_lds_bytes(n, m, &R->klds_ok, &ub, true); R->kflags = R->klds_ok | ((int)(ub / 8) << 1); }
+    { size_t ub = 0; R->lds = small_lds_bytes(n, m, &R->klds_ok, &ub, true); R->kflags = (R->klds_ok ? K_PACKED : K_GLOBAL) | ((int)(ub / 8) << 2); }
     {   // vectors into LDS when they fit beside everything else (QPDO_SMALL_VEC_LDS=0: keep them in global memory)
         const size_t off = (R->lds + 15) & ~(size_t)15;
         const size_t vbytes = ((size_t)NV_COUNT * n + (size_t)MV_COUNT * m) * 8 + 3 * m * 4 + 16;

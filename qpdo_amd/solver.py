@@ -112,7 +112,8 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_update_matrices", "qpdo_amd_direct_solve", "qpdo_amd_download_factor", "qpdo_amd_pcg_probe", "qpdo_amd_download_compact",
                "qpdo_amd_fleet_create", "qpdo_amd_fleet_update", "qpdo_amd_fleet_warm_start", "qpdo_amd_fleet_warm_start_last",
                "qpdo_amd_fleet_solve", "qpdo_amd_fleet_get_stats", "qpdo_amd_fleet_get_certificates", "qpdo_amd_fleet_destroy",
-               "qpdo_amd_fleet_create_ex", "qpdo_amd_fleet_update_matrices", "qpdo_amd_fleet_get_matrix_stats"]
+               "qpdo_amd_fleet_create_ex", "qpdo_amd_fleet_update_matrices", "qpdo_amd_fleet_get_matrix_stats",
+               "qpdo_amd_small_factor_layout", "qpdo_amd_fleet_factor_layout", "qpdo_amd_batch_factor_layout"]
 
 
 class FleetStats(C.Structure):
@@ -130,6 +131,8 @@ class FleetMatrixStats(C.Structure):
 FLEET_TABLE_BYTES = 16     # QPDO_AMD_FLEET_TABLE_BYTES
 FLEET_MATRIX_UPDATES = 1   # QPDO_AMD_FLEET_MATRIX_UPDATES
 FLEET_MATRIX_TABLE_BYTES = 8     # QPDO_AMD_FLEET_MATRIX_TABLE_BYTES
+K_GLOBAL, K_PACKED, K_BAND = 0, 1, 2     # QPDO_AMD_SMALL_K_*: where the fused kernel keeps the Newton matrix
+KIND_BATCH, KIND_STREAM, KIND_FLEET = 0, 1, 2
 
 _lib = None
 
@@ -201,6 +204,12 @@ def lib():
         L.qpdo_amd_fleet_get_stats.argtypes = [C.c_void_p, C.POINTER(FleetStats)]
         L.qpdo_amd_fleet_get_certificates.argtypes = [C.c_void_p, C.c_long, dp, dp]
         L.qpdo_amd_fleet_destroy.argtypes = [C.c_void_p]
+        if hasattr(L, "qpdo_amd_small_factor_layout"):      # (absent from an older build named by QPDO_AMD_LIB for A/B timing: calling it there raises)
+            L.qpdo_amd_small_factor_layout.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), C.POINTER(QPDOSettings), C.c_int, C.POINTER(C.c_long)]
+            L.qpdo_amd_small_factor_layout.restype = C.c_int
+            L.qpdo_amd_fleet_factor_layout.argtypes = [C.c_void_p]
+            L.qpdo_amd_fleet_factor_layout.restype = C.c_int
+            L.qpdo_amd_batch_factor_layout.restype = C.c_int
         _lib = L
     return _lib
 
@@ -891,6 +900,10 @@ class Fleet:
             res.append(r)
         return res
 
+    def factor_layout(self):
+        """where this fleet's launches keep the Newton matrix: K_GLOBAL, K_PACKED or K_BAND (qpdo_amd_fleet_factor_layout)"""
+        return int(lib().qpdo_amd_fleet_factor_layout(self._h))
+
     def stats(self):
         s = FleetStats()
         self._call(lib().qpdo_amd_fleet_get_stats(self._h, C.byref(s)), "stats")
@@ -940,6 +953,25 @@ def solve_batch(probs, settings=None, nthreads=16, **kw):
     """Solve independent QPs (dicts from qpdo_amd.problems) concurrently on this process's GPU.
     Returns a list of dicts (info, x, y) and the number of failed items."""
     return Batch(probs).run(settings, nthreads, **kw)
+
+
+def small_factor_layout(probs, kind, settings=None, **kw):
+    """(layout, [half-bandwidth of every item]) of a fused-kernel launch over `probs`: K_GLOBAL, K_PACKED or K_BAND, or -1 when an item
+    does not fit the fused kernel.  kind: KIND_BATCH (solve_batch), KIND_STREAM (a batch of a BatchStream), KIND_FLEET.  Host arithmetic
+    by the function the launches go through (qpdo_amd_small_factor_layout); needs no device."""
+    if settings is None:
+        settings = default_settings(**kw)
+    img = Batch(probs)
+    n = len(probs)
+    arr = (C.POINTER(QPDOData) * max(1, n))(*[img.items[i].data for i in range(n)])
+    bw = (C.c_long * max(1, n))()
+    lay = int(lib().qpdo_amd_small_factor_layout(n, arr, C.byref(settings), int(kind), bw))
+    return lay, [int(bw[i]) for i in range(n)]
+
+
+def batch_factor_layout():
+    """the layout the last solve_batch of this process took (qpdo_amd_batch_factor_layout); -1: none yet through the fused kernel"""
+    return int(lib().qpdo_amd_batch_factor_layout())
 
 
 # ---- one large QP row-partitioned over the ranks of a torch.distributed job ---------------------------------
