@@ -16,6 +16,19 @@
  *                    message; the dense solver accepts
  *                    n <= 40000 -- its assembly tiles the LDS accumulator, QPDO_DENSE_ASM_TILE rows at a time -- and is also the rescue of
  *                    a PCG solve that cannot converge up to that order)
+ *   QPDO_BAND_COUPLING  unset or "0": off (default).  "<R>", 1 <= R <= 64: a COUPLING ROW is a row of A whose column span (last - first column)
+ *                    exceeds 127 -- a budget over the whole horizon, a terminal average, a conservation equality on a chain-structured QP.
+ *                    With 1 .. R of them, Q's bandwidth <= 127 and the other rows' spans <= 127, the band solver's half-bandwidth is that of
+ *                    the rest (b_core, at least 3) and the selection rule above runs on it (automatic from n = 2048, on request from n =
+ *                    4 (b_core + 1)); the Newton matrix is then solved as band plus low rank, K = B + U W U': the band LDL' of B = Q + sigma I
+ *                    + the other rows' term, one multi-right-hand-side band solve for Z = B^-1 U (a column per coupling row with a nonzero
+ *                    weight), the k x k system S = W^-1 + U'Z factored in LDS, and every solve checked against the true K (three SpMV;
+ *                    refinement sweeps and acceptance rule of the dense low-rank path).  While the other rows' weights and sigma stay, B's
+ *                    factor and Z are kept and only S is rebuilt (factor_count does not move).  A solve that misses the check, or a pivot
+ *                    of B or S that is not a positive finite number, hands the pass to the dense solver / PCG (band_fallbacks;
+ *                    QPDOAmdStats.coupled_*).  No such row: the plain band solver, bit for bit.  More than R: the matrix counts as not
+ *                    banded ("band" makes qpdo_setup fail with a message that names both numbers).  Q or the other rows wider than 127:
+ *                    the half-bandwidth over all rows, as without the variable.  Read at qpdo_setup; one GPU
  *   QPDO_HYBRID      where the dense solver is selected automatically and n >= 8192, every solve starts with PCG and switches to the dense
  *                    factor at the first Newton pass that needs more than 450 PCG iterations (default since round 4; same per-pass integers;
  *                    QPDOAmdStats.hybrid_pcg_passes counts the PCG passes; every numerical PCG failure hands the pass to the dense factor).  "0": off; "1": on from n = 4096; "<budget>" > 1: on from n = 4096 with that budget
@@ -131,6 +144,11 @@ typedef struct {
                              * pass, are counted but never touch the factor: updown_rejects); factor_count does not move on such a pass */
     long   updown_rejects;  /* up/downdated factors given up for a refactorization: a scan met a pivot that is not a positive finite number
                              * (the factor was not touched by that row), or a solve missed its residual check after the refinement sweeps */
+    /* band solver with coupling rows (QPDO_BAND_COUPLING; appended: the members above keep their offsets) */
+    long   coupled_rows;    /* coupling rows of the workspace (r; 0: none, or the variable is off)                                        */
+    long   coupled_solves;  /* band solves with at least one weighted coupling row that were accepted by their residual check             */
+    long   coupled_sweeps;  /* sweeps of those solves: one band solve, the k x k correction and 3 SpMV each (1 = accepted at once)         */
+    long   coupled_rejects; /* such solves that missed the residual check after the sweeps: the pass went to the band fallback (band_fallbacks) */
 } QPDOAmdStats;
 
 int  qpdo_amd_device_count(void);
@@ -175,7 +193,9 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
 /* ---- the direct solvers as single linear solves (tests of the factorizations; tests/test_gpu_direct_solvers.py) ----------------------
  * qpdo_amd_direct_solve: x (n) = K^-1 rhs (n) with K = Q + sigma I + A' diag(dw) A (dw: m weights), Q and A the workspace's stored, i.e.
  * scaled, matrices (the caller's own with settings->scaling = 0), through the workspace's direct solver exactly as a Newton pass drives
- * it: the dense LDL' (QPDO_LINSOLVE=dense, with its QPDO_DENSE_* routes) or the band LDL' (QPDO_LINSOLVE=band).
+ * it: the dense LDL' (QPDO_LINSOLVE=dense, with its QPDO_DENSE_* routes) or the band LDL' (QPDO_LINSOLVE=band; with coupling rows,
+ * QPDO_BAND_COUPLING, every call brings B's factor, Z and S up to date with dw: B is factored again only where a weight of another row or
+ * sigma moved, or bit 0 asks for it; a solve that misses its residual check returns QPDO_AMD_DIRECT_LOST like a bad pivot).
  *   flags bit 0  refactor.  Clear: the factor kept from the previous call is reused -- with QPDO_DENSE_LOWRANK on, every row whose weight
  *                differs from the factored one gets a low-rank slot (more than 256 such rows refactor); otherwise it is reused as it is,
  *                i.e. the caller passes the factored weights.  No factor yet, or (dense) another sigma: refactor.  With QPDO_DENSE_UPDOWN on,
@@ -203,7 +223,12 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
  *     7  Wb     (np / 64) x (w + 1) x 64 x 64: Wb[(J (w+1) + s) 4096 + c 64 + r] = element (r, c) of tile (J + s, J) of the unit-lower L
  *               (diagonal tiles: 1 on the diagonal, 0 above it; rows / columns n .. np-1 identity padding; tiles whose block row is
  *               >= np / 64 are zero).  An element outside the band, i - j > b, is an exact zero.
- *     8  Wd     np: D (ones behind n).  */
+ *     8  Wd     np: D (ones behind n).
+ *   band with coupling rows (QPDO_BAND_COUPLING; arrays 4 and 5 hold the factor of B, which 6 its geometry):
+ *     9  the coupled geometry, 4 entries: r = the coupling rows of the workspace, k = those with a nonzero weight at the last factorization,
+ *            b_core, np (k and np 0 before the first factorization).
+ *    10  the r coupling row numbers, ascending, as doubles.
+ *    11  Z      np x k, leading dimension np: column j = B^-1 (the j-th weighted coupling row, ascending, as a dense column).  */
 #define QPDO_AMD_DIRECT_LOST (-2)
 int  qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags);
 int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count);

@@ -206,8 +206,9 @@ __device__ __forceinline__ double band_rl64(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
 }
-__global__ __launch_bounds__(256) void k_band_solve(int n, int b, const double *__restrict__ Lb, const double *__restrict__ Lt,
-                                                    const double *__restrict__ rhs, double *__restrict__ z, double *__restrict__ x) {
+// (the body of k_band_solve; k_band_solve_multi runs it once per workgroup on a column of its own)
+__device__ __forceinline__ void band_solve_body(int n, int b, const double *__restrict__ Lb, const double *__restrict__ Lt, const double *__restrict__ rhs,
+                                                double *__restrict__ z, double *__restrict__ x) {
     extern __shared__ __attribute__((aligned(16))) double band_sbuf[];       // 4 x (BAND_SC * B1)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, B1 = b + 1, CH = BAND_SC * B1;
     const int nchunks = (n + BAND_SC - 1) / BAND_SC;
@@ -302,5 +303,168 @@ __global__ __launch_bounds__(256) void k_band_solve(int n, int b, const double *
             }
         }
         BAND_SYNC();
+    }
+}
+__global__ __launch_bounds__(256) void k_band_solve(int n, int b, const double *__restrict__ Lb, const double *__restrict__ Lt,
+                                                    const double *__restrict__ rhs, double *__restrict__ z, double *__restrict__ x) {
+    band_solve_body(n, b, Lb, Lt, rhs, z, x);
+}
+
+// ---- chain QPs with a few dense coupling rows (QPDO_BAND_COUPLING; host side: dev/host_band.inc) ------------------------------------------
+// A row of A that touches the whole horizon (a budget, a terminal average, a conservation equality) makes A'DA a full matrix, but K is
+// still band plus low rank: K = B + U W U', B = Q + sigma I + A_b' D_b A_b over the remaining rows, the columns of U = the coupling rows
+// with a nonzero weight, W = their weights.  B gets the band factorization above; the solve is Woodbury's,
+//   x = z0 - Z S^-1 (U' z0),   z0 = B^-1 v,   Z = B^-1 U,   S = W^-1 + U' Z  (k x k, symmetric positive definite),
+// inside the residual-checked refinement of the low-rank path (host_dense.inc dense_refine_checked).  The coupling rows keep fixed slots
+// 0 .. r-1 (ascending row number); a 64-bit mask names the slots a launch works on, in ascending order.
+static const int BC_MAX = 64;               // coupling rows a workspace accepts (one bit of the slot masks each)
+__device__ __forceinline__ int bc_nth_slot(u64 mask, int j) {                 // the j-th set bit of mask
+    for (int i = 0; i < j; i++) mask &= mask - 1;
+    return __ffsll((unsigned long long)mask) - 1;
+}
+// One pass over the row pointers: the rows whose column span exceeds BAND_MAX_B are counted and listed in ascending order (the first cap
+// of them), out = {their count, the largest span of the other rows, the largest span of all rows}.  One workgroup, contiguous chunk of
+// rows per thread, k_wb_select's scheme: plain stores in a fixed order.
+__global__ __launch_bounds__(1024) void k_bc_classify(int m, const int *__restrict__ rp, const int *__restrict__ ci, int cap, int *__restrict__ rows,
+                                                      int *__restrict__ out) {
+    __shared__ int sums[1024], mxc[1024], mxa[1024];
+    const int chunk = (m + 1023) / 1024;
+    const int beg = min(threadIdx.x * chunk, m), end = min(beg + chunk, m);
+    int c = 0, core = 0, all = 0;
+    for (int i = beg; i < end; i++) {
+        const int s = rp[i + 1] > rp[i] ? ci[rp[i + 1] - 1] - ci[rp[i]] : 0;
+        all = s > all ? s : all;
+        if (s > BAND_MAX_B) c++; else core = s > core ? s : core;
+    }
+    sums[threadIdx.x] = c; mxc[threadIdx.x] = core; mxa[threadIdx.x] = all;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0, a = 0, b = 0;
+        for (int i = 0; i < 1024; i++) { const int t = sums[i]; sums[i] = run; run += t; a = mxc[i] > a ? mxc[i] : a; b = mxa[i] > b ? mxa[i] : b; }
+        out[0] = run; out[1] = a; out[2] = b;
+    }
+    __syncthreads();
+    int pos = sums[threadIdx.x];
+    for (int i = beg; i < end; i++)
+        if (rp[i + 1] > rp[i] && ci[rp[i + 1] - 1] - ci[rp[i]] > BAND_MAX_B) { if (pos < cap) rows[pos] = i; pos++; }
+}
+// core weights: d with the coupling rows zeroed (k_band_assemble skips zero-weight rows, so B is assembled from the other rows alone);
+// info[0] |= 1 where they differ from the weights of the kept band factor, info[1] = k, the number of coupling rows with a nonzero
+// weight, info[2], info[3] = their slots as a 64-bit mask.  info[0] is zeroed by the host before the launch.
+__global__ void k_bc_prepare(int m, int r, const int *__restrict__ rows, const double *__restrict__ dw, double *__restrict__ dcore,
+                             const double *__restrict__ dfact, int *__restrict__ info) {
+    __shared__ int rs[BC_MAX];
+    for (int a = threadIdx.x; a < r; a += blockDim.x) rs[a] = rows[a];
+    __syncthreads();
+    int moved = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
+        int lo = 0, hi = r;                                                   // (rs ascending)
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (rs[mid] < i) lo = mid + 1; else hi = mid; }
+        const double dc = (lo < r && rs[lo] == i) ? 0.0 : dw[i];
+        dcore[i] = dc;
+        moved |= dc != dfact[i];
+    }
+    if (__any(moved) && (threadIdx.x & 63) == 0) atomicOr(&info[0], 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        u64 act = 0; int k = 0;
+        for (int a = 0; a < r; a++) if (dw[rs[a]] != 0.0) { act |= 1ull << a; k++; }
+        info[1] = k; info[2] = (int)(u32)act; info[3] = (int)(u32)(act >> 32);
+    }
+}
+// Z(:, s) = B^-1 (coupling row s as a dense column) for the slots s of `todo`: one workgroup per slot, each running k_band_solve's two
+// sweeps on columns of its own (U: the right-hand side, T: the forward sweep's result; np entries each) -- the columns advance together on
+// different CUs for the time of one solve.
+__global__ __launch_bounds__(256) void k_band_solve_multi(int n, int np, int b, const double *__restrict__ Lb, const double *__restrict__ Lt, u64 todo,
+                                                          const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                          const double *__restrict__ aval, double *U, double *T, double *Z) {
+    const int s = bc_nth_slot(todo, blockIdx.x), row = rows[s];
+    double *u = U + (size_t)s * np;
+    for (int i = threadIdx.x; i < np; i += 256) u[i] = 0.0;
+    __syncthreads();
+    for (int e = arp[row] + threadIdx.x; e < arp[row + 1]; e += 256) u[aci[e]] = aval[e];
+    __syncthreads();
+    band_solve_body(n, b, Lb, Lt, u, T + (size_t)s * np, Z + (size_t)s * np);
+}
+// S(a, c) = [a == c] / d_a + A(row_a, :) Z(:, slot_c) over the active slots, a <= c and its mirror image (k_wb_G's scheme; leading
+// dimension BC_MAX)
+__global__ __launch_bounds__(64) void k_bc_S(u64 act, const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
+                                             const double *__restrict__ aval, const double *__restrict__ dw, const double *__restrict__ Z, int np,
+                                             double *__restrict__ S) {
+    const int a = blockIdx.x, c = blockIdx.y;
+    if (a > c) return;
+    const int r = rows[bc_nth_slot(act, a)];
+    const double *zc = Z + (size_t)bc_nth_slot(act, c) * np;
+    double sacc = 0.0;
+    for (int e = arp[r] + threadIdx.x; e < arp[r + 1]; e += 64) sacc += aval[e] * zc[aci[e]];
+    sacc = wave_sum(sacc);
+    if (threadIdx.x == 0) {
+        if (a == c) sacc = 1.0 / dw[r] + sacc;
+        S[a * BC_MAX + c] = sacc; S[c * BC_MAX + a] = sacc;
+    }
+}
+// S = L D L' in one workgroup's LDS, no pivoting (S is symmetric positive definite); SL: L below the diagonal, D on it.  A pivot that is
+// not a positive finite number is latched like one of the band factorization (bit 1 of C_CHAIN_ERR).
+__global__ __launch_bounds__(256) void k_bc_factor_S(int k, const double *__restrict__ S, double *__restrict__ SL, int *__restrict__ err) {
+    __shared__ double M[BC_MAX * BC_MAX];
+    const int tid = threadIdx.x;
+    for (int e = tid; e < k * k; e += 256) { const int i = e / k, j = e - i * k; M[i * BC_MAX + j] = S[i * BC_MAX + j]; }
+    __syncthreads();
+    bool bad_pivot = false;
+    for (int j = 0; j < k; j++) {
+        const double dj = M[j * BC_MAX + j];
+        bad_pivot = bad_pivot || !(dj > 0.0 && dj < 1e300);
+        // column j: the multipliers below the diagonal, their products with d_j in row j above it (scratch: the upper triangle)
+        for (int i = j + 1 + tid; i < k; i += 256) { const double w = M[i * BC_MAX + j]; M[j * BC_MAX + i] = w; M[i * BC_MAX + j] = w / dj; }
+        __syncthreads();
+        const int nn = k - j - 1;
+        for (int e = tid; e < nn * nn; e += 256) {
+            const int i = j + 1 + e / nn, c = j + 1 + e % nn;
+            if (c <= i) M[i * BC_MAX + c] = M[i * BC_MAX + c] - M[i * BC_MAX + j] * M[j * BC_MAX + c];
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < k * k; e += 256) { const int i = e / k, j = e - i * k; if (j <= i) SL[i * BC_MAX + j] = M[i * BC_MAX + j]; }
+    if (bad_pivot && tid == 0) atomicOr(err, 2);
+}
+// t = S^-1 (U' z0): the k dot products A(row_a, :) z0, one wave each in turn, then both triangular solves by one wave (lane a keeps
+// entry a, the pivot entry is broadcast with v_readlane)
+__global__ __launch_bounds__(1024) void k_bc_t(int k, u64 act, const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
+                                               const double *__restrict__ aval, const double *__restrict__ z0, const double *__restrict__ SL,
+                                               double *__restrict__ t) {
+    __shared__ double M[BC_MAX * BC_MAX], v[BC_MAX];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int e = tid; e < k * k; e += 1024) { const int i = e / k, j = e - i * k; if (j <= i) M[i * BC_MAX + j] = SL[i * BC_MAX + j]; }
+    for (int a = wave; a < k; a += 16) {
+        const int r = rows[bc_nth_slot(act, a)];
+        double sacc = 0.0;
+        for (int e = arp[r] + lane; e < arp[r + 1]; e += 64) sacc += aval[e] * z0[aci[e]];
+        sacc = wave_sum(sacc);
+        if (lane == 0) v[a] = sacc;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    const bool in = lane < k;
+    double val = in ? v[lane] : 0.0;
+    for (int j = 0; j < k; j++) {
+        const double vj = band_rl64(val, j);
+        if (in && lane > j) val = val - M[lane * BC_MAX + j] * vj;
+    }
+    if (in) val = val / M[lane * BC_MAX + lane];
+    for (int j = k - 1; j > 0; j--) {
+        const double xj = band_rl64(val, j);
+        if (lane < j) val = val - M[j * BC_MAX + lane] * xj;
+    }
+    if (in) t[lane] = val;
+}
+// out = z0 - Z(:, active slots) t
+__global__ void k_bc_apply(int n, int np, int k, u64 act, const double *__restrict__ Z, const double *__restrict__ t, const double *__restrict__ z0,
+                           double *__restrict__ out) {
+    __shared__ double ts[BC_MAX]; __shared__ int sl[BC_MAX];
+    for (int a = threadIdx.x; a < k; a += blockDim.x) { ts[a] = t[a]; sl[a] = bc_nth_slot(act, a); }
+    __syncthreads();
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+        double sacc = 0.0;
+        for (int a = 0; a < k; a++) sacc += Z[(size_t)sl[a] * np + j] * ts[a];
+        out[j] = z0[j] - sacc;
     }
 }

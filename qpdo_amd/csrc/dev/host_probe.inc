@@ -88,7 +88,8 @@ int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *
     const bool refactor = (flags & 1) != 0, carry = (flags & 2) != 0;
     int rc = 0;
     if (d->linsolve == 3) {
-        if (refactor || !d->dense_valid) rc = band_factor(d);
+        // (a coupled workspace follows moved weights itself -- band_coupled_refresh keeps what still holds -- so it is always asked)
+        if (refactor || !d->dense_valid || d->bc_r > 0) rc = band_factor(d, refactor);
         if (!rc) rc = band_solve(d);
     } else {
         // a Newton pass knows whether (sigma_f, d) moved since the factorization; this caller only says "refactor" or not, and where the
@@ -103,7 +104,7 @@ int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *
     if (!rc && d->hctrl->cnt[C_CHAIN_ERR]) {
         lost = true;
         LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0;
+        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0; d->bc_factored = 0;
     }
     d->sigma_f = sigma_keep;
     if (m) HIPCHK(hipMemcpyAsync(d->d, d_keep.data(), (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
@@ -111,7 +112,8 @@ int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *
     HIPCHK(hipStreamSynchronize(d->stream));
     if (rc) return rc;
     if (lost) {
-        snprintf(g_err, sizeof(g_err), "direct solve: %s", d->linsolve == 3 ? "the band factorization met a pivot that is not a positive finite number"
+        snprintf(g_err, sizeof(g_err), "direct solve: %s", d->linsolve == 3 ? (d->bc_r > 0 ? "the band factorization or the coupling rows' k x k system met a pivot that is not a positive finite number, or the solve missed its residual check"
+                                                                                            : "the band factorization met a pivot that is not a positive finite number")
                                                                             : "a polling kernel lost its producer");
         return QDEV_DIRECT_LOST;
     }
@@ -124,6 +126,19 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
     if (which == 6) {
         if (count < 4) return set_err(hipErrorInvalidValue, "download factor: the geometry needs 4 entries", __LINE__);
         dst[0] = d->Kd ? (double)ld : 0.0; dst[1] = d->Kd ? (double)nb : 0.0; dst[2] = (d->Kb || d->bw_Wb) ? (double)d->band_np : 0.0; dst[3] = (d->Kb || d->bw_Wb) ? (double)d->band_b : 0.0;
+        return 0;
+    }
+    if (which >= 9 && which <= 11) {                    // coupled mode (QPDO_BAND_COUPLING)
+        if (d->bc_r <= 0) return set_err(hipErrorInvalidValue, "download factor: this workspace has no coupling rows", __LINE__);
+        const size_t np = (size_t)d->band_np;           // (0 before the first factorization, like k)
+        const size_t len = which == 9 ? 4 : which == 10 ? (size_t)d->bc_r : np * (size_t)d->bc_k;
+        if (count < 0 || (size_t)count != len) return set_err(hipErrorInvalidValue, "download factor: count is not the array's length", __LINE__);
+        if (which == 9) { dst[0] = (double)d->bc_r; dst[1] = (double)d->bc_k; dst[2] = (double)d->band_b; dst[3] = (double)np; return 0; }
+        if (which == 10) { for (int a = 0; a < d->bc_r; a++) dst[a] = (double)d->bc_rows_h[(size_t)a]; return 0; }
+        size_t j = 0;                                    // Z: the columns of the weighted coupling rows, in ascending row order
+        for (int a = 0; a < d->bc_r; a++)
+            if (d->bc_act >> a & 1) HIPCHK(hipMemcpyAsync(dst + np * j++, d->bc_Z + np * (size_t)a, np * 8, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
         return 0;
     }
     const double *src = nullptr; size_t len = 0;

@@ -288,10 +288,14 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     // natural-order factorization gives the reference on such problems -- by default from n = 2048 up (below, the dense MFMA factor of a
     // small matrix is as fast), or when asked for (QPDO_LINSOLVE=band; an explicit pcg / dense keeps those).  Half-bandwidths 128 .. 1023
     // (the tiled solver of dev/band_wide.inc) are taken only when asked for: its crossover against dense and PCG decides the default later.
+    // QPDO_BAND_COUPLING=<R>, 1 <= R <= 64 (opt-in): up to R rows of A wider than the band are taken out of it and handled as a low-rank
+    // term of the band solver (dev/band.inc, host_band.inc); the selection rule below is the same, on the half-bandwidth of the rest.
+    { const char *bc = getenv("QPDO_BAND_COUPLING"); const int R = (bc && *bc) ? atoi(bc) : 0; d->band_coupling = R <= 0 ? 0 : R > BC_MAX ? BC_MAX : R; }
     if (linsolve < 0 || linsolve == 3) {
         int rcb = band_detect(d); if (rcb) return rcb;
         const int wide_enough = d->n >= 4 * (d->band_b + 1);
         if (d->band_b > 0 && wide_enough && (linsolve == 3 || (d->band_b <= BAND_MAX_B && d->n >= 2048))) d->linsolve = 3;
+        else if (linsolve == 3 && d->bc_over) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: %d rows of A are wider than the band (column span > %d), QPDO_BAND_COUPLING accepts %d", d->bc_over, BAND_MAX_B, d->band_coupling); return -1; }
         else if (linsolve == 3) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: the Newton matrix is not banded (half-bandwidth > %d or order too small)", BAND_WIDE_MAX_B); return -1; }
     }
     if (pcg_tol > 0) d->pcg_tol = pcg_tol;
@@ -308,7 +312,7 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     if (d->linsolve != 1 || d->comm.active) d->ud_cap = 0;
     d->st.linsolve = d->linsolve;
     d->cfg.linsolve = d->linsolve; d->cfg.dense_chain = d->dense_chain; d->cfg.dense_mid = d->dense_mid; d->cfg.dense_lookahead = d->dense_lookahead;
-    d->cfg.wb_enable = d->wb_enable; d->cfg.ud_cap = d->ud_cap; d->cfg.deflate = d->deflate; d->cfg.pcg_maxit = d->pcg_maxit; d->cfg.band_b = d->band_b;
+    d->cfg.wb_enable = d->wb_enable; d->cfg.ud_cap = d->ud_cap; d->cfg.deflate = d->deflate; d->cfg.pcg_maxit = d->pcg_maxit; d->cfg.band_b = d->band_b; d->cfg.bc_r = d->bc_r;
     return 0;
 }
 // absolute stopping rule of the linear solves follows the caller's eps_abs (QPDO_PCG_ABS: the factor, default 1e-5; 0 disables)
@@ -318,7 +322,7 @@ int qdev_set_eps_abs(QpdoDev *d, double eps_abs) {
     d->pcg_abs = d->pcg_abs_factor > 0.0 ? d->pcg_abs_factor * eps_abs : -1.0;
     return 0;
 }
-int qdev_get_stats(QpdoDev *d, QdevStats *out) { *out = d->st; return 0; }
+int qdev_get_stats(QpdoDev *d, QdevStats *out) { *out = d->st; out->coupled_rows = d->bc_r; return 0; }
 int qdev_get_ac_sample(QpdoDev *d, double *seconds_sum, double *bytes_sum, long *samples, long *schur_passes) {
     *seconds_sum = d->ev_ac_ms * 1e-3; *bytes_sum = d->ev_ac_bytes; *samples = (long)d->ev_ac_n; *schur_passes = (long)d->schur_passes;
     return 0;
@@ -534,7 +538,7 @@ int qdev_begin_solve(QpdoDev *d) {
     if (d->hybrid) { d->linsolve = 0; d->hybrid_active = 1; }
     if (d->direct_hook_used) {       // a factor kept by the test entry qdev_direct_solve is not this solve's: start as an untouched workspace
         d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0; d->dense_fact_sigma = 0.0;
-        d->dense_last_branch = -1; d->dense_last_sigma = -1.0; d->direct_hook_used = 0;
+        d->dense_last_branch = -1; d->dense_last_sigma = -1.0; d->direct_hook_used = 0; d->bc_factored = 0;
     }
     // the lost-producer latch of the polling kernels is cleared by the redo (step_redo_if_lost) -- and here, so that a solve that was
     // left between the latch and its redo (a HIP error on the way) cannot make k_axpy5 skip every iterate update of the next solve

@@ -62,6 +62,7 @@ static int reset_to_setup_state(QpdoDev *d) {
     // what a solve may have switched (fallbacks of the linear solvers, the hybrid's hand-over)
     d->linsolve = d->cfg.linsolve; d->dense_chain = d->cfg.dense_chain; d->dense_mid = d->cfg.dense_mid; d->dense_lookahead = d->cfg.dense_lookahead;
     d->wb_enable = d->cfg.wb_enable; d->ud_cap = d->cfg.ud_cap; d->deflate = d->cfg.deflate; d->pcg_maxit = d->cfg.pcg_maxit; d->band_b = d->cfg.band_b;
+    d->bc_r = d->cfg.bc_r; d->bc_factored = 0; d->bc_k = 0;      // (the coupling rows are the pattern's, like band_b; the kept factor of B is not)
     d->st = QdevStats{}; d->st.linsolve = d->linsolve;
     d->ev_spmv_ms = 0; d->ev_spmv_n = 0; d->ev_ac_ms = 0; d->ev_ac_bytes = 0; d->ev_ac_n = 0;
     // the vectors and control blocks as dev_alloc left them: zero (q, l, u are written by the caller next; D, E by the scaling)

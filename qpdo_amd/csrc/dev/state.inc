@@ -95,6 +95,13 @@ struct QpdoDev {
     int dense_asm_tile = 19000;   // rows of a column the assembly accumulates in LDS at a time (152 KB of the 160 KB)
     // band direct solver (dev/band.inc): half-bandwidth of Q + A'A (-1: not banded within BAND_WIDE_MAX_B), order padded to 4, band storage
     int band_b = -1, band_np = 0; double *Kb = nullptr, *Lt = nullptr, *band_z = nullptr;
+    // chain QPs with dense coupling rows (QPDO_BAND_COUPLING = band_coupling > 0; dev/band.inc): bc_r of them (0: none, the plain band
+    // solver), band_b is then the half-bandwidth of the OTHER rows and of Q.  bc_over: more than band_coupling were counted (setup's
+    // message).  The kept factor of B belongs to (bc_dfact, bc_fact_sigma); bc_zvalid: the slots whose column of Z = B^-1 U was solved with
+    // it; bc_act / bc_k: the slots with a nonzero weight that S was last built and factored for.
+    int band_coupling = 0, bc_r = 0, bc_over = 0, bc_k = 0, bc_factored = 0; double bc_fact_sigma = 0.0; u64 bc_zvalid = 0, bc_act = 0;
+    int *bc_rows = nullptr, *bc_info = nullptr; std::vector<int> bc_rows_h;
+    double *bc_dcore = nullptr, *bc_dfact = nullptr, *bc_U = nullptr, *bc_T = nullptr, *bc_Z = nullptr, *bc_S = nullptr, *bc_SL = nullptr, *bc_t = nullptr, *bc_z0 = nullptr;
     // half-bandwidths BAND_MAX_B + 1 .. BAND_WIDE_MAX_B (dev/band_wide.inc): order padded to 64, w = (b + 63) / 64; the band as 64 x 64 tiles
     // (w + 1 per block column), the diagonal tiles while they are being updated, D, the diagonal blocks' inverses and their transposes
     int bw_w = 0; double *bw_Wb = nullptr, *bw_Wdiag = nullptr, *bw_Wd = nullptr, *bw_Li = nullptr, *bw_LiT = nullptr;
@@ -170,6 +177,6 @@ struct QpdoDev {
     double *qstage = nullptr;                     // the caller's stored Q values (stype +-1), gathered through mapQ
     std::vector<long long> upd_Ap, upd_Qp;        // column pointers whose pattern passed the device check (later calls compare these)
     // what qdev_configure decided; a solve may change these (fallbacks, hybrid), qpdo_amd_update_matrices puts them back
-    struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, ud_cap, deflate, pcg_maxit, band_b; } cfg{};
+    struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, ud_cap, deflate, pcg_maxit, band_b, bc_r; } cfg{};
 };
 

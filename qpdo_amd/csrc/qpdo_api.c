@@ -1115,6 +1115,8 @@ int qpdo_amd_get_stats(const QPDOWorkspace *work, QPDOAmdStats *out) {
     out->onelaunch_factors = (long)st.onelaunch_factors;
     out->ahead_steps = (long)st.ahead_steps; out->ahead_skips = (long)st.ahead_skips;
     out->updown_solves = (long)st.updown_solves; out->updown_rows = (long)st.updown_rows; out->updown_rejects = (long)st.updown_rejects;
+    out->coupled_rows = (long)st.coupled_rows; out->coupled_solves = (long)st.coupled_solves; out->coupled_sweeps = (long)st.coupled_sweeps;
+    out->coupled_rejects = (long)st.coupled_rejects;
     out->fused_solves = work->chol->fused_solves;
     out->fused_kernel_s = work->chol->last_fused ? work->chol->fused_kernel_s : 0.0;
     if (work->chol->last_fused) { out->factor_count = work->chol->fused_factor_count; out->linsolve = 2; }

@@ -75,6 +75,10 @@ typedef struct {
     int64_t updown_solves;      /* dense solves with a kept factor that carries in-place up/downdates, accepted by their residual check */
     int64_t updown_rows;        /* changed rows SENT through the in-place up/downdate of the kept factor (QPDO_DENSE_UPDOWN); refused rows included */
     int64_t updown_rejects;     /* up/downdated factors given up for a refactorization: a scan met a bad pivot, or a solve missed its residual check */
+    int64_t coupled_rows;       /* QPDO_BAND_COUPLING: coupling rows of the workspace (filled in by qdev_get_stats) */
+    int64_t coupled_solves;     /* band solves with at least one weighted coupling row, accepted by their residual check */
+    int64_t coupled_sweeps;     /* sweeps of those solves (each one band solve, the k x k correction and 3 SpMV) */
+    int64_t coupled_rejects;    /* such solves that missed the residual check: the pass went to the band fallback */
 } QdevStats;
 
 int qdev_device_count(void);

@@ -97,7 +97,8 @@ class Stats(C.Structure):
                 ("pcg_max_relres", C.c_double), ("pcg_dense_fallbacks", C.c_long), ("fused_solves", C.c_long), ("fused_kernel_s", C.c_double),
                 ("pcg_rescues", C.c_long), ("pcg_rescue_kinds", C.c_long), ("hybrid_pcg_passes", C.c_long), ("band_fallbacks", C.c_long),
                 ("onelaunch_factors", C.c_long), ("ahead_steps", C.c_long), ("ahead_skips", C.c_long),
-                ("updown_solves", C.c_long), ("updown_rows", C.c_long), ("updown_rejects", C.c_long)]
+                ("updown_solves", C.c_long), ("updown_rows", C.c_long), ("updown_rejects", C.c_long),
+                ("coupled_rows", C.c_long), ("coupled_solves", C.c_long), ("coupled_sweeps", C.c_long), ("coupled_rejects", C.c_long)]
 
 
 API_SYMBOLS = ["qpdo_set_default_settings", "qpdo_setup", "qpdo_warm_start", "qpdo_solve", "qpdo_update_settings",
@@ -585,6 +586,19 @@ class QPDO:
         (i, j) = Kd[i, j]), Kb / Lt as np x (b + 1) arrays (row j = column / row j of the band), Dg flat, Linv / LinvT as their raw nb x 4096
         arrays.  A band wider than 127 has Wb and Wd instead of Kb and Lt: Wb as (np / 64) x (w + 1) x 64 x 64, w = (b + 63) // 64, where
         Wb[J, s, c, r] is element (r, c) of tile (J + s, J) of the unit-lower L; Wd = D flat."""
+        if name in ("coupled_geometry", "coupled_rows", "Z"):
+            # band solver with coupling rows (QPDO_BAND_COUPLING): dict(r, k, b_core, np); the r row numbers; Z = B^-1 U as np x k
+            g = np.zeros(4)
+            if lib().qpdo_amd_download_factor(self._w, 9, _as_dp(g), 4):
+                raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+            geo = dict(r=int(g[0]), k=int(g[1]), b_core=int(g[2]), np=int(g[3]))
+            if name == "coupled_geometry":
+                return geo
+            which, count = (10, geo["r"]) if name == "coupled_rows" else (11, geo["np"] * geo["k"])
+            out = np.zeros(max(count, 1))
+            if lib().qpdo_amd_download_factor(self._w, which, _as_dp(out), count):
+                raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+            return out[:count].astype(np.int64) if name == "coupled_rows" else out[:count].reshape(geo["k"], geo["np"]).T
         g = self.factor_geometry()
         ld, nb, npad, b = g["ld"], g["nb"], g["np"], g["b"]
         which, count = {"Kd": (0, ld * ld), "Dg": (1, ld), "Linv": (2, nb * 4096), "LinvT": (3, nb * 4096),
