@@ -14,8 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libqpdo_amd.so")
 GEN_PATH = os.path.join(_HERE, "libqpdo_gen.so")
 
 HIP_SOURCES = ["qpdo_dev.hip", "qpdo_small.hip"]
-C_SOURCES = ["qpdo_api.c"]
-HEADERS = ["qpdo_dev.h", os.path.join(INCLUDE, "qpdo.h"), os.path.join(INCLUDE, "qpdo_amd_ext.h")] + \
+C_SOURCES = ["qpdo_api.c", "csc_convert.c"]
+HEADERS = ["qpdo_dev.h", "csc_convert.h", os.path.join(INCLUDE, "qpdo.h"), os.path.join(INCLUDE, "qpdo_amd_ext.h")] + \
     sorted(os.path.join("dev", f) for f in os.listdir(os.path.join(CSRC, "dev")) if f.endswith(".inc"))
 
 
@@ -107,7 +107,7 @@ def build_lib_testhooks(out_dir):
     so = os.path.join(out_dir, "libqpdo_amd_testhooks.so")
     gomp = subprocess.check_output(["gcc", "-print-file-name=libgomp.so"], text=True).strip()
     subprocess.check_call([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, o, os.path.join(CSRC, "qpdo_small.hip.o"),
-                           os.path.join(CSRC, "qpdo_api.c.o"), "-lm", "-lpthread", "-L/opt/rocm/lib", "-lrccl", gomp])
+                           *(os.path.join(CSRC, s + ".o") for s in C_SOURCES), "-lm", "-lpthread", "-L/opt/rocm/lib", "-lrccl", gomp])
     return so
 
 
@@ -137,7 +137,7 @@ def build_all(force=False, verbose=False):
 def build_abi_driver(out_dir, sanitize=False, driver="abi_driver.c"):
     """Compiles tests/abi_driver.c -- a plain-C caller that includes only include/qpdo.h -- (or another stand-alone C caller under
     tests/, `driver`) and links it against the
-    product library.  sanitize=True: the host driver (qpdo_api.c, gcc) is rebuilt with -fsanitize=address,undefined and
+    product library.  sanitize=True: the host driver (qpdo_api.c and csc_convert.c, gcc) is rebuilt with -fsanitize=address,undefined and
     linked with the already compiled device objects into libqpdo_amd_asan.so inside out_dir (the product library in
     the tree is not touched); the driver is instrumented too.  Returns the path of the executable."""
     root = os.path.dirname(_HERE)
@@ -155,13 +155,15 @@ def build_abi_driver(out_dir, sanitize=False, driver="abi_driver.c"):
     objs = [os.path.join(CSRC, s + ".o") for s in HIP_SOURCES]
     if not all(os.path.exists(o) for o in objs):
         build_lib(force=True)
-    api = os.path.join(out_dir, "qpdo_api_asan.o")
     san = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-g"]
-    subprocess.check_call(["gcc", "-std=gnu11", "-O1", *san, "-ffp-contract=off", "-fopenmp", "-fPIC", "-Wall", "-I", INCLUDE, "-I", CSRC,
-                           "-c", os.path.join(CSRC, "qpdo_api.c"), "-o", api])
+    api = []
+    for s in C_SOURCES:
+        api.append(os.path.join(out_dir, os.path.splitext(s)[0] + "_asan.o"))
+        subprocess.check_call(["gcc", "-std=gnu11", "-O1", *san, "-ffp-contract=off", "-fopenmp", "-fPIC", "-Wall", "-I", INCLUDE, "-I", CSRC,
+                               "-c", os.path.join(CSRC, s), "-o", api[-1]])
     so = os.path.join(out_dir, "libqpdo_amd_asan.so")
     rt = [subprocess.check_output(["gcc", "-print-file-name=" + n], text=True).strip() for n in ("libgomp.so", "libasan.so", "libubsan.so")]
-    subprocess.check_call([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, api, *objs, "-lm", "-lpthread", "-L/opt/rocm/lib", "-lrccl", *rt])
+    subprocess.check_call([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, *api, *objs, "-lm", "-lpthread", "-L/opt/rocm/lib", "-lrccl", *rt])
     subprocess.check_call(["gcc", "-std=gnu11", "-O1", *san, "-Wall", "-I", INCLUDE, src, "-o", exe, "-L", out_dir, "-lqpdo_amd_asan",
                            "-Wl,-rpath," + out_dir, "-lm"])
     return exe

@@ -173,6 +173,7 @@ void qdev_small_fleet_destroy(void *h) { fleet_free((SmallFleet *)h); }
 // failure with qdev_small_last_error() set and nothing left allocated.
 void *qdev_small_fleet_create(int device, long count, const void *const *data_, const void *settings_, long flags) {
     int rc = 0;
+    std::atomic<int> conv_failed{0};
     const bool mu = (flags & QPDO_AMD_FLEET_MATRIX_UPDATES) != 0;
     struct MatLay { size_t mapA = 0, mapQ = 0, rq = 0, rl = 0, ru = 0, rawA = 0, rawQ = 0; bool has_mapQ = false; };
     std::vector<MatLay> ml(mu ? (size_t)count : 0);
@@ -249,10 +250,10 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     h = (char *)calloc(upload_bytes ? upload_bytes : 1, 1);
     if (!h) { snprintf(s_err, sizeof(s_err), "fleet: host staging allocation failed"); rc = -1; goto done; }
     parallel_items(count, [&](long i) {              // the conversions of slot_submit, straight into the staging image
-        static thread_local ConvScratch W;
-        if (!mu) { lay_convert(data[i], lay[(size_t)i], h, W); return; }
+        static thread_local ItemScratch W;
+        if (!mu) { if (lay_convert(data[i], lay[(size_t)i], h, W)) conv_failed = 1; return; }
         const QPDOData *d = data[i]; const MatLay &X = ml[(size_t)i]; FleetPattern &Pt = F->pat[(size_t)i];
-        lay_convert(d, lay[(size_t)i], h, W, (int *)(h + X.mapA), X.has_mapQ ? (int *)(h + X.mapQ) : nullptr);
+        if (lay_convert(d, lay[(size_t)i], h, W, (int *)(h + X.mapA), X.has_mapQ ? (int *)(h + X.mapQ) : nullptr)) { conv_failed = 1; return; }
         auto keep = [](const cholmod_sparse *M, std::vector<int> &p, std::vector<int> &ix) {
             const long long nc = (long long)M->ncol, nnz = idx_at(M->p, M->itype, nc);
             p.resize((size_t)nc + 1); ix.resize((size_t)nnz);
@@ -262,6 +263,7 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
         Pt.Anrow = d->A->nrow; Pt.Ancol = d->A->ncol; Pt.Qnrow = d->Q->nrow; Pt.Qncol = d->Q->ncol; Pt.Qstype = d->Q->stype;
         keep(d->A, Pt.Ap, Pt.Ai); keep(d->Q, Pt.Qp, Pt.Qi);
     });
+    if (conv_failed) { snprintf(s_err, sizeof(s_err), "fleet: host memory for the matrix conversions"); rc = -1; goto done; }
     SHIP(hipMemcpyAsync(F->arena, h, upload_bytes, hipMemcpyHostToDevice, F->stream));     // the only matrix upload the fleet ever makes
     F->matrix_bytes = (long)upload_bytes;
     {

@@ -6,8 +6,8 @@
 //   * transposition = a STABLE LSD radix sort of the entry positions by their minor index (8-bit digits, ballot ranking inside a wave,
 //     per-(digit, block) offsets from a scanned histogram): entries of one output row keep their source order, i.e. ascending major
 //     index -- the rows come out column-sorted, exactly the arrays the host's counting pass produced (duplicates keep their order too);
-//   * the symmetric expansion merges, per row, the kept part of the transposed triangle with the mirrored stored column (the rule of
-//     qpdo_api.c sym_to_full_csr).
+//   * the symmetric expansion merges, per row, the kept part of the transposed triangle with the mirrored stored column (the rule
+//     written down in csc_convert.h, which csc_convert.c sym_to_full_csr implements on the host).
 // Integer work only; the arrays are bit-for-bit those of the host path (tests: test_device_setup_matches_host_setup).
 // ------------------------------------------------------------------------------------------------
 static const int RT_ITEMS = 32;                      // keys per thread per block of the sort (scan_sort.inc)

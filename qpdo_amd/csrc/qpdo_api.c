@@ -15,12 +15,12 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
-#include <omp.h>
 #include <pthread.h>
 
 #include "qpdo.h"
 #include "qpdo_amd_ext.h"
 #include "qpdo_dev.h"
+#include "csc_convert.h"
 #include "pass_decision.h"
 
 struct QPDO_TIMER { struct timespec tic, toc; };   /* reference include/util.h:98-104 */
@@ -156,12 +156,7 @@ static void warn_hw_queues_once(int depth) {
 
 static int env_int_early(const char *name, int dflt) { const char *v = getenv(name); return (v && *v) ? atoi(v) : dflt; }
 static double wall_now(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-/* ---- matrix intake: CSC (int32 or int64 indices) -> int32 CSR triples ------------- */
-typedef struct { int32_t nrows, ncols; int64_t nnz; int32_t *rp, *ci; double *val; } HostCsr;
-static void host_csr_free(HostCsr *h) { free(h->rp); free(h->ci); free(h->val); memset(h, 0, sizeof(*h)); }
-static inline int64_t idx_at(const void *a, int itype, int64_t k) {
-    return itype == 0 ? (int64_t)((const int32_t *)a)[k] : (int64_t)((const int64_t *)a)[k];
-}
+/* ---- matrix intake: CSC (int32 or int64 indices) -> int32 CSR triples (csc_convert.h) ------------- */
 static int sparse_ok(const cholmod_sparse *M) {
     if (!M || !M->p) return 0;
     if (M->itype != 0 && M->itype != 2) return 0;      /* CHOLMOD_INT / CHOLMOD_LONG */
@@ -185,132 +180,30 @@ static void host_csr_free_async(HostCsr *a, HostCsr *b, HostCsr *c) {
     }
     host_csr_free(a); host_csr_free(b); host_csr_free(c);
 }
-/* host threads for the conversions (OpenMP; QPDO_SETUP_THREADS, default min(16, cores)) */
-static int conv_threads(void) {
-    int t = env_int_early("QPDO_SETUP_THREADS", 0);
-    if (t <= 0) { t = omp_get_max_threads(); if (t > 16) t = 16; }
-    return t < 1 ? 1 : t;
-}
-/* the CSC arrays of an r x c matrix are the CSR arrays of its c x r transpose */
-static int csc_as_csr_of_transpose(const cholmod_sparse *M, HostCsr *out) {
-    const int64_t nc = (int64_t)M->ncol, nnz = idx_at(M->p, M->itype, nc);
+/* One image of M into arrays of its own: CSR(M), CSR(M') or the full symmetric CSR (M = Q).  The conversions run on
+ * QPDO_SETUP_THREADS OpenMP threads (default min(16, cores)).  Returns 1, or 0 (no memory; a full Q of INT32_MAX entries or more). */
+enum { IMG_CSR, IMG_CSR_T, IMG_SYM_FULL };
+static int host_csr_from(const cholmod_sparse *M, int which, HostCsr *out) {
+    const int64_t nnz = idx_at(M->p, M->itype, (int64_t)M->ncol);
+    /* a triangle mirrors into 2 nnz - (its diagonal entries): room for 2 nnz, at most n untouched entries too many, spares the full Q
+     * a serial count pass over the stored entries (sym_full_nnz) before the threaded conversion */
+    const int64_t cap = (which == IMG_SYM_FULL && M->stype) ? 2 * nnz : nnz;
+    const int threads = env_int_early("QPDO_SETUP_THREADS", 0);
+    ConvScratch W;
+    int rc = 0;
     memset(out, 0, sizeof(*out));
-    out->nrows = (int32_t)M->ncol; out->ncols = (int32_t)M->nrow; out->nnz = nnz;
-    out->rp = malloc(((size_t)nc + 1) * sizeof(int32_t));
-    out->ci = malloc((size_t)(nnz ? nnz : 1) * sizeof(int32_t));
-    out->val = malloc((size_t)(nnz ? nnz : 1) * sizeof(double));
+    out->nrows = (int32_t)(which == IMG_CSR ? M->nrow : M->ncol); out->ncols = (int32_t)(which == IMG_CSR ? M->ncol : M->nrow);
+    out->rp = malloc(((size_t)out->nrows + 1) * sizeof(int32_t));
+    out->ci = malloc((size_t)(cap ? cap : 1) * sizeof(int32_t));
+    out->val = malloc((size_t)(cap ? cap : 1) * sizeof(double));
     if (!out->rp || !out->ci || !out->val) { host_csr_free(out); return 0; }
-    const int T = conv_threads();
-    const double *x = M->x;
-#pragma omp parallel num_threads(T) if (nnz > 200000)
-    {
-#pragma omp for schedule(static) nowait
-        for (int64_t j = 0; j <= nc; j++) out->rp[j] = (int32_t)idx_at(M->p, M->itype, j);
-#pragma omp for schedule(static)
-        for (int64_t k = 0; k < nnz; k++) { out->ci[k] = (int32_t)idx_at(M->i, M->itype, k); out->val[k] = x[k]; }
-    }
-    return 1;
-}
-/* CSR of the r x c matrix itself, rows column-sorted.  The columns are cut into T contiguous ranges of equal
- * nnz; thread t counts its range per row, a prefix over (row, t) gives every thread its first slot in each row,
- * and the threads scatter their ranges in column order -- the result is the one a serial counting pass gives. */
-static int csc_to_csr(const cholmod_sparse *M, HostCsr *out) {
-    const int64_t nr = (int64_t)M->nrow, nc = (int64_t)M->ncol, nnz = idx_at(M->p, M->itype, nc);
-    memset(out, 0, sizeof(*out));
-    out->nrows = (int32_t)nr; out->ncols = (int32_t)nc; out->nnz = nnz;
-    int T = conv_threads();
-    if ((nnz < 200000 && env_int_early("QPDO_SETUP_THREADS", 0) <= 0) || (int64_t)T * nr > 400000000LL) T = 1;
-    out->rp = calloc((size_t)nr + 1, sizeof(int32_t));
-    out->ci = malloc((size_t)(nnz ? nnz : 1) * sizeof(int32_t));
-    out->val = malloc((size_t)(nnz ? nnz : 1) * sizeof(double));
-    int32_t *cnt = calloc((size_t)T * (size_t)(nr ? nr : 1), sizeof(int32_t));     /* cnt[t*nr + i] */
-    int64_t *cut = malloc(((size_t)T + 1) * sizeof(int64_t));                          /* column ranges */
-    if (!out->rp || !out->ci || !out->val || !cnt || !cut) { free(cnt); free(cut); host_csr_free(out); return 0; }
-    cut[0] = 0; cut[T] = nc;
-    for (int t = 1; t < T; t++) {            /* first column whose start offset reaches t/T of the entries */
-        const int64_t target = nnz / T * t;
-        int64_t lo = cut[t - 1], hi = nc;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (idx_at(M->p, M->itype, mid) < target) lo = mid + 1; else hi = mid; }
-        cut[t] = lo;
-    }
-    const double *x = M->x;
-#pragma omp parallel num_threads(T)
-    {
-        const int t = omp_get_thread_num();
-        int32_t *c = cnt + (size_t)t * (size_t)nr;
-        const int64_t kb = idx_at(M->p, M->itype, cut[t]), ke = idx_at(M->p, M->itype, cut[t + 1]);
-        for (int64_t k = kb; k < ke; k++) c[idx_at(M->i, M->itype, k)]++;
-#pragma omp barrier
-#pragma omp for schedule(static)
-        for (int64_t i = 0; i < nr; i++) {   /* row totals; cnt becomes the offset of thread t inside row i */
-            int32_t run = 0;
-            for (int tt = 0; tt < T; tt++) { const int32_t v = cnt[(size_t)tt * (size_t)nr + i]; cnt[(size_t)tt * (size_t)nr + i] = run; run += v; }
-            out->rp[i + 1] = run;
-        }
-#pragma omp single
-        for (int64_t i = 0; i < nr; i++) out->rp[i + 1] += out->rp[i];
-        for (int64_t j = cut[t]; j < cut[t + 1]; j++) {
-            const int64_t b = idx_at(M->p, M->itype, j), e = idx_at(M->p, M->itype, j + 1);
-            for (int64_t k = b; k < e; k++) {
-                const int64_t i = idx_at(M->i, M->itype, k);
-                const int32_t s = out->rp[i] + c[i]++;
-                out->ci[s] = (int32_t)j; out->val[s] = x[k];
-            }
-        }
-    }
-    free(cnt); free(cut);
-    return 1;
-}
-/* full symmetric CSR of Q from one stored triangle (stype -1 lower, +1 upper) or from full storage (stype 0).
- * Lower stored: row i = CSR(L) row i (columns <= i, ascending) followed by column i of L below the diagonal
- * (ascending rows = ascending columns of the mirror).  Upper stored: column i of U up to the diagonal, then
- * CSR(U) row i beyond it.  Rows come out column-sorted for column-sorted input; entries on the wrong side of
- * the stored triangle are ignored, as CHOLMOD does for stype != 0. */
-static int sym_to_full_csr(const cholmod_sparse *Q, HostCsr *out) {
-    const int64_t n = (int64_t)Q->ncol;
-    const int st = Q->stype;
-    if (st == 0) return csc_as_csr_of_transpose(Q, out);      /* symmetric: transpose == itself */
-    HostCsr R;                                                /* CSR of the stored matrix (all its entries) */
-    if (!csc_to_csr(Q, &R)) return 0;
-    memset(out, 0, sizeof(*out));
-    out->nrows = out->ncols = (int32_t)n;
-    out->rp = calloc((size_t)n + 1, sizeof(int32_t));
-    if (!out->rp) { host_csr_free(&R); return 0; }
-    const int T = conv_threads();
-    const int par = R.nnz > 200000;
-    /* an entry (i,j) of the stored matrix counts when it is on the stored side or the diagonal */
-#define KEEP_CSR(i, j) ((st < 0) ? ((j) <= (i)) : ((j) >= (i)))      /* CSR row i keeps (i,j): own triangle incl. diagonal */
-#define KEEP_MIR(i, j) ((st < 0) ? ((i) > (j)) : ((i) < (j)))        /* CSC column j entry (i,j) mirrors into row j as (j,i) */
-#pragma omp parallel for schedule(static) num_threads(T) if (par)
-    for (int64_t i = 0; i < n; i++) {
-        int32_t c = 0;
-        for (int32_t k = R.rp[i]; k < R.rp[i + 1]; k++) c += KEEP_CSR(i, (int64_t)R.ci[k]);
-        const int64_t b = idx_at(Q->p, Q->itype, i), e = idx_at(Q->p, Q->itype, i + 1);
-        for (int64_t k = b; k < e; k++) c += KEEP_MIR(idx_at(Q->i, Q->itype, k), i);
-        out->rp[i + 1] = c;
-    }
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; i++) { total += out->rp[i + 1]; if (total >= (int64_t)INT32_MAX) { host_csr_free(&R); host_csr_free(out); return 0; } out->rp[i + 1] = (int32_t)total; }
-    out->nnz = total;
-    out->ci = malloc((size_t)(total ? total : 1) * sizeof(int32_t));
-    out->val = malloc((size_t)(total ? total : 1) * sizeof(double));
-    if (!out->ci || !out->val) { host_csr_free(&R); host_csr_free(out); return 0; }
-    const double *x = Q->x;
-#pragma omp parallel for schedule(static) num_threads(T) if (par)
-    for (int64_t i = 0; i < n; i++) {
-        int32_t s = out->rp[i];
-        const int64_t b = idx_at(Q->p, Q->itype, i), e = idx_at(Q->p, Q->itype, i + 1);
-        if (st < 0) {       /* columns <= i from the CSR row, then the mirrored column below the diagonal */
-            for (int32_t k = R.rp[i]; k < R.rp[i + 1]; k++) if (KEEP_CSR(i, (int64_t)R.ci[k])) { out->ci[s] = R.ci[k]; out->val[s] = R.val[k]; s++; }
-            for (int64_t k = b; k < e; k++) { const int64_t r = idx_at(Q->i, Q->itype, k); if (KEEP_MIR(r, i)) { out->ci[s] = (int32_t)r; out->val[s] = x[k]; s++; } }
-        } else {            /* mirrored column above the diagonal, then columns >= i from the CSR row */
-            for (int64_t k = b; k < e; k++) { const int64_t r = idx_at(Q->i, Q->itype, k); if (KEEP_MIR(r, i)) { out->ci[s] = (int32_t)r; out->val[s] = x[k]; s++; } }
-            for (int32_t k = R.rp[i]; k < R.rp[i + 1]; k++) if (KEEP_CSR(i, (int64_t)R.ci[k])) { out->ci[s] = R.ci[k]; out->val[s] = R.val[k]; s++; }
-        }
-    }
-#undef KEEP_CSR
-#undef KEEP_MIR
-    host_csr_free(&R);
+    conv_scratch_init(&W);
+    if (which == IMG_CSR) rc = csc_to_csr(M, out->rp, out->ci, out->val, NULL, threads, &W);
+    else if (which == IMG_CSR_T) csc_as_csr_of_transpose(M, out->rp, out->ci, out->val, threads);
+    else rc = sym_to_full_csr(M, out->rp, out->ci, out->val, NULL, threads, &W);
+    conv_scratch_free(&W);
+    if (rc) { host_csr_free(out); return 0; }
+    out->nnz = out->rp[out->nrows];
     return 1;
 }
 
@@ -401,6 +294,71 @@ static void small_resident_setup(QPDOWorkspace *work, const QPDOSettings *settin
     }
 }
 
+/* QPDO_LINSOLVE as the backend's mode: -1 automatic, 0 pcg, 1 dense, 3 band */
+static int linsolve_mode_env(void) {
+    const char *ls = getenv("QPDO_LINSOLVE");
+    if (ls && !strcmp(ls, "pcg")) return 0;
+    if (ls && !strcmp(ls, "dense")) return 1;
+    if (ls && !strcmp(ls, "band")) return 3;
+    return -1;
+}
+/* the device of this process: QPDO_DEVICE, else LOCAL_RANK, modulo the visible devices.  Returns 0 when there is none: the caller refuses */
+#define NO_DEVICE_MSG "no HIP device available (this library has no CPU path)"
+static int pick_device(int *device) {
+    const int ndev = qdev_device_count();
+    if (ndev <= 0) return 0;
+    *device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
+    return 1;
+}
+
+/* The device backend from the three host images: whole on one GPU, or -- a row partition -- this rank's rows [m0, m0+mloc) of A, the
+ * same columns of A' and rows [n0, n0+nloc) of Q (cut_row_partition, csc_convert.h; the ranges go into dd). */
+static QdevCsr csr_view(const HostCsr *h) { QdevCsr v = {h->nrows, h->ncols, h->nnz, h->rp, h->ci, h->val}; return v; }
+static int create_from_host(QPDOWorkspace *work, int device, const HostCsr *Ar, const HostCsr *At, const HostCsr *Qf, QdevDist *dd) {
+    const int32_t n = (int32_t)work->data->n, m = (int32_t)work->data->m;
+    const QdevCsr a = csr_view(Ar), t = csr_view(At), qf = csr_view(Qf);
+    if (dd->world <= 1 && !dd->force)
+        return qdev_create(&work->chol->dev, device, n, m, &a, &t, &qf, work->data->q, work->data->l, work->data->u);
+    RowPartition P;
+    if (cut_row_partition(Ar, At, Qf, dd->rank, dd->world, &P)) return -1;
+    dd->m0 = P.m0; dd->mloc = P.mloc; dd->n0 = P.n0; dd->nloc = P.nloc;
+    const QdevCsr al = csr_view(&P.Al), tl = csr_view(&P.Tl), ql = csr_view(&P.Ql);
+    const int rc = qdev_create_dist(&work->chol->dev, device, n, m, &al, &tl, &qf, &ql, work->data->q, work->data->l, work->data->u, dd);
+    row_partition_free(&P);
+    return rc;
+}
+
+/* scale_data (scaling.c:24-91) for the matrices, q, l, u now on the device: A, Q, q there, l and u through the host mirrors; the
+ * totals installed; || Dinv q || (qpdo.c:163-165).  allocate: qpdo_setup -- the scaling arrays are made first, and the unscaled
+ * values stay on the device for qpdo_amd_update_matrices (a matrix it is not given is scaled again from them).  An unscaled
+ * workspace installs the identity.  Returns 0, -1 with the reason in qdev_last_error(), or 1 when the scaling arrays cannot be allocated. */
+static int apply_scaling(QPDOWorkspace *work, int allocate, int prof) {
+    const size_t n = work->data->n, m = work->data->m;
+    QpdoDev *dev = work->chol->dev;
+    if (allocate && work->settings->scaling) {
+        QPDOScaling *sc = work->scaling = calloc(1, sizeof(QPDOScaling));
+        if (sc) { sc->D = calloc(n ? n : 1, sizeof(c_float)); sc->Dinv = calloc(n ? n : 1, sizeof(c_float)); sc->E = calloc(m ? m : 1, sizeof(c_float)); sc->Einv = calloc(m ? m : 1, sizeof(c_float)); }
+        if (!sc || !sc->D || !sc->Dinv || !sc->E || !sc->Einv) return 1;
+        if (qdev_keep_raw_values(dev)) return -1;
+    }
+    QPDOScaling *sc = work->scaling;
+    if (!sc) {
+        if (qdev_set_scaling(dev, 0, NULL, NULL, NULL, NULL, 1.0, 1.0)) return -1;
+        work->norm_q = vec_norm_inf(work->data->q, n);
+        return 0;
+    }
+    const double ts0 = wall_now();
+    if (qdev_scale_data(dev, (int)work->settings->scaling, 0, sc->D, sc->E, &sc->c)) return -1;
+    if (prof) fprintf(stderr, "[setup] device scaling    %.3f s\n", wall_now() - ts0);
+    if (install_scaling(work) || qdev_download_q(dev, work->data->q)) return -1;
+    for (size_t i = 0; i < m; i++) { work->data->l[i] = sc->E[i] * work->data->l[i]; work->data->u[i] = sc->E[i] * work->data->u[i]; }
+    if (qdev_upload_bounds(dev, work->data->l, work->data->u)) return -1;
+    c_float mx = 0.0;
+    for (size_t i = 0; i < n; i++) { c_float s = c_absval(sc->Dinv[i] * work->data->q[i]); mx = s > mx ? s : mx; }
+    work->norm_q = mx;
+    return 0;
+}
+
 /* ---- qpdo_setup (reference src/qpdo.c:49-212) ----------------------------------------- */
 QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
     if (!validate_data(data)) { QPDO_EPRINT("Data validation returned failure"); return QPDO_NULL; }
@@ -442,134 +400,49 @@ QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
     work->chol->fix_status_reset = env_int("QPDO_FIX_STATUS_RESET", 0);
     work->chol->q_raw = vec_dup(data->q, n); work->chol->l_raw = vec_dup(data->l, m); work->chol->u_raw = vec_dup(data->u, m);
     if (!work->chol->q_raw || !work->chol->l_raw || !work->chol->u_raw) goto fail;
-    work->chol->q_stype = data->Q->stype;
-    work->chol->q_nnz = idx_at(data->Q->p, data->Q->itype, (int64_t)data->Q->ncol); work->chol->a_nnz = idx_at(data->A->p, data->A->itype, (int64_t)data->A->ncol);
+    const cholmod_sparse *A = data->A, *Q = data->Q;
+    work->chol->q_stype = Q->stype;
+    work->chol->q_nnz = idx_at(Q->p, Q->itype, (int64_t)Q->ncol); work->chol->a_nnz = idx_at(A->p, A->itype, (int64_t)A->ncol);
 
-    int on_device = 0;
-    {   /* matrices to the device.  One GPU (the default): the caller's CSC arrays are uploaded as they are -- they ARE CSR(A') -- and
-         * CSR(A) and the full symmetric CSR(Q) are built on the device (qdev_create_csc: the same arrays, bit for bit, that the host
-         * conversions below produce; QPDO_SETUP_HOST=1 keeps those).  A row-partitioned workspace cuts its slices on the host. */
-        QdevDist dd0;
-        pthread_mutex_lock(&g_dist_mu); dd0 = g_dist; pthread_mutex_unlock(&g_dist_mu);
-        if (dd0.world <= 1 && !dd0.force && !env_int("QPDO_SETUP_HOST", 0)) {
-            const int prof = env_int("QPDO_SETUP_PROF", 0);
-            const double t0 = wall_now();
-            int ndev = qdev_device_count();
-            if (ndev <= 0) { QPDO_EPRINT("no HIP device available (this library has no CPU path)"); goto fail; }
-            int device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
-            const cholmod_sparse *A = data->A, *Q = data->Q;
-            QdevCsc a = {(int32_t)A->nrow, (int32_t)A->ncol, idx_at(A->p, A->itype, (int64_t)A->ncol), A->itype, A->p, A->i, (const double *)A->x, 0};
-            QdevCsc qq = {(int32_t)Q->nrow, (int32_t)Q->ncol, idx_at(Q->p, Q->itype, (int64_t)Q->ncol), Q->itype, Q->p, Q->i, (const double *)Q->x, Q->stype};
-            if (qdev_create_csc(&work->chol->dev, device, (int32_t)n, (int32_t)m, &a, &qq, work->data->q, work->data->l, work->data->u)) {
-                QPDO_EPRINT("device backend: %s", qdev_last_error()); goto fail;
-            }
-            if (prof) fprintf(stderr, "[setup] device create     %.3f s (upload of the CSC arrays, transpositions and slab tables on the device)\n", wall_now() - t0);
-            const char *ls = getenv("QPDO_LINSOLVE");
-            int mode = -1;
-            if (ls && !strcmp(ls, "pcg")) mode = 0; else if (ls && !strcmp(ls, "dense")) mode = 1; else if (ls && !strcmp(ls, "band")) mode = 3;
-            if (qdev_configure(work->chol->dev, mode, env_double("QPDO_PCG_TOL", 0.0), env_int("QPDO_PCG_MAXIT", 0))) { QPDO_EPRINT("device backend: %s", qdev_last_error()); goto fail; }
-            on_device = 1;
-        }
-    }
-    if (!on_device) {   /* host conversions (row-partitioned workspaces; QPDO_SETUP_HOST=1) */
+    /* matrices to the device.  One GPU (the default): the caller's CSC arrays are uploaded as they are -- they ARE CSR(A') -- and
+     * CSR(A) and the full symmetric CSR(Q) are built on the device (qdev_create_csc: the same arrays, bit for bit, that the host
+     * conversions of csc_convert.c produce; QPDO_SETUP_HOST=1 keeps those).  A row-partitioned workspace cuts its slices on the host. */
+    const int prof = env_int("QPDO_SETUP_PROF", 0);
+    int device;
+    QdevDist dd;
+    pthread_mutex_lock(&g_dist_mu); dd = g_dist; pthread_mutex_unlock(&g_dist_mu);
+    double t0 = wall_now();
+    if (dd.world <= 1 && !dd.force && !env_int("QPDO_SETUP_HOST", 0)) {
+        if (!pick_device(&device)) { QPDO_EPRINT(NO_DEVICE_MSG); goto fail; }
+        QdevCsc a = {(int32_t)A->nrow, (int32_t)A->ncol, work->chol->a_nnz, A->itype, A->p, A->i, (const double *)A->x, 0};
+        QdevCsc qq = {(int32_t)Q->nrow, (int32_t)Q->ncol, work->chol->q_nnz, Q->itype, Q->p, Q->i, (const double *)Q->x, Q->stype};
+        if (qdev_create_csc(&work->chol->dev, device, (int32_t)n, (int32_t)m, &a, &qq, work->data->q, work->data->l, work->data->u)) goto fail_dev;
+        if (prof) fprintf(stderr, "[setup] device create     %.3f s (upload of the CSC arrays, transpositions and slab tables on the device)\n", wall_now() - t0);
+    } else {   /* host conversions (row-partitioned workspaces; QPDO_SETUP_HOST=1) */
         HostCsr Ar = {0}, At = {0}, Qf = {0};
-        const int prof = env_int("QPDO_SETUP_PROF", 0);
-        double t0 = wall_now();
-        int ok = csc_to_csr(data->A, &Ar);
+        int ok = host_csr_from(A, IMG_CSR, &Ar);
         if (prof) { fprintf(stderr, "[setup] CSR(A)            %.3f s\n", wall_now() - t0); t0 = wall_now(); }
-        ok = ok && csc_as_csr_of_transpose(data->A, &At);
+        ok = ok && host_csr_from(A, IMG_CSR_T, &At);
         if (prof) { fprintf(stderr, "[setup] CSR(A') narrowing %.3f s\n", wall_now() - t0); t0 = wall_now(); }
-        ok = ok && sym_to_full_csr(data->Q, &Qf);
+        ok = ok && host_csr_from(Q, IMG_SYM_FULL, &Qf);
         if (prof) { fprintf(stderr, "[setup] full CSR(Q)       %.3f s\n", wall_now() - t0); t0 = wall_now(); }
         if (!ok) { host_csr_free(&Ar); host_csr_free(&At); host_csr_free(&Qf); QPDO_EPRINT("matrix conversion failed"); goto fail; }
-        QdevCsr a = {Ar.nrows, Ar.ncols, Ar.nnz, Ar.rp, Ar.ci, Ar.val};
-        QdevCsr t = {At.nrows, At.ncols, At.nnz, At.rp, At.ci, At.val};
-        QdevCsr qf = {Qf.nrows, Qf.ncols, Qf.nnz, Qf.rp, Qf.ci, Qf.val};
-        int device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0));
-        int ndev = qdev_device_count();
-        if (ndev <= 0) {
-            host_csr_free(&Ar); host_csr_free(&At); host_csr_free(&Qf);
-            QPDO_EPRINT("no HIP device available (this library has no CPU path)"); goto fail;
-        }
-        device = device % ndev;
-        int rc;
-        QdevDist dd;
+        if (!pick_device(&device)) { host_csr_free(&Ar); host_csr_free(&At); host_csr_free(&Qf); QPDO_EPRINT(NO_DEVICE_MSG); goto fail; }
         if (dist_take(&dd)) {
             host_csr_free(&Ar); host_csr_free(&At); host_csr_free(&Qf);
             QPDO_EPRINT("the RCCL unique id of qpdo_amd_dist_config has already created a communicator: call qpdo_amd_dist_config "
                         "with a fresh id before setting up another row-partitioned workspace"); goto fail;
         }
-        if (dd.world <= 1 && !dd.force) {
-            rc = qdev_create(&work->chol->dev, device, (int32_t)n, (int32_t)m, &a, &t, &qf, work->data->q, work->data->l, work->data->u);
-        } else {
-            /* row partition: rows [m0, m0+mloc) of A, the same columns of A', rows [n0, n0+nloc) of Q */
-            const int64_t rpm = ((int64_t)m + dd.world - 1) / dd.world, rpn = ((int64_t)n + dd.world - 1) / dd.world;
-            int64_t m0 = (int64_t)dd.rank * rpm; if (m0 > (int64_t)m) m0 = (int64_t)m;
-            int64_t m1 = m0 + rpm; if (m1 > (int64_t)m) m1 = (int64_t)m;
-            int64_t n0 = (int64_t)dd.rank * rpn; if (n0 > (int64_t)n) n0 = (int64_t)n;
-            int64_t n1 = n0 + rpn; if (n1 > (int64_t)n) n1 = (int64_t)n;
-            dd.m0 = (int32_t)m0; dd.mloc = (int32_t)(m1 - m0); dd.n0 = (int32_t)n0; dd.nloc = (int32_t)(n1 - n0);
-            int32_t *arp = malloc(((size_t)dd.mloc + 1) * sizeof(int32_t)), *qrp = malloc(((size_t)dd.nloc + 1) * sizeof(int32_t));
-            int32_t *trp = malloc(((size_t)n + 1) * sizeof(int32_t));
-            int64_t tn = 0;
-            for (int64_t j = 0; j < (int64_t)n; j++) for (int32_t k = At.rp[j]; k < At.rp[j + 1]; k++) tn += (At.ci[k] >= m0 && At.ci[k] < m1);
-            int32_t *tci = malloc((size_t)(tn ? tn : 1) * sizeof(int32_t)); double *tval = malloc((size_t)(tn ? tn : 1) * sizeof(double));
-            if (!arp || !qrp || !trp || !tci || !tval) { free(arp); free(qrp); free(trp); free(tci); free(tval); rc = -1; }
-            else {
-                for (int32_t i = 0; i <= dd.mloc; i++) arp[i] = Ar.rp[m0 + i] - Ar.rp[m0];
-                for (int32_t i = 0; i <= dd.nloc; i++) qrp[i] = Qf.rp[n0 + i] - Qf.rp[n0];
-                int64_t pos = 0;
-                for (int64_t j = 0; j < (int64_t)n; j++) {
-                    trp[j] = (int32_t)pos;
-                    for (int32_t k = At.rp[j]; k < At.rp[j + 1]; k++)
-                        if (At.ci[k] >= m0 && At.ci[k] < m1) { tci[pos] = At.ci[k] - (int32_t)m0; tval[pos] = At.val[k]; pos++; }
-                }
-                trp[n] = (int32_t)pos;
-                QdevCsr al = {dd.mloc, (int32_t)n, arp[dd.mloc], arp, Ar.ci + Ar.rp[m0], Ar.val + Ar.rp[m0]};
-                QdevCsr tl = {(int32_t)n, dd.mloc, pos, trp, tci, tval};
-                QdevCsr ql = {dd.nloc, (int32_t)n, qrp[dd.nloc], qrp, Qf.ci + Qf.rp[n0], Qf.val + Qf.rp[n0]};
-                rc = qdev_create_dist(&work->chol->dev, device, (int32_t)n, (int32_t)m, &al, &tl, &qf, &ql, work->data->q, work->data->l, work->data->u, &dd);
-                free(arp); free(qrp); free(trp); free(tci); free(tval);
-            }
-        }
+        const int rc = create_from_host(work, device, &Ar, &At, &Qf, &dd);
         if (prof) { fprintf(stderr, "[setup] device create     %.3f s (upload, slab tables)\n", wall_now() - t0); t0 = wall_now(); }
         host_csr_free_async(&Ar, &At, &Qf);       /* unmapping several GB takes ~0.5 s: off the caller's path */
         if (prof) { fprintf(stderr, "[setup] host free         %.3f s\n", wall_now() - t0); }
-        if (rc) { QPDO_EPRINT("device backend: %s", qdev_last_error()); goto fail; }
-        const char *ls = getenv("QPDO_LINSOLVE");
-        int mode = -1;
-        if (ls && !strcmp(ls, "pcg")) mode = 0; else if (ls && !strcmp(ls, "dense")) mode = 1; else if (ls && !strcmp(ls, "band")) mode = 3;
-        if (qdev_configure(work->chol->dev, mode, env_double("QPDO_PCG_TOL", 0.0), env_int("QPDO_PCG_MAXIT", 0))) { QPDO_EPRINT("device backend: %s", qdev_last_error()); goto fail; }
+        if (rc) goto fail_dev;
     }
-
-    if (settings->scaling) {
-        work->scaling = malloc(sizeof(QPDOScaling));
-        if (!work->scaling) goto fail;
-        work->scaling->D = calloc(n ? n : 1, sizeof(c_float));
-        work->scaling->Dinv = calloc(n ? n : 1, sizeof(c_float));
-        work->scaling->E = calloc(m ? m : 1, sizeof(c_float));
-        work->scaling->Einv = calloc(m ? m : 1, sizeof(c_float));
-        if (!work->scaling->D || !work->scaling->Dinv || !work->scaling->E || !work->scaling->Einv) goto fail;
-        /* the unscaled values stay on the device for qpdo_amd_update_matrices (a matrix it is not given is scaled again from them) */
-        if (qdev_keep_raw_values(work->chol->dev)) goto fail_dev;
-        /* scale_data (scaling.c:24-91): A, Q, q on the device; l, u through the host mirrors */
-        const double ts0 = wall_now();
-        if (qdev_scale_data(work->chol->dev, (int)settings->scaling, 0, work->scaling->D, work->scaling->E, &work->scaling->c)) goto fail_dev;
-        if (env_int("QPDO_SETUP_PROF", 0)) fprintf(stderr, "[setup] device scaling    %.3f s\n", wall_now() - ts0);
-        if (install_scaling(work)) goto fail_dev;
-        if (qdev_download_q(work->chol->dev, work->data->q)) goto fail_dev;
-        for (size_t i = 0; i < m; i++) { work->data->l[i] = work->scaling->E[i] * work->data->l[i]; work->data->u[i] = work->scaling->E[i] * work->data->u[i]; }
-        if (qdev_upload_bounds(work->chol->dev, work->data->l, work->data->u)) goto fail_dev;
-        {   /* || Dinv q || (qpdo.c:163-165) */
-            c_float mx = 0.0;
-            for (size_t i = 0; i < n; i++) { c_float s = c_absval(work->scaling->Dinv[i] * work->data->q[i]); mx = s > mx ? s : mx; }
-            work->norm_q = mx;
-        }
-    } else {
-        work->scaling = QPDO_NULL;
-        if (qdev_set_scaling(work->chol->dev, 0, NULL, NULL, NULL, NULL, 1.0, 1.0)) goto fail_dev;
-        work->norm_q = vec_norm_inf(work->data->q, n);
-    }
+    if (qdev_configure(work->chol->dev, linsolve_mode_env(), env_double("QPDO_PCG_TOL", 0.0), env_int("QPDO_PCG_MAXIT", 0))) goto fail_dev;
+    const int scaled = apply_scaling(work, 1, prof);
+    if (scaled < 0) goto fail_dev;
+    if (scaled) goto fail;
     small_resident_setup(work, settings);
     update_status(work->info, QPDO_UNSOLVED);
     work->info->solve_time = 0.0;
@@ -984,24 +857,7 @@ int qpdo_amd_update_matrices(QPDOWorkspace *work, const cholmod_sparse *Q, const
     /* from here on, as qpdo_setup: the host mirrors, the scaling, the fused resident, the post-setup scalars */
     memcpy(work->data->q, be->q_raw, n * sizeof(c_float));
     if (m) { memcpy(work->data->l, be->l_raw, m * sizeof(c_float)); memcpy(work->data->u, be->u_raw, m * sizeof(c_float)); }
-    int fail = 0;
-    if (work->scaling) {
-        QPDOScaling *sc = work->scaling;
-        fail = qdev_scale_data(be->dev, (int)work->settings->scaling, 0, sc->D, sc->E, &sc->c) || install_scaling(work) ||
-               qdev_download_q(be->dev, work->data->q);
-        if (!fail) {
-            for (size_t i = 0; i < m; i++) { work->data->l[i] = sc->E[i] * work->data->l[i]; work->data->u[i] = sc->E[i] * work->data->u[i]; }
-            fail = qdev_upload_bounds(be->dev, work->data->l, work->data->u);
-        }
-        if (!fail) {
-            c_float mx = 0.0;
-            for (size_t i = 0; i < n; i++) { c_float s = c_absval(sc->Dinv[i] * work->data->q[i]); mx = s > mx ? s : mx; }
-            work->norm_q = mx;
-        }
-    } else {
-        fail = qdev_set_scaling(be->dev, 0, NULL, NULL, NULL, NULL, 1.0, 1.0);
-        work->norm_q = vec_norm_inf(work->data->q, n);
-    }
+    const int fail = apply_scaling(work, 0, 0);
     if (n) { memset(work->x, 0, n * sizeof(c_float)); memset(work->dx, 0, n * sizeof(c_float)); memset(work->solution->x, 0, n * sizeof(c_float)); }
     if (m) { memset(work->y, 0, m * sizeof(c_float)); memset(work->dy, 0, m * sizeof(c_float)); memset(work->solution->y, 0, m * sizeof(c_float)); }
     work->initialized = 0; work->n_mu_changed = 0; work->sigma = work->settings->sigma_init; work->tau = 0.0;
@@ -1173,9 +1029,8 @@ long qpdo_amd_solve_batch(long count, QPDOAmdBatchItem *items, const QPDOSetting
         long bad = 0;
         for (long i = 0; i < count; i++) if (!validate_data(items[i].data)) bad++;
         if (!bad) {
-            int ndev = qdev_device_count();
-            if (ndev > 0) {
-                int device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
+            int device;
+            if (pick_device(&device)) {
                 const double tb0 = wall_now();
                 const int rcb = qdev_small_batch(device, count, items, settings);
                 if (env_int("QPDO_SMALL_PROF", 0) == 2) fprintf(stderr, "[qpdo_small host] qdev_small_batch total   %.3f s\n", wall_now() - tb0);
@@ -1198,9 +1053,8 @@ long qpdo_amd_solve_batch(long count, QPDOAmdBatchItem *items, const QPDOSetting
 
 /* streamed batches: see include/qpdo_amd_ext.h */
 QPDOAmdBatchStream *qpdo_amd_batch_stream_create(int depth) {
-    int ndev = qdev_device_count();
-    if (ndev <= 0) { QPDO_EPRINT("no HIP device available (this library has no CPU path)"); return NULL; }
-    int device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
+    int device;
+    if (!pick_device(&device)) { QPDO_EPRINT(NO_DEVICE_MSG); return NULL; }
     warn_hw_queues_once(depth);
     return (QPDOAmdBatchStream *)qdev_small_stream_create(device, depth);
 }
@@ -1248,9 +1102,8 @@ QPDOAmdFleet *qpdo_amd_fleet_create_ex(long count, const QPDOData *const *data, 
                 fleet_refuse(msg); return NULL;
             }
     }
-    const int ndev = qdev_device_count();
-    if (ndev <= 0) { fleet_refuse("qpdo_amd_fleet_create: no HIP device available (this library has no CPU path)"); return NULL; }
-    const int device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
+    int device;
+    if (!pick_device(&device)) { fleet_refuse("qpdo_amd_fleet_create: " NO_DEVICE_MSG); return NULL; }
     void *f = qdev_small_fleet_create(device, count, (const void *const *)data, settings, flags);
     if (!f) { char msg[320]; snprintf(msg, sizeof(msg), "qpdo_amd_fleet_create: %s", qdev_small_last_error()); fleet_refuse(msg); }
     return (QPDOAmdFleet *)f;

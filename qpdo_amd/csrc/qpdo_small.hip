@@ -21,6 +21,7 @@
 #include <cstring>
 #include <ctime>
 #include <algorithm>
+#include <atomic>
 #include <vector>
 #include <thread>
 #include <mutex>
@@ -29,6 +30,7 @@
 #include "qpdo.h"
 #include "qpdo_amd_ext.h"
 #include "qpdo_dev.h"
+#include "csc_convert.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -1777,70 +1779,10 @@ __global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet(SmallQP *probs, i
 static thread_local char s_err[256] = "";
 #define SHIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { snprintf(s_err, sizeof(s_err), "%s: %s", #call, hipGetErrorString(e__)); rc = -1; goto done; } } while (0)
 
-static inline long long idx_at(const void *a, int itype, long long k) { return itype == 0 ? (long long)((const int *)a)[k] : (long long)((const long long *)a)[k]; }
 // CSC -> the kernel's CSR images (A, A' = the CSC arrays narrowed, the full symmetric Q) straight into caller-provided arrays (the pinned
-// staging buffer of a batch): no per-item vectors, no second copy.  `next` / the temporaries are per-thread scratch that only grows.
-// Row i of the full Q = (lower stored) CSR row i of the stored triangle [columns <= i] followed by the stored column i below the
-// diagonal, (upper stored) the stored column i above the diagonal followed by CSR row i [columns >= i]; same rule as the host driver's
-// sym_to_full_csr (qpdo_api.c).
-// `map` (optional): for entry s of the CSR image its position k in the caller's CSC arrays.
-static void csc_to_csr32_raw(const cholmod_sparse *M, int *rp, int *ci, double *val, std::vector<int> &next, int *map = nullptr) {
-    const long long nr = (long long)M->nrow, nc = (long long)M->ncol, nnz = idx_at(M->p, M->itype, nc);
-    for (long long i = 0; i <= nr; i++) rp[i] = 0;
-    for (long long k = 0; k < nnz; k++) rp[idx_at(M->i, M->itype, k) + 1]++;
-    for (long long i = 0; i < nr; i++) rp[i + 1] += rp[i];
-    if ((long long)next.size() < nr + 1) next.resize((size_t)nr + 1);
-    for (long long i = 0; i < nr; i++) next[(size_t)i] = rp[i];
-    const double *x = (const double *)M->x;
-    for (long long j = 0; j < nc; j++)
-        for (long long k = idx_at(M->p, M->itype, j); k < idx_at(M->p, M->itype, j + 1); k++) { const int s2 = next[(size_t)idx_at(M->i, M->itype, k)]++; ci[s2] = (int)j; val[s2] = x[k]; if (map) map[s2] = (int)k; }
-}
-static void csc_as_csrT32_raw(const cholmod_sparse *M, int *rp, int *ci, double *val) {
-    const long long nc = (long long)M->ncol, nnz = idx_at(M->p, M->itype, nc);
-    for (long long j = 0; j <= nc; j++) rp[j] = (int)idx_at(M->p, M->itype, j);
-    for (long long k = 0; k < nnz; k++) ci[k] = (int)idx_at(M->i, M->itype, k);
-    if (nnz) memcpy(val, M->x, (size_t)nnz * 8);
-}
-static long long sym_full_nnz(const cholmod_sparse *Q) {              // entries of the full symmetric matrix (sym_full32's count)
-    const long long n = (long long)Q->ncol, nnz = idx_at(Q->p, Q->itype, n);
-    const int st = Q->stype;
-    if (st == 0) return nnz;
-    long long c = 0;
-    for (long long j = 0; j < n; j++)
-        for (long long k = idx_at(Q->p, Q->itype, j); k < idx_at(Q->p, Q->itype, j + 1); k++) {
-            const long long i = idx_at(Q->i, Q->itype, k);
-            if (st < 0) c += (i >= j) + (i > j); else c += (i <= j) + (i < j);      // the stored triangle once, its strict part mirrored
-        }
-    return c;
-}
-struct ConvScratch { std::vector<int> next, Rrp, Rci, Rmap; std::vector<double> Rval; };
-// `map` (optional, stype != 0): for entry s of the full matrix the position in the caller's stored values it was taken from
-static void sym_full32_raw(const cholmod_sparse *Q, int *rp, int *ci, double *val, ConvScratch &W, int *map = nullptr) {
-    const int st = Q->stype;
-    if (st == 0) { csc_as_csrT32_raw(Q, rp, ci, val); return; }
-    const long long n = (long long)Q->ncol, nnzs = idx_at(Q->p, Q->itype, n);
-    if ((long long)W.Rrp.size() < n + 1) W.Rrp.resize((size_t)n + 1);
-    if ((long long)W.Rci.size() < nnzs + 1) { W.Rci.resize((size_t)nnzs + 1); W.Rval.resize((size_t)nnzs + 1); }
-    if (map && (long long)W.Rmap.size() < nnzs + 1) W.Rmap.resize((size_t)nnzs + 1);
-    csc_to_csr32_raw(Q, W.Rrp.data(), W.Rci.data(), W.Rval.data(), W.next, map ? W.Rmap.data() : nullptr);
-    const int *Rrp = W.Rrp.data(), *Rci = W.Rci.data(), *Rmap = W.Rmap.data(); const double *Rval = W.Rval.data();
-    const double *x = (const double *)Q->x;
-    auto keep_csr = [&](long long i, long long j) { return st < 0 ? j <= i : j >= i; };
-    auto keep_mir = [&](long long i, long long j) { return st < 0 ? i > j : i < j; };
-    int s2 = 0;
-    for (long long i = 0; i < n; i++) {                                  // (the rule and the order of sym_full32)
-        rp[i] = s2;
-        const long long b0 = idx_at(Q->p, Q->itype, i), e0 = idx_at(Q->p, Q->itype, i + 1);
-        if (st < 0) {
-            for (int k = Rrp[i]; k < Rrp[i + 1]; k++) if (keep_csr(i, Rci[k])) { ci[s2] = Rci[k]; val[s2] = Rval[k]; if (map) map[s2] = Rmap[k]; s2++; }
-            for (long long k = b0; k < e0; k++) { const long long r = idx_at(Q->i, Q->itype, k); if (keep_mir(r, i)) { ci[s2] = (int)r; val[s2] = x[k]; if (map) map[s2] = (int)k; s2++; } }
-        } else {
-            for (long long k = b0; k < e0; k++) { const long long r = idx_at(Q->i, Q->itype, k); if (keep_mir(r, i)) { ci[s2] = (int)r; val[s2] = x[k]; if (map) map[s2] = (int)k; s2++; } }
-            for (int k = Rrp[i]; k < Rrp[i + 1]; k++) if (keep_csr(i, Rci[k])) { ci[s2] = Rci[k]; val[s2] = Rval[k]; if (map) map[s2] = Rmap[k]; s2++; }
-        }
-    }
-    rp[n] = s2;
-}
+// staging buffer of a batch): the conversions of csc_convert.h, on one thread (the callers run inside parallel_items).  No per-item
+// vectors, no second copy; the temporaries are per-thread scratch that only grows.
+struct ItemScratch : ConvScratch { ItemScratch() { conv_scratch_init(this); } ~ItemScratch() { conv_scratch_free(this); } };
 // One in-flight batch owns a SLOT: a stream, a device arena, pinned host staging for the inputs, the outputs and the per-item
 // control structs, and the per-item conversion buffers -- all grow-only and kept between batches (hipMalloc/hipFree of ~0.5 GB
 // cost ~0.1 s per batch; releasing the host buffers another 0.1 s).  qdev_small_batch uses one static slot; a batch STREAM
@@ -1864,12 +1806,14 @@ template <class R> static void lay_scratch(Lay &L, size_t n, size_t m, R &reserv
     L.iv = reserve(3 * m * 4 + 4); L.tpos = reserve(L.nnzA * 4 + 4); L.K = reserve(n * n * 8);
 }
 // CSC -> the three CSR images, and q, l, u, into the host image h of the arena
-static void lay_convert(const QPDOData *d, const Lay &L, char *h, ConvScratch &W, int *mapA = nullptr, int *mapQ = nullptr) {
+// (returns -1 when the scratch cannot grow)
+static int lay_convert(const QPDOData *d, const Lay &L, char *h, ConvScratch &W, int *mapA = nullptr, int *mapQ = nullptr) {
     const size_t n = d->n, m = d->m;
-    csc_to_csr32_raw(d->A, (int *)(h + L.Arp), (int *)(h + L.Aci), (double *)(h + L.Aval), W.next, mapA);
-    csc_as_csrT32_raw(d->A, (int *)(h + L.Trp), (int *)(h + L.Tci), (double *)(h + L.Tval));
-    sym_full32_raw(d->Q, (int *)(h + L.Qrp), (int *)(h + L.Qci), (double *)(h + L.Qval), W, mapQ);
+    if (csc_to_csr(d->A, (int *)(h + L.Arp), (int *)(h + L.Aci), (double *)(h + L.Aval), mapA, 1, &W)) return -1;
+    csc_as_csr_of_transpose(d->A, (int *)(h + L.Trp), (int *)(h + L.Tci), (double *)(h + L.Tval), 1);
+    if (sym_to_full_csr(d->Q, (int *)(h + L.Qrp), (int *)(h + L.Qci), (double *)(h + L.Qval), mapQ, 1, &W)) return -1;
     memcpy(h + L.q, d->q, n * 8); if (m) { memcpy(h + L.l, d->l, m * 8); memcpy(h + L.u, d->u, m * 8); }
+    return 0;
 }
 // the item's descriptor over the device arena (x0 / y0, prof, res and batch_vec_off are the caller's)
 static void lay_describe(SmallQP &p, const QPDOData *d, const Lay &L, char *dbase) {
@@ -2016,6 +1960,7 @@ static volatile double s_last_kernel_s = 0.0;   // (a statistic: written by whic
 // pack the batch into the slot's staging buffer, upload, launch, enqueue the downloads: returns without waiting for the GPU
 static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *items, const QPDOSettings *settings, bool one_at_a_time) {
     int rc = 0;
+    std::atomic<int> conv_failed{0};
     const bool tprof = getenv("QPDO_SMALL_PROF") && !strcmp(getenv("QPDO_SMALL_PROF"), "2");
     auto now = []() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
     double tp0 = now();
@@ -2073,9 +2018,9 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
                 const size_t reg_end = (i + 1 < count) ? lay[(size_t)i + 1].Arp : upload_bytes;     // this item's input region, padding included
                 // conversions straight into the staging buffer; the slack behind every array (4 / 8 bytes + alignment) is zeroed like the
                 // memset of the whole region used to do it
-                static thread_local ConvScratch W;
+                static thread_local ItemScratch W;
                 auto tail0 = [&](size_t off, size_t bytes, size_t next_off) { if (next_off > off + bytes) memset(h + off + bytes, 0, next_off - off - bytes); };
-                lay_convert(d, L, h, W);
+                if (lay_convert(d, L, h, W)) { conv_failed = 1; return; }
                 tail0(L.Arp, (m + 1) * 4, L.Aci); tail0(L.Aci, L.nnzA * 4, L.Aval); tail0(L.Aval, L.nnzA * 8, L.Trp);
                 tail0(L.Trp, (n + 1) * 4, L.Tci); tail0(L.Tci, L.nnzA * 4, L.Tval); tail0(L.Tval, L.nnzA * 8, L.Qrp);
                 tail0(L.Qrp, (n + 1) * 4, L.Qci); tail0(L.Qci, L.nnzQ * 4, L.Qval); tail0(L.Qval, L.nnzQ * 8, L.q);
@@ -2089,6 +2034,7 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
                 if (items[i].x0) memcpy(h + L.x0, items[i].x0, n * 8);
                 if (items[i].y0 && m) memcpy(h + L.y0, items[i].y0, m * 8);
             });
+            if (conv_failed) { snprintf(s_err, sizeof(s_err), "batch: host memory for the matrix conversions"); rc = -1; goto done; }
             const size_t b0 = lay[(size_t)i0].Arp, b1 = (i1 < count) ? lay[(size_t)i1].Arp : upload_bytes;
             if (b1 > b0) SHIP(hipMemcpyAsync(dbase + b0, harena + b0, b1 - b0, hipMemcpyHostToDevice, S.stream));
         }
