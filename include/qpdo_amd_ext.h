@@ -442,6 +442,62 @@ int  qpdo_amd_fleet_factor_layout(const QPDOAmdFleet *f);
 /* the infeasibility certificates of `item` from the last solve: prim_inf_cert (m values, meaningful at status -3), dual_inf_cert (n, at -4);
  * either may be NULL */
 int  qpdo_amd_fleet_get_certificates(const QPDOAmdFleet *f, long item, c_float *prim_inf_cert, c_float *dual_inf_cert);
+/* ---- DEVICE-RESIDENT inputs and outputs on the CALLER'S STREAM (batched simulators, learned-model MPC, sampling planners: q, l, u are
+ * computed on the GPU and x is consumed there) ------------------------------------------------------------------------------------------
+ * The calls above take host pointers and return when the device is done.  The *_dev calls below take DEVICE arrays, enqueue on the stream
+ * the caller names (`void *stream`: a hipStream_t; NULL is the null stream) and return at once: no stream synchronisation, no copy to or
+ * from the host, no spinning on pinned memory.  Per item they are the host calls bit for bit: an item updated, warm-started or solved from
+ * device memory is the item the host call with the same values leaves.  The kernels that do the work are the host calls' own; two small
+ * ones (one workgroup per item) move the vectors between the caller's arrays and the fleet's staging / outputs.
+ * PACKED LAYOUT  The n-vectors of all items live back to back in ONE array of N = sum n_i doubles, item i at noff[i]; the m-vectors in
+ *          one array of M = sum m_i doubles, item i at moff[i] (a uniform fleet: (count, n) and (count, m) row-major tensors).
+ *          qpdo_amd_fleet_packed_layout fills count + 1 entries each, the last one the total, as pure host arithmetic (no device needed);
+ *          qpdo_amd_fleet_get_packed_layout does the same for an existing fleet.  n_len / m_len of every call must equal N / M.
+ * Arrays   every array is a device (or managed) pointer on the fleet's device.  NULL: not passed (update, warm start) / not wanted (solve).
+ * item_mask  optional, `count` int32 on the device.  update: bit 0 / 1 / 2 = the item takes q / l / u from the arrays passed, a clear bit
+ *          leaves that vector unchanged.  warm start: bit 0 / 1 = x0 / y0 are taken, a clear bit starts that vector from zero (a NULL
+ *          entry of the host call).  NULL mask: every item takes every array passed.
+ * update_dev       no q, l and u at all: returns 0 and launches nothing.  l <= u CANNOT be checked on the host here -- the data is on the
+ *          device -- and so, UNLIKE THE ALL-OR-NOTHING HOST CALL, the check is made on the device PER ITEM: an item that takes both l
+ *          and u with l > u somewhere is not touched at all by that call, its q included; it is counted, and the smallest such item
+ *          index since the last qpdo_amd_fleet_sync is kept; all other items proceed.
+ * warm_start_dev   neither x0 nor y0: every item starts from zero, as qpdo_amd_fleet_warm_start(f, NULL, NULL).
+ * warm_start_last_dev  qpdo_amd_fleet_warm_start_last on the caller's stream.
+ * solve_dev        ONE solve launch, then the results into the arrays wanted: x (N), y (M) -- NaN for items whose status is -3 or -4, as
+ *          qpdo_amd_fleet_solve returns them --; status, count x 3 int64: status_val, iterations, oterations; norms, count x 5 doubles:
+ *          res_prim_norm, res_dual_norm, res_prim_in_norm, res_dual_in_norm, objective; prim_inf_cert (M) / dual_inf_cert (N): NaN except
+ *          the item's certificate at status -3 / -4.  With no array wanted the solve still runs (fetch_last delivers it).
+ * Checks   all on the host, before any launch; a refused call returns nonzero with qpdo_amd_last_error() set and has launched nothing:
+ *          NULL fleet; n_len != N or m_len != M; a passed pointer that hipPointerGetAttributes does not report as device or managed
+ *          memory of the fleet's device (the message names the argument).  The extent of an array cannot be checked: it is the caller's.
+ * ORDER    One event orders all streams a fleet is driven on, its own included: EVERY fleet call, host or device, first makes its stream
+ *          wait for the event the previous fleet call recorded and records it again behind its last operation.  Host and device calls
+ *          may therefore be mixed freely, and the caller may change streams between calls.  What the caller must order itself is its own
+ *          arrays: they are read / written on the stream passed, so produce inputs and consume outputs on that stream (or behind an event
+ *          of it), and keep them alive and unchanged until the call's work is done.  Still one thread at a time per fleet.  hipGraph
+ *          capture of these calls is not supported.
+ * fetch_last  (HOST pointers, as qpdo_amd_fleet_solve) waits for the event, downloads the descriptors and outputs of the last solve,
+ *          whichever kind of call launched it, and delivers exactly what qpdo_amd_fleet_solve would have delivered, launching nothing.
+ *          After a solve_dev, qpdo_amd_fleet_get_certificates is refused ("no solve yet") until a fetch_last has made the host image current.
+ * sync     waits for that event, i.e. for everything the fleet was asked to do; fills the counters (out may be NULL), refreshes
+ *          last_kernel_seconds of QPDOAmdFleetStats from the last solve_dev, and resets the refusal record.
+ * Stats    solve_launches and solves grow by 1 per solve_dev; vector_bytes_uploaded_last_call is 0 after update_dev / warm_start_dev. */
+typedef struct {
+    long update_calls, warm_start_calls, solve_calls;   /* device calls that launched, since create (warm_start_last_dev counts as a warm start) */
+    long refused_items;                     /* items refused by update_dev calls (l > u) since the last sync ... */
+    long first_refused_item;                /* ... and the smallest such item index; -1: none */
+} QPDOAmdFleetDevStats;
+/* the HIP device ordinal the fleet lives on (every array of a device call must be memory of this device); -1: NULL fleet */
+int  qpdo_amd_fleet_device(const QPDOAmdFleet *f);
+int  qpdo_amd_fleet_packed_layout(long count, const QPDOData *const *data, long *noff, long *moff);
+int  qpdo_amd_fleet_get_packed_layout(const QPDOAmdFleet *f, long *noff, long *moff);
+int  qpdo_amd_fleet_update_dev(QPDOAmdFleet *f, const double *q, const double *l, const double *u, const int *item_mask, long n_len, long m_len, void *stream);
+int  qpdo_amd_fleet_warm_start_dev(QPDOAmdFleet *f, const double *x0, const double *y0, const int *item_mask, long n_len, long m_len, void *stream);
+int  qpdo_amd_fleet_warm_start_last_dev(QPDOAmdFleet *f, void *stream);
+int  qpdo_amd_fleet_solve_dev(QPDOAmdFleet *f, double *x, double *y, long *status, double *norms, double *prim_inf_cert, double *dual_inf_cert, long n_len, long m_len,
+                              void *stream);
+int  qpdo_amd_fleet_fetch_last(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info);
+int  qpdo_amd_fleet_sync(QPDOAmdFleet *f, QPDOAmdFleetDevStats *out);
 void qpdo_amd_fleet_destroy(QPDOAmdFleet *f);
 
 #ifdef __cplusplus

@@ -122,6 +122,70 @@ __global__ __launch_bounds__(SM_THREADS) void k_small_fleet_update(SmallQP *prob
     if (threadIdx.x == 0) { R->r_c = c; R->r_cinv = cinv; if (prox) R->sigma_end = st.sigma_init; }
 }
 
+// ---- device-resident inputs and outputs (qpdo_amd_fleet_*_dev): the caller's PACKED arrays -- the n-vectors of all items back to back, item
+// i at offs[i], the m-vectors at offs[count + 1 + i]; offs[count] = N and offs[2 count + 1] = M are the totals -- on one side, the staging and
+// the call table that the kernels above and k_small_fleet op 1 already read on the other.  One workgroup per item, 8-byte accesses that
+// are contiguous over the lanes, the item's offsets in scalar registers.
+#define FLEET_IO_THREADS 256
+#define FLEET_REC_NONE 2147483647                   // rec[1] while no item was refused
+// kind 0, an update: a0 = q (mask bit 0), a1 = l (bit 1), a2 = u (bit 2).  kind 1, a warm start: a0 = x0 (bit 0), a1 = y0 (bit 1), a2 = NULL.
+// A vector of the item is TAKEN when its array is passed and its mask bit is set (mask NULL: all set): it is copied to the fixed place
+// stage[offs n | N + offs m | N + M + offs m] and the item's table entry names that place; the others get -1, which the consumers read as
+// "unchanged" (update) or "from zero" (warm start).  An update item with l and u both taken and l > u somewhere is REFUSED: the table
+// entry says -1, -1, -1 -- q included, the item is not touched --, rec[0] counts it and rec[1] keeps the smallest such item.  The test
+// completes (a block-wide OR) before the table is written; what a refused item left in the staging is never read.
+__global__ __launch_bounds__(FLEET_IO_THREADS) void k_small_fleet_gather(int count, const int *offs, int kind, const double *a0, const double *a1, const double *a2,
+                                                                         const int *mask, int *tab, double *stage, int *rec) {
+    if ((int)blockIdx.x >= count) return;
+    const int b = blockIdx.x;
+    const int no = __builtin_amdgcn_readfirstlane(offs[b]), n = __builtin_amdgcn_readfirstlane(offs[b + 1]) - no;
+    const int mo = __builtin_amdgcn_readfirstlane(offs[count + 1 + b]), m = __builtin_amdgcn_readfirstlane(offs[count + 2 + b]) - mo;
+    const int N = __builtin_amdgcn_readfirstlane(offs[count]), M = __builtin_amdgcn_readfirstlane(offs[2 * count + 1]);
+    const int mk = mask ? __builtin_amdgcn_readfirstlane(mask[b]) : 7;
+    const int t0 = a0 && (mk & 1), t1 = a1 && (mk & 2), t2 = a2 && (mk & 4);
+    const int s0 = no, s1 = N + mo, s2 = N + M + mo;
+    if (t0) { const double *src = a0 + no; double *dst = stage + s0; FOR_T(j, n) dst[j] = src[j]; }
+    int bad = 0;
+    if (t1 && t2) {
+        const double *ls = a1 + mo, *us = a2 + mo; double *ld = stage + s1, *ud = stage + s2;
+        FOR_T(i, m) { const double lv = ls[i], uv = us[i]; ld[i] = lv; ud[i] = uv; bad |= lv > uv; }
+    } else {
+        if (t1) { const double *src = a1 + mo; double *dst = stage + s1; FOR_T(i, m) dst[i] = src[i]; }
+        if (t2) { const double *src = a2 + mo; double *dst = stage + s2; FOR_T(i, m) dst[i] = src[i]; }
+    }
+    bad = kind == 0 ? __syncthreads_or(bad) : 0;
+    if (threadIdx.x == 0) {
+        int *t = tab + 4 * b;
+        t[0] = (t0 && !bad) ? s0 : -1; t[1] = (t1 && !bad) ? s1 : -1; t[2] = (t2 && !bad) ? s2 : -1; t[3] = 0;
+        if (bad) { atomicAdd(rec, 1); atomicMin(rec + 1, b); }
+    }
+}
+// After k_small_fleet op 0: what qpdo_amd_fleet_solve delivers for item i, into the caller's packed arrays (a NULL array is not wanted).  x, y:
+// NaN at status -3 / -4; prim_inf_cert (m): the item's dy at -3, dual_inf_cert (n): its dx at -4, NaN otherwise (the rule of the reference's
+// mex gateway); status: status_val, iterations, oterations; norms: res_prim, res_dual, res_prim_in, res_dual_in, objective.
+__global__ __launch_bounds__(FLEET_IO_THREADS) void k_small_fleet_scatter(const SmallQP *probs, int count, const int *offs, double *x, double *y, long *status,
+                                                                          double *norms, double *prim_inf_cert, double *dual_inf_cert) {
+    if ((int)blockIdx.x >= count) return;
+    const int b = blockIdx.x;
+    const SmallQP &Pg = probs[b];
+    const int no = __builtin_amdgcn_readfirstlane(offs[b]), n = __builtin_amdgcn_readfirstlane(offs[b + 1]) - no;
+    const int mo = __builtin_amdgcn_readfirstlane(offs[count + 1 + b]), m = __builtin_amdgcn_readfirstlane(offs[count + 2 + b]) - mo;
+    const int stv = __builtin_amdgcn_readfirstlane((int)Pg.info.status_val);
+    const int pinf = stv == QPDO_PRIMAL_INFEASIBLE, dinf = stv == QPDO_DUAL_INFEASIBLE, infeasible = pinf || dinf;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);      // the bits of the host's NAN
+    if (x) { const double *src = uni_ptr(Pg.sol_x); double *dst = x + no; FOR_T(j, n) dst[j] = infeasible ? nan : src[j]; }
+    if (y) { const double *src = uni_ptr(Pg.sol_y); double *dst = y + mo; FOR_T(i, m) dst[i] = infeasible ? nan : src[i]; }
+    if (prim_inf_cert) { const double *src = uni_ptr(Pg.cert_dy); double *dst = prim_inf_cert + mo; FOR_T(i, m) dst[i] = pinf ? src[i] : nan; }
+    if (dual_inf_cert) { const double *src = uni_ptr(Pg.cert_dx); double *dst = dual_inf_cert + no; FOR_T(j, n) dst[j] = dinf ? src[j] : nan; }
+    if (threadIdx.x == 0) {
+        if (status) { long *s = status + 3 * (size_t)b; s[0] = Pg.info.status_val; s[1] = Pg.info.iterations; s[2] = Pg.info.oterations; }
+        if (norms) {
+            double *v = norms + 5 * (size_t)b;
+            v[0] = Pg.info.res_prim_norm; v[1] = Pg.info.res_dual_norm; v[2] = Pg.info.res_prim_in_norm; v[3] = Pg.info.res_dual_in_norm; v[4] = Pg.info.objective;
+        }
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 struct FleetItem { int n, m; size_t o_q, o_l, o_u, o_solx, o_soly, o_dx, o_dy, out_off; };
 // MATRIX_UPDATES: the create-time CSC pattern of an item's A and stored Q (host copies: every update_matrices call is compared against them in full)
@@ -145,7 +209,18 @@ struct SmallFleet {
     char *dmstage = nullptr, *hmstage = nullptr;    // a matrix call's [table: 2 ints per item][values], device and pinned
     size_t mstage_doubles = 0;
     long m_calls = 0, m_items_last = 0, m_bytes_last = 0, m_extra_bytes = 0; double m_kernel_s = 0.0;
+    // device-resident inputs and outputs (the *_dev calls; DESIGN.md 3.6)
+    hipEvent_t ev_chain = nullptr;                  // recorded at the end of every fleet call on the stream it used; the next call's stream waits for it
+    int *doffs = nullptr, *drec = nullptr;          // the packed layout [noff: count + 1][moff: count + 1], then the refusal record {items, smallest item}
+    int *hrec = nullptr;                            // pinned: the record as qdev_small_fleet_sync reads it
+    std::vector<long> noff, moff;
+    long d_updates = 0, d_warm_starts = 0, d_solves = 0;
+    bool timing_pending = false;                    // ev0 / ev1 bracket a device solve whose duration has not been read yet
 };
+// Ordering between the streams the fleet is driven on, its own included: ONE event.  Every call makes its stream wait for what the previous
+// call recorded and records again behind its last operation, so host and device calls mix freely and the caller may change streams.
+static hipError_t fleet_enter(SmallFleet *F, hipStream_t s) { return hipStreamWaitEvent(s, F->ev_chain, 0); }
+static hipError_t fleet_leave(SmallFleet *F, hipStream_t s) { return hipEventRecord(F->ev_chain, s); }
 static void fleet_free(SmallFleet *F) {
     if (!F) return;
     (void)hipSetDevice(F->device);
@@ -154,6 +229,9 @@ static void fleet_free(SmallFleet *F) {
     if (F->dprobs) (void)hipFree(F->dprobs);
     if (F->dres) (void)hipFree(F->dres);
     if (F->dstage) (void)hipFree(F->dstage);
+    if (F->doffs) (void)hipFree(F->doffs);
+    if (F->hrec) (void)hipHostFree(F->hrec);
+    if (F->ev_chain) (void)hipEventDestroy(F->ev_chain);
     if (F->dmstage) (void)hipFree(F->dmstage);
     if (F->hmstage) (void)hipHostFree(F->hmstage);
     if (F->hstage) (void)hipHostFree(F->hstage);
@@ -186,6 +264,7 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     std::vector<SmallQP> hp((size_t)count);
     std::vector<SmallRes> hr((size_t)count);
     std::vector<size_t> o_rec((size_t)count);
+    std::vector<int> hoffs(2 * ((size_t)count + 1) + 2);        // the packed layout and the empty refusal record, as uploaded
     char *h = nullptr;
     size_t total = 0, nmax = 1, mmax = 0, stage = 0;
     auto reserve = [&](size_t bytes) { size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; };
@@ -198,6 +277,8 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
         if (n > nmax) nmax = n;
         if (m > mmax) mmax = m;
         stage += n + 2 * m;                          // the largest call: q, l and u of every item
+        F->noff.push_back(F->noff.empty() ? 0 : F->noff.back() + (long)data[i - 1]->n);
+        F->moff.push_back(F->moff.empty() ? 0 : F->moff.back() + (long)data[i - 1]->m);
         if (mu) {                                    // the maps ride in create's upload
             MatLay &X = ml[(size_t)i];
             X.mapA = reserve_extra(L.nnzA * 4 + 4);
@@ -209,6 +290,9 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     if (mstage >= 2147483647ULL) { snprintf(s_err, sizeof(s_err), "fleet: %zu matrix entries per call exceed the 2^31 the call table can address; split the fleet", mstage); delete F; return nullptr; }
     // (a call's table holds 32-bit offsets, in doubles, into the staging of the whole fleet)
     if (stage >= 2147483647ULL) { snprintf(s_err, sizeof(s_err), "fleet: %zu vector elements per call exceed the 2^31 the call table can address; split the fleet", stage); delete F; return nullptr; }
+    F->noff.push_back(F->noff.back() + (long)data[count - 1]->n); F->moff.push_back(F->moff.back() + (long)data[count - 1]->m);
+    for (long i = 0; i <= count; i++) { hoffs[(size_t)i] = (int)F->noff[(size_t)i]; hoffs[(size_t)(count + 1 + i)] = (int)F->moff[(size_t)i]; }    // (N + 2 M = stage < 2^31)
+    hoffs[2 * ((size_t)count + 1)] = 0; hoffs[2 * ((size_t)count + 1) + 1] = FLEET_REC_NONE;
     const size_t upload_bytes = total;
     for (long i = 0; i < count; i++) {
         const QPDOData *d = data[i]; Lay &L = lay[(size_t)i];
@@ -229,6 +313,10 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     SHIP(hipSetDevice(device));
     SHIP(hipStreamCreateWithFlags(&F->stream, hipStreamNonBlocking));
     SHIP(hipEventCreate(&F->ev0)); SHIP(hipEventCreate(&F->ev1));
+    SHIP(hipEventCreateWithFlags(&F->ev_chain, hipEventDisableTiming));
+    SHIP(hipMalloc((void **)&F->doffs, hoffs.size() * sizeof(int)));
+    F->drec = F->doffs + 2 * ((size_t)count + 1);
+    SHIP(hipHostMalloc((void **)&F->hrec, 2 * sizeof(int), hipHostMallocDefault));
     SHIP(hipMalloc((void **)&F->arena, total));
     SHIP(hipMalloc((void **)&F->dprobs, (size_t)count * sizeof(SmallQP)));
     SHIP(hipMalloc((void **)&F->dres, (size_t)count * sizeof(SmallRes)));
@@ -301,9 +389,11 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     }
     SHIP(hipMemcpyAsync(F->dprobs, hp.data(), (size_t)count * sizeof(SmallQP), hipMemcpyHostToDevice, F->stream));
     SHIP(hipMemcpyAsync(F->dres, hr.data(), (size_t)count * sizeof(SmallRes), hipMemcpyHostToDevice, F->stream));
+    SHIP(hipMemcpyAsync(F->doffs, hoffs.data(), hoffs.size() * sizeof(int), hipMemcpyHostToDevice, F->stream));
     SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
     hipLaunchKernelGGL(k_small_fleet_setup, dim3((unsigned)count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)count, F->st);
     SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, F->stream));
     SHIP(hipStreamSynchronize(F->stream));           // (the pageable staging images above are read until here)
 done:
     free(h);
@@ -326,10 +416,12 @@ int qdev_small_fleet_update(void *h_, const double *const *q, const double *cons
         if (u && u[i]) { t[2] = (int)off; if (m) memcpy(hs + off, u[i], m * 8); off += m; }
     }
     SHIP(hipSetDevice(F->device));
+    SHIP(fleet_enter(F, F->stream));
     if (off) SHIP(hipMemcpyAsync(F->dstage, hs, off * 8, hipMemcpyHostToDevice, F->stream));
     SHIP(hipMemcpyAsync(F->dtab, ht, (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES, hipMemcpyHostToDevice, F->stream));
     hipLaunchKernelGGL(k_small_fleet_update, dim3((unsigned)F->count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)F->count, F->st, (const int *)F->dtab, (const double *)F->dstage);
     SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, F->stream));
     SHIP(hipStreamSynchronize(F->stream));           // (the pinned staging is free for the next call)
     F->vector_bytes_last = (long)(off * 8 + (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES);
 done:
@@ -377,14 +469,17 @@ int qdev_small_fleet_update_matrices(void *h_, const void *const *Q_, const void
         items += (t[0] >= 0 || t[1] >= 0);
     }
     SHIP(hipSetDevice(F->device));
+    SHIP(fleet_enter(F, F->stream));
     SHIP(hipMemcpyAsync(F->dmstage, F->hmstage, tab_bytes + off * 8, hipMemcpyHostToDevice, F->stream));
     SHIP(hipEventRecord(F->ev0, F->stream));
     hipLaunchKernelGGL(k_small_fleet_matrices, dim3((unsigned)F->count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)F->count, F->st,
                        (const int *)F->dmstage, (const double *)(F->dmstage + tab_bytes));
     SHIP(hipGetLastError());
     SHIP(hipEventRecord(F->ev1, F->stream));
+    SHIP(fleet_leave(F, F->stream));
     SHIP(hipStreamSynchronize(F->stream));           // (the pinned staging is free for the next call)
     { float ms = 0.f; if (hipEventElapsedTime(&ms, F->ev0, F->ev1) == hipSuccess) F->m_kernel_s = (double)ms * 1e-3; }
+    F->timing_pending = false;                       // (ev0 / ev1 no longer bracket a solve)
     F->m_calls++; F->m_items_last = items; F->m_bytes_last = (long)(tab_bytes + off * 8);
 done:
     return rc;
@@ -401,6 +496,7 @@ int qdev_small_fleet_warm_start(void *h_, const double *const *x0, const double 
     double *hs = (double *)F->hstage; int *ht = (int *)(hs + F->stage_doubles);
     size_t off = 0;
     SHIP(hipSetDevice(F->device));
+    SHIP(fleet_enter(F, F->stream));
     if (!last) {
         for (long i = 0; i < F->count; i++) {
             const size_t n = (size_t)F->it[(size_t)i].n, m = (size_t)F->it[(size_t)i].m;
@@ -415,28 +511,22 @@ int qdev_small_fleet_warm_start(void *h_, const double *const *x0, const double 
     hipLaunchKernelGGL(k_small_fleet, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, F->stream, F->dprobs, (int)F->count, F->st, F->kflags, last ? 2 : 1,
                        (const int *)F->dtab, (const double *)F->dstage);
     SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, F->stream));
     SHIP(hipStreamSynchronize(F->stream));
     F->vector_bytes_last = last ? 0 : (long)(off * 8 + (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES);
 done:
     return rc;
 }
-// ONE launch for the whole fleet; x, y: arrays of `count` pointers or NULL (entries may be NULL), info: `count` QPDOInfo
-int qdev_small_fleet_solve(void *h_, double *const *x, double *const *y, void *info_) {
+// The last solve's descriptors and outputs to the host on the fleet's stream (the caller has made it wait for the chain event), then what a
+// solve delivers: info[i], x and y with NaN for the infeasible statuses.  The end of a host solve, and the whole of fetch_last.
+static int fleet_fetch(SmallFleet *F, double *const *x, double *const *y, QPDOInfo *info) {
     int rc = 0;
-    SmallFleet *F = (SmallFleet *)h_;
-    QPDOInfo *info = (QPDOInfo *)info_;
-    SHIP(hipSetDevice(F->device));
-    SHIP(hipEventRecord(F->ev0, F->stream));
-    hipLaunchKernelGGL(k_small_fleet, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, F->stream, F->dprobs, (int)F->count, F->st, F->kflags, 0,
-                       (const int *)F->dtab, (const double *)F->dstage);
-    SHIP(hipGetLastError());
-    SHIP(hipEventRecord(F->ev1, F->stream));
-    F->solve_launches++;
     SHIP(hipMemcpyAsync(F->hp, F->dprobs, (size_t)F->count * sizeof(SmallQP), hipMemcpyDeviceToHost, F->stream));
     if (F->out_bytes) SHIP(hipMemcpyAsync(F->hout, F->arena + F->out_off, F->out_bytes, hipMemcpyDeviceToHost, F->stream));
+    SHIP(fleet_leave(F, F->stream));
     SHIP(hipStreamSynchronize(F->stream));
-    { float ms = 0.f; if (hipEventElapsedTime(&ms, F->ev0, F->ev1) == hipSuccess) F->kernel_s = (double)ms * 1e-3; }
-    F->solves++; F->solved = true;
+    if (F->timing_pending) { float ms = 0.f; if (hipEventElapsedTime(&ms, F->ev0, F->ev1) == hipSuccess) F->kernel_s = (double)ms * 1e-3; }
+    F->timing_pending = false; F->solved = true;
     parallel_items(F->count, [&](long i) {
         const FleetItem &I = F->it[(size_t)i];
         if (info) info[i] = F->hp[(size_t)i].info;
@@ -448,6 +538,134 @@ int qdev_small_fleet_solve(void *h_, double *const *x, double *const *y, void *i
     });
 done:
     return rc;
+}
+// ONE launch for the whole fleet; x, y: arrays of `count` pointers or NULL (entries may be NULL), info: `count` QPDOInfo
+int qdev_small_fleet_solve(void *h_, double *const *x, double *const *y, void *info_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    SHIP(hipSetDevice(F->device));
+    SHIP(fleet_enter(F, F->stream));
+    SHIP(hipEventRecord(F->ev0, F->stream));
+    hipLaunchKernelGGL(k_small_fleet, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, F->stream, F->dprobs, (int)F->count, F->st, F->kflags, 0,
+                       (const int *)F->dtab, (const double *)F->dstage);
+    SHIP(hipGetLastError());
+    SHIP(hipEventRecord(F->ev1, F->stream));
+    F->solve_launches++; F->solves++; F->timing_pending = true;
+    rc = fleet_fetch(F, x, y, (QPDOInfo *)info_);
+done:
+    return rc;
+}
+
+// ---- the calls on device arrays and the caller's stream (include/qpdo_amd_ext.h): checks on the host, then launches, no wait ---------------
+static int fleet_dev_lens(const SmallFleet *F, long n_len, long m_len) {
+    const long N = F->noff.back(), M = F->moff.back();
+    if (n_len != N) { snprintf(s_err, sizeof(s_err), "n_len is %ld, the fleet's packed n-vectors have %ld elements", n_len, N); return -1; }
+    if (m_len != M) { snprintf(s_err, sizeof(s_err), "m_len is %ld, the fleet's packed m-vectors have %ld elements", m_len, M); return -1; }
+    return 0;
+}
+// a passed array must be device (or managed) memory of the fleet's device by the runtime's own record: no kernel sees any other pointer
+static int fleet_dev_ptr(const SmallFleet *F, const void *p, const char *name) {
+    if (!p) return 0;
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) (void)hipGetLastError();    // (a pointer the runtime does not know: the error is the answer, not a fault of this call)
+    if (e == hipSuccess && (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) && a.device == F->device) return 0;
+    snprintf(s_err, sizeof(s_err), "%s is not device memory on the fleet's device %d", name, F->device);
+    return -1;
+}
+static void fleet_gather(SmallFleet *F, hipStream_t s, int kind, const double *a0, const double *a1, const double *a2, const int *mask) {
+    hipLaunchKernelGGL(k_small_fleet_gather, dim3((unsigned)F->count), dim3(FLEET_IO_THREADS), 0, s, (int)F->count, (const int *)F->doffs, kind, a0, a1, a2, mask,
+                       F->dtab, F->dstage, F->drec);
+}
+int qdev_small_fleet_update_dev(void *h_, const double *q, const double *l, const double *u, const int *item_mask, long n_len, long m_len, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    hipStream_t s = (hipStream_t)stream_;
+    SHIP(hipSetDevice(F->device));
+    if (fleet_dev_lens(F, n_len, m_len) || fleet_dev_ptr(F, q, "q") || fleet_dev_ptr(F, l, "l") || fleet_dev_ptr(F, u, "u") || fleet_dev_ptr(F, item_mask, "item_mask")) return -1;
+    if (!q && !l && !u) return 0;
+    SHIP(fleet_enter(F, s));
+    fleet_gather(F, s, 0, q, l, u, item_mask);
+    SHIP(hipGetLastError());
+    hipLaunchKernelGGL(k_small_fleet_update, dim3((unsigned)F->count), dim3(SM_THREADS), 0, s, F->dprobs, (int)F->count, F->st, (const int *)F->dtab, (const double *)F->dstage);
+    SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, s));
+    F->vector_bytes_last = 0; F->d_updates++;
+done:
+    return rc;
+}
+// last = 1: warm_start_last on the caller's stream (nothing to gather)
+int qdev_small_fleet_warm_start_dev(void *h_, const double *x0, const double *y0, const int *item_mask, long n_len, long m_len, int last, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    hipStream_t s = (hipStream_t)stream_;
+    SHIP(hipSetDevice(F->device));
+    if (!last && (fleet_dev_lens(F, n_len, m_len) || fleet_dev_ptr(F, x0, "x0") || fleet_dev_ptr(F, y0, "y0") || fleet_dev_ptr(F, item_mask, "item_mask"))) return -1;
+    SHIP(fleet_enter(F, s));
+    if (!last) { fleet_gather(F, s, 1, x0, y0, nullptr, item_mask); SHIP(hipGetLastError()); }
+    hipLaunchKernelGGL(k_small_fleet, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, s, F->dprobs, (int)F->count, F->st, F->kflags, last ? 2 : 1,
+                       (const int *)F->dtab, (const double *)F->dstage);
+    SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, s));
+    F->vector_bytes_last = 0; F->d_warm_starts++;
+done:
+    return rc;
+}
+int qdev_small_fleet_solve_dev(void *h_, double *x, double *y, long *status, double *norms, double *prim_inf_cert, double *dual_inf_cert, long n_len, long m_len, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    hipStream_t s = (hipStream_t)stream_;
+    SHIP(hipSetDevice(F->device));
+    if (fleet_dev_lens(F, n_len, m_len) || fleet_dev_ptr(F, x, "x") || fleet_dev_ptr(F, y, "y") || fleet_dev_ptr(F, status, "status") || fleet_dev_ptr(F, norms, "norms") ||
+        fleet_dev_ptr(F, prim_inf_cert, "prim_inf_cert") || fleet_dev_ptr(F, dual_inf_cert, "dual_inf_cert")) return -1;
+    SHIP(fleet_enter(F, s));
+    SHIP(hipEventRecord(F->ev0, s));
+    hipLaunchKernelGGL(k_small_fleet, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, s, F->dprobs, (int)F->count, F->st, F->kflags, 0,
+                       (const int *)F->dtab, (const double *)F->dstage);
+    SHIP(hipGetLastError());
+    SHIP(hipEventRecord(F->ev1, s));
+    F->solve_launches++; F->solves++; F->d_solves++;
+    F->timing_pending = true; F->solved = false;     // (the host image is the previous solve's until fetch_last)
+    if (x || y || status || norms || prim_inf_cert || dual_inf_cert) {
+        hipLaunchKernelGGL(k_small_fleet_scatter, dim3((unsigned)F->count), dim3(FLEET_IO_THREADS), 0, s, (const SmallQP *)F->dprobs, (int)F->count, (const int *)F->doffs,
+                           x, y, status, norms, prim_inf_cert, dual_inf_cert);
+        SHIP(hipGetLastError());
+    }
+    SHIP(fleet_leave(F, s));
+done:
+    return rc;
+}
+int qdev_small_fleet_fetch_last(void *h_, double *const *x, double *const *y, void *info_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    if (!F->solves) { snprintf(s_err, sizeof(s_err), "no solve yet"); return -1; }
+    SHIP(hipSetDevice(F->device));
+    SHIP(fleet_enter(F, F->stream));
+    rc = fleet_fetch(F, x, y, (QPDOInfo *)info_);
+done:
+    return rc;
+}
+// waits for everything the fleet was asked to do; out5: device updates, warm starts, solves since create, then the refusal record since the last sync
+int qdev_small_fleet_sync(void *h_, long *out5) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    SHIP(hipSetDevice(F->device));
+    SHIP(fleet_enter(F, F->stream));
+    SHIP(hipMemcpyAsync(F->hrec, F->drec, 2 * sizeof(int), hipMemcpyDeviceToHost, F->stream));
+    SHIP(hipMemsetD32Async((hipDeviceptr_t)F->drec, 0, 1, F->stream));
+    SHIP(hipMemsetD32Async((hipDeviceptr_t)(F->drec + 1), FLEET_REC_NONE, 1, F->stream));
+    SHIP(fleet_leave(F, F->stream));
+    SHIP(hipStreamSynchronize(F->stream));
+    if (F->timing_pending) { float ms = 0.f; if (hipEventElapsedTime(&ms, F->ev0, F->ev1) == hipSuccess) F->kernel_s = (double)ms * 1e-3; F->timing_pending = false; }
+    out5[0] = F->d_updates; out5[1] = F->d_warm_starts; out5[2] = F->d_solves;
+    out5[3] = F->hrec[0]; out5[4] = F->hrec[0] ? F->hrec[1] : -1;
+done:
+    return rc;
+}
+void qdev_small_fleet_packed_layout(const void *h_, long *noff, long *moff) {
+    const SmallFleet *F = (const SmallFleet *)h_;
+    memcpy(noff, F->noff.data(), F->noff.size() * sizeof(long)); memcpy(moff, F->moff.data(), F->moff.size() * sizeof(long));
 }
 // the certificates of the last solve as the kernel left them (host image): dy (m) of a primal infeasible item, dx (n) of a dual infeasible one
 int qdev_small_fleet_certificates(const void *h_, long item, double *prim_inf_cert, double *dual_inf_cert) {
@@ -464,6 +682,7 @@ void qdev_small_fleet_stats(const void *h_, long *out5, double *kernel_s) {
     *kernel_s = F->kernel_s;
 }
 int qdev_small_fleet_layout(const void *h_) { return ((const SmallFleet *)h_)->layout; }
+int qdev_small_fleet_device(const void *h_) { return ((const SmallFleet *)h_)->device; }
 void qdev_small_fleet_dims(const void *h_, long item, int *n, int *m) {
     const SmallFleet *F = (const SmallFleet *)h_;
     *n = F->it[(size_t)item].n; *m = F->it[(size_t)item].m;

@@ -1176,4 +1176,60 @@ int qpdo_amd_fleet_get_certificates(const QPDOAmdFleet *f, long item, c_float *p
     if (qdev_small_fleet_certificates(f, item, prim_inf_cert, dual_inf_cert)) return fleet_refuse("qpdo_amd_fleet_get_certificates: no solve yet");
     return 0;
 }
+int qpdo_amd_fleet_device(const QPDOAmdFleet *f) {
+    if (!f) { fleet_refuse("qpdo_amd_fleet_device: NULL fleet"); return -1; }
+    return qdev_small_fleet_device(f);
+}
+/* the packed layout of the device calls: pure host arithmetic, no device needed */
+int qpdo_amd_fleet_packed_layout(long count, const QPDOData *const *data, long *noff, long *moff) {
+    if (count <= 0) return fleet_refuse("qpdo_amd_fleet_packed_layout: count must be positive");
+    if (!data) return fleet_refuse("qpdo_amd_fleet_packed_layout: NULL data array");
+    if (!noff || !moff) return fleet_refuse("qpdo_amd_fleet_packed_layout: NULL output");
+    for (long i = 0; i < count; i++) if (!data[i]) return fleet_refuse("qpdo_amd_fleet_packed_layout: NULL item");
+    noff[0] = moff[0] = 0;
+    for (long i = 0; i < count; i++) { noff[i + 1] = noff[i] + (long)data[i]->n; moff[i + 1] = moff[i] + (long)data[i]->m; }
+    return 0;
+}
+int qpdo_amd_fleet_get_packed_layout(const QPDOAmdFleet *f, long *noff, long *moff) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_get_packed_layout: NULL fleet");
+    if (!noff || !moff) return fleet_refuse("qpdo_amd_fleet_get_packed_layout: NULL output");
+    qdev_small_fleet_packed_layout(f, noff, moff);
+    return 0;
+}
+/* device arrays on the caller's stream: the checks that need the runtime (is this pointer device memory?) are in qdev_small_fleet_*_dev */
+static int fleet_dev_failed(const char *name) { char msg[320]; snprintf(msg, sizeof(msg), "%s: %s", name, qdev_small_last_error()); return fleet_refuse(msg); }
+int qpdo_amd_fleet_update_dev(QPDOAmdFleet *f, const double *q, const double *l, const double *u, const int *item_mask, long n_len, long m_len, void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_update_dev: NULL fleet");
+    if (qdev_small_fleet_update_dev(f, q, l, u, item_mask, n_len, m_len, stream)) return fleet_dev_failed("qpdo_amd_fleet_update_dev");
+    return 0;
+}
+int qpdo_amd_fleet_warm_start_dev(QPDOAmdFleet *f, const double *x0, const double *y0, const int *item_mask, long n_len, long m_len, void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_warm_start_dev: NULL fleet");
+    if (qdev_small_fleet_warm_start_dev(f, x0, y0, item_mask, n_len, m_len, 0, stream)) return fleet_dev_failed("qpdo_amd_fleet_warm_start_dev");
+    return 0;
+}
+int qpdo_amd_fleet_warm_start_last_dev(QPDOAmdFleet *f, void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_warm_start_last_dev: NULL fleet");
+    if (qdev_small_fleet_warm_start_dev(f, NULL, NULL, NULL, 0, 0, 1, stream)) return fleet_dev_failed("qpdo_amd_fleet_warm_start_last_dev");
+    return 0;
+}
+int qpdo_amd_fleet_solve_dev(QPDOAmdFleet *f, double *x, double *y, long *status, double *norms, double *prim_inf_cert, double *dual_inf_cert, long n_len, long m_len,
+                             void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_solve_dev: NULL fleet");
+    if (qdev_small_fleet_solve_dev(f, x, y, status, norms, prim_inf_cert, dual_inf_cert, n_len, m_len, stream)) return fleet_dev_failed("qpdo_amd_fleet_solve_dev");
+    return 0;
+}
+int qpdo_amd_fleet_fetch_last(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_fetch_last: NULL fleet");
+    if (!info) return fleet_refuse("qpdo_amd_fleet_fetch_last: NULL info array");
+    if (qdev_small_fleet_fetch_last(f, x, y, info)) return fleet_dev_failed("qpdo_amd_fleet_fetch_last");
+    return 0;
+}
+int qpdo_amd_fleet_sync(QPDOAmdFleet *f, QPDOAmdFleetDevStats *out) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_sync: NULL fleet");
+    long st[5] = {0, 0, 0, 0, -1};
+    if (qdev_small_fleet_sync(f, st)) return fleet_dev_failed("qpdo_amd_fleet_sync");
+    if (out) { out->update_calls = st[0]; out->warm_start_calls = st[1]; out->solve_calls = st[2]; out->refused_items = st[3]; out->first_refused_item = st[4]; }
+    return 0;
+}
 void qpdo_amd_fleet_destroy(QPDOAmdFleet *f) { if (f) qdev_small_fleet_destroy(f); }

@@ -250,6 +250,16 @@ int   qdev_small_fleet_update_matrices(void *fleet, const void *const *Q /* chol
 void  qdev_small_fleet_matrix_stats(const void *fleet, long *out4, double *kernel_seconds);
 void  qdev_small_fleet_dims(const void *fleet, long item, int *n, int *m);
 int   qdev_small_fleet_layout(const void *fleet);
+int   qdev_small_fleet_device(const void *fleet);
+/* device arrays in the fleet's packed layout on the caller's stream (hipStream_t; NULL: the null stream): the length and pointer checks
+ * are inside (before any launch): nonzero with qdev_small_last_error() naming the argument.  Nothing here waits for the device */
+int   qdev_small_fleet_update_dev(void *fleet, const double *q, const double *l, const double *u, const int *item_mask, long n_len, long m_len, void *stream);
+int   qdev_small_fleet_warm_start_dev(void *fleet, const double *x0, const double *y0, const int *item_mask, long n_len, long m_len, int last, void *stream);
+int   qdev_small_fleet_solve_dev(void *fleet, double *x, double *y, long *status, double *norms, double *prim_inf_cert, double *dual_inf_cert, long n_len, long m_len,
+                                 void *stream);
+int   qdev_small_fleet_fetch_last(void *fleet, double *const *x, double *const *y, void *info /* QPDOInfo[count] */);
+int   qdev_small_fleet_sync(void *fleet, long *out5);
+void  qdev_small_fleet_packed_layout(const void *fleet, long *noff, long *moff);
 void  qdev_small_fleet_destroy(void *fleet);
 
 /* ---- ONE small workspace through the fused kernel (the default path of qpdo_solve for problems whose whole state fits one

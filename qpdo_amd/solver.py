@@ -114,7 +114,10 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_create", "qpdo_amd_fleet_update", "qpdo_amd_fleet_warm_start", "qpdo_amd_fleet_warm_start_last",
                "qpdo_amd_fleet_solve", "qpdo_amd_fleet_get_stats", "qpdo_amd_fleet_get_certificates", "qpdo_amd_fleet_destroy",
                "qpdo_amd_fleet_create_ex", "qpdo_amd_fleet_update_matrices", "qpdo_amd_fleet_get_matrix_stats",
-               "qpdo_amd_small_factor_layout", "qpdo_amd_fleet_factor_layout", "qpdo_amd_batch_factor_layout"]
+               "qpdo_amd_small_factor_layout", "qpdo_amd_fleet_factor_layout", "qpdo_amd_batch_factor_layout",
+               "qpdo_amd_fleet_device", "qpdo_amd_fleet_packed_layout", "qpdo_amd_fleet_get_packed_layout", "qpdo_amd_fleet_update_dev",
+               "qpdo_amd_fleet_warm_start_dev", "qpdo_amd_fleet_warm_start_last_dev", "qpdo_amd_fleet_solve_dev", "qpdo_amd_fleet_fetch_last",
+               "qpdo_amd_fleet_sync"]
 
 
 class FleetStats(C.Structure):
@@ -127,6 +130,12 @@ class FleetMatrixStats(C.Structure):
     """QPDOAmdFleetMatrixStats (include/qpdo_amd_ext.h)"""
     _fields_ = [("calls", C.c_long), ("items_last_call", C.c_long), ("value_bytes_uploaded_last_call", C.c_long),
                 ("resident_extra_bytes", C.c_long), ("last_kernel_seconds", C.c_double)]
+
+
+class FleetDevStats(C.Structure):
+    """QPDOAmdFleetDevStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("update_calls", C.c_long), ("warm_start_calls", C.c_long), ("solve_calls", C.c_long), ("refused_items", C.c_long),
+                ("first_refused_item", C.c_long)]
 
 
 FLEET_TABLE_BYTES = 16     # QPDO_AMD_FLEET_TABLE_BYTES
@@ -205,6 +214,17 @@ def lib():
         L.qpdo_amd_fleet_get_stats.argtypes = [C.c_void_p, C.POINTER(FleetStats)]
         L.qpdo_amd_fleet_get_certificates.argtypes = [C.c_void_p, C.c_long, dp, dp]
         L.qpdo_amd_fleet_destroy.argtypes = [C.c_void_p]
+        if hasattr(L, "qpdo_amd_fleet_solve_dev"):          # (device arrays on the caller's stream; absent from an older build, as below)
+            lp, vp = C.POINTER(C.c_long), C.c_void_p        # (device pointers travel as plain addresses)
+            L.qpdo_amd_fleet_device.argtypes = [C.c_void_p]
+            L.qpdo_amd_fleet_packed_layout.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), lp, lp]
+            L.qpdo_amd_fleet_get_packed_layout.argtypes = [C.c_void_p, lp, lp]
+            L.qpdo_amd_fleet_update_dev.argtypes = [C.c_void_p, vp, vp, vp, vp, C.c_long, C.c_long, vp]
+            L.qpdo_amd_fleet_warm_start_dev.argtypes = [C.c_void_p, vp, vp, vp, C.c_long, C.c_long, vp]
+            L.qpdo_amd_fleet_warm_start_last_dev.argtypes = [C.c_void_p, vp]
+            L.qpdo_amd_fleet_solve_dev.argtypes = [C.c_void_p, vp, vp, vp, vp, vp, vp, C.c_long, C.c_long, vp]
+            L.qpdo_amd_fleet_fetch_last.argtypes = [C.c_void_p, pp, pp, C.POINTER(QPDOInfo)]
+            L.qpdo_amd_fleet_sync.argtypes = [C.c_void_p, C.POINTER(FleetDevStats)]
         if hasattr(L, "qpdo_amd_small_factor_layout"):      # (absent from an older build named by QPDO_AMD_LIB for A/B timing: calling it there raises)
             L.qpdo_amd_small_factor_layout.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), C.POINTER(QPDOSettings), C.c_int, C.POINTER(C.c_long)]
             L.qpdo_amd_small_factor_layout.restype = C.c_int
@@ -772,6 +792,48 @@ class BatchStream:
             pass
 
 
+_one_hip_runtime = False
+
+
+def require_one_hip_runtime():
+    """A torch wheel bundles its own HIP runtime, and the loader shares it with libqpdo_amd.so only if torch was imported BEFORE the
+    library was loaded; the other way round the process holds two runtimes, and a device pointer or stream of one means nothing to the
+    other.  The device calls refuse to run in such a process (checked once, from the process's own memory map)."""
+    global _one_hip_runtime
+    if _one_hip_runtime:
+        return
+    try:
+        with open("/proc/self/maps") as f:
+            paths = {os.path.realpath(ln.split()[-1]) for ln in f if "libamdhip64" in ln}
+    except OSError:
+        paths = set()
+    if len(paths) > 1:
+        raise RuntimeError("two HIP runtimes are loaded in this process (%s): import torch before the first qpdo_amd call, so that "
+                           "libqpdo_amd.so binds to the runtime torch ships (INTEGRATION.md)" % ", ".join(sorted(paths)))
+    _one_hip_runtime = True
+
+
+def check_device_tensor(name, t, device_index, dtype, count):
+    """The one check of every tensor a Fleet device call hands to the library, made BEFORE any library call: a GPU tensor on the fleet's
+    device, of the dtype named ("float64", "int32", "int64"), contiguous, with `count` elements.  ValueError names the argument.  Returns
+    the tensor's address, None for None.  (Reads attributes only: torch itself is imported by the callers.)"""
+    if t is None:
+        return None
+    if not all(hasattr(t, a) for a in ("device", "dtype", "is_contiguous", "numel", "data_ptr")):
+        raise ValueError("%s: expected a torch tensor on the GPU, got %s" % (name, type(t).__name__))
+    if str(t.dtype) != "torch." + dtype:
+        raise ValueError("%s: expected dtype %s, got %s" % (name, dtype, t.dtype))
+    if not t.is_contiguous():
+        raise ValueError("%s: the tensor is not contiguous" % name)
+    if t.numel() != count:
+        raise ValueError("%s: expected %d elements (the fleet's packed layout), got %d" % (name, count, t.numel()))
+    if t.device.type != "cuda":
+        raise ValueError("%s: expected a tensor on the GPU, got one on device '%s'" % (name, t.device))
+    if t.device.index != device_index:
+        raise ValueError("%s: the tensor is on GPU %s, the fleet on GPU %d" % (name, t.device.index, device_index))
+    return t.data_ptr()
+
+
 class Fleet:
     """A resident fleet of small QPs (qpdo_amd_fleet_*): set up once, then per control step update() / warm_start_last() / solve(), one
     launch each for all items.  Item i carries the bits of a QPDO workspace of its own driven through the same calls.  The settings are
@@ -803,6 +865,7 @@ class Fleet:
         self._yp = (dp * self.count)(*[_as_dp(y) for _, y in self._outs])
         self._info = (QPDOInfo * self.count)()
         self.kernel_seconds = 0.0
+        self._layout, self._device, self._dev_out = None, None, None     # (the device calls: filled on first use)
 
     def _ptrs(self, vecs, which, clip=False):
         """list of `count` vectors (None entries allowed) -> (array of pointers or None, the arrays kept alive)"""
@@ -913,6 +976,88 @@ class Fleet:
                     r["dual_inf_cert"] = dc
             res.append(r)
         return res
+
+    # ---- device arrays on the caller's stream (qpdo_amd_fleet_*_dev): torch tensors in, torch tensors out, no host wait ----------------
+    def packed_layout(self):
+        """(noff, moff), count + 1 entries each: item i's n-vector is [noff[i], noff[i + 1]) of a packed n-array, its m-vector
+        [moff[i], moff[i + 1]) of a packed m-array; the last entries are the totals N and M"""
+        if getattr(self, "_layout", None) is None:
+            no, mo = (C.c_long * (self.count + 1))(), (C.c_long * (self.count + 1))()
+            self._call(lib().qpdo_amd_fleet_get_packed_layout(self._h, no, mo), "packed_layout")
+            self._layout = (np.array(no[:], np.int64), np.array(mo[:], np.int64))
+            self._device = int(lib().qpdo_amd_fleet_device(self._h))
+        return self._layout
+
+    def _dev_args(self, pairs, mask):
+        """[(name, tensor, dtype, count)] (+ the optional int32 mask) -> addresses, after every tensor has passed check_device_tensor"""
+        self.packed_layout()
+        ptrs = [check_device_tensor(nm, t, self._device, dt, cnt) for nm, t, dt, cnt in pairs]
+        return ptrs, check_device_tensor("mask", mask, self._device, "int32", self.count)
+
+    def _stream(self):
+        import torch
+        require_one_hip_runtime()
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def update_device(self, q=None, l=None, u=None, mask=None):
+        """update() from packed GPU tensors on torch's current stream; returns without waiting.  q: N float64, l / u: M float64 (clamped to
+        +-1e20 as update() clips), mask: count int32, bit 0 / 1 / 2 = the item takes q / l / u.  An item that takes l and u with l > u
+        somewhere is left untouched and counted (sync()); the others proceed."""
+        import torch
+        (no, mo) = self.packed_layout()
+        N, M = int(no[-1]), int(mo[-1])
+        (qp, _, _), mp = self._dev_args([("q", q, "float64", N), ("l", l, "float64", M), ("u", u, "float64", M)], mask)
+        # qpdo.m:215-216.  The clamped copies are made on the current stream and read by launches on it: torch's allocator reuses their
+        # memory only for work that the same stream runs afterwards
+        l = None if l is None else torch.clamp(l, -QPDO_INFTY, QPDO_INFTY)
+        u = None if u is None else torch.clamp(u, -QPDO_INFTY, QPDO_INFTY)
+        lp, up = (None if l is None else l.data_ptr()), (None if u is None else u.data_ptr())
+        self._call(lib().qpdo_amd_fleet_update_dev(self._h, qp, lp, up, mp, N, M, self._stream()), "update_device")
+
+    def warm_start_device(self, x=None, y=None, mask=None):
+        """warm_start() from packed GPU tensors (x: N, y: M float64; mask bit 0 / 1 = the item takes x / y, else starts it from zero)"""
+        (no, mo) = self.packed_layout()
+        N, M = int(no[-1]), int(mo[-1])
+        (xp, yp), mp = self._dev_args([("x", x, "float64", N), ("y", y, "float64", M)], mask)
+        self._call(lib().qpdo_amd_fleet_warm_start_dev(self._h, xp, yp, mp, N, M, self._stream()), "warm_start_device")
+
+    def warm_start_last_device(self):
+        self.packed_layout()
+        self._call(lib().qpdo_amd_fleet_warm_start_last_dev(self._h, self._stream()), "warm_start_last_device")
+
+    def solve_device(self, out=None):
+        """solve() on torch's current stream into GPU tensors; returns them without waiting: x (N), y (M), status (count, 3) int64 =
+        status_val, iterations, oterations, norms (count, 5) = the four residual norms and the objective, prim_inf_cert (M),
+        dual_inf_cert (N); NaN rules of results().  The tensors are allocated once and reused by later calls unless `out` (a dict with
+        any of these keys) supplies them."""
+        import torch
+        (no, mo) = self.packed_layout()
+        N, M = int(no[-1]), int(mo[-1])
+        spec = [("x", "float64", (N,)), ("y", "float64", (M,)), ("status", "int64", (self.count, 3)), ("norms", "float64", (self.count, 5)),
+                ("prim_inf_cert", "float64", (M,)), ("dual_inf_cert", "float64", (N,))]
+        if out is None:
+            if getattr(self, "_dev_out", None) is None:
+                dev = torch.device("cuda", self._device)
+                self._dev_out = {k: torch.empty(shape, dtype=getattr(torch, dt), device=dev) for k, dt, shape in spec}
+            out = self._dev_out
+        unknown = set(out) - {k for k, _, _ in spec}
+        if unknown:
+            raise ValueError("out: unknown keys %r" % sorted(unknown))
+        ptrs, _ = self._dev_args([(k, out.get(k), dt, int(np.prod(shape))) for k, dt, shape in spec], None)
+        self._call(lib().qpdo_amd_fleet_solve_dev(self._h, *ptrs, N, M, self._stream()), "solve_device")
+        return out
+
+    def fetch_last(self):
+        """what results() returns, for the last solve whichever call launched it (waits for it; launches nothing)"""
+        self._call(lib().qpdo_amd_fleet_fetch_last(self._h, self._xp, self._yp, self._info), "fetch_last")
+        self.kernel_seconds = self.stats()["last_kernel_seconds"]
+        return self.results()
+
+    def sync(self):
+        """waits for everything this fleet was asked to do; the device-call counters and the refusal record since the last sync()"""
+        s = FleetDevStats()
+        self._call(lib().qpdo_amd_fleet_sync(self._h, C.byref(s)), "sync")
+        return {f: getattr(s, f) for f, _ in FleetDevStats._fields_}
 
     def factor_layout(self):
         """where this fleet's launches keep the Newton matrix: K_GLOBAL, K_PACKED or K_BAND (qpdo_amd_fleet_factor_layout)"""
