@@ -65,8 +65,17 @@
  *   QPDO_DEFLATE     "0" disables the heavy-row deflation of the PCG preconditioner
  *   QPDO_IDX16       "0" disables the 16-bit slab-local column indices
  *   QPDO_PCG_SCHUR   "0" disables / "1" forces the Schur-complement mode of the PCG (default: automatic)
- *   QPDO_PCG_INNER_F32  "1": the Schur mode's inner (preconditioner) solve streams an fp32 copy of the compact matrix values;
- *                    vectors, accumulation and the outer CG on the exact K stay fp64 (opt-in, default off)
+ *   QPDO_PCG_INNER_REFINE  how the Schur mode solves its inner (preconditioner) system S' s = b.  Default (unset or "1", one GPU, both compact
+ *                    matrices under the slab kernel with 16-bit indices): the inner CG streams fp32 copies of the compact matrix values (6
+ *                    instead of 10 bytes per nonzero; +4 bytes per nonzero of A and A' of device memory) and only PROPOSES corrections; after
+ *                    each CG sweep the residual b - S' s is formed with the fp64 matrices and the solve is accepted on ||b - S' s||_2 <= tau
+ *                    ||b||_2, today's tolerance: THE ACCEPTANCE IS IN FP64, as are all vectors, accumulations and tests.  A solve that is not
+ *                    accepted after QPDO_INNER_REFINE_MAXSWEEP sweeps (default 6) is redone by the fp64 inner CG (QPDOAmdStats.inner_refine_*).
+ *                    QPDO_INNER_REFINE_THETA (default 0.8): a sweep's CG runs to a recursive residual of theta tau ||b|| (cost knob).
+ *                    "0": the fp64 inner CG.  Row-partitioned solves always take the fp64 inner CG
+ *   QPDO_PCG_INNER_F32  "1": ONE inner CG solve on the fp32 copies, accepted on its own recursive residual -- nothing checks what the rounded
+ *                    matrices did to it (opt-in, default off, never the measured configuration; overrides QPDO_PCG_INNER_REFINE); vectors,
+ *                    accumulation and the outer CG on the exact K stay fp64
  *   QPDO_PCG_TOL     relative residual tolerance of the Jacobi-PCG solve (default 1e-12)
  *   QPDO_PCG_ABS     factor f of the absolute stopping rule of the PCG solve: stop when the residual, in the unscaled inf-norm of
  *                    the reference's inner dual residual, is <= f * eps_abs (default 1e-5; 0: relative rule only; proximal only)
@@ -149,6 +158,13 @@ typedef struct {
     long   coupled_solves;  /* band solves with at least one weighted coupling row that were accepted by their residual check             */
     long   coupled_sweeps;  /* sweeps of those solves: one band solve, the k x k correction and 3 SpMV each (1 = accepted at once)         */
     long   coupled_rejects; /* such solves that missed the residual check after the sweeps: the pass went to the band fallback (band_fallbacks) */
+    /* refined inner solves of the Schur mode (QPDO_PCG_INNER_REFINE, the default; appended: the members above keep their offsets) */
+    long   inner_refine_sweeps;       /* fp32 CG sweeps that converged and were followed by a residual formed with the fp64 matrices (>= inner_solves
+                                       * when no inner solve needed the fallback at its first sweep)                                           */
+    long   inner_refine_fp64_applies; /* applications of S' with the fp64 matrices that formed those residuals (two products each)              */
+    long   inner_refine_fallbacks;    /* inner solves redone by the fp64 inner CG: QPDO_INNER_REFINE_MAXSWEEP sweeps (default 6) did not reach the
+                                       * tolerance, or a sweep did not converge                                                                */
+    double inner_refine_max_res_over_tol; /* largest ||b - S' s||_2 / (tau ||b||_2) an inner solve was accepted with, fp64 residual: <= 1        */
 } QPDOAmdStats;
 
 int  qpdo_amd_device_count(void);
@@ -245,6 +261,10 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *           and right-hand side 2-norms of the last iteration, [6], [7] = inner solves and inner steps launched, [8] = class: 0 ok,
  *           1 not converged, 2 NaN residual, [9] = iterations of the outer CG alone (= [1] outside the Schur mode), [10] = 1 when the Schur
  *           mode took its inner diagonal from the pass's one read of the weighted rows (QPDO_COMPACT_ONE_READ), 0 when k_schur_diag ran.
+ *   mode 32, 33  the compact matrices are built from dw and ONE product runs through the slab kernel's fp32-stream instance (the stream of the
+ *           refined inner solve): mode 32 out[0 .. k) = A_c32 v, mode 33 out (n) = A_c32' v[0 .. k), A_c32 = the compact values rounded to float,
+ *           products and sums in double.  info[0] = k.  Refused (-1) where the pass has no fp32 images: a compact matrix on the plain kernel
+ *           or without 16-bit indices, QPDO_PCG_INNER_REFINE=0 without QPDO_PCG_INNER_F32=1, or k > n.
  * Returns 0; QPDO_AMD_PCG_NOT_CONVERGED / QPDO_AMD_PCG_NAN for a solve of class 1 / 2 (out is not written, qpdo_amd_last_error carries the
  * solver's message); -1 on any other failure.  The workspace's weights, sigma, direction, right-hand side, stopping rule, Schur-mode
  * state and counters are put back: the next qpdo_solve runs as on a workspace that never saw the call.

@@ -226,21 +226,24 @@ static const int PCG_NAN = -8;                  // a NaN residual: a numerical f
 //
 // One application  w = S' u = u ./ d + A_c ((A_c' u) ./ Dq):  t in d->tmp_n, the partial sums of (A_c' u).t in Pf (fcnt of them).
 // par: parity of the local partial sums (in P3) that accompany this application.
-static bool schur_inner_f32(const QpdoDev *d) {
-    return d->inner_f32 && d->Atc.use_slab && d->Arc.use_slab && d->Atc.vsm32 && d->Arc.vsm32 && d->Atc.i16sm && d->Arc.i16sm;
+// both compact matrices of this pass take the 16-bit slab kernel and have their fp32 images
+static bool schur_f32_ready(const QpdoDev *d) {
+    return !d->comm.active && d->Atc.use_slab && d->Arc.use_slab && d->Atc.vsm32 && d->Arc.vsm32 && d->Atc.i16sm && d->Arc.i16sm;
 }
-static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const int *done2, bool sample, int *fcnt) {
+// QPDO_PCG_INNER_F32=1: ONE inner CG solve on the fp32 images, accepted on its own recursive residual (opt-in, never the measured configuration)
+static bool schur_inner_f32(const QpdoDev *d) { return d->inner_f32 && schur_f32_ready(d); }
+// the default: the fp32 images only propose corrections, the solve is accepted on the fp64 residual (schur_inner_solve)
+static bool schur_inner_refine(const QpdoDev *d) { return d->inner_refine && !d->inner_f32 && schur_f32_ready(d); }
+// f32: both products stream the fp32 images (single GPU)
+static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const int *done2, bool sample, int *fcnt, bool f32) {
     const bool dist = d->comm.active;
     const int n = d->n, kl = d->kact;
     double *Pf = d->part2 + 6 * PGRID;
     if (!dist) {
-        const bool f32 = schur_inner_f32(d);
-        if (f32) launch_spmv_slab32(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, done2);
-        else launch_spmv(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, true, done2);
+        launch_spmv(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, true, done2, f32);
         // HIP-event sample of the dominant kernel (the A_c product), taken mid-batch by the caller's choice of `sample`
         if (sample) (void)hipEventRecord(d->ev0, d->stream);
-        if (f32) launch_spmv_slab32(d, d->Arc, d->tmp_n, EpiSchurW{d->dc, u, w}, done2);
-        else launch_spmv(d, d->Arc, d->tmp_n, EpiSchurW{d->dc, u, w}, false, done2);
+        launch_spmv(d, d->Arc, d->tmp_n, EpiSchurW{d->dc, u, w}, false, done2, f32);
         if (sample) (void)hipEventRecord(d->ev1, d->stream);
         *fcnt = spmv_pgrid(d->Atc);
         return 0;
@@ -256,8 +259,10 @@ static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const 
     *fcnt = vgrid(n);
     return 0;
 }
-// s_x = S'^-1 s_v by the single-reduction Jacobi-PCG (device latch in ctrl2, batches of iterations between host syncs)
-static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
+// s_x = S'^-1 b by the single-reduction Jacobi-PCG (device latch in ctrl2, batches of iterations between host syncs), to a recursive
+// residual of tol ||b||.  f32: the products stream the fp32 images.  init: b = s_v and k_cgcg_init runs; otherwise the caller has left the
+// state of step 0 (k_refine_init, k_refine_norm).  first_batch: iterations issued before the first host read.
+static int schur_inner_cg(QpdoDev *d, double tol, bool f32, bool init, int first_batch, int *iters) {
     const bool dist = d->comm.active;
     const int kl = d->kact, g = vgrid(kl);
     double *P3 = d->part2;                   // [3 sums][2 parities][PGRID]; Pf behind them
@@ -265,23 +270,18 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
     const int *done2 = &d->ctrl2->cnt[C_PCG_DONE];
     const double *glob3 = dist ? d->dist_tmp + d->n : (const double *)nullptr;
     int fcnt = 0;
-    // Two-launch schedule (single GPU, fp64 inner matrices, one element per thread of k_cgcg_step's grid): product 2 of application
+    // Two-launch schedule (single GPU, either value width, one element per thread of k_cgcg_step's grid): product 2 of application
     // j - 1 performs step j (EpiSchurStep), product 1 of application j forms that step's three partial sums first (EpiDivDotSums).
     // QPDO_INNER_FOLD=0 selects the three-launch schedule; both run the same device functions (pcg_kernels.inc) and give the same bits.
-    const bool fold = d->inner_fold && !dist && !schur_inner_f32(d) && (long long)g * BLK >= kl;
-    LAUNCH(k_cgcg_init, g, kl, (const double *)d->s_v, (const double *)d->s_diag, (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, P3, d->ctrl2);
+    const bool fold = d->inner_fold && !dist && (long long)g * BLK >= kl;
+    if (init) LAUNCH(k_cgcg_init, g, kl, (const double *)d->s_v, (const double *)d->s_diag, (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, P3, d->ctrl2);
     int rc = 0;
     if (fold) {
-        launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, 0, d->s_r, d->s_z, d->dc, (double *)nullptr}, true, done2);
+        launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, 0, d->s_r, d->s_z, d->dc, (double *)nullptr}, true, done2, f32);
         fcnt = spmv_pgrid(d->Atc);
-    } else { rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt); if (rc) return -1; }
-    d->st.inner_solves++;
+    } else { rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt, f32); if (rc) return -1; }
     int j = 0;
-    // Batches between host syncs.  The iteration count of an inner solve is almost the same as that of the previous one
-    // in the pass (same operator, same tolerance), so the first batch runs to just short of it and the rest are short:
-    // few syncs and few latched (no-op) launches after convergence.  (Row-partitioned: the collectives of a latched
-    // iteration still run, on every rank alike.)
-    int batch = d->schur_last_inner > 12 ? d->schur_last_inner - 6 : d->pcg_batch;
+    int batch = first_batch;
     while (j < SCHUR_INNER_MAXIT) {
         const int it_before = j, sample_b = batch / 2;
         for (int b = 0; b < batch; b++, j++) {           // issue iteration j: step j, then S' applied to the new u
@@ -289,29 +289,84 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
             if (fold) {
                 // (the HIP-event sample of the A_c product includes the step it performs; its byte count is that of the product)
                 if (sample) (void)hipEventRecord(d->ev0, d->stream);
-                launch_spmv(d, d->Arc, d->tmp_n, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol}, false);
+                launch_spmv(d, d->Arc, d->tmp_n, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol}, false, nullptr, f32);
                 if (sample) (void)hipEventRecord(d->ev1, d->stream);
-                launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3}, true, done2);
+                launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3}, true, done2, f32);
             } else {
                 LAUNCH(k_cgcg_step, g, kl, j, d->ctrl2, glob3, P3, g, (const double *)Pf, fcnt, (const double *)d->s_Sp, (const double *)d->s_diag,
                        (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol);
-                rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, sample, &fcnt); if (rc) return -1;
+                rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, sample, &fcnt, f32); if (rc) return -1;
             }
             d->st.inner_steps++;
         }
         rc = read_ctrl2(d); if (rc) return rc;
         if (!dist && d->hctrl2->cnt[C_PCG_IT] > it_before + sample_b) {          // the sampled iteration of this batch really ran
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, d->ev0, d->ev1) == hipSuccess) { d->ev_ac_ms += ms; d->ev_ac_bytes += d->Arc.alg_bytes(); d->ev_ac_n++; }
+            // (the bytes of the product that was sampled: the roofline fraction stays a statement about the kernel that ran)
+            if (hipEventElapsedTime(&ms, d->ev0, d->ev1) == hipSuccess) { d->ev_ac_ms += ms; d->ev_ac_bytes += f32 ? d->Arc.alg_bytes32() : d->Arc.alg_bytes(); d->ev_ac_n++; }
         }
         if (d->hctrl2->cnt[C_PCG_DONE]) break;
         batch = 4;
     }
-    d->schur_last_inner = d->hctrl2->cnt[C_PCG_IT];
     *iters = d->hctrl2->cnt[C_PCG_IT];
     const double rn = d->hctrl2->val[V_RNORM], bn = d->hctrl2->val[V_BNORM];
     const bool conv = d->hctrl2->cnt[C_PCG_DONE] && (rn <= tol * bn);          // the latch is also set by a NaN residual
     return conv ? 0 : 1;                                                       // 1: not converged
+}
+// s = S'^-1 s_v to ||s_v - S' s||_2 <= tol ||s_v||_2; leaves d->s_sol pointing at s.  Returns 0, 1 (not converged) or < 0 (failure).
+// Default where both compact matrices have their fp32 images (schur_inner_refine): iterative refinement.  s = 0, rho = b; per sweep the
+// CG runs on the fp32 images with right-hand side rho to a recursive residual of theta tol ||b|| and gives e; s += e; rho = b - S' s with
+// the fp64 images (one EpiDivDot and one EpiSchurW product, k_refine_init); the solve is accepted when ||rho|| <= tol ||b||.  The rounded
+// matrices only propose corrections: what is accepted satisfies today's tolerance on the fp64 residual, and every vector, accumulation
+// and test is fp64.  Past refine_maxsweep sweeps (or a sweep that does not converge) the solve is redone by the fp64 CG and counted.
+// theta is a cost knob (QPDO_INNER_REFINE_THETA): docs/LAB_NOTES.md.
+static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
+    // The iteration count of an inner solve is almost the same as that of the previous one in the pass (same operator, same
+    // tolerance), so the first batch runs to just short of it and the rest are short: few syncs and few latched (no-op) launches
+    // after convergence.  (Row-partitioned: the collectives of a latched iteration still run, on every rank alike.)
+    const int first_batch = d->schur_last_inner > 12 ? d->schur_last_inner - 6 : d->pcg_batch;
+    d->st.inner_solves++;
+    d->s_sol = d->s_x;
+    if (!schur_inner_refine(d)) {
+        const int st = schur_inner_cg(d, tol, schur_inner_f32(d), true, first_batch, iters);
+        if (st >= 0) d->schur_last_inner = *iters;
+        return st;
+    }
+    const int kl = d->kact, g = vgrid(kl);
+    double bn = 0.0, rho = 0.0;
+    int total = 0;
+    for (int sweep = 0; sweep < d->refine_maxsweep; sweep++) {
+        int it = 0;
+        // the sweep's own right-hand side is rho: theta tol ||b|| relative to ||rho|| (not accepted: rho > tol ||b||, so this is < theta)
+        const double tol_s = sweep == 0 ? d->refine_theta * tol : d->refine_theta * tol * bn / rho;
+        const int st = schur_inner_cg(d, tol_s, true, sweep == 0, sweep == 0 ? first_batch : d->pcg_batch, &it);
+        if (st < 0) return st;
+        total += it;
+        if (sweep == 0) { bn = d->hctrl2->val[V_BNORM]; d->schur_last_inner = it; }
+        if (st) break;                                                         // not converged, or NaN: the fp64 CG decides
+        LAUNCH(k_refine_acc, g, kl, sweep == 0 ? 1 : 0, (const double *)d->s_x, d->s_acc);
+        int fcnt = 0;
+        if (schur_S_apply(d, d->s_acc, d->s_Sp, 0, nullptr, false, &fcnt, false)) return -1;
+        LAUNCH(k_refine_init, g, kl, (const double *)d->s_v, (const double *)d->s_Sp, (const double *)d->s_diag, (const double *)d->dc,
+               d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, d->part2);
+        LAUNCH(k_refine_norm, 1, (const double *)d->part2, g, d->ctrl2);
+        { const int rc = read_ctrl2(d); if (rc) return rc; }
+        rho = d->hctrl2->val[V_RNORM];
+        d->st.inner_refine_sweeps++; d->st.inner_refine_fp64_applies++;
+        if (!(rho == rho)) break;
+        if (rho <= tol * bn) {
+            const double ratio = bn > 0.0 ? rho / (tol * bn) : 0.0;
+            if (ratio > d->st.inner_refine_max_res_over_tol) d->st.inner_refine_max_res_over_tol = ratio;
+            d->s_sol = d->s_acc;
+            *iters = total;
+            return 0;
+        }
+    }
+    d->st.inner_refine_fallbacks++;
+    int it = 0;
+    const int st = schur_inner_cg(d, tol, false, true, first_batch, &it);
+    *iters = total + it;
+    return st;
 }
 // z <- M^-1 r given u = Dq^-1 r in pc_z; leaves the r.z partials in p_rz.  Returns their count (or -1 on failure).
 static int schur_apply(QpdoDev *d, double tol, double *p_rz, int *inner_iters, int *status) {
@@ -323,13 +378,13 @@ static int schur_apply(QpdoDev *d, double tol, double *p_rz, int *inner_iters, i
     *inner_iters += it;
     if (*status < 0) return -1;
     if (dist) {
-        if (kl > 0) launch_spmv(d, d->Atc, d->s_x, EpiStore{d->dist_tmp}, false);
+        if (kl > 0) launch_spmv(d, d->Atc, d->s_sol, EpiStore{d->dist_tmp}, false);
         else HIPCHK(hipMemsetAsync(d->dist_tmp, 0, (size_t)d->n * 8, d->stream));
         if (comm_allreduce(d, d->dist_tmp, (size_t)d->n, 0)) return -1;
         hipLaunchKernelGGL((k_epi_apply<EpiDeflZ>), dim3(vgrid(d->n)), dim3(BLK), 0, d->stream, d->n, (const double *)d->dist_tmp, EpiDeflZ{d->pc_diag, d->pc_r, d->pc_z, p_rz});
         return vgrid(d->n);
     }
-    launch_spmv(d, d->Atc, d->s_x, EpiDeflZ{d->pc_diag, d->pc_r, d->pc_z, p_rz}, true);
+    launch_spmv(d, d->Atc, d->s_sol, EpiDeflZ{d->pc_diag, d->pc_r, d->pc_z, p_rz}, true);
     return spmv_pgrid(d->Atc);
 }
 // The per-block partial arrays of the outer PCG in d->part, named once per solve.

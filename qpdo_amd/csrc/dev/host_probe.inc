@@ -165,7 +165,8 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
 // pcg_K_apply on p = v with the latch cleared (every launch of the product leaves at once while C_PCG_DONE is set): out = K v, info =
 // [kact, cnt] and the cnt per-block partial sums of p.Kp from info[QDEV_PCG_INFO_HEAD] on.  mode 1: ONE pcg_solve of K x = v with the
 // relative stopping rule alone: out = x, info = [kact, iters, defl_r, Schur mode delivered, V_RNORM, V_BNORM, inner solves, inner steps,
-// class (0 ok, 1 not converged, 2 NaN), outer iterations].  info holds QDEV_PCG_INFO_LEN doubles.  A solve of class 1 or 2 returns QDEV_PCG_NOT_CONVERGED /
+// class (0 ok, 1 not converged, 2 NaN), outer iterations].  mode 32 / 33: build_compact, then one product of the fp32-stream slab kernel with
+// A_c / A_c' (refused where the pass has no fp32 images).  info holds QDEV_PCG_INFO_LEN doubles.  A solve of class 1 or 2 returns QDEV_PCG_NOT_CONVERGED /
 // QDEV_PCG_NAN with pcg_verdict's message, never a HIP code.  Whatever the call overwrites -- the weights, sigma_f, dx, rhs, the stopping
 // rule, the Schur mode's strikes and batch memory, the counters -- is put back: the next solve runs as on a workspace that never saw it.
 static_assert(QDEV_PCG_NOT_CONVERGED == PCG_NOT_CONVERGED && QDEV_PCG_NAN == PCG_NAN, "qpdo_dev.h carries the PCG failure classes");
@@ -174,14 +175,14 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
     HIPCHK(hipSetDevice(d->device));
     if (d->comm.active) return set_err(hipErrorInvalidValue, "pcg probe: not for row-partitioned workspaces", __LINE__);
     if (d->linsolve != 0) return set_err(hipErrorInvalidValue, "pcg probe: the workspace's solver is not PCG", __LINE__);
-    if (mode != 0 && mode != 1) return set_err(hipErrorInvalidValue, "pcg probe: mode is 0 (one K product) or 1 (one solve)", __LINE__);
+    if (mode != 0 && mode != 1 && mode != 32 && mode != 33) return set_err(hipErrorInvalidValue, "pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product)", __LINE__);
     const int n = d->n, m = d->m;
     std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1)), rhs_keep((size_t)(n > 0 ? n : 1));
     if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
     if (n) HIPCHK(hipMemcpyAsync(dx_keep.data(), d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
     if (n) HIPCHK(hipMemcpyAsync(rhs_keep.data(), d->rhs, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
     if (m) HIPCHK(hipMemcpyAsync(d->d, dw, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
-    if (n) HIPCHK(hipMemcpyAsync(mode == 0 ? d->pc_p : d->rhs, v, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(mode != 1 ? d->pc_p : d->rhs, v, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     const double sigma_keep = d->sigma_f, abs_keep = d->pcg_abs_now;
     const int off_keep = d->schur_off, strikes_keep = d->schur_strikes, inner_keep = d->schur_last_inner, jac_keep = d->last_jacobi_iters;
@@ -204,6 +205,20 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
         if (!rc) HIPCHK(hipStreamSynchronize(d->stream));
         if (!rc) HIPCHK(hipGetLastError());
         info[0] = (double)d->kact; info[1] = (double)cnt;
+    } else if (mode == 32 || mode == 33) {
+        // the slab kernel's fp32-stream instances on their own: out[0 .. k) = A_c32 v (mode 32), out (n) = A_c32' v[0 .. k) (mode 33), A_c32 =
+        // the compact values rounded to float, products and sums in double
+        rc = build_compact(d);
+        const int k = d->kact;
+        if (!rc && (!schur_f32_ready(d) || k > n)) rc = set_err(hipErrorInvalidValue, "pcg probe: this pass has no fp32 images (both compact matrices under the slab kernel with 16-bit indices, QPDO_PCG_INNER_REFINE or QPDO_PCG_INNER_F32 on, k <= n)", __LINE__);
+        if (!rc) {
+            if (mode == 32) launch_spmv(d, d->Arc, d->pc_p, EpiStore{d->tc}, false, nullptr, true);
+            else launch_spmv(d, d->Atc, d->pc_p, EpiStore{d->tmp_n}, false, nullptr, true);
+            HIPCHK(hipMemcpyAsync(out, mode == 32 ? d->tc : d->tmp_n, (size_t)(mode == 32 ? k : n) * 8, hipMemcpyDeviceToHost, d->stream));
+            HIPCHK(hipStreamSynchronize(d->stream));
+            HIPCHK(hipGetLastError());
+        }
+        info[0] = (double)k;
     } else {
         int iters = 0;
         d->sdiag_from_build = 0;

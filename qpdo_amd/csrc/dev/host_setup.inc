@@ -120,7 +120,7 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
     A_(ls_bt, (size_t)2 * d->ls_nblk + 2);
     A_(ctrl, 1); A_(part, (size_t)P_COUNT * PGRID);
     A_(ctrl2, 1); A_(part2, (size_t)7 * PGRID);      // inner CG: 3 sums x 2 parities, then the n-dot partials
-    A_(s_x, m); A_(s_r, m); A_(s_z, m); A_(s_p, m); A_(s_Sp, m); A_(s_diag, m); A_(s_v, m); A_(s_s, m);
+    A_(s_x, m); A_(s_r, m); A_(s_z, m); A_(s_p, m); A_(s_Sp, m); A_(s_diag, m); A_(s_v, m); A_(s_s, m); A_(s_acc, m);
 #undef A_
     static_assert(sizeof(Ctrl) % 8 == 0 && sizeof(Ctrl) <= 64 * 8 && sizeof(Ctrl) <= CTRL_SEQ_OFF, "k_ctrl_publish copies the control block with one wave");
     if (!rc) { e = hipHostMalloc((void **)&d->hctrl, CTRL_SEQ_OFF + 64, hipHostMallocCoherent); if (e != hipSuccess) rc = set_err(e, "hipHostMalloc", __LINE__); }
@@ -170,6 +170,11 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         d->Arc.vsm = nullptr; d->Arc.i16sm = nullptr; d->Arc.cism = nullptr; d->Arc.seg = nullptr; d->Arc.vsm32 = nullptr;
         d->Atc.vsm = nullptr; d->Atc.i16sm = nullptr; d->Atc.cism = nullptr; d->Atc.seg = nullptr; d->Atc.vsm32 = nullptr;
         { const char *f32 = getenv("QPDO_PCG_INNER_F32"); d->inner_f32 = (f32 && atoi(f32) != 0) ? 1 : 0; }
+        // the default inner solve: fp32 stream, accepted on the fp64 residual (single GPU; "0": the fp64 inner CG)
+        { const char *rf = getenv("QPDO_PCG_INNER_REFINE"); d->inner_refine = !(rf && *rf && atoi(rf) == 0) && !d->comm.active; }
+        { const char *ms = getenv("QPDO_INNER_REFINE_MAXSWEEP"); d->refine_maxsweep = (ms && atoi(ms) > 0) ? atoi(ms) : 6; }
+        { const char *th = getenv("QPDO_INNER_REFINE_THETA"); d->refine_theta = (th && atof(th) > 0 && atof(th) <= 1.0) ? atof(th) : 0.8; }
+        const bool with_f32 = d->inner_f32 != 0 || d->inner_refine != 0;
         { const char *fo = getenv("QPDO_INNER_FOLD"); d->inner_fold = !(fo && *fo && atoi(fo) == 0); }
         { const char *co = getenv("QPDO_COMPACT_ONE_READ"); d->compact_one_read = !(co && *co && atoi(co) == 0); }
         { const char *ct = getenv("QPDO_COMPACT_T_ONE_READ"); d->compact_t_one_read = !(ct && *ct && atoi(ct) == 0); }
@@ -178,13 +183,13 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         if (!rc) rc = dev_alloc(d, &d->Arc.val, (size_t)d->Ar.nnz);
         if (!rc && d->Ar.use_slab) rc = dev_alloc(d, &d->Arc.sp, (size_t)m * (d->Ar.nslabs + 1));
         if (!rc && d->Ar.ci16) rc = dev_alloc(d, &d->Arc.ci16, (size_t)d->Ar.nnz);
-        if (!rc && d->Ar.use_slab) rc = slab_major_alloc(d, &d->Arc, (size_t)d->Ar.nnz, (size_t)m * d->Ar.nslabs, d->inner_f32 != 0);
+        if (!rc && d->Ar.use_slab) rc = slab_major_alloc(d, &d->Arc, (size_t)d->Ar.nnz, (size_t)m * d->Ar.nslabs, with_f32);
         if (!rc) rc = dev_alloc(d, &d->Atc.rp, (size_t)n + 1);
         if (!rc) rc = dev_alloc(d, &d->Atc.ci, (size_t)d->At.nnz);
         if (!rc) rc = dev_alloc(d, &d->Atc.val, (size_t)d->At.nnz);
         if (!rc && d->At.use_slab) rc = dev_alloc(d, &d->Atc.sp, (size_t)n * (d->At.nslabs + 1));
         if (!rc && d->At.ci16) rc = dev_alloc(d, &d->Atc.ci16, (size_t)d->At.nnz);
-        if (!rc && d->At.use_slab) rc = slab_major_alloc(d, &d->Atc, (size_t)d->At.nnz, (size_t)n * d->At.nslabs, d->inner_f32 != 0);
+        if (!rc && d->At.use_slab) rc = slab_major_alloc(d, &d->Atc, (size_t)d->At.nnz, (size_t)n * d->At.nslabs, with_f32);
         if (!rc) rc = dev_alloc(d, &d->row_cnt, (size_t)(n > m ? n : m));
         if (!rc) rc = dev_alloc(d, &d->cidx, (size_t)m);
         if (!rc) rc = dev_alloc(d, &d->rowlist, (size_t)m);

@@ -69,7 +69,7 @@ static int reset_to_setup_state(QpdoDev *d) {
     double *vn[] = {d->x, d->xbar, d->Qx, d->Aty, d->df, d->res_dual, d->res_dual_in, d->rhs, d->dx, d->Qdx, d->Atdy, d->D, d->Dinv,
                     d->pc_r, d->pc_z, d->pc_p, d->pc_Kp, d->pc_diag, d->tmp_n, d->qdiag};
     double *vm[] = {d->y, d->ybar, d->Ax, d->mu, d->isq, d->w, d->res_prim, d->res_prim_old, d->res_prim_in, d->dy, d->Adx, d->d, d->E, d->Einv,
-                    d->pc_t, d->at_scale, d->tmp_m, d->s_x, d->s_r, d->s_z, d->s_p, d->s_Sp, d->s_diag, d->s_v, d->s_s, d->dc, d->tc};
+                    d->pc_t, d->at_scale, d->tmp_m, d->s_x, d->s_r, d->s_z, d->s_p, d->s_Sp, d->s_diag, d->s_v, d->s_s, d->s_acc, d->dc, d->tc};
     for (double *p : vn) HIPCHK(hipMemsetAsync(p, 0, n * 8, d->stream));
     if (m) {
         for (double *p : vm) HIPCHK(hipMemsetAsync(p, 0, m * 8, d->stream));

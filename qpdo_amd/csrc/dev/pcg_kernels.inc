@@ -108,7 +108,7 @@ __global__ void k_pcg_p(int n, const Ctrl *__restrict__ ctrl, const double *__re
 // workgroups of one launch read what another workgroup of the same launch must not overwrite.  All reductions run in a fixed
 // order: bitwise reproducible, and the same bits from both schedules --
 //     three launches: k_cgcg_step, product 1 (EpiDivDot), product 2 (EpiSchurW);
-//     two launches (single GPU, fp64 matrices, k <= PGRID * 256): product 2 performs the step behind its rows (EpiSchurStep) and
+//     two launches (single GPU, either value width of the matrix stream, k <= PGRID * 256): product 2 performs the step behind its rows (EpiSchurStep) and
 //     product 1 forms the step's partial sums in front of its own (EpiDivDotSums) --
 // because both are built from the same three functions: cgcg_scalars, cgcg_elem, cgcg_sums (+ cgcg_put3).
 // ------------------------------------------------------------------------------------------------
@@ -184,6 +184,34 @@ __global__ __launch_bounds__(256) void k_cgcg_init(int k, const double *__restri
     }
     cgcg_put3(a, c, e, P3, 0, blockIdx.x, sm);
     if (blockIdx.x == 0 && threadIdx.x == 0) { ctrl->cnt[C_PCG_DONE] = 0; ctrl->cnt[C_PCG_IT] = 0; ctrl->val[V_RNORM] = 0.0; }
+}
+// ---- refinement of the inner solve (schur_inner_solve): the CG above runs on the fp32 copies of the matrices and only proposes
+// corrections; these three kernels keep the solution and form the residual that accepts it, all in fp64 ----
+// sol = e (first sweep) or sol += e
+__global__ __launch_bounds__(256) void k_refine_acc(int k, int first, const double *__restrict__ e, double *__restrict__ sol) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) sol[i] = first ? e[i] : sol[i] + e[i];
+}
+// rho = b - w, w = S' sol formed with the fp64 matrices, as the right-hand side of the next sweep: k_cgcg_init with rho for b -- the CG
+// state of the sweep and the three partial sums of its step 0 in cgcg_put3's fixed order, (rho, rho) among them
+__global__ __launch_bounds__(256) void k_refine_init(int k, const double *__restrict__ b, const double *__restrict__ w, const double *__restrict__ dg,
+                                                     const double *__restrict__ dc, double *__restrict__ x, double *__restrict__ r, double *__restrict__ u,
+                                                     double *__restrict__ p, double *__restrict__ s, double *__restrict__ P3 /* slot 0 written */) {
+    __shared__ double sm[16];
+    double a = 0.0, c = 0.0, e = 0.0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
+        const double bi = b[i] - w[i], ui = bi / dg[i];
+        x[i] = 0.0; r[i] = bi; u[i] = ui; p[i] = 0.0; s[i] = 0.0;
+        double ta, tc, te;
+        cgcg_sums(bi, ui, dc[i], ta, tc, te);
+        a += ta; c += tc; e += te;
+    }
+    cgcg_put3(a, c, e, P3, 0, blockIdx.x, sm);
+}
+// ||rho||_2 from those partial sums -> V_RNORM, and the control block as k_cgcg_init leaves it for the sweep
+__global__ __launch_bounds__(256) void k_refine_norm(const double *__restrict__ P3, int cnt, Ctrl *ctrl) {
+    __shared__ double sm[16];
+    const double rr = reduce_partials(P3 + (1 * 2 + 0) * PGRID, cnt, sm);
+    if (threadIdx.x == 0) { ctrl->cnt[C_PCG_DONE] = 0; ctrl->cnt[C_PCG_IT] = 0; ctrl->val[V_RNORM] = sqrt(rr); }
 }
 // sums of the three local partial arrays of parity `par` -> out[0..3) (multi GPU: appended to the all-reduce payload)
 __global__ __launch_bounds__(256) void k_cgcg_pack3(const int *__restrict__ done, const double *__restrict__ P3, int par, int cnt, double *__restrict__ out) {

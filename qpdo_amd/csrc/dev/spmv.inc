@@ -84,13 +84,26 @@ static constexpr int SLAB_TPR = 16;     // lanes per row segment (16 x 16-byte l
 // alone -6 % per launch at the compact shapes, non-temporal index words +10 %, alone or together with the values.  The C4 solve does
 // not show the lab's gain -- back-to-back launches re-read nothing of the matrix from L2 either way -- and is 0.5 % slower with it:
 // off by default, docs/LAB_NOTES.md R7.)
+// VT (the value type of the stream): double reads vsm, 10 bytes per nonzero with 16-bit indices; float reads the fp32 copy vsm32 (16-bit
+// indices only), 6 bytes per nonzero: one lane trip is then a 16-byte load of FOUR values plus an 8-byte load of four indices, SLAB_UNR32
+// of them in flight -- 256 entries per trip of a lane group, so a C4 segment is still one trip.  Products and sums are in double for
+// both; everything else of the schedule (early loads, global_load_lds copy, prologue hook, dynamic rows, fixed-order row sums) is shared.
 typedef double slab_d2 __attribute__((ext_vector_type(2)));
-template <class Epi, bool I16, bool OVL, bool NT>
+typedef float slab_f4 __attribute__((ext_vector_type(4)));
+#define SLAB_UNR32 4             // fp32 stream: 16-byte value loads in flight per lane
+template <class VT> struct SlabStream;
+template <> struct SlabStream<double> { static constexpr int EPL = 2, UNR = SLAB_UNR; using Vec = double2; };      // EPL: entries per lane and load
+template <> struct SlabStream<float>  { static constexpr int EPL = 4, UNR = SLAB_UNR32; using Vec = float4; };
+template <class VT, class Epi, bool I16, bool OVL, bool NT>
 __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                     int rows_per_wg, const int2 *__restrict__ seg, const int *__restrict__ cism,
                                                     const unsigned short *__restrict__ i16sm,
-                                                    const double *__restrict__ vsm, const double *__restrict__ x, Epi epi) {
+                                                    const VT *__restrict__ vsm, const double *__restrict__ x, Epi epi) {
     constexpr int TPR = SLAB_TPR;
+    constexpr bool F32 = std::is_same<VT, float>::value;
+    static_assert(!F32 || I16, "the fp32 stream has 16-bit indices only");
+    constexpr int EPL = SlabStream<VT>::EPL, UNR = SlabStream<VT>::UNR;
+    using Vec = typename SlabStream<VT>::Vec;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double sm[32];
     __shared__ int next_row;
@@ -103,61 +116,77 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
     for (int r = tid; r < R; r += SLAB_THREADS) acc[r] = 0.0;
     const int lane = tid & (TPR - 1);
     constexpr int NG = SLAB_THREADS / TPR;              // lane groups per workgroup
-    constexpr int STEP = 2 * SLAB_UNR * TPR;            // entries per trip of a lane group
-    // 16-byte value loads and paired index loads from an even start (the element before an odd `beg` and the one after an
-    // odd end are masked): one instruction covers 2*TPR consecutive entries and SLAB_UNR of them are in flight per lane -- a
-    // C4 segment (~170 entries) is a single trip.  No scalar tail loop: slots past the end re-read the first pair and
-    // contribute exact zeros.  (Lab, tools/lab/slab_lab.hip, C4 shape: 8-byte loads x4: 5.8 TB/s; 16-byte x4: 6.2; x8: 6.9
+    constexpr int STEP = EPL * UNR * TPR;               // entries per trip of a lane group
+    // 16-byte value loads and the matching index loads from a start aligned to EPL entries (the elements before an unaligned
+    // `beg` and those after the end are masked): one instruction covers EPL*TPR consecutive entries and UNR of them are in flight
+    // per lane -- a C4 segment (~170 entries) is a single trip.  No scalar tail loop: slots past the end re-read the first load
+    // and contribute exact zeros.  (Lab, tools/lab/slab_lab.hip, C4 shape: 8-byte loads x4: 5.8 TB/s; 16-byte x4: 6.2; x8: 6.9
     // with the slab-major image, 6.2 without.)
-    // index words: a pair of 16-bit slab-local indices, or a pair of 32-bit ones; unpacked at the use, so that nothing waits for a
+    // index words: EPL 16-bit slab-local indices, or a pair of 32-bit ones; unpacked at the use, so that nothing waits for a
     // load in flight before the row's first trip is computed
-    using IdxW = typename std::conditional<I16, unsigned, int2>::type;
-    auto load_trip = [&](double2 *v, IdxW *w, int k, int kb, int end) {
+    using IdxW = typename std::conditional<F32, uint2, typename std::conditional<I16, unsigned, int2>::type>::type;
+    auto load_trip = [&](Vec *v, IdxW *w, int k, int kb, int end) {
 #pragma unroll
-        for (int u = 0; u < SLAB_UNR; u++) {
-            const int kk = k + u * 2 * TPR;
+        for (int u = 0; u < UNR; u++) {
+            const int kk = k + u * EPL * TPR;
             const int kc = kk < end ? kk : kb;
-            if constexpr (NT) {
-                const slab_d2 t = __builtin_nontemporal_load(reinterpret_cast<const slab_d2 *>(vsm + kc));
-                v[u] = make_double2(t.x, t.y);
-            } else v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
-            if constexpr (I16) w[u] = *reinterpret_cast<const unsigned *>(i16sm + kc);
-            else               w[u] = *reinterpret_cast<const int2 *>(cism + kc);
+            if constexpr (F32) {
+                if constexpr (NT) {
+                    const slab_f4 t = __builtin_nontemporal_load(reinterpret_cast<const slab_f4 *>(vsm + kc));
+                    v[u] = make_float4(t.x, t.y, t.z, t.w);
+                } else v[u] = *reinterpret_cast<const float4 *>(vsm + kc);
+                w[u] = *reinterpret_cast<const uint2 *>(i16sm + kc);
+            } else {
+                if constexpr (NT) {
+                    const slab_d2 t = __builtin_nontemporal_load(reinterpret_cast<const slab_d2 *>(vsm + kc));
+                    v[u] = make_double2(t.x, t.y);
+                } else v[u] = *reinterpret_cast<const double2 *>(vsm + kc);
+                if constexpr (I16) w[u] = *reinterpret_cast<const unsigned *>(i16sm + kc);
+                else               w[u] = *reinterpret_cast<const int2 *>(cism + kc);
+            }
         }
     };
     // OVL: the first trip of the group's prefetched row (pv, pw: written on every pass of the prefetch, so that they are live
     // only from there to the row's first trip -- the register allocator then gives them the registers of the streaming loop)
-    double2 pv[SLAB_UNR]; IdxW pw[SLAB_UNR];
+    Vec pv[UNR]; IdxW pw[UNR];
     int pr = -1, pbeg = 0, pend = 0;
     // row r's segment [beg, end) of the staged slab, added to acc[r]; PRE: the loads of the first trip are in pv / pw
     auto row_seg = [&](int r, int beg, int end, auto pre) {
         constexpr bool PRE = decltype(pre)::value;
-        const int kb = beg & ~1;
-        double sa[2 * SLAB_UNR];
+        const int kb = beg & ~(EPL - 1);
+        double sa[EPL * UNR];
 #pragma unroll
-        for (int u = 0; u < 2 * SLAB_UNR; u++) sa[u] = 0.0;
-        auto fma_trip = [&](const double2 *v, const IdxW *w, int k) {
+        for (int u = 0; u < EPL * UNR; u++) sa[u] = 0.0;
+        auto fma_trip = [&](const Vec *v, const IdxW *w, int k) {
 #pragma unroll
-            for (int u = 0; u < SLAB_UNR; u++) {
-                const int kk = k + u * 2 * TPR;
-                int ax, ay;
-                if constexpr (I16) { ax = (int)(w[u] & 0xffffu); ay = (int)(w[u] >> 16); }
-                else               { ax = w[u].x; ay = w[u].y; }
-                const double px = v[u].x * xs[ax], py = v[u].y * xs[ay];
-                sa[2 * u] += (kk >= beg && kk < end) ? px : 0.0;
-                sa[2 * u + 1] += (kk + 1 < end) ? py : 0.0;
+            for (int u = 0; u < UNR; u++) {
+                const int kk = k + u * EPL * TPR;
+                double vv[EPL]; int ax[EPL];
+                if constexpr (F32) {
+                    vv[0] = (double)v[u].x; vv[1] = (double)v[u].y; vv[2] = (double)v[u].z; vv[3] = (double)v[u].w;
+                    ax[0] = (int)(w[u].x & 0xffffu); ax[1] = (int)(w[u].x >> 16); ax[2] = (int)(w[u].y & 0xffffu); ax[3] = (int)(w[u].y >> 16);
+                } else {
+                    vv[0] = v[u].x; vv[1] = v[u].y;
+                    if constexpr (I16) { ax[0] = (int)(w[u] & 0xffffu); ax[1] = (int)(w[u] >> 16); }
+                    else               { ax[0] = w[u].x; ax[1] = w[u].y; }
+                }
+#pragma unroll
+                for (int e = 0; e < EPL; e++) {         // (kk + EPL - 1 >= beg always: kb > beg - EPL)
+                    const double pe = vv[e] * xs[ax[e]];
+                    sa[EPL * u + e] += ((e == EPL - 1 || kk + e >= beg) && kk + e < end) ? pe : 0.0;
+                }
             }
         };
-        int k = kb + 2 * lane;
+        int k = kb + EPL * lane;
         if (PRE && k < end) { fma_trip(pv, pw, k); k += STEP; }
         for (; k < end; k += STEP) {
-            double2 v[SLAB_UNR]; IdxW w[SLAB_UNR];
+            Vec v[UNR]; IdxW w[UNR];
             load_trip(v, w, k, kb, end);
             fma_trip(v, w, k);
         }
         double t = 0.0;
 #pragma unroll
-        for (int u = 0; u < SLAB_UNR; u++) t += sa[2 * u] + sa[2 * u + 1];
+        for (int u = 0; u < EPL * UNR / 2; u++) t += sa[2 * u] + sa[2 * u + 1];
 #pragma unroll
         for (int o = TPR / 2; o > 0; o >>= 1) t += __shfl_down(t, o, TPR);
         if (lane == 0) acc[r] += t;
@@ -166,14 +195,14 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
     // with s == nslabs too (no loads then): pv / pw are defined on every path around the slab loop.
     auto prefetch = [&](int s) {
 #pragma unroll
-        for (int u = 0; u < SLAB_UNR; u++) { pv[u] = make_double2(0.0, 0.0); pw[u] = IdxW{}; }
+        for (int u = 0; u < UNR; u++) { pv[u] = Vec{}; pw[u] = IdxW{}; }
         pr = -1;
         const int g = tid / TPR;
         if (s < nslabs && g < R && !epi.skip(row0 + g)) {
             const int2 sg = seg[(size_t)(row0 + g) * nslabs + s];
             pr = g; pbeg = sg.x; pend = sg.x + sg.y;
-            const int kb = pbeg & ~1;
-            if (kb + 2 * lane < pend) load_trip(pv, pw, kb + 2 * lane, kb, pend);
+            const int kb = pbeg & ~(EPL - 1);
+            if (kb + EPL * lane < pend) load_trip(pv, pw, kb + EPL * lane, kb, pend);
         }
     };
     if (OVL) prefetch(0);
@@ -218,86 +247,6 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
             row_seg(r, sg.x, sg.x + sg.y, std::false_type());
         }
         if (OVL) prefetch(s + 1);
-    }
-    __syncthreads();
-    for (int r = tid; r < R; r += SLAB_THREADS) epi.row(row0 + r, acc[r]);
-    epi.finish(sm);
-}
-// fp32-value variant for the inner solve of the Schur mode (opt-in, QPDO_PCG_INNER_F32=1): the inner system only defines
-// a preconditioner, so its matrix may be a rounded copy -- M32 = Dq + A32' D A32 is still SPD and differs from M by 1e-7
-// relative in the stiff subspace -- while every vector, every accumulation and the outer CG on the exact K stay fp64.
-// Streams 6 instead of 10 bytes per nonzero: 16-byte loads of 4 values + 8-byte loads of 4 indices, 4 in flight per lane.
-template <class Epi>
-__global__ __launch_bounds__(1024) void k_spmv_slab32(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
-                                                      int rows_per_wg, const int2 *__restrict__ seg, const unsigned short *__restrict__ i16sm,
-                                                      const float *__restrict__ vsm32, const double *__restrict__ x, Epi epi) {
-    constexpr int TPR = SLAB_TPR;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ double sm[32];
-    __shared__ int next_row;
-    if (done && *done) return;
-    double *xs = lds;
-    double *acc = lds + W;
-    const int tid = threadIdx.x;
-    const int row0 = blockIdx.x * rows_per_wg;
-    const int R = min(rows_per_wg, nrows - row0);
-    for (int r = tid; r < R; r += SLAB_THREADS) acc[r] = 0.0;
-    const int lane = tid & (TPR - 1);
-    for (int s = 0; s < nslabs; s++) {
-        const int c0 = s * W;
-        const int cw = min(W, ncols - c0);
-        __syncthreads();
-        {
-            const int pairs = cw >> 1;
-            const double2 *src = reinterpret_cast<const double2 *>(x + c0);
-            double2 *dst = reinterpret_cast<double2 *>(xs);
-            for (int i = tid; i < pairs; i += SLAB_THREADS) dst[i] = src[i];
-            if ((cw & 1) && tid == 0) xs[cw - 1] = x[c0 + cw - 1];
-            if (tid == 0) next_row = 0;
-        }
-        __syncthreads();
-        const int gw = (tid & 63) / TPR;
-        for (;;) {
-            int base = 0;
-            if ((tid & 63) == 0) base = atomicAdd(&next_row, 64 / TPR);
-            base = __shfl(base, 0, 64);
-            if (base >= R) break;
-            const int r = base + gw;
-            if (r >= R) continue;
-            const int row = row0 + r;
-            const int2 sg = seg[(size_t)row * nslabs + s];
-            const int beg = sg.x, end = sg.x + sg.y;
-            const int kb = beg & ~3;
-            double sa[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) sa[u] = 0.0;
-            for (int k = kb + 4 * lane; k < end; k += 16 * TPR) {
-                float4 v[4]; ushort4 a[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int kk = k + u * 4 * TPR;
-                    const int kc = kk < end ? kk : kb;
-                    v[u] = *reinterpret_cast<const float4 *>(vsm32 + kc);
-                    a[u] = *reinterpret_cast<const ushort4 *>(i16sm + kc);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int kk = k + u * 4 * TPR;
-                    const double p0 = (double)v[u].x * xs[a[u].x], p1 = (double)v[u].y * xs[a[u].y];
-                    const double p2 = (double)v[u].z * xs[a[u].z], p3 = (double)v[u].w * xs[a[u].w];
-                    sa[4 * u]     += (kk >= beg && kk < end) ? p0 : 0.0;
-                    sa[4 * u + 1] += (kk + 1 >= beg && kk + 1 < end) ? p1 : 0.0;
-                    sa[4 * u + 2] += (kk + 2 >= beg && kk + 2 < end) ? p2 : 0.0;
-                    sa[4 * u + 3] += (kk + 3 < end) ? p3 : 0.0;
-                }
-            }
-            double t = 0.0;
-#pragma unroll
-            for (int u = 0; u < 8; u++) t += sa[2 * u] + sa[2 * u + 1];
-#pragma unroll
-            for (int o = TPR / 2; o > 0; o >>= 1) t += __shfl_down(t, o, TPR);
-            if (lane == 0) acc[r] += t;
-        }
     }
     __syncthreads();
     for (int r = tid; r < R; r += SLAB_THREADS) epi.row(row0 + r, acc[r]);
@@ -558,23 +507,25 @@ static void launch_slab(QpdoDev *d, const DevCsr &M, Args... args) {
     d->st.spmv_calls++;
     d->st.spmv_bytes += (int64_t)M.alg_bytes();
 }
+// f32: the product streams the fp32 copy of the values (M.vsm32 and M.i16sm must exist: the callers check, schur_f32_ready)
 template <class Epi>
-static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done) {
-#define SLAB_GO(I16, OVL, NT) launch_slab<k_spmv_slab<Epi, I16, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, M.vsm, x, epi)
-#define SLAB_GO_NT(I16, OVL) do { if (M.slab_nt) SLAB_GO(I16, OVL, true); else SLAB_GO(I16, OVL, false); } while (0)
-    if (M.slab_ovl) { if (M.i16sm) SLAB_GO_NT(true, true); else SLAB_GO_NT(false, true); }
-    else            { if (M.i16sm) SLAB_GO_NT(true, false); else SLAB_GO_NT(false, false); }
+static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done, bool f32 = false) {
+#define SLAB_GO(VT, VSM, I16, OVL, NT) launch_slab<k_spmv_slab<VT, Epi, I16, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, VSM, x, epi)
+#define SLAB_GO_NT(VT, VSM, I16, OVL) do { if (M.slab_nt) SLAB_GO(VT, VSM, I16, OVL, true); else SLAB_GO(VT, VSM, I16, OVL, false); } while (0)
+    if (f32) {
+        if (M.slab_ovl) SLAB_GO_NT(float, (const float *)M.vsm32, true, true); else SLAB_GO_NT(float, (const float *)M.vsm32, true, false);
+        d->st.spmv_bytes -= (int64_t)(4.0 * (double)M.nnz);        // (launch_slab counted the fp64 stream)
+        return;
+    }
+    if (M.slab_ovl) { if (M.i16sm) SLAB_GO_NT(double, (const double *)M.vsm, true, true); else SLAB_GO_NT(double, (const double *)M.vsm, false, true); }
+    else            { if (M.i16sm) SLAB_GO_NT(double, (const double *)M.vsm, true, false); else SLAB_GO_NT(double, (const double *)M.vsm, false, false); }
 #undef SLAB_GO_NT
 #undef SLAB_GO
 }
-template <class Epi>
-static void launch_spmv_slab32(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done) {
-    launch_slab<k_spmv_slab32<Epi>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.i16sm, M.vsm32, x, epi);
-}
 // y = M x with the kernel M was set up for; done: the PCG's latch (the product is skipped once it is set), or nullptr
 template <class Epi>
-static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, bool partials, const int *done = nullptr) {
-    if (M.use_slab) { launch_spmv_slab(d, M, x, epi, done); return; }
+static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, bool partials, const int *done = nullptr, bool f32 = false) {
+    if (M.use_slab) { launch_spmv_slab(d, M, x, epi, done, f32); return; }
     const int g = spmv_grid(M, partials);
     DISPATCH_TPR(M, k_spmv, g, done, M.nrows, M.rp, M.ci, M.val, x, epi);
     d->st.spmv_calls++;

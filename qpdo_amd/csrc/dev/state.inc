@@ -35,8 +35,9 @@ struct DevCsr {
     // row stride (measured on C4: 6.4 -> 7.3 TB/s algorithmic).  seg[r*nslabs+s] = {start, length}; rebuilt lazily
     // (sm_dirty) after the values or the structure of the row-major arrays change.
     double *vsm = nullptr; unsigned short *i16sm = nullptr; int *cism = nullptr; int2 *seg = nullptr; mutable int sm_dirty = 1;
-    float *vsm32 = nullptr;           // optional fp32 copy of vsm (QPDO_PCG_INNER_F32: values of the Schur mode's inner preconditioner solve)
+    float *vsm32 = nullptr;           // optional fp32 copy of vsm (the stream of the Schur mode's inner CG: QPDO_PCG_INNER_REFINE, QPDO_PCG_INNER_F32)
     double alg_bytes() const { return 12.0 * (double)nnz + 4.0 * (nrows + 1) + 8.0 * nrows + 8.0 * ncols; }
+    double alg_bytes32() const { return alg_bytes() - 4.0 * (double)nnz; }       // the same product on the fp32 copy of the values
 };
 
 // Row partition of one large QP over G ranks (one process per GPU): every vector is replicated, only the
@@ -153,6 +154,9 @@ struct QpdoDev {
     Ctrl *ctrl2 = nullptr, *hctrl2 = nullptr; double *part2 = nullptr;
     double *s_x = nullptr, *s_r = nullptr, *s_z = nullptr, *s_p = nullptr, *s_Sp = nullptr, *s_diag = nullptr, *s_v = nullptr, *s_s = nullptr;
     int kg = 0;                                                           // row-partitioned Schur mode: global number of weighted rows (k-vectors stay partitioned)
+    // Schur mode, inner solve (host_pcg.inc schur_inner_solve).  inner_refine (QPDO_PCG_INNER_REFINE, default 1): the CG streams the fp32 copies
+    // and the solve is accepted on the residual formed with the fp64 matrices; inner_f32 (QPDO_PCG_INNER_F32=1): ONE fp32 CG solve, unverified
+    int inner_refine = 1, refine_maxsweep = 6; double refine_theta = 0.8; double *s_acc = nullptr, *s_sol = nullptr;
     int inner_f32 = 0; int inner_fold = 1 /* the inner CG's vector step inside its two products (QPDO_INNER_FOLD=0: k_cgcg_step) */; int schur_mode = -1 /* -1 auto, 0 off, 1 on */, schur_off = 0, schur_strikes = 0, last_jacobi_iters = 0, schur_last_inner = 0; long long schur_passes = 0;
     double *part = nullptr;  // P_COUNT * PGRID
     // scaling

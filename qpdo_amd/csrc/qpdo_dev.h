@@ -79,6 +79,10 @@ typedef struct {
     int64_t coupled_solves;     /* band solves with at least one weighted coupling row, accepted by their residual check */
     int64_t coupled_sweeps;     /* sweeps of those solves (each one band solve, the k x k correction and 3 SpMV) */
     int64_t coupled_rejects;    /* such solves that missed the residual check: the pass went to the band fallback */
+    int64_t inner_refine_sweeps;        /* Schur mode, refined inner solves: fp32 CG sweeps that converged and were followed by an fp64 residual */
+    int64_t inner_refine_fp64_applies;  /* applications of S' with the fp64 matrices that formed those residuals */
+    int64_t inner_refine_fallbacks;     /* inner solves redone by the fp64 CG (sweep cap reached, or a sweep that did not converge) */
+    double  inner_refine_max_res_over_tol; /* largest accepted ||b - S' s|| / (tau ||b||) of the last qpdo_solve: <= 1 */
 } QdevStats;
 
 int qdev_device_count(void);

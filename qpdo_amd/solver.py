@@ -98,7 +98,9 @@ class Stats(C.Structure):
                 ("pcg_rescues", C.c_long), ("pcg_rescue_kinds", C.c_long), ("hybrid_pcg_passes", C.c_long), ("band_fallbacks", C.c_long),
                 ("onelaunch_factors", C.c_long), ("ahead_steps", C.c_long), ("ahead_skips", C.c_long),
                 ("updown_solves", C.c_long), ("updown_rows", C.c_long), ("updown_rejects", C.c_long),
-                ("coupled_rows", C.c_long), ("coupled_solves", C.c_long), ("coupled_sweeps", C.c_long), ("coupled_rejects", C.c_long)]
+                ("coupled_rows", C.c_long), ("coupled_solves", C.c_long), ("coupled_sweeps", C.c_long), ("coupled_rejects", C.c_long),
+                ("inner_refine_sweeps", C.c_long), ("inner_refine_fp64_applies", C.c_long), ("inner_refine_fallbacks", C.c_long),
+                ("inner_refine_max_res_over_tol", C.c_double)]
 
 
 API_SYMBOLS = ["qpdo_set_default_settings", "qpdo_setup", "qpdo_warm_start", "qpdo_solve", "qpdo_update_settings",
@@ -539,6 +541,13 @@ class QPDO:
         return out, dict(kact=int(info[0]), iters=int(info[1]), defl_r=int(info[2]), schur=bool(info[3]), rnorm=float(info[4]),
                          bnorm=float(info[5]), inner_solves=int(info[6]), inner_steps=int(info[7]), outer=int(info[9]),
                          diag_from_build=bool(info[10]))
+
+    def pcg_f32_product(self, dw, which, v):
+        """one product of the slab kernel's fp32-stream instance after a fresh build of the compact matrices (qpdo_amd_pcg_probe, mode 32 / 33):
+        which = "Arc": A_c32 v (k values), "Atc": A_c32' v[:k] (n values); v has n entries.  Returns the product and k."""
+        out, info = self._pcg_probe(dw, 0.0, v, {"Arc": 32, "Atc": 33}[which])
+        k = int(info[0])
+        return (out[:k].copy() if which == "Arc" else out), k
 
     _COMPACT_VECS = {"rowlist": (49, np.int32, "k"), "cidx": (50, np.int32, "m"), "dc": (51, np.float64, "k"),
                      "flag_bits": (52, np.uint64, "words"), "flag_wprefix": (53, np.int32, "words"), "pc_diag": (54, np.float64, "n"),

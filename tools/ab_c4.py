@@ -1,6 +1,8 @@
 """A/B timing of builds of libqpdo_amd.so on one box: the C4 cold-start solve, alternating processes.
 usage: ab_c4.py libA.so libB.so [more sides ...] [reps]
 A side is a library, or VAR=VALUE,VAR=VALUE@library: that build with those environment switches (e.g. QPDO_INNER_FOLD=0@libqpdo_amd.so).
+Per solve: wall time, passes, status, linear-solver iterations, inner solves of the Schur mode and, for the refined inner solve
+(QPDO_PCG_INNER_REFINE), its sweeps, fallbacks and the largest accepted ||rho|| / (tau ||b||).
 With QPDO_SETUP_PROF=1 among them (or in the environment) the set-up's "[setup] ..." timing lines are printed under the side's line."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +15,9 @@ s = solver.QPDO().setup(p["Q"], p["q"], p["A"], p["l"], p["u"], Qstype=-1, verbo
 out = []
 for _ in range(2):
     t0 = time.time(); r = s.solve(); solver.lib().qpdo_amd_sync(s._w); dt = time.time() - t0
-    out.append(dict(t=dt, it=r["info"]["iterations"], st=r["info"]["status_val"], cg=s.stats()["lin_iters"]))
+    st = s.stats()
+    out.append(dict(t=dt, it=r["info"]["iterations"], st=r["info"]["status_val"], cg=st["lin_iters"], inner=st["inner_solves"],
+                    sweeps=st["inner_refine_sweeps"], fallbacks=st["inner_refine_fallbacks"], worst=round(st["inner_refine_max_res_over_tol"], 3)))
 print(json.dumps(out))
 """ % ROOT
 args = sys.argv[1:]
