@@ -165,6 +165,8 @@ typedef struct {
     long   inner_refine_fallbacks;    /* inner solves redone by the fp64 inner CG: QPDO_INNER_REFINE_MAXSWEEP sweeps (default 6) did not reach the
                                        * tolerance, or a sweep did not converge                                                                */
     double inner_refine_max_res_over_tol; /* largest ||b - S' s||_2 / (tau ||b||_2) an inner solve was accepted with, fp64 residual: <= 1        */
+    long   inner_x32_steps;           /* inner CG steps (inner_steps) whose two products staged fp32 copies of their operand vectors and streamed the
+                                       * column slabs in pairs (the default of the fp32 sweeps; QPDO_INNER_X32=0: none)                        */
 } QPDOAmdStats;
 
 int  qpdo_amd_device_count(void);
@@ -265,6 +267,9 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *           refined inner solve): mode 32 out[0 .. k) = A_c32 v, mode 33 out (n) = A_c32' v[0 .. k), A_c32 = the compact values rounded to float,
  *           products and sums in double.  info[0] = k.  Refused (-1) where the pass has no fp32 images: a compact matrix on the plain kernel
  *           or without 16-bit indices, QPDO_PCG_INNER_REFINE=0 without QPDO_PCG_INNER_F32=1, or k > n.
+ *   mode 34, 35  the same two products through the pair-wide instance that the fp32 inner CG runs by default: v is rounded to float as well
+ *           and the column slabs are streamed in pairs; products and sums in double (a float times a float is exact there).  Refused
+ *           (-1) as modes 32, 33 and under QPDO_INNER_X32=0.
  * Returns 0; QPDO_AMD_PCG_NOT_CONVERGED / QPDO_AMD_PCG_NAN for a solve of class 1 / 2 (out is not written, qpdo_amd_last_error carries the
  * solver's message); -1 on any other failure.  The workspace's weights, sigma, direction, right-hand side, stopping rule, Schur-mode
  * state and counters are put back: the next qpdo_solve runs as on a workspace that never saw the call.
@@ -288,7 +293,9 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *   which = 64 + 16 mat + part, mat 0 A_c, 1 A_c': the slab-major image that the slab kernel streams (count 0 where the matrix does not
  *   take the slab kernel):
  *     part 0  seg  int32 pairs, 2 nrows nslabs: seg[r nslabs + s] = {first position in the image, length} of row r's entries in slab s
- *          1  vsm  double nnz: the values, per workgroup the segments of slab 0 back to back, then those of slab 1, ...
+ *          1  vsm  double nnz: the values, per workgroup the segments of slab 0 back to back, then those of slab 1, ...; where the pair-wide
+ *                  products run on the matrix (mode 34, 35 available) in pair order instead: per workgroup the slab pairs (0, 1), (2, 3), ..., in a pair the
+ *                  rows, per row its segment of the even slab and then that of the odd one (adjacent), an odd last slab by rows
  *          2  the slab-local column indices in the same order: uint16 where ci16 is present, else int32 (ci - s W)
  *   96 (count 0, dst unused): marks both images stale and runs one product with each compact matrix that takes the slab kernel, so
  *      that the image is rebuilt from the CSR, sp and seg as after any change of the row-major arrays */

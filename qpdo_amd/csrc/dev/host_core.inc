@@ -96,6 +96,13 @@ static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, 
     M->sm_dirty = 1;
     return rc;
 }
+// QPDO_SLAB_MAX_W=<columns, a multiple of 64>: caps the slab width wherever one is computed (here, and for the per-pass compact matrices in
+// create_tail and build_compact), so that small problems reach several slabs (tests).  Unset: the LDS decides alone.
+static long long slab_cap_w(long long lds_doubles) {
+    const char *mw = getenv("QPDO_SLAB_MAX_W");
+    const long long cap = (mw && *mw) ? atoll(mw) : 0;
+    return (cap > 0 && cap % 64 == 0 && cap < lds_doubles) ? cap : lds_doubles;
+}
 static int setup_slabs(QpdoDev *d, DevCsr *M) {
     { const char *ov = getenv("QPDO_SLAB_OVERLAP"); M->slab_ovl = !(ov && *ov && atoi(ov) == 0); }
     { const char *nt = getenv("QPDO_SLAB_NT"); M->slab_nt = (nt && atoi(nt) != 0) ? 1 : 0; }
@@ -109,8 +116,9 @@ static int setup_slabs(QpdoDev *d, DevCsr *M) {
     const int NWG = 256;                                 // one workgroup per CU
     M->rows_per_wg = (M->nrows + NWG - 1) / NWG;
     M->slab_grid = (M->nrows + M->rows_per_wg - 1) / M->rows_per_wg;
-    const long long lds_doubles = (160 * 1024 - 1024) / 8 - M->rows_per_wg;
-    if (lds_doubles < 1024) return 0;
+    const long long lds_room = (160 * 1024 - 1024) / 8 - M->rows_per_wg;
+    if (lds_room < 1024) return 0;
+    const long long lds_doubles = slab_cap_w(lds_room);
     int nslabs = (int)((M->ncols + lds_doubles - 1) / lds_doubles);
     if (nslabs < 1) nslabs = 1;
     int W = (M->ncols + nslabs - 1) / nslabs;
@@ -133,7 +141,7 @@ static int setup_slabs(QpdoDev *d, DevCsr *M) {
     return 0;
 }
 static void slab_major_build(QpdoDev *d, const DevCsr &M) {
-    hipLaunchKernelGGL(k_slab_seg, dim3(M.slab_grid), dim3(1024), 0, d->stream, M.nrows, M.nslabs, M.rows_per_wg, (const int *)M.sp, M.seg);
+    hipLaunchKernelGGL(k_slab_seg, dim3(M.slab_grid), dim3(1024), 0, d->stream, M.nrows, M.nslabs, M.rows_per_wg, (const int *)M.sp, M.seg, M.seg_pairs);
     hipLaunchKernelGGL(k_slab_permute, dim3(2048), dim3(256), 0, d->stream, M.nrows, M.nslabs, M.W, (const int *)M.sp, (const int2 *)M.seg,
                        (const int *)M.ci, (const unsigned short *)M.ci16, (const double *)M.val, M.vsm, M.i16sm, M.cism, M.vsm32);
     M.sm_dirty = 0;

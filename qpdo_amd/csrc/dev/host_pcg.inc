@@ -31,7 +31,7 @@ static int build_compact(QpdoDev *d) {
         R.rows_per_wg = (k + 255) / 256; R.slab_grid = (k + R.rows_per_wg - 1) / R.rows_per_wg;
         // own slab width: k/256 rows per workgroup need less accumulator space than m/256, the x slice can be wider
         // (C4 late passes: 5 slabs of 20 k columns instead of 6 of 16.7 k)
-        const long long lds_doubles = (160 * 1024 - 1024) / 8 - R.rows_per_wg;
+        const long long lds_doubles = slab_cap_w((160 * 1024 - 1024) / 8 - R.rows_per_wg);
         int nslabs = (int)((n + lds_doubles - 1) / lds_doubles); if (nslabs < 1) nslabs = 1;
         int W = ((n + nslabs - 1) / nslabs + 63) & ~63;
         if (W > lds_doubles) { nslabs++; W = ((n + nslabs - 1) / nslabs + 63) & ~63; }
@@ -45,7 +45,7 @@ static int build_compact(QpdoDev *d) {
         // this pass can take the Schur mode on one GPU and k_schur_diag would run 64 lanes per row -- that mode's inner diagonal
         const bool diag = d->Ar.tpr == 64 && !d->comm.active && schur_allowed(d, k);
         LAUNCH(k_build_slab_ptr_rows, vgrid(k), k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const int *)R.rp, R.nslabs, R.W, R.sp);
-        hipLaunchKernelGGL(k_slab_seg, dim3(R.slab_grid), dim3(1024), 0, d->stream, R.nrows, R.nslabs, R.rows_per_wg, (const int *)R.sp, R.seg);
+        hipLaunchKernelGGL(k_slab_seg, dim3(R.slab_grid), dim3(1024), 0, d->stream, R.nrows, R.nslabs, R.rows_per_wg, (const int *)R.sp, R.seg, R.seg_pairs);
 #define COPY_ROWS_SLAB(DIAG) LAUNCH((k_copy_rows_slab<DIAG>), PASS_GRID, k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const unsigned short *)d->Ar.ci16, \
             d->Ar.val, (const int *)R.rp, R.ci, R.ci16, R.val, RW16, R.nslabs, R.W, (const int *)R.sp, (const int2 *)R.seg, R.vsm, R.i16sm, R.cism, \
             R.vsm32, (const double *)d->qdiag, d->sigma_f, (const double *)d->dc, d->s_diag)
@@ -84,7 +84,7 @@ static int build_compact(QpdoDev *d) {
         dev_scan(d, d->row_cnt, n, T.rp, T.rp + n, d->scan_tsum);
         if (spT) {
             LAUNCH(k_sp_add_rp, vgrid(n), n, T.nslabs, (const int *)T.rp, T.sp);
-            hipLaunchKernelGGL(k_slab_seg, dim3(T.slab_grid), dim3(1024), 0, d->stream, T.nrows, T.nslabs, T.rows_per_wg, (const int *)T.sp, T.seg);
+            hipLaunchKernelGGL(k_slab_seg, dim3(T.slab_grid), dim3(1024), 0, d->stream, T.nrows, T.nslabs, T.rows_per_wg, (const int *)T.sp, T.seg, T.seg_pairs);
         }
         hipLaunchKernelGGL(k_compact_rows_bits_slab, dim3(PASS_GRID), dim3(BLK), lds_tab, d->stream, n, M.rp, M.ci, M.val, (const u64 *)d->flag_bits,
                            (const int *)d->flag_wprefix, words, (const int *)T.rp, T.ci, T.val, W16, M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr,
@@ -234,16 +234,21 @@ static bool schur_f32_ready(const QpdoDev *d) {
 static bool schur_inner_f32(const QpdoDev *d) { return d->inner_f32 && schur_f32_ready(d); }
 // the default: the fp32 images only propose corrections, the solve is accepted on the fp64 residual (schur_inner_solve)
 static bool schur_inner_refine(const QpdoDev *d) { return d->inner_refine && !d->inner_f32 && schur_f32_ready(d); }
-// f32: both products stream the fp32 images (single GPU)
-static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const int *done2, bool sample, int *fcnt, bool f32) {
+// The fp32 inner CG stages fp32 copies of its two operand vectors and streams the column slabs in pairs (k_spmv_slab, XT = float;
+// QPDO_INNER_X32=0: fp64 operands, slab by slab).  The copies are written where the vectors are: u = s_z -> s_z32 (cgcg_elem, k_cgcg_init,
+// k_refine_init), t = tmp_n -> tmp_n32 (EpiDivDotSums, EpiDivDot).  Both schedules of the CG use the same width.
+static bool schur_x32(const QpdoDev *d) { return d->inner_x32 && d->s_z32 && d->tmp_n32 && d->Arc.seg_pairs && d->Atc.seg_pairs && schur_f32_ready(d); }
+// f32: both products stream the fp32 images (single GPU); x32: and stage the fp32 copies of their operands, u being s_z
+static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const int *done2, bool sample, int *fcnt, bool f32, bool x32 = false) {
     const bool dist = d->comm.active;
     const int n = d->n, kl = d->kact;
     double *Pf = d->part2 + 6 * PGRID;
     if (!dist) {
-        launch_spmv(d, d->Atc, u, EpiDivDot{d->pc_diag, d->tmp_n, Pf}, true, done2, f32);
+        const float *u32 = (f32 && x32) ? d->s_z32 : nullptr; float *t32 = (f32 && x32) ? d->tmp_n32 : nullptr;
+        launch_spmv_inner(d, d->Atc, u, u32, EpiDivDot{d->pc_diag, d->tmp_n, Pf, 0.0, t32}, true, done2, f32);
         // HIP-event sample of the dominant kernel (the A_c product), taken mid-batch by the caller's choice of `sample`
         if (sample) (void)hipEventRecord(d->ev0, d->stream);
-        launch_spmv(d, d->Arc, d->tmp_n, EpiSchurW{d->dc, u, w}, false, done2, f32);
+        launch_spmv_inner(d, d->Arc, d->tmp_n, t32, EpiSchurW{d->dc, u, w}, false, done2, f32);
         if (sample) (void)hipEventRecord(d->ev1, d->stream);
         *fcnt = spmv_pgrid(d->Atc);
         return 0;
@@ -274,12 +279,15 @@ static int schur_inner_cg(QpdoDev *d, double tol, bool f32, bool init, int first
     // j - 1 performs step j (EpiSchurStep), product 1 of application j forms that step's three partial sums first (EpiDivDotSums).
     // QPDO_INNER_FOLD=0 selects the three-launch schedule; both run the same device functions (pcg_kernels.inc) and give the same bits.
     const bool fold = d->inner_fold && !dist && (long long)g * BLK >= kl;
-    if (init) LAUNCH(k_cgcg_init, g, kl, (const double *)d->s_v, (const double *)d->s_diag, (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, P3, d->ctrl2);
+    // fp32 operands (schur_x32): u32, t32 are the copies that the step and product 1 write and the products stage; null otherwise
+    const bool x32 = f32 && schur_x32(d);
+    float *u32 = x32 ? d->s_z32 : nullptr, *t32 = x32 ? d->tmp_n32 : nullptr;
+    if (init) LAUNCH(k_cgcg_init, g, kl, (const double *)d->s_v, (const double *)d->s_diag, (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, P3, d->ctrl2, u32);
     int rc = 0;
     if (fold) {
-        launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, 0, d->s_r, d->s_z, d->dc, (double *)nullptr}, true, done2, f32);
+        launch_spmv_inner(d, d->Atc, d->s_z, u32, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, 0, d->s_r, d->s_z, d->dc, (double *)nullptr, 0.0, t32}, true, done2, f32);
         fcnt = spmv_pgrid(d->Atc);
-    } else { rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt, f32); if (rc) return -1; }
+    } else { rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt, f32, x32); if (rc) return -1; }
     int j = 0;
     int batch = first_batch;
     while (j < SCHUR_INNER_MAXIT) {
@@ -289,15 +297,16 @@ static int schur_inner_cg(QpdoDev *d, double tol, bool f32, bool init, int first
             if (fold) {
                 // (the HIP-event sample of the A_c product includes the step it performs; its byte count is that of the product)
                 if (sample) (void)hipEventRecord(d->ev0, d->stream);
-                launch_spmv(d, d->Arc, d->tmp_n, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol}, false, nullptr, f32);
+                launch_spmv_inner(d, d->Arc, d->tmp_n, t32, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol, nullptr, u32}, false, nullptr, f32);
                 if (sample) (void)hipEventRecord(d->ev1, d->stream);
-                launch_spmv(d, d->Atc, d->s_z, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3}, true, done2, f32);
+                launch_spmv_inner(d, d->Atc, d->s_z, u32, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3, 0.0, t32}, true, done2, f32);
             } else {
                 LAUNCH(k_cgcg_step, g, kl, j, d->ctrl2, glob3, P3, g, (const double *)Pf, fcnt, (const double *)d->s_Sp, (const double *)d->s_diag,
-                       (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol);
-                rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, sample, &fcnt, f32); if (rc) return -1;
+                       (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol, u32);
+                rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, sample, &fcnt, f32, x32); if (rc) return -1;
             }
             d->st.inner_steps++;
+            if (x32) d->st.inner_x32_steps++;
         }
         rc = read_ctrl2(d); if (rc) return rc;
         if (!dist && d->hctrl2->cnt[C_PCG_IT] > it_before + sample_b) {          // the sampled iteration of this batch really ran
@@ -348,7 +357,7 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
         int fcnt = 0;
         if (schur_S_apply(d, d->s_acc, d->s_Sp, 0, nullptr, false, &fcnt, false)) return -1;
         LAUNCH(k_refine_init, g, kl, (const double *)d->s_v, (const double *)d->s_Sp, (const double *)d->s_diag, (const double *)d->dc,
-               d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, d->part2);
+               d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, d->part2, schur_x32(d) ? d->s_z32 : (float *)nullptr);
         LAUNCH(k_refine_norm, 1, (const double *)d->part2, g, d->ctrl2);
         { const int rc = read_ctrl2(d); if (rc) return rc; }
         rho = d->hctrl2->val[V_RNORM];

@@ -175,7 +175,7 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
     HIPCHK(hipSetDevice(d->device));
     if (d->comm.active) return set_err(hipErrorInvalidValue, "pcg probe: not for row-partitioned workspaces", __LINE__);
     if (d->linsolve != 0) return set_err(hipErrorInvalidValue, "pcg probe: the workspace's solver is not PCG", __LINE__);
-    if (mode != 0 && mode != 1 && mode != 32 && mode != 33) return set_err(hipErrorInvalidValue, "pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product)", __LINE__);
+    if (mode != 0 && mode != 1 && (mode < 32 || mode > 35)) return set_err(hipErrorInvalidValue, "pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product), 34 or 35 (one pair-wide fp32 product)", __LINE__);
     const int n = d->n, m = d->m;
     std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1)), rhs_keep((size_t)(n > 0 ? n : 1));
     if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
@@ -205,15 +205,25 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
         if (!rc) HIPCHK(hipStreamSynchronize(d->stream));
         if (!rc) HIPCHK(hipGetLastError());
         info[0] = (double)d->kact; info[1] = (double)cnt;
-    } else if (mode == 32 || mode == 33) {
+    } else if (mode >= 32 && mode <= 35) {
         // the slab kernel's fp32-stream instances on their own: out[0 .. k) = A_c32 v (mode 32), out (n) = A_c32' v[0 .. k) (mode 33), A_c32 =
-        // the compact values rounded to float, products and sums in double
+        // the compact values rounded to float, products and sums in double.  Modes 34 / 35: the same two products by the pair-wide
+        // instance, v rounded to float as well (the copy is made on the host here; the solver writes it with the vector)
+        const bool x32 = mode >= 34;
+        if (x32) mode -= 2;
         rc = build_compact(d);
         const int k = d->kact;
         if (!rc && (!schur_f32_ready(d) || k > n)) rc = set_err(hipErrorInvalidValue, "pcg probe: this pass has no fp32 images (both compact matrices under the slab kernel with 16-bit indices, QPDO_PCG_INNER_REFINE or QPDO_PCG_INNER_F32 on, k <= n)", __LINE__);
+        if (!rc && x32 && !schur_x32(d)) rc = set_err(hipErrorInvalidValue, "pcg probe: this workspace has no fp32 operand vectors (QPDO_INNER_X32=0, or no fp32 images)", __LINE__);
+        if (!rc && x32) {
+            std::vector<float> v32((size_t)n);
+            for (int i = 0; i < n; i++) v32[(size_t)i] = (float)v[i];
+            HIPCHK(hipMemcpyAsync(mode == 32 ? d->tmp_n32 : d->s_z32, v32.data(), (size_t)(mode == 32 ? n : k) * sizeof(float), hipMemcpyHostToDevice, d->stream));
+            HIPCHK(hipStreamSynchronize(d->stream));
+        }
         if (!rc) {
-            if (mode == 32) launch_spmv(d, d->Arc, d->pc_p, EpiStore{d->tc}, false, nullptr, true);
-            else launch_spmv(d, d->Atc, d->pc_p, EpiStore{d->tmp_n}, false, nullptr, true);
+            if (mode == 32) launch_spmv_inner(d, d->Arc, d->pc_p, x32 ? d->tmp_n32 : (const float *)nullptr, EpiStore{d->tc}, false, nullptr, true);
+            else launch_spmv_inner(d, d->Atc, d->pc_p, x32 ? d->s_z32 : (const float *)nullptr, EpiStore{d->tmp_n}, false, nullptr, true);
             HIPCHK(hipMemcpyAsync(out, mode == 32 ? d->tc : d->tmp_n, (size_t)(mode == 32 ? k : n) * 8, hipMemcpyDeviceToHost, d->stream));
             HIPCHK(hipStreamSynchronize(d->stream));
             HIPCHK(hipGetLastError());

@@ -176,6 +176,7 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         { const char *th = getenv("QPDO_INNER_REFINE_THETA"); d->refine_theta = (th && atof(th) > 0 && atof(th) <= 1.0) ? atof(th) : 0.8; }
         const bool with_f32 = d->inner_f32 != 0 || d->inner_refine != 0;
         { const char *fo = getenv("QPDO_INNER_FOLD"); d->inner_fold = !(fo && *fo && atoi(fo) == 0); }
+        { const char *x3 = getenv("QPDO_INNER_X32"); d->inner_x32 = !(x3 && *x3 && atoi(x3) == 0); }
         { const char *co = getenv("QPDO_COMPACT_ONE_READ"); d->compact_one_read = !(co && *co && atoi(co) == 0); }
         { const char *ct = getenv("QPDO_COMPACT_T_ONE_READ"); d->compact_t_one_read = !(ct && *ct && atoi(ct) == 0); }
         rc = dev_alloc(d, &d->Arc.rp, (size_t)m + 1);
@@ -198,7 +199,10 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         if (!rc) rc = dev_alloc(d, &d->kcount, 4);
         if (!rc) rc = dev_alloc(d, &d->dc, (size_t)m);
         if (!rc) rc = dev_alloc(d, &d->tc, (size_t)m);
-        d->lds_doubles_At = (160 * 1024 - 1024) / 8 - d->At.rows_per_wg;
+        if (!rc && with_f32 && d->inner_x32) { rc = dev_alloc(d, &d->s_z32, (size_t)m + 4); if (!rc) rc = dev_alloc(d, &d->tmp_n32, (size_t)n + 4); }
+        // pair order only where the pair-wide products will run: the slab-by-slab products are slower on it (docs/LAB_NOTES.md)
+        d->Arc.seg_pairs = (d->Arc.vsm32 && d->s_z32 && d->tmp_n32) ? 1 : 0; d->Atc.seg_pairs = (d->Atc.vsm32 && d->s_z32 && d->tmp_n32) ? 1 : 0;
+        d->lds_doubles_At = (int)slab_cap_w((160 * 1024 - 1024) / 8 - d->At.rows_per_wg);
         if (!rc) rc = dev_alloc(d, &d->qdiag, (size_t)n);
         const char *df = getenv("QPDO_DEFLATE");
         d->deflate = !(df && !strcmp(df, "0"));

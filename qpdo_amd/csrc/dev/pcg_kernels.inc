@@ -122,8 +122,9 @@ __device__ __forceinline__ void cgcg_put3(double a, double c, double e, double *
     if (threadIdx.x == 0) { P3[(0 * 2 + par) * PGRID + blk] = a; P3[(1 * 2 + par) * PGRID + blk] = c; P3[(2 * 2 + par) * PGRID + blk] = e; }
 }
 // Element i of the step, operands in registers (the caller decides when they are loaded); leaves the new r_i, u_i in ri, un.
+// u32 (or null): the fp32 copy of u that the pair-wide fp32 product stages (spmv.inc, XT = float), written where u is.
 __device__ __forceinline__ void cgcg_elem(int i, double alpha, double beta, double ui, double wi, double pi0, double si0, double xi, double ri0, double dgi,
-                                          double *x, double *r, double *u, double *p, double *s, double &ri, double &un) {
+                                          double *x, double *r, double *u, double *p, double *s, double &ri, double &un, float *u32) {
     const double pi = ui + beta * pi0, si = wi + beta * si0;
     p[i] = pi; s[i] = si;
     x[i] = xi + alpha * pi;
@@ -131,6 +132,7 @@ __device__ __forceinline__ void cgcg_elem(int i, double alpha, double beta, doub
     r[i] = ri;
     un = ri / dgi;
     u[i] = un;
+    if (u32) u32[i] = (float)un;
 }
 // The scalar part of step j, run by every workgroup of the launch that performs it (its first 256 threads reduce; all threads get
 // the result).  false: no step -- an EARLIER launch has latched (the latch holds the index of the launch that set it, + 1), or the
@@ -172,12 +174,14 @@ __device__ __forceinline__ bool cgcg_scalars(int j, Ctrl *ctrl, const double *__
 }
 __global__ __launch_bounds__(256) void k_cgcg_init(int k, const double *__restrict__ b, const double *__restrict__ dg, const double *__restrict__ dc,
                                                    double *__restrict__ x, double *__restrict__ r, double *__restrict__ u, double *__restrict__ p,
-                                                   double *__restrict__ s, double *__restrict__ P3 /* slot 0 written */, Ctrl *ctrl) {
+                                                   double *__restrict__ s, double *__restrict__ P3 /* slot 0 written */, Ctrl *ctrl,
+                                                   float *__restrict__ u32 /* or null: cgcg_elem */) {
     __shared__ double sm[16];
     double a = 0.0, c = 0.0, e = 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
         const double bi = b[i], ui = bi / dg[i];
         x[i] = 0.0; r[i] = bi; u[i] = ui; p[i] = 0.0; s[i] = 0.0;
+        if (u32) u32[i] = (float)ui;
         double ta, tc, te;
         cgcg_sums(bi, ui, dc[i], ta, tc, te);
         a += ta; c += tc; e += te;
@@ -195,12 +199,14 @@ __global__ __launch_bounds__(256) void k_refine_acc(int k, int first, const doub
 // state of the sweep and the three partial sums of its step 0 in cgcg_put3's fixed order, (rho, rho) among them
 __global__ __launch_bounds__(256) void k_refine_init(int k, const double *__restrict__ b, const double *__restrict__ w, const double *__restrict__ dg,
                                                      const double *__restrict__ dc, double *__restrict__ x, double *__restrict__ r, double *__restrict__ u,
-                                                     double *__restrict__ p, double *__restrict__ s, double *__restrict__ P3 /* slot 0 written */) {
+                                                     double *__restrict__ p, double *__restrict__ s, double *__restrict__ P3 /* slot 0 written */,
+                                                     float *__restrict__ u32 /* or null: cgcg_elem */) {
     __shared__ double sm[16];
     double a = 0.0, c = 0.0, e = 0.0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < k; i += gridDim.x * blockDim.x) {
         const double bi = b[i] - w[i], ui = bi / dg[i];
         x[i] = 0.0; r[i] = bi; u[i] = ui; p[i] = 0.0; s[i] = 0.0;
+        if (u32) u32[i] = (float)ui;
         double ta, tc, te;
         cgcg_sums(bi, ui, dc[i], ta, tc, te);
         a += ta; c += tc; e += te;
@@ -225,7 +231,7 @@ __global__ __launch_bounds__(256) void k_cgcg_pack3(const int *__restrict__ done
 __global__ __launch_bounds__(256) void k_cgcg_step(int k, int j, Ctrl *ctrl, const double *__restrict__ glob3, double *__restrict__ P3, int pcnt,
                                                    const double *__restrict__ Pf, int fcnt, const double *__restrict__ w, const double *__restrict__ dg,
                                                    const double *__restrict__ dc, double *__restrict__ x, double *__restrict__ r, double *__restrict__ u,
-                                                   double *__restrict__ p, double *__restrict__ s, double tol) {
+                                                   double *__restrict__ p, double *__restrict__ s, double tol, float *__restrict__ u32) {
     __shared__ double sm[16];
     // The vector operands do not depend on the scalars: when the grid covers k with one element per thread (k <= PGRID * 256)
     // their loads are issued first and are in flight while the partial sums are re-reduced.
@@ -237,12 +243,12 @@ __global__ __launch_bounds__(256) void k_cgcg_step(int k, int j, Ctrl *ctrl, con
     if (!cgcg_scalars(j, ctrl, glob3, P3, pcnt, Pf, fcnt, tol, sm, alpha, beta)) return;
     double a = 0.0, c = 0.0, e = 0.0, ri, un;
     if (own) {
-        cgcg_elem(i, alpha, beta, ui, wi, pi0, si0, xi, ri0, dgi, x, r, u, p, s, ri, un);
+        cgcg_elem(i, alpha, beta, ui, wi, pi0, si0, xi, ri0, dgi, x, r, u, p, s, ri, un, u32);
         cgcg_sums(ri, un, dci, a, c, e);
     } else if (stride < k) {                                     // (not reached with vgrid(k) for k <= 262144; the fold is off beyond)
         for (int q = i; q < k; q += stride) {
             double ta, tc, te;
-            cgcg_elem(q, alpha, beta, u[q], w[q], p[q], s[q], x[q], r[q], dg[q], x, r, u, p, s, ri, un);
+            cgcg_elem(q, alpha, beta, u[q], w[q], p[q], s[q], x[q], r[q], dg[q], x, r, u, p, s, ri, un, u32);
             cgcg_sums(ri, un, dc[q], ta, tc, te);
             a += ta; c += tc; e += te;
         }
@@ -257,6 +263,7 @@ struct EpiDivDotSums {
     const double *w; double *out, *p_f;
     int k, np; const double *r, *u, *dc; double *P3;
     double acc = 0.0;
+    float *out32 = nullptr;                     // the fp32 copy of t for the pair-wide fp32 product that follows, or null
     __device__ bool skip(int) const { return false; }
     __device__ bool prologue(double *sm) {
         if (!P3) return true;
@@ -269,7 +276,7 @@ struct EpiDivDotSums {
         }
         return true;
     }
-    __device__ void row(int r_, double s) { const double t = s / w[r_]; out[r_] = t; acc += s * t; }
+    __device__ void row(int r_, double s) { const double t = s / w[r_]; out[r_] = t; if (out32) out32[r_] = (float)t; acc += s * t; }
     __device__ void finish(double *sm) {
         double t = block_sum(acc, sm);
         if (threadIdx.x == 0) p_f[blockIdx.x] = t;
@@ -283,6 +290,7 @@ struct EpiSchurStep {
     int j; Ctrl *ctrl; const double *P3; int pcnt; const double *Pf; int fcnt;
     const double *dg, *dc; double *x, *r, *u, *p, *s; double tol;
     const double *ab = nullptr;                 // alpha, beta in LDS
+    float *u32 = nullptr;                       // cgcg_elem
     __device__ bool skip(int) const { return false; }
     __device__ bool prologue(double *sm) {
         double alpha, beta;
@@ -295,7 +303,7 @@ struct EpiSchurStep {
     __device__ void row(int i, double acc) {
         const double ui = u[i], wi = ui / dc[i] + acc;
         double ri, un;
-        cgcg_elem(i, ab[0], ab[1], ui, wi, p[i], s[i], x[i], r[i], dg[i], x, r, u, p, s, ri, un);
+        cgcg_elem(i, ab[0], ab[1], ui, wi, p[i], s[i], x[i], r[i], dg[i], x, r, u, p, s, ri, un, u32);
     }
     __device__ void finish(double *) {}
 };

@@ -90,26 +90,38 @@ static constexpr int SLAB_TPR = 16;     // lanes per row segment (16 x 16-byte l
 // both; everything else of the schedule (early loads, global_load_lds copy, prologue hook, dynamic rows, fixed-order row sums) is shared.
 typedef double slab_d2 __attribute__((ext_vector_type(2)));
 typedef float slab_f4 __attribute__((ext_vector_type(4)));
+// XT (the type of the staged operand): double as above; float (only with VT = float, and only on an image in pair order, k_slab_seg)
+// reads an fp32 copy of x, so the LDS that holds W doubles holds the slices of TWO column slabs and the kernel walks slab PAIRS: a row's
+// two segments of a pair are adjacent in the image and are streamed as one segment, [beg, mid) of slab 2S and [mid, end) of slab 2S + 1
+// (a last single slab is a pair with an empty second half); an entry at or behind mid gathers xs[W + its slab-local index].  Half the
+// row hand-outs, seg loads and shuffle trees, half the slab boundaries and half the staging traffic of the slab-by-slab instance, and
+// no other matrix byte.  A float times a float is exact in double, so the product's own rounding is that of the sums alone, as before.
 #define SLAB_UNR32 4             // fp32 stream: 16-byte value loads in flight per lane
-template <class VT> struct SlabStream;
-template <> struct SlabStream<double> { static constexpr int EPL = 2, UNR = SLAB_UNR; using Vec = double2; };      // EPL: entries per lane and load
-template <> struct SlabStream<float>  { static constexpr int EPL = 4, UNR = SLAB_UNR32; using Vec = float4; };
-template <class VT, class Epi, bool I16, bool OVL, bool NT>
+#define SLAB_UNR32X 4            // fp32 stream with the fp32 operand: a C4 pair segment (330-400 entries) is two trips of 256 (measured on the C4 solve: 2, 6 and 8 in flight are 4-8 % slower, docs/LAB_NOTES.md)
+template <class VT, class XT> struct SlabStream;
+// EPL: entries per lane and load; NSA: partial sums per lane (entry EPL u + e of a trip goes to sum (EPL u + e) mod NSA)
+template <> struct SlabStream<double, double> { static constexpr int EPL = 2, UNR = SLAB_UNR, NSA = EPL * UNR; using Vec = double2; };
+template <> struct SlabStream<float, double>  { static constexpr int EPL = 4, UNR = SLAB_UNR32, NSA = EPL * UNR; using Vec = float4; };
+template <> struct SlabStream<float, float>   { static constexpr int EPL = 4, UNR = SLAB_UNR32X, NSA = 8; using Vec = float4; };     // (one sum per entry spills from 8 loads on)
+template <class VT, class XT, class Epi, bool I16, bool OVL, bool NT>
 __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                     int rows_per_wg, const int2 *__restrict__ seg, const int *__restrict__ cism,
                                                     const unsigned short *__restrict__ i16sm,
-                                                    const VT *__restrict__ vsm, const double *__restrict__ x, Epi epi) {
+                                                    const VT *__restrict__ vsm, const XT *__restrict__ x, Epi epi) {
     constexpr int TPR = SLAB_TPR;
-    constexpr bool F32 = std::is_same<VT, float>::value;
+    constexpr bool F32 = std::is_same<VT, float>::value, X32 = std::is_same<XT, float>::value;
     static_assert(!F32 || I16, "the fp32 stream has 16-bit indices only");
-    constexpr int EPL = SlabStream<VT>::EPL, UNR = SlabStream<VT>::UNR;
-    using Vec = typename SlabStream<VT>::Vec;
+    static_assert(!X32 || F32, "the fp32 operand goes with the fp32 stream only");
+    constexpr int EPL = SlabStream<VT, XT>::EPL, UNR = SlabStream<VT, XT>::UNR, NSA = SlabStream<VT, XT>::NSA;
+    static_assert((EPL * UNR) % NSA == 0 && NSA % 2 == 0, "the partial sums take the entries of a trip in turn");
+    using Vec = typename SlabStream<VT, XT>::Vec;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double sm[32];
     __shared__ int next_row;
     if (done && *done) return;
-    double *xs = lds;
+    XT *xs = reinterpret_cast<XT *>(lds);               // W doubles, or the 2 W floats of a slab pair
     double *acc = lds + W;
+    const int nsteps = X32 ? (nslabs + 1) >> 1 : nslabs, CW = X32 ? 2 * W : W;      // slabs, or slab pairs, and their columns
     const int tid = threadIdx.x;
     const int row0 = blockIdx.x * rows_per_wg;
     const int R = min(rows_per_wg, nrows - row0);
@@ -149,14 +161,25 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
     // OVL: the first trip of the group's prefetched row (pv, pw: written on every pass of the prefetch, so that they are live
     // only from there to the row's first trip -- the register allocator then gives them the registers of the streaming loop)
     Vec pv[UNR]; IdxW pw[UNR];
-    int pr = -1, pbeg = 0, pend = 0;
-    // row r's segment [beg, end) of the staged slab, added to acc[r]; PRE: the loads of the first trip are in pv / pw
-    auto row_seg = [&](int r, int beg, int end, auto pre) {
+    int pr = -1, pbeg = 0, pmid = 0, pend = 0;
+    // segment [beg, end) of `row` in step s: that of slab s, or the two adjacent ones of pair s with the second slab's entries from mid on
+    auto seg_of = [&](int row, int s, int &beg, int &mid, int &end) {
+        if constexpr (X32) {
+            const int2 a = seg[(size_t)row * nslabs + 2 * s];
+            const int lb = 2 * s + 1 < nslabs ? seg[(size_t)row * nslabs + 2 * s + 1].y : 0;
+            beg = a.x; mid = a.x + a.y; end = mid + lb;
+        } else {
+            const int2 a = seg[(size_t)row * nslabs + s];
+            beg = a.x; end = a.x + a.y; mid = end;
+        }
+    };
+    // row r's segment [beg, end) of the staged slab (pair), added to acc[r]; PRE: the loads of the first trip are in pv / pw
+    auto row_seg = [&](int r, int beg, int mid, int end, auto pre) {
         constexpr bool PRE = decltype(pre)::value;
         const int kb = beg & ~(EPL - 1);
-        double sa[EPL * UNR];
+        double sa[NSA];
 #pragma unroll
-        for (int u = 0; u < EPL * UNR; u++) sa[u] = 0.0;
+        for (int u = 0; u < NSA; u++) sa[u] = 0.0;
         auto fma_trip = [&](const Vec *v, const IdxW *w, int k) {
 #pragma unroll
             for (int u = 0; u < UNR; u++) {
@@ -172,8 +195,8 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
                 }
 #pragma unroll
                 for (int e = 0; e < EPL; e++) {         // (kk + EPL - 1 >= beg always: kb > beg - EPL)
-                    const double pe = vv[e] * xs[ax[e]];
-                    sa[EPL * u + e] += ((e == EPL - 1 || kk + e >= beg) && kk + e < end) ? pe : 0.0;
+                    const double pe = vv[e] * (double)xs[ax[e] + ((X32 && kk + e >= mid) ? W : 0)];
+                    sa[(EPL * u + e) % NSA] += ((e == EPL - 1 || kk + e >= beg) && kk + e < end) ? pe : 0.0;
                 }
             }
         };
@@ -186,7 +209,7 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
         }
         double t = 0.0;
 #pragma unroll
-        for (int u = 0; u < EPL * UNR / 2; u++) t += sa[2 * u] + sa[2 * u + 1];
+        for (int u = 0; u < NSA / 2; u++) t += sa[2 * u] + sa[2 * u + 1];
 #pragma unroll
         for (int o = TPR / 2; o > 0; o >>= 1) t += __shfl_down(t, o, TPR);
         if (lane == 0) acc[r] += t;
@@ -198,9 +221,9 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
         for (int u = 0; u < UNR; u++) { pv[u] = Vec{}; pw[u] = IdxW{}; }
         pr = -1;
         const int g = tid / TPR;
-        if (s < nslabs && g < R && !epi.skip(row0 + g)) {
-            const int2 sg = seg[(size_t)(row0 + g) * nslabs + s];
-            pr = g; pbeg = sg.x; pend = sg.x + sg.y;
+        if (s < nsteps && g < R && !epi.skip(row0 + g)) {
+            seg_of(row0 + g, s, pbeg, pmid, pend);
+            pr = g;
             const int kb = pbeg & ~(EPL - 1);
             if (kb + EPL * lane < pend) load_trip(pv, pw, kb + EPL * lane, kb, pend);
         }
@@ -208,27 +231,29 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
     if (OVL) prefetch(0);
     // (behind the first matrix loads: the hook's few KB from L2 and its barriers run while those are in flight)
     if (!epi_prologue(epi, sm, 0)) return;
-    for (int s = 0; s < nslabs; s++) {
-        const int c0 = s * W;
-        const int cw = min(W, ncols - c0);
+    for (int s = 0; s < nsteps; s++) {
+        const int c0 = s * CW;
+        const int cw = min(CW, ncols - c0);
         __syncthreads();
-        {   // stage x[c0 .. c0+cw) : 16-byte loads, then the odd tail
-            const int pairs = cw >> 1;
-            const double2 *src = reinterpret_cast<const double2 *>(x + c0);
-            double2 *dst = reinterpret_cast<double2 *>(xs);
+        {   // stage x[c0 .. c0+cw) : 16-byte loads, then the tail (one double, or up to three floats)
+            using V16 = typename std::conditional<X32, float4, double2>::type;
+            constexpr int E16 = 16 / (int)sizeof(XT);
+            const int vecs = cw / E16;
+            const V16 *src = reinterpret_cast<const V16 *>(x + c0);
+            V16 *dst = reinterpret_cast<V16 *>(xs);
             if (OVL) {      // global -> LDS without VGPRs: every copy of a lane in flight at once, not one L2 round trip each
-                for (int i = tid; i < pairs; i += SLAB_THREADS)
+                for (int i = tid; i < vecs; i += SLAB_THREADS)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + i),
                                                      (__attribute__((address_space(3))) void *)(dst + (i & ~63)), 16, 0, 0);
             } else {
-                for (int i = tid; i < pairs; i += SLAB_THREADS) dst[i] = src[i];
+                for (int i = tid; i < vecs; i += SLAB_THREADS) dst[i] = src[i];
             }
-            if ((cw & 1) && tid == 0) xs[cw - 1] = x[c0 + cw - 1];
+            if (tid < (cw & (E16 - 1))) { const int i = (cw & ~(E16 - 1)) + tid; xs[i] = x[c0 + i]; }
             if (tid == 0) next_row = OVL ? NG : 0;
             if (OVL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the copies have landed in LDS
         }
         __syncthreads();
-        if (OVL && pr >= 0) row_seg(pr, pbeg, pend, std::true_type());
+        if (OVL && pr >= 0) row_seg(pr, pbeg, pmid, pend, std::true_type());
         // Rows are handed out dynamically (LDS counter): with only a few row segments per lane group and slab a
         // static split leaves groups idle at the end-of-slab barrier.  One lane per WAVE grabs a batch of 64/TPR
         // rows and broadcasts it wave-wide, so the loop exit is wave-uniform (no divergent break around the
@@ -243,8 +268,9 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
             if (r >= R) continue;
             const int row = row0 + r;
             if (epi.skip(row)) continue;
-            const int2 sg = seg[(size_t)row * nslabs + s];
-            row_seg(r, sg.x, sg.x + sg.y, std::false_type());
+            int beg, mid, end;
+            seg_of(row, s, beg, mid, end);
+            row_seg(r, beg, mid, end, std::false_type());
         }
         if (OVL) prefetch(s + 1);
     }
@@ -291,23 +317,32 @@ __global__ void k_build_slab_ptr_rows(int k, const int *__restrict__ rowlist, co
     }
 }
 
-// slab-major order of the segments of one workgroup's rows: t = s*R + r; exclusive scan of the lengths
-__global__ __launch_bounds__(1024) void k_slab_seg(int nrows, int nslabs, int rows_per_wg, const int *__restrict__ sp, int2 *__restrict__ seg) {
+// slab-major order of the segments of one workgroup's rows: t = s*R + r; exclusive scan of the lengths.  pairs (DevCsr::seg_pairs: the
+// compact matrices whose fp32 copy is streamed with fp32 operands): pair-major, (pair S = s / 2, row r, parity s & 1), so that the two segments of a row in a slab pair are
+// adjacent -- seg[row][2S+1].x == seg[row][2S].x + seg[row][2S].y -- and the pair-wide product (k_spmv_slab, XT = float) streams them
+// as one; an odd last slab follows in (r) order.  The slab-by-slab products read seg[row][s] and take either order.
+__global__ __launch_bounds__(1024) void k_slab_seg(int nrows, int nslabs, int rows_per_wg, const int *__restrict__ sp, int2 *__restrict__ seg, int pairs) {
     __shared__ int sums[1024];
     const int row0 = blockIdx.x * rows_per_wg;
     const int R = min(rows_per_wg, nrows - row0);
     if (R <= 0) return;
     const int T = R * nslabs, chunk = (T + 1023) / 1024;
     const int t0 = min((int)threadIdx.x * chunk, T), t1 = min(t0 + chunk, T);
+    const int TP = 2 * R * (nslabs >> 1);               // pairs: the segments of the whole pairs come first
+    auto at = [&](int t, int &sl, int &r) {             // position t of the order -> (slab, row)
+        if (!pairs) { sl = t / R; r = t - sl * R; }
+        else if (t < TP) { const int S = t / (2 * R), u = t - 2 * R * S; r = u >> 1; sl = 2 * S + (u & 1); }
+        else { r = t - TP; sl = nslabs - 1; }
+    };
     int c = 0;
-    for (int t = t0; t < t1; t++) { const int sl = t / R, r = t - sl * R; const int *q = sp + (size_t)(row0 + r) * (nslabs + 1) + sl; c += q[1] - q[0]; }
+    for (int t = t0; t < t1; t++) { int sl, r; at(t, sl, r); const int *q = sp + (size_t)(row0 + r) * (nslabs + 1) + sl; c += q[1] - q[0]; }
     sums[threadIdx.x] = c;
     __syncthreads();
     if (threadIdx.x == 0) { int run = 0; for (int i = 0; i < 1024; i++) { const int v = sums[i]; sums[i] = run; run += v; } }
     __syncthreads();
     int pos = sp[(size_t)row0 * (nslabs + 1)] + sums[threadIdx.x];
     for (int t = t0; t < t1; t++) {
-        const int sl = t / R, r = t - sl * R; const int *q = sp + (size_t)(row0 + r) * (nslabs + 1) + sl;
+        int sl, r; at(t, sl, r); const int *q = sp + (size_t)(row0 + r) * (nslabs + 1) + sl;
         const int len = q[1] - q[0];
         seg[(size_t)(row0 + r) * nslabs + sl] = make_int2(pos, len);
         pos += len;
@@ -444,8 +479,9 @@ struct EpiPcgAt {                          // Kp += A' t ; partial p.Kp
 };
 struct EpiDivDot {                         // t = (M x) ./ w ; partial sum of (M x) .* t   (product 1 of the single-reduction inner CG)
     const double *w; double *out, *p_f; double acc = 0.0;
+    float *out32 = nullptr;                // the fp32 copy of t for the pair-wide fp32 product that follows (three-launch schedule), or null
     __device__ bool skip(int) const { return false; }
-    __device__ void row(int r, double s) { const double t = s / w[r]; out[r] = t; acc += s * t; }
+    __device__ void row(int r, double s) { const double t = s / w[r]; out[r] = t; if (out32) out32[r] = (float)t; acc += s * t; }
     __device__ void finish(double *sm) {
         double t = block_sum(acc, sm);
         if (threadIdx.x == 0) p_f[blockIdx.x] = t;
@@ -510,7 +546,7 @@ static void launch_slab(QpdoDev *d, const DevCsr &M, Args... args) {
 // f32: the product streams the fp32 copy of the values (M.vsm32 and M.i16sm must exist: the callers check, schur_f32_ready)
 template <class Epi>
 static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done, bool f32 = false) {
-#define SLAB_GO(VT, VSM, I16, OVL, NT) launch_slab<k_spmv_slab<VT, Epi, I16, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, VSM, x, epi)
+#define SLAB_GO(VT, VSM, I16, OVL, NT) launch_slab<k_spmv_slab<VT, double, Epi, I16, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, VSM, x, epi)
 #define SLAB_GO_NT(VT, VSM, I16, OVL) do { if (M.slab_nt) SLAB_GO(VT, VSM, I16, OVL, true); else SLAB_GO(VT, VSM, I16, OVL, false); } while (0)
     if (f32) {
         if (M.slab_ovl) SLAB_GO_NT(float, (const float *)M.vsm32, true, true); else SLAB_GO_NT(float, (const float *)M.vsm32, true, false);
@@ -522,6 +558,16 @@ static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi e
 #undef SLAB_GO_NT
 #undef SLAB_GO
 }
+// The pair-wide fp32 product: fp32 copy of the values, fp32 copy x32 of the operand.  M takes the slab kernel, carries vsm32 and i16sm
+// (schur_f32_ready) and its image is in pair order (DevCsr::seg_pairs, k_slab_seg).
+template <class Epi>
+static void launch_spmv_x32(QpdoDev *d, const DevCsr &M, const float *x32, Epi epi, const int *done) {
+#define SLAB_GO(OVL, NT) launch_slab<k_spmv_slab<float, float, Epi, true, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, (const float *)M.vsm32, x32, epi)
+    if (M.slab_ovl) { if (M.slab_nt) SLAB_GO(true, true); else SLAB_GO(true, false); }
+    else            { if (M.slab_nt) SLAB_GO(false, true); else SLAB_GO(false, false); }
+#undef SLAB_GO
+    d->st.spmv_bytes -= (int64_t)(4.0 * (double)M.nnz);            // (launch_slab counted the fp64 stream)
+}
 // y = M x with the kernel M was set up for; done: the PCG's latch (the product is skipped once it is set), or nullptr
 template <class Epi>
 static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, bool partials, const int *done = nullptr, bool f32 = false) {
@@ -530,6 +576,11 @@ static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, b
     DISPATCH_TPR(M, k_spmv, g, done, M.nrows, M.rp, M.ci, M.val, x, epi);
     d->st.spmv_calls++;
     d->st.spmv_bytes += (int64_t)M.alg_bytes();
+}
+// One product of the Schur mode's fp32 inner CG (f32): pair-wide with the fp32 copy x32 of x where there is one, otherwise slab by slab with x.
+template <class Epi>
+static void launch_spmv_inner(QpdoDev *d, const DevCsr &M, const double *x, const float *x32, Epi epi, bool partials, const int *done, bool f32) {
+    if (f32 && x32) launch_spmv_x32(d, M, x32, epi, done); else launch_spmv(d, M, x, epi, partials, done, f32);
 }
 
 // Two independent products in ONE launch (small problems: a launch is ~4-5 us whatever it computes, and Q dx and A dx of a Newton step

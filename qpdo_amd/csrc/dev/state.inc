@@ -35,6 +35,7 @@ struct DevCsr {
     // row stride (measured on C4: 6.4 -> 7.3 TB/s algorithmic).  seg[r*nslabs+s] = {start, length}; rebuilt lazily
     // (sm_dirty) after the values or the structure of the row-major arrays change.
     double *vsm = nullptr; unsigned short *i16sm = nullptr; int *cism = nullptr; int2 *seg = nullptr; mutable int sm_dirty = 1;
+    int seg_pairs = 0;                // the image is in pair order (k_slab_seg): the compact matrices of a workspace whose fp32 CG stages fp32 operands
     float *vsm32 = nullptr;           // optional fp32 copy of vsm (the stream of the Schur mode's inner CG: QPDO_PCG_INNER_REFINE, QPDO_PCG_INNER_F32)
     double alg_bytes() const { return 12.0 * (double)nnz + 4.0 * (nrows + 1) + 8.0 * nrows + 8.0 * ncols; }
     double alg_bytes32() const { return alg_bytes() - 4.0 * (double)nnz; }       // the same product on the fp32 copy of the values
@@ -157,6 +158,9 @@ struct QpdoDev {
     // Schur mode, inner solve (host_pcg.inc schur_inner_solve).  inner_refine (QPDO_PCG_INNER_REFINE, default 1): the CG streams the fp32 copies
     // and the solve is accepted on the residual formed with the fp64 matrices; inner_f32 (QPDO_PCG_INNER_F32=1): ONE fp32 CG solve, unverified
     int inner_refine = 1, refine_maxsweep = 6; double refine_theta = 0.8; double *s_acc = nullptr, *s_sol = nullptr;
+    // inner_x32 (QPDO_INNER_X32, default 1): the fp32 CG also stages fp32 copies of its operand vectors (s_z32 of s_z, tmp_n32 of tmp_n) and
+    // walks the column slabs in pairs (spmv.inc, XT = float); 0: fp64 operands, slab by slab
+    int inner_x32 = 1; float *s_z32 = nullptr, *tmp_n32 = nullptr;
     int inner_f32 = 0; int inner_fold = 1 /* the inner CG's vector step inside its two products (QPDO_INNER_FOLD=0: k_cgcg_step) */; int schur_mode = -1 /* -1 auto, 0 off, 1 on */, schur_off = 0, schur_strikes = 0, last_jacobi_iters = 0, schur_last_inner = 0; long long schur_passes = 0;
     double *part = nullptr;  // P_COUNT * PGRID
     // scaling

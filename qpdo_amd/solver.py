@@ -100,7 +100,7 @@ class Stats(C.Structure):
                 ("updown_solves", C.c_long), ("updown_rows", C.c_long), ("updown_rejects", C.c_long),
                 ("coupled_rows", C.c_long), ("coupled_solves", C.c_long), ("coupled_sweeps", C.c_long), ("coupled_rejects", C.c_long),
                 ("inner_refine_sweeps", C.c_long), ("inner_refine_fp64_applies", C.c_long), ("inner_refine_fallbacks", C.c_long),
-                ("inner_refine_max_res_over_tol", C.c_double)]
+                ("inner_refine_max_res_over_tol", C.c_double), ("inner_x32_steps", C.c_long)]
 
 
 API_SYMBOLS = ["qpdo_set_default_settings", "qpdo_setup", "qpdo_warm_start", "qpdo_solve", "qpdo_update_settings",
@@ -542,10 +542,11 @@ class QPDO:
                          bnorm=float(info[5]), inner_solves=int(info[6]), inner_steps=int(info[7]), outer=int(info[9]),
                          diag_from_build=bool(info[10]))
 
-    def pcg_f32_product(self, dw, which, v):
+    def pcg_f32_product(self, dw, which, v, x32=False):
         """one product of the slab kernel's fp32-stream instance after a fresh build of the compact matrices (qpdo_amd_pcg_probe, mode 32 / 33):
-        which = "Arc": A_c32 v (k values), "Atc": A_c32' v[:k] (n values); v has n entries.  Returns the product and k."""
-        out, info = self._pcg_probe(dw, 0.0, v, {"Arc": 32, "Atc": 33}[which])
+        which = "Arc": A_c32 v (k values), "Atc": A_c32' v[:k] (n values); v has n entries.  x32: the pair-wide instance with v rounded
+        to float32 as well (mode 34 / 35).  Returns the product and k."""
+        out, info = self._pcg_probe(dw, 0.0, v, {"Arc": 32, "Atc": 33}[which] + (2 if x32 else 0))
         k = int(info[0])
         return (out[:k].copy() if which == "Arc" else out), k
 
