@@ -73,6 +73,11 @@
  *                    accepted after QPDO_INNER_REFINE_MAXSWEEP sweeps (default 6) is redone by the fp64 inner CG (QPDOAmdStats.inner_refine_*).
  *                    QPDO_INNER_REFINE_THETA (default 0.8): a sweep's CG runs to a recursive residual of theta tau ||b|| (cost knob).
  *                    "0": the fp64 inner CG.  Row-partitioned solves always take the fp64 inner CG
+ *   QPDO_INNER_H16   "0": no coarse sweeps.  Default (with the refined inner solve and QPDO_INNER_X32 on): the first QPDO_INNER_H16_MAXSWEEP
+ *                    sweeps (default 2) of a refined inner solve stream HALF-PRECISION copies of the compact matrix values, scaled by one power
+ *                    of two per workspace (4 bytes per nonzero; +2 bytes per nonzero of A and A' of device memory), and stop at a recursive
+ *                    residual of max(theta tau ||b||, QPDO_INNER_H16_ETA ||rho||) (default 1e-3); the sweeps behind them are the fp32 sweeps.
+ *                    Acceptance is unchanged: after every sweep, on the residual of the fp64 matrices (QPDOAmdStats.inner_h16_*)
  *   QPDO_PCG_INNER_F32  "1": ONE inner CG solve on the fp32 copies, accepted on its own recursive residual -- nothing checks what the rounded
  *                    matrices did to it (opt-in, default off, never the measured configuration; overrides QPDO_PCG_INNER_REFINE); vectors,
  *                    accumulation and the outer CG on the exact K stay fp64
@@ -166,7 +171,11 @@ typedef struct {
                                        * tolerance, or a sweep did not converge                                                                */
     double inner_refine_max_res_over_tol; /* largest ||b - S' s||_2 / (tau ||b||_2) an inner solve was accepted with, fp64 residual: <= 1        */
     long   inner_x32_steps;           /* inner CG steps (inner_steps) whose two products staged fp32 copies of their operand vectors and streamed the
-                                       * column slabs in pairs (the default of the fp32 sweeps; QPDO_INNER_X32=0: none)                        */
+                                       * column slabs in pairs (the default of the narrow sweeps, coarse ones included; QPDO_INNER_X32=0: none) */
+    long   inner_h16_steps;           /* inner CG steps of COARSE sweeps: both products streamed the half-precision copies of the compact matrix
+                                       * values (4 bytes per nonzero; QPDO_INNER_H16=0 or QPDO_INNER_X32=0: none)                              */
+    long   inner_h16_sweeps;          /* coarse sweeps among inner_refine_sweeps: the first QPDO_INNER_H16_MAXSWEEP (default 2) sweeps of a refined
+                                       * inner solve, each stopped at max(theta tau ||b||, QPDO_INNER_H16_ETA ||rho||) (default 1e-3)          */
 } QPDOAmdStats;
 
 int  qpdo_amd_device_count(void);
@@ -270,6 +279,10 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *   mode 34, 35  the same two products through the pair-wide instance that the fp32 inner CG runs by default: v is rounded to float as well
  *           and the column slabs are streamed in pairs; products and sums in double (a float times a float is exact there).  Refused
  *           (-1) as modes 32, 33 and under QPDO_INNER_X32=0.
+ *   mode 36, 37  the same two products through the pair-wide HALF-PRECISION instance that the coarse sweeps of the refined inner solve run:
+ *           the values are those of the half-precision image -- (half)(float)(a 2^e), one power of two per workspace with max |a_ij| 2^e in
+ *           [2^14, 2^15) -- v is rounded to float, products and sums in double, the row sums times 2^-e.  info[0] = k, info[1] = e.  Refused
+ *           (-1) as modes 34, 35, under QPDO_INNER_H16=0 and where max |a_ij| is 0 or not finite.
  * Returns 0; QPDO_AMD_PCG_NOT_CONVERGED / QPDO_AMD_PCG_NAN for a solve of class 1 / 2 (out is not written, qpdo_amd_last_error carries the
  * solver's message); -1 on any other failure.  The workspace's weights, sigma, direction, right-hand side, stopping rule, Schur-mode
  * state and counters are put back: the next qpdo_solve runs as on a workspace that never saw the call.
@@ -288,6 +301,7 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *      sigma; deflated: the remainder without the heavy rows, floored)      55 s_diag double k: Schur mode, 1 / dw_i + sum_j A_ij^2 / pc_diag_j
  *   56 defl_list int32 (deflated rows): their compact row numbers      57 defl_Sinv double 256 x 256, row stride 256: the inverse of
  *      S = D_h^-1 + A_h P^-1 A_h' in its leading block
+ *   59 int64 2: [1 where the images of A_c and A_c' carry half-precision values (mode 36, 37 available), else 0; the exponent e of their scale]
  *   60 ls_idx uint32 2 m: the breakpoint indices in the order the last linesearch's radix sort left them (2 m > 8192, or QPDO_LS_SMALL=0;
  *      candidates first, by ratio, ties by index)
  *   which = 64 + 16 mat + part, mat 0 A_c, 1 A_c': the slab-major image that the slab kernel streams (count 0 where the matrix does not
@@ -297,6 +311,7 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *                  products run on the matrix (mode 34, 35 available) in pair order instead: per workgroup the slab pairs (0, 1), (2, 3), ..., in a pair the
  *                  rows, per row its segment of the even slab and then that of the odd one (adjacent), an odd last slab by rows
  *          2  the slab-local column indices in the same order: uint16 where ci16 is present, else int32 (ci - s W)
+ *          3  vsm16  IEEE half nnz: (half)(float)(vsm 2^e) in the same order, the stream of the coarse sweeps (count 0 where which 59 says 0)
  *   96 (count 0, dst unused): marks both images stale and runs one product with each compact matrix that takes the slab kernel, so
  *      that the image is rebuilt from the CSR, sp and seg as after any change of the row-major arrays */
 #define QPDO_AMD_PCG_NOT_CONVERGED (-3)

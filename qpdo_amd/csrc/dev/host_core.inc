@@ -81,16 +81,20 @@ static int upload_csr(QpdoDev *d, DevCsr *M, const QdevCsr *h) {
 static int read_ctrl(QpdoDev *d);
 // decide whether M streams from HBM (then use the LDS-staged kernel) and build its slab pointers
 // arrays of the slab-major image (two padding entries: the 16-byte loads may touch one element past a segment)
-static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, bool with_f32 = false) {
-    const size_t PAD = 4;       // the vector loads may touch up to three elements past a segment
+static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, bool with_f32 = false, bool with_h16 = false) {
+    // the vector loads start at a multiple of their entry count (2, 4; 8 for the half-precision stream, which reads eight values and eight
+    // 16-bit indices per load) below the segment's end: up to seven elements past it
+    const size_t PAD = 8;
     int rc = dev_alloc(d, &M->vsm, nnz_cap + PAD);
     if (!rc) rc = M->ci16 ? dev_alloc(d, &M->i16sm, nnz_cap + PAD) : dev_alloc(d, &M->cism, nnz_cap + PAD);
     if (!rc && with_f32 && M->ci16) rc = dev_alloc(d, &M->vsm32, nnz_cap + PAD);
+    if (!rc && with_h16 && M->vsm32) rc = dev_alloc(d, &M->vsm16, nnz_cap + PAD);
     if (!rc) rc = dev_alloc(d, &M->seg, nseg > 0 ? nseg : 1);
     if (!rc) {
         hipError_t e = hipMemsetAsync(M->vsm + nnz_cap, 0, PAD * sizeof(double), d->stream);
         if (e == hipSuccess) e = M->i16sm ? hipMemsetAsync(M->i16sm + nnz_cap, 0, PAD * sizeof(unsigned short), d->stream) : hipMemsetAsync(M->cism + nnz_cap, 0, PAD * sizeof(int), d->stream);
         if (e == hipSuccess && M->vsm32) e = hipMemsetAsync(M->vsm32 + nnz_cap, 0, PAD * sizeof(float), d->stream);
+        if (e == hipSuccess && M->vsm16) e = hipMemsetAsync(M->vsm16 + nnz_cap, 0, PAD * sizeof(_Float16), d->stream);
         if (e != hipSuccess) rc = set_err(e, "hipMemsetAsync", __LINE__);
     }
     M->sm_dirty = 1;
@@ -140,10 +144,13 @@ static int setup_slabs(QpdoDev *d, DevCsr *M) {
     if (M->use_slab) { rc = slab_major_alloc(d, M, (size_t)M->nnz, (size_t)M->nrows * nslabs); if (rc) return rc; }
     return 0;
 }
+// where the builders of M's image write its half-precision values: nowhere while the workspace has no scale (h16_refresh_scale)
+static inline _Float16 *h16_dst(const QpdoDev *d, const DevCsr &M) { return d->h16_set ? M.vsm16 : (_Float16 *)nullptr; }
 static void slab_major_build(QpdoDev *d, const DevCsr &M) {
     hipLaunchKernelGGL(k_slab_seg, dim3(M.slab_grid), dim3(1024), 0, d->stream, M.nrows, M.nslabs, M.rows_per_wg, (const int *)M.sp, M.seg, M.seg_pairs);
     hipLaunchKernelGGL(k_slab_permute, dim3(2048), dim3(256), 0, d->stream, M.nrows, M.nslabs, M.W, (const int *)M.sp, (const int2 *)M.seg,
-                       (const int *)M.ci, (const unsigned short *)M.ci16, (const double *)M.val, M.vsm, M.i16sm, M.cism, M.vsm32);
+                       (const int *)M.ci, (const unsigned short *)M.ci16, (const double *)M.val, M.vsm, M.i16sm, M.cism, M.vsm32,
+                       h16_dst(d, M), d->h16_scale);
     M.sm_dirty = 0;
 }
 // Read-back of a control block.  A pass of the multi-kernel routes makes 1-3 of these and, at mid-size orders, they are a tenth of its time:
@@ -191,6 +198,22 @@ static inline double nrm_of(const Ctrl *c, int slot) {
     double v; u64 b = c->nrm[slot]; memcpy(&v, &b, 8); return v;
 }
 #define LAUNCH(kernel, grid, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLK), 0, d->stream, __VA_ARGS__)
+// The scale of the half-precision images: 2^e with max |a_ij| 2^e in [2^14, 2^15), the maximum over A as the workspace holds it (the compact
+// rows are a subset of its rows; A' has the same entries).  Called where A's values are set; one read of A and one host read.  A maximum
+// of 0, inf or NaN leaves the coarse sweeps off.  No-op for a workspace without half-precision images.
+static int h16_refresh_scale(QpdoDev *d) {
+    d->h16_set = 0; d->h16_e = 0; d->h16_scale = 0.0;
+    if (!d->Arc.vsm16 || !d->Atc.vsm16 || d->Ar.nnz <= 0 || d->Ar.nnz > 0x7fffffffLL) return 0;
+    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
+    LAUNCH(k_absmax_mul, 2048, (int)d->Ar.nnz, (const double *)d->Ar.val, (const double *)nullptr, d->ctrl, N_A);
+    int rc = read_ctrl(d); if (rc) return rc;
+    const double amax = nrm_of(d->hctrl, N_A);
+    if (!(amax > 0.0) || !(amax <= 1.7976931348623157e308)) return 0;
+    int ex = 0; (void)frexp(amax, &ex);               // amax = f 2^ex, f in [0.5, 1): amax 2^(15 - ex) in [2^14, 2^15)
+    d->h16_e = 15 - ex; d->h16_scale = ldexp(1.0, d->h16_e); d->h16_set = 1;
+    d->Arc.sm_dirty = d->Atc.sm_dirty = 1;
+    return 0;
+}
 // ---- the integer scan and the sorting pass (dev/scan_sort.inc) ----------------------------------------------------------------------
 // exclusive scan of cnt[0 .. n) into out[0 .. n) (cnt == out: in place), the total into *total (or nowhere): tile sums, then every tile's
 // own scan behind the sums in front of it.  tsum: scratch of scan_tiles(n) ints (a pass: d->scan_tsum; the set-up: its TempAllocs)

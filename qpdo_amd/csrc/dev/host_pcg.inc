@@ -48,7 +48,7 @@ static int build_compact(QpdoDev *d) {
         hipLaunchKernelGGL(k_slab_seg, dim3(R.slab_grid), dim3(1024), 0, d->stream, R.nrows, R.nslabs, R.rows_per_wg, (const int *)R.sp, R.seg, R.seg_pairs);
 #define COPY_ROWS_SLAB(DIAG) LAUNCH((k_copy_rows_slab<DIAG>), PASS_GRID, k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const unsigned short *)d->Ar.ci16, \
             d->Ar.val, (const int *)R.rp, R.ci, R.ci16, R.val, RW16, R.nslabs, R.W, (const int *)R.sp, (const int2 *)R.seg, R.vsm, R.i16sm, R.cism, \
-            R.vsm32, (const double *)d->qdiag, d->sigma_f, (const double *)d->dc, d->s_diag)
+            R.vsm32, h16_dst(d, R), d->h16_scale, (const double *)d->qdiag, d->sigma_f, (const double *)d->dc, d->s_diag)
         if (diag) { COPY_ROWS_SLAB(true); d->sdiag_valid = 1; d->sdiag_sigma = d->sigma_f; } else COPY_ROWS_SLAB(false);
 #undef COPY_ROWS_SLAB
     } else {
@@ -88,7 +88,7 @@ static int build_compact(QpdoDev *d) {
         }
         hipLaunchKernelGGL(k_compact_rows_bits_slab, dim3(PASS_GRID), dim3(BLK), lds_tab, d->stream, n, M.rp, M.ci, M.val, (const u64 *)d->flag_bits,
                            (const int *)d->flag_wprefix, words, (const int *)T.rp, T.ci, T.val, W16, M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr,
-                           T.nslabs, T.W, (const int *)spT, (const int2 *)T.seg, T.vsm, T.i16sm, T.cism, T.vsm32);
+                           T.nslabs, T.W, (const int *)spT, (const int2 *)T.seg, T.vsm, T.i16sm, T.cism, T.vsm32, h16_dst(d, T), d->h16_scale);
     } else if (lds_tab <= 60 * 1024) {          // flags and renumbering as LDS tables: the kernels stream the matrix only
         DISPATCH_TPR_LDS(M, k_count_flagged_bits, g, (size_t)words * 8, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt);
         dev_scan(d, d->row_cnt, n, T.rp, T.rp + n, d->scan_tsum);
@@ -238,17 +238,21 @@ static bool schur_inner_refine(const QpdoDev *d) { return d->inner_refine && !d-
 // QPDO_INNER_X32=0: fp64 operands, slab by slab).  The copies are written where the vectors are: u = s_z -> s_z32 (cgcg_elem, k_cgcg_init,
 // k_refine_init), t = tmp_n -> tmp_n32 (EpiDivDotSums, EpiDivDot).  Both schedules of the CG use the same width.
 static bool schur_x32(const QpdoDev *d) { return d->inner_x32 && d->s_z32 && d->tmp_n32 && d->Arc.seg_pairs && d->Atc.seg_pairs && schur_f32_ready(d); }
-// f32: both products stream the fp32 images (single GPU); x32: and stage the fp32 copies of their operands, u being s_z
-static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const int *done2, bool sample, int *fcnt, bool f32, bool x32 = false) {
+// The coarse sweeps of the refined solve stream the half-precision images: the workspace has them, a scale, and the fp32 operand vectors
+// (QPDO_INNER_H16; off with QPDO_INNER_X32=0)
+static bool schur_h16_ready(const QpdoDev *d) { return d->inner_h16 && d->h16_set && d->Arc.vsm16 && d->Atc.vsm16 && schur_x32(d); }
+// width: both products stream that copy of the values (narrow ones: single GPU); x32: and stage the fp32 copies of their operands, u being s_z
+static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const int *done2, bool sample, int *fcnt, StreamWidth width, bool x32 = false) {
     const bool dist = d->comm.active;
     const int n = d->n, kl = d->kact;
     double *Pf = d->part2 + 6 * PGRID;
     if (!dist) {
-        const float *u32 = (f32 && x32) ? d->s_z32 : nullptr; float *t32 = (f32 && x32) ? d->tmp_n32 : nullptr;
-        launch_spmv_inner(d, d->Atc, u, u32, EpiDivDot{d->pc_diag, d->tmp_n, Pf, 0.0, t32}, true, done2, f32);
+        const bool narrow = width != STREAM_F64;
+        const float *u32 = (narrow && x32) ? d->s_z32 : nullptr; float *t32 = (narrow && x32) ? d->tmp_n32 : nullptr;
+        launch_spmv_inner(d, d->Atc, u, u32, EpiDivDot{d->pc_diag, d->tmp_n, Pf, 0.0, t32}, true, done2, width);
         // HIP-event sample of the dominant kernel (the A_c product), taken mid-batch by the caller's choice of `sample`
         if (sample) (void)hipEventRecord(d->ev0, d->stream);
-        launch_spmv_inner(d, d->Arc, d->tmp_n, t32, EpiSchurW{d->dc, u, w}, false, done2, f32);
+        launch_spmv_inner(d, d->Arc, d->tmp_n, t32, EpiSchurW{d->dc, u, w}, false, done2, width);
         if (sample) (void)hipEventRecord(d->ev1, d->stream);
         *fcnt = spmv_pgrid(d->Atc);
         return 0;
@@ -265,9 +269,9 @@ static int schur_S_apply(QpdoDev *d, const double *u, double *w, int par, const 
     return 0;
 }
 // s_x = S'^-1 b by the single-reduction Jacobi-PCG (device latch in ctrl2, batches of iterations between host syncs), to a recursive
-// residual of tol ||b||.  f32: the products stream the fp32 images.  init: b = s_v and k_cgcg_init runs; otherwise the caller has left the
-// state of step 0 (k_refine_init, k_refine_norm).  first_batch: iterations issued before the first host read.
-static int schur_inner_cg(QpdoDev *d, double tol, bool f32, bool init, int first_batch, int *iters) {
+// residual of tol ||b||.  width: the copy of the matrix values that the products stream.  init: b = s_v and k_cgcg_init runs; otherwise the
+// caller has left the state of step 0 (k_refine_init, k_refine_norm).  first_batch: iterations issued before the first host read.
+static int schur_inner_cg(QpdoDev *d, double tol, StreamWidth width, bool init, int first_batch, int *iters) {
     const bool dist = d->comm.active;
     const int kl = d->kact, g = vgrid(kl);
     double *P3 = d->part2;                   // [3 sums][2 parities][PGRID]; Pf behind them
@@ -280,14 +284,14 @@ static int schur_inner_cg(QpdoDev *d, double tol, bool f32, bool init, int first
     // QPDO_INNER_FOLD=0 selects the three-launch schedule; both run the same device functions (pcg_kernels.inc) and give the same bits.
     const bool fold = d->inner_fold && !dist && (long long)g * BLK >= kl;
     // fp32 operands (schur_x32): u32, t32 are the copies that the step and product 1 write and the products stage; null otherwise
-    const bool x32 = f32 && schur_x32(d);
+    const bool x32 = width != STREAM_F64 && schur_x32(d);
     float *u32 = x32 ? d->s_z32 : nullptr, *t32 = x32 ? d->tmp_n32 : nullptr;
     if (init) LAUNCH(k_cgcg_init, g, kl, (const double *)d->s_v, (const double *)d->s_diag, (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, P3, d->ctrl2, u32);
     int rc = 0;
     if (fold) {
-        launch_spmv_inner(d, d->Atc, d->s_z, u32, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, 0, d->s_r, d->s_z, d->dc, (double *)nullptr, 0.0, t32}, true, done2, f32);
+        launch_spmv_inner(d, d->Atc, d->s_z, u32, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, 0, d->s_r, d->s_z, d->dc, (double *)nullptr, 0.0, t32}, true, done2, width);
         fcnt = spmv_pgrid(d->Atc);
-    } else { rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt, f32, x32); if (rc) return -1; }
+    } else { rc = schur_S_apply(d, d->s_z, d->s_Sp, 0, dist ? nullptr : done2, false, &fcnt, width, x32); if (rc) return -1; }
     int j = 0;
     int batch = first_batch;
     while (j < SCHUR_INNER_MAXIT) {
@@ -297,22 +301,23 @@ static int schur_inner_cg(QpdoDev *d, double tol, bool f32, bool init, int first
             if (fold) {
                 // (the HIP-event sample of the A_c product includes the step it performs; its byte count is that of the product)
                 if (sample) (void)hipEventRecord(d->ev0, d->stream);
-                launch_spmv_inner(d, d->Arc, d->tmp_n, t32, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol, nullptr, u32}, false, nullptr, f32);
+                launch_spmv_inner(d, d->Arc, d->tmp_n, t32, EpiSchurStep{j, d->ctrl2, P3, g, Pf, fcnt, d->s_diag, d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol, nullptr, u32}, false, nullptr, width);
                 if (sample) (void)hipEventRecord(d->ev1, d->stream);
-                launch_spmv_inner(d, d->Atc, d->s_z, u32, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3, 0.0, t32}, true, done2, f32);
+                launch_spmv_inner(d, d->Atc, d->s_z, u32, EpiDivDotSums{d->pc_diag, d->tmp_n, Pf, kl, (j + 1) & 1, d->s_r, d->s_z, d->dc, P3, 0.0, t32}, true, done2, width);
             } else {
                 LAUNCH(k_cgcg_step, g, kl, j, d->ctrl2, glob3, P3, g, (const double *)Pf, fcnt, (const double *)d->s_Sp, (const double *)d->s_diag,
                        (const double *)d->dc, d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, tol, u32);
-                rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, sample, &fcnt, f32, x32); if (rc) return -1;
+                rc = schur_S_apply(d, d->s_z, d->s_Sp, (j + 1) & 1, dist ? nullptr : done2, sample, &fcnt, width, x32); if (rc) return -1;
             }
             d->st.inner_steps++;
             if (x32) d->st.inner_x32_steps++;
+            if (width == STREAM_H16) d->st.inner_h16_steps++;
         }
         rc = read_ctrl2(d); if (rc) return rc;
         if (!dist && d->hctrl2->cnt[C_PCG_IT] > it_before + sample_b) {          // the sampled iteration of this batch really ran
             float ms = 0.f;
             // (the bytes of the product that was sampled: the roofline fraction stays a statement about the kernel that ran)
-            if (hipEventElapsedTime(&ms, d->ev0, d->ev1) == hipSuccess) { d->ev_ac_ms += ms; d->ev_ac_bytes += f32 ? d->Arc.alg_bytes32() : d->Arc.alg_bytes(); d->ev_ac_n++; }
+            if (hipEventElapsedTime(&ms, d->ev0, d->ev1) == hipSuccess) { d->ev_ac_ms += ms; d->ev_ac_bytes += width == STREAM_H16 ? d->Arc.alg_bytes16() : width == STREAM_F32 ? d->Arc.alg_bytes32() : d->Arc.alg_bytes(); d->ev_ac_n++; }
         }
         if (d->hctrl2->cnt[C_PCG_DONE]) break;
         batch = 4;
@@ -337,25 +342,37 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
     d->st.inner_solves++;
     d->s_sol = d->s_x;
     if (!schur_inner_refine(d)) {
-        const int st = schur_inner_cg(d, tol, schur_inner_f32(d), true, first_batch, iters);
+        const int st = schur_inner_cg(d, tol, schur_inner_f32(d) ? STREAM_F32 : STREAM_F64, true, first_batch, iters);
         if (st >= 0) d->schur_last_inner = *iters;
         return st;
     }
     const int kl = d->kact, g = vgrid(kl);
     double bn = 0.0, rho = 0.0;
     int total = 0;
+    // Coarse sweeps (schur_h16_ready): the first h16_maxsweep sweeps stream the half-precision images and stop at a recursive residual of
+    // max(theta tol ||b||, h16_eta ||rho||) -- the 11-bit matrix gains 2.5-2.8 decades of the fp64 residual per sweep whatever the CG is
+    // asked for (tools/inner_h16_model.py).  Acceptance is the same test on the same fp64 residual after every sweep, coarse or not.
+    const int coarse_sweeps = schur_h16_ready(d) ? d->h16_maxsweep : 0;
     for (int sweep = 0; sweep < d->refine_maxsweep; sweep++) {
         int it = 0;
+        const bool coarse = sweep < coarse_sweeps;
         // the sweep's own right-hand side is rho: theta tol ||b|| relative to ||rho|| (not accepted: rho > tol ||b||, so this is < theta)
-        const double tol_s = sweep == 0 ? d->refine_theta * tol : d->refine_theta * tol * bn / rho;
-        const int st = schur_inner_cg(d, tol_s, true, sweep == 0, sweep == 0 ? first_batch : d->pcg_batch, &it);
+        double tol_s = sweep == 0 ? d->refine_theta * tol : d->refine_theta * tol * bn / rho;
+        if (coarse && tol_s < d->h16_eta) tol_s = d->h16_eta;
+        // with coarse sweeps a later sweep's iteration count is remembered like the first one's: batches of pcg_batch, their reads and
+        // latched launches, would cost a 40-iteration sweep a tenth of its time
+        int *mem = sweep == 0 ? &d->schur_last_inner : sweep < QpdoDev::SWEEP_MEMORY ? &d->sweep_last_inner[sweep] : (int *)nullptr;
+        const int fb = sweep == 0 ? first_batch : (coarse_sweeps && mem && *mem > 12) ? *mem - 6 : d->pcg_batch;
+        const int st = schur_inner_cg(d, tol_s, coarse ? STREAM_H16 : STREAM_F32, sweep == 0, fb, &it);
         if (st < 0) return st;
         total += it;
-        if (sweep == 0) { bn = d->hctrl2->val[V_BNORM]; d->schur_last_inner = it; }
+        if (sweep == 0) bn = d->hctrl2->val[V_BNORM];
+        if (mem) *mem = it;
         if (st) break;                                                         // not converged, or NaN: the fp64 CG decides
+        if (coarse) d->st.inner_h16_sweeps++;
         LAUNCH(k_refine_acc, g, kl, sweep == 0 ? 1 : 0, (const double *)d->s_x, d->s_acc);
         int fcnt = 0;
-        if (schur_S_apply(d, d->s_acc, d->s_Sp, 0, nullptr, false, &fcnt, false)) return -1;
+        if (schur_S_apply(d, d->s_acc, d->s_Sp, 0, nullptr, false, &fcnt, STREAM_F64)) return -1;
         LAUNCH(k_refine_init, g, kl, (const double *)d->s_v, (const double *)d->s_Sp, (const double *)d->s_diag, (const double *)d->dc,
                d->s_x, d->s_r, d->s_z, d->s_p, d->s_s, d->part2, schur_x32(d) ? d->s_z32 : (float *)nullptr);
         LAUNCH(k_refine_norm, 1, (const double *)d->part2, g, d->ctrl2);
@@ -373,7 +390,7 @@ static int schur_inner_solve(QpdoDev *d, double tol, int *iters) {
     }
     d->st.inner_refine_fallbacks++;
     int it = 0;
-    const int st = schur_inner_cg(d, tol, false, true, first_batch, &it);
+    const int st = schur_inner_cg(d, tol, STREAM_F64, true, first_batch, &it);
     *iters = total + it;
     return st;
 }
@@ -459,6 +476,7 @@ static int pcg_schur_solve(QpdoDev *d, int *iters_out, int *fallback) {
     { int rc0 = read_ctrl(d); if (rc0) return rc0; }
     const double dmax = nrm_of(d->hctrl, N_A);
     d->schur_last_inner = 0;
+    for (int &v : d->sweep_last_inner) v = 0;
     // Base value: the inner solve only defines a preconditioner, so this is a cost knob, not an accuracy one.  C4 time-to-eps against
     // it (tools/tol_probe.py, one box): 1e-6 8.01 s, 2e-6 7.83, 3e-6 7.45, 4e-6 7.56, 5e-6 7.67, 7e-6 8.03, 1e-5 8.70 (the on-the-fly
     // tightening starts to fire), 1e-4 20.4; the n = 1.3e4 / 3e4 fixtures have the same shallow basin.  3e-6 = its middle.

@@ -166,7 +166,8 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
 // [kact, cnt] and the cnt per-block partial sums of p.Kp from info[QDEV_PCG_INFO_HEAD] on.  mode 1: ONE pcg_solve of K x = v with the
 // relative stopping rule alone: out = x, info = [kact, iters, defl_r, Schur mode delivered, V_RNORM, V_BNORM, inner solves, inner steps,
 // class (0 ok, 1 not converged, 2 NaN), outer iterations].  mode 32 / 33: build_compact, then one product of the fp32-stream slab kernel with
-// A_c / A_c' (refused where the pass has no fp32 images).  info holds QDEV_PCG_INFO_LEN doubles.  A solve of class 1 or 2 returns QDEV_PCG_NOT_CONVERGED /
+// A_c / A_c' (refused where the pass has no fp32 images); 34 / 35: the pair-wide fp32 instance; 36 / 37: the pair-wide half-precision instance
+// (refused where the workspace has no half-precision images or no scale), info[1] = the scale's exponent e.  info holds QDEV_PCG_INFO_LEN doubles.  A solve of class 1 or 2 returns QDEV_PCG_NOT_CONVERGED /
 // QDEV_PCG_NAN with pcg_verdict's message, never a HIP code.  Whatever the call overwrites -- the weights, sigma_f, dx, rhs, the stopping
 // rule, the Schur mode's strikes and batch memory, the counters -- is put back: the next solve runs as on a workspace that never saw it.
 static_assert(QDEV_PCG_NOT_CONVERGED == PCG_NOT_CONVERGED && QDEV_PCG_NAN == PCG_NAN, "qpdo_dev.h carries the PCG failure classes");
@@ -175,7 +176,7 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
     HIPCHK(hipSetDevice(d->device));
     if (d->comm.active) return set_err(hipErrorInvalidValue, "pcg probe: not for row-partitioned workspaces", __LINE__);
     if (d->linsolve != 0) return set_err(hipErrorInvalidValue, "pcg probe: the workspace's solver is not PCG", __LINE__);
-    if (mode != 0 && mode != 1 && (mode < 32 || mode > 35)) return set_err(hipErrorInvalidValue, "pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product), 34 or 35 (one pair-wide fp32 product)", __LINE__);
+    if (mode != 0 && mode != 1 && (mode < 32 || mode > 37)) return set_err(hipErrorInvalidValue, "pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product), 34 or 35 (one pair-wide fp32 product), 36 or 37 (one pair-wide half-precision product)", __LINE__);
     const int n = d->n, m = d->m;
     std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1)), rhs_keep((size_t)(n > 0 ? n : 1));
     if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
@@ -205,16 +206,18 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
         if (!rc) HIPCHK(hipStreamSynchronize(d->stream));
         if (!rc) HIPCHK(hipGetLastError());
         info[0] = (double)d->kact; info[1] = (double)cnt;
-    } else if (mode >= 32 && mode <= 35) {
+    } else if (mode >= 32 && mode <= 37) {
         // the slab kernel's fp32-stream instances on their own: out[0 .. k) = A_c32 v (mode 32), out (n) = A_c32' v[0 .. k) (mode 33), A_c32 =
         // the compact values rounded to float, products and sums in double.  Modes 34 / 35: the same two products by the pair-wide
-        // instance, v rounded to float as well (the copy is made on the host here; the solver writes it with the vector)
-        const bool x32 = mode >= 34;
-        if (x32) mode -= 2;
+        // instance, v rounded to float as well (the copy is made on the host here; the solver writes it with the vector).  Modes 36 / 37: the
+        // pair-wide instance on the half-precision images, out = 2^-e (A_c16 v32) with A_c16 = the values times 2^e rounded to float, then half
+        const bool h16 = mode >= 36, x32 = mode >= 34;
+        mode = 32 + (mode & 1);
         rc = build_compact(d);
         const int k = d->kact;
         if (!rc && (!schur_f32_ready(d) || k > n)) rc = set_err(hipErrorInvalidValue, "pcg probe: this pass has no fp32 images (both compact matrices under the slab kernel with 16-bit indices, QPDO_PCG_INNER_REFINE or QPDO_PCG_INNER_F32 on, k <= n)", __LINE__);
         if (!rc && x32 && !schur_x32(d)) rc = set_err(hipErrorInvalidValue, "pcg probe: this workspace has no fp32 operand vectors (QPDO_INNER_X32=0, or no fp32 images)", __LINE__);
+        if (!rc && h16 && !schur_h16_ready(d)) rc = set_err(hipErrorInvalidValue, "pcg probe: this workspace has no half-precision images or no scale for them (QPDO_INNER_H16=0, QPDO_INNER_X32=0, or max |a_ij| is 0 or not finite)", __LINE__);
         if (!rc && x32) {
             std::vector<float> v32((size_t)n);
             for (int i = 0; i < n; i++) v32[(size_t)i] = (float)v[i];
@@ -222,13 +225,15 @@ int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, 
             HIPCHK(hipStreamSynchronize(d->stream));
         }
         if (!rc) {
-            if (mode == 32) launch_spmv_inner(d, d->Arc, d->pc_p, x32 ? d->tmp_n32 : (const float *)nullptr, EpiStore{d->tc}, false, nullptr, true);
-            else launch_spmv_inner(d, d->Atc, d->pc_p, x32 ? d->s_z32 : (const float *)nullptr, EpiStore{d->tmp_n}, false, nullptr, true);
+            const StreamWidth width = h16 ? STREAM_H16 : STREAM_F32;
+            if (mode == 32) launch_spmv_inner(d, d->Arc, d->pc_p, x32 ? d->tmp_n32 : (const float *)nullptr, EpiStore{d->tc}, false, nullptr, width);
+            else launch_spmv_inner(d, d->Atc, d->pc_p, x32 ? d->s_z32 : (const float *)nullptr, EpiStore{d->tmp_n}, false, nullptr, width);
             HIPCHK(hipMemcpyAsync(out, mode == 32 ? d->tc : d->tmp_n, (size_t)(mode == 32 ? k : n) * 8, hipMemcpyDeviceToHost, d->stream));
             HIPCHK(hipStreamSynchronize(d->stream));
             HIPCHK(hipGetLastError());
         }
         info[0] = (double)k;
+        if (h16) info[1] = (double)d->h16_e;
     } else {
         int iters = 0;
         d->sdiag_from_build = 0;
@@ -265,6 +270,12 @@ int qdev_download_compact(QpdoDev *d, int which, void *dst, long count) {
         if (count != 5) return set_err(hipErrorInvalidValue, "download compact: the index space's geometry has 5 entries", __LINE__);
         long long *g = (long long *)dst;
         g[0] = d->n; g[1] = d->m; g[2] = k; g[3] = words; g[4] = d->defl_r;
+        return 0;
+    }
+    if (which == 59) {
+        if (count != 2) return set_err(hipErrorInvalidValue, "download compact: the half-precision images' state has 2 entries", __LINE__);
+        long long *g = (long long *)dst;
+        g[0] = (d->h16_set && d->Arc.vsm16 && d->Atc.vsm16) ? 1 : 0; g[1] = g[0] ? d->h16_e : 0;
         return 0;
     }
     if (which >= 0 && which < 48) {
@@ -315,6 +326,7 @@ int qdev_download_compact(QpdoDev *d, int which, void *dst, long count) {
             case 0: src = M.seg; len = (size_t)2 * M.nrows * (size_t)M.nslabs; esz = 4; break;
             case 1: src = M.vsm; len = (size_t)M.nnz; break;
             case 2: if (M.i16sm) { src = M.i16sm; esz = 2; } else { src = M.cism; esz = 4; } len = (size_t)M.nnz; break;
+            case 3: if (h16_dst(d, M)) { src = M.vsm16; esz = 2; len = (size_t)M.nnz; } break;      // (count 0 where the image has no half-precision values)
             default: return set_err(hipErrorInvalidValue, "download compact: unknown array", __LINE__);
         }
     } else switch (which) {

@@ -55,6 +55,7 @@ static int reset_to_setup_state(QpdoDev *d) {
     d->qdiag_valid = 0; d->dense_valid = 0; d->dense_factored = 0; d->mid_fwd_valid = 0;
     d->wb_k = 0; d->dense_fact_sigma = 0.0; d->dense_last_branch = -1; d->dense_last_sigma = -1.0; d->sigma_f = 0.0;
     d->hybrid_active = 0; d->schur_off = 0; d->schur_strikes = 0; d->last_jacobi_iters = 0; d->schur_last_inner = 0; d->pcg_abs_now = -1.0;
+    for (int &v : d->sweep_last_inner) v = 0;
     d->ahead_inflight = 0; d->ahead_branch = -1; d->ahead_sigma_f02 = 0.0; d->ahead_spmv_calls0 = 0; d->ahead_spmv_bytes0 = 0;
     d->tail_shift = 0; d->tail_muchg = 0; d->tail_sigma = 0; d->tail_dsig = 0.0;
     d->step_pending = 0; d->axpy_pending = 0; d->ctrl_clean = 0; d->defer_step = 0; d->pend_proximal = 0; d->pend_sigma = 0.0; d->cur_proximal = 1;
@@ -181,6 +182,7 @@ int qdev_update_matrices(QpdoDev *d, const QdevCsc *A, const QdevCsc *Q, const d
                            (const u32 *)d->mapA, needA ? d->Ar.val : (double *)nullptr, nQ, gatherQ ? (const double *)d->qstage : (const double *)nullptr,
                            (const u32 *)d->mapQ, d->rawQ, d->Qf.val);
     rc = reset_to_setup_state(d);
+    if (!rc) rc = h16_refresh_scale(d);          // (new values of A: a new scale of the half-precision images)
     if (!rc) {
         HIPCHK(hipMemcpyAsync(d->q, q, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
         if (d->m) { HIPCHK(hipMemcpyAsync(d->l, l, (size_t)d->m * 8, hipMemcpyHostToDevice, d->stream)); HIPCHK(hipMemcpyAsync(d->u, u, (size_t)d->m * 8, hipMemcpyHostToDevice, d->stream)); }

@@ -98,20 +98,36 @@ typedef float slab_f4 __attribute__((ext_vector_type(4)));
 // no other matrix byte.  A float times a float is exact in double, so the product's own rounding is that of the sums alone, as before.
 #define SLAB_UNR32 4             // fp32 stream: 16-byte value loads in flight per lane
 #define SLAB_UNR32X 4            // fp32 stream with the fp32 operand: a C4 pair segment (330-400 entries) is two trips of 256 (measured on the C4 solve: 2, 6 and 8 in flight are 4-8 % slower, docs/LAB_NOTES.md)
+// VT = _Float16 (with XT = float, pair order): the half-precision copy vsm16 of the values, scaled by a power of two (QpdoDev::h16_e) that
+// the finished row sums undo -- 4 bytes per nonzero.  One lane trip is a 16-byte load of EIGHT values plus a 16-byte load of eight indices,
+// a start aligned to eight entries.  half -> float -> double, products and sums in double: an 11-bit value times a 24-bit operand is exact
+// there, so the row sums stay the only rounding.  Four loads in flight per lane and EIGHT lanes per row segment: a trip of 256 entries, so
+// a C4 pair segment (330-400 entries) is two trips, with 128 bytes per lane in flight.  Measured on the C4 solve against (loads, lanes) =
+// (2, 16), (4, 16), (3, 16), (2, 8), (3, 8): docs/LAB_NOTES.md.  (The macros exist for such builds.)
+#ifndef SLAB_UNR16
+#define SLAB_UNR16 4
+#endif
+#ifndef SLAB_TPR16
+#define SLAB_TPR16 8
+#endif
+typedef _Float16 slab_h8 __attribute__((ext_vector_type(8)));
 template <class VT, class XT> struct SlabStream;
-// EPL: entries per lane and load; NSA: partial sums per lane (entry EPL u + e of a trip goes to sum (EPL u + e) mod NSA)
-template <> struct SlabStream<double, double> { static constexpr int EPL = 2, UNR = SLAB_UNR, NSA = EPL * UNR; using Vec = double2; };
-template <> struct SlabStream<float, double>  { static constexpr int EPL = 4, UNR = SLAB_UNR32, NSA = EPL * UNR; using Vec = float4; };
-template <> struct SlabStream<float, float>   { static constexpr int EPL = 4, UNR = SLAB_UNR32X, NSA = 8; using Vec = float4; };     // (one sum per entry spills from 8 loads on)
+// EPL: entries per lane and load; NSA: partial sums per lane (entry EPL u + e of a trip goes to sum (EPL u + e) mod NSA); TPR: lanes per row segment
+template <> struct SlabStream<double, double> { static constexpr int EPL = 2, UNR = SLAB_UNR, NSA = EPL * UNR, TPR = SLAB_TPR; using Vec = double2; };
+template <> struct SlabStream<float, double>  { static constexpr int EPL = 4, UNR = SLAB_UNR32, NSA = EPL * UNR, TPR = SLAB_TPR; using Vec = float4; };
+template <> struct SlabStream<float, float>   { static constexpr int EPL = 4, UNR = SLAB_UNR32X, NSA = 8, TPR = SLAB_TPR; using Vec = float4; };     // (one sum per entry spills from 8 loads on)
+template <> struct SlabStream<_Float16, float> { static constexpr int EPL = 8, UNR = SLAB_UNR16, NSA = 8, TPR = SLAB_TPR16; using Vec = slab_h8; };
 template <class VT, class XT, class Epi, bool I16, bool OVL, bool NT>
 __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                     int rows_per_wg, const int2 *__restrict__ seg, const int *__restrict__ cism,
                                                     const unsigned short *__restrict__ i16sm,
-                                                    const VT *__restrict__ vsm, const XT *__restrict__ x, Epi epi) {
-    constexpr int TPR = SLAB_TPR;
-    constexpr bool F32 = std::is_same<VT, float>::value, X32 = std::is_same<XT, float>::value;
-    static_assert(!F32 || I16, "the fp32 stream has 16-bit indices only");
-    static_assert(!X32 || F32, "the fp32 operand goes with the fp32 stream only");
+                                                    const VT *__restrict__ vsm, const XT *__restrict__ x, Epi epi, double rscale) {
+    constexpr int TPR = SlabStream<VT, XT>::TPR;
+    // NARROW: a copy of the values narrower than double (float, half); rscale: what undoes the scale of the half-precision copy (H16 only)
+    constexpr bool F32 = std::is_same<VT, float>::value, H16 = std::is_same<VT, _Float16>::value, NARROW = F32 || H16, X32 = std::is_same<XT, float>::value;
+    static_assert(!NARROW || I16, "the narrow streams have 16-bit indices only");
+    static_assert(!X32 || NARROW, "the fp32 operand goes with the narrow streams only");
+    static_assert(!H16 || X32, "the half-precision stream is pair-wide only");
     constexpr int EPL = SlabStream<VT, XT>::EPL, UNR = SlabStream<VT, XT>::UNR, NSA = SlabStream<VT, XT>::NSA;
     static_assert((EPL * UNR) % NSA == 0 && NSA % 2 == 0, "the partial sums take the entries of a trip in turn");
     using Vec = typename SlabStream<VT, XT>::Vec;
@@ -131,18 +147,24 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
     constexpr int STEP = EPL * UNR * TPR;               // entries per trip of a lane group
     // 16-byte value loads and the matching index loads from a start aligned to EPL entries (the elements before an unaligned
     // `beg` and those after the end are masked): one instruction covers EPL*TPR consecutive entries and UNR of them are in flight
-    // per lane -- a C4 segment (~170 entries) is a single trip.  No scalar tail loop: slots past the end re-read the first load
-    // and contribute exact zeros.  (Lab, tools/lab/slab_lab.hip, C4 shape: 8-byte loads x4: 5.8 TB/s; 16-byte x4: 6.2; x8: 6.9
+    // per lane -- a C4 segment of one slab (~170 entries) is a single trip of the slab-by-slab instances, a C4 pair segment (330-400) two
+    // trips of 256 of the pair-wide ones.  EPL is 2 (double), 4 (float) or 8 (half: both loads of a lane are 16 bytes, starts aligned to
+    // eight entries, hence eight entries of padding behind every image array).  No scalar tail loop: slots past the end re-read the
+    // first load and contribute exact zeros.  (Lab, tools/lab/slab_lab.hip, C4 shape: 8-byte loads x4: 5.8 TB/s; 16-byte x4: 6.2; x8: 6.9
     // with the slab-major image, 6.2 without.)
     // index words: EPL 16-bit slab-local indices, or a pair of 32-bit ones; unpacked at the use, so that nothing waits for a
     // load in flight before the row's first trip is computed
-    using IdxW = typename std::conditional<F32, uint2, typename std::conditional<I16, unsigned, int2>::type>::type;
+    using IdxW = typename std::conditional<H16, uint4, typename std::conditional<F32, uint2, typename std::conditional<I16, unsigned, int2>::type>::type>::type;
     auto load_trip = [&](Vec *v, IdxW *w, int k, int kb, int end) {
 #pragma unroll
         for (int u = 0; u < UNR; u++) {
             const int kk = k + u * EPL * TPR;
             const int kc = kk < end ? kk : kb;
-            if constexpr (F32) {
+            if constexpr (H16) {
+                if constexpr (NT) v[u] = __builtin_nontemporal_load(reinterpret_cast<const slab_h8 *>(vsm + kc));
+                else v[u] = *reinterpret_cast<const slab_h8 *>(vsm + kc);
+                w[u] = *reinterpret_cast<const uint4 *>(i16sm + kc);
+            } else if constexpr (F32) {
                 if constexpr (NT) {
                     const slab_f4 t = __builtin_nontemporal_load(reinterpret_cast<const slab_f4 *>(vsm + kc));
                     v[u] = make_float4(t.x, t.y, t.z, t.w);
@@ -185,7 +207,11 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
             for (int u = 0; u < UNR; u++) {
                 const int kk = k + u * EPL * TPR;
                 double vv[EPL]; int ax[EPL];
-                if constexpr (F32) {
+                if constexpr (H16) {
+                    const unsigned wd[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+#pragma unroll
+                    for (int e = 0; e < EPL; e++) { vv[e] = (double)(float)v[u][e]; ax[e] = (int)((e & 1) ? wd[e >> 1] >> 16 : wd[e >> 1] & 0xffffu); }
+                } else if constexpr (F32) {
                     vv[0] = (double)v[u].x; vv[1] = (double)v[u].y; vv[2] = (double)v[u].z; vv[3] = (double)v[u].w;
                     ax[0] = (int)(w[u].x & 0xffffu); ax[1] = (int)(w[u].x >> 16); ax[2] = (int)(w[u].y & 0xffffu); ax[3] = (int)(w[u].y >> 16);
                 } else {
@@ -275,7 +301,7 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
         if (OVL) prefetch(s + 1);
     }
     __syncthreads();
-    for (int r = tid; r < R; r += SLAB_THREADS) epi.row(row0 + r, acc[r]);
+    for (int r = tid; r < R; r += SLAB_THREADS) epi.row(row0 + r, H16 ? acc[r] * rscale : acc[r]);      // (a power of two: exact)
     epi.finish(sm);
 }
 // slab pointers by binary search in each (column-sorted) row; with `unsorted` given, also flags unsorted rows (a walk over the whole row)
@@ -348,11 +374,15 @@ __global__ __launch_bounds__(1024) void k_slab_seg(int nrows, int nslabs, int ro
         pos += len;
     }
 }
+// One entry of the half-precision image (DevCsr::vsm16): v scaled by the workspace's power of two h16s = 2^e (exact), rounded to float and
+// then to half, each step to nearest even; what lands in the subnormal range of half stays a subnormal.
+__device__ __forceinline__ _Float16 h16_round(double v, double h16s) { return (_Float16)(float)(v * h16s); }
 // copy values and slab-local indices of every (row, slab) segment to its slab-major place; 16 lanes per row
 __global__ __launch_bounds__(256) void k_slab_permute(int nrows, int nslabs, int W, const int *__restrict__ sp, const int2 *__restrict__ seg,
                                                       const int *__restrict__ ci, const unsigned short *__restrict__ ci16,
                                                       const double *__restrict__ val, double *__restrict__ vsm,
-                                                      unsigned short *__restrict__ i16sm, int *__restrict__ cism, float *__restrict__ vsm32) {
+                                                      unsigned short *__restrict__ i16sm, int *__restrict__ cism, float *__restrict__ vsm32,
+                                                      _Float16 *__restrict__ vsm16, double h16s) {
     const int lane = threadIdx.x & 15;
     const int ngroups = gridDim.x * (blockDim.x >> 4);
     for (int row = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4); row < nrows; row += ngroups)
@@ -363,6 +393,7 @@ __global__ __launch_bounds__(256) void k_slab_permute(int nrows, int nslabs, int
                 const double v = val[src + e];
                 vsm[sg.x + e] = v;
                 if (vsm32) vsm32[sg.x + e] = (float)v;
+                if (vsm16) vsm16[sg.x + e] = h16_round(v, h16s);
                 if (i16sm) i16sm[sg.x + e] = ci16[src + e]; else cism[sg.x + e] = ci[src + e] - sl * W;
             }
         }
@@ -546,7 +577,7 @@ static void launch_slab(QpdoDev *d, const DevCsr &M, Args... args) {
 // f32: the product streams the fp32 copy of the values (M.vsm32 and M.i16sm must exist: the callers check, schur_f32_ready)
 template <class Epi>
 static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, const int *done, bool f32 = false) {
-#define SLAB_GO(VT, VSM, I16, OVL, NT) launch_slab<k_spmv_slab<VT, double, Epi, I16, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, VSM, x, epi)
+#define SLAB_GO(VT, VSM, I16, OVL, NT) launch_slab<k_spmv_slab<VT, double, Epi, I16, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, VSM, x, epi, 1.0)
 #define SLAB_GO_NT(VT, VSM, I16, OVL) do { if (M.slab_nt) SLAB_GO(VT, VSM, I16, OVL, true); else SLAB_GO(VT, VSM, I16, OVL, false); } while (0)
     if (f32) {
         if (M.slab_ovl) SLAB_GO_NT(float, (const float *)M.vsm32, true, true); else SLAB_GO_NT(float, (const float *)M.vsm32, true, false);
@@ -558,15 +589,16 @@ static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi e
 #undef SLAB_GO_NT
 #undef SLAB_GO
 }
-// The pair-wide fp32 product: fp32 copy of the values, fp32 copy x32 of the operand.  M takes the slab kernel, carries vsm32 and i16sm
-// (schur_f32_ready) and its image is in pair order (DevCsr::seg_pairs, k_slab_seg).
-template <class Epi>
-static void launch_spmv_x32(QpdoDev *d, const DevCsr &M, const float *x32, Epi epi, const int *done) {
-#define SLAB_GO(OVL, NT) launch_slab<k_spmv_slab<float, float, Epi, true, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, (const float *)M.vsm32, x32, epi)
+// The pair-wide products: a narrow copy `vals` of the values -- fp32 (vsm32), or half precision (vsm16, whose scale rscale = 2^-e undoes)
+// -- and the fp32 copy x32 of the operand.  M takes the slab kernel, carries that copy and i16sm (schur_f32_ready, schur_h16_ready) and
+// its image is in pair order (DevCsr::seg_pairs, k_slab_seg).
+template <class VT, class Epi>
+static void launch_spmv_x32(QpdoDev *d, const DevCsr &M, const VT *vals, double rscale, const float *x32, Epi epi, const int *done) {
+#define SLAB_GO(OVL, NT) launch_slab<k_spmv_slab<VT, float, Epi, true, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, vals, x32, epi, rscale)
     if (M.slab_ovl) { if (M.slab_nt) SLAB_GO(true, true); else SLAB_GO(true, false); }
     else            { if (M.slab_nt) SLAB_GO(false, true); else SLAB_GO(false, false); }
 #undef SLAB_GO
-    d->st.spmv_bytes -= (int64_t)(4.0 * (double)M.nnz);            // (launch_slab counted the fp64 stream)
+    d->st.spmv_bytes -= (int64_t)((12.0 - 4.0 - (double)sizeof(VT)) * (double)M.nnz);      // (launch_slab counted the fp64 stream)
 }
 // y = M x with the kernel M was set up for; done: the PCG's latch (the product is skipped once it is set), or nullptr
 template <class Epi>
@@ -577,10 +609,15 @@ static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, b
     d->st.spmv_calls++;
     d->st.spmv_bytes += (int64_t)M.alg_bytes();
 }
-// One product of the Schur mode's fp32 inner CG (f32): pair-wide with the fp32 copy x32 of x where there is one, otherwise slab by slab with x.
+// The width of the matrix stream of one product of the Schur mode's inner solve: the fp64 values, their fp32 copy, their half-precision copy
+enum StreamWidth { STREAM_F64 = 0, STREAM_F32, STREAM_H16 };
+// One product of the Schur mode's inner CG.  STREAM_F32: pair-wide with the fp32 copy x32 of x where there is one, otherwise slab by slab
+// with x.  STREAM_H16: pair-wide only (x32 and M.vsm16 must exist: schur_h16_ready); the row sums are multiplied by 2^-e of the workspace.
 template <class Epi>
-static void launch_spmv_inner(QpdoDev *d, const DevCsr &M, const double *x, const float *x32, Epi epi, bool partials, const int *done, bool f32) {
-    if (f32 && x32) launch_spmv_x32(d, M, x32, epi, done); else launch_spmv(d, M, x, epi, partials, done, f32);
+static void launch_spmv_inner(QpdoDev *d, const DevCsr &M, const double *x, const float *x32, Epi epi, bool partials, const int *done, StreamWidth width) {
+    if (width == STREAM_H16) launch_spmv_x32(d, M, (const _Float16 *)M.vsm16, ldexp(1.0, -d->h16_e), x32, epi, done);
+    else if (width == STREAM_F32 && x32) launch_spmv_x32(d, M, (const float *)M.vsm32, 1.0, x32, epi, done);
+    else launch_spmv(d, M, x, epi, partials, done, width == STREAM_F32);
 }
 
 // Two independent products in ONE launch (small problems: a launch is ~4-5 us whatever it computes, and Q dx and A dx of a Newton step
@@ -782,8 +819,9 @@ __global__ __launch_bounds__(256) void k_copy_rows_slab(int k, const int *__rest
                                                         const int *__restrict__ rp2, int *__restrict__ ci2, unsigned short *__restrict__ ci16_2,
                                                         double *__restrict__ val2, int W16, int nslabs, int W, const int *__restrict__ sp,
                                                         const int2 *__restrict__ seg, double *__restrict__ vsm, unsigned short *__restrict__ i16sm,
-                                                        int *__restrict__ cism, float *__restrict__ vsm32, const double *__restrict__ qdiag,
-                                                        double sigma_f, const double *__restrict__ dc, double *__restrict__ sdiag) {
+                                                        int *__restrict__ cism, float *__restrict__ vsm32, _Float16 *__restrict__ vsm16, double h16s,
+                                                        const double *__restrict__ qdiag, double sigma_f, const double *__restrict__ dc,
+                                                        double *__restrict__ sdiag) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * BLK + threadIdx.x) >> 6;
     const int nwaves = gridDim.x * (BLK >> 6);
@@ -814,6 +852,7 @@ __global__ __launch_bounds__(256) void k_copy_rows_slab(int k, const int *__rest
                     const int q = p + shift;
                     vsm[q] = v[u];
                     if (vsm32) vsm32[q] = (float)v[u];
+                    if (vsm16) vsm16[q] = h16_round(v[u], h16s);
                     if (i16sm) i16sm[q] = c16; else cism[q] = cl;
                     if (DIAG) s += v[u] * v[u] / (qdiag[c[u]] + sigma_f);
                 }
@@ -1008,7 +1047,8 @@ __global__ __launch_bounds__(256) void k_compact_rows_bits_slab(int nrows, const
                                                                 int *__restrict__ ci2, double *__restrict__ val2, int W16,
                                                                 unsigned short *__restrict__ ci16, int nslabs, int W, const int *__restrict__ sp,
                                                                 const int2 *__restrict__ seg, double *__restrict__ vsm,
-                                                                unsigned short *__restrict__ i16sm, int *__restrict__ cism, float *__restrict__ vsm32) {
+                                                                unsigned short *__restrict__ i16sm, int *__restrict__ cism, float *__restrict__ vsm32,
+                                                                _Float16 *__restrict__ vsm16, double h16s) {
     extern __shared__ u64 sbits_cmps[];
     int *spre = reinterpret_cast<int *>(sbits_cmps + words);
     for (int i = threadIdx.x; i < words; i += BLK) { sbits_cmps[i] = bits[i]; spre[i] = wprefix[i]; }
@@ -1046,6 +1086,7 @@ __global__ __launch_bounds__(256) void k_compact_rows_bits_slab(int nrows, const
                         if (W16 > 0) ci16[pos] = (unsigned short)cl;
                         vsm[q] = v[u];
                         if (vsm32) vsm32[q] = (float)v[u];
+                        if (vsm16) vsm16[q] = h16_round(v[u], h16s);
                         if (i16sm) i16sm[q] = (unsigned short)cl; else cism[q] = cl;
                     } else if (W16 > 0) ci16[pos] = (unsigned short)(cn % W16);
                 }

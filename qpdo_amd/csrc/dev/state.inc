@@ -37,8 +37,12 @@ struct DevCsr {
     double *vsm = nullptr; unsigned short *i16sm = nullptr; int *cism = nullptr; int2 *seg = nullptr; mutable int sm_dirty = 1;
     int seg_pairs = 0;                // the image is in pair order (k_slab_seg): the compact matrices of a workspace whose fp32 CG stages fp32 operands
     float *vsm32 = nullptr;           // optional fp32 copy of vsm (the stream of the Schur mode's inner CG: QPDO_PCG_INNER_REFINE, QPDO_PCG_INNER_F32)
+    // optional half-precision copy of vsm in the same image, scaled by the workspace's power of two (QpdoDev::h16_e): the stream of the
+    // refined inner solve's coarse sweeps (QPDO_INNER_H16).  Only on an image in pair order (seg_pairs).
+    _Float16 *vsm16 = nullptr;
     double alg_bytes() const { return 12.0 * (double)nnz + 4.0 * (nrows + 1) + 8.0 * nrows + 8.0 * ncols; }
     double alg_bytes32() const { return alg_bytes() - 4.0 * (double)nnz; }       // the same product on the fp32 copy of the values
+    double alg_bytes16() const { return alg_bytes() - 6.0 * (double)nnz; }       // ... and on the half-precision copy
 };
 
 // Row partition of one large QP over G ranks (one process per GPU): every vector is replicated, only the
@@ -161,6 +165,13 @@ struct QpdoDev {
     // inner_x32 (QPDO_INNER_X32, default 1): the fp32 CG also stages fp32 copies of its operand vectors (s_z32 of s_z, tmp_n32 of tmp_n) and
     // walks the column slabs in pairs (spmv.inc, XT = float); 0: fp64 operands, slab by slab
     int inner_x32 = 1; float *s_z32 = nullptr, *tmp_n32 = nullptr;
+    // inner_h16 (QPDO_INNER_H16, default 1; off with QPDO_INNER_X32=0): the first h16_maxsweep sweeps (QPDO_INNER_H16_MAXSWEEP) of a refined
+    // inner solve are COARSE: the CG streams the half-precision images (DevCsr::vsm16) and stops at max(theta tau ||b||, h16_eta ||rho||)
+    // (QPDO_INNER_H16_ETA).  h16_set: the images' scale 2^h16_e is valid -- max |a_ij| 2^h16_e lies in [2^14, 2^15), taken over A where its
+    // values are set (h16_refresh_scale: setup, qpdo_amd_update_matrices); a maximum of 0, inf or NaN leaves the coarse sweeps off.
+    // h16_scale = 2^h16_e (0: the builders write no half-precision values)
+    int inner_h16 = 1, h16_maxsweep = 2, h16_set = 0, h16_e = 0; double h16_eta = 1e-3, h16_scale = 0.0;
+    static const int SWEEP_MEMORY = 8; int sweep_last_inner[SWEEP_MEMORY] = {0, 0, 0, 0, 0, 0, 0, 0};      // as schur_last_inner, per sweep index from 1 on
     int inner_f32 = 0; int inner_fold = 1 /* the inner CG's vector step inside its two products (QPDO_INNER_FOLD=0: k_cgcg_step) */; int schur_mode = -1 /* -1 auto, 0 off, 1 on */, schur_off = 0, schur_strikes = 0, last_jacobi_iters = 0, schur_last_inner = 0; long long schur_passes = 0;
     double *part = nullptr;  // P_COUNT * PGRID
     // scaling

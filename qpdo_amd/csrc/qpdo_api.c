@@ -924,7 +924,7 @@ int qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long c
 }
 /* the pointer checks of the two PCG test entries are made here, before the backend is touched (tests/pcg_probe_args_driver.c) */
 int qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, const double *v, double *out, int mode, double *info) {
-    if (mode != 0 && mode != 1 && (mode < 32 || mode > 35)) { qdev_set_error("pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product), 34 or 35 (one pair-wide fp32 product)"); return -1; }
+    if (mode != 0 && mode != 1 && (mode < 32 || mode > 37)) { qdev_set_error("pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product), 34 or 35 (one pair-wide fp32 product), 36 or 37 (one pair-wide half-precision product)"); return -1; }
     if (!dw || !v || !out || !info) { qdev_set_error("pcg probe: NULL vector (dw, v, out and info are required, also at m = 0)"); return -1; }
     if (!(sigma == sigma)) { qdev_set_error("pcg probe: sigma is NaN"); return -1; }
     if (!work || !work->chol || !work->chol->dev) { qdev_set_error("pcg probe: NULL workspace"); return -1; }
@@ -932,7 +932,7 @@ int qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, cons
     return rc == QDEV_PCG_NOT_CONVERGED ? QPDO_AMD_PCG_NOT_CONVERGED : rc == QDEV_PCG_NAN ? QPDO_AMD_PCG_NAN : rc ? -1 : 0;
 }
 int qpdo_amd_download_compact(QPDOWorkspace *work, int which, void *dst, long count) {
-    if (which < 0 || which > 96 || (which > 57 && which < 64 && which != 60) || (which < 48 && which % 16 > 5) || (which >= 64 && which < 96 && which % 16 > 2)) {
+    if (which < 0 || which > 96 || (which > 57 && which < 64 && which != 59 && which != 60) || (which < 48 && which % 16 > 5) || (which >= 64 && which < 96 && which % 16 > 3)) {
         qdev_set_error("download compact: unknown array"); return -1;
     }
     if (count < 0) { qdev_set_error("download compact: negative count"); return -1; }
@@ -976,6 +976,7 @@ int qpdo_amd_get_stats(const QPDOWorkspace *work, QPDOAmdStats *out) {
     out->inner_refine_sweeps = (long)st.inner_refine_sweeps; out->inner_refine_fp64_applies = (long)st.inner_refine_fp64_applies;
     out->inner_refine_fallbacks = (long)st.inner_refine_fallbacks; out->inner_refine_max_res_over_tol = st.inner_refine_max_res_over_tol;
     out->inner_x32_steps = (long)st.inner_x32_steps;
+    out->inner_h16_steps = (long)st.inner_h16_steps; out->inner_h16_sweeps = (long)st.inner_h16_sweeps;
     out->fused_solves = work->chol->fused_solves;
     out->fused_kernel_s = work->chol->last_fused ? work->chol->fused_kernel_s : 0.0;
     if (work->chol->last_fused) { out->factor_count = work->chol->fused_factor_count; out->linsolve = 2; }

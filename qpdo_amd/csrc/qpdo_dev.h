@@ -83,7 +83,9 @@ typedef struct {
     int64_t inner_refine_fp64_applies;  /* applications of S' with the fp64 matrices that formed those residuals */
     int64_t inner_refine_fallbacks;     /* inner solves redone by the fp64 CG (sweep cap reached, or a sweep that did not converge) */
     double  inner_refine_max_res_over_tol; /* largest accepted ||b - S' s|| / (tau ||b||) of the last qpdo_solve: <= 1 */
-    int64_t inner_x32_steps;            /* inner_steps whose two products staged the fp32 copies of their operands (pair-wide fp32 products) */
+    int64_t inner_x32_steps;            /* inner_steps whose two products staged the fp32 copies of their operands (pair-wide products, coarse ones included) */
+    int64_t inner_h16_steps;            /* inner_steps of coarse sweeps: both products streamed the half-precision images */
+    int64_t inner_h16_sweeps;           /* coarse sweeps among inner_refine_sweeps */
 } QdevStats;
 
 int qdev_device_count(void);

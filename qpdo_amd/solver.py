@@ -100,7 +100,8 @@ class Stats(C.Structure):
                 ("updown_solves", C.c_long), ("updown_rows", C.c_long), ("updown_rejects", C.c_long),
                 ("coupled_rows", C.c_long), ("coupled_solves", C.c_long), ("coupled_sweeps", C.c_long), ("coupled_rejects", C.c_long),
                 ("inner_refine_sweeps", C.c_long), ("inner_refine_fp64_applies", C.c_long), ("inner_refine_fallbacks", C.c_long),
-                ("inner_refine_max_res_over_tol", C.c_double), ("inner_x32_steps", C.c_long)]
+                ("inner_refine_max_res_over_tol", C.c_double), ("inner_x32_steps", C.c_long),
+                ("inner_h16_steps", C.c_long), ("inner_h16_sweeps", C.c_long)]
 
 
 API_SYMBOLS = ["qpdo_set_default_settings", "qpdo_setup", "qpdo_warm_start", "qpdo_solve", "qpdo_update_settings",
@@ -550,6 +551,14 @@ class QPDO:
         k = int(info[0])
         return (out[:k].copy() if which == "Arc" else out), k
 
+    def pcg_h16_product(self, dw, which, v):
+        """one product of the slab kernel's pair-wide half-precision instance after a fresh build of the compact matrices (qpdo_amd_pcg_probe,
+        mode 36 / 37): the values as the half-precision image holds them, v rounded to float32.  Returns the product, k and the exponent e
+        of the image's scale 2^e."""
+        out, info = self._pcg_probe(dw, 0.0, v, {"Arc": 36, "Atc": 37}[which])
+        k = int(info[0])
+        return (out[:k].copy() if which == "Arc" else out), k, int(info[1])
+
     _COMPACT_VECS = {"rowlist": (49, np.int32, "k"), "cidx": (50, np.int32, "m"), "dc": (51, np.float64, "k"),
                      "flag_bits": (52, np.uint64, "words"), "flag_wprefix": (53, np.int32, "words"), "pc_diag": (54, np.float64, "n"),
                      "s_diag": (55, np.float64, "k"), "defl_list": (56, np.int32, "defl_r"), "defl_Sinv": (57, np.float64, None)}
@@ -586,14 +595,16 @@ class QPDO:
 
     def download_compact_image(self, name):
         """the slab-major image of "Arc" or "Atc" as the slab kernel streams it (qpdo_amd_download_compact, which >= 64): seg as an
-        nrows x nslabs x 2 array of (start, length), vsm, and the slab-local indices; None where the matrix takes the plain kernel"""
+        nrows x nslabs x 2 array of (start, length), vsm, the slab-local indices and vsm16, the half-precision values as float16 (None where
+        the image has none); None where the matrix takes the plain kernel"""
         mat = {"Arc": 0, "Atc": 1}[name]
         g = self._compact_get(16 * mat, np.int64, 7)
         nrows, nnz, use_slab, nslabs, has_ci16 = int(g[0]), int(g[2]), int(g[3]), int(g[4]), int(g[6])
         if not use_slab:
             return None
         base = 64 + 16 * mat
-        return dict(seg=self._compact_get(base, np.int32, 2 * nrows * nslabs).reshape(nrows, nslabs, 2),
+        h16 = self._compact_get(59, np.int64, 2)               # [the images carry half-precision values, the exponent of their scale]
+        return dict(vsm16=self._compact_get(base + 3, np.float16, nnz) if h16[0] else None, h16_e=int(h16[1]) if h16[0] else None, seg=self._compact_get(base, np.int32, 2 * nrows * nslabs).reshape(nrows, nslabs, 2),
                     vsm=self._compact_get(base + 1, np.float64, nnz),
                     idx=self._compact_get(base + 2, np.uint16 if has_ci16 else np.int32, nnz))
 
