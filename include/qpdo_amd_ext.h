@@ -319,6 +319,14 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
 #define QPDO_AMD_PCG_INFO_LEN 1040
 int  qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, const double *v, double *out, int mode, double *info);
 int  qpdo_amd_download_compact(QPDOWorkspace *work, int which, void *dst, long count);
+/* The trip shape of the slab kernel's instance that streams values of value_bytes (8 double, 4 float, 2 half) against a staged operand
+ * of operand_bytes (8 double, 4 float): shape = {EPL, UNR, NSA, TPR}.  A lane group of TPR lanes walks a row segment in trips of EPL UNR TPR
+ * entries from the segment's start rounded down to EPL entries; lane l's load u of a trip holds the EPL entries from EPL (TPR u + l) on;
+ * entry EPL u + e of a lane's trip is added to the lane's partial sum (EPL u + e) mod NSA; the NSA sums are folded in pairs, in order, and
+ * the lanes' sums by a shuffle tree (offsets TPR / 2 down to 1); a row's segments are added in slab (operand_bytes 4: slab-pair) order.
+ * For tests that reproduce the kernel's summation order.  Needs no workspace and no GPU.  Returns 0, or -1 for a combination that no
+ * instance streams (8/8, 4/8, 4/4 and 2/4 exist) or a NULL shape. */
+int  qpdo_amd_slab_trip_shape(int value_bytes, int operand_bytes, int *shape);
 /* copy a device-resident vector to the host: 0 x, 1 Qx, 2 y, 3 mu, 4 d (factor weights),
  * 5 dx, 6 dy, 7 Ax, 8 Aty, 9 l, 10 u, 11 ybar, 12 xbar, 13 w (of the last loop pass that ran) */
 int  qpdo_amd_download(QPDOWorkspace *work, int which, double *dst);

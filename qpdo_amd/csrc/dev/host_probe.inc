@@ -349,6 +349,14 @@ int qdev_download_compact(QpdoDev *d, int which, void *dst, long count) {
     HIPCHK(hipStreamSynchronize(d->stream));
     return 0;
 }
+// the trip shape of a slab instance, for tests that reproduce its summation order (qpdo_amd_slab_trip_shape)
+int qdev_slab_trip_shape(int value_bytes, int operand_bytes, int *shape) {
+    if (value_bytes == 8 && operand_bytes == 8) return slab_trip_shape<double, double>(shape);
+    if (value_bytes == 4 && operand_bytes == 8) return slab_trip_shape<float, double>(shape);
+    if (value_bytes == 4 && operand_bytes == 4) return slab_trip_shape<float, float>(shape);
+    if (value_bytes == 2 && operand_bytes == 4) return slab_trip_shape<_Float16, float>(shape);
+    return -1;
+}
 int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host) {
     HIPCHK(hipSetDevice(d->device));
     DevCsr *M = mat_by_id(d, which);

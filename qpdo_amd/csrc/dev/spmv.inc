@@ -117,6 +117,12 @@ template <> struct SlabStream<double, double> { static constexpr int EPL = 2, UN
 template <> struct SlabStream<float, double>  { static constexpr int EPL = 4, UNR = SLAB_UNR32, NSA = EPL * UNR, TPR = SLAB_TPR; using Vec = float4; };
 template <> struct SlabStream<float, float>   { static constexpr int EPL = 4, UNR = SLAB_UNR32X, NSA = 8, TPR = SLAB_TPR; using Vec = float4; };     // (one sum per entry spills from 8 loads on)
 template <> struct SlabStream<_Float16, float> { static constexpr int EPL = 8, UNR = SLAB_UNR16, NSA = 8, TPR = SLAB_TPR16; using Vec = slab_h8; };
+template <class VT, class XT>
+static int slab_trip_shape(int *shape) {                // {EPL, UNR, NSA, TPR} for the host (qdev_slab_trip_shape)
+    using S = SlabStream<VT, XT>;
+    shape[0] = S::EPL; shape[1] = S::UNR; shape[2] = S::NSA; shape[3] = S::TPR;
+    return 0;
+}
 template <class VT, class XT, class Epi, bool I16, bool OVL, bool NT>
 __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done, int nrows, int ncols, int nslabs, int W,
                                                     int rows_per_wg, const int2 *__restrict__ seg, const int *__restrict__ cism,
@@ -202,27 +208,64 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
         double sa[NSA];
 #pragma unroll
         for (int u = 0; u < NSA; u++) sa[u] = 0.0;
+        // A trip in straight-line code, GB loads at a time.  Gathers: the operand of EVERY entry slot is read from LDS, whatever the slot's
+        // position -- an index word of a load is a slab-local index of the image or its zero padding, so the address is inside xs; only
+        // behind the last entry of a per-pass image that an earlier, larger pass wrote may a slot hold an index of that pass's wider slab,
+        // and an LDS read past the workgroup's allocation returns zero, is a read, and feeds a slot that does not count -- and the reads
+        // do not depend on each other: they are issued together and waited for together, not one LDS round trip per entry.
+        // Products: the slot at position p of the image counts when beg <= p < end.  Only the first load of a lane's trip can lie before
+        // beg (kb > beg - EPL), and there the test is one unsigned compare, p - beg < end - beg; every other load compares the entry's
+        // number with end - kk.  A slot that does not count adds +0.0 whatever was gathered for it: the select is on the product, so a
+        // NaN or an Inf of a column that the row does not touch, or of LDS that the last slab did not stage, never reaches a sum.  The
+        // pair's second slab (entries from mid on) is a second base pointer, chosen by the entry's number against mid - kk.  No `&&` or
+        // `||` in here: the compiler makes a branch per entry of their short circuit and sinks the gather under it.
+        constexpr int GB = X32 ? UNR : UNR / 2;         // (a double operand is two registers per gather: half a trip keeps every instance within 128)
+        const unsigned len = (unsigned)(end - beg);
         auto fma_trip = [&](const Vec *v, const IdxW *w, int k) {
 #pragma unroll
-            for (int u = 0; u < UNR; u++) {
-                const int kk = k + u * EPL * TPR;
-                double vv[EPL]; int ax[EPL];
-                if constexpr (H16) {
-                    const unsigned wd[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+            for (int u0 = 0; u0 < UNR; u0 += GB) {
+                XT xg[GB][EPL];
 #pragma unroll
-                    for (int e = 0; e < EPL; e++) { vv[e] = (double)(float)v[u][e]; ax[e] = (int)((e & 1) ? wd[e >> 1] >> 16 : wd[e >> 1] & 0xffffu); }
-                } else if constexpr (F32) {
-                    vv[0] = (double)v[u].x; vv[1] = (double)v[u].y; vv[2] = (double)v[u].z; vv[3] = (double)v[u].w;
-                    ax[0] = (int)(w[u].x & 0xffffu); ax[1] = (int)(w[u].x >> 16); ax[2] = (int)(w[u].y & 0xffffu); ax[3] = (int)(w[u].y >> 16);
-                } else {
-                    vv[0] = v[u].x; vv[1] = v[u].y;
-                    if constexpr (I16) { ax[0] = (int)(w[u] & 0xffffu); ax[1] = (int)(w[u] >> 16); }
-                    else               { ax[0] = w[u].x; ax[1] = w[u].y; }
+                for (int g = 0; g < GB; g++) {
+                    const int u = u0 + g;
+                    int ax[EPL];
+                    if constexpr (H16) {
+                        const unsigned wd[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
+#pragma unroll
+                        for (int e = 0; e < EPL; e++) ax[e] = (int)((e & 1) ? wd[e >> 1] >> 16 : wd[e >> 1] & 0xffffu);
+                    } else if constexpr (F32) {
+                        ax[0] = (int)(w[u].x & 0xffffu); ax[1] = (int)(w[u].x >> 16); ax[2] = (int)(w[u].y & 0xffffu); ax[3] = (int)(w[u].y >> 16);
+                    } else {
+                        if constexpr (I16) { ax[0] = (int)(w[u] & 0xffffu); ax[1] = (int)(w[u] >> 16); }
+                        else               { ax[0] = w[u].x; ax[1] = w[u].y; }
+                    }
+                    const int tm = mid - (k + u * EPL * TPR);
+#pragma unroll
+                    for (int e = 0; e < EPL; e++) {
+                        if constexpr (X32) { const XT *xb = e >= tm ? xs + W : xs; xg[g][e] = xb[ax[e]]; }
+                        else               xg[g][e] = xs[ax[e]];
+                    }
                 }
 #pragma unroll
-                for (int e = 0; e < EPL; e++) {         // (kk + EPL - 1 >= beg always: kb > beg - EPL)
-                    const double pe = vv[e] * (double)xs[ax[e] + ((X32 && kk + e >= mid) ? W : 0)];
-                    sa[(EPL * u + e) % NSA] += ((e == EPL - 1 || kk + e >= beg) && kk + e < end) ? pe : 0.0;
+                for (int g = 0; g < GB; g++) {
+                    const int u = u0 + g, kk = k + u * EPL * TPR;
+                    double vv[EPL];
+                    if constexpr (H16) {
+#pragma unroll
+                        for (int e = 0; e < EPL; e++) vv[e] = (double)(float)v[u][e];
+                    } else if constexpr (F32) {
+                        vv[0] = (double)v[u].x; vv[1] = (double)v[u].y; vv[2] = (double)v[u].z; vv[3] = (double)v[u].w;
+                    } else {
+                        vv[0] = v[u].x; vv[1] = v[u].y;
+                    }
+                    const unsigned t = (unsigned)(kk - beg);
+                    const int hi = end - kk;
+#pragma unroll
+                    for (int e = 0; e < EPL; e++) {
+                        const double pe = vv[e] * (double)xg[g][e];
+                        const bool in = u == 0 ? t + (unsigned)e < len : e < hi;
+                        sa[(EPL * u + e) % NSA] += in ? pe : 0.0;
+                    }
                 }
             }
         };

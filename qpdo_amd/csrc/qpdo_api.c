@@ -940,6 +940,11 @@ int qpdo_amd_download_compact(QPDOWorkspace *work, int which, void *dst, long co
     if (!work || !work->chol || !work->chol->dev) { qdev_set_error("download compact: NULL workspace"); return -1; }
     return qdev_download_compact(work->chol->dev, which, dst, count) ? -1 : 0;
 }
+int qpdo_amd_slab_trip_shape(int value_bytes, int operand_bytes, int *shape) {
+    if (!shape) { qdev_set_error("slab trip shape: NULL shape"); return -1; }
+    if (qdev_slab_trip_shape(value_bytes, operand_bytes, shape)) { qdev_set_error("slab trip shape: no instance streams that value and operand width (bytes: 8/8, 4/8, 4/4, 2/4)"); return -1; }
+    return 0;
+}
 int qpdo_amd_download(QPDOWorkspace *work, int which, double *dst) { return qdev_download_vec(work->chol->dev, which, dst); }
 int qpdo_amd_get_stats(const QPDOWorkspace *work, QPDOAmdStats *out) {
     QdevStats st;

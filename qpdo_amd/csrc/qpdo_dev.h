@@ -228,6 +228,8 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count);
 #define QDEV_PCG_INFO_LEN (16 + 1024)
 int qdev_pcg_probe(QpdoDev *d, const double *dw, double sigma, const double *v, double *out, int mode, double *info);
 int qdev_download_compact(QpdoDev *d, int which, void *dst, long count);
+/* {EPL, UNR, NSA, TPR} of the slab kernel's instance for a value and an operand width in bytes (dev/spmv.inc SlabStream); -1: no such instance */
+int qdev_slab_trip_shape(int value_bytes, int operand_bytes, int *shape);
 /* standalone piecewise-affine linesearch for parity tests (2m entries) */
 int qdev_linesearch(QpdoDev *d, double eta, double beta, const double *delta, const double *alpha,
                     double *tau);

@@ -120,7 +120,7 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_small_factor_layout", "qpdo_amd_fleet_factor_layout", "qpdo_amd_batch_factor_layout",
                "qpdo_amd_fleet_device", "qpdo_amd_fleet_packed_layout", "qpdo_amd_fleet_get_packed_layout", "qpdo_amd_fleet_update_dev",
                "qpdo_amd_fleet_warm_start_dev", "qpdo_amd_fleet_warm_start_last_dev", "qpdo_amd_fleet_solve_dev", "qpdo_amd_fleet_fetch_last",
-               "qpdo_amd_fleet_sync"]
+               "qpdo_amd_fleet_sync", "qpdo_amd_slab_trip_shape"]
 
 
 class FleetStats(C.Structure):
@@ -228,6 +228,9 @@ def lib():
             L.qpdo_amd_fleet_solve_dev.argtypes = [C.c_void_p, vp, vp, vp, vp, vp, vp, C.c_long, C.c_long, vp]
             L.qpdo_amd_fleet_fetch_last.argtypes = [C.c_void_p, pp, pp, C.POINTER(QPDOInfo)]
             L.qpdo_amd_fleet_sync.argtypes = [C.c_void_p, C.POINTER(FleetDevStats)]
+        if hasattr(L, "qpdo_amd_slab_trip_shape"):          # (absent from an older build, as below)
+            L.qpdo_amd_slab_trip_shape.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
+            L.qpdo_amd_slab_trip_shape.restype = C.c_int
         if hasattr(L, "qpdo_amd_small_factor_layout"):      # (absent from an older build named by QPDO_AMD_LIB for A/B timing: calling it there raises)
             L.qpdo_amd_small_factor_layout.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), C.POINTER(QPDOSettings), C.c_int, C.POINTER(C.c_long)]
             L.qpdo_amd_small_factor_layout.restype = C.c_int
@@ -254,6 +257,15 @@ class PcgNaN(RuntimeError):
 
 class LostProducer(RuntimeError):
     """qpdo_amd_direct_solve: a polling kernel lost its producer, or the band factorization met a bad pivot"""
+
+
+def slab_trip_shape(value_bytes, operand_bytes):
+    """(EPL, UNR, NSA, TPR) of the slab kernel's instance that streams values of value_bytes against a staged operand of operand_bytes
+    (qpdo_amd_slab_trip_shape: 8/8, 4/8, 4/4, 2/4); what a reproduction of the kernel's summation order needs.  No GPU is touched."""
+    shape = (C.c_int * 4)()
+    if lib().qpdo_amd_slab_trip_shape(int(value_bytes), int(operand_bytes), shape):
+        raise ValueError("slab_trip_shape: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+    return tuple(shape)
 
 
 def device_count():
