@@ -531,7 +531,33 @@ int  qpdo_amd_fleet_get_certificates(const QPDOAmdFleet *f, long item, c_float *
  *          After a solve_dev, qpdo_amd_fleet_get_certificates is refused ("no solve yet") until a fetch_last has made the host image current.
  * sync     waits for that event, i.e. for everything the fleet was asked to do; fills the counters (out may be NULL), refreshes
  *          last_kernel_seconds of QPDOAmdFleetStats from the last solve_dev, and resets the refusal record.
- * Stats    solve_launches and solves grow by 1 per solve_dev; vector_bytes_uploaded_last_call is 0 after update_dev / warm_start_dev. */
+ * Stats    solve_launches and solves grow by 1 per solve_dev; vector_bytes_uploaded_last_call is 0 after update_dev / warm_start_dev.
+ * ---- new Q / A VALUES from device arrays (a fleet created with QPDO_AMD_FLEET_MATRIX_UPDATES): the first call of the real-time-iteration
+ * step  update_matrices_dev -> update_dev(q, l, u) -> warm_start_last_dev -> solve_dev, which then runs on the caller's stream from end to
+ * end without a host wait.  The pattern is fixed at create, so the call carries VALUES ONLY and compares no pattern.
+ * CONTRACT  After the call every item that took a matrix is, bit for bit, what qpdo_amd_fleet_update_matrices leaves when given the same
+ *          values for the same items: what qpdo_setup leaves for the new matrix or matrices, the latest values of the one not taken, the
+ *          latest unscaled q, l, u, c and the fleet's settings; status QPDO_UNSOLVED, no pending warm start, and warm_start_last(_dev) still
+ *          starts from the x, y of the previous solve.  An item that takes neither matrix is not touched (state, status, pending warm start).
+ * PACKED VALUE LAYOUT  The stored values of all items' Q live back to back in ONE array of NQ = sum nnzQ_i doubles, item i at qoff[i], in
+ *          the order of data[i]->Q->x at create (the caller's stored triangle for stype +-1, the full matrix for stype 0); the CSC values of
+ *          all items' A in one array of NA = sum nnzA_i doubles, item i at aoff[i], in the order of data[i]->A->x.  An item with m = 0, or with
+ *          a Q that stores no entry, occupies nothing.  qpdo_amd_fleet_packed_matrix_layout fills count + 1 entries each, the last one the
+ *          total, as pure host arithmetic (either itype, no device needed); qpdo_amd_fleet_get_packed_matrix_layout does the same for an
+ *          existing fleet and is refused for one created without the flag.  q_len / a_len must equal NQ / NA.
+ * update_matrices_dev  Qx (NQ) / Ax (NA): device (or managed) arrays on the fleet's device; NULL: that matrix is unchanged for all items; both
+ *          NULL: returns 0 and launches nothing.  item_mask: optional, `count` int32 on the device, bit 0 = the item takes Q from Qx, bit 1 = A
+ *          from Ax; a clear bit (or a NULL array) leaves that matrix unchanged for the item; NULL mask: every item takes every array passed.
+ *          Checks, all on the host before any launch (a refused call has launched nothing): NULL fleet; a fleet without the flag; q_len != NQ
+ *          or a_len != NA (the message names both numbers); a passed pointer that is not device or managed memory of the fleet's device (the
+ *          message names Qx, Ax or item_mask).  The values themselves are not examined, as in the host call.
+ *          Cost: no upload, no host copy, no stream synchronisation, no event timing.  TWO launches on `stream`: one workgroup per item
+ *          copies the values taken into the fleet's matrix staging (8 bytes read and written per entry taken) and writes the item's table
+ *          entry, then the host call's own kernel runs unchanged.  A table of 2 (count + 1) int32 offsets is uploaded once, at create.
+ *          ORDER is that of the other device calls (above); hipGraph capture stays unsupported.
+ * Stats    QPDOAmdFleetMatrixStats after a device call that launched: calls + 1; value_bytes_uploaded_last_call 0; items_last_call -1 (which
+ *          items took a matrix is known on the device only); last_kernel_seconds keeps the last HOST call's figure.  resident_extra_bytes
+ *          includes the offset table.  solve_launches and solves of QPDOAmdFleetStats do not move. */
 typedef struct {
     long update_calls, warm_start_calls, solve_calls;   /* device calls that launched, since create (warm_start_last_dev counts as a warm start) */
     long refused_items;                     /* items refused by update_dev calls (l > u) since the last sync ... */
@@ -546,6 +572,9 @@ int  qpdo_amd_fleet_warm_start_dev(QPDOAmdFleet *f, const double *x0, const doub
 int  qpdo_amd_fleet_warm_start_last_dev(QPDOAmdFleet *f, void *stream);
 int  qpdo_amd_fleet_solve_dev(QPDOAmdFleet *f, double *x, double *y, long *status, double *norms, double *prim_inf_cert, double *dual_inf_cert, long n_len, long m_len,
                               void *stream);
+int  qpdo_amd_fleet_packed_matrix_layout(long count, const QPDOData *const *data, long *qoff, long *aoff);
+int  qpdo_amd_fleet_get_packed_matrix_layout(const QPDOAmdFleet *f, long *qoff, long *aoff);
+int  qpdo_amd_fleet_update_matrices_dev(QPDOAmdFleet *f, const double *Qx, const double *Ax, const int *item_mask, long q_len, long a_len, void *stream);
 int  qpdo_amd_fleet_fetch_last(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info);
 int  qpdo_amd_fleet_sync(QPDOAmdFleet *f, QPDOAmdFleetDevStats *out);
 void qpdo_amd_fleet_destroy(QPDOAmdFleet *f);

@@ -6,7 +6,8 @@
 //   warm start  k_small_fleet, op 1/2  the shared solve body in mode 1 (qpdo.c:217-299)
 //   solve       k_small_fleet, op 0    the shared solve body from the item's state (mode 2), or from zero (mode 0)
 //   new Q / A   k_small_fleet_matrices the new values into the item's three CSR images, then the item's setup again (flag MATRIX_UPDATES)
-// each ONE launch for the whole fleet, in the oracle's operation order: item i carries the bits of a workspace of its own.
+// each ONE launch for the whole fleet, in the oracle's operation order: item i carries the bits of a workspace of its own.  The *_dev calls
+// put a gather (k_small_fleet_gather, k_small_fleet_gather_matrices) in front of the same kernels and a scatter behind the solve.
 
 // What qpdo_setup leaves behind for the item's unscaled matrices, q, l, u, everything but tpos (a function of the pattern): the state zeroed,
 // Ruiz + cost scaling, the record of a fresh workspace.  ONE copy, for create (k_small_fleet_setup) and for new matrix values
@@ -160,6 +161,26 @@ __global__ __launch_bounds__(FLEET_IO_THREADS) void k_small_fleet_gather(int cou
         if (bad) { atomicAdd(rec, 1); atomicMin(rec + 1, b); }
     }
 }
+// The matrix counterpart (qpdo_amd_fleet_update_matrices_dev): the caller's PACKED value arrays -- the stored values of all items' Q back to
+// back, item i at offs[i], the CSC values of all items' A, item i at offs[count + 1 + i]; offs[count] = NQ and offs[2 count + 1] = NA are the
+// totals -- on one side, the matrix staging and the two-int table that k_small_fleet_matrices already reads on the other.  Bit 0 of the mask:
+// the item takes Q, bit 1: A (mask NULL: both).  A matrix of the item is TAKEN when its array is passed and its bit is set: it is copied to
+// the fixed place stage[offs q | NQ + offs a] and the table entry names that place -- also for a matrix without a stored entry, where the
+// place is a valid offset and nothing is copied (the consumer's test is >= 0) --; the other gets -1, "unchanged".
+__global__ __launch_bounds__(FLEET_IO_THREADS) void k_small_fleet_gather_matrices(int count, const int *offs, const double *Qx, const double *Ax, const int *mask,
+                                                                                  int *tab, double *stage) {
+    if ((int)blockIdx.x >= count) return;
+    const int b = blockIdx.x;
+    const int qo = __builtin_amdgcn_readfirstlane(offs[b]), nq = __builtin_amdgcn_readfirstlane(offs[b + 1]) - qo;
+    const int ao = __builtin_amdgcn_readfirstlane(offs[count + 1 + b]), na = __builtin_amdgcn_readfirstlane(offs[count + 2 + b]) - ao;
+    const int NQ = __builtin_amdgcn_readfirstlane(offs[count]);
+    const int mk = mask ? __builtin_amdgcn_readfirstlane(mask[b]) : 3;
+    const int tQ = Qx && (mk & 1), tA = Ax && (mk & 2);
+    const int sQ = qo, sA = NQ + ao;
+    if (tQ) { const double *src = Qx + qo; double *dst = stage + sQ; FOR_T(k, nq) dst[k] = src[k]; }
+    if (tA) { const double *src = Ax + ao; double *dst = stage + sA; FOR_T(k, na) dst[k] = src[k]; }
+    if (threadIdx.x == 0) { int *t = tab + 2 * b; t[0] = tQ ? sQ : -1; t[1] = tA ? sA : -1; }
+}
 // After k_small_fleet op 0: what qpdo_amd_fleet_solve delivers for item i, into the caller's packed arrays (a NULL array is not wanted).  x, y:
 // NaN at status -3 / -4; prim_inf_cert (m): the item's dy at -3, dual_inf_cert (n): its dx at -4, NaN otherwise (the rule of the reference's
 // mex gateway); status: status_val, iterations, oterations; norms: res_prim, res_dual, res_prim_in, res_dual_in, objective.
@@ -209,6 +230,8 @@ struct SmallFleet {
     char *dmstage = nullptr, *hmstage = nullptr;    // a matrix call's [table: 2 ints per item][values], device and pinned
     size_t mstage_doubles = 0;
     long m_calls = 0, m_items_last = 0, m_bytes_last = 0, m_extra_bytes = 0; double m_kernel_s = 0.0;
+    int *dmoffs = nullptr;                          // the packed value layout [qoff: count + 1][aoff: count + 1] of update_matrices_dev
+    std::vector<long> qoff, aoff;
     // device-resident inputs and outputs (the *_dev calls; DESIGN.md 3.6)
     hipEvent_t ev_chain = nullptr;                  // recorded at the end of every fleet call on the stream it used; the next call's stream waits for it
     int *doffs = nullptr, *drec = nullptr;          // the packed layout [noff: count + 1][moff: count + 1], then the refusal record {items, smallest item}
@@ -233,6 +256,7 @@ static void fleet_free(SmallFleet *F) {
     if (F->hrec) (void)hipHostFree(F->hrec);
     if (F->ev_chain) (void)hipEventDestroy(F->ev_chain);
     if (F->dmstage) (void)hipFree(F->dmstage);
+    if (F->dmoffs) (void)hipFree(F->dmoffs);
     if (F->hmstage) (void)hipHostFree(F->hmstage);
     if (F->hstage) (void)hipHostFree(F->hstage);
     if (F->hout) (void)hipHostFree(F->hout);
@@ -265,6 +289,7 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     std::vector<SmallRes> hr((size_t)count);
     std::vector<size_t> o_rec((size_t)count);
     std::vector<int> hoffs(2 * ((size_t)count + 1) + 2);        // the packed layout and the empty refusal record, as uploaded
+    std::vector<int> hmoffs(mu ? 2 * ((size_t)count + 1) : 0);  // MATRIX_UPDATES: the packed value layout, as uploaded
     char *h = nullptr;
     size_t total = 0, nmax = 1, mmax = 0, stage = 0;
     auto reserve = [&](size_t bytes) { size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; };
@@ -284,7 +309,10 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
             X.mapA = reserve_extra(L.nnzA * 4 + 4);
             X.has_mapQ = d->Q->stype != 0;
             if (X.has_mapQ) X.mapQ = reserve_extra(L.nnzQ * 4 + 4);
-            mstage += L.nnzA + (size_t)idx_at(d->Q->p, d->Q->itype, (long long)d->Q->ncol);      // the largest call: every stored entry of every Q and A
+            const size_t storedQ = (size_t)idx_at(d->Q->p, d->Q->itype, (long long)d->Q->ncol);
+            mstage += L.nnzA + storedQ;              // the largest call: every stored entry of every Q and A
+            if (i == 0) { F->qoff.push_back(0); F->aoff.push_back(0); }
+            F->qoff.push_back(F->qoff.back() + (long)storedQ); F->aoff.push_back(F->aoff.back() + (long)L.nnzA);
         }
     }
     if (mstage >= 2147483647ULL) { snprintf(s_err, sizeof(s_err), "fleet: %zu matrix entries per call exceed the 2^31 the call table can address; split the fleet", mstage); delete F; return nullptr; }
@@ -293,6 +321,7 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     F->noff.push_back(F->noff.back() + (long)data[count - 1]->n); F->moff.push_back(F->moff.back() + (long)data[count - 1]->m);
     for (long i = 0; i <= count; i++) { hoffs[(size_t)i] = (int)F->noff[(size_t)i]; hoffs[(size_t)(count + 1 + i)] = (int)F->moff[(size_t)i]; }    // (N + 2 M = stage < 2^31)
     hoffs[2 * ((size_t)count + 1)] = 0; hoffs[2 * ((size_t)count + 1) + 1] = FLEET_REC_NONE;
+    if (mu) for (long i = 0; i <= count; i++) { hmoffs[(size_t)i] = (int)F->qoff[(size_t)i]; hmoffs[(size_t)(count + 1 + i)] = (int)F->aoff[(size_t)i]; }  // (NQ + NA = mstage < 2^31)
     const size_t upload_bytes = total;
     for (long i = 0; i < count; i++) {
         const QPDOData *d = data[i]; Lay &L = lay[(size_t)i];
@@ -329,7 +358,8 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
         F->mstage_doubles = mstage;
         SHIP(hipMalloc((void **)&F->dmstage, mbytes));
         SHIP(hipHostMalloc((void **)&F->hmstage, mbytes, hipHostMallocDefault));
-        F->m_extra_bytes = (long)(extra + mbytes);
+        SHIP(hipMalloc((void **)&F->dmoffs, hmoffs.size() * sizeof(int)));
+        F->m_extra_bytes = (long)(extra + mbytes + hmoffs.size() * sizeof(int));
         F->pat.resize((size_t)count);
     }
     SHIP(hipHostMalloc((void **)&F->hout, out_bytes ? out_bytes : 1, hipHostMallocDefault));
@@ -390,6 +420,7 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     SHIP(hipMemcpyAsync(F->dprobs, hp.data(), (size_t)count * sizeof(SmallQP), hipMemcpyHostToDevice, F->stream));
     SHIP(hipMemcpyAsync(F->dres, hr.data(), (size_t)count * sizeof(SmallRes), hipMemcpyHostToDevice, F->stream));
     SHIP(hipMemcpyAsync(F->doffs, hoffs.data(), hoffs.size() * sizeof(int), hipMemcpyHostToDevice, F->stream));
+    if (mu) SHIP(hipMemcpyAsync(F->dmoffs, hmoffs.data(), hmoffs.size() * sizeof(int), hipMemcpyHostToDevice, F->stream));
     SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
     hipLaunchKernelGGL(k_small_fleet_setup, dim3((unsigned)count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)count, F->st);
     SHIP(hipGetLastError());
@@ -611,6 +642,45 @@ int qdev_small_fleet_warm_start_dev(void *h_, const double *x0, const double *y0
     F->vector_bytes_last = 0; F->d_warm_starts++;
 done:
     return rc;
+}
+// New Q / A values from the caller's packed device arrays (layout: qdev_small_fleet_packed_matrix_layout).  The pattern is fixed at create
+// and the arrays carry values only, so there is nothing to compare: the gather fills the staging and the table, k_small_fleet_matrices
+// runs behind it as in the host call.  No event timing: m_kernel_s keeps the last host call's figure.
+static const char *const FLEET_NO_MATRIX_FLAG = "the fleet was created without QPDO_AMD_FLEET_MATRIX_UPDATES (qpdo_amd_fleet_create_ex)";   // (the host call's message)
+int qdev_small_fleet_update_matrices_dev(void *h_, const double *Qx, const double *Ax, const int *item_mask, long q_len, long a_len, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    hipStream_t s = (hipStream_t)stream_;
+    if (!(F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES)) { snprintf(s_err, sizeof(s_err), "%s", FLEET_NO_MATRIX_FLAG); return -1; }
+    const long NQ = F->qoff.back(), NA = F->aoff.back();
+    if (q_len != NQ) { snprintf(s_err, sizeof(s_err), "q_len is %ld, the fleet's packed Q values have %ld elements", q_len, NQ); return -1; }
+    if (a_len != NA) { snprintf(s_err, sizeof(s_err), "a_len is %ld, the fleet's packed A values have %ld elements", a_len, NA); return -1; }
+    SHIP(hipSetDevice(F->device));
+    if (fleet_dev_ptr(F, Qx, "Qx") || fleet_dev_ptr(F, Ax, "Ax") || fleet_dev_ptr(F, item_mask, "item_mask")) return -1;
+    if (!Qx && !Ax) return 0;
+    {
+        const size_t tab_bytes = (size_t)F->count * QPDO_AMD_FLEET_MATRIX_TABLE_BYTES;
+        SHIP(fleet_enter(F, s));
+        // dmstage is shared with the host matrix call.  No new hazard: both calls wait for the chain event before they write it, this one
+        // records the event behind the consumer kernel, and the host call ends in its own stream sync -- so whichever call comes next
+        // starts writing only after the previous call's k_small_fleet_matrices has read the table and the values.
+        hipLaunchKernelGGL(k_small_fleet_gather_matrices, dim3((unsigned)F->count), dim3(FLEET_IO_THREADS), 0, s, (int)F->count, (const int *)F->dmoffs, Qx, Ax, item_mask,
+                           (int *)F->dmstage, (double *)(F->dmstage + tab_bytes));
+        SHIP(hipGetLastError());
+        hipLaunchKernelGGL(k_small_fleet_matrices, dim3((unsigned)F->count), dim3(SM_THREADS), 0, s, F->dprobs, (int)F->count, F->st,
+                           (const int *)F->dmstage, (const double *)(F->dmstage + tab_bytes));
+        SHIP(hipGetLastError());
+        SHIP(fleet_leave(F, s));
+        F->m_calls++; F->m_items_last = -1; F->m_bytes_last = 0;      // (which items took a matrix is known on the device only)
+    }
+done:
+    return rc;
+}
+int qdev_small_fleet_packed_matrix_layout(const void *h_, long *qoff, long *aoff) {
+    const SmallFleet *F = (const SmallFleet *)h_;
+    if (!(F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES)) { snprintf(s_err, sizeof(s_err), "%s", FLEET_NO_MATRIX_FLAG); return -1; }
+    memcpy(qoff, F->qoff.data(), F->qoff.size() * sizeof(long)); memcpy(aoff, F->aoff.data(), F->aoff.size() * sizeof(long));
+    return 0;
 }
 int qdev_small_fleet_solve_dev(void *h_, double *x, double *y, long *status, double *norms, double *prim_inf_cert, double *dual_inf_cert, long n_len, long m_len, void *stream_) {
     int rc = 0;

@@ -1228,6 +1228,28 @@ int qpdo_amd_fleet_solve_dev(QPDOAmdFleet *f, double *x, double *y, long *status
     if (qdev_small_fleet_solve_dev(f, x, y, status, norms, prim_inf_cert, dual_inf_cert, n_len, m_len, stream)) return fleet_dev_failed("qpdo_amd_fleet_solve_dev");
     return 0;
 }
+/* the packed VALUE layout of update_matrices_dev: the stored entries of every Q and of every A, pure host arithmetic (either itype) */
+static long fleet_stored_entries(const cholmod_sparse *M) { return (M && M->p) ? (long)idx_at(M->p, M->itype, (int64_t)M->ncol) : 0L; }
+int qpdo_amd_fleet_packed_matrix_layout(long count, const QPDOData *const *data, long *qoff, long *aoff) {
+    if (count <= 0) return fleet_refuse("qpdo_amd_fleet_packed_matrix_layout: count must be positive");
+    if (!data) return fleet_refuse("qpdo_amd_fleet_packed_matrix_layout: NULL data array");
+    if (!qoff || !aoff) return fleet_refuse("qpdo_amd_fleet_packed_matrix_layout: NULL output");
+    for (long i = 0; i < count; i++) if (!data[i]) return fleet_refuse("qpdo_amd_fleet_packed_matrix_layout: NULL item");
+    qoff[0] = aoff[0] = 0;
+    for (long i = 0; i < count; i++) { qoff[i + 1] = qoff[i] + fleet_stored_entries(data[i]->Q); aoff[i + 1] = aoff[i] + fleet_stored_entries(data[i]->A); }
+    return 0;
+}
+int qpdo_amd_fleet_get_packed_matrix_layout(const QPDOAmdFleet *f, long *qoff, long *aoff) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_get_packed_matrix_layout: NULL fleet");
+    if (!qoff || !aoff) return fleet_refuse("qpdo_amd_fleet_get_packed_matrix_layout: NULL output");
+    if (qdev_small_fleet_packed_matrix_layout(f, qoff, aoff)) return fleet_dev_failed("qpdo_amd_fleet_get_packed_matrix_layout");
+    return 0;
+}
+int qpdo_amd_fleet_update_matrices_dev(QPDOAmdFleet *f, const double *Qx, const double *Ax, const int *item_mask, long q_len, long a_len, void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_update_matrices_dev: NULL fleet");
+    if (qdev_small_fleet_update_matrices_dev(f, Qx, Ax, item_mask, q_len, a_len, stream)) return fleet_dev_failed("qpdo_amd_fleet_update_matrices_dev");
+    return 0;
+}
 int qpdo_amd_fleet_fetch_last(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info) {
     if (!f) return fleet_refuse("qpdo_amd_fleet_fetch_last: NULL fleet");
     if (!info) return fleet_refuse("qpdo_amd_fleet_fetch_last: NULL info array");

@@ -269,6 +269,10 @@ int   qdev_small_fleet_solve_dev(void *fleet, double *x, double *y, long *status
 int   qdev_small_fleet_fetch_last(void *fleet, double *const *x, double *const *y, void *info /* QPDOInfo[count] */);
 int   qdev_small_fleet_sync(void *fleet, long *out5);
 void  qdev_small_fleet_packed_layout(const void *fleet, long *noff, long *moff);
+/* new Q / A values from packed device arrays (values only: the pattern is the create-time one); checks inside, as above.  The layout getter is
+ * refused (nonzero, qdev_small_last_error()) for a fleet without QPDO_AMD_FLEET_MATRIX_UPDATES */
+int   qdev_small_fleet_update_matrices_dev(void *fleet, const double *Qx, const double *Ax, const int *item_mask, long q_len, long a_len, void *stream);
+int   qdev_small_fleet_packed_matrix_layout(const void *fleet, long *qoff, long *aoff);
 void  qdev_small_fleet_destroy(void *fleet);
 
 /* ---- ONE small workspace through the fused kernel (the default path of qpdo_solve for problems whose whole state fits one

@@ -120,7 +120,8 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_small_factor_layout", "qpdo_amd_fleet_factor_layout", "qpdo_amd_batch_factor_layout",
                "qpdo_amd_fleet_device", "qpdo_amd_fleet_packed_layout", "qpdo_amd_fleet_get_packed_layout", "qpdo_amd_fleet_update_dev",
                "qpdo_amd_fleet_warm_start_dev", "qpdo_amd_fleet_warm_start_last_dev", "qpdo_amd_fleet_solve_dev", "qpdo_amd_fleet_fetch_last",
-               "qpdo_amd_fleet_sync", "qpdo_amd_slab_trip_shape"]
+               "qpdo_amd_fleet_sync", "qpdo_amd_slab_trip_shape",
+               "qpdo_amd_fleet_packed_matrix_layout", "qpdo_amd_fleet_get_packed_matrix_layout", "qpdo_amd_fleet_update_matrices_dev"]
 
 
 class FleetStats(C.Structure):
@@ -228,6 +229,10 @@ def lib():
             L.qpdo_amd_fleet_solve_dev.argtypes = [C.c_void_p, vp, vp, vp, vp, vp, vp, C.c_long, C.c_long, vp]
             L.qpdo_amd_fleet_fetch_last.argtypes = [C.c_void_p, pp, pp, C.POINTER(QPDOInfo)]
             L.qpdo_amd_fleet_sync.argtypes = [C.c_void_p, C.POINTER(FleetDevStats)]
+            if hasattr(L, "qpdo_amd_fleet_update_matrices_dev"):    # (new matrix values from device arrays; absent from an older build)
+                L.qpdo_amd_fleet_packed_matrix_layout.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), lp, lp]
+                L.qpdo_amd_fleet_get_packed_matrix_layout.argtypes = [C.c_void_p, lp, lp]
+                L.qpdo_amd_fleet_update_matrices_dev.argtypes = [C.c_void_p, vp, vp, vp, C.c_long, C.c_long, vp]
         if hasattr(L, "qpdo_amd_slab_trip_shape"):          # (absent from an older build, as below)
             L.qpdo_amd_slab_trip_shape.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
             L.qpdo_amd_slab_trip_shape.restype = C.c_int
@@ -867,6 +872,56 @@ def check_device_tensor(name, t, device_index, dtype, count):
     return t.data_ptr()
 
 
+def _fleet_mat_views(dims, qstype, mats, which):
+    """list of `count` scipy matrices (None entries allowed) -> (array of cholmod_sparse pointers or None, what they point into, the views
+    by item: header and value array); converted as Batch converts at create.  which: "Q" (n x n, in the item's create-time Qstype storage) or "A" (m x n).
+    dims: the items' (n, m); qstype: their create-time Qstype.  Host arithmetic: no fleet, no device."""
+    if mats is None:
+        return None, [], {}
+    count = len(dims)
+    if len(mats) != count:
+        raise ValueError("%s: expected a list of %d matrices, got %d" % (which, count, len(mats)))
+    keep, views, arr = [], {}, (C.POINTER(CholmodSparse) * count)()
+    for i, M in enumerate(mats):
+        if M is None:
+            continue
+        n, m = dims[i]
+        shape = (n, n) if which == "Q" else (m, n)
+        M = sp.csc_matrix(M)
+        if M.shape != shape:
+            raise ValueError("%s[%d]: expected shape %r, got %r" % (which, i, shape, M.shape))
+        view = _sparse_view(M, qstype[i] if which == "Q" else 0, keep)
+        views[i] = (view, keep[-1])                          # (the header and the value array its x points to)
+        keep.append(view)
+        arr[i] = C.pointer(view)
+    return arr, keep, views
+
+
+def pack_matrix_values(dims, qstype, qoff, aoff, Q=None, A=None):
+    """Lists of `count` scipy matrices (None entries and None lists allowed, as Fleet.update_matrices takes them) -> (Q_values, A_values,
+    mask): the float64 arrays of the packed value layout (qoff / aoff: count + 1 offsets each, the last one the total; None for a None
+    list) and the int32 mask those lists imply, bit 0 = the item has a Q entry, bit 1 = an A entry.  Every matrix goes through the
+    conversion the host call hands to the library (_fleet_mat_views), and the values are read from THAT header: their order is the
+    create-time one by construction.  Items without an entry keep zeros.  A function of the problems' host images: no fleet, no device."""
+    count = len(dims)
+    mask = np.zeros(count, np.int32)
+    out = []
+    for which, mats, off, bit in (("Q", Q, qoff, 1), ("A", A, aoff, 2)):
+        _, _, views = _fleet_mat_views(dims, qstype, mats, which)
+        if mats is None:
+            out.append(None)
+            continue
+        vals = np.zeros(int(off[count]), np.float64)
+        for i, (_, x) in views.items():
+            nnz = int(off[i + 1] - off[i])
+            if len(x) != nnz:
+                raise ValueError("%s[%d]: %d stored entries, the pattern at create has %d" % (which, i, len(x), nnz))
+            vals[int(off[i]):int(off[i + 1])] = x
+            mask[i] |= bit
+        out.append(vals)
+    return out[0], out[1], mask
+
+
 class Fleet:
     """A resident fleet of small QPs (qpdo_amd_fleet_*): set up once, then per control step update() / warm_start_last() / solve(), one
     launch each for all items.  Item i carries the bits of a QPDO workspace of its own driven through the same calls.  The settings are
@@ -899,6 +954,7 @@ class Fleet:
         self._info = (QPDOInfo * self.count)()
         self.kernel_seconds = 0.0
         self._layout, self._device, self._dev_out = None, None, None     # (the device calls: filled on first use)
+        self._mlayout = None
 
     def _ptrs(self, vecs, which, clip=False):
         """list of `count` vectors (None entries allowed) -> (array of pointers or None, the arrays kept alive)"""
@@ -933,22 +989,7 @@ class Fleet:
     def _mat_ptrs(self, mats, which):
         """list of `count` scipy matrices (None entries allowed) -> (array of cholmod_sparse pointers or None, what they point into); converted
         as Batch converts at create.  which: "Q" (n x n, in the item's create-time Qstype storage) or "A" (m x n)"""
-        if mats is None:
-            return None, []
-        if len(mats) != self.count:
-            raise ValueError("%s: expected a list of %d matrices, got %d" % (which, self.count, len(mats)))
-        keep, arr = [], (C.POINTER(CholmodSparse) * self.count)()
-        for i, M in enumerate(mats):
-            if M is None:
-                continue
-            n, m = self.dims[i]
-            shape = (n, n) if which == "Q" else (m, n)
-            M = sp.csc_matrix(M)
-            if M.shape != shape:
-                raise ValueError("%s[%d]: expected shape %r, got %r" % (which, i, shape, M.shape))
-            view = _sparse_view(M, self._qstype[i] if which == "Q" else 0, keep)
-            keep.append(view)
-            arr[i] = C.pointer(view)
+        arr, keep, _ = _fleet_mat_views(self.dims, self._qstype, mats, which)
         return arr, keep
 
     def update_matrices(self, Q=None, A=None):
@@ -1046,6 +1087,32 @@ class Fleet:
         u = None if u is None else torch.clamp(u, -QPDO_INFTY, QPDO_INFTY)
         lp, up = (None if l is None else l.data_ptr()), (None if u is None else u.data_ptr())
         self._call(lib().qpdo_amd_fleet_update_dev(self._h, qp, lp, up, mp, N, M, self._stream()), "update_device")
+
+    def packed_matrix_layout(self):
+        """(qoff, aoff), count + 1 entries each: item i's stored Q values are [qoff[i], qoff[i + 1]) of a packed Q-value array, its CSC A
+        values [aoff[i], aoff[i + 1]) of a packed A-value array; the last entries are the totals NQ and NA.  Needs matrix_updates=True."""
+        if getattr(self, "_mlayout", None) is None:
+            qo, ao = (C.c_long * (self.count + 1))(), (C.c_long * (self.count + 1))()
+            self._call(lib().qpdo_amd_fleet_get_packed_matrix_layout(self._h, qo, ao), "packed_matrix_layout")
+            self._mlayout = (np.array(qo[:], np.int64), np.array(ao[:], np.int64))
+        return self._mlayout
+
+    def pack_matrix_values(self, Q=None, A=None):
+        """lists of scipy matrices as update_matrices() takes them -> (Q_values, A_values, mask): two float64 numpy arrays in the packed
+        value layout (None for a None list; zeros where an item has no entry) and the int32 mask the lists imply.  Move them to the GPU
+        for update_matrices_device(); packing matrices whose values are their own indices (0, 1, 2, ...) gives the index map from a
+        caller's ordering to the packed one."""
+        qoff, aoff = self.packed_matrix_layout()
+        return pack_matrix_values(self.dims, self._qstype, qoff, aoff, Q, A)
+
+    def update_matrices_device(self, Q_values=None, A_values=None, mask=None):
+        """update_matrices() from packed GPU tensors on torch's current stream; returns without waiting.  Q_values: NQ float64, A_values: NA
+        float64 (packed_matrix_layout(); values only, the pattern is the create-time one), mask: count int32, bit 0 / 1 = the item takes
+        Q / A.  None: that matrix is unchanged for every item.  Needs matrix_updates=True."""
+        qoff, aoff = self.packed_matrix_layout()
+        NQ, NA = int(qoff[-1]), int(aoff[-1])
+        (qp, ap), mp = self._dev_args([("Q_values", Q_values, "float64", NQ), ("A_values", A_values, "float64", NA)], mask)
+        self._call(lib().qpdo_amd_fleet_update_matrices_dev(self._h, qp, ap, mp, NQ, NA, self._stream()), "update_matrices_device")
 
     def warm_start_device(self, x=None, y=None, mask=None):
         """warm_start() from packed GPU tensors (x: N, y: M float64; mask bit 0 / 1 = the item takes x / y, else starts it from zero)"""
