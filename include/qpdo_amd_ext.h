@@ -577,6 +577,57 @@ int  qpdo_amd_fleet_get_packed_matrix_layout(const QPDOAmdFleet *f, long *qoff, 
 int  qpdo_amd_fleet_update_matrices_dev(QPDOAmdFleet *f, const double *Qx, const double *Ax, const int *item_mask, long q_len, long a_len, void *stream);
 int  qpdo_amd_fleet_fetch_last(QPDOAmdFleet *f, c_float *const *x, c_float *const *y, QPDOInfo *info);
 int  qpdo_amd_fleet_sync(QPDOAmdFleet *f, QPDOAmdFleetDevStats *out);
+/* ---- the ADJOINT of the last solve (learned-model MPC: a loss gradient goes back through the QP to whatever produced q, l, u, Q, A) --------
+ * Item: min 1/2 x'Qx + q'x s.t. l <= Ax <= u, solved to the x, y solve(_dev) delivered.  All quantities below are the caller's UNSCALED ones.
+ * ACTIVE SET  t = Ax + y.  Row i is upper-active (flag +1) if t_i >= u_i, else lower-active (-1) if t_i <= l_i, else inactive (0): the
+ *          projection of the outer residual (termination.c).  A row with l_i = u_i is always active; a bound of magnitude >= 1e20 is never
+ *          reached.  The rule is evaluated in the item's scaled space, so a row within rounding of a bound may fall either way: the call
+ *          DELIVERS its flags (`active`), and everything else is defined by them.  S: the flagged rows, k = |S|.
+ * SYSTEM   Given gx = dL/dx (N) and gy = dL/dy (M, or NULL = zero; entries of inactive rows are ignored and may hold anything, NaN included):
+ *              [ Q    A_S' ] [vx]   [ gx   ]
+ *              [ A_S  0    ] [vy] = [ gy_S ]
+ *          dq = -vx;  du_i = vy_i on +1 rows, dl_i = vy_i on -1 rows, every other entry of dl, du an exact +0.0;  for a stored entry (i, j) of
+ *          A: -(y_i vx_j + vy_i x_j) on a flagged row, else +0.0;  for a stored entry (a, b) of Q: -vx_a x_b (stype 0), -(vx_a x_b + vx_b x_a)
+ *          (off-diagonal, stype +-1), -vx_a x_a (diagonal); a stored entry in the triangle that stype +-1 ignores gets +0.0.  dQx (NQ) /
+ *          dAx (NA) are in the packed value layout of
+ *          qpdo_amd_fleet_get_packed_matrix_layout and are evaluated from the very dq, dl, du delivered and the x, y of the solve.
+ * METHOD   One launch (k_small_fleet_adjoint), one workgroup per item, in the solve's own launch shape.  In the item's scaled space, block
+ *          elimination on the regularised matrix: K = Qs + sigma I + As_S' W As_S is assembled and factored by the solve loop's own device
+ *          functions (all three layouts of K), and  K dvx = rx + As_S' W ry,  dvy = W (As_S dvx - ry)  is repeated on the residual of the
+ *          TRUE system (no sigma, no W^-1): the proximal method of multipliers on an equality QP, which converges for PSD Q and a consistent
+ *          system.  sigma = 1e-10 s, W_i = 1e10 s / ||row i of As||^2 with s the largest |diagonal entry| of Qs (1 when there is none).
+ * ACCEPTANCE  max(||Q vx + A_S' vy - gx||_inf, ||A_S vx - gy_S||_inf) <= tol * max(||gx||_inf, ||gy_S||_inf), on the true residual in unscaled terms,
+ *          looked at before every sweep; at most max_sweeps sweeps.  A residual that is not finite is never accepted.
+ * adj_status  count x 3 int64: code, sweeps, k.  code 0: accepted.  1: the residual did not reach tol in max_sweeps sweeps -- the system is
+ *          inconsistent (dependent active rows with gy_S outside their range), singular, or so ill-conditioned that the sweeps contract
+ *          too slowly; the code says that no gradient is delivered, not which of these it was (more sweeps settle the last case).  2: the item's status is not QPDO_SOLVED --
+ *          never solved, infeasible, out of passes, or matrices replaced since its last solve.  3: a pivot of K that is not a positive
+ *          finite number.  An item with code != 0 gets NaN in all its slices of dq, dl, du, dQx, dAx and 0 flags; adj_res (count): the
+ *          accepted relative residual, NaN otherwise.  An item with m = 0 solves Q vx = gx.
+ * FLAG     create_ex with QPDO_AMD_FLEET_ADJOINT (combinable with QPDO_AMD_FLEET_MATRIX_UPDATES); a fleet without it is what it was and is
+ *          refused here.  The launch works in the solve's work-vector area and K buffer and reads the packed layouts the *_dev calls already
+ *          keep, so the flag reserves no memory of its own: QPDOAmdFleetAdjointStats.resident_extra_bytes reports 0.  The call writes none
+ *          of the item's state, of the last solve's outputs, of the matrices, q, l, u: every later solve carries the bits it would have had.
+ * Checks   all on the host before the launch; a refused call returns nonzero with qpdo_amd_last_error() set and has launched nothing: NULL
+ *          fleet; a fleet without the flag; n_len != N or m_len != M; dQx or dAx on a fleet without QPDO_AMD_FLEET_MATRIX_UPDATES, q_len != NQ
+ *          with dQx or a_len != NA with dAx (both numbers named); NULL gx, dq, dl or du; a passed pointer that is not device or managed
+ *          memory of the fleet's device (named); tol not a positive finite number; max_sweeps < 1; THE MOST RECENT STATE-CHANGING FLEET CALL
+ *          WAS NOT A SOLVE -- an update, warm start or matrix update since the last solve(_dev) means the resident q, l, u or matrices are no
+ *          longer those of the x, y returned.  adjoint_dev, fetch_last, sync and the getters do not count: several adjoint calls may follow
+ *          one solve (the rows of a Jacobian).
+ * ORDER    that of the other device calls: enqueues on `stream`, returns at once, joins the fleet's one-event chain.  No hipGraph capture.
+ * Stats    adjoint_calls of QPDOAmdFleetAdjointStats counts the calls that launched (QPDOAmdFleetDevStats keeps its five members: its size
+ *          is part of the ABI); solve_launches, solves and the device-call counters do not move. */
+#define QPDO_AMD_FLEET_ADJOINT 8L
+typedef struct {
+    long adjoint_calls;                     /* adjoint_dev calls that launched, since create */
+    long resident_extra_bytes;              /* device memory the flag holds beyond a fleet without it: 0 */
+} QPDOAmdFleetAdjointStats;
+int  qpdo_amd_fleet_adjoint_dev(QPDOAmdFleet *f, const double *gx /* N */, const double *gy /* M or NULL */, double *dq /* N */, double *dl /* M */, double *du /* M */,
+                                double *dQx /* NQ or NULL */, double *dAx /* NA or NULL */, int *active /* M int32 or NULL */,
+                                long *adj_status /* count x 3: code, sweeps, k; or NULL */, double *adj_res /* count; or NULL */, double tol, long max_sweeps,
+                                long n_len, long m_len, long q_len, long a_len, void *stream);
+int  qpdo_amd_fleet_get_adjoint_stats(const QPDOAmdFleet *f, QPDOAmdFleetAdjointStats *out);
 void qpdo_amd_fleet_destroy(QPDOAmdFleet *f);
 
 #ifdef __cplusplus

@@ -239,6 +239,9 @@ struct SmallFleet {
     std::vector<long> noff, moff;
     long d_updates = 0, d_warm_starts = 0, d_solves = 0;
     bool timing_pending = false;                    // ev0 / ev1 bracket a device solve whose duration has not been read yet
+    // QPDO_AMD_FLEET_ADJOINT: the most recent state-changing call was a solve (the resident q, l, u and matrices belong to the x, y it returned)
+    bool last_was_solve = false;
+    long adjoint_calls = 0;
 };
 // Ordering between the streams the fleet is driven on, its own included: ONE event.  Every call makes its stream wait for what the previous
 // call recorded and records again behind its last operation, so host and device calls mix freely and the caller may change streams.
@@ -422,6 +425,8 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     SHIP(hipMemcpyAsync(F->doffs, hoffs.data(), hoffs.size() * sizeof(int), hipMemcpyHostToDevice, F->stream));
     if (mu) SHIP(hipMemcpyAsync(F->dmoffs, hmoffs.data(), hmoffs.size() * sizeof(int), hipMemcpyHostToDevice, F->stream));
     SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
+    if (flags & QPDO_AMD_FLEET_ADJOINT)                // (the adjoint launch takes the solve's plan: nothing of its own is resident)
+        SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet_adjoint), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
     hipLaunchKernelGGL(k_small_fleet_setup, dim3((unsigned)count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)count, F->st);
     SHIP(hipGetLastError());
     SHIP(fleet_leave(F, F->stream));
@@ -456,6 +461,7 @@ int qdev_small_fleet_update(void *h_, const double *const *q, const double *cons
     SHIP(hipStreamSynchronize(F->stream));           // (the pinned staging is free for the next call)
     F->vector_bytes_last = (long)(off * 8 + (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES);
 done:
+    F->last_was_solve = false;
     return rc;
 }
 // Q, A: arrays of `count` cholmod_sparse pointers or NULL; entries may be NULL.  Every passed matrix is compared with the create-time pattern
@@ -513,6 +519,7 @@ int qdev_small_fleet_update_matrices(void *h_, const void *const *Q_, const void
     F->timing_pending = false;                       // (ev0 / ev1 no longer bracket a solve)
     F->m_calls++; F->m_items_last = items; F->m_bytes_last = (long)(tab_bytes + off * 8);
 done:
+    F->last_was_solve = false;
     return rc;
 }
 void qdev_small_fleet_matrix_stats(const void *h_, long *out4, double *kernel_s) {
@@ -546,6 +553,7 @@ int qdev_small_fleet_warm_start(void *h_, const double *const *x0, const double 
     SHIP(hipStreamSynchronize(F->stream));
     F->vector_bytes_last = last ? 0 : (long)(off * 8 + (size_t)F->count * QPDO_AMD_FLEET_TABLE_BYTES);
 done:
+    F->last_was_solve = false;
     return rc;
 }
 // The last solve's descriptors and outputs to the host on the fleet's stream (the caller has made it wait for the chain event), then what a
@@ -581,7 +589,7 @@ int qdev_small_fleet_solve(void *h_, double *const *x, double *const *y, void *i
                        (const int *)F->dtab, (const double *)F->dstage);
     SHIP(hipGetLastError());
     SHIP(hipEventRecord(F->ev1, F->stream));
-    F->solve_launches++; F->solves++; F->timing_pending = true;
+    F->solve_launches++; F->solves++; F->timing_pending = true; F->last_was_solve = true;
     rc = fleet_fetch(F, x, y, (QPDOInfo *)info_);
 done:
     return rc;
@@ -622,7 +630,7 @@ int qdev_small_fleet_update_dev(void *h_, const double *q, const double *l, cons
     hipLaunchKernelGGL(k_small_fleet_update, dim3((unsigned)F->count), dim3(SM_THREADS), 0, s, F->dprobs, (int)F->count, F->st, (const int *)F->dtab, (const double *)F->dstage);
     SHIP(hipGetLastError());
     SHIP(fleet_leave(F, s));
-    F->vector_bytes_last = 0; F->d_updates++;
+    F->vector_bytes_last = 0; F->d_updates++; F->last_was_solve = false;
 done:
     return rc;
 }
@@ -639,7 +647,7 @@ int qdev_small_fleet_warm_start_dev(void *h_, const double *x0, const double *y0
                        (const int *)F->dtab, (const double *)F->dstage);
     SHIP(hipGetLastError());
     SHIP(fleet_leave(F, s));
-    F->vector_bytes_last = 0; F->d_warm_starts++;
+    F->vector_bytes_last = 0; F->d_warm_starts++; F->last_was_solve = false;
 done:
     return rc;
 }
@@ -672,6 +680,7 @@ int qdev_small_fleet_update_matrices_dev(void *h_, const double *Qx, const doubl
         SHIP(hipGetLastError());
         SHIP(fleet_leave(F, s));
         F->m_calls++; F->m_items_last = -1; F->m_bytes_last = 0;      // (which items took a matrix is known on the device only)
+        F->last_was_solve = false;
     }
 done:
     return rc;
@@ -695,7 +704,7 @@ int qdev_small_fleet_solve_dev(void *h_, double *x, double *y, long *status, dou
                        (const int *)F->dtab, (const double *)F->dstage);
     SHIP(hipGetLastError());
     SHIP(hipEventRecord(F->ev1, s));
-    F->solve_launches++; F->solves++; F->d_solves++;
+    F->solve_launches++; F->solves++; F->d_solves++; F->last_was_solve = true;
     F->timing_pending = true; F->solved = false;     // (the host image is the previous solve's until fetch_last)
     if (x || y || status || norms || prim_inf_cert || dual_inf_cert) {
         hipLaunchKernelGGL(k_small_fleet_scatter, dim3((unsigned)F->count), dim3(FLEET_IO_THREADS), 0, s, (const SmallQP *)F->dprobs, (int)F->count, (const int *)F->doffs,
@@ -706,6 +715,47 @@ int qdev_small_fleet_solve_dev(void *h_, double *x, double *y, long *status, dou
 done:
     return rc;
 }
+// The adjoint of the last solve on the caller's stream (include/qpdo_amd_ext.h): every check on the host, then ONE launch in the solve's own
+// launch shape (layout word, dynamic LDS), no wait.  Moves none of the solve's counters.
+int qdev_small_fleet_adjoint_dev(void *h_, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active, long *adj_status,
+                                 double *adj_res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    hipStream_t s = (hipStream_t)stream_;
+    if (!(F->flags & QPDO_AMD_FLEET_ADJOINT)) { snprintf(s_err, sizeof(s_err), "the fleet was created without QPDO_AMD_FLEET_ADJOINT (qpdo_amd_fleet_create_ex)"); return -1; }
+    if (fleet_dev_lens(F, n_len, m_len)) return -1;
+    if (dQx || dAx) {
+        if (!(F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES)) {
+            snprintf(s_err, sizeof(s_err), "%s was passed, but %s", dQx ? "dQx" : "dAx", FLEET_NO_MATRIX_FLAG); return -1;
+        }
+        const long NQ = F->qoff.back(), NA = F->aoff.back();
+        if (dQx && q_len != NQ) { snprintf(s_err, sizeof(s_err), "q_len is %ld, the fleet's packed Q values have %ld elements", q_len, NQ); return -1; }
+        if (dAx && a_len != NA) { snprintf(s_err, sizeof(s_err), "a_len is %ld, the fleet's packed A values have %ld elements", a_len, NA); return -1; }
+    }
+    if (!gx) { snprintf(s_err, sizeof(s_err), "gx is NULL"); return -1; }
+    if (!dq) { snprintf(s_err, sizeof(s_err), "dq is NULL"); return -1; }
+    if (!dl) { snprintf(s_err, sizeof(s_err), "dl is NULL"); return -1; }
+    if (!du) { snprintf(s_err, sizeof(s_err), "du is NULL"); return -1; }
+    if (!(tol > 0.0) || !(tol <= 1.7976931348623157e308)) { snprintf(s_err, sizeof(s_err), "tol is %g, it must be a positive finite number", tol); return -1; }
+    if (max_sweeps < 1) { snprintf(s_err, sizeof(s_err), "max_sweeps is %ld, it must be at least 1", max_sweeps); return -1; }
+    if (!F->last_was_solve) {
+        snprintf(s_err, sizeof(s_err), "the most recent state-changing fleet call was not a solve: the resident q, l, u and matrices must be those of the x, y returned");
+        return -1;
+    }
+    SHIP(hipSetDevice(F->device));
+    if (fleet_dev_ptr(F, gx, "gx") || fleet_dev_ptr(F, gy, "gy") || fleet_dev_ptr(F, dq, "dq") || fleet_dev_ptr(F, dl, "dl") || fleet_dev_ptr(F, du, "du") ||
+        fleet_dev_ptr(F, dQx, "dQx") || fleet_dev_ptr(F, dAx, "dAx") || fleet_dev_ptr(F, active, "active") || fleet_dev_ptr(F, adj_status, "adj_status") ||
+        fleet_dev_ptr(F, adj_res, "adj_res")) return -1;
+    SHIP(fleet_enter(F, s));
+    hipLaunchKernelGGL(k_small_fleet_adjoint, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, s, F->dprobs, (int)F->count, F->st, F->kflags, (const int *)F->doffs,
+                       (const int *)F->dmoffs, gx, gy, dq, dl, du, dQx, dAx, active, adj_status, adj_res, tol, (int)(max_sweeps > 1000000 ? 1000000 : max_sweeps));
+    SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, s));
+    F->adjoint_calls++;
+done:
+    return rc;
+}
+long qdev_small_fleet_adjoint_calls(const void *h_) { return ((const SmallFleet *)h_)->adjoint_calls; }
 int qdev_small_fleet_fetch_last(void *h_, double *const *x, double *const *y, void *info_) {
     int rc = 0;
     SmallFleet *F = (SmallFleet *)h_;

@@ -1091,7 +1091,9 @@ QPDOAmdFleet *qpdo_amd_fleet_create(long count, const QPDOData *const *data, con
     return qpdo_amd_fleet_create_ex(count, data, settings, 0L);
 }
 QPDOAmdFleet *qpdo_amd_fleet_create_ex(long count, const QPDOData *const *data, const QPDOSettings *settings, long flags) {
-    if (flags & ~QPDO_AMD_FLEET_MATRIX_UPDATES) { fleet_refuse("qpdo_amd_fleet_create_ex: unknown flag bits (known: QPDO_AMD_FLEET_MATRIX_UPDATES)"); return NULL; }
+    if (flags & ~(QPDO_AMD_FLEET_MATRIX_UPDATES | QPDO_AMD_FLEET_ADJOINT)) {
+        fleet_refuse("qpdo_amd_fleet_create_ex: unknown flag bits (known: QPDO_AMD_FLEET_MATRIX_UPDATES, QPDO_AMD_FLEET_ADJOINT)"); return NULL;
+    }
     if (count <= 0) { fleet_refuse("qpdo_amd_fleet_create: count must be positive"); return NULL; }
     if (!data) { fleet_refuse("qpdo_amd_fleet_create: NULL data array"); return NULL; }
     if (!settings) { fleet_refuse("qpdo_amd_fleet_create: NULL settings"); return NULL; }
@@ -1261,6 +1263,19 @@ int qpdo_amd_fleet_sync(QPDOAmdFleet *f, QPDOAmdFleetDevStats *out) {
     long st[5] = {0, 0, 0, 0, -1};
     if (qdev_small_fleet_sync(f, st)) return fleet_dev_failed("qpdo_amd_fleet_sync");
     if (out) { out->update_calls = st[0]; out->warm_start_calls = st[1]; out->solve_calls = st[2]; out->refused_items = st[3]; out->first_refused_item = st[4]; }
+    return 0;
+}
+int qpdo_amd_fleet_adjoint_dev(QPDOAmdFleet *f, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active,
+                               long *adj_status, double *adj_res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_adjoint_dev: NULL fleet");
+    if (qdev_small_fleet_adjoint_dev(f, gx, gy, dq, dl, du, dQx, dAx, active, adj_status, adj_res, tol, max_sweeps, n_len, m_len, q_len, a_len, stream))
+        return fleet_dev_failed("qpdo_amd_fleet_adjoint_dev");
+    return 0;
+}
+int qpdo_amd_fleet_get_adjoint_stats(const QPDOAmdFleet *f, QPDOAmdFleetAdjointStats *out) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_get_adjoint_stats: NULL fleet");
+    if (!out) return fleet_refuse("qpdo_amd_fleet_get_adjoint_stats: NULL output");
+    out->adjoint_calls = qdev_small_fleet_adjoint_calls(f); out->resident_extra_bytes = 0;
     return 0;
 }
 void qpdo_amd_fleet_destroy(QPDOAmdFleet *f) { if (f) qdev_small_fleet_destroy(f); }

@@ -273,6 +273,10 @@ void  qdev_small_fleet_packed_layout(const void *fleet, long *noff, long *moff);
  * refused (nonzero, qdev_small_last_error()) for a fleet without QPDO_AMD_FLEET_MATRIX_UPDATES */
 int   qdev_small_fleet_update_matrices_dev(void *fleet, const double *Qx, const double *Ax, const int *item_mask, long q_len, long a_len, void *stream);
 int   qdev_small_fleet_packed_matrix_layout(const void *fleet, long *qoff, long *aoff);
+/* the adjoint of the last solve (a fleet created with QPDO_AMD_FLEET_ADJOINT): every check but the NULL fleet, then one launch on `stream` */
+int   qdev_small_fleet_adjoint_dev(void *fleet, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active,
+                                   long *adj_status, double *adj_res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream);
+long  qdev_small_fleet_adjoint_calls(const void *fleet);
 void  qdev_small_fleet_destroy(void *fleet);
 
 /* ---- ONE small workspace through the fused kernel (the default path of qpdo_solve for problems whose whole state fits one

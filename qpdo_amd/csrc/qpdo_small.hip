@@ -1773,6 +1773,223 @@ __global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet(SmallQP *probs, i
     small_solve_body<1, 1>(probs, count, st, kflags, op, tab, stage);
 }
 
+// ---- the ADJOINT of a fleet's last solve (qpdo_amd_fleet_adjoint_dev, include/qpdo_amd_ext.h) -------------------------------
+// One workgroup per item, in the launch shape of k_small_fleet (the same layout word and dynamic LDS: K is where the solve keeps it).  At the
+// x, y the last solve returned the rows are classified (t = Ax + y against the bounds: the projection of the outer residual), and
+//   [ Q  A_S' ; A_S  0 ] [vx ; vy] = [gx ; gy_S]
+// is solved in the item's SCALED space -- Qs = c D Q D, As = E A D, vxs = D^-1 vx, vys = c E^-1 vy, gxs = c D gx, gys = E gy: the same
+// system in the stored matrices -- by block elimination on the regularised matrix [Qs + sigma I, As_S' ; As_S, -W^-1]:
+//   (Qs + sigma I + As_S' W As_S) dvx = rx + As_S' W ry,   dvy = W (As_S dvx - ry),
+// repeated on the residual (rx, ry) of the TRUE system (the proximal method of multipliers on an equality QP).  The matrix is the Newton
+// matrix of the solve with weights W on the flagged rows: small_assemble, the factorization and the triangular solves of the solve loop.
+// sigma and W are the kernel's own: with s = the largest |diagonal entry| of Qs (1 for an LP), sigma = 1e-10 s and W_i = 1e10 s / ||row i of
+// As||^2, so that every flagged row enters K with the same weight 1e10 s whatever the item's scaling.  A direction of Q with curvature
+// lambda contracts by sigma / (sigma + lambda) per sweep, and the multiplier error along a singular direction of A_S (Qs + sigma I)^-1 A_S'
+// with value nu by 1 / (1 + W nu): both constants are set from the sweep emulated on the CPU oracle's solutions of all 4096 C3 items, the
+// test fleets and badly scaled variants (docs/LAB_NOTES.md) -- W = 1e6 s left 4.5 % of the C3 items, nonsingular ones with n active rows of
+// full rank and sv_min / sv_max ~ 2e-8 of the KKT matrix, at a relative residual of 1e-6 after 20 sweeps, W = 1e8 s still four of 4096
+// (sv_min / sv_max 5e-11 .. 8e-10); sigma = 1e-6 s stalled on a Q of condition 1e8.  The solve's own final mu is gone with its
+// LDS.
+// Acceptance on the true residual in UNSCALED terms; a residual that is not finite never passes.
+// codes: 0 accepted, 1 not accepted after max_sweeps, 2 the item's status is not QPDO_SOLVED, 3 a pivot that is not a positive finite number.
+#define ADJ_SIGMA_REL 1e-10
+#define ADJ_ROW_WEIGHT 1e10
+__device__ void small_adjoint_refuse(int code, int sweeps, int k, int n, int m, int nq, int na, double *dq, double *dl, double *du, double *dQ, double *dA,
+                                     int *active, long *adj_status, double *adj_res) {
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    FOR_T(j, n) dq[j] = nan;
+    FOR_T(i, m) { dl[i] = nan; du[i] = nan; if (active) active[i] = 0; }
+    if (dQ) { FOR_T(e, nq) dQ[e] = nan; }
+    if (dA) { FOR_T(e, na) dA[e] = nan; }
+    if (threadIdx.x == 0) {
+        if (adj_status) { long *s = adj_status + 3 * (size_t)blockIdx.x; s[0] = code; s[1] = sweeps; s[2] = k; }
+        if (adj_res) adj_res[blockIdx.x] = nan;
+    }
+}
+__global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet_adjoint(SmallQP *probs, int count, QPDOSettings st, int kflags, const int *offs, const int *moffs,
+                                                                       const double *gx_, const double *gy_, double *dq_, double *dl_, double *du_, double *dQx_, double *dAx_,
+                                                                       int *active_, long *adj_status, double *adj_res, double tol, int max_sweeps) {
+    const int klay = kflags & 3, klds_ok = klay == K_PACKED, kband = klay == K_BAND;
+    __shared__ double sm[32];
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    if ((int)blockIdx.x >= count) return;
+    const int b = blockIdx.x;
+    SmallQP &Pg = probs[b];
+    SmallQP P;
+    P.n = __builtin_amdgcn_readfirstlane(Pg.n); P.m = __builtin_amdgcn_readfirstlane(Pg.m); P.bw = __builtin_amdgcn_readfirstlane(Pg.bw);
+#define UNI_PTR(f) P.f = uni_ptr(Pg.f)
+    UNI_PTR(Arp); UNI_PTR(Aci); UNI_PTR(Aval); UNI_PTR(Trp); UNI_PTR(Tci); UNI_PTR(Tval); UNI_PTR(Qrp); UNI_PTR(Qci); UNI_PTR(Qval);
+    UNI_PTR(q); UNI_PTR(l); UNI_PTR(u); UNI_PTR(nv); UNI_PTR(mv); UNI_PTR(iv); UNI_PTR(tpos); UNI_PTR(K); UNI_PTR(sol_x); UNI_PTR(sol_y);
+#undef UNI_PTR
+    P.prof = nullptr;
+    const SmallRes *Rg = uni_ptr(Pg.res);
+    const int n = P.n, m = P.m;
+    // the item's slices of the caller's packed arrays
+    const int no = __builtin_amdgcn_readfirstlane(offs[b]), mo = __builtin_amdgcn_readfirstlane(offs[count + 1 + b]);
+    const bool wantQ = dQx_ != nullptr, wantA = dAx_ != nullptr;
+    int qo = 0, nq = 0, ao = 0, na = 0;
+    if (wantQ || wantA) {
+        qo = __builtin_amdgcn_readfirstlane(moffs[b]); nq = __builtin_amdgcn_readfirstlane(moffs[b + 1]) - qo;
+        ao = __builtin_amdgcn_readfirstlane(moffs[count + 1 + b]); na = __builtin_amdgcn_readfirstlane(moffs[count + 2 + b]) - ao;
+    }
+    const double *gx = gx_ + no, *gy = gy_ ? gy_ + mo : nullptr;
+    double *dq = dq_ + no, *dl = dl_ + mo, *du = du_ + mo, *dQ = wantQ ? dQx_ + qo : nullptr, *dA = wantA ? dAx_ + ao : nullptr;
+    int *active = active_ ? active_ + mo : nullptr;
+    const long fs = Rg->fleet_status;
+    if (__builtin_amdgcn_readfirstlane((int)(fs != QPDO_SOLVED))) { small_adjoint_refuse(2, 0, 0, n, m, nq, na, dq, dl, du, dQ, dA, active, adj_status, adj_res); return; }
+    // the work vectors where the solve has them (beside the factor in LDS, or the item's global area: every solve zeroes them before use)
+    const unsigned voff = (unsigned)__builtin_amdgcn_readfirstlane((int)Rg->lds_vec_off);
+    if (voff) {
+        P.nv = uni_ptr((double *)((char *)dyn + voff));
+        P.mv = P.nv + (size_t)NV_COUNT * n;
+        P.iv = (int *)(P.mv + (size_t)MV_COUNT * m);
+    }
+    enum { AN_X = 0, AN_VX, AN_RX, AN_DVX, AN_RHS, AN_T1, AN_T2, AN_GX, AN_D, AN_DINV, AN_COUNT };
+    enum { AM_VY = 0, AM_RY, AM_WRY, AM_W, AM_AV, AM_GY, AM_E, AM_EINV, AM_COUNT };
+    static_assert(AN_COUNT <= NV_COUNT && AM_COUNT <= MV_COUNT, "the adjoint lives in the solve's work-vector area");
+    double *xsc = P.nv + (size_t)AN_X * n, *vx = P.nv + (size_t)AN_VX * n, *rx = P.nv + (size_t)AN_RX * n, *dvx = P.nv + (size_t)AN_DVX * n,
+           *rhs = P.nv + (size_t)AN_RHS * n, *t1 = P.nv + (size_t)AN_T1 * n, *t2 = P.nv + (size_t)AN_T2 * n, *gxs = P.nv + (size_t)AN_GX * n,
+           *D = P.nv + (size_t)AN_D * n, *Dinv = P.nv + (size_t)AN_DINV * n;
+    double *vy = P.mv + (size_t)AM_VY * m, *ry = P.mv + (size_t)AM_RY * m, *wry = P.mv + (size_t)AM_WRY * m, *W = P.mv + (size_t)AM_W * m,
+           *Av = P.mv + (size_t)AM_AV * m, *gys = P.mv + (size_t)AM_GY * m, *E = P.mv + (size_t)AM_E * m, *Einv = P.mv + (size_t)AM_EINV * m;
+    int *flag = P.iv;
+    // dynamic LDS as the solve lays it out: [xs: n][column buffers: 16n with the look-ahead factorization, else 8n][gbuf][d_s: m][rp_s: m+1][U: K]
+    double *xs = dyn, *gbuf = dyn + (klds_ok ? 16 : 8) * (size_t)n;
+    double *d_s = gbuf + (((size_t)(n > m ? n : m) / 4 + 4 + 1) & ~(size_t)1);
+    int *rp_s = (int *)(d_s + m);
+    double *Klds = (double *)(rp_s + (((size_t)m + 1 + 3) & ~(size_t)3));
+    const int bw = P.bw;
+    KView kv; kv.n = n; kv.packed = klds_ok; kv.ld = kband ? bw : n; kv.K = (klds_ok | kband) ? Klds : P.K;
+    const int scaled = st.scaling > 0;
+    const double sc_c = scaled ? Rg->r_c : 1.0, sc_cinv = scaled ? Rg->r_cinv : 1.0;
+    const double *rD = uni_ptr(Rg->rD), *rDinv = uni_ptr(Rg->rDinv), *rE = uni_ptr(Rg->rE), *rEinv = uni_ptr(Rg->rEinv);
+    const int *mapA = uni_ptr(Rg->mapA), *mapQ = uni_ptr(Rg->mapQ);
+
+    // ---- the scaled x, the right-hand side, the largest diagonal entry of Qs
+    FOR_T(r, m + 1) rp_s[r] = P.Arp[r];
+    double mgx = 0.0, mqd = 0.0, mgy = 0.0, nonfin = 0.0;
+    FOR_T(j, n) {
+        const double d = scaled ? rD[j] : 1.0, di = scaled ? rDinv[j] : 1.0;
+        D[j] = d; Dinv[j] = di;
+        xsc[j] = scaled ? P.sol_x[j] * di : P.sol_x[j];
+        const double g = gx[j];
+        gxs[j] = scaled ? sc_c * (d * g) : g;
+        vx[j] = 0.0;
+        const double ag = s_abs(g);
+        mgx = ag > mgx ? ag : mgx;
+        if (!(ag <= 1.7976931348623157e308)) nonfin = 1.0;
+        for (int k = P.Qrp[j]; k < P.Qrp[j + 1]; k++) if (P.Qci[k] == j) { const double a = s_abs(P.Qval[k]); mqd = a > mqd ? a : mqd; }
+    }
+    FOR_T(i, m) { const double e = scaled ? rE[i] : 1.0; E[i] = e; Einv[i] = scaled ? rEinv[i] : 1.0; vy[i] = 0.0; }
+    SYNC;
+    spmv_rows(m, P.Arp, P.Aci, P.Aval, xsc, Av);
+    // ---- the active set: t = Ax + y in the scaled space (E t against E l, E u: the outer residual's projection, termination.c)
+    int cnt = 0;
+    FOR_T(i, m) {                                     // (entry i of the product was written by this very thread)
+        const double e = E[i], yi = P.sol_y[i];
+        const double t = Av[i] + (scaled ? e * yi : yi);
+        const double lo = P.l[i], up = P.u[i];
+        int f = 0;
+        if (up < e * SM_INFTY && t >= up) f = 1;
+        else if (lo > -e * SM_INFTY && t <= lo) f = -1;
+        flag[i] = f; cnt += (f != 0);
+        if (active) active[i] = f;
+        double g = 0.0;
+        if (f && gy) { g = gy[i]; const double ag = s_abs(g); mgy = ag > mgy ? ag : mgy; if (!(ag <= 1.7976931348623157e308)) nonfin = 1.0; }
+        gys[i] = scaled ? e * g : g;
+        double a2 = 0.0;
+        for (int k = rp_s[i]; k < rp_s[i + 1]; k++) { const double a = P.Aval[k]; a2 += a * a; }
+        W[i] = a2;                                     // (the row's squared norm until s is known)
+    }
+    blk_max4(mgx, mqd, mgy, nonfin, sm);
+    const int kact = blk_sum_int(cnt, (int *)sm);
+    SYNC;
+    const double gnorm = s_max(mgx, mgy);
+    const double s = mqd > 0.0 ? mqd : 1.0, sigma = ADJ_SIGMA_REL * s;
+    FOR_T(i, m) { const double a2 = W[i]; W[i] = (flag[i] && a2 > 0.0) ? (ADJ_ROW_WEIGHT * s) / a2 : 0.0; }
+    SYNC;
+    // ---- K = Qs + sigma I + As_S' W As_S and its LDL' (the solve loop's own functions)
+    small_assemble(P, kv, W, sigma, rp_s, d_s);
+    if (klds_ok) small_factor4_la<1>(n, Klds, dyn);
+    else if (kband) small_factor_band(n, bw, Klds, dyn);
+    else small_factor4_t<false>(n, P.K, dyn);
+    {
+        int bad = 0;
+        FOR_T(j, n) { const double dj = kv.at(j, j); bad |= !(dj > 0.0 && dj <= 1.7976931348623157e308); }
+        if (__syncthreads_or(bad)) { small_adjoint_refuse(3, 0, kact, n, m, nq, na, dq, dl, du, dQ, dA, active, adj_status, adj_res); return; }
+    }
+    // ---- sweeps
+    int sweep = 0; double rel = 0.0; bool accepted = false;
+    for (;; sweep++) {
+        spmv_rows(n, P.Qrp, P.Qci, P.Qval, vx, t1);
+        spmv_rows(m, P.Arp, P.Aci, P.Aval, vx, Av);
+        spmv_rows(n, P.Trp, P.Tci, P.Tval, vy, t2);
+        double m1 = 0.0, m2 = 0.0, nf = nonfin, z = 0.0;
+        FOR_T(j, n) {                                 // (own entries of the products)
+            const double r = (gxs[j] - t1[j]) - t2[j];
+            rx[j] = r;
+            const double a = s_abs(r * Dinv[j]);
+            m1 = a > m1 ? a : m1;
+            if (!(a <= 1.7976931348623157e308)) nf = 1.0;
+        }
+        FOR_T(i, m) {
+            const double r = flag[i] ? gys[i] - Av[i] : 0.0;
+            ry[i] = r; wry[i] = W[i] * r;
+            const double a = s_abs(r * Einv[i]);
+            m2 = a > m2 ? a : m2;
+            if (!(a <= 1.7976931348623157e308)) nf = 1.0;
+        }
+        blk_max4(m1, m2, nf, z, sm);
+        const double rn = s_max(m1 * sc_cinv, m2);
+        rel = gnorm > 0.0 ? rn / gnorm : rn;
+        if (nf == 0.0 && rn <= tol * gnorm) { accepted = true; break; }
+        if (sweep >= max_sweeps) break;
+        spmv_rows(n, P.Trp, P.Tci, P.Tval, wry, t2);
+        FOR_T(j, n) rhs[j] = rx[j] + t2[j];
+        SYNC;
+        if (kband) small_ldl_solve_band(n, bw, Klds, rhs, dvx, xs); else small_ldl_solve(P, kv, rhs, dvx, xs);
+        spmv_rows(m, P.Arp, P.Aci, P.Aval, dvx, Av);
+        FOR_T(i, m) vy[i] = vy[i] + W[i] * (Av[i] - ry[i]);
+        FOR_T(j, n) vx[j] = vx[j] + dvx[j];
+        SYNC;
+    }
+    if (!accepted) { small_adjoint_refuse(1, sweep, kact, n, m, nq, na, dq, dl, du, dQ, dA, active, adj_status, adj_res); return; }
+    // ---- back to the caller's space: vx = D vxs, vy = E vys / c
+    FOR_T(j, n) { const double v = scaled ? D[j] * vx[j] : vx[j]; t1[j] = v; dq[j] = -v; }
+    FOR_T(i, m) {
+        const int f = flag[i];
+        double v = 0.0;
+        if (f) { v = vy[i]; if (scaled) { v = E[i] * v; v = v * sc_cinv; } }
+        Av[i] = v;
+        du[i] = f > 0 ? v : 0.0; dl[i] = f < 0 ? v : 0.0;
+    }
+    if (threadIdx.x == 0) {
+        if (adj_status) { long *sp = adj_status + 3 * (size_t)b; sp[0] = 0; sp[1] = sweep; sp[2] = kact; }
+        if (adj_res) adj_res[b] = rel;
+    }
+    if (!wantQ && !wantA) return;
+    SYNC;
+    // ---- dL/dA and dL/dQ per stored entry, from the very vx, vy written above and the x, y the solve returned
+    const double *xu = P.sol_x, *yu = P.sol_y, *vxu = t1, *vyu = Av;
+    if (wantA) {
+        FOR_T(i, m) {
+            const int f = flag[i];
+            const double yi = yu[i], vyi = vyu[i];
+            for (int k = rp_s[i]; k < rp_s[i + 1]; k++) { const int j = P.Aci[k]; dA[mapA[k]] = f ? -(yi * vxu[j] + vyi * xu[j]) : 0.0; }
+        }
+    }
+    if (wantQ) {
+        // a stored entry that the full symmetric image does not carry (the other triangle under stype +-1) has no part in the solve: +0.0
+        if (mapQ) { FOR_T(e, nq) dQ[e] = 0.0; SYNC; }
+        FOR_T(r, n) for (int k = P.Qrp[r]; k < P.Qrp[r + 1]; k++) {
+            const int cc = P.Qci[k];
+            if (!mapQ) dQ[k] = -(vxu[cc] * xu[r]);                // stype 0: CSR entry k of row r IS stored entry k, row cc of column r
+            else if (r == cc) dQ[mapQ[k]] = -(vxu[r] * xu[r]);
+            else if (r > cc) dQ[mapQ[k]] = -(vxu[r] * xu[cc] + vxu[cc] * xu[r]);      // (its mirror image names the same stored entry)
+        }
+    }
+}
+
 // ================================================================================================
 // host side: pack a batch into one arena, one upload, one launch, one download
 // ================================================================================================

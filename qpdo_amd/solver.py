@@ -121,7 +121,8 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_device", "qpdo_amd_fleet_packed_layout", "qpdo_amd_fleet_get_packed_layout", "qpdo_amd_fleet_update_dev",
                "qpdo_amd_fleet_warm_start_dev", "qpdo_amd_fleet_warm_start_last_dev", "qpdo_amd_fleet_solve_dev", "qpdo_amd_fleet_fetch_last",
                "qpdo_amd_fleet_sync", "qpdo_amd_slab_trip_shape",
-               "qpdo_amd_fleet_packed_matrix_layout", "qpdo_amd_fleet_get_packed_matrix_layout", "qpdo_amd_fleet_update_matrices_dev"]
+               "qpdo_amd_fleet_packed_matrix_layout", "qpdo_amd_fleet_get_packed_matrix_layout", "qpdo_amd_fleet_update_matrices_dev",
+               "qpdo_amd_fleet_adjoint_dev", "qpdo_amd_fleet_get_adjoint_stats"]
 
 
 class FleetStats(C.Structure):
@@ -142,7 +143,14 @@ class FleetDevStats(C.Structure):
                 ("first_refused_item", C.c_long)]
 
 
+class FleetAdjointStats(C.Structure):
+    """QPDOAmdFleetAdjointStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("adjoint_calls", C.c_long), ("resident_extra_bytes", C.c_long)]
+
+
 FLEET_TABLE_BYTES = 16     # QPDO_AMD_FLEET_TABLE_BYTES
+FLEET_ADJOINT = 8          # QPDO_AMD_FLEET_ADJOINT
+ADJ_ACCEPTED, ADJ_NOT_ACCEPTED, ADJ_NOT_SOLVED, ADJ_BAD_PIVOT = 0, 1, 2, 3     # the codes of adj_status
 FLEET_MATRIX_UPDATES = 1   # QPDO_AMD_FLEET_MATRIX_UPDATES
 FLEET_MATRIX_TABLE_BYTES = 8     # QPDO_AMD_FLEET_MATRIX_TABLE_BYTES
 K_GLOBAL, K_PACKED, K_BAND = 0, 1, 2     # QPDO_AMD_SMALL_K_*: where the fused kernel keeps the Newton matrix
@@ -233,6 +241,9 @@ def lib():
                 L.qpdo_amd_fleet_packed_matrix_layout.argtypes = [C.c_long, C.POINTER(C.POINTER(QPDOData)), lp, lp]
                 L.qpdo_amd_fleet_get_packed_matrix_layout.argtypes = [C.c_void_p, lp, lp]
                 L.qpdo_amd_fleet_update_matrices_dev.argtypes = [C.c_void_p, vp, vp, vp, C.c_long, C.c_long, vp]
+            if hasattr(L, "qpdo_amd_fleet_adjoint_dev"):            # (the adjoint of the last solve; absent from an older build)
+                L.qpdo_amd_fleet_adjoint_dev.argtypes = [C.c_void_p] + [vp] * 10 + [C.c_double, C.c_long] + [C.c_long] * 4 + [vp]
+                L.qpdo_amd_fleet_get_adjoint_stats.argtypes = [C.c_void_p, C.POINTER(FleetAdjointStats)]
         if hasattr(L, "qpdo_amd_slab_trip_shape"):          # (absent from an older build, as below)
             L.qpdo_amd_slab_trip_shape.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
             L.qpdo_amd_slab_trip_shape.restype = C.c_int
@@ -925,9 +936,10 @@ def pack_matrix_values(dims, qstype, qoff, aoff, Q=None, A=None):
 class Fleet:
     """A resident fleet of small QPs (qpdo_amd_fleet_*): set up once, then per control step update() / warm_start_last() / solve(), one
     launch each for all items.  Item i carries the bits of a QPDO workspace of its own driven through the same calls.  The settings are
-    fixed at construction.  matrix_updates=True (QPDO_AMD_FLEET_MATRIX_UPDATES) also allows update_matrices(): new Q / A values per item."""
+    fixed at construction.  matrix_updates=True (QPDO_AMD_FLEET_MATRIX_UPDATES) also allows update_matrices(): new Q / A values per item;
+    adjoint=True (QPDO_AMD_FLEET_ADJOINT) allows adjoint_device(): gradients of the last solve (qpdo_amd/torch_layer.py builds on it)."""
 
-    def __init__(self, probs, settings=None, matrix_updates=False, **kw):
+    def __init__(self, probs, settings=None, matrix_updates=False, adjoint=False, **kw):
         self._h = None
         if settings is None:
             settings = default_settings(**kw)
@@ -941,8 +953,9 @@ class Fleet:
         self.dims = [(len(x), len(y)) for x, y in img.outs]
         arr = (C.POINTER(QPDOData) * max(1, self.count))(*[img.items[i].data for i in range(self.count)])
         self._qstype = [int(p.get("Qstype", -1)) for p in probs]
-        if matrix_updates:
-            h = lib().qpdo_amd_fleet_create_ex(self.count, arr, C.byref(settings), FLEET_MATRIX_UPDATES)
+        if matrix_updates or adjoint:
+            flags = (FLEET_MATRIX_UPDATES if matrix_updates else 0) | (FLEET_ADJOINT if adjoint else 0)
+            h = lib().qpdo_amd_fleet_create_ex(self.count, arr, C.byref(settings), flags)
         else:
             h = lib().qpdo_amd_fleet_create(self.count, arr, C.byref(settings))
         if not h:
@@ -955,6 +968,8 @@ class Fleet:
         self.kernel_seconds = 0.0
         self._layout, self._device, self._dev_out = None, None, None     # (the device calls: filled on first use)
         self._mlayout = None
+        self._adj_out = None
+        self.solve_serial = 0                                # solve()/solve_device() calls so far (FleetQP: is a backward still current?)
 
     def _ptrs(self, vecs, which, clip=False):
         """list of `count` vectors (None entries allowed) -> (array of pointers or None, the arrays kept alive)"""
@@ -1016,6 +1031,7 @@ class Fleet:
     def solve(self, results=True):
         """results=False: skip building the per-item dicts; the outputs are in info_view() and outs"""
         self._call(lib().qpdo_amd_fleet_solve(self._h, self._xp, self._yp, self._info), "solve")
+        self.solve_serial = getattr(self, "solve_serial", 0) + 1
         self.kernel_seconds = self.stats()["last_kernel_seconds"]
         return self.results() if results else None
 
@@ -1145,7 +1161,56 @@ class Fleet:
             raise ValueError("out: unknown keys %r" % sorted(unknown))
         ptrs, _ = self._dev_args([(k, out.get(k), dt, int(np.prod(shape))) for k, dt, shape in spec], None)
         self._call(lib().qpdo_amd_fleet_solve_dev(self._h, *ptrs, N, M, self._stream()), "solve_device")
+        self.solve_serial = getattr(self, "solve_serial", 0) + 1
         return out
+
+    def adjoint_device(self, gx, gy=None, matrices=False, out=None, tol=1e-9, max_sweeps=20):
+        """The adjoint of the last solve (qpdo_amd_fleet_adjoint_dev) on torch's current stream; returns without waiting.  gx: N float64 =
+        dL/dx, gy: M float64 = dL/dy or None (zero; entries of inactive rows are ignored).  Returns a dict of GPU tensors: dq (N), dl, du
+        (M), dQ_values (NQ) / dA_values (NA) in the packed value layout (None unless matrices=True, which needs matrix_updates=True),
+        active (M int32: +1 upper-active, -1 lower-active, 0), status (count, 3) int64 = code, sweeps, active rows (code 0 accepted,
+        1 not accepted, 2 the item is not solved, 3 bad pivot), residual (count) = the accepted relative residual.  An item with code != 0
+        has NaN in all its slices.  The tensors are allocated once and reused unless `out` (a dict with any of these keys) supplies
+        them.  Needs adjoint=True, and the most recent update / warm start / solve call of the fleet must be a solve."""
+        import torch
+        (no, mo) = self.packed_layout()
+        N, M = int(no[-1]), int(mo[-1])
+        NQ = NA = 0
+        if matrices:
+            qoff, aoff = self.packed_matrix_layout()
+            NQ, NA = int(qoff[-1]), int(aoff[-1])
+        spec = [("dq", "float64", (N,)), ("dl", "float64", (M,)), ("du", "float64", (M,)), ("dQ_values", "float64", (NQ,)), ("dA_values", "float64", (NA,)),
+                ("active", "int32", (M,)), ("status", "int64", (self.count, 3)), ("residual", "float64", (self.count,))]
+        (gxp, gyp), _ = self._dev_args([("gx", gx, "float64", N), ("gy", gy, "float64", M)], None)
+        if gx is None:
+            raise ValueError("gx: expected a tensor, got None")
+        if out is None:
+            if getattr(self, "_adj_out", None) is None or (matrices and self._adj_out["dQ_values"] is None):
+                dev = torch.device("cuda", self._device)
+                self._adj_out = {k: (None if k in ("dQ_values", "dA_values") and not matrices else torch.empty(shape, dtype=getattr(torch, dt), device=dev))
+                                 for k, dt, shape in spec}
+            out = dict(self._adj_out)
+            if not matrices:
+                out["dQ_values"] = out["dA_values"] = None
+        else:
+            unknown = set(out) - {k for k, _, _ in spec}
+            if unknown:
+                raise ValueError("out: unknown keys %r" % sorted(unknown))
+            out = {k: out.get(k) for k, _, _ in spec}
+            if not matrices:
+                out["dQ_values"] = out["dA_values"] = None
+        for k in ("dq", "dl", "du") + (("dQ_values", "dA_values") if matrices else ()):
+            if out[k] is None:
+                raise ValueError("out: '%s' is needed" % k)
+        ptrs, _ = self._dev_args([(k, out[k], dt, int(np.prod(shape))) for k, dt, shape in spec], None)
+        self._call(lib().qpdo_amd_fleet_adjoint_dev(self._h, gxp, gyp, *ptrs, float(tol), int(max_sweeps), N, M, NQ, NA, self._stream()), "adjoint_device")
+        return out
+
+    def adjoint_stats(self):
+        """adjoint_calls: adjoint_device calls that launched, since create; resident_extra_bytes: what adjoint=True holds on the device (0)"""
+        s = FleetAdjointStats()
+        self._call(lib().qpdo_amd_fleet_get_adjoint_stats(self._h, C.byref(s)), "adjoint_stats")
+        return {f: getattr(s, f) for f, _ in FleetAdjointStats._fields_}
 
     def fetch_last(self):
         """what results() returns, for the last solve whichever call launched it (waits for it; launches nothing)"""
