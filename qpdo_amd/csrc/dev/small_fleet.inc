@@ -394,10 +394,10 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
         F->lds = plan.lds; F->layout = plan.layout;
         F->kflags = small_kflags(plan);
         // the work vectors beside the factor in LDS when both fit (as a batch through the latency kernel has them)
-        size_t voff, vbytes;
-        small_vec_lds(F->lds, nmax, mmax, &voff, &vbytes);
-        const unsigned vec_off = (plan.layout != K_GLOBAL && voff + vbytes <= SMALL_LDS_BUDGET) ? (unsigned)voff : 0u;
-        if (vec_off) F->lds = voff + vbytes;
+        size_t lds_vec = 0;
+        const size_t voff = small_vec_lds(F->lds, nmax, mmax, &lds_vec);
+        const unsigned vec_off = plan.layout != K_GLOBAL ? (unsigned)voff : 0u;
+        if (vec_off) F->lds = lds_vec;
         char *dbase = F->arena;
         for (long i = 0; i < count; i++) {
             const QPDOData *d = data[i]; Lay &L = lay[(size_t)i]; SmallQP &p = hp[(size_t)i]; SmallRes &r = hr[(size_t)i]; FleetItem &I = F->it[(size_t)i];

@@ -31,6 +31,7 @@
 #include "qpdo_amd_ext.h"
 #include "qpdo_dev.h"
 #include "csc_convert.h"
+#include "small_lds.h"                   // the workgroup's LDS plan, NV_* / MV_* (the work vectors), K_GLOBAL / K_PACKED / K_BAND
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -95,8 +96,6 @@ struct SmallRes {
     const int *mapA, *mapQ;
     double *raw_q, *raw_l, *raw_u, *rawA, *rawQ;
 };
-enum { NV_X = 0, NV_XBAR, NV_QX, NV_ATY, NV_DF, NV_RD, NV_RDI, NV_RHS, NV_DX, NV_QDX, NV_ATDY, NV_D, NV_DINV, NV_T, NV_COUNT };
-enum { MV_Y = 0, MV_YBAR, MV_AX, MV_MU, MV_ISQ, MV_W, MV_RP, MV_RPOLD, MV_RPI, MV_DY, MV_ADX, MV_DW, MV_E, MV_EINV, MV_ATS, MV_T, MV_DWF, MV_COUNT };
 
 // diagnostic phase timer: lane 0 adds wall-clock ticks (100 MHz) to a buffer no other code reads
 #define PH(k) do { if (P.prof && threadIdx.x == 0) { const long long t_ = wall_clock64(); P.prof[k] += t_ - tph; tph = t_; } } while (0)
@@ -374,7 +373,6 @@ __device__ void small_scale(SmallQP &P, int iters, double *D, double *Dinv, doub
 // K is addressed as K[koff(j) + i] (i >= j).  When the packed lower triangle fits in LDS it lives there
 // (koff = j*n - j(j+1)/2); otherwise, when the lower BAND of every item fits, there as band storage -- element (i, j), j <= i <= j + b, at
 // j (b+1) + (i - j), i.e. koff = j*b --; otherwise in global memory as a full column-major square (koff = j*n).  ld: b or n.
-enum { K_GLOBAL = 0, K_PACKED = 1, K_BAND = 2 };      // = QPDO_AMD_SMALL_K_* (qpdo_amd_ext.h)
 struct KView {
     double *K; int n; int packed; int ld;
     __device__ __forceinline__ size_t off(int j) const { return packed ? (size_t)j * n - (size_t)j * (j + 1) / 2 : (size_t)j * ld; }
@@ -1283,6 +1281,37 @@ __device__ __attribute__((noinline)) void small_ldl_solve_band(int n_, int b_, d
     SYNC;
 }
 
+// ---- the item's view: what a one-workgroup-per-item kernel (the solve body, the fleet's adjoint) sets up before it computes -------------
+// Every field of the item's descriptor is the same for all threads, but loaded from global memory it lands in VECTOR registers, and
+// so does every pointer derived from it (~45 of them are live across the solve loop: two thirds of the 128-VGPR budget).  Passing
+// each field through v_readfirstlane tells the compiler it is uniform: the descriptor and the address arithmetic move to SGPRs.
+// ADJ: the adjoint's subset (no warm start, no certificates, no profile).  Returns the item's resident record (latency shape only).  Then, with
+// the kernel's own work between them (the adjoint refuses an unsolved item first): small_item_vectors, SMALL_LDS_CARVE (small_lds.h) + SMALL_KVIEW.
+template <int LAT, int ADJ = 0>
+__device__ __forceinline__ SmallRes *small_item_load(SmallQP &Pg, SmallQP &P) {
+    P.n = __builtin_amdgcn_readfirstlane(Pg.n); P.m = __builtin_amdgcn_readfirstlane(Pg.m); P.bw = __builtin_amdgcn_readfirstlane(Pg.bw);
+#define UNI_PTR(f) P.f = uni_ptr(Pg.f)
+    UNI_PTR(Arp); UNI_PTR(Aci); UNI_PTR(Aval); UNI_PTR(Trp); UNI_PTR(Tci); UNI_PTR(Tval); UNI_PTR(Qrp); UNI_PTR(Qci); UNI_PTR(Qval);
+#define UNI_SOLVE(f) if constexpr (!ADJ) UNI_PTR(f)
+    UNI_PTR(q); UNI_PTR(l); UNI_PTR(u); UNI_SOLVE(x0); UNI_SOLVE(y0); UNI_PTR(nv); UNI_PTR(mv); UNI_SOLVE(lsv); UNI_PTR(iv); UNI_PTR(tpos); UNI_PTR(K);
+    UNI_PTR(sol_x); UNI_PTR(sol_y); UNI_SOLVE(cert_dx); UNI_SOLVE(cert_dy); UNI_SOLVE(prof);
+#undef UNI_SOLVE
+#undef UNI_PTR
+    if constexpr (LAT) return uni_ptr(Pg.res); else return nullptr;        // (compiled out of the batch kernel: its register budget is spoken for)
+}
+// voff != 0: the launch keeps the work vectors in LDS behind U (small_lds.h): the item's nv / mv / iv are there
+__device__ __forceinline__ void small_item_vectors(SmallQP &P, double *dyn, unsigned voff) {
+    if (voff) {
+        P.nv = uni_ptr((double *)((char *)dyn + voff));
+        P.mv = P.nv + (size_t)NV_COUNT * P.n;
+        P.iv = (int *)(P.mv + (size_t)MV_COUNT * P.m);
+    }
+}
+// K where the launch's layout word puts it: packed or as a band at the start of U (Klds), else the item's square in global memory.
+// Statements in place, as the carve-up: behind a function the compiler schedules k_small_solve differently (more spills).
+#define SMALL_KVIEW(kv, n, bw, klds_ok, kband, Klds, Kglobal) \
+    KView kv; kv.n = (n); kv.packed = (klds_ok); kv.ld = (kband) ? (bw) : (n); kv.K = ((klds_ok) | (kband)) ? (Klds) : (Kglobal)
+
 // ---- the whole solve of one QP by one workgroup ----------------------------------------------------------
 // LAT = 0: the batch kernel (held to 128 VGPRs so that two workgroups share a CU); LAT = 1: the latency variant for ONE workspace
 // (qdev_small_resident_solve): the same code with the whole register file of a CU's SIMDs to itself (no spills) -- same operations
@@ -1298,28 +1327,20 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
     __shared__ double sm[32];
     __shared__ double red_scr[64];                    // two banks of reduction partials (RedBank)
     extern __shared__ __attribute__((aligned(16))) double dyn[];
-    // dynamic LDS: [xs: n][colbuf: n][tk: 2n][12n more for the four-column factorization with look-ahead][gbuf][d_s: m][rp_s: m+1][U], U = one region shared by the packed factor K
-    // (if it fits; else the item's band image n (b+1), K_BAND, if those of all items fit) and the linesearch scratch (delta, alpha, sort keys, sort indices, flags).  The linesearch of a
+    // dynamic LDS: small_lds.h has the plan ([xs][column buffers][gbuf][d_s][rp_s][U][work vectors]).  U is one region shared by K (the packed factor if it
+    // fits; else the item's band image n (b+1), K_BAND, if those of all items fit) and the linesearch scratch.  The linesearch of a
     // pass runs after the pass's solve, so it may overwrite K: the factor is then rebuilt in the next pass instead
     // of being reused when the weights did not change -- the same bits, a little more work -- and the workgroup needs
     // ~67 KB instead of ~104 KB at n = 120, m = 360: two workgroups per CU instead of one.
     if ((int)blockIdx.x >= count) return;
-    // Every field of the item's descriptor is the same for all threads, but loaded from global memory it lands in VECTOR registers, and
-    // so does every pointer derived from it (~45 of them are live across the solve loop: two thirds of the 128-VGPR budget).  Passing
-    // each field through v_readfirstlane tells the compiler it is uniform: the descriptor and the address arithmetic move to SGPRs.
     SmallQP &Pg = probs[blockIdx.x];                  // (outputs are written through this one)
     SmallQP P;
-    P.n = __builtin_amdgcn_readfirstlane(Pg.n); P.m = __builtin_amdgcn_readfirstlane(Pg.m); P.bw = __builtin_amdgcn_readfirstlane(Pg.bw);
-#define UNI_PTR(f) P.f = uni_ptr(Pg.f)
-    UNI_PTR(Arp); UNI_PTR(Aci); UNI_PTR(Aval); UNI_PTR(Trp); UNI_PTR(Tci); UNI_PTR(Tval); UNI_PTR(Qrp); UNI_PTR(Qci); UNI_PTR(Qval);
-    UNI_PTR(q); UNI_PTR(l); UNI_PTR(u); UNI_PTR(x0); UNI_PTR(y0); UNI_PTR(nv); UNI_PTR(mv); UNI_PTR(lsv); UNI_PTR(iv); UNI_PTR(tpos); UNI_PTR(K);
-    UNI_PTR(sol_x); UNI_PTR(sol_y); UNI_PTR(cert_dx); UNI_PTR(cert_dy); UNI_PTR(prof);
+    SmallRes *Rg = small_item_load<LAT>(Pg, P);
     // resident-mode extras (compiled out of the batch kernel: its register budget is spoken for)
-    SmallRes *Rg = nullptr; int resident = 0;
+    int resident = 0; unsigned voff = 0;
     const double *rD = nullptr, *rDinv = nullptr, *rE = nullptr, *rEinv = nullptr; double *state_x = nullptr, *state_Qx = nullptr;
     QPDOAmdTraceRec *trace = nullptr; long trace_cap = 0; double *out_x = nullptr, *out_y = nullptr; int mode = 0;
     if constexpr (LAT) {
-        Rg = uni_ptr(Pg.res);
         if (Rg) {
             resident = 1;
             rD = uni_ptr(Rg->rD); rDinv = uni_ptr(Rg->rDinv); rE = uni_ptr(Rg->rE); rEinv = uni_ptr(Rg->rEinv);
@@ -1339,14 +1360,9 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
             // One workspace has the CU to itself: its ~30 work vectors move from global memory (L2-resident, but every barrier that follows a
             // vector update waits for the stores' round trip) into LDS when they fit beside the factor.  Same operations on the same values.
         }
-        const unsigned voff = (unsigned)__builtin_amdgcn_readfirstlane((int)(Rg ? Rg->lds_vec_off : Pg.batch_vec_off));
-        if (voff) {
-            P.nv = uni_ptr((double *)((char *)dyn + voff));
-            P.mv = P.nv + (size_t)NV_COUNT * P.n;
-            P.iv = (int *)(P.mv + (size_t)MV_COUNT * P.m);
-        }
+        voff = (unsigned)__builtin_amdgcn_readfirstlane((int)(Rg ? Rg->lds_vec_off : Pg.batch_vec_off));
     }
-#undef UNI_PTR
+    small_item_vectors(P, dyn, voff);
     P.c_const = Pg.c_const;
     const int n = P.n, m = P.m;
     // info->setup_time / solve_time / run_time of this item (reference PROFILING build, qpdo.c:79-82,327-329,461-464) and the
@@ -1364,17 +1380,9 @@ __device__ __forceinline__ void small_solve_body(SmallQP *probs, int count, cons
            *res_prim_old = V[MV_RPOLD], *res_prim_in = V[MV_RPI], *dy = V[MV_DY], *Adx = V[MV_ADX], *dw = V[MV_DW], *E = V[MV_E],
            *Einv = V[MV_EINV], *ats = V[MV_ATS], *tm = V[MV_T], *dwf = V[MV_DWF];
     int *active = P.iv, *active_old = P.iv + m, *changed = P.iv + 2 * m;
-    double *xs = dyn, *colbuf = dyn + n, *tk = dyn + 2 * (size_t)n, *gbuf = dyn + ((LAT && (FLEET ? klds_ok : !kband)) ? 16 : 8) * (size_t)n;   // dyn .. dyn + 8n: l and l*d of four columns during a factorization; the latency kernel: two such buffers (look-ahead; a fleet whose factor is not packed in LDS and a band launch have no look-ahead: one)
-    double *d_s = gbuf + (((size_t)(n > m ? n : m) / 4 + 4 + 1) & ~(size_t)1);
-    int *rp_s = (int *)(d_s + m);
-    double *Klds = (double *)(rp_s + (((size_t)m + 1 + 3) & ~(size_t)3));          // start of U
-    double *ls_delta = Klds, *ls_alpha = ls_delta + 2 * (size_t)m;
-    size_t np2s = 1; while (np2s < 2 * (size_t)m) np2s <<= 1;                         // the bitonic sort pads 2m to a power of two
-    u64 *skey = (u64 *)(ls_alpha + 2 * (size_t)m);
-    u32 *sidx = (u32 *)(skey + np2s);
-    unsigned char *jflag = (unsigned char *)(sidx + np2s);
+    SMALL_LDS_CARVE(dyn, n, m, small_lds_colbuf_sets(LAT, FLEET, klay));      // declares xs, gbuf, d_s, rp_s, Klds (the start of U), ls_delta, ls_alpha, skey, sidx, jflag (small_lds.h)
     const int bw = P.bw, k_in_lds = klds_ok | kband;
-    KView kv; kv.n = n; kv.packed = klds_ok; kv.ld = kband ? bw : n; kv.K = k_in_lds ? Klds : P.K;
+    SMALL_KVIEW(kv, n, bw, klds_ok, kband, Klds, P.K);
     const int scaled = st.scaling > 0, prox = (int)st.proximal;
     double sc_c = 1.0, sc_cinv = 1.0;
 
@@ -1816,13 +1824,8 @@ __global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet_adjoint(SmallQP *
     const int b = blockIdx.x;
     SmallQP &Pg = probs[b];
     SmallQP P;
-    P.n = __builtin_amdgcn_readfirstlane(Pg.n); P.m = __builtin_amdgcn_readfirstlane(Pg.m); P.bw = __builtin_amdgcn_readfirstlane(Pg.bw);
-#define UNI_PTR(f) P.f = uni_ptr(Pg.f)
-    UNI_PTR(Arp); UNI_PTR(Aci); UNI_PTR(Aval); UNI_PTR(Trp); UNI_PTR(Tci); UNI_PTR(Tval); UNI_PTR(Qrp); UNI_PTR(Qci); UNI_PTR(Qval);
-    UNI_PTR(q); UNI_PTR(l); UNI_PTR(u); UNI_PTR(nv); UNI_PTR(mv); UNI_PTR(iv); UNI_PTR(tpos); UNI_PTR(K); UNI_PTR(sol_x); UNI_PTR(sol_y);
-#undef UNI_PTR
+    const SmallRes *Rg = small_item_load<1, 1>(Pg, P);
     P.prof = nullptr;
-    const SmallRes *Rg = uni_ptr(Pg.res);
     const int n = P.n, m = P.m;
     // the item's slices of the caller's packed arrays
     const int no = __builtin_amdgcn_readfirstlane(offs[b]), mo = __builtin_amdgcn_readfirstlane(offs[count + 1 + b]);
@@ -1838,12 +1841,7 @@ __global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet_adjoint(SmallQP *
     const long fs = Rg->fleet_status;
     if (__builtin_amdgcn_readfirstlane((int)(fs != QPDO_SOLVED))) { small_adjoint_refuse(2, 0, 0, n, m, nq, na, dq, dl, du, dQ, dA, active, adj_status, adj_res); return; }
     // the work vectors where the solve has them (beside the factor in LDS, or the item's global area: every solve zeroes them before use)
-    const unsigned voff = (unsigned)__builtin_amdgcn_readfirstlane((int)Rg->lds_vec_off);
-    if (voff) {
-        P.nv = uni_ptr((double *)((char *)dyn + voff));
-        P.mv = P.nv + (size_t)NV_COUNT * n;
-        P.iv = (int *)(P.mv + (size_t)MV_COUNT * m);
-    }
+    small_item_vectors(P, dyn, (unsigned)__builtin_amdgcn_readfirstlane((int)Rg->lds_vec_off));
     enum { AN_X = 0, AN_VX, AN_RX, AN_DVX, AN_RHS, AN_T1, AN_T2, AN_GX, AN_D, AN_DINV, AN_COUNT };
     enum { AM_VY = 0, AM_RY, AM_WRY, AM_W, AM_AV, AM_GY, AM_E, AM_EINV, AM_COUNT };
     static_assert(AN_COUNT <= NV_COUNT && AM_COUNT <= MV_COUNT, "the adjoint lives in the solve's work-vector area");
@@ -1853,13 +1851,10 @@ __global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet_adjoint(SmallQP *
     double *vy = P.mv + (size_t)AM_VY * m, *ry = P.mv + (size_t)AM_RY * m, *wry = P.mv + (size_t)AM_WRY * m, *W = P.mv + (size_t)AM_W * m,
            *Av = P.mv + (size_t)AM_AV * m, *gys = P.mv + (size_t)AM_GY * m, *E = P.mv + (size_t)AM_E * m, *Einv = P.mv + (size_t)AM_EINV * m;
     int *flag = P.iv;
-    // dynamic LDS as the solve lays it out: [xs: n][column buffers: 16n with the look-ahead factorization, else 8n][gbuf][d_s: m][rp_s: m+1][U: K]
-    double *xs = dyn, *gbuf = dyn + (klds_ok ? 16 : 8) * (size_t)n;
-    double *d_s = gbuf + (((size_t)(n > m ? n : m) / 4 + 4 + 1) & ~(size_t)1);
-    int *rp_s = (int *)(d_s + m);
-    double *Klds = (double *)(rp_s + (((size_t)m + 1 + 3) & ~(size_t)3));
+    // the dynamic LDS as the solve carves it (small_lds.h), K in U
+    SMALL_LDS_CARVE(dyn, n, m, small_lds_colbuf_sets(1, 1, klay));
     const int bw = P.bw;
-    KView kv; kv.n = n; kv.packed = klds_ok; kv.ld = kband ? bw : n; kv.K = (klds_ok | kband) ? Klds : P.K;
+    SMALL_KVIEW(kv, n, bw, klds_ok, kband, Klds, P.K);
     const int scaled = st.scaling > 0;
     const double sc_c = scaled ? Rg->r_c : 1.0, sc_cinv = scaled ? Rg->r_cinv : 1.0;
     const double *rD = uni_ptr(Rg->rD), *rDinv = uni_ptr(Rg->rDinv), *rE = uni_ptr(Rg->rE), *rEinv = uni_ptr(Rg->rEinv);
@@ -2044,10 +2039,12 @@ static void lay_describe(SmallQP &p, const QPDOData *d, const Lay &L, char *dbas
     p.K = (double *)(dbase + L.K);
     p.sol_x = (double *)(dbase + L.solx); p.sol_y = (double *)(dbase + L.soly); p.cert_dx = (double *)(dbase + L.dx); p.cert_dy = (double *)(dbase + L.dy);
 }
-// the work vectors of an item of (nmax, mmax) behind `lds` bytes of the latency layout: their offset and size in the dynamic LDS
-static void small_vec_lds(size_t lds, size_t nmax, size_t mmax, size_t *voff, size_t *vbytes) {
-    *voff = (lds + 15) & ~(size_t)15;
-    *vbytes = ((size_t)NV_COUNT * nmax + (size_t)MV_COUNT * mmax) * 8 + 3 * mmax * 4 + 16;
+// The work vectors of an item of (nmax, mmax) behind `lds` bytes of the dynamic LDS (small_lds.h), if both fit the budget: their offset (the
+// kernels' lds_vec_off / batch_vec_off; 0: no room) and the launch's dynamic LDS with them.  Whether a launch takes it is its caller's rule.
+static size_t small_vec_lds(size_t lds, size_t nmax, size_t mmax, size_t *lds_with) {
+    size_t vbytes; const size_t voff = small_lds_vec(lds, (int)nmax, (int)mmax, &vbytes);
+    if (voff + vbytes > SMALL_LDS_BUDGET) return 0;
+    *lds_with = voff + vbytes; return voff;
 }
 struct SmallSlot {
     int device = -1;
@@ -2097,21 +2094,18 @@ static int pinned_reserve(char **buf, size_t *cap, size_t need) {
     *cap = want;
     return 0;
 }
-// dynamic LDS of a workgroup whose largest item has (nmax, mmax): the fixed part + the union region U (packed factor K if it fits,
-// else the linesearch scratch alone; the kernel's layout, k_small_solve).  klds_ok (optional out): 1 when K lives in LDS; passing
-// NULL sizes the K-in-global-memory layout.
-static const size_t SMALL_LDS_BUDGET = 160 * 1024 - 1024;                // static LDS: reduction scratch only
-static size_t small_lds_bytes(size_t nmax, size_t mmax, int *klds_ok, size_t *union_bytes = nullptr, bool lat = false) {
-    size_t lds = (lat ? 16 : 8) * nmax * 8 + ((((nmax > mmax ? nmax : mmax) / 4 + 4 + 1) & ~(size_t)1) * 8) + mmax * 8 + (((mmax + 1 + 3) & ~(size_t)3) * 4);
-    const size_t kbytes = nmax * (nmax + 1) / 2 * 8;
-    size_t np2 = 1; while (np2 < 2 * mmax) np2 <<= 1;
-    size_t lsbytes = 2 * mmax * (8 + 8) + np2 * (8 + 4) + ((2 * mmax + 15) & ~(size_t)15);   // delta, alpha, keys, indices, flags
-    { const size_t gdots = 8 * (2 * (mmax / 4 + 4) + 2 * (nmax / 4 + 4)); if (gdots > lsbytes) lsbytes = gdots; }   // the group arrays of the four dot products live there too
-    const int ok = klds_ok && (lds + (kbytes > lsbytes ? kbytes : lsbytes) <= SMALL_LDS_BUDGET);
-    if (klds_ok) *klds_ok = ok;
-    const size_t ub = (ok && kbytes > lsbytes) ? kbytes : lsbytes;
+// Column-buffer sets of a launch (lat: k_small_solve_lat / k_small_fleet*) as its kernel counts them; 0 for the one combination no launch takes:
+// the latency kernel outside a fleet with K in global memory (slot_submit sends it PACKED and BAND plans only, the resident create refuses the item).
+static int small_launch_sets(int lat, int fleet, int layout) {
+    return (lat && !fleet && layout == K_GLOBAL) ? 0 : small_lds_colbuf_sets(lat, fleet, layout);
+}
+// dynamic LDS of a workgroup whose largest item has (nmax, mmax), read from the kernels' plan (small_lds.h): the fixed part + the union region U (packed
+// factor K if it fits, else the linesearch scratch alone).  klds_ok (optional out): 1 when K lives in LDS; passing NULL sizes the K-in-global-memory layout.
+static size_t small_lds_bytes(size_t nmax, size_t mmax, int sets, int *klds_ok, size_t *union_bytes = nullptr) {
+    const SmallLds L = small_lds_layout((int)nmax, (int)mmax, sets);
+    const size_t ub = small_lds_union_bytes(&L, klds_ok != nullptr, klds_ok);
     if (union_bytes) *union_bytes = ub;
-    return lds + ub;
+    return L.U + ub;
 }
 // ---- where K lives: THE rule, in one place (slot_submit, the fleet's create and qpdo_amd_small_factor_layout all come here) --------------
 // Half-bandwidth of Q + sigma I + A'DA for every D: the largest |i - j| over the stored entries of Q and the largest column span (last
@@ -2156,12 +2150,13 @@ struct SmallPlan { int layout; size_t lds, ubytes; };
 static int small_kflags(const SmallPlan &p) { return p.layout | ((int)(p.ubytes / 8) << 2); }
 template <class BB> static SmallPlan small_plan(int kind, size_t nmax, size_t mmax, BB band_bytes) {
     SmallPlan p; int ok = 0;
-    p.lds = small_lds_bytes(nmax, mmax, &ok, &p.ubytes, kind == 2);
+    const int fleet = kind == 2;                      // a fleet's kernels have the latency shape, a batch is planned for the wide kernel
+    p.lds = small_lds_bytes(nmax, mmax, small_launch_sets(fleet, fleet, K_PACKED), &ok, &p.ubytes);
     bool forced_global = false;
     if (kind != 2) { if (const char *kg = getenv("QPDO_SMALL_K_GLOBAL")) { if (atoi(kg) && ok) { ok = 0; forced_global = true; } } }      // occupancy experiments
     if (ok) { p.layout = K_PACKED; return p; }
     p.layout = K_GLOBAL;
-    p.lds = small_lds_bytes(nmax, mmax, nullptr, &p.ubytes, false);      // the factor in global memory: no look-ahead, one set of column buffers (fits up to n = m = 1024)
+    p.lds = small_lds_bytes(nmax, mmax, small_launch_sets(fleet, fleet, K_GLOBAL), nullptr, &p.ubytes);      // the factor in global memory: no look-ahead, one set of column buffers (fits up to n = m = 1024)
     const char *be = getenv("QPDO_SMALL_BAND");
     if (forced_global || (be && atoi(be) == 0)) return p;
     const size_t bb = band_bytes(), fixed = p.lds - p.ubytes;
@@ -2283,7 +2278,7 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
         if (plan.layout == K_BAND) for (long i = 0; i < count; i++) hp[(size_t)i].bw = bws[(size_t)i];
         S.layout = plan.layout;
         int klds_lat = 0; size_t ub_lat = 0;
-        const size_t lds_lat = small_lds_bytes(nmax, mmax, &klds_lat, &ub_lat, true);           // the latency kernel's layout (two factor buffers)
+        const size_t lds_lat = small_lds_bytes(nmax, mmax, small_launch_sets(1, 0, K_PACKED), &klds_lat, &ub_lat);       // the latency kernel's layout (two factor buffers)
         SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(budget)));
         if (const char *pad = getenv("QPDO_SMALL_LDS_MIN")) { const size_t v = (size_t)atol(pad); if (v > lds && v <= budget) lds = v; }   // occupancy experiments
         const int kflags = small_kflags(plan);       // (the LDS_MIN padding experiment below the launch only grows the tail)
@@ -2295,10 +2290,10 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
         // overlap their stragglers with the next batches' ordinary items: they take the wide kernel.
         // A band launch takes the latency kernel on the same conditions: its work vectors go behind the band image where they fit (its
         // fixed part is the wide kernel's: no look-ahead buffers).
-        size_t voff, vbytes;
-        small_vec_lds(plan.layout == K_BAND ? plan.lds : lds_lat, nmax, mmax, &voff, &vbytes);
+        size_t lds_vec = 0;
+        const size_t voff = small_vec_lds(plan.layout == K_BAND ? plan.lds : lds_lat, nmax, mmax, &lds_vec);
         const char *bk = getenv("QPDO_SMALL_BATCH_KERNEL");
-        const bool lat_fits = (plan.layout == K_BAND || (klds_ok && klds_lat && ub_lat == ubytes)) && voff + vbytes <= budget;
+        const bool lat_fits = small_launch_sets(1, 0, plan.layout) && (plan.layout == K_BAND || (klds_ok && klds_lat && ub_lat == ubytes)) && voff;
         const bool use_lat = lat_fits && !(bk && !strcmp(bk, "wide")) && (bk ? !strcmp(bk, "lat") : (one_at_a_time && (count <= 256 || settings->max_iter >= 1000)));
         if (use_lat) {
             for (long i = 0; i < count; i++) hp[(size_t)i].batch_vec_off = (unsigned)voff;
@@ -2306,7 +2301,7 @@ static int slot_submit(SmallSlot &S, int device, long count, QPDOAmdBatchItem *i
         }
         SHIP(hipMemcpyAsync(S.dprobs, hp, (size_t)count * sizeof(SmallQP), hipMemcpyHostToDevice, S.stream));
         SHIP(hipEventRecord(S.ev0, S.stream));
-        if (use_lat) hipLaunchKernelGGL(k_small_solve_lat, dim3((unsigned)count), dim3(SM_THREADS), voff + vbytes, S.stream, S.dprobs, (int)count, *settings, kflags);
+        if (use_lat) hipLaunchKernelGGL(k_small_solve_lat, dim3((unsigned)count), dim3(SM_THREADS), lds_vec, S.stream, S.dprobs, (int)count, *settings, kflags);
         else hipLaunchKernelGGL(k_small_solve, dim3((unsigned)count), dim3(SM_THREADS), lds, S.stream, S.dprobs, (int)count, *settings, kflags);
         SHIP(hipEventRecord(S.ev1, S.stream));
     }
@@ -2479,7 +2474,7 @@ struct SmallResident {
 int qdev_small_resident_fits(int32_t n, int32_t m) {
     if (n < 1 || n > SM_MAX_N || m < 0 || m > SM_MAX_M) return 0;
     int ok = 0;
-    (void)small_lds_bytes((size_t)n, (size_t)m, &ok, nullptr, true);
+    (void)small_lds_bytes((size_t)n, (size_t)m, small_launch_sets(1, 0, K_PACKED), &ok);
     return ok;                                          // the packed factor must live in LDS: beyond that one workgroup is the wrong shape
 }
 void qdev_small_resident_destroy(void *h) {
@@ -2516,13 +2511,15 @@ void *qdev_small_resident_create(const QdevSmallView *v, long trace_cap) {
     SHIP(hipHostMalloc((void **)&R->htrace, (size_t)trace_cap * sizeof(QPDOAmdTraceRec), hipHostMallocDefault));
     R->trace_cap = trace_cap;
     SHIP(hipEventCreate(&R->ev0)); SHIP(hipEventCreate(&R->ev1));
-    { size_t ub = 0; R->lds = small_lds_bytes(n, m, &R->klds_ok, &ub, true); R->kflags = (R->klds_ok ? K_PACKED : K_GLOBAL) | ((int)(ub / 8) << 2); }
-    {   // vectors into LDS when they fit beside everything else (QPDO_SMALL_VEC_LDS=0: keep them in global memory)
-        const size_t off = (R->lds + 15) & ~(size_t)15;
-        const size_t vbytes = ((size_t)NV_COUNT * n + (size_t)MV_COUNT * m) * 8 + 3 * m * 4 + 16;
+    {   // the latency kernel on a packed factor (an item whose factor does not fit is refused below)
+        SmallPlan plan; plan.lds = small_lds_bytes(n, m, small_launch_sets(1, 0, K_PACKED), &R->klds_ok, &plan.ubytes);
+        plan.layout = R->klds_ok ? K_PACKED : K_GLOBAL;
+        R->lds = plan.lds; R->kflags = small_kflags(plan);
+        // vectors into LDS when they fit beside everything else (QPDO_SMALL_VEC_LDS=0: keep them in global memory)
+        size_t lds_vec = 0; const size_t voff = small_vec_lds(R->lds, n, m, &lds_vec);
         const char *ve = getenv("QPDO_SMALL_VEC_LDS");
         R->lds_vec_off = 0;
-        if (R->klds_ok && off + vbytes <= SMALL_LDS_BUDGET && !(ve && atoi(ve) == 0)) { R->lds_vec_off = (unsigned)off; R->lds = off + vbytes; }
+        if (R->klds_ok && voff && !(ve && atoi(ve) == 0)) { R->lds_vec_off = (unsigned)voff; R->lds = lds_vec; }
     }
     if (!R->klds_ok) { snprintf(s_err, sizeof(s_err), "resident fused solve: the packed factor of n = %d does not fit in LDS", v->n); rc = -1; goto done; }
     SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_solve_lat), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
