@@ -628,6 +628,72 @@ int  qpdo_amd_fleet_adjoint_dev(QPDOAmdFleet *f, const double *gx /* N */, const
                                 long *adj_status /* count x 3: code, sweeps, k; or NULL */, double *adj_res /* count; or NULL */, double tol, long max_sweeps,
                                 long n_len, long m_len, long q_len, long a_len, void *stream);
 int  qpdo_amd_fleet_get_adjoint_stats(const QPDOAmdFleet *f, QPDOAmdFleetAdjointStats *out);
+/* ---- MANY RIGHT-HAND SIDES PER FACTORIZATION: the rows of a Jacobian (adjoint_multi_dev) and the TANGENT of the last solve (tangent_dev) ----
+ * Both solve the adjoint's system -- the KKT matrix of the active set is symmetric -- on a fleet created with QPDO_AMD_FLEET_ADJOINT (the
+ * matrix arrays dQx, dAx, tQx, tAx also need QPDO_AMD_FLEET_MATRIX_UPDATES); there is no flag of their own.  One launch (k_small_fleet_sens),
+ * one workgroup per item, in the solve's own launch shape.  Per item, ONCE: the status gate, the classification of the rows, W and sigma,
+ * the assembly of K, its factorization (all three layouts of K) and the pivot check, exactly as in adjoint_dev.  Then the nrhs right-hand
+ * sides follow, each by the adjoint call's sweeps, sigma, W and acceptance rule, every right-hand side's operations in the single call's order.
+ * LAYOUT   right-hand-side major: right-hand side r of an array whose per-RHS length is L (N, M, NQ or NA) starts at r * L, and every such
+ *          slab is one of the packed arrays the other device calls take.  n_len, m_len, q_len, a_len stay N, M, NQ, NA.  `active` (M) is ONE
+ *          array: the flags depend on the solve, not on the right-hand side; an item with code 2 or 3 gets 0 flags, every other item its
+ *          flags whatever the codes of its right-hand sides.  status[r][item] (nrhs x count x 3 int64) is the triple (code, sweeps, k) of
+ *          the single call with the same codes 0 .. 3; codes 2 and 3 are the item's and repeat for every r, code 1 is one right-hand
+ *          side's own and touches no other right-hand side of the item.  res[r][item] (nrhs x count) as adj_res.
+ * ADJOINT  qpdo_amd_fleet_adjoint_multi_dev: slab r of dq, dl, du, dQx, dAx, status and res carries THE BITS qpdo_amd_fleet_adjoint_dev delivers
+ *          for slab r of gx / gy after the same solve (NaN slices included), in all three layouts of K, with and without scaling.
+ * TANGENT  qpdo_amd_fleet_tangent_dev: the first-order change (dx, dy) of the solution for a change (tq, tl, tu, tQ, tA) of the item's data at
+ *          a fixed active set -- the advanced-step / sensitivity update of an MPC controller: x + dx for the measured state from one
+ *          factorization and a few triangular solves instead of a re-solve.  All quantities are the caller's UNSCALED ones; S and the flags as
+ *          for the adjoint; b = u on +1 rows and l on -1 rows:
+ *              [ Q    A_S' ] [dx  ]   [ -(tq + tQ x + tA_S' y_S) ]
+ *              [ A_S  0    ] [dy_S] = [  tb_S - tA_S x           ]
+ *          dy_i is an exact +0.0 off S.  A NULL array is a zero perturbation (all five NULL: refused).  Entries of tl, tu, tAx on rows that do
+ *          not use them (tl on a row that is not -1, tu on a row that is not +1, tAx on an unflagged row) are ignored and may hold NaN.  tQ
+ *          acts as the symmetric matrix its stored entries stand for: under stype +-1 an off-diagonal stored entry (a, b) contributes to
+ *          rows a and b and an entry in the ignored triangle contributes nothing; under stype 0 the caller passes a SYMMETRIC perturbation
+ *          (as the solver reads a stype-0 Q as symmetric) and row a is evaluated from the stored entries of COLUMN a.  The right-hand side
+ *          is formed in fp64 on the device from the x, y the solve returned, one thread per row in ascending stored order
+ *          (rx_j: tq_j, then the entries of row j of tQ, then those of column j of tA in the caller's CSC order; ry_i: the entries of
+ *          row i of tA in column order, subtracted from tb_i), taken into the item's scaled space as the adjoint takes gx, gy, and solved
+ *          by the same sweeps.  ACCEPTANCE on the true unscaled residual against tol * max(||rx||_inf, ||ry_S||_inf); a non-finite entry
+ *          among those used is never accepted (code 1); a zero right-hand side is accepted at sweep 0 with zeros.
+ * DUALITY  with (vx, vy) = (-dq, dl + du) of the adjoint for (gx, gy) and (dx, dy) of the tangent, in exact arithmetic
+ *              <gx, dx> + <gy_S, dy_S> = <dq, tq> + <dl, tl> + <du, tu> + <dQx, tQx> + <dAx, tAx>.
+ * Checks   the adjoint call's, on the host before the launch (a refused call has launched nothing), and: nrhs < 1; nrhs > 2147483647 (the
+ *          kernel counts right-hand sides in 32 bits; the offsets r * N, r * M, r * NQ, r * NA are formed in 64 bits and have no limit of
+ *          their own); NULL dx or dy; "no tangent passed".  THE MOST RECENT STATE-CHANGING FLEET CALL WAS NOT A SOLVE applies unchanged;
+ *          neither call is state-changing: any mix of adjoint_dev, adjoint_multi_dev and tangent_dev calls may follow one solve.
+ * ORDER    that of the other device calls: enqueues on `stream`, returns at once, joins the fleet's one-event chain.  No hipGraph capture.
+ * GROUPS   qpdo_amd_fleet_rhs_group: the right-hand sides one workgroup carries AT ONCE on this fleet; -1: NULL fleet.  G = 8 where K is
+ *          PACKED in LDS (one right-hand side per wave of the workgroup: wave w runs the triangular solves of right-hand side w, the
+ *          products and element loops run over (right-hand side, row) pairs, a right-hand side leaves the sweeps at its own sweep count);
+ *          a last, partial group and nrhs < G work; a call with nrhs = 1 runs as G = 1.  G = 1 in the BAND and GLOBAL layouts: the
+ *          right-hand sides follow one another in the solve's work-vector area.  Either way every right-hand side receives the single
+ *          call's operations in its order.  QPDO_AMD_FLEET_RHS_GROUP=1..8 in the environment at create overrides G (a measuring switch).
+ * MEMORY   G = 1 needs none.  G > 1 keeps the carried right-hand sides' vectors in a device scratch of G x (7 N + 5 M) doubles, allocated
+ *          ONCE by the first call with nrhs > 1 -- a host allocation: THAT CALL MAY BLOCK until earlier device work has finished, as
+ *          qpdo_amd_update_matrices says of its maps --, reported in scratch_bytes and freed by qpdo_amd_fleet_destroy.
+ *          QPDOAmdFleetAdjointStats.resident_extra_bytes stays 0.
+ * Stats    QPDOAmdFleetSensitivityStats counts the two calls that launched and their right-hand sides; adjoint_calls, solve_launches, solves and
+ *          the device-call counters do not move. */
+typedef struct {
+    long calls;                             /* adjoint_multi_dev + tangent_dev calls that launched, since create */
+    long rhs_total;                         /* right-hand sides of those calls */
+    long scratch_bytes;                     /* device scratch allocated for carrying G > 1 right-hand sides at once; 0 until a call needs it */
+} QPDOAmdFleetSensitivityStats;
+int  qpdo_amd_fleet_adjoint_multi_dev(QPDOAmdFleet *f, long nrhs, const double *gx /* nrhs x N */, const double *gy /* nrhs x M or NULL */,
+                                      double *dq /* nrhs x N */, double *dl /* nrhs x M */, double *du /* nrhs x M */,
+                                      double *dQx /* nrhs x NQ or NULL */, double *dAx /* nrhs x NA or NULL */, int *active /* M int32 or NULL */,
+                                      long *status /* nrhs x count x 3 or NULL */, double *res /* nrhs x count or NULL */, double tol, long max_sweeps,
+                                      long n_len, long m_len, long q_len, long a_len, void *stream);
+int  qpdo_amd_fleet_tangent_dev(QPDOAmdFleet *f, long nrhs, const double *tq /* nrhs x N or NULL */, const double *tl /* nrhs x M or NULL */,
+                                const double *tu /* nrhs x M or NULL */, const double *tQx /* nrhs x NQ or NULL */, const double *tAx /* nrhs x NA or NULL */,
+                                double *dx /* nrhs x N */, double *dy /* nrhs x M */, int *active /* M int32 or NULL */,
+                                long *status /* nrhs x count x 3 or NULL */, double *res /* nrhs x count or NULL */, double tol, long max_sweeps,
+                                long n_len, long m_len, long q_len, long a_len, void *stream);
+int  qpdo_amd_fleet_rhs_group(const QPDOAmdFleet *f);
+int  qpdo_amd_fleet_get_sensitivity_stats(const QPDOAmdFleet *f, QPDOAmdFleetSensitivityStats *out);
 void qpdo_amd_fleet_destroy(QPDOAmdFleet *f);
 
 #ifdef __cplusplus

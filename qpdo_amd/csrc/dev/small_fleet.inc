@@ -211,6 +211,7 @@ __global__ __launch_bounds__(FLEET_IO_THREADS) void k_small_fleet_scatter(const 
 struct FleetItem { int n, m; size_t o_q, o_l, o_u, o_solx, o_soly, o_dx, o_dy, out_off; };
 // MATRIX_UPDATES: the create-time CSC pattern of an item's A and stored Q (host copies: every update_matrices call is compared against them in full)
 struct FleetPattern { size_t Anrow = 0, Ancol = 0, Qnrow = 0, Qncol = 0; int Qstype = 0; std::vector<int> Ap, Ai, Qp, Qi; };
+static const int FLEET_RHS_GROUP = 8;                 // one right-hand side per wave of the workgroup
 struct SmallFleet {
     int device = 0; long count = 0; QPDOSettings st;
     hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -242,6 +243,8 @@ struct SmallFleet {
     // QPDO_AMD_FLEET_ADJOINT: the most recent state-changing call was a solve (the resident q, l, u and matrices belong to the x, y it returned)
     bool last_was_solve = false;
     long adjoint_calls = 0;
+    int rhs_group = 1; double *sens_scratch = nullptr; long sens_scratch_bytes = 0;     // k_small_fleet_sens: G, and its slots (allocated at the first call that needs them)
+    long sens_calls = 0, sens_rhs = 0;              // adjoint_multi_dev + tangent_dev calls that launched, and their right-hand sides
 };
 // Ordering between the streams the fleet is driven on, its own included: ONE event.  Every call makes its stream wait for what the previous
 // call recorded and records again behind its last operation, so host and device calls mix freely and the caller may change streams.
@@ -260,6 +263,7 @@ static void fleet_free(SmallFleet *F) {
     if (F->ev_chain) (void)hipEventDestroy(F->ev_chain);
     if (F->dmstage) (void)hipFree(F->dmstage);
     if (F->dmoffs) (void)hipFree(F->dmoffs);
+    if (F->sens_scratch) (void)hipFree(F->sens_scratch);
     if (F->hmstage) (void)hipHostFree(F->hmstage);
     if (F->hstage) (void)hipHostFree(F->hstage);
     if (F->hout) (void)hipHostFree(F->hout);
@@ -427,6 +431,14 @@ void *qdev_small_fleet_create(int device, long count, const void *const *data_, 
     SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
     if (flags & QPDO_AMD_FLEET_ADJOINT)                // (the adjoint launch takes the solve's plan: nothing of its own is resident)
         SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet_adjoint), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
+    if ((flags & QPDO_AMD_FLEET_ADJOINT) && F->layout == K_PACKED) {
+        // (a measuring switch: QPDO_AMD_FLEET_RHS_GROUP=1..8 at create overrides the group size, tools/fleet_sensitivity_latency.py)
+        const char *e = getenv("QPDO_AMD_FLEET_RHS_GROUP");
+        const int g = e ? atoi(e) : FLEET_RHS_GROUP;
+        F->rhs_group = g < 1 ? 1 : (g > 8 ? 8 : g);
+    }
+    if (flags & QPDO_AMD_FLEET_ADJOINT)                // (adjoint_multi_dev, tangent_dev: the same plan)
+        SHIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_small_fleet_sens), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMALL_LDS_BUDGET));
     hipLaunchKernelGGL(k_small_fleet_setup, dim3((unsigned)count), dim3(SM_THREADS), 0, F->stream, F->dprobs, (int)count, F->st);
     SHIP(hipGetLastError());
     SHIP(fleet_leave(F, F->stream));
@@ -756,6 +768,103 @@ done:
     return rc;
 }
 long qdev_small_fleet_adjoint_calls(const void *h_) { return ((const SmallFleet *)h_)->adjoint_calls; }
+// Many right-hand sides per factorization (include/qpdo_amd_ext.h): the adjoint call's checks and a few of their own on the host, then ONE
+// launch of k_small_fleet_sens in the solve's launch shape, no wait.  Neither call changes the fleet's state or moves any other counter.
+// The kernel addresses right-hand side r at r * (per-RHS length) in 64 bits; what it counts in 32 bits is the right-hand sides.
+static const long FLEET_SENS_MAX_NRHS = 2147483647L;
+static int fleet_sens_checks(const SmallFleet *F, long nrhs, bool matrices, const char *mname, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len,
+                             bool need_q, bool need_a) {
+    if (!(F->flags & QPDO_AMD_FLEET_ADJOINT)) { snprintf(s_err, sizeof(s_err), "the fleet was created without QPDO_AMD_FLEET_ADJOINT (qpdo_amd_fleet_create_ex)"); return -1; }
+    if (nrhs < 1) { snprintf(s_err, sizeof(s_err), "nrhs is %ld, it must be at least 1", nrhs); return -1; }
+    if (nrhs > FLEET_SENS_MAX_NRHS) { snprintf(s_err, sizeof(s_err), "nrhs is %ld, the kernel counts at most %ld right-hand sides", nrhs, FLEET_SENS_MAX_NRHS); return -1; }
+    if (fleet_dev_lens(F, n_len, m_len)) return -1;
+    if (matrices) {
+        if (!(F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES)) { snprintf(s_err, sizeof(s_err), "%s was passed, but %s", mname, FLEET_NO_MATRIX_FLAG); return -1; }
+        const long NQ = F->qoff.back(), NA = F->aoff.back();
+        if (need_q && q_len != NQ) { snprintf(s_err, sizeof(s_err), "q_len is %ld, the fleet's packed Q values have %ld elements", q_len, NQ); return -1; }
+        if (need_a && a_len != NA) { snprintf(s_err, sizeof(s_err), "a_len is %ld, the fleet's packed A values have %ld elements", a_len, NA); return -1; }
+    }
+    if (!(tol > 0.0) || !(tol <= 1.7976931348623157e308)) { snprintf(s_err, sizeof(s_err), "tol is %g, it must be a positive finite number", tol); return -1; }
+    if (max_sweeps < 1) { snprintf(s_err, sizeof(s_err), "max_sweeps is %ld, it must be at least 1", max_sweeps); return -1; }
+    return 0;
+}
+static int fleet_sens_launch(SmallFleet *F, hipStream_t s, SensArgs &a, long nrhs) {
+    int rc = 0;
+    a.nrhs = (int)nrhs; a.N = F->noff.back(); a.M = F->moff.back();
+    a.NQ = (F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES) ? F->qoff.back() : 0; a.NA = (F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES) ? F->aoff.back() : 0;
+    a.group = nrhs > 1 ? F->rhs_group : 1; a.scratch = nullptr;
+    if (a.group > 1) {
+        // the slots of the right-hand sides carried at once: a host allocation, once (the first call with nrhs > 1 may block)
+        if (!F->sens_scratch) {
+            const size_t bytes = (size_t)F->rhs_group * (7 * (size_t)a.N + 5 * (size_t)a.M) * sizeof(double);
+            SHIP(hipMalloc((void **)&F->sens_scratch, bytes));
+            F->sens_scratch_bytes = (long)bytes;
+        }
+        a.scratch = F->sens_scratch;
+    }
+    SHIP(fleet_enter(F, s));
+    hipLaunchKernelGGL(k_small_fleet_sens, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, s, F->dprobs, (int)F->count, F->st, F->kflags, (const int *)F->doffs,
+                       (const int *)F->dmoffs, a);
+    SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, s));
+    F->sens_calls++; F->sens_rhs += nrhs;
+done:
+    return rc;
+}
+static const char *const FLEET_NOT_A_SOLVE = "the most recent state-changing fleet call was not a solve: the resident q, l, u and matrices must be those of the x, y returned";
+int qdev_small_fleet_adjoint_multi_dev(void *h_, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active,
+                                       long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    if (fleet_sens_checks(F, nrhs, dQx || dAx, dQx ? "dQx" : "dAx", tol, max_sweeps, n_len, m_len, q_len, a_len, dQx != nullptr, dAx != nullptr)) return -1;
+    if (!gx) { snprintf(s_err, sizeof(s_err), "gx is NULL"); return -1; }
+    if (!dq) { snprintf(s_err, sizeof(s_err), "dq is NULL"); return -1; }
+    if (!dl) { snprintf(s_err, sizeof(s_err), "dl is NULL"); return -1; }
+    if (!du) { snprintf(s_err, sizeof(s_err), "du is NULL"); return -1; }
+    if (!F->last_was_solve) { snprintf(s_err, sizeof(s_err), "%s", FLEET_NOT_A_SOLVE); return -1; }
+    SHIP(hipSetDevice(F->device));
+    if (fleet_dev_ptr(F, gx, "gx") || fleet_dev_ptr(F, gy, "gy") || fleet_dev_ptr(F, dq, "dq") || fleet_dev_ptr(F, dl, "dl") || fleet_dev_ptr(F, du, "du") ||
+        fleet_dev_ptr(F, dQx, "dQx") || fleet_dev_ptr(F, dAx, "dAx") || fleet_dev_ptr(F, active, "active") || fleet_dev_ptr(F, status, "status") ||
+        fleet_dev_ptr(F, res, "res")) return -1;
+    {
+        SensArgs a;
+        memset(&a, 0, sizeof(a));
+        a.mode = 0; a.in_n = gx; a.in_l = gy; a.out_n = dq; a.out_m1 = dl; a.out_m2 = du; a.out_q = dQx; a.out_a = dAx;
+        a.active = active; a.status = status; a.res = res; a.tol = tol; a.max_sweeps = (int)(max_sweeps > 1000000 ? 1000000 : max_sweeps);
+        rc = fleet_sens_launch(F, (hipStream_t)stream_, a, nrhs);
+    }
+done:
+    return rc;
+}
+int qdev_small_fleet_tangent_dev(void *h_, long nrhs, const double *tq, const double *tl, const double *tu, const double *tQx, const double *tAx, double *dx, double *dy,
+                                 int *active, long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    if (fleet_sens_checks(F, nrhs, tQx || tAx, tQx ? "tQx" : "tAx", tol, max_sweeps, n_len, m_len, q_len, a_len, tQx != nullptr, tAx != nullptr)) return -1;
+    if (!tq && !tl && !tu && !tQx && !tAx) { snprintf(s_err, sizeof(s_err), "no tangent passed: tq, tl, tu, tQx and tAx are all NULL"); return -1; }
+    if (!dx) { snprintf(s_err, sizeof(s_err), "dx is NULL"); return -1; }
+    if (!dy) { snprintf(s_err, sizeof(s_err), "dy is NULL"); return -1; }
+    if (!F->last_was_solve) { snprintf(s_err, sizeof(s_err), "%s", FLEET_NOT_A_SOLVE); return -1; }
+    SHIP(hipSetDevice(F->device));
+    if (fleet_dev_ptr(F, tq, "tq") || fleet_dev_ptr(F, tl, "tl") || fleet_dev_ptr(F, tu, "tu") || fleet_dev_ptr(F, tQx, "tQx") || fleet_dev_ptr(F, tAx, "tAx") ||
+        fleet_dev_ptr(F, dx, "dx") || fleet_dev_ptr(F, dy, "dy") || fleet_dev_ptr(F, active, "active") || fleet_dev_ptr(F, status, "status") ||
+        fleet_dev_ptr(F, res, "res")) return -1;
+    {
+        SensArgs a;
+        memset(&a, 0, sizeof(a));
+        a.mode = 1; a.in_n = tq; a.in_l = tl; a.in_u = tu; a.in_q = tQx; a.in_a = tAx; a.out_n = dx; a.out_m1 = dy;
+        a.active = active; a.status = status; a.res = res; a.tol = tol; a.max_sweeps = (int)(max_sweeps > 1000000 ? 1000000 : max_sweeps);
+        rc = fleet_sens_launch(F, (hipStream_t)stream_, a, nrhs);
+    }
+done:
+    return rc;
+}
+// right-hand sides one workgroup carries at once: FLEET_RHS_GROUP in the PACKED layout, 1 (one after another) in the others
+int qdev_small_fleet_rhs_group(const void *h_) { return ((const SmallFleet *)h_)->rhs_group; }
+void qdev_small_fleet_sens_stats(const void *h_, long *out3) {
+    const SmallFleet *F = (const SmallFleet *)h_;
+    out3[0] = F->sens_calls; out3[1] = F->sens_rhs; out3[2] = F->sens_scratch_bytes;
+}
 int qdev_small_fleet_fetch_last(void *h_, double *const *x, double *const *y, void *info_) {
     int rc = 0;
     SmallFleet *F = (SmallFleet *)h_;

@@ -1278,4 +1278,28 @@ int qpdo_amd_fleet_get_adjoint_stats(const QPDOAmdFleet *f, QPDOAmdFleetAdjointS
     out->adjoint_calls = qdev_small_fleet_adjoint_calls(f); out->resident_extra_bytes = 0;
     return 0;
 }
+int qpdo_amd_fleet_adjoint_multi_dev(QPDOAmdFleet *f, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx,
+                                     int *active, long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_adjoint_multi_dev: NULL fleet");
+    if (qdev_small_fleet_adjoint_multi_dev(f, nrhs, gx, gy, dq, dl, du, dQx, dAx, active, status, res, tol, max_sweeps, n_len, m_len, q_len, a_len, stream))
+        return fleet_dev_failed("qpdo_amd_fleet_adjoint_multi_dev");
+    return 0;
+}
+int qpdo_amd_fleet_tangent_dev(QPDOAmdFleet *f, long nrhs, const double *tq, const double *tl, const double *tu, const double *tQx, const double *tAx, double *dx,
+                               double *dy, int *active, long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len,
+                               void *stream) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_tangent_dev: NULL fleet");
+    if (qdev_small_fleet_tangent_dev(f, nrhs, tq, tl, tu, tQx, tAx, dx, dy, active, status, res, tol, max_sweeps, n_len, m_len, q_len, a_len, stream))
+        return fleet_dev_failed("qpdo_amd_fleet_tangent_dev");
+    return 0;
+}
+int qpdo_amd_fleet_rhs_group(const QPDOAmdFleet *f) { return f ? qdev_small_fleet_rhs_group(f) : -1; }
+int qpdo_amd_fleet_get_sensitivity_stats(const QPDOAmdFleet *f, QPDOAmdFleetSensitivityStats *out) {
+    if (!f) return fleet_refuse("qpdo_amd_fleet_get_sensitivity_stats: NULL fleet");
+    if (!out) return fleet_refuse("qpdo_amd_fleet_get_sensitivity_stats: NULL output");
+    long s[3] = {0, 0, 0};
+    qdev_small_fleet_sens_stats(f, s);
+    out->calls = s[0]; out->rhs_total = s[1]; out->scratch_bytes = s[2];
+    return 0;
+}
 void qpdo_amd_fleet_destroy(QPDOAmdFleet *f) { if (f) qdev_small_fleet_destroy(f); }

@@ -277,6 +277,14 @@ int   qdev_small_fleet_packed_matrix_layout(const void *fleet, long *qoff, long 
 int   qdev_small_fleet_adjoint_dev(void *fleet, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active,
                                    long *adj_status, double *adj_res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream);
 long  qdev_small_fleet_adjoint_calls(const void *fleet);
+/* nrhs right-hand sides per factorization, adjoints or tangents (k_small_fleet_sens): every check but the NULL fleet, then one launch on `stream` */
+int   qdev_small_fleet_adjoint_multi_dev(void *fleet, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx,
+                                         int *active, long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream);
+int   qdev_small_fleet_tangent_dev(void *fleet, long nrhs, const double *tq, const double *tl, const double *tu, const double *tQx, const double *tAx, double *dx,
+                                   double *dy, int *active, long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len,
+                                   void *stream);
+int   qdev_small_fleet_rhs_group(const void *fleet);
+void  qdev_small_fleet_sens_stats(const void *fleet, long *out3);      /* calls, right-hand sides, scratch bytes */
 void  qdev_small_fleet_destroy(void *fleet);
 
 /* ---- ONE small workspace through the fused kernel (the default path of qpdo_solve for problems whose whole state fits one

@@ -1985,6 +1985,455 @@ __global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet_adjoint(SmallQP *
     }
 }
 
+// ---- MANY right-hand sides per factorization: adjoints and TANGENTS of a fleet's last solve (qpdo_amd_fleet_adjoint_multi_dev,
+// qpdo_amd_fleet_tangent_dev, include/qpdo_amd_ext.h) ----------------------------------------------------------------------
+// The launch shape, the system, sigma, W, the sweeps and the acceptance rule are k_small_fleet_adjoint's.  What depends on the solve alone
+// is done ONCE per workgroup: the status gate, the classification, W and sigma, small_assemble, the layout's factorization and the pivot
+// check.  Then the right-hand sides follow one after another in the same work vectors; right-hand side r of an array whose per-RHS length is
+// L starts at r * L.  Every right-hand side's operations are the adjoint kernel's in its order (the maxima that the adjoint kernel takes
+// in one reduction with the diagonal of Qs are taken in a reduction of their own here: a maximum does not depend on the order), so slab r
+// of an adjoint launch carries the bits of the single launch with slab r.
+// mode 0 (adjoint): the right-hand side is (gx, gy_S) as passed; out: dq, dl, du, dQx, dAx.
+// mode 1 (tangent): it is formed in fp64 from the x, y the solve returned and the caller's perturbations, one thread per row, ascending
+// stored order:  rx_j = -((tq_j + sum_k tQ[k] x_c(k)) + sum_k tA[k] y_i(k))  (row j of the full Q image, then column j of the caller's CSC
+// A, flagged rows only),  ry_i = tb_i - sum_k tA[k] x_j(k)  (row i of CSR(A); tb = tu on +1 rows, tl on -1 rows);  out: dx = D vxs,
+// dy = E vys / c on S and +0.0 off it.
+// codes as the adjoint's; 2 and 3 are the item's and repeat for every right-hand side; 1 is one right-hand side's own.
+// TWO COPIES: the prologue, the sweep loop and the dQ / dA epilogue below repeat k_small_fleet_adjoint's statements; a __device__ function
+// shared by both kernels was NOT tried.  k_small_fleet_adjoint has to keep its device code, and moving statements of these kernels
+// behind inline functions changed their streams in three attempts out of four when the LDS plan was unified (docs/LAB_NOTES.md), so
+// the old kernel is left alone.  What holds the copies together is the bit comparison of every output slab with the single call in
+// tests/test_gpu_fleet_sensitivity.py (both paths below, all layouts); a change to the sweep in one kernel belongs in the other too.
+// one wave's triangular solves for ONE right-hand side of a group (the dispatch of small_ldl_solve, out of line: four instances of the wave
+// solve inlined into the kernel a second time cost it 1244 vector-register spills)
+__device__ __attribute__((noinline)) void small_ldl_solve_slot(int n, const lds_f64 *Kl, const double *b, double *xout) {
+    if (n <= 64) small_ldl_solve_wave<1, 4>(n, Kl, b, xout);
+    else if (n <= 128) small_ldl_solve_wave<2, 4>(n, Kl, b, xout);
+    else if (n <= 192) small_ldl_solve_wave<3, 2>(n, Kl, b, xout);
+    else small_ldl_solve_wave<4, 2>(n, Kl, b, xout);
+}
+struct SensArgs {
+    int mode, nrhs;
+    long N, M, NQ, NA;                                                     // per-RHS lengths of the packed arrays
+    const double *in_n, *in_l, *in_u, *in_q, *in_a;                        // adjoint: gx, gy, -, -, -;  tangent: tq, tl, tu, tQx, tAx
+    double *out_n, *out_m1, *out_m2, *out_q, *out_a;                       // adjoint: dq, dl, du, dQx, dAx;  tangent: dx, dy, -, -, -
+    int *active; long *status; double *res;
+    double tol; int max_sweeps;
+    int group; double *scratch;                                            // right-hand sides carried at once (1: one after another) and their slots: group * (7 N + 5 M) doubles
+};
+__device__ void small_sens_refuse(const SensArgs &a, int r, int code, int sweeps, int k, int count, int n, int m, int nq, int na, int no, int mo, int qo, int ao) {
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double *on = a.out_n + (size_t)r * a.N + no, *o1 = a.out_m1 + (size_t)r * a.M + mo;
+    FOR_T(j, n) on[j] = nan;
+    FOR_T(i, m) o1[i] = nan;
+    if (a.out_m2) { double *o2 = a.out_m2 + (size_t)r * a.M + mo; FOR_T(i, m) o2[i] = nan; }
+    if (a.out_q) { double *oq = a.out_q + (size_t)r * a.NQ + qo; FOR_T(e, nq) oq[e] = nan; }
+    if (a.out_a) { double *oa = a.out_a + (size_t)r * a.NA + ao; FOR_T(e, na) oa[e] = nan; }
+    if (threadIdx.x == 0) {
+        const size_t slot = (size_t)r * count + blockIdx.x;
+        if (a.status) { long *s = a.status + 3 * slot; s[0] = code; s[1] = sweeps; s[2] = k; }
+        if (a.res) a.res[slot] = nan;
+    }
+}
+__global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet_sens(SmallQP *probs, int count, QPDOSettings st, int kflags, const int *offs, const int *moffs, SensArgs a) {
+    const int klay = kflags & 3, klds_ok = klay == K_PACKED, kband = klay == K_BAND;
+    __shared__ double sm[32];
+    extern __shared__ __attribute__((aligned(16))) double dyn[];
+    if ((int)blockIdx.x >= count) return;
+    const int b = blockIdx.x;
+    SmallQP &Pg = probs[b];
+    SmallQP P;
+    const SmallRes *Rg = small_item_load<1, 1>(Pg, P);
+    P.prof = nullptr;
+    const int n = P.n, m = P.m;
+    const bool tang = a.mode != 0;
+    const int nrhs = a.nrhs, max_sweeps = a.max_sweeps;
+    const double tol = a.tol;
+    // the item's slices of the caller's packed arrays
+    const int no = __builtin_amdgcn_readfirstlane(offs[b]), mo = __builtin_amdgcn_readfirstlane(offs[count + 1 + b]);
+    const bool wantQ = !tang && a.out_q != nullptr, wantA = !tang && a.out_a != nullptr;
+    int qo = 0, nq = 0, ao = 0, na = 0;
+    if (a.out_q || a.out_a || a.in_q || a.in_a) {
+        qo = __builtin_amdgcn_readfirstlane(moffs[b]); nq = __builtin_amdgcn_readfirstlane(moffs[b + 1]) - qo;
+        ao = __builtin_amdgcn_readfirstlane(moffs[count + 1 + b]); na = __builtin_amdgcn_readfirstlane(moffs[count + 2 + b]) - ao;
+    }
+    int *active = a.active ? a.active + mo : nullptr;
+    const long fs = Rg->fleet_status;
+    if (__builtin_amdgcn_readfirstlane((int)(fs != QPDO_SOLVED))) {
+        if (active) { FOR_T(i, m) active[i] = 0; }
+        for (int r = 0; r < nrhs; r++) small_sens_refuse(a, r, 2, 0, 0, count, n, m, nq, na, no, mo, qo, ao);
+        return;
+    }
+    // the work vectors where the solve has them, named as in k_small_fleet_adjoint
+    small_item_vectors(P, dyn, (unsigned)__builtin_amdgcn_readfirstlane((int)Rg->lds_vec_off));
+    enum { AN_X = 0, AN_VX, AN_RX, AN_DVX, AN_RHS, AN_T1, AN_T2, AN_GX, AN_D, AN_DINV, AN_COUNT };
+    enum { AM_VY = 0, AM_RY, AM_WRY, AM_W, AM_AV, AM_GY, AM_E, AM_EINV, AM_COUNT };
+    static_assert(AN_COUNT <= NV_COUNT && AM_COUNT <= MV_COUNT, "the sensitivities live in the solve's work-vector area");
+    double *xsc = P.nv + (size_t)AN_X * n, *vx = P.nv + (size_t)AN_VX * n, *rx = P.nv + (size_t)AN_RX * n, *dvx = P.nv + (size_t)AN_DVX * n,
+           *rhs = P.nv + (size_t)AN_RHS * n, *t1 = P.nv + (size_t)AN_T1 * n, *t2 = P.nv + (size_t)AN_T2 * n, *gxs = P.nv + (size_t)AN_GX * n,
+           *D = P.nv + (size_t)AN_D * n, *Dinv = P.nv + (size_t)AN_DINV * n;
+    double *vy = P.mv + (size_t)AM_VY * m, *ry = P.mv + (size_t)AM_RY * m, *wry = P.mv + (size_t)AM_WRY * m, *W = P.mv + (size_t)AM_W * m,
+           *Av = P.mv + (size_t)AM_AV * m, *gys = P.mv + (size_t)AM_GY * m, *E = P.mv + (size_t)AM_E * m, *Einv = P.mv + (size_t)AM_EINV * m;
+    int *flag = P.iv;
+    SMALL_LDS_CARVE(dyn, n, m, small_lds_colbuf_sets(1, 1, klay));
+    const int bw = P.bw;
+    SMALL_KVIEW(kv, n, bw, klds_ok, kband, Klds, P.K);
+    const int scaled = st.scaling > 0;
+    const double sc_c = scaled ? Rg->r_c : 1.0, sc_cinv = scaled ? Rg->r_cinv : 1.0;
+    const double *rD = uni_ptr(Rg->rD), *rDinv = uni_ptr(Rg->rDinv), *rE = uni_ptr(Rg->rE), *rEinv = uni_ptr(Rg->rEinv);
+    const int *mapA = uni_ptr(Rg->mapA), *mapQ = uni_ptr(Rg->mapQ);
+    const double *xu = P.sol_x, *yu = P.sol_y;
+
+    // ---- ONCE: the scaled x, the largest diagonal entry of Qs, the active set, W and sigma, K and its LDL', the pivot check
+    FOR_T(r, m + 1) rp_s[r] = P.Arp[r];
+    double mqd = 0.0;
+    FOR_T(j, n) {
+        const double d = scaled ? rD[j] : 1.0, di = scaled ? rDinv[j] : 1.0;
+        D[j] = d; Dinv[j] = di;
+        xsc[j] = scaled ? P.sol_x[j] * di : P.sol_x[j];
+        for (int k = P.Qrp[j]; k < P.Qrp[j + 1]; k++) if (P.Qci[k] == j) { const double q = s_abs(P.Qval[k]); mqd = q > mqd ? q : mqd; }
+    }
+    FOR_T(i, m) { const double e = scaled ? rE[i] : 1.0; E[i] = e; Einv[i] = scaled ? rEinv[i] : 1.0; }
+    SYNC;
+    spmv_rows(m, P.Arp, P.Aci, P.Aval, xsc, Av);
+    int cnt = 0;
+    FOR_T(i, m) {                                     // (entry i of the product was written by this very thread)
+        const double e = E[i], yi = P.sol_y[i];
+        const double t = Av[i] + (scaled ? e * yi : yi);
+        const double lo = P.l[i], up = P.u[i];
+        int f = 0;
+        if (up < e * SM_INFTY && t >= up) f = 1;
+        else if (lo > -e * SM_INFTY && t <= lo) f = -1;
+        flag[i] = f; cnt += (f != 0);
+        if (active) active[i] = f;
+        double a2 = 0.0;
+        for (int k = rp_s[i]; k < rp_s[i + 1]; k++) { const double v = P.Aval[k]; a2 += v * v; }
+        W[i] = a2;                                     // (the row's squared norm until s is known)
+    }
+    mqd = blk_max(mqd, sm);
+    const int kact = blk_sum_int(cnt, (int *)sm);
+    SYNC;
+    const double s = mqd > 0.0 ? mqd : 1.0, sigma = ADJ_SIGMA_REL * s;
+    FOR_T(i, m) { const double a2 = W[i]; W[i] = (flag[i] && a2 > 0.0) ? (ADJ_ROW_WEIGHT * s) / a2 : 0.0; }
+    SYNC;
+    small_assemble(P, kv, W, sigma, rp_s, d_s);
+    if (klds_ok) small_factor4_la<1>(n, Klds, dyn);
+    else if (kband) small_factor_band(n, bw, Klds, dyn);
+    else small_factor4_t<false>(n, P.K, dyn);
+    {
+        int bad = 0;
+        FOR_T(j, n) { const double dj = kv.at(j, j); bad |= !(dj > 0.0 && dj <= 1.7976931348623157e308); }
+        if (__syncthreads_or(bad)) {
+            if (active) { FOR_T(i, m) active[i] = 0; }
+            for (int r = 0; r < nrhs; r++) small_sens_refuse(a, r, 3, 0, kact, count, n, m, nq, na, no, mo, qo, ao);
+            return;
+        }
+    }
+    // ---- the right-hand sides G AT ONCE (PACKED layout, n <= 256, more than one right-hand side; a.group > 1 only with a.scratch)
+    // Slot g of a group keeps its 7 n-vectors and 5 m-vectors in the item's global scratch.  The products and element loops run over
+    // (slot, row) pairs -- a pair is always the same thread's, so "own entries" holds as above --, wave w runs small_ldl_solve_wave for
+    // slot w, and a slot leaves the sweeps at its own sweep count (`live`): every right-hand side receives exactly the operations the loop
+    // below gives it, in its order.  Its maxima are taken with LDS atomics on the bit patterns (non-negative doubles order as their
+    // bits; a value that is not finite raises the slot's mark instead, and a marked slot is never accepted, so the maxima matter only
+    // where all values are finite).
+    if (a.group > 1 && nrhs > 1 && klds_ok && n <= 256) {
+        __shared__ u64 gm1[8], gm2[8];
+        __shared__ double gnf[8], gnon[8], gng[8];
+        enum { SV_VX = 0, SV_RX, SV_DVX, SV_RHS, SV_T1, SV_GX, SV_NCOUNT, SM_VY = 0, SM_RY, SM_WRY, SM_AV, SM_GY, SM_MCOUNT };
+        static_assert(SV_NCOUNT <= 7 && SM_MCOUNT <= 5, "the host sizes a slot at 7 n-vectors and 5 m-vectors");
+        const lds_f64 *Kl = (const lds_f64 *)kv.K;
+        const int G = a.group, per = 7 * n + 5 * m, tid = threadIdx.x, wave = threadIdx.x >> 6;
+        double *sc = a.scratch + (size_t)G * (7 * (size_t)no + 5 * (size_t)mo);
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#define SLOT_N(g, k) (sc + (size_t)(g) * per + (size_t)(k) * n)
+#define SLOT_M(g, k) (sc + (size_t)(g) * per + 7 * (size_t)n + (size_t)(k) * m)
+#define SENS_MAX(acc, mark, v) do { const double v_ = (v); if (!(v_ <= 1.7976931348623157e308)) (mark) = 1.0; \
+        else { const u64 b_ = (u64)__double_as_longlong(v_); if (b_ > *(volatile u64 *)&(acc)) atomicMax(&(acc), b_); } } while (0)
+#pragma nounroll
+        for (int r0 = 0; r0 < nrhs; r0 += G) {
+            const int Gc = nrhs - r0 < G ? nrhs - r0 : G;
+            SYNC;                                     // (the previous group's last readers are through)
+            if (tid < 8) { gm1[tid] = 0; gm2[tid] = 0; gnon[tid] = 0.0; }
+            SYNC;
+            for (int idx = tid; idx < Gc * n; idx += blockDim.x) {
+                const int g = idx / n, j = idx - g * n;
+                const size_t r = (size_t)(r0 + g);
+                double gv;
+                if (!tang) gv = a.in_n[r * a.N + no + j];
+                else {
+                    double acc = a.in_n ? a.in_n[r * a.N + no + j] : 0.0;
+                    if (a.in_q) { const double *tQ = a.in_q + r * a.NQ + qo; for (int k = P.Qrp[j]; k < P.Qrp[j + 1]; k++) acc += tQ[mapQ ? mapQ[k] : k] * xu[P.Qci[k]]; }
+                    if (a.in_a) { const double *tA = a.in_a + r * a.NA + ao; for (int k = P.Trp[j]; k < P.Trp[j + 1]; k++) { const int i = P.Tci[k]; if (flag[i]) acc += tA[k] * yu[i]; } }
+                    gv = -acc;
+                }
+                SLOT_N(g, SV_GX)[j] = scaled ? sc_c * (D[j] * gv) : gv;
+                SLOT_N(g, SV_VX)[j] = 0.0;
+                SENS_MAX(gm1[g], gnon[g], s_abs(gv));
+            }
+            for (int idx = tid; idx < Gc * m; idx += blockDim.x) {
+                const int g = idx / m, i = idx - g * m, f = flag[i];
+                const size_t r = (size_t)(r0 + g);
+                double gv = 0.0;
+                if (f && (tang || a.in_l)) {
+                    if (!tang) gv = a.in_l[r * a.M + mo + i];
+                    else {
+                        const double *tb = f > 0 ? a.in_u : a.in_l;
+                        double acc = 0.0;
+                        if (a.in_a) { const double *tA = a.in_a + r * a.NA + ao; for (int k = rp_s[i]; k < rp_s[i + 1]; k++) acc += tA[mapA[k]] * xu[P.Aci[k]]; }
+                        gv = (tb ? tb[r * a.M + mo + i] : 0.0) - acc;
+                    }
+                    SENS_MAX(gm2[g], gnon[g], s_abs(gv));
+                }
+                SLOT_M(g, SM_GY)[i] = scaled ? E[i] * gv : gv;
+                SLOT_M(g, SM_VY)[i] = 0.0;
+            }
+            SYNC;
+            if (tid < 8) gng[tid] = s_max(__longlong_as_double((long long)gm1[tid]), __longlong_as_double((long long)gm2[tid]));
+            unsigned live = (1u << Gc) - 1u, okmask = 0u;
+            for (int sweep = 0;; sweep++) {
+                if (tid < 8) { gm1[tid] = 0; gm2[tid] = 0; gnf[tid] = gnon[tid]; }
+                SYNC;
+                for (int idx = tid; idx < Gc * n; idx += blockDim.x) {
+                    const int g = idx / n, j = idx - g * n;
+                    if (!((live >> g) & 1u)) continue;
+                    const double *vx = SLOT_N(g, SV_VX), *vy = SLOT_M(g, SM_VY);
+                    double s1 = 0.0, s2 = 0.0;
+                    for (int k = P.Qrp[j]; k < P.Qrp[j + 1]; k++) s1 += P.Qval[k] * vx[P.Qci[k]];
+                    for (int k = P.Trp[j]; k < P.Trp[j + 1]; k++) s2 += P.Tval[k] * vy[P.Tci[k]];
+                    const double rr = (SLOT_N(g, SV_GX)[j] - s1) - s2;
+                    SLOT_N(g, SV_RX)[j] = rr;
+                    SENS_MAX(gm1[g], gnf[g], s_abs(rr * Dinv[j]));
+                }
+                for (int idx = tid; idx < Gc * m; idx += blockDim.x) {
+                    const int g = idx / m, i = idx - g * m;
+                    if (!((live >> g) & 1u)) continue;
+                    const double *vx = SLOT_N(g, SV_VX);
+                    double s1 = 0.0;
+                    for (int k = rp_s[i]; k < rp_s[i + 1]; k++) s1 += P.Aval[k] * vx[P.Aci[k]];
+                    const double rr = flag[i] ? SLOT_M(g, SM_GY)[i] - s1 : 0.0;
+                    SLOT_M(g, SM_RY)[i] = rr; SLOT_M(g, SM_WRY)[i] = W[i] * rr;
+                    SENS_MAX(gm2[g], gnf[g], s_abs(rr * Einv[i]));
+                }
+                SYNC;
+                for (int g = 0; g < Gc; g++) {
+                    if (!((live >> g) & 1u)) continue;
+                    const double m1 = __longlong_as_double((long long)gm1[g]), m2 = __longlong_as_double((long long)gm2[g]), gn = gng[g];
+                    const double rn = s_max(m1 * sc_cinv, m2);
+                    const double rel = gn > 0.0 ? rn / gn : rn;
+                    const bool acc = gnf[g] == 0.0 && rn <= tol * gn;
+                    if (!acc && sweep < max_sweeps) continue;
+                    live &= ~(1u << g);
+                    if (acc) okmask |= 1u << g;
+                    if (tid == 0) {
+                        const size_t slot = (size_t)(r0 + g) * count + b;
+                        if (a.status) { long *sp = a.status + 3 * slot; sp[0] = acc ? 0 : 1; sp[1] = sweep; sp[2] = kact; }
+                        if (a.res) a.res[slot] = acc ? rel : nan;
+                    }
+                }
+                SYNC;                                 // (the accumulators are zeroed again at the top)
+                if (!live) break;
+                for (int idx = tid; idx < Gc * n; idx += blockDim.x) {
+                    const int g = idx / n, j = idx - g * n;
+                    if (!((live >> g) & 1u)) continue;
+                    const double *wry = SLOT_M(g, SM_WRY);
+                    double s1 = 0.0;
+                    for (int k = P.Trp[j]; k < P.Trp[j + 1]; k++) s1 += P.Tval[k] * wry[P.Tci[k]];
+                    SLOT_N(g, SV_RHS)[j] = SLOT_N(g, SV_RX)[j] + s1;
+                }
+                SYNC;
+                if (wave < Gc && ((live >> wave) & 1u)) {
+                    const double *bb = SLOT_N(wave, SV_RHS); double *xo = SLOT_N(wave, SV_DVX);
+                    small_ldl_solve_slot(n, Kl, bb, xo);
+                }
+                SYNC;
+                for (int idx = tid; idx < Gc * m; idx += blockDim.x) {
+                    const int g = idx / m, i = idx - g * m;
+                    if (!((live >> g) & 1u)) continue;
+                    const double *dvx = SLOT_N(g, SV_DVX);
+                    double s1 = 0.0;
+                    for (int k = rp_s[i]; k < rp_s[i + 1]; k++) s1 += P.Aval[k] * dvx[P.Aci[k]];
+                    double *vy = SLOT_M(g, SM_VY);
+                    vy[i] = vy[i] + W[i] * (s1 - SLOT_M(g, SM_RY)[i]);
+                }
+                for (int idx = tid; idx < Gc * n; idx += blockDim.x) {
+                    const int g = idx / n, j = idx - g * n;
+                    if (!((live >> g) & 1u)) continue;
+                    double *vx = SLOT_N(g, SV_VX);
+                    vx[j] = vx[j] + SLOT_N(g, SV_DVX)[j];
+                }
+                SYNC;
+            }
+            // ---- back to the caller's space, slot by slot; a slot that was not accepted delivers NaN
+            for (int idx = tid; idx < Gc * n; idx += blockDim.x) {
+                const int g = idx / n, j = idx - g * n;
+                double *on = a.out_n + (size_t)(r0 + g) * a.N + no;
+                if (!((okmask >> g) & 1u)) { on[j] = nan; continue; }
+                const double vxj = SLOT_N(g, SV_VX)[j];
+                const double v = scaled ? D[j] * vxj : vxj;
+                SLOT_N(g, SV_T1)[j] = v; on[j] = tang ? v : -v;
+            }
+            for (int idx = tid; idx < Gc * m; idx += blockDim.x) {
+                const int g = idx / m, i = idx - g * m, f = flag[i];
+                double *o1 = a.out_m1 + (size_t)(r0 + g) * a.M + mo, *o2 = a.out_m2 ? a.out_m2 + (size_t)(r0 + g) * a.M + mo : nullptr;
+                if (!((okmask >> g) & 1u)) { o1[i] = nan; if (o2) o2[i] = nan; continue; }
+                double v = 0.0;
+                if (f) { v = SLOT_M(g, SM_VY)[i]; if (scaled) { v = E[i] * v; v = v * sc_cinv; } }
+                SLOT_M(g, SM_AV)[i] = v;
+                if (tang) o1[i] = v;
+                else { o2[i] = f > 0 ? v : 0.0; o1[i] = f < 0 ? v : 0.0; }
+            }
+            if (!wantQ && !wantA) continue;
+            SYNC;
+            for (int g = 0; g < Gc; g++) {
+                const bool ok = (okmask >> g) & 1u;
+                const double *vxu = SLOT_N(g, SV_T1), *vyu = SLOT_M(g, SM_AV);
+                if (wantA) {
+                    double *dA = a.out_a + (size_t)(r0 + g) * a.NA + ao;
+                    if (!ok) { FOR_T(e, na) dA[e] = nan; }
+                    else FOR_T(i, m) {
+                        const int f = flag[i];
+                        const double yi = yu[i], vyi = vyu[i];
+                        for (int k = rp_s[i]; k < rp_s[i + 1]; k++) { const int j = P.Aci[k]; dA[mapA[k]] = f ? -(yi * vxu[j] + vyi * xu[j]) : 0.0; }
+                    }
+                }
+                if (wantQ) {
+                    double *dQ = a.out_q + (size_t)(r0 + g) * a.NQ + qo;
+                    if (!ok) { FOR_T(e, nq) dQ[e] = nan; continue; }
+                    if (mapQ) { FOR_T(e, nq) dQ[e] = 0.0; SYNC; }
+                    FOR_T(rr, n) for (int k = P.Qrp[rr]; k < P.Qrp[rr + 1]; k++) {
+                        const int cc = P.Qci[k];
+                        if (!mapQ) dQ[k] = -(vxu[cc] * xu[rr]);
+                        else if (rr == cc) dQ[mapQ[k]] = -(vxu[rr] * xu[rr]);
+                        else if (rr > cc) dQ[mapQ[k]] = -(vxu[rr] * xu[cc] + vxu[cc] * xu[rr]);
+                    }
+                }
+            }
+        }
+#undef SLOT_N
+#undef SLOT_M
+#undef SENS_MAX
+        return;
+    }
+    // ---- the right-hand sides, one after another
+#pragma nounroll
+    for (int r = 0; r < nrhs; r++) {
+        const double *in_n = a.in_n ? a.in_n + (size_t)r * a.N + no : nullptr, *in_l = a.in_l ? a.in_l + (size_t)r * a.M + mo : nullptr,
+                     *in_u = a.in_u ? a.in_u + (size_t)r * a.M + mo : nullptr, *in_q = a.in_q ? a.in_q + (size_t)r * a.NQ + qo : nullptr,
+                     *in_a = a.in_a ? a.in_a + (size_t)r * a.NA + ao : nullptr;
+        double *on = a.out_n + (size_t)r * a.N + no, *o1 = a.out_m1 + (size_t)r * a.M + mo, *o2 = a.out_m2 ? a.out_m2 + (size_t)r * a.M + mo : nullptr;
+        SYNC;                                         // (the previous right-hand side's last readers of the work vectors are through)
+        double mgx = 0.0, mgy = 0.0, nonfin = 0.0, z0 = 0.0;
+        FOR_T(j, n) {
+            double g;
+            if (!tang) g = in_n[j];
+            else {
+                double acc = in_n ? in_n[j] : 0.0;
+                if (in_q) for (int k = P.Qrp[j]; k < P.Qrp[j + 1]; k++) acc += in_q[mapQ ? mapQ[k] : k] * xu[P.Qci[k]];
+                if (in_a) for (int k = P.Trp[j]; k < P.Trp[j + 1]; k++) { const int i = P.Tci[k]; if (flag[i]) acc += in_a[k] * yu[i]; }
+                g = -acc;
+            }
+            gxs[j] = scaled ? sc_c * (D[j] * g) : g;
+            vx[j] = 0.0;
+            const double ag = s_abs(g);
+            mgx = ag > mgx ? ag : mgx;
+            if (!(ag <= 1.7976931348623157e308)) nonfin = 1.0;
+        }
+        FOR_T(i, m) {
+            const int f = flag[i];
+            double g = 0.0;
+            if (f && (tang || in_l)) {
+                if (!tang) g = in_l[i];
+                else {
+                    const double *tb = f > 0 ? in_u : in_l;
+                    double acc = 0.0;
+                    if (in_a) for (int k = rp_s[i]; k < rp_s[i + 1]; k++) acc += in_a[mapA[k]] * xu[P.Aci[k]];
+                    g = (tb ? tb[i] : 0.0) - acc;
+                }
+                const double ag = s_abs(g);
+                mgy = ag > mgy ? ag : mgy;
+                if (!(ag <= 1.7976931348623157e308)) nonfin = 1.0;
+            }
+            gys[i] = scaled ? E[i] * g : g;
+            vy[i] = 0.0;
+        }
+        blk_max4(mgx, mgy, nonfin, z0, sm);
+        const double gnorm = s_max(mgx, mgy);
+        // ---- sweeps (k_small_fleet_adjoint's, operation for operation)
+        int sweep = 0; double rel = 0.0; bool accepted = false;
+        for (;; sweep++) {
+            spmv_rows(n, P.Qrp, P.Qci, P.Qval, vx, t1);
+            spmv_rows(m, P.Arp, P.Aci, P.Aval, vx, Av);
+            spmv_rows(n, P.Trp, P.Tci, P.Tval, vy, t2);
+            double m1 = 0.0, m2 = 0.0, nf = nonfin, z = 0.0;
+            FOR_T(j, n) {                             // (own entries of the products)
+                const double rr = (gxs[j] - t1[j]) - t2[j];
+                rx[j] = rr;
+                const double ar = s_abs(rr * Dinv[j]);
+                m1 = ar > m1 ? ar : m1;
+                if (!(ar <= 1.7976931348623157e308)) nf = 1.0;
+            }
+            FOR_T(i, m) {
+                const double rr = flag[i] ? gys[i] - Av[i] : 0.0;
+                ry[i] = rr; wry[i] = W[i] * rr;
+                const double ar = s_abs(rr * Einv[i]);
+                m2 = ar > m2 ? ar : m2;
+                if (!(ar <= 1.7976931348623157e308)) nf = 1.0;
+            }
+            blk_max4(m1, m2, nf, z, sm);
+            const double rn = s_max(m1 * sc_cinv, m2);
+            rel = gnorm > 0.0 ? rn / gnorm : rn;
+            if (nf == 0.0 && rn <= tol * gnorm) { accepted = true; break; }
+            if (sweep >= max_sweeps) break;
+            spmv_rows(n, P.Trp, P.Tci, P.Tval, wry, t2);
+            FOR_T(j, n) rhs[j] = rx[j] + t2[j];
+            SYNC;
+            if (kband) small_ldl_solve_band(n, bw, Klds, rhs, dvx, xs); else small_ldl_solve(P, kv, rhs, dvx, xs);
+            spmv_rows(m, P.Arp, P.Aci, P.Aval, dvx, Av);
+            FOR_T(i, m) vy[i] = vy[i] + W[i] * (Av[i] - ry[i]);
+            FOR_T(j, n) vx[j] = vx[j] + dvx[j];
+            SYNC;
+        }
+        if (!accepted) { small_sens_refuse(a, r, 1, sweep, kact, count, n, m, nq, na, no, mo, qo, ao); continue; }
+        // ---- back to the caller's space: vx = D vxs, vy = E vys / c
+        FOR_T(j, n) { const double v = scaled ? D[j] * vx[j] : vx[j]; t1[j] = v; on[j] = tang ? v : -v; }
+        FOR_T(i, m) {
+            const int f = flag[i];
+            double v = 0.0;
+            if (f) { v = vy[i]; if (scaled) { v = E[i] * v; v = v * sc_cinv; } }
+            Av[i] = v;
+            if (tang) o1[i] = v;
+            else { o2[i] = f > 0 ? v : 0.0; o1[i] = f < 0 ? v : 0.0; }
+        }
+        if (threadIdx.x == 0) {
+            const size_t slot = (size_t)r * count + b;
+            if (a.status) { long *sp = a.status + 3 * slot; sp[0] = 0; sp[1] = sweep; sp[2] = kact; }
+            if (a.res) a.res[slot] = rel;
+        }
+        if (!wantQ && !wantA) continue;
+        SYNC;
+        // ---- dL/dA and dL/dQ per stored entry (k_small_fleet_adjoint's)
+        const double *vxu = t1, *vyu = Av;
+        if (wantA) {
+            double *dA = a.out_a + (size_t)r * a.NA + ao;
+            FOR_T(i, m) {
+                const int f = flag[i];
+                const double yi = yu[i], vyi = vyu[i];
+                for (int k = rp_s[i]; k < rp_s[i + 1]; k++) { const int j = P.Aci[k]; dA[mapA[k]] = f ? -(yi * vxu[j] + vyi * xu[j]) : 0.0; }
+            }
+        }
+        if (wantQ) {
+            double *dQ = a.out_q + (size_t)r * a.NQ + qo;
+            if (mapQ) { FOR_T(e, nq) dQ[e] = 0.0; SYNC; }
+            FOR_T(rr, n) for (int k = P.Qrp[rr]; k < P.Qrp[rr + 1]; k++) {
+                const int cc = P.Qci[k];
+                if (!mapQ) dQ[k] = -(vxu[cc] * xu[rr]);
+                else if (rr == cc) dQ[mapQ[k]] = -(vxu[rr] * xu[rr]);
+                else if (rr > cc) dQ[mapQ[k]] = -(vxu[rr] * xu[cc] + vxu[cc] * xu[rr]);
+            }
+        }
+    }
+}
+
 // ================================================================================================
 // host side: pack a batch into one arena, one upload, one launch, one download
 // ================================================================================================

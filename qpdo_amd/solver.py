@@ -122,7 +122,8 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_warm_start_dev", "qpdo_amd_fleet_warm_start_last_dev", "qpdo_amd_fleet_solve_dev", "qpdo_amd_fleet_fetch_last",
                "qpdo_amd_fleet_sync", "qpdo_amd_slab_trip_shape",
                "qpdo_amd_fleet_packed_matrix_layout", "qpdo_amd_fleet_get_packed_matrix_layout", "qpdo_amd_fleet_update_matrices_dev",
-               "qpdo_amd_fleet_adjoint_dev", "qpdo_amd_fleet_get_adjoint_stats"]
+               "qpdo_amd_fleet_adjoint_dev", "qpdo_amd_fleet_get_adjoint_stats",
+               "qpdo_amd_fleet_adjoint_multi_dev", "qpdo_amd_fleet_tangent_dev", "qpdo_amd_fleet_rhs_group", "qpdo_amd_fleet_get_sensitivity_stats"]
 
 
 class FleetStats(C.Structure):
@@ -146,6 +147,11 @@ class FleetDevStats(C.Structure):
 class FleetAdjointStats(C.Structure):
     """QPDOAmdFleetAdjointStats (include/qpdo_amd_ext.h)"""
     _fields_ = [("adjoint_calls", C.c_long), ("resident_extra_bytes", C.c_long)]
+
+
+class FleetSensitivityStats(C.Structure):
+    """QPDOAmdFleetSensitivityStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("calls", C.c_long), ("rhs_total", C.c_long), ("scratch_bytes", C.c_long)]
 
 
 FLEET_TABLE_BYTES = 16     # QPDO_AMD_FLEET_TABLE_BYTES
@@ -244,6 +250,12 @@ def lib():
             if hasattr(L, "qpdo_amd_fleet_adjoint_dev"):            # (the adjoint of the last solve; absent from an older build)
                 L.qpdo_amd_fleet_adjoint_dev.argtypes = [C.c_void_p] + [vp] * 10 + [C.c_double, C.c_long] + [C.c_long] * 4 + [vp]
                 L.qpdo_amd_fleet_get_adjoint_stats.argtypes = [C.c_void_p, C.POINTER(FleetAdjointStats)]
+            if hasattr(L, "qpdo_amd_fleet_tangent_dev"):            # (many right-hand sides per factorization; absent from an older build)
+                L.qpdo_amd_fleet_adjoint_multi_dev.argtypes = [C.c_void_p, C.c_long] + [vp] * 10 + [C.c_double, C.c_long] + [C.c_long] * 4 + [vp]
+                L.qpdo_amd_fleet_tangent_dev.argtypes = [C.c_void_p, C.c_long] + [vp] * 10 + [C.c_double, C.c_long] + [C.c_long] * 4 + [vp]
+                L.qpdo_amd_fleet_rhs_group.argtypes = [C.c_void_p]
+                L.qpdo_amd_fleet_rhs_group.restype = C.c_int
+                L.qpdo_amd_fleet_get_sensitivity_stats.argtypes = [C.c_void_p, C.POINTER(FleetSensitivityStats)]
         if hasattr(L, "qpdo_amd_slab_trip_shape"):          # (absent from an older build, as below)
             L.qpdo_amd_slab_trip_shape.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
             L.qpdo_amd_slab_trip_shape.restype = C.c_int
@@ -1211,6 +1223,104 @@ class Fleet:
         s = FleetAdjointStats()
         self._call(lib().qpdo_amd_fleet_get_adjoint_stats(self._h, C.byref(s)), "adjoint_stats")
         return {f: getattr(s, f) for f, _ in FleetAdjointStats._fields_}
+
+    # ---- many right-hand sides per factorization (qpdo_amd_fleet_adjoint_multi_dev, qpdo_amd_fleet_tangent_dev) --------------------------
+    def _sens_out(self, spec, out, needed, cache):
+        """the output tensors of a sensitivity call: `out` (a dict with any of spec's keys), or ONE set per call kind (`cache`), kept for the
+        most recent shapes only and reused while they stay the same -- a caller who changes R gets new tensors and the old set is dropped"""
+        import torch
+        if out is None:
+            store = getattr(self, "_sens_cache", None)
+            if store is None:
+                store = self._sens_cache = {}
+            key = tuple((k, shape) for k, _, shape in spec)
+            if store.get(cache, (None, None))[0] != key:
+                dev = torch.device("cuda", self._device)
+                store[cache] = (key, {k: (None if shape is None else torch.empty(shape, dtype=getattr(torch, dt), device=dev)) for k, dt, shape in spec})
+            return dict(store[cache][1])
+        unknown = set(out) - {k for k, _, _ in spec}
+        if unknown:
+            raise ValueError("out: unknown keys %r" % sorted(unknown))
+        out = {k: (None if shape is None else out.get(k)) for k, _, shape in spec}
+        for k in needed:
+            if out[k] is None:
+                raise ValueError("out: '%s' is needed" % k)
+        return out
+
+    def adjoint_many_device(self, gx, gy=None, matrices=False, out=None, tol=1e-9, max_sweeps=20):
+        """R adjoints of the last solve from ONE classification, assembly and factorization per item (qpdo_amd_fleet_adjoint_multi_dev) on
+        torch's current stream; returns without waiting.  gx: (R, N) float64, gy: (R, M) float64 or None.  Returns what adjoint_device
+        returns with a leading R on dq, dl, du, dQ_values, dA_values, status (R, count, 3) and residual (R, count); active (M) is one array,
+        the flags being the solve's.  Slab r carries the bits of adjoint_device(gx[r], gy[r]).  Needs adjoint=True (matrices=True also
+        matrix_updates=True), and the most recent update / warm start / solve call of the fleet must be a solve."""
+        (no, mo) = self.packed_layout()
+        N, M = int(no[-1]), int(mo[-1])
+        if gx is None:
+            raise ValueError("gx: expected a tensor, got None")
+        if not hasattr(gx, "dim") or gx.dim() != 2:
+            raise ValueError("gx: expected a tensor of shape (R, %d)" % N)
+        R = int(gx.shape[0])
+        if R < 1:
+            raise ValueError("gx: expected at least one right-hand side, got shape %r" % (tuple(gx.shape),))
+        NQ = NA = 0
+        if matrices:
+            qoff, aoff = self.packed_matrix_layout()
+            NQ, NA = int(qoff[-1]), int(aoff[-1])
+        spec = [("dq", "float64", (R, N)), ("dl", "float64", (R, M)), ("du", "float64", (R, M)), ("dQ_values", "float64", (R, NQ) if matrices else None),
+                ("dA_values", "float64", (R, NA) if matrices else None), ("active", "int32", (M,)), ("status", "int64", (R, self.count, 3)),
+                ("residual", "float64", (R, self.count))]
+        (gxp, gyp), _ = self._dev_args([("gx", gx, "float64", R * N), ("gy", gy, "float64", R * M)], None)
+        out = self._sens_out(spec, out, ("dq", "dl", "du") + (("dQ_values", "dA_values") if matrices else ()), "adjoint_many")
+        ptrs, _ = self._dev_args([(k, out[k], dt, 0 if shape is None else int(np.prod(shape))) for k, dt, shape in spec], None)
+        self._call(lib().qpdo_amd_fleet_adjoint_multi_dev(self._h, R, gxp, gyp, *ptrs, float(tol), int(max_sweeps), N, M, NQ, NA, self._stream()), "adjoint_many_device")
+        return out
+
+    def tangent_device(self, tq=None, tl=None, tu=None, tQ_values=None, tA_values=None, out=None, tol=1e-9, max_sweeps=20):
+        """The tangent of the last solve (qpdo_amd_fleet_tangent_dev) on torch's current stream; returns without waiting: the first-order
+        change (dx, dy) of the solution for a change tq (N), tl, tu (M), tQ_values (NQ), tA_values (NA) of the fleet's data at the solve's
+        active set.  Every passed array is (L,) or (R, L) float64 and all must agree on R; None is a zero perturbation (not all five).
+        Entries of tl, tu, tA_values on rows that do not use them are ignored.  A stype-0 Q takes a symmetric tQ.  Returns a dict of GPU
+        tensors with the leading R where the inputs had one: dx (N), dy (M; +0.0 off the active rows), active (M int32), status (count, 3)
+        int64 = code, sweeps, active rows, residual (count).  A right-hand side with code != 0 has NaN in its slices of dx, dy.  Needs
+        adjoint=True (tQ_values / tA_values also matrix_updates=True), and the most recent state-changing call must be a solve."""
+        (no, mo) = self.packed_layout()
+        N, M = int(no[-1]), int(mo[-1])
+        NQ = NA = 0
+        if tQ_values is not None or tA_values is not None:
+            qoff, aoff = self.packed_matrix_layout()
+            NQ, NA = int(qoff[-1]), int(aoff[-1])
+        ins = [("tq", tq, N), ("tl", tl, M), ("tu", tu, M), ("tQ_values", tQ_values, NQ), ("tA_values", tA_values, NA)]
+        passed = [(nm, t) for nm, t, _ in ins if t is not None]
+        if not passed:
+            raise ValueError("no tangent passed: tq, tl, tu, tQ_values and tA_values are all None")
+        for nm, t in passed:
+            if not hasattr(t, "dim") or t.dim() not in (1, 2):
+                raise ValueError("%s: expected a tensor of shape (L,) or (R, L)" % nm)
+        dims = {t.dim() for _, t in passed}
+        Rs = {int(t.shape[0]) if t.dim() == 2 else 1 for _, t in passed}
+        if len(dims) != 1 or len(Rs) != 1:
+            raise ValueError("the passed tangents do not agree on R: %s" % ", ".join("%s %r" % (nm, tuple(t.shape)) for nm, t in passed))
+        lead, R = dims == {2}, Rs.pop()
+        if R < 1:
+            raise ValueError("%s: expected at least one right-hand side" % passed[0][0])
+        sh = (lambda *s: (R,) + s) if lead else (lambda *s: s)
+        spec = [("dx", "float64", sh(N)), ("dy", "float64", sh(M)), ("active", "int32", (M,)), ("status", "int64", sh(self.count, 3)),
+                ("residual", "float64", sh(self.count))]
+        inp, _ = self._dev_args([(nm, t, "float64", R * L) for nm, t, L in ins], None)
+        out = self._sens_out(spec, out, ("dx", "dy"), "tangent")
+        ptrs, _ = self._dev_args([(k, out[k], dt, int(np.prod(shape))) for k, dt, shape in spec], None)
+        self._call(lib().qpdo_amd_fleet_tangent_dev(self._h, R, *inp, *ptrs, float(tol), int(max_sweeps), N, M, NQ, NA, self._stream()), "tangent_device")
+        return out
+
+    def rhs_group(self):
+        """right-hand sides one workgroup carries at once in adjoint_many_device / tangent_device (1: one after another)"""
+        return int(lib().qpdo_amd_fleet_rhs_group(self._h))
+
+    def sensitivity_stats(self):
+        """calls: adjoint_many_device + tangent_device calls that launched, since create; rhs_total: their right-hand sides; scratch_bytes"""
+        s = FleetSensitivityStats()
+        self._call(lib().qpdo_amd_fleet_get_sensitivity_stats(self._h, C.byref(s)), "sensitivity_stats")
+        return {f: getattr(s, f) for f, _ in FleetSensitivityStats._fields_}
 
     def fetch_last(self):
         """what results() returns, for the last solve whichever call launched it (waits for it; launches nothing)"""

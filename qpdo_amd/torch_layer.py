@@ -67,14 +67,16 @@ class FleetQP(torch.nn.Module):
     as they are in the fleet.  warm_start_last: start every solve from the previous solution.  on_failure: what the gradient slices of an item
     whose adjoint was not delivered (status code != 0: not solved, not accepted) hold -- "nan" (as the call returns them) or "zero".
     layer.status: (count, 3) int64 of the last forward (status_val, iterations, oterations); layer.adjoint_status: (count, 3) int64 of the last
-    backward (code, sweeps, active rows)."""
+    backward (code, sweeps, active rows).
+    layer.tangent(...) and layer.vjp_many(gx, gy) are the forward sensitivity and R backward products of the most recent forward, from one
+    factorization per item; their status tensors are kept as layer.tangent_status and layer.vjp_status."""
 
     def __init__(self, fleet, warm_start_last=True, on_failure="nan"):
         super().__init__()
         if on_failure not in ON_FAILURE:
             raise ValueError("on_failure: expected one of %r, got %r" % (ON_FAILURE, on_failure))
         self.fleet, self.warm_start_last, self.on_failure = fleet, bool(warm_start_last), on_failure
-        self.status, self.adjoint_status = None, None
+        self.status, self.adjoint_status, self.tangent_status, self.vjp_status = None, None, None, None
         self._item_of = None
 
     def _build_item_index(self):
@@ -97,4 +99,46 @@ class FleetQP(torch.nn.Module):
     def forward(self, q=None, l=None, u=None, Q_values=None, A_values=None):
         if self.on_failure == "zero" and self._item_of is None:
             self._build_item_index()
-        return _FleetQPFunction.apply(self, q, l, u, Q_values, A_values)
+        x, y = _FleetQPFunction.apply(self, q, l, u, Q_values, A_values)
+        self._serial = self.fleet.solve_serial
+        return x, y
+
+    # ---- sensitivities of the most recent forward beside autograd: many right-hand sides per factorization ---------------------------------
+    def _guard(self, what):
+        """the serial guard of backward: the fleet holds ONE solution, that of the most recent forward of this layer"""
+        serial, now = getattr(self, "_serial", None), getattr(self.fleet, "solve_serial", 0)
+        if serial is None:
+            raise RuntimeError("FleetQP.%s: no forward yet" % what)
+        if now != serial:
+            raise RuntimeError("FleetQP.%s: the fleet has been solved again since this forward (solve %d, now %d); a fleet holds one "
+                               "solution -- call %s before the next forward" % (what, serial, now, what))
+
+    def _failed(self, out, keys):
+        """on_failure applied to a sensitivity result: "zero" replaces the slices of right-hand sides with code != 0 by zeros (on the device)"""
+        res = {k: (None if v is None else v.clone()) for k, v in out.items()}
+        if self.on_failure == "zero":
+            if self._item_of is None:
+                self._build_item_index()
+            code = res["status"][..., 0]
+            for k, owner in keys.items():
+                if res[k] is not None and self._item_of[owner].numel():
+                    res[k] = torch.where(code[..., self._item_of[owner]] != 0, torch.zeros_like(res[k]), res[k])
+        return res
+
+    def tangent(self, tq=None, tl=None, tu=None, tQ_values=None, tA_values=None, tol=1e-9, max_sweeps=20):
+        """The first-order change (dx, dy) of the most recent forward's x, y for a change of its inputs (Fleet.tangent_device; arrays (L,) or
+        (R, L)): a dict with dx, dy, active, status, residual.  Raises when the fleet has been solved again since that forward."""
+        self._guard("tangent")
+        out = self.fleet.tangent_device(*(None if t is None else t.detach().contiguous() for t in (tq, tl, tu, tQ_values, tA_values)), tol=tol, max_sweeps=max_sweeps)
+        self.tangent_status = out["status"].clone()
+        return self._failed(out, dict(dx="dq", dy="dl"))
+
+    def vjp_many(self, gx, gy=None, matrices=False, tol=1e-9, max_sweeps=20):
+        """R vector-Jacobian products of the most recent forward at once (Fleet.adjoint_many_device; gx (R, N), gy (R, M) or None): a dict with
+        dq, dl, du, dQ_values, dA_values (matrices=True), active, status, residual, each gradient with the leading R.  Raises when the fleet
+        has been solved again since that forward."""
+        self._guard("vjp_many")
+        out = self.fleet.adjoint_many_device(gx.detach().contiguous(), None if gy is None else gy.detach().contiguous(), matrices=matrices, tol=tol,
+                                             max_sweeps=max_sweeps)
+        self.vjp_status = out["status"].clone()
+        return self._failed(out, dict(dq="dq", dl="dl", du="du", dQ_values="dQ_values", dA_values="dA_values"))
