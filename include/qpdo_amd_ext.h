@@ -614,7 +614,9 @@ int  qpdo_amd_fleet_sync(QPDOAmdFleet *f, QPDOAmdFleetDevStats *out);
  *          memory of the fleet's device (named); tol not a positive finite number; max_sweeps < 1; THE MOST RECENT STATE-CHANGING FLEET CALL
  *          WAS NOT A SOLVE -- an update, warm start or matrix update since the last solve(_dev) means the resident q, l, u or matrices are no
  *          longer those of the x, y returned.  adjoint_dev, fetch_last, sync and the getters do not count: several adjoint calls may follow
- *          one solve (the rows of a Jacobian).
+ *          one solve (the rows of a Jacobian).  Where several faults coincide the first in this order is reported, for adjoint_dev and
+ *          adjoint_multi_dev alike: the flag, (nrhs,) the lengths, the matrix flag and q_len / a_len, tol, max_sweeps, the NULL pointers,
+ *          "was not a solve", the pointers that are not device memory.
  * ORDER    that of the other device calls: enqueues on `stream`, returns at once, joins the fleet's one-event chain.  No hipGraph capture.
  * Stats    adjoint_calls of QPDOAmdFleetAdjointStats counts the calls that launched (QPDOAmdFleetDevStats keeps its five members: its size
  *          is part of the ABI); solve_launches, solves and the device-call counters do not move. */

@@ -727,49 +727,9 @@ int qdev_small_fleet_solve_dev(void *h_, double *x, double *y, long *status, dou
 done:
     return rc;
 }
-// The adjoint of the last solve on the caller's stream (include/qpdo_amd_ext.h): every check on the host, then ONE launch in the solve's own
-// launch shape (layout word, dynamic LDS), no wait.  Moves none of the solve's counters.
-int qdev_small_fleet_adjoint_dev(void *h_, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active, long *adj_status,
-                                 double *adj_res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {
-    int rc = 0;
-    SmallFleet *F = (SmallFleet *)h_;
-    hipStream_t s = (hipStream_t)stream_;
-    if (!(F->flags & QPDO_AMD_FLEET_ADJOINT)) { snprintf(s_err, sizeof(s_err), "the fleet was created without QPDO_AMD_FLEET_ADJOINT (qpdo_amd_fleet_create_ex)"); return -1; }
-    if (fleet_dev_lens(F, n_len, m_len)) return -1;
-    if (dQx || dAx) {
-        if (!(F->flags & QPDO_AMD_FLEET_MATRIX_UPDATES)) {
-            snprintf(s_err, sizeof(s_err), "%s was passed, but %s", dQx ? "dQx" : "dAx", FLEET_NO_MATRIX_FLAG); return -1;
-        }
-        const long NQ = F->qoff.back(), NA = F->aoff.back();
-        if (dQx && q_len != NQ) { snprintf(s_err, sizeof(s_err), "q_len is %ld, the fleet's packed Q values have %ld elements", q_len, NQ); return -1; }
-        if (dAx && a_len != NA) { snprintf(s_err, sizeof(s_err), "a_len is %ld, the fleet's packed A values have %ld elements", a_len, NA); return -1; }
-    }
-    if (!gx) { snprintf(s_err, sizeof(s_err), "gx is NULL"); return -1; }
-    if (!dq) { snprintf(s_err, sizeof(s_err), "dq is NULL"); return -1; }
-    if (!dl) { snprintf(s_err, sizeof(s_err), "dl is NULL"); return -1; }
-    if (!du) { snprintf(s_err, sizeof(s_err), "du is NULL"); return -1; }
-    if (!(tol > 0.0) || !(tol <= 1.7976931348623157e308)) { snprintf(s_err, sizeof(s_err), "tol is %g, it must be a positive finite number", tol); return -1; }
-    if (max_sweeps < 1) { snprintf(s_err, sizeof(s_err), "max_sweeps is %ld, it must be at least 1", max_sweeps); return -1; }
-    if (!F->last_was_solve) {
-        snprintf(s_err, sizeof(s_err), "the most recent state-changing fleet call was not a solve: the resident q, l, u and matrices must be those of the x, y returned");
-        return -1;
-    }
-    SHIP(hipSetDevice(F->device));
-    if (fleet_dev_ptr(F, gx, "gx") || fleet_dev_ptr(F, gy, "gy") || fleet_dev_ptr(F, dq, "dq") || fleet_dev_ptr(F, dl, "dl") || fleet_dev_ptr(F, du, "du") ||
-        fleet_dev_ptr(F, dQx, "dQx") || fleet_dev_ptr(F, dAx, "dAx") || fleet_dev_ptr(F, active, "active") || fleet_dev_ptr(F, adj_status, "adj_status") ||
-        fleet_dev_ptr(F, adj_res, "adj_res")) return -1;
-    SHIP(fleet_enter(F, s));
-    hipLaunchKernelGGL(k_small_fleet_adjoint, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, s, F->dprobs, (int)F->count, F->st, F->kflags, (const int *)F->doffs,
-                       (const int *)F->dmoffs, gx, gy, dq, dl, du, dQx, dAx, active, adj_status, adj_res, tol, (int)(max_sweeps > 1000000 ? 1000000 : max_sweeps));
-    SHIP(hipGetLastError());
-    SHIP(fleet_leave(F, s));
-    F->adjoint_calls++;
-done:
-    return rc;
-}
 long qdev_small_fleet_adjoint_calls(const void *h_) { return ((const SmallFleet *)h_)->adjoint_calls; }
-// Many right-hand sides per factorization (include/qpdo_amd_ext.h): the adjoint call's checks and a few of their own on the host, then ONE
-// launch of k_small_fleet_sens in the solve's launch shape, no wait.  Neither call changes the fleet's state or moves any other counter.
+// The adjoint of the last solve and many right-hand sides per factorization (include/qpdo_amd_ext.h): ONE set of checks on the host, then
+// ONE launch in the solve's launch shape, no wait.  No call changes the fleet's state or moves a counter other than its own.
 // The kernel addresses right-hand side r at r * (per-RHS length) in 64 bits; what it counts in 32 bits is the right-hand sides.
 static const long FLEET_SENS_MAX_NRHS = 2147483647L;
 static int fleet_sens_checks(const SmallFleet *F, long nrhs, bool matrices, const char *mname, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len,
@@ -812,10 +772,10 @@ done:
     return rc;
 }
 static const char *const FLEET_NOT_A_SOLVE = "the most recent state-changing fleet call was not a solve: the resident q, l, u and matrices must be those of the x, y returned";
-int qdev_small_fleet_adjoint_multi_dev(void *h_, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active,
-                                       long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {
+// every check of adjoint_dev (nrhs = 1) and adjoint_multi_dev, in ONE order; sname, rname: what the call names its status and residual arrays
+static int fleet_adjoint_checks(SmallFleet *F, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active,
+                                long *status, const char *sname, double *res, const char *rname, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len) {
     int rc = 0;
-    SmallFleet *F = (SmallFleet *)h_;
     if (fleet_sens_checks(F, nrhs, dQx || dAx, dQx ? "dQx" : "dAx", tol, max_sweeps, n_len, m_len, q_len, a_len, dQx != nullptr, dAx != nullptr)) return -1;
     if (!gx) { snprintf(s_err, sizeof(s_err), "gx is NULL"); return -1; }
     if (!dq) { snprintf(s_err, sizeof(s_err), "dq is NULL"); return -1; }
@@ -824,17 +784,38 @@ int qdev_small_fleet_adjoint_multi_dev(void *h_, long nrhs, const double *gx, co
     if (!F->last_was_solve) { snprintf(s_err, sizeof(s_err), "%s", FLEET_NOT_A_SOLVE); return -1; }
     SHIP(hipSetDevice(F->device));
     if (fleet_dev_ptr(F, gx, "gx") || fleet_dev_ptr(F, gy, "gy") || fleet_dev_ptr(F, dq, "dq") || fleet_dev_ptr(F, dl, "dl") || fleet_dev_ptr(F, du, "du") ||
-        fleet_dev_ptr(F, dQx, "dQx") || fleet_dev_ptr(F, dAx, "dAx") || fleet_dev_ptr(F, active, "active") || fleet_dev_ptr(F, status, "status") ||
-        fleet_dev_ptr(F, res, "res")) return -1;
-    {
-        SensArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = 0; a.in_n = gx; a.in_l = gy; a.out_n = dq; a.out_m1 = dl; a.out_m2 = du; a.out_q = dQx; a.out_a = dAx;
-        a.active = active; a.status = status; a.res = res; a.tol = tol; a.max_sweeps = (int)(max_sweeps > 1000000 ? 1000000 : max_sweeps);
-        rc = fleet_sens_launch(F, (hipStream_t)stream_, a, nrhs);
-    }
+        fleet_dev_ptr(F, dQx, "dQx") || fleet_dev_ptr(F, dAx, "dAx") || fleet_dev_ptr(F, active, "active") || fleet_dev_ptr(F, status, sname) ||
+        fleet_dev_ptr(F, res, rname)) return -1;
 done:
     return rc;
+}
+// The adjoint of the last solve on the caller's stream (include/qpdo_amd_ext.h): the checks, then ONE launch of its own kernel in the solve's
+// launch shape (layout word, dynamic LDS), no wait.  Moves adjoint_calls and no other counter.  (k_small_fleet_sens with one right-hand side
+// delivers the same bits, but 0.02 ms later on 4096 C3 items: profiles/fleet_one_sens_kernel_latency.txt.)
+int qdev_small_fleet_adjoint_dev(void *h_, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active, long *adj_status,
+                                 double *adj_res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {
+    int rc = 0;
+    SmallFleet *F = (SmallFleet *)h_;
+    hipStream_t s = (hipStream_t)stream_;
+    if (fleet_adjoint_checks(F, 1, gx, gy, dq, dl, du, dQx, dAx, active, adj_status, "adj_status", adj_res, "adj_res", tol, max_sweeps, n_len, m_len, q_len, a_len)) return -1;
+    SHIP(fleet_enter(F, s));
+    hipLaunchKernelGGL(k_small_fleet_adjoint, dim3((unsigned)F->count), dim3(SM_THREADS), F->lds, s, F->dprobs, (int)F->count, F->st, F->kflags, (const int *)F->doffs,
+                       (const int *)F->dmoffs, gx, gy, dq, dl, du, dQx, dAx, active, adj_status, adj_res, tol, (int)(max_sweeps > 1000000 ? 1000000 : max_sweeps));
+    SHIP(hipGetLastError());
+    SHIP(fleet_leave(F, s));
+    F->adjoint_calls++;
+done:
+    return rc;
+}
+int qdev_small_fleet_adjoint_multi_dev(void *h_, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du, double *dQx, double *dAx, int *active,
+                                       long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {
+    SmallFleet *F = (SmallFleet *)h_;
+    if (fleet_adjoint_checks(F, nrhs, gx, gy, dq, dl, du, dQx, dAx, active, status, "status", res, "res", tol, max_sweeps, n_len, m_len, q_len, a_len)) return -1;
+    SensArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mode = 0; a.in_n = gx; a.in_l = gy; a.out_n = dq; a.out_m1 = dl; a.out_m2 = du; a.out_q = dQx; a.out_a = dAx;
+    a.active = active; a.status = status; a.res = res; a.tol = tol; a.max_sweeps = (int)(max_sweeps > 1000000 ? 1000000 : max_sweeps);
+    return fleet_sens_launch(F, (hipStream_t)stream_, a, nrhs);
 }
 int qdev_small_fleet_tangent_dev(void *h_, long nrhs, const double *tq, const double *tl, const double *tu, const double *tQx, const double *tAx, double *dx, double *dy,
                                  int *active, long *status, double *res, double tol, long max_sweeps, long n_len, long m_len, long q_len, long a_len, void *stream_) {

@@ -2004,6 +2004,10 @@ __global__ __launch_bounds__(SM_THREADS, 2) void k_small_fleet_adjoint(SmallQP *
 // behind inline functions changed their streams in three attempts out of four when the LDS plan was unified (docs/LAB_NOTES.md), so
 // the old kernel is left alone.  What holds the copies together is the bit comparison of every output slab with the single call in
 // tests/test_gpu_fleet_sensitivity.py (both paths below, all layouts); a change to the sweep in one kernel belongs in the other too.
+// Since then ONE kernel was built and timed: the single call as this kernel's nrhs = 1 launch is 0.02 ms (0.6 %) later on 4096 C3 items, about
+// the parent's own spread, and with the statements that the two paths below share behind inline functions 0.04 ms, at unchanged register
+// figures (profiles/fleet_one_sens_kernel_latency.txt, docs/LAB_NOTES.md).  So the copies stay; the single call's bits are pinned by a
+// recording (tests/golden/fleet_adjoint_parent_bits.json) for whoever makes the nrhs = 1 path as fast as the old kernel.
 // one wave's triangular solves for ONE right-hand side of a group (the dispatch of small_ldl_solve, out of line: four instances of the wave
 // solve inlined into the kernel a second time cost it 1244 vector-register spills)
 __device__ __attribute__((noinline)) void small_ldl_solve_slot(int n, const lds_f64 *Kl, const double *b, double *xout) {

@@ -7,7 +7,8 @@ vy = dl + du read back, the longdouble residual of the unscaled adjoint system m
     tol max(||gx||, ||gy_S||) + (n + k + 2) eps || |M| |v| ||_inf
 (the second term: the rounding of the kernel's own fp64 residual evaluation, the standard dot-product bound), and where M's float64
 condition number is below 1 / eps -- beyond that a float64 inverse says nothing -- also ||v - v_ref|| <= 2 ||M^-1||_inf (that bound).
-usage: _fleet_adjoint_worker.py OUT.json"""
+usage: _fleet_adjoint_worker.py OUT.json
+       _fleet_adjoint_worker.py --record PATH     (writes what the scenario parent_bits compares against: tests/golden/fleet_adjoint_parent_bits.json)"""
 import functools
 import json
 import os
@@ -415,13 +416,72 @@ def fleet_qp_layer():
         F.close()
 
 
+GOLDEN_BITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fleet_adjoint_parent_bits.json")
+BITS_KEYS = ("dq", "dl", "du", "dQ_values", "dA_values", "active", "residual")
+
+
+def sha(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def single_call_bits():
+    """The single call's outputs on fleet P / B / G, scaling 10 and 0, gy None and given (NaN on the inactive rows), matrices off and on, from
+    fixed seeds: per case the SHA-256 of x and y of the solve and of every output array, and the status array in full.  Only solve_device and
+    adjoint_device are used, so the same function records (--record, at the commit whose bits are to be kept) and recomputes."""
+    cases = {}
+    for name in ("P", "B", "G"):
+        for scaling in (10, 0):
+            F = solver.Fleet(list(fleet(name)), matrix_updates=True, adjoint=True, scaling=scaling, **ST)
+            try:
+                assert F.factor_layout() == LAYOUT[name]
+                no, mo = F.packed_layout()
+                sol = host(F.solve_device())
+                rng = np.random.default_rng(900 + scaling)
+                gx = rng.standard_normal(int(no[-1]))
+                flags = host(F.adjoint_device(gpu(gx)))["active"]
+                gy = rng.standard_normal(int(mo[-1]))
+                gy[flags == 0] = np.nan
+                for with_gy in (False, True):
+                    for matrices in (False, True):
+                        o = host(F.adjoint_device(gpu(gx), gpu(gy) if with_gy else None, matrices=matrices, out=sentinel_out(F, matrices), tol=TOL))
+                        c = {"x": sha(sol["x"]), "y": sha(sol["y"]), "status": o["status"].tolist()}
+                        c.update({k: sha(o[k]) for k in BITS_KEYS if o.get(k) is not None})
+                        assert len(c) == 3 + len(BITS_KEYS) - (0 if matrices else 2), sorted(c)
+                        cases["%s[%d] gy=%s matrices=%s" % (name, scaling, with_gy, matrices)] = c
+            finally:
+                F.close()
+    return cases
+
+
+def parent_bits():
+    """the single call delivers the bits it delivered at the commit before this scenario was added (the recording)"""
+    with open(GOLDEN_BITS) as f:
+        want = json.load(f)["cases"]
+    got = single_call_bits()
+    assert sorted(got) == sorted(want) and len(want) == 24, (sorted(got), sorted(want))
+    stale = [k for k in want if (got[k]["x"], got[k]["y"]) != (want[k]["x"], want[k]["y"])]
+    assert not stale, ("the SOLVE's x / y are not the recorded ones: the recording is stale (a change to the solve; record again), "
+                       "this says nothing about the adjoint", stale)
+    moved = {k: [f for f in want[k] if got[k].get(f) != want[k][f]] for k in want if got[k] != want[k]}
+    assert not moved, ("the single adjoint call's outputs are not the recorded ones", moved)
+
+
+def record(path):
+    with open(path, "w") as f:
+        json.dump({"cases": single_call_bits()}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 SCENARIOS = {"fleet_%s[%d]" % (nm, sc): functools.partial(one_fleet, nm, sc) for nm in ("P", "B", "G") for sc in (10, 0)}
 SCENARIOS.update({"no_bit_moves[%s]" % nm: functools.partial(no_bit_moves, nm) for nm in ("P", "B", "G")})
 SCENARIOS.update({"not_accepted": not_accepted, "refusals_launch_nothing": refusals_launch_nothing, "streams": streams,
-                  "fleet_qp_layer": fleet_qp_layer})
+                  "fleet_qp_layer": fleet_qp_layer, "parent_bits": parent_bits})
 
 
 def main():
+    if sys.argv[1] == "--record":
+        return record(sys.argv[2])
     out = {}
     for name, run in SCENARIOS.items():
         try:

@@ -9,7 +9,11 @@ the library is loaded (one HIP runtime in the process; tests/test_gpu_fleet_devi
                     layout of K (GLOBAL: the adjoint overwrites the items' global work vectors and K buffer)
   refusals          before a solve, after an update, without the flags, wrong lengths, host pointers: nothing launched, no counter moved
   streams           the call on a side stream behind a solve on another, ordered by the fleet's event
-  FleetQP           backward equals the direct call bit for bit; which inputs get gradients; "zero"; the stale backward"""
+  FleetQP           backward equals the direct call bit for bit; which inputs get gradients; "zero"; the stale backward
+  parent bits       every output of the call on fleets P / B / G (both scalings, gy None and given, matrices off and on) hashes to what the
+                    call delivered at the commit before this test (tests/golden/fleet_adjoint_parent_bits.json, recorded with
+                    _fleet_adjoint_worker.py --record PATH on an MI355X): the anchor for any change to the kernel behind the call, or to which
+                    kernel that is; a moved x or y of the SOLVE is reported as a stale recording, not as a changed adjoint"""
 import functools
 import json
 import os
@@ -64,3 +68,7 @@ def test_the_call_on_a_side_stream(scenario):
 
 def test_fleet_qp_layer(scenario):
     assert scenario("fleet_qp_layer") == "ok"
+
+
+def test_the_single_call_keeps_its_recorded_bits(scenario):
+    assert scenario("parent_bits") == "ok"
