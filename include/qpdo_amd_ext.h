@@ -330,6 +330,69 @@ int  qpdo_amd_slab_trip_shape(int value_bytes, int operand_bytes, int *shape);
 /* copy a device-resident vector to the host: 0 x, 1 Qx, 2 y, 3 mu, 4 d (factor weights),
  * 5 dx, 6 dy, 7 Ax, 8 Aty, 9 l, 10 u, 11 ybar, 12 xbar, 13 w (of the last loop pass that ran) */
 int  qpdo_amd_download(QPDOWorkspace *work, int which, double *dst);
+/* ---- the ADJOINT of a workspace's last solve: gradients of the solution w.r.t. q, l, u, Q, A at every size the direct solvers take ----------
+ * The contract of qpdo_amd_fleet_adjoint_dev / _adjoint_multi_dev (below), applied to ONE workspace on its own direct solver.  All pointers
+ * are HOST pointers, as for every other single-workspace entry point.  Arrays are right-hand-side major: right-hand side r of an array whose
+ * per-RHS length is L (n, m, nnz(Q as stored), nnz(A)) starts at r * L.  All quantities are the caller's UNSCALED ones; x, y are the ones
+ * qpdo_solve delivered in work->solution: the call uploads them and forms the scaled x itself, it reads nothing of the iterate state on the
+ * device, and so it also works after a solve that ran as the fused one-launch kernel.
+ * ACTIVE SET  t = Ax + y.  Row i is upper-active (flag +1) if t_i >= u_i, else lower-active (-1) if t_i <= l_i, else inactive (0).  A bound of
+ *          magnitude >= 1e20 is never reached.  The rule is evaluated in the workspace's scaled space (E_i t_i against the stored scaled
+ *          bounds), so a row within rounding of a bound may fall either way: the call DELIVERS its flags (`active`, m int32, ONE array: the
+ *          flags depend on the solve, not on the right-hand side), and everything else is defined by them.  S: the flagged rows, k = |S|.
+ * SYSTEM   Given gx = dL/dx (nrhs x n) and gy = dL/dy (nrhs x m, or NULL = zero; entries of inactive rows are ignored and may hold anything,
+ *          NaN included):
+ *              [ Q    A_S' ] [vx]   [ gx   ]
+ *              [ A_S  0    ] [vy] = [ gy_S ]
+ *          dq = -vx;  du_i = vy_i on +1 rows, dl_i = vy_i on -1 rows, every other entry of dl, du an exact +0.0;  for a stored entry (i, j) of
+ *          A: -(y_i vx_j + vy_i x_j) on a flagged row, else +0.0;  for a stored entry (a, b) of Q: -vx_a x_b (stype 0), -(vx_a x_b + vx_b x_a)
+ *          (off-diagonal, stype +-1), -vx_a x_a (diagonal); a stored entry in the triangle that stype +-1 ignores gets +0.0.  dAx follows the
+ *          order of data->A->x at setup, dQx the order of Q->x as stored at setup; both are evaluated from the very dq, dl, du delivered.
+ *          Q is needed only with dQx: the first such call compares its pattern with the setup's on the device (and, for stype +-1, builds the
+ *          map that qpdo_amd_update_matrices builds on its first call with a Q; whichever call comes first builds it); later calls compare
+ *          the column pointers.  A workspace with m = 0 solves Q vx = gx.
+ * METHOD   The fleet's, on the scaled matrices Qs, As: sigma = 1e-10 s, W_i = 1e10 s / ||row i of As||^2 on flagged rows and 0 elsewhere, s the
+ *          largest |diagonal entry| of Qs (1 when there is none).  K = Qs + sigma I + As' W As is factored ONCE per call by the workspace's
+ *          direct solver -- always a full factorization, whatever QPDO_DENSE_LOWRANK / QPDO_DENSE_UPDOWN say --, and per right-hand side
+ *          K dvx = rx + As_S' W ry,  dvy = W (As_S dvx - ry)  is repeated on the residual (rx, ry) of the TRUE system (no sigma, no W^-1);
+ *          the right-hand sides follow one another on the one factor, each with the single call's operations in its order: slab r of an
+ *          nrhs = R call carries the bits of the nrhs = 1 call with that gx / gy, and the same call twice returns the same bits.
+ * ACCEPTANCE  max(||Q vx + A_S' vy - gx||_inf, ||A_S vx - gy_S||_inf) <= tol * max(||gx||_inf, ||gy_S||_inf), on the true residual in unscaled
+ *          terms, looked at before every sweep; at most max_sweeps sweeps.  A residual that is not finite is never accepted.
+ * status   nrhs x 3: (code, sweeps, k).  code 0: accepted.  1: not accepted within max_sweeps (an inconsistent, singular or very
+ *          ill-conditioned system; this right-hand side's own).  3: a pivot of K that is not a positive finite number, or a polling kernel of
+ *          the triangular solves that lost its producer; the latch is cleared as qpdo_amd_direct_solve clears it, nothing is redone, code 3
+ *          repeats for every r and `active` is all 0.  A right-hand side with code != 0 gets NaN in all its slices of dq, dl, du, dQx, dAx and
+ *          NaN in res[r]; res[r] of an accepted one is its relative residual.  (There is no code 2: a workspace that is not solved is refused.)
+ * Accepted workspaces: one GPU; the workspace's solver is the dense LDL' or the band LDL' with half-bandwidth <= 127 and no coupling rows.
+ *          Refused with a message that names what to do instead: PCG workspaces, hybrid workspaces (the automatically chosen dense solver
+ *          from n = 8192, whose solves start with PCG: set QPDO_LINSOLVE=dense), band with b > 127, QPDO_BAND_COUPLING workspaces with
+ *          coupling rows, row-partitioned workspaces.
+ * Checks   all before anything is launched or written; a refused call returns nonzero with qpdo_amd_last_error() set and leaves every
+ *          output array untouched.  The first fault in this order is reported: nrhs < 1; tol not a positive finite number; max_sweeps < 1;
+ *          NULL gx, dq, dl or du; dQx without Q; NULL workspace; info->status_val != QPDO_SOLVED; THE MOST RECENT STATE-CHANGING CALL WAS NOT A
+ *          SOLVE -- qpdo_warm_start, qpdo_update_q, qpdo_update_bounds or qpdo_amd_update_matrices since the last qpdo_solve mean that the
+ *          resident q, l, u or matrices are no longer those of the x, y in work->solution (the adjoint and the getters do not count: several
+ *          adjoint calls may follow one solve) --; the solver kind; the shape, stype, entry count and pattern of Q.
+ * No trace The call writes none of the workspace's state, solution, matrices, q, l, u, info, trace or QPDOAmdStats: what it overwrites on
+ *          the way (the factor weights, sigma, the direction and right-hand side vectors, the counters) is put back, and the factor it leaves
+ *          is dropped by the next qpdo_solve, as after qpdo_amd_direct_solve.  Every later qpdo_solve carries the bits it would have had.
+ * Stats    QPDOAmdAdjointStats: calls that launched, their right-hand sides, factorizations (one per call), sweeps of all right-hand sides,
+ *          the device memory the calls hold -- 6 n + 7 m doubles and m flags of work vectors, allocated by the FIRST call (a host
+ *          allocation: THAT CALL MAY BLOCK until earlier device work has finished), plus one array per entry of A / of the stored Q from the
+ *          first call that asks for dAx / dQx; freed by qpdo_cleanup --, and the wall time of the last call. */
+typedef struct {
+    long   calls, rhs_total, factorizations, sweeps_total, scratch_bytes;
+    double last_seconds;
+} QPDOAmdAdjointStats;
+int  qpdo_amd_adjoint(QPDOWorkspace *work, long nrhs,
+                      const double *gx /* nrhs x n */, const double *gy /* nrhs x m or NULL */,
+                      double *dq /* nrhs x n */, double *dl /* nrhs x m */, double *du /* nrhs x m */,
+                      const cholmod_sparse *Q /* the setup's Q pattern; needed only with dQx */,
+                      double *dQx /* nrhs x nnz(Q as stored) or NULL */, double *dAx /* nrhs x nnz(A) or NULL */,
+                      int *active /* m int32 or NULL */, long *status /* nrhs x 3 or NULL */, double *res /* nrhs or NULL */,
+                      double tol, long max_sweeps);
+int  qpdo_amd_get_adjoint_stats(const QPDOWorkspace *work, QPDOAmdAdjointStats *out);
 
 /* ---- one large QP row-partitioned over G GPUs (BASELINE.json configs[3]) --------------------------------
  * One process per GPU.  Every rank calls the normal API with the SAME full problem; the library keeps rows

@@ -1,0 +1,373 @@
+// adjoint.inc -- part of qpdo_dev.hip (one translation unit; included in order): qpdo_amd_adjoint -- the gradients of a workspace's solution
+// w.r.t. q, l, u, Q, A (include/qpdo_amd_ext.h; DESIGN.md 3.7).  The method is the fleet's (qpdo_small.hip k_small_fleet_adjoint), device
+// wide: at the x, y the solve delivered the rows are classified (t = Ax + y against the bounds), and
+//   [ Q  A_S' ; A_S  0 ] [vx ; vy] = [gx ; gy_S]
+// is solved in the workspace's SCALED space -- Qs = c D Q D, As = E A D, vxs = D^-1 vx, vys = c E^-1 vy, gxs = c D gx, gys = E gy: the same
+// system in the stored matrices -- by block elimination on the regularised matrix:
+//   K dvx = rx + As_S' W ry,   dvy = W (As_S dvx - ry),   K = Qs + sigma I + As_S' W As_S,
+// repeated on the residual (rx, ry) of the TRUE system.  K is the Newton matrix with weights W on the flagged rows: it is factored ONCE per
+// call by the workspace's own direct solver (dense_factor / band_factor) and solved by dense_solve / band_solve; the products are the
+// workspace's SpMV.  The kernels here are streams over n, m or nnz.  Every reduction is a maximum or an integer count (exact and order
+// free on the control block, helpers.inc block_max_to), so two calls on one solve deliver the same bits.
+#define ADJ_SIGMA_REL 1e-10
+#define ADJ_ROW_WEIGHT 1e10
+#define ADJ_DBL_MAX 1.7976931348623157e308
+static const int ADJ_LPR = 16;                    // lanes per matrix row in the row-wise kernels (rows of A, A', Q: tens of entries)
+enum { ADJ_N_XU = 0, ADJ_N_GXS, ADJ_N_VX, ADJ_N_RX, ADJ_N_T1, ADJ_N_T2, ADJ_N_COUNT };
+enum { ADJ_M_YU = 0, ADJ_M_GYS, ADJ_M_VY, ADJ_M_RY, ADJ_M_WRY, ADJ_M_AV, ADJ_M_A2, ADJ_M_COUNT };
+
+__device__ __forceinline__ double adj_abs(double v) { return v < 0 ? -v : v; }
+static inline int adj_grid_rows(long long nrows) { return vgrid(nrows * ADJ_LPR); }
+
+// zero the slots a right-hand side uses: N_A = ||gx||, N_B = ||gy_S||, N_C / N_D = the sweep's two residual norms, C_VIOL = the
+// non-finite marker (all: a new right-hand side; else: the two residual norms of the next sweep)
+__global__ void k_adj_ctrl_clear(Ctrl *c, int all) {
+    const int t = threadIdx.x;
+    if (blockIdx.x) return;
+    if (t == 0) c->nrm[N_C] = 0ull;
+    if (t == 1) c->nrm[N_D] = 0ull;
+    if (all && t == 2) c->nrm[N_A] = 0ull;
+    if (all && t == 3) c->nrm[N_B] = 0ull;
+    if (all && t == 4) c->cnt[C_VIOL] = 0;
+}
+// once per call, n side: xs = D^-1 x; the largest |diagonal entry| of Qs into N_C (from qdiag when the workspace holds it)
+__global__ void k_adj_scale_x(int n, int scaled, const double *__restrict__ Dinv, const double *__restrict__ xu, const double *__restrict__ qdiag,
+                              const int *__restrict__ Qrp, const int *__restrict__ Qci, const double *__restrict__ Qval, double *__restrict__ xs, Ctrl *ctrl) {
+    __shared__ double sm[32];
+    double mqd = 0.0;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+        xs[j] = scaled ? xu[j] * Dinv[j] : xu[j];
+        if (qdiag) { const double a = adj_abs(qdiag[j]); mqd = a > mqd ? a : mqd; }
+        else for (int k = Qrp[j]; k < Qrp[j + 1]; k++) if (Qci[k] == j) { const double a = adj_abs(Qval[k]); mqd = a > mqd ? a : mqd; }
+    }
+    block_max_to(mqd, &ctrl->nrm[N_C], sm);
+}
+// once per call, m side (Av = As xs is there): the flags from t = Axs + E y against the stored (scaled) bounds, the rows' squared norms,
+// the number of flagged rows into C_MUCH.  ADJ_LPR lanes per row; the lanes' partial sums are folded in a fixed order.
+__global__ void k_adj_classify(int m, int scaled, const double *__restrict__ E, const double *__restrict__ yu, const double *__restrict__ l,
+                               const double *__restrict__ u, const double *__restrict__ Av, const int *__restrict__ Arp, const double *__restrict__ Aval,
+                               int *__restrict__ flag, double *__restrict__ a2out, Ctrl *ctrl) {
+    __shared__ int smi[32];
+    const int lane = threadIdx.x & (ADJ_LPR - 1);
+    const int groups = gridDim.x * (blockDim.x / ADJ_LPR);
+    int cnt = 0;
+    const int rounds = (m + groups - 1) / groups;          // (every lane takes part in every shuffle)
+    for (int it = 0; it < rounds; it++) {
+        const int i = it * groups + blockIdx.x * (blockDim.x / ADJ_LPR) + (threadIdx.x / ADJ_LPR);
+        double a2 = 0.0;
+        if (i < m) for (int k = Arp[i] + lane; k < Arp[i + 1]; k += ADJ_LPR) { const double a = Aval[k]; a2 += a * a; }
+#pragma unroll
+        for (int o = ADJ_LPR / 2; o > 0; o >>= 1) a2 += __shfl_down(a2, o, ADJ_LPR);
+        if (i < m && lane == 0) {
+            const double e = scaled ? E[i] : 1.0, yi = yu[i];
+            const double t = Av[i] + (scaled ? e * yi : yi);
+            const double lo = l[i], up = u[i];
+            int f = 0;
+            if (up < e * QPDO_INFTY_D && t >= up) f = 1;
+            else if (lo > -e * QPDO_INFTY_D && t <= lo) f = -1;
+            flag[i] = f; cnt += (f != 0);
+            a2out[i] = a2;
+        }
+    }
+    const int tot = block_sum_int(cnt, smi);
+    if (threadIdx.x == 0 && tot) atomicAdd(&ctrl->cnt[C_MUCH], tot);
+}
+// once per call, after s is known: the factorization's weights d_i = W_i = 1e10 s / ||row i of As||^2 on flagged rows, 0 elsewhere
+__global__ void k_adj_weights(int m, double s, const int *__restrict__ flag, const double *__restrict__ a2, double *__restrict__ W) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
+        const double v = a2[i];
+        W[i] = (flag[i] && v > 0.0) ? (ADJ_ROW_WEIGHT * s) / v : 0.0;
+    }
+}
+// dense route: the pivots of the fresh factor; one that is not a positive finite number sets C_DINF
+__global__ void k_adj_check_pivots(int n, const double *__restrict__ Dg, Ctrl *ctrl) {
+    int bad = 0;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) { const double dj = Dg[j]; bad |= !(dj > 0.0 && dj <= ADJ_DBL_MAX); }
+    if (bad) ctrl->cnt[C_DINF] = 1;
+}
+// per right-hand side: gxs = c D gx, gys = E gy on flagged rows (0 elsewhere: gy of an inactive row is never read), vx = vy = 0,
+// ||gx||inf -> N_A, ||gy_S||inf -> N_B, a non-finite entry among those used -> C_VIOL
+__global__ void k_adj_rhs(int n, int m, int scaled, double c, const double *__restrict__ D, const double *__restrict__ E, const double *__restrict__ gx,
+                          const double *__restrict__ gy, const int *__restrict__ flag, double *__restrict__ gxs, double *__restrict__ gys, double *__restrict__ vx,
+                          double *__restrict__ vy, Ctrl *ctrl) {
+    __shared__ double sm[32];
+    double mgx = 0.0, mgy = 0.0; int nonfin = 0;
+    const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (int j = t0; j < n; j += stride) {
+        const double g = gx[j];
+        gxs[j] = scaled ? c * (D[j] * g) : g;
+        vx[j] = 0.0;
+        const double ag = adj_abs(g);
+        mgx = ag > mgx ? ag : mgx;
+        if (!(ag <= ADJ_DBL_MAX)) nonfin = 1;
+    }
+    for (int i = t0; i < m; i += stride) {
+        double g = 0.0;
+        if (flag[i] && gy) { g = gy[i]; const double ag = adj_abs(g); mgy = ag > mgy ? ag : mgy; if (!(ag <= ADJ_DBL_MAX)) nonfin = 1; }
+        gys[i] = scaled ? E[i] * g : g;
+        vy[i] = 0.0;
+    }
+    block_max_to(mgx, &ctrl->nrm[N_A], sm);
+    block_max_to(mgy, &ctrl->nrm[N_B], sm + 16);
+    if (nonfin) ctrl->cnt[C_VIOL] = 1;
+}
+// per sweep, behind t1 = Qs vx, Av = As vx, t2 = As' vy: rx = (gxs - t1) - t2, ry = gys - Av on flagged rows, wry = W ry; the two
+// inf-norms in unscaled terms (||rx D^-1|| -> N_C, the host multiplies by 1 / c; ||ry E^-1|| -> N_D); a non-finite one -> C_VIOL
+__global__ void k_adj_resid(int n, int m, int scaled, const double *__restrict__ Dinv, const double *__restrict__ Einv, const double *__restrict__ gxs,
+                            const double *__restrict__ t1, const double *__restrict__ t2, const double *__restrict__ gys, const double *__restrict__ Av,
+                            const int *__restrict__ flag, const double *__restrict__ W, double *__restrict__ rx, double *__restrict__ ry,
+                            double *__restrict__ wry, Ctrl *ctrl) {
+    __shared__ double sm[32];
+    double m1 = 0.0, m2 = 0.0; int nonfin = 0;
+    const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (int j = t0; j < n; j += stride) {
+        const double r = (gxs[j] - t1[j]) - t2[j];
+        rx[j] = r;
+        const double a = adj_abs(scaled ? r * Dinv[j] : r);
+        m1 = a > m1 ? a : m1;
+        if (!(a <= ADJ_DBL_MAX)) nonfin = 1;
+    }
+    for (int i = t0; i < m; i += stride) {
+        const double r = flag[i] ? gys[i] - Av[i] : 0.0;
+        ry[i] = r; wry[i] = W[i] * r;
+        const double a = adj_abs(scaled ? r * Einv[i] : r);
+        m2 = a > m2 ? a : m2;
+        if (!(a <= ADJ_DBL_MAX)) nonfin = 1;
+    }
+    block_max_to(m1, &ctrl->nrm[N_C], sm);
+    block_max_to(m2, &ctrl->nrm[N_D], sm + 16);
+    if (nonfin) ctrl->cnt[C_VIOL] = 1;
+}
+// the solve's right-hand side: rhs = rx + As' wry (t2 holds the product)
+__global__ void k_adj_solve_rhs(int n, const double *__restrict__ rx, const double *__restrict__ t2, double *__restrict__ rhs) {
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) rhs[j] = rx[j] + t2[j];
+}
+// behind Av = As dvx: vy += W (Av - ry), vx += dvx
+__global__ void k_adj_update(int n, int m, const double *__restrict__ dvx, const double *__restrict__ Av, const double *__restrict__ ry,
+                             const double *__restrict__ W, double *__restrict__ vx, double *__restrict__ vy) {
+    const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (int i = t0; i < m; i += stride) vy[i] = vy[i] + W[i] * (Av[i] - ry[i]);
+    for (int j = t0; j < n; j += stride) vx[j] = vx[j] + dvx[j];
+}
+// back to the caller's space: vx = D vxs, vy = E vys / c; dq = -vx, du = vy on +1 rows, dl = vy on -1 rows, every other entry +0.0
+__global__ void k_adj_grad_vec(int n, int m, int scaled, double cinv, const double *__restrict__ D, const double *__restrict__ E, const int *__restrict__ flag,
+                               const double *__restrict__ vx, const double *__restrict__ vy, double *__restrict__ vxu, double *__restrict__ vyu,
+                               double *__restrict__ dq, double *__restrict__ dl, double *__restrict__ du) {
+    const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (int j = t0; j < n; j += stride) { const double v = scaled ? D[j] * vx[j] : vx[j]; vxu[j] = v; dq[j] = -v; }
+    for (int i = t0; i < m; i += stride) {
+        const int f = flag[i];
+        double v = 0.0;
+        if (f) { v = vy[i]; if (scaled) { v = E[i] * v; v = v * cinv; } }
+        vyu[i] = v;
+        du[i] = f > 0 ? v : 0.0; dl[i] = f < 0 ? v : 0.0;
+    }
+}
+// dL/dA over the rows of CSR(A') (= the caller's CSC arrays of A, so entry k is the caller's entry k): -(y_i vx_j + vy_i x_j) on a flagged
+// row i, +0.0 elsewhere
+__global__ void k_adj_grad_A(int n, const int *__restrict__ Trp, const int *__restrict__ Tci, const int *__restrict__ flag, const double *__restrict__ xu,
+                             const double *__restrict__ yu, const double *__restrict__ vxu, const double *__restrict__ vyu, double *__restrict__ dA) {
+    const int lane = threadIdx.x & (ADJ_LPR - 1);
+    const int groups = gridDim.x * (blockDim.x / ADJ_LPR);
+    for (int j = blockIdx.x * (blockDim.x / ADJ_LPR) + (threadIdx.x / ADJ_LPR); j < n; j += groups) {
+        const double vxj = vxu[j], xj = xu[j];
+        for (int k = Trp[j] + lane; k < Trp[j + 1]; k += ADJ_LPR) { const int i = Tci[k]; dA[k] = flag[i] ? -(yu[i] * vxj + vyu[i] * xj) : 0.0; }
+    }
+}
+// dL/dQ over the rows of the full CSR(Q).  mapQ == null (stype 0): entry k of row r IS the caller's entry k, row cc of column r.
+// Otherwise the stored entry is written from the lower-triangle image (its mirror names the same stored entry); dQ was zero-filled.
+__global__ void k_adj_grad_Q(int n, const int *__restrict__ Qrp, const int *__restrict__ Qci, const u32 *__restrict__ mapQ, const double *__restrict__ xu,
+                             const double *__restrict__ vxu, double *__restrict__ dQ) {
+    const int lane = threadIdx.x & (ADJ_LPR - 1);
+    const int groups = gridDim.x * (blockDim.x / ADJ_LPR);
+    for (int r = blockIdx.x * (blockDim.x / ADJ_LPR) + (threadIdx.x / ADJ_LPR); r < n; r += groups) {
+        const double vr = vxu[r], xr = xu[r];
+        for (int k = Qrp[r] + lane; k < Qrp[r + 1]; k += ADJ_LPR) {
+            const int cc = Qci[k];
+            if (!mapQ) dQ[k] = -(vxu[cc] * xr);
+            else if (r == cc) dQ[mapQ[k]] = -(vr * xr);
+            else if (r > cc) dQ[mapQ[k]] = -(vr * xu[cc] + vxu[cc] * xr);
+        }
+    }
+}
+
+static int adjoint_refuse(const char *msg) { snprintf(g_err, sizeof(g_err), "qpdo_amd_adjoint: %s", msg); return -1; }
+
+int qdev_get_adjoint_stats(QpdoDev *d, QdevAdjointStats *out) { *out = d->adj; return 0; }
+
+// the workspaces the call takes: one GPU, the dense LDL' or the plain band LDL' with b <= 127 as the workspace's solver
+int qdev_adjoint_check_kind(QpdoDev *d) {
+    if (d->comm.active) return adjoint_refuse("row-partitioned workspaces are not supported (solve the QP on one GPU, or take finite differences of qpdo_solve)");
+    if (d->hybrid) return adjoint_refuse("the workspace starts its solves with PCG (the hybrid of an automatically chosen dense solver from n = 8192, QPDO_HYBRID); set up with QPDO_LINSOLVE=dense");
+    if (d->linsolve != 1 && d->linsolve != 3)
+        return adjoint_refuse("the workspace's solver is PCG; the adjoint needs a direct solver: set up with QPDO_LINSOLVE=dense (n <= 40000) or QPDO_LINSOLVE=band");
+    if (d->linsolve == 3 && d->band_b > BAND_MAX_B) return adjoint_refuse("the band solver's half-bandwidth is above 127; set up with QPDO_LINSOLVE=dense");
+    if (d->linsolve == 3 && d->bc_r > 0) return adjoint_refuse("the band solver carries coupling rows (QPDO_BAND_COUPLING); set up without it or with QPDO_LINSOLVE=dense");
+    return 0;
+}
+
+int qdev_adjoint(QpdoDev *d, const double *x, const double *y, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du,
+                 const QdevCsc *Q, double *dQx, double *dAx, int *active, long *status, double *res, double tol, long max_sweeps) {
+    HIPCHK(hipSetDevice(d->device));
+    struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
+    const int n = d->n, m = d->m;
+    // ---- checks: nothing is launched or written before they pass ------------------------------------------------------------------
+    { int rck = qdev_adjoint_check_kind(d); if (rck) return rck; }
+    const int kind = d->linsolve;
+    const bool wantQ = dQx != nullptr, wantA = dAx != nullptr;
+    u32 *newMapQ = nullptr; double *newStage = nullptr;
+    bool firstQ = false;
+    if (wantQ) {
+        int rc = 0, differs = 0;
+        firstQ = d->upd_Qp.empty();
+        if (!firstQ && !upd_colptr_same(Q, d->upd_Qp)) differs = 1;
+        if (firstQ) {
+            TempAllocs tmp;
+            rc = upd_first_Q(d, tmp, Q, &differs, &newMapQ, &newStage);
+            if (!rc) { hipError_t e = hipGetLastError(); if (e != hipSuccess) rc = set_err(e, "adjoint checks", __LINE__); }
+            tmp.release(d->stream);
+            h2d_staging_release(d);
+        }
+        if (!rc && differs) rc = adjoint_refuse("the pattern of Q differs from the one given to qpdo_setup (dQx follows the setup's stored entries)");
+        if (rc) { upd_free(d, newMapQ); upd_free(d, newStage); return rc; }
+    }
+    // ---- the checks passed --------------------------------------------------------------------------------------------------------
+    if (newMapQ) { d->mapQ = newMapQ; d->qstage = newStage; }
+    if (wantQ && firstQ) upd_colptr(Q, d->upd_Qp);
+    const long long nnzA = d->At.nnz, nnzQf = d->Qf.nnz, nnzQ = wantQ ? (long long)Q->nnz : 0;
+    if (!d->adj_n) {                                       // the first call: a host allocation, which may wait for earlier device work
+        int rc = upd_alloc(d, &d->adj_n, (size_t)ADJ_N_COUNT * n);
+        if (!rc) rc = upd_alloc(d, &d->adj_m, (size_t)ADJ_M_COUNT * m);
+        if (!rc) rc = upd_alloc(d, &d->adj_flag, (size_t)m);
+        if (rc) return rc;
+        d->adj.scratch_bytes += ((int64_t)ADJ_N_COUNT * n + (int64_t)ADJ_M_COUNT * m) * 8 + (int64_t)m * 4;
+    }
+    if (wantA && !d->adj_dA) { int rc = upd_alloc(d, &d->adj_dA, (size_t)nnzA); if (rc) return rc; d->adj.scratch_bytes += nnzA * 8; }
+    if (wantQ && !d->adj_dQ) { int rc = upd_alloc(d, &d->adj_dQ, (size_t)nnzQ); if (rc) return rc; d->adj.scratch_bytes += nnzQ * 8; }
+    double *xu = d->adj_n + (size_t)ADJ_N_XU * n, *gxs = d->adj_n + (size_t)ADJ_N_GXS * n, *vx = d->adj_n + (size_t)ADJ_N_VX * n,
+           *rx = d->adj_n + (size_t)ADJ_N_RX * n, *t1 = d->adj_n + (size_t)ADJ_N_T1 * n, *t2 = d->adj_n + (size_t)ADJ_N_T2 * n;
+    double *yu = d->adj_m + (size_t)ADJ_M_YU * m, *gys = d->adj_m + (size_t)ADJ_M_GYS * m, *vy = d->adj_m + (size_t)ADJ_M_VY * m,
+           *ry = d->adj_m + (size_t)ADJ_M_RY * m, *wry = d->adj_m + (size_t)ADJ_M_WRY * m, *Av = d->adj_m + (size_t)ADJ_M_AV * m,
+           *a2 = d->adj_m + (size_t)ADJ_M_A2 * m;
+    int *flag = d->adj_flag;
+    const int scaled = d->scaled;
+    const double sc_c = scaled ? d->sc_c : 1.0, sc_cinv = scaled ? d->sc_cinv : 1.0;
+    const int gnm = vgrid(n > m ? n : m);
+    const double nan = __builtin_nan("");
+
+    // ---- what the call overwrites of the workspace is kept (host_probe.inc direct_keep_*), the counters too -----------------------
+    DirectKeep keep;
+    const QdevStats st_keep = d->st;
+    { int rc = direct_keep_save(d, keep, true); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(xu, x, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    if (m) HIPCHK(hipMemcpyAsync(yu, y, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    int rc = 0, code3 = 0, kact = 0;
+    // ---- once per call: the scaled x, the flags, s, W, the factorization --------------------------------------------------------------
+    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
+    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+    LAUNCH(k_adj_scale_x, vgrid(n), n, scaled, (const double *)d->Dinv, (const double *)xu, d->qdiag_valid ? (const double *)d->qdiag : (const double *)nullptr,
+           (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val, t1, d->ctrl);
+    if (m) {
+        launch_spmv(d, d->Ar, t1, EpiStore{Av}, false);
+        LAUNCH(k_adj_classify, adj_grid_rows(m), m, scaled, (const double *)d->E, (const double *)yu, (const double *)d->l, (const double *)d->u, (const double *)Av,
+               (const int *)d->Ar.rp, (const double *)d->Ar.val, flag, a2, d->ctrl);
+    }
+    rc = read_ctrl(d);
+    if (!rc) {
+        const double mqd = nrm_of(d->hctrl, N_C);
+        const double s = mqd > 0.0 ? mqd : 1.0;
+        kact = d->hctrl->cnt[C_MUCH];
+        d->sigma_f = ADJ_SIGMA_REL * s;
+        if (m) LAUNCH(k_adj_weights, vgrid(m), m, s, (const int *)flag, (const double *)a2, d->d);
+        // forced: a fresh factorization of (sigma_f, d), whatever the low-rank and up/downdate routes would do with a kept factor
+        if (kind == 3) rc = band_factor(d, true);
+        else {
+            rc = dense_factor(d);
+            if (!rc) LAUNCH(k_adj_check_pivots, vgrid(n), n, (const double *)d->Dg, d->ctrl);
+        }
+    }
+    // ---- the right-hand sides, one after the other on the one factor ---------------------------------------------------------------------
+    long sweeps_total = 0;
+    for (long r = 0; r < nrhs && !rc; r++) {
+        const double *gxr = gx + (size_t)r * n, *gyr = gy ? gy + (size_t)r * m : nullptr;
+        double *dqr = dq + (size_t)r * n, *dlr = dl + (size_t)r * m, *dur = du + (size_t)r * m;
+        double *dQr = wantQ ? dQx + (size_t)r * nnzQ : nullptr, *dAr = wantA ? dAx + (size_t)r * nnzA : nullptr;
+        int code = code3 ? 3 : 1; long sweep = 0; double rel = nan;
+        if (!code3) {
+            // (gx, gy of this right-hand side travel through rx, ry: both are written by the first sweep's residual before they are read)
+            HIPCHK(hipMemcpyAsync(rx, gxr, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+            if (m && gyr) HIPCHK(hipMemcpyAsync(ry, gyr, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+            LAUNCH(k_adj_ctrl_clear, 1, d->ctrl, 1);
+            LAUNCH(k_adj_rhs, gnm, n, m, scaled, sc_c, (const double *)d->D, (const double *)d->E, (const double *)rx, gyr ? (const double *)ry : (const double *)nullptr,
+                   (const int *)flag, gxs, gys, vx, vy, d->ctrl);
+            for (;; sweep++) {
+                if (sweep) LAUNCH(k_adj_ctrl_clear, 1, d->ctrl, 0);
+                launch_spmv(d, d->Qf, vx, EpiStore{t1}, false);
+                if (m) { launch_spmv(d, d->Ar, vx, EpiStore{Av}, false); launch_spmv(d, d->At, vy, EpiStore{t2}, false); }
+                else HIPCHK(hipMemsetAsync(t2, 0, (size_t)n * 8, d->stream));
+                LAUNCH(k_adj_resid, gnm, n, m, scaled, (const double *)d->Dinv, (const double *)d->Einv, (const double *)gxs, (const double *)t1, (const double *)t2,
+                       (const double *)gys, (const double *)Av, (const int *)flag, (const double *)d->d, rx, ry, wry, d->ctrl);
+                rc = read_ctrl(d); if (rc) break;
+                if (d->hctrl->cnt[C_CHAIN_ERR] || d->hctrl->cnt[C_DINF]) { code3 = 1; code = 3; break; }
+                const double gnorm = fmax(nrm_of(d->hctrl, N_A), nrm_of(d->hctrl, N_B));
+                const double rn = fmax(nrm_of(d->hctrl, N_C) * sc_cinv, nrm_of(d->hctrl, N_D));
+                rel = gnorm > 0.0 ? rn / gnorm : rn;
+                if (!d->hctrl->cnt[C_VIOL] && rn <= tol * gnorm) { code = 0; break; }
+                if (sweep >= max_sweeps) break;
+                if (m) launch_spmv(d, d->At, wry, EpiStore{t2}, false);
+                LAUNCH(k_adj_solve_rhs, vgrid(n), n, (const double *)rx, (const double *)t2, d->rhs);
+                rc = kind == 3 ? band_solve(d) : dense_solve(d); if (rc) break;
+                if (m) launch_spmv(d, d->Ar, d->dx, EpiStore{Av}, false);
+                LAUNCH(k_adj_update, gnm, n, m, (const double *)d->dx, (const double *)Av, (const double *)ry, (const double *)d->d, vx, vy);
+            }
+            if (rc) break;
+            sweeps_total += sweep;
+        }
+        if (status) { status[3 * r] = code; status[3 * r + 1] = code == 3 ? 0 : sweep; status[3 * r + 2] = kact; }
+        if (res) res[r] = code == 0 ? rel : nan;
+        if (code != 0) {
+            for (int j = 0; j < n; j++) dqr[j] = nan;
+            for (int i = 0; i < m; i++) { dlr[i] = nan; dur[i] = nan; }
+            for (long long e = 0; e < nnzQ; e++) dQr[e] = nan;
+            if (wantA) for (long long e = 0; e < nnzA; e++) dAr[e] = nan;
+            continue;
+        }
+        // the unscaled vx into rx, vy into ry (the sweeps are over); dq in t1, dl in wry, du in Av
+        LAUNCH(k_adj_grad_vec, gnm, n, m, scaled, sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)flag, (const double *)vx, (const double *)vy,
+               rx, ry, t1, wry, Av);
+        HIPCHK(hipMemcpyAsync(dqr, t1, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+        if (m) { HIPCHK(hipMemcpyAsync(dlr, wry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipMemcpyAsync(dur, Av, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); }
+        if (wantA && nnzA) {
+            LAUNCH(k_adj_grad_A, adj_grid_rows(n), n, (const int *)d->At.rp, (const int *)d->At.ci, (const int *)flag, (const double *)xu, (const double *)yu,
+                   (const double *)rx, (const double *)ry, d->adj_dA);
+            HIPCHK(hipMemcpyAsync(dAr, d->adj_dA, (size_t)nnzA * 8, hipMemcpyDeviceToHost, d->stream));
+        }
+        if (wantQ && nnzQ) {
+            const bool mapped = Q->stype != 0;
+            if (mapped) HIPCHK(hipMemsetAsync(d->adj_dQ, 0, (size_t)nnzQ * 8, d->stream));
+            if (nnzQf) LAUNCH(k_adj_grad_Q, adj_grid_rows(n), n, (const int *)d->Qf.rp, (const int *)d->Qf.ci, mapped ? (const u32 *)d->mapQ : (const u32 *)nullptr,
+                              (const double *)xu, (const double *)rx, d->adj_dQ);
+            HIPCHK(hipMemcpyAsync(dQr, d->adj_dQ, (size_t)nnzQ * 8, hipMemcpyDeviceToHost, d->stream));
+        }
+        HIPCHK(hipStreamSynchronize(d->stream));
+    }
+    if (!rc && active && m) {
+        if (code3) memset(active, 0, (size_t)m * sizeof(int));
+        else HIPCHK(hipMemcpyAsync(active, flag, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (code3) {               // the latch is cleared as qdev_direct_solve does; nothing is redone
+        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0; d->bc_factored = 0;
+    }
+    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
+    d->ctrl_clean = 0;
+    d->st = st_keep;
+    { int rck = direct_keep_restore(d, keep); if (rck && !rc) rc = rck; }
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    struct timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1);
+    d->adj.calls++; d->adj.factorizations++; d->adj.rhs_total += nrhs; d->adj.sweeps_total += sweeps_total;
+    d->adj.last_seconds = (double)(ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double)(ts1.tv_nsec - ts0.tv_nsec);
+    return 0;
+}

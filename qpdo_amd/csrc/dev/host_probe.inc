@@ -69,20 +69,44 @@ int qdev_bench_dense_factor(QpdoDev *d, int reps, double *avg_seconds, double *c
 // solve (dense_factor(d, true)).  The workspace's weights, sigma_f and dx are put back afterwards; the kept factor stays for the next
 // call and is dropped by the next qdev_begin_solve.  A lost producer of a polling kernel, or a bad band pivot, returns
 // QDEV_DIRECT_LOST with the latch cleared -- never a silent redo.
+// What a call that drives the direct solver on its own (qdev_direct_solve, qdev_adjoint) overwrites of the workspace: the weights d->d,
+// sigma_f, the direction dx and -- with_rhs -- the right-hand side.  direct_keep_save enqueues the copies to the host (the caller
+// synchronises the stream before it changes sigma_f's users or lets the vectors go) and marks the factor such a call leaves as not a
+// solve's own (direct_hook_used: the next qdev_begin_solve drops it); direct_keep_restore puts everything back and waits.
+extern "C++" {
+struct DirectKeep { std::vector<double> d, dx, rhs; double sigma_f = 0.0; bool with_rhs = false; };
+}
+static int direct_keep_save(QpdoDev *d, DirectKeep &k, bool with_rhs) {
+    const int n = d->n, m = d->m;
+    k.d.resize((size_t)(m > 0 ? m : 1)); k.dx.resize((size_t)(n > 0 ? n : 1)); k.with_rhs = with_rhs;
+    if (with_rhs) k.rhs.resize((size_t)(n > 0 ? n : 1));
+    if (m) HIPCHK(hipMemcpyAsync(k.d.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(k.dx.data(), d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (n && with_rhs) HIPCHK(hipMemcpyAsync(k.rhs.data(), d->rhs, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    k.sigma_f = d->sigma_f;
+    d->direct_hook_used = 1;
+    return 0;
+}
+static int direct_keep_restore(QpdoDev *d, const DirectKeep &k) {
+    const int n = d->n, m = d->m;
+    d->sigma_f = k.sigma_f;
+    if (m) HIPCHK(hipMemcpyAsync(d->d, k.d.data(), (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    if (n) HIPCHK(hipMemcpyAsync(d->dx, k.dx.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    if (n && k.with_rhs) HIPCHK(hipMemcpyAsync(d->rhs, k.rhs.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
 int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *rhs, double *x, int flags) {
     HIPCHK(hipSetDevice(d->device));
     if (d->comm.active) return set_err(hipErrorInvalidValue, "direct solve: not for row-partitioned workspaces", __LINE__);
     if (d->linsolve != 1 && d->linsolve != 3) return set_err(hipErrorInvalidValue, "direct solve: the workspace's solver is not a direct one (dense or band)", __LINE__);
     const int n = d->n, m = d->m;
-    std::vector<double> d_keep((size_t)(m > 0 ? m : 1)), dx_keep((size_t)(n > 0 ? n : 1));
-    if (m) HIPCHK(hipMemcpyAsync(d_keep.data(), d->d, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
-    if (n) HIPCHK(hipMemcpyAsync(dx_keep.data(), d->dx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    DirectKeep keep;
+    { int rck = direct_keep_save(d, keep, false); if (rck) return rck; }
     if (m) HIPCHK(hipMemcpyAsync(d->d, dw, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
     if (n) HIPCHK(hipMemcpyAsync(d->rhs, rhs, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
-    const double sigma_keep = d->sigma_f;
     d->sigma_f = sigma;
-    d->direct_hook_used = 1;
     LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
     if (d->ud_cap) LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_UD_REJECT, 0);      // (a latch left by a call that ended early is not this call's)
     const bool refactor = (flags & 1) != 0, carry = (flags & 2) != 0;
@@ -106,10 +130,7 @@ int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *
         LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
         d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0; d->bc_factored = 0;
     }
-    d->sigma_f = sigma_keep;
-    if (m) HIPCHK(hipMemcpyAsync(d->d, d_keep.data(), (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
-    if (n) HIPCHK(hipMemcpyAsync(d->dx, dx_keep.data(), (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
+    { int rck = direct_keep_restore(d, keep); if (rck) return rck; }
     if (rc) return rc;
     if (lost) {
         snprintf(g_err, sizeof(g_err), "direct solve: %s", d->linsolve == 3 ? (d->bc_r > 0 ? "the band factorization or the coupling rows' k x k system met a pivot that is not a positive finite number, or the solve missed its residual check"

@@ -45,6 +45,49 @@ static int pattern_error(const char *which) {
     return -1;
 }
 
+// The first time a caller's Q is seen (qdev_update_matrices, qdev_adjoint with dQx): its (p, i) against the workspace's full CSR(Q) on the
+// device, *differs |= 1 where the pattern is another one.  stype 0: Qf IS the caller's CSC arrays.  stype +-1: setup's symmetric
+// expansion is run again with index payloads, which also gives *mapQ (per entry of Qf, the caller's position of the stored entry it
+// came from) and *stage (room for the caller's stored values); both are long-lived allocations that the caller adopts, or hands to
+// upd_free when the call is refused.  Writes nothing of the workspace.
+static int upd_first_Q(QpdoDev *d, TempAllocs &tmp, const QdevCsc *Q, int *differs, u32 **mapQ, double **stage) {
+    const int n = d->n;
+    int rc = 0;
+    if (Q->stype == 0) {
+        DevCsr P;
+        if (Q->nnz != d->Qf.nnz) { *differs |= 1; return 0; }
+        rc = upload_csc_as_csr_of_transpose(d, tmp, &P, Q, true, false);
+        if (!rc) rc = upd_compare(d, tmp, P.rp, d->Qf.rp, (long long)n + 1, differs);
+        if (!rc) rc = upd_compare(d, tmp, P.ci, d->Qf.ci, Q->nnz, differs);
+        return rc;
+    }
+    DevCsr S, R; int *cnt = nullptr, *tsum = nullptr, *orp = nullptr, *oci = nullptr; u32 *permR = nullptr, *iota = nullptr;
+    rc = upload_csc_as_csr_of_transpose(d, tmp, &S, Q, true, false);
+    if (!rc && (tmp.get(&permR, (size_t)S.nnz) || tmp.get(&iota, (size_t)S.nnz) || tmp.get(&cnt, (size_t)n + 1) || tmp.get(&tsum, (size_t)scan_tiles(n)) || tmp.get(&orp, (size_t)n + 1)))
+        rc = set_err(hipErrorOutOfMemory, "update scratch", __LINE__);
+    if (!rc) rc = dev_transpose(d, tmp, S, &R, true, permR);
+    int total = 0;
+    if (!rc) {
+        hipLaunchKernelGGL(k_sym_count, dim3(vgrid(n)), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const int *)S.rp, (const int *)S.ci, cnt);
+        dev_scan(d, cnt, n, orp, orp + n, tsum);
+        hipError_t e = hipMemcpyAsync(&total, orp + n, sizeof(int), hipMemcpyDeviceToHost, d->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        if (e != hipSuccess) rc = set_err(e, "symmetric expansion", __LINE__);
+    }
+    if (!rc && (long long)total != d->Qf.nnz) { *differs |= 1; return 0; }
+    if (!rc && tmp.get(&oci, (size_t)total)) rc = set_err(hipErrorOutOfMemory, "update scratch", __LINE__);
+    if (!rc) rc = upd_alloc(d, mapQ, (size_t)total);
+    if (!rc) rc = upd_alloc(d, stage, (size_t)S.nnz);
+    if (!rc) {
+        hipLaunchKernelGGL(k_iota_u32, dim3(vgrid(S.nnz)), dim3(BLK), 0, d->stream, (long long)S.nnz, iota);
+        hipLaunchKernelGGL(k_sym_fill<u32>, dim3(2048), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const u32 *)permR,
+                           (const int *)S.rp, (const int *)S.ci, (const u32 *)iota, (const int *)orp, oci, *mapQ);
+        rc = upd_compare(d, tmp, orp, d->Qf.rp, (long long)n + 1, differs);
+    }
+    if (!rc) rc = upd_compare(d, tmp, oci, d->Qf.ci, total, differs);
+    return rc;
+}
+
 // Every piece of workspace state that outlives one solve, back to its value after create_tail + qdev_configure.  The pattern-only
 // decisions of setup stay (linsolve's automatic choice, band_b, max_row_nnz_A, the slab tables: band_detect and k_max_row_len read rp / ci
 // only); buffers whose contents are only read under a validity flag keep their contents (the dense / band factors, the Woodbury slots).
@@ -127,41 +170,8 @@ int qdev_update_matrices(QpdoDev *d, const QdevCsc *A, const QdevCsc *Q, const d
         }
         const bool firstQ = Q && d->upd_Qp.empty();
         if (!rc && Q && !firstQ && !upd_colptr_same(Q, d->upd_Qp)) rc = pattern_error("Q");
-        if (!rc && firstQ && Q->stype == 0) {                  // full storage: Qf IS the caller's CSC arrays
-            DevCsr P;
-            if (Q->nnz != d->Qf.nnz) rc = pattern_error("Q");
-            if (!rc) rc = upload_csc_as_csr_of_transpose(d, tmp, &P, Q, true, false);
-            if (!rc) rc = upd_compare(d, tmp, P.rp, d->Qf.rp, (long long)n + 1, &differs);
-            if (!rc) rc = upd_compare(d, tmp, P.ci, d->Qf.ci, Q->nnz, &differs);
-            if (!rc && differs) rc = pattern_error("Q");
-        }
-        if (!rc && firstQ && Q->stype != 0) {                  // one stored triangle: setup's symmetric expansion with index payloads
-            DevCsr S, R; int *cnt = nullptr, *tsum = nullptr, *orp = nullptr, *oci = nullptr; u32 *permR = nullptr, *iota = nullptr;
-            rc = upload_csc_as_csr_of_transpose(d, tmp, &S, Q, true, false);
-            if (!rc && (tmp.get(&permR, (size_t)S.nnz) || tmp.get(&iota, (size_t)S.nnz) || tmp.get(&cnt, (size_t)n + 1) || tmp.get(&tsum, (size_t)scan_tiles(n)) || tmp.get(&orp, (size_t)n + 1)))
-                rc = set_err(hipErrorOutOfMemory, "update scratch", __LINE__);
-            if (!rc) rc = dev_transpose(d, tmp, S, &R, true, permR);
-            int total = 0;
-            if (!rc) {
-                hipLaunchKernelGGL(k_sym_count, dim3(vgrid(n)), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const int *)S.rp, (const int *)S.ci, cnt);
-                dev_scan(d, cnt, n, orp, orp + n, tsum);
-                hipError_t e = hipMemcpyAsync(&total, orp + n, sizeof(int), hipMemcpyDeviceToHost, d->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-                if (e != hipSuccess) rc = set_err(e, "symmetric expansion", __LINE__);
-            }
-            if (!rc && (long long)total != d->Qf.nnz) rc = pattern_error("Q");
-            if (!rc && tmp.get(&oci, (size_t)total)) rc = set_err(hipErrorOutOfMemory, "update scratch", __LINE__);
-            if (!rc) rc = upd_alloc(d, &newMapQ, (size_t)total);
-            if (!rc) rc = upd_alloc(d, &newStage, (size_t)S.nnz);
-            if (!rc) {
-                hipLaunchKernelGGL(k_iota_u32, dim3(vgrid(S.nnz)), dim3(BLK), 0, d->stream, (long long)S.nnz, iota);
-                hipLaunchKernelGGL(k_sym_fill<u32>, dim3(2048), dim3(BLK), 0, d->stream, n, Q->stype, (const int *)R.rp, (const int *)R.ci, (const u32 *)permR,
-                                   (const int *)S.rp, (const int *)S.ci, (const u32 *)iota, (const int *)orp, oci, newMapQ);
-                rc = upd_compare(d, tmp, orp, d->Qf.rp, (long long)n + 1, &differs);
-            }
-            if (!rc) rc = upd_compare(d, tmp, oci, d->Qf.ci, total, &differs);
-            if (!rc && differs) rc = pattern_error("Q");
-        }
+        if (!rc && firstQ) rc = upd_first_Q(d, tmp, Q, &differs, &newMapQ, &newStage);
+        if (!rc && firstQ && differs) rc = pattern_error("Q");
         if (!rc) { hipError_t e = hipGetLastError(); if (e != hipSuccess) rc = set_err(e, "update checks", __LINE__); }
         tmp.release(d->stream);
         h2d_staging_release(d);

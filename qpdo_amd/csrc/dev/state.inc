@@ -195,6 +195,10 @@ struct QpdoDev {
     u32 *mapA = nullptr, *mapQ = nullptr;         // mapA[k]: CSC position of entry k of CSR(A); mapQ[k]: the caller's position of entry k of Qf
     double *qstage = nullptr;                     // the caller's stored Q values (stype +-1), gathered through mapQ
     std::vector<long long> upd_Ap, upd_Qp;        // column pointers whose pattern passed the device check (later calls compare these)
+    // qpdo_amd_adjoint (dev/adjoint.inc): the call's own work vectors (6 n + 7 m doubles and m flags, allocated by the first call), the
+    // per-entry outputs (allocated by the first call that asks for them) and its counters
+    double *adj_n = nullptr, *adj_m = nullptr, *adj_dA = nullptr, *adj_dQ = nullptr; int *adj_flag = nullptr;
+    QdevAdjointStats adj{};
     // what qdev_configure decided; a solve may change these (fallbacks, hybrid), qpdo_amd_update_matrices puts them back
     struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, ud_cap, deflate, pcg_maxit, band_b, bc_r; } cfg{};
 };

@@ -42,6 +42,8 @@ struct QPDOBackend {
      * bit) and the shape of the matrices given to qpdo_setup */
     c_float *q_raw, *l_raw, *u_raw;
     int q_stype; int64_t q_nnz, a_nnz;
+    int solved_last;              /* the most recent state-changing call was qpdo_solve (set there; cleared by qpdo_warm_start, qpdo_update_q,
+                                   * qpdo_update_bounds, qpdo_amd_update_matrices): what qpdo_amd_adjoint asks before it reads the solution */
 };
 
 #define c_max(a, b) (((a) > (b)) ? (a) : (b))
@@ -459,6 +461,7 @@ fail:
 
 /* ---- qpdo_warm_start (reference src/qpdo.c:217-299) --------------------------------------- */
 void qpdo_warm_start(QPDOWorkspace *work, c_float *x_warm_start, c_float *y_warm_start) {
+    work->chol->solved_last = 0;
     work->sigma = work->settings->sigma_init;
     if (work->info->status_val != QPDO_UNSOLVED) work->info->setup_time = 0;
     tic(work->timer);
@@ -588,6 +591,7 @@ void qpdo_solve(QPDOWorkspace *work) {
     const QPDOSettings *s;
     if (work->settings->verbose) print_header();
     if (!work->initialized) { be->auto_ws = 1; qpdo_warm_start(work, NULL, NULL); be->auto_ws = 0; }
+    be->solved_last = 1;
     s = work->settings;
     const int prox = (int)s->proximal;
     work->eps_in = s->eps_abs_in;
@@ -791,6 +795,7 @@ void qpdo_update_settings(QPDOWorkspace *work, const QPDOSettings *settings) {
 /* ---- qpdo_update_bounds (reference src/qpdo.c:522-544) ------------------------------------------ */
 void qpdo_update_bounds(QPDOWorkspace *work, const c_float *l, const c_float *u) {
     size_t m = work->data->m;
+    work->chol->solved_last = 0;
     if (l != NULL && u != NULL) {
         for (size_t j = 0; j < m; j++) {
             if (l[j] > u[j]) {
@@ -813,6 +818,7 @@ void qpdo_update_bounds(QPDOWorkspace *work, const c_float *l, const c_float *u)
 void qpdo_update_q(QPDOWorkspace *work, const c_float *q) {
     size_t n = work->data->n;
     QpdoDev *dev = work->chol->dev;
+    work->chol->solved_last = 0;
     memcpy(work->data->q, q, n * sizeof(c_float));
     memcpy(work->chol->q_raw, q, n * sizeof(c_float));
     if (work->settings->scaling) {
@@ -854,6 +860,7 @@ int qpdo_amd_update_matrices(QPDOWorkspace *work, const cholmod_sparse *Q, const
     /* the device checks the pattern (and refuses a row-partitioned workspace) before it writes anything */
     const int rc = qdev_update_matrices(be->dev, A ? &a : NULL, Q ? &qq : NULL, be->q_raw, be->l_raw, be->u_raw);
     if (rc) return rc;
+    be->solved_last = 0;
     /* from here on, as qpdo_setup: the host mirrors, the scaling, the fused resident, the post-setup scalars */
     memcpy(work->data->q, be->q_raw, n * sizeof(c_float));
     if (m) { memcpy(work->data->l, be->l_raw, m * sizeof(c_float)); memcpy(work->data->u, be->u_raw, m * sizeof(c_float)); }
@@ -921,6 +928,51 @@ int qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, c
 }
 int qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count) {
     return qdev_download_factor(work->chol->dev, which, dst, count) ? -1 : 0;
+}
+/* ---- qpdo_amd_adjoint (include/qpdo_amd_ext.h): the argument checks, in the header's order, before the backend is touched
+ * (tests/adjoint_args_driver.c); then the state checks; the solver kind and the pattern of Q are the backend's (dev/adjoint.inc) */
+static int adjoint_refuse(const char *msg) {
+    char buf[240];
+    snprintf(buf, sizeof(buf), "qpdo_amd_adjoint: %s", msg);
+    qdev_set_error(buf);
+    return -1;
+}
+int qpdo_amd_adjoint(QPDOWorkspace *work, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du, const cholmod_sparse *Q,
+                     double *dQx, double *dAx, int *active, long *status, double *res, double tol, long max_sweeps) {
+    if (nrhs < 1) return adjoint_refuse("nrhs must be at least 1");
+    if (!(tol > 0.0) || !(tol <= 1.7976931348623157e308)) return adjoint_refuse("tol is not a positive finite number");
+    if (max_sweeps < 1) return adjoint_refuse("max_sweeps must be at least 1");
+    if (!gx) return adjoint_refuse("gx is NULL");
+    if (!dq) return adjoint_refuse("dq is NULL");
+    if (!dl) return adjoint_refuse("dl is NULL");
+    if (!du) return adjoint_refuse("du is NULL");
+    if (dQx && !Q) return adjoint_refuse("dQx needs Q (the matrix in the pattern given to qpdo_setup)");
+    if (!work || !work->chol || !work->chol->dev || !work->data || !work->info || !work->solution) return adjoint_refuse("NULL workspace");
+    struct QPDOBackend *be = work->chol;
+    const size_t n = work->data->n;
+    if (work->info->status_val != QPDO_SOLVED) return adjoint_refuse("the workspace's status is not QPDO_SOLVED (never solved, infeasible, out of passes or an error): there is no solution to differentiate");
+    if (!be->solved_last)
+        return adjoint_refuse("the most recent state-changing call was not a solve (qpdo_warm_start, qpdo_update_q, qpdo_update_bounds or qpdo_amd_update_matrices since the last qpdo_solve): call qpdo_solve first");
+    if (qdev_adjoint_check_kind(be->dev)) return -1;
+    QdevCsc qq;
+    if (dQx) {
+        if (!sparse_ok(Q)) return adjoint_refuse("unsupported sparse storage of Q");
+        if (Q->nrow != n || Q->ncol != n) return adjoint_refuse("Q is not n x n");
+        if (Q->stype != be->q_stype) return adjoint_refuse("the pattern of Q differs from the one given to qpdo_setup (another stype)");
+        if (idx_at(Q->p, Q->itype, (int64_t)n) != be->q_nnz) return adjoint_refuse("the pattern of Q differs from the one given to qpdo_setup (another number of entries)");
+        QdevCsc v = {(int32_t)Q->nrow, (int32_t)Q->ncol, be->q_nnz, Q->itype, Q->p, Q->i, (const double *)Q->x, Q->stype};
+        qq = v;
+    }
+    return qdev_adjoint(be->dev, work->solution->x, work->solution->y, nrhs, gx, gy, dq, dl, du, dQx ? &qq : NULL, dQx, dAx, active, status, res, tol, max_sweeps) ? -1 : 0;
+}
+int qpdo_amd_get_adjoint_stats(const QPDOWorkspace *work, QPDOAmdAdjointStats *out) {
+    if (!work || !work->chol || !work->chol->dev) { qdev_set_error("qpdo_amd_get_adjoint_stats: NULL workspace"); return -1; }
+    if (!out) { qdev_set_error("qpdo_amd_get_adjoint_stats: NULL out"); return -1; }
+    QdevAdjointStats st;
+    qdev_get_adjoint_stats(work->chol->dev, &st);
+    out->calls = (long)st.calls; out->rhs_total = (long)st.rhs_total; out->factorizations = (long)st.factorizations;
+    out->sweeps_total = (long)st.sweeps_total; out->scratch_bytes = (long)st.scratch_bytes; out->last_seconds = st.last_seconds;
+    return 0;
 }
 /* the pointer checks of the two PCG test entries are made here, before the backend is touched (tests/pcg_probe_args_driver.c) */
 int qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, const double *v, double *out, int mode, double *info) {

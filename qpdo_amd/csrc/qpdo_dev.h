@@ -220,6 +220,18 @@ int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host);
 #define QDEV_DIRECT_LOST (-9)
 int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *rhs, double *x, int flags);
 int qdev_download_factor(QpdoDev *d, int which, double *dst, long count);
+/* the adjoint of the last solve on the workspace's direct solver (qpdo_amd_adjoint, dev/adjoint.inc).  x, y: the UNSCALED solution the solve
+ * delivered; Q: the caller's Q in the setup's pattern, needed (and looked at) only with dQx.  The argument and state checks are the
+ * caller's (qpdo_api.c); the solver kind and the pattern of Q are checked here before anything is launched or written.  Returns 0 (the
+ * codes are in status), or nonzero with qdev_last_error() set. */
+typedef struct {
+    int64_t calls, rhs_total, factorizations, sweeps_total, scratch_bytes;
+    double last_seconds;
+} QdevAdjointStats;
+int qdev_adjoint(QpdoDev *d, const double *x, const double *y, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du,
+                 const QdevCsc *Q, double *dQx, double *dAx, int *active, long *status, double *res, double tol, long max_sweeps);
+int qdev_get_adjoint_stats(QpdoDev *d, QdevAdjointStats *out);
+int qdev_adjoint_check_kind(QpdoDev *d);      /* the solver-kind check alone (the caller's Q checks come behind it) */
 /* the PCG path as single steps (tests; qpdo_amd_pcg_probe, dev/host_probe.inc): mode 0 one K product after build_compact, mode 1 one
  * pcg_solve; and the compact structures the last of either left (qpdo_amd_download_compact).  info: QDEV_PCG_INFO_LEN doubles. */
 #define QDEV_PCG_NOT_CONVERGED (-7)

@@ -69,4 +69,5 @@ extern "C" {
 #include "dev/host_step.inc"
 #include "dev/host_probe.inc"
 #include "dev/host_update.inc"
+#include "dev/adjoint.inc"
 }  // extern "C"

@@ -123,7 +123,14 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_sync", "qpdo_amd_slab_trip_shape",
                "qpdo_amd_fleet_packed_matrix_layout", "qpdo_amd_fleet_get_packed_matrix_layout", "qpdo_amd_fleet_update_matrices_dev",
                "qpdo_amd_fleet_adjoint_dev", "qpdo_amd_fleet_get_adjoint_stats",
-               "qpdo_amd_fleet_adjoint_multi_dev", "qpdo_amd_fleet_tangent_dev", "qpdo_amd_fleet_rhs_group", "qpdo_amd_fleet_get_sensitivity_stats"]
+               "qpdo_amd_fleet_adjoint_multi_dev", "qpdo_amd_fleet_tangent_dev", "qpdo_amd_fleet_rhs_group", "qpdo_amd_fleet_get_sensitivity_stats",
+               "qpdo_amd_adjoint", "qpdo_amd_get_adjoint_stats"]
+
+
+class AdjointStats(C.Structure):
+    """QPDOAmdAdjointStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("calls", C.c_long), ("rhs_total", C.c_long), ("factorizations", C.c_long), ("sweeps_total", C.c_long),
+                ("scratch_bytes", C.c_long), ("last_seconds", C.c_double)]
 
 
 class FleetStats(C.Structure):
@@ -205,6 +212,12 @@ def lib():
         L.qpdo_amd_download_compact.restype = C.c_int
         L.qpdo_amd_update_matrices.argtypes = [W, C.POINTER(CholmodSparse), C.POINTER(CholmodSparse)]
         L.qpdo_amd_update_matrices.restype = C.c_int
+        if hasattr(L, "qpdo_amd_adjoint"):                  # (absent from an older build named by QPDO_AMD_LIB: calling it there raises)
+            L.qpdo_amd_adjoint.argtypes = [W, C.c_long, dp, dp, dp, dp, dp, C.POINTER(CholmodSparse), dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_long), dp,
+                                           C.c_double, C.c_long]
+            L.qpdo_amd_adjoint.restype = C.c_int
+            L.qpdo_amd_get_adjoint_stats.argtypes = [W, C.POINTER(AdjointStats)]
+            L.qpdo_amd_get_adjoint_stats.restype = C.c_int
         L.qpdo_amd_dist_config.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qpdo_amd_dist_unique_id.argtypes = [C.c_void_p]
         L.qpdo_amd_solve_batch.restype = C.c_long
@@ -409,6 +422,7 @@ class QPDO:
         self._w, self.n, self.m = w, n, m
         # the pattern as handed over (sorted CSC; keep[] holds Q's p, i, x then A's): update_matrices projects onto it
         self._Qstype, self._Qpat, self._Apat = Qstype, (keep[3], keep[4]), (keep[6], keep[7])
+        self._Qview, self._Qview_keep = Qs, keep[3:6]      # (the header over Q's arrays as handed over: adjoint passes it with dQx)
         return self
 
     def update_matrices(self, Q=None, A=None):
@@ -553,6 +567,52 @@ class QPDO:
             msg = (lib().qpdo_amd_last_error() or b"").decode()
             raise (LostProducer if rc == DIRECT_LOST else RuntimeError)("direct_solve: %s" % msg)
         return x
+
+    def adjoint(self, gx, gy=None, matrices=False, tol=1e-9, max_sweeps=20):
+        """The gradients of a loss L(x, y) of the last solve's solution w.r.t. q, l, u (and, matrices=True, the stored values of Q and A)
+        from gx = dL/dx and gy = dL/dy (None: zero), through the workspace's direct solver (qpdo_amd_adjoint, include/qpdo_amd_ext.h).
+        gx: (n,) or (R, n), gy: (m,) / (R, m): R right-hand sides on ONE factorization; the outputs carry the same leading R.  Returns
+        dict(dq, dl, du, dQ_values, dA_values (None without matrices), active (m,) int32, status (3,) / (R, 3) int64: code, sweeps,
+        active rows, residual).  A right-hand side whose code is not 0 holds NaN.  A refused call raises RuntimeError with the reason."""
+        def arr(name, a, length):
+            if not isinstance(a, np.ndarray):
+                raise ValueError("%s: expected a numpy array, got %s" % (name, type(a).__name__))
+            if a.dtype != np.float64:
+                raise ValueError("%s: expected dtype float64, got %s" % (name, a.dtype))
+            if a.ndim not in (1, 2) or a.shape[-1] != length:
+                raise ValueError("%s: expected shape (%d,) or (R, %d), got %s" % (name, length, length, a.shape))
+            return np.ascontiguousarray(a)
+        gx = arr("gx", gx, self.n)
+        single = gx.ndim == 1
+        R = 1 if single else gx.shape[0]
+        if R < 1:
+            raise ValueError("gx: expected at least one right-hand side")
+        if gy is not None:
+            gy = arr("gy", gy, self.m)
+            if gy.shape != gx.shape[:-1] + (self.m,):
+                raise ValueError("gy: expected shape %s to go with gx, got %s" % (gx.shape[:-1] + (self.m,), gy.shape))
+        if not self._w:
+            raise RuntimeError("adjoint: no workspace (call setup first)")
+        nq, na = len(self._Qview_keep[2]), len(self._Apat[1])
+        dq, dl, du = np.empty((R, self.n)), np.empty((R, self.m)), np.empty((R, self.m))
+        dQ, dA = (np.empty((R, nq)), np.empty((R, na))) if matrices else (None, None)
+        active, status, res = np.zeros(self.m, np.int32), np.zeros((R, 3), np.int64), np.empty(R)
+        rc = lib().qpdo_amd_adjoint(self._w, R, _as_dp(gx), _as_dp(gy), _as_dp(dq), _as_dp(dl), _as_dp(du), C.byref(self._Qview) if matrices else None,
+                                    _as_dp(dQ), _as_dp(dA), active.ctypes.data_as(C.POINTER(C.c_int)), status.ctypes.data_as(C.POINTER(C.c_long)),
+                                    _as_dp(res), float(tol), int(max_sweeps))
+        if rc:
+            raise RuntimeError("adjoint: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+        out = dict(dq=dq, dl=dl, du=du, dQ_values=dQ, dA_values=dA, status=status, residual=res)
+        if single:
+            out = {k: (None if v is None else v[0]) for k, v in out.items()}
+        out["active"] = active
+        return out
+
+    def adjoint_stats(self):
+        s = AdjointStats()
+        if lib().qpdo_amd_get_adjoint_stats(self._w, C.byref(s)):
+            raise RuntimeError("adjoint_stats: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+        return {f: getattr(s, f) for f, _ in AdjointStats._fields_}
 
     def _pcg_probe(self, dw, sigma, v, mode):
         dw = np.ascontiguousarray(dw, np.float64)

@@ -7,7 +7,17 @@
 
 Forward is the fleet's control step  update_matrices_device -> update_device -> warm_start_last_device -> solve_device  on torch's current
 stream; backward is ONE adjoint_device call on the current stream (qpdo_amd_fleet_adjoint_dev, include/qpdo_amd_ext.h).  Nothing waits for the
-host.  The fleet holds ONE solution: a backward belongs to the most recent forward, and one that comes after the fleet has moved on raises."""
+host.  The fleet holds ONE solution: a backward belongs to the most recent forward, and one that comes after the fleet has moved on raises.
+
+One QP of any size the direct solvers take (dense LDL', band LDL') goes through WorkspaceQP, over solver.QPDO's host calls:
+
+    qp = solver.QPDO().setup(Q, q, A, l, u)
+    layer = WorkspaceQP(qp)
+    x, y = layer(q, l, u, Q_values, A_values)       # tensors on any device; the values in the setup's stored pattern
+    loss(x, y).backward()
+
+Forward is  update_matrices -> update_bounds -> update_q -> (warm start from the previous x, y) -> solve,  backward ONE qpdo_amd_adjoint call;
+the tensors travel through the host, since that API is a host API."""
 import torch
 
 ON_FAILURE = ("nan", "zero")
@@ -142,3 +152,87 @@ class FleetQP(torch.nn.Module):
                                              max_sweeps=max_sweeps)
         self.vjp_status = out["status"].clone()
         return self._failed(out, dict(dq="dq", dl="dl", du="du", dQ_values="dQ_values", dA_values="dA_values"))
+
+
+class _WorkspaceQPFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, layer, q, l, u, Q_values, A_values):
+        import numpy as np
+        import scipy.sparse as sp
+        qp = layer.qp
+
+        def host(t):
+            return None if t is None else np.ascontiguousarray(t.detach().cpu().numpy(), np.float64)
+
+        def mat(vals, pat, shape):
+            return None if vals is None else sp.csc_matrix((host(vals), pat[1], pat[0]), shape=shape)
+        if Q_values is not None or A_values is not None:
+            qp.update_matrices(Q=mat(Q_values, qp._Qpat, (qp.n, qp.n)), A=mat(A_values, qp._Apat, (qp.m, qp.n)))
+        if l is not None or u is not None:
+            qp.update_bounds(host(l), host(u))
+        if q is not None:
+            qp.update_q(host(q))
+        if layer.warm_start_last and layer._last is not None:
+            qp.warm_start(*layer._last)
+        r = qp.solve()
+        layer.serial += 1
+        layer.status = r["info"]["status_val"]
+        layer._last = (r["x"], r["y"]) if np.isfinite(r["x"]).all() and np.isfinite(r["y"]).all() else None
+        ref = next((t for t in (q, l, u, Q_values, A_values) if t is not None), None)
+        ctx.layer, ctx.serial = layer, layer.serial
+        ctx.device, ctx.solved, ctx.sizes = (None if ref is None else ref.device), layer.status == 1, (len(qp._Qview_keep[2]), len(qp._Apat[1]))
+        to = dict(dtype=torch.float64, device=ref.device) if ref is not None else dict(dtype=torch.float64)
+        return torch.from_numpy(r["x"]).to(**to), torch.from_numpy(r["y"]).to(**to)
+
+    @staticmethod
+    def backward(ctx, gx, gy):
+        import numpy as np
+        layer, qp = ctx.layer, ctx.layer.qp
+        if layer.serial != ctx.serial:
+            raise RuntimeError("WorkspaceQP.backward: the workspace has been solved again since this forward (solve %d, now %d); a workspace "
+                               "holds one solution -- call backward before the next forward" % (ctx.serial, layer.serial))
+        need = ctx.needs_input_grad[1:]                      # q, l, u, Q_values, A_values
+        matrices = bool(need[3] or need[4])
+        gxh = np.zeros(qp.n) if gx is None else np.ascontiguousarray(gx.detach().cpu().numpy(), np.float64)
+        gyh = None if gy is None else np.ascontiguousarray(gy.detach().cpu().numpy(), np.float64)
+        if ctx.solved:
+            out = qp.adjoint(gxh, gyh, matrices=matrices, tol=layer.tol, max_sweeps=layer.max_sweeps)
+        else:
+            # the forward's solve did not end with QPDO_SOLVED (out of passes, infeasible): no adjoint call (the library refuses such a
+            # workspace); the gradients are what FleetQP gives for an item with code 2 -- NaN, or zeros under on_failure = "zero"
+            nan = lambda k: np.full(k, np.nan)
+            out = dict(dq=nan(qp.n), dl=nan(qp.m), du=nan(qp.m), dQ_values=nan(ctx.sizes[0]), dA_values=nan(ctx.sizes[1]), status=np.array([2, 0, 0], np.int64))
+        layer.adjoint_status = out["status"].copy()
+        grads = []
+        for want, key in zip(need, ("dq", "dl", "du", "dQ_values", "dA_values")):
+            if not want:
+                grads.append(None)
+                continue
+            g = out[key]
+            if layer.on_failure == "zero" and out["status"][0] != 0:
+                g = np.zeros_like(g)
+            t = torch.from_numpy(np.ascontiguousarray(g))
+            grads.append(t.to(ctx.device) if ctx.device is not None else t)
+        return (None, *grads)
+
+
+class WorkspaceQP(torch.nn.Module):
+    """x, y = layer(q, l, u, Q_values=None, A_values=None): the solution of ONE QP held by a solver.QPDO workspace as a differentiable function
+    of its data, at every size the workspace's direct solvers take (QPDO_LINSOLVE=dense or band; see qpdo_amd_adjoint for what is refused).
+    qp: a solver.QPDO after setup.  q, l, u: tensors of n / m / m entries; Q_values / A_values: the stored values in the setup's pattern
+    (qp._Qpat / qp._Apat: CSC column pointers and row indices; Q in the stype given to setup).  None inputs are left as they are in the
+    workspace.  warm_start_last: start every solve from the previous finite solution.  on_failure: what the gradients hold when the adjoint
+    was not delivered -- code 1 (not accepted), 3 (bad pivot), or 2: the forward's solve did not end with QPDO_SOLVED, in which case no
+    adjoint call is made -- : "nan" or "zero", as in FleetQP.  layer.status: status_val of the last forward;
+    layer.adjoint_status: (code, sweeps, active rows) of the last backward.  The workspace holds ONE solution: a backward that comes after
+    another forward raises."""
+
+    def __init__(self, qp, warm_start_last=True, on_failure="nan", tol=1e-9, max_sweeps=20):
+        super().__init__()
+        if on_failure not in ON_FAILURE:
+            raise ValueError("on_failure: expected one of %r, got %r" % (ON_FAILURE, on_failure))
+        self.qp, self.warm_start_last, self.on_failure, self.tol, self.max_sweeps = qp, bool(warm_start_last), on_failure, float(tol), int(max_sweeps)
+        self.status, self.adjoint_status, self.serial, self._last = None, None, 0, None
+
+    def forward(self, q=None, l=None, u=None, Q_values=None, A_values=None):
+        return _WorkspaceQPFunction.apply(self, q, l, u, Q_values, A_values)
