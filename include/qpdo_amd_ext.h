@@ -393,6 +393,66 @@ int  qpdo_amd_adjoint(QPDOWorkspace *work, long nrhs,
                       int *active /* m int32 or NULL */, long *status /* nrhs x 3 or NULL */, double *res /* nrhs or NULL */,
                       double tol, long max_sweeps);
 int  qpdo_amd_get_adjoint_stats(const QPDOWorkspace *work, QPDOAmdAdjointStats *out);
+/* ---- the TANGENT of a workspace's last solve: the first-order change (dx, dy) of the solution for a change of q, l, u, Q, A -----------------
+ * The contract of qpdo_amd_fleet_tangent_dev (below), applied to ONE workspace on its own direct solver, at every size qpdo_amd_adjoint
+ * takes: the advanced-step update x + dx of an MPC controller from one factorization and a few triangular solves instead of a re-solve, or
+ * a few columns of dx / dtheta without the n right-hand sides the adjoint would need.  All pointers are HOST pointers.  Arrays are
+ * right-hand-side major: right-hand side r of an array whose per-RHS length is L (n, m, nnz(Q as stored), nnz(A)) starts at r * L.  All
+ * quantities are the caller's UNSCALED ones; x, y are those in work->solution (uploaded by the call, as the adjoint does).
+ * ACTIVE SET  the rule, the flags and k are exactly those qpdo_amd_adjoint delivers after the same solve (one classification code for both
+ *          calls); `active` is ONE array of m int32.  S: the flagged rows; b = u on +1 rows and l on -1 rows.
+ * SYSTEM   Given a perturbation (tq, tl, tu, tQ, tA) of the data:
+ *              [ Q    A_S' ] [dx  ]   [ -(tq + tQ x + tA_S' y_S) ]
+ *              [ A_S  0    ] [dy_S] = [  tb_S - tA_S x           ]
+ *          dy_i is an exact +0.0 off S.  A NULL array is a zero perturbation; all five NULL is refused ("no tangent passed").  tQx follows
+ *          the order of Q->x as stored at setup, tAx the order of data->A->x at setup.  tQ acts as the symmetric matrix its stored entries
+ *          stand for: under stype +-1 an off-diagonal stored entry (a, b) contributes to rows a and b and an entry in the ignored triangle
+ *          contributes nothing; under stype 0 the caller passes a SYMMETRIC perturbation (as the solver reads a stype-0 Q as symmetric) and
+ *          row a is evaluated from the stored entries of COLUMN a.  Q is needed only with tQx and is looked at as qpdo_amd_adjoint looks at
+ *          it with dQx (the first such call of either kind, or of qpdo_amd_update_matrices, compares the pattern on the device and builds
+ *          the map).  A workspace with m = 0 solves Q dx = -(tq + tQ x).
+ * IGNORED  tl on a row that is not -1, tu on a row that is not +1 and tAx on an unflagged row are ignored and may hold anything, NaN
+ *          included: the kernels branch past them (they are not multiplied by zero).
+ * RIGHT-HAND SIDE  formed in fp64 on the device from the unscaled x, y, by 16 lanes per row with a FIXED split and fold.  Component rx_j:
+ *          lane L (0 .. 15) adds, into one partial sum that starts at 0, the products of the entries L, L + 16, ... of row j of tQ in
+ *          stored order (stype 0: the stored entries of column j; stype +-1: row j of the symmetric image, ascending columns) and then
+ *          those of the entries L, L + 16, ... of column j of tA in the caller's CSC order (flagged rows only); the 16 partial sums are
+ *          folded pairwise at distances 8, 4, 2, 1 (lane L += lane L + distance); rx_j = -(tq_j + fold).  Component ry_i of a flagged row:
+ *          the same split and fold over the entries of row i of tA in column order; ry_i = tb_i - fold.  Nothing else enters: the
+ *          right-hand side depends on the inputs of ITS slab alone.
+ * METHOD   qpdo_amd_adjoint's, by the same code: ONE full factorization of K per call with the adjoint's sigma and W, then per right-hand
+ *          side the adjoint's sweeps on the true residual (the KKT matrix of the active set is symmetric: the adjoint's driver is fed (rx, ry)
+ *          where the adjoint feeds it (gx, gy)).  The right-hand sides follow one another on the one factor: slab r of an nrhs = R call
+ *          carries the bits of the nrhs = 1 call with slab r of the inputs, and the same call twice returns the same bits.
+ * ACCEPTANCE  the true unscaled residual's inf-norm <= tol * max(||rx||_inf, ||ry_S||_inf), looked at before every sweep; at most max_sweeps
+ *          sweeps.  A non-finite entry among those used is never accepted (code 1).  A zero right-hand side is accepted at sweep 0 with zeros.
+ * status   nrhs x 3: (code, sweeps, k); codes 0, 1 and 3 with the adjoint's meaning.  A right-hand side with code != 0 gets NaN in its slices
+ *          of dx and dy and NaN in res[r]; code 1 is that right-hand side's own and touches no other.  After code 3 `active` is all 0.
+ * Accepted workspaces and refusals: those of qpdo_amd_adjoint, by the same function; the messages begin with "qpdo_amd_tangent:".
+ * Checks   all before anything is launched or written; a refused call returns nonzero with qpdo_amd_last_error() set and leaves every
+ *          output array untouched.  The first fault in this order is reported: nrhs < 1; tol not a positive finite number; max_sweeps < 1;
+ *          NULL dx or dy; no tangent passed; tQx without Q; NULL workspace; info->status_val != QPDO_SOLVED; the most recent state-changing
+ *          call was not a solve (the adjoint's flag; the call itself is not state-changing: any mix of adjoint and tangent calls may
+ *          follow one solve); the solver kind; the shape, stype, entry count and pattern of Q.
+ * No trace The call writes none of the workspace's state, solution, matrices, q, l, u, info, trace, QPDOAmdStats or QPDOAmdAdjointStats (nor
+ *          does qpdo_amd_adjoint move QPDOAmdTangentStats); every later qpdo_solve carries the bits it would have had.
+ * Stats    QPDOAmdTangentStats, the adjoint's members for the tangent calls.  The 6 n + 7 m doubles and m flags of work vectors are SHARED
+ *          with qpdo_amd_adjoint and booked in scratch_bytes of whichever kind of call allocated them; the staging of one right-hand
+ *          side's tq, tl, tu, tQx, tAx is the tangent's own, each array allocated by the first call that passes it (with tAx, on a workspace
+ *          that never saw qpdo_amd_update_matrices, also the map from CSR(A) to the caller's order); freed by qpdo_cleanup.  These are host
+ *          allocations: THE FIRST CALL (and the first that passes a further array) MAY BLOCK until earlier device work has finished. */
+typedef struct {
+    long   calls, rhs_total, factorizations, sweeps_total, scratch_bytes;
+    double last_seconds;
+} QPDOAmdTangentStats;
+int  qpdo_amd_tangent(QPDOWorkspace *work, long nrhs,
+                      const double *tq /* nrhs x n or NULL */, const double *tl /* nrhs x m or NULL */, const double *tu /* nrhs x m or NULL */,
+                      const cholmod_sparse *Q /* the setup's Q pattern; needed only with tQx */,
+                      const double *tQx /* nrhs x nnz(Q as stored) or NULL */, const double *tAx /* nrhs x nnz(A) or NULL */,
+                      double *dx /* nrhs x n */, double *dy /* nrhs x m */,
+                      int *active /* m int32 or NULL */, long *status /* nrhs x 3 or NULL */, double *res /* nrhs or NULL */,
+                      double tol, long max_sweeps);
+int  qpdo_amd_get_tangent_stats(const QPDOWorkspace *work, QPDOAmdTangentStats *out);
 
 /* ---- one large QP row-partitioned over G GPUs (BASELINE.json configs[3]) --------------------------------
  * One process per GPU.  Every rank calls the normal API with the SAME full problem; the library keeps rows

@@ -190,20 +190,242 @@ __global__ void k_adj_grad_Q(int n, const int *__restrict__ Qrp, const int *__re
         }
     }
 }
+// ---- qpdo_amd_tangent: the right-hand side of the tangent system, formed from the caller's perturbations and the UNSCALED x, y ------------
+// rx_j = -(tq_j + (tQ x)_j + (tA_S' y_S)_j) over the rows of the full CSR(Q) and of CSR(A') (whose value order is the caller's CSC order of
+// A).  tQ is read through mapQ (stype +-1: the stored entry a Qf entry came from) or straight (mapQ == null, stype 0: entry k of row j of Qf
+// IS the caller's entry k of column j).  ADJ_LPR lanes per row: lane L adds the entries Qrp[j] + L, + ADJ_LPR, ... of tQ and then the
+// entries Trp[j] + L, + ADJ_LPR, ... of tA to ONE partial sum in that order, the 16 partial sums are folded 8, 4, 2, 1 (lane L += lane
+// L + o), and lane 0 adds tq_j to the fold.  An entry of tA on an unflagged row is branched past (it may hold NaN).  A null tq, tQ or tA
+// is a zero perturbation.  Every lane takes part in every shuffle.
+__global__ void k_tan_rhs_x(int n, const double *__restrict__ tq, const int *__restrict__ Qrp, const int *__restrict__ Qci, const u32 *__restrict__ mapQ,
+                            const double *__restrict__ tQ, const int *__restrict__ Trp, const int *__restrict__ Tci, const double *__restrict__ tA,
+                            const int *__restrict__ flag, const double *__restrict__ xu, const double *__restrict__ yu, double *__restrict__ rx) {
+    const int lane = threadIdx.x & (ADJ_LPR - 1);
+    const int groups = gridDim.x * (blockDim.x / ADJ_LPR);
+    const int rounds = (n + groups - 1) / groups;
+    for (int it = 0; it < rounds; it++) {
+        const int j = it * groups + blockIdx.x * (blockDim.x / ADJ_LPR) + (threadIdx.x / ADJ_LPR);
+        double s = 0.0;
+        if (j < n) {
+            if (tQ) for (int k = Qrp[j] + lane; k < Qrp[j + 1]; k += ADJ_LPR) s += tQ[mapQ ? mapQ[k] : (u32)k] * xu[Qci[k]];
+            if (tA) for (int k = Trp[j] + lane; k < Trp[j + 1]; k += ADJ_LPR) { const int i = Tci[k]; if (flag[i]) s += tA[k] * yu[i]; }
+        }
+#pragma unroll
+        for (int o = ADJ_LPR / 2; o > 0; o >>= 1) s += __shfl_down(s, o, ADJ_LPR);
+        if (j < n && lane == 0) rx[j] = -((tq ? tq[j] : 0.0) + s);
+    }
+}
+// ry_i = tb_i - (tA x)_i on flagged rows (tb = tu on +1 rows, tl on -1 rows), a plain 0 elsewhere, over the rows of CSR(A); tA is read
+// through mapA (the caller's CSC position of an entry of CSR(A)).  The lane split and the fold are k_tan_rhs_x's; lane 0 subtracts the
+// fold from tb_i.  Nothing of an unflagged row is read, nor tl on a +1 row, nor tu on a -1 row.
+__global__ void k_tan_rhs_y(int m, const double *__restrict__ tl, const double *__restrict__ tu, const int *__restrict__ Arp, const int *__restrict__ Aci,
+                            const u32 *__restrict__ mapA, const double *__restrict__ tA, const int *__restrict__ flag, const double *__restrict__ xu,
+                            double *__restrict__ ry) {
+    const int lane = threadIdx.x & (ADJ_LPR - 1);
+    const int groups = gridDim.x * (blockDim.x / ADJ_LPR);
+    const int rounds = (m + groups - 1) / groups;
+    for (int it = 0; it < rounds; it++) {
+        const int i = it * groups + blockIdx.x * (blockDim.x / ADJ_LPR) + (threadIdx.x / ADJ_LPR);
+        const int f = i < m ? flag[i] : 0;
+        double s = 0.0;
+        if (f && tA) for (int k = Arp[i] + lane; k < Arp[i + 1]; k += ADJ_LPR) s += tA[mapA[k]] * xu[Aci[k]];
+#pragma unroll
+        for (int o = ADJ_LPR / 2; o > 0; o >>= 1) s += __shfl_down(s, o, ADJ_LPR);
+        if (i < m && lane == 0) {
+            double r = 0.0;
+            if (f) { const double *tb = f > 0 ? tu : tl; r = (tb ? tb[i] : 0.0) - s; }
+            ry[i] = r;
+        }
+    }
+}
+// back to the caller's space, with k_adj_grad_vec's arithmetic: dx = D vxs, dy = E vys / c on flagged rows, an exact +0.0 elsewhere
+__global__ void k_tan_out(int n, int m, int scaled, double cinv, const double *__restrict__ D, const double *__restrict__ E, const int *__restrict__ flag,
+                          const double *__restrict__ vx, const double *__restrict__ vy, double *__restrict__ dx, double *__restrict__ dy) {
+    const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (int j = t0; j < n; j += stride) dx[j] = scaled ? D[j] * vx[j] : vx[j];
+    for (int i = t0; i < m; i += stride) {
+        double v = 0.0;
+        if (flag[i]) { v = vy[i]; if (scaled) { v = E[i] * v; v = v * cinv; } }
+        dy[i] = v;
+    }
+}
 
 static int adjoint_refuse(const char *msg) { snprintf(g_err, sizeof(g_err), "qpdo_amd_adjoint: %s", msg); return -1; }
 
 int qdev_get_adjoint_stats(QpdoDev *d, QdevAdjointStats *out) { *out = d->adj; return 0; }
+int qdev_get_tangent_stats(QpdoDev *d, QdevTangentStats *out) { *out = d->tan; return 0; }
 
-// the workspaces the call takes: one GPU, the dense LDL' or the plain band LDL' with b <= 127 as the workspace's solver
-int qdev_adjoint_check_kind(QpdoDev *d) {
-    if (d->comm.active) return adjoint_refuse("row-partitioned workspaces are not supported (solve the QP on one GPU, or take finite differences of qpdo_solve)");
-    if (d->hybrid) return adjoint_refuse("the workspace starts its solves with PCG (the hybrid of an automatically chosen dense solver from n = 8192, QPDO_HYBRID); set up with QPDO_LINSOLVE=dense");
-    if (d->linsolve != 1 && d->linsolve != 3)
-        return adjoint_refuse("the workspace's solver is PCG; the adjoint needs a direct solver: set up with QPDO_LINSOLVE=dense (n <= 40000) or QPDO_LINSOLVE=band");
-    if (d->linsolve == 3 && d->band_b > BAND_MAX_B) return adjoint_refuse("the band solver's half-bandwidth is above 127; set up with QPDO_LINSOLVE=dense");
-    if (d->linsolve == 3 && d->bc_r > 0) return adjoint_refuse("the band solver carries coupling rows (QPDO_BAND_COUPLING); set up without it or with QPDO_LINSOLVE=dense");
+// the workspaces the two calls take: one GPU, the dense LDL' or the plain band LDL' with b <= 127 as the workspace's solver.  who: the
+// entry point's name, which the message begins with
+int qdev_adjoint_check_kind(QpdoDev *d, const char *who) {
+    const char *msg = nullptr;
+    if (d->comm.active) msg = "row-partitioned workspaces are not supported (solve the QP on one GPU, or take finite differences of qpdo_solve)";
+    else if (d->hybrid) msg = "the workspace starts its solves with PCG (the hybrid of an automatically chosen dense solver from n = 8192, QPDO_HYBRID); set up with QPDO_LINSOLVE=dense";
+    else if (d->linsolve != 1 && d->linsolve != 3)
+        msg = "the workspace's solver is PCG; the adjoint needs a direct solver: set up with QPDO_LINSOLVE=dense (n <= 40000) or QPDO_LINSOLVE=band";
+    else if (d->linsolve == 3 && d->band_b > BAND_MAX_B) msg = "the band solver's half-bandwidth is above 127; set up with QPDO_LINSOLVE=dense";
+    else if (d->linsolve == 3 && d->bc_r > 0) msg = "the band solver carries coupling rows (QPDO_BAND_COUPLING); set up without it or with QPDO_LINSOLVE=dense";
+    if (!msg) return 0;
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
+    return -1;
+}
+
+// the last of the two calls' checks: the caller's Q (passed with dQx / tQx, `arr`) against the setup's pattern.  The first time a Q is
+// seen it is compared on the device and, for stype +-1, mapQ is built (upd_first_Q: whichever of qpdo_amd_update_matrices, the adjoint
+// and the tangent comes first builds it); later calls compare the column pointers.  Nothing is adopted from a refused call.
+static int adj_check_Q(QpdoDev *d, const QdevCsc *Q, const char *who, const char *arr) {
+    u32 *newMapQ = nullptr; double *newStage = nullptr;
+    int rc = 0, differs = 0;
+    const bool firstQ = d->upd_Qp.empty();
+    if (!firstQ && !upd_colptr_same(Q, d->upd_Qp)) differs = 1;
+    if (firstQ) {
+        TempAllocs tmp;
+        rc = upd_first_Q(d, tmp, Q, &differs, &newMapQ, &newStage);
+        if (!rc) { hipError_t e = hipGetLastError(); if (e != hipSuccess) rc = set_err(e, "adjoint checks", __LINE__); }
+        tmp.release(d->stream);
+        h2d_staging_release(d);
+    }
+    if (!rc && differs) {
+        snprintf(g_err, sizeof(g_err), "%s: the pattern of Q differs from the one given to qpdo_setup (%s follows the setup's stored entries)", who, arr);
+        rc = -1;
+    }
+    if (rc) { upd_free(d, newMapQ); upd_free(d, newStage); return rc; }
+    if (newMapQ) { d->mapQ = newMapQ; d->qstage = newStage; }
+    if (firstQ) upd_colptr(Q, d->upd_Qp);
     return 0;
+}
+
+// ---- ONE sweep driver for qdev_adjoint and qdev_tangent ------------------------------------------------------------------------------------
+// AdjCall: what one call of either kind holds between adj_begin and adj_end -- the work vectors, the scaling, what is kept of the workspace.
+extern "C++" {
+struct AdjCall {
+    int n = 0, m = 0, scaled = 0, kind = 0, gnm = 1;
+    double sc_c = 1.0, sc_cinv = 1.0;
+    double *xu = nullptr, *gxs = nullptr, *vx = nullptr, *rx = nullptr, *t1 = nullptr, *t2 = nullptr;
+    double *yu = nullptr, *gys = nullptr, *vy = nullptr, *ry = nullptr, *wry = nullptr, *Av = nullptr, *a2 = nullptr;
+    int *flag = nullptr;
+    DirectKeep keep; QdevStats st_keep;
+    int code3 = 0, kact = 0;
+    long sweeps_total = 0;
+};
+}
+// the work vectors (allocated by the first call of either kind: a host allocation, which may wait for earlier device work; booked in that
+// kind's scratch_bytes)
+static int adj_vectors(QpdoDev *d, AdjCall &c, int64_t *booked) {
+    const int n = d->n, m = d->m;
+    if (!d->adj_n) {
+        int rc = upd_alloc(d, &d->adj_n, (size_t)ADJ_N_COUNT * n);
+        if (!rc) rc = upd_alloc(d, &d->adj_m, (size_t)ADJ_M_COUNT * m);
+        if (!rc) rc = upd_alloc(d, &d->adj_flag, (size_t)m);
+        if (rc) return rc;
+        *booked += ((int64_t)ADJ_N_COUNT * n + (int64_t)ADJ_M_COUNT * m) * 8 + (int64_t)m * 4;
+    }
+    c.n = n; c.m = m; c.kind = d->linsolve;
+    c.xu = d->adj_n + (size_t)ADJ_N_XU * n; c.gxs = d->adj_n + (size_t)ADJ_N_GXS * n; c.vx = d->adj_n + (size_t)ADJ_N_VX * n;
+    c.rx = d->adj_n + (size_t)ADJ_N_RX * n; c.t1 = d->adj_n + (size_t)ADJ_N_T1 * n; c.t2 = d->adj_n + (size_t)ADJ_N_T2 * n;
+    c.yu = d->adj_m + (size_t)ADJ_M_YU * m; c.gys = d->adj_m + (size_t)ADJ_M_GYS * m; c.vy = d->adj_m + (size_t)ADJ_M_VY * m;
+    c.ry = d->adj_m + (size_t)ADJ_M_RY * m; c.wry = d->adj_m + (size_t)ADJ_M_WRY * m; c.Av = d->adj_m + (size_t)ADJ_M_AV * m;
+    c.a2 = d->adj_m + (size_t)ADJ_M_A2 * m;
+    c.flag = d->adj_flag;
+    c.scaled = d->scaled;
+    c.sc_c = c.scaled ? d->sc_c : 1.0; c.sc_cinv = c.scaled ? d->sc_cinv : 1.0;
+    c.gnm = vgrid(n > m ? n : m);
+    return 0;
+}
+// once per call: what the call overwrites of the workspace is kept (host_probe.inc direct_keep_*), the counters too; x, y go up; the scaled
+// x, the flags, s, W, the forced factorization, the pivot check.  Returns nonzero on an error of the runtime (adj_end still follows).
+static int adj_begin(QpdoDev *d, AdjCall &c, const double *x, const double *y) {
+    const int n = c.n, m = c.m;
+    c.st_keep = d->st;
+    { int rc = direct_keep_save(d, c.keep, true); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(c.xu, x, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+    if (m) HIPCHK(hipMemcpyAsync(c.yu, y, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
+    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+    LAUNCH(k_adj_scale_x, vgrid(n), n, c.scaled, (const double *)d->Dinv, (const double *)c.xu, d->qdiag_valid ? (const double *)d->qdiag : (const double *)nullptr,
+           (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val, c.t1, d->ctrl);
+    if (m) {
+        launch_spmv(d, d->Ar, c.t1, EpiStore{c.Av}, false);
+        LAUNCH(k_adj_classify, adj_grid_rows(m), m, c.scaled, (const double *)d->E, (const double *)c.yu, (const double *)d->l, (const double *)d->u, (const double *)c.Av,
+               (const int *)d->Ar.rp, (const double *)d->Ar.val, c.flag, c.a2, d->ctrl);
+    }
+    int rc = read_ctrl(d);
+    if (rc) return rc;
+    const double mqd = nrm_of(d->hctrl, N_C);
+    const double s = mqd > 0.0 ? mqd : 1.0;
+    c.kact = d->hctrl->cnt[C_MUCH];
+    d->sigma_f = ADJ_SIGMA_REL * s;
+    if (m) LAUNCH(k_adj_weights, vgrid(m), m, s, (const int *)c.flag, (const double *)c.a2, d->d);
+    // forced: a fresh factorization of (sigma_f, d), whatever the low-rank and up/downdate routes would do with a kept factor
+    if (c.kind == 3) rc = band_factor(d, true);
+    else {
+        rc = dense_factor(d);
+        if (!rc) LAUNCH(k_adj_check_pivots, vgrid(n), n, (const double *)d->Dg, d->ctrl);
+    }
+    return rc;
+}
+// per right-hand side: the UNSCALED right-hand side is in (c.rx, c.ry) -- both are rewritten by the first sweep's residual after k_adj_rhs
+// has read them; have_ry false: ry is zero and not read --; k_adj_rhs, the sweeps, the acceptance.  On return with *code == 0 the scaled
+// solution is in (c.vx, c.vy) and c.rx, c.ry, c.t1, c.t2, c.wry, c.Av are free.  A code 3 is latched in c.code3: the right-hand sides
+// behind it are not run.
+static int adj_sweeps(QpdoDev *d, AdjCall &c, bool have_ry, double tol, long max_sweeps, int *code_out, long *sweep_out, double *rel_out) {
+    const int n = c.n, m = c.m, scaled = c.scaled;
+    const double nan = __builtin_nan("");
+    int code = c.code3 ? 3 : 1, rc = 0; long sweep = 0; double rel = nan;
+    if (!c.code3) {
+        LAUNCH(k_adj_ctrl_clear, 1, d->ctrl, 1);
+        LAUNCH(k_adj_rhs, c.gnm, n, m, scaled, c.sc_c, (const double *)d->D, (const double *)d->E, (const double *)c.rx, have_ry ? (const double *)c.ry : (const double *)nullptr,
+               (const int *)c.flag, c.gxs, c.gys, c.vx, c.vy, d->ctrl);
+        for (;; sweep++) {
+            if (sweep) LAUNCH(k_adj_ctrl_clear, 1, d->ctrl, 0);
+            launch_spmv(d, d->Qf, c.vx, EpiStore{c.t1}, false);
+            if (m) { launch_spmv(d, d->Ar, c.vx, EpiStore{c.Av}, false); launch_spmv(d, d->At, c.vy, EpiStore{c.t2}, false); }
+            else HIPCHK(hipMemsetAsync(c.t2, 0, (size_t)n * 8, d->stream));
+            LAUNCH(k_adj_resid, c.gnm, n, m, scaled, (const double *)d->Dinv, (const double *)d->Einv, (const double *)c.gxs, (const double *)c.t1, (const double *)c.t2,
+                   (const double *)c.gys, (const double *)c.Av, (const int *)c.flag, (const double *)d->d, c.rx, c.ry, c.wry, d->ctrl);
+            rc = read_ctrl(d); if (rc) break;
+            if (d->hctrl->cnt[C_CHAIN_ERR] || d->hctrl->cnt[C_DINF]) { c.code3 = 1; code = 3; break; }
+            const double gnorm = fmax(nrm_of(d->hctrl, N_A), nrm_of(d->hctrl, N_B));
+            const double rn = fmax(nrm_of(d->hctrl, N_C) * c.sc_cinv, nrm_of(d->hctrl, N_D));
+            rel = gnorm > 0.0 ? rn / gnorm : rn;
+            if (!d->hctrl->cnt[C_VIOL] && rn <= tol * gnorm) { code = 0; break; }
+            if (sweep >= max_sweeps) break;
+            if (m) launch_spmv(d, d->At, c.wry, EpiStore{c.t2}, false);
+            LAUNCH(k_adj_solve_rhs, vgrid(n), n, (const double *)c.rx, (const double *)c.t2, d->rhs);
+            rc = c.kind == 3 ? band_solve(d) : dense_solve(d); if (rc) break;
+            if (m) launch_spmv(d, d->Ar, d->dx, EpiStore{c.Av}, false);
+            LAUNCH(k_adj_update, c.gnm, n, m, (const double *)d->dx, (const double *)c.Av, (const double *)c.ry, (const double *)d->d, c.vx, c.vy);
+        }
+        if (rc) return rc;
+        c.sweeps_total += sweep;
+    }
+    *code_out = code; *sweep_out = code == 3 ? 0 : sweep; *rel_out = code == 0 ? rel : nan;
+    return 0;
+}
+// the end of a call: the flags out (all 0 after a code 3), the code-3 latch cleared as qdev_direct_solve does (nothing is redone), the
+// control block, the counters and what adj_begin kept put back.  rc: what the call met so far; returned, or the restore's own error.
+static int adj_end(QpdoDev *d, AdjCall &c, int *active, int rc) {
+    if (!rc && active && c.m) {
+        if (c.code3) memset(active, 0, (size_t)c.m * sizeof(int));
+        else HIPCHK(hipMemcpyAsync(active, c.flag, (size_t)c.m * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (c.code3) {
+        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
+        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0; d->bc_factored = 0;
+    }
+    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
+    d->ctrl_clean = 0;
+    d->st = c.st_keep;
+    { int rck = direct_keep_restore(d, c.keep); if (rck && !rc) rc = rck; }
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+static void adj_book(QdevAdjointStats &st, long nrhs, long sweeps_total, const struct timespec &ts0) {
+    struct timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1);
+    st.calls++; st.factorizations++; st.rhs_total += nrhs; st.sweeps_total += sweeps_total;
+    st.last_seconds = (double)(ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double)(ts1.tv_nsec - ts0.tv_nsec);
 }
 
 int qdev_adjoint(QpdoDev *d, const double *x, const double *y, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du,
@@ -212,120 +434,31 @@ int qdev_adjoint(QpdoDev *d, const double *x, const double *y, long nrhs, const 
     struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
     const int n = d->n, m = d->m;
     // ---- checks: nothing is launched or written before they pass ------------------------------------------------------------------
-    { int rck = qdev_adjoint_check_kind(d); if (rck) return rck; }
-    const int kind = d->linsolve;
+    { int rck = qdev_adjoint_check_kind(d, "qpdo_amd_adjoint"); if (rck) return rck; }
     const bool wantQ = dQx != nullptr, wantA = dAx != nullptr;
-    u32 *newMapQ = nullptr; double *newStage = nullptr;
-    bool firstQ = false;
-    if (wantQ) {
-        int rc = 0, differs = 0;
-        firstQ = d->upd_Qp.empty();
-        if (!firstQ && !upd_colptr_same(Q, d->upd_Qp)) differs = 1;
-        if (firstQ) {
-            TempAllocs tmp;
-            rc = upd_first_Q(d, tmp, Q, &differs, &newMapQ, &newStage);
-            if (!rc) { hipError_t e = hipGetLastError(); if (e != hipSuccess) rc = set_err(e, "adjoint checks", __LINE__); }
-            tmp.release(d->stream);
-            h2d_staging_release(d);
-        }
-        if (!rc && differs) rc = adjoint_refuse("the pattern of Q differs from the one given to qpdo_setup (dQx follows the setup's stored entries)");
-        if (rc) { upd_free(d, newMapQ); upd_free(d, newStage); return rc; }
-    }
+    if (wantQ) { int rck = adj_check_Q(d, Q, "qpdo_amd_adjoint", "dQx"); if (rck) return rck; }
     // ---- the checks passed --------------------------------------------------------------------------------------------------------
-    if (newMapQ) { d->mapQ = newMapQ; d->qstage = newStage; }
-    if (wantQ && firstQ) upd_colptr(Q, d->upd_Qp);
     const long long nnzA = d->At.nnz, nnzQf = d->Qf.nnz, nnzQ = wantQ ? (long long)Q->nnz : 0;
-    if (!d->adj_n) {                                       // the first call: a host allocation, which may wait for earlier device work
-        int rc = upd_alloc(d, &d->adj_n, (size_t)ADJ_N_COUNT * n);
-        if (!rc) rc = upd_alloc(d, &d->adj_m, (size_t)ADJ_M_COUNT * m);
-        if (!rc) rc = upd_alloc(d, &d->adj_flag, (size_t)m);
-        if (rc) return rc;
-        d->adj.scratch_bytes += ((int64_t)ADJ_N_COUNT * n + (int64_t)ADJ_M_COUNT * m) * 8 + (int64_t)m * 4;
-    }
+    AdjCall c;
+    { int rck = adj_vectors(d, c, &d->adj.scratch_bytes); if (rck) return rck; }
     if (wantA && !d->adj_dA) { int rc = upd_alloc(d, &d->adj_dA, (size_t)nnzA); if (rc) return rc; d->adj.scratch_bytes += nnzA * 8; }
     if (wantQ && !d->adj_dQ) { int rc = upd_alloc(d, &d->adj_dQ, (size_t)nnzQ); if (rc) return rc; d->adj.scratch_bytes += nnzQ * 8; }
-    double *xu = d->adj_n + (size_t)ADJ_N_XU * n, *gxs = d->adj_n + (size_t)ADJ_N_GXS * n, *vx = d->adj_n + (size_t)ADJ_N_VX * n,
-           *rx = d->adj_n + (size_t)ADJ_N_RX * n, *t1 = d->adj_n + (size_t)ADJ_N_T1 * n, *t2 = d->adj_n + (size_t)ADJ_N_T2 * n;
-    double *yu = d->adj_m + (size_t)ADJ_M_YU * m, *gys = d->adj_m + (size_t)ADJ_M_GYS * m, *vy = d->adj_m + (size_t)ADJ_M_VY * m,
-           *ry = d->adj_m + (size_t)ADJ_M_RY * m, *wry = d->adj_m + (size_t)ADJ_M_WRY * m, *Av = d->adj_m + (size_t)ADJ_M_AV * m,
-           *a2 = d->adj_m + (size_t)ADJ_M_A2 * m;
-    int *flag = d->adj_flag;
-    const int scaled = d->scaled;
-    const double sc_c = scaled ? d->sc_c : 1.0, sc_cinv = scaled ? d->sc_cinv : 1.0;
-    const int gnm = vgrid(n > m ? n : m);
     const double nan = __builtin_nan("");
-
-    // ---- what the call overwrites of the workspace is kept (host_probe.inc direct_keep_*), the counters too -----------------------
-    DirectKeep keep;
-    const QdevStats st_keep = d->st;
-    { int rc = direct_keep_save(d, keep, true); if (rc) return rc; }
-    HIPCHK(hipMemcpyAsync(xu, x, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
-    if (m) HIPCHK(hipMemcpyAsync(yu, y, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    int rc = 0, code3 = 0, kact = 0;
-    // ---- once per call: the scaled x, the flags, s, W, the factorization --------------------------------------------------------------
-    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
-    LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-    LAUNCH(k_adj_scale_x, vgrid(n), n, scaled, (const double *)d->Dinv, (const double *)xu, d->qdiag_valid ? (const double *)d->qdiag : (const double *)nullptr,
-           (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val, t1, d->ctrl);
-    if (m) {
-        launch_spmv(d, d->Ar, t1, EpiStore{Av}, false);
-        LAUNCH(k_adj_classify, adj_grid_rows(m), m, scaled, (const double *)d->E, (const double *)yu, (const double *)d->l, (const double *)d->u, (const double *)Av,
-               (const int *)d->Ar.rp, (const double *)d->Ar.val, flag, a2, d->ctrl);
-    }
-    rc = read_ctrl(d);
-    if (!rc) {
-        const double mqd = nrm_of(d->hctrl, N_C);
-        const double s = mqd > 0.0 ? mqd : 1.0;
-        kact = d->hctrl->cnt[C_MUCH];
-        d->sigma_f = ADJ_SIGMA_REL * s;
-        if (m) LAUNCH(k_adj_weights, vgrid(m), m, s, (const int *)flag, (const double *)a2, d->d);
-        // forced: a fresh factorization of (sigma_f, d), whatever the low-rank and up/downdate routes would do with a kept factor
-        if (kind == 3) rc = band_factor(d, true);
-        else {
-            rc = dense_factor(d);
-            if (!rc) LAUNCH(k_adj_check_pivots, vgrid(n), n, (const double *)d->Dg, d->ctrl);
-        }
-    }
+    int rc = adj_begin(d, c, x, y);
     // ---- the right-hand sides, one after the other on the one factor ---------------------------------------------------------------------
-    long sweeps_total = 0;
     for (long r = 0; r < nrhs && !rc; r++) {
         const double *gxr = gx + (size_t)r * n, *gyr = gy ? gy + (size_t)r * m : nullptr;
         double *dqr = dq + (size_t)r * n, *dlr = dl + (size_t)r * m, *dur = du + (size_t)r * m;
         double *dQr = wantQ ? dQx + (size_t)r * nnzQ : nullptr, *dAr = wantA ? dAx + (size_t)r * nnzA : nullptr;
-        int code = code3 ? 3 : 1; long sweep = 0; double rel = nan;
-        if (!code3) {
-            // (gx, gy of this right-hand side travel through rx, ry: both are written by the first sweep's residual before they are read)
-            HIPCHK(hipMemcpyAsync(rx, gxr, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
-            if (m && gyr) HIPCHK(hipMemcpyAsync(ry, gyr, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
-            LAUNCH(k_adj_ctrl_clear, 1, d->ctrl, 1);
-            LAUNCH(k_adj_rhs, gnm, n, m, scaled, sc_c, (const double *)d->D, (const double *)d->E, (const double *)rx, gyr ? (const double *)ry : (const double *)nullptr,
-                   (const int *)flag, gxs, gys, vx, vy, d->ctrl);
-            for (;; sweep++) {
-                if (sweep) LAUNCH(k_adj_ctrl_clear, 1, d->ctrl, 0);
-                launch_spmv(d, d->Qf, vx, EpiStore{t1}, false);
-                if (m) { launch_spmv(d, d->Ar, vx, EpiStore{Av}, false); launch_spmv(d, d->At, vy, EpiStore{t2}, false); }
-                else HIPCHK(hipMemsetAsync(t2, 0, (size_t)n * 8, d->stream));
-                LAUNCH(k_adj_resid, gnm, n, m, scaled, (const double *)d->Dinv, (const double *)d->Einv, (const double *)gxs, (const double *)t1, (const double *)t2,
-                       (const double *)gys, (const double *)Av, (const int *)flag, (const double *)d->d, rx, ry, wry, d->ctrl);
-                rc = read_ctrl(d); if (rc) break;
-                if (d->hctrl->cnt[C_CHAIN_ERR] || d->hctrl->cnt[C_DINF]) { code3 = 1; code = 3; break; }
-                const double gnorm = fmax(nrm_of(d->hctrl, N_A), nrm_of(d->hctrl, N_B));
-                const double rn = fmax(nrm_of(d->hctrl, N_C) * sc_cinv, nrm_of(d->hctrl, N_D));
-                rel = gnorm > 0.0 ? rn / gnorm : rn;
-                if (!d->hctrl->cnt[C_VIOL] && rn <= tol * gnorm) { code = 0; break; }
-                if (sweep >= max_sweeps) break;
-                if (m) launch_spmv(d, d->At, wry, EpiStore{t2}, false);
-                LAUNCH(k_adj_solve_rhs, vgrid(n), n, (const double *)rx, (const double *)t2, d->rhs);
-                rc = kind == 3 ? band_solve(d) : dense_solve(d); if (rc) break;
-                if (m) launch_spmv(d, d->Ar, d->dx, EpiStore{Av}, false);
-                LAUNCH(k_adj_update, gnm, n, m, (const double *)d->dx, (const double *)Av, (const double *)ry, (const double *)d->d, vx, vy);
-            }
-            if (rc) break;
-            sweeps_total += sweep;
+        int code = 3; long sweep = 0; double rel = nan;
+        if (!c.code3) {
+            HIPCHK(hipMemcpyAsync(c.rx, gxr, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+            if (m && gyr) HIPCHK(hipMemcpyAsync(c.ry, gyr, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
         }
-        if (status) { status[3 * r] = code; status[3 * r + 1] = code == 3 ? 0 : sweep; status[3 * r + 2] = kact; }
-        if (res) res[r] = code == 0 ? rel : nan;
+        rc = adj_sweeps(d, c, gyr != nullptr, tol, max_sweeps, &code, &sweep, &rel);
+        if (rc) break;
+        if (status) { status[3 * r] = code; status[3 * r + 1] = sweep; status[3 * r + 2] = c.kact; }
+        if (res) res[r] = rel;
         if (code != 0) {
             for (int j = 0; j < n; j++) dqr[j] = nan;
             for (int i = 0; i < m; i++) { dlr[i] = nan; dur[i] = nan; }
@@ -334,40 +467,96 @@ int qdev_adjoint(QpdoDev *d, const double *x, const double *y, long nrhs, const 
             continue;
         }
         // the unscaled vx into rx, vy into ry (the sweeps are over); dq in t1, dl in wry, du in Av
-        LAUNCH(k_adj_grad_vec, gnm, n, m, scaled, sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)flag, (const double *)vx, (const double *)vy,
-               rx, ry, t1, wry, Av);
-        HIPCHK(hipMemcpyAsync(dqr, t1, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
-        if (m) { HIPCHK(hipMemcpyAsync(dlr, wry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipMemcpyAsync(dur, Av, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); }
+        LAUNCH(k_adj_grad_vec, c.gnm, n, m, c.scaled, c.sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)c.flag, (const double *)c.vx, (const double *)c.vy,
+               c.rx, c.ry, c.t1, c.wry, c.Av);
+        HIPCHK(hipMemcpyAsync(dqr, c.t1, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+        if (m) { HIPCHK(hipMemcpyAsync(dlr, c.wry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipMemcpyAsync(dur, c.Av, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); }
         if (wantA && nnzA) {
-            LAUNCH(k_adj_grad_A, adj_grid_rows(n), n, (const int *)d->At.rp, (const int *)d->At.ci, (const int *)flag, (const double *)xu, (const double *)yu,
-                   (const double *)rx, (const double *)ry, d->adj_dA);
+            LAUNCH(k_adj_grad_A, adj_grid_rows(n), n, (const int *)d->At.rp, (const int *)d->At.ci, (const int *)c.flag, (const double *)c.xu, (const double *)c.yu,
+                   (const double *)c.rx, (const double *)c.ry, d->adj_dA);
             HIPCHK(hipMemcpyAsync(dAr, d->adj_dA, (size_t)nnzA * 8, hipMemcpyDeviceToHost, d->stream));
         }
         if (wantQ && nnzQ) {
             const bool mapped = Q->stype != 0;
             if (mapped) HIPCHK(hipMemsetAsync(d->adj_dQ, 0, (size_t)nnzQ * 8, d->stream));
             if (nnzQf) LAUNCH(k_adj_grad_Q, adj_grid_rows(n), n, (const int *)d->Qf.rp, (const int *)d->Qf.ci, mapped ? (const u32 *)d->mapQ : (const u32 *)nullptr,
-                              (const double *)xu, (const double *)rx, d->adj_dQ);
+                              (const double *)c.xu, (const double *)c.rx, d->adj_dQ);
             HIPCHK(hipMemcpyAsync(dQr, d->adj_dQ, (size_t)nnzQ * 8, hipMemcpyDeviceToHost, d->stream));
         }
         HIPCHK(hipStreamSynchronize(d->stream));
     }
-    if (!rc && active && m) {
-        if (code3) memset(active, 0, (size_t)m * sizeof(int));
-        else HIPCHK(hipMemcpyAsync(active, flag, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    }
-    if (code3) {               // the latch is cleared as qdev_direct_solve does; nothing is redone
-        LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 0);
-        d->dense_valid = 0; d->dense_factored = 0; d->wb_k = 0; d->mid_fwd_valid = 0; d->bc_factored = 0;
-    }
-    LAUNCH(k_ctrl_clear_aux, 1, d->ctrl);
-    d->ctrl_clean = 0;
-    d->st = st_keep;
-    { int rck = direct_keep_restore(d, keep); if (rck && !rc) rc = rck; }
+    rc = adj_end(d, c, active, rc);
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    struct timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1);
-    d->adj.calls++; d->adj.factorizations++; d->adj.rhs_total += nrhs; d->adj.sweeps_total += sweeps_total;
-    d->adj.last_seconds = (double)(ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double)(ts1.tv_nsec - ts0.tv_nsec);
+    adj_book(d->adj, nrhs, c.sweeps_total, ts0);
     return 0;
 }
+
+// qpdo_amd_tangent (include/qpdo_amd_ext.h): the adjoint's call with the right-hand side formed on the device -- the caller's perturbations
+// go up into the tangent's own staging, k_tan_rhs_x / k_tan_rhs_y write the unscaled (rx, ry) where the adjoint's upload puts (gx, gy),
+// and adj_sweeps takes it from there.  The right-hand sides follow one another on the one factor, as in the adjoint.
+int qdev_tangent(QpdoDev *d, const double *x, const double *y, long nrhs, const double *tq, const double *tl, const double *tu, const QdevCsc *Q,
+                 const double *tQx, const double *tAx, double *dx, double *dy, int *active, long *status, double *res, double tol, long max_sweeps) {
+    HIPCHK(hipSetDevice(d->device));
+    struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
+    const int n = d->n, m = d->m;
+    // ---- checks: nothing is launched or written before they pass ------------------------------------------------------------------
+    { int rck = qdev_adjoint_check_kind(d, "qpdo_amd_tangent"); if (rck) return rck; }
+    if (tQx) { int rck = adj_check_Q(d, Q, "qpdo_amd_tangent", "tQx"); if (rck) return rck; }
+    // ---- the checks passed --------------------------------------------------------------------------------------------------------
+    const long long nnzA = d->At.nnz, nnzQ = tQx ? (long long)Q->nnz : 0;
+    const bool useQ = tQx && nnzQ && d->Qf.nnz, useA = tAx && m && nnzA, useL = tl && m, useU = tu && m;
+    AdjCall c;
+    { int rck = adj_vectors(d, c, &d->tan.scratch_bytes); if (rck) return rck; }
+    if (useA && !d->mapA) {                                    // (the map qpdo_amd_update_matrices builds on its first call; whichever comes first)
+        TempAllocs tmp; u32 *newMapA = nullptr;
+        int rc = upd_first_mapA(d, tmp, &newMapA, "qpdo_amd_tangent");
+        if (!rc) { hipError_t e = hipGetLastError(); if (e != hipSuccess) rc = set_err(e, "tangent map", __LINE__); }
+        tmp.release(d->stream);
+        if (rc) { upd_free(d, newMapA); return rc; }
+        d->mapA = newMapA;
+    }
+    struct { bool use; double **buf; size_t len; } stage[] = {{tq != nullptr, &d->tan_q, (size_t)n}, {useL, &d->tan_l, (size_t)m}, {useU, &d->tan_u, (size_t)m},
+                                                             {useQ, &d->tan_Q, (size_t)nnzQ}, {useA, &d->tan_A, (size_t)nnzA}};
+    for (auto &s : stage)
+        if (s.use && !*s.buf) { int rc = upd_alloc(d, s.buf, s.len); if (rc) return rc; d->tan.scratch_bytes += (int64_t)s.len * 8; }
+    const double nan = __builtin_nan("");
+    int rc = adj_begin(d, c, x, y);
+    for (long r = 0; r < nrhs && !rc; r++) {
+        double *dxr = dx + (size_t)r * n, *dyr = dy + (size_t)r * m;
+        int code = 3; long sweep = 0; double rel = nan;
+        if (!c.code3) {
+            if (tq) HIPCHK(hipMemcpyAsync(d->tan_q, tq + (size_t)r * n, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+            if (useL) HIPCHK(hipMemcpyAsync(d->tan_l, tl + (size_t)r * m, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+            if (useU) HIPCHK(hipMemcpyAsync(d->tan_u, tu + (size_t)r * m, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+            if (useQ) HIPCHK(hipMemcpyAsync(d->tan_Q, tQx + (size_t)r * nnzQ, (size_t)nnzQ * 8, hipMemcpyHostToDevice, d->stream));
+            if (useA) HIPCHK(hipMemcpyAsync(d->tan_A, tAx + (size_t)r * nnzA, (size_t)nnzA * 8, hipMemcpyHostToDevice, d->stream));
+            LAUNCH(k_tan_rhs_x, adj_grid_rows(n), n, tq ? (const double *)d->tan_q : (const double *)nullptr, (const int *)d->Qf.rp, (const int *)d->Qf.ci,
+                   Q && Q->stype != 0 ? (const u32 *)d->mapQ : (const u32 *)nullptr, useQ ? (const double *)d->tan_Q : (const double *)nullptr,
+                   (const int *)d->At.rp, (const int *)d->At.ci, useA ? (const double *)d->tan_A : (const double *)nullptr, (const int *)c.flag,
+                   (const double *)c.xu, (const double *)c.yu, c.rx);
+            if (m) LAUNCH(k_tan_rhs_y, adj_grid_rows(m), m, useL ? (const double *)d->tan_l : (const double *)nullptr, useU ? (const double *)d->tan_u : (const double *)nullptr,
+                          (const int *)d->Ar.rp, (const int *)d->Ar.ci, (const u32 *)d->mapA, useA ? (const double *)d->tan_A : (const double *)nullptr,
+                          (const int *)c.flag, (const double *)c.xu, c.ry);
+        }
+        rc = adj_sweeps(d, c, m > 0, tol, max_sweeps, &code, &sweep, &rel);
+        if (rc) break;
+        if (status) { status[3 * r] = code; status[3 * r + 1] = sweep; status[3 * r + 2] = c.kact; }
+        if (res) res[r] = rel;
+        if (code != 0) {
+            for (int j = 0; j < n; j++) dxr[j] = nan;
+            for (int i = 0; i < m; i++) dyr[i] = nan;
+            continue;
+        }
+        // the unscaled dx into rx, dy into ry (the sweeps are over)
+        LAUNCH(k_tan_out, c.gnm, n, m, c.scaled, c.sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)c.flag, (const double *)c.vx, (const double *)c.vy,
+               c.rx, c.ry);
+        HIPCHK(hipMemcpyAsync(dxr, c.rx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+        if (m) HIPCHK(hipMemcpyAsync(dyr, c.ry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+    }
+    rc = adj_end(d, c, active, rc);
+    if (rc) return rc;
+    adj_book(d->tan, nrhs, c.sweeps_total, ts0);
+    return 0;
+}
+

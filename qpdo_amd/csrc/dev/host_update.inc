@@ -88,6 +88,21 @@ static int upd_first_Q(QpdoDev *d, TempAllocs &tmp, const QdevCsc *Q, int *diffe
     return rc;
 }
 
+// The first time the position of CSR(A)'s entries in the caller's CSC arrays is needed (qdev_update_matrices, qdev_tangent with tAx):
+// setup's transposition of the CSC arrays again, its permutation kept as *mapA -- a long-lived allocation that the caller adopts, or hands
+// to upd_free when the call fails -- and the result compared with the workspace's CSR(A).  who: the entry point's name, for the message.
+// Writes nothing of the workspace.
+static int upd_first_mapA(QpdoDev *d, TempAllocs &tmp, u32 **mapA, const char *who) {
+    DevCsr R;
+    int differs = 0;
+    int rc = upd_alloc(d, mapA, (size_t)d->At.nnz);
+    if (!rc) rc = dev_transpose(d, tmp, d->At, &R, true, *mapA);
+    if (!rc) rc = upd_compare(d, tmp, R.rp, d->Ar.rp, (long long)d->m + 1, &differs);
+    if (!rc) rc = upd_compare(d, tmp, R.ci, d->Ar.ci, d->Ar.nnz, &differs);
+    if (!rc && differs) { snprintf(g_err, sizeof(g_err), "%s: CSR(A) of the workspace is not the transposition of its CSC arrays", who); rc = -1; }
+    return rc;
+}
+
 // Every piece of workspace state that outlives one solve, back to its value after create_tail + qdev_configure.  The pattern-only
 // decisions of setup stay (linsolve's automatic choice, band_b, max_row_nnz_A, the slab tables: band_detect and k_max_row_len read rp / ci
 // only); buffers whose contents are only read under a validity flag keep their contents (the dense / band factors, the Woodbury slots).
@@ -160,14 +175,7 @@ int qdev_update_matrices(QpdoDev *d, const QdevCsc *A, const QdevCsc *Q, const d
             if (!rc) rc = upd_compare(d, tmp, P.ci, d->At.ci, A->nnz, &differs);
             if (!rc && differs) rc = pattern_error("A");
         }
-        if (!rc && needA && !d->mapA) {                        // mapA: setup's transposition of the CSC arrays, its permutation kept
-            DevCsr R;
-            rc = upd_alloc(d, &newMapA, (size_t)d->At.nnz);
-            if (!rc) rc = dev_transpose(d, tmp, d->At, &R, true, newMapA);
-            if (!rc) rc = upd_compare(d, tmp, R.rp, d->Ar.rp, (long long)d->m + 1, &differs);
-            if (!rc) rc = upd_compare(d, tmp, R.ci, d->Ar.ci, d->Ar.nnz, &differs);
-            if (!rc && differs) { snprintf(g_err, sizeof(g_err), "qpdo_amd_update_matrices: CSR(A) of the workspace is not the transposition of its CSC arrays"); rc = -1; }
-        }
+        if (!rc && needA && !d->mapA) rc = upd_first_mapA(d, tmp, &newMapA, "qpdo_amd_update_matrices");
         const bool firstQ = Q && d->upd_Qp.empty();
         if (!rc && Q && !firstQ && !upd_colptr_same(Q, d->upd_Qp)) rc = pattern_error("Q");
         if (!rc && firstQ) rc = upd_first_Q(d, tmp, Q, &differs, &newMapQ, &newStage);

@@ -199,6 +199,10 @@ struct QpdoDev {
     // per-entry outputs (allocated by the first call that asks for them) and its counters
     double *adj_n = nullptr, *adj_m = nullptr, *adj_dA = nullptr, *adj_dQ = nullptr; int *adj_flag = nullptr;
     QdevAdjointStats adj{};
+    // qpdo_amd_tangent (dev/adjoint.inc) shares those work vectors; its own: the staging of one right-hand side's tq, tl, tu, tQx, tAx (each
+    // allocated by the first call that passes the array) and its counters
+    double *tan_q = nullptr, *tan_l = nullptr, *tan_u = nullptr, *tan_Q = nullptr, *tan_A = nullptr;
+    QdevTangentStats tan{};
     // what qdev_configure decided; a solve may change these (fallbacks, hybrid), qpdo_amd_update_matrices puts them back
     struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, ud_cap, deflate, pcg_maxit, band_b, bc_r; } cfg{};
 };

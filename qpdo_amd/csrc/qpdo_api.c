@@ -953,7 +953,7 @@ int qpdo_amd_adjoint(QPDOWorkspace *work, long nrhs, const double *gx, const dou
     if (work->info->status_val != QPDO_SOLVED) return adjoint_refuse("the workspace's status is not QPDO_SOLVED (never solved, infeasible, out of passes or an error): there is no solution to differentiate");
     if (!be->solved_last)
         return adjoint_refuse("the most recent state-changing call was not a solve (qpdo_warm_start, qpdo_update_q, qpdo_update_bounds or qpdo_amd_update_matrices since the last qpdo_solve): call qpdo_solve first");
-    if (qdev_adjoint_check_kind(be->dev)) return -1;
+    if (qdev_adjoint_check_kind(be->dev, "qpdo_amd_adjoint")) return -1;
     QdevCsc qq;
     if (dQx) {
         if (!sparse_ok(Q)) return adjoint_refuse("unsupported sparse storage of Q");
@@ -970,6 +970,50 @@ int qpdo_amd_get_adjoint_stats(const QPDOWorkspace *work, QPDOAmdAdjointStats *o
     if (!out) { qdev_set_error("qpdo_amd_get_adjoint_stats: NULL out"); return -1; }
     QdevAdjointStats st;
     qdev_get_adjoint_stats(work->chol->dev, &st);
+    out->calls = (long)st.calls; out->rhs_total = (long)st.rhs_total; out->factorizations = (long)st.factorizations;
+    out->sweeps_total = (long)st.sweeps_total; out->scratch_bytes = (long)st.scratch_bytes; out->last_seconds = st.last_seconds;
+    return 0;
+}
+/* ---- qpdo_amd_tangent (include/qpdo_amd_ext.h): the argument checks, in the header's order, before the backend is touched
+ * (tests/tangent_args_driver.c); then the adjoint's state checks; the solver kind and the pattern of Q are the backend's (dev/adjoint.inc) */
+static int tangent_refuse(const char *msg) {
+    char buf[240];
+    snprintf(buf, sizeof(buf), "qpdo_amd_tangent: %s", msg);
+    qdev_set_error(buf);
+    return -1;
+}
+int qpdo_amd_tangent(QPDOWorkspace *work, long nrhs, const double *tq, const double *tl, const double *tu, const cholmod_sparse *Q, const double *tQx,
+                     const double *tAx, double *dx, double *dy, int *active, long *status, double *res, double tol, long max_sweeps) {
+    if (nrhs < 1) return tangent_refuse("nrhs must be at least 1");
+    if (!(tol > 0.0) || !(tol <= 1.7976931348623157e308)) return tangent_refuse("tol is not a positive finite number");
+    if (max_sweeps < 1) return tangent_refuse("max_sweeps must be at least 1");
+    if (!dx) return tangent_refuse("dx is NULL");
+    if (!dy) return tangent_refuse("dy is NULL");
+    if (!tq && !tl && !tu && !tQx && !tAx) return tangent_refuse("no tangent passed (tq, tl, tu, tQx and tAx are all NULL)");
+    if (tQx && !Q) return tangent_refuse("tQx needs Q (the matrix in the pattern given to qpdo_setup)");
+    if (!work || !work->chol || !work->chol->dev || !work->data || !work->info || !work->solution) return tangent_refuse("NULL workspace");
+    struct QPDOBackend *be = work->chol;
+    const size_t n = work->data->n;
+    if (work->info->status_val != QPDO_SOLVED) return tangent_refuse("the workspace's status is not QPDO_SOLVED (never solved, infeasible, out of passes or an error): there is no solution to differentiate");
+    if (!be->solved_last)
+        return tangent_refuse("the most recent state-changing call was not a solve (qpdo_warm_start, qpdo_update_q, qpdo_update_bounds or qpdo_amd_update_matrices since the last qpdo_solve): call qpdo_solve first");
+    if (qdev_adjoint_check_kind(be->dev, "qpdo_amd_tangent")) return -1;
+    QdevCsc qq;
+    if (tQx) {
+        if (!sparse_ok(Q)) return tangent_refuse("unsupported sparse storage of Q");
+        if (Q->nrow != n || Q->ncol != n) return tangent_refuse("Q is not n x n");
+        if (Q->stype != be->q_stype) return tangent_refuse("the pattern of Q differs from the one given to qpdo_setup (another stype)");
+        if (idx_at(Q->p, Q->itype, (int64_t)n) != be->q_nnz) return tangent_refuse("the pattern of Q differs from the one given to qpdo_setup (another number of entries)");
+        QdevCsc v = {(int32_t)Q->nrow, (int32_t)Q->ncol, be->q_nnz, Q->itype, Q->p, Q->i, (const double *)Q->x, Q->stype};
+        qq = v;
+    }
+    return qdev_tangent(be->dev, work->solution->x, work->solution->y, nrhs, tq, tl, tu, tQx ? &qq : NULL, tQx, tAx, dx, dy, active, status, res, tol, max_sweeps) ? -1 : 0;
+}
+int qpdo_amd_get_tangent_stats(const QPDOWorkspace *work, QPDOAmdTangentStats *out) {
+    if (!work || !work->chol || !work->chol->dev) { qdev_set_error("qpdo_amd_get_tangent_stats: NULL workspace"); return -1; }
+    if (!out) { qdev_set_error("qpdo_amd_get_tangent_stats: NULL out"); return -1; }
+    QdevTangentStats st;
+    qdev_get_tangent_stats(work->chol->dev, &st);
     out->calls = (long)st.calls; out->rhs_total = (long)st.rhs_total; out->factorizations = (long)st.factorizations;
     out->sweeps_total = (long)st.sweeps_total; out->scratch_bytes = (long)st.scratch_bytes; out->last_seconds = st.last_seconds;
     return 0;

@@ -231,7 +231,14 @@ typedef struct {
 int qdev_adjoint(QpdoDev *d, const double *x, const double *y, long nrhs, const double *gx, const double *gy, double *dq, double *dl, double *du,
                  const QdevCsc *Q, double *dQx, double *dAx, int *active, long *status, double *res, double tol, long max_sweeps);
 int qdev_get_adjoint_stats(QpdoDev *d, QdevAdjointStats *out);
-int qdev_adjoint_check_kind(QpdoDev *d);      /* the solver-kind check alone (the caller's Q checks come behind it) */
+int qdev_adjoint_check_kind(QpdoDev *d, const char *who);   /* the solver-kind check alone (the caller's Q checks come behind it); who: the
+                                                              * entry point's name, which the message begins with */
+/* the tangent of the last solve (qpdo_amd_tangent, dev/adjoint.inc): the adjoint's call -- the same checks, once-per-call part and sweep
+ * driver -- with the right-hand side formed on the device from the caller's perturbations (NULL: zero).  Q is needed only with tQx. */
+typedef QdevAdjointStats QdevTangentStats;
+int qdev_tangent(QpdoDev *d, const double *x, const double *y, long nrhs, const double *tq, const double *tl, const double *tu, const QdevCsc *Q,
+                 const double *tQx, const double *tAx, double *dx, double *dy, int *active, long *status, double *res, double tol, long max_sweeps);
+int qdev_get_tangent_stats(QpdoDev *d, QdevTangentStats *out);
 /* the PCG path as single steps (tests; qpdo_amd_pcg_probe, dev/host_probe.inc): mode 0 one K product after build_compact, mode 1 one
  * pcg_solve; and the compact structures the last of either left (qpdo_amd_download_compact).  info: QDEV_PCG_INFO_LEN doubles. */
 #define QDEV_PCG_NOT_CONVERGED (-7)

@@ -124,11 +124,17 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_packed_matrix_layout", "qpdo_amd_fleet_get_packed_matrix_layout", "qpdo_amd_fleet_update_matrices_dev",
                "qpdo_amd_fleet_adjoint_dev", "qpdo_amd_fleet_get_adjoint_stats",
                "qpdo_amd_fleet_adjoint_multi_dev", "qpdo_amd_fleet_tangent_dev", "qpdo_amd_fleet_rhs_group", "qpdo_amd_fleet_get_sensitivity_stats",
-               "qpdo_amd_adjoint", "qpdo_amd_get_adjoint_stats"]
+               "qpdo_amd_adjoint", "qpdo_amd_get_adjoint_stats", "qpdo_amd_tangent", "qpdo_amd_get_tangent_stats"]
 
 
 class AdjointStats(C.Structure):
     """QPDOAmdAdjointStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("calls", C.c_long), ("rhs_total", C.c_long), ("factorizations", C.c_long), ("sweeps_total", C.c_long),
+                ("scratch_bytes", C.c_long), ("last_seconds", C.c_double)]
+
+
+class TangentStats(C.Structure):
+    """QPDOAmdTangentStats (include/qpdo_amd_ext.h)"""
     _fields_ = [("calls", C.c_long), ("rhs_total", C.c_long), ("factorizations", C.c_long), ("sweeps_total", C.c_long),
                 ("scratch_bytes", C.c_long), ("last_seconds", C.c_double)]
 
@@ -218,6 +224,12 @@ def lib():
             L.qpdo_amd_adjoint.restype = C.c_int
             L.qpdo_amd_get_adjoint_stats.argtypes = [W, C.POINTER(AdjointStats)]
             L.qpdo_amd_get_adjoint_stats.restype = C.c_int
+        if hasattr(L, "qpdo_amd_tangent"):
+            L.qpdo_amd_tangent.argtypes = [W, C.c_long, dp, dp, dp, C.POINTER(CholmodSparse), dp, dp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_long), dp,
+                                           C.c_double, C.c_long]
+            L.qpdo_amd_tangent.restype = C.c_int
+            L.qpdo_amd_get_tangent_stats.argtypes = [W, C.POINTER(TangentStats)]
+            L.qpdo_amd_get_tangent_stats.restype = C.c_int
         L.qpdo_amd_dist_config.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qpdo_amd_dist_unique_id.argtypes = [C.c_void_p]
         L.qpdo_amd_solve_batch.restype = C.c_long
@@ -613,6 +625,62 @@ class QPDO:
         if lib().qpdo_amd_get_adjoint_stats(self._w, C.byref(s)):
             raise RuntimeError("adjoint_stats: %s" % (lib().qpdo_amd_last_error() or b"").decode())
         return {f: getattr(s, f) for f, _ in AdjointStats._fields_}
+
+    def tangent(self, tq=None, tl=None, tu=None, tQ_values=None, tA_values=None, tol=1e-9, max_sweeps=20):
+        """The first-order change (dx, dy) of the last solve's solution for a change (tq, tl, tu, tQ_values, tA_values) of q, l, u and the
+        stored values of Q and A (None: no change), at the fixed active set, through the workspace's direct solver (qpdo_amd_tangent,
+        include/qpdo_amd_ext.h).  Every array is (L,) or (R, L) with L = n, m, m, the stored entries of Q, the entries of A: R right-hand
+        sides on ONE factorization; all arrays passed agree on R and the outputs carry the same leading R.  Returns dict(dx, dy, active
+        (m,) int32, status (3,) / (R, 3) int64: code, sweeps, active rows, residual).  A right-hand side whose code is not 0 holds NaN.  A
+        refused call raises RuntimeError with the reason."""
+        if not hasattr(self, "_Qview_keep"):
+            nq, na = None, None
+        else:
+            nq, na = len(self._Qview_keep[2]), len(self._Apat[1])
+        given = [(k, a, length) for k, a, length in (("tq", tq, self.n), ("tl", tl, self.m), ("tu", tu, self.m), ("tQ_values", tQ_values, nq),
+                                                      ("tA_values", tA_values, na)) if a is not None]
+        if not given:
+            raise ValueError("no tangent passed: at least one of tq, tl, tu, tQ_values, tA_values is needed")
+        arrs, lead = {}, None
+        for name, a, length in given:
+            if not isinstance(a, np.ndarray):
+                raise ValueError("%s: expected a numpy array, got %s" % (name, type(a).__name__))
+            if a.dtype != np.float64:
+                raise ValueError("%s: expected dtype float64, got %s" % (name, a.dtype))
+            if length is None:
+                raise RuntimeError("tangent: no workspace (call setup first)")
+            if a.ndim not in (1, 2) or a.shape[-1] != length:
+                raise ValueError("%s: expected shape (%d,) or (R, %d), got %s" % (name, length, length, a.shape))
+            if lead is None:
+                lead, first = a.shape[:-1], name
+            elif a.shape[:-1] != lead:
+                raise ValueError("%s and %s do not agree on R: leading shapes %s and %s" % (first, name, lead, a.shape[:-1]))
+            arrs[name] = np.ascontiguousarray(a)
+        single = lead == ()
+        R = 1 if single else lead[0]
+        if R < 1:
+            raise ValueError("%s: expected at least one right-hand side" % first)
+        if not self._w:
+            raise RuntimeError("tangent: no workspace (call setup first)")
+        dx, dy = np.empty((R, self.n)), np.empty((R, self.m))
+        active, status, res = np.zeros(self.m, np.int32), np.zeros((R, 3), np.int64), np.empty(R)
+        g = arrs.get
+        rc = lib().qpdo_amd_tangent(self._w, R, _as_dp(g("tq")), _as_dp(g("tl")), _as_dp(g("tu")), C.byref(self._Qview) if "tQ_values" in arrs else None,
+                                    _as_dp(g("tQ_values")), _as_dp(g("tA_values")), _as_dp(dx), _as_dp(dy), active.ctypes.data_as(C.POINTER(C.c_int)),
+                                    status.ctypes.data_as(C.POINTER(C.c_long)), _as_dp(res), float(tol), int(max_sweeps))
+        if rc:
+            raise RuntimeError("tangent: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+        out = dict(dx=dx, dy=dy, status=status, residual=res)
+        if single:
+            out = {k: v[0] for k, v in out.items()}
+        out["active"] = active
+        return out
+
+    def tangent_stats(self):
+        s = TangentStats()
+        if lib().qpdo_amd_get_tangent_stats(self._w, C.byref(s)):
+            raise RuntimeError("tangent_stats: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+        return {f: getattr(s, f) for f, _ in TangentStats._fields_}
 
     def _pcg_probe(self, dw, sigma, v, mode):
         dw = np.ascontiguousarray(dw, np.float64)

@@ -225,7 +225,10 @@ class WorkspaceQP(torch.nn.Module):
     was not delivered -- code 1 (not accepted), 3 (bad pivot), or 2: the forward's solve did not end with QPDO_SOLVED, in which case no
     adjoint call is made -- : "nan" or "zero", as in FleetQP.  layer.status: status_val of the last forward;
     layer.adjoint_status: (code, sweeps, active rows) of the last backward.  The workspace holds ONE solution: a backward that comes after
-    another forward raises."""
+    another forward raises.
+    layer.tangent(...) and layer.vjp_many(gx, gy) are the forward sensitivity (ONE qpdo_amd_tangent call) and R backward products (ONE
+    qpdo_amd_adjoint call) of the most recent forward, R right-hand sides on one factorization; on_failure is applied per right-hand side and
+    their status tensors are kept as layer.tangent_status and layer.vjp_status."""
 
     def __init__(self, qp, warm_start_last=True, on_failure="nan", tol=1e-9, max_sweeps=20):
         super().__init__()
@@ -233,6 +236,64 @@ class WorkspaceQP(torch.nn.Module):
             raise ValueError("on_failure: expected one of %r, got %r" % (ON_FAILURE, on_failure))
         self.qp, self.warm_start_last, self.on_failure, self.tol, self.max_sweeps = qp, bool(warm_start_last), on_failure, float(tol), int(max_sweeps)
         self.status, self.adjoint_status, self.serial, self._last = None, None, 0, None
+        self.tangent_status, self.vjp_status = None, None
 
     def forward(self, q=None, l=None, u=None, Q_values=None, A_values=None):
         return _WorkspaceQPFunction.apply(self, q, l, u, Q_values, A_values)
+
+    # ---- sensitivities of the most recent forward beside autograd: many right-hand sides per factorization ---------------------------------
+    def _guard(self, what):
+        if self.serial == 0:
+            raise RuntimeError("WorkspaceQP.%s: no forward yet" % what)
+
+    def _sensitivity(self, call, sizes, inputs):
+        """the host round trip and on_failure of tangent / vjp_many.  call(**numpy inputs) -> the solver's dict; sizes: per
+        gradient key its per-right-hand-side length (what a forward that did not end with QPDO_SOLVED is answered with, code 2)"""
+        import numpy as np
+        ref = next((t for t in inputs.values() if t is not None), None)
+        host = {k: (None if t is None else np.ascontiguousarray(t.detach().cpu().numpy(), np.float64)) for k, t in inputs.items()}
+        if self.status == 1:
+            out = call(**host)
+        else:
+            lead = next(a for a in host.values() if a is not None).shape[:-1]
+            out = {k: np.full(lead + (length,), np.nan) for k, length in sizes.items()}
+            out.update(status=np.broadcast_to(np.array([2, 0, 0], np.int64), lead + (3,)).copy(), residual=np.full(lead, np.nan),
+                       active=np.zeros(self.qp.m, np.int32))
+        res = {}
+        for k, v in out.items():
+            if v is None:
+                res[k] = None
+                continue
+            v = np.array(v)
+            if k in sizes and self.on_failure == "zero":
+                v[out["status"][..., 0] != 0] = 0.0
+            t = torch.from_numpy(v)
+            res[k] = t.to(ref.device) if k in sizes else t
+        return res
+
+    def tangent(self, tq=None, tl=None, tu=None, tQ_values=None, tA_values=None, tol=1e-9, max_sweeps=20):
+        """The first-order change (dx, dy) of the most recent forward's x, y for a change of its inputs (solver.QPDO.tangent; tensors (L,) or
+        (R, L)): a dict with dx, dy (on the inputs' device), active, status, residual.  Raises before any forward; the library refuses
+        when the workspace has been updated or warm-started since that forward's solve."""
+        if all(t is None for t in (tq, tl, tu, tQ_values, tA_values)):
+            raise ValueError("no tangent passed: at least one of tq, tl, tu, tQ_values, tA_values is needed")
+        self._guard("tangent")
+        out = self._sensitivity(lambda **kw: self.qp.tangent(tol=tol, max_sweeps=max_sweeps, **kw), dict(dx=self.qp.n, dy=self.qp.m),
+                                dict(tq=tq, tl=tl, tu=tu, tQ_values=tQ_values, tA_values=tA_values))
+        self.tangent_status = out["status"].clone()
+        return out
+
+    def vjp_many(self, gx, gy=None, matrices=False, tol=1e-9, max_sweeps=20):
+        """R vector-Jacobian products of the most recent forward at once (solver.QPDO.adjoint; gx (R, n), gy (R, m) or None): a dict with dq,
+        dl, du, dQ_values, dA_values (matrices=True; else None), active, status, residual, each gradient with the leading R.  Raises before
+        any forward; the library refuses when the workspace has been updated or warm-started since that forward's solve."""
+        self._guard("vjp_many")
+        qp = self.qp
+        sizes = dict(dq=qp.n, dl=qp.m, du=qp.m)
+        if matrices:
+            sizes.update(dQ_values=len(qp._Qview_keep[2]), dA_values=len(qp._Apat[1]))
+        out = self._sensitivity(lambda **kw: qp.adjoint(matrices=matrices, tol=tol, max_sweeps=max_sweeps, **kw), sizes, dict(gx=gx, gy=gy))
+        if not matrices:
+            out.update(dQ_values=None, dA_values=None)
+        self.vjp_status = out["status"].clone()
+        return out
