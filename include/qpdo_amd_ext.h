@@ -60,6 +60,9 @@
  *   QPDO_DENSE_LOOKAHEAD "0": factor on one stream, "1": overlap the next panel with the trailing update (default: from n = 7000 up;
  *                    read at qpdo_setup)
  *   QPDO_DENSE_SOLVE "steps": per-block-step triangular solve kernels instead of the one-launch chained solves
+ *   QPDO_AMD_RHS_GROUP  "1".."8": the right-hand sides qpdo_amd_adjoint / qpdo_amd_tangent carry through every launch of their sweep loop at
+ *                    once (default 8 where the workspace qualifies: "GROUPS of right-hand sides" below; "1": one after the other).  A
+ *                    measuring switch; the same bits at every value.  Read at qpdo_setup
  *   QPDO_SETUP_THREADS  host threads of the CSC -> CSR conversions in qpdo_setup (default min(16, cores)); QPDO_SETUP_PROF=1 prints phase times
  *   QPDO_SPMV        "slab" | "plain" (default: LDS-staged slab kernel for matrices >= 192 MB)
  *   QPDO_DEFLATE     "0" disables the heavy-row deflation of the PCG preconditioner
@@ -453,6 +456,42 @@ int  qpdo_amd_tangent(QPDOWorkspace *work, long nrhs,
                       int *active /* m int32 or NULL */, long *status /* nrhs x 3 or NULL */, double *res /* nrhs or NULL */,
                       double tol, long max_sweeps);
 int  qpdo_amd_get_tangent_stats(const QPDOWorkspace *work, QPDOAmdTangentStats *out);
+/* ---- GROUPS of right-hand sides in qpdo_amd_adjoint / qpdo_amd_tangent ----------------------------------------------------------------------
+ * Both calls keep their contracts above, every sentence of them.  What a group size G > 1 changes is WHEN the work is launched: a call with
+ * nrhs = R > 1 takes its right-hand sides in ceil(R / G) groups of up to G (the last may be partial), and inside a group every launch of
+ * the sweep loop -- the five products (a multi-vector CSR product: one read of the matrix, a gather per right-hand side), the four vector
+ * kernels, the two triangular solves (one column per right-hand side) -- is made ONCE for the group, with ONE read-back per sweep.  Every
+ * right-hand side still receives the single call's operations in the single call's order: slab r carries the bits of the nrhs = 1 call
+ * with slab r of the inputs.  A right-hand side leaves the sweeps at its own sweep count (accepted, or code 1 at max_sweeps); from then on
+ * no launch reads or writes its vectors.  The non-finite marker is per right-hand side (a code 1 touches no other); the code-3 latch is the
+ * call's: it hits the right-hand sides of the group in flight and all behind it.  A call with nrhs = 1 runs the G = 1 code path.
+ * G        8 where the workspace is one the two calls accept, Q, A and A' all take the plain CSR kernel, and the solver is the band LDL'
+ *          (b <= 127) or the dense LDL' with the chained one-launch solves.  G = 1 (the right-hand sides follow one another): a matrix on
+ *          the slab kernel (>= 192 MB, QPDO_SPMV) -- a multi-vector slab product does not exist --, and the stepwise dense solves
+ *          (QPDO_DENSE_SOLVE=steps, or after a lost producer).  QPDO_AMD_RHS_GROUP=1..8 in the environment at qpdo_setup overrides G (a
+ *          measuring switch, as QPDO_AMD_FLEET_RHS_GROUP is for the fleet; tools/workspace_group_latency.py); 1 runs the launch sequence
+ *          of a build without groups.
+ * Scratch  G copies of the per-right-hand-side work vectors (5 n + 5 m doubles each; x, y, the row norms and the flags are shared with the
+ *          single path), the solves' columns (G x (n + 5 ld) doubles, ld = n rounded up to 64) and the group control array, allocated
+ *          ONCE by the first call of either kind with nrhs > 1 on a workspace with G > 1 -- host allocations: THAT CALL MAY BLOCK until
+ *          earlier device work has finished --, booked in QPDOAmdGroupStats.scratch_bytes ALONE (not in the two calls' scratch_bytes), freed
+ *          by qpdo_cleanup.  No trace: as before, with these buffers included.
+ * qpdo_amd_rhs_group  G >= 1 as the workspace stands; 0: a workspace the two calls refuse; -1: NULL.
+ * qpdo_amd_spmv_group  test hook beside qpdo_amd_spmv: slab g of y (nvec x nrows) = M (slab g of v, nvec x ncols) for every g in
+ *          live_mask, bit for bit what qpdo_amd_spmv returns for that slab; slabs outside the mask are not written.  nvec 1..8.  Refused
+ *          (-1, message), before any device call: nvec out of range, a mask bit >= nvec, which not 0 (A), 1 (A') or 2 (Q), NULL pointers; then a row-partitioned workspace
+ *          and a matrix on the slab kernel. */
+typedef struct {
+    long group;         /* = qpdo_amd_rhs_group */
+    long groups_run;    /* groups carried through the sweep driver by adjoint + tangent calls since setup (nrhs = 1 or G = 1: one per
+                           right-hand side) */
+    long rounds_total;  /* looks at the residual = read-backs of the sweep loop: per group 1 + the largest sweep count among its right-hand
+                           sides (code 3: unspecified) */
+    long scratch_bytes; /* device memory of the group's vectors; 0 until a call with nrhs > 1 on a G > 1 workspace */
+} QPDOAmdGroupStats;
+int  qpdo_amd_rhs_group(const QPDOWorkspace *work);
+int  qpdo_amd_get_group_stats(const QPDOWorkspace *work, QPDOAmdGroupStats *out);
+int  qpdo_amd_spmv_group(QPDOWorkspace *work, int which, int nvec, unsigned live_mask, const double *v, double *y);
 
 /* ---- one large QP row-partitioned over G GPUs (BASELINE.json configs[3]) --------------------------------
  * One process per GPU.  Every rank calls the normal API with the SAME full problem; the library keeps rows

@@ -85,12 +85,14 @@ __global__ void k_adj_check_pivots(int n, const double *__restrict__ Dg, Ctrl *c
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) { const double dj = Dg[j]; bad |= !(dj > 0.0 && dj <= ADJ_DBL_MAX); }
     if (bad) ctrl->cnt[C_DINF] = 1;
 }
+// ---- the four vector kernels of the sweep loop: ONE body each, run by the single call's kernel on the control block's slots and by the
+// group's kernel (grid.y = the right-hand side, vectors a fixed stride apart, masked by `live`) on that right-hand side's slots of the
+// group control array -- the same expressions in the same order for both.
 // per right-hand side: gxs = c D gx, gys = E gy on flagged rows (0 elsewhere: gy of an inactive row is never read), vx = vy = 0,
-// ||gx||inf -> N_A, ||gy_S||inf -> N_B, a non-finite entry among those used -> C_VIOL
-__global__ void k_adj_rhs(int n, int m, int scaled, double c, const double *__restrict__ D, const double *__restrict__ E, const double *__restrict__ gx,
-                          const double *__restrict__ gy, const int *__restrict__ flag, double *__restrict__ gxs, double *__restrict__ gys, double *__restrict__ vx,
-                          double *__restrict__ vy, Ctrl *ctrl) {
-    __shared__ double sm[32];
+// ||gx||inf -> nA, ||gy_S||inf -> nB, a non-finite entry among those used -> viol
+__device__ __forceinline__ void adj_rhs_body(int n, int m, int scaled, double c, const double *__restrict__ D, const double *__restrict__ E,
+                                             const double *__restrict__ gx, const double *__restrict__ gy, const int *__restrict__ flag, double *__restrict__ gxs,
+                                             double *__restrict__ gys, double *__restrict__ vx, double *__restrict__ vy, u64 *nA, u64 *nB, int *viol, double *sm) {
     double mgx = 0.0, mgy = 0.0; int nonfin = 0;
     const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     for (int j = t0; j < n; j += stride) {
@@ -107,17 +109,32 @@ __global__ void k_adj_rhs(int n, int m, int scaled, double c, const double *__re
         gys[i] = scaled ? E[i] * g : g;
         vy[i] = 0.0;
     }
-    block_max_to(mgx, &ctrl->nrm[N_A], sm);
-    block_max_to(mgy, &ctrl->nrm[N_B], sm + 16);
-    if (nonfin) ctrl->cnt[C_VIOL] = 1;
+    block_max_to(mgx, nA, sm);
+    block_max_to(mgy, nB, sm + 16);
+    if (nonfin) *viol = 1;
+}
+__global__ void k_adj_rhs(int n, int m, int scaled, double c, const double *__restrict__ D, const double *__restrict__ E, const double *__restrict__ gx,
+                          const double *__restrict__ gy, const int *__restrict__ flag, double *__restrict__ gxs, double *__restrict__ gys, double *__restrict__ vx,
+                          double *__restrict__ vy, Ctrl *ctrl) {
+    __shared__ double sm[32];
+    adj_rhs_body(n, m, scaled, c, D, E, gx, gy, flag, gxs, gys, vx, vy, &ctrl->nrm[N_A], &ctrl->nrm[N_B], &ctrl->cnt[C_VIOL], sm);
+}
+__global__ void k_adj_rhs_group(int n, int m, int scaled, double c, const double *__restrict__ D, const double *__restrict__ E, const double *__restrict__ gx,
+                                const double *__restrict__ gy, const int *__restrict__ flag, double *__restrict__ gxs, double *__restrict__ gys, double *__restrict__ vx,
+                                double *__restrict__ vy, unsigned live, AdjGrpCtrl *gc) {
+    __shared__ double sm[32];
+    const size_t g = blockIdx.y;
+    if (!((live >> g) & 1u)) return;
+    adj_rhs_body(n, m, scaled, c, D, E, gx + g * n, gy ? gy + g * m : nullptr, flag, gxs + g * n, gys + g * m, vx + g * n, vy + g * m, &gc[g].nrm[0], &gc[g].nrm[1],
+                 &gc[g].nonfin, sm);
 }
 // per sweep, behind t1 = Qs vx, Av = As vx, t2 = As' vy: rx = (gxs - t1) - t2, ry = gys - Av on flagged rows, wry = W ry; the two
-// inf-norms in unscaled terms (||rx D^-1|| -> N_C, the host multiplies by 1 / c; ||ry E^-1|| -> N_D); a non-finite one -> C_VIOL
-__global__ void k_adj_resid(int n, int m, int scaled, const double *__restrict__ Dinv, const double *__restrict__ Einv, const double *__restrict__ gxs,
-                            const double *__restrict__ t1, const double *__restrict__ t2, const double *__restrict__ gys, const double *__restrict__ Av,
-                            const int *__restrict__ flag, const double *__restrict__ W, double *__restrict__ rx, double *__restrict__ ry,
-                            double *__restrict__ wry, Ctrl *ctrl) {
-    __shared__ double sm[32];
+// inf-norms in unscaled terms (||rx D^-1|| -> nC, the host multiplies by 1 / c; ||ry E^-1|| -> nD); a non-finite one -> viol
+__device__ __forceinline__ void adj_resid_body(int n, int m, int scaled, const double *__restrict__ Dinv, const double *__restrict__ Einv,
+                                               const double *__restrict__ gxs, const double *__restrict__ t1, const double *__restrict__ t2,
+                                               const double *__restrict__ gys, const double *__restrict__ Av, const int *__restrict__ flag,
+                                               const double *__restrict__ W, double *__restrict__ rx, double *__restrict__ ry, double *__restrict__ wry, u64 *nC,
+                                               u64 *nD, int *viol, double *sm) {
     double m1 = 0.0, m2 = 0.0; int nonfin = 0;
     const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     for (int j = t0; j < n; j += stride) {
@@ -134,20 +151,76 @@ __global__ void k_adj_resid(int n, int m, int scaled, const double *__restrict__
         m2 = a > m2 ? a : m2;
         if (!(a <= ADJ_DBL_MAX)) nonfin = 1;
     }
-    block_max_to(m1, &ctrl->nrm[N_C], sm);
-    block_max_to(m2, &ctrl->nrm[N_D], sm + 16);
-    if (nonfin) ctrl->cnt[C_VIOL] = 1;
+    block_max_to(m1, nC, sm);
+    block_max_to(m2, nD, sm + 16);
+    if (nonfin) *viol = 1;
+}
+__global__ void k_adj_resid(int n, int m, int scaled, const double *__restrict__ Dinv, const double *__restrict__ Einv, const double *__restrict__ gxs,
+                            const double *__restrict__ t1, const double *__restrict__ t2, const double *__restrict__ gys, const double *__restrict__ Av,
+                            const int *__restrict__ flag, const double *__restrict__ W, double *__restrict__ rx, double *__restrict__ ry,
+                            double *__restrict__ wry, Ctrl *ctrl) {
+    __shared__ double sm[32];
+    adj_resid_body(n, m, scaled, Dinv, Einv, gxs, t1, t2, gys, Av, flag, W, rx, ry, wry, &ctrl->nrm[N_C], &ctrl->nrm[N_D], &ctrl->cnt[C_VIOL], sm);
+}
+__global__ void k_adj_resid_group(int n, int m, int scaled, const double *__restrict__ Dinv, const double *__restrict__ Einv, const double *__restrict__ gxs,
+                                  const double *__restrict__ t1, const double *__restrict__ t2, const double *__restrict__ gys, const double *__restrict__ Av,
+                                  const int *__restrict__ flag, const double *__restrict__ W, double *__restrict__ rx, double *__restrict__ ry,
+                                  double *__restrict__ wry, unsigned live, AdjGrpCtrl *gc) {
+    __shared__ double sm[32];
+    const size_t g = blockIdx.y;
+    if (!((live >> g) & 1u)) return;
+    adj_resid_body(n, m, scaled, Dinv, Einv, gxs + g * n, t1 + g * n, t2 + g * n, gys + g * m, Av + g * m, flag, W, rx + g * n, ry + g * m, wry + g * m,
+                   &gc[g].nrm[2], &gc[g].nrm[3], &gc[g].nonfin, sm);
 }
 // the solve's right-hand side: rhs = rx + As' wry (t2 holds the product)
-__global__ void k_adj_solve_rhs(int n, const double *__restrict__ rx, const double *__restrict__ t2, double *__restrict__ rhs) {
+__device__ __forceinline__ void adj_solve_rhs_body(int n, const double *__restrict__ rx, const double *__restrict__ t2, double *__restrict__ rhs) {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) rhs[j] = rx[j] + t2[j];
 }
+__global__ void k_adj_solve_rhs(int n, const double *__restrict__ rx, const double *__restrict__ t2, double *__restrict__ rhs) { adj_solve_rhs_body(n, rx, t2, rhs); }
+// (the group's right-hand sides are COMPACT: that of live vector g is column slot(g) = the number of live vectors below g)
+__device__ __forceinline__ size_t adj_slot(unsigned live, size_t g) { return (size_t)__popc(live & ((1u << g) - 1u)); }
+__global__ void k_adj_solve_rhs_group(int n, const double *__restrict__ rx, const double *__restrict__ t2, double *__restrict__ rhs, unsigned live) {
+    const size_t g = blockIdx.y;
+    if (!((live >> g) & 1u)) return;
+    adj_solve_rhs_body(n, rx + g * n, t2 + g * n, rhs + adj_slot(live, g) * n);
+}
 // behind Av = As dvx: vy += W (Av - ry), vx += dvx
-__global__ void k_adj_update(int n, int m, const double *__restrict__ dvx, const double *__restrict__ Av, const double *__restrict__ ry,
-                             const double *__restrict__ W, double *__restrict__ vx, double *__restrict__ vy) {
+__device__ __forceinline__ void adj_update_body(int n, int m, const double *__restrict__ dvx, const double *__restrict__ Av, const double *__restrict__ ry,
+                                                const double *__restrict__ W, double *__restrict__ vx, double *__restrict__ vy) {
     const int t0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     for (int i = t0; i < m; i += stride) vy[i] = vy[i] + W[i] * (Av[i] - ry[i]);
     for (int j = t0; j < n; j += stride) vx[j] = vx[j] + dvx[j];
+}
+__global__ void k_adj_update(int n, int m, const double *__restrict__ dvx, const double *__restrict__ Av, const double *__restrict__ ry,
+                             const double *__restrict__ W, double *__restrict__ vx, double *__restrict__ vy) {
+    adj_update_body(n, m, dvx, Av, ry, W, vx, vy);
+}
+// (dvx: the solve's columns, compact and ldx apart)
+__global__ void k_adj_update_group(int n, int m, const double *__restrict__ dvx, long long ldx, const double *__restrict__ Av, const double *__restrict__ ry,
+                                   const double *__restrict__ W, double *__restrict__ vx, double *__restrict__ vy, unsigned live) {
+    const size_t g = blockIdx.y;
+    if (!((live >> g) & 1u)) return;
+    adj_update_body(n, m, dvx + adj_slot(live, g) * (size_t)ldx, Av + g * m, ry + g * m, W, vx + g * n, vy + g * m);
+}
+// the group control array: all = 1 zeroes every slot of every right-hand side (a new group), else the two residual norms of the next sweep
+__global__ void k_adj_grp_clear(AdjGrpCtrl *gc, int G, int all) {
+    const int g = threadIdx.x >> 3, t = threadIdx.x & 7;
+    if (blockIdx.x || g >= G) return;
+    if (t == 2 || t == 3) gc[g].nrm[t] = 0ull;
+    if (all && t < 2) gc[g].nrm[t] = 0ull;
+    if (all && t == 4) gc[g].nonfin = 0;
+}
+// the read-back of a group's sweep: k_ctrl_publish with the group control array written to ITS pinned copy before the sequence word
+__global__ __launch_bounds__(128) void k_adj_grp_publish(const Ctrl *__restrict__ c, Ctrl *host, const AdjGrpCtrl *__restrict__ gc, AdjGrpCtrl *hgc, int G, u64 *hseq,
+                                                         u64 seq) {
+    const u64 *src = (const u64 *)c; u64 *dst = (u64 *)host;
+    const u64 *gsrc = (const u64 *)gc; u64 *gdst = (u64 *)hgc;
+    const int t = threadIdx.x;
+    if (t < (int)(sizeof(Ctrl) / 8)) dst[t] = src[t];
+    else if (t >= 64 && t - 64 < G * (int)(sizeof(AdjGrpCtrl) / 8)) gdst[t - 64] = gsrc[t - 64];
+    __threadfence_system();
+    __syncthreads();
+    if (t == 0) __hip_atomic_store(hseq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 // back to the caller's space: vx = D vxs, vy = E vys / c; dq = -vx, du = vy on +1 rows, dl = vy on -1 rows, every other entry +0.0
 __global__ void k_adj_grad_vec(int n, int m, int scaled, double cinv, const double *__restrict__ D, const double *__restrict__ E, const int *__restrict__ flag,
@@ -257,18 +330,32 @@ int qdev_get_tangent_stats(QpdoDev *d, QdevTangentStats *out) { *out = d->tan; r
 
 // the workspaces the two calls take: one GPU, the dense LDL' or the plain band LDL' with b <= 127 as the workspace's solver.  who: the
 // entry point's name, which the message begins with
+static const char *adj_kind_refusal(const QpdoDev *d) {
+    if (d->comm.active) return "row-partitioned workspaces are not supported (solve the QP on one GPU, or take finite differences of qpdo_solve)";
+    if (d->hybrid) return "the workspace starts its solves with PCG (the hybrid of an automatically chosen dense solver from n = 8192, QPDO_HYBRID); set up with QPDO_LINSOLVE=dense";
+    if (d->linsolve != 1 && d->linsolve != 3)
+        return "the workspace's solver is PCG; the adjoint needs a direct solver: set up with QPDO_LINSOLVE=dense (n <= 40000) or QPDO_LINSOLVE=band";
+    if (d->linsolve == 3 && d->band_b > BAND_MAX_B) return "the band solver's half-bandwidth is above 127; set up with QPDO_LINSOLVE=dense";
+    if (d->linsolve == 3 && d->bc_r > 0) return "the band solver carries coupling rows (QPDO_BAND_COUPLING); set up without it or with QPDO_LINSOLVE=dense";
+    return nullptr;
+}
 int qdev_adjoint_check_kind(QpdoDev *d, const char *who) {
-    const char *msg = nullptr;
-    if (d->comm.active) msg = "row-partitioned workspaces are not supported (solve the QP on one GPU, or take finite differences of qpdo_solve)";
-    else if (d->hybrid) msg = "the workspace starts its solves with PCG (the hybrid of an automatically chosen dense solver from n = 8192, QPDO_HYBRID); set up with QPDO_LINSOLVE=dense";
-    else if (d->linsolve != 1 && d->linsolve != 3)
-        msg = "the workspace's solver is PCG; the adjoint needs a direct solver: set up with QPDO_LINSOLVE=dense (n <= 40000) or QPDO_LINSOLVE=band";
-    else if (d->linsolve == 3 && d->band_b > BAND_MAX_B) msg = "the band solver's half-bandwidth is above 127; set up with QPDO_LINSOLVE=dense";
-    else if (d->linsolve == 3 && d->bc_r > 0) msg = "the band solver carries coupling rows (QPDO_BAND_COUPLING); set up without it or with QPDO_LINSOLVE=dense";
+    const char *msg = adj_kind_refusal(d);
     if (!msg) return 0;
     snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
     return -1;
 }
+// The group size of the two calls on this workspace as it stands: the right-hand sides that go through every launch of the sweep loop at
+// once.  0: a workspace the calls refuse.  1 (the right-hand sides follow one another): a matrix on the slab kernel -- a slab multi-vector
+// product does not exist --, and the dense route on the stepwise solves (QPDO_DENSE_SOLVE=steps, or after a lost producer).  Otherwise
+// QPDO_AMD_RHS_GROUP as read at setup, 8 by default.
+int qdev_rhs_group(QpdoDev *d) {
+    if (adj_kind_refusal(d)) return 0;
+    if (d->Qf.use_slab || d->Ar.use_slab || d->At.use_slab) return 1;
+    if (d->linsolve == 1 && !d->dense_chain) return 1;
+    return d->rhs_group_cfg;
+}
+int qdev_get_group_stats(QpdoDev *d, QdevGroupStats *out) { *out = d->grp; out->group = qdev_rhs_group(d); return 0; }
 
 // the last of the two calls' checks: the caller's Q (passed with dQx / tQx, `arr`) against the setup's pattern.  The first time a Q is
 // seen it is compared on the device and, for stype +-1, mapQ is built (upd_first_Q: whichever of qpdo_amd_update_matrices, the adjoint
@@ -307,11 +394,25 @@ struct AdjCall {
     DirectKeep keep; QdevStats st_keep;
     int code3 = 0, kact = 0;
     long sweeps_total = 0;
+    // G: the right-hand sides a group carries.  The per-right-hand-side vectors are five n-vectors at bn and five m-vectors at bm, G slabs
+    // each: vector v of right-hand side k at bn + (v G + k) n.  G = 1: the single call's vectors inside adj_n / adj_m.  The named pointers
+    // above are those of the right-hand side adj_point chose last; at k = 0 they are the bases the group kernels take.
+    int G = 1;
+    double *bn = nullptr, *bm = nullptr;
+    // the group's solve: the right-hand sides (n apart) and the solutions (ldx apart), compact over the live right-hand sides; the dense
+    // route's padded columns, polled vectors and forward results (ld apart), the band route's forward results (np apart)
+    double *srhs = nullptr, *sdvx = nullptr, *sx = nullptr, *spub1 = nullptr, *schy = nullptr, *spub2 = nullptr, *sz = nullptr;
+    long long ldx = 0;
 };
+}
+static void adj_point(AdjCall &c, int k) {
+    const size_t n = (size_t)c.n, m = (size_t)c.m, G = (size_t)c.G, kk = (size_t)k;
+    c.gxs = c.bn + (0 * G + kk) * n; c.vx = c.bn + (1 * G + kk) * n; c.rx = c.bn + (2 * G + kk) * n; c.t1 = c.bn + (3 * G + kk) * n; c.t2 = c.bn + (4 * G + kk) * n;
+    c.gys = c.bm + (0 * G + kk) * m; c.vy = c.bm + (1 * G + kk) * m; c.ry = c.bm + (2 * G + kk) * m; c.wry = c.bm + (3 * G + kk) * m; c.Av = c.bm + (4 * G + kk) * m;
 }
 // the work vectors (allocated by the first call of either kind: a host allocation, which may wait for earlier device work; booked in that
 // kind's scratch_bytes)
-static int adj_vectors(QpdoDev *d, AdjCall &c, int64_t *booked) {
+static int adj_vectors(QpdoDev *d, AdjCall &c, long nrhs, int64_t *booked) {
     const int n = d->n, m = d->m;
     if (!d->adj_n) {
         int rc = upd_alloc(d, &d->adj_n, (size_t)ADJ_N_COUNT * n);
@@ -321,15 +422,42 @@ static int adj_vectors(QpdoDev *d, AdjCall &c, int64_t *booked) {
         *booked += ((int64_t)ADJ_N_COUNT * n + (int64_t)ADJ_M_COUNT * m) * 8 + (int64_t)m * 4;
     }
     c.n = n; c.m = m; c.kind = d->linsolve;
-    c.xu = d->adj_n + (size_t)ADJ_N_XU * n; c.gxs = d->adj_n + (size_t)ADJ_N_GXS * n; c.vx = d->adj_n + (size_t)ADJ_N_VX * n;
-    c.rx = d->adj_n + (size_t)ADJ_N_RX * n; c.t1 = d->adj_n + (size_t)ADJ_N_T1 * n; c.t2 = d->adj_n + (size_t)ADJ_N_T2 * n;
-    c.yu = d->adj_m + (size_t)ADJ_M_YU * m; c.gys = d->adj_m + (size_t)ADJ_M_GYS * m; c.vy = d->adj_m + (size_t)ADJ_M_VY * m;
-    c.ry = d->adj_m + (size_t)ADJ_M_RY * m; c.wry = d->adj_m + (size_t)ADJ_M_WRY * m; c.Av = d->adj_m + (size_t)ADJ_M_AV * m;
-    c.a2 = d->adj_m + (size_t)ADJ_M_A2 * m;
+    static_assert(ADJ_N_GXS == 1 && ADJ_N_VX == 2 && ADJ_N_RX == 3 && ADJ_N_T1 == 4 && ADJ_N_T2 == 5, "adj_point's order of the n-vectors");
+    static_assert(ADJ_M_GYS == 1 && ADJ_M_VY == 2 && ADJ_M_RY == 3 && ADJ_M_WRY == 4 && ADJ_M_AV == 5, "adj_point's order of the m-vectors");
+    c.xu = d->adj_n + (size_t)ADJ_N_XU * n; c.yu = d->adj_m + (size_t)ADJ_M_YU * m; c.a2 = d->adj_m + (size_t)ADJ_M_A2 * m;
+    c.G = 1; c.bn = d->adj_n + (size_t)ADJ_N_GXS * n; c.bm = d->adj_m + (size_t)ADJ_M_GYS * m;
+    adj_point(c, 0);
     c.flag = d->adj_flag;
     c.scaled = d->scaled;
     c.sc_c = c.scaled ? d->sc_c : 1.0; c.sc_cinv = c.scaled ? d->sc_cinv : 1.0;
     c.gnm = vgrid(n > m ? n : m);
+    // a call with nrhs > 1 where the workspace's group size is above 1: the group's vectors (allocated by the first such call of either
+    // kind: host allocations, which may wait for earlier device work; booked in the group's scratch_bytes alone).  xu, yu, a2 and the
+    // flags stay the single call's.
+    const int G = nrhs > 1 ? qdev_rhs_group(d) : 1;
+    if (G <= 1) return 0;
+    const int Gc = d->rhs_group_cfg;
+    const size_t ld = (size_t)((n + DNB - 1) / DNB * DNB), ldx = c.kind == 3 ? (size_t)n : ld;      // (ld: dense_alloc's; it covers band_alloc's np)
+    if (!d->grp_hctrl) {
+        static_assert(sizeof(AdjGrpCtrl) == 40 && SPMV_GROUP_MAX * sizeof(AdjGrpCtrl) / 8 <= 64 && sizeof(Ctrl) / 8 <= 64, "k_adj_grp_publish copies both blocks with two waves");
+        const size_t sol = (size_t)Gc * ((size_t)n + 5 * ld);                 // (the larger of the two routes' layouts: the solver may change, the buffers stay)
+        int rc = upd_alloc(d, &d->grp_n, (size_t)5 * Gc * n);
+        if (!rc) rc = upd_alloc(d, &d->grp_m, (size_t)5 * Gc * m);
+        if (!rc) rc = upd_alloc(d, &d->grp_sol, sol);
+        if (!rc) rc = upd_alloc(d, &d->grp_ctrl, (size_t)SPMV_GROUP_MAX);
+        if (rc) return rc;
+        HIPCHK(hipHostMalloc((void **)&d->grp_hctrl, SPMV_GROUP_MAX * sizeof(AdjGrpCtrl), hipHostMallocCoherent));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_group), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
+        d->grp.scratch_bytes += (int64_t)(((size_t)5 * Gc * ((size_t)n + m) + sol) * 8 + SPMV_GROUP_MAX * sizeof(AdjGrpCtrl));
+    }
+    c.G = G; c.bn = d->grp_n; c.bm = d->grp_m;
+    adj_point(c, 0);
+    double *p = d->grp_sol;
+    c.ldx = (long long)ldx;
+    c.srhs = p; p += (size_t)Gc * n;
+    c.sdvx = p; p += (size_t)Gc * ldx;
+    if (c.kind == 3) c.sz = p;
+    else { c.sx = p; c.spub1 = p + (size_t)Gc * ld; c.schy = p + (size_t)2 * Gc * ld; c.spub2 = p + (size_t)3 * Gc * ld; }
     return 0;
 }
 // once per call: what the call overwrites of the workspace is kept (host_probe.inc direct_keep_*), the counters too; x, y go up; the scaled
@@ -365,6 +493,27 @@ static int adj_begin(QpdoDev *d, AdjCall &c, const double *x, const double *y) {
     }
     return rc;
 }
+// THE acceptance of a right-hand side after a sweep, for both sweep drivers.  nrm: its four maxima in the control block's order N_A .. N_D
+// (||gx||, ||gy_S||, the sweep's two residual norms) as bit patterns; viol: its non-finite marker.  *rel: the relative residual.
+static bool adj_accept(const u64 *nrm, int viol, double sc_cinv, double tol, double *rel) {
+    double v[4]; memcpy(v, nrm, sizeof(v));
+    const double gnorm = fmax(v[0], v[1]);
+    const double rn = fmax(v[2] * sc_cinv, v[3]);
+    *rel = gnorm > 0.0 ? rn / gnorm : rn;
+    return !viol && rn <= tol * gnorm;
+}
+// read_ctrl with the first cnt slots of the group control array brought along into d->grp_hctrl: one publication, or a second copy
+static int read_ctrl_group(QpdoDev *d, int cnt) {
+    if (!d->ctrl_publish) {
+        HIPCHK(hipMemcpyAsync(d->grp_hctrl, d->grp_ctrl, (size_t)cnt * sizeof(AdjGrpCtrl), hipMemcpyDeviceToHost, d->stream));
+        return read_ctrl(d);
+    }
+    const u64 seq = ++d->pub_seq;
+    hipLaunchKernelGGL(k_adj_grp_publish, dim3(1), dim3(128), 0, d->stream, (const Ctrl *)d->ctrl, d->hctrl, (const AdjGrpCtrl *)d->grp_ctrl, d->grp_hctrl, cnt, d->hseq, seq);
+    { int rc = ctrl_wait(d, d->hseq, seq); if (rc) return rc; }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 // per right-hand side: the UNSCALED right-hand side is in (c.rx, c.ry) -- both are rewritten by the first sweep's residual after k_adj_rhs
 // has read them; have_ry false: ry is zero and not read --; k_adj_rhs, the sweeps, the acceptance.  On return with *code == 0 the scaled
 // solution is in (c.vx, c.vy) and c.rx, c.ry, c.t1, c.t2, c.wry, c.Av are free.  A code 3 is latched in c.code3: the right-hand sides
@@ -385,11 +534,9 @@ static int adj_sweeps(QpdoDev *d, AdjCall &c, bool have_ry, double tol, long max
             LAUNCH(k_adj_resid, c.gnm, n, m, scaled, (const double *)d->Dinv, (const double *)d->Einv, (const double *)c.gxs, (const double *)c.t1, (const double *)c.t2,
                    (const double *)c.gys, (const double *)c.Av, (const int *)c.flag, (const double *)d->d, c.rx, c.ry, c.wry, d->ctrl);
             rc = read_ctrl(d); if (rc) break;
+            d->grp.rounds_total++;
             if (d->hctrl->cnt[C_CHAIN_ERR] || d->hctrl->cnt[C_DINF]) { c.code3 = 1; code = 3; break; }
-            const double gnorm = fmax(nrm_of(d->hctrl, N_A), nrm_of(d->hctrl, N_B));
-            const double rn = fmax(nrm_of(d->hctrl, N_C) * c.sc_cinv, nrm_of(d->hctrl, N_D));
-            rel = gnorm > 0.0 ? rn / gnorm : rn;
-            if (!d->hctrl->cnt[C_VIOL] && rn <= tol * gnorm) { code = 0; break; }
+            if (adj_accept(d->hctrl->nrm + N_A, d->hctrl->cnt[C_VIOL], c.sc_cinv, tol, &rel)) { code = 0; break; }
             if (sweep >= max_sweeps) break;
             if (m) launch_spmv(d, d->At, c.wry, EpiStore{c.t2}, false);
             LAUNCH(k_adj_solve_rhs, vgrid(n), n, (const double *)c.rx, (const double *)c.t2, d->rhs);
@@ -399,8 +546,77 @@ static int adj_sweeps(QpdoDev *d, AdjCall &c, bool have_ry, double tol, long max
         }
         if (rc) return rc;
         c.sweeps_total += sweep;
+        d->grp.groups_run++;
     }
     *code_out = code; *sweep_out = code == 3 ? 0 : sweep; *rel_out = code == 0 ? rel : nan;
+    return 0;
+}
+// The same for the cnt <= c.G right-hand sides of a group (G > 1; the unscaled right-hand sides in slabs 0 .. cnt - 1 of rx, ry): every
+// launch of the sweep loop is made once for the right-hand sides still in the sweeps (`live`), with one read-back per sweep -- the
+// control block (the call's code-3 latch) and the group control array (per right-hand side the four maxima and the non-finite marker)
+// in one publication or two copies.  Every right-hand side receives adj_sweeps' operations in adj_sweeps' order: the vector kernels run
+// the single kernels' bodies, the products k_spmv's row loop per vector, the solves the single solve's kernel per column.  A right-hand
+// side leaves at its own sweep count -- accepted, or code 1 at max_sweeps -- and from then on no launch reads or writes its vectors: its
+// solution stays in its slab of (vx, vy).  The solves' columns are compact over the live right-hand sides: a column that left is neither
+// produced nor polled.  A code 3 hits the right-hand sides still in the sweeps, and the latch those behind them.
+static int adj_sweeps_group(QpdoDev *d, AdjCall &c, int cnt, bool have_ry, double tol, long max_sweeps, int *code_out, long *sweep_out, double *rel_out) {
+    const int n = c.n, m = c.m, scaled = c.scaled, G = c.G;
+    const double nan = __builtin_nan("");
+    for (int k = 0; k < cnt; k++) { code_out[k] = c.code3 ? 3 : 1; sweep_out[k] = 0; rel_out[k] = nan; }
+    if (c.code3) return 0;
+    adj_point(c, 0);                                       // the bases of the group's vectors
+    AdjGrpCtrl *gc = d->grp_ctrl; const AdjGrpCtrl *hg = d->grp_hctrl;
+    unsigned live = (1u << cnt) - 1u;
+    int rc = 0; long sweep = 0;
+    const dim3 gv(c.gnm, cnt), gvn(vgrid(n), cnt);
+    LAUNCH(k_adj_grp_clear, 1, gc, G, 1);
+    LAUNCH(k_adj_rhs_group, gv, n, m, scaled, c.sc_c, (const double *)d->D, (const double *)d->E, (const double *)c.rx, have_ry ? (const double *)c.ry : (const double *)nullptr,
+           (const int *)c.flag, c.gxs, c.gys, c.vx, c.vy, live, gc);
+    for (;; sweep++) {
+        if (sweep) LAUNCH(k_adj_grp_clear, 1, gc, G, 0);
+        launch_spmv_group(d, d->Qf, c.vx, n, false, c.t1, n, live);
+        if (m) { launch_spmv_group(d, d->Ar, c.vx, n, false, c.Av, m, live); launch_spmv_group(d, d->At, c.vy, m, false, c.t2, n, live); }
+        else HIPCHK(hipMemsetAsync(c.t2, 0, (size_t)G * n * 8, d->stream));      // (t2 is scratch: a right-hand side that left does not read it again)
+        LAUNCH(k_adj_resid_group, gv, n, m, scaled, (const double *)d->Dinv, (const double *)d->Einv, (const double *)c.gxs, (const double *)c.t1, (const double *)c.t2,
+               (const double *)c.gys, (const double *)c.Av, (const int *)c.flag, (const double *)d->d, c.rx, c.ry, c.wry, live, gc);
+        rc = read_ctrl_group(d, cnt); if (rc) break;
+        d->grp.rounds_total++;
+        if (d->hctrl->cnt[C_CHAIN_ERR] || d->hctrl->cnt[C_DINF]) {
+            c.code3 = 1;
+            for (int k = 0; k < cnt; k++) if ((live >> k) & 1u) { code_out[k] = 3; sweep_out[k] = 0; rel_out[k] = nan; }
+            live = 0;
+            break;
+        }
+        for (int k = 0; k < cnt; k++) {
+            if (!((live >> k) & 1u)) continue;
+            double rel = nan;
+            const bool ok = adj_accept(hg[k].nrm, hg[k].nonfin, c.sc_cinv, tol, &rel);
+            if (!ok && sweep < max_sweeps) continue;
+            code_out[k] = ok ? 0 : 1; sweep_out[k] = sweep; rel_out[k] = ok ? rel : nan;
+            c.sweeps_total += sweep;
+            live &= ~(1u << k);
+        }
+        if (!live) break;
+        if (m) launch_spmv_group(d, d->At, c.wry, m, false, c.t2, n, live);
+        LAUNCH(k_adj_solve_rhs_group, gvn, n, (const double *)c.rx, (const double *)c.t2, c.srhs, live);
+        const int nl = __builtin_popcount(live);
+        if (c.kind == 3) {
+            const size_t lds = (size_t)4 * BAND_SC * (d->band_b + 1) * sizeof(double);
+            hipLaunchKernelGGL(k_band_solve_group, dim3(nl), dim3(256), lds, d->stream, n, d->band_np, d->band_b, (const double *)d->Kb, (const double *)d->Lt,
+                               (const double *)c.srhs, (long long)n, c.sz, c.sdvx);
+        } else {
+            const int ld = d->dense_ld;
+            LAUNCH(k_dense_load_rhs_group, dim3(vgrid(ld), nl), n, ld, (const double *)c.srhs, (long long)n, c.sx, c.spub1, c.spub2);
+            // the single solve's kernel on the grid (columns, block rows).  (One workgroup per block row that reads each tile once for all
+            // columns was built and measured 1.24x - 1.33x slower per call at n = 1000 and n = 1e4: docs/LAB_NOTES.md.)
+            launch_ldl_chain<true>(d, nl, c.sx, c.spub1, c.schy, ld);
+            launch_ldl_chain<false>(d, nl, c.schy, c.spub2, c.sdvx, n);
+        }
+        if (m) launch_spmv_group(d, d->Ar, c.sdvx, c.ldx, true, c.Av, m, live);
+        LAUNCH(k_adj_update_group, gv, n, m, (const double *)c.sdvx, c.ldx, (const double *)c.Av, (const double *)c.ry, (const double *)d->d, c.vx, c.vy, live);
+    }
+    if (rc) return rc;
+    d->grp.groups_run++;
     return 0;
 }
 // the end of a call: the flags out (all 0 after a code 3), the code-3 latch cleared as qdev_direct_solve does (nothing is redone), the
@@ -440,50 +656,58 @@ int qdev_adjoint(QpdoDev *d, const double *x, const double *y, long nrhs, const 
     // ---- the checks passed --------------------------------------------------------------------------------------------------------
     const long long nnzA = d->At.nnz, nnzQf = d->Qf.nnz, nnzQ = wantQ ? (long long)Q->nnz : 0;
     AdjCall c;
-    { int rck = adj_vectors(d, c, &d->adj.scratch_bytes); if (rck) return rck; }
+    { int rck = adj_vectors(d, c, nrhs, &d->adj.scratch_bytes); if (rck) return rck; }
     if (wantA && !d->adj_dA) { int rc = upd_alloc(d, &d->adj_dA, (size_t)nnzA); if (rc) return rc; d->adj.scratch_bytes += nnzA * 8; }
     if (wantQ && !d->adj_dQ) { int rc = upd_alloc(d, &d->adj_dQ, (size_t)nnzQ); if (rc) return rc; d->adj.scratch_bytes += nnzQ * 8; }
     const double nan = __builtin_nan("");
     int rc = adj_begin(d, c, x, y);
-    // ---- the right-hand sides, one after the other on the one factor ---------------------------------------------------------------------
-    for (long r = 0; r < nrhs && !rc; r++) {
-        const double *gxr = gx + (size_t)r * n, *gyr = gy ? gy + (size_t)r * m : nullptr;
-        double *dqr = dq + (size_t)r * n, *dlr = dl + (size_t)r * m, *dur = du + (size_t)r * m;
-        double *dQr = wantQ ? dQx + (size_t)r * nnzQ : nullptr, *dAr = wantA ? dAx + (size_t)r * nnzA : nullptr;
-        int code = 3; long sweep = 0; double rel = nan;
-        if (!c.code3) {
-            HIPCHK(hipMemcpyAsync(c.rx, gxr, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
-            if (m && gyr) HIPCHK(hipMemcpyAsync(c.ry, gyr, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
+    // ---- the right-hand sides on the one factor, in groups of up to c.G (G = 1: one after the other) ---------------------------------------
+    for (long r0 = 0; r0 < nrhs && !rc; r0 += c.G) {
+        const int cnt = (int)(nrhs - r0 < c.G ? nrhs - r0 : c.G);
+        int code[SPMV_GROUP_MAX]; long sweep[SPMV_GROUP_MAX]; double rel[SPMV_GROUP_MAX];
+        for (int k = 0; k < cnt && !c.code3; k++) {
+            const long r = r0 + k;
+            adj_point(c, k);
+            HIPCHK(hipMemcpyAsync(c.rx, gx + (size_t)r * n, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
+            if (m && gy) HIPCHK(hipMemcpyAsync(c.ry, gy + (size_t)r * m, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
         }
-        rc = adj_sweeps(d, c, gyr != nullptr, tol, max_sweeps, &code, &sweep, &rel);
+        rc = c.G == 1 ? adj_sweeps(d, c, gy != nullptr, tol, max_sweeps, code, sweep, rel) : adj_sweeps_group(d, c, cnt, gy != nullptr, tol, max_sweeps, code, sweep, rel);
         if (rc) break;
-        if (status) { status[3 * r] = code; status[3 * r + 1] = sweep; status[3 * r + 2] = c.kact; }
-        if (res) res[r] = rel;
-        if (code != 0) {
-            for (int j = 0; j < n; j++) dqr[j] = nan;
-            for (int i = 0; i < m; i++) { dlr[i] = nan; dur[i] = nan; }
-            for (long long e = 0; e < nnzQ; e++) dQr[e] = nan;
-            if (wantA) for (long long e = 0; e < nnzA; e++) dAr[e] = nan;
-            continue;
+        bool any = false;
+        for (int k = 0; k < cnt; k++) {
+            const long r = r0 + k;
+            double *dqr = dq + (size_t)r * n, *dlr = dl + (size_t)r * m, *dur = du + (size_t)r * m;
+            double *dQr = wantQ ? dQx + (size_t)r * nnzQ : nullptr, *dAr = wantA ? dAx + (size_t)r * nnzA : nullptr;
+            if (status) { status[3 * r] = code[k]; status[3 * r + 1] = sweep[k]; status[3 * r + 2] = c.kact; }
+            if (res) res[r] = rel[k];
+            if (code[k] != 0) {
+                for (int j = 0; j < n; j++) dqr[j] = nan;
+                for (int i = 0; i < m; i++) { dlr[i] = nan; dur[i] = nan; }
+                for (long long e = 0; e < nnzQ; e++) dQr[e] = nan;
+                if (wantA) for (long long e = 0; e < nnzA; e++) dAr[e] = nan;
+                continue;
+            }
+            any = true;
+            adj_point(c, k);
+            // the unscaled vx into rx, vy into ry (the sweeps are over); dq in t1, dl in wry, du in Av
+            LAUNCH(k_adj_grad_vec, c.gnm, n, m, c.scaled, c.sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)c.flag, (const double *)c.vx, (const double *)c.vy,
+                   c.rx, c.ry, c.t1, c.wry, c.Av);
+            HIPCHK(hipMemcpyAsync(dqr, c.t1, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+            if (m) { HIPCHK(hipMemcpyAsync(dlr, c.wry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipMemcpyAsync(dur, c.Av, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); }
+            if (wantA && nnzA) {
+                LAUNCH(k_adj_grad_A, adj_grid_rows(n), n, (const int *)d->At.rp, (const int *)d->At.ci, (const int *)c.flag, (const double *)c.xu, (const double *)c.yu,
+                       (const double *)c.rx, (const double *)c.ry, d->adj_dA);
+                HIPCHK(hipMemcpyAsync(dAr, d->adj_dA, (size_t)nnzA * 8, hipMemcpyDeviceToHost, d->stream));
+            }
+            if (wantQ && nnzQ) {
+                const bool mapped = Q->stype != 0;
+                if (mapped) HIPCHK(hipMemsetAsync(d->adj_dQ, 0, (size_t)nnzQ * 8, d->stream));
+                if (nnzQf) LAUNCH(k_adj_grad_Q, adj_grid_rows(n), n, (const int *)d->Qf.rp, (const int *)d->Qf.ci, mapped ? (const u32 *)d->mapQ : (const u32 *)nullptr,
+                                  (const double *)c.xu, (const double *)c.rx, d->adj_dQ);
+                HIPCHK(hipMemcpyAsync(dQr, d->adj_dQ, (size_t)nnzQ * 8, hipMemcpyDeviceToHost, d->stream));
+            }
         }
-        // the unscaled vx into rx, vy into ry (the sweeps are over); dq in t1, dl in wry, du in Av
-        LAUNCH(k_adj_grad_vec, c.gnm, n, m, c.scaled, c.sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)c.flag, (const double *)c.vx, (const double *)c.vy,
-               c.rx, c.ry, c.t1, c.wry, c.Av);
-        HIPCHK(hipMemcpyAsync(dqr, c.t1, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
-        if (m) { HIPCHK(hipMemcpyAsync(dlr, c.wry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipMemcpyAsync(dur, c.Av, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream)); }
-        if (wantA && nnzA) {
-            LAUNCH(k_adj_grad_A, adj_grid_rows(n), n, (const int *)d->At.rp, (const int *)d->At.ci, (const int *)c.flag, (const double *)c.xu, (const double *)c.yu,
-                   (const double *)c.rx, (const double *)c.ry, d->adj_dA);
-            HIPCHK(hipMemcpyAsync(dAr, d->adj_dA, (size_t)nnzA * 8, hipMemcpyDeviceToHost, d->stream));
-        }
-        if (wantQ && nnzQ) {
-            const bool mapped = Q->stype != 0;
-            if (mapped) HIPCHK(hipMemsetAsync(d->adj_dQ, 0, (size_t)nnzQ * 8, d->stream));
-            if (nnzQf) LAUNCH(k_adj_grad_Q, adj_grid_rows(n), n, (const int *)d->Qf.rp, (const int *)d->Qf.ci, mapped ? (const u32 *)d->mapQ : (const u32 *)nullptr,
-                              (const double *)c.xu, (const double *)c.rx, d->adj_dQ);
-            HIPCHK(hipMemcpyAsync(dQr, d->adj_dQ, (size_t)nnzQ * 8, hipMemcpyDeviceToHost, d->stream));
-        }
-        HIPCHK(hipStreamSynchronize(d->stream));
+        if (any) HIPCHK(hipStreamSynchronize(d->stream));
     }
     rc = adj_end(d, c, active, rc);
     if (rc) return rc;
@@ -506,7 +730,7 @@ int qdev_tangent(QpdoDev *d, const double *x, const double *y, long nrhs, const 
     const long long nnzA = d->At.nnz, nnzQ = tQx ? (long long)Q->nnz : 0;
     const bool useQ = tQx && nnzQ && d->Qf.nnz, useA = tAx && m && nnzA, useL = tl && m, useU = tu && m;
     AdjCall c;
-    { int rck = adj_vectors(d, c, &d->tan.scratch_bytes); if (rck) return rck; }
+    { int rck = adj_vectors(d, c, nrhs, &d->tan.scratch_bytes); if (rck) return rck; }
     if (useA && !d->mapA) {                                    // (the map qpdo_amd_update_matrices builds on its first call; whichever comes first)
         TempAllocs tmp; u32 *newMapA = nullptr;
         int rc = upd_first_mapA(d, tmp, &newMapA, "qpdo_amd_tangent");
@@ -521,10 +745,12 @@ int qdev_tangent(QpdoDev *d, const double *x, const double *y, long nrhs, const 
         if (s.use && !*s.buf) { int rc = upd_alloc(d, s.buf, s.len); if (rc) return rc; d->tan.scratch_bytes += (int64_t)s.len * 8; }
     const double nan = __builtin_nan("");
     int rc = adj_begin(d, c, x, y);
-    for (long r = 0; r < nrhs && !rc; r++) {
-        double *dxr = dx + (size_t)r * n, *dyr = dy + (size_t)r * m;
-        int code = 3; long sweep = 0; double rel = nan;
-        if (!c.code3) {
+    for (long r0 = 0; r0 < nrhs && !rc; r0 += c.G) {
+        const int cnt = (int)(nrhs - r0 < c.G ? nrhs - r0 : c.G);
+        int code[SPMV_GROUP_MAX]; long sweep[SPMV_GROUP_MAX]; double rel[SPMV_GROUP_MAX];
+        for (int k = 0; k < cnt && !c.code3; k++) {          // (one staging for the caller's arrays: the formation kernels of right-hand side k run behind its copies)
+            const long r = r0 + k;
+            adj_point(c, k);
             if (tq) HIPCHK(hipMemcpyAsync(d->tan_q, tq + (size_t)r * n, (size_t)n * 8, hipMemcpyHostToDevice, d->stream));
             if (useL) HIPCHK(hipMemcpyAsync(d->tan_l, tl + (size_t)r * m, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
             if (useU) HIPCHK(hipMemcpyAsync(d->tan_u, tu + (size_t)r * m, (size_t)m * 8, hipMemcpyHostToDevice, d->stream));
@@ -538,21 +764,28 @@ int qdev_tangent(QpdoDev *d, const double *x, const double *y, long nrhs, const 
                           (const int *)d->Ar.rp, (const int *)d->Ar.ci, (const u32 *)d->mapA, useA ? (const double *)d->tan_A : (const double *)nullptr,
                           (const int *)c.flag, (const double *)c.xu, c.ry);
         }
-        rc = adj_sweeps(d, c, m > 0, tol, max_sweeps, &code, &sweep, &rel);
+        rc = c.G == 1 ? adj_sweeps(d, c, m > 0, tol, max_sweeps, code, sweep, rel) : adj_sweeps_group(d, c, cnt, m > 0, tol, max_sweeps, code, sweep, rel);
         if (rc) break;
-        if (status) { status[3 * r] = code; status[3 * r + 1] = sweep; status[3 * r + 2] = c.kact; }
-        if (res) res[r] = rel;
-        if (code != 0) {
-            for (int j = 0; j < n; j++) dxr[j] = nan;
-            for (int i = 0; i < m; i++) dyr[i] = nan;
-            continue;
+        bool any = false;
+        for (int k = 0; k < cnt; k++) {
+            const long r = r0 + k;
+            double *dxr = dx + (size_t)r * n, *dyr = dy + (size_t)r * m;
+            if (status) { status[3 * r] = code[k]; status[3 * r + 1] = sweep[k]; status[3 * r + 2] = c.kact; }
+            if (res) res[r] = rel[k];
+            if (code[k] != 0) {
+                for (int j = 0; j < n; j++) dxr[j] = nan;
+                for (int i = 0; i < m; i++) dyr[i] = nan;
+                continue;
+            }
+            any = true;
+            adj_point(c, k);
+            // the unscaled dx into rx, dy into ry (the sweeps are over)
+            LAUNCH(k_tan_out, c.gnm, n, m, c.scaled, c.sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)c.flag, (const double *)c.vx, (const double *)c.vy,
+                   c.rx, c.ry);
+            HIPCHK(hipMemcpyAsync(dxr, c.rx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+            if (m) HIPCHK(hipMemcpyAsync(dyr, c.ry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
         }
-        // the unscaled dx into rx, dy into ry (the sweeps are over)
-        LAUNCH(k_tan_out, c.gnm, n, m, c.scaled, c.sc_cinv, (const double *)d->D, (const double *)d->E, (const int *)c.flag, (const double *)c.vx, (const double *)c.vy,
-               c.rx, c.ry);
-        HIPCHK(hipMemcpyAsync(dxr, c.rx, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
-        if (m) HIPCHK(hipMemcpyAsync(dyr, c.ry, (size_t)m * 8, hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
+        if (any) HIPCHK(hipStreamSynchronize(d->stream));
     }
     rc = adj_end(d, c, active, rc);
     if (rc) return rc;

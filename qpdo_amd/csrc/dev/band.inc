@@ -309,6 +309,13 @@ __global__ __launch_bounds__(256) void k_band_solve(int n, int b, const double *
                                                     const double *__restrict__ rhs, double *__restrict__ z, double *__restrict__ x) {
     band_solve_body(n, b, Lb, Lt, rhs, z, x);
 }
+// the group path's solve (dev/adjoint.inc adj_sweeps_group): one workgroup per live right-hand side, each running k_band_solve's two sweeps
+// on columns of its own (rhs and x: ldx apart, z: np apart) -- the columns advance together on different CUs for the time of one solve
+__global__ __launch_bounds__(256) void k_band_solve_group(int n, int np, int b, const double *__restrict__ Lb, const double *__restrict__ Lt,
+                                                          const double *rhs, long long ldx, double *z, double *x) {
+    const long long s = blockIdx.x;
+    band_solve_body(n, b, Lb, Lt, rhs + s * ldx, z + s * np, x + s * ldx);
+}
 
 // ---- chain QPs with a few dense coupling rows (QPDO_BAND_COUPLING; host side: dev/host_band.inc) ------------------------------------------
 // A row of A that touches the whole horizon (a budget, a terminal average, a conservation equality) makes A'DA a full matrix, but K is

@@ -827,6 +827,17 @@ __global__ void k_dense_load_rhs(int n, int ld, const double *__restrict__ b, do
         if (s1) { reinterpret_cast<unsigned long long *>(s1)[i] = CH_SENT; reinterpret_cast<unsigned long long *>(s2)[i] = CH_SENT; }
     }
 }
+// k_dense_load_rhs for the columns of a group (blockIdx.y = column, ld apart in every array): b's column (ldb apart) padded to ld, the
+// sentinels of the column's two polled vectors refilled
+__global__ void k_dense_load_rhs_group(int n, int ld, const double *__restrict__ b, long long ldb, double *__restrict__ x, double *__restrict__ s1,
+                                       double *__restrict__ s2) {
+    const long long col = blockIdx.y;
+    b += col * ldb; x += col * ld; s1 += col * ld; s2 += col * ld;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ld; i += gridDim.x * blockDim.x) {
+        x[i] = i < n ? b[i] : 0.0;
+        reinterpret_cast<unsigned long long *>(s1)[i] = CH_SENT; reinterpret_cast<unsigned long long *>(s2)[i] = CH_SENT;
+    }
+}
 __global__ void k_dense_scale_d(int ld, const double *__restrict__ z, const double *__restrict__ Dg, double *__restrict__ y) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ld; i += gridDim.x * blockDim.x) y[i] = z[i] / Dg[i];
 }

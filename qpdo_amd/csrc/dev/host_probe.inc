@@ -389,6 +389,30 @@ int qdev_spmv(QpdoDev *d, int which, const double *v_host, double *y_host) {
     HIPCHK(hipStreamSynchronize(d->stream));
     return 0;
 }
+// the group path's product on host vectors (qpdo_amd_spmv_group): nvec vectors up, one k_spmv_group launch on the slabs of live_mask,
+// those slabs down.  Its own temporary buffers: nothing of the workspace is written.
+int qdev_spmv_group(QpdoDev *d, int which, int nvec, unsigned live_mask, const double *v_host, double *y_host) {
+    HIPCHK(hipSetDevice(d->device));
+    if (d->comm.active) { snprintf(g_err, sizeof(g_err), "qpdo_amd_spmv_group: row-partitioned workspaces are not supported"); return -1; }
+    DevCsr *M = mat_by_id(d, which);
+    if (M->use_slab) { snprintf(g_err, sizeof(g_err), "qpdo_amd_spmv_group: the matrix is on the slab kernel (a slab multi-vector product does not exist)"); return -1; }
+    const size_t nc = (size_t)M->ncols, nr = (size_t)M->nrows;
+    TempAllocs tmp; double *xin = nullptr, *yout = nullptr;
+    int rc = 0;
+    if (tmp.get(&xin, (size_t)nvec * nc + 1) || tmp.get(&yout, (size_t)nvec * nr + 1)) rc = set_err(hipErrorOutOfMemory, "spmv group scratch", __LINE__);
+    hipError_t e = hipSuccess;
+    if (!rc && nc) e = hipMemcpyAsync(xin, v_host, (size_t)nvec * nc * 8, hipMemcpyHostToDevice, d->stream);
+    if (!rc && e == hipSuccess) {
+        launch_spmv_group(d, *M, xin, (long long)nc, false, yout, (long long)nr, live_mask);
+        for (int g = 0; g < nvec && nr && e == hipSuccess; g++)
+            if ((live_mask >> g) & 1u) e = hipMemcpyAsync(y_host + (size_t)g * nr, yout + (size_t)g * nr, nr * 8, hipMemcpyDeviceToHost, d->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (!rc && e != hipSuccess) rc = set_err(e, "spmv group", __LINE__);
+    tmp.release(d->stream);
+    return rc;
+}
 int qdev_linesearch(QpdoDev *d, double eta, double beta, const double *delta, const double *alpha, double *tau) {
     HIPCHK(hipSetDevice(d->device));
     const int M2 = 2 * d->m;

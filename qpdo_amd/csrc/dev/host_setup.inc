@@ -251,6 +251,7 @@ void qdev_destroy(QpdoDev *d) {
     for (void *p : d->allocs) (void)hipFree(p);
     if (d->hctrl) (void)hipHostFree(d->hctrl);
     if (d->hctrl2) (void)hipHostFree(d->hctrl2);
+    if (d->grp_hctrl) (void)hipHostFree(d->grp_hctrl);
     if (d->hpack) (void)hipHostFree(d->hpack);
     if (d->comm.hbuf) (void)hipHostFree(d->comm.hbuf);
     if (d->comm.nccl) ncclCommDestroy(d->comm.nccl);
@@ -272,6 +273,9 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     if (sc && *sc) d->schur_mode = atoi(sc) != 0;
     const char *ch = getenv("QPDO_DENSE_SOLVE");
     if (ch && !strcmp(ch, "steps")) d->dense_chain = 0;
+    // (a measuring switch: QPDO_AMD_RHS_GROUP=1..8 overrides the group size of qpdo_amd_adjoint / qpdo_amd_tangent, dev/adjoint.inc qdev_rhs_group;
+    // 1: the right-hand sides follow one another; tools/workspace_group_latency.py)
+    { const char *rg = getenv("QPDO_AMD_RHS_GROUP"); const int g = (rg && *rg) ? atoi(rg) : SPMV_GROUP_MAX; d->rhs_group_cfg = g >= 1 && g <= SPMV_GROUP_MAX ? g : SPMV_GROUP_MAX; }
     { const char *md = getenv("QPDO_DENSE_MID"); if (md && *md) d->dense_mid = atoi(md) != 0; }      // 0: mid-size orders through the multi-launch factorization too
     { const char *la = getenv("QPDO_DENSE_LOOKAHEAD"); if (la && *la) d->dense_lookahead = atoi(la) != 0; }
     // Low-rank update of the kept factor: pays from n ~ 2500 up (tools/lowrank_crossover.py, m = 2n: n = 256: 39 ms with, 11 ms without;

@@ -652,6 +652,72 @@ static void launch_spmv(QpdoDev *d, const DevCsr &M, const double *x, Epi epi, b
     d->st.spmv_calls++;
     d->st.spmv_bytes += (int64_t)M.alg_bytes();
 }
+// ---- the multi-vector product of the group path (dev/adjoint.inc adj_sweeps_group; qpdo_amd_spmv_group) -----------------------------------
+// y_g = M x_g for the vectors g of `live` (a kernel argument: every branch on it is uniform over the launch), at most G of them.  The row
+// loop is spmv_rows' with ONE read of rp / ci / val per entry and a gather per live vector; every vector keeps its own s0, s1, tail,
+// s0 + s1 and shuffle tree, so its bits are k_spmv's with that vector alone.  Operands and results are right-hand-side major: vector g's
+// result at y + g ys; its operand at x + g xs, or, compact, at x + (the number of live vectors below g) xs -- where the group's solves
+// left their columns.  A vector outside the mask is neither read nor written.  Plain store (the EpiStore of k_spmv).
+// Registers: G x 2 partial sums of doubles are 32 VGPRs at G = 8, the gathers in flight and the addresses beside them: the compiler's
+// count is 70 VGPRs (72 at TPR = 64), no scratch, 7 waves per SIMD at every TPR -- the vector bases are uniform and stay in SGPRs.
+static const int SPMV_GROUP_MAX = 8;
+template <int TPR, int G>
+__global__ __launch_bounds__(256) void k_spmv_group(int nrows, const int *__restrict__ rp, const int *__restrict__ ci, const double *__restrict__ val,
+                                                    const double *__restrict__ x, long long xs, int compact, double *__restrict__ y, long long ys, unsigned live) {
+    const int lane = threadIdx.x & (TPR - 1);
+    const int group = (blockIdx.x * BLK + threadIdx.x) / TPR;
+    const int ngroups = gridDim.x * (BLK / TPR);
+    const double *xg[G];
+    {
+        int slot = 0;
+#pragma unroll
+        for (int g = 0; g < G; g++) { xg[g] = x + (long long)(compact ? slot : g) * xs; slot += (live >> g) & 1u; }
+    }
+    for (int row = group; row < nrows; row += ngroups) {
+        const int beg = rp[row], end = rp[row + 1];
+        double s0[G], s1[G];
+#pragma unroll
+        for (int g = 0; g < G; g++) { s0[g] = 0.0; s1[g] = 0.0; }
+        int k = beg + lane;
+        for (; k + TPR < end; k += 2 * TPR) {
+            const double v0 = val[k], v1 = val[k + TPR];
+            const int c0 = ci[k], c1 = ci[k + TPR];
+#pragma unroll
+            for (int g = 0; g < G; g++)
+                if ((live >> g) & 1u) {
+                    s0[g] += v0 * xg[g][c0];
+                    s1[g] += v1 * xg[g][c1];
+                }
+        }
+        if (k < end) {
+            const double v0 = val[k]; const int c0 = ci[k];
+#pragma unroll
+            for (int g = 0; g < G; g++) if ((live >> g) & 1u) s0[g] += v0 * xg[g][c0];
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            if ((live >> g) & 1u) {
+                double s = s0[g] + s1[g];
+                for (int o = TPR / 2; o > 0; o >>= 1) s += __shfl_down(s, o, TPR);
+                if (lane == 0) y[(long long)g * ys + row] = s;
+            }
+    }
+}
+// M takes the plain kernel (the callers check: a slab multi-vector product does not exist); the grid is launch_spmv's
+static void launch_spmv_group(QpdoDev *d, const DevCsr &M, const double *x, long long xs, bool compact, double *y, long long ys, unsigned live) {
+    const int g = spmv_grid(M, false);
+#define SPMV_GROUP_GO(T) hipLaunchKernelGGL((k_spmv_group<T, SPMV_GROUP_MAX>), dim3(g), dim3(BLK), 0, d->stream, M.nrows, (const int *)M.rp, (const int *)M.ci, (const double *)M.val, x, xs, compact ? 1 : 0, y, ys, live)
+    switch (M.tpr) {
+        case 4:  SPMV_GROUP_GO(4); break;
+        case 8:  SPMV_GROUP_GO(8); break;
+        case 16: SPMV_GROUP_GO(16); break;
+        case 32: SPMV_GROUP_GO(32); break;
+        default: SPMV_GROUP_GO(64); break;
+    }
+#undef SPMV_GROUP_GO
+    d->st.spmv_calls++;
+    d->st.spmv_bytes += (int64_t)(M.alg_bytes() + (double)(__builtin_popcount(live) - 1) * 8.0 * (M.nrows + M.ncols));
+}
 // The width of the matrix stream of one product of the Schur mode's inner solve: the fp64 values, their fp32 copy, their half-precision copy
 enum StreamWidth { STREAM_F64 = 0, STREAM_F32, STREAM_H16 };
 // One product of the Schur mode's inner CG.  STREAM_F32: pair-wide with the fp32 copy x32 of x where there is one, otherwise slab by slab

@@ -13,6 +13,9 @@ struct Ctrl {
     int cnt[C_COUNT];
     double val[V_COUNT];
 };
+// one right-hand side's slots of the group control array (dev/adjoint.inc adj_sweeps_group): the four maxima the single call keeps in
+// N_A .. N_D of the control block, and the non-finite marker it keeps in C_VIOL
+struct AdjGrpCtrl { u64 nrm[4]; int nonfin, pad; };
 
 // partial-sum slots (each PGRID doubles)
 enum { P_ETA_M = 0, P_BETA_M, P_A0, P_B0, P_DXQDX, P_DXDF, P_PKP, P_RZ, P_RR, P_OOB, P_QDX, P_OBJ, P_F1, P_F2, P_RINF, P_COUNT };
@@ -203,6 +206,14 @@ struct QpdoDev {
     // allocated by the first call that passes the array) and its counters
     double *tan_q = nullptr, *tan_l = nullptr, *tan_u = nullptr, *tan_Q = nullptr, *tan_A = nullptr;
     QdevTangentStats tan{};
+    // the group path of the two calls (dev/adjoint.inc adj_sweeps_group): rhs_group_cfg right-hand sides go through every launch of the sweep
+    // loop at once (QPDO_AMD_RHS_GROUP at setup; the rule that makes it 1: qdev_rhs_group).  The group's vectors -- rhs_group_cfg copies of the
+    // per-right-hand-side work vectors, the solve's columns, the group control array and its pinned host copy -- are allocated by the first
+    // call with nrhs > 1 on a workspace whose group size is above 1 and booked in grp.scratch_bytes alone.
+    int rhs_group_cfg = 8;
+    double *grp_n = nullptr, *grp_m = nullptr, *grp_sol = nullptr;
+    AdjGrpCtrl *grp_ctrl = nullptr, *grp_hctrl = nullptr;
+    QdevGroupStats grp{};
     // what qdev_configure decided; a solve may change these (fallbacks, hybrid), qpdo_amd_update_matrices puts them back
     struct { int linsolve, dense_chain, dense_mid, dense_lookahead, wb_enable, ud_cap, deflate, pcg_maxit, band_b, bc_r; } cfg{};
 };

@@ -1018,6 +1018,29 @@ int qpdo_amd_get_tangent_stats(const QPDOWorkspace *work, QPDOAmdTangentStats *o
     out->sweeps_total = (long)st.sweeps_total; out->scratch_bytes = (long)st.scratch_bytes; out->last_seconds = st.last_seconds;
     return 0;
 }
+/* ---- groups of right-hand sides in the two calls (include/qpdo_amd_ext.h; dev/adjoint.inc adj_sweeps_group) ---- */
+int qpdo_amd_rhs_group(const QPDOWorkspace *work) {
+    if (!work || !work->chol || !work->chol->dev) return -1;
+    return qdev_rhs_group(work->chol->dev);
+}
+int qpdo_amd_get_group_stats(const QPDOWorkspace *work, QPDOAmdGroupStats *out) {
+    if (!work || !work->chol || !work->chol->dev) { qdev_set_error("qpdo_amd_get_group_stats: NULL workspace"); return -1; }
+    if (!out) { qdev_set_error("qpdo_amd_get_group_stats: NULL out"); return -1; }
+    QdevGroupStats st;
+    qdev_get_group_stats(work->chol->dev, &st);
+    out->group = (long)st.group; out->groups_run = (long)st.groups_run; out->rounds_total = (long)st.rounds_total; out->scratch_bytes = (long)st.scratch_bytes;
+    return 0;
+}
+/* the range and pointer checks are made here, before the backend is touched (tests/group_args_driver.c) */
+int qpdo_amd_spmv_group(QPDOWorkspace *work, int which, int nvec, unsigned live_mask, const double *v, double *y) {
+    if (nvec < 1 || nvec > 8) { qdev_set_error("qpdo_amd_spmv_group: nvec must be 1 .. 8"); return -1; }
+    if (live_mask >> nvec) { qdev_set_error("qpdo_amd_spmv_group: live_mask names a vector >= nvec"); return -1; }
+    if (which < 0 || which > 2) { qdev_set_error("qpdo_amd_spmv_group: which is 0 (A), 1 (A') or 2 (Q)"); return -1; }
+    if (!v) { qdev_set_error("qpdo_amd_spmv_group: v is NULL"); return -1; }
+    if (!y) { qdev_set_error("qpdo_amd_spmv_group: y is NULL"); return -1; }
+    if (!work || !work->chol || !work->chol->dev) { qdev_set_error("qpdo_amd_spmv_group: NULL workspace"); return -1; }
+    return qdev_spmv_group(work->chol->dev, which, nvec, live_mask, v, y) ? -1 : 0;
+}
 /* the pointer checks of the two PCG test entries are made here, before the backend is touched (tests/pcg_probe_args_driver.c) */
 int qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, const double *v, double *out, int mode, double *info) {
     if (mode != 0 && mode != 1 && (mode < 32 || mode > 37)) { qdev_set_error("pcg probe: mode is 0 (one K product), 1 (one solve), 32 or 33 (one fp32-stream product), 34 or 35 (one pair-wide fp32 product), 36 or 37 (one pair-wide half-precision product)"); return -1; }

@@ -239,6 +239,15 @@ typedef QdevAdjointStats QdevTangentStats;
 int qdev_tangent(QpdoDev *d, const double *x, const double *y, long nrhs, const double *tq, const double *tl, const double *tu, const QdevCsc *Q,
                  const double *tQx, const double *tAx, double *dx, double *dy, int *active, long *status, double *res, double tol, long max_sweeps);
 int qdev_get_tangent_stats(QpdoDev *d, QdevTangentStats *out);
+/* the group path of the two calls (dev/adjoint.inc): with a group size G > 1 a call with nrhs > 1 carries up to G right-hand sides through
+ * every launch of its sweep loop.  qdev_rhs_group: G >= 1, or 0 on a workspace the two calls refuse (no message is set). */
+typedef struct { int64_t group, groups_run, rounds_total, scratch_bytes; } QdevGroupStats;
+int qdev_rhs_group(QpdoDev *d);
+int qdev_get_group_stats(QpdoDev *d, QdevGroupStats *out);
+/* test hook (qpdo_amd_spmv_group): the multi-vector product of the group path on nvec host vectors, the slabs of live_mask only.  The
+ * range checks of nvec, the mask and the pointers are the caller's; a matrix on the slab kernel and a row-partitioned workspace are
+ * refused here before anything is launched. */
+int qdev_spmv_group(QpdoDev *d, int which, int nvec, unsigned live_mask, const double *v_host, double *y_host);
 /* the PCG path as single steps (tests; qpdo_amd_pcg_probe, dev/host_probe.inc): mode 0 one K product after build_compact, mode 1 one
  * pcg_solve; and the compact structures the last of either left (qpdo_amd_download_compact).  info: QDEV_PCG_INFO_LEN doubles. */
 #define QDEV_PCG_NOT_CONVERGED (-7)

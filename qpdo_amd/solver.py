@@ -124,7 +124,8 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_packed_matrix_layout", "qpdo_amd_fleet_get_packed_matrix_layout", "qpdo_amd_fleet_update_matrices_dev",
                "qpdo_amd_fleet_adjoint_dev", "qpdo_amd_fleet_get_adjoint_stats",
                "qpdo_amd_fleet_adjoint_multi_dev", "qpdo_amd_fleet_tangent_dev", "qpdo_amd_fleet_rhs_group", "qpdo_amd_fleet_get_sensitivity_stats",
-               "qpdo_amd_adjoint", "qpdo_amd_get_adjoint_stats", "qpdo_amd_tangent", "qpdo_amd_get_tangent_stats"]
+               "qpdo_amd_adjoint", "qpdo_amd_get_adjoint_stats", "qpdo_amd_tangent", "qpdo_amd_get_tangent_stats",
+               "qpdo_amd_rhs_group", "qpdo_amd_get_group_stats", "qpdo_amd_spmv_group"]
 
 
 class AdjointStats(C.Structure):
@@ -137,6 +138,11 @@ class TangentStats(C.Structure):
     """QPDOAmdTangentStats (include/qpdo_amd_ext.h)"""
     _fields_ = [("calls", C.c_long), ("rhs_total", C.c_long), ("factorizations", C.c_long), ("sweeps_total", C.c_long),
                 ("scratch_bytes", C.c_long), ("last_seconds", C.c_double)]
+
+
+class GroupStats(C.Structure):
+    """QPDOAmdGroupStats (include/qpdo_amd_ext.h)"""
+    _fields_ = [("group", C.c_long), ("groups_run", C.c_long), ("rounds_total", C.c_long), ("scratch_bytes", C.c_long)]
 
 
 class FleetStats(C.Structure):
@@ -230,6 +236,13 @@ def lib():
             L.qpdo_amd_tangent.restype = C.c_int
             L.qpdo_amd_get_tangent_stats.argtypes = [W, C.POINTER(TangentStats)]
             L.qpdo_amd_get_tangent_stats.restype = C.c_int
+        if hasattr(L, "qpdo_amd_rhs_group"):
+            L.qpdo_amd_rhs_group.argtypes = [W]
+            L.qpdo_amd_rhs_group.restype = C.c_int
+            L.qpdo_amd_get_group_stats.argtypes = [W, C.POINTER(GroupStats)]
+            L.qpdo_amd_get_group_stats.restype = C.c_int
+            L.qpdo_amd_spmv_group.argtypes = [W, C.c_int, C.c_int, C.c_uint, dp, dp]
+            L.qpdo_amd_spmv_group.restype = C.c_int
         L.qpdo_amd_dist_config.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.qpdo_amd_dist_unique_id.argtypes = [C.c_void_p]
         L.qpdo_amd_solve_batch.restype = C.c_long
@@ -681,6 +694,98 @@ class QPDO:
         if lib().qpdo_amd_get_tangent_stats(self._w, C.byref(s)):
             raise RuntimeError("tangent_stats: %s" % (lib().qpdo_amd_last_error() or b"").decode())
         return {f: getattr(s, f) for f, _ in TangentStats._fields_}
+
+    def rhs_group(self):
+        """The right-hand sides adjoint / tangent carry through every launch of their sweep loop at once on this workspace
+        (qpdo_amd_rhs_group): 8 where it qualifies, 1: one after the other, 0: a workspace the two calls refuse."""
+        g = lib().qpdo_amd_rhs_group(self._w)
+        if g < 0:
+            raise RuntimeError("rhs_group: no workspace (call setup first)")
+        return g
+
+    def group_stats(self):
+        s = GroupStats()
+        if lib().qpdo_amd_get_group_stats(self._w, C.byref(s)):
+            raise RuntimeError("group_stats: %s" % (lib().qpdo_amd_last_error() or b"").decode())
+        return {f: getattr(s, f) for f, _ in GroupStats._fields_}
+
+    def spmv_group(self, which, v, live_mask, fill=0.0):
+        """Test hook (qpdo_amd_spmv_group): y[g] = M v[g] for the slabs g of live_mask; v: (nvec, ncols).  The other slabs of the
+        returned (nvec, nrows) array keep `fill`."""
+        v = np.ascontiguousarray(v, np.float64)
+        rows = {0: self.m, 1: self.n, 2: self.n}[which]
+        y = np.full((v.shape[0], rows), fill)
+        rc = lib().qpdo_amd_spmv_group(self._w, which, v.shape[0], int(live_mask), _as_dp(v), _as_dp(y))
+        if rc:
+            raise RuntimeError(lib().qpdo_amd_last_error().decode())
+        return y
+
+    def jacobian(self, wrt=("q", "l", "u"), outputs=("x",), mode="auto", tol=1e-9, max_sweeps=20):
+        """Dense Jacobians of the last solve's solution at the fixed active set: dx_dq (n x n), dx_dl, dx_du (n x m) for the names in wrt
+        and, with "y" in outputs, dy_dq (m x n), dy_dl, dy_du (m x m), from ONE call with many right-hand sides -- which the workspace
+        carries through its sweeps in groups (rhs_group()).
+          mode="tangent": R = the sum of the sizes of wrt; column j of d._dq is tangent(tq = e_j), of d._dl tangent(tl = e_j), ...
+          mode="adjoint": R = the sum of the sizes of outputs; row i of dx_d. is adjoint(gx = e_i), row i of dy_d. adjoint(gx = 0, gy = e_i)
+          mode="auto": the mode with fewer right-hand sides, adjoint on a tie.
+        Returns a dict with the requested blocks, active (m,) int32, status (R, 3) int64 and the mode taken.  A right-hand side whose
+        code is not 0 leaves NaN in its column (tangent) or row (adjoint) of every block.  Host memory: the call's arrays hold R x (n + m)
+        doubles each (the unit right-hand sides and the results); the blocks returned are copies of those.  Names are checked before
+        any library call; a refused call raises RuntimeError with the reason."""
+        def names(arg, what, allowed):
+            if isinstance(arg, str) or not isinstance(arg, (tuple, list)):
+                raise ValueError("%s: expected a tuple of names from %s, got %r" % (what, allowed, arg))
+            for a in arg:
+                if a not in allowed:
+                    raise ValueError("%s: unknown name %r (expected names from %s)" % (what, a, allowed))
+            if len(set(arg)) != len(arg):
+                raise ValueError("%s: a name is given twice: %r" % (what, tuple(arg)))
+            if not arg:
+                raise ValueError("%s: expected at least one name from %s" % (what, allowed))
+            return tuple(arg)
+        wrt = names(wrt, "wrt", ("q", "l", "u"))
+        outputs = names(outputs, "outputs", ("x", "y"))
+        if mode not in ("auto", "tangent", "adjoint"):
+            raise ValueError("mode: expected 'auto', 'tangent' or 'adjoint', got %r" % (mode,))
+        if not self._w:
+            raise RuntimeError("jacobian: no workspace (call setup first)")
+        n, m = self.n, self.m
+        size = {"q": n, "l": m, "u": m, "x": n, "y": m}
+        r_tan, r_adj = sum(size[k] for k in wrt), sum(size[k] for k in outputs)
+        if mode == "auto":
+            mode = "tangent" if r_tan < r_adj else "adjoint"
+        out = {"mode": mode}
+        if mode == "tangent":
+            if r_tan < 1:
+                raise ValueError("wrt: the names given have no entries on this workspace (m = 0)")
+            arrs, off = {}, 0
+            for k in wrt:
+                a = np.zeros((r_tan, size[k]))
+                a[off + np.arange(size[k]), np.arange(size[k])] = 1.0
+                arrs["t" + k] = a
+                off += size[k]
+            t = self.tangent(tol=tol, max_sweeps=max_sweeps, **arrs)
+            off = 0
+            for k in wrt:
+                for o in outputs:
+                    out["d%s_d%s" % (o, k)] = np.ascontiguousarray(t["d" + o][off:off + size[k]].T)
+                off += size[k]
+            out["active"], out["status"] = t["active"], t["status"]
+            return out
+        if r_adj < 1:
+            raise ValueError("outputs: the names given have no entries on this workspace (m = 0)")
+        gx, gy = np.zeros((r_adj, n)), (np.zeros((r_adj, m)) if "y" in outputs else None)
+        off = 0
+        for o in outputs:
+            (gx if o == "x" else gy)[off + np.arange(size[o]), np.arange(size[o])] = 1.0
+            off += size[o]
+        a = self.adjoint(gx, gy, tol=tol, max_sweeps=max_sweeps)
+        off = 0
+        for o in outputs:
+            for k in wrt:
+                out["d%s_d%s" % (o, k)] = a["d" + k][off:off + size[o]].copy()
+            off += size[o]
+        out["active"], out["status"] = a["active"], a["status"]
+        return out
 
     def _pcg_probe(self, dw, sigma, v, mode):
         dw = np.ascontiguousarray(dw, np.float64)
