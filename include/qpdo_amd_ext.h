@@ -29,6 +29,11 @@
  *                    QPDOAmdStats.coupled_*).  No such row: the plain band solver, bit for bit.  More than R: the matrix counts as not
  *                    banded ("band" makes qpdo_setup fail with a message that names both numbers).  Q or the other rows wider than 127:
  *                    the half-bandwidth over all rows, as without the variable.  Read at qpdo_setup; one GPU
+ *   QPDO_BAND_ORDER  unset, "" or "0": the band solver works in the caller's variable order (default).  "rcm": qpdo_setup computes a reverse
+ *                    Cuthill-McKee order of the pattern of Q + A'A on the host and, where that narrows the half-bandwidth, the band
+ *                    detection, the selection rule above and the band solver run on the reordered matrix (qpdo_amd_band_order_config
+ *                    below, which overrides the variable, has the contract and the kinds of workspace that ignore it).  Any other value
+ *                    makes qpdo_setup fail with a message
  *   QPDO_HYBRID      where the dense solver is selected automatically and n >= 8192, every solve starts with PCG and switches to the dense
  *                    factor at the first Newton pass that needs more than 450 PCG iterations (default since round 4; same per-pass integers;
  *                    QPDOAmdStats.hybrid_pcg_passes counts the PCG passes; every numerical PCG failure hands the pass to the dense factor).  "0": off; "1": on from n = 4096; "<budget>" > 1: on from n = 4096 with that budget
@@ -258,10 +263,50 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
  *     9  the coupled geometry, 4 entries: r = the coupling rows of the workspace, k = those with a nonzero weight at the last factorization,
  *            b_core, np (k and np 0 before the first factorization).
  *    10  the r coupling row numbers, ascending, as doubles.
- *    11  Z      np x k, leading dimension np: column j = B^-1 (the j-th weighted coupling row, ascending, as a dense column).  */
+ *    11  Z      np x k, leading dimension np: column j = B^-1 (the j-th weighted coupling row, ascending, as a dense column).
+ *   band under a variable order (qpdo_amd_band_order_config below):
+ *    12  newold n entries as doubles: newold[k] = the caller's index of the variable at position k of the solver's order (-1 with a
+ *               message on a workspace that adopted none).  On such a workspace arrays 4, 5, 7 and 8 are in the SOLVER's order: they
+ *               hold the factor of P K P', P K P'(k, l) = K(newold[k], newold[l]).  */
 #define QPDO_AMD_DIRECT_LOST (-2)
 int  qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags);
 int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count);
+/* ---- a variable order for the band solver (qpdo_amd/csrc/band_order.c) ------------------------------------------------------
+ * The band solver factors K in the order of its variables; band_detect measures the half-bandwidth in the caller's order.  A chain QP
+ * whose variables are not numbered along the chain (all states, then all inputs; one block per signal) is banded only after a
+ * relabelling.  Opt-in: with nothing configured every workspace, launch and bit is what it is without this section.
+ *
+ * qpdo_amd_band_order: reverse Cuthill-McKee on the pattern of Q + A'A (never formed: the search walks the rows of A), O(nnz), pure
+ *   host code, deterministic.  Q's stype is honoured as qpdo_setup honours it, explicit zeros count, both itypes; A may be NULL or
+ *   have no rows.  newold[k] = the caller's index of the variable that takes position k (n entries); info4 (may be NULL) =
+ *   {b_natural, b_ordered, connected components, early_out}: the exact half-bandwidths (the largest |i - j| over the stored entries
+ *   of Q, the largest column span over the rows of A) in the caller's order and under newold -- the solver itself never goes below 3.
+ *   A row of A with more than 1024 entries forces a half-bandwidth above 1023 under every order: the identity comes back at once,
+ *   early_out = 1.  Degrees are exact (distinct neighbours; sum of squared row lengths of work, at most 1024 nnz(A)); the searches
+ *   are O(nnz).  Returns 0, or -1 (bad arguments, no memory).
+ * qpdo_amd_band_order_config: applies to the workspaces set up afterwards in this process (read once per qpdo_setup, as
+ *   qpdo_amd_dist_config).  ENV (the default): QPDO_BAND_ORDER decides.  RCM: qpdo_setup runs qpdo_amd_band_order and adopts the
+ *   order only if b_ordered < b_natural; otherwise the workspace is the natural-order one, bit for bit, nothing allocated.  GIVEN:
+ *   newold (n entries, copied) is adopted always, the identity included; -1 with a message if it is not a permutation of 0 .. n-1,
+ *   and a qpdo_setup whose n differs fails with a message.  The selection rule of QPDO_LINSOLVE then runs on the adopted
+ *   half-bandwidth (automatic: b <= 127 and n >= 2048; "band": b <= 1023 and n >= 4 (b + 1)), the PCG rescue included.
+ *   An adopted order costs two int32 arrays of n on the device.  The assembly kernels write the band of P K P' (the same bits the
+ *   natural-order band of K holds for the same entries); every solve takes its right-hand side and delivers its solution in the
+ *   CALLER's order -- the gather and the scatter are folded into the solve kernels' first load and last store: one launch per solve,
+ *   as without an order -- so qpdo_amd_direct_solve, qpdo_amd_adjoint / _tangent (groups of 8 included), the band fallback ladder,
+ *   qpdo_amd_update_matrices (fixed pattern: the order stays) and qpdo_update_q see no difference.
+ *   IGNORED (the natural order is kept, `reason` says why): 2 row-partitioned workspaces; 3 QPDO_BAND_COUPLING > 0 (a coupling row is
+ *   wide under every order); 4 workspaces on the fused small-problem route; 5 QPDO_LINSOLVE = dense or pcg.  reason 1: RCM found no
+ *   narrower order.  0: adopted, or nothing configured.
+ * qpdo_amd_get_band_order: what the workspace's setup decided; newold (n entries, or NULL) is written only when adopted = 1. */
+#define QPDO_AMD_BAND_ORDER_ENV     0   /* default: QPDO_BAND_ORDER in the environment decides ("rcm"; unset, "" or "0": natural) */
+#define QPDO_AMD_BAND_ORDER_NATURAL 1
+#define QPDO_AMD_BAND_ORDER_RCM     2
+#define QPDO_AMD_BAND_ORDER_GIVEN   3   /* newold (n entries, copied; must be a permutation of 0..n-1, else -1 with a message) */
+typedef struct { long mode, adopted, b_natural, b_ordered, reason; double order_seconds; } QPDOAmdBandOrderInfo;
+int  qpdo_amd_band_order(const cholmod_sparse *Q, const cholmod_sparse *A, long *newold, long *info4);
+int  qpdo_amd_band_order_config(int mode, const long *newold, long n);
+int  qpdo_amd_get_band_order(const QPDOWorkspace *work, QPDOAmdBandOrderInfo *out, long *newold /* n entries or NULL */);
 /* ---- the PCG linear-solve path as single steps (tests of its pieces; tests/test_gpu_pcg_pieces.py) ------------------------------------
  * K = Q + sigma I + A' diag(dw) A with the workspace's stored matrices (the caller's own with settings->scaling = 0), dw: m weights; a row
  * is "weighted" when dw_i != 0.0 (so -0.0 is not, a subnormal is).  Only for PCG workspaces (QPDO_LINSOLVE=pcg) on one GPU: a dense, band

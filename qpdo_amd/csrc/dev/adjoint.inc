@@ -448,6 +448,7 @@ static int adj_vectors(QpdoDev *d, AdjCall &c, long nrhs, int64_t *booked) {
         if (rc) return rc;
         HIPCHK(hipHostMalloc((void **)&d->grp_hctrl, SPMV_GROUP_MAX * sizeof(AdjGrpCtrl), hipHostMallocCoherent));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_group), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
+        if (d->bo_newold) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_group_perm), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
         d->grp.scratch_bytes += (int64_t)(((size_t)5 * Gc * ((size_t)n + m) + sol) * 8 + SPMV_GROUP_MAX * sizeof(AdjGrpCtrl));
     }
     c.G = G; c.bn = d->grp_n; c.bm = d->grp_m;
@@ -602,8 +603,12 @@ static int adj_sweeps_group(QpdoDev *d, AdjCall &c, int cnt, bool have_ry, doubl
         const int nl = __builtin_popcount(live);
         if (c.kind == 3) {
             const size_t lds = (size_t)4 * BAND_SC * (d->band_b + 1) * sizeof(double);
-            hipLaunchKernelGGL(k_band_solve_group, dim3(nl), dim3(256), lds, d->stream, n, d->band_np, d->band_b, (const double *)d->Kb, (const double *)d->Lt,
-                               (const double *)c.srhs, (long long)n, c.sz, c.sdvx);
+            if (d->bo_newold)
+                hipLaunchKernelGGL(k_band_solve_group_perm, dim3(nl), dim3(256), lds, d->stream, n, d->band_np, d->band_b, (const double *)d->Kb, (const double *)d->Lt,
+                                   (const double *)c.srhs, (long long)n, c.sz, c.sdvx, (const int *)d->bo_newold);
+            else
+                hipLaunchKernelGGL(k_band_solve_group, dim3(nl), dim3(256), lds, d->stream, n, d->band_np, d->band_b, (const double *)d->Kb, (const double *)d->Lt,
+                                   (const double *)c.srhs, (long long)n, c.sz, c.sdvx);
         } else {
             const int ld = d->dense_ld;
             LAUNCH(k_dense_load_rhs_group, dim3(vgrid(ld), nl), n, ld, (const double *)c.srhs, (long long)n, c.sx, c.spub1, c.spub2);

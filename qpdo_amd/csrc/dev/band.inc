@@ -31,34 +31,55 @@ __global__ void k_band_span_Q(int n, const int *__restrict__ rp, const int *__re
 // assembly: one wave per column j, accumulator of b + 1 doubles in LDS; Q first, then the weighted rows of A that touch column j in
 // ascending order, sigma_f last -- the per-element order of k_dense_assemble, so the band holds the very values the dense matrix would.
 // Columns n .. np-1 (np = n rounded up to 4) are identity padding: the factorization takes four columns per step.
-__global__ __launch_bounds__(256) void k_band_assemble(int n, int np, int b, const int *__restrict__ qrp, const int *__restrict__ qci,
-                                                      const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
-                                                      const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
-                                                      const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
-                                                      double *__restrict__ Kb) {
-    __shared__ double acc_s[4][128];
+// PERM (a variable order of the band solver, dev/host_band.inc): the wave of column pj assembles the caller's column j = newold[pj], and an
+// entry with the caller's row i lands at oldnew[i] - pj when that is in 0 .. b -- the band of P K P', each element summed in the order
+// above, so it holds the very bits the natural-order band of K holds for the same entries.  PERM = false is the code without an order.
+template <bool PERM>
+__device__ __forceinline__ void band_assemble_body(int n, int np, int b, const int *__restrict__ qrp, const int *__restrict__ qci,
+                                                   const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
+                                                   const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                   const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
+                                                   double *__restrict__ Kb, const int *__restrict__ newold, const int *__restrict__ oldnew,
+                                                   double (*acc_s)[128]) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, B1 = b + 1;
     double *acc = acc_s[wave];
-    for (int j = blockIdx.x * 4 + wave; j < np; j += gridDim.x * 4) {
-        double *col = Kb + (size_t)j * B1;
-        if (j >= n) { for (int t = lane; t <= b; t += 64) col[t] = (t == 0) ? 1.0 : 0.0; continue; }
+    for (int pj = blockIdx.x * 4 + wave; pj < np; pj += gridDim.x * 4) {
+        double *col = Kb + (size_t)pj * B1;
+        if (pj >= n) { for (int t = lane; t <= b; t += 64) col[t] = (t == 0) ? 1.0 : 0.0; continue; }
+        const int j = PERM ? newold[pj] : pj;
         acc[lane] = 0.0; acc[lane + 64] = 0.0;
         __builtin_amdgcn_wave_barrier();
-        for (int k = qrp[j] + lane; k < qrp[j + 1]; k += 64) { const int c = qci[k]; if (c >= j && c - j <= b) acc[c - j] += qval[k]; }
+        for (int k = qrp[j] + lane; k < qrp[j + 1]; k += 64) { const int c = PERM ? oldnew[qci[k]] : qci[k]; if (c >= pj && c - pj <= b) acc[c - pj] += qval[k]; }
         __builtin_amdgcn_wave_barrier();
         for (int t = trp[j]; t < trp[j + 1]; t++) {                   // (uniform over the wave)
             const int r = tci[t];
             const double wgt = dw[r];
             if (wgt == 0.0) continue;
             const double vj = wgt * tval[t];
-            for (int e = arp[r] + lane; e < arp[r + 1]; e += 64) { const int i = aci[e]; if (i >= j && i - j <= b) acc[i - j] += vj * aval[e]; }
+            for (int e = arp[r] + lane; e < arp[r + 1]; e += 64) { const int i = PERM ? oldnew[aci[e]] : aci[e]; if (i >= pj && i - pj <= b) acc[i - pj] += vj * aval[e]; }
             __builtin_amdgcn_wave_barrier();                          // one wave: its LDS operations are served in order
         }
         if (lane == 0) acc[0] += sigma_f;
         __builtin_amdgcn_wave_barrier();
-        for (int t = lane; t <= b; t += 64) col[t] = (j + t < n) ? acc[t] : 0.0;
+        for (int t = lane; t <= b; t += 64) col[t] = (pj + t < n) ? acc[t] : 0.0;
         __builtin_amdgcn_wave_barrier();
     }
+}
+__global__ __launch_bounds__(256) void k_band_assemble(int n, int np, int b, const int *__restrict__ qrp, const int *__restrict__ qci,
+                                                      const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
+                                                      const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                      const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
+                                                      double *__restrict__ Kb) {
+    __shared__ double acc_s[4][128];
+    band_assemble_body<false>(n, np, b, qrp, qci, qval, trp, tci, tval, arp, aci, aval, dw, sigma_f, Kb, nullptr, nullptr, acc_s);
+}
+__global__ __launch_bounds__(256) void k_band_assemble_perm(int n, int np, int b, const int *__restrict__ qrp, const int *__restrict__ qci,
+                                                           const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
+                                                           const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                           const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
+                                                           double *__restrict__ Kb, const int *__restrict__ newold, const int *__restrict__ oldnew) {
+    __shared__ double acc_s[4][128];
+    band_assemble_body<true>(n, np, b, qrp, qci, qval, trp, tci, tval, arp, aci, aval, dw, sigma_f, Kb, newold, oldnew, acc_s);
 }
 // natural-order LDL' inside the band, four columns per step (the leading 4 x 4 block is factored redundantly by every thread, the panel
 // rows and the trailing window are updated in parallel: the scheme of the fused small-problem kernel, on a window that slides).  The ring
@@ -207,13 +228,18 @@ __device__ __forceinline__ double band_rl64(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 // (the body of k_band_solve; k_band_solve_multi runs it once per workgroup on a column of its own)
+// PERM (a variable order, see band_assemble_body): rhs and x are in the caller's order -- entry i of the solver's order is read from
+// rhs[perm[i]] and delivered to x[perm[i]], perm = newold; the gather and the scatter ARE the sweep's first loads and last stores, no
+// launch and no vector of their own.  z stays in the solver's order.  PERM = false is the code without an order.
+template <bool PERM>
 __device__ __forceinline__ void band_solve_body(int n, int b, const double *__restrict__ Lb, const double *__restrict__ Lt, const double *__restrict__ rhs,
-                                                double *__restrict__ z, double *__restrict__ x) {
+                                                double *__restrict__ z, double *__restrict__ x, const int *__restrict__ perm) {
     extern __shared__ __attribute__((aligned(16))) double band_sbuf[];       // 4 x (BAND_SC * B1)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, B1 = b + 1, CH = BAND_SC * B1;
     const int nchunks = (n + BAND_SC - 1) / BAND_SC;
     const long long total = (long long)n * B1;
     auto ld = [&](const double *v, int i) { return (i >= 0 && i < n) ? v[i] : 0.0; };
+    auto ld_rhs = [&](int i) { return (i >= 0 && i < n) ? rhs[PERM ? perm[i] : i] : 0.0; };
     auto copy_chunk = [&](const double *src, int c, int t0, int nt) {          // columns c*SC .. c*SC + SC - 1 of the band: CH contiguous doubles
         if (c < 0 || c >= nchunks) return;
         double *dst = band_sbuf + (size_t)(c & 3) * CH;
@@ -240,7 +266,7 @@ __device__ __forceinline__ void band_solve_body(int n, int b, const double *__re
     copy_chunk(Lb, 0, tid, 256); copy_chunk(Lb, 1, tid, 256);
     if (wave != 0) chunk_load(Lb, 2);
     BAND_SYNC();
-    double s0 = ld(rhs, lane), s1 = ld(rhs, 64 + lane), s2 = ld(rhs, 128 + lane);
+    double s0 = ld_rhs(lane), s1 = ld_rhs(64 + lane), s2 = ld_rhs(128 + lane);
     for (int g = 0; g < nchunks; g++) {
         if (wave != 0) { chunk_store(g + 2); chunk_load(Lb, g + 3); }
         else {
@@ -265,7 +291,7 @@ __device__ __forceinline__ void band_solve_body(int n, int b, const double *__re
                 const int gc = (lane < BAND_SC) ? (jb / BAND_SC) : (jb / BAND_SC + 1);
                 const double dd = (jb + lane < n) ? band_sbuf[(size_t)(gc & 3) * CH + (size_t)(lane & (BAND_SC - 1)) * B1] : 1.0;
                 if (jb + lane < n) z[jb + lane] = s0 / dd;
-                s0 = s1; s1 = s2; s2 = ld(rhs, jb + 192 + lane);
+                s0 = s1; s1 = s2; s2 = ld_rhs(jb + 192 + lane);
             }
         }
         BAND_SYNC();
@@ -298,7 +324,7 @@ __device__ __forceinline__ void band_solve_body(int n, int b, const double *__re
                 }
             }
             if ((g & 1) == 0) {                                    // rows jb .. jb + 63 are final
-                if (jb + lane < n) x[jb + lane] = s0;
+                if (jb + lane < n) x[PERM ? perm[jb + lane] : jb + lane] = s0;
                 s0 = s1; s1 = s2; s2 = ld(z, jb - 192 + lane);
             }
         }
@@ -307,14 +333,24 @@ __device__ __forceinline__ void band_solve_body(int n, int b, const double *__re
 }
 __global__ __launch_bounds__(256) void k_band_solve(int n, int b, const double *__restrict__ Lb, const double *__restrict__ Lt,
                                                     const double *__restrict__ rhs, double *__restrict__ z, double *__restrict__ x) {
-    band_solve_body(n, b, Lb, Lt, rhs, z, x);
+    band_solve_body<false>(n, b, Lb, Lt, rhs, z, x, nullptr);
+}
+__global__ __launch_bounds__(256) void k_band_solve_perm(int n, int b, const double *__restrict__ Lb, const double *__restrict__ Lt,
+                                                         const double *__restrict__ rhs, double *__restrict__ z, double *__restrict__ x,
+                                                         const int *__restrict__ perm) {
+    band_solve_body<true>(n, b, Lb, Lt, rhs, z, x, perm);
 }
 // the group path's solve (dev/adjoint.inc adj_sweeps_group): one workgroup per live right-hand side, each running k_band_solve's two sweeps
 // on columns of its own (rhs and x: ldx apart, z: np apart) -- the columns advance together on different CUs for the time of one solve
 __global__ __launch_bounds__(256) void k_band_solve_group(int n, int np, int b, const double *__restrict__ Lb, const double *__restrict__ Lt,
                                                           const double *rhs, long long ldx, double *z, double *x) {
     const long long s = blockIdx.x;
-    band_solve_body(n, b, Lb, Lt, rhs + s * ldx, z + s * np, x + s * ldx);
+    band_solve_body<false>(n, b, Lb, Lt, rhs + s * ldx, z + s * np, x + s * ldx, nullptr);
+}
+__global__ __launch_bounds__(256) void k_band_solve_group_perm(int n, int np, int b, const double *__restrict__ Lb, const double *__restrict__ Lt,
+                                                               const double *rhs, long long ldx, double *z, double *x, const int *__restrict__ perm) {
+    const long long s = blockIdx.x;
+    band_solve_body<true>(n, b, Lb, Lt, rhs + s * ldx, z + s * np, x + s * ldx, perm);
 }
 
 // ---- chain QPs with a few dense coupling rows (QPDO_BAND_COUPLING; host side: dev/host_band.inc) ------------------------------------------
@@ -390,7 +426,7 @@ __global__ __launch_bounds__(256) void k_band_solve_multi(int n, int np, int b, 
     __syncthreads();
     for (int e = arp[row] + threadIdx.x; e < arp[row + 1]; e += 256) u[aci[e]] = aval[e];
     __syncthreads();
-    band_solve_body(n, b, Lb, Lt, u, T + (size_t)s * np, Z + (size_t)s * np);
+    band_solve_body<false>(n, b, Lb, Lt, u, T + (size_t)s * np, Z + (size_t)s * np, nullptr);
 }
 // S(a, c) = [a == c] / d_a + A(row_a, :) Z(:, slot_c) over the active slots, a <= c and its mirror image (k_wb_G's scheme; leading
 // dimension BC_MAX)

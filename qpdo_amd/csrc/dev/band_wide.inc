@@ -24,28 +24,32 @@ static const int BW_T = DNB * DNB;                                 // doubles pe
 // assembly: one wave per column j, accumulator of 64 (w + 1) doubles in LDS (the column's part of its w + 1 tiles); k_band_assemble's
 // per-element order -- Q first, then the weighted rows of A that touch column j in ascending order, sigma_f last -- so the tiles hold the
 // very values the dense and the narrow-band matrices would.
-__global__ __launch_bounds__(256) void k_bw_assemble(int n, int np, int b, int w, const int *__restrict__ qrp, const int *__restrict__ qci,
-                                                    const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
-                                                    const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
-                                                    const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
-                                                    double *__restrict__ Wb, double *__restrict__ Wdiag) {
-    __shared__ double acc_s[4][DNB * (BW_MAX_W + 1)];
+// PERM: band_assemble_body's rule (dev/band.inc) -- column pj of the tiles is the caller's column newold[pj], the caller's row i lands in row
+// oldnew[i]; PERM = false is the code without an order.
+template <bool PERM>
+__device__ __forceinline__ void bw_assemble_body(int n, int np, int b, int w, const int *__restrict__ qrp, const int *__restrict__ qci,
+                                                 const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
+                                                 const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                 const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
+                                                 double *__restrict__ Wb, double *__restrict__ Wdiag, const int *__restrict__ newold,
+                                                 const int *__restrict__ oldnew, double (*acc_s)[DNB * (BW_MAX_W + 1)]) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, len = DNB * (w + 1);
     double *acc = acc_s[wave];
-    for (int j = blockIdx.x * 4 + wave; j < np; j += gridDim.x * 4) {
-        const int J = j >> 6, c = j & 63, r0 = J * DNB;             // acc[i - r0] = K(i, j), r0 <= i < r0 + len (j - r0 + b < len)
+    for (int pj = blockIdx.x * 4 + wave; pj < np; pj += gridDim.x * 4) {
+        const int J = pj >> 6, c = pj & 63, r0 = J * DNB;           // acc[i - r0] = K(i, pj), r0 <= i < r0 + len (pj - r0 + b < len)
         double *tiles = Wb + (size_t)J * (w + 1) * BW_T + (size_t)c * DNB, *dcol = Wdiag + (size_t)J * BW_T + (size_t)c * DNB;
         for (int t = lane; t < len; t += 64) acc[t] = 0.0;
         __builtin_amdgcn_wave_barrier();
-        if (j < n) {
-            for (int k = qrp[j] + lane; k < qrp[j + 1]; k += 64) { const int i = qci[k]; if (i >= j && i - j <= b) acc[i - r0] += qval[k]; }
+        if (pj < n) {
+            const int j = PERM ? newold[pj] : pj;
+            for (int k = qrp[j] + lane; k < qrp[j + 1]; k += 64) { const int i = PERM ? oldnew[qci[k]] : qci[k]; if (i >= pj && i - pj <= b) acc[i - r0] += qval[k]; }
             __builtin_amdgcn_wave_barrier();
             for (int t = trp[j]; t < trp[j + 1]; t++) {               // (uniform over the wave)
                 const int r = tci[t];
                 const double wgt = dw[r];
                 if (wgt == 0.0) continue;
                 const double vj = wgt * tval[t];
-                for (int e = arp[r] + lane; e < arp[r + 1]; e += 64) { const int i = aci[e]; if (i >= j && i - j <= b) acc[i - r0] += vj * aval[e]; }
+                for (int e = arp[r] + lane; e < arp[r + 1]; e += 64) { const int i = PERM ? oldnew[aci[e]] : aci[e]; if (i >= pj && i - pj <= b) acc[i - r0] += vj * aval[e]; }
                 __builtin_amdgcn_wave_barrier();                      // one wave: its LDS operations are served in order
             }
             if (lane == 0) acc[c] += sigma_f;
@@ -53,12 +57,29 @@ __global__ __launch_bounds__(256) void k_bw_assemble(int n, int np, int b, int w
         __builtin_amdgcn_wave_barrier();
         for (int t = lane; t < len; t += 64) {
             const int i = r0 + t;
-            const double v = (i >= j && i - j <= b && (i < n || i == j)) ? acc[t] : 0.0;
+            const double v = (i >= pj && i - pj <= b && (i < n || i == pj)) ? acc[t] : 0.0;
             if (t < DNB) { dcol[t] = v; tiles[t] = 0.0; }
             else tiles[(size_t)(t >> 6) * BW_T + (t & 63)] = v;
         }
         __builtin_amdgcn_wave_barrier();
     }
+}
+__global__ __launch_bounds__(256) void k_bw_assemble(int n, int np, int b, int w, const int *__restrict__ qrp, const int *__restrict__ qci,
+                                                    const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
+                                                    const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                    const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
+                                                    double *__restrict__ Wb, double *__restrict__ Wdiag) {
+    __shared__ double acc_s[4][DNB * (BW_MAX_W + 1)];
+    bw_assemble_body<false>(n, np, b, w, qrp, qci, qval, trp, tci, tval, arp, aci, aval, dw, sigma_f, Wb, Wdiag, nullptr, nullptr, acc_s);
+}
+__global__ __launch_bounds__(256) void k_bw_assemble_perm(int n, int np, int b, int w, const int *__restrict__ qrp, const int *__restrict__ qci,
+                                                         const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
+                                                         const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                         const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
+                                                         double *__restrict__ Wb, double *__restrict__ Wdiag, const int *__restrict__ newold,
+                                                         const int *__restrict__ oldnew) {
+    __shared__ double acc_s[4][DNB * (BW_MAX_W + 1)];
+    bw_assemble_body<true>(n, np, b, w, qrp, qci, qval, trp, tci, tval, arp, aci, aval, dw, sigma_f, Wb, Wdiag, newold, oldnew, acc_s);
 }
 // S: DG_LDS doubles for the elimination of the diagonal tile + the two [32][80] operand images of the panel product (reused as the
 // [col][row] image of the result)
@@ -183,10 +204,12 @@ __global__ __launch_bounds__(256) void k_bw_update(int k, int w, double *__restr
 // loads its next tile (64 doubles per lane) while it multiplies the current one -- across the steps' barriers too -- and the inverse and
 // the right-hand side of step J + 1 are loaded during step J.  Wave v takes the tiles s = v + 1, v + 5, ...; partial sums are added in a
 // fixed order.
-template <bool FWD>
+// PERM (a variable order): the forward sweep's `in` and the backward sweep's `out` are in the caller's order, entry i of the solver's order at
+// perm[i] (band_solve_body's rule, dev/band.inc)
+template <bool FWD, bool PERM>
 __device__ __forceinline__ void bw_sweep(int nbc, int w, const double *__restrict__ Wb, const double *__restrict__ inv, const double *__restrict__ Wd,
                                          const double *__restrict__ in, int nin, double *__restrict__ out, int nout, double (*win)[DNB],
-                                         double (*part)[DNB], double (*part2)[DNB], double *tot) {
+                                         double (*part)[DNB], double (*part2)[DNB], double *tot, const int *__restrict__ perm) {
     const int tid = threadIdx.x, v = tid >> 6, l = tid & 63;
     auto lim = [&](int J) { const int r = FWD ? J : nbc - 1 - J; return r < w ? r : w; };
     auto tile_of = [&](int J, int s) { return FWD ? Wb + ((size_t)(J - s) * (w + 1) + s) * BW_T : Wb + ((size_t)J * (w + 1) + s) * BW_T; };
@@ -210,11 +233,11 @@ __device__ __forceinline__ void bw_sweep(int nbc, int w, const double *__restric
     const int J0 = FWD ? 0 : nbc - 1, dJ = FWD ? 1 : -1;
     load_tile(cur, J0, v + 1);
     load_inv(li, J0);
-    double rin = (J0 * DNB + l < nin) ? in[(size_t)J0 * DNB + l] : 0.0;
+    double rin = (J0 * DNB + l < nin) ? in[(PERM && FWD) ? (size_t)perm[J0 * DNB + l] : (size_t)J0 * DNB + l] : 0.0;
     for (int J = J0; J >= 0 && J < nbc; J += dJ) {
         const int Jn = J + dJ;
         load_inv(li_n, Jn);
-        const double rin_n = (Jn >= 0 && Jn * DNB + l < nin) ? in[(size_t)Jn * DNB + l] : 0.0;
+        const double rin_n = (Jn >= 0 && Jn * DNB + l < nin) ? in[(PERM && FWD) ? (size_t)perm[Jn * DNB + l] : (size_t)Jn * DNB + l] : 0.0;
         const double dd = FWD ? Wd[(size_t)J * DNB + l] : 1.0;
         double acc = 0.0;
         for (int s = v + 1;; s += 4) {
@@ -241,7 +264,7 @@ __device__ __forceinline__ void bw_sweep(int nbc, int w, const double *__restric
         if (v == 0) {
             const double z = (part2[0][l] + part2[1][l]) + (part2[2][l] + part2[3][l]);
             win[J % (BW_MAX_W + 1)][l] = z;
-            if (J * DNB + l < nout) out[(size_t)J * DNB + l] = FWD ? z / dd : z;
+            if (J * DNB + l < nout) out[(PERM && !FWD) ? (size_t)perm[J * DNB + l] : (size_t)J * DNB + l] = FWD ? z / dd : z;
         }
         __syncthreads();
 #pragma unroll
@@ -254,8 +277,18 @@ __global__ __launch_bounds__(256) void k_bw_solve(int n, int nbc, int w, const d
                                                   const double *__restrict__ LiT, const double *__restrict__ Wd, const double *__restrict__ rhs,
                                                   double *__restrict__ z, double *__restrict__ x) {
     __shared__ double win[BW_MAX_W + 1][DNB], part[4][DNB], part2[4][DNB], tot[DNB];
-    bw_sweep<true>(nbc, w, Wb, Li, Wd, rhs, n, z, nbc * DNB, win, part, part2, tot);
+    bw_sweep<true, false>(nbc, w, Wb, Li, Wd, rhs, n, z, nbc * DNB, win, part, part2, tot, nullptr);
     __threadfence_block();
     __syncthreads();
-    bw_sweep<false>(nbc, w, Wb, LiT, Wd, z, nbc * DNB, x, n, win, part, part2, tot);
+    bw_sweep<false, false>(nbc, w, Wb, LiT, Wd, z, nbc * DNB, x, n, win, part, part2, tot, nullptr);
+}
+// the same under a variable order: rhs and x in the caller's order, perm = newold
+__global__ __launch_bounds__(256) void k_bw_solve_perm(int n, int nbc, int w, const double *__restrict__ Wb, const double *__restrict__ Li,
+                                                       const double *__restrict__ LiT, const double *__restrict__ Wd, const double *__restrict__ rhs,
+                                                       double *__restrict__ z, double *__restrict__ x, const int *__restrict__ perm) {
+    __shared__ double win[BW_MAX_W + 1][DNB], part[4][DNB], part2[4][DNB], tot[DNB];
+    bw_sweep<true, true>(nbc, w, Wb, Li, Wd, rhs, n, z, nbc * DNB, win, part, part2, tot, perm);
+    __threadfence_block();
+    __syncthreads();
+    bw_sweep<false, true>(nbc, w, Wb, LiT, Wd, z, nbc * DNB, x, n, win, part, part2, tot, perm);
 }

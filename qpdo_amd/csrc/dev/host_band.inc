@@ -7,6 +7,11 @@
 static int band_detect(QpdoDev *d) {
     d->band_b = -1; d->bc_r = 0; d->bc_over = 0;
     if (d->comm.active || d->n < 8) return 0;
+    if (d->bo_newold) {                                  // a variable order: its half-bandwidth was measured where the order was made (band_order.c)
+        const int b = d->bo_b < 3 ? 3 : d->bo_b;
+        if (b <= BAND_WIDE_MAX_B) d->band_b = b;
+        return 0;
+    }
     int cls[3] = {0, 0, 0};                             // coupling rows, the largest span of the other rows, of all rows
     if (d->band_coupling > 0 && d->m > 0) {
         int rc = 0;
@@ -67,9 +72,14 @@ static int band_wide_factor(QpdoDev *d) {
     int rc = band_wide_alloc(d); if (rc) return rc;
     const int n = d->n, np = d->band_np, b = d->band_b, w = d->bw_w, nbc = np / DNB;
     int g = (np + 3) / 4; if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_bw_assemble, dim3(g), dim3(256), 0, d->stream, n, np, b, w, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
-                       (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
-                       (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->bw_Wb, d->bw_Wdiag);
+    if (d->bo_newold)
+        hipLaunchKernelGGL(k_bw_assemble_perm, dim3(g), dim3(256), 0, d->stream, n, np, b, w, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
+                           (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                           (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->bw_Wb, d->bw_Wdiag, (const int *)d->bo_newold, (const int *)d->bo_oldnew);
+    else
+        hipLaunchKernelGGL(k_bw_assemble, dim3(g), dim3(256), 0, d->stream, n, np, b, w, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
+                           (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                           (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->bw_Wb, d->bw_Wdiag);
     for (int k = 0; k < nbc; k++) {
         const int wk = nbc - 1 - k < w ? nbc - 1 - k : w;          // tiles below the diagonal one in block column k
         hipLaunchKernelGGL(k_bw_panel, dim3(wk > 0 ? wk : 1), dim3(256), BW_PANEL_LDS * 8, d->stream, k, w, nbc, d->bw_Wb, (const double *)d->bw_Wdiag,
@@ -91,6 +101,7 @@ static int band_alloc(QpdoDev *d) {
     if (!rc) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_factor<256, BAND_MAX_B>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
+        if (e == hipSuccess && d->bo_newold) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_perm), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         if (e == hipSuccess && d->bc_r > 0) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_multi), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         if (e != hipSuccess) rc = set_err(e, "hipFuncSetAttribute", __LINE__);
     }
@@ -155,17 +166,29 @@ static int band_factor(QpdoDev *d, bool force = false) {
     int rc = band_alloc(d); if (rc) return rc;
     const int n = d->n, np = d->band_np, b = d->band_b;
     int g = (np + 3) / 4; if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(k_band_assemble, dim3(g), dim3(256), 0, d->stream, n, np, b, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
-                       (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
-                       (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->Kb);
+    if (d->bo_newold)
+        hipLaunchKernelGGL(k_band_assemble_perm, dim3(g), dim3(256), 0, d->stream, n, np, b, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
+                           (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                           (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->Kb, (const int *)d->bo_newold, (const int *)d->bo_oldnew);
+    else
+        hipLaunchKernelGGL(k_band_assemble, dim3(g), dim3(256), 0, d->stream, n, np, b, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
+                           (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                           (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->Kb);
     const size_t lds = ((size_t)(b + 4) * (b + 1) + 8 * (size_t)(b + 4)) * sizeof(double);
     // (a one-wave variant for narrow bands -- no workgroup barrier at all -- was measured slower: 76.6 against 57.0 ms at n = 2e5, b = 3)
     hipLaunchKernelGGL((k_band_factor<256, BAND_MAX_B>), dim3(1), dim3(256), lds, d->stream, np, b, d->Kb, d->Lt, &d->ctrl->cnt[C_CHAIN_ERR]);
     d->dense_valid = 1; d->st.factor_count++;
     return 0;
 }
+// d->rhs -> d->dx, both in the caller's order; a workspace with a variable order launches the _perm instance of the same kernel (one launch
+// per solve either way: the gather and the scatter are that kernel's first loads and last stores)
 static int band_solve(QpdoDev *d) {
     if (d->band_b > BAND_MAX_B) {
+        if (d->bo_newold) {
+            hipLaunchKernelGGL(k_bw_solve_perm, dim3(1), dim3(256), 0, d->stream, d->n, d->band_np / DNB, d->bw_w, (const double *)d->bw_Wb, (const double *)d->bw_Li,
+                               (const double *)d->bw_LiT, (const double *)d->bw_Wd, (const double *)d->rhs, d->band_z, d->dx, (const int *)d->bo_newold);
+            return 0;
+        }
         hipLaunchKernelGGL(k_bw_solve, dim3(1), dim3(256), 0, d->stream, d->n, d->band_np / DNB, d->bw_w, (const double *)d->bw_Wb, (const double *)d->bw_Li,
                            (const double *)d->bw_LiT, (const double *)d->bw_Wd, (const double *)d->rhs, d->band_z, d->dx);
         return 0;
@@ -199,6 +222,11 @@ static int band_solve(QpdoDev *d) {
         if (!latched) { d->st.coupled_rejects++; LAUNCH(k_ctrl_set_int, 1, d->ctrl, C_CHAIN_ERR, 2); }
         if (d->defl_debug) fprintf(stderr, "[band coupled] pass %lld: k = %d, %s; last sweep |r|inf = %.3e, |rhs|inf = %.3e\n", (long long)d->st.newton_passes, k,
                                    latched ? "bad pivot latched" : "residual check missed", nrm_of(d->hctrl, N_B), nrm_of(d->hctrl, N_A));
+        return 0;
+    }
+    if (d->bo_newold) {
+        hipLaunchKernelGGL(k_band_solve_perm, dim3(1), dim3(256), lds, d->stream, d->n, d->band_b, (const double *)d->Kb, (const double *)d->Lt, (const double *)d->rhs,
+                           d->band_z, d->dx, (const int *)d->bo_newold);
         return 0;
     }
     hipLaunchKernelGGL(k_band_solve, dim3(1), dim3(256), lds, d->stream, d->n, d->band_b, (const double *)d->Kb, (const double *)d->Lt, (const double *)d->rhs, d->band_z, d->dx);

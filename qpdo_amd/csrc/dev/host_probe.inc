@@ -162,6 +162,14 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
         HIPCHK(hipStreamSynchronize(d->stream));
         return 0;
     }
+    if (which == 12) {                                  // the variable order of the band solver
+        if (!d->bo_newold) return set_err(hipErrorInvalidValue, "download factor: this workspace has adopted no variable order", __LINE__);
+        if (count < 0 || count != (long)d->n) return set_err(hipErrorInvalidValue, "download factor: count is not the array's length", __LINE__);
+        std::vector<int32_t> no((size_t)(d->n ? d->n : 1));
+        int rcn = qdev_band_order_newold(d, no.data()); if (rcn) return rcn;
+        for (int k = 0; k < d->n; k++) dst[k] = (double)no[(size_t)k];
+        return 0;
+    }
     const double *src = nullptr; size_t len = 0;
     if ((which == 4 || which == 5) && d->bw_Wb) return set_err(hipErrorInvalidValue, "download factor: a band wider than 127 is held as tiles (arrays 7 and 8)", __LINE__);
     switch (which) {

@@ -264,6 +264,33 @@ void qdev_destroy(QpdoDev *d) {
 }
 int qdev_sync(QpdoDev *d) { HIPCHK(hipSetDevice(d->device)); HIPCHK(hipStreamSynchronize(d->stream)); return 0; }
 
+// The band solver's variable order (host side of the order: csrc/band_order.c; qpdo_dev.h has the contract).  The two int32 arrays are the
+// only resident memory an order costs.
+int qdev_set_band_order(QpdoDev *d, const int32_t *newold, int b_natural, int b_ordered) {
+    HIPCHK(hipSetDevice(d->device));
+    d->bo_seen_nat = b_natural; d->bo_seen_ord = b_ordered;
+    if (!newold) return 0;
+    const size_t n = (size_t)d->n;
+    std::vector<int32_t> oldnew(n ? n : 1);
+    for (size_t k = 0; k < n; k++) oldnew[(size_t)newold[k]] = (int32_t)k;
+    int rc = dev_alloc(d, &d->bo_newold, n ? n : 1);
+    if (!rc) rc = dev_alloc(d, &d->bo_oldnew, n ? n : 1);
+    if (rc) { d->bo_newold = nullptr; return rc; }
+    if (n) {
+        HIPCHK(hipMemcpyAsync(d->bo_newold, newold, n * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+        HIPCHK(hipMemcpyAsync(d->bo_oldnew, oldnew.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+    }
+    d->bo_b = b_ordered;
+    return 0;
+}
+int qdev_band_order_newold(QpdoDev *d, int32_t *newold) {
+    HIPCHK(hipSetDevice(d->device));
+    if (!d->bo_newold) return set_err(hipErrorInvalidValue, "this workspace has adopted no variable order", __LINE__);
+    if (d->n) HIPCHK(hipMemcpyAsync(newold, d->bo_newold, (size_t)d->n * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
 int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     const char *gr = getenv("QPDO_PCG_GRAPH");
     if (gr && !strcmp(gr, "0")) d->pcg_graph = 0;
@@ -319,6 +346,11 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
         const int wide_enough = d->n >= 4 * (d->band_b + 1);
         if (d->band_b > 0 && wide_enough && (linsolve == 3 || (d->band_b <= BAND_MAX_B && d->n >= 2048))) d->linsolve = 3;
         else if (linsolve == 3 && d->bc_over) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: %d rows of A are wider than the band (column span > %d), QPDO_BAND_COUPLING accepts %d", d->bc_over, BAND_MAX_B, d->band_coupling); return -1; }
+        else if (linsolve == 3 && d->bo_seen_ord >= 0) {
+            snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: the Newton matrix is not banded (half-bandwidth > %d or order too small; half-bandwidth %d in the caller's "
+                     "variable order, %d under the configured band order)", BAND_WIDE_MAX_B, d->bo_seen_nat, d->bo_seen_ord);
+            return -1;
+        }
         else if (linsolve == 3) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: the Newton matrix is not banded (half-bandwidth > %d or order too small)", BAND_WIDE_MAX_B); return -1; }
     }
     if (pcg_tol > 0) d->pcg_tol = pcg_tol;

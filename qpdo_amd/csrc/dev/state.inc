@@ -104,6 +104,11 @@ struct QpdoDev {
     int dense_asm_tile = 19000;   // rows of a column the assembly accumulates in LDS at a time (152 KB of the 160 KB)
     // band direct solver (dev/band.inc): half-bandwidth of Q + A'A (-1: not banded within BAND_WIDE_MAX_B), order padded to 4, band storage
     int band_b = -1, band_np = 0; double *Kb = nullptr, *Lt = nullptr, *band_z = nullptr;
+    // a variable order of the band solver (qdev_set_band_order; null: the caller's order, and nothing below is read): bo_newold[k] = the
+    // caller's index of the variable at position k, bo_oldnew its inverse (device, n each); bo_b: the half-bandwidth under it, from the
+    // host (band_order.c; band_detect takes it instead of measuring).  bo_seen_*: the bandwidths of an order that was looked at,
+    // adopted or not, for setup's "not banded" message (-1: none was).
+    int *bo_newold = nullptr, *bo_oldnew = nullptr; int bo_b = -1, bo_seen_nat = -1, bo_seen_ord = -1;
     // chain QPs with dense coupling rows (QPDO_BAND_COUPLING = band_coupling > 0; dev/band.inc): bc_r of them (0: none, the plain band
     // solver), band_b is then the half-bandwidth of the OTHER rows and of Q.  bc_over: more than band_coupling were counted (setup's
     // message).  The kept factor of B belongs to (bc_dfact, bc_fact_sigma); bc_zvalid: the slots whose column of Z = B^-1 U was solved with

@@ -21,6 +21,7 @@
 #include "qpdo_amd_ext.h"
 #include "qpdo_dev.h"
 #include "csc_convert.h"
+#include "band_order.h"
 #include "pass_decision.h"
 
 struct QPDO_TIMER { struct timespec tic, toc; };   /* reference include/util.h:98-104 */
@@ -42,6 +43,7 @@ struct QPDOBackend {
      * bit) and the shape of the matrices given to qpdo_setup */
     c_float *q_raw, *l_raw, *u_raw;
     int q_stype; int64_t q_nnz, a_nnz;
+    QPDOAmdBandOrderInfo band_order;      /* what qpdo_setup decided about the band solver's variable order (band_order_setup) */
     int solved_last;              /* the most recent state-changing call was qpdo_solve (set there; cleared by qpdo_warm_start, qpdo_update_q,
                                    * qpdo_update_bounds, qpdo_amd_update_matrices): what qpdo_amd_adjoint asks before it reads the solution */
 };
@@ -283,11 +285,14 @@ static int install_scaling(QPDOWorkspace *work) {
 
 /* small problems: the fused one-launch solve (QPDO_SMALL_FUSED=0 keeps the generic path; an explicit QPDO_LINSOLVE asks for one of the
  * generic path's solvers; a row-partitioned workspace is never small) */
-static void small_resident_setup(QPDOWorkspace *work, const QPDOSettings *settings) {
-    const size_t n = work->data->n, m = work->data->m;
+static int small_route_wanted(size_t n, size_t m) {
     const char *ls = getenv("QPDO_LINSOLVE");
     const int want = env_int("QPDO_SMALL_FUSED", 1) && !(ls && *ls && strcmp(ls, "auto"));
-    if (want && (long)n <= env_int("QPDO_SMALL_FUSED_MAX_N", 160) && qdev_small_resident_fits((int32_t)n, (int32_t)m)) {
+    return want && (long)n <= env_int("QPDO_SMALL_FUSED_MAX_N", 160) && qdev_small_resident_fits((int32_t)n, (int32_t)m);
+}
+static void small_resident_setup(QPDOWorkspace *work, const QPDOSettings *settings) {
+    const size_t n = work->data->n, m = work->data->m;
+    if (small_route_wanted(n, m)) {
         QdevSmallView v;
         if (qdev_small_view(work->chol->dev, &v) == 0) {
             long cap = (long)settings->max_iter < 16384 ? (long)settings->max_iter : 16384;
@@ -311,6 +316,51 @@ static int pick_device(int *device) {
     if (ndev <= 0) return 0;
     *device = env_int("QPDO_DEVICE", env_int("LOCAL_RANK", 0)) % ndev;
     return 1;
+}
+
+/* The band solver's variable order for this workspace (band_order.h; contract: qpdo_amd_ext.h), between the creation of the device
+ * backend and qdev_configure, whose band detection and selection rule then run on the adopted order.  Nothing configured: nothing is
+ * computed, allocated or launched.  Returns 0, or -1 with the message printed. */
+static int band_order_setup(QPDOWorkspace *work, const cholmod_sparse *Q, const cholmod_sparse *A, const QdevDist *dd) {
+    QPDOAmdBandOrderInfo *bo = &work->chol->band_order;
+    const long n = (long)work->data->n;
+    char msg[256] = "";
+    int mode = QPDO_AMD_BAND_ORDER_NATURAL, rc = 0;
+    int32_t *given = NULL;
+    memset(bo, 0, sizeof(*bo));
+    bo->b_natural = bo->b_ordered = -1;
+    if (band_order_snapshot(n, &mode, &given, msg, sizeof(msg))) { qdev_set_error(msg); QPDO_EPRINT("%s", msg); return -1; }
+    bo->mode = mode;
+    if (mode == QPDO_AMD_BAND_ORDER_NATURAL) return 0;
+    const int ls = linsolve_mode_env();
+    if (dd->world > 1 || dd->force) bo->reason = BAND_ORDER_REASON_PARTITIONED;
+    else if (env_int("QPDO_BAND_COUPLING", 0) > 0) bo->reason = BAND_ORDER_REASON_COUPLING;
+    else if (small_route_wanted((size_t)n, work->data->m)) bo->reason = BAND_ORDER_REASON_FUSED;
+    else if (ls == 0 || ls == 1) bo->reason = BAND_ORDER_REASON_LINSOLVE;
+    if (bo->reason) { free(given); return 0; }
+    const double t0 = wall_now();
+    long *newold = malloc(((size_t)n + 1) * sizeof(long));
+    int32_t *no32 = given ? given : malloc(((size_t)n + 1) * sizeof(int32_t)), *oldnew = NULL;
+    if (!newold || !no32) { QPDO_EPRINT("band order: out of memory"); free(newold); free(no32); return -1; }
+    if (mode == QPDO_AMD_BAND_ORDER_RCM) {
+        long info[4];
+        if (qpdo_amd_band_order(Q, A, newold, info)) { QPDO_EPRINT("band order: the ordering failed (out of memory)"); rc = -1; }
+        for (long k = 0; !rc && k < n; k++) no32[k] = (int32_t)newold[k];
+        bo->b_natural = info[0]; bo->b_ordered = info[1];
+        bo->adopted = !rc && info[1] < info[0];
+        if (!rc && !bo->adopted) bo->reason = BAND_ORDER_REASON_NO_GAIN;
+    } else {
+        oldnew = malloc(((size_t)n + 1) * sizeof(int32_t));
+        if (!oldnew) { QPDO_EPRINT("band order: out of memory"); rc = -1; }
+        for (long k = 0; !rc && k < n; k++) oldnew[no32[k]] = (int32_t)k;
+        if (!rc) { bo->b_natural = band_order_bandwidth(Q, A, NULL); bo->b_ordered = band_order_bandwidth(Q, A, oldnew); }
+        if (!rc && (bo->b_natural < 0 || bo->b_ordered < 0)) { QPDO_EPRINT("band order: out of memory"); rc = -1; }
+        bo->adopted = !rc;
+    }
+    bo->order_seconds = wall_now() - t0;
+    if (!rc && qdev_set_band_order(work->chol->dev, bo->adopted ? no32 : NULL, (int)bo->b_natural, (int)bo->b_ordered)) { QPDO_EPRINT("device backend: %s", qdev_last_error()); rc = -1; }
+    free(newold); free(no32); free(oldnew);
+    return rc;
 }
 
 /* The device backend from the three host images: whole on one GPU, or -- a row partition -- this rank's rows [m0, m0+mloc) of A, the
@@ -441,6 +491,7 @@ QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
         if (prof) { fprintf(stderr, "[setup] host free         %.3f s\n", wall_now() - t0); }
         if (rc) goto fail_dev;
     }
+    if (band_order_setup(work, Q, A, &dd)) goto fail;
     if (qdev_configure(work->chol->dev, linsolve_mode_env(), env_double("QPDO_PCG_TOL", 0.0), env_int("QPDO_PCG_MAXIT", 0))) goto fail_dev;
     const int scaled = apply_scaling(work, 1, prof);
     if (scaled < 0) goto fail_dev;
@@ -925,6 +976,18 @@ int qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const doub
 int qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags) {
     const int rc = qdev_direct_solve(work->chol->dev, dw, sigma, rhs, x, flags);
     return rc == QDEV_DIRECT_LOST ? QPDO_AMD_DIRECT_LOST : rc ? -1 : 0;
+}
+int qpdo_amd_get_band_order(const QPDOWorkspace *work, QPDOAmdBandOrderInfo *out, long *newold) {
+    if (!work || !work->chol || !out) return -1;
+    *out = work->chol->band_order;
+    if (newold && out->adopted) {
+        const size_t n = work->data->n;
+        int32_t *no = malloc((n + 1) * sizeof(int32_t));
+        if (!no || qdev_band_order_newold(work->chol->dev, no)) { free(no); return -1; }
+        for (size_t k = 0; k < n; k++) newold[k] = no[k];
+        free(no);
+    }
+    return 0;
 }
 int qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count) {
     return qdev_download_factor(work->chol->dev, which, dst, count) ? -1 : 0;

@@ -188,6 +188,11 @@ int qdev_download_vec(QpdoDev *d, int which, double *dst);   /* 0 x, 1 Qx, 2 y *
 int qdev_upload_vec(QpdoDev *d, int which, const double *src);
 
 /* configuration (environment-driven in the driver) */
+/* Before qdev_configure.  newold (n entries, a permutation: the caller has checked it) non-NULL: the band solver of this workspace works in
+ * that variable order, whose half-bandwidth is b_ordered; NULL: only the two bandwidths of an order that was looked at and not adopted are
+ * noted, for qdev_configure's "not banded" message.  qdev_band_order_newold: the adopted order back (returns -1 with a message when none). */
+int qdev_set_band_order(QpdoDev *d, const int32_t *newold, int b_natural, int b_ordered);
+int qdev_band_order_newold(QpdoDev *d, int32_t *newold);
 int qdev_configure(QpdoDev *d, int linsolve /*0 pcg,1 dense,-1 auto*/, double pcg_tol, int pcg_maxit);
 /* the linear solves stop at pcg_tol relative OR at 1e-5 eps_abs in the reference's unscaled inf-norm of the dual residual */
 int qdev_set_eps_abs(QpdoDev *d, double eps_abs);

@@ -132,6 +132,24 @@ def full_Q(prob):
     return (T + T.T - sp.diags(T.diagonal())).tocsc()
 
 
+def permute_variables(prob, newold):
+    """The same QP in another variable order: variable newold[k] of `prob` is variable k of the result (Q -> P Q P', A -> A P', q -> P q; the
+    rows of A, l, u untouched).  x of the result is x[newold] of the original's.  Q comes back in the storage it had (a triangle stays that
+    triangle).  The relabelling that hides a chain from the band solver -- and, with newold from solver.band_order, the one that shows it."""
+    newold = np.asarray(newold, dtype=np.int64)
+    n = prob["n"]
+    if newold.shape != (n,) or not np.array_equal(np.sort(newold), np.arange(n)):
+        raise ValueError("newold must be a permutation of 0 .. n-1")
+    st = prob.get("Qstype", -1)
+    Qp = full_Q(prob).tocsr()[newold][:, newold]
+    Qp = (Qp if st == 0 else sp.tril(Qp) if st < 0 else sp.triu(Qp)).tocsc()
+    A = prob["A"].tocsc()[:, newold].tocsc()
+    Qp.sort_indices(); A.sort_indices()
+    out = dict(prob)
+    out.update(Q=Qp, A=A, q=np.asarray(prob["q"], dtype=np.float64)[newold].copy())
+    return out
+
+
 def infeasibility_kat(case):
     """case in {'degenerate','primal_infeasible','dual_infeasible'}; expected status 1 / -3 / -4
     (reference examples/infeasibility_tests.m:30,48,75)."""

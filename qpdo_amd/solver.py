@@ -125,7 +125,19 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_adjoint_dev", "qpdo_amd_fleet_get_adjoint_stats",
                "qpdo_amd_fleet_adjoint_multi_dev", "qpdo_amd_fleet_tangent_dev", "qpdo_amd_fleet_rhs_group", "qpdo_amd_fleet_get_sensitivity_stats",
                "qpdo_amd_adjoint", "qpdo_amd_get_adjoint_stats", "qpdo_amd_tangent", "qpdo_amd_get_tangent_stats",
-               "qpdo_amd_rhs_group", "qpdo_amd_get_group_stats", "qpdo_amd_spmv_group"]
+               "qpdo_amd_rhs_group", "qpdo_amd_get_group_stats", "qpdo_amd_spmv_group",
+               "qpdo_amd_band_order", "qpdo_amd_band_order_config", "qpdo_amd_get_band_order"]
+
+
+class BandOrderInfo(C.Structure):
+    """QPDOAmdBandOrderInfo (include/qpdo_amd_ext.h)"""
+    _fields_ = [("mode", C.c_long), ("adopted", C.c_long), ("b_natural", C.c_long), ("b_ordered", C.c_long), ("reason", C.c_long),
+                ("order_seconds", C.c_double)]
+
+
+BAND_ORDER_ENV, BAND_ORDER_NATURAL, BAND_ORDER_RCM, BAND_ORDER_GIVEN = 0, 1, 2, 3      # QPDO_AMD_BAND_ORDER_*
+BAND_ORDER_REASONS = {0: "", 1: "reverse Cuthill-McKee found no narrower order", 2: "row-partitioned workspace", 3: "QPDO_BAND_COUPLING is set",
+                      4: "fused small-problem route", 5: "QPDO_LINSOLVE is dense or pcg"}
 
 
 class AdjointStats(C.Structure):
@@ -236,6 +248,14 @@ def lib():
             L.qpdo_amd_tangent.restype = C.c_int
             L.qpdo_amd_get_tangent_stats.argtypes = [W, C.POINTER(TangentStats)]
             L.qpdo_amd_get_tangent_stats.restype = C.c_int
+        if hasattr(L, "qpdo_amd_band_order"):
+            lp_ = C.POINTER(C.c_long)
+            L.qpdo_amd_band_order.argtypes = [C.POINTER(CholmodSparse), C.POINTER(CholmodSparse), lp_, lp_]
+            L.qpdo_amd_band_order.restype = C.c_int
+            L.qpdo_amd_band_order_config.argtypes = [C.c_int, lp_, C.c_long]
+            L.qpdo_amd_band_order_config.restype = C.c_int
+            L.qpdo_amd_get_band_order.argtypes = [W, C.POINTER(BandOrderInfo), lp_]
+            L.qpdo_amd_get_band_order.restype = C.c_int
         if hasattr(L, "qpdo_amd_rhs_group"):
             L.qpdo_amd_rhs_group.argtypes = [W]
             L.qpdo_amd_rhs_group.restype = C.c_int
@@ -913,6 +933,12 @@ class QPDO:
             if lib().qpdo_amd_download_factor(self._w, which, _as_dp(out), count):
                 raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
             return out[:count].astype(np.int64) if name == "coupled_rows" else out[:count].reshape(geo["k"], geo["np"]).T
+        if name == "perm":
+            # the band solver's variable order (band_order_config): newold, n integers; Kb / Lt / Wb / Wd are then in that order
+            out = np.zeros(max(self.n, 1))
+            if lib().qpdo_amd_download_factor(self._w, 12, _as_dp(out), self.n):
+                raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+            return out[:self.n].astype(np.int64)
         g = self.factor_geometry()
         ld, nb, npad, b = g["ld"], g["nb"], g["np"], g["b"]
         which, count = {"Kd": (0, ld * ld), "Dg": (1, ld), "Linv": (2, nb * 4096), "LinvT": (3, nb * 4096),
@@ -929,6 +955,18 @@ class QPDO:
             return out.reshape(npad // 64, (b + 63) // 64 + 1, 64, 64)
         if name in ("Linv", "LinvT"):
             return out.reshape(nb, 4096)
+        return out
+
+    def band_order_info(self):
+        """what setup decided about the band solver's variable order (QPDOAmdBandOrderInfo): mode, adopted, b_natural / b_ordered (-1 where
+        no order was looked at), reason (+ reason_text) where a configured order was not adopted, order_seconds; newold where adopted"""
+        info = BandOrderInfo()
+        newold = np.zeros(max(self.n, 1), dtype=np.int64 if C.sizeof(C.c_long) == 8 else np.int32)
+        if lib().qpdo_amd_get_band_order(self._w, C.byref(info), newold.ctypes.data_as(C.POINTER(C.c_long))):
+            raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+        out = {f: getattr(info, f) for f, _ in BandOrderInfo._fields_}
+        out["reason_text"] = BAND_ORDER_REASONS.get(int(info.reason), "")
+        out["newold"] = newold[:self.n].astype(np.int64) if info.adopted else None
         return out
 
     def download(self, name):
@@ -1644,6 +1682,41 @@ def batch_factor_layout():
 # ---- one large QP row-partitioned over the ranks of a torch.distributed job ---------------------------------
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_double), C.c_long, C.c_int)
 _dist_keep = []
+
+
+def band_order_config(mode, newold=None):
+    """The band solver's variable order for the workspaces set up next in this process (qpdo_amd_band_order_config): mode "env" (the default:
+    QPDO_BAND_ORDER decides), "natural", "rcm", or "given" with newold -- newold[k] = the caller's index of the variable at position k."""
+    code = {"env": BAND_ORDER_ENV, "natural": BAND_ORDER_NATURAL, "rcm": BAND_ORDER_RCM, "given": BAND_ORDER_GIVEN}.get(mode, mode)
+    if code not in (BAND_ORDER_ENV, BAND_ORDER_NATURAL, BAND_ORDER_RCM, BAND_ORDER_GIVEN):
+        raise ValueError("unknown band order mode %r" % (mode,))
+    arr, n = None, 0
+    if code == BAND_ORDER_GIVEN:
+        if newold is None:
+            raise ValueError("mode 'given' needs newold")
+        arr = np.ascontiguousarray(newold, dtype=np.int64 if C.sizeof(C.c_long) == 8 else np.int32)
+        n = len(arr)
+        if not np.array_equal(np.sort(arr), np.arange(n)):
+            raise ValueError("newold is not a permutation of 0 .. n-1")
+    if lib().qpdo_amd_band_order_config(code, None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_long)), n):
+        raise ValueError("qpdo_amd_band_order_config refused the order")
+
+
+def band_order(Q, A, Qstype=-1):
+    """Reverse Cuthill-McKee on the pattern of Q + A'A (qpdo_amd_band_order; host only, no device): (newold, info) with newold[k] = the
+    index of the variable that takes position k and info = dict(b_natural, b_ordered, components, early_out).  Q as setup takes it: a
+    stored triangle with Qstype -1 / +1, or both triangles with 0.  problems.permute_variables(prob, newold) is the reordered QP."""
+    keep = []
+    Q = sp.csc_matrix(Q)
+    n = Q.shape[0]
+    A = sp.csc_matrix((0, n)) if A is None else sp.csc_matrix(A)
+    qv, av = _sparse_view(Q, int(Qstype), keep), _sparse_view(A, 0, keep)
+    ltype = np.int64 if C.sizeof(C.c_long) == 8 else np.int32
+    newold, info = np.zeros(max(n, 1), dtype=ltype), np.zeros(4, dtype=ltype)
+    lp_ = C.POINTER(C.c_long)
+    if lib().qpdo_amd_band_order(C.byref(qv), C.byref(av), newold.ctypes.data_as(lp_), info.ctypes.data_as(lp_)):
+        raise RuntimeError("qpdo_amd_band_order failed")
+    return newold[:n].astype(np.int64), dict(b_natural=int(info[0]), b_ordered=int(info[1]), components=int(info[2]), early_out=int(info[3]))
 
 
 def dist_config(rank, world, mode="rccl", group=None, force=False):
