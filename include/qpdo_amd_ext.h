@@ -412,10 +412,17 @@ int  qpdo_amd_download(QPDOWorkspace *work, int which, double *dst);
  *          the triangular solves that lost its producer; the latch is cleared as qpdo_amd_direct_solve clears it, nothing is redone, code 3
  *          repeats for every r and `active` is all 0.  A right-hand side with code != 0 gets NaN in all its slices of dq, dl, du, dQx, dAx and
  *          NaN in res[r]; res[r] of an accepted one is its relative residual.  (There is no code 2: a workspace that is not solved is refused.)
- * Accepted workspaces: one GPU; the workspace's solver is the dense LDL' or the band LDL' with half-bandwidth <= 127 and no coupling rows.
+ * Accepted workspaces: one GPU; the workspace's solver is the dense LDL' or the band LDL' of every kind -- half-bandwidth <= 127, the
+ *          tiled wide band (128 .. 1023), either in the natural order or under an adopted variable order (QPDO_BAND_ORDER), and
+ *          half-bandwidth <= 127 with coupling rows (QPDO_BAND_COUPLING).  With coupling rows K = B + U W_c U' (B: the band part, U: the
+ *          flagged coupling rows, W_c: their weights) is not factored as one matrix: B and S = W_c^-1 + U' B^-1 U are, once per call, and
+ *          the solve of every sweep is ONE Woodbury application dvx = z0 - Z S^-1 U' z0, z0 = B^-1 rhs, Z = B^-1 U, without the residual
+ *          check and the refinement a Newton pass wraps around it: the sweeps already refine on the true system.  Such a workspace TAKES
+ *          MORE SWEEPS than a plain band one (3 .. 8 against 2 on the test instances), and an inner solve that is too inexact ends as
+ *          code 1, never as code 3; code 3 there is a pivot of B or of S that is not a positive finite number.  When no coupling row is
+ *          flagged, the plain band solve on B is the whole solve.
  *          Refused with a message that names what to do instead: PCG workspaces, hybrid workspaces (the automatically chosen dense solver
- *          from n = 8192, whose solves start with PCG: set QPDO_LINSOLVE=dense), band with b > 127, QPDO_BAND_COUPLING workspaces with
- *          coupling rows, row-partitioned workspaces.
+ *          from n = 8192, whose solves start with PCG: set QPDO_LINSOLVE=dense), row-partitioned workspaces.
  * Checks   all before anything is launched or written; a refused call returns nonzero with qpdo_amd_last_error() set and leaves every
  *          output array untouched.  The first fault in this order is reported: nrhs < 1; tol not a positive finite number; max_sweeps < 1;
  *          NULL gx, dq, dl or du; dQx without Q; NULL workspace; info->status_val != QPDO_SOLVED; THE MOST RECENT STATE-CHANGING CALL WAS NOT A
@@ -476,7 +483,9 @@ int  qpdo_amd_get_adjoint_stats(const QPDOWorkspace *work, QPDOAmdAdjointStats *
  *          sweeps.  A non-finite entry among those used is never accepted (code 1).  A zero right-hand side is accepted at sweep 0 with zeros.
  * status   nrhs x 3: (code, sweeps, k); codes 0, 1 and 3 with the adjoint's meaning.  A right-hand side with code != 0 gets NaN in its slices
  *          of dx and dy and NaN in res[r]; code 1 is that right-hand side's own and touches no other.  After code 3 `active` is all 0.
- * Accepted workspaces and refusals: those of qpdo_amd_adjoint, by the same function; the messages begin with "qpdo_amd_tangent:".
+ * Accepted workspaces and refusals: those of qpdo_amd_adjoint, by the same function -- the wide band, a variable order and coupling rows
+ *          included, with the adjoint's one Woodbury application per sweep and its larger sweep counts on a workspace with coupling rows;
+ *          PCG, hybrid and row-partitioned workspaces are refused; the messages begin with "qpdo_amd_tangent:".
  * Checks   all before anything is launched or written; a refused call returns nonzero with qpdo_amd_last_error() set and leaves every
  *          output array untouched.  The first fault in this order is reported: nrhs < 1; tol not a positive finite number; max_sweeps < 1;
  *          NULL dx or dy; no tangent passed; tQx without Q; NULL workspace; info->status_val != QPDO_SOLVED; the most recent state-changing
@@ -511,13 +520,18 @@ int  qpdo_amd_get_tangent_stats(const QPDOWorkspace *work, QPDOAmdTangentStats *
  * no launch reads or writes its vectors.  The non-finite marker is per right-hand side (a code 1 touches no other); the code-3 latch is the
  * call's: it hits the right-hand sides of the group in flight and all behind it.  A call with nrhs = 1 runs the G = 1 code path.
  * G        8 where the workspace is one the two calls accept, Q, A and A' all take the plain CSR kernel, and the solver is the band LDL'
- *          (b <= 127) or the dense LDL' with the chained one-launch solves.  G = 1 (the right-hand sides follow one another): a matrix on
+ *          (every kind the calls accept: b <= 127, the wide band 128 .. 1023, a variable order, coupling rows) or the dense LDL' with the
+ *          chained one-launch solves.  The band solves of a group run the single solve's kernel body once per live right-hand side, one
+ *          workgroup each (k_band_solve_group, k_bw_solve_group and their _perm instances); with coupling rows the Woodbury application's
+ *          three launches are made once per group (k_band_solve_group, k_bc_t_group, k_bc_apply_group), and a group's right-hand sides
+ *          may leave at different sweep counts.  G = 1 (the right-hand sides follow one another): a matrix on
  *          the slab kernel (>= 192 MB, QPDO_SPMV) -- a multi-vector slab product does not exist --, and the stepwise dense solves
  *          (QPDO_DENSE_SOLVE=steps, or after a lost producer).  QPDO_AMD_RHS_GROUP=1..8 in the environment at qpdo_setup overrides G (a
  *          measuring switch, as QPDO_AMD_FLEET_RHS_GROUP is for the fleet; tools/workspace_group_latency.py); 1 runs the launch sequence
  *          of a build without groups.
  * Scratch  G copies of the per-right-hand-side work vectors (5 n + 5 m doubles each; x, y, the row norms and the flags are shared with the
- *          single path), the solves' columns (G x (n + 5 ld) doubles, ld = n rounded up to 64) and the group control array, allocated
+ *          single path), the solves' columns (G x (n + 5 ld) doubles, ld = n rounded up to 64; the band routes' columns -- with coupling
+ *          rows z0 and t too -- lie inside them) and the group control array, allocated
  *          ONCE by the first call of either kind with nrhs > 1 on a workspace with G > 1 -- host allocations: THAT CALL MAY BLOCK until
  *          earlier device work has finished --, booked in QPDOAmdGroupStats.scratch_bytes ALONE (not in the two calls' scratch_bytes), freed
  *          by qpdo_cleanup.  No trace: as before, with these buffers included.

@@ -328,15 +328,14 @@ static int adjoint_refuse(const char *msg) { snprintf(g_err, sizeof(g_err), "qpd
 int qdev_get_adjoint_stats(QpdoDev *d, QdevAdjointStats *out) { *out = d->adj; return 0; }
 int qdev_get_tangent_stats(QpdoDev *d, QdevTangentStats *out) { *out = d->tan; return 0; }
 
-// the workspaces the two calls take: one GPU, the dense LDL' or the plain band LDL' with b <= 127 as the workspace's solver.  who: the
-// entry point's name, which the message begins with
+// the workspaces the two calls take: one GPU, the dense LDL' or the band LDL' as the workspace's solver -- the band of every kind: b <= 127,
+// the tiled wide band (128 .. 1023), either under an adopted variable order, and b <= 127 with coupling rows.  who: the entry point's
+// name, which the message begins with
 static const char *adj_kind_refusal(const QpdoDev *d) {
     if (d->comm.active) return "row-partitioned workspaces are not supported (solve the QP on one GPU, or take finite differences of qpdo_solve)";
     if (d->hybrid) return "the workspace starts its solves with PCG (the hybrid of an automatically chosen dense solver from n = 8192, QPDO_HYBRID); set up with QPDO_LINSOLVE=dense";
     if (d->linsolve != 1 && d->linsolve != 3)
         return "the workspace's solver is PCG; the adjoint needs a direct solver: set up with QPDO_LINSOLVE=dense (n <= 40000) or QPDO_LINSOLVE=band";
-    if (d->linsolve == 3 && d->band_b > BAND_MAX_B) return "the band solver's half-bandwidth is above 127; set up with QPDO_LINSOLVE=dense";
-    if (d->linsolve == 3 && d->bc_r > 0) return "the band solver carries coupling rows (QPDO_BAND_COUPLING); set up without it or with QPDO_LINSOLVE=dense";
     return nullptr;
 }
 int qdev_adjoint_check_kind(QpdoDev *d, const char *who) {
@@ -400,8 +399,9 @@ struct AdjCall {
     int G = 1;
     double *bn = nullptr, *bm = nullptr;
     // the group's solve: the right-hand sides (n apart) and the solutions (ldx apart), compact over the live right-hand sides; the dense
-    // route's padded columns, polled vectors and forward results (ld apart), the band route's forward results (np apart)
-    double *srhs = nullptr, *sdvx = nullptr, *sx = nullptr, *spub1 = nullptr, *schy = nullptr, *spub2 = nullptr, *sz = nullptr;
+    // route's padded columns, polled vectors and forward results (ld apart), the band route's forward results (np apart) and, with coupling
+    // rows, the Woodbury application's z0 columns (ldx apart) and t columns (BC_MAX apart)
+    double *srhs = nullptr, *sdvx = nullptr, *sx = nullptr, *spub1 = nullptr, *schy = nullptr, *spub2 = nullptr, *sz = nullptr, *sz0 = nullptr, *st = nullptr;
     long long ldx = 0;
 };
 }
@@ -451,13 +451,17 @@ static int adj_vectors(QpdoDev *d, AdjCall &c, long nrhs, int64_t *booked) {
         if (d->bo_newold) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_group_perm), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
         d->grp.scratch_bytes += (int64_t)(((size_t)5 * Gc * ((size_t)n + m) + sol) * 8 + SPMV_GROUP_MAX * sizeof(AdjGrpCtrl));
     }
+    // the band route's columns inside the per-column share n + 5 ld of grp_sol: right-hand side n, solution n, then three parts of ld -- the
+    // forward result (np <= ld: band_alloc rounds n up to 4, band_wide_alloc to DNB as ld is) and, with coupling rows, z0 (n) and t (BC_MAX)
+    static_assert(BC_MAX <= DNB, "a column's t fits the ld entries set aside for it");
+    if (c.kind == 3 && (size_t)d->band_np > ld) return set_err(hipErrorInvalidValue, "adjoint group: the band solve's columns do not fit the group's solve buffer", __LINE__);
     c.G = G; c.bn = d->grp_n; c.bm = d->grp_m;
     adj_point(c, 0);
     double *p = d->grp_sol;
     c.ldx = (long long)ldx;
     c.srhs = p; p += (size_t)Gc * n;
     c.sdvx = p; p += (size_t)Gc * ldx;
-    if (c.kind == 3) c.sz = p;
+    if (c.kind == 3) { c.sz = p; c.sz0 = p + (size_t)Gc * ld; c.st = p + (size_t)2 * Gc * ld; }
     else { c.sx = p; c.spub1 = p + (size_t)Gc * ld; c.schy = p + (size_t)2 * Gc * ld; c.spub2 = p + (size_t)3 * Gc * ld; }
     return 0;
 }
@@ -541,7 +545,9 @@ static int adj_sweeps(QpdoDev *d, AdjCall &c, bool have_ry, double tol, long max
             if (sweep >= max_sweeps) break;
             if (m) launch_spmv(d, d->At, c.wry, EpiStore{c.t2}, false);
             LAUNCH(k_adj_solve_rhs, vgrid(n), n, (const double *)c.rx, (const double *)c.t2, d->rhs);
-            rc = c.kind == 3 ? band_solve(d) : dense_solve(d); if (rc) break;
+            // (coupling rows: ONE Woodbury application on the fresh factors of B and S, not band_solve's checked refinement -- this loop is
+            // the refinement on the true system, and an inexact inner solve costs sweeps or ends as code 1, never as code 3)
+            rc = c.kind != 3 ? dense_solve(d) : d->bc_k > 0 ? band_coupled_apply(d, d->rhs, d->dx) : band_solve(d); if (rc) break;
             if (m) launch_spmv(d, d->Ar, d->dx, EpiStore{c.Av}, false);
             LAUNCH(k_adj_update, c.gnm, n, m, (const double *)d->dx, (const double *)c.Av, (const double *)c.ry, (const double *)d->d, c.vx, c.vy);
         }
@@ -601,7 +607,24 @@ static int adj_sweeps_group(QpdoDev *d, AdjCall &c, int cnt, bool have_ry, doubl
         if (m) launch_spmv_group(d, d->At, c.wry, m, false, c.t2, n, live);
         LAUNCH(k_adj_solve_rhs_group, gvn, n, (const double *)c.rx, (const double *)c.t2, c.srhs, live);
         const int nl = __builtin_popcount(live);
-        if (c.kind == 3) {
+        if (c.kind == 3 && d->band_b > BAND_MAX_B) {
+            const int nbc = d->band_np / DNB;
+            if (d->bo_newold)
+                hipLaunchKernelGGL(k_bw_solve_group_perm, dim3(nl), dim3(256), 0, d->stream, n, nbc, d->bw_w, (const double *)d->bw_Wb, (const double *)d->bw_Li,
+                                   (const double *)d->bw_LiT, (const double *)d->bw_Wd, (const double *)c.srhs, (long long)n, c.sz, c.sdvx, (const int *)d->bo_newold);
+            else
+                hipLaunchKernelGGL(k_bw_solve_group, dim3(nl), dim3(256), 0, d->stream, n, nbc, d->bw_w, (const double *)d->bw_Wb, (const double *)d->bw_Li,
+                                   (const double *)d->bw_LiT, (const double *)d->bw_Wd, (const double *)c.srhs, (long long)n, c.sz, c.sdvx);
+        } else if (c.kind == 3 && d->bc_k > 0) {
+            // band_coupled_apply per live column: the single kernels' bodies on columns of their own
+            const size_t lds = (size_t)4 * BAND_SC * (d->band_b + 1) * sizeof(double);
+            hipLaunchKernelGGL(k_band_solve_group, dim3(nl), dim3(256), lds, d->stream, n, d->band_np, d->band_b, (const double *)d->Kb, (const double *)d->Lt,
+                               (const double *)c.srhs, (long long)n, c.sz, c.sz0);
+            hipLaunchKernelGGL(k_bc_t_group, dim3(nl), dim3(1024), 0, d->stream, d->bc_k, d->bc_act, (const int *)d->bc_rows, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                               (const double *)d->Ar.val, (const double *)c.sz0, (long long)n, (const double *)d->bc_SL, c.st);
+            LAUNCH(k_bc_apply_group, dim3(vgrid(n), nl), n, d->band_np, d->bc_k, d->bc_act, (const double *)d->bc_Z, (const double *)c.st, (const double *)c.sz0, c.sdvx,
+                   (long long)n);
+        } else if (c.kind == 3) {
             const size_t lds = (size_t)4 * BAND_SC * (d->band_b + 1) * sizeof(double);
             if (d->bo_newold)
                 hipLaunchKernelGGL(k_band_solve_group_perm, dim3(nl), dim3(256), lds, d->stream, n, d->band_np, d->band_b, (const double *)d->Kb, (const double *)d->Lt,

@@ -470,11 +470,11 @@ __global__ __launch_bounds__(256) void k_bc_factor_S(int k, const double *__rest
     if (bad_pivot && tid == 0) atomicOr(err, 2);
 }
 // t = S^-1 (U' z0): the k dot products A(row_a, :) z0, one wave each in turn, then both triangular solves by one wave (lane a keeps
-// entry a, the pivot entry is broadcast with v_readlane)
-__global__ __launch_bounds__(1024) void k_bc_t(int k, u64 act, const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
-                                               const double *__restrict__ aval, const double *__restrict__ z0, const double *__restrict__ SL,
-                                               double *__restrict__ t) {
-    __shared__ double M[BC_MAX * BC_MAX], v[BC_MAX];
+// entry a, the pivot entry is broadcast with v_readlane).  ONE body: k_bc_t runs it on the workspace's z0 and t, k_bc_t_group (the
+// sensitivity calls' groups, dev/adjoint.inc) once per workgroup on a column of its own.  M: BC_MAX * BC_MAX doubles of LDS, v: BC_MAX.
+__device__ __forceinline__ void bc_t_body(int k, u64 act, const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
+                                          const double *__restrict__ aval, const double *__restrict__ z0, const double *__restrict__ SL, double *__restrict__ t,
+                                          double *M, double *v) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int e = tid; e < k * k; e += 1024) { const int i = e / k, j = e - i * k; if (j <= i) M[i * BC_MAX + j] = SL[i * BC_MAX + j]; }
     for (int a = wave; a < k; a += 16) {
@@ -499,10 +499,23 @@ __global__ __launch_bounds__(1024) void k_bc_t(int k, u64 act, const int *__rest
     }
     if (in) t[lane] = val;
 }
-// out = z0 - Z(:, active slots) t
-__global__ void k_bc_apply(int n, int np, int k, u64 act, const double *__restrict__ Z, const double *__restrict__ t, const double *__restrict__ z0,
-                           double *__restrict__ out) {
-    __shared__ double ts[BC_MAX]; __shared__ int sl[BC_MAX];
+__global__ __launch_bounds__(1024) void k_bc_t(int k, u64 act, const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
+                                               const double *__restrict__ aval, const double *__restrict__ z0, const double *__restrict__ SL,
+                                               double *__restrict__ t) {
+    __shared__ double M[BC_MAX * BC_MAX], v[BC_MAX];
+    bc_t_body(k, act, rows, arp, aci, aval, z0, SL, t, M, v);
+}
+// (one workgroup per live column: z0 ldx apart, t BC_MAX apart, both compact over the live right-hand sides)
+__global__ __launch_bounds__(1024) void k_bc_t_group(int k, u64 act, const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                     const double *__restrict__ aval, const double *__restrict__ z0, long long ldx,
+                                                     const double *__restrict__ SL, double *__restrict__ t) {
+    __shared__ double M[BC_MAX * BC_MAX], v[BC_MAX];
+    const long long s = blockIdx.x;
+    bc_t_body(k, act, rows, arp, aci, aval, z0 + s * ldx, SL, t + s * BC_MAX, M, v);
+}
+// out = z0 - Z(:, active slots) t.  ONE body, as above: k_bc_apply_group's grid.y is the live column (z0 and out ldx apart, t BC_MAX apart)
+__device__ __forceinline__ void bc_apply_body(int n, int np, int k, u64 act, const double *__restrict__ Z, const double *__restrict__ t,
+                                              const double *__restrict__ z0, double *__restrict__ out, double *ts, int *sl) {
     for (int a = threadIdx.x; a < k; a += blockDim.x) { ts[a] = t[a]; sl[a] = bc_nth_slot(act, a); }
     __syncthreads();
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
@@ -510,4 +523,15 @@ __global__ void k_bc_apply(int n, int np, int k, u64 act, const double *__restri
         for (int a = 0; a < k; a++) sacc += Z[(size_t)sl[a] * np + j] * ts[a];
         out[j] = z0[j] - sacc;
     }
+}
+__global__ void k_bc_apply(int n, int np, int k, u64 act, const double *__restrict__ Z, const double *__restrict__ t, const double *__restrict__ z0,
+                           double *__restrict__ out) {
+    __shared__ double ts[BC_MAX]; __shared__ int sl[BC_MAX];
+    bc_apply_body(n, np, k, act, Z, t, z0, out, ts, sl);
+}
+__global__ void k_bc_apply_group(int n, int np, int k, u64 act, const double *__restrict__ Z, const double *__restrict__ t, const double *__restrict__ z0,
+                                 double *__restrict__ out, long long ldx) {
+    __shared__ double ts[BC_MAX]; __shared__ int sl[BC_MAX];
+    const long long s = blockIdx.y;
+    bc_apply_body(n, np, k, act, Z, t + s * BC_MAX, z0 + s * ldx, out + s * ldx, ts, sl);
 }

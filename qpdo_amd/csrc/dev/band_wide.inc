@@ -292,3 +292,26 @@ __global__ __launch_bounds__(256) void k_bw_solve_perm(int n, int nbc, int w, co
     __syncthreads();
     bw_sweep<false, true>(nbc, w, Wb, LiT, Wd, z, nbc * DNB, x, n, win, part, part2, tot, perm);
 }
+// the group path's solve (dev/adjoint.inc adj_sweeps_group): one workgroup per live right-hand side, each running k_bw_solve's two sweeps on
+// columns of its own (rhs and x: ldx apart, z: np = 64 nbc apart) -- to k_bw_solve what k_band_solve_group is to k_band_solve.  Per column
+// it is the single kernel's code.  (No kernel that loads a tile once for all columns: the chain is latency bound, DESIGN.md 3.7.1.)
+__global__ __launch_bounds__(256) void k_bw_solve_group(int n, int nbc, int w, const double *__restrict__ Wb, const double *__restrict__ Li,
+                                                        const double *__restrict__ LiT, const double *__restrict__ Wd, const double *rhs, long long ldx,
+                                                        double *z, double *x) {
+    __shared__ double win[BW_MAX_W + 1][DNB], part[4][DNB], part2[4][DNB], tot[DNB];
+    const long long s = blockIdx.x, np = (long long)nbc * DNB;
+    bw_sweep<true, false>(nbc, w, Wb, Li, Wd, rhs + s * ldx, n, z + s * np, nbc * DNB, win, part, part2, tot, nullptr);
+    __threadfence_block();
+    __syncthreads();
+    bw_sweep<false, false>(nbc, w, Wb, LiT, Wd, z + s * np, nbc * DNB, x + s * ldx, n, win, part, part2, tot, nullptr);
+}
+__global__ __launch_bounds__(256) void k_bw_solve_group_perm(int n, int nbc, int w, const double *__restrict__ Wb, const double *__restrict__ Li,
+                                                             const double *__restrict__ LiT, const double *__restrict__ Wd, const double *rhs, long long ldx,
+                                                             double *z, double *x, const int *__restrict__ perm) {
+    __shared__ double win[BW_MAX_W + 1][DNB], part[4][DNB], part2[4][DNB], tot[DNB];
+    const long long s = blockIdx.x, np = (long long)nbc * DNB;
+    bw_sweep<true, true>(nbc, w, Wb, Li, Wd, rhs + s * ldx, n, z + s * np, nbc * DNB, win, part, part2, tot, perm);
+    __threadfence_block();
+    __syncthreads();
+    bw_sweep<false, true>(nbc, w, Wb, LiT, Wd, z + s * np, nbc * DNB, x + s * ldx, n, win, part, part2, tot, perm);
+}

@@ -180,6 +180,18 @@ static int band_factor(QpdoDev *d, bool force = false) {
     d->dense_valid = 1; d->st.factor_count++;
     return 0;
 }
+// Coupled mode with k = d->bc_k > 0 weighted coupling rows: ONE Woodbury application out = z0 - Z S^-1 (U' z0), z0 = B^-1 v, three
+// launches, no read-back and no latch of its own.  band_solve wraps it in the residual-checked refinement of a Newton pass; the
+// sensitivity calls (dev/adjoint.inc adj_sweeps) take it as it is -- their sweep loop already refines on the true system.
+static int band_coupled_apply(QpdoDev *d, const double *v, double *out) {
+    const int n = d->n, np = d->band_np, k = d->bc_k;
+    const size_t lds = (size_t)4 * BAND_SC * (d->band_b + 1) * sizeof(double);
+    hipLaunchKernelGGL(k_band_solve, dim3(1), dim3(256), lds, d->stream, n, d->band_b, (const double *)d->Kb, (const double *)d->Lt, v, d->band_z, d->bc_z0);
+    hipLaunchKernelGGL(k_bc_t, dim3(1), dim3(1024), 0, d->stream, k, d->bc_act, (const int *)d->bc_rows, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                       (const double *)d->Ar.val, (const double *)d->bc_z0, (const double *)d->bc_SL, d->bc_t);
+    LAUNCH(k_bc_apply, vgrid(n), n, np, k, d->bc_act, (const double *)d->bc_Z, (const double *)d->bc_t, (const double *)d->bc_z0, out);
+    return 0;
+}
 // d->rhs -> d->dx, both in the caller's order; a workspace with a variable order launches the _perm instance of the same kernel (one launch
 // per solve either way: the gather and the scatter are that kernel's first loads and last stores)
 static int band_solve(QpdoDev *d) {
@@ -199,14 +211,10 @@ static int band_solve(QpdoDev *d) {
         // true K that the dense low-rank path uses (dense_refine_checked: its acceptance rule, its sweeps).  A solve that misses the check,
         // like a latched pivot of B or S, sets the latch of the band fallback: the device skips the pass's iterate update, and the
         // host hands the pass and the rest of the solve to another solver (host_step.inc step_redo_if_lost).
-        const int n = d->n, np = d->band_np, k = d->bc_k;
+        const int n = d->n, k = d->bc_k;
         bool ok = false, latched = false;
         int rc = dense_refine_checked(d, [&](int it) -> int {
-            hipLaunchKernelGGL(k_band_solve, dim3(1), dim3(256), lds, d->stream, n, d->band_b, (const double *)d->Kb, (const double *)d->Lt,
-                               (const double *)(it == 0 ? d->rhs : d->pc_r), d->band_z, d->bc_z0);
-            hipLaunchKernelGGL(k_bc_t, dim3(1), dim3(1024), 0, d->stream, k, d->bc_act, (const int *)d->bc_rows, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
-                               (const double *)d->Ar.val, (const double *)d->bc_z0, (const double *)d->bc_SL, d->bc_t);
-            LAUNCH(k_bc_apply, vgrid(n), n, np, k, d->bc_act, (const double *)d->bc_Z, (const double *)d->bc_t, (const double *)d->bc_z0, it == 0 ? d->dx : d->pc_z);
+            band_coupled_apply(d, it == 0 ? d->rhs : d->pc_r, it == 0 ? d->dx : d->pc_z);
             if (it > 0) LAUNCH(k_add_to, vgrid(n), n, (const double *)d->pc_z, d->dx);
             return 0;
         }, [&](bool *go) -> int {

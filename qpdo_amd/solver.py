@@ -618,7 +618,9 @@ class QPDO:
         from gx = dL/dx and gy = dL/dy (None: zero), through the workspace's direct solver (qpdo_amd_adjoint, include/qpdo_amd_ext.h).
         gx: (n,) or (R, n), gy: (m,) / (R, m): R right-hand sides on ONE factorization; the outputs carry the same leading R.  Returns
         dict(dq, dl, du, dQ_values, dA_values (None without matrices), active (m,) int32, status (3,) / (R, 3) int64: code, sweeps,
-        active rows, residual).  A right-hand side whose code is not 0 holds NaN.  A refused call raises RuntimeError with the reason."""
+        active rows, residual).  A right-hand side whose code is not 0 holds NaN.  A refused call raises RuntimeError with the reason.
+        Taken: the dense LDL' and every band workspace (QPDO_LINSOLVE=band: half-bandwidth <= 127, the wide band 128 .. 1023, a variable
+        order, coupling rows -- the last takes more sweeps, one Woodbury application each); refused: PCG, hybrid, row-partitioned."""
         def arr(name, a, length):
             if not isinstance(a, np.ndarray):
                 raise ValueError("%s: expected a numpy array, got %s" % (name, type(a).__name__))
@@ -717,7 +719,8 @@ class QPDO:
 
     def rhs_group(self):
         """The right-hand sides adjoint / tangent carry through every launch of their sweep loop at once on this workspace
-        (qpdo_amd_rhs_group): 8 where it qualifies, 1: one after the other, 0: a workspace the two calls refuse."""
+        (qpdo_amd_rhs_group): 8 where it qualifies (the dense LDL' with chained solves and every band workspace, the wide band and coupling
+        rows included), 1: one after the other, 0: a workspace the two calls refuse."""
         g = lib().qpdo_amd_rhs_group(self._w)
         if g < 0:
             raise RuntimeError("rhs_group: no workspace (call setup first)")

@@ -218,7 +218,7 @@ class _WorkspaceQPFunction(torch.autograd.Function):
 
 class WorkspaceQP(torch.nn.Module):
     """x, y = layer(q, l, u, Q_values=None, A_values=None): the solution of ONE QP held by a solver.QPDO workspace as a differentiable function
-    of its data, at every size the workspace's direct solvers take (QPDO_LINSOLVE=dense or band; see qpdo_amd_adjoint for what is refused).
+    of its data, at every size the workspace's direct solvers take (QPDO_LINSOLVE=dense or band -- the wide band, a variable order and coupling rows included; see qpdo_amd_adjoint for what is refused).
     qp: a solver.QPDO after setup.  q, l, u: tensors of n / m / m entries; Q_values / A_values: the stored values in the setup's pattern
     (qp._Qpat / qp._Apat: CSC column pointers and row indices; Q in the stype given to setup).  None inputs are left as they are in the
     workspace.  warm_start_last: start every solve from the previous finite solution.  on_failure: what the gradients hold when the adjoint
