@@ -360,6 +360,8 @@ int  qpdo_amd_get_band_order(const QPDOWorkspace *work, QPDOAmdBandOrderInfo *ou
  *                  rows, per row its segment of the even slab and then that of the odd one (adjacent), an odd last slab by rows
  *          2  the slab-local column indices in the same order: uint16 where ci16 is present, else int32 (ci - s W)
  *          3  vsm16  IEEE half nnz: (half)(float)(vsm 2^e) in the same order, the stream of the coarse sweeps (count 0 where which 59 says 0)
+ *          4  p16sm  uint16 nnz: the pair-local column indices of an image in pair order, part 2's index plus W for an entry of the odd
+ *                  slab of a pair -- what the pair-wide products gather with (count 0 where the image is not in pair order)
  *   96 (count 0, dst unused): marks both images stale and runs one product with each compact matrix that takes the slab kernel, so
  *      that the image is rebuilt from the CSR, sp and seg as after any change of the row-major arrays */
 #define QPDO_AMD_PCG_NOT_CONVERGED (-3)

@@ -81,7 +81,10 @@ static int upload_csr(QpdoDev *d, DevCsr *M, const QdevCsr *h) {
 static int read_ctrl(QpdoDev *d);
 // decide whether M streams from HBM (then use the LDS-staged kernel) and build its slab pointers
 // arrays of the slab-major image (two padding entries: the 16-byte loads may touch one element past a segment)
-static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, bool with_f32 = false, bool with_h16 = false) {
+// with_p16: the pair-local index words of an image that will be in pair order.  They are 16 bits wide because a pair's 2 W floats share
+// the LDS with the row sums: W < SLAB_LDS_BYTES / 8 whatever the pass.
+static_assert(2 * (SLAB_LDS_BYTES / 8) <= 65536, "pair-local indices are 16 bits wide");
+static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, bool with_f32 = false, bool with_h16 = false, bool with_p16 = false) {
     // the vector loads start at a multiple of their entry count (2, 4; 8 for the half-precision stream, which reads eight values and eight
     // 16-bit indices per load) below the segment's end: up to seven elements past it
     const size_t PAD = 8;
@@ -89,6 +92,7 @@ static int slab_major_alloc(QpdoDev *d, DevCsr *M, size_t nnz_cap, size_t nseg, 
     if (!rc) rc = M->ci16 ? dev_alloc(d, &M->i16sm, nnz_cap + PAD) : dev_alloc(d, &M->cism, nnz_cap + PAD);
     if (!rc && with_f32 && M->ci16) rc = dev_alloc(d, &M->vsm32, nnz_cap + PAD);
     if (!rc && with_h16 && M->vsm32) rc = dev_alloc(d, &M->vsm16, nnz_cap + PAD);
+    if (!rc && with_p16 && M->vsm32) rc = dev_alloc(d, &M->p16sm, nnz_cap + PAD);      // (zeroed, its padding too)
     if (!rc) rc = dev_alloc(d, &M->seg, nseg > 0 ? nseg : 1);
     if (!rc) {
         hipError_t e = hipMemsetAsync(M->vsm + nnz_cap, 0, PAD * sizeof(double), d->stream);
@@ -150,7 +154,7 @@ static void slab_major_build(QpdoDev *d, const DevCsr &M) {
     hipLaunchKernelGGL(k_slab_seg, dim3(M.slab_grid), dim3(1024), 0, d->stream, M.nrows, M.nslabs, M.rows_per_wg, (const int *)M.sp, M.seg, M.seg_pairs);
     hipLaunchKernelGGL(k_slab_permute, dim3(2048), dim3(256), 0, d->stream, M.nrows, M.nslabs, M.W, (const int *)M.sp, (const int2 *)M.seg,
                        (const int *)M.ci, (const unsigned short *)M.ci16, (const double *)M.val, M.vsm, M.i16sm, M.cism, M.vsm32,
-                       h16_dst(d, M), d->h16_scale);
+                       h16_dst(d, M), d->h16_scale, M.p16sm);
     M.sm_dirty = 0;
 }
 // Read-back of a control block.  A pass of the multi-kernel routes makes 1-3 of these and, at mid-size orders, they are a tenth of its time:

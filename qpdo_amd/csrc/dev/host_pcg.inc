@@ -48,7 +48,7 @@ static int build_compact(QpdoDev *d) {
         hipLaunchKernelGGL(k_slab_seg, dim3(R.slab_grid), dim3(1024), 0, d->stream, R.nrows, R.nslabs, R.rows_per_wg, (const int *)R.sp, R.seg, R.seg_pairs);
 #define COPY_ROWS_SLAB(DIAG) LAUNCH((k_copy_rows_slab<DIAG>), PASS_GRID, k, (const int *)d->rowlist, d->Ar.rp, d->Ar.ci, (const unsigned short *)d->Ar.ci16, \
             d->Ar.val, (const int *)R.rp, R.ci, R.ci16, R.val, RW16, R.nslabs, R.W, (const int *)R.sp, (const int2 *)R.seg, R.vsm, R.i16sm, R.cism, \
-            R.vsm32, h16_dst(d, R), d->h16_scale, (const double *)d->qdiag, d->sigma_f, (const double *)d->dc, d->s_diag)
+            R.vsm32, h16_dst(d, R), d->h16_scale, (const double *)d->qdiag, d->sigma_f, (const double *)d->dc, d->s_diag, R.p16sm)
         if (diag) { COPY_ROWS_SLAB(true); d->sdiag_valid = 1; d->sdiag_sigma = d->sigma_f; } else COPY_ROWS_SLAB(false);
 #undef COPY_ROWS_SLAB
     } else {
@@ -88,7 +88,7 @@ static int build_compact(QpdoDev *d) {
         }
         hipLaunchKernelGGL(k_compact_rows_bits_slab, dim3(PASS_GRID), dim3(BLK), lds_tab, d->stream, n, M.rp, M.ci, M.val, (const u64 *)d->flag_bits,
                            (const int *)d->flag_wprefix, words, (const int *)T.rp, T.ci, T.val, W16, M.ci16 ? d->Atc.ci16 : (unsigned short *)nullptr,
-                           T.nslabs, T.W, (const int *)spT, (const int2 *)T.seg, T.vsm, T.i16sm, T.cism, T.vsm32, h16_dst(d, T), d->h16_scale);
+                           T.nslabs, T.W, (const int *)spT, (const int2 *)T.seg, T.vsm, T.i16sm, T.cism, T.vsm32, h16_dst(d, T), d->h16_scale, T.p16sm);
     } else if (lds_tab <= 60 * 1024) {          // flags and renumbering as LDS tables: the kernels stream the matrix only
         DISPATCH_TPR_LDS(M, k_count_flagged_bits, g, (size_t)words * 8, n, M.rp, M.ci, (const u64 *)d->flag_bits, words, d->row_cnt);
         dev_scan(d, d->row_cnt, n, T.rp, T.rp + n, d->scan_tsum);

@@ -356,6 +356,7 @@ int qdev_download_compact(QpdoDev *d, int which, void *dst, long count) {
             case 1: src = M.vsm; len = (size_t)M.nnz; break;
             case 2: if (M.i16sm) { src = M.i16sm; esz = 2; } else { src = M.cism; esz = 4; } len = (size_t)M.nnz; break;
             case 3: if (h16_dst(d, M)) { src = M.vsm16; esz = 2; len = (size_t)M.nnz; } break;      // (count 0 where the image has no half-precision values)
+            case 4: if (M.seg_pairs) { src = M.p16sm; esz = 2; len = (size_t)M.nnz; } break;        // (count 0 where the image is not in pair order)
             default: return set_err(hipErrorInvalidValue, "download compact: unknown array", __LINE__);
         }
     } else switch (which) {

@@ -167,8 +167,8 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
     if (!rc) {   // per-pass compact copies used by PCG
         d->Arc = d->Ar; d->Arc.rp = nullptr; d->Arc.ci = nullptr; d->Arc.val = nullptr; d->Arc.sp = nullptr; d->Arc.ci16 = nullptr;
         d->Atc = d->At; d->Atc.rp = nullptr; d->Atc.ci = nullptr; d->Atc.val = nullptr; d->Atc.sp = nullptr; d->Atc.ci16 = nullptr;
-        d->Arc.vsm = nullptr; d->Arc.i16sm = nullptr; d->Arc.cism = nullptr; d->Arc.seg = nullptr; d->Arc.vsm32 = nullptr; d->Arc.vsm16 = nullptr;
-        d->Atc.vsm = nullptr; d->Atc.i16sm = nullptr; d->Atc.cism = nullptr; d->Atc.seg = nullptr; d->Atc.vsm32 = nullptr; d->Atc.vsm16 = nullptr;
+        d->Arc.vsm = nullptr; d->Arc.i16sm = nullptr; d->Arc.cism = nullptr; d->Arc.seg = nullptr; d->Arc.vsm32 = nullptr; d->Arc.vsm16 = nullptr; d->Arc.p16sm = nullptr;
+        d->Atc.vsm = nullptr; d->Atc.i16sm = nullptr; d->Atc.cism = nullptr; d->Atc.seg = nullptr; d->Atc.vsm32 = nullptr; d->Atc.vsm16 = nullptr; d->Atc.p16sm = nullptr;
         { const char *f32 = getenv("QPDO_PCG_INNER_F32"); d->inner_f32 = (f32 && atoi(f32) != 0) ? 1 : 0; }
         // the default inner solve: fp32 stream, accepted on the fp64 residual (single GPU; "0": the fp64 inner CG)
         { const char *rf = getenv("QPDO_PCG_INNER_REFINE"); d->inner_refine = !(rf && *rf && atoi(rf) == 0) && !d->comm.active; }
@@ -186,6 +186,7 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         { const char *hs = getenv("QPDO_INNER_H16_MAXSWEEP"); d->h16_maxsweep = (hs && *hs && atoi(hs) >= 0) ? atoi(hs) : 2; }
         { const char *he = getenv("QPDO_INNER_H16_ETA"); d->h16_eta = (he && atof(he) > 0 && atof(he) < 1.0) ? atof(he) : 1e-3; }
         const bool with_h16 = d->inner_h16 != 0;
+        const bool with_p16 = with_f32 && d->inner_x32;      // the images that will be in pair order (below) carry pair-local index words
         { const char *co = getenv("QPDO_COMPACT_ONE_READ"); d->compact_one_read = !(co && *co && atoi(co) == 0); }
         { const char *ct = getenv("QPDO_COMPACT_T_ONE_READ"); d->compact_t_one_read = !(ct && *ct && atoi(ct) == 0); }
         rc = dev_alloc(d, &d->Arc.rp, (size_t)m + 1);
@@ -193,13 +194,13 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         if (!rc) rc = dev_alloc(d, &d->Arc.val, (size_t)d->Ar.nnz);
         if (!rc && d->Ar.use_slab) rc = dev_alloc(d, &d->Arc.sp, (size_t)m * (d->Ar.nslabs + 1));
         if (!rc && d->Ar.ci16) rc = dev_alloc(d, &d->Arc.ci16, (size_t)d->Ar.nnz);
-        if (!rc && d->Ar.use_slab) rc = slab_major_alloc(d, &d->Arc, (size_t)d->Ar.nnz, (size_t)m * d->Ar.nslabs, with_f32, with_h16);
+        if (!rc && d->Ar.use_slab) rc = slab_major_alloc(d, &d->Arc, (size_t)d->Ar.nnz, (size_t)m * d->Ar.nslabs, with_f32, with_h16, with_p16);
         if (!rc) rc = dev_alloc(d, &d->Atc.rp, (size_t)n + 1);
         if (!rc) rc = dev_alloc(d, &d->Atc.ci, (size_t)d->At.nnz);
         if (!rc) rc = dev_alloc(d, &d->Atc.val, (size_t)d->At.nnz);
         if (!rc && d->At.use_slab) rc = dev_alloc(d, &d->Atc.sp, (size_t)n * (d->At.nslabs + 1));
         if (!rc && d->At.ci16) rc = dev_alloc(d, &d->Atc.ci16, (size_t)d->At.nnz);
-        if (!rc && d->At.use_slab) rc = slab_major_alloc(d, &d->Atc, (size_t)d->At.nnz, (size_t)n * d->At.nslabs, with_f32, with_h16);
+        if (!rc && d->At.use_slab) rc = slab_major_alloc(d, &d->Atc, (size_t)d->At.nnz, (size_t)n * d->At.nslabs, with_f32, with_h16, with_p16);
         if (!rc) rc = dev_alloc(d, &d->row_cnt, (size_t)(n > m ? n : m));
         if (!rc) rc = dev_alloc(d, &d->cidx, (size_t)m);
         if (!rc) rc = dev_alloc(d, &d->rowlist, (size_t)m);
@@ -210,7 +211,7 @@ static int create_tail(QpdoDev *d, int32_t n, int32_t m, const double *q, const 
         if (!rc) rc = dev_alloc(d, &d->tc, (size_t)m);
         if (!rc && with_f32 && d->inner_x32) { rc = dev_alloc(d, &d->s_z32, (size_t)m + 4); if (!rc) rc = dev_alloc(d, &d->tmp_n32, (size_t)n + 4); }
         // pair order only where the pair-wide products will run: the slab-by-slab products are slower on it (docs/LAB_NOTES.md)
-        d->Arc.seg_pairs = (d->Arc.vsm32 && d->s_z32 && d->tmp_n32) ? 1 : 0; d->Atc.seg_pairs = (d->Atc.vsm32 && d->s_z32 && d->tmp_n32) ? 1 : 0;
+        d->Arc.seg_pairs = (d->Arc.p16sm && d->s_z32 && d->tmp_n32) ? 1 : 0; d->Atc.seg_pairs = (d->Atc.p16sm && d->s_z32 && d->tmp_n32) ? 1 : 0;
         d->lds_doubles_At = (int)slab_cap_w((160 * 1024 - 1024) / 8 - d->At.rows_per_wg);
         if (!rc) rc = dev_alloc(d, &d->qdiag, (size_t)n);
         const char *df = getenv("QPDO_DEFLATE");

@@ -67,6 +67,7 @@ __global__ __launch_bounds__(256) void k_spmv(const int *__restrict__ done, int 
 // in LDS across slabs in a fixed order, so results are reproducible.
 // ------------------------------------------------------------------------------------------------
 static const int SLAB_THREADS = 1024;
+static constexpr int SLAB_LDS_BYTES = 160 * 1024 - 512;      // dynamic LDS a launch may ask for: the x slice (pair) and the row sums
 #define SLAB_UNR 8               // 16-byte loads in flight per lane
 static constexpr int SLAB_TPR = 16;     // lanes per row segment (16 x 16-byte loads measured best at C4; 8 and 32: tools/lab/slab_lab.hip)
 // OVL (the default; QPDO_SLAB_OVERLAP=0 keeps the old schedule): the slab boundaries are hidden behind matrix loads already in flight.
@@ -93,7 +94,8 @@ typedef float slab_f4 __attribute__((ext_vector_type(4)));
 // XT (the type of the staged operand): double as above; float (only with VT = float, and only on an image in pair order, k_slab_seg)
 // reads an fp32 copy of x, so the LDS that holds W doubles holds the slices of TWO column slabs and the kernel walks slab PAIRS: a row's
 // two segments of a pair are adjacent in the image and are streamed as one segment, [beg, mid) of slab 2S and [mid, end) of slab 2S + 1
-// (a last single slab is a pair with an empty second half); an entry at or behind mid gathers xs[W + its slab-local index].  Half the
+// (a last single slab is a pair with an empty second half); an entry at or behind mid gathers xs[W + its slab-local index]: these
+// instances read the image's PAIR-LOCAL index words (DevCsr::p16sm, passed as `i16sm`), which carry that W already.  Half the
 // row hand-outs, seg loads and shuffle trees, half the slab boundaries and half the staging traffic of the slab-by-slab instance, and
 // no other matrix byte.  A float times a float is exact in double, so the product's own rounding is that of the sums alone, as before.
 #define SLAB_UNR32 4             // fp32 stream: 16-byte value loads in flight per lane
@@ -109,6 +111,15 @@ typedef float slab_f4 __attribute__((ext_vector_type(4)));
 #endif
 #ifndef SLAB_TPR16
 #define SLAB_TPR16 8
+#endif
+// SLAB_GB16: loads of a trip whose operands are gathered before their products (SLAB_UNR16: the whole trip; SLAB_UNR16 / 2: half trips).
+// SLAB_SKIP16: a load behind the first that no lane of the wave needs is neither gathered nor multiplied.  (Measured on the C4 solve,
+// docs/LAB_NOTES.md, "fused exact products".)
+#ifndef SLAB_GB16
+#define SLAB_GB16 (SLAB_UNR16 / 2)
+#endif
+#ifndef SLAB_SKIP16
+#define SLAB_SKIP16 1
 #endif
 typedef _Float16 slab_h8 __attribute__((ext_vector_type(8)));
 template <class VT, class XT> struct SlabStream;
@@ -189,45 +200,59 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
     // OVL: the first trip of the group's prefetched row (pv, pw: written on every pass of the prefetch, so that they are live
     // only from there to the row's first trip -- the register allocator then gives them the registers of the streaming loop)
     Vec pv[UNR]; IdxW pw[UNR];
-    int pr = -1, pbeg = 0, pmid = 0, pend = 0;
-    // segment [beg, end) of `row` in step s: that of slab s, or the two adjacent ones of pair s with the second slab's entries from mid on
-    auto seg_of = [&](int row, int s, int &beg, int &mid, int &end) {
+    int pr = -1, pbeg = 0, pend = 0;
+    // segment [beg, end) of `row` in step s: that of slab s, or the two adjacent ones of pair s (which entries are the second slab's is in
+    // the pair-local index words)
+    auto seg_of = [&](int row, int s, int &beg, int &end) {
         if constexpr (X32) {
             const int2 a = seg[(size_t)row * nslabs + 2 * s];
             const int lb = 2 * s + 1 < nslabs ? seg[(size_t)row * nslabs + 2 * s + 1].y : 0;
-            beg = a.x; mid = a.x + a.y; end = mid + lb;
+            beg = a.x; end = a.x + a.y + lb;
         } else {
             const int2 a = seg[(size_t)row * nslabs + s];
-            beg = a.x; end = a.x + a.y; mid = end;
+            beg = a.x; end = a.x + a.y;
         }
     };
     // row r's segment [beg, end) of the staged slab (pair), added to acc[r]; PRE: the loads of the first trip are in pv / pw
-    auto row_seg = [&](int r, int beg, int mid, int end, auto pre) {
+    auto row_seg = [&](int r, int beg, int end, auto pre) {
         constexpr bool PRE = decltype(pre)::value;
         const int kb = beg & ~(EPL - 1);
         double sa[NSA];
 #pragma unroll
         for (int u = 0; u < NSA; u++) sa[u] = 0.0;
         // A trip in straight-line code, GB loads at a time.  Gathers: the operand of EVERY entry slot is read from LDS, whatever the slot's
-        // position -- an index word of a load is a slab-local index of the image or its zero padding, so the address is inside xs; only
-        // behind the last entry of a per-pass image that an earlier, larger pass wrote may a slot hold an index of that pass's wider slab,
+        // position -- an index word of a load is an index of the image into xs (slab-local; pair-local, [0, 2 W), in the pair-wide
+        // instances, whose index words are DevCsr::p16sm) or its zero padding, so the address is inside xs; only behind the last entry of a
+        // per-pass image that an earlier, larger pass wrote may a slot hold an index of that pass's wider slab (pair: below 2 W_old),
         // and an LDS read past the workgroup's allocation returns zero, is a read, and feeds a slot that does not count -- and the reads
         // do not depend on each other: they are issued together and waited for together, not one LDS round trip per entry.
         // Products: the slot at position p of the image counts when beg <= p < end.  Only the first load of a lane's trip can lie before
         // beg (kb > beg - EPL), and there the test is one unsigned compare, p - beg < end - beg; every other load compares the entry's
-        // number with end - kk.  A slot that does not count adds +0.0 whatever was gathered for it: the select is on the product, so a
-        // NaN or an Inf of a column that the row does not touch, or of LDS that the last slab did not stage, never reaches a sum.  The
-        // pair's second slab (entries from mid on) is a second base pointer, chosen by the entry's number against mid - kk.  No `&&` or
-        // `||` in here: the compiler makes a branch per entry of their short circuit and sinks the gather under it.
-        constexpr int GB = X32 ? UNR : UNR / 2;         // (a double operand is two registers per gather: half a trip keeps every instance within 128)
+        // number with end - kk.  A slot that does not count adds a zero whatever was gathered for it, so a NaN or an Inf of a column that
+        // the row does not touch, or of LDS that the last slab did not stage, never reaches a sum.  fp32 and fp64 values (which may be
+        // Inf): the select is on the product, +0.0 for a masked slot.  Half-precision values (finite by construction, h16_round): the
+        // select is on the OPERAND, xm = in ? x : 0, and the slot is one fma(v, xm, s) -- v xm is exact in double (11 x 24 bits, exponents
+        // far inside the range), so the fma rounds once where s + v x rounded; a masked slot adds v (+0) = +-0 to a sum that began as
+        // +0.0 and, to nearest, never becomes -0.0, so s stays s.  No `&&` or `||` in here: the compiler makes a branch per entry of
+        // their short circuit and sinks the gather under it.
+        // SKIP (half-precision instance): load u >= 1 of a trip is neither gathered nor multiplied when no lane of the wave has an entry in
+        // it (kk >= end for all 64; one uniform branch per load) -- every slot of it would have added +-0, and which sum a slot goes to
+        // does not depend on it.
+        constexpr int GB = H16 ? SLAB_GB16 : X32 ? UNR : UNR / 2;    // (a double operand is two registers per gather: half a trip keeps every instance within 128)
+        constexpr bool SKIP = H16 && SLAB_SKIP16 != 0;
+        static_assert(UNR % GB == 0, "whole gather batches");
         const unsigned len = (unsigned)(end - beg);
         auto fma_trip = [&](const Vec *v, const IdxW *w, int k) {
 #pragma unroll
             for (int u0 = 0; u0 < UNR; u0 += GB) {
                 XT xg[GB][EPL];
+                bool live[GB];
 #pragma unroll
                 for (int g = 0; g < GB; g++) {
                     const int u = u0 + g;
+                    live[g] = true;
+                    if constexpr (SKIP) { if (u > 0) live[g] = __builtin_amdgcn_ballot_w64(k + u * EPL * TPR < end) != 0; }
+                    if (!live[g]) continue;
                     int ax[EPL];
                     if constexpr (H16) {
                         const unsigned wd[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
@@ -239,15 +264,12 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
                         if constexpr (I16) { ax[0] = (int)(w[u] & 0xffffu); ax[1] = (int)(w[u] >> 16); }
                         else               { ax[0] = w[u].x; ax[1] = w[u].y; }
                     }
-                    const int tm = mid - (k + u * EPL * TPR);
 #pragma unroll
-                    for (int e = 0; e < EPL; e++) {
-                        if constexpr (X32) { const XT *xb = e >= tm ? xs + W : xs; xg[g][e] = xb[ax[e]]; }
-                        else               xg[g][e] = xs[ax[e]];
-                    }
+                    for (int e = 0; e < EPL; e++) xg[g][e] = xs[ax[e]];
                 }
 #pragma unroll
                 for (int g = 0; g < GB; g++) {
+                    if (!live[g]) continue;
                     const int u = u0 + g, kk = k + u * EPL * TPR;
                     double vv[EPL];
                     if constexpr (H16) {
@@ -262,11 +284,19 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
                     const int hi = end - kk;
 #pragma unroll
                     for (int e = 0; e < EPL; e++) {
-                        const double pe = vv[e] * (double)xg[g][e];
                         const bool in = u == 0 ? t + (unsigned)e < len : e < hi;
-                        sa[(EPL * u + e) % NSA] += in ? pe : 0.0;
+                        if constexpr (H16) {
+                            const float xm = in ? xg[g][e] : 0.0f;
+                            sa[(EPL * u + e) % NSA] = __builtin_fma(vv[e], (double)xm, sa[(EPL * u + e) % NSA]);
+                        } else {
+                            const double pe = vv[e] * (double)xg[g][e];
+                            sa[(EPL * u + e) % NSA] += in ? pe : 0.0;
+                        }
                     }
                 }
+                // (a build without SKIP: the scheduler otherwise hoists the next batch's gathers and conversions over this one's products, 128 VGPRs
+                // and 12-24 bytes of scratch; with SKIP the uniform branches keep the batches apart and this line changes no instruction)
+                if constexpr (H16 && !SKIP) __builtin_amdgcn_sched_barrier(0);
             }
         };
         int k = kb + EPL * lane;
@@ -291,7 +321,7 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
         pr = -1;
         const int g = tid / TPR;
         if (s < nsteps && g < R && !epi.skip(row0 + g)) {
-            seg_of(row0 + g, s, pbeg, pmid, pend);
+            seg_of(row0 + g, s, pbeg, pend);
             pr = g;
             const int kb = pbeg & ~(EPL - 1);
             if (kb + EPL * lane < pend) load_trip(pv, pw, kb + EPL * lane, kb, pend);
@@ -322,7 +352,7 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
             if (OVL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the copies have landed in LDS
         }
         __syncthreads();
-        if (OVL && pr >= 0) row_seg(pr, pbeg, pmid, pend, std::true_type());
+        if (OVL && pr >= 0) row_seg(pr, pbeg, pend, std::true_type());
         // Rows are handed out dynamically (LDS counter): with only a few row segments per lane group and slab a
         // static split leaves groups idle at the end-of-slab barrier.  One lane per WAVE grabs a batch of 64/TPR
         // rows and broadcasts it wave-wide, so the loop exit is wave-uniform (no divergent break around the
@@ -337,9 +367,9 @@ __global__ __launch_bounds__(1024) void k_spmv_slab(const int *__restrict__ done
             if (r >= R) continue;
             const int row = row0 + r;
             if (epi.skip(row)) continue;
-            int beg, mid, end;
-            seg_of(row, s, beg, mid, end);
-            row_seg(r, beg, mid, end, std::false_type());
+            int beg, end;
+            seg_of(row, s, beg, end);
+            row_seg(r, beg, end, std::false_type());
         }
         if (OVL) prefetch(s + 1);
     }
@@ -419,13 +449,20 @@ __global__ __launch_bounds__(1024) void k_slab_seg(int nrows, int nslabs, int ro
 }
 // One entry of the half-precision image (DevCsr::vsm16): v scaled by the workspace's power of two h16s = 2^e (exact), rounded to float and
 // then to half, each step to nearest even; what lands in the subnormal range of half stays a subnormal.
+// INVARIANT: every value of the half-precision image is finite.  h16_refresh_scale keeps max |a| 2^e in [2^14, 2^15), below half's largest
+// finite 65504, and sets no scale (no image, no coarse sweeps) for an A whose largest magnitude is not finite; the allocation is zeroed,
+// its padding included.  k_spmv_slab's half-precision instance relies on it: it masks the operand of a slot that does not count, not the
+// product, and v (+0) is a zero only for a finite v.
 __device__ __forceinline__ _Float16 h16_round(double v, double h16s) { return (_Float16)(float)(v * h16s); }
+// One entry of the pair-local index image (DevCsr::p16sm): the slab-local index c16 of an entry of slab sl, plus W in the odd slab of a
+// pair -- where the pair-wide product finds its operand among the 2 W floats of the staged pair.  (A last single slab is even.)
+__device__ __forceinline__ unsigned short pair_local(unsigned short c16, int sl, int W) { return (unsigned short)(c16 + ((sl & 1) ? W : 0)); }
 // copy values and slab-local indices of every (row, slab) segment to its slab-major place; 16 lanes per row
 __global__ __launch_bounds__(256) void k_slab_permute(int nrows, int nslabs, int W, const int *__restrict__ sp, const int2 *__restrict__ seg,
                                                       const int *__restrict__ ci, const unsigned short *__restrict__ ci16,
                                                       const double *__restrict__ val, double *__restrict__ vsm,
                                                       unsigned short *__restrict__ i16sm, int *__restrict__ cism, float *__restrict__ vsm32,
-                                                      _Float16 *__restrict__ vsm16, double h16s) {
+                                                      _Float16 *__restrict__ vsm16, double h16s, unsigned short *__restrict__ p16sm) {
     const int lane = threadIdx.x & 15;
     const int ngroups = gridDim.x * (blockDim.x >> 4);
     for (int row = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4); row < nrows; row += ngroups)
@@ -438,6 +475,7 @@ __global__ __launch_bounds__(256) void k_slab_permute(int nrows, int nslabs, int
                 if (vsm32) vsm32[sg.x + e] = (float)v;
                 if (vsm16) vsm16[sg.x + e] = h16_round(v, h16s);
                 if (i16sm) i16sm[sg.x + e] = ci16[src + e]; else cism[sg.x + e] = ci[src + e] - sl * W;
+                if (p16sm) p16sm[sg.x + e] = pair_local(ci16[src + e], sl, W);
             }
         }
 }
@@ -610,7 +648,7 @@ static void slab_major_build(QpdoDev *d, const DevCsr &M);
 template <auto K, class... Args>
 static void launch_slab(QpdoDev *d, const DevCsr &M, Args... args) {
     static thread_local bool attr_set = false;   // per kernel
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr_set = true; }
+    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, SLAB_LDS_BYTES); attr_set = true; }
     if (M.sm_dirty) slab_major_build(d, M);
     const size_t lds = ((size_t)M.W + (size_t)M.rows_per_wg) * sizeof(double);
     hipLaunchKernelGGL(K, dim3(M.slab_grid), dim3(SLAB_THREADS), lds, d->stream, args...);
@@ -634,10 +672,10 @@ static void launch_spmv_slab(QpdoDev *d, const DevCsr &M, const double *x, Epi e
 }
 // The pair-wide products: a narrow copy `vals` of the values -- fp32 (vsm32), or half precision (vsm16, whose scale rscale = 2^-e undoes)
 // -- and the fp32 copy x32 of the operand.  M takes the slab kernel, carries that copy and i16sm (schur_f32_ready, schur_h16_ready) and
-// its image is in pair order (DevCsr::seg_pairs, k_slab_seg).
+// its image is in pair order (DevCsr::seg_pairs, k_slab_seg), which comes with the pair-local index words p16sm that these instances stream.
 template <class VT, class Epi>
 static void launch_spmv_x32(QpdoDev *d, const DevCsr &M, const VT *vals, double rscale, const float *x32, Epi epi, const int *done) {
-#define SLAB_GO(OVL, NT) launch_slab<k_spmv_slab<VT, float, Epi, true, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.i16sm, vals, x32, epi, rscale)
+#define SLAB_GO(OVL, NT) launch_slab<k_spmv_slab<VT, float, Epi, true, OVL, NT>>(d, M, done, M.nrows, M.ncols, M.nslabs, M.W, M.rows_per_wg, M.seg, M.cism, M.p16sm, vals, x32, epi, rscale)
     if (M.slab_ovl) { if (M.slab_nt) SLAB_GO(true, true); else SLAB_GO(true, false); }
     else            { if (M.slab_nt) SLAB_GO(false, true); else SLAB_GO(false, false); }
 #undef SLAB_GO
@@ -930,7 +968,7 @@ __global__ __launch_bounds__(256) void k_copy_rows_slab(int k, const int *__rest
                                                         const int2 *__restrict__ seg, double *__restrict__ vsm, unsigned short *__restrict__ i16sm,
                                                         int *__restrict__ cism, float *__restrict__ vsm32, _Float16 *__restrict__ vsm16, double h16s,
                                                         const double *__restrict__ qdiag, double sigma_f, const double *__restrict__ dc,
-                                                        double *__restrict__ sdiag) {
+                                                        double *__restrict__ sdiag, unsigned short *__restrict__ p16sm) {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * BLK + threadIdx.x) >> 6;
     const int nwaves = gridDim.x * (BLK >> 6);
@@ -963,6 +1001,7 @@ __global__ __launch_bounds__(256) void k_copy_rows_slab(int k, const int *__rest
                     if (vsm32) vsm32[q] = (float)v[u];
                     if (vsm16) vsm16[q] = h16_round(v[u], h16s);
                     if (i16sm) i16sm[q] = c16; else cism[q] = cl;
+                    if (p16sm) p16sm[q] = pair_local(c16, sl, W);
                     if (DIAG) s += v[u] * v[u] / (qdiag[c[u]] + sigma_f);
                 }
             }
@@ -1157,7 +1196,7 @@ __global__ __launch_bounds__(256) void k_compact_rows_bits_slab(int nrows, const
                                                                 unsigned short *__restrict__ ci16, int nslabs, int W, const int *__restrict__ sp,
                                                                 const int2 *__restrict__ seg, double *__restrict__ vsm,
                                                                 unsigned short *__restrict__ i16sm, int *__restrict__ cism, float *__restrict__ vsm32,
-                                                                _Float16 *__restrict__ vsm16, double h16s) {
+                                                                _Float16 *__restrict__ vsm16, double h16s, unsigned short *__restrict__ p16sm) {
     extern __shared__ u64 sbits_cmps[];
     int *spre = reinterpret_cast<int *>(sbits_cmps + words);
     for (int i = threadIdx.x; i < words; i += BLK) { sbits_cmps[i] = bits[i]; spre[i] = wprefix[i]; }
@@ -1197,6 +1236,7 @@ __global__ __launch_bounds__(256) void k_compact_rows_bits_slab(int nrows, const
                         if (vsm32) vsm32[q] = (float)v[u];
                         if (vsm16) vsm16[q] = h16_round(v[u], h16s);
                         if (i16sm) i16sm[q] = (unsigned short)cl; else cism[q] = cl;
+                        if (p16sm) p16sm[q] = pair_local((unsigned short)cl, sl, W);
                     } else if (W16 > 0) ci16[pos] = (unsigned short)(cn % W16);
                 }
                 base += __popcll(bal);

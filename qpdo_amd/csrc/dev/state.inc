@@ -43,6 +43,10 @@ struct DevCsr {
     // optional half-precision copy of vsm in the same image, scaled by the workspace's power of two (QpdoDev::h16_e): the stream of the
     // refined inner solve's coarse sweeps (QPDO_INNER_H16).  Only on an image in pair order (seg_pairs).
     _Float16 *vsm16 = nullptr;
+    // pair-local 16-bit indices of an image in pair order (seg_pairs): i16sm's slab-local index, plus W for an entry of the odd slab of a
+    // pair -- the index words of the pair-wide products (k_spmv_slab, XT = float), whose LDS holds the 2 W floats of a pair (2 W <= 65536:
+    // the kernel's LDS holds fewer than 40 960 floats).  The slab-by-slab products of the same image read i16sm.
+    unsigned short *p16sm = nullptr;
     double alg_bytes() const { return 12.0 * (double)nnz + 4.0 * (nrows + 1) + 8.0 * nrows + 8.0 * ncols; }
     double alg_bytes32() const { return alg_bytes() - 4.0 * (double)nnz; }       // the same product on the fp32 copy of the values
     double alg_bytes16() const { return alg_bytes() - 6.0 * (double)nnz; }       // ... and on the half-precision copy

@@ -1114,7 +1114,7 @@ int qpdo_amd_pcg_probe(QPDOWorkspace *work, const double *dw, double sigma, cons
     return rc == QDEV_PCG_NOT_CONVERGED ? QPDO_AMD_PCG_NOT_CONVERGED : rc == QDEV_PCG_NAN ? QPDO_AMD_PCG_NAN : rc ? -1 : 0;
 }
 int qpdo_amd_download_compact(QPDOWorkspace *work, int which, void *dst, long count) {
-    if (which < 0 || which > 96 || (which > 57 && which < 64 && which != 59 && which != 60) || (which < 48 && which % 16 > 5) || (which >= 64 && which < 96 && which % 16 > 3)) {
+    if (which < 0 || which > 96 || (which > 57 && which < 64 && which != 59 && which != 60) || (which < 48 && which % 16 > 5) || (which >= 64 && which < 96 && which % 16 > 4)) {
         qdev_set_error("download compact: unknown array"); return -1;
     }
     if (count < 0) { qdev_set_error("download compact: negative count"); return -1; }

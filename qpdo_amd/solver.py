@@ -892,7 +892,7 @@ class QPDO:
     def download_compact_image(self, name):
         """the slab-major image of "Arc" or "Atc" as the slab kernel streams it (qpdo_amd_download_compact, which >= 64): seg as an
         nrows x nslabs x 2 array of (start, length), vsm, the slab-local indices and vsm16, the half-precision values as float16 (None where
-        the image has none); None where the matrix takes the plain kernel"""
+        the image has none); None where the matrix takes the plain kernel.  download_compact_pair_index has the pair-local indices."""
         mat = {"Arc": 0, "Atc": 1}[name]
         g = self._compact_get(16 * mat, np.int64, 7)
         nrows, nnz, use_slab, nslabs, has_ci16 = int(g[0]), int(g[2]), int(g[3]), int(g[4]), int(g[6])
@@ -903,6 +903,18 @@ class QPDO:
         return dict(vsm16=self._compact_get(base + 3, np.float16, nnz) if h16[0] else None, h16_e=int(h16[1]) if h16[0] else None, seg=self._compact_get(base, np.int32, 2 * nrows * nslabs).reshape(nrows, nslabs, 2),
                     vsm=self._compact_get(base + 1, np.float64, nnz),
                     idx=self._compact_get(base + 2, np.uint16 if has_ci16 else np.int32, nnz))
+
+    def download_compact_pair_index(self, name):
+        """the pair-local 16-bit indices of the image of "Arc" or "Atc" (qpdo_amd_download_compact, which 68 / 84): what the pair-wide
+        products gather with -- the slab-local index, plus W in the odd slab of a pair; None where the image is not in pair order"""
+        mat = {"Arc": 0, "Atc": 1}[name]
+        g = self._compact_get(16 * mat, np.int64, 7)
+        if not int(g[3]):
+            return None
+        which, probe = 64 + 16 * mat + 4, np.zeros(1, np.uint16)
+        if lib().qpdo_amd_download_compact(self._w, which, probe.ctypes.data_as(C.c_void_p), 0) == 0:
+            return None                                       # (the array's length is 0: a count of 0 is accepted only then)
+        return self._compact_get(which, np.uint16, int(g[2]))
 
     def download_linesearch_order(self):
         """the breakpoint indices as the last linesearch's radix sort left them (qpdo_amd_download_compact, which 60)"""
