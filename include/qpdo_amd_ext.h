@@ -29,6 +29,23 @@
  *                    QPDOAmdStats.coupled_*).  No such row: the plain band solver, bit for bit.  More than R: the matrix counts as not
  *                    banded ("band" makes qpdo_setup fail with a message that names both numbers).  Q or the other rows wider than 127:
  *                    the half-bandwidth over all rows, as without the variable.  Read at qpdo_setup; one GPU
+ *   QPDO_BAND_BORDER unset or "0": off (default).  "<C>", 1 <= C <= 64: BORDER VARIABLES are a few variables that appear everywhere on a
+ *                    chain-structured QP -- a global slack, a free final time, a shared parameter, the first stage of a multi-scenario
+ *                    problem -- and give K a dense row and column each.  They MUST BE NUMBERED LAST (problems.permute_variables, or the
+ *                    caller's own numbering).  qpdo_setup runs qpdo_amd_band_border (below) on the pattern: K = [B C; C' D] with B the
+ *                    n_core x n_core core of half-bandwidth b_core <= 127 and c = n - n_core trailing border variables.  With 1 <= c <= C
+ *                    and a core that the selection rule above takes on (n_core, b_core) -- automatic for n_core >= 2048, on request from
+ *                    n_core = 4 (b_core + 1) -- the band solver runs by block elimination: the band LDL' of B (the bits of the plain band
+ *                    workspace on the problem without the border columns), the c columns of [C; D], one multi-right-hand-side band solve
+ *                    for Z = B^-1 C, S = D - C'Z factored in LDS; a solve is z0 = B^-1 rhs_1, t = S^-1 (rhs_2 - C'z0), x = [z0 - Z t; t]:
+ *                    three launches, an exact LDL' of K in that order, no refinement.  A pivot of B or S that is not a positive finite
+ *                    number hands the pass to the dense solver / PCG (band_fallbacks).  c = 0: the plain band workspace, bit for bit.
+ *                    c > C, or a core the rule does not take: as if the variable were unset (QPDOAmdBandBorderInfo keeps c in `over`;
+ *                    for c > C "band" makes qpdo_setup fail with a message that names both numbers).  IGNORED, with the reason recorded:
+ *                    row-partitioned workspaces, the fused small-problem route, QPDO_LINSOLVE = dense or pcg, QPDO_BAND_COUPLING > 0
+ *                    (the coupling-row mode keeps precedence).  A configured band order is ignored on a workspace that adopts a border
+ *                    (reason 6 of qpdo_amd_get_band_order).  qpdo_amd_adjoint / _tangent take such a workspace with the right-hand
+ *                    sides one after the other (qpdo_amd_rhs_group = 1).  Read at qpdo_setup; one GPU
  *   QPDO_BAND_ORDER  unset, "" or "0": the band solver works in the caller's variable order (default).  "rcm": qpdo_setup computes a reverse
  *                    Cuthill-McKee order of the pattern of Q + A'A on the host and, where that narrows the half-bandwidth, the band
  *                    detection, the selection rule above and the band solver run on the reordered matrix (qpdo_amd_band_order_config
@@ -267,7 +284,11 @@ int  qpdo_amd_linesearch(QPDOWorkspace *work, double eta, double beta, const dou
  *   band under a variable order (qpdo_amd_band_order_config below):
  *    12  newold n entries as doubles: newold[k] = the caller's index of the variable at position k of the solver's order (-1 with a
  *               message on a workspace that adopted none).  On such a workspace arrays 4, 5, 7 and 8 are in the SOLVER's order: they
- *               hold the factor of P K P', P K P'(k, l) = K(newold[k], newold[l]).  */
+ *               hold the factor of P K P', P K P'(k, l) = K(newold[k], newold[l]).
+ *   band with border variables (QPDO_BAND_BORDER; arrays 4 and 5 hold the factor of the core B, which 6 its geometry):
+ *    13  the border geometry, 4 entries: n_core, c, b_core, np = n_core rounded up to 4 (0 before the first factorization).
+ *    14  C      np x c, leading dimension np: column j = K(0 .. n_core-1, n_core + j) (rows n_core .. np-1 zero).
+ *    15  Z      np x c, leading dimension np: column j = B^-1 C(:, j) (-1 with a message on a workspace without a border).  */
 #define QPDO_AMD_DIRECT_LOST (-2)
 int  qpdo_amd_direct_solve(QPDOWorkspace *work, const double *dw, double sigma, const double *rhs, double *x, int flags);
 int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count);
@@ -296,8 +317,9 @@ int  qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long 
  *   as without an order -- so qpdo_amd_direct_solve, qpdo_amd_adjoint / _tangent (groups of 8 included), the band fallback ladder,
  *   qpdo_amd_update_matrices (fixed pattern: the order stays) and qpdo_update_q see no difference.
  *   IGNORED (the natural order is kept, `reason` says why): 2 row-partitioned workspaces; 3 QPDO_BAND_COUPLING > 0 (a coupling row is
- *   wide under every order); 4 workspaces on the fused small-problem route; 5 QPDO_LINSOLVE = dense or pcg.  reason 1: RCM found no
- *   narrower order.  0: adopted, or nothing configured.
+ *   wide under every order); 4 workspaces on the fused small-problem route; 5 QPDO_LINSOLVE = dense or pcg; 6 a workspace that adopted
+ *   a border of coupling variables (QPDO_BAND_BORDER: an arrowhead is wide under every order).  reason 1: RCM found no narrower order.
+ *   0: adopted, or nothing configured.
  * qpdo_amd_get_band_order: what the workspace's setup decided; newold (n entries, or NULL) is written only when adopted = 1. */
 #define QPDO_AMD_BAND_ORDER_ENV     0   /* default: QPDO_BAND_ORDER in the environment decides ("rcm"; unset, "" or "0": natural) */
 #define QPDO_AMD_BAND_ORDER_NATURAL 1
@@ -307,6 +329,22 @@ typedef struct { long mode, adopted, b_natural, b_ordered, reason; double order_
 int  qpdo_amd_band_order(const cholmod_sparse *Q, const cholmod_sparse *A, long *newold, long *info4);
 int  qpdo_amd_band_order_config(int mode, const long *newold, long n);
 int  qpdo_amd_get_band_order(const QPDOWorkspace *work, QPDOAmdBandOrderInfo *out, long *newold /* n entries or NULL */);
+/* ---- a border of coupling variables over a band core (QPDO_BAND_BORDER above; qpdo_amd/csrc/band_border.c) ---------------
+ * qpdo_amd_band_border: the detection, O(nnz), pure host code, deterministic.  With T = 127, n_core starts at n; a stored entry (i, j) of Q
+ *   with |i - j| > T sets n_core <= max(i, j); a row of A with ascending columns c1 < c2 < ... sets n_core <= the first column that
+ *   exceeds c1 + T (every column of the row below that one is then within T of every other).  info4 = {n_core, c = n - n_core, b_core,
+ *   reason}: b_core = the half-bandwidth of the pattern restricted to the columns < n_core, at least 3; reason = 1 when c > max_border,
+ *   else 0.  The border variables are the TRAILING ones: number shared variables last.  Q's stype is honoured as qpdo_setup honours it,
+ *   explicit zeros count, both itypes, row indices in any order within a column; A may be NULL or have no rows.  Returns 0, or -1 (bad
+ *   arguments, no memory).
+ * qpdo_amd_get_band_border: what the workspace's setup decided.  max_border: C as read (0: unset); border: the adopted c (0: none);
+ *   n_core, b_core: the detection's (0 where it did not run); over: a c that was seen and not adopted; reason: 0 adopted, no border or
+ *   unset; 1 c > C; 2 row-partitioned; 3 QPDO_BAND_COUPLING > 0; 4 the fused small-problem route; 5 QPDO_LINSOLVE = dense or pcg; 6 the
+ *   core is too short for the selection rule.  border_solves: the solves by block elimination since the counters were last reset (with
+ *   QPDOAmdStats). */
+typedef struct { long max_border, border, n_core, b_core, over, reason; long border_solves; } QPDOAmdBandBorderInfo;
+int  qpdo_amd_band_border(const cholmod_sparse *Q, const cholmod_sparse *A, long max_border, long *info4);
+int  qpdo_amd_get_band_border(const QPDOWorkspace *work, QPDOAmdBandBorderInfo *out);
 /* ---- the PCG linear-solve path as single steps (tests of its pieces; tests/test_gpu_pcg_pieces.py) ------------------------------------
  * K = Q + sigma I + A' diag(dw) A with the workspace's stored matrices (the caller's own with settings->scaling = 0), dw: m weights; a row
  * is "weighted" when dw_i != 0.0 (so -0.0 is not, a subnormal is).  Only for PCG workspaces (QPDO_LINSOLVE=pcg) on one GPU: a dense, band

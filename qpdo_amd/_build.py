@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libqpdo_amd.so")
 GEN_PATH = os.path.join(_HERE, "libqpdo_gen.so")
 
 HIP_SOURCES = ["qpdo_dev.hip", "qpdo_small.hip"]
-C_SOURCES = ["qpdo_api.c", "csc_convert.c", "band_order.c"]
+C_SOURCES = ["qpdo_api.c", "csc_convert.c", "band_order.c", "band_border.c"]
 HEADERS = ["qpdo_dev.h", "csc_convert.h", "band_order.h", "small_lds.h", os.path.join(INCLUDE, "qpdo.h"), os.path.join(INCLUDE, "qpdo_amd_ext.h")] + \
     sorted(os.path.join("dev", f) for f in os.listdir(os.path.join(CSRC, "dev")) if f.endswith(".inc"))
 
@@ -137,7 +137,7 @@ def build_all(force=False, verbose=False):
 def build_abi_driver(out_dir, sanitize=False, driver="abi_driver.c"):
     """Compiles tests/abi_driver.c -- a plain-C caller that includes only include/qpdo.h -- (or another stand-alone C caller under
     tests/, `driver`) and links it against the
-    product library.  sanitize=True: the host driver (qpdo_api.c, csc_convert.c and band_order.c, gcc) is rebuilt with -fsanitize=address,undefined and
+    product library.  sanitize=True: the host driver (qpdo_api.c, csc_convert.c, band_order.c and band_border.c, gcc) is rebuilt with -fsanitize=address,undefined and
     linked with the already compiled device objects into libqpdo_amd_asan.so inside out_dir (the product library in
     the tree is not touched); the driver is instrumented too.  Returns the path of the executable."""
     root = os.path.dirname(_HERE)

@@ -28,7 +28,18 @@ enum {
     BAND_ORDER_REASON_PARTITIONED = 2,   /* row-partitioned workspace */
     BAND_ORDER_REASON_COUPLING = 3,      /* QPDO_BAND_COUPLING > 0: a coupling row is wide under every order */
     BAND_ORDER_REASON_FUSED = 4,         /* the fused small-problem route */
-    BAND_ORDER_REASON_LINSOLVE = 5       /* QPDO_LINSOLVE is dense or pcg */
+    BAND_ORDER_REASON_LINSOLVE = 5,      /* QPDO_LINSOLVE is dense or pcg */
+    BAND_ORDER_REASON_BORDER = 6         /* the workspace adopted a border of coupling variables (QPDO_BAND_BORDER): an arrowhead is wide under every order */
+};
+/* reasons a border of coupling variables was not adopted (QPDOAmdBandBorderInfo.reason; 2 .. 5 as above: the detection does not run) */
+enum {
+    BAND_BORDER_REASON_NONE = 0,         /* adopted, no border (c = 0), or the variable unset */
+    BAND_BORDER_REASON_OVER = 1,         /* more border columns than QPDO_BAND_BORDER accepts */
+    BAND_BORDER_REASON_PARTITIONED = 2,
+    BAND_BORDER_REASON_COUPLING = 3,     /* QPDO_BAND_COUPLING > 0: the coupling-row mode keeps precedence */
+    BAND_BORDER_REASON_FUSED = 4,
+    BAND_BORDER_REASON_LINSOLVE = 5,
+    BAND_BORDER_REASON_CORE = 6          /* the core is too short for the band solver's selection rule */
 };
 
 /* The half-bandwidth of the pattern of Q + A'A by band_detect's definition (dev/host_band.inc) -- the largest |i - j| over the

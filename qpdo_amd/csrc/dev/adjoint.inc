@@ -346,12 +346,13 @@ int qdev_adjoint_check_kind(QpdoDev *d, const char *who) {
 }
 // The group size of the two calls on this workspace as it stands: the right-hand sides that go through every launch of the sweep loop at
 // once.  0: a workspace the calls refuse.  1 (the right-hand sides follow one another): a matrix on the slab kernel -- a slab multi-vector
-// product does not exist --, and the dense route on the stepwise solves (QPDO_DENSE_SOLVE=steps, or after a lost producer).  Otherwise
-// QPDO_AMD_RHS_GROUP as read at setup, 8 by default.
+// product does not exist --, and the dense route on the stepwise solves (QPDO_DENSE_SOLVE=steps, or after a lost producer), and
+// the band solver's bordered mode (QPDO_BAND_BORDER), which has no group kernels.  Otherwise QPDO_AMD_RHS_GROUP as read at setup, 8 by default.
 int qdev_rhs_group(QpdoDev *d) {
     if (adj_kind_refusal(d)) return 0;
     if (d->Qf.use_slab || d->Ar.use_slab || d->At.use_slab) return 1;
     if (d->linsolve == 1 && !d->dense_chain) return 1;
+    if (d->linsolve == 3 && d->bb_c > 0) return 1;
     return d->rhs_group_cfg;
 }
 int qdev_get_group_stats(QpdoDev *d, QdevGroupStats *out) { *out = d->grp; out->group = qdev_rhs_group(d); return 0; }

@@ -469,6 +469,24 @@ __global__ __launch_bounds__(256) void k_bc_factor_S(int k, const double *__rest
     for (int e = tid; e < k * k; e += 256) { const int i = e / k, j = e - i * k; if (j <= i) SL[i * BC_MAX + j] = M[i * BC_MAX + j]; }
     if (bad_pivot && tid == 0) atomicOr(err, 2);
 }
+// t = (L D L')^-1 v for the k x k factor in M (leading dimension BC_MAX; L below the diagonal, D on it), by the workgroup's first wave: lane
+// a keeps entry a, the pivot entry is broadcast with v_readlane.  (Behind the barrier that publishes M and v.)
+__device__ __forceinline__ void bc_tri_solve(int k, const double *M, const double *v, double *__restrict__ t) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave != 0) return;
+    const bool in = lane < k;
+    double val = in ? v[lane] : 0.0;
+    for (int j = 0; j < k; j++) {
+        const double vj = band_rl64(val, j);
+        if (in && lane > j) val = val - M[lane * BC_MAX + j] * vj;
+    }
+    if (in) val = val / M[lane * BC_MAX + lane];
+    for (int j = k - 1; j > 0; j--) {
+        const double xj = band_rl64(val, j);
+        if (lane < j) val = val - M[j * BC_MAX + lane] * xj;
+    }
+    if (in) t[lane] = val;
+}
 // t = S^-1 (U' z0): the k dot products A(row_a, :) z0, one wave each in turn, then both triangular solves by one wave (lane a keeps
 // entry a, the pivot entry is broadcast with v_readlane).  ONE body: k_bc_t runs it on the workspace's z0 and t, k_bc_t_group (the
 // sensitivity calls' groups, dev/adjoint.inc) once per workgroup on a column of its own.  M: BC_MAX * BC_MAX doubles of LDS, v: BC_MAX.
@@ -485,19 +503,7 @@ __device__ __forceinline__ void bc_t_body(int k, u64 act, const int *__restrict_
         if (lane == 0) v[a] = sacc;
     }
     __syncthreads();
-    if (wave != 0) return;
-    const bool in = lane < k;
-    double val = in ? v[lane] : 0.0;
-    for (int j = 0; j < k; j++) {
-        const double vj = band_rl64(val, j);
-        if (in && lane > j) val = val - M[lane * BC_MAX + j] * vj;
-    }
-    if (in) val = val / M[lane * BC_MAX + lane];
-    for (int j = k - 1; j > 0; j--) {
-        const double xj = band_rl64(val, j);
-        if (lane < j) val = val - M[j * BC_MAX + lane] * xj;
-    }
-    if (in) t[lane] = val;
+    bc_tri_solve(k, M, v, t);
 }
 __global__ __launch_bounds__(1024) void k_bc_t(int k, u64 act, const int *__restrict__ rows, const int *__restrict__ arp, const int *__restrict__ aci,
                                                const double *__restrict__ aval, const double *__restrict__ z0, const double *__restrict__ SL,
@@ -534,4 +540,106 @@ __global__ void k_bc_apply_group(int n, int np, int k, u64 act, const double *__
     __shared__ double ts[BC_MAX]; __shared__ int sl[BC_MAX];
     const long long s = blockIdx.y;
     bc_apply_body(n, np, k, act, Z, t + s * BC_MAX, z0 + s * ldx, out + s * ldx, ts, sl);
+}
+
+// ---- chain QPs with a few coupling VARIABLES (QPDO_BAND_BORDER; host side: dev/host_band.inc band_border_refresh) ----------------------------
+// Variables that appear everywhere -- a global slack, a free final time, a shared parameter -- give K a dense row and column each, and no
+// order narrows an arrowhead.  Numbered last, they leave K = [B C; C' D]: B (nc x nc, the core variables) banded, C nc x c, D c x c, c <=
+// BC_MAX.  Block elimination is an exact LDL' of the SPD K in that order -- nothing cancels, so unlike the Woodbury solve of the coupling
+// rows it needs no residual check around it:
+//   refresh   B = L D L' (k_band_assemble / k_band_factor on n = nc: the assembly drops what lands at a row >= n, so Kb holds the bits of
+//             the plain band workspace of the core-only problem), [C; D] (k_bb_assemble), Z = B^-1 C (k_band_solve_group, a workgroup
+//             per column), S = D - C'Z (k_bb_S), S = L D L' in LDS (k_bc_factor_S);
+//   solve     z0 = B^-1 rhs_1 (k_band_solve), t = S^-1 (rhs_2 - C'z0) (k_bb_t), x_1 = z0 - Z t, x_2 = t (k_bb_apply).
+// C, Z and the forward results: columns np apart (np = nc rounded up to 4); D, S and its factor: leading dimension BC_MAX.
+// Every sum below has a fixed order: the same call twice gives the same bits.
+
+// Column jb of [C; D] = column v = nc + jb of K, one workgroup per border column, plain stores.  Rows of A are column-sorted, so the border
+// entries of a row are its tail: A(r, v) is found by walking back from the row's end while the column is >= nc (at most c steps).
+//   core rows i < nc, a thread per element: Q(i, v), then the weighted rows of A that hold both i and v in ascending order -- the
+//     per-element order and the products (w A(r, v)) A(r, i) of band_assemble_body on column v; rows i = nc .. np-1 of C are zero;
+//   border rows a >= jb, a wave per element (a border variable may sit in every row of A): lane l sums the rows l, l + 64, ... of its
+//     variable's list, ascending, the lanes are summed by wave_sum's tree; Q(u, v) first, sigma_f on the diagonal last.  The element goes
+//     to D(a, jb) and D(jb, a): D is symmetric bit for bit.
+__global__ __launch_bounds__(1024) void k_bb_assemble(int nc, int np, int c, const int *__restrict__ qrp, const int *__restrict__ qci,
+                                                      const double *__restrict__ qval, const int *__restrict__ trp, const int *__restrict__ tci,
+                                                      const double *__restrict__ tval, const int *__restrict__ arp, const int *__restrict__ aci,
+                                                      const double *__restrict__ aval, const double *__restrict__ dw, double sigma_f,
+                                                      double *__restrict__ Cm, double *__restrict__ Dm) {
+    const int jb = blockIdx.x, v = nc + jb, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double *col = Cm + (size_t)jb * np;
+    // (w A(r, v)) a_ri added to acc when row r holds v; rows without v, or without weight, add nothing
+    auto row_term = [&](int r, double a_ri, double &acc) {
+        const double wgt = dw[r];
+        if (wgt == 0.0) return;
+        for (int e = arp[r + 1] - 1; e >= arp[r] && aci[e] >= nc; e--)
+            if (aci[e] == v) { acc += (wgt * aval[e]) * a_ri; break; }
+    };
+    for (int i = threadIdx.x; i < np; i += 1024) {
+        double acc = 0.0;
+        if (i < nc) {
+            for (int k = qrp[i]; k < qrp[i + 1]; k++) if (qci[k] == v) acc += qval[k];
+            for (int t = trp[i]; t < trp[i + 1]; t++) row_term(tci[t], tval[t], acc);
+        }
+        col[i] = acc;
+    }
+    for (int a = jb + wave; a < c; a += 16) {
+        const int u = nc + a;
+        double qacc = 0.0, acc = 0.0;
+        for (int k = qrp[u] + lane; k < qrp[u + 1]; k += 64) if (qci[k] == v) qacc += qval[k];
+        for (int t = trp[u] + lane; t < trp[u + 1]; t += 64) row_term(tci[t], tval[t], acc);
+        qacc = wave_sum(qacc); acc = wave_sum(acc);
+        if (lane == 0) {
+            double e = qacc + acc;
+            if (a == jb) e += sigma_f;
+            Dm[a * BC_MAX + jb] = e; Dm[jb * BC_MAX + a] = e;
+        }
+    }
+}
+// S(a, j) = D(a, j) - C(:, a)'Z(:, j), a >= j and its mirror image; one workgroup per element: thread l sums the rows l, l + 256, ...
+// ascending, the threads are summed by wave_sum's tree and the four waves in order
+__global__ __launch_bounds__(256) void k_bb_S(int nc, int np, const double *__restrict__ Cm, const double *__restrict__ Z, const double *__restrict__ Dm,
+                                              double *__restrict__ S) {
+    __shared__ double part[4];
+    const int a = blockIdx.x, j = blockIdx.y;
+    if (a < j) return;
+    const double *ca = Cm + (size_t)a * np, *zj = Z + (size_t)j * np;
+    double sacc = 0.0;
+    for (int i = threadIdx.x; i < nc; i += 256) sacc += ca[i] * zj[i];
+    sacc = wave_sum(sacc);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sacc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s = Dm[a * BC_MAX + j] - (((part[0] + part[1]) + part[2]) + part[3]);
+        S[a * BC_MAX + j] = s; S[j * BC_MAX + a] = s;
+    }
+}
+// t = S^-1 (rhs_2 - C'z0): the c dot products C(:, a)'z0, one wave each in turn (lane l sums the rows l, l + 64, ... ascending, then
+// wave_sum's tree), then both triangular solves by one wave (bc_tri_solve).  One workgroup.
+__global__ __launch_bounds__(1024) void k_bb_t(int nc, int np, int c, const double *__restrict__ Cm, const double *__restrict__ z0,
+                                               const double *__restrict__ rhs2, const double *__restrict__ SL, double *__restrict__ t) {
+    __shared__ double M[BC_MAX * BC_MAX], v[BC_MAX];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int e = tid; e < c * c; e += 1024) { const int i = e / c, j = e - i * c; if (j <= i) M[i * BC_MAX + j] = SL[i * BC_MAX + j]; }
+    for (int a = wave; a < c; a += 16) {
+        const double *ca = Cm + (size_t)a * np;
+        double sacc = 0.0;
+        for (int i = lane; i < nc; i += 64) sacc += ca[i] * z0[i];
+        sacc = wave_sum(sacc);
+        if (lane == 0) v[a] = rhs2[a] - sacc;
+    }
+    __syncthreads();
+    bc_tri_solve(c, M, v, t);
+}
+// in place on x = [z0; .]: x_1 = z0 - Z t (the columns in ascending order), x_2 = t
+__global__ void k_bb_apply(int nc, int np, int c, const double *__restrict__ Z, const double *__restrict__ t, double *x) {
+    __shared__ double ts[BC_MAX];
+    for (int a = threadIdx.x; a < c; a += blockDim.x) ts[a] = t[a];
+    __syncthreads();
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nc + c; j += gridDim.x * blockDim.x) {
+        if (j >= nc) { x[j] = ts[j - nc]; continue; }
+        double sacc = 0.0;
+        for (int a = 0; a < c; a++) sacc += Z[(size_t)a * np + j] * ts[a];
+        x[j] = x[j] - sacc;
+    }
 }

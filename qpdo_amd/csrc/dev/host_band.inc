@@ -93,7 +93,7 @@ static int band_wide_factor(QpdoDev *d) {
 static int band_alloc(QpdoDev *d) {
     if (d->band_b > BAND_MAX_B) return band_wide_alloc(d);
     if (d->Kb) return 0;
-    d->band_np = (d->n + 3) & ~3;
+    d->band_np = ((d->bb_c > 0 ? d->bb_ncore : d->n) + 3) & ~3;
     const size_t cnt = (size_t)d->band_np * (d->band_b + 1);
     int rc = dev_alloc(d, &d->Kb, cnt);
     if (!rc) rc = dev_alloc(d, &d->Lt, cnt);
@@ -103,9 +103,20 @@ static int band_alloc(QpdoDev *d) {
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         if (e == hipSuccess && d->bo_newold) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_perm), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         if (e == hipSuccess && d->bc_r > 0) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_multi), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
+        if (e == hipSuccess && d->bb_c > 0) e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_band_solve_group), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         if (e != hipSuccess) rc = set_err(e, "hipFuncSetAttribute", __LINE__);
     }
-    if (!rc && d->bc_r > 0) {                            // coupled mode: three np x r arrays (right-hand sides, forward results, Z), the k x k system
+    if (!rc && d->bb_c > 0) {                            // bordered mode: three np x c arrays (C, forward results, Z), the c x c blocks
+        const size_t cols = (size_t)d->band_np * (size_t)d->bb_c;
+        rc = dev_alloc(d, &d->bb_C, cols);
+        if (!rc) rc = dev_alloc(d, &d->bb_T, cols);
+        if (!rc) rc = dev_alloc(d, &d->bb_Z, cols);
+        if (!rc) rc = dev_alloc(d, &d->bb_D, (size_t)BC_MAX * BC_MAX);
+        if (!rc) rc = dev_alloc(d, &d->bb_S, (size_t)BC_MAX * BC_MAX);
+        if (!rc) rc = dev_alloc(d, &d->bb_SL, (size_t)BC_MAX * BC_MAX);
+        if (!rc) rc = dev_alloc(d, &d->bb_t, (size_t)BC_MAX);
+    }
+    if (!rc && d->bc_r > 0) {                           // coupled mode: three np x r arrays (right-hand sides, forward results, Z), the k x k system
         const size_t cols = (size_t)d->band_np * (size_t)d->bc_r, mm = (size_t)d->m;
         rc = dev_alloc(d, &d->bc_dcore, mm);
         if (!rc) rc = dev_alloc(d, &d->bc_dfact, mm);
@@ -159,9 +170,34 @@ static int band_coupled_refresh(QpdoDev *d, bool force) {
     d->bc_act = act; d->bc_k = k; d->dense_valid = 1;
     return 0;
 }
+// Bordered mode (dev/band.inc): the factor of the core B, the border columns [C; D], Z = B^-1 C and the factored S = D - C'Z for the
+// current (sigma_f, d).  Five launches behind the assembly, whatever c is; no read-back.  The core goes through the plain band solver's
+// two kernels with n = n_core: k_band_assemble drops what lands at a row >= n, so the border variables never reach the band and Kb holds
+// the bits of a plain band workspace on the problem without the border columns.
+static int band_border_refresh(QpdoDev *d) {
+    int rc = band_alloc(d); if (rc) return rc;
+    const int nc = d->bb_ncore, np = d->band_np, b = d->band_b, c = d->bb_c;
+    int g = (np + 3) / 4; if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(k_band_assemble, dim3(g), dim3(256), 0, d->stream, nc, np, b, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
+                       (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                       (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->Kb);
+    const size_t lds_f = ((size_t)(b + 4) * (b + 1) + 8 * (size_t)(b + 4)) * sizeof(double), lds_s = (size_t)4 * BAND_SC * (b + 1) * sizeof(double);
+    hipLaunchKernelGGL((k_band_factor<256, BAND_MAX_B>), dim3(1), dim3(256), lds_f, d->stream, np, b, d->Kb, d->Lt, &d->ctrl->cnt[C_CHAIN_ERR]);
+    hipLaunchKernelGGL(k_bb_assemble, dim3(c), dim3(1024), 0, d->stream, nc, np, c, (const int *)d->Qf.rp, (const int *)d->Qf.ci, (const double *)d->Qf.val,
+                       (const int *)d->At.rp, (const int *)d->At.ci, (const double *)d->At.val, (const int *)d->Ar.rp, (const int *)d->Ar.ci,
+                       (const double *)d->Ar.val, (const double *)d->d, d->sigma_f, d->bb_C, d->bb_D);
+    hipLaunchKernelGGL(k_band_solve_group, dim3(c), dim3(256), lds_s, d->stream, nc, np, b, (const double *)d->Kb, (const double *)d->Lt,
+                       (const double *)d->bb_C, (long long)np, d->bb_T, d->bb_Z);
+    hipLaunchKernelGGL(k_bb_S, dim3(c, c), dim3(256), 0, d->stream, nc, np, (const double *)d->bb_C, (const double *)d->bb_Z, (const double *)d->bb_D, d->bb_S);
+    hipLaunchKernelGGL(k_bc_factor_S, dim3(1), dim3(256), 0, d->stream, c, (const double *)d->bb_S, d->bb_SL, &d->ctrl->cnt[C_CHAIN_ERR]);
+    HIPCHK(hipGetLastError());
+    d->dense_valid = 1; d->st.factor_count++;
+    return 0;
+}
 // force (coupled mode only): factor B again even where the kept factor's weights and sigma_f are the current ones
 static int band_factor(QpdoDev *d, bool force = false) {
     if (d->band_b > BAND_MAX_B) return band_wide_factor(d);
+    if (d->bb_c > 0) return band_border_refresh(d);
     if (d->bc_r > 0) return band_coupled_refresh(d, force);
     int rc = band_alloc(d); if (rc) return rc;
     const int n = d->n, np = d->band_np, b = d->band_b;
@@ -206,6 +242,17 @@ static int band_solve(QpdoDev *d) {
         return 0;
     }
     const size_t lds = (size_t)4 * BAND_SC * (d->band_b + 1) * sizeof(double);
+    if (d->bb_c > 0) {
+        // Bordered mode: rhs and dx carry the border entries behind the core's, so nothing is gathered.  z0 = B^-1 rhs_1 goes straight
+        // into dx, t = S^-1 (rhs_2 - C'z0), then dx_1 -= Z t and dx_2 = t in place: three launches, a plain direct solve.
+        const int nc = d->bb_ncore, np = d->band_np, c = d->bb_c;
+        hipLaunchKernelGGL(k_band_solve, dim3(1), dim3(256), lds, d->stream, nc, d->band_b, (const double *)d->Kb, (const double *)d->Lt, (const double *)d->rhs, d->band_z, d->dx);
+        hipLaunchKernelGGL(k_bb_t, dim3(1), dim3(1024), 0, d->stream, nc, np, c, (const double *)d->bb_C, (const double *)d->dx, (const double *)d->rhs + nc,
+                           (const double *)d->bb_SL, d->bb_t);
+        LAUNCH(k_bb_apply, vgrid(d->n), nc, np, c, (const double *)d->bb_Z, (const double *)d->bb_t, d->dx);
+        d->st.border_solves++;
+        return 0;
+    }
     if (d->bc_k > 0) {
         // Coupled mode with k weighted coupling rows: x = z0 - Z S^-1 (U' z0), z0 = B^-1 v, as the inner solver of the refinement on the
         // true K that the dense low-rank path uses (dense_refine_checked: its acceptance rule, its sweeps).  A solve that misses the check,

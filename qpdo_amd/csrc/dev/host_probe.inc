@@ -134,6 +134,7 @@ int qdev_direct_solve(QpdoDev *d, const double *dw, double sigma, const double *
     if (rc) return rc;
     if (lost) {
         snprintf(g_err, sizeof(g_err), "direct solve: %s", d->linsolve == 3 ? (d->bc_r > 0 ? "the band factorization or the coupling rows' k x k system met a pivot that is not a positive finite number, or the solve missed its residual check"
+                                                                                            : d->bb_c > 0 ? "the band factorization of the core or the border's c x c system met a pivot that is not a positive finite number"
                                                                                             : "the band factorization met a pivot that is not a positive finite number")
                                                                             : "a polling kernel lost its producer");
         return QDEV_DIRECT_LOST;
@@ -168,6 +169,15 @@ int qdev_download_factor(QpdoDev *d, int which, double *dst, long count) {
         std::vector<int32_t> no((size_t)(d->n ? d->n : 1));
         int rcn = qdev_band_order_newold(d, no.data()); if (rcn) return rcn;
         for (int k = 0; k < d->n; k++) dst[k] = (double)no[(size_t)k];
+        return 0;
+    }
+    if (which >= 13 && which <= 15) {                   // bordered mode (QPDO_BAND_BORDER)
+        if (d->bb_c <= 0) return set_err(hipErrorInvalidValue, "download factor: this workspace has no border variables", __LINE__);
+        const size_t np = (size_t)d->band_np, len = which == 13 ? 4 : np * (size_t)d->bb_c;      // (np: 0 before the first factorization)
+        if (count < 0 || (size_t)count != len) return set_err(hipErrorInvalidValue, "download factor: count is not the array's length", __LINE__);
+        if (which == 13) { dst[0] = (double)d->bb_ncore; dst[1] = (double)d->bb_c; dst[2] = (double)d->band_b; dst[3] = (double)np; return 0; }
+        if (len) HIPCHK(hipMemcpyAsync(dst, which == 14 ? d->bb_C : d->bb_Z, len * 8, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
         return 0;
     }
     const double *src = nullptr; size_t len = 0;

@@ -292,6 +292,14 @@ int qdev_band_order_newold(QpdoDev *d, int32_t *newold) {
     HIPCHK(hipStreamSynchronize(d->stream));
     return 0;
 }
+// The bordered band (host side of the detection: csrc/band_border.c; qpdo_dev.h has the contract).  Nothing is allocated before the first
+// factorization (band_alloc).
+int qdev_set_band_border(QpdoDev *d, int max_border, int n_core, int border, int b_core, int over) {
+    if (border < 0 || border > BC_MAX || (border > 0 && (n_core < 1 || n_core + border != d->n || b_core < 3 || b_core > BAND_MAX_B)))
+        return set_err(hipErrorInvalidValue, "band border: not a border of this workspace", __LINE__);
+    d->bb_max = max_border; d->bb_c = border; d->bb_ncore = border ? n_core : 0; d->bb_bcore = border ? b_core : 0; d->bb_over = over;
+    return 0;
+}
 int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     const char *gr = getenv("QPDO_PCG_GRAPH");
     if (gr && !strcmp(gr, "0")) d->pcg_graph = 0;
@@ -342,10 +350,14 @@ int qdev_configure(QpdoDev *d, int linsolve, double pcg_tol, int pcg_maxit) {
     // QPDO_BAND_COUPLING=<R>, 1 <= R <= 64 (opt-in): up to R rows of A wider than the band are taken out of it and handled as a low-rank
     // term of the band solver (dev/band.inc, host_band.inc); the selection rule below is the same, on the half-bandwidth of the rest.
     { const char *bc = getenv("QPDO_BAND_COUPLING"); const int R = (bc && *bc) ? atoi(bc) : 0; d->band_coupling = R <= 0 ? 0 : R > BC_MAX ? BC_MAX : R; }
-    if (linsolve < 0 || linsolve == 3) {
+    // QPDO_BAND_BORDER=<C> (opt-in): a border of 1 .. C trailing variables over a core that this rule takes was adopted by the caller
+    // (qdev_set_band_border; csrc/band_border.c has the detection and qpdo_api.c the rule on (n_core, b_core)): the band solver, on the core.
+    if ((linsolve < 0 || linsolve == 3) && d->bb_c > 0) { d->band_b = d->bb_bcore; d->bc_r = 0; d->bc_over = 0; d->linsolve = 3; }
+    else if (linsolve < 0 || linsolve == 3) {
         int rcb = band_detect(d); if (rcb) return rcb;
         const int wide_enough = d->n >= 4 * (d->band_b + 1);
         if (d->band_b > 0 && wide_enough && (linsolve == 3 || (d->band_b <= BAND_MAX_B && d->n >= 2048))) d->linsolve = 3;
+        else if (linsolve == 3 && d->bb_over) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: the Newton matrix is not banded: %d trailing border variables reach beyond the band (half-bandwidth > %d), QPDO_BAND_BORDER accepts %d", d->bb_over, BAND_MAX_B, d->bb_max); return -1; }
         else if (linsolve == 3 && d->bc_over) { snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: %d rows of A are wider than the band (column span > %d), QPDO_BAND_COUPLING accepts %d", d->bc_over, BAND_MAX_B, d->band_coupling); return -1; }
         else if (linsolve == 3 && d->bo_seen_ord >= 0) {
             snprintf(g_err, sizeof(g_err), "QPDO_LINSOLVE=band: the Newton matrix is not banded (half-bandwidth > %d or order too small; half-bandwidth %d in the caller's "

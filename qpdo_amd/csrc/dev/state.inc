@@ -120,6 +120,12 @@ struct QpdoDev {
     int band_coupling = 0, bc_r = 0, bc_over = 0, bc_k = 0, bc_factored = 0; double bc_fact_sigma = 0.0; u64 bc_zvalid = 0, bc_act = 0;
     int *bc_rows = nullptr, *bc_info = nullptr; std::vector<int> bc_rows_h;
     double *bc_dcore = nullptr, *bc_dfact = nullptr, *bc_U = nullptr, *bc_T = nullptr, *bc_Z = nullptr, *bc_S = nullptr, *bc_SL = nullptr, *bc_t = nullptr, *bc_z0 = nullptr;
+    // chain QPs with a few coupling VARIABLES (QPDO_BAND_BORDER; qdev_set_band_border before qdev_configure; dev/band.inc, the bordered
+    // mode): the trailing bb_c variables (0: none, and nothing below is read) border a core of bb_ncore variables whose half-bandwidth
+    // bb_bcore becomes band_b; band_np is then bb_ncore rounded up to 4.  bb_over / bb_max: a border of bb_over > bb_max columns was seen and
+    // not adopted (setup's message).  C, the forward results and Z = B^-1 C: band_np x bb_c; D, S and its factor: BC_MAX x BC_MAX; t: BC_MAX.
+    int bb_c = 0, bb_ncore = 0, bb_bcore = 0, bb_over = 0, bb_max = 0;
+    double *bb_C = nullptr, *bb_T = nullptr, *bb_Z = nullptr, *bb_D = nullptr, *bb_S = nullptr, *bb_SL = nullptr, *bb_t = nullptr;
     // half-bandwidths BAND_MAX_B + 1 .. BAND_WIDE_MAX_B (dev/band_wide.inc): order padded to 64, w = (b + 63) / 64; the band as 64 x 64 tiles
     // (w + 1 per block column), the diagonal tiles while they are being updated, D, the diagonal blocks' inverses and their transposes
     int bw_w = 0; double *bw_Wb = nullptr, *bw_Wdiag = nullptr, *bw_Wd = nullptr, *bw_Li = nullptr, *bw_LiT = nullptr;

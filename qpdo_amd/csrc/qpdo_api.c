@@ -44,6 +44,7 @@ struct QPDOBackend {
     c_float *q_raw, *l_raw, *u_raw;
     int q_stype; int64_t q_nnz, a_nnz;
     QPDOAmdBandOrderInfo band_order;      /* what qpdo_setup decided about the band solver's variable order (band_order_setup) */
+    QPDOAmdBandBorderInfo band_border;    /* ... and about a border of coupling variables (band_border_setup); border_solves is read from the device */
     int solved_last;              /* the most recent state-changing call was qpdo_solve (set there; cleared by qpdo_warm_start, qpdo_update_q,
                                    * qpdo_update_bounds, qpdo_amd_update_matrices): what qpdo_amd_adjoint asks before it reads the solution */
 };
@@ -318,6 +319,37 @@ static int pick_device(int *device) {
     return 1;
 }
 
+/* QPDO_BAND_BORDER=<C> (contract: qpdo_amd_ext.h): a border of trailing coupling variables over a band core, between the creation of the
+ * device backend and band_order_setup / qdev_configure.  The detection is band_border.c's; the rule that adopts a border -- 1 <= c <= C and
+ * a core that the band solver's selection rule takes on (n_core, b_core) -- is applied here, and qdev_configure finds the decision made.
+ * Variable unset or 0: nothing is computed.  Returns 0, or -1 with the message printed. */
+static int band_border_setup(QPDOWorkspace *work, const cholmod_sparse *Q, const cholmod_sparse *A, const QdevDist *dd) {
+    QPDOAmdBandBorderInfo *bb = &work->chol->band_border;
+    memset(bb, 0, sizeof(*bb));
+    const int C = env_int("QPDO_BAND_BORDER", 0);
+    if (C <= 0) return 0;
+    bb->max_border = C > 64 ? 64 : C;
+    const int ls = linsolve_mode_env();
+    if (dd->world > 1 || dd->force) bb->reason = BAND_BORDER_REASON_PARTITIONED;
+    else if (env_int("QPDO_BAND_COUPLING", 0) > 0) bb->reason = BAND_BORDER_REASON_COUPLING;
+    else if (small_route_wanted(work->data->n, work->data->m)) bb->reason = BAND_BORDER_REASON_FUSED;
+    else if (ls == 0 || ls == 1) bb->reason = BAND_BORDER_REASON_LINSOLVE;
+    if (bb->reason) return 0;
+    long info[4];
+    if (qpdo_amd_band_border(Q, A, bb->max_border, info)) { QPDO_EPRINT("band border: the detection failed (out of memory)"); return -1; }
+    bb->n_core = info[0]; bb->b_core = info[2];
+    const long c = info[1];
+    if (c == 0) return 0;                                                   /* a plain band, or no band at all: as without the variable */
+    const int worth = ls == 3 ? bb->n_core >= 4 * (bb->b_core + 1) : (bb->b_core <= 127 && bb->n_core >= 2048);
+    if (c > bb->max_border) { bb->over = c; bb->reason = BAND_BORDER_REASON_OVER; }
+    else if (!worth) { bb->over = c; bb->reason = BAND_BORDER_REASON_CORE; }
+    else bb->border = c;
+    if (qdev_set_band_border(work->chol->dev, (int)bb->max_border, (int)bb->n_core, (int)bb->border, (int)bb->b_core, c > bb->max_border ? (int)c : 0)) {
+        QPDO_EPRINT("device backend: %s", qdev_last_error()); return -1;
+    }
+    return 0;
+}
+
 /* The band solver's variable order for this workspace (band_order.h; contract: qpdo_amd_ext.h), between the creation of the device
  * backend and qdev_configure, whose band detection and selection rule then run on the adopted order.  Nothing configured: nothing is
  * computed, allocated or launched.  Returns 0, or -1 with the message printed. */
@@ -333,7 +365,8 @@ static int band_order_setup(QPDOWorkspace *work, const cholmod_sparse *Q, const 
     bo->mode = mode;
     if (mode == QPDO_AMD_BAND_ORDER_NATURAL) return 0;
     const int ls = linsolve_mode_env();
-    if (dd->world > 1 || dd->force) bo->reason = BAND_ORDER_REASON_PARTITIONED;
+    if (work->chol->band_border.border > 0) bo->reason = BAND_ORDER_REASON_BORDER;
+    else if (dd->world > 1 || dd->force) bo->reason = BAND_ORDER_REASON_PARTITIONED;
     else if (env_int("QPDO_BAND_COUPLING", 0) > 0) bo->reason = BAND_ORDER_REASON_COUPLING;
     else if (small_route_wanted((size_t)n, work->data->m)) bo->reason = BAND_ORDER_REASON_FUSED;
     else if (ls == 0 || ls == 1) bo->reason = BAND_ORDER_REASON_LINSOLVE;
@@ -491,6 +524,7 @@ QPDOWorkspace *qpdo_setup(const QPDOData *data, const QPDOSettings *settings) {
         if (prof) { fprintf(stderr, "[setup] host free         %.3f s\n", wall_now() - t0); }
         if (rc) goto fail_dev;
     }
+    if (band_border_setup(work, Q, A, &dd)) goto fail;
     if (band_order_setup(work, Q, A, &dd)) goto fail;
     if (qdev_configure(work->chol->dev, linsolve_mode_env(), env_double("QPDO_PCG_TOL", 0.0), env_int("QPDO_PCG_MAXIT", 0))) goto fail_dev;
     const int scaled = apply_scaling(work, 1, prof);
@@ -987,6 +1021,14 @@ int qpdo_amd_get_band_order(const QPDOWorkspace *work, QPDOAmdBandOrderInfo *out
         for (size_t k = 0; k < n; k++) newold[k] = no[k];
         free(no);
     }
+    return 0;
+}
+int qpdo_amd_get_band_border(const QPDOWorkspace *work, QPDOAmdBandBorderInfo *out) {
+    if (!work || !work->chol || !work->chol->dev || !out) return -1;
+    QdevStats st;
+    qdev_get_stats(work->chol->dev, &st);
+    *out = work->chol->band_border;
+    out->border_solves = (long)st.border_solves;
     return 0;
 }
 int qpdo_amd_download_factor(QPDOWorkspace *work, int which, double *dst, long count) {

@@ -86,6 +86,7 @@ typedef struct {
     int64_t inner_x32_steps;            /* inner_steps whose two products staged the fp32 copies of their operands (pair-wide products, coarse ones included) */
     int64_t inner_h16_steps;            /* inner_steps of coarse sweeps: both products streamed the half-precision images */
     int64_t inner_h16_sweeps;           /* coarse sweeps among inner_refine_sweeps */
+    int64_t border_solves;              /* QPDO_BAND_BORDER: band solves by block elimination over the border variables (qpdo_amd_get_band_border) */
 } QdevStats;
 
 int qdev_device_count(void);
@@ -193,6 +194,11 @@ int qdev_upload_vec(QpdoDev *d, int which, const double *src);
  * noted, for qdev_configure's "not banded" message.  qdev_band_order_newold: the adopted order back (returns -1 with a message when none). */
 int qdev_set_band_order(QpdoDev *d, const int32_t *newold, int b_natural, int b_ordered);
 int qdev_band_order_newold(QpdoDev *d, int32_t *newold);
+/* Before qdev_configure.  border > 0: the trailing `border` variables (<= 64) are a border over a band core of n_core = n - border variables
+ * with half-bandwidth b_core (3 .. 127), and qdev_configure selects the band solver in its bordered mode (the caller has applied the
+ * selection rule to the core); border = 0 with over > 0: a border of `over` > max_border columns was seen and not adopted, noted for
+ * qdev_configure's "not banded" message. */
+int qdev_set_band_border(QpdoDev *d, int max_border, int n_core, int border, int b_core, int over);
 int qdev_configure(QpdoDev *d, int linsolve /*0 pcg,1 dense,-1 auto*/, double pcg_tol, int pcg_maxit);
 /* the linear solves stop at pcg_tol relative OR at 1e-5 eps_abs in the reference's unscaled inf-norm of the dual residual */
 int qdev_set_eps_abs(QpdoDev *d, double eps_abs);

@@ -116,6 +116,43 @@ def banded_random_qp(seed, n, bw, n_win=None, win=None):
     return dict(n=n, m=m, Q=Q, Qstype=-1, A=A, q=q, l=l, u=u, c=0.0, seed=int(seed))
 
 
+def bordered_banded_qp(seed, n_core, bw, c, share=0.5, q_links=2, cost=0.5):
+    """banded_random_qp(seed, n_core, bw) with c trailing BORDER variables eps_0 .. eps_{c-1} (a bordered band: QPDO_BAND_BORDER).  Each
+    enters a `share` of the core's window rows like a slack, a.x - g eps in [l, u] with g in 0.5 .. 1.5, and -- so that every one of them
+    meets a row that starts 128 or more columns before it, whatever the seed -- the box row of x_0 (n_core >= 128).  Each has a row
+    0 <= eps of its own behind the core's rows, a diagonal of Q in 1 .. 2 and q_links entries of Q into random core variables (their
+    magnitudes are added to the core's diagonal: Q stays diagonally dominant).  Linear costs: -cost for even k, which pulls eps off its
+    bound, +cost for odd k, which tends to pin it there."""
+    core = banded_random_qp(seed, n_core, bw)
+    assert n_core >= 128 and c >= 1
+    rng = np.random.default_rng(seed + 104729)
+    n, m0 = n_core + c, core["m"]
+    A0 = sp.coo_matrix(core["A"])
+    win_rows = np.arange(n_core, m0)
+    rr, cc, vv = [A0.row], [A0.col], [A0.data]
+    Qc = sp.coo_matrix(sp.tril(core["Q"]))
+    qr, qc, qv = [Qc.row], [Qc.col], [Qc.data]
+    dq = np.zeros(n_core)
+    for k in range(c):
+        rows = np.concatenate([[0], win_rows[rng.random(len(win_rows)) < share], [m0 + k]])
+        g = -(0.5 + rng.random(len(rows)))
+        g[-1] = 1.0
+        rr.append(rows); cc.append(np.full(len(rows), n_core + k)); vv.append(g)
+        links = rng.choice(n_core, size=q_links, replace=False) if q_links else np.zeros(0, dtype=np.int64)
+        lv = 0.04 * (rng.random(len(links)) - 0.5)
+        dq[links] += np.abs(lv)
+        qr.append(np.concatenate([np.full(len(links), n_core + k), [n_core + k]])); qc.append(np.concatenate([links, [n_core + k]]))
+        qv.append(np.concatenate([lv, [1.0 + rng.random()]]))
+    qr.append(np.arange(n_core)); qc.append(np.arange(n_core)); qv.append(dq)
+    A = sp.csc_matrix((np.concatenate(vv), (np.concatenate(rr), np.concatenate(cc))), shape=(m0 + c, n))
+    Q = sp.csc_matrix((np.concatenate(qv), (np.concatenate(qr), np.concatenate(qc))), shape=(n, n))      # lower triangle (duplicates summed)
+    A.sort_indices(); Q.sort_indices()
+    q = np.concatenate([core["q"], np.where(np.arange(c) % 2 == 0, -cost, cost)])
+    l = np.concatenate([core["l"], np.zeros(c)])
+    u = np.concatenate([core["u"], np.full(c, 1e20)])
+    return dict(n=n, m=m0 + c, Q=Q, Qstype=-1, A=A, q=q, l=l, u=u, c=0.0, seed=int(seed), n_core=n_core, border=c)
+
+
 def config_qp(name, index=0):
     cfg = CONFIGS[name]
     seed = BASE_SEED + 1000 * (list(CONFIGS).index(name) + 1) + index

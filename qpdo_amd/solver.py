@@ -126,7 +126,8 @@ EXT_SYMBOLS = ["qpdo_amd_dist_config", "qpdo_amd_dist_unique_id", "qpdo_amd_solv
                "qpdo_amd_fleet_adjoint_multi_dev", "qpdo_amd_fleet_tangent_dev", "qpdo_amd_fleet_rhs_group", "qpdo_amd_fleet_get_sensitivity_stats",
                "qpdo_amd_adjoint", "qpdo_amd_get_adjoint_stats", "qpdo_amd_tangent", "qpdo_amd_get_tangent_stats",
                "qpdo_amd_rhs_group", "qpdo_amd_get_group_stats", "qpdo_amd_spmv_group",
-               "qpdo_amd_band_order", "qpdo_amd_band_order_config", "qpdo_amd_get_band_order"]
+               "qpdo_amd_band_order", "qpdo_amd_band_order_config", "qpdo_amd_get_band_order",
+               "qpdo_amd_band_border", "qpdo_amd_get_band_border"]
 
 
 class BandOrderInfo(C.Structure):
@@ -137,7 +138,17 @@ class BandOrderInfo(C.Structure):
 
 BAND_ORDER_ENV, BAND_ORDER_NATURAL, BAND_ORDER_RCM, BAND_ORDER_GIVEN = 0, 1, 2, 3      # QPDO_AMD_BAND_ORDER_*
 BAND_ORDER_REASONS = {0: "", 1: "reverse Cuthill-McKee found no narrower order", 2: "row-partitioned workspace", 3: "QPDO_BAND_COUPLING is set",
-                      4: "fused small-problem route", 5: "QPDO_LINSOLVE is dense or pcg"}
+                      4: "fused small-problem route", 5: "QPDO_LINSOLVE is dense or pcg", 6: "the workspace adopted a border of coupling variables"}
+
+
+class BandBorderInfo(C.Structure):
+    """QPDOAmdBandBorderInfo (include/qpdo_amd_ext.h)"""
+    _fields_ = [("max_border", C.c_long), ("border", C.c_long), ("n_core", C.c_long), ("b_core", C.c_long), ("over", C.c_long), ("reason", C.c_long),
+                ("border_solves", C.c_long)]
+
+
+BAND_BORDER_REASONS = {0: "", 1: "more border variables than QPDO_BAND_BORDER accepts", 2: "row-partitioned workspace", 3: "QPDO_BAND_COUPLING is set",
+                       4: "fused small-problem route", 5: "QPDO_LINSOLVE is dense or pcg", 6: "the core is too short for the band solver"}
 
 
 class AdjointStats(C.Structure):
@@ -256,6 +267,11 @@ def lib():
             L.qpdo_amd_band_order_config.restype = C.c_int
             L.qpdo_amd_get_band_order.argtypes = [W, C.POINTER(BandOrderInfo), lp_]
             L.qpdo_amd_get_band_order.restype = C.c_int
+        if hasattr(L, "qpdo_amd_band_border"):
+            L.qpdo_amd_band_border.argtypes = [C.POINTER(CholmodSparse), C.POINTER(CholmodSparse), C.c_long, C.POINTER(C.c_long)]
+            L.qpdo_amd_band_border.restype = C.c_int
+            L.qpdo_amd_get_band_border.argtypes = [W, C.POINTER(BandBorderInfo)]
+            L.qpdo_amd_get_band_border.restype = C.c_int
         if hasattr(L, "qpdo_amd_rhs_group"):
             L.qpdo_amd_rhs_group.argtypes = [W]
             L.qpdo_amd_rhs_group.restype = C.c_int
@@ -948,6 +964,19 @@ class QPDO:
             if lib().qpdo_amd_download_factor(self._w, which, _as_dp(out), count):
                 raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
             return out[:count].astype(np.int64) if name == "coupled_rows" else out[:count].reshape(geo["k"], geo["np"]).T
+        if name in ("border_geometry", "border_C", "border_Z"):
+            # band solver with border variables (QPDO_BAND_BORDER): dict(n_core, c, b_core, np); C = K[:n_core, n_core:] and Z = B^-1 C as np x c
+            g = np.zeros(4)
+            if lib().qpdo_amd_download_factor(self._w, 13, _as_dp(g), 4):
+                raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+            geo = dict(n_core=int(g[0]), c=int(g[1]), b_core=int(g[2]), np=int(g[3]))
+            if name == "border_geometry":
+                return geo
+            count = geo["np"] * geo["c"]
+            out = np.zeros(max(count, 1))
+            if lib().qpdo_amd_download_factor(self._w, 14 if name == "border_C" else 15, _as_dp(out), count):
+                raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+            return out[:count].reshape(geo["c"], geo["np"]).T
         if name == "perm":
             # the band solver's variable order (band_order_config): newold, n integers; Kb / Lt / Wb / Wd are then in that order
             out = np.zeros(max(self.n, 1))
@@ -982,6 +1011,16 @@ class QPDO:
         out = {f: getattr(info, f) for f, _ in BandOrderInfo._fields_}
         out["reason_text"] = BAND_ORDER_REASONS.get(int(info.reason), "")
         out["newold"] = newold[:self.n].astype(np.int64) if info.adopted else None
+        return out
+
+    def band_border(self):
+        """what setup decided about a border of coupling variables (QPDOAmdBandBorderInfo, QPDO_BAND_BORDER): max_border, border (the adopted
+        c), n_core, b_core, over (a c that was seen and not adopted), reason (+ reason_text), border_solves"""
+        info = BandBorderInfo()
+        if lib().qpdo_amd_get_band_border(self._w, C.byref(info)):
+            raise RuntimeError((lib().qpdo_amd_last_error() or b"").decode())
+        out = {f: int(getattr(info, f)) for f, _ in BandBorderInfo._fields_}
+        out["reason_text"] = BAND_BORDER_REASONS.get(out["reason"], "")
         return out
 
     def download(self, name):
@@ -1732,6 +1771,22 @@ def band_order(Q, A, Qstype=-1):
     if lib().qpdo_amd_band_order(C.byref(qv), C.byref(av), newold.ctypes.data_as(lp_), info.ctypes.data_as(lp_)):
         raise RuntimeError("qpdo_amd_band_order failed")
     return newold[:n].astype(np.int64), dict(b_natural=int(info[0]), b_ordered=int(info[1]), components=int(info[2]), early_out=int(info[3]))
+
+
+def band_border(Q, A, max_border=64, Qstype=-1):
+    """The detection of a border of coupling variables over a band core (qpdo_amd_band_border; host only, no device): dict(n_core, c,
+    b_core, reason) -- the trailing c = n - n_core variables reach beyond half-bandwidth 127, the rest has half-bandwidth b_core; reason 1
+    when c > max_border.  Q as setup takes it (band_order above).  The border variables are the trailing ones: number shared variables
+    last (problems.permute_variables)."""
+    keep = []
+    Q = sp.csc_matrix(Q)
+    n = Q.shape[0]
+    A = sp.csc_matrix((0, n)) if A is None else sp.csc_matrix(A)
+    qv, av = _sparse_view(Q, int(Qstype), keep), _sparse_view(A, 0, keep)
+    info = np.zeros(4, dtype=np.int64 if C.sizeof(C.c_long) == 8 else np.int32)
+    if lib().qpdo_amd_band_border(C.byref(qv), C.byref(av), int(max_border), info.ctypes.data_as(C.POINTER(C.c_long))):
+        raise RuntimeError("qpdo_amd_band_border failed")
+    return dict(n_core=int(info[0]), c=int(info[1]), b_core=int(info[2]), reason=int(info[3]))
 
 
 def dist_config(rank, world, mode="rccl", group=None, force=False):
